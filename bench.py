@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MSamples/s of signal_packer compress on MI355X (default: xdelta_hzr, 64ch x 65536 x int32).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c5] [--packer ...]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c5] [--packer ...] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (rspt_hip_compress_batch_dev) over one batch of
 synthetic blocks per GPU, inputs already resident in HBM.  Two distinct batches alternate in
@@ -64,7 +64,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of the produced streams")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32 / float64; "
+                         "larger outputs as a fixed, seeded sample; rank 0's only): two builds run with the same arguments compare output for output")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.workload == "c5":
         a.nch = a.nch or 12
         a.ns = a.ns or 8192
@@ -258,6 +263,8 @@ def bench_prefilter(args):
         pk.iir_prefilter_batch(work, IIR_N, IIR_D, IIR_INIT, per_channel=per_channel)  # (in place: every step filters the previous step's output)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"filtered": (work, pk.block_bytes, None)})
     ms = dt / args.steps * 1e3
     nc = len(IIR_N)
     # instructions the wave that holds a channel's filter state cannot hand to anyone else: per sample the NC - 1 feedback products and
@@ -281,6 +288,47 @@ def bench_prefilter(args):
     print(json.dumps(res), flush=True)
     pk.close()
     return 0 if verified is not False else 3
+
+
+DUMP_BUDGET = 64 << 20  # bytes --dump-outputs may write in all
+DUMP_SAMPLE = 1 << 22  # byte positions of a sampled output (a float32 value and a float64 position each: 48 MiB)
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: the arrays the timed path handed its caller in its last timed step, as DIR/<name>.npy.  The inputs are the
+    same bytes in every run with the same arguments, so two builds compare output for output.
+    outputs: name -> 1-D integer device tensor (written whole, float64), or name -> (rows x row-stride uint8 device tensor, width,
+    valid): the bytes at offsets < width of every row (width depends on the arguments only, never on the build), past valid[row]
+    (None: all valid) not an output.  Those go out at DUMP_SAMPLE fixed positions (all of them when there are no more):
+    DIR/<name>.npy the byte values as float32, -1 where a position lies past its row's valid bytes, DIR/<name>_index.npy the flat
+    positions row * width + offset as float64 (drawn by numpy RandomState(0), sorted)."""
+    import numpy as np
+    import torch
+
+    files = {}
+    for name, v in outputs.items():
+        if not isinstance(v, tuple):
+            files[name] = v.cpu().numpy().astype(np.float64)
+            continue
+        t, width, valid = v
+        rows = t.shape[0]
+        assert 0 < width <= t.shape[1]
+        if rows * width <= DUMP_SAMPLE:
+            pos = np.arange(rows * width, dtype=np.int64)
+        else:
+            pos = np.unique(np.random.RandomState(0).randint(0, rows * width, DUMP_SAMPLE, dtype=np.int64))
+        row, off = pos // width, pos % width
+        vals = t[torch.from_numpy(row).to(t.device), torch.from_numpy(off).to(t.device)].cpu().numpy().astype(np.float32)
+        if valid is not None:
+            vals[off >= valid.cpu().numpy()[row]] = -1
+        files[name] = vals
+        files[name + "_index"] = pos.astype(np.float64)
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_BUDGET, "--dump-outputs: %d bytes over the %d-byte budget" % (total, DUMP_BUDGET)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    sys.stderr.write("bench.py: %s written to %s (%d bytes)\n" % (", ".join(sorted(files)), out_dir, total))
 
 
 def kernels_sha():
@@ -472,6 +520,14 @@ def main():
         one_step(i)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the buffers of the last timed step, before anything below runs on them again (streams sampled within the block's size;
+        # the rare stream longer than its block has its full length in sizes)
+        n = nstep[0] - 1
+        if decomp:
+            dump_outputs(args.dump_outputs, {"decoded": (d_back[n % S], pk.block_bytes, None), "used": d_used[n % S]})
+        else:
+            dump_outputs(args.dump_outputs, {"streams": (d_dst[n % nbuf], pk.block_bytes, d_sizes[n % nbuf]), "sizes": d_sizes[n % nbuf]})
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

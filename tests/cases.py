@@ -3,6 +3,7 @@
 Everything here is integer arithmetic (or the repo's shipped data files), so the
 same bytes come out on every box.
 """
+import hashlib
 import os
 import sys
 
@@ -272,3 +273,112 @@ def iir_big_case():
 
 def iir_big_data(c):
     return synth.synth_native(c["nch"], c["ns"], c["block"], bps=c["bps"], ecg=True).numpy()
+
+
+# ---- inputs of the tests that pin the restatement to the compiled reference (tests/golden/ref_record.json) ----
+
+def digest(b):
+    """what ref_record.json holds of an output: the first 32 hex digits of its sha256"""
+    return hashlib.sha256(np.ascontiguousarray(b).tobytes() if isinstance(b, np.ndarray) else bytes(b)).hexdigest()[:32]
+
+
+def hzr_soup_block(seed):
+    """hzr-oriented byte soup: alphabet size, zero density and run structure vary."""
+    r = np.random.RandomState(seed)
+    n = int(r.choice([1, 2, 3, 17, 255, 256, 1000, 4096, 65535, 65536, 65537, 70000, 140000]))
+    kind = seed % 6
+    if kind == 0:
+        a = r.randint(0, 256, n)
+    elif kind == 1:
+        a = r.randint(0, r.randint(2, 9), n)  # tie-heavy small alphabets
+    elif kind == 2:
+        a = np.minimum(r.geometric(0.3, n), 255)  # deep trees
+    elif kind == 3:
+        a = np.where(r.rand(n) < r.choice([0.5, 0.9, 0.99, 0.999]), 0, r.randint(1, 256, n))
+    elif kind == 4:
+        a = np.zeros(n, dtype=np.int64)
+        for _ in range(r.randint(1, 12)):
+            a[r.randint(0, n)] = r.randint(1, 4)
+    else:
+        a = np.full(n, r.randint(0, 256))
+        if n > 4 and r.rand() < 0.5:
+            a[r.randint(0, n)] ^= 1
+    return a.astype(np.uint8)
+
+
+HZR_SOUP_SEEDS = 320
+PAYLOAD_BOUNDARY_SIZES = (16, 24, 32, 48, 64, 96, 128)
+PAYLOAD_BOUNDARY_SEEDS = 300
+
+
+def payload_boundary_block(n, seed):
+    r = np.random.RandomState(10000 + seed)
+    return r.randint(0, r.randint(2, 40), n).astype(np.uint8)
+
+
+RANDOM_PACKER_SEEDS = 60
+
+
+def random_packer_case(seed):
+    r = np.random.RandomState(seed)
+    kind = ["xdelta_hzr", "hzr", "hadamard", "dct"][seed % 4]
+    bps = int(r.randint(1, 5))
+    nch = int(r.randint(1, 6))
+    if kind == "hadamard":
+        ns = 1 << int(r.randint(1, 11))
+    elif kind == "dct":
+        ns = int(r.randint(2, 130))
+    else:
+        ns = int(r.randint(1, 3000))
+    nb = int(r.randint(1, 5))
+    amp = int(r.choice([3, 100, 3000, 1 << 15, 1 << 22, 1 << 30]))
+    data = _rand_native(nch, ns, bps, 500 + seed, amp, walk=bool(r.randint(0, 2)))
+    return dict(kind=kind, bps=bps, nch=nch, ns=ns, nb=nb, amp=amp, data=data)
+
+
+NEEDED_NB_SEEDS = 150
+
+
+def needed_nb_case(seed):
+    r = np.random.RandomState(7000 + seed)
+    bps, nch, ns = int(r.randint(1, 5)), int(r.randint(1, 5)), int(r.randint(1, 200))
+    nb0 = int(r.randint(1, 5))
+    amp = int(r.choice([2, 60, 130, 3000, 40000, 1 << 23, 1 << 30]))
+    data = _rand_native(nch, ns, bps, 900 + seed, amp, walk=bool(seed & 1))
+    return dict(bps=bps, nch=nch, ns=ns, nb=nb0, amp=amp, data=data)
+
+
+BIG_ENDIAN_SHAPE = (3, 257)  # nch, ns
+
+
+def big_endian_block(bps):
+    nch, ns = BIG_ENDIAN_SHAPE
+    return _rand_native(nch, ns, bps, 700 + bps, 1 << (8 * bps - 2))
+
+
+def reverse_samples(native, bps):
+    return np.ascontiguousarray(native.reshape(-1, bps)[:, ::-1]).reshape(-1)
+
+
+DCT_VS_FP64_SHAPES = [(4, 3, 256, False), (4, 2, 1000, True), (3, 4, 2048, True), (4, 2, 4096, True)]  # bps, nch, ns, ecg
+
+
+def dct_vs_fp64_data(bps, nch, ns, ecg):
+    return synth.synth_native(nch, ns, block_index=5, bps=bps, ecg=ecg).numpy().reshape(-1)
+
+
+DCT_OUT_OF_RANGE_SHAPES = [(4, 8, 2048, 1 << 29), (3, 4, 2048, 1 << 21), (4, 1, 3000, 1 << 29), (4, 3, 257, (1 << 31) - 1)]  # bps, nch, ns, amp
+DCT_OUT_OF_RANGE_SEEDS = 3
+
+
+def dct_out_of_range_data(bps, nch, ns, amp, seed):
+    return _rand_native(nch, ns, bps, 9100 + seed, amp, walk=bool(seed & 1))
+
+
+IIR_FULL_SCALE_SHAPE = (5, 5000, 4)  # nch, ns, bps
+IIR_FULL_SCALE_COEFS = {"bandpass": IIR_BANDPASS, "highpass": IIR_HIGHPASS}
+
+
+def iir_full_scale_data():
+    nch, ns, bps = IIR_FULL_SCALE_SHAPE
+    return _rand_native(nch, ns, bps, 424242, (1 << 31) - 1, walk=False)

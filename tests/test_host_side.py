@@ -3,6 +3,7 @@ page-locked staging buffers for the host-pointer API, and the C++ factories' dev
 import os
 import subprocess
 import sys
+import zlib
 
 import numpy as np
 import pytest
@@ -12,22 +13,21 @@ import cases
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _reverse_samples(native, bps):
-    return np.ascontiguousarray(native.reshape(-1, bps)[:, ::-1]).reshape(-1)
-
-
 @pytest.mark.parametrize("bps", [1, 2, 3, 4])
-def test_reference_big_endian_ingest_is_a_byte_reversal(ref, bps):
+def test_reference_big_endian_ingest_is_a_byte_reversal(orc, ref_record, bps):
     """convert_native_to_i32(reverse_byte_order=true) of the byte-reversed block == the little-endian conversion
-    (utils.cpp:127-137,145-154,162-170,178-184): what the GPU's big-endian mode relies on -- pinned by the REAL reference"""
-    nch, ns = 3, 257
-    le = cases._rand_native(nch, ns, bps, 700 + bps, 1 << (8 * bps - 2))
-    be = _reverse_samples(le, bps)
-    a = ref.native_to_i32(le, ns, nch, bps, reverse_byte_order=False)
-    b = ref.native_to_i32(be, ns, nch, bps, reverse_byte_order=True)
-    assert (a == b).all()
+    (utils.cpp:127-137,145-154,162-170,178-184): what the GPU's big-endian mode relies on -- pinned by the REAL reference
+    (its answers recorded in tests/golden/ref_record.json)"""
+    nch, ns = cases.BIG_ENDIAN_SHAPE
+    le = cases.big_endian_block(bps)
+    be = cases.reverse_samples(le, bps)
+    rec = ref_record["big_endian"][str(bps)]
+    assert zlib.crc32(le.tobytes()) == rec["in_crc32"], "test input drifted"
+    a = orc.native_to_i32(le, ns, nch, bps)  # the little-endian conversion ...
+    assert cases.digest(a) == rec["le_i32"]  # ... as the reference makes it
+    assert cases.digest(a) == rec["be_i32"]  # the reference's reverse_byte_order ingest of the byte-reversed block
     if bps > 1:  # (the reference's 1-byte reverse branch of convert_i32_to_native writes at offset +1: utils.cpp:116-118)
-        assert ref.i32_to_native(a, bps, reverse_byte_order=True) == be.tobytes()
+        assert cases.digest(be) == rec["be_native"]
 
 
 def test_cxx_shard_example_compiles(tmp_path):
@@ -56,7 +56,7 @@ def test_big_endian_feed(api, orc, golden, packer_cases, name):
     import torch
 
     c, g = packer_cases[name], golden["packers"][name]
-    be = _reverse_samples(c["data"], c["bps"])
+    be = cases.reverse_samples(c["data"], c["bps"])
     pk = api.SignalPacker(c["kind"], c["bps"], c["nch"], c["ns"], c["nb"])
     pk.set_byte_order(big_endian=True)
     got = pk.compress(be)

@@ -5,18 +5,22 @@ import zlib
 import numpy as np
 import pytest
 
-from rspt_amd import synth
+import cases
 
 PRDN_TOL = 0.05
 CR_TOL = 0.01
 
 
-@pytest.mark.parametrize("bps,nch,ns,ecg", [(4, 3, 256, False), (4, 2, 1000, True), (3, 4, 2048, True), (4, 2, 4096, True)])
-def test_fp64_restatement_vs_reference(orc, ref, bps, nch, ns, ecg):
-    data = synth.synth_native(nch, ns, block_index=5, bps=bps, ecg=ecg).numpy().reshape(-1)
-    pr = ref.packer("dct", bps, nch, ns)
-    s_ref = pr.compress(data)
-    d_ref, _, _ = pr.decompress(s_ref)
+@pytest.mark.parametrize("bps,nch,ns,ecg", cases.DCT_VS_FP64_SHAPES)
+def test_fp64_restatement_vs_reference(orc, ref_record, bps, nch, ns, ecg):
+    data = cases.dct_vs_fp64_data(bps, nch, ns, ecg)
+    rec = ref_record["dct_vs_fp64"]["%d_%d_%d" % (bps, nch, ns)]
+    assert zlib.crc32(data.tobytes()) == rec["in_crc32"], "test input drifted"
+    s_ref = bytes.fromhex(rec["stream"])  # the reference's stream (tests/golden/ref_record.json)
+    pt = orc.packer("dct", bps, nch, ns)
+    d_ref, used_ref, _ = pt.decompress(s_ref)  # decoded by the table restatement, which decodes it as the reference does:
+    pt.close()
+    assert used_ref == len(s_ref) and cases.digest(d_ref) == rec["decoded"]
     s_big, _ = orc.dct_big_compress(data, bps, nch, ns)
     d_big, used = orc.dct_big_decompress(s_big, bps, nch, ns)
     assert used == len(s_big)

@@ -118,26 +118,32 @@ def test_hadamard_beyond_65536_points_golden(orc, golden, name):
     pk.close()
 
 
-@pytest.mark.parametrize("bps,nch,ns,amp", [(4, 8, 2048, 1 << 29), (3, 4, 2048, 1 << 21), (4, 1, 3000, 1 << 29), (4, 3, 257, (1 << 31) - 1)])
-def test_dct_beyond_its_range_restatement_equals_the_reference(orc, ref, bps, nch, ns, amp):
+@pytest.mark.parametrize("bps,nch,ns,amp", cases.DCT_OUT_OF_RANGE_SHAPES)
+def test_dct_beyond_its_range_restatement_equals_the_reference(orc, ref_record, bps, nch, ns, amp):
     """Out of the dct packer's range the decoded doubles overflow int32 and `(int)x` (signal_packer_dct.cpp:98) is whatever the
-    build makes of it: the reference compiled here (oracle/_ref, x86-64: 0x80000000) is the authority, the restatement follows
-    it -- and the GPU path follows the restatement (tests/test_gpu_lossy_and_decode.py, same shapes)."""
-    for seed in range(3):
-        x = cases._rand_native(nch, ns, bps, 9100 + seed, amp, walk=bool(seed & 1))
-        po, pr = orc.packer("dct", bps, nch, ns), ref.packer("dct", bps, nch, ns)
+    build makes of it: the reference compiled by oracle/Makefile (x86-64: 0x80000000; its answers in tests/golden/ref_record.json)
+    is the authority, the restatement follows it -- and the GPU path follows the restatement (tests/test_gpu_lossy_and_decode.py,
+    same shapes)."""
+    rec = ref_record["dct_out_of_range"]["%d_%d_%d_%d" % (bps, nch, ns, amp)]
+    for seed in range(cases.DCT_OUT_OF_RANGE_SEEDS):
+        x = cases.dct_out_of_range_data(bps, nch, ns, amp, seed)
+        in_crc32, stream_want, decoded_want = rec[seed]
+        assert zlib.crc32(x.tobytes()) == in_crc32, "test input drifted (seed %d)" % seed
+        po = orc.packer("dct", bps, nch, ns)
         s = po.compress(x)
-        assert s == pr.compress(x)
-        assert po.decompress(s)[0] == pr.decompress(s)[0]
+        assert cases.digest(s) == stream_want
+        assert cases.digest(po.decompress(s)[0]) == decoded_want
 
 
-def test_iir_at_full_scale_restatement_equals_the_reference(orc, ref):
+def test_iir_at_full_scale_restatement_equals_the_reference(orc, ref_record):
     """the band-pass overshoots past 2^31 on full-scale int32 input: the truncated double is the reference build's (rspt_test.cpp:130)"""
-    nch, ns, bps = 5, 5000, 4
-    data = cases._rand_native(nch, ns, bps, 424242, (1 << 31) - 1, walk=False)
-    for coef in (cases.IIR_BANDPASS, cases.IIR_HIGHPASS):
+    nch, ns, bps = cases.IIR_FULL_SCALE_SHAPE
+    data = cases.iir_full_scale_data()
+    rec = ref_record["iir_full_scale"]
+    assert zlib.crc32(data.tobytes()) == rec["in_crc32"], "test input drifted"
+    for name, coef in cases.IIR_FULL_SCALE_COEFS.items():
         a = orc.iir_prefilter(data, bps, nch, ns, coef[0], coef[1], 2000)
-        assert a == ref.iir_prefilter(data, bps, nch, ns, coef[0], coef[1], 2000)
+        assert cases.digest(a) == rec[name], name
         v = orc.native_to_i32(np.frombuffer(a, dtype=np.uint8), ns, nch, bps)
         x = orc.native_to_i32(data, ns, nch, bps)
     # (the case is only worth its name if the overflow happens)
