@@ -17,8 +17,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -105,30 +108,51 @@ const char* kStageNames[ST_COUNT] = {"preprocess", "nb_scan", "hzr_hist", "hzr_t
 
 }  // namespace
 
-struct Feed;
-struct rspt_hip_packer {
-    Geom g{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int last_hip_error = 0;
-    unsigned nb_ctor = 0;
-    unsigned nb_host = 0;  // last value of the device nb_state the host has seen (a lower bound: nb only grows)
+// ---- owners of HIP resources: move-only, each releases what it holds when destroyed or reset, and nothing when empty ----
+template <class T, auto Release>
+class Owned {
+  public:
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() {
+        if (h_) Release(h_);
+        h_ = nullptr;
+    }
+    T* out() {  // for the HIP call that creates the resource
+        reset();
+        return &h_;
+    }
+    operator T() const { return h_; }
 
-    // workspace
+  private:
+    T h_ = nullptr;
+};
+template <class T> using Dev = Owned<T*, hipFree>;          // device memory
+template <class T> using Pinned = Owned<T*, hipHostFree>;   // page-locked host memory
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+// Everything rspt_hip_reserve() sizes; replacing it releases the old workspace as a whole.
+struct Workspace {
     size_t cap_blocks = 0;
-    uint8_t* planes = nullptr;     // [cap][4][plane_stride]
-    int32_t* planar = nullptr;     // [cap][N] (transform packers, decode)
-    uint32_t* needmask = nullptr;  // [cap]
-    uint32_t* nbuse = nullptr;     // [cap]
-    uint32_t* dec_nb = nullptr;    // [cap] decode: planes of each stream (container index entry, else nb_state)
-    uint32_t* work_ctr = nullptr;  // [16] work counter of the persistent k_hist at 0, the WorkQueues of k_encode from 4 (zeroed per call)
-    uint32_t* big_list = nullptr;  // [cap*4*nblk] hzr blocks for the workgroup-per-block encoder (filled by k_layout)
-    uint32_t* small_list = nullptr;  // [cap*4*nblk] hzr blocks for the wave-per-block encoder
-    int num_cu = 256;
-    uint32_t* nzflag = nullptr;    // [cap*4*nblk] set by the front end when an hzr block holds a non-zero byte (= zbuf[set of the last call])
+    Dev<uint8_t> planes;      // [cap][4][plane_stride]
+    Dev<int32_t> planar;      // [cap][N] (transform packers, decode)
+    Dev<uint32_t> nbuse;      // [cap]
+    Dev<uint32_t> dec_nb;     // [cap] decode: planes of each stream (container index entry, else nb_state)
+    Dev<uint32_t> big_list;   // [cap*4*nblk] hzr blocks for the workgroup-per-block encoder (filled by k_layout)
+    Dev<uint32_t> small_list; // [cap*4*nblk] hzr blocks for the wave-per-block encoder
     // The per-call zero region [nzflag | needmask | work counters | row sums] exists twice: while a call works in one copy its
     // k_tree zeroes the other for the next call (one store per thread) -- the memset in front of every call was a 9 us launch.
-    uint32_t* zbuf[2] = {nullptr, nullptr};
+    Dev<uint32_t> zbuf[2];
     size_t zcap_words = 0;
     bool zero_ready[2] = {false, false};  // the copy is known to be all zero
     int zset = 0;                          // the copy the next call works in
@@ -137,29 +161,88 @@ struct rspt_hip_packer {
     // front end writes only the 128-byte lines that hold a non-zero byte into a clean block; k_layout sets the bits of
     // the blocks in which data stays behind, and the encoders wipe the non-zero granules of all others right after
     // reading them (light blocks only: block_is_wiped).
-    uint32_t* plane_dirty = nullptr;  // [cap*4][4]
-    uint32_t dirty_shift = 0;
-    bool planes_unknown = false;      // something else (decompress, a diagnostic run) wrote the planes: flag them all
-    uint32_t* nb_state = nullptr;  // [4] persistent: [0] = nb; [2] = work counter of the decoder's persistent grid (zeroed by k_dec_frame)
-    uint32_t* hist = nullptr;      // [cap*4*nblk][264]
-    uint32_t* seghist = nullptr;   // [cap*4*nblk][16][264] u16: tokens ending in each 4 KiB segment (k_hist -> k_tree)
-    uint32_t* segbase = nullptr;   // [cap*4*nblk][16] stream bit at which each segment's tokens start (k_tree -> k_encode)
-    uint32_t* lists = nullptr;     // [cap*4*nblk][16][kListCap] (position << 9 | value) entries of the sparse segments (k_hist -> k_encode)
-    uint2* listinfo = nullptr;     // [cap*4*nblk][16] {entries or kListNone, position behind the last literal before the segment}
-    uint32_t* cw = nullptr;        // [cap*4*nblk][264] code | length << 24 per symbol
-    uint32_t* tdesc = nullptr;     // [..][92]
-    BlockMeta* meta = nullptr;     // [..]
-    uint64_t* out_off = nullptr;   // [..]
-    uint8_t* means = nullptr;      // [cap][hdr_len]
-    int32_t* planar2 = nullptr;    // [cap][N] second int32 buffer (dct output / idct output)
-    uint32_t* txor = nullptr;      // [cap][ntile] decode scans
-    uint32_t* tsum = nullptr;      // [cap][ntile]
-    uint32_t* rowrec = nullptr;    // [cap][N / 256][kRowRec] row tile records of the int32 decode path (k_inv_rows)
-    uint64_t* blk_off = nullptr;   // [cap*4*nblk] decode: hzr block offsets inside each stream
-    CrcConsts* crc = nullptr;
-    // dct (signal_packer_dct.cpp:60-74): COS[x][i] and its transpose, built on the host like the reference ctor
-    float* cos_tab = nullptr;
-    float* cos_tab_t = nullptr;
+    Dev<uint32_t> plane_dirty;  // [cap*4][4]
+    bool planes_unknown = false;  // something else (decompress, a diagnostic run) wrote the planes: flag them all
+    Dev<uint32_t> hist;      // [cap*4*nblk][264]
+    Dev<uint32_t> seghist;   // [cap*4*nblk][16][264] u16: tokens ending in each 4 KiB segment (k_hist -> k_tree)
+    Dev<uint32_t> segbase;   // [cap*4*nblk][16] stream bit at which each segment's tokens start (k_tree -> k_encode)
+    Dev<uint32_t> lists;     // [cap*4*nblk][16][kListCap] (position << 9 | value) entries of the sparse segments (k_hist -> k_encode)
+    Dev<uint2> listinfo;     // [cap*4*nblk][16] {entries or kListNone, position behind the last literal before the segment}
+    Dev<uint32_t> cw;        // [cap*4*nblk][264] code | length << 24 per symbol
+    Dev<uint32_t> tdesc;     // [..][92]
+    Dev<BlockMeta> meta;     // [..]
+    Dev<uint64_t> out_off;   // [..]
+    Dev<uint8_t> means;      // [cap][hdr_len]
+    Dev<int32_t> planar2;    // [cap][N] second int32 buffer (dct output / idct output)
+    Dev<uint32_t> txor;      // [cap][ntile] decode scans
+    Dev<uint32_t> tsum;      // [cap][ntile]
+    Dev<uint32_t> rowrec;    // [cap][N / 256][kRowRec] row tile records of the int32 decode path (k_inv_rows)
+    Dev<uint64_t> blk_off;   // [cap*4*nblk] decode: hzr block offsets inside each stream
+    Dev<double2> fft_scratch;  // [fft_bpp][nch][n] (dct beyond the dense table)
+    size_t fft_bpp = 0;        // blocks per pass (bounds the scratch to ~1 GiB)
+    Dev<int32_t> mean_i32;     // [cap][nch]
+};
+
+// rspt_hip_compress / rspt_hip_decompress: one block staged on the device
+struct HostStaging {
+    Dev<uint8_t> src;
+    Dev<uint8_t> dst;
+    Dev<uint64_t> size;
+    size_t dst_cap = 0;
+};
+
+// One group of blocks in flight between the host and the device: up, compress (or decompress), down.
+struct Slot {
+    Dev<uint8_t> d_src;
+    Dev<uint8_t> d_dst;
+    Dev<uint64_t> d_sizes;
+    Pinned<uint64_t> h_sizes;  // [n] stream lengths + [1] the nb_state behind the group (the feed)
+    Event ev_up, ev_comp, ev_down;
+};
+
+// rspt_hip_compress_many / rspt_hip_decompress_many: two slots of a chunk of blocks each
+struct ManyStaging {
+    size_t chunk = 0, stride = 0;
+    Slot slot[2];
+    Dev<uint64_t> idx[2];  // [4 + 2 x chunk] a container header + index over a slot's streams (decompress_many with src_len)
+    Pinned<uint64_t> hidx;  // 2 x (4 + 2 x chunk)
+};
+
+// rspt_hip_feed_*: a ring of block groups in flight
+struct FeedSlot : Slot {
+    enum State { FREE, FILLING, COMPRESSING, DOWNLOADING, DONE } state = FREE;
+    std::vector<void*> dst_host;
+    std::vector<size_t> dst_cap;
+    size_t count = 0, delivered = 0, first_seq = 0;
+    int error = 0;  // the group's launch failed: every block of it is reported with this status
+};
+struct Feed {
+    size_t G = 0, stride = 0;
+    std::vector<FeedSlot> slots;
+    size_t head = 0, tail = 0;  // ring positions: oldest slot not yet FREE; the slot being filled / filled next
+    size_t next_seq = 0;
+};
+
+// rspt_hip_gather_post_*: two slots of sizes (device + page-locked host) and events, on a gather stream of their own
+struct LagGather {
+    Stream stream;
+    Dev<uint64_t> dtotals[2];
+    Pinned<uint64_t> htotals[2];
+    Event ev_in[2], ev_sizes[2], ev_payload[2];
+    bool posted[2] = {false, false};
+    int world = 0;
+};
+
+// The members are constructed in the order they are declared and released in the reverse order (rspt_hip_packer_destroy).
+struct rspt_hip_packer {
+    Geom g{};
+    int device = 0;
+    int last_hip_error = 0;
+    unsigned nb_ctor = 0;
+    unsigned nb_host = 0;  // last value of the device nb_state the host has seen (a lower bound: nb only grows)
+    int num_cu = 256;
+    uint32_t dirty_shift = 0;  // (Workspace::plane_dirty)
+    // dct (signal_packer_dct.cpp:60-74)
     double dct_scale0 = 0, dct_scale1 = 0, idct_scale = 0;
     float dct_cs0 = 0;
     // dct beyond the dense table: fp64 FFT path (transforms.hip: k_dctfft_*)
@@ -167,47 +250,11 @@ struct rspt_hip_packer {
     uint32_t fft_l1 = 0, fft_l2 = 0;   // n = 2^(l1+l2)
     bool dct_real = false;             // forward transform through the real-input FFT (n >= 256)
     uint32_t fftr_la = 0, fftr_lb = 0; // n/2 = 2^(la+lb)
-    double2* fft_tw = nullptr;         // [n] (cos, sin)(2 pi t / n)
-    double2* fft_post = nullptr;       // [n] (cos, sin)(pi k / 2n)
-    double2* fft_scratch = nullptr;    // [fft_bpp][nch][n]
-    size_t fft_bpp = 0;                // blocks per pass (bounds the scratch to ~1 GiB)
-    int32_t* mean_i32 = nullptr;       // [cap][nch]
-    long long* row_sum = nullptr;      // [blocks][nch] channel sums taken by the de-interleave pass (dct at large ns); lives in the per-call zero region
-    bool have_row_sum = false;         // this call's front end filled row_sum
     uint32_t ntile = 0;
     uint32_t Tn_native = 0;  // tile of k_planar_native
-
-    // host API staging
-    uint8_t* h_src = nullptr;  // device
-    uint8_t* h_dst = nullptr;  // device
-    uint64_t* h_size = nullptr;
-    size_t h_dst_cap = 0;
-    // rspt_hip_compress_many: two slots of a chunk of blocks each
-    uint8_t* m_src[2] = {nullptr, nullptr};   // device
-    uint8_t* m_dst[2] = {nullptr, nullptr};   // device
-    uint64_t* m_sizes[2] = {nullptr, nullptr};  // device
-    uint64_t* m_hsizes = nullptr;             // page-locked host, 2 x chunk
-    uint64_t* m_idx[2] = {nullptr, nullptr};  // device: [4 + 2 x chunk] a container header + index over a slot's streams (decompress_many with src_len)
-    uint64_t* m_hidx = nullptr;               // page-locked host, 2 x (4 + 2 x chunk)
-    struct Feed* feed = nullptr;              // rspt_hip_feed_*: a ring of block groups in flight
-    uint64_t* gat_totals = nullptr;           // device [gat_world]: container lengths of all ranks (rspt_hip_gather_containers)
-    int gat_world = 0;
-    // rspt_hip_gather_post_*: two slots of sizes (device + page-locked host), events, the gather stream
-    uint64_t* lag_dtotals[2] = {nullptr, nullptr};
-    uint64_t* lag_htotals[2] = {nullptr, nullptr};
-    hipEvent_t lag_ev_in[2] = {}, lag_ev_sizes[2] = {}, lag_ev_payload[2] = {};
-    bool lag_posted[2] = {false, false};
-    hipStream_t lag_stream = nullptr;
-    int lag_world = 0;
-    size_t m_chunk = 0, m_stride = 0;
-    hipStream_t m_up = nullptr, m_down = nullptr;
-    hipEvent_t m_ev_up[2] = {}, m_ev_comp[2] = {}, m_ev_down[2] = {};
-
     // tile geometry for the front end
     uint32_t T = 0, in_lds = 0;  // k_tile_planar: tile staged in LDS
     uint32_t Tp[5] = {0, 0, 0, 0, 0};  // k_tile_planes: tile length when kcount planes are staged: rows [kcount*nch][Tp+16] + nz flags
-
-    unsigned long long* stamps = nullptr;  // diagnostic s_memtime stamps: [512 hzr blocks][16 waves][8]
     bool wide = false;          // more channels than a 16-sample tile of the front-end kernels holds in LDS: k_wide_planar + k_planar_planes
     uint32_t k1_threads = 256;  // workgroup size of k_tile_planes (RSPT_K1_THREADS)
     uint32_t k1_grid = 0;       // workgroups of k_tile_planes; 0 = by LDS footprint (RSPT_K1_GRID, tuning knob)
@@ -217,16 +264,43 @@ struct rspt_hip_packer {
     uint32_t psel = 0;    // RSPT_PLANESEL (diagnostic builds only): which planes the hzr kernels take; bit 8 / 9: stop behind k_hist / k_tree
     int verify = 0;       // decompress checks the block CRCs (rspt_hip_set_verify)
     int big_endian = 0;   // samples arrive / leave with their bytes reversed (rspt_hip_set_byte_order)
-
-    // the small-block encoder runs beside the big one (it fills the CUs the persistent grid frees in its tail)
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    uint32_t* h_nsmall = nullptr;  // page-locked, device-visible: the small-block count of a recent batch (written by k_encode_small)
-
-    // profiling
     bool profiling = false;
-    hipEvent_t ev[ST_COUNT + 1] = {};
     bool ev_valid = false;
+
+    // ---- per-handle constants (rspt_hip_packer_create; h_nsmall at the first compress) ----
+    Stream stream;
+    // the small-block encoder runs beside the big one (it fills the CUs the persistent grid frees in its tail)
+    Stream side;
+    Event ev_fork, ev_join;
+    Event ev[ST_COUNT + 1];  // profiling
+    Dev<unsigned long long> stamps;  // diagnostic s_memtime stamps: [512 hzr blocks][16 waves][8]
+    Dev<CrcConsts> crc;
+    Dev<uint32_t> nb_state;  // [4] persistent: [0] = nb; [2] = work counter of the decoder's persistent grid (zeroed by k_dec_frame)
+    // dct: COS[x][i] and its transpose, built on the host like the reference ctor; beyond the dense table the FFT twiddles
+    Dev<float> cos_tab, cos_tab_t;
+    Dev<double2> fft_tw;    // [n] (cos, sin)(2 pi t / n)
+    Dev<double2> fft_post;  // [n] (cos, sin)(pi k / 2n)
+    Pinned<uint32_t> h_nsmall;  // device-visible: the small-block count of a recent batch (written by k_encode_small)
+    // the copy streams of the many-block pipeline and the feed, made by whichever of them comes first
+    Stream m_up, m_down;
+
+    // ---- the workspace, and the views into its per-call zero region (set by every compress call) ----
+    Workspace ws;
+    uint32_t* nzflag = nullptr;    // view: [cap*4*nblk] set by the front end when an hzr block holds a non-zero byte (= zbuf[set of the last call])
+    uint32_t* needmask = nullptr;  // view: [cap]
+    uint32_t* work_ctr = nullptr;  // view: [16] work counter of the persistent k_hist at 0, the WorkQueues of k_encode from 4 (zeroed per call)
+    long long* row_sum = nullptr;  // view: [blocks][nch] channel sums taken by the de-interleave pass (dct at large ns)
+    bool have_row_sum = false;     // this call's front end filled row_sum
+
+    // ---- host API staging ----
+    HostStaging stage;
+    ManyStaging many;
+    std::unique_ptr<Feed> feed;  // open between rspt_hip_feed_begin and rspt_hip_feed_end
+
+    // ---- gather state ----
+    Dev<uint64_t> gat_totals;  // [gat_world]: container lengths of all ranks (rspt_hip_gather_containers)
+    int gat_world = 0;
+    LagGather lag;
 };
 
 #define HIPCHK(p, call)                         \
@@ -240,6 +314,25 @@ struct rspt_hip_packer {
 
 static void stamp(rspt_hip_packer* p, int i, hipStream_t st) {
     if (p->profiling) hipEventRecord(p->ev[i], st);
+}
+
+// f(std::integral_constant<int, BPS>()) for the handle's sample width
+template <class F>
+static auto by_bps(uint32_t bps, F&& f) {
+    switch (bps) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        default: return f(std::integral_constant<int, 4>());
+    }
+}
+
+// tile of k_tile_planar_i32x4 / k_planar_native_i32x4: T4 samples x nch channels in at most 32 KiB of LDS (four workgroups
+// per CU), T4 a multiple of 4
+static uint32_t tile_i32x4(const Geom& g) {
+    uint32_t T4 = (uint32_t)((32768ull / (4ull * g.nch) - 1) & ~3ull);
+    T4 = T4 > 1024 ? 1024 : T4 < 4 ? 4 : T4;
+    return T4 > g.ns ? g.ns : T4;
 }
 
 template <int BPS, bool XD>
@@ -260,8 +353,8 @@ static void launch_planes(rspt_hip_packer* p, const uint8_t* d_src, size_t nbloc
         constexpr int SB = BPS;
         auto go = [&](auto kern) {
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, d_src, g, T, kfirst, kcount, p->planes, p->needmask, p->nzflag, nbuse, p->ablate,
-                               (uint32_t)nblocks, nbuse ? nullptr : p->work_ctr + 1, p->nb_state, p->nbuse, p->plane_dirty, p->dirty_shift);
+            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, d_src, g, T, kfirst, kcount, p->ws.planes, p->needmask, p->nzflag, nbuse, p->ablate,
+                               (uint32_t)nblocks, nbuse ? nullptr : p->work_ctr + 1, p->nb_state, p->ws.nbuse, p->ws.plane_dirty, p->dirty_shift);
         };
         if (g.ns & 15u)
             go(&k_tile_stream<SB, XD, true>);  // (a short last group per channel, plane rows at any byte alignment)
@@ -270,8 +363,8 @@ static void launch_planes(rspt_hip_packer* p, const uint8_t* d_src, size_t nbloc
         return;
     }
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_planes<BPS, XD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_tile_planes<BPS, XD>), grid, dim3(p->k1_threads), lds, st, d_src, g, T, kfirst, kcount, p->planes, p->needmask, p->nzflag, nbuse, p->ablate, (uint32_t)nblocks,
-                       nbuse ? nullptr : p->work_ctr + 1, p->nb_state, p->nbuse);
+    hipLaunchKernelGGL((k_tile_planes<BPS, XD>), grid, dim3(p->k1_threads), lds, st, d_src, g, T, kfirst, kcount, p->ws.planes, p->needmask, p->nzflag, nbuse, p->ablate, (uint32_t)nblocks,
+                       nbuse ? nullptr : p->work_ctr + 1, p->nb_state, p->ws.nbuse);
 }
 
 // main front-end pass; returns the number of planes it wrote (xdelta: nb as last seen by the host)
@@ -281,15 +374,15 @@ static uint32_t launch_front(rspt_hip_packer* p, const uint8_t* d_src, size_t nb
     if (p->wide) {
         // wide blocks (> ~1000 channels): transpose to the planar block, then -- for the two hzr packers -- the flat stage over it.
         // All four planes are written (an escalation inside the batch needs no second pass), nbuse[] says how many the encoders take.
-        hipLaunchKernelGGL(k_wide_planar<BPS>, dim3((g.ns + 63) / 64, (g.nch + 63) / 64, (unsigned)nblocks), dim3(256), 0, st, d_src, g, p->planar);
+        hipLaunchKernelGGL(k_wide_planar<BPS>, dim3((g.ns + 63) / 64, (g.nch + 63) / 64, (unsigned)nblocks), dim3(256), 0, st, d_src, g, p->ws.planar);
         if (g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_HZR) {
             const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR;
             const dim3 pg((g.N + 4095) / 4096, (unsigned)nblocks);
             if (xd)
-                hipLaunchKernelGGL((k_planar_planes<true>), pg, dim3(256), 0, st, p->planar, g, 4u, p->planes, p->nzflag, p->needmask);
+                hipLaunchKernelGGL((k_planar_planes<true>), pg, dim3(256), 0, st, p->ws.planar, g, 4u, p->ws.planes, p->nzflag, p->needmask);
             else
-                hipLaunchKernelGGL((k_planar_planes<false>), pg, dim3(256), 0, st, p->planar, g, 4u, p->planes, p->nzflag, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_nb_scan, dim3(1), dim3(1024), 0, st, p->needmask, (uint32_t)nblocks, p->nb_state, p->nbuse, xd ? 1 : 0);
+                hipLaunchKernelGGL((k_planar_planes<false>), pg, dim3(256), 0, st, p->ws.planar, g, 4u, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
+            hipLaunchKernelGGL(k_nb_scan, dim3(1), dim3(1024), 0, st, p->needmask, (uint32_t)nblocks, p->nb_state, p->ws.nbuse, xd ? 1 : 0);
         }
         return 4;
     }
@@ -303,17 +396,15 @@ static uint32_t launch_front(rspt_hip_packer* p, const uint8_t* d_src, size_t nb
         return 4;
     }
     if (BPS == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_src) & 15) == 0) {
-        uint32_t T4 = (uint32_t)((32768ull / (4ull * g.nch) - 1) & ~3ull);  // T4 samples x nch channels in at most 32 KiB of LDS
-        T4 = T4 > 1024 ? 1024 : T4 < 4 ? 4 : T4;
-        if (T4 > g.ns) T4 = g.ns;
+        const uint32_t T4 = tile_i32x4(g);
         hipLaunchKernelGGL(k_tile_planar_i32x4, dim3((g.ns + T4 - 1) / T4, (unsigned)nblocks), dim3(256), g.nch * (T4 + 1) * 4, st, d_src, g, T4,
-                           p->planar, p->row_sum);
+                           p->ws.planar, p->row_sum);
         p->have_row_sum = p->row_sum != nullptr;
         return 4;
     }
     dim3 grid((g.ns + p->T - 1) / p->T, (unsigned)nblocks);
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_planar<BPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->in_lds);
-    hipLaunchKernelGGL((k_tile_planar<BPS>), grid, dim3(256), p->in_lds, st, d_src, g, p->T, p->planar);
+    hipLaunchKernelGGL((k_tile_planar<BPS>), grid, dim3(256), p->in_lds, st, d_src, g, p->T, p->ws.planar);
     return 4;
 }
 
@@ -338,10 +429,10 @@ static void launch_dct_fft(rspt_hip_packer* p, uint32_t B, const int32_t* in, in
         const uint32_t R = 1u << (kFftLdsLog - lb - 1), npairs = (1u << (la - 1)) - 1, ngroups = (npairs + R - 1) / R;
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dctr_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dctr_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr);
-        for (uint32_t b0 = 0; b0 < B; b0 += (uint32_t)p->fft_bpp) {
-            const uint32_t nbk = std::min<uint32_t>((uint32_t)p->fft_bpp, B - b0);
-            hipLaunchKernelGGL(k_dctr_cols, dim3(1u << (lb - lwr), g.nch, nbk), dim3(fthr), ldsc, st, in, g, p->mean_i32, p->fft_tw, p->fft_scratch, la, lb, b0);
-            hipLaunchKernelGGL(k_dctr_rows, dim3(ngroups + 1, g.nch, nbk), dim3(fthr), ldsr, st, p->fft_scratch, g, p->fft_tw, p->fft_post, out, la, lb, b0,
+        for (uint32_t b0 = 0; b0 < B; b0 += (uint32_t)p->ws.fft_bpp) {
+            const uint32_t nbk = std::min<uint32_t>((uint32_t)p->ws.fft_bpp, B - b0);
+            hipLaunchKernelGGL(k_dctr_cols, dim3(1u << (lb - lwr), g.nch, nbk), dim3(fthr), ldsc, st, in, g, p->ws.mean_i32, p->fft_tw, p->ws.fft_scratch, la, lb, b0);
+            hipLaunchKernelGGL(k_dctr_rows, dim3(ngroups + 1, g.nch, nbk), dim3(fthr), ldsr, st, p->ws.fft_scratch, g, p->fft_tw, p->fft_post, out, la, lb, b0,
                                p->dct_scale0, p->dct_scale1);
         }
         return;
@@ -354,20 +445,20 @@ static void launch_dct_fft(rspt_hip_packer* p, uint32_t B, const int32_t* in, in
         const uint32_t ldsr = ((uint32_t)sizeof(double2) << (lb + lrr)) + ((uint32_t)sizeof(double2) << (lb - 1));
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_idctr_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_idctr_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr);
-        for (uint32_t b0 = 0; b0 < B; b0 += (uint32_t)p->fft_bpp) {
-            const uint32_t nbk = std::min<uint32_t>((uint32_t)p->fft_bpp, B - b0);
-            hipLaunchKernelGGL(k_idctr_cols, dim3(1u << (lb - lwr), g.nch, nbk), dim3(fthr), ldsc, st, in, g, p->fft_tw, p->fft_post, p->fft_scratch, la, lb, b0,
+        for (uint32_t b0 = 0; b0 < B; b0 += (uint32_t)p->ws.fft_bpp) {
+            const uint32_t nbk = std::min<uint32_t>((uint32_t)p->ws.fft_bpp, B - b0);
+            hipLaunchKernelGGL(k_idctr_cols, dim3(1u << (lb - lwr), g.nch, nbk), dim3(fthr), ldsc, st, in, g, p->fft_tw, p->fft_post, p->ws.fft_scratch, la, lb, b0,
                                p->dct_cs0);
-            hipLaunchKernelGGL(k_idctr_rows, dim3(1u << (la - lrr), g.nch, nbk), dim3(fthr), ldsr, st, p->fft_scratch, g, p->means, p->fft_tw, out, la, lb, b0,
+            hipLaunchKernelGGL(k_idctr_rows, dim3(1u << (la - lrr), g.nch, nbk), dim3(fthr), ldsr, st, p->ws.fft_scratch, g, p->ws.means, p->fft_tw, out, la, lb, b0,
                                p->idct_scale);
         }
         return;
     }
-    for (uint32_t b0 = 0; b0 < B; b0 += (uint32_t)p->fft_bpp) {
-        const uint32_t nbk = std::min<uint32_t>((uint32_t)p->fft_bpp, B - b0);
-        hipLaunchKernelGGL((k_dctfft_cols<FORWARD>), dim3(1u << (l2 - lw), g.nch, nbk), dim3(fthr), lds_c, st, in, g, p->mean_i32, p->fft_tw,
-                           p->fft_post, p->fft_scratch, l1, l2, b0, p->dct_cs0);
-        hipLaunchKernelGGL((k_dctfft_rows<FORWARD>), dim3(1u << (l1 - lr), g.nch, nbk), dim3(fthr), lds_r, st, p->fft_scratch, g, p->means,
+    for (uint32_t b0 = 0; b0 < B; b0 += (uint32_t)p->ws.fft_bpp) {
+        const uint32_t nbk = std::min<uint32_t>((uint32_t)p->ws.fft_bpp, B - b0);
+        hipLaunchKernelGGL((k_dctfft_cols<FORWARD>), dim3(1u << (l2 - lw), g.nch, nbk), dim3(fthr), lds_c, st, in, g, p->ws.mean_i32, p->fft_tw,
+                           p->fft_post, p->ws.fft_scratch, l1, l2, b0, p->dct_cs0);
+        hipLaunchKernelGGL((k_dctfft_rows<FORWARD>), dim3(1u << (l1 - lr), g.nch, nbk), dim3(fthr), lds_r, st, p->ws.fft_scratch, g, p->ws.means,
                            p->fft_tw, p->fft_post, out, l1, l2, b0, FORWARD ? p->dct_scale0 : 0.0, FORWARD ? p->dct_scale1 : p->idct_scale);
     }
 }
@@ -378,18 +469,18 @@ static void launch_fwht_big(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
     const Geom& g = p->g;
     const uint32_t segs = g.ns >> 15;  // 32768-point pieces per row: 4 .. 128
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_seg), hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4);
-    hipLaunchKernelGGL(k_fwht_seg, dim3(segs, g.nch, B), dim3(1024), 32768 * 4, st, p->planar, g);
+    hipLaunchKernelGGL(k_fwht_seg, dim3(segs, g.nch, B), dim3(1024), 32768 * 4, st, p->ws.planar, g);
     const uint32_t m1 = segs > 64u ? 64u : segs, m2 = segs / m1;
-    hipLaunchKernelGGL((k_fwht_cross<FORWARD>), dim3(g.ns / m1 / 256u, g.nch, B), dim3(256), 0, st, p->planar, g, p->means, p->mean_i32, m1, 32768u,
+    hipLaunchKernelGGL((k_fwht_cross<FORWARD>), dim3(g.ns / m1 / 256u, g.nch, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m1, 32768u,
                        m2 == 1u ? 1u : 0u);
     if (m2 > 1u)
-        hipLaunchKernelGGL((k_fwht_cross<FORWARD>), dim3(g.ns / m2 / 256u, g.nch, B), dim3(256), 0, st, p->planar, g, p->means, p->mean_i32, m2,
+        hipLaunchKernelGGL((k_fwht_cross<FORWARD>), dim3(g.ns / m2 / 256u, g.nch, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m2,
                            32768u * m1, 1u);
 }
 
 template <int BPS>
 static void launch_fixup(rspt_hip_packer* p, const uint8_t* d_src, size_t nblocks, uint32_t np, hipStream_t st) {
-    launch_planes<BPS, true>(p, d_src, nblocks, np, 4 - np, p->nbuse, st);
+    launch_planes<BPS, true>(p, d_src, nblocks, np, 4 - np, p->ws.nbuse, st);
 }
 
 
@@ -436,7 +527,7 @@ static void launch_inv_native(rspt_hip_packer* p, uint32_t B, uint32_t nrow, voi
     constexpr uint32_t S = (1024u / CG) * 16u, lds = CG * (S + 1u) * 4u;  // > 64 KiB: the limit is raised per kernel
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_inv_native<XDELTA, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const dim3 ng((g.ns + S - 1) / S, (g.nch + CG - 1) / CG, B);
-    hipLaunchKernelGGL((k_inv_native<XDELTA, CG>), ng, dim3(1024), lds, st, p->planes, g, p->dec_nb, nrow, p->txor, p->tsum, (uint8_t*)d_dst);
+    hipLaunchKernelGGL((k_inv_native<XDELTA, CG>), ng, dim3(1024), lds, st, p->ws.planes, g, p->ws.dec_nb, nrow, p->ws.txor, p->ws.tsum, (uint8_t*)d_dst);
 }
 
 extern "C" {
@@ -464,76 +555,6 @@ int rspt_hip_device_count(void) {
     return n;
 }
 
-static void free_workspace(rspt_hip_packer* p) {
-    hipFree(p->planes);
-    hipFree(p->planar);
-    hipFree(p->nbuse);
-    hipFree(p->dec_nb);
-    p->dec_nb = nullptr;
-    hipFree(p->zbuf[0]);
-    hipFree(p->zbuf[1]);
-    p->zbuf[0] = p->zbuf[1] = nullptr;
-    hipFree(p->plane_dirty);
-    p->plane_dirty = nullptr;
-    hipFree(p->big_list);
-    hipFree(p->small_list);
-    p->nzflag = p->big_list = p->small_list = nullptr;
-    hipFree(p->hist);
-    hipFree(p->seghist);
-    hipFree(p->segbase);
-    hipFree(p->lists);
-    hipFree(p->listinfo);
-    p->seghist = p->segbase = p->lists = nullptr;
-    p->listinfo = nullptr;
-    hipFree(p->cw);
-    hipFree(p->tdesc);
-    hipFree(p->meta);
-    hipFree(p->out_off);
-    hipFree(p->means);
-    hipFree(p->planar2);
-    hipFree(p->txor);
-    hipFree(p->tsum);
-    hipFree(p->rowrec);
-    hipFree(p->blk_off);
-    hipFree(p->fft_scratch);
-    hipFree(p->mean_i32);
-    p->fft_scratch = nullptr;
-    p->mean_i32 = nullptr;
-    p->planar2 = nullptr;
-    p->txor = p->tsum = p->rowrec = nullptr;
-    p->blk_off = nullptr;
-    p->planes = nullptr;
-    p->planar = nullptr;
-    p->needmask = p->nbuse = p->hist = p->cw = p->tdesc = nullptr;
-    p->meta = nullptr;
-    p->out_off = nullptr;
-    p->means = nullptr;
-    p->cap_blocks = 0;
-}
-
-// everything ensure_many() creates; leaves the fields null so that a later call can start over
-static void free_many(rspt_hip_packer* p) {
-    for (int i = 0; i < 2; ++i) {
-        hipFree(p->m_src[i]);
-        hipFree(p->m_dst[i]);
-        hipFree(p->m_sizes[i]);
-        hipFree(p->m_idx[i]);
-        p->m_src[i] = p->m_dst[i] = nullptr;
-        p->m_sizes[i] = p->m_idx[i] = nullptr;
-        if (p->m_ev_up[i]) hipEventDestroy(p->m_ev_up[i]);
-        if (p->m_ev_comp[i]) hipEventDestroy(p->m_ev_comp[i]);
-        if (p->m_ev_down[i]) hipEventDestroy(p->m_ev_down[i]);
-        p->m_ev_up[i] = p->m_ev_comp[i] = p->m_ev_down[i] = nullptr;
-    }
-    if (p->m_hsizes) hipHostFree(p->m_hsizes);
-    if (p->m_hidx) hipHostFree(p->m_hidx);
-    p->m_hsizes = p->m_hidx = nullptr;
-    if (p->m_up) hipStreamDestroy(p->m_up);
-    if (p->m_down) hipStreamDestroy(p->m_down);
-    p->m_up = p->m_down = nullptr;
-    p->m_chunk = p->m_stride = 0;
-}
-
 int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps, size_t nch, size_t ns, size_t nb, int device) {
     if (!out) return RSPT_HIP_ERR_ARG;
     *out = nullptr;
@@ -550,7 +571,7 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return RSPT_HIP_ERR_NO_DEVICE;  // code objects are gfx950 only
     if (hipSetDevice(device) != hipSuccess) return RSPT_HIP_ERR_NO_DEVICE;
 
-    rspt_hip_packer* p = new (std::nothrow) rspt_hip_packer();
+    std::unique_ptr<rspt_hip_packer> p(new (std::nothrow) rspt_hip_packer());  // (released on every error exit)
     if (!p) return RSPT_HIP_ERR_ALLOC;
     p->device = device;
     Geom& g = p->g;
@@ -620,16 +641,10 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
         uint32_t T = (uint32_t)(65536ull / (4ull * g.nch));
         T = T > 1 ? T - 1 : 0;
         if (T > 1024) T = 1024;
-        if (T < 1) {
-            delete p;
-            return RSPT_HIP_ERR_UNSUPPORTED;
-        }
+        if (T < 1) return RSPT_HIP_ERR_UNSUPPORTED;
         p->Tn_native = T;
     }
-    if (kind == RSPT_HIP_KIND_HADAMARD && ns > (1u << 22)) {  // (up to 65536 one workgroup per channel; beyond, two passes: launch_fwht_big)
-        delete p;
-        return RSPT_HIP_ERR_UNSUPPORTED;
-    }
+    if (kind == RSPT_HIP_KIND_HADAMARD && ns > (1u << 22)) return RSPT_HIP_ERR_UNSUPPORTED;  // (up to 65536 one workgroup per channel; beyond, two passes: launch_fwht_big)
     if (kind == RSPT_HIP_KIND_DCT) {
         // The reference's dense n x n table (bit-exact) for every n it can run itself -- its table index `(2x+1)*i` is an
         // int (signal_packer_dct.cpp:60-74): n <= 32768 -- except n = 2^k > 8192, which take the fp64 FFT path (PRDN / CR
@@ -637,10 +652,7 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
         // (8.6 GB at 32768).  RSPT_HIP_DCT_FORCE_FFT forces the FFT path for small n = 2^k (cross-check against the table).
         const bool pow2 = (ns & (ns - 1)) == 0;
         p->dct_fft = (ns > 8192 && pow2) || (force_fft && pow2 && ns >= 16);
-        if (p->dct_fft ? ns > (1u << 22) : ns > 32768) {
-            delete p;
-            return RSPT_HIP_ERR_UNSUPPORTED;
-        }
+        if (p->dct_fft ? ns > (1u << 22) : ns > 32768) return RSPT_HIP_ERR_UNSUPPORTED;
         if (p->dct_fft) {
             uint32_t k = 0;
             while ((1ull << k) < ns) ++k;
@@ -658,16 +670,9 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
             }
         }
     }
-    hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete p;
-        return RSPT_HIP_ERR_LAUNCH;
-    }
+    if (hipStreamCreateWithFlags(p->stream.out(), hipStreamNonBlocking) != hipSuccess) return RSPT_HIP_ERR_LAUNCH;
     p->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (hipMalloc(&p->stamps, (512 * 16 * 8 + 2 * 16384) * sizeof(unsigned long long)) != hipSuccess) {
-        rspt_hip_packer_destroy(p);
-        return RSPT_HIP_ERR_ALLOC;
-    }
+    if (hipMalloc(p->stamps.out(), (512 * 16 * 8 + 2 * 16384) * sizeof(unsigned long long)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
     {
         // ~87 KB of constants, computed once per process (a function-local static: packers are created from several host
         // threads at once -- one per device, tests/cxx/shard_devices.cpp -- and the initialisation of such a static is thread-safe)
@@ -676,28 +681,22 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
             make_crc_consts(*c);
             return c;
         }();
-        if (hipMalloc(&p->crc, sizeof(CrcConsts)) != hipSuccess || hipMalloc(&p->nb_state, 4 * sizeof(uint32_t)) != hipSuccess) {
-            rspt_hip_packer_destroy(p);
+        if (hipMalloc(p->crc.out(), sizeof(CrcConsts)) != hipSuccess || hipMalloc(p->nb_state.out(), 4 * sizeof(uint32_t)) != hipSuccess)
             return RSPT_HIP_ERR_ALLOC;
-        }
         uint32_t nb0 = p->nb_ctor;
         if (hipMemcpy(p->crc, &cc, sizeof(cc), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->nb_state, &nb0, sizeof(nb0), hipMemcpyHostToDevice) != hipSuccess) {
-            rspt_hip_packer_destroy(p);
+            hipMemcpy(p->nb_state, &nb0, sizeof(nb0), hipMemcpyHostToDevice) != hipSuccess)
             return RSPT_HIP_ERR_LAUNCH;
-        }
     }
-    for (int i = 0; i <= ST_COUNT; ++i) hipEventCreate(&p->ev[i]);
+    for (int i = 0; i <= ST_COUNT; ++i) hipEventCreate(p->ev[i].out());
     // (highest priority: the latency-bound small blocks go first and are done long before the big encoder, so that the
     // join at the end of the call finds its event complete)
     int prio_lo = 0, prio_hi = 0;
     hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (hipStreamCreateWithPriority(&p->side, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess) {
-        rspt_hip_packer_destroy(p);
+    if (hipStreamCreateWithPriority(p->side.out(), hipStreamNonBlocking, prio_hi) != hipSuccess ||
+        hipEventCreateWithFlags(p->ev_fork.out(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(p->ev_join.out(), hipEventDisableTiming) != hipSuccess)
         return RSPT_HIP_ERR_LAUNCH;
-    }
     if (kind == RSPT_HIP_KIND_DCT) {
         const double ratio1 = sqrt(2.0 / (double)(int)ns);
         const float cs0 = (float)(1 / sqrt(2));
@@ -715,23 +714,17 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
             tw[t] = make_double2(cos(a), sin(a));
             post[t] = make_double2(cos(b), sin(b));
         }
-        if (hipMalloc(&p->fft_tw, n * sizeof(double2)) != hipSuccess || hipMalloc(&p->fft_post, n * sizeof(double2)) != hipSuccess) {
-            rspt_hip_packer_destroy(p);
+        if (hipMalloc(p->fft_tw.out(), n * sizeof(double2)) != hipSuccess || hipMalloc(p->fft_post.out(), n * sizeof(double2)) != hipSuccess)
             return RSPT_HIP_ERR_ALLOC;
-        }
         if (hipMemcpy(p->fft_tw, tw.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->fft_post, post.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess) {
-            rspt_hip_packer_destroy(p);
+            hipMemcpy(p->fft_post, post.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess)
             return RSPT_HIP_ERR_LAUNCH;
-        }
     } else if (kind == RSPT_HIP_KIND_DCT) {
         // init_cos_table (signal_packer_dct.cpp:60-74), host libm, same expression and types.  Built in slabs of rows by
         // all host threads (10^9 cosines at n = 32768) and uploaded slab by slab; the transposed copy is made on the device.
         const size_t n = ns;
-        if (hipMalloc(&p->cos_tab, n * n * sizeof(float)) != hipSuccess || hipMalloc(&p->cos_tab_t, n * n * sizeof(float)) != hipSuccess) {
-            rspt_hip_packer_destroy(p);
+        if (hipMalloc(p->cos_tab.out(), n * n * sizeof(float)) != hipSuccess || hipMalloc(p->cos_tab_t.out(), n * n * sizeof(float)) != hipSuccess)
             return RSPT_HIP_ERR_ALLOC;
-        }
         const double PI = 3.14159265358979323846;
         const double pi_n_2 = PI / ((double)(int)n * 2.0);
         const size_t slab = std::max<size_t>(1, std::min<size_t>(n, (64u << 20) / (n * sizeof(float))));
@@ -754,64 +747,27 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
                 for (unsigned t = 0; t < nthr; ++t) th.emplace_back(fill, nr * t / nthr, nr * (t + 1) / nthr);
                 for (auto& t : th) t.join();
             }
-            if (hipMemcpy(p->cos_tab + x0 * n, tab.data(), nr * n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-                rspt_hip_packer_destroy(p);
-                return RSPT_HIP_ERR_LAUNCH;
-            }
+            if (hipMemcpy(p->cos_tab + x0 * n, tab.data(), nr * n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return RSPT_HIP_ERR_LAUNCH;
         }
         hipLaunchKernelGGL(k_transpose_f32, dim3((unsigned)((n + 31) / 32), (unsigned)((n + 31) / 32)), dim3(256), 0, 0, p->cos_tab, p->cos_tab_t,
                            (uint32_t)n);
-        if (hipGetLastError() != hipSuccess) {
-            rspt_hip_packer_destroy(p);
-            return RSPT_HIP_ERR_LAUNCH;
-        }
+        if (hipGetLastError() != hipSuccess) return RSPT_HIP_ERR_LAUNCH;
     }
-    if (hipDeviceSynchronize() != hipSuccess) {  // setup copies ran on the null stream; the handle's stream does not wait for it
-        rspt_hip_packer_destroy(p);
-        return RSPT_HIP_ERR_LAUNCH;
-    }
-    *out = p;
+    // setup copies ran on the null stream; the handle's stream does not wait for it
+    if (hipDeviceSynchronize() != hipSuccess) return RSPT_HIP_ERR_LAUNCH;
+    *out = p.release();
     return RSPT_HIP_OK;
 }
 
 void rspt_hip_packer_destroy(rspt_hip_packer* p) {
     if (!p) return;
     hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    free_workspace(p);
-    hipFree(p->stamps);
-    hipFree(p->crc);
-    hipFree(p->nb_state);
-    hipFree(p->cos_tab);
-    hipFree(p->cos_tab_t);
-    hipFree(p->fft_tw);
-    hipFree(p->fft_post);
-    hipFree(p->h_src);
-    hipFree(p->h_dst);
-    hipFree(p->h_size);
+    // An open feed ends first: its partly filled group is still submitted, and that launch needs the workspace and constants.
     if (p->feed) rspt_hip_feed_end(p);
-    free_many(p);
-    hipFree(p->gat_totals);
-    if (p->lag_stream) hipStreamSynchronize(p->lag_stream);
-    for (int i = 0; i < 2; ++i) {
-        hipFree(p->lag_dtotals[i]);
-        if (p->lag_htotals[i]) hipHostFree(p->lag_htotals[i]);
-        if (p->lag_ev_in[i]) hipEventDestroy(p->lag_ev_in[i]);
-        if (p->lag_ev_sizes[i]) hipEventDestroy(p->lag_ev_sizes[i]);
-        if (p->lag_ev_payload[i]) hipEventDestroy(p->lag_ev_payload[i]);
-    }
-    if (p->lag_stream) hipStreamDestroy(p->lag_stream);
-    for (int i = 0; i <= ST_COUNT; ++i)
-        if (p->ev[i]) hipEventDestroy(p->ev[i]);
-    if (p->side) {
-        hipStreamSynchronize(p->side);
-        hipStreamDestroy(p->side);
-    }
-    if (p->h_nsmall) hipHostFree(p->h_nsmall);
-    if (p->ev_fork) hipEventDestroy(p->ev_fork);
-    if (p->ev_join) hipEventDestroy(p->ev_join);
-    if (p->stream) hipStreamDestroy(p->stream);
-    delete p;
+    const hipStream_t streams[] = {p->stream, p->side, p->lag.stream};
+    for (hipStream_t s : streams)
+        if (s) hipStreamSynchronize(s);
+    delete p;  // the members go in reverse order of construction
 }
 
 size_t rspt_hip_block_bytes(const rspt_hip_packer* p) { return p ? (size_t)p->g.block_bytes : 0; }
@@ -825,66 +781,60 @@ size_t rspt_hip_max_compressed_size(const rspt_hip_packer* p) {
 
 int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     if (!p || max_blocks == 0) return RSPT_HIP_ERR_ARG;
-    if (max_blocks <= p->cap_blocks) return RSPT_HIP_OK;
+    if (max_blocks <= p->ws.cap_blocks) return RSPT_HIP_OK;
     if (max_blocks > 65535) return RSPT_HIP_ERR_ARG;  // grid.y / grid.z limit; shard larger batches
     HIPCHK(p, hipSetDevice(p->device));
     HIPCHK(p, hipStreamSynchronize(p->stream));
-    free_workspace(p);
+    p->ws = Workspace();  // (released before the new one is made: the two are never held at once)
     const Geom& g = p->g;
+    Workspace w;
     const size_t nhb = max_blocks * kMaxPlanes * g.nblk;
     bool ok = true;
-    ok &= hipMalloc(&p->planes, max_blocks * kMaxPlanes * g.plane_stride + 4096) == hipSuccess;
-    ok &= hipMalloc(&p->nbuse, max_blocks * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->dec_nb, max_blocks * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->plane_dirty, max_blocks * kMaxPlanes * 4 * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.planes.out(), max_blocks * kMaxPlanes * g.plane_stride + 4096) == hipSuccess;
+    ok &= hipMalloc(w.nbuse.out(), max_blocks * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.dec_nb.out(), max_blocks * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.plane_dirty.out(), max_blocks * kMaxPlanes * 4 * sizeof(uint32_t)) == hipSuccess;
     // one region zeroed per call by a single memset: [nzflag: B*4*nblk][needmask: B][work counters: 16]; the last two are
     // placed per call right behind the part of nzflag in use
-    p->zcap_words = nhb + max_blocks + 32 + 2 * max_blocks * (size_t)g.nch + 2;
-    for (int i = 0; i < 2; ++i) {
-        ok &= hipMalloc(&p->zbuf[i], p->zcap_words * sizeof(uint32_t)) == hipSuccess;
-        p->zero_ready[i] = false;
-    }
-    p->zset = 0;
-    p->nzflag = p->zbuf[0];
-    ok &= hipMalloc(&p->big_list, nhb * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->small_list, nhb * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->hist, nhb * kSymStride * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->cw, nhb * kSymStride * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->seghist, nhb * (size_t)kSegHistStride * sizeof(uint16_t)) == hipSuccess;
-    ok &= hipMalloc(&p->segbase, nhb * (size_t)kEncWaves * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->lists, nhb * (size_t)kEncWaves * kListCap * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->listinfo, nhb * (size_t)kEncWaves * sizeof(uint2)) == hipSuccess;
-    ok &= hipMalloc(&p->tdesc, nhb * kTdescWords * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->meta, nhb * sizeof(BlockMeta)) == hipSuccess;
-    ok &= hipMalloc(&p->out_off, nhb * sizeof(uint64_t)) == hipSuccess;
-    ok &= hipMalloc(&p->means, max_blocks * (size_t)(g.hdr_len ? g.hdr_len : 4)) == hipSuccess;
+    w.zcap_words = nhb + max_blocks + 32 + 2 * max_blocks * (size_t)g.nch + 2;
+    for (int i = 0; i < 2; ++i) ok &= hipMalloc(w.zbuf[i].out(), w.zcap_words * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.big_list.out(), nhb * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.small_list.out(), nhb * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.hist.out(), nhb * kSymStride * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.cw.out(), nhb * kSymStride * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.seghist.out(), nhb * (size_t)kSegHistStride * sizeof(uint16_t)) == hipSuccess;
+    ok &= hipMalloc(w.segbase.out(), nhb * (size_t)kEncWaves * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.lists.out(), nhb * (size_t)kEncWaves * kListCap * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.listinfo.out(), nhb * (size_t)kEncWaves * sizeof(uint2)) == hipSuccess;
+    ok &= hipMalloc(w.tdesc.out(), nhb * kTdescWords * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.meta.out(), nhb * sizeof(BlockMeta)) == hipSuccess;
+    ok &= hipMalloc(w.out_off.out(), nhb * sizeof(uint64_t)) == hipSuccess;
+    ok &= hipMalloc(w.means.out(), max_blocks * (size_t)(g.hdr_len ? g.hdr_len : 4)) == hipSuccess;
     // planar int32 scratch: transform packers on compress, every packer on decompress
-    ok &= hipMalloc(&p->planar, max_blocks * (size_t)g.N * sizeof(int32_t) + 4096) == hipSuccess;
+    ok &= hipMalloc(w.planar.out(), max_blocks * (size_t)g.N * sizeof(int32_t) + 4096) == hipSuccess;
     const size_t nscan = std::max<size_t>(p->ntile, g.N / kRowTile + 1);  // tiles of 4096, or row tiles of 256 (k_inv_native)
-    ok &= hipMalloc(&p->txor, max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->tsum, max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
-    if (g.ns % kRowTile == 0 && g.bps == 4) ok &= hipMalloc(&p->rowrec, max_blocks * (g.N / kRowTile) * (size_t)kRowRec * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(&p->blk_off, nhb * sizeof(uint64_t)) == hipSuccess;
-    if (g.kind == RSPT_HIP_KIND_DCT) ok &= hipMalloc(&p->planar2, max_blocks * (size_t)g.N * sizeof(int32_t) + 4096) == hipSuccess;
-    if (g.kind == RSPT_HIP_KIND_HADAMARD && g.ns > 65536u) ok &= hipMalloc(&p->mean_i32, max_blocks * (size_t)g.nch * sizeof(int32_t)) == hipSuccess;
+    ok &= hipMalloc(w.txor.out(), max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.tsum.out(), max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
+    if (g.ns % kRowTile == 0 && g.bps == 4) ok &= hipMalloc(w.rowrec.out(), max_blocks * (g.N / kRowTile) * (size_t)kRowRec * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.blk_off.out(), nhb * sizeof(uint64_t)) == hipSuccess;
+    if (g.kind == RSPT_HIP_KIND_DCT) ok &= hipMalloc(w.planar2.out(), max_blocks * (size_t)g.N * sizeof(int32_t) + 4096) == hipSuccess;
+    if (g.kind == RSPT_HIP_KIND_HADAMARD && g.ns > 65536u) ok &= hipMalloc(w.mean_i32.out(), max_blocks * (size_t)g.nch * sizeof(int32_t)) == hipSuccess;
     if (g.kind == RSPT_HIP_KIND_DCT && p->dct_fft) {
         const size_t per_block = (size_t)g.N * sizeof(double2);
-        p->fft_bpp = std::max<size_t>(1, std::min<size_t>(max_blocks, ((size_t)1 << 30) / per_block));
-        ok &= hipMalloc(&p->fft_scratch, p->fft_bpp * per_block) == hipSuccess;
-        ok &= hipMalloc(&p->mean_i32, max_blocks * (size_t)g.nch * sizeof(int32_t)) == hipSuccess;
+        w.fft_bpp = std::max<size_t>(1, std::min<size_t>(max_blocks, ((size_t)1 << 30) / per_block));
+        ok &= hipMalloc(w.fft_scratch.out(), w.fft_bpp * per_block) == hipSuccess;
+        ok &= hipMalloc(w.mean_i32.out(), max_blocks * (size_t)g.nch * sizeof(int32_t)) == hipSuccess;
     }
-    if (!ok) {
-        free_workspace(p);
-        return RSPT_HIP_ERR_ALLOC;
-    }
+    if (!ok) return RSPT_HIP_ERR_ALLOC;
     // the clean-plane invariant starts from zeroed planes
-    HIPCHK(p, hipMemset(p->planes, 0, max_blocks * kMaxPlanes * g.plane_stride + 4096));
-    HIPCHK(p, hipMemset(p->plane_dirty, 0, max_blocks * kMaxPlanes * 4 * sizeof(uint32_t)));
+    HIPCHK(p, hipMemset(w.planes, 0, max_blocks * kMaxPlanes * g.plane_stride + 4096));
+    HIPCHK(p, hipMemset(w.plane_dirty, 0, max_blocks * kMaxPlanes * 4 * sizeof(uint32_t)));
     p->dirty_shift = 0;
     while (((g.nblk - 1) >> p->dirty_shift) >= 128u) ++p->dirty_shift;
     HIPCHK(p, hipDeviceSynchronize());  // (the calls that follow may come on any stream)
-    p->planes_unknown = false;
-    p->cap_blocks = max_blocks;
+    w.cap_blocks = max_blocks;
+    p->ws = std::move(w);
+    p->nzflag = p->ws.zbuf[0];
     return RSPT_HIP_OK;
 }
 
@@ -904,7 +854,7 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
     const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR;
     {
         const size_t nhb_call = nblocks * kMaxPlanes * g.nblk;
-        p->nzflag = p->zbuf[p->zset];
+        p->nzflag = p->ws.zbuf[p->ws.zset];
         p->needmask = p->nzflag + nhb_call;
         p->work_ctr = p->needmask + ((nblocks + 3) & ~(size_t)3);
         size_t zwords = (size_t)((p->work_ctr + 16) - p->nzflag);
@@ -915,65 +865,53 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
             p->row_sum = reinterpret_cast<long long*>(p->nzflag + zwords);
             zwords += 2 * nblocks * (size_t)g.nch;
         }
-        if (!p->zero_ready[p->zset]) HIPCHK(p, hipMemsetAsync(p->nzflag, 0, zwords * sizeof(uint32_t), st));  // (first call, or after a failed one)
-        p->zero_ready[0] = p->zero_ready[1] = false;  // this copy is in use now; the other one becomes ready once k_tree is launched
+        if (!p->ws.zero_ready[p->ws.zset]) HIPCHK(p, hipMemsetAsync(p->nzflag, 0, zwords * sizeof(uint32_t), st));  // (first call, or after a failed one)
+        p->ws.zero_ready[0] = p->ws.zero_ready[1] = false;  // this copy is in use now; the other one becomes ready once k_tree is launched
     }
-    if (p->planes_unknown || (p->ablate & ~(3u << 26)) || p->psel) {  // (diagnostic runs skip kernels and stores: never trust the planes they leave; probes 26 / 27 store everything)
-        HIPCHK(p, hipMemsetAsync(p->plane_dirty, 0xFF, p->cap_blocks * kMaxPlanes * 4 * sizeof(uint32_t), st));
-        p->planes_unknown = false;
+    if (p->ws.planes_unknown || (p->ablate & ~(3u << 26)) || p->psel) {  // (diagnostic runs skip kernels and stores: never trust the planes they leave; probes 26 / 27 store everything)
+        HIPCHK(p, hipMemsetAsync(p->ws.plane_dirty, 0xFF, p->ws.cap_blocks * kMaxPlanes * 4 * sizeof(uint32_t), st));
+        p->ws.planes_unknown = false;
     }
-    uint32_t np = 4;
-    switch (g.bps) {
-        case 1: np = launch_front<1>(p, src, nblocks, st); break;
-        case 2: np = launch_front<2>(p, src, nblocks, st); break;
-        case 3: np = launch_front<3>(p, src, nblocks, st); break;
-        default: np = launch_front<4>(p, src, nblocks, st); break;
-    }
+    const uint32_t np = by_bps(g.bps, [&](auto bps) { return launch_front<decltype(bps)::value>(p, src, nblocks, st); });
     if (g.kind == RSPT_HIP_KIND_HADAMARD) {
         // per channel: mean removal, WHT, truncating /n (signal_packer_hadamard.cpp:57-72)
         const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
         if (g.ns > 65536u) {  // two passes over the planar row (any 2^k the reference's own transform takes, fwht.c:4-28)
-            hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->planar, g, p->means, p->mean_i32);
+            hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32);
             launch_fwht_big<true>(p, B, st);
-            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->planar, g, 3u, p->planes, p->nzflag, (uint32_t*)nullptr);
+            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, 3u, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
         } else if (g.ns == 65536u) {  // the whole row in registers: read once, and the byte planes written straight from them
             hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-            hipLaunchKernelGGL((k_fwht64k<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->planar, g, p->means, p->planes, p->nzflag, 3u);
+            hipLaunchKernelGGL((k_fwht64k<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, p->nzflag, 3u);
         } else {
             hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-            hipLaunchKernelGGL((k_fwht<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->planar, g, p->means);
-            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->planar, g, 3u, p->planes, p->nzflag, (uint32_t*)nullptr);
+            hipLaunchKernelGGL((k_fwht<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
+            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, 3u, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
         }
     } else if (g.kind == RSPT_HIP_KIND_DCT) {
         if (p->dct_fft) {
             if (p->have_row_sum)  // the de-interleave pass summed the channels on its way: no second pass over the planar block
-                hipLaunchKernelGGL(k_means_from_sums, dim3((B * g.nch + 255) / 256), dim3(256), 0, st, p->row_sum, g, B, p->means, p->mean_i32);
+                hipLaunchKernelGGL(k_means_from_sums, dim3((B * g.nch + 255) / 256), dim3(256), 0, st, p->row_sum, g, B, p->ws.means, p->ws.mean_i32);
             else
-                hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->planar, g, p->means, p->mean_i32);
-            launch_dct_fft<true>(p, B, p->planar, p->planar2, st);
+                hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32);
+            launch_dct_fft<true>(p, B, p->ws.planar, p->ws.planar2, st);
         } else {
-            hipLaunchKernelGGL((k_dct<true>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->planar, g, p->means,
-                               p->cos_tab, p->dct_scale0, p->dct_scale1, p->dct_cs0, p->planar2);
+            hipLaunchKernelGGL((k_dct<true>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means,
+                               p->cos_tab, p->dct_scale0, p->dct_scale1, p->dct_cs0, p->ws.planar2);
         }
-        hipLaunchKernelGGL((k_planar_planes<true>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->planar2, g, 2u, p->planes, p->nzflag, (uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_planar_planes<true>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar2, g, 2u, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
     }
     HIPCHK(p, hipGetLastError());
 
     stamp(p, ST_NB, st);
     if (g.kind != RSPT_HIP_KIND_XDELTA_HZR && g.kind != RSPT_HIP_KIND_HZR)  // (k_tile_planes runs the scan in its last workgroup)
-        hipLaunchKernelGGL(k_nb_scan, dim3(1), dim3(1024), 0, st, p->needmask, B, p->nb_state, p->nbuse, 0);
-    if (xd && np < 4) {  // nb may have escalated in this call: add the planes the main pass did not write
-        switch (g.bps) {
-            case 1: launch_fixup<1>(p, src, nblocks, np, st); break;
-            case 2: launch_fixup<2>(p, src, nblocks, np, st); break;
-            case 3: launch_fixup<3>(p, src, nblocks, np, st); break;
-            default: launch_fixup<4>(p, src, nblocks, np, st); break;
-        }
-    }
+        hipLaunchKernelGGL(k_nb_scan, dim3(1), dim3(1024), 0, st, p->needmask, B, p->nb_state, p->ws.nbuse, 0);
+    if (xd && np < 4)  // nb may have escalated in this call: add the planes the main pass did not write
+        by_bps(g.bps, [&](auto bps) { launch_fixup<decltype(bps)::value>(p, src, nblocks, np, st); });
     stamp(p, ST_HIST, st);
     // (the list of k_hist's blocks sits in big_list until k_layout refills that array for k_encode; its count in work_ctr[2])
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
-    hipLaunchKernelGGL(k_histlist, dim3((nhb + 255) / 256), dim3(256), 0, st, p->nzflag, p->nbuse, g, nhb, p->big_list, p->work_ctr + 2, p->psel);
+    hipLaunchKernelGGL(k_histlist, dim3((nhb + 255) / 256), dim3(256), 0, st, p->nzflag, p->ws.nbuse, g, nhb, p->ws.big_list, p->work_ctr + 2, p->psel);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -986,8 +924,8 @@ static uint32_t persistent_grid(const rspt_hip_packer* p, uint32_t nhb, uint32_t
 static int phase_hist(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
     const Geom& g = p->g;
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
-    hipLaunchKernelGGL(k_hist, dim3(persistent_grid(p, nhb, p->hist_grid)), dim3(kEncThreads), 0, st, p->planes, g, p->nzflag, p->hist, p->seghist, p->work_ctr,
-                       p->big_list, p->work_ctr + 2, p->lists, p->listinfo);
+    hipLaunchKernelGGL(k_hist, dim3(persistent_grid(p, nhb, p->hist_grid)), dim3(kEncThreads), 0, st, p->ws.planes, g, p->nzflag, p->ws.hist, p->ws.seghist, p->work_ctr,
+                       p->ws.big_list, p->work_ctr + 2, p->ws.lists, p->ws.listinfo);
     HIPCHK(p, hipGetLastError());  // (a failing launch is reported at its own stage)
     return RSPT_HIP_OK;
 }
@@ -995,8 +933,8 @@ static int phase_hist(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
 static int phase_tree(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
     const Geom& g = p->g;
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
-    hipLaunchKernelGGL(k_tree, dim3((nhb + 3) / 4), dim3(256), 0, st, p->hist, p->planes, g, p->nbuse, p->nzflag, nhb, p->cw, p->tdesc, p->meta, p->seghist, p->segbase,
-                       p->zbuf[p->zset ^ 1], (uint32_t)p->zcap_words, p->psel);
+    hipLaunchKernelGGL(k_tree, dim3((nhb + 3) / 4), dim3(256), 0, st, p->ws.hist, p->ws.planes, g, p->ws.nbuse, p->nzflag, nhb, p->ws.cw, p->ws.tdesc, p->ws.meta, p->ws.seghist, p->ws.segbase,
+                       p->ws.zbuf[p->ws.zset ^ 1], (uint32_t)p->ws.zcap_words, p->psel);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -1004,8 +942,8 @@ static int phase_tree(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
 static int phase_layout(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_stride, uint64_t* d_sizes, hipStream_t st) {
     const Geom& g = p->g;
     WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
-    hipLaunchKernelGGL(k_layout, dim3(B), dim3(256), 0, st, g, p->nbuse, p->meta, p->means, (uint8_t*)d_dst, (uint64_t)dst_stride, p->out_off,
-                       d_sizes, p->crc, p->nzflag, wq, p->big_list, p->small_list, p->plane_dirty, p->dirty_shift, p->psel);
+    hipLaunchKernelGGL(k_layout, dim3(B), dim3(256), 0, st, g, p->ws.nbuse, p->ws.meta, p->ws.means, (uint8_t*)d_dst, (uint64_t)dst_stride, p->ws.out_off,
+                       d_sizes, p->crc, p->nzflag, wq, p->ws.big_list, p->ws.small_list, p->ws.plane_dirty, p->dirty_shift, p->psel);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -1016,8 +954,8 @@ static int phase_small(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_s
     WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
     const uint32_t want = (nhb + kSmallWaves - 1) / kSmallWaves;
     const uint32_t sgrid = (uint32_t)(6 * p->num_cu) < want ? (uint32_t)(6 * p->num_cu) : want;  // ~22 KiB of LDS per workgroup
-    hipLaunchKernelGGL(k_encode_small, dim3(sgrid), dim3(kSmallWaves * 64), 0, ss, p->planes, g, p->nzflag, p->meta, p->cw, p->tdesc, p->out_off,
-                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->small_list, p->ablate, p->h_nsmall);
+    hipLaunchKernelGGL(k_encode_small, dim3(sgrid), dim3(kSmallWaves * 64), 0, ss, p->ws.planes, g, p->nzflag, p->ws.meta, p->ws.cw, p->ws.tdesc, p->ws.out_off,
+                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->ws.small_list, p->ablate, p->h_nsmall);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -1027,15 +965,15 @@ static int phase_encode(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_
     const Geom& g = p->g;
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
     WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
-    hipLaunchKernelGGL(k_encode, dim3(persistent_grid(p, nhb, p->enc_grid)), dim3(kEncThreads), 0, st, p->planes, g, p->nzflag, p->meta, p->cw, p->tdesc, p->out_off,
-                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->big_list, p->segbase, p->lists, p->listinfo, p->stamps, yield);
+    hipLaunchKernelGGL(k_encode, dim3(persistent_grid(p, nhb, p->enc_grid)), dim3(kEncThreads), 0, st, p->ws.planes, g, p->nzflag, p->ws.meta, p->ws.cw, p->ws.tdesc, p->ws.out_off,
+                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->ws.big_list, p->ws.segbase, p->ws.lists, p->ws.listinfo, p->stamps, yield);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
 
 static int ensure_nsmall(rspt_hip_packer* p) {
     if (!p->h_nsmall) {
-        if (hipHostMalloc((void**)&p->h_nsmall, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        if (hipHostMalloc((void**)p->h_nsmall.out(), sizeof(uint32_t), hipHostMallocMapped) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
         *p->h_nsmall = 0xFFFFFFFFu;  // (unknown yet)
     }
     return RSPT_HIP_OK;
@@ -1057,14 +995,14 @@ static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t n
         return RSPT_HIP_OK;
     }
     if ((rc = phase_tree(p, B, st)) != 0) return rc;
-    const int zset_next = p->zset ^ 1;
+    const int zset_next = p->ws.zset ^ 1;
 
     stamp(p, ST_LAYOUT, st);
     if (p->psel & 512u) {  // (diagnostic builds only: stop behind k_tree)
         for (int i = ST_LAYOUT + 1; i <= ST_COUNT; ++i) stamp(p, i, st);
         if (p->profiling) p->ev_valid = true;
-        p->zero_ready[zset_next] = true;
-        p->zset = zset_next;
+        p->ws.zero_ready[zset_next] = true;
+        p->ws.zset = zset_next;
         return RSPT_HIP_OK;
     }
     if ((rc = phase_layout(p, B, d_dst, dst_stride, d_sizes, st)) != 0) return rc;
@@ -1088,8 +1026,8 @@ static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t n
     stamp(p, ST_COUNT, st);
     if (p->profiling) p->ev_valid = true;
     HIPCHK(p, hipGetLastError());
-    p->zero_ready[zset_next] = true;  // every launch went out: the other copy is zero when the next call starts
-    p->zset = zset_next;
+    p->ws.zero_ready[zset_next] = true;  // every launch went out: the other copy is zero when the next call starts
+    p->ws.zset = zset_next;
     return RSPT_HIP_OK;
 }
 
@@ -1109,11 +1047,11 @@ size_t rspt_hip_pack_bound(const rspt_hip_packer* p, size_t nblocks) {
 int rspt_hip_pack_batch_dev(rspt_hip_packer* p, const void* d_dst, size_t dst_stride, const uint64_t* d_sizes, size_t nblocks, void* d_packed,
                             uint64_t* d_total, void* stream) {
     if (!p || !d_dst || !d_sizes || !d_packed || !d_total || nblocks == 0 || nblocks > 65535) return RSPT_HIP_ERR_ARG;
-    if (nblocks > p->cap_blocks) return RSPT_HIP_ERR_ARG;  // the per-stream nb comes from the handle's last compress call of >= nblocks blocks
+    if (nblocks > p->ws.cap_blocks) return RSPT_HIP_ERR_ARG;  // the per-stream nb comes from the handle's last compress call of >= nblocks blocks
     if ((reinterpret_cast<uintptr_t>(d_dst) & 15) || (dst_stride & 15) || (reinterpret_cast<uintptr_t>(d_packed) & 15)) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_pack_index, dim3(1), dim3(1024), 0, st, d_sizes, (uint32_t)nblocks, p->nb_state, p->nbuse, (uint8_t*)d_packed, d_total);
+    hipLaunchKernelGGL(k_pack_index, dim3(1), dim3(1024), 0, st, d_sizes, (uint32_t)nblocks, p->nb_state, p->ws.nbuse, (uint8_t*)d_packed, d_total);
     hipLaunchKernelGGL(k_pack_copy, dim3(32, (unsigned)nblocks), dim3(256), 0, st, (const uint8_t*)d_dst, (uint64_t)dst_stride, (uint32_t)nblocks,
                        (uint8_t*)d_packed);
     HIPCHK(p, hipGetLastError());
@@ -1174,19 +1112,15 @@ int rspt_hip_set_verify(rspt_hip_packer* p, int on) {
 }
 
 static int ensure_host_staging(rspt_hip_packer* p) {
-    const size_t need_dst = rspt_hip_max_compressed_size(p) + 64;
-    if (!p->h_src) {
-        if (hipMalloc(&p->h_src, p->g.block_bytes + 64) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        hipMemset(p->h_src, 0, p->g.block_bytes + 64);
-        hipDeviceSynchronize();  // the memset runs on the null stream; our copies use a non-blocking stream
-    }
-    if (!p->h_size && hipMalloc(&p->h_size, sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-    if (p->h_dst_cap < need_dst) {
-        hipFree(p->h_dst);
-        p->h_dst = nullptr;
-        if (hipMalloc(&p->h_dst, need_dst) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        p->h_dst_cap = need_dst;
-    }
+    if (p->stage.src) return RSPT_HIP_OK;
+    HostStaging s;
+    s.dst_cap = rspt_hip_max_compressed_size(p) + 64;
+    if (hipMalloc(s.src.out(), p->g.block_bytes + 64) != hipSuccess || hipMalloc(s.dst.out(), s.dst_cap) != hipSuccess ||
+        hipMalloc(s.size.out(), sizeof(uint64_t)) != hipSuccess)
+        return RSPT_HIP_ERR_ALLOC;
+    hipMemset(s.src, 0, p->g.block_bytes + 64);
+    hipDeviceSynchronize();  // the memset runs on the null stream; our copies use a non-blocking stream
+    p->stage = std::move(s);
     return RSPT_HIP_OK;
 }
 
@@ -1219,14 +1153,14 @@ int rspt_hip_compress(rspt_hip_packer* p, const void* src_host, void* dst_host, 
     const uint8_t* d_src = (const uint8_t*)device_view_of_host(src_host);
     if (d_src && (reinterpret_cast<uintptr_t>(d_src) & 15)) d_src = nullptr;  // (tile loads are 16-byte aligned chunks)
     if (!d_src) {
-        HIPCHK(p, hipMemcpyAsync(p->h_src, src_host, p->g.block_bytes, hipMemcpyHostToDevice, p->stream));
-        d_src = p->h_src;
+        HIPCHK(p, hipMemcpyAsync(p->stage.src, src_host, p->g.block_bytes, hipMemcpyHostToDevice, p->stream));
+        d_src = p->stage.src;
     }
-    rc = compress_batch_serial(p, d_src, 1, d_dst ? d_dst : p->h_dst, d_dst ? dst_max_len : p->h_dst_cap, p->h_size, p->stream);
+    rc = compress_batch_serial(p, d_src, 1, d_dst ? d_dst : p->stage.dst, d_dst ? dst_max_len : p->stage.dst_cap, p->stage.size, p->stream);
     if (rc) return rc;
     uint64_t sz = 0;
     uint32_t nb_now = 0;
-    HIPCHK(p, hipMemcpyAsync(&sz, p->h_size, sizeof(sz), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(p, hipMemcpyAsync(&sz, p->stage.size, sizeof(sz), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(p, hipMemcpyAsync(&nb_now, p->nb_state, sizeof(nb_now), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(p, hipStreamSynchronize(p->stream));
     if (nb_now >= 1 && nb_now <= 4) p->nb_host = nb_now;  // the next call writes exactly the planes it needs
@@ -1239,39 +1173,48 @@ int rspt_hip_compress(rspt_hip_packer* p, const void* src_host, void* dst_host, 
         return RSPT_HIP_ERR_DST_TOO_SMALL;
     }
     if (!d_dst) {
-        HIPCHK(p, hipMemcpyAsync(dst_host, p->h_dst, (size_t)sz, hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(p, hipMemcpyAsync(dst_host, p->stage.dst, (size_t)sz, hipMemcpyDeviceToHost, p->stream));
         HIPCHK(p, hipStreamSynchronize(p->stream));
     }
     *dst_len = (size_t)sz;
     return RSPT_HIP_OK;
 }
 
+// the copy streams of the many-block pipeline and the feed: made once, by whichever of the two comes first
+static int ensure_copy_streams(rspt_hip_packer* p) {
+    if (!p->m_up && hipStreamCreateWithFlags(p->m_up.out(), hipStreamNonBlocking) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+    if (!p->m_down && hipStreamCreateWithFlags(p->m_down.out(), hipStreamNonBlocking) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+    return RSPT_HIP_OK;
+}
+
+// the staging stride of one compressed stream in a slot
+static size_t slot_stride(const rspt_hip_packer* p) { return (rspt_hip_max_compressed_size(p) + 255) & ~(size_t)255; }
+
+// a slot for n blocks (a caller that gets false drops the slot: nothing half-made is kept)
+static bool alloc_slot(const rspt_hip_packer* p, Slot& s, size_t n) {
+    return hipMalloc(s.d_src.out(), n * p->g.block_bytes + 64) == hipSuccess && hipMalloc(s.d_dst.out(), n * slot_stride(p)) == hipSuccess &&
+           hipMalloc(s.d_sizes.out(), n * sizeof(uint64_t)) == hipSuccess &&
+           hipHostMalloc((void**)s.h_sizes.out(), (n + 1) * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess &&
+           hipEventCreateWithFlags(s.ev_up.out(), hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(s.ev_comp.out(), hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(s.ev_down.out(), hipEventDisableTiming) == hipSuccess;
+}
+
 static int ensure_many(rspt_hip_packer* p) {
-    if (p->m_chunk) return RSPT_HIP_OK;
+    if (p->many.chunk) return RSPT_HIP_OK;
+    int rc = ensure_copy_streams(p);
+    if (rc) return rc;
     // ~64 MiB of samples per chunk: long enough copies for the DMA engines, short enough that the pipeline fills quickly
     size_t chunk = (64ull << 20) / p->g.block_bytes;
     chunk = chunk < 1 ? 1 : chunk > 64 ? 64 : chunk;
-    const size_t stride = (rspt_hip_max_compressed_size(p) + 255) & ~(size_t)255;
-    bool ok = true;
-    for (int i = 0; i < 2; ++i) {
-        ok &= hipMalloc(&p->m_src[i], chunk * p->g.block_bytes + 64) == hipSuccess;
-        ok &= hipMalloc(&p->m_dst[i], chunk * stride) == hipSuccess;
-        ok &= hipMalloc(&p->m_sizes[i], chunk * sizeof(uint64_t)) == hipSuccess;
-        ok &= hipEventCreateWithFlags(&p->m_ev_up[i], hipEventDisableTiming) == hipSuccess;
-        ok &= hipEventCreateWithFlags(&p->m_ev_comp[i], hipEventDisableTiming) == hipSuccess;
-        ok &= hipEventCreateWithFlags(&p->m_ev_down[i], hipEventDisableTiming) == hipSuccess;
-    }
-    for (int i = 0; i < 2; ++i) ok &= hipMalloc(&p->m_idx[i], (4 + 2 * chunk) * sizeof(uint64_t)) == hipSuccess;
-    ok &= hipHostMalloc((void**)&p->m_hsizes, 2 * chunk * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-    ok &= hipHostMalloc((void**)&p->m_hidx, 2 * (4 + 2 * chunk) * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-    if (!p->m_up) ok &= hipStreamCreateWithFlags(&p->m_up, hipStreamNonBlocking) == hipSuccess;  // (rspt_hip_feed_begin may have made them)
-    if (!p->m_down) ok &= hipStreamCreateWithFlags(&p->m_down, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) {  // nothing half-made stays behind: a retry starts from null fields instead of allocating over live pointers
-        free_many(p);
-        return RSPT_HIP_ERR_ALLOC;
-    }
-    p->m_chunk = chunk;
-    p->m_stride = stride;
+    ManyStaging m;
+    bool ok = alloc_slot(p, m.slot[0], chunk) && alloc_slot(p, m.slot[1], chunk);
+    for (int i = 0; i < 2; ++i) ok = ok && hipMalloc(m.idx[i].out(), (4 + 2 * chunk) * sizeof(uint64_t)) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)m.hidx.out(), 2 * (4 + 2 * chunk) * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
+    if (!ok) return RSPT_HIP_ERR_ALLOC;
+    m.chunk = chunk;
+    m.stride = slot_stride(p);
+    p->many = std::move(m);
     return rspt_hip_reserve(p, chunk);
 }
 
@@ -1295,17 +1238,17 @@ int rspt_hip_compress_many(rspt_hip_packer* p, const void* src_host, size_t nblo
 
 static int compress_many_pipeline(rspt_hip_packer* p, const void* src_host, size_t nblocks, void* dst_host, size_t dst_stride, size_t* dst_len) {
     int rc = RSPT_HIP_OK;
-    const size_t C = p->m_chunk, bb = p->g.block_bytes;
+    const size_t C = p->many.chunk, bb = p->g.block_bytes;
     const size_t nchunk = (nblocks + C - 1) / C;
     const uint8_t* src = (const uint8_t*)src_host;
     uint8_t* dst = (uint8_t*)dst_host;
     bool too_small = false;
     // the streams of chunk k leave for the host (exact lengths: its sizes have to be here first)
     auto download = [&](size_t k) -> int {
-        const int slot = (int)(k & 1);
+        Slot& s = p->many.slot[k & 1];
         const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
-        HIPCHK(p, hipEventSynchronize(p->m_ev_comp[slot]));
-        const uint64_t* hs = p->m_hsizes + (size_t)slot * C;
+        HIPCHK(p, hipEventSynchronize(s.ev_comp));
+        const uint64_t* hs = s.h_sizes;
         for (size_t i = 0; i < cnt; ++i) {
             const uint64_t sz = hs[i];
             if ((sz >> 63) || sz > dst_stride) {  // flagged by the device (did not fit the staging stride), or too long for the caller's
@@ -1314,25 +1257,25 @@ static int compress_many_pipeline(rspt_hip_packer* p, const void* src_host, size
                 continue;
             }
             dst_len[first + i] = (size_t)sz;
-            HIPCHK(p, hipMemcpyAsync(dst + (first + i) * dst_stride, p->m_dst[slot] + i * p->m_stride, (size_t)sz, hipMemcpyDeviceToHost, p->m_down));
+            HIPCHK(p, hipMemcpyAsync(dst + (first + i) * dst_stride, s.d_dst + i * p->many.stride, (size_t)sz, hipMemcpyDeviceToHost, p->m_down));
         }
-        HIPCHK(p, hipEventRecord(p->m_ev_down[slot], p->m_down));
+        HIPCHK(p, hipEventRecord(s.ev_down, p->m_down));
         return RSPT_HIP_OK;
     };
     for (size_t k = 0; k < nchunk; ++k) {
-        const int slot = (int)(k & 1);
+        Slot& s = p->many.slot[k & 1];
         const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
         if (k >= 2) {
-            HIPCHK(p, hipStreamWaitEvent(p->m_up, p->m_ev_comp[slot], 0));     // chunk k-2 has been read out of this slot
-            HIPCHK(p, hipStreamWaitEvent(p->stream, p->m_ev_down[slot], 0));  // ... and its streams have left it
+            HIPCHK(p, hipStreamWaitEvent(p->m_up, s.ev_comp, 0));     // chunk k-2 has been read out of this slot
+            HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_down, 0));  // ... and its streams have left it
         }
-        HIPCHK(p, hipMemcpyAsync(p->m_src[slot], src + first * bb, cnt * bb, hipMemcpyHostToDevice, p->m_up));
-        HIPCHK(p, hipEventRecord(p->m_ev_up[slot], p->m_up));
-        HIPCHK(p, hipStreamWaitEvent(p->stream, p->m_ev_up[slot], 0));
-        rc = compress_batch_serial(p, p->m_src[slot], cnt, p->m_dst[slot], p->m_stride, p->m_sizes[slot], p->stream);
+        HIPCHK(p, hipMemcpyAsync(s.d_src, src + first * bb, cnt * bb, hipMemcpyHostToDevice, p->m_up));
+        HIPCHK(p, hipEventRecord(s.ev_up, p->m_up));
+        HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_up, 0));
+        rc = compress_batch_serial(p, s.d_src, cnt, s.d_dst, p->many.stride, s.d_sizes, p->stream);
         if (rc) return rc;
-        HIPCHK(p, hipMemcpyAsync(p->m_hsizes + (size_t)slot * C, p->m_sizes[slot], cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(p, hipEventRecord(p->m_ev_comp[slot], p->stream));
+        HIPCHK(p, hipMemcpyAsync(s.h_sizes, s.d_sizes, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(p, hipEventRecord(s.ev_comp, p->stream));
         if (k >= 1) {
             rc = download(k - 1);
             if (rc) return rc;
@@ -1349,75 +1292,29 @@ static int compress_many_pipeline(rspt_hip_packer* p, const void* src_host, size
 }
 
 // ---- rspt_hip_feed_*: blocks that arrive over time ---------------------------------------------------------------------------
-struct FeedSlot {
-    enum State { FREE, FILLING, COMPRESSING, DOWNLOADING, DONE } state = FREE;
-    uint8_t* d_src = nullptr;
-    uint8_t* d_dst = nullptr;
-    uint64_t* d_sizes = nullptr;
-    uint64_t* h_sizes = nullptr;  // page-locked: [G] stream lengths + [1] nb_state behind this group
-    std::vector<void*> dst_host;
-    std::vector<size_t> dst_cap;
-    size_t count = 0, delivered = 0, first_seq = 0;
-    int error = 0;  // the group's launch failed: every block of it is reported with this status
-    hipEvent_t ev_up = nullptr, ev_comp = nullptr, ev_down = nullptr;
-};
-struct Feed {
-    size_t G = 0, stride = 0;
-    std::vector<FeedSlot> slots;
-    size_t head = 0, tail = 0;  // ring positions: oldest slot not yet FREE; the slot being filled / filled next
-    size_t next_seq = 0;
-};
-
-static void feed_free(rspt_hip_packer* p) {
-    Feed* f = p->feed;
-    if (!f) return;
-    for (auto& s : f->slots) {
-        hipFree(s.d_src);
-        hipFree(s.d_dst);
-        hipFree(s.d_sizes);
-        if (s.h_sizes) hipHostFree(s.h_sizes);
-        if (s.ev_up) hipEventDestroy(s.ev_up);
-        if (s.ev_comp) hipEventDestroy(s.ev_comp);
-        if (s.ev_down) hipEventDestroy(s.ev_down);
-    }
-    delete f;
-    p->feed = nullptr;
-}
-
 int rspt_hip_feed_begin(rspt_hip_packer* p, size_t blocks_per_launch, size_t slots) {
     if (!p || blocks_per_launch == 0 || blocks_per_launch > 4096 || slots < 2 || slots > 64 || p->feed) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
-    if (!p->m_up && hipStreamCreateWithFlags(&p->m_up, hipStreamNonBlocking) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-    if (!p->m_down && hipStreamCreateWithFlags(&p->m_down, hipStreamNonBlocking) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-    int rc = rspt_hip_reserve(p, blocks_per_launch);
+    int rc = ensure_copy_streams(p);
     if (rc) return rc;
-    Feed* f = new (std::nothrow) Feed();
+    rc = rspt_hip_reserve(p, blocks_per_launch);
+    if (rc) return rc;
+    std::unique_ptr<Feed> f(new (std::nothrow) Feed());
     if (!f) return RSPT_HIP_ERR_ALLOC;
-    p->feed = f;
     f->G = blocks_per_launch;
-    f->stride = (rspt_hip_max_compressed_size(p) + 255) & ~(size_t)255;
+    f->stride = slot_stride(p);
     f->slots.resize(slots);
-    bool ok = true;
     for (auto& s : f->slots) {
-        ok &= hipMalloc(&s.d_src, f->G * p->g.block_bytes + 64) == hipSuccess;
-        ok &= hipMalloc(&s.d_dst, f->G * f->stride) == hipSuccess;
-        ok &= hipMalloc(&s.d_sizes, f->G * sizeof(uint64_t)) == hipSuccess;
-        ok &= hipHostMalloc((void**)&s.h_sizes, (f->G + 1) * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-        ok &= hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming) == hipSuccess;
-        ok &= hipEventCreateWithFlags(&s.ev_comp, hipEventDisableTiming) == hipSuccess;
-        ok &= hipEventCreateWithFlags(&s.ev_down, hipEventDisableTiming) == hipSuccess;
+        if (!alloc_slot(p, s, f->G)) return RSPT_HIP_ERR_ALLOC;
         s.dst_host.resize(f->G);
         s.dst_cap.resize(f->G);
     }
-    if (!ok) {
-        feed_free(p);
-        return RSPT_HIP_ERR_ALLOC;
-    }
+    p->feed = std::move(f);
     return RSPT_HIP_OK;
 }
 
 static int feed_launch(rspt_hip_packer* p, FeedSlot& s) {
-    Feed* f = p->feed;
+    Feed* f = p->feed.get();
     HIPCHK(p, hipEventRecord(s.ev_up, p->m_up));
     HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_up, 0));
     const int rc = compress_batch_serial(p, s.d_src, s.count, s.d_dst, f->stride, s.d_sizes, p->stream);
@@ -1432,7 +1329,7 @@ static int feed_launch(rspt_hip_packer* p, FeedSlot& s) {
 int rspt_hip_feed_submit(rspt_hip_packer* p) {
     if (!p || !p->feed) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
-    Feed* f = p->feed;
+    Feed* f = p->feed.get();
     FeedSlot& s = f->slots[f->tail];
     if (s.state != FeedSlot::FILLING || s.count == 0) return RSPT_HIP_OK;
     const int rc = feed_launch(p, s);
@@ -1447,7 +1344,7 @@ int rspt_hip_feed_submit(rspt_hip_packer* p) {
 int rspt_hip_feed_push(rspt_hip_packer* p, const void* src_host, void* dst_host, size_t dst_cap) {
     if (!p || !p->feed || !src_host || !dst_host) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
-    Feed* f = p->feed;
+    Feed* f = p->feed.get();
     FeedSlot& s = f->slots[f->tail];
     if (s.state != FeedSlot::FREE && s.state != FeedSlot::FILLING) return RSPT_HIP_ERR_BUSY;  // the ring is full: poll first
     if (s.state == FeedSlot::FREE) {
@@ -1468,7 +1365,7 @@ int rspt_hip_feed_push(rspt_hip_packer* p, const void* src_host, void* dst_host,
 
 // move every slot as far as it can go without waiting (wait = true: wait for each step instead)
 static int feed_advance(rspt_hip_packer* p, bool wait) {
-    Feed* f = p->feed;
+    Feed* f = p->feed.get();
     const size_t n = f->slots.size();
     for (size_t k = 0; k < n; ++k) {
         FeedSlot& s = f->slots[(f->head + k) % n];
@@ -1508,7 +1405,7 @@ static int feed_advance(rspt_hip_packer* p, bool wait) {
 int rspt_hip_feed_poll(rspt_hip_packer* p, size_t* seq, size_t* dst_len, int* status) {
     if (!p || !p->feed || !seq || !dst_len || !status) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
-    Feed* f = p->feed;
+    Feed* f = p->feed.get();
     const int rc = feed_advance(p, false);
     if (rc) return rc;
     FeedSlot& s = f->slots[f->head];
@@ -1547,7 +1444,7 @@ int rspt_hip_feed_end(rspt_hip_packer* p) {
     hipStreamSynchronize(p->m_up);
     hipStreamSynchronize(p->stream);
     hipStreamSynchronize(p->m_down);  // nothing is copying from or into the caller's buffers any more
-    feed_free(p);
+    p->feed.reset();
     return RSPT_HIP_OK;
 }
 
@@ -1573,17 +1470,17 @@ int rspt_hip_decompress_packed_dev(rspt_hip_packer* p, const void* d_packed, siz
 
 static int decompress_many_pipeline(rspt_hip_packer* p, const void* src_host, size_t src_stride, const size_t* src_len, size_t nblocks, void* dst_host,
                                     size_t* consumed) {
-    const size_t C = p->m_chunk, bb = p->g.block_bytes;
+    const size_t C = p->many.chunk, bb = p->g.block_bytes;
     const size_t nchunk = (nblocks + C - 1) / C;
     const uint8_t* src = (const uint8_t*)src_host;
     uint8_t* dst = (uint8_t*)dst_host;
     bool corrupt = false;
-    // the slots are used the other way round: streams go up into m_dst, blocks come back out of m_src
+    // the slots are used the other way round: streams go up into d_dst, blocks come back out of d_src
     auto finish = [&](size_t k) -> int {
-        const int slot = (int)(k & 1);
+        Slot& s = p->many.slot[k & 1];
         const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
-        HIPCHK(p, hipEventSynchronize(p->m_ev_comp[slot]));
-        const uint64_t* hs = p->m_hsizes + (size_t)slot * C;
+        HIPCHK(p, hipEventSynchronize(s.ev_comp));
+        const uint64_t* hs = s.h_sizes;
         for (size_t i = 0; i < cnt; ++i) {
             const bool bad = (hs[i] >> 63) != 0;
             consumed[first + i] = bad ? 0 : (size_t)hs[i];
@@ -1593,44 +1490,45 @@ static int decompress_many_pipeline(rspt_hip_packer* p, const void* src_host, si
     };
     for (size_t k = 0; k < nchunk; ++k) {
         const int slot = (int)(k & 1);
+        Slot& s = p->many.slot[slot];
         const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
         if (k >= 2) {
-            HIPCHK(p, hipStreamWaitEvent(p->m_up, p->m_ev_comp[slot], 0));     // chunk k-2 has been decoded out of this slot
-            HIPCHK(p, hipStreamWaitEvent(p->stream, p->m_ev_down[slot], 0));  // ... and its blocks have left it
+            HIPCHK(p, hipStreamWaitEvent(p->m_up, s.ev_comp, 0));     // chunk k-2 has been decoded out of this slot
+            HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_down, 0));  // ... and its blocks have left it
         }
         uint64_t* hidx = nullptr;
         if (src_len) {
             // Only src_len[i] bytes of every stream go up, into a slot that still holds an earlier chunk's bytes behind them: the
             // decoder is therefore bounded by each stream's OWN length -- an index over the slot in the container's form
             // (offset, length; nb 0 = the handle's state), checked on the device like any container -- and not by the slot stride.
-            hidx = p->m_hidx + (size_t)slot * (4 + 2 * C);
-            if (k >= 2) HIPCHK(p, hipEventSynchronize(p->m_ev_up[slot]));  // (the upload of chunk k-2 has read this staging index)
+            hidx = p->many.hidx + (size_t)slot * (4 + 2 * C);
+            if (k >= 2) HIPCHK(p, hipEventSynchronize(s.ev_up));  // (the upload of chunk k-2 has read this staging index)
             hidx[0] = 0x4B43415054505352ull;
             hidx[1] = cnt;
-            hidx[2] = (uint64_t)cnt * p->m_stride;
+            hidx[2] = (uint64_t)cnt * p->many.stride;
             hidx[3] = 0;
             for (size_t i = 0; i < cnt; ++i) {
                 const size_t nbytes = src_len[first + i] < src_stride ? src_len[first + i] : src_stride;
-                hidx[4 + 2 * i] = (uint64_t)i * p->m_stride;
+                hidx[4 + 2 * i] = (uint64_t)i * p->many.stride;
                 hidx[4 + 2 * i + 1] = nbytes;
-                if (nbytes) HIPCHK(p, hipMemcpyAsync(p->m_dst[slot] + i * p->m_stride, src + (first + i) * src_stride, nbytes, hipMemcpyHostToDevice, p->m_up));
+                if (nbytes) HIPCHK(p, hipMemcpyAsync(s.d_dst + i * p->many.stride, src + (first + i) * src_stride, nbytes, hipMemcpyHostToDevice, p->m_up));
             }
-            HIPCHK(p, hipMemcpyAsync(p->m_idx[slot], hidx, (4 + 2 * cnt) * sizeof(uint64_t), hipMemcpyHostToDevice, p->m_up));
+            HIPCHK(p, hipMemcpyAsync(p->many.idx[slot], hidx, (4 + 2 * cnt) * sizeof(uint64_t), hipMemcpyHostToDevice, p->m_up));
         } else {
-            HIPCHK(p, hipMemcpy2DAsync(p->m_dst[slot], p->m_stride, src + first * src_stride, src_stride, src_stride, cnt, hipMemcpyHostToDevice, p->m_up));
+            HIPCHK(p, hipMemcpy2DAsync(s.d_dst, p->many.stride, src + first * src_stride, src_stride, src_stride, cnt, hipMemcpyHostToDevice, p->m_up));
         }
-        HIPCHK(p, hipEventRecord(p->m_ev_up[slot], p->m_up));
-        HIPCHK(p, hipStreamWaitEvent(p->stream, p->m_ev_up[slot], 0));
-        const int rc = hidx ? decompress_dev(p, p->m_dst[slot], 0, p->m_idx[slot] + 4, 32 + 16 * cnt + cnt * p->m_stride, cnt, p->m_src[slot],
-                                             p->m_sizes[slot], (void*)p->stream)
-                            : rspt_hip_decompress_batch_dev(p, p->m_dst[slot], p->m_stride, cnt, p->m_src[slot], p->m_sizes[slot], (void*)p->stream);
+        HIPCHK(p, hipEventRecord(s.ev_up, p->m_up));
+        HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_up, 0));
+        const int rc = hidx ? decompress_dev(p, s.d_dst, 0, p->many.idx[slot] + 4, 32 + 16 * cnt + cnt * p->many.stride, cnt, s.d_src,
+                                             s.d_sizes, (void*)p->stream)
+                            : rspt_hip_decompress_batch_dev(p, s.d_dst, p->many.stride, cnt, s.d_src, s.d_sizes, (void*)p->stream);
         if (rc) return rc;
-        HIPCHK(p, hipMemcpyAsync(p->m_hsizes + (size_t)slot * C, p->m_sizes[slot], cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(p, hipEventRecord(p->m_ev_comp[slot], p->stream));
+        HIPCHK(p, hipMemcpyAsync(s.h_sizes, s.d_sizes, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(p, hipEventRecord(s.ev_comp, p->stream));
         // the blocks leave as soon as they are decoded: their size is known beforehand
-        HIPCHK(p, hipStreamWaitEvent(p->m_down, p->m_ev_comp[slot], 0));
-        HIPCHK(p, hipMemcpyAsync(dst + first * bb, p->m_src[slot], cnt * bb, hipMemcpyDeviceToHost, p->m_down));
-        HIPCHK(p, hipEventRecord(p->m_ev_down[slot], p->m_down));
+        HIPCHK(p, hipStreamWaitEvent(p->m_down, s.ev_comp, 0));
+        HIPCHK(p, hipMemcpyAsync(dst + first * bb, s.d_src, cnt * bb, hipMemcpyDeviceToHost, p->m_down));
+        HIPCHK(p, hipEventRecord(s.ev_down, p->m_down));
         if (k >= 1) {
             const int rf = finish(k - 1);
             if (rf) return rf;
@@ -1649,7 +1547,7 @@ int rspt_hip_decompress_many(rspt_hip_packer* p, const void* src_host, size_t sr
     HIPCHK(p, hipSetDevice(p->device));
     int rc = ensure_many(p);
     if (rc) return rc;
-    if (src_stride > p->m_stride) return RSPT_HIP_ERR_ARG;
+    if (src_stride > p->many.stride) return RSPT_HIP_ERR_ARG;
     rc = decompress_many_pipeline(p, src_host, src_stride, src_len, nblocks, dst_host, consumed);
     if (rc != RSPT_HIP_OK && rc != RSPT_HIP_ERR_CORRUPT) {
         hipStreamSynchronize(p->m_up);
@@ -1666,23 +1564,23 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
     int rc = rspt_hip_reserve(p, nblocks);
     if (rc) return rc;
     HIPCHK(p, hipSetDevice(p->device));
-    p->planes_unknown = true;  // the decoded planes land in the compressor's plane workspace
+    p->ws.planes_unknown = true;  // the decoded planes land in the compressor's plane workspace
     hipStream_t st = (hipStream_t)stream;
     {
         const Geom& g = p->g;
         const uint32_t B = (uint32_t)nblocks;
         const uint8_t* src = (const uint8_t*)d_src;
         HIPCHK(p, hipMemsetAsync(d_consumed, 0, nblocks * sizeof(uint64_t), st));
-        hipLaunchKernelGGL(k_dec_frame, dim3((B * kMaxPlanes + 63) / 64), dim3(64), 0, st, src, (uint64_t)src_stride, B, g, p->nb_state, p->blk_off,
-                           d_consumed, p->means, pidx, p->nb_state + 2, (uint64_t)packed_len, p->dec_nb);
+        hipLaunchKernelGGL(k_dec_frame, dim3((B * kMaxPlanes + 63) / 64), dim3(64), 0, st, src, (uint64_t)src_stride, B, g, p->nb_state, p->ws.blk_off,
+                           d_consumed, p->ws.means, pidx, p->nb_state + 2, (uint64_t)packed_len, p->ws.dec_nb);
         {
             // persistent: block costs differ 10x (dense plane 0 against light planes) and the dispatcher places workgroup i
             // on XCD i % 8 in order, so a plain grid ran its second half at a quarter of the slots (tools/census_decode.py)
             // (k_dec_block takes the blocks plane-fastest: dense and light ones in turns)
             const uint32_t total = g.nblk * B * kMaxPlanes;
             const uint32_t want = 2u * (uint32_t)p->num_cu;  // two 1024-thread workgroups (76 KiB of LDS each) per CU
-            hipLaunchKernelGGL(k_dec_block, dim3(want < total ? want : total), dim3(kDecThreads), 0, st, src, (uint64_t)src_stride, g, p->dec_nb, p->blk_off,
-                               p->planes, d_consumed, p->ablate ? p->stamps : nullptr, p->verify ? p->crc : nullptr, pidx, p->nb_state + 2, total);
+            hipLaunchKernelGGL(k_dec_block, dim3(want < total ? want : total), dim3(kDecThreads), 0, st, src, (uint64_t)src_stride, g, p->ws.dec_nb, p->ws.blk_off,
+                               p->ws.planes, d_consumed, p->ablate ? p->stamps : nullptr, p->verify ? p->crc : nullptr, pidx, p->nb_state + 2, total);
         }
         const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_DCT;
         const dim3 tg(p->ntile, B);
@@ -1693,8 +1591,8 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
             const uint32_t nrow = g.N / kRowTile;
             const dim3 rg((g.N / 16 + 255) / 256, B);
             if (xd) {
-                hipLaunchKernelGGL(k_inv_rows, rg, dim3(256), 0, st, p->planes, g, p->dec_nb, nrow, p->rowrec);
-                hipLaunchKernelGGL(k_inv_scan_rows, dim3(B), dim3(1024), 0, st, p->rowrec, nrow, p->txor, p->tsum);
+                hipLaunchKernelGGL(k_inv_rows, rg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, nrow, p->ws.rowrec);
+                hipLaunchKernelGGL(k_inv_scan_rows, dim3(B), dim3(1024), 0, st, p->ws.rowrec, nrow, p->ws.txor, p->ws.tsum);
             }
             if (g.nch <= 16) {
                 if (xd)
@@ -1712,51 +1610,46 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
             return RSPT_HIP_OK;
         }
         if (xd) {
-            hipLaunchKernelGGL((k_inv_tile<0, true>), tg, dim3(256), 0, st, p->planes, g, p->dec_nb, p->ntile, p->txor, p->tsum, p->planar);
-            hipLaunchKernelGGL((k_inv_scan_tiles<true>), dim3(B), dim3(1024), 0, st, p->txor, p->ntile);
-            hipLaunchKernelGGL((k_inv_tile<1, true>), tg, dim3(256), 0, st, p->planes, g, p->dec_nb, p->ntile, p->txor, p->tsum, p->planar);
-            hipLaunchKernelGGL((k_inv_scan_tiles<false>), dim3(B), dim3(1024), 0, st, p->tsum, p->ntile);
-            hipLaunchKernelGGL((k_inv_tile<2, true>), tg, dim3(256), 0, st, p->planes, g, p->dec_nb, p->ntile, p->txor, p->tsum, p->planar);
+            hipLaunchKernelGGL((k_inv_tile<0, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
+            hipLaunchKernelGGL((k_inv_scan_tiles<true>), dim3(B), dim3(1024), 0, st, p->ws.txor, p->ntile);
+            hipLaunchKernelGGL((k_inv_tile<1, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
+            hipLaunchKernelGGL((k_inv_scan_tiles<false>), dim3(B), dim3(1024), 0, st, p->ws.tsum, p->ntile);
+            hipLaunchKernelGGL((k_inv_tile<2, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
         } else {
-            hipLaunchKernelGGL((k_inv_tile<2, false>), tg, dim3(256), 0, st, p->planes, g, p->dec_nb, p->ntile, p->txor, p->tsum, p->planar);
+            hipLaunchKernelGGL((k_inv_tile<2, false>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
         }
-        const int32_t* final_planar = p->planar;
+        const int32_t* final_planar = p->ws.planar;
         if (g.kind == RSPT_HIP_KIND_HADAMARD) {
             const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
             if (g.ns > 65536u) {
                 launch_fwht_big<false>(p, B, st);
             } else if (g.ns == 65536u) {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht64k<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->planar, g, p->means, (uint8_t*)nullptr,
+                hipLaunchKernelGGL((k_fwht64k<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
                                    (uint32_t*)nullptr, 0u);
             } else {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->planar, g, p->means);
+                hipLaunchKernelGGL((k_fwht<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
             }
         } else if (g.kind == RSPT_HIP_KIND_DCT) {
             if (p->dct_fft)
-                launch_dct_fft<false>(p, B, p->planar, p->planar2, st);
+                launch_dct_fft<false>(p, B, p->ws.planar, p->ws.planar2, st);
             else
-                hipLaunchKernelGGL((k_dct<false>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->planar, g,
-                                   p->means, p->cos_tab_t, 0.0, p->idct_scale, p->dct_cs0, p->planar2);
-            final_planar = p->planar2;
+                hipLaunchKernelGGL((k_dct<false>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g,
+                                   p->ws.means, p->cos_tab_t, 0.0, p->idct_scale, p->dct_cs0, p->ws.planar2);
+            final_planar = p->ws.planar2;
         }
         const uint32_t T = min(p->Tn_native, g.ns);
         const uint32_t lds = g.nch * (T + 1) * 4;
         const dim3 ng((g.ns + T - 1) / T, B);
         if (g.bps == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0) {
-            // T4 samples x nch channels in at most 32 KiB of LDS (four workgroups per CU), T4 a multiple of 4
-            uint32_t T4 = (uint32_t)((32768ull / (4ull * g.nch) - 1) & ~3ull);
-            T4 = T4 > 1024 ? 1024 : T4 < 4 ? 4 : T4;
-            if (T4 > g.ns) T4 = g.ns;
+            const uint32_t T4 = tile_i32x4(g);
             hipLaunchKernelGGL(k_planar_native_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, final_planar, g, T4,
                                (uint8_t*)d_dst);
-        } else
-        switch (g.bps) {
-            case 1: hipLaunchKernelGGL((k_planar_native<1>), ng, dim3(256), lds, st, final_planar, g, T, (uint8_t*)d_dst); break;
-            case 2: hipLaunchKernelGGL((k_planar_native<2>), ng, dim3(256), lds, st, final_planar, g, T, (uint8_t*)d_dst); break;
-            case 3: hipLaunchKernelGGL((k_planar_native<3>), ng, dim3(256), lds, st, final_planar, g, T, (uint8_t*)d_dst); break;
-            default: hipLaunchKernelGGL((k_planar_native<4>), ng, dim3(256), lds, st, final_planar, g, T, (uint8_t*)d_dst); break;
+        } else {
+            by_bps(g.bps, [&](auto bps) {
+                hipLaunchKernelGGL((k_planar_native<decltype(bps)::value>), ng, dim3(256), lds, st, final_planar, g, T, (uint8_t*)d_dst);
+            });
         }
         // (big-endian samples: the kernels above reverse each sample as they write it -- g.be)
     }
@@ -1780,21 +1673,21 @@ static int decompress_host(rspt_hip_packer* p, const void* src_host, size_t src_
         uint32_t len;
         memcpy(&len, s + pos, 4);
         pos += 4 + (size_t)len;
-        if (pos > p->h_dst_cap || pos > src_cap) return RSPT_HIP_ERR_CORRUPT;
+        if (pos > p->stage.dst_cap || pos > src_cap) return RSPT_HIP_ERR_CORRUPT;
     }
-    HIPCHK(p, hipMemcpyAsync(p->h_dst, src_host, pos, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(p, hipMemcpyAsync(p->stage.dst, src_host, pos, hipMemcpyHostToDevice, p->stream));
     // a page-locked destination takes the samples straight from the inverse's last kernel (the download is that kernel's
     // stores, across the link): one synchronisation, no copy phase of its own
     uint8_t* d_out = (uint8_t*)device_view_of_host(dst_host);
     if (d_out && (reinterpret_cast<uintptr_t>(d_out) & 15)) d_out = nullptr;
-    rc = rspt_hip_decompress_batch_dev(p, p->h_dst, p->h_dst_cap, 1, d_out ? d_out : p->h_src, p->h_size, (void*)p->stream);
+    rc = rspt_hip_decompress_batch_dev(p, p->stage.dst, p->stage.dst_cap, 1, d_out ? d_out : p->stage.src, p->stage.size, (void*)p->stream);
     if (rc) return rc;
     uint64_t used = 0;
-    HIPCHK(p, hipMemcpyAsync(&used, p->h_size, sizeof(used), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(p, hipMemcpyAsync(&used, p->stage.size, sizeof(used), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(p, hipStreamSynchronize(p->stream));
     if (used >> 63) return RSPT_HIP_ERR_CORRUPT;
     if (!d_out) {
-        HIPCHK(p, hipMemcpyAsync(dst_host, p->h_src, p->g.block_bytes, hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(p, hipMemcpyAsync(dst_host, p->stage.src, p->g.block_bytes, hipMemcpyDeviceToHost, p->stream));
         HIPCHK(p, hipStreamSynchronize(p->stream));
     }
     *src_len = (size_t)used;
@@ -1822,12 +1715,7 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
     c.nc = (uint32_t)nr_coefficients;
     c.init_steps = 4 * init_nr_samples;
     hipStream_t st = (hipStream_t)stream;
-    switch (p->g.bps) {
-        case 1: launch_iir_nc<1>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st); break;
-        case 2: launch_iir_nc<2>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st); break;
-        case 3: launch_iir_nc<3>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st); break;
-        default: launch_iir_nc<4>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st); break;
-    }
+    by_bps(p->g.bps, [&](auto bps) { launch_iir_nc<decltype(bps)::value>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st); });
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -1930,10 +1818,8 @@ int rspt_hip_gather_containers(rspt_hip_packer* p, void* comm, int rank, int wor
     if (!p || !h_totals || world < 1) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
     if (p->gat_world < world) {  // (a few words, kept with the handle)
-        hipFree(p->gat_totals);
-        p->gat_totals = nullptr;
         p->gat_world = 0;
-        if (hipMalloc(&p->gat_totals, (size_t)world * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        if (hipMalloc(p->gat_totals.out(), (size_t)world * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
         p->gat_world = world;
     }
     uint64_t* d_all = p->gat_totals;
@@ -1948,24 +1834,20 @@ int rspt_hip_gather_containers(rspt_hip_packer* p, void* comm, int rank, int wor
 // stream behind an event on `stream`; the host reads them when it posts the payload -- one step later, when they have long
 // arrived -- again on the gather stream, so that the payload of step i overlaps the kernels of step i + 1.
 static int gather_lag_ensure(rspt_hip_packer* p, int world) {
-    if (p->lag_world >= world && p->lag_stream) return RSPT_HIP_OK;
+    if (p->lag.world >= world) return RSPT_HIP_OK;
+    LagGather l;
+    bool ok = hipStreamCreateWithFlags(l.stream.out(), hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; i < 2; ++i) {
-        hipFree(p->lag_dtotals[i]);
-        if (p->lag_htotals[i]) hipHostFree(p->lag_htotals[i]);
-        p->lag_dtotals[i] = p->lag_htotals[i] = nullptr;
+        ok = ok && hipMalloc(l.dtotals[i].out(), (size_t)world * sizeof(uint64_t)) == hipSuccess;
+        ok = ok && hipHostMalloc((void**)l.htotals[i].out(), (size_t)world * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(l.ev_in[i].out(), hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(l.ev_sizes[i].out(), hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(l.ev_payload[i].out(), hipEventDisableTiming) == hipSuccess;
     }
-    p->lag_world = 0;
-    bool ok = true;
-    for (int i = 0; i < 2; ++i) {
-        ok &= hipMalloc(&p->lag_dtotals[i], (size_t)world * sizeof(uint64_t)) == hipSuccess;
-        ok &= hipHostMalloc((void**)&p->lag_htotals[i], (size_t)world * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-        if (!p->lag_ev_in[i]) ok &= hipEventCreateWithFlags(&p->lag_ev_in[i], hipEventDisableTiming) == hipSuccess;
-        if (!p->lag_ev_sizes[i]) ok &= hipEventCreateWithFlags(&p->lag_ev_sizes[i], hipEventDisableTiming) == hipSuccess;
-        if (!p->lag_ev_payload[i]) ok &= hipEventCreateWithFlags(&p->lag_ev_payload[i], hipEventDisableTiming) == hipSuccess;
-    }
-    if (!p->lag_stream) ok &= hipStreamCreateWithFlags(&p->lag_stream, hipStreamNonBlocking) == hipSuccess;
     if (!ok) return RSPT_HIP_ERR_ALLOC;
-    p->lag_world = world;
+    if (p->lag.stream) HIPCHK(p, hipStreamSynchronize(p->lag.stream));  // (nothing may still use the smaller set it replaces)
+    l.world = world;
+    p->lag = std::move(l);
     return RSPT_HIP_OK;
 }
 
@@ -1974,51 +1856,51 @@ int rspt_hip_gather_post_sizes(rspt_hip_packer* p, void* comm, int world, const 
     HIPCHK(p, hipSetDevice(p->device));
     int rc = gather_lag_ensure(p, world);
     if (rc) return rc;
-    HIPCHK(p, hipEventRecord(p->lag_ev_in[slot], (hipStream_t)stream));  // d_total (and the container) are written on `stream`
-    HIPCHK(p, hipStreamWaitEvent(p->lag_stream, p->lag_ev_in[slot], 0));
-    rc = rspt_hip_gather_sizes(p, comm, world, d_total, p->lag_dtotals[slot], p->lag_htotals[slot], (void*)p->lag_stream);
+    HIPCHK(p, hipEventRecord(p->lag.ev_in[slot], (hipStream_t)stream));  // d_total (and the container) are written on `stream`
+    HIPCHK(p, hipStreamWaitEvent(p->lag.stream, p->lag.ev_in[slot], 0));
+    rc = rspt_hip_gather_sizes(p, comm, world, d_total, p->lag.dtotals[slot], p->lag.htotals[slot], (void*)p->lag.stream);
     if (rc) return rc;
-    HIPCHK(p, hipEventRecord(p->lag_ev_sizes[slot], p->lag_stream));
-    p->lag_posted[slot] = true;
+    HIPCHK(p, hipEventRecord(p->lag.ev_sizes[slot], p->lag.stream));
+    p->lag.posted[slot] = true;
     return RSPT_HIP_OK;
 }
 
 int rspt_hip_gather_post_payload(rspt_hip_packer* p, void* comm, int rank, int world, int root, const void* d_packed, int slot, void* d_recv,
                                  size_t recv_stride, uint64_t* h_totals) {
-    if (!p || slot < 0 || slot > 1 || !p->lag_posted[slot] || world > p->lag_world) return RSPT_HIP_ERR_ARG;
+    if (!p || slot < 0 || slot > 1 || !p->lag.posted[slot] || world > p->lag.world) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
-    HIPCHK(p, hipEventSynchronize(p->lag_ev_sizes[slot]));  // (a step old in the steady state: does not wait)
-    p->lag_posted[slot] = false;
-    if (h_totals) memcpy(h_totals, p->lag_htotals[slot], (size_t)world * sizeof(uint64_t));
-    const int rc = rspt_hip_gather_payload(p, comm, rank, world, root, d_packed, p->lag_htotals[slot], d_recv, recv_stride, (void*)p->lag_stream);
+    HIPCHK(p, hipEventSynchronize(p->lag.ev_sizes[slot]));  // (a step old in the steady state: does not wait)
+    p->lag.posted[slot] = false;
+    if (h_totals) memcpy(h_totals, p->lag.htotals[slot], (size_t)world * sizeof(uint64_t));
+    const int rc = rspt_hip_gather_payload(p, comm, rank, world, root, d_packed, p->lag.htotals[slot], d_recv, recv_stride, (void*)p->lag.stream);
     if (rc) return rc;
-    HIPCHK(p, hipEventRecord(p->lag_ev_payload[slot], p->lag_stream));
+    HIPCHK(p, hipEventRecord(p->lag.ev_payload[slot], p->lag.stream));
     return RSPT_HIP_OK;
 }
 
 int rspt_hip_gather_wait(rspt_hip_packer* p, int slot, void* stream) {
     if (!p || slot < 0 || slot > 1) return RSPT_HIP_ERR_ARG;
-    if (!p->lag_ev_payload[slot]) return RSPT_HIP_OK;  // (nothing was ever posted)
+    if (!p->lag.ev_payload[slot]) return RSPT_HIP_OK;  // (nothing was ever posted)
     HIPCHK(p, hipSetDevice(p->device));
-    HIPCHK(p, hipStreamWaitEvent((hipStream_t)stream, p->lag_ev_payload[slot], 0));
+    HIPCHK(p, hipStreamWaitEvent((hipStream_t)stream, p->lag.ev_payload[slot], 0));
     return RSPT_HIP_OK;
 }
 
 long long rspt_hip_debug_read(rspt_hip_packer* p, int which, void* host_buf, size_t cap) {
-    if (!p || !host_buf || p->cap_blocks == 0) return RSPT_HIP_ERR_ARG;
+    if (!p || !host_buf || p->ws.cap_blocks == 0) return RSPT_HIP_ERR_ARG;
     if (hipSetDevice(p->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return RSPT_HIP_ERR_LAUNCH;
     const Geom& g = p->g;
-    const size_t nhb = p->cap_blocks * kMaxPlanes * g.nblk;
+    const size_t nhb = p->ws.cap_blocks * kMaxPlanes * g.nblk;
     const void* src = nullptr;
     size_t n = 0;
     switch (which) {
-        case 0: src = p->planes; n = p->cap_blocks * kMaxPlanes * g.plane_stride; break;
-        case 1: src = p->planar; n = p->cap_blocks * (size_t)g.N * 4; break;
-        case 2: src = p->planar2; n = p->planar2 ? p->cap_blocks * (size_t)g.N * 4 : 0; break;
-        case 3: src = p->hist; n = nhb * kSymStride * 4; break;
-        case 4: src = p->meta; n = nhb * sizeof(BlockMeta); break;
-        case 5: src = p->nbuse; n = p->cap_blocks * 4; break;
-        case 6: src = p->means; n = p->cap_blocks * (size_t)g.hdr_len; break;
+        case 0: src = p->ws.planes; n = p->ws.cap_blocks * kMaxPlanes * g.plane_stride; break;
+        case 1: src = p->ws.planar; n = p->ws.cap_blocks * (size_t)g.N * 4; break;
+        case 2: src = p->ws.planar2; n = p->ws.planar2 ? p->ws.cap_blocks * (size_t)g.N * 4 : 0; break;
+        case 3: src = p->ws.hist; n = nhb * kSymStride * 4; break;
+        case 4: src = p->ws.meta; n = nhb * sizeof(BlockMeta); break;
+        case 5: src = p->ws.nbuse; n = p->ws.cap_blocks * 4; break;
+        case 6: src = p->ws.means; n = p->ws.cap_blocks * (size_t)g.hdr_len; break;
         case 8: src = p->nzflag; n = nhb * 4; break;
         case 7: src = p->stamps; n = (512 * 16 * 8 + 2 * 16384) * sizeof(unsigned long long); break;
         default: return RSPT_HIP_ERR_ARG;

@@ -353,6 +353,46 @@ def test_feed_equals_a_loop_of_compress_calls(api, orc, group, slots, pinned):
         b.close()
 
 
+
+@pytest.mark.gpu
+def test_closing_a_handle_with_an_open_feed_releases_everything(api):
+    """rspt_hip_packer_destroy with a partly filled feed group ends the feed first (the group is still submitted, while the
+    workspace and the constants it needs are there) and only then releases the handle: five such closes of a full-size handle
+    leave device memory where five create / reserve / compress_many / close rounds leave it"""
+    import torch
+
+    bps, nch, ns, group = 4, 64, 65536, 4
+    blocks = [cases._rand_native(nch, ns, bps, 7100 + i, 2000) for i in range(2)]
+
+    def feed_round():
+        pk = api.new_xdelta_hzr(bps, nch, ns, 2)
+        dst = [np.zeros(pk.max_compressed_size, dtype=np.uint8) for _ in blocks]
+        pk.feed_begin(group, 2)
+        for b, d in zip(blocks, dst):
+            assert pk.feed_push(b, d)
+        pk.close()  # no feed_end: (the buffers stay alive until close returns)
+
+    def control_round():
+        pk = api.new_xdelta_hzr(bps, nch, ns, 2)
+        pk.reserve(group)
+        out = np.zeros((len(blocks), pk.max_compressed_size), dtype=np.uint8)
+        pk.compress_many(np.concatenate(blocks), out)
+        pk.close()
+
+    def drift(round_):
+        torch.cuda.synchronize()
+        before = torch.cuda.mem_get_info()[0]
+        for _ in range(5):
+            round_()
+        torch.cuda.synchronize()
+        return before - torch.cuda.mem_get_info()[0]
+
+    control_round()  # (the first launches load the code objects)
+    d_feed = drift(feed_round)
+    d_ctrl = drift(control_round)
+    print("device memory drift over 5 rounds: open feed %d bytes, control %d bytes" % (d_feed, d_ctrl))
+    assert d_feed <= d_ctrl + (64 << 20), (d_feed, d_ctrl)  # (a leaked 2-block workspace of this handle: over 64 MiB a round)
+
 @pytest.mark.gpu
 def test_batch_entry_points_refuse_while_a_feed_is_open(api):
     """the feed owns the handle's plane workspace and copy streams: batch / many-block calls in between return RSPT_HIP_ERR_ARG
