@@ -290,6 +290,23 @@ int rspt_hip_gather_wait(rspt_hip_packer* p, int slot, void* stream);
 int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
                                      int init_nr_samples, int per_channel, void* stream);
 
+/* ---- optional stage in front of compress: the reference's FIR pre-filter ---------------------------------------
+ * i_filter::new_fir(kernel, kernel_size), init_history_values(first sample of the channel, n), filter_opt on every sample
+ * (lib_rspt/lib_filter/fir_filter.cpp), result truncated to int32 and stored in the native sample width, on nblocks
+ * device-resident blocks (interleaved native layout, as for compress), bit-identical with the reference.  With K = kernel_size:
+ *     y[c][t] = ((((0.0 + x[c][t-K+1]*k[0]) + x[c][t-K+2]*k[1]) + ...) + x[c][t]*k[K-1]),    x[c][s < 0] = x[c][0]
+ * every product and sum rounded on its own (no fused multiply-add), in ascending tap order; the truncation is x86-64's: every
+ * NaN, +-inf and |y| >= 2^31 becomes INT32_MIN, and the store keeps the low bps bytes.  Samples are little-endian.
+ * One filter object shared by all channels of a block gives the same result as one filter per channel (the history
+ * initialisation replaces the whole window), so there is no mode to choose.
+ *   d_src, d_dst    nblocks blocks each; d_dst == d_src filters in place, any other overlap is RSPT_HIP_ERR_ARG
+ *   kernel          host array of kernel_size doubles, 1 <= kernel_size <= 65536; read before the call returns
+ * The handle only supplies the shape (bps, nch, ns); any packer kind will do.  nblocks * nch must stay below 2^31, as for the IIR
+ * stage.  Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive calls on one handle
+ * are stream-ordered.  Device and page-locked memory the stage needs belong to the handle. */
+int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                     void* stream);
+
 /* The handle's own (non-blocking) stream, as a hipStream_t. */
 void* rspt_hip_stream(rspt_hip_packer* p);
 

@@ -33,6 +33,7 @@
 #include "transforms.hip"
 #include "decode.hip"
 #include "filter.hip"
+#include "fir.hip"
 
 using namespace rspt;
 
@@ -233,6 +234,29 @@ struct LagGather {
     int world = 0;
 };
 
+// rspt_hip_fir_prefilter_batch_dev: the coefficients of the last kSlots calls (the caller's array may go as soon as a call
+// returns, so each call copies it into page-locked memory and from there, on the call's stream, to the device), and the halo
+// rows of an in-place call.  `done` of a slot is recorded behind the call's kernels; a slot is refilled, a buffer replaced and
+// the handle destroyed only once the calls that use them are past it.
+struct FirStage {
+    static constexpr int kSlots = 4;
+    struct CoefSlot {
+        Pinned<double> host;
+        Dev<double> dev;
+        size_t cap = 0;
+        Event done;
+        bool used = false;
+    };
+    CoefSlot slot[kSlots];
+    int next = 0;
+    Dev<uint8_t> halo;
+    size_t halo_cap = 0;
+    void wait_all() {
+        for (CoefSlot& s : slot)
+            if (s.used) hipEventSynchronize(s.done);
+    }
+};
+
 // The members are constructed in the order they are declared and released in the reverse order (rspt_hip_packer_destroy).
 struct rspt_hip_packer {
     Geom g{};
@@ -296,6 +320,9 @@ struct rspt_hip_packer {
     HostStaging stage;
     ManyStaging many;
     std::unique_ptr<Feed> feed;  // open between rspt_hip_feed_begin and rspt_hip_feed_end
+
+    // ---- FIR pre-filter stage ----
+    FirStage fir;
 
     // ---- gather state ----
     Dev<uint64_t> gat_totals;  // [gat_world]: container lengths of all ranks (rspt_hip_gather_containers)
@@ -519,6 +546,42 @@ static void launch_iir_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const Ii
         case 4: launch_iir<BPS, 4>(p, buf, B, c, per_channel, st); break;
         default: launch_iir<BPS, 5>(p, buf, B, c, per_channel, st); break;
     }
+}
+
+// The FIR stage's decomposition (fir.hip): channel groups of up to 256 lanes' channels, runs of kFirR outputs per lane, and
+// spans along the time axis until there are about four workgroups per CU -- each span at least 4 (K - 1) rows, so that the
+// halo an in-place call stages is at most a quarter of the batch.
+static FirGeom fir_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K) {
+    const Geom& g = p->g;
+    FirGeom f{};
+    f.block_bytes = g.block_bytes;
+    f.stride = g.nch * g.bps;  // (the caller checks the product below before it launches)
+    f.nch = g.nch;
+    f.ns = g.ns;
+    f.K = K;
+    f.cw = g.nch < kFirThreads ? g.nch : kFirThreads;
+    f.subs = kFirThreads / f.cw;
+    f.ncg = (g.nch + f.cw - 1) / f.cw;
+    const uint32_t C = f.subs * kFirR;
+    const uint64_t base_units = (uint64_t)nblocks * f.ncg;
+    const uint64_t want = 4ull * (uint64_t)p->num_cu;
+    uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
+    const uint64_t min_span = K > 1 ? 4ull * (K - 1) : 1;
+    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
+    nsplit = nsplit > max_split ? max_split : nsplit;
+    nsplit = nsplit < 1 ? 1 : nsplit;
+    const uint64_t span = ((g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
+    f.span = (uint32_t)span;
+    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
+    f.units = base_units * f.nsplit;
+    return f;
+}
+
+template <int BPS>
+static void launch_fir(const FirGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st) {
+    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+    if (aligned) hipLaunchKernelGGL((k_fir<BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f);
+    else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f);
 }
 
 template <bool XDELTA, int CG>
@@ -767,6 +830,7 @@ void rspt_hip_packer_destroy(rspt_hip_packer* p) {
     const hipStream_t streams[] = {p->stream, p->side, p->lag.stream};
     for (hipStream_t s : streams)
         if (s) hipStreamSynchronize(s);
+    p->fir.wait_all();  // (the FIR stage runs on the caller's streams)
     delete p;  // the members go in reverse order of construction
 }
 
@@ -1717,6 +1781,71 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
     hipStream_t st = (hipStream_t)stream;
     by_bps(p->g.bps, [&](auto bps) { launch_iir_nc<decltype(bps)::value>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st); });
     HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                     void* stream) {
+    if (!p || !d_src || !d_dst || !kernel || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
+    if (kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+    const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    const bool in_place = s0 == d0;
+    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    const uint64_t subs = kFirThreads / (p->g.nch < kFirThreads ? p->g.nch : kFirThreads);  // (as fir_geom)
+    if (subs * kFirR * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;  // (k_fir's 32-bit row offsets: 2^25 channels and more)
+    const FirGeom f = fir_geom(p, nblocks, (uint32_t)kernel_size);
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    FirStage& fs = p->fir;
+    // the halo of an in-place call with more than one span per block
+    const uint64_t pieces = in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;
+    const uint64_t halo_bytes = pieces * (uint64_t)(kernel_size - 1) * f.stride;
+    if (halo_bytes > fs.halo_cap) {
+        fs.wait_all();  // (no earlier call may still read the buffer being replaced)
+        fs.halo_cap = 0;
+        if (hipMalloc(fs.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        fs.halo_cap = halo_bytes;
+    }
+    // the coefficients: the host waits only when kSlots calls are still ahead on the device
+    FirStage::CoefSlot& cs = fs.slot[fs.next];
+    if (cs.used) HIPCHK(p, hipEventSynchronize(cs.done));
+    if (cs.cap < kernel_size) {
+        cs.cap = 0;
+        if (hipHostMalloc((void**)cs.host.out(), kernel_size * sizeof(double), hipHostMallocDefault) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        if (hipMalloc(cs.dev.out(), kernel_size * sizeof(double)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        cs.cap = kernel_size;
+    }
+    if (!cs.done && hipEventCreateWithFlags(cs.done.out(), hipEventDisableTiming) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+    memcpy(cs.host, kernel, kernel_size * sizeof(double));
+    fs.next = (fs.next + 1) % FirStage::kSlots;
+    cs.used = true;  // (from here on every path records `done`: the copy below reads the page-locked slot)
+    hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && pieces) {
+        const bool words = (s0 % 4) == 0 && (f.block_bytes % 4) == 0 && (f.stride % 4) == 0;
+        const uint32_t grid = (uint32_t)(pieces < 65536 ? pieces : 65536);
+        if (words) hipLaunchKernelGGL(k_fir_halo<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)fs.halo, f, pieces);
+        else hipLaunchKernelGGL(k_fir_halo<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)fs.halo, f, pieces);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        const uint32_t bps = p->g.bps;
+        const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;  // (block_bytes is a multiple of bps)
+        by_bps(bps, [&](auto b) {
+            launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, cs.dev, aligned, st);
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t er = hipEventRecord(cs.done, st);
+    if (er != hipSuccess) {  // (nothing to wait on later: let the device get past the slot now)
+        hipStreamSynchronize(st);
+        cs.used = false;
+    }
+    if (e == hipSuccess) e = er;
+    if (e != hipSuccess) {
+        p->last_hip_error = (int)e;
+        return RSPT_HIP_ERR_LAUNCH;
+    }
     return RSPT_HIP_OK;
 }
 
