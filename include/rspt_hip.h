@@ -307,6 +307,21 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
 int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
                                      void* stream);
 
+/* ---- optional stage in front of compress: the reference's rolling-window median -------------------------------
+ * rolling_window_median<double>(window) (lib_rspt/lib_stat/rolling_window_median.h), one fresh object per channel of every
+ * block, insert((double)x[c][t]) for t = 0 ... ns - 1, (int32_t) of each return value stored in the native sample width, on
+ * nblocks device-resident blocks (interleaved native layout, as for compress), bit-identical with the reference.  With
+ * W = window, lo = max(0, t - W + 1), m = t - lo + 1 and s = sorted(x[c][lo .. t]):
+ *     y[c][t] = m odd ? s[m / 2] : (int32_t)(((int64_t)s[m / 2 - 1] + s[m / 2]) / 2)      (C division: toward zero)
+ * so the first W - 1 outputs of a channel are medians of an expanding window, a window of ns or more is the expanding median
+ * of the whole channel, and window = 1 copies the block.  Samples are little-endian, read sign-extended from bps bytes.
+ *   d_src, d_dst    nblocks blocks each; d_dst == d_src filters in place, any other overlap is RSPT_HIP_ERR_ARG
+ *   window          1 or more (0 is RSPT_HIP_ERR_ARG); windows above 32 need ns <= 2^18 (else RSPT_HIP_ERR_UNSUPPORTED)
+ * The handle only supplies the shape (bps, nch, ns); any packer kind will do.  nblocks * nch must stay below 2^31.
+ * Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive calls on one handle are
+ * stream-ordered.  Device memory the stage needs belongs to the handle. */
+int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream);
+
 /* The handle's own (non-blocking) stream, as a hipStream_t. */
 void* rspt_hip_stream(rspt_hip_packer* p);
 

@@ -24,7 +24,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_packer_destroy", "rspt_hip_compress", "rspt_hip_decompress", "rspt_hip_decompress_bounded", "rspt_hip_max_compressed_size",
     "rspt_hip_block_bytes", "rspt_hip_current_nb", "rspt_hip_set_nb", "rspt_hip_set_verify", "rspt_hip_reserve", "rspt_hip_compress_batch_dev",
     "rspt_hip_decompress_batch_dev", "rspt_hip_decompress_packed_dev", "rspt_hip_pack_bound", "rspt_hip_pack_batch_dev", "rspt_hip_stream", "rspt_hip_synchronize", "rspt_hip_set_profiling", "rspt_hip_stage_count",
-    "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
+    "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
     "rspt_hip_gather_post_sizes", "rspt_hip_gather_post_payload", "rspt_hip_gather_wait",
     "rspt_hip_feed_begin", "rspt_hip_feed_push", "rspt_hip_feed_submit", "rspt_hip_feed_poll", "rspt_hip_feed_flush", "rspt_hip_feed_end",
@@ -112,6 +112,8 @@ def lib():
                                                    C.c_int, C.c_void_p]
     L.rspt_hip_fir_prefilter_batch_dev.restype = C.c_int
     L.rspt_hip_fir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p]
+    L.rspt_hip_median_filter_batch_dev.restype = C.c_int
+    L.rspt_hip_median_filter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.rspt_hip_feed_begin.restype, L.rspt_hip_feed_begin.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]
     L.rspt_hip_feed_push.restype, L.rspt_hip_feed_push.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.rspt_hip_feed_submit.restype, L.rspt_hip_feed_submit.argtypes = C.c_int, [C.c_void_p]
@@ -369,6 +371,22 @@ class SignalPacker:
         rc = self._L.rspt_hip_fir_prefilter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, k.ctypes.data_as(C.POINTER(C.c_double)),
                                                       k.size, st)
         self._check("rspt_hip_fir_prefilter_batch_dev", rc)
+        return out
+
+    def median_filter_batch(self, d_src, window, d_dst=None, stream=None):
+        """The reference's rolling-window median (rolling_window_median<double>(window), one per channel; rspt_hip.h) on
+        device-resident blocks: in place when d_dst is None, else into d_dst (same size, not overlapping d_src); asynchronous.
+        Returns the output."""
+        import torch
+
+        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
+        nblocks = d_src.numel() // self.block_bytes
+        assert nblocks * self.block_bytes == d_src.numel()
+        out = d_src if d_dst is None else d_dst
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == d_src.numel()
+        st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
+        rc = self._L.rspt_hip_median_filter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, int(window), st)
+        self._check("rspt_hip_median_filter_batch_dev", rc)
         return out
 
     def synchronize(self):

@@ -34,6 +34,7 @@
 #include "decode.hip"
 #include "filter.hip"
 #include "fir.hip"
+#include "median.hip"
 
 using namespace rspt;
 
@@ -257,6 +258,22 @@ struct FirStage {
     }
 };
 
+// rspt_hip_median_filter_batch_dev: the halo rows of an in-place short-window call, and the sort buffers of the generic path
+// (two key buffers and the ranks of one piece of the batch).  `done` is recorded behind every call's kernels; a buffer is
+// replaced and the handle destroyed only once the last call is past it.
+struct MedianStage {
+    Dev<uint8_t> halo;
+    size_t halo_cap = 0;
+    Dev<uint64_t> keys_a, keys_b;
+    Dev<uint32_t> rank;
+    size_t key_cap = 0;  // samples of each of the three
+    Event done;
+    bool used = false;
+    void wait() {
+        if (used) hipEventSynchronize(done);
+    }
+};
+
 // The members are constructed in the order they are declared and released in the reverse order (rspt_hip_packer_destroy).
 struct rspt_hip_packer {
     Geom g{};
@@ -323,6 +340,9 @@ struct rspt_hip_packer {
 
     // ---- FIR pre-filter stage ----
     FirStage fir;
+
+    // ---- rolling median stage ----
+    MedianStage med;
 
     // ---- gather state ----
     Dev<uint64_t> gat_totals;  // [gat_world]: container lengths of all ranks (rspt_hip_gather_containers)
@@ -584,6 +604,87 @@ static void launch_fir(const FirGeom& f, const uint8_t* src, uint8_t* dst, const
     else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f);
 }
 
+// The median stage's short-window decomposition (median.hip): as fir_geom, with runs of kMedRun outputs, and spans of at least
+// 4 (W - 1) rows (so that the halo of an in-place call is at most a quarter of the batch).
+static MedGeom med_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t W) {
+    const Geom& g = p->g;
+    MedGeom f{};
+    f.block_bytes = g.block_bytes;
+    f.stride = g.nch * g.bps;
+    f.nch = g.nch;
+    f.ns = g.ns;
+    f.W = W;
+    f.cw = g.nch < kMedThreads ? g.nch : kMedThreads;
+    f.subs = kMedThreads / f.cw;
+    f.ncg = (g.nch + f.cw - 1) / f.cw;
+    const uint32_t C = f.subs * kMedRun;
+    const uint64_t base_units = (uint64_t)nblocks * f.ncg;
+    const uint64_t want = 4ull * (uint64_t)p->num_cu;
+    uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
+    const uint64_t min_span = W > 1 ? 4ull * (W - 1) : 1;
+    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
+    nsplit = nsplit > max_split ? max_split : nsplit;
+    nsplit = nsplit < 1 ? 1 : nsplit;
+    const uint64_t span = ((g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
+    f.span = (uint32_t)span;
+    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
+    f.units = base_units * f.nsplit;
+    return f;
+}
+
+// the k_fir_halo geometry that copies the W - 1 rows in front of every span but the first
+static FirGeom med_halo_geom(const MedGeom& m) {
+    FirGeom f{};
+    f.block_bytes = m.block_bytes;
+    f.stride = m.stride;
+    f.nch = m.nch;
+    f.ns = m.ns;
+    f.K = m.W;
+    f.span = m.span;
+    f.nsplit = m.nsplit;
+    return f;
+}
+
+template <uint32_t N, int BPS>
+static void launch_med_short(const MedGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st) {
+    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+    if (aligned) hipLaunchKernelGGL((k_med_short<N, BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f);
+    else hipLaunchKernelGGL((k_med_short<N, BPS, false>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f);
+}
+
+// The generic path on the pairs [pair0, pair0 + npairs) of the batch: sort (tile sort, merge passes), then walk.
+template <int BPS>
+static hipError_t launch_med_generic(rspt_hip_packer* p, const MedGeom& f, const uint8_t* src, uint8_t* dst, uint64_t pair0, uint64_t npairs,
+                                     bool aligned, hipStream_t st) {
+    MedianStage& ms = p->med;
+    const uint32_t ns = f.ns;
+    const uint32_t tiles = (ns + kMedTile - 1) / kMedTile;
+    uint64_t* a = ms.keys_a;
+    uint64_t* b = ms.keys_b;
+    uint32_t* rank = ms.rank;
+    const bool one_tile = tiles == 1;
+    if (aligned) hipLaunchKernelGGL((k_med_tile_sort<BPS, (BPS == 4 || BPS == 2)>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a,
+                                    one_tile ? rank : nullptr, f, pair0);
+    else hipLaunchKernelGGL((k_med_tile_sort<BPS, false>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a, one_tile ? rank : nullptr, f,
+                            pair0);
+    hipError_t e = hipGetLastError();
+    const uint64_t total = npairs * ns;
+    for (uint32_t width = kMedTile; e == hipSuccess && width < ns; width *= 2) {
+        const bool last = (uint64_t)width * 2 >= ns;
+        hipLaunchKernelGGL(k_med_merge, dim3((uint32_t)((total + kMedThreads - 1) / kMedThreads)), dim3(kMedThreads), 0, st, a, b, last ? rank : nullptr, ns,
+                           width, total);
+        e = hipGetLastError();
+        std::swap(a, b);
+    }
+    if (e != hipSuccess) return e;
+    const uint32_t spans = (ns + kMedSpan - 1) / kMedSpan;
+    const uint32_t n0 = (ns + 31) / 32;
+    const size_t lds = (size_t)(n0 + (n0 + 31) / 32) * sizeof(uint32_t);
+    if (aligned) hipLaunchKernelGGL((k_med_walk<BPS, (BPS == 4 || BPS == 2)>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0);
+    else hipLaunchKernelGGL((k_med_walk<BPS, false>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0);
+    return hipGetLastError();
+}
+
 template <bool XDELTA, int CG>
 static void launch_inv_native(rspt_hip_packer* p, uint32_t B, uint32_t nrow, void* d_dst, hipStream_t st) {
     const Geom& g = p->g;
@@ -830,7 +931,8 @@ void rspt_hip_packer_destroy(rspt_hip_packer* p) {
     const hipStream_t streams[] = {p->stream, p->side, p->lag.stream};
     for (hipStream_t s : streams)
         if (s) hipStreamSynchronize(s);
-    p->fir.wait_all();  // (the FIR stage runs on the caller's streams)
+    p->fir.wait_all();  // (the FIR and median stages run on the caller's streams)
+    p->med.wait();
     delete p;  // the members go in reverse order of construction
 }
 
@@ -1840,6 +1942,98 @@ int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void
     if (er != hipSuccess) {  // (nothing to wait on later: let the device get past the slot now)
         hipStreamSynchronize(st);
         cs.used = false;
+    }
+    if (e == hipSuccess) e = er;
+    if (e != hipSuccess) {
+        p->last_hip_error = (int)e;
+        return RSPT_HIP_ERR_LAUNCH;
+    }
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream) {
+    if (!p || !d_src || !d_dst || window == 0 || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
+    const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    const bool in_place = s0 == d0;
+    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    const Geom& g = p->g;
+    const uint32_t W = (uint32_t)(window < g.ns ? window : g.ns);  // a window of ns or more is the expanding median of the channel
+    if (W > kMedShortMax && g.ns > kMedMaxRanks) return RSPT_HIP_ERR_UNSUPPORTED;  // (the generic path's bitmaps live in LDS)
+    const uint64_t subs = kMedThreads / (g.nch < kMedThreads ? g.nch : kMedThreads);  // (as med_geom)
+    if (subs * kMedRun * g.nch * g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;  // (32-bit row offsets, as the FIR stage)
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (W == 1) {  // a copy, sample width kept
+        if (in_place) return RSPT_HIP_OK;
+        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, st));
+        return RSPT_HIP_OK;
+    }
+    MedianStage& ms = p->med;
+    const MedGeom f = med_geom(p, nblocks, W);
+    const uint32_t bps = g.bps;
+    const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;  // (block_bytes is a multiple of bps)
+    const uint64_t pairs = (uint64_t)nblocks * g.nch;
+    // buffers: the short path's halo (in place, more than one span per block), the generic path's keys and ranks for a piece of
+    // up to 2^25 samples (or one channel)
+    const bool is_short = W <= kMedShortMax;
+    const uint64_t pieces = is_short && in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;
+    const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
+    const uint64_t piece_pairs = is_short ? 0 : std::min<uint64_t>(pairs, std::max<uint64_t>(1, (1ull << 25) / g.ns));
+    const uint64_t key_samples = piece_pairs * g.ns;
+    if (halo_bytes > ms.halo_cap || key_samples > ms.key_cap) {
+        ms.wait();  // (no earlier call may still use a buffer being replaced)
+        if (halo_bytes > ms.halo_cap) {
+            ms.halo_cap = 0;
+            if (hipMalloc(ms.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            ms.halo_cap = halo_bytes;
+        }
+        if (key_samples > ms.key_cap) {
+            ms.key_cap = 0;
+            ms.rank.reset();
+            ms.keys_b.reset();
+            if (hipMalloc(ms.keys_a.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            if (hipMalloc(ms.keys_b.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            if (hipMalloc(ms.rank.out(), key_samples * sizeof(uint32_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            ms.key_cap = key_samples;
+        }
+    }
+    if (!ms.done && hipEventCreateWithFlags(ms.done.out(), hipEventDisableTiming) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+    hipError_t e = hipSuccess;
+    if (is_short) {
+        if (pieces) {
+            const FirGeom h = med_halo_geom(f);
+            const bool words = (s0 % 4) == 0 && (f.block_bytes % 4) == 0 && (f.stride % 4) == 0;
+            const uint32_t grid = (uint32_t)(pieces < 65536 ? pieces : 65536);
+            if (words) hipLaunchKernelGGL(k_fir_halo<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)ms.halo, h, pieces);
+            else hipLaunchKernelGGL(k_fir_halo<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)ms.halo, h, pieces);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            const uint8_t* halo = pieces ? (const uint8_t*)ms.halo : nullptr;
+            by_bps(bps, [&](auto bb) {
+                constexpr int B = decltype(bb)::value;
+                if (W <= 4) launch_med_short<4, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
+                else if (W <= 8) launch_med_short<8, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
+                else if (W <= 16) launch_med_short<16, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
+                else launch_med_short<32, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
+            });
+            e = hipGetLastError();
+        }
+    } else {
+        for (uint64_t pair0 = 0; e == hipSuccess && pair0 < pairs; pair0 += piece_pairs) {
+            const uint64_t np = std::min(piece_pairs, pairs - pair0);
+            e = by_bps(bps, [&](auto bb) {
+                return launch_med_generic<decltype(bb)::value>(p, f, (const uint8_t*)d_src, (uint8_t*)d_dst, pair0, np, aligned, st);
+            });
+        }
+    }
+    const hipError_t er = hipEventRecord(ms.done, st);
+    if (er != hipSuccess) {  // (nothing to wait on later: let the device get past the buffers now)
+        hipStreamSynchronize(st);
+        ms.used = false;
+    } else {
+        ms.used = true;
     }
     if (e == hipSuccess) e = er;
     if (e != hipSuccess) {

@@ -1,0 +1,136 @@
+"""The rolling-median stage: its test inputs and a numpy restatement of the reference.
+
+The reference's rolling_window_median<double>(W) (lib_rspt/lib_stat/rolling_window_median.h), one fresh object per channel,
+returns the true median of the last min(t + 1, W) samples; (int32_t) of it is, in integers,
+    m odd: s[m / 2]        m even: (int32_t)(((int64_t)s[m / 2 - 1] + s[m / 2]) / 2), C division (toward zero)
+with s the sorted window.  The cases feed tests/golden/make_median_record.py, which records the compiled reference's answers
+in tests/golden/median_record.json; the inputs are integer arithmetic or the shipped recordings, and the record holds their crc32.
+"""
+import heapq
+import zlib
+
+import numpy as np
+
+import cases
+from fir_cases import i32_to_native, native_to_i32  # noqa: F401  (the same sample reading as the FIR stage)
+from rspt_amd import synth
+
+INT32_MIN = -(1 << 31)
+INT32_MAX = (1 << 31) - 1
+
+# rspt_test.cpp test_8_rolling_window_median: its 20 inputs and, per window, the first 20 results it expects (doubles)
+REF20 = [1, 2, 3, 4, 5, 6, 7, 8, 4, 5, 6, 5, 4, 3, 2, 1, 1, 1, 1, 9]
+REF20_EXPECTED = {
+    5: [1, 1.5, 2, 2.5, 3, 4, 5, 6, 6, 6, 6, 5, 5, 5, 4, 3, 2, 1, 1, 1],
+    6: [1, 1.5, 2, 2.5, 3, 3.5, 4.5, 5.5, 5.5, 5.5, 6, 5.5, 5, 4.5, 4.5, 3.5, 2.5, 1.5, 1, 1],
+    7: [1, 1.5, 2, 2.5, 3, 3.5, 4, 5, 5, 5, 6, 6, 5, 5, 4, 4, 3, 2, 1, 1],
+    1500: [1, 1.5, 2, 2.5, 3, 3.5, 4, 4.5, 4, 4.5, 5, 5, 5, 4.5, 4, 4, 4, 4, 4, 4],
+}
+
+
+def half_sum(a, b):
+    """(int32_t)(((double)a + b) / 2.0) in integers: the sum is exact, the halving truncates toward zero"""
+    s = np.asarray(a, dtype=np.int64) + np.asarray(b, dtype=np.int64)
+    return np.where(s < 0, -((-s) // 2), s // 2).astype(np.int32)
+
+
+def _expanding(x):
+    """[ns][nch] -> the median of x[0 .. t] per channel (two heaps)"""
+    ns, nch = x.shape
+    y = np.empty((ns, nch), dtype=np.int32)
+    for c in range(nch):
+        low, high = [], []  # max-heap (negated) of the lower half, min-heap of the upper half; len(low) in {len(high), len(high) + 1}
+        col = x[:, c].tolist()
+        out = y[:, c]
+        for t, v in enumerate(col):
+            if low and v > -low[0]:
+                heapq.heappush(high, v)
+            else:
+                heapq.heappush(low, -v)
+            if len(low) > len(high) + 1:
+                heapq.heappush(high, -heapq.heappop(low))
+            elif len(high) > len(low):
+                heapq.heappush(low, -heapq.heappop(high))
+            if len(low) > len(high):
+                out[t] = -low[0]
+            else:
+                a, b = -low[0], high[0]
+                s = a + b
+                out[t] = -((-s) // 2) if s < 0 else s // 2
+    return y
+
+
+def median_i32(x, W):
+    """y[t][c] = the reference's (int32_t) median of x[max(0, t - W + 1) .. t][c]"""
+    x = np.asarray(x, dtype=np.int32)
+    ns, nch = x.shape
+    W = min(int(W), ns)
+    if W == ns:
+        return _expanding(x)
+    y = np.empty((ns, nch), dtype=np.int32)
+    for t in range(W - 1):  # the expanding warm-up
+        s = np.sort(x[: t + 1], axis=0)
+        m = t + 1
+        y[t] = s[m // 2] if m & 1 else half_sum(s[m // 2 - 1], s[m // 2])
+    v = np.lib.stride_tricks.sliding_window_view(x, W, axis=0)  # [ns - W + 1][nch][W]
+    k = [W // 2] if W & 1 else [W // 2 - 1, W // 2]
+    step = max(1, (1 << 22) // (nch * W))
+    for r in range(0, v.shape[0], step):
+        p = np.partition(v[r : r + step], k, axis=-1)
+        y[W - 1 + r : W - 1 + r + p.shape[0]] = p[..., k[0]] if W & 1 else half_sum(p[..., k[0]], p[..., k[1]])
+    return y
+
+
+def median_filter(native, bps, nch, ns, W):
+    """the filtered block in the native sample width (bytes), as rspt_hip_median_filter_batch_dev writes it"""
+    return i32_to_native(median_i32(native_to_i32(native, bps, nch, ns), W), bps)
+
+
+def crc(a):
+    return zlib.crc32(np.ascontiguousarray(a).tobytes())
+
+
+def _i32(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int32)).view(np.uint8)
+
+
+def median_cases():
+    """name, bps, nch, ns, W, data (native bytes)"""
+    ecg = np.frombuffer(synth.ecg_12ch_i32(), dtype=np.uint8)
+    ds = np.frombuffer(synth.data_stream_3ch_i24(), dtype=np.uint8)
+    C = []
+
+    def add(name, bps, nch, ns, W, data):
+        data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).reshape(-1)[: bps * nch * ns])
+        assert data.size == bps * nch * ns, name
+        C.append(dict(name=name, bps=bps, nch=nch, ns=ns, W=W, data=data))
+
+    for W in (5, 6, 7, 1500):
+        add("ref20_w%d" % W, 4, 1, 20, W, _i32(REF20))
+    r5 = cases._rand_native(5, 1000, 2, 81, 1 << 14)
+    for W in (1, 2, 3, 10, 11, 32, 33, 64, 101):
+        add("rand5x1000_i16_w%d" % W, 2, 5, 1000, W, r5)
+    r3 = cases._rand_native(3, 200, 4, 82, 1 << 30)
+    for W in (199, 200, 207):
+        add("rand3x200_i32_w%d" % W, 4, 3, 200, W, r3)
+    add("rand4x1_i32_w3_ns1", 4, 4, 1, 3, cases._rand_native(4, 1, 4, 83, 1 << 20))
+    add("rand1x5000_i32_w257", 4, 1, 5000, 257, cases._rand_native(1, 5000, 4, 84, 1 << 24, walk=True))
+    tern = (cases.hash_i32(7 * 1001, 85, 3) % 3 - 1).astype(np.int8).view(np.uint8)  # 3 distinct values: heavy ties
+    for W in (6, 51):
+        add("ternary7x1001_i8_w%d" % W, 1, 7, 1001, W, tern)
+    add("synth5x3000_i16_w15", 2, 5, 3000, 15, synth.synth_native(5, 3000, 3, bps=2, ecg=True).numpy())
+    for W in (31, 1000):
+        add("ds3x20000_i24_w%d" % W, 3, 3, 20000, W, ds)
+    full = np.where(cases.hash_i32(6 * 3000, 86, 4) >= 0, INT32_MAX, INT32_MIN).astype(np.int32)
+    for W in (4, 40):
+        add("full_scale6x3000_i32_w%d" % W, 4, 6, 3000, W, _i32(full))
+    for W in (101, 1001):
+        add("ecg12x34199_i32_w%d" % W, 4, 12, 34199, W, ecg)
+    return C
+
+
+BIG = dict(name="synth64x65536_i32", bps=4, nch=64, ns=65536, block=7, windows=[101, 65536])
+
+
+def big_data():
+    return synth.synth_native(BIG["nch"], BIG["ns"], BIG["block"], bps=BIG["bps"], ecg=True).numpy()
