@@ -356,9 +356,9 @@ class SignalPacker:
         self._check("rspt_hip_iir_prefilter_batch_dev", rc)
         return d_buf
 
-    def fir_prefilter_batch(self, d_src, kernel, d_dst=None, stream=None):
-        """The reference's FIR pre-filter (i_filter::new_fir, init_history_values, filter_opt; rspt_hip.h) on device-resident
-        blocks: in place when d_dst is None, else into d_dst (same size, not overlapping d_src); asynchronous.  Returns the output."""
+    def _window_call_buffers(self, d_src, d_dst, stream):
+        """(nblocks, output, stream) of a windowed stage's call (fir_prefilter_batch, median_filter_batch): whole blocks of
+        contiguous uint8 on the device, the output d_src itself when d_dst is None, the current stream when stream is None."""
         import torch
 
         assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
@@ -366,8 +366,14 @@ class SignalPacker:
         assert nblocks * self.block_bytes == d_src.numel()
         out = d_src if d_dst is None else d_dst
         assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == d_src.numel()
-        k = np.ascontiguousarray(kernel, dtype=np.float64).reshape(-1)
         st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
+        return nblocks, out, st
+
+    def fir_prefilter_batch(self, d_src, kernel, d_dst=None, stream=None):
+        """The reference's FIR pre-filter (i_filter::new_fir, init_history_values, filter_opt; rspt_hip.h) on device-resident
+        blocks: in place when d_dst is None, else into d_dst (same size, not overlapping d_src); asynchronous.  Returns the output."""
+        nblocks, out, st = self._window_call_buffers(d_src, d_dst, stream)
+        k = np.ascontiguousarray(kernel, dtype=np.float64).reshape(-1)
         rc = self._L.rspt_hip_fir_prefilter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, k.ctypes.data_as(C.POINTER(C.c_double)),
                                                       k.size, st)
         self._check("rspt_hip_fir_prefilter_batch_dev", rc)
@@ -377,14 +383,7 @@ class SignalPacker:
         """The reference's rolling-window median (rolling_window_median<double>(window), one per channel; rspt_hip.h) on
         device-resident blocks: in place when d_dst is None, else into d_dst (same size, not overlapping d_src); asynchronous.
         Returns the output."""
-        import torch
-
-        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
-        nblocks = d_src.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_src.numel()
-        out = d_src if d_dst is None else d_dst
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == d_src.numel()
-        st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
+        nblocks, out, st = self._window_call_buffers(d_src, d_dst, stream)
         rc = self._L.rspt_hip_median_filter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, int(window), st)
         self._check("rspt_hip_median_filter_batch_dev", rc)
         return out

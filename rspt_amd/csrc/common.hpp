@@ -48,6 +48,21 @@ struct Geom {
     uint64_t block_bytes;   // bps*nch*ns
 };
 
+// Decomposition of the sliding-window stages (k_fir, k_med_short; the host's win_geom makes it), passed to their kernels by
+// value: a workgroup takes one span of rows of one channel group of one block, lane <-> (channel, run of consecutive outputs),
+// channel fastest.  k_fir_halo reads the spans from it, the median's generic kernels only the block's shape and K.
+struct WinGeom {
+    uint64_t block_bytes;
+    uint32_t stride;   // nch * bps: one row of the interleaved block (below 2^27: the host checks)
+    uint32_t nch, ns, K;  // K: the window length (FIR taps, median window)
+    uint32_t cw;       // channels of a workgroup
+    uint32_t subs;     // runs per channel in a chunk (chunk = subs * run rows; run = kFirR, kMedRun)
+    uint32_t ncg;      // channel groups: ceil(nch / cw)
+    uint32_t span;     // rows of a workgroup (a multiple of the chunk, >= K - 1 where there is more than one span)
+    uint32_t nsplit;   // spans per block
+    uint64_t units;    // nblocks * ncg * nsplit
+};
+
 // CRC-32C constants for the parallel checksum (tools/kernel_model.py:crc_parallel).
 struct CrcConsts {
     uint32_t table[4][256];  // slice-by-4 LUTs, reflected poly 0x82F63B78; table[0] = hzr_crc32c.c:32
@@ -82,6 +97,32 @@ struct BlockMeta {
 
 __device__ __forceinline__ uint32_t hb_index(const Geom& g, uint32_t b, uint32_t k, uint32_t j) {
     return (b * kMaxPlanes + k) * g.nblk + j;
+}
+
+// Sample access of the pre-filter stages (filter.hip, fir.hip, median.hip): one load / store per sample where the block's base
+// allows it (aligned = the block base is a multiple of 4 for int32, of 2 for int16; rows are then aligned too), bytes otherwise
+// and for int24 / int8
+template <int BPS>
+__device__ __forceinline__ int32_t sample_load(const uint8_t* p, bool aligned) {
+    if (BPS == 4 && aligned) return *reinterpret_cast<const int32_t*>(p);
+    if (BPS == 2 && aligned) return (int32_t) * reinterpret_cast<const int16_t*>(p);
+    if (BPS == 4) return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+    if (BPS == 3) return (int32_t)(((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16)) << 8) >> 8;
+    if (BPS == 2) return (int32_t)(int16_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8));
+    return (int32_t)(int8_t)p[0];
+}
+template <int BPS>
+__device__ __forceinline__ void sample_store(uint8_t* p, int32_t v, bool aligned) {
+    if (BPS == 4 && aligned) {
+        *reinterpret_cast<int32_t*>(p) = v;
+        return;
+    }
+    if (BPS == 2 && aligned) {
+        *reinterpret_cast<int16_t*>(p) = (int16_t)v;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < BPS; ++k) p[k] = (uint8_t)((uint32_t)v >> (8 * k));
 }
 
 // ---------------------------------------------------------------------------

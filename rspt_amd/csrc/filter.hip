@@ -31,31 +31,6 @@ struct IirCoef {
     int32_t init_steps;  // 4 * nr_samples of init_history_values (iir_filter.cpp:106-110)
 };
 
-// sample access: one load / store per sample where the block's base allows it (aligned = the block base is a multiple of 4 for
-// int32, of 2 for int16; rows are then aligned too), bytes otherwise and for int24 / int8
-template <int BPS>
-__device__ __forceinline__ int32_t iir_load(const uint8_t* p, bool aligned) {
-    if (BPS == 4 && aligned) return *reinterpret_cast<const int32_t*>(p);
-    if (BPS == 2 && aligned) return (int32_t) * reinterpret_cast<const int16_t*>(p);
-    if (BPS == 4) return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
-    if (BPS == 3) return (int32_t)(((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16)) << 8) >> 8;
-    if (BPS == 2) return (int32_t)(int16_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8));
-    return (int32_t)(int8_t)p[0];
-}
-template <int BPS>
-__device__ __forceinline__ void iir_store(uint8_t* p, int32_t v, bool aligned) {
-    if (BPS == 4 && aligned) {
-        *reinterpret_cast<int32_t*>(p) = v;
-        return;
-    }
-    if (BPS == 2 && aligned) {
-        *reinterpret_cast<int16_t*>(p) = (int16_t)v;
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < BPS; ++k) p[k] = (uint8_t)((uint32_t)v >> (8 * k));
-}
-
 // The filter state: x[i] = input i samples ago, y[i] = output i samples ago (x_ring_ / y_ring_ of iir_filter.cpp:46-62).
 template <int NC>
 struct IirState {
@@ -108,7 +83,7 @@ struct IirState {
 // scheduler places into the latency of the dependent chain, and the results leave as one store per sample.
 template <int BPS, int NC>
 __device__ __forceinline__ void iir_channel(uint8_t* p, size_t stride, uint32_t ns, const IirCoef& c, IirState<NC>& f, bool aligned) {
-    const double x0 = (double)iir_load<BPS>(p, aligned);
+    const double x0 = (double)sample_load<BPS>(p, aligned);
     {
         int32_t i = 0;
         for (; i < c.init_steps && i < NC - 1; ++i) f.step(c, x0);  // (the x ring still holds older inputs)
@@ -126,13 +101,13 @@ __device__ __forceinline__ void iir_channel(uint8_t* p, size_t stride, uint32_t 
     const uint32_t nfull = ns / CH;
     if (nfull) {
 #pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) cur[e] = iir_load<BPS>(p + (size_t)e * stride, aligned);
+        for (uint32_t e = 0; e < CH; ++e) cur[e] = sample_load<BPS>(p + (size_t)e * stride, aligned);
     }
     for (uint32_t k = 0; k < nfull; ++k) {
         uint8_t* q = p + (size_t)k * CH * stride;
         if (k + 1 < nfull) {
 #pragma unroll
-            for (uint32_t e = 0; e < CH; ++e) nxt[e] = iir_load<BPS>(q + (size_t)(CH + e) * stride, aligned);
+            for (uint32_t e = 0; e < CH; ++e) nxt[e] = sample_load<BPS>(q + (size_t)(CH + e) * stride, aligned);
         }
         // feed-forward sums of the chunk (xs[e + NC - 1] = sample e of the chunk, the NC - 1 values in front come from the state)
         double xs[CH + NC - 1], ff[CH];
@@ -162,20 +137,20 @@ __device__ __forceinline__ void iir_channel(uint8_t* p, size_t stride, uint32_t 
 #pragma unroll
         for (int i = 0; i < NC; ++i) f.x[i] = xs[CH + NC - 2 - i];  // the last NC inputs, newest first
 #pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) iir_store<BPS>(q + (size_t)e * stride, out[e], aligned);
+        for (uint32_t e = 0; e < CH; ++e) sample_store<BPS>(q + (size_t)e * stride, out[e], aligned);
 #pragma unroll
         for (uint32_t e = 0; e < CH; ++e) cur[e] = nxt[e];
     }
     for (uint32_t s = nfull * CH; s < ns; ++s) {  // the tail, sample by sample
         uint8_t* q = p + (size_t)s * stride;
-        f.shift((double)iir_load<BPS>(q, aligned));
+        f.shift((double)sample_load<BPS>(q, aligned));
         double a = (c.d[0] * f.x[0]);
 #pragma unroll
         for (int i = 1; i < NC; ++i) a = (a + (c.d[i] * f.x[i]));
 #pragma unroll
         for (int i = 1; i < NC; ++i) a = (a - (c.n[i] * f.y[i]));
         f.y[0] = a;
-        iir_store<BPS>(q, trunc_i32_c(a), aligned);
+        sample_store<BPS>(q, trunc_i32_c(a), aligned);
     }
 }
 
@@ -254,7 +229,7 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
     constexpr uint32_t kWriter = 1 + kIirProd;
     for (uint32_t sc = 0; sc < nser; ++sc) {
         uint8_t* p = base + (size_t)sc * BPS;
-        const double x0 = (double)iir_load<BPS>(p, aligned);
+        const double x0 = (double)sample_load<BPS>(p, aligned);
         int32_t cur[SET], nxt[SET], nx2[SET];
         // element j of a producer's set in chunk t is sample t * 64 + (role - 1) * 16 - H + j; in front of the channel: the history (x0, see below)
         auto load_set = [&](int32_t (&v)[SET], uint32_t t) {
@@ -262,13 +237,13 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
             if (s0 >= 0 && s0 + (int32_t)SET <= (int32_t)ns) {  // (wave-uniform; all but a channel's first and last sets)
                 const uint8_t* q = p + (size_t)s0 * stride;
 #pragma unroll
-                for (uint32_t j = 0; j < SET; ++j) v[j] = iir_load<BPS>(q + (size_t)j * stride, aligned);
+                for (uint32_t j = 0; j < SET; ++j) v[j] = sample_load<BPS>(q + (size_t)j * stride, aligned);
             } else {
 #pragma unroll
                 for (uint32_t j = 0; j < SET; ++j) {
                     int32_t si = s0 + (int32_t)j;
                     si = si < 0 ? 0 : si >= (int32_t)ns ? (int32_t)ns - 1 : si;  // (clamped: what lies outside is never used as such)
-                    v[j] = iir_load<BPS>(p + (size_t)si * stride, aligned);
+                    v[j] = sample_load<BPS>(p + (size_t)si * stride, aligned);
                 }
             }
         };
@@ -355,18 +330,18 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
 #pragma unroll
                             for (uint32_t e = 0; e < 16; ++e) v[e] = L.out[bi][e0 + e][lane];
 #if defined(IIR_PROBE) && IIR_PROBE == 3  // timing probe (never in the product): one store in sixteen
-                            if (valid) iir_store<BPS>(q + (size_t)e0 * stride, v[0] ^ v[5] ^ v[15], aligned);
+                            if (valid) sample_store<BPS>(q + (size_t)e0 * stride, v[0] ^ v[5] ^ v[15], aligned);
 #else
                             if (valid) {
 #pragma unroll
-                                for (uint32_t e = 0; e < 16; ++e) iir_store<BPS>(q + (size_t)(e0 + e) * stride, v[e], aligned);
+                                for (uint32_t e = 0; e < 16; ++e) sample_store<BPS>(q + (size_t)(e0 + e) * stride, v[e], aligned);
                             }
 #endif
                         }
                     } else {
                         for (uint32_t e = 0; e < cnt; ++e) {
                             const int32_t v = L.out[bi][e][lane];
-                            if (valid) iir_store<BPS>(q + (size_t)e * stride, v, aligned);
+                            if (valid) sample_store<BPS>(q + (size_t)e * stride, v, aligned);
                         }
                     }
                 }

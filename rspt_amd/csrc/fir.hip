@@ -36,18 +36,6 @@ constexpr uint32_t kFirR = 16;          // consecutive outputs per lane (indepen
 constexpr uint32_t kFirThreads = 256;
 constexpr uint32_t kFirMaxTaps = 65536;
 
-struct FirGeom {
-    uint64_t block_bytes;
-    uint32_t stride;   // nch * bps: one row of the interleaved block (below 2^27: the host checks)
-    uint32_t nch, ns, K;
-    uint32_t cw;       // channels of a workgroup
-    uint32_t subs;     // runs of kFirR outputs per channel in a chunk (chunk = subs * kFirR rows)
-    uint32_t ncg;      // channel groups: ceil(nch / cw)
-    uint32_t span;     // rows of a workgroup (a multiple of the chunk, >= K - 1 where there is more than one span)
-    uint32_t nsplit;   // spans per block
-    uint64_t units;    // nblocks * ncg * nsplit
-};
-
 // (int32_t) of the reference's x86-64 build (cvttsd2si): every NaN, +-inf and every value whose truncation does not fit
 // becomes 0x80000000.  (trunc_i32_c in common.hpp serves the other stages and is left as it is.)
 __device__ __forceinline__ int32_t fir_trunc_i32(double y) {
@@ -98,7 +86,7 @@ __device__ __forceinline__ void fir_taps(double (&acc)[R], const double* __restr
 // block's row with the same layout.
 template <int BPS, bool ALIGNED>
 __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* __restrict__ coef,
-                                                    FirGeom g) {
+                                                    WinGeom g) {
     constexpr uint32_t R = kFirR;
     const uint32_t tid = threadIdx.x;
     const uint32_t cl = tid % g.cw, sub = tid / g.cw;
@@ -139,12 +127,12 @@ __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t
             double acc[R];
             if (fast) {
                 const uint8_t* rowbase = src + blk + (uint64_t)(uint32_t)first * stride;
-                fir_taps<R>(acc, coef, K, [&](uint32_t m) { return iir_load<BPS>(rowbase + (uint64_t)m * stride + lane_off, ALIGNED); });
+                fir_taps<R>(acc, coef, K, [&](uint32_t m) { return sample_load<BPS>(rowbase + (uint64_t)m * stride + lane_off, ALIGNED); });
             } else {
                 fir_taps<R>(acc, coef, K, [&](uint32_t m) {
                     const int32_t s = min(max(sb + (int32_t)m, 0), ns1);  // x[s < 0] = x[0]; rows past the block are never used
                     const uintptr_t base = s < lim ? hrow0 : srow0;
-                    return iir_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(uint32_t)s * stride), ALIGNED);
+                    return sample_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(uint32_t)s * stride), ALIGNED);
                 });
             }
             __syncthreads();  // every lane of the workgroup has read the chunk's rows before any of them is overwritten
@@ -153,7 +141,7 @@ __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t
                 const int32_t t0 = a + (int32_t)(subc * R);
 #pragma unroll
                 for (uint32_t r = 0; r < R; ++r)
-                    if (t0 + (int32_t)r < hi) iir_store<BPS>(out + r * stride, fir_trunc_i32(acc[r]), ALIGNED);
+                    if (t0 + (int32_t)r < hi) sample_store<BPS>(out + r * stride, fir_trunc_i32(acc[r]), ALIGNED);
             }
         }
     }
@@ -162,7 +150,7 @@ __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t
 // In place: copy the K - 1 rows in front of every span but the first (rows [w * span - K + 1, w * span), all inside the block
 // because span >= K - 1) into the handle's side buffer, one piece after the other.
 template <bool WORDS>
-__global__ __launch_bounds__(256) void k_fir_halo(const uint8_t* __restrict__ src, uint8_t* __restrict__ halo, FirGeom g, uint64_t pieces) {
+__global__ __launch_bounds__(256) void k_fir_halo(const uint8_t* __restrict__ src, uint8_t* __restrict__ halo, WinGeom g, uint64_t pieces) {
     const uint64_t n = (uint64_t)(g.K - 1) * g.stride;  // bytes of a piece
     for (uint64_t pc = blockIdx.x; pc < pieces; pc += gridDim.x) {
         const uint64_t b = pc / (g.nsplit - 1);

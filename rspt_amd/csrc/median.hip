@@ -73,27 +73,15 @@ __device__ __forceinline__ int32_t med_step(int32_t (&s)[N], uint32_t m, uint32_
     return (int32_t)(sum / 2);
 }
 
-struct MedGeom {
-    uint64_t block_bytes;
-    uint32_t stride;   // nch * bps
-    uint32_t nch, ns, W;
-    uint32_t cw;       // channels of a workgroup
-    uint32_t subs;     // runs per channel in a chunk (chunk = subs * kMedRun rows)
-    uint32_t ncg;      // channel groups
-    uint32_t span;     // rows of a workgroup (a multiple of the chunk)
-    uint32_t nsplit;   // spans per block
-    uint64_t units;    // nblocks * ncg * nsplit
-};
-
 // One span of one channel group of one block per unit.  `halo` is null out of place; in place it holds, for span w >= 1 of
 // block b, the W - 1 rows in front of the span at halo + ((b * (nsplit - 1) + w - 1) * (W - 1)) * stride (k_fir_halo's layout).
 template <uint32_t N, int BPS, bool ALIGNED>
-__global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, uint8_t* dst, const uint8_t* halo, MedGeom g) {
+__global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, uint8_t* dst, const uint8_t* halo, WinGeom g) {
     constexpr uint32_t R = kMedRun, G = 8;
     __shared__ int32_t stage[R * kMedThreads];  // [r][tid]: the chunk's outputs until every read of the chunk is done
     const uint32_t tid = threadIdx.x;
     const uint32_t cl = tid % g.cw, sub = tid / g.cw;
-    const uint32_t W = g.W;
+    const uint32_t W = g.K;
     const uint32_t C = g.subs * R;
     const uint32_t stride = g.stride;
     for (uint64_t u = blockIdx.x; u < g.units; u += gridDim.x) {
@@ -114,7 +102,7 @@ __global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, u
                                     : srow0;
         auto ld = [&](int32_t s) {
             const uintptr_t base = s < lim ? hrow0 : srow0;
-            return iir_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(uint32_t)s * stride), ALIGNED);
+            return sample_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(uint32_t)s * stride), ALIGNED);
         };
         const uint32_t nq = ((uint32_t)(hi - lo) + C - 1) / C;
         for (uint32_t q = nq; q-- > 0;) {
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, u
             if (live) {
                 uint8_t* out = dst + blk + chc * BPS;
                 for (int32_t t = t0; t < e; ++t)
-                    iir_store<BPS>(out + (uint64_t)(uint32_t)t * stride, stage[(uint32_t)(t - t0) * kMedThreads + tid], ALIGNED);
+                    sample_store<BPS>(out + (uint64_t)(uint32_t)t * stride, stage[(uint32_t)(t - t0) * kMedThreads + tid], ALIGNED);
             }
             __syncthreads();  // (the stage is refilled by the next chunk)
         }
@@ -179,7 +167,7 @@ __device__ __forceinline__ int32_t med_key_value(uint64_t k) { return (int32_t)(
 // Pair p = (block, channel) of the piece [pair0, pair0 + npairs): keys[p][0 .. ns) sorted in runs of kMedTile.  With
 // `rank` (ns <= kMedTile: the sort is complete), also rank[p][t] = position of sample t.
 template <int BPS, bool ALIGNED>
-__global__ __launch_bounds__(kMedThreads) void k_med_tile_sort(const uint8_t* src, uint64_t* keys, uint32_t* rank, MedGeom g, uint64_t pair0) {
+__global__ __launch_bounds__(kMedThreads) void k_med_tile_sort(const uint8_t* src, uint64_t* keys, uint32_t* rank, WinGeom g, uint64_t pair0) {
     __shared__ uint64_t sk[kMedTile];
     const uint32_t tiles = (g.ns + kMedTile - 1) / kMedTile;
     const uint64_t p = blockIdx.x / tiles;
@@ -189,7 +177,7 @@ __global__ __launch_bounds__(kMedThreads) void k_med_tile_sort(const uint8_t* sr
     const uint8_t* base = src + (pair / g.nch) * g.block_bytes + ch * BPS;
     for (uint32_t i = threadIdx.x; i < kMedTile; i += kMedThreads) {
         const uint32_t t = t0 + i;
-        sk[i] = t < g.ns ? med_key(iir_load<BPS>(base + (uint64_t)t * g.stride, ALIGNED), t) : ~0ull;  // (padding sorts last)
+        sk[i] = t < g.ns ? med_key(sample_load<BPS>(base + (uint64_t)t * g.stride, ALIGNED), t) : ~0ull;  // (padding sorts last)
     }
     __syncthreads();
     for (uint32_t k = 2; k <= kMedTile; k <<= 1) {
@@ -298,12 +286,12 @@ struct MedBits {
 // One wave per (pair of the piece, span of kMedSpan outputs).  keys: the piece's sorted keys, rank: their inverse.  The state
 // (p = rank of the lower median, below = window members with a smaller rank) is computed alike by every lane.
 template <int BPS, bool ALIGNED>
-__global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ rank, uint8_t* dst, MedGeom g,
+__global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ rank, uint8_t* dst, WinGeom g,
                                                  uint64_t pair0) {
     extern __shared__ uint32_t med_lds[];
     const uint32_t lane = threadIdx.x;
     const bool writer = lane == 0;
-    const uint32_t ns = g.ns, W = g.W;
+    const uint32_t ns = g.ns, W = g.K;
     const uint32_t spans = (ns + kMedSpan - 1) / kMedSpan;
     const uint64_t p = blockIdx.x / spans;
     const uint32_t lo = (blockIdx.x % spans) * kMedSpan;
@@ -405,7 +393,7 @@ __global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ ke
         }
         if (lane < n) {
             const int64_t sum = (int64_t)med_key_value(kp[myp]) + (int64_t)med_key_value(kp[myq]);
-            iir_store<BPS>(out + (uint64_t)t * g.stride, (int32_t)(sum / 2), ALIGNED);
+            sample_store<BPS>(out + (uint64_t)t * g.stride, (int32_t)(sum / 2), ALIGNED);
         }
     }
 }

@@ -235,43 +235,52 @@ struct LagGather {
     int world = 0;
 };
 
+// The last call of a windowed stage (FIR, median) that uses a set of the handle's buffers: `done` is recorded behind the call's
+// kernels on the caller's stream, and the buffers are refilled, replaced or released only once the device is past it.
+struct LastCall {
+    Event done;  // made by the first call
+    bool used = false;
+    bool make_event() { return done || hipEventCreateWithFlags(done.out(), hipEventDisableTiming) == hipSuccess; }
+    hipError_t wait() const { return used ? hipEventSynchronize(done) : hipSuccess; }
+    // (a failed record leaves nothing to wait on later: the device gets past the buffers now)
+    hipError_t record(hipStream_t st) {
+        const hipError_t e = hipEventRecord(done, st);
+        if (e != hipSuccess) hipStreamSynchronize(st);
+        used = e == hipSuccess;
+        return e;
+    }
+};
+
 // rspt_hip_fir_prefilter_batch_dev: the coefficients of the last kSlots calls (the caller's array may go as soon as a call
 // returns, so each call copies it into page-locked memory and from there, on the call's stream, to the device), and the halo
-// rows of an in-place call.  `done` of a slot is recorded behind the call's kernels; a slot is refilled, a buffer replaced and
-// the handle destroyed only once the calls that use them are past it.
+// rows of an in-place call.  A slot is refilled only once its last call is past it; the halo is replaced, and the handle
+// destroyed, only once the calls of all slots are.
 struct FirStage {
     static constexpr int kSlots = 4;
     struct CoefSlot {
         Pinned<double> host;
         Dev<double> dev;
         size_t cap = 0;
-        Event done;
-        bool used = false;
+        LastCall last;
     };
     CoefSlot slot[kSlots];
     int next = 0;
     Dev<uint8_t> halo;
     size_t halo_cap = 0;
     void wait_all() {
-        for (CoefSlot& s : slot)
-            if (s.used) hipEventSynchronize(s.done);
+        for (CoefSlot& s : slot) s.last.wait();
     }
 };
 
 // rspt_hip_median_filter_batch_dev: the halo rows of an in-place short-window call, and the sort buffers of the generic path
-// (two key buffers and the ranks of one piece of the batch).  `done` is recorded behind every call's kernels; a buffer is
-// replaced and the handle destroyed only once the last call is past it.
+// (two key buffers and the ranks of one piece of the batch), all behind the stage's last call.
 struct MedianStage {
     Dev<uint8_t> halo;
     size_t halo_cap = 0;
     Dev<uint64_t> keys_a, keys_b;
     Dev<uint32_t> rank;
     size_t key_cap = 0;  // samples of each of the three
-    Event done;
-    bool used = false;
-    void wait() {
-        if (used) hipEventSynchronize(done);
-    }
+    LastCall last;
 };
 
 // The members are constructed in the order they are declared and released in the reverse order (rspt_hip_packer_destroy).
@@ -568,21 +577,22 @@ static void launch_iir_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const Ii
     }
 }
 
-// The FIR stage's decomposition (fir.hip): channel groups of up to 256 lanes' channels, runs of kFirR outputs per lane, and
-// spans along the time axis until there are about four workgroups per CU -- each span at least 4 (K - 1) rows, so that the
-// halo an in-place call stages is at most a quarter of the batch.
-static FirGeom fir_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K) {
+// The decomposition of a sliding-window stage (WinGeom): channel groups of up to `threads` lanes' channels, runs of `run`
+// outputs per lane (kFirThreads / kFirR, kMedThreads / kMedRun), and spans along the time axis until there are about four
+// workgroups per CU -- each span at least 4 (K - 1) rows, so that the halo an in-place call stages is at most a quarter of the
+// batch.
+static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run) {
     const Geom& g = p->g;
-    FirGeom f{};
+    WinGeom f{};
     f.block_bytes = g.block_bytes;
-    f.stride = g.nch * g.bps;  // (the caller checks the product below before it launches)
+    f.stride = g.nch * g.bps;  // (window_call_checks checks the chunk's row offsets before a launch)
     f.nch = g.nch;
     f.ns = g.ns;
     f.K = K;
-    f.cw = g.nch < kFirThreads ? g.nch : kFirThreads;
-    f.subs = kFirThreads / f.cw;
+    f.cw = g.nch < threads ? g.nch : threads;
+    f.subs = threads / f.cw;
     f.ncg = (g.nch + f.cw - 1) / f.cw;
-    const uint32_t C = f.subs * kFirR;
+    const uint32_t C = f.subs * run;
     const uint64_t base_units = (uint64_t)nblocks * f.ncg;
     const uint64_t want = 4ull * (uint64_t)p->num_cu;
     uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
@@ -598,55 +608,14 @@ static FirGeom fir_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K) {
 }
 
 template <int BPS>
-static void launch_fir(const FirGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st) {
+static void launch_fir(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st) {
     const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
     if (aligned) hipLaunchKernelGGL((k_fir<BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f);
     else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f);
 }
 
-// The median stage's short-window decomposition (median.hip): as fir_geom, with runs of kMedRun outputs, and spans of at least
-// 4 (W - 1) rows (so that the halo of an in-place call is at most a quarter of the batch).
-static MedGeom med_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t W) {
-    const Geom& g = p->g;
-    MedGeom f{};
-    f.block_bytes = g.block_bytes;
-    f.stride = g.nch * g.bps;
-    f.nch = g.nch;
-    f.ns = g.ns;
-    f.W = W;
-    f.cw = g.nch < kMedThreads ? g.nch : kMedThreads;
-    f.subs = kMedThreads / f.cw;
-    f.ncg = (g.nch + f.cw - 1) / f.cw;
-    const uint32_t C = f.subs * kMedRun;
-    const uint64_t base_units = (uint64_t)nblocks * f.ncg;
-    const uint64_t want = 4ull * (uint64_t)p->num_cu;
-    uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
-    const uint64_t min_span = W > 1 ? 4ull * (W - 1) : 1;
-    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
-    nsplit = nsplit > max_split ? max_split : nsplit;
-    nsplit = nsplit < 1 ? 1 : nsplit;
-    const uint64_t span = ((g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
-    f.span = (uint32_t)span;
-    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
-    f.units = base_units * f.nsplit;
-    return f;
-}
-
-// the k_fir_halo geometry that copies the W - 1 rows in front of every span but the first
-static FirGeom med_halo_geom(const MedGeom& m) {
-    FirGeom f{};
-    f.block_bytes = m.block_bytes;
-    f.stride = m.stride;
-    f.nch = m.nch;
-    f.ns = m.ns;
-    f.K = m.W;
-    f.span = m.span;
-    f.nsplit = m.nsplit;
-    return f;
-}
-
 template <uint32_t N, int BPS>
-static void launch_med_short(const MedGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st) {
+static void launch_med_short(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st) {
     const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
     if (aligned) hipLaunchKernelGGL((k_med_short<N, BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f);
     else hipLaunchKernelGGL((k_med_short<N, BPS, false>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f);
@@ -654,7 +623,7 @@ static void launch_med_short(const MedGeom& f, const uint8_t* src, uint8_t* dst,
 
 // The generic path on the pairs [pair0, pair0 + npairs) of the batch: sort (tile sort, merge passes), then walk.
 template <int BPS>
-static hipError_t launch_med_generic(rspt_hip_packer* p, const MedGeom& f, const uint8_t* src, uint8_t* dst, uint64_t pair0, uint64_t npairs,
+static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const uint8_t* src, uint8_t* dst, uint64_t pair0, uint64_t npairs,
                                      bool aligned, hipStream_t st) {
     MedianStage& ms = p->med;
     const uint32_t ns = f.ns;
@@ -932,7 +901,7 @@ void rspt_hip_packer_destroy(rspt_hip_packer* p) {
     for (hipStream_t s : streams)
         if (s) hipStreamSynchronize(s);
     p->fir.wait_all();  // (the FIR and median stages run on the caller's streams)
-    p->med.wait();
+    p->med.last.wait();
     delete p;  // the members go in reverse order of construction
 }
 
@@ -1886,22 +1855,56 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
     return RSPT_HIP_OK;
 }
 
-int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
-                                     void* stream) {
-    if (!p || !d_src || !d_dst || !kernel || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
-    if (kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+// The checks of both windowed entry points, in the order they return: a null handle or buffer, nblocks == 0 or nblocks * nch
+// >= 2^31, and buffers that overlap without being the same (ERR_ARG); then a chunk's row offsets, which k_fir and k_med_short
+// compute in 32 bits (ERR_UNSUPPORTED: 2^24 channels and more).  Sets the geometry for the window K and whether the call is in place.
+static int window_call_checks(const rspt_hip_packer* p, const void* d_src, const void* d_dst, size_t nblocks, uint32_t K, uint32_t threads,
+                              uint32_t run, WinGeom* f, bool* in_place) {
+    if (!p || !d_src || !d_dst || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
     const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    const bool in_place = s0 == d0;
-    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
-    const uint64_t subs = kFirThreads / (p->g.nch < kFirThreads ? p->g.nch : kFirThreads);  // (as fir_geom)
-    if (subs * kFirR * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;  // (k_fir's 32-bit row offsets: 2^25 channels and more)
-    const FirGeom f = fir_geom(p, nblocks, (uint32_t)kernel_size);
+    *in_place = s0 == d0;
+    if (!*in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    *f = win_geom(p, nblocks, K, threads, run);
+    if ((uint64_t)f->subs * run * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;
+    return RSPT_HIP_OK;
+}
+
+// The halo of an in-place call with more than one span per block: the K - 1 rows in front of every span but the first,
+// nblocks (nsplit - 1) pieces of (K - 1) rows.
+static uint64_t halo_pieces(const WinGeom& f, size_t nblocks, bool in_place) {
+    return in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;
+}
+
+static hipError_t launch_halo(const WinGeom& f, const void* d_src, uint8_t* halo, uint64_t pieces, hipStream_t st) {
+    const bool words = (reinterpret_cast<uintptr_t>(d_src) % 4) == 0 && (f.block_bytes % 4) == 0 && (f.stride % 4) == 0;
+    const uint32_t grid = (uint32_t)(pieces < 65536 ? pieces : 65536);
+    if (words) hipLaunchKernelGGL(k_fir_halo<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, halo, f, pieces);
+    else hipLaunchKernelGGL(k_fir_halo<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, halo, f, pieces);
+    return hipGetLastError();
+}
+
+// The end of a windowed call from the point where it has enqueued work: record `last` behind it, and report the first error.
+static int finish_window_call(rspt_hip_packer* p, LastCall& last, hipError_t e, hipStream_t st) {
+    const hipError_t er = last.record(st);
+    if (e == hipSuccess) e = er;
+    if (e != hipSuccess) {
+        p->last_hip_error = (int)e;
+        return RSPT_HIP_ERR_LAUNCH;
+    }
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                     void* stream) {
+    if (!kernel || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+    WinGeom f;
+    bool in_place;
+    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, (uint32_t)kernel_size, kFirThreads, kFirR, &f, &in_place)) return rc;
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     FirStage& fs = p->fir;
-    // the halo of an in-place call with more than one span per block
-    const uint64_t pieces = in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;
+    const uint64_t pieces = halo_pieces(f, nblocks, in_place);
     const uint64_t halo_bytes = pieces * (uint64_t)(kernel_size - 1) * f.stride;
     if (halo_bytes > fs.halo_cap) {
         fs.wait_all();  // (no earlier call may still read the buffer being replaced)
@@ -1911,78 +1914,59 @@ int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void
     }
     // the coefficients: the host waits only when kSlots calls are still ahead on the device
     FirStage::CoefSlot& cs = fs.slot[fs.next];
-    if (cs.used) HIPCHK(p, hipEventSynchronize(cs.done));
+    HIPCHK(p, cs.last.wait());
     if (cs.cap < kernel_size) {
         cs.cap = 0;
         if (hipHostMalloc((void**)cs.host.out(), kernel_size * sizeof(double), hipHostMallocDefault) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
         if (hipMalloc(cs.dev.out(), kernel_size * sizeof(double)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
         cs.cap = kernel_size;
     }
-    if (!cs.done && hipEventCreateWithFlags(cs.done.out(), hipEventDisableTiming) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+    if (!cs.last.make_event()) return RSPT_HIP_ERR_ALLOC;
     memcpy(cs.host, kernel, kernel_size * sizeof(double));
     fs.next = (fs.next + 1) % FirStage::kSlots;
-    cs.used = true;  // (from here on every path records `done`: the copy below reads the page-locked slot)
+    // (from here on every path ends in finish_window_call, which records `last`: the copy below reads the page-locked slot)
     hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && pieces) {
-        const bool words = (s0 % 4) == 0 && (f.block_bytes % 4) == 0 && (f.stride % 4) == 0;
-        const uint32_t grid = (uint32_t)(pieces < 65536 ? pieces : 65536);
-        if (words) hipLaunchKernelGGL(k_fir_halo<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)fs.halo, f, pieces);
-        else hipLaunchKernelGGL(k_fir_halo<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)fs.halo, f, pieces);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess && pieces) e = launch_halo(f, d_src, fs.halo, pieces, st);
     if (e == hipSuccess) {
         const uint32_t bps = p->g.bps;
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
         const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;  // (block_bytes is a multiple of bps)
         by_bps(bps, [&](auto b) {
             launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, cs.dev, aligned, st);
         });
         e = hipGetLastError();
     }
-    const hipError_t er = hipEventRecord(cs.done, st);
-    if (er != hipSuccess) {  // (nothing to wait on later: let the device get past the slot now)
-        hipStreamSynchronize(st);
-        cs.used = false;
-    }
-    if (e == hipSuccess) e = er;
-    if (e != hipSuccess) {
-        p->last_hip_error = (int)e;
-        return RSPT_HIP_ERR_LAUNCH;
-    }
-    return RSPT_HIP_OK;
+    return finish_window_call(p, cs.last, e, st);
 }
 
 int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream) {
-    if (!p || !d_src || !d_dst || window == 0 || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
-    const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    const bool in_place = s0 == d0;
-    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    if (!p || window == 0) return RSPT_HIP_ERR_ARG;
     const Geom& g = p->g;
     const uint32_t W = (uint32_t)(window < g.ns ? window : g.ns);  // a window of ns or more is the expanding median of the channel
+    WinGeom f;
+    bool in_place;
+    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, W, kMedThreads, kMedRun, &f, &in_place)) return rc;
     if (W > kMedShortMax && g.ns > kMedMaxRanks) return RSPT_HIP_ERR_UNSUPPORTED;  // (the generic path's bitmaps live in LDS)
-    const uint64_t subs = kMedThreads / (g.nch < kMedThreads ? g.nch : kMedThreads);  // (as med_geom)
-    if (subs * kMedRun * g.nch * g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;  // (32-bit row offsets, as the FIR stage)
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     if (W == 1) {  // a copy, sample width kept
         if (in_place) return RSPT_HIP_OK;
-        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, st));
+        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, (uint64_t)nblocks * g.block_bytes, hipMemcpyDeviceToDevice, st));
         return RSPT_HIP_OK;
     }
     MedianStage& ms = p->med;
-    const MedGeom f = med_geom(p, nblocks, W);
     const uint32_t bps = g.bps;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
     const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;  // (block_bytes is a multiple of bps)
     const uint64_t pairs = (uint64_t)nblocks * g.nch;
-    // buffers: the short path's halo (in place, more than one span per block), the generic path's keys and ranks for a piece of
-    // up to 2^25 samples (or one channel)
+    // buffers: the short path's halo, the generic path's keys and ranks for a piece of up to 2^25 samples (or one channel)
     const bool is_short = W <= kMedShortMax;
-    const uint64_t pieces = is_short && in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;
+    const uint64_t pieces = is_short ? halo_pieces(f, nblocks, in_place) : 0;
     const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
     const uint64_t piece_pairs = is_short ? 0 : std::min<uint64_t>(pairs, std::max<uint64_t>(1, (1ull << 25) / g.ns));
     const uint64_t key_samples = piece_pairs * g.ns;
     if (halo_bytes > ms.halo_cap || key_samples > ms.key_cap) {
-        ms.wait();  // (no earlier call may still use a buffer being replaced)
+        ms.last.wait();  // (no earlier call may still use a buffer being replaced)
         if (halo_bytes > ms.halo_cap) {
             ms.halo_cap = 0;
             if (hipMalloc(ms.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
@@ -1998,17 +1982,10 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
             ms.key_cap = key_samples;
         }
     }
-    if (!ms.done && hipEventCreateWithFlags(ms.done.out(), hipEventDisableTiming) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+    if (!ms.last.make_event()) return RSPT_HIP_ERR_ALLOC;
     hipError_t e = hipSuccess;
     if (is_short) {
-        if (pieces) {
-            const FirGeom h = med_halo_geom(f);
-            const bool words = (s0 % 4) == 0 && (f.block_bytes % 4) == 0 && (f.stride % 4) == 0;
-            const uint32_t grid = (uint32_t)(pieces < 65536 ? pieces : 65536);
-            if (words) hipLaunchKernelGGL(k_fir_halo<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)ms.halo, h, pieces);
-            else hipLaunchKernelGGL(k_fir_halo<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, (uint8_t*)ms.halo, h, pieces);
-            e = hipGetLastError();
-        }
+        if (pieces) e = launch_halo(f, d_src, ms.halo, pieces, st);
         if (e == hipSuccess) {
             const uint8_t* halo = pieces ? (const uint8_t*)ms.halo : nullptr;
             by_bps(bps, [&](auto bb) {
@@ -2028,19 +2005,7 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
             });
         }
     }
-    const hipError_t er = hipEventRecord(ms.done, st);
-    if (er != hipSuccess) {  // (nothing to wait on later: let the device get past the buffers now)
-        hipStreamSynchronize(st);
-        ms.used = false;
-    } else {
-        ms.used = true;
-    }
-    if (e == hipSuccess) e = er;
-    if (e != hipSuccess) {
-        p->last_hip_error = (int)e;
-        return RSPT_HIP_ERR_LAUNCH;
-    }
-    return RSPT_HIP_OK;
+    return finish_window_call(p, ms.last, e, st);
 }
 
 // ---- multi-GPU gather over RCCL.  RCCL is bound at run time: a process that never gathers (the C++ drop-in on one
