@@ -282,6 +282,11 @@ int rspt_hip_gather_wait(rspt_hip_packer* p, int slot, void* stream);
  * (n, d, nr_coefficients), init_history_values(first sample of the channel, init_nr_samples), filter_opt on every sample
  * (lib_rspt/lib_filter/iir_filter.cpp:46-116), result truncated to int32 and stored back in the native sample width --
  * nblocks device-resident blocks (interleaved native layout, as for compress), IN PLACE, bit-identical with the reference.
+ * Every product and sum is rounded on its own (no fused multiply-add); the truncation is x86-64's: every NaN, +-inf and
+ * |y| >= 2^31 becomes INT32_MIN (an unstable filter or non-finite coefficients reach them), and the store keeps the low bps
+ * bytes.  Samples are read and written little-endian, whatever rspt_hip_set_byte_order says.
+ *   init_nr_samples 0 .. 2^28: filter() runs 4 * init_nr_samples times on the channel's first sample before the channel
+ *   nblocks         1 or more; nblocks * nch must stay below 2^31 (else RSPT_HIP_ERR_ARG, as for a bad order or history)
  *   n, d            host arrays of nr_coefficients doubles (2..5): feedback (n[0] unused) and feed-forward coefficients
  *   per_channel     0: one filter object for all channels of a block, its state running on from channel to channel, as
  *                      in the reference's harness (the channels of a block are then a serial chain: one thread per block);

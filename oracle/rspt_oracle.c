@@ -791,6 +791,12 @@ static void add_means(orc_packer* p, const uint8_t* header) {
     }
 }
 
+/* (int32_t)y as the reference's x86-64 build computes it (cvttsd2si): every NaN, +-inf and every value whose truncation
+ * does not fit becomes INT32_MIN.  In C the out-of-range cast is undefined, so it is spelt out. */
+static int32_t orc_trunc_i32(double y) {
+    return (y > -2147483649.0 && y < 2147483648.0) ? (int32_t)y : INT32_MIN; /* (false for NaN) */
+}
+
 /* signal_packer_dct.cpp:76-87.  `int * float` multiplies in float, the sum
  * runs in double, the scale is (double)Cs*sqrt(2/n)/128, the store truncates. */
 static void dct_forward(const orc_packer* p, const int32_t* src, int32_t* dst) {
@@ -805,7 +811,7 @@ static void dct_forward(const orc_packer* p, const int32_t* src, int32_t* dst) {
         }
         float cs = i ? 1.0f : cs0;
         sum *= cs * ratio1 / 128.0;
-        dst[i] = (int32_t)sum;
+        dst[i] = orc_trunc_i32(sum);
     }
 }
 
@@ -822,7 +828,7 @@ static void dct_inverse(const orc_packer* p, const int32_t* src, int32_t* dst) {
             sum += prod;
         }
         sum *= ratio1 * 128.0;
-        dst[i] = (int32_t)sum;
+        dst[i] = orc_trunc_i32(sum);
     }
 }
 
@@ -1040,7 +1046,7 @@ int orc_iir_prefilter_native(uint8_t* native, size_t bps, size_t nch, size_t ns,
             memset(f.y, 0, sizeof f.y);
         }
         for (int i = 0; i < 4 * init_nr_samples; ++i) iir_filter(&f, (double)row[0]); /* init_history_values :106-110 */
-        for (size_t s = 0; s < ns; ++s) row[s] = (int32_t)iir_filter_opt(&f, (double)row[s]);
+        for (size_t s = 0; s < ns; ++s) row[s] = orc_trunc_i32(iir_filter_opt(&f, (double)row[s]));
     }
     orc_i32_to_native(native, planar, ns, nch, bps);
     free(planar);

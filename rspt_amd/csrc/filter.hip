@@ -284,9 +284,12 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
                         // sixteen samples at a time: their feed-forward sums are read from LDS together (one wait), the results
                         // written together -- per sample the wave issues the recurrence and little else.  The truncation is the
                         // GPU's own (saturating) conversion here; C's as the reference's build does it (trunc_i32_c, common.hpp) differs
-                        // from it only where the double is out of range, i.e. where this conversion returns INT_MAX: the largest
-                        // result of the chunk is tracked (half an instruction per sample instead of two), and a chunk that
-                        // reaches INT_MAX -- full-scale input through a filter that overshoots -- is done once more, exactly.
+                        // from it only where this conversion returns INT_MAX (the double is >= 2^31 or +inf) and where the double
+                        // is NaN (this conversion: 0).  The largest result of the chunk is tracked (half an instruction per sample
+                        // instead of two); a NaN needs no tracking, because it is absorbing: the step after it multiplies it by
+                        // n[1], so every later output is NaN and the chunk's last one says whether any was (its high word: an
+                        // all-ones exponent, NaN or +-inf).  A chunk that reaches INT_MAX -- full-scale input through a filter that
+                        // overshoots -- or ends non-finite -- an unstable filter, non-finite coefficients -- is done once more, exactly.
                         double ysave[NC];
 #pragma unroll
                         for (int i = 0; i < NC; ++i) ysave[i] = f.y[i];
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
 #pragma unroll
                             for (uint32_t e = 0; e < 16; ++e) L.out[bi][e0 + e][lane] = o[e];
                         }
-                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx == 0x7FFFFFFF) != 0ull, 0)) {
+                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx == 0x7FFFFFFF || (__double2hiint(f.y[0]) & 0x7FF00000) == 0x7FF00000) != 0ull, 0)) {
 #pragma unroll
                             for (int i = 0; i < NC; ++i) f.y[i] = ysave[i];
 #pragma unroll 1

@@ -36,12 +36,6 @@ constexpr uint32_t kFirR = 16;          // consecutive outputs per lane (indepen
 constexpr uint32_t kFirThreads = 256;
 constexpr uint32_t kFirMaxTaps = 65536;
 
-// (int32_t) of the reference's x86-64 build (cvttsd2si): every NaN, +-inf and every value whose truncation does not fit
-// becomes 0x80000000.  (trunc_i32_c in common.hpp serves the other stages and is left as it is.)
-__device__ __forceinline__ int32_t fir_trunc_i32(double y) {
-    return (y > -2147483649.0 && y < 2147483648.0) ? (int32_t)y : (int32_t)0x80000000u;
-}
-
 // The K taps of R consecutive outputs of one lane, ld(m) = window element m (the sample of row sb + m, see k_fir).  Tap i of
 // output r reads element r + i + skip, where skip = G R - K virtual taps in front of the first group make every group R wide.
 // Group g multiplies the window elements [g R, g R + 2 R) -- held in two halves lo, hi -- while the loads of the half after
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t
                 const int32_t t0 = a + (int32_t)(subc * R);
 #pragma unroll
                 for (uint32_t r = 0; r < R; ++r)
-                    if (t0 + (int32_t)r < hi) sample_store<BPS>(out + r * stride, fir_trunc_i32(acc[r]), ALIGNED);
+                    if (t0 + (int32_t)r < hi) sample_store<BPS>(out + r * stride, trunc_i32_c(acc[r]), ALIGNED);  // (x86-64's (int32_t): common.hpp)
             }
         }
     }

@@ -76,14 +76,18 @@ def pick_shape(r, kind):
 
 def iir_case(seed, r):
     """the pre-filter stage (rspt_test.cpp:116-136): both modes against the restatement, amplitudes up to full scale (the truncated
-    double overflows int32 there: the reference's conversion, not the GPU's saturating one, decides what comes out)"""
+    double overflows int32 there: the reference's conversion, not the GPU's saturating one, decides what comes out), every
+    filter order, and now and then an unstable filter (outputs past 2^31, then +-inf, then NaN: INT32_MIN, as in the reference)"""
+    import iir_cases
+
     bps = int(r.choice([4, 4, 3, 2]))
     nch, ns = int(r.integers(1, 20)), int(r.choice([1, 5, 100, 2000, 2047, 2048, 2049, 5000, 40000]))
-    n, d = (cases.IIR_BANDPASS, cases.IIR_BANDPASS, cases.IIR_LOWPASS, cases.IIR_HIGHPASS)[int(r.integers(0, 4))]
+    n, d = (cases.IIR_BANDPASS, cases.IIR_BANDPASS, cases.IIR_LOWPASS, cases.IIR_HIGHPASS, iir_cases.STABLE[2], iir_cases.STABLE[4],
+            iir_cases.unstable(1.5), iir_cases.unstable(1.01, nc=4))[int(r.integers(0, 8))]
     init = int(r.choice([0, 3, 2000]))
     lim = 1 << (8 * bps - 1)
     amp = int(min(lim - 1, r.choice([100, 1 << 14, 1 << 21, 1 << 29, (1 << 31) - 1])))
-    desc = "seed %d: iir int%d %dch x %d init %d amp %d" % (seed, 8 * bps, nch, ns, init, amp)
+    desc = "seed %d: iir int%d %dch x %d n %s d %s init %d amp %d" % (seed, 8 * bps, nch, ns, list(n), list(d), init, amp)
     data = cases._rand_native(nch, ns, bps, int(r.integers(1 << 30)), amp, walk=bool(r.integers(2)))
     pk = api.new_xdelta_hzr(bps, nch, ns, 3)
     bad = []

@@ -109,6 +109,34 @@ def test_gpu_prefilter_rejects_bad_orders(api):
     pk.close()
 
 
+@pytest.mark.gpu
+def test_gpu_prefilter_rejects_bad_arguments(api):
+    """a negative history, one past 2^28, no blocks, and nblocks * nch >= 2^31 (the first count past the limit, for an odd
+    and an even channel count) are refused before anything is launched: the buffer is left as it was"""
+    import ctypes as C
+
+    import torch
+
+    for nch in (3, 2):
+        pk = api.new_xdelta_hzr(4, nch, 64, 3)
+        d_buf = torch.full((4 * pk.block_bytes,), 7, dtype=torch.uint8, device="cuda")
+        n, d = np.array([1.0, -0.5]), np.array([0.25, 0.25])
+        dp = C.POINTER(C.c_double)
+        st = torch.cuda.current_stream().cuda_stream
+
+        def call(nblocks, init):
+            return pk._L.rspt_hip_iir_prefilter_batch_dev(pk._h, d_buf.data_ptr(), nblocks, n.ctypes.data_as(dp), d.ctypes.data_as(dp), 2, init, 0, st)
+
+        for nblocks, init in ((4, -1), (4, (1 << 28) + 1), (0, 1), (0x7FFFFFFF // nch + 1, 1), (1 << 40, 1)):
+            assert nblocks * nch >= 1 << 31 or nblocks == 0 or init < 0 or init > 1 << 28
+            assert call(nblocks, init) == -1, (nch, nblocks, init)
+        torch.cuda.synchronize()
+        assert (d_buf == 7).all()
+        assert call(4, 256) == 0 and call(4, 0) == 0  # (in range: accepted)
+        torch.cuda.synchronize()
+        pk.close()
+
+
 # ---- the full-size block: the size at which fused multiply-adds once flipped output counts (no small fixture ever did) ----
 BIG_MODES = [("shared", 2000), ("per_channel", 2000), ("shared", 0), ("per_channel", 0)]
 
