@@ -327,6 +327,58 @@ int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void
  * stream-ordered.  Device memory the stage needs belongs to the handle. */
 int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream);
 
+/* ---- the reference's Butterworth designer (host only: no GPU, no handle) -------------------------------------------
+ * create_filter_iir(num, den, butterworth, type, order, sampling_rate, cutoff_low, cutoff_high) of
+ * lib_rspt/lib_filter/iir_filter_design.cpp, bit-identical with the reference's x86-64 build (same libm calls, same order of
+ * operations, no contraction).  type: high_pass 0, low_pass 1, band_pass 2, band_stop 3 (the reference never reads `kind`).
+ *   order 2, low/high pass    3 coefficients (cutoff_low)       order 2, band_pass        5 (4th order, cutoff_low .. high)
+ *   order 1, low/high pass    2 coefficients (cutoff_low)       order 1, band_pass        3
+ * As in the reference, order 1 band_stop gives the first-order band-pass, order 2 band_stop is refused, and so is every other
+ * order, sampling_rate <= 0, cutoff_low <= 0 and (band-pass) cutoff_high <= cutoff_low: RSPT_HIP_ERR_ARG, with num, den and
+ * *nr_coefficients untouched (so is a type outside 0..3).  num and den must hold 5 doubles each.  num is the feed-forward
+ * side and den (den[0] = 1) the feedback side; i_filter::new_iir(n, d) takes them the other way round, so the IIR stage's
+ * call is rspt_hip_iir_prefilter_batch_dev(..., n = den, d = num, nr_coefficients, ...). */
+int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff_low, double cutoff_high, double* num, double* den,
+                        size_t* nr_coefficients);
+
+/* ---- the reference's R-peak detectors ------------------------------------------------------------------------------
+ * One detector per (block, channel) of nblocks device-resident blocks (the handle's shape, interleaved native layout; any
+ * packer kind; samples little-endian, read sign-extended from bps bytes; d_src is only read), fed (double) of every sample:
+ *   variant 0  ONLINE      peak_detector::detect             band-pass order 2 (10-20 Hz, 5 coefficients), integrator
+ *                                                            low-pass order 2 (3 Hz), threshold low-pass order 2 (0.15 Hz), A = 25
+ *   variant 1  ONLINE_1ST  peak_detector_1st_order::detect   band-pass order 1 (10-20 Hz, 3 coefficients), integrator order 1, A = 25
+ *   variant 2  OFFLINE_FW  peak_detector_offline::detect_fw  band-pass order 1 (15-25 Hz), integrator order 1, A = 70
+ * bit-identical with the reference's x86-64 build.  Per sample x: s = integrator(bp(x)^2), h = threshold(s), then the
+ * reference's state machine with threshold_ratio 1.5, reference_ratio 0.5, peak_attenuation = 1 / (1 + A / fs) and
+ * nr_slope_samples = (int)(100 fs / 1000).  Each filter is y0 = d0 x0 + d1 x1 + ... - n1 y1 - n2 y2 ..., left to right, with
+ * the designer's numerator as d and its denominator as n (rspt_hip_design_iir), every product and sum rounded on its own.
+ * Only the band-pass is initialised: 4 * (int)fs calls of filter(x) -- ONLINE / ONLINE_1ST at the sample where the sample
+ * index is 0 (the first sample of a fresh detector), OFFLINE_FW with the first sample of every block, on whatever state the
+ * filter holds.  With nr_slope_samples 0 (fs < 10) a detector fires on every sample whose counter is 0; with 1 (10 <= fs < 20)
+ * it never fires.
+ *   event         a sample at which detect() takes its marker branch, whatever the value: marker_val, or the integrator output
+ *                 s where marker_val == -1.0 (so a marker of 0.0 or an s of 0.0 is still an event)
+ *   d_count       [nblocks][nch] uint32: the exact number of events of each (block, channel); required
+ *   d_index       [nblocks][nch][max_peaks] int32: the sample index within the block (the detect() call, not shifted back) of
+ *   d_value       [nblocks][nch][max_peaks] double: ... and the value of the first max_peaks events; later events are counted
+ *                 only.  max_peaks = 0 gives counts alone (d_index / d_value may then be NULL; else both are required)
+ *   d_sig, d_threshold  optional [nblocks][ns][nch] doubles: s and h of every sample (peak_sample / threshold_sample;
+ *                 filt_signal / threshold_signal for OFFLINE_FW); NULL for none (both or neither)
+ *   d_state       NULL: a fresh detector per (block, channel).  Else a caller-owned device buffer of
+ *                 rspt_hip_peak_state_bytes bytes holding one detector per channel: channel c runs through blocks
+ *                 0 .. nblocks - 1 in order and on across calls (OFFLINE_FW: every block is one detect_fw call on the object).
+ *                 All-zero bytes are a fresh detector.  A state belongs to the variant and sampling rate that made it.  Only
+ *                 nch lanes run in this mode, so it is slower than fresh mode on few channels.  The sample index is the
+ *                 reference's int: it wraps after 2^31 samples of a channel, and after 2^32 the band-pass history runs again.
+ * RSPT_HIP_ERR_ARG for an unknown variant, a sampling_rate that is not finite, <= 0 or > 2^20, a NULL d_src or d_count,
+ * max_peaks > 0 with a NULL d_index or d_value, only one of d_sig / d_threshold, nblocks == 0, nblocks * nch >= 2^31, or
+ * max_peaks above 2^32.  Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive calls
+ * on one handle are stream-ordered.  The stage allocates nothing of its own. */
+int rspt_hip_peak_state_bytes(rspt_hip_packer* p, size_t* bytes); /* one detector per channel: nch * 208 bytes */
+int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
+                                   void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
+                                   double* d_threshold, void* stream);
+
 /* The handle's own (non-blocking) stream, as a hipStream_t. */
 void* rspt_hip_stream(rspt_hip_packer* p);
 

@@ -24,7 +24,8 @@ C_ABI_SYMBOLS = [
     "rspt_hip_packer_destroy", "rspt_hip_compress", "rspt_hip_decompress", "rspt_hip_decompress_bounded", "rspt_hip_max_compressed_size",
     "rspt_hip_block_bytes", "rspt_hip_current_nb", "rspt_hip_set_nb", "rspt_hip_set_verify", "rspt_hip_reserve", "rspt_hip_compress_batch_dev",
     "rspt_hip_decompress_batch_dev", "rspt_hip_decompress_packed_dev", "rspt_hip_pack_bound", "rspt_hip_pack_batch_dev", "rspt_hip_stream", "rspt_hip_synchronize", "rspt_hip_set_profiling", "rspt_hip_stage_count",
-    "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
+    "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_design_iir",
+    "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
     "rspt_hip_gather_post_sizes", "rspt_hip_gather_post_payload", "rspt_hip_gather_wait",
     "rspt_hip_feed_begin", "rspt_hip_feed_push", "rspt_hip_feed_submit", "rspt_hip_feed_poll", "rspt_hip_feed_flush", "rspt_hip_feed_end",
@@ -114,6 +115,12 @@ def lib():
     L.rspt_hip_fir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p]
     L.rspt_hip_median_filter_batch_dev.restype = C.c_int
     L.rspt_hip_median_filter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.rspt_hip_design_iir.restype = C.c_int
+    L.rspt_hip_design_iir.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _szp]
+    L.rspt_hip_peak_state_bytes.restype, L.rspt_hip_peak_state_bytes.argtypes = C.c_int, [C.c_void_p, _szp]
+    L.rspt_hip_peak_detect_batch_dev.restype = C.c_int
+    L.rspt_hip_peak_detect_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rspt_hip_feed_begin.restype, L.rspt_hip_feed_begin.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]
     L.rspt_hip_feed_push.restype, L.rspt_hip_feed_push.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.rspt_hip_feed_submit.restype, L.rspt_hip_feed_submit.argtypes = C.c_int, [C.c_void_p]
@@ -388,6 +395,49 @@ class SignalPacker:
         self._check("rspt_hip_median_filter_batch_dev", rc)
         return out
 
+    def peak_state_bytes(self):
+        n = C.c_size_t()
+        self._check("rspt_hip_peak_state_bytes", self._L.rspt_hip_peak_state_bytes(self._h, C.byref(n)))
+        return n.value
+
+    def peak_state(self, device=None):
+        """A zeroed state for peak_detect_batch(state=...): a fresh detector for every channel (uint8 device tensor)."""
+        import torch
+
+        return torch.zeros(self.peak_state_bytes(), dtype=torch.uint8, device=device if device is not None else "cuda")
+
+    def peak_detect_batch(self, d_src, variant="online", sampling_rate=None, marker_val=1.0, max_peaks=64, state=None, traces=False, stream=None):
+        """The reference's R-peak detectors (peak_detector.h; rspt_hip.h: rspt_hip_peak_detect_batch_dev) on device-resident
+        blocks, which are only read.  variant: "online" (peak_detector), "online_1st" (peak_detector_1st_order) or "offline_fw"
+        (peak_detector_offline::detect_fw).  state: None for a fresh detector per (block, channel), or a peak_state() tensor that
+        carries one detector per channel through the blocks and across calls (of one variant and sampling rate).  Asynchronous.
+        Returns (count [nblocks, nch] int32, index [nblocks, nch, max_peaks] int32, value [nblocks, nch, max_peaks] float64) and,
+        with traces, (sig, threshold) [nblocks, ns, nch] float64 as well."""
+        import torch
+
+        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
+        if sampling_rate is None:
+            raise ValueError("peak_detect_batch: sampling_rate is required")
+        nblocks = d_src.numel() // self.block_bytes
+        assert nblocks * self.block_bytes == d_src.numel()
+        v = PEAK_VARIANTS[variant] if isinstance(variant, str) else int(variant)
+        dev = d_src.device
+        count = torch.empty((nblocks, self.nch), dtype=torch.int32, device=dev)
+        index = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.int32, device=dev)
+        value = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.float64, device=dev)
+        sig = thr = None
+        if traces:
+            sig = torch.empty((nblocks, self.ns, self.nch), dtype=torch.float64, device=dev)
+            thr = torch.empty_like(sig)
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.peak_state_bytes()
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        rc = self._L.rspt_hip_peak_detect_batch_dev(self._h, d_src.data_ptr(), nblocks, v, float(sampling_rate), float(marker_val), ptr(state),
+                                                    count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
+        self._check("rspt_hip_peak_detect_batch_dev", rc)
+        return (count, index, value, sig, thr) if traces else (count, index, value)
+
     def synchronize(self):
         self._check("rspt_hip_synchronize", self._L.rspt_hip_synchronize(self._h))
 
@@ -441,6 +491,26 @@ class HostBuffer:
 
 
 # factory names of lib_rspt/signal_packer.h:59-69
+FILTER_TYPES = {"high_pass": 0, "low_pass": 1, "band_pass": 2, "band_stop": 3}
+PEAK_VARIANTS = {"online": 0, "online_1st": 1, "offline_fw": 2}
+
+
+def design_iir(type, order, fs, lo, hi=0.0):
+    """The reference's Butterworth designer (create_filter_iir; rspt_hip.h: rspt_hip_design_iir), bit-exact, on the host.
+    type: "high_pass" / "low_pass" / "band_pass" / "band_stop" or 0..3; order 1 or 2; fs, lo, hi in Hz.  Returns (num, den)
+    float64 arrays: num the feed-forward side, den (den[0] = 1) the feedback side.  Raises RsptHipError where the reference
+    refuses the design.  To run the result as the IIR pre-filter, pass them crossed, as i_filter::new_iir(n, d) takes them:
+        num, den = design_iir("band_pass", 2, 2000.0, 0.4, 200.0)
+        packer.iir_prefilter_batch(buf, n=den, d=num)"""
+    t = FILTER_TYPES[type] if isinstance(type, str) else int(type)
+    num, den, n = np.zeros(5), np.zeros(5), C.c_size_t()
+    rc = lib().rspt_hip_design_iir(t, int(order), float(fs), float(lo), float(hi), num.ctypes.data_as(C.POINTER(C.c_double)),
+                                   den.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n))
+    if rc != 0:
+        raise RsptHipError("rspt_hip_design_iir", rc)
+    return num[: n.value].copy(), den[: n.value].copy()
+
+
 def new_xdelta_hzr(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, nr_bytes_to_encode, device=0):
     return SignalPacker(KIND_XDELTA_HZR, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, nr_bytes_to_encode, device)
 

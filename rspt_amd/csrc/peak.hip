@@ -1,0 +1,422 @@
+// peak.hip -- the R-peak detector stage and the Butterworth designer it is built on.
+//
+// Restates create_filter_iir (lib_rspt/lib_filter/iir_filter_design.cpp) on the host and three detectors of
+// lib_rspt/peak_detector.h on the device: peak_detector::detect (ONLINE), peak_detector_1st_order::detect (ONLINE_1ST) and
+// peak_detector_offline::detect_fw (OFFLINE_FW).  A detector is a band-pass filter, squaring, an integrating low-pass, a
+// low-pass threshold and a small state machine; every sample of a channel depends on the one before, so one lane holds one
+// detector and walks its samples in order.  Lanes map to flat (block, channel) pairs (a fresh detector each), or to the
+// channels alone when the caller keeps one detector per channel across blocks and calls (stateful mode).
+//
+// Double arithmetic in the reference's order of operations, every product and sum rounded on its own (no FMA: see the pragma),
+// so every trace value and every event is bit-identical with the reference's x86-64 build.
+#include <cmath>
+
+#include "common.hpp"
+
+// NO contraction (as filter.hip): the filters' products and sums must each be rounded on their own.
+#pragma clang fp contract(off)
+
+namespace rspt {
+
+enum : int { kPeakOnline = 0, kPeakOnline1st = 1, kPeakOfflineFw = 2 };
+enum : int { kFiltHighPass = 0, kFiltLowPass = 1, kFiltBandPass = 2, kFiltBandStop = 3 };
+
+// ---- the designer (host) ------------------------------------------------------------------------------------------------
+// create_filter_iir(num, den, butterworth, type, order, fs, lo, hi): the four designs, in the reference's order of
+// operations.  Returns the coefficient count (3, 2, 5 or 3), or 0 where the reference returns false.  pow(k, 2) is k * k (what
+// both g++ -O2 and clang make of it); pow(k, 3) and pow(k, 4) stay calls of libm's pow.
+
+// (z - 1)^n (sign < 0) or (z + 1)^n, highest power first: coefficient k is the product of (n - i + 1) / i over i = 1..k
+static void binom_row(int n, int sign, double* out) {
+    for (int k = 0; k <= n; ++k) {
+        double c = 1.0;
+        for (int i = 1; i <= k; ++i) c = c * ((double)(n - i + 1) / i);
+        out[k] = (sign < 0 && (k & 1)) ? c * -1.0 : (sign < 0 ? c * 1.0 : c);
+    }
+}
+
+// r[i + j] += p[i] * q[j], from zeros (r holds np + nq - 1 doubles)
+static void poly_conv(const double* p, int np, const double* q, int nq, double* r) {
+    for (int i = 0; i < np + nq - 1; ++i) r[i] = 0.0;
+    for (int i = 0; i < np; ++i)
+        for (int j = 0; j < nq; ++j) r[i + j] = r[i + j] + p[i] * q[j];
+}
+
+static int design_iir(int type, int order, double fs, double lo, double hi, double* num, double* den) {
+    if (type < kFiltHighPass || type > kFiltBandStop) return 0;
+    const double pi = M_PI;
+    if (order == 2 && (type == kFiltLowPass || type == kFiltHighPass)) {
+        if (fs <= 0 || lo <= 0) return 0;
+        const double K = tan(pi * lo / fs);
+        const double K2 = K * K;
+        const double r2 = sqrt(2.0);
+        const double a0 = 1.0 + r2 * K + K2;
+        const double a1 = 2.0 * (K2 - 1.0);
+        const double a2 = 1.0 - r2 * K + K2;
+        if (type == kFiltLowPass) {
+            num[0] = K2 / a0;
+            num[1] = (2.0 * K2) / a0;
+            num[2] = K2 / a0;
+        } else {
+            num[0] = 1.0 / a0;
+            num[1] = -2.0 / a0;
+            num[2] = 1.0 / a0;
+        }
+        den[0] = 1.0;
+        den[1] = a1 / a0;
+        den[2] = a2 / a0;
+        return 3;
+    }
+    if (order == 2) {  // the band-pass from the second-order low-pass prototype: 4th order, 5 coefficients
+        if (type != kFiltBandPass || fs <= 0 || lo <= 0 || hi <= lo) return 0;
+        const double k = 2.0 / (1.0 / fs);  // bilinear transform s = k (z - 1) / (z + 1)
+        const double w1 = k * tan(pi * lo / fs), w2 = k * tan(pi * hi / fs);
+        const double bw = w2 - w1;
+        const double w0 = sqrt(w1 * w2);
+        // analog denominator s^4 + a3 s^3 + a2 s^2 + a1 s + a0 and numerator bw^2 s^2, each power of s taken to z
+        const double a3 = sqrt(2.0) * bw;
+        const double a2 = 2.0 * w0 * w0 + bw * bw;
+        const double a1 = sqrt(2.0) * bw * w0 * w0;
+        const double a0 = w0 * w0 * w0 * w0;
+        double zm[5][5], zp[5][5];  // zm[n] = (z - 1)^n, zp[n] = (z + 1)^n
+        for (int n = 1; n <= 4; ++n) {
+            binom_row(n, -1, zm[n]);
+            binom_row(n, +1, zp[n]);
+        }
+        double t[5][5];  // the five terms, unscaled: (z-1)^4, (z-1)^3 (z+1), (z-1)^2 (z+1)^2, (z-1) (z+1)^3, (z+1)^4
+        for (int i = 0; i < 5; ++i) t[0][i] = zm[4][i];
+        poly_conv(zm[3], 4, zp[1], 2, t[1]);
+        poly_conv(zm[2], 3, zp[2], 3, t[2]);
+        poly_conv(zm[1], 2, zp[3], 4, t[3]);
+        for (int i = 0; i < 5; ++i) t[4][i] = zp[4][i];
+        const double s[5] = {1.0 * pow(k, 4), a3 * pow(k, 3), a2 * (k * k), a1 * k, a0};
+        double d[5];
+        for (int i = 0; i < 5; ++i) d[i] = t[0][i] * s[0];
+        for (int j = 1; j < 5; ++j)
+            for (int i = 0; i < 5; ++i) d[i] = d[i] + t[j][i] * s[j];
+        const double g = bw * bw * (k * k);
+        const double nz[5] = {1.0, 0.0, -2.0, 0.0, 1.0};  // (z - 1)^2 (z + 1)^2
+        const double norm = d[0];
+        for (int i = 0; i < 5; ++i) {
+            den[i] = d[i] / norm;
+            num[i] = (nz[i] * g) / norm;
+        }
+        return 5;
+    }
+    if (order == 1 && (type == kFiltLowPass || type == kFiltHighPass)) {
+        if (fs <= 0 || lo <= 0) return 0;
+        const double K = tan(pi * lo / fs);
+        const double a0 = 1.0 + K, a1 = 1.0 - K;
+        num[0] = (type == kFiltLowPass ? K : 1.0) / a0;
+        num[1] = (type == kFiltLowPass ? K : -1.0) / a0;
+        den[0] = 1.0;
+        den[1] = -a1 / a0;
+        return 2;
+    }
+    if (order == 1) {  // band_pass -- and band_stop: the reference's first-order band-pass never looks at the type
+        if (fs <= 0 || lo <= 0 || hi <= lo) return 0;
+        const double K1 = tan(pi * lo / fs), K2 = tan(pi * hi / fs);
+        // a first-order high-pass at lo in series with a first-order low-pass at hi
+        const double hn0 = 1.0 / (1.0 + K1), hn1 = -1.0 / (1.0 + K1), hd1 = -(1.0 - K1) / (1.0 + K1);
+        const double ln0 = K2 / (1.0 + K2), ln1 = K2 / (1.0 + K2), ld1 = -(1.0 - K2) / (1.0 + K2);
+        const double n3[3] = {ln0 * hn0, ln0 * hn1 + ln1 * hn0, ln1 * hn1};
+        const double d3[3] = {1.0 * 1.0, 1.0 * hd1 + ld1 * 1.0, ld1 * hd1};
+        const double norm = d3[0];
+        for (int i = 0; i < 3; ++i) {
+            num[i] = n3[i] / norm;
+            den[i] = d3[i] / norm;
+        }
+        return 3;
+    }
+    return 0;
+}
+
+// ---- the detector (device) ----------------------------------------------------------------------------------------------
+
+// Everything a launch needs besides the pointers: the three filters' feed-forward (the designer's numerator, the struct's d)
+// and feedback (its denominator, the struct's n) coefficients, and the constants.
+struct PeakCoef {
+    double bf[5], bb[5];  // band-pass
+    double gf[3], gb[3];  // integrator
+    double tf[3], tb[3];  // threshold
+    double atten;         // 1 / (1 + A / fs)
+    double marker;
+    int32_t nslope;       // (int)(100 fs / 1000)
+    int32_t hist;         // 4 * (int)fs: history calls of the band-pass
+};
+
+struct PeakArgs {
+    const uint8_t* src;
+    uint64_t block_bytes;
+    uint32_t stride, nch, ns, nblocks;
+    uint32_t lanes;        // nblocks * nch (fresh) or nch (stateful)
+    uint8_t* state;        // stateful: the caller's state (PeakStateView), else null
+    uint32_t* count;       // [nblocks][nch]
+    int32_t* index;        // [nblocks][nch][max_peaks]
+    double* value;
+    uint64_t max_peaks;
+    double* sig;           // [nblocks][ns][nch] (traces), or null
+    double* thr;
+};
+
+// The state of one detector per channel, structure of arrays so that lanes of a wave touch consecutive words: 24 doubles
+// [field][nch] -- band-pass x[5] y[5], integrator x[3] y[3], threshold x[3] y[3] (newest first), previous peak amplitude,
+// previous signal value -- then 4 int32 [field][nch]: searching, samples after the peak, sample index, (unused).  All zero is
+// a fresh detector: that is what the reference's constructor leaves.
+constexpr uint32_t kPeakStateDoubles = 24, kPeakStateInts = 4;
+constexpr uint32_t kPeakStateBytesPerChannel = kPeakStateDoubles * 8 + kPeakStateInts * 4;
+
+template <int N>
+struct PkFilt {
+    double x[N], y[N];  // input / output i samples ago
+    // iir_filter_*_order::filter: all feed-forward terms left to right, then the feedback terms
+    __device__ __forceinline__ double step(const double* f, const double* b, double in) {
+#pragma unroll
+        for (int i = N - 1; i > 0; --i) {
+            x[i] = x[i - 1];
+            y[i] = y[i - 1];
+        }
+        x[0] = in;
+        double a = f[0] * x[0];
+#pragma unroll
+        for (int i = 1; i < N; ++i) a = a + f[i] * x[i];
+#pragma unroll
+        for (int i = 1; i < N; ++i) a = a - b[i] * y[i];
+        y[0] = a;
+        return a;
+    }
+    // the feedback half of a step whose feed-forward sum ff is known (the input is already in the x ring)
+    __device__ __forceinline__ double feedback(const double* b, double ff) {
+        double a = ff;
+#pragma unroll
+        for (int i = 1; i < N; ++i) a = a - b[i] * y[i - 1];  // (y[i - 1] is y[i] of the step being taken)
+#pragma unroll
+        for (int i = N - 1; i > 0; --i) y[i] = y[i - 1];
+        y[0] = a;
+        return a;
+    }
+    // init_history_values(x0, .): `steps` calls of filter(x0).  Once the x ring holds only x0 the feed-forward sum is one number.
+    __device__ void history(const double* f, const double* b, double x0, int32_t steps) {
+        int32_t i = 0;
+        for (; i < steps && i < N; ++i) step(f, b, x0);
+        if (i >= steps) return;
+        double ff = f[0] * x0;
+#pragma unroll
+        for (int k = 1; k < N; ++k) ff = ff + f[k] * x0;
+        for (; i < steps; ++i) feedback(b, ff);
+    }
+};
+
+template <int V>
+struct PeakDet {
+    static constexpr int NB = V == kPeakOnline ? 5 : 3;  // iir_filter_4th_order / iir_filter_2nd_order
+    static constexpr int NG = V == kPeakOnline ? 3 : 2;  // iir_filter_2nd_order / iir_filter_1st_order
+    PkFilt<NB> bp;
+    PkFilt<NG> ig;
+    PkFilt<3> th;
+    double prev_amp, prev_sig;
+    int32_t searching, after;
+    uint32_t idx;  // sample_indx_ (an int: wraps)
+
+    __device__ void clear() {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) bp.x[i] = bp.y[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < NG; ++i) ig.x[i] = ig.y[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) th.x[i] = th.y[i] = 0.0;
+        prev_amp = prev_sig = 0.0;
+        searching = after = 0;
+        idx = 0;
+    }
+    __device__ void load(const uint8_t* st, uint32_t nch, uint32_t c) {
+        const double* d = reinterpret_cast<const double*>(st);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            bp.x[i] = d[(size_t)i * nch + c];
+            bp.y[i] = d[(size_t)(5 + i) * nch + c];
+        }
+#pragma unroll
+        for (int i = 0; i < NG; ++i) {
+            ig.x[i] = d[(size_t)(10 + i) * nch + c];
+            ig.y[i] = d[(size_t)(13 + i) * nch + c];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            th.x[i] = d[(size_t)(16 + i) * nch + c];
+            th.y[i] = d[(size_t)(19 + i) * nch + c];
+        }
+        prev_amp = d[(size_t)22 * nch + c];
+        prev_sig = d[(size_t)23 * nch + c];
+        const int32_t* w = reinterpret_cast<const int32_t*>(d + (size_t)kPeakStateDoubles * nch);
+        searching = w[c];
+        after = w[(size_t)nch + c];
+        idx = (uint32_t)w[(size_t)2 * nch + c];
+    }
+    __device__ void save(uint8_t* st, uint32_t nch, uint32_t c) const {
+        double* d = reinterpret_cast<double*>(st);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            d[(size_t)i * nch + c] = bp.x[i];
+            d[(size_t)(5 + i) * nch + c] = bp.y[i];
+        }
+#pragma unroll
+        for (int i = 0; i < NG; ++i) {
+            d[(size_t)(10 + i) * nch + c] = ig.x[i];
+            d[(size_t)(13 + i) * nch + c] = ig.y[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            d[(size_t)(16 + i) * nch + c] = th.x[i];
+            d[(size_t)(19 + i) * nch + c] = th.y[i];
+        }
+        d[(size_t)22 * nch + c] = prev_amp;
+        d[(size_t)23 * nch + c] = prev_sig;
+        int32_t* w = reinterpret_cast<int32_t*>(d + (size_t)kPeakStateDoubles * nch);
+        w[c] = searching;
+        w[(size_t)nch + c] = after;
+        w[(size_t)2 * nch + c] = (int32_t)idx;
+    }
+
+    // Everything of detect() behind the band-pass output s: squaring and the integrator, the threshold, the state machine
+    // (branch-free, as written in the reference).  Returns whether the sample is an event; sig / h: the two trace values.
+    __device__ __forceinline__ bool tail(const PeakCoef& c, double s_bp, double& sig, double& h) {
+        const double s = ig.step(c.gf, c.gb, s_bp * s_bp);
+        h = th.step(c.tf, c.tb, s);
+        sig = s;
+        const bool c1 = searching && (s > h * 1.5) && (prev_sig > s);
+        const bool take = c1 && ((prev_amp == 0.0) || (prev_sig > prev_amp * 0.5));
+        const double damped = prev_amp * c.atten;
+        const bool rise = !c1 && (prev_sig < s);
+        prev_amp = take ? prev_sig : (c1 ? damped : prev_amp);
+        after = take ? 1 : (rise ? 0 : after);
+        searching = take ? 0 : (rise ? 1 : searching);
+        prev_sig = s;
+        after = after ? (int32_t)((uint32_t)after + 1u) : 0;
+        const bool fire = after == c.nslope;
+        after = fire ? 0 : after;
+        return fire;
+    }
+};
+
+// Runs one detector through one block (ns samples at p, row stride `stride`); events and traces of this (block, channel).
+template <int BPS, int V, bool TR>
+__device__ void peak_block(PeakDet<V>& D, const PeakCoef& c, const uint8_t* p, uint32_t stride, uint32_t ns, bool aligned, uint32_t* count,
+                           int32_t* index, double* value, uint64_t max_peaks, double* sig, double* thr, uint32_t nch) {
+    constexpr int NB = PeakDet<V>::NB;
+    uint32_t cnt = 0;
+    auto emit = [&](uint32_t t, bool fire, double s, double h) {
+        if (TR) {
+            sig[(size_t)t * nch] = s;
+            thr[(size_t)t * nch] = h;
+        }
+        if (fire) {
+            if (cnt < max_peaks) {
+                index[cnt] = (int32_t)t;
+                value[cnt] = c.marker == -1.0 ? s : c.marker;
+            }
+            ++cnt;
+        }
+    };
+    if (V == kPeakOfflineFw) D.bp.history(c.bf, c.bb, (double)sample_load<BPS>(p, aligned), c.hist);  // every detect_fw call
+    // ONLINE: the history runs where sample_indx_ is 0 -- the first sample of a fresh detector, or where the int wraps back
+    // to 0 after 2^32 samples (then this block takes the sample-by-sample path below)
+    bool simple = false;
+    if (V != kPeakOfflineFw) {  // sample 0's `if (!sample_indx_++)`
+        const bool first = D.idx == 0;
+        simple = !first && (uint64_t)D.idx + ns > (1ull << 32);  // (0 comes back inside this block)
+        if (first) D.bp.history(c.bf, c.bb, (double)sample_load<BPS>(p, aligned), c.hist);
+        D.idx += 1;
+    }
+    if (simple) {
+        for (uint32_t t = 0; t < ns; ++t) {
+            const double x = (double)sample_load<BPS>(p + (size_t)t * stride, aligned);
+            if (t > 0) {  // (sample 0's index was handled above)
+                if (D.idx == 0) D.bp.history(c.bf, c.bb, x, c.hist);
+                D.idx += 1;
+            }
+            double s, h;
+            const bool f = D.tail(c, D.bp.step(c.bf, c.bb, x), s, h);
+            emit(t, f, s, h);
+        }
+        count[0] = cnt;
+        return;
+    }
+    if (V != kPeakOfflineFw) D.idx += ns - 1;  // (no wrap back to 0 in this block)
+    // Chunks of CH samples: the next chunk's loads are in flight while this one runs, and the band-pass feed-forward sums of
+    // the chunk (independent of every output) are formed up front, for the scheduler to place into the dependent chain.
+    constexpr uint32_t CH = 16;
+    int32_t cur[CH], nxt[CH];
+    const uint32_t nfull = ns / CH;
+    if (nfull) {
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) cur[e] = sample_load<BPS>(p + (size_t)e * stride, aligned);
+    }
+    for (uint32_t k = 0; k < nfull; ++k) {
+        const uint8_t* q = p + (size_t)k * CH * stride;
+        if (k + 1 < nfull) {
+#pragma unroll
+            for (uint32_t e = 0; e < CH; ++e) nxt[e] = sample_load<BPS>(q + (size_t)(CH + e) * stride, aligned);
+        }
+        double xs[CH + NB - 1], ff[CH];
+#pragma unroll
+        for (int i = 0; i < NB - 1; ++i) xs[i] = D.bp.x[NB - 2 - i];
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) xs[NB - 1 + e] = (double)cur[e];
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) {
+            double a = c.bf[0] * xs[NB - 1 + e];
+#pragma unroll
+            for (int i = 1; i < NB; ++i) a = a + c.bf[i] * xs[NB - 1 + e - i];
+            ff[e] = a;
+        }
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) {
+            double s, h;
+            const bool f = D.tail(c, D.bp.feedback(c.bb, ff[e]), s, h);
+            emit(k * CH + e, f, s, h);
+        }
+#pragma unroll
+        for (int i = 0; i < NB; ++i) D.bp.x[i] = xs[CH + NB - 2 - i];
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) cur[e] = nxt[e];
+    }
+    for (uint32_t t = nfull * CH; t < ns; ++t) {
+        double s, h;
+        const bool f = D.tail(c, D.bp.step(c.bf, c.bb, (double)sample_load<BPS>(p + (size_t)t * stride, aligned)), s, h);
+        emit(t, f, s, h);
+    }
+    count[0] = cnt;
+}
+
+// One lane per detector: lane q = (block q / nch, channel q % nch) fresh, or channel q through every block (stateful).
+template <int BPS, int V, bool TR>
+__global__ __launch_bounds__(64) void k_peak(PeakArgs a, PeakCoef c) {
+    const uint32_t q = blockIdx.x * 64u + threadIdx.x;
+    if (q >= a.lanes) return;
+    // (wave-uniform: every block base and row start is aligned when the first one is and the sizes are multiples)
+    const bool aligned = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(a.src) % BPS) == 0 && (a.block_bytes % BPS) == 0;
+    PeakDet<V> D;
+    uint32_t b0, b1, ch;
+    if (a.state) {
+        ch = q;
+        b0 = 0;
+        b1 = a.nblocks;
+        D.load(a.state, a.nch, ch);
+    } else {
+        b0 = q / a.nch;
+        ch = q - b0 * a.nch;
+        b1 = b0 + 1;
+        D.clear();
+    }
+    for (uint32_t b = b0; b < b1; ++b) {
+        const uint64_t pair = (uint64_t)b * a.nch + ch;
+        const uint64_t tr = (uint64_t)b * a.ns * a.nch + ch;
+        peak_block<BPS, V, TR>(D, c, a.src + (size_t)b * a.block_bytes + (size_t)ch * BPS, a.stride, a.ns, aligned, a.count + pair,
+                               a.index + pair * a.max_peaks, a.value + pair * a.max_peaks, a.max_peaks, TR ? a.sig + tr : nullptr,
+                               TR ? a.thr + tr : nullptr, a.nch);
+    }
+    if (a.state) D.save(a.state, a.nch, ch);
+}
+
+}  // namespace rspt

@@ -35,6 +35,7 @@
 #include "filter.hip"
 #include "fir.hip"
 #include "median.hip"
+#include "peak.hip"
 
 using namespace rspt;
 
@@ -2006,6 +2007,86 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
         }
     }
     return finish_window_call(p, ms.last, e, st);
+}
+
+int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff_low, double cutoff_high, double* num, double* den,
+                        size_t* nr_coefficients) {
+    if (!num || !den || !nr_coefficients) return RSPT_HIP_ERR_ARG;
+    double n[5], d[5];
+    const int nc = design_iir(type, order, sampling_rate, cutoff_low, cutoff_high, n, d);
+    if (nc == 0) return RSPT_HIP_ERR_ARG;
+    for (int i = 0; i < nc; ++i) {
+        num[i] = n[i];
+        den[i] = d[i];
+    }
+    *nr_coefficients = (size_t)nc;
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_peak_state_bytes(rspt_hip_packer* p, size_t* bytes) {
+    if (!p || !bytes) return RSPT_HIP_ERR_ARG;
+    *bytes = (size_t)p->g.nch * kPeakStateBytesPerChannel;
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
+                                   void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
+                                   double* d_threshold, void* stream) {
+    if (!p || !d_src || !d_count || nblocks == 0) return RSPT_HIP_ERR_ARG;
+    if (variant < kPeakOnline || variant > kPeakOfflineFw) return RSPT_HIP_ERR_ARG;
+    if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return RSPT_HIP_ERR_ARG;
+    if (max_peaks > 0 && (!d_index || !d_value)) return RSPT_HIP_ERR_ARG;
+    if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
+    // the three filters as the detector's constructor designs them (create_filter_iir(f.d, f.n, ...): numerator -> d)
+    static const struct { int bp_order; double bp_lo, bp_hi; int ig_order; double A; } kVar[3] = {
+        {2, 10.0, 20.0, 2, 25.0}, {1, 10.0, 20.0, 1, 25.0}, {1, 15.0, 25.0, 1, 70.0}};
+    const auto& v = kVar[variant];
+    PeakCoef c{};
+    if (!design_iir(kFiltBandPass, v.bp_order, sampling_rate, v.bp_lo, v.bp_hi, c.bf, c.bb) ||
+        !design_iir(kFiltLowPass, v.ig_order, sampling_rate, 3.0, 0.0, c.gf, c.gb) ||
+        !design_iir(kFiltLowPass, 2, sampling_rate, 0.15, 0.0, c.tf, c.tb))
+        return RSPT_HIP_ERR_ARG;  // (not reached: every design is valid for fs > 0)
+    c.atten = 1.0 / (1.0 + v.A / sampling_rate);
+    c.marker = marker_val;
+    c.nslope = (int32_t)((100.0 * sampling_rate) / 1000.0);
+    c.hist = 4 * (int32_t)sampling_rate;
+    PeakArgs a{};
+    a.src = (const uint8_t*)d_src;
+    a.block_bytes = g.block_bytes;
+    a.stride = g.nch * g.bps;
+    a.nch = g.nch;
+    a.ns = g.ns;
+    a.nblocks = (uint32_t)nblocks;
+    a.lanes = d_state ? g.nch : (uint32_t)(nblocks * g.nch);
+    a.state = (uint8_t*)d_state;
+    a.count = d_count;
+    a.index = d_index;
+    a.value = d_value;
+    a.max_peaks = max_peaks;
+    a.sig = d_sig;
+    a.thr = d_threshold;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t grid = (a.lanes + 63) / 64;
+    by_bps(g.bps, [&](auto bb) {
+        constexpr int B = decltype(bb)::value;
+        auto go = [&](auto vv, auto tr) {
+            hipLaunchKernelGGL((k_peak<B, decltype(vv)::value, decltype(tr)::value>), dim3(grid), dim3(64), 0, st, a, c);
+        };
+        using O = std::integral_constant<int, kPeakOnline>;
+        using O1 = std::integral_constant<int, kPeakOnline1st>;
+        using F = std::integral_constant<int, kPeakOfflineFw>;
+        using T = std::true_type;
+        using N = std::false_type;
+        const bool tr = d_sig != nullptr;
+        if (variant == kPeakOnline) tr ? go(O(), T()) : go(O(), N());
+        else if (variant == kPeakOnline1st) tr ? go(O1(), T()) : go(O1(), N());
+        else tr ? go(F(), T()) : go(F(), N());
+    });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
 }
 
 // ---- multi-GPU gather over RCCL.  RCCL is bound at run time: a process that never gathers (the C++ drop-in on one
