@@ -379,6 +379,48 @@ int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t
                                    void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
                                    double* d_threshold, void* stream);
 
+/* ---- the reference's zero-phase offline R-peak detector ------------------------------------------------------------
+ * peak_detector_offline::detect of lib_rspt/peak_detector.h, bit-identical with the reference's x86-64 build, one detector per
+ * (block, channel) of nblocks device-resident blocks (the handle's shape, interleaved native layout; any packer kind; samples
+ * little-endian, read sign-extended from bps bytes; d_src is only read).  Per block, with x = (double) of each sample: the
+ * band-pass (order 1, 15-25 Hz) and the baseline (low-pass order 1, 0.5 Hz) each take 4 * (int)fs calls of filter(x[0]) on
+ * whatever state they hold; the baseline runs forward and then backward over its own output; the band-pass runs forward
+ * (outputs dropped) and then backward over x again; the integrator (low-pass order 1, 3 Hz) runs forward over the squares and
+ * backward over its own output (filt_signal); the threshold (low-pass order 2, 0.15 Hz) runs forward over filt_signal (outputs
+ * dropped) and backward over it again (threshold_signal).  No filter is reset between passes.  detect_fw's state machine
+ * (A = 70, nr_slope_samples = (int)(100 fs / 1000)) then writes peak_signal: marker_val, or filt_signal where marker_val == -1.0,
+ * at each firing, 0 elsewhere.  Each non-zero peak_signal[i], i >= nr_slope_samples, ascending, moves to i - nr_slope_samples + 1.
+ * Then, with radius = (int)(10 fs / 1000), each non-zero peak_signal[i], radius <= i <= ns - radius - 1, ascending, moves to the
+ * index of the largest (strict <, first wins) or the smallest (strict >) of x[j] - baseline[j] over i - radius <= j < i + radius
+ * (the largest where max > -min; from -2e6 / 2e6 and index 0, so radius 0 (fs < 100) moves every peak to index 0).  A peak moved
+ * ahead is visited again; a peak moved onto another replaces it.  A value is a peak where it is not zero (a NaN is one; 0.0 and
+ * -0.0 are not).
+ *   d_count       [nblocks][nch] uint32: the exact number of non-zero entries of the final peak_signal; required
+ *   d_index       [nblocks][nch][max_peaks] int32 and
+ *   d_value       [nblocks][nch][max_peaks] double: the first max_peaks of them in ascending index order (index within the block,
+ *                 value); max_peaks = 0 gives counts alone (d_index / d_value may then be NULL; else both are required)
+ *   d_sig, d_threshold  optional [nblocks][ns][nch] doubles: filt_signal and threshold_signal as detect() leaves them; NULL for
+ *                 none (both or neither)
+ *   d_state       NULL: a fresh object per (block, channel).  Else a caller-owned device buffer of rspt_hip_peak_state_bytes
+ *                 bytes holding one object per channel: channel c runs through blocks 0 .. nblocks - 1 in order and on across
+ *                 calls, carrying the four filters and the state machine.  The layout is OFFLINE_FW's of
+ *                 rspt_hip_peak_detect_batch_dev, the baseline filter in band-pass slots OFFLINE_FW never uses, so one state may
+ *                 take detect_fw (variant 2) and detect calls in turn, as one reference object can.  All-zero bytes are fresh.
+ *   d_work        required: a caller-owned device buffer of at least rspt_hip_peak_offline_work_bytes(p, nblocks, d_state != NULL)
+ *                 bytes, 8-byte aligned; the call overwrites it.  The stage allocates nothing of its own.
+ * The reference's optional peak_indexes vector is not produced: it is sized by the count of shifted peaks before the
+ * relocation, and overflows where a peak sits at nr_slope_samples - 1.  d_count / d_index hold the final peak_signal instead,
+ * which is defined in every case.
+ * RSPT_HIP_ERR_ARG for everything rspt_hip_peak_detect_batch_dev refuses (sampling_rate not finite, <= 0 or > 2^20, a NULL
+ * d_src or d_count, max_peaks > 0 with a NULL d_index or d_value, only one of d_sig / d_threshold, nblocks == 0,
+ * nblocks * nch >= 2^31, max_peaks above 2^32), a NULL or misaligned d_work, and the reference's undefined cases: fs < 10
+ * (nr_slope_samples 0: its shift runs past the end of the array) and ns < radius (its unsigned loop bound wraps).
+ * Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev. */
+int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int stateful, size_t* bytes);
+int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
+                                           void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
+                                           size_t max_peaks, double* d_sig, double* d_threshold, void* stream);
+
 /* The handle's own (non-blocking) stream, as a hipStream_t. */
 void* rspt_hip_stream(rspt_hip_packer* p);
 

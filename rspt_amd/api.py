@@ -25,7 +25,8 @@ C_ABI_SYMBOLS = [
     "rspt_hip_block_bytes", "rspt_hip_current_nb", "rspt_hip_set_nb", "rspt_hip_set_verify", "rspt_hip_reserve", "rspt_hip_compress_batch_dev",
     "rspt_hip_decompress_batch_dev", "rspt_hip_decompress_packed_dev", "rspt_hip_pack_bound", "rspt_hip_pack_batch_dev", "rspt_hip_stream", "rspt_hip_synchronize", "rspt_hip_set_profiling", "rspt_hip_stage_count",
     "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_design_iir",
-    "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
+    "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
+    "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
     "rspt_hip_gather_post_sizes", "rspt_hip_gather_post_payload", "rspt_hip_gather_wait",
     "rspt_hip_feed_begin", "rspt_hip_feed_push", "rspt_hip_feed_submit", "rspt_hip_feed_poll", "rspt_hip_feed_flush", "rspt_hip_feed_end",
@@ -121,6 +122,11 @@ def lib():
     L.rspt_hip_peak_detect_batch_dev.restype = C.c_int
     L.rspt_hip_peak_detect_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rspt_hip_peak_offline_work_bytes.restype = C.c_int
+    L.rspt_hip_peak_offline_work_bytes.argtypes = [C.c_void_p, C.c_size_t, C.c_int, _szp]
+    L.rspt_hip_peak_detect_offline_batch_dev.restype = C.c_int
+    L.rspt_hip_peak_detect_offline_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rspt_hip_feed_begin.restype, L.rspt_hip_feed_begin.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]
     L.rspt_hip_feed_push.restype, L.rspt_hip_feed_push.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.rspt_hip_feed_submit.restype, L.rspt_hip_feed_submit.argtypes = C.c_int, [C.c_void_p]
@@ -436,6 +442,43 @@ class SignalPacker:
         rc = self._L.rspt_hip_peak_detect_batch_dev(self._h, d_src.data_ptr(), nblocks, v, float(sampling_rate), float(marker_val), ptr(state),
                                                     count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
         self._check("rspt_hip_peak_detect_batch_dev", rc)
+        return (count, index, value, sig, thr) if traces else (count, index, value)
+
+    def peak_offline_work_bytes(self, nblocks, stateful=False):
+        n = C.c_size_t()
+        self._check("rspt_hip_peak_offline_work_bytes", self._L.rspt_hip_peak_offline_work_bytes(self._h, nblocks, int(bool(stateful)), C.byref(n)))
+        return n.value
+
+    def peak_detect_offline_batch(self, d_src, sampling_rate, marker_val=1.0, max_peaks=64, state=None, traces=False, stream=None):
+        """The reference's zero-phase offline R-peak detector (peak_detector_offline::detect; rspt_hip.h:
+        rspt_hip_peak_detect_offline_batch_dev) on device-resident blocks, which are only read.  state: None for a fresh object per
+        (block, channel), or a peak_state() tensor carrying one object per channel through the blocks and across calls (it may
+        alternate with peak_detect_batch(variant="offline_fw") calls at the same rate).  The workspace is allocated here.
+        Asynchronous.  Returns what peak_detect_batch returns: (count, index, value) of the final peak_signal's non-zero entries
+        and, with traces, (filt_signal, threshold_signal) [nblocks, ns, nch] float64 as well."""
+        import torch
+
+        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
+        nblocks = d_src.numel() // self.block_bytes
+        assert nblocks * self.block_bytes == d_src.numel()
+        dev = d_src.device
+        count = torch.empty((nblocks, self.nch), dtype=torch.int32, device=dev)
+        index = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.int32, device=dev)
+        value = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.float64, device=dev)
+        sig = thr = None
+        if traces:
+            sig = torch.empty((nblocks, self.ns, self.nch), dtype=torch.float64, device=dev)
+            thr = torch.empty_like(sig)
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.peak_state_bytes()
+        work = torch.empty(max(1, (self.peak_offline_work_bytes(max(nblocks, 1), state is not None) + 7) // 8), dtype=torch.float64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        rc = self._L.rspt_hip_peak_detect_offline_batch_dev(self._h, d_src.data_ptr(), nblocks, float(sampling_rate), float(marker_val), ptr(state),
+                                                            work.data_ptr(), count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
+        self._check("rspt_hip_peak_detect_offline_batch_dev", rc)
+        if stream is not None:  # (the workspace goes back to torch's pool only once the caller's stream is past this call)
+            work.record_stream(torch.cuda.ExternalStream(stream, device=dev))
         return (count, index, value, sig, thr) if traces else (count, index, value)
 
     def synchronize(self):

@@ -2,7 +2,7 @@
 //
 // Restates create_filter_iir (lib_rspt/lib_filter/iir_filter_design.cpp) on the host and three detectors of
 // lib_rspt/peak_detector.h on the device: peak_detector::detect (ONLINE), peak_detector_1st_order::detect (ONLINE_1ST) and
-// peak_detector_offline::detect_fw (OFFLINE_FW).  A detector is a band-pass filter, squaring, an integrating low-pass, a
+// peak_detector_offline::detect_fw (OFFLINE_FW), and the zero-phase peak_detector_offline::detect (k_peak_offline, below).  A detector is a band-pass filter, squaring, an integrating low-pass, a
 // low-pass threshold and a small state machine; every sample of a channel depends on the one before, so one lane holds one
 // detector and walks its samples in order.  Lanes map to flat (block, channel) pairs (a fresh detector each), or to the
 // channels alone when the caller keeps one detector per channel across blocks and calls (stateful mode).
@@ -284,6 +284,10 @@ struct PeakDet {
         const double s = ig.step(c.gf, c.gb, s_bp * s_bp);
         h = th.step(c.tf, c.tb, s);
         sig = s;
+        return machine(c, s, h);
+    }
+    // The state machine alone, on the integrator output s and the threshold h of one sample.
+    __device__ __forceinline__ bool machine(const PeakCoef& c, double s, double h) {
         const bool c1 = searching && (s > h * 1.5) && (prev_sig > s);
         const bool take = c1 && ((prev_amp == 0.0) || (prev_sig > prev_amp * 0.5));
         const double damped = prev_amp * c.atten;
@@ -417,6 +421,250 @@ __global__ __launch_bounds__(64) void k_peak(PeakArgs a, PeakCoef c) {
                                TR ? a.thr + tr : nullptr, a.nch);
     }
     if (a.state) D.save(a.state, a.nch, ch);
+}
+
+// ---- peak_detector_offline::detect (zero-phase) -------------------------------------------------------------------------
+// One lane per detector, as k_peak, but every filter runs forward and then backward over the block, so a lane keeps its
+// block in a caller-owned workspace.  A wave's slab holds, for its 64 lanes, three double arrays V, F, T and one int32 array
+// E, each [ns][64]: the 64 lanes touch 512 consecutive bytes for one t, whatever nch is.  Per block:
+//   asc   baseline forward -> V, band-pass forward (state only)
+//   desc  baseline backward in place, V = x - baseline; band-pass backward on x -> F
+//   asc   integrator forward on F^2 -> F            desc  integrator backward -> F (filt_signal)
+//   asc   threshold forward (state only)            desc  threshold backward -> T (threshold_signal)
+//   asc   the state machine over (F, T): peak_signal p written over T (T[t] is read before p[t] is written), with the
+//         shift folded in (below); E lists the non-zero positions of p
+//   the relocation, event by event, on the dense p; then one ascending pass over p for the counts and events.
+// The shift loop moves p[i] to p[i - nslope + 1] for ascending i >= nslope.  Its target is never ahead of i and its source
+// is never a target of an earlier move, so performing each move at the moment the state machine writes p[i] is the same
+// thing; with nslope 1 the move is onto itself, and p[i] = 0 then removes it, as in the reference.
+
+struct PeakOffCoef {
+    PeakCoef c;              // band-pass (3 coefficients), integrator (2), threshold (3), atten, marker, nslope, hist
+    double lf[2], lb[2];     // baseline low-pass (0.5 Hz, order 1)
+    int32_t radius;          // (int)(10 fs / 1000)
+};
+
+struct PeakOffArgs {
+    const uint8_t* src;
+    uint64_t block_bytes;
+    uint32_t stride, nch, ns, nblocks;
+    uint32_t lanes;          // nblocks * nch (fresh) or nch (stateful)
+    uint8_t* state;          // stateful: the caller's state (PeakStateView), else null
+    uint8_t* work;           // ceil(lanes / 64) slabs of kPeakOffSlabBytesPerSample * ns bytes
+    uint32_t* count;
+    int32_t* index;
+    double* value;
+    uint64_t max_peaks;
+    double* sig;
+    double* thr;
+};
+
+// bytes of a wave's slab per sample: three double arrays and one int32 array of 64 lanes
+constexpr uint64_t kPeakOffSlabBytesPerSample = 64ull * (3 * 8 + 4);
+
+// Walks t over [0, ns) (ascending) or (ns, 0] (descending), CH samples at a time, the next chunk's loads in flight while this
+// one runs.  load(t) may read what body writes: the chunk loaded ahead is never the one being written.
+template <int CH, bool DESC, class Ld, class Body>
+__device__ __forceinline__ void off_walk(uint32_t ns, Ld load, Body body) {
+    using T = decltype(load(0u));
+    T cur[CH], nxt[CH];
+    const uint32_t nfull = ns / CH;
+    auto at = [&](uint32_t i) { return DESC ? ns - 1u - i : i; };
+    if (nfull) {
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) cur[e] = load(at(e));
+    }
+    for (uint32_t k = 0; k < nfull; ++k) {
+        if (k + 1 < nfull) {
+#pragma unroll
+            for (uint32_t e = 0; e < CH; ++e) nxt[e] = load(at((k + 1) * CH + e));
+        }
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) body(at(k * CH + e), cur[e]);
+#pragma unroll
+        for (uint32_t e = 0; e < CH; ++e) cur[e] = nxt[e];
+    }
+    for (uint32_t i = nfull * CH; i < ns; ++i) body(at(i), load(at(i)));
+}
+
+struct OffPair {
+    double a, b;
+};
+
+// Runs detect() once: one block of one detector (D: band-pass, integrator, threshold, state machine; bl: the baseline).
+// V, F, T, E: this lane's column of its wave's slab (element t at [t * 64]).
+template <int BPS, bool TR>
+__device__ void peak_offline_block(PeakDet<kPeakOfflineFw>& D, PkFilt<2>& bl, const PeakOffCoef& k, const uint8_t* p, uint32_t stride,
+                                   uint32_t ns, bool aligned, double* V, double* F, double* T, int32_t* E, uint32_t* count, int32_t* index,
+                                   double* value, uint64_t max_peaks, double* sig, double* thr, uint32_t nch) {
+    const PeakCoef& c = k.c;
+    auto xs = [&](uint32_t t) { return (double)sample_load<BPS>(p + (size_t)t * stride, aligned); };
+    const double x0 = xs(0);
+    D.bp.history(c.bf, c.bb, x0, c.hist);  // bandpass_ then baseline_ init_history_values(ecg_signal[0], fs)
+    bl.history(k.lf, k.lb, x0, c.hist);
+    // baseline forward (stored), band-pass forward (state only)
+    off_walk<16, false>(ns, xs, [&](uint32_t t, double x) {
+        V[(size_t)t * 64] = bl.step(k.lf, k.lb, x);
+        D.bp.step(c.bf, c.bb, x);
+    });
+    // baseline backward in place (kept as x - baseline, all the relocation reads), band-pass backward on x again
+    off_walk<8, true>(ns, [&](uint32_t t) { return OffPair{xs(t), V[(size_t)t * 64]}; }, [&](uint32_t t, OffPair v) {
+        V[(size_t)t * 64] = v.a - bl.step(k.lf, k.lb, v.b);
+        F[(size_t)t * 64] = D.bp.step(c.bf, c.bb, v.a);
+    });
+    auto fs = [&](uint32_t t) { return F[(size_t)t * 64]; };
+    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step(c.gf, c.gb, f * f); });
+    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step(c.gf, c.gb, f); });
+    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { D.th.step(c.tf, c.tb, f); });
+    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { T[(size_t)t * 64] = D.th.step(c.tf, c.tb, f); });
+    // the state machine; p over T, the shift folded in; E: the non-zero positions of p, those below nslope first (n0 of them)
+    const uint32_t nslope = (uint32_t)c.nslope;  // (>= 1: the host refuses 0)
+    uint32_t n = 0, n0 = 0;
+    off_walk<8, false>(ns, [&](uint32_t t) { return OffPair{F[(size_t)t * 64], T[(size_t)t * 64]}; }, [&](uint32_t t, OffPair v) {
+        if (TR) {
+            sig[(size_t)t * nch] = v.a;
+            thr[(size_t)t * nch] = v.b;
+        }
+        const bool fire = D.machine(c, v.a, v.b);
+        const double val = c.marker == -1.0 ? v.a : c.marker;
+        const bool ev = fire && val != 0.0;  // (`if (peak_signal[i])`: NaN is an event, -0.0 is not)
+        const bool below = t < nslope;
+        T[(size_t)t * 64] = ev && below ? val : 0.0;
+        if (ev && (below || nslope > 1)) {
+            const uint32_t at = below ? t : t - nslope + 1u;
+            if (!below) T[(size_t)at * 64] = val;
+            E[(size_t)n * 64] = (int32_t)at;
+            n += 1;
+            n0 += below ? 1u : 0u;
+        }
+    });
+    // the relocation: visits the non-zero p[i], radius <= i <= ns - radius - 1, in ascending order, as the reference's loop
+    // does -- including a value moved ahead of i (visited again) and a value written over another (the later write wins).
+    // The candidates past the last visit `pos` are the E positions and, up to `fwd`, the targets of moves ahead.
+    const int32_t r = k.radius;
+    const int32_t lim = (int32_t)ns - r - 1;
+    int32_t pos = r - 1, fwd = -1;
+    uint32_t ia = 0, ib = n0;
+    constexpr int32_t kNone = 0x7fffffff;
+    for (;;) {
+        while (ia < n0 && E[(size_t)ia * 64] <= pos) ++ia;
+        while (ib < n && E[(size_t)ib * 64] <= pos) ++ib;
+        const int32_t ca = ia < n0 ? E[(size_t)ia * 64] : kNone, cb = ib < n ? E[(size_t)ib * 64] : kNone;
+        int32_t q = ca < cb ? ca : cb;
+        if (fwd > pos) {  // a dense look at (pos, min(fwd, q - 1)], 8 loads at a time
+            const int32_t hi = fwd < q - 1 ? fwd : q - 1;
+            for (int32_t a0 = pos + 1; a0 <= hi; a0 += 8) {
+                double w[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) w[u] = T[(size_t)(a0 + u <= hi ? a0 + u : hi) * 64];
+                int32_t f = kNone;
+#pragma unroll
+                for (int u = 7; u >= 0; --u) f = (a0 + u <= hi && w[u] != 0.0) ? a0 + u : f;
+                if (f != kNone) {
+                    q = f;
+                    break;
+                }
+            }
+        }
+        if (q > lim) break;
+        const double pv = T[(size_t)q * 64];
+        double mx = -2000000.0, mn = 2000000.0;
+        int32_t mxi = 0, mni = 0;
+        const int32_t j1 = q + r;  // (exclusive)
+        for (int32_t j0 = q - r; j0 < j1; j0 += 8) {
+            double w[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) w[u] = V[(size_t)(j0 + u < j1 ? j0 + u : j1 - 1) * 64];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (j0 + u < j1) {
+                    if (mx < w[u]) {
+                        mx = w[u];
+                        mxi = j0 + u;
+                    }
+                    if (mn > w[u]) {
+                        mn = w[u];
+                        mni = j0 + u;
+                    }
+                }
+            }
+        }
+        const int32_t to = mx > -mn ? mxi : mni;
+        T[(size_t)q * 64] = 0.0;
+        T[(size_t)to * 64] = pv;
+        if (to > q && to > fwd) fwd = to;
+        pos = q;
+    }
+    // the counts and the events: the non-zero final p in ascending order
+    uint32_t cnt = 0;
+    off_walk<16, false>(ns, [&](uint32_t t) { return T[(size_t)t * 64]; }, [&](uint32_t t, double v) {
+        if (v != 0.0) {
+            if (cnt < max_peaks) {
+                index[cnt] = (int32_t)t;
+                value[cnt] = v;
+            }
+            ++cnt;
+        }
+    });
+    count[0] = cnt;
+}
+
+// The baseline filter of the offline object lives in band-pass slots 3-4 of the state (x) and 8-9 (y), which OFFLINE_FW's
+// three-coefficient band-pass never reads or writes: one state can take detect_fw and detect calls in turn.
+__device__ __forceinline__ void off_baseline_load(PkFilt<2>& bl, const uint8_t* st, uint32_t nch, uint32_t c) {
+    const double* d = reinterpret_cast<const double*>(st);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        bl.x[i] = d[(size_t)(3 + i) * nch + c];
+        bl.y[i] = d[(size_t)(8 + i) * nch + c];
+    }
+}
+__device__ __forceinline__ void off_baseline_save(const PkFilt<2>& bl, uint8_t* st, uint32_t nch, uint32_t c) {
+    double* d = reinterpret_cast<double*>(st);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        d[(size_t)(3 + i) * nch + c] = bl.x[i];
+        d[(size_t)(8 + i) * nch + c] = bl.y[i];
+    }
+}
+
+// One lane per detector: lane q = (block q / nch, channel q % nch) fresh, or channel q through every block (stateful).
+template <int BPS, bool TR>
+__global__ __launch_bounds__(64) void k_peak_offline(PeakOffArgs a, PeakOffCoef k) {
+    const uint32_t q = blockIdx.x * 64u + threadIdx.x;
+    if (q >= a.lanes) return;
+    const bool aligned = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(a.src) % BPS) == 0 && (a.block_bytes % BPS) == 0;
+    double* V = reinterpret_cast<double*>(a.work + (size_t)blockIdx.x * kPeakOffSlabBytesPerSample * a.ns) + threadIdx.x;
+    double* F = V + (size_t)64 * a.ns;
+    double* T = F + (size_t)64 * a.ns;
+    int32_t* E = reinterpret_cast<int32_t*>(T - threadIdx.x + (size_t)64 * a.ns) + threadIdx.x;
+    PeakDet<kPeakOfflineFw> D;
+    PkFilt<2> bl;
+    uint32_t b0, b1, ch;
+    if (a.state) {
+        ch = q;
+        b0 = 0;
+        b1 = a.nblocks;
+        D.load(a.state, a.nch, ch);
+        off_baseline_load(bl, a.state, a.nch, ch);
+    } else {
+        b0 = q / a.nch;
+        ch = q - b0 * a.nch;
+        b1 = b0 + 1;
+        D.clear();
+        bl.x[0] = bl.x[1] = bl.y[0] = bl.y[1] = 0.0;
+    }
+    for (uint32_t b = b0; b < b1; ++b) {
+        const uint64_t pair = (uint64_t)b * a.nch + ch;
+        const uint64_t tr = (uint64_t)b * a.ns * a.nch + ch;
+        peak_offline_block<BPS, TR>(D, bl, k, a.src + (size_t)b * a.block_bytes + (size_t)ch * BPS, a.stride, a.ns, aligned, V, F, T, E,
+                                    a.count + pair, a.index + pair * a.max_peaks, a.value + pair * a.max_peaks, a.max_peaks,
+                                    TR ? a.sig + tr : nullptr, TR ? a.thr + tr : nullptr, a.nch);
+    }
+    if (a.state) {
+        D.save(a.state, a.nch, ch);
+        off_baseline_save(bl, a.state, a.nch, ch);
+    }
 }
 
 }  // namespace rspt

@@ -2089,6 +2089,69 @@ int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t
     return RSPT_HIP_OK;
 }
 
+int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int stateful, size_t* bytes) {
+    if (!p || !bytes || nblocks == 0) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
+    const uint64_t lanes = stateful ? g.nch : (uint64_t)nblocks * g.nch;
+    *bytes = (size_t)(((lanes + 63) / 64) * kPeakOffSlabBytesPerSample * g.ns);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
+                                           void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
+                                           size_t max_peaks, double* d_sig, double* d_threshold, void* stream) {
+    if (!p || !d_src || !d_count || !d_work || nblocks == 0) return RSPT_HIP_ERR_ARG;
+    if (((uintptr_t)d_work % 8) != 0) return RSPT_HIP_ERR_ARG;
+    if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return RSPT_HIP_ERR_ARG;
+    if (max_peaks > 0 && (!d_index || !d_value)) return RSPT_HIP_ERR_ARG;
+    if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
+    // the reference's undefined cases: nr_slope_samples 0 (the shift runs every event off the end of the array) and a block
+    // shorter than the relocation radius (the unsigned bound len - radius wraps)
+    const int32_t nslope = (int32_t)((100.0 * sampling_rate) / 1000.0);
+    const int32_t radius = (int32_t)((10.0 * sampling_rate) / 1000.0);
+    if (nslope == 0 || (uint64_t)g.ns < (uint64_t)radius) return RSPT_HIP_ERR_ARG;
+    // peak_detector_offline's constructor: create_filter_iir(f.d, f.n, ...), the numerator as d
+    PeakOffCoef k{};
+    PeakCoef& c = k.c;
+    if (!design_iir(kFiltBandPass, 1, sampling_rate, 15.0, 25.0, c.bf, c.bb) || !design_iir(kFiltLowPass, 1, sampling_rate, 3.0, 0.0, c.gf, c.gb) ||
+        !design_iir(kFiltLowPass, 1, sampling_rate, 0.5, 0.0, k.lf, k.lb) || !design_iir(kFiltLowPass, 2, sampling_rate, 0.15, 0.0, c.tf, c.tb))
+        return RSPT_HIP_ERR_ARG;  // (not reached: every design is valid for fs > 0)
+    c.atten = 1.0 / (1.0 + 70.0 / sampling_rate);
+    c.marker = marker_val;
+    c.nslope = nslope;
+    c.hist = 4 * (int32_t)sampling_rate;
+    k.radius = radius;
+    PeakOffArgs a{};
+    a.src = (const uint8_t*)d_src;
+    a.block_bytes = g.block_bytes;
+    a.stride = g.nch * g.bps;
+    a.nch = g.nch;
+    a.ns = g.ns;
+    a.nblocks = (uint32_t)nblocks;
+    a.lanes = d_state ? g.nch : (uint32_t)(nblocks * g.nch);
+    a.state = (uint8_t*)d_state;
+    a.work = (uint8_t*)d_work;
+    a.count = d_count;
+    a.index = d_index;
+    a.value = d_value;
+    a.max_peaks = max_peaks;
+    a.sig = d_sig;
+    a.thr = d_threshold;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t grid = (a.lanes + 63) / 64;
+    by_bps(g.bps, [&](auto bb) {
+        constexpr int B = decltype(bb)::value;
+        if (d_sig) hipLaunchKernelGGL((k_peak_offline<B, true>), dim3(grid), dim3(64), 0, st, a, k);
+        else hipLaunchKernelGGL((k_peak_offline<B, false>), dim3(grid), dim3(64), 0, st, a, k);
+    });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
 // ---- multi-GPU gather over RCCL.  RCCL is bound at run time: a process that never gathers (the C++ drop-in on one
 // GPU, the tests on the CPU box) does not load it.  A communicator must never cross library instances -- an ncclComm_t made by one
 // copy of RCCL is garbage to another (PyTorch wheels bundle their own librccl.so next to /opt/rocm's) -- so the binding goes to the
