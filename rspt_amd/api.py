@@ -412,21 +412,15 @@ class SignalPacker:
 
         return torch.zeros(self.peak_state_bytes(), dtype=torch.uint8, device=device if device is not None else "cuda")
 
-    def peak_detect_batch(self, d_src, variant="online", sampling_rate=None, marker_val=1.0, max_peaks=64, state=None, traces=False, stream=None):
-        """The reference's R-peak detectors (peak_detector.h; rspt_hip.h: rspt_hip_peak_detect_batch_dev) on device-resident
-        blocks, which are only read.  variant: "online" (peak_detector), "online_1st" (peak_detector_1st_order) or "offline_fw"
-        (peak_detector_offline::detect_fw).  state: None for a fresh detector per (block, channel), or a peak_state() tensor that
-        carries one detector per channel through the blocks and across calls (of one variant and sampling rate).  Asynchronous.
-        Returns (count [nblocks, nch] int32, index [nblocks, nch, max_peaks] int32, value [nblocks, nch, max_peaks] float64) and,
-        with traces, (sig, threshold) [nblocks, ns, nch] float64 as well."""
+    def _peak_call_buffers(self, d_src, max_peaks, state, traces, stream):
+        """What both peak entries share: checks d_src (whole blocks of contiguous uint8 on the device) and state, allocates
+        (count, index, value, sig, thr) -- sig and thr None without traces -- and picks the stream (the current one when None).
+        -> (nblocks, outputs, stream, ptr); ptr(t): t's device pointer, None for None or an empty tensor."""
         import torch
 
         assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
-        if sampling_rate is None:
-            raise ValueError("peak_detect_batch: sampling_rate is required")
         nblocks = d_src.numel() // self.block_bytes
         assert nblocks * self.block_bytes == d_src.numel()
-        v = PEAK_VARIANTS[variant] if isinstance(variant, str) else int(variant)
         dev = d_src.device
         count = torch.empty((nblocks, self.nch), dtype=torch.int32, device=dev)
         index = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.int32, device=dev)
@@ -439,10 +433,24 @@ class SignalPacker:
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.peak_state_bytes()
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        return nblocks, (count, index, value, sig, thr), st, ptr
+
+    def peak_detect_batch(self, d_src, variant="online", sampling_rate=None, marker_val=1.0, max_peaks=64, state=None, traces=False, stream=None):
+        """The reference's R-peak detectors (peak_detector.h; rspt_hip.h: rspt_hip_peak_detect_batch_dev) on device-resident
+        blocks, which are only read.  variant: "online" (peak_detector), "online_1st" (peak_detector_1st_order) or "offline_fw"
+        (peak_detector_offline::detect_fw).  state: None for a fresh detector per (block, channel), or a peak_state() tensor that
+        carries one detector per channel through the blocks and across calls (of one variant and sampling rate).  Asynchronous.
+        Returns (count [nblocks, nch] int32, index [nblocks, nch, max_peaks] int32, value [nblocks, nch, max_peaks] float64) and,
+        with traces, (sig, threshold) [nblocks, ns, nch] float64 as well."""
+        if sampling_rate is None:
+            raise ValueError("peak_detect_batch: sampling_rate is required")
+        v = PEAK_VARIANTS[variant] if isinstance(variant, str) else int(variant)
+        nblocks, out, st, ptr = self._peak_call_buffers(d_src, max_peaks, state, traces, stream)
+        count, index, value, sig, thr = out
         rc = self._L.rspt_hip_peak_detect_batch_dev(self._h, d_src.data_ptr(), nblocks, v, float(sampling_rate), float(marker_val), ptr(state),
                                                     count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
         self._check("rspt_hip_peak_detect_batch_dev", rc)
-        return (count, index, value, sig, thr) if traces else (count, index, value)
+        return out if traces else out[:3]
 
     def peak_offline_work_bytes(self, nblocks, stateful=False):
         n = C.c_size_t()
@@ -458,28 +466,16 @@ class SignalPacker:
         and, with traces, (filt_signal, threshold_signal) [nblocks, ns, nch] float64 as well."""
         import torch
 
-        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
-        nblocks = d_src.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_src.numel()
+        nblocks, out, st, ptr = self._peak_call_buffers(d_src, max_peaks, state, traces, stream)
+        count, index, value, sig, thr = out
         dev = d_src.device
-        count = torch.empty((nblocks, self.nch), dtype=torch.int32, device=dev)
-        index = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.int32, device=dev)
-        value = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.float64, device=dev)
-        sig = thr = None
-        if traces:
-            sig = torch.empty((nblocks, self.ns, self.nch), dtype=torch.float64, device=dev)
-            thr = torch.empty_like(sig)
-        if state is not None:
-            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.peak_state_bytes()
         work = torch.empty(max(1, (self.peak_offline_work_bytes(max(nblocks, 1), state is not None) + 7) // 8), dtype=torch.float64, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
         rc = self._L.rspt_hip_peak_detect_offline_batch_dev(self._h, d_src.data_ptr(), nblocks, float(sampling_rate), float(marker_val), ptr(state),
                                                             work.data_ptr(), count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
         self._check("rspt_hip_peak_detect_offline_batch_dev", rc)
         if stream is not None:  # (the workspace goes back to torch's pool only once the caller's stream is past this call)
             work.record_stream(torch.cuda.ExternalStream(stream, device=dev))
-        return (count, index, value, sig, thr) if traces else (count, index, value)
+        return out if traces else out[:3]
 
     def synchronize(self):
         self._check("rspt_hip_synchronize", self._L.rspt_hip_synchronize(self._h))

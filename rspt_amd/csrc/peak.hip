@@ -7,6 +7,11 @@
 // detector and walks its samples in order.  Lanes map to flat (block, channel) pairs (a fresh detector each), or to the
 // channels alone when the caller keeps one detector per channel across blocks and calls (stateful mode).
 //
+// k_peak and k_peak_offline share one frame: their arguments (PeakArgs; PeakOffArgs adds the workspace), their detector state
+// (PeakDet; PeakDet<OFFLINE_FW, true> adds the offline object's baseline in unused state slots), the alignment test
+// (peak_aligned) and each (block, channel)'s output pointers (peak_out).  The few lines of lane mapping stay in each kernel: moved
+// into a helper they changed k_peak's register allocation.
+//
 // Double arithmetic in the reference's order of operations, every product and sum rounded on its own (no FMA: see the pragma),
 // so every trace value and every event is bit-identical with the reference's x86-64 build.
 #include <cmath>
@@ -159,6 +164,11 @@ struct PeakArgs {
     double* thr;
 };
 
+// k_peak_offline's arguments: k_peak's and the workspace
+struct PeakOffArgs : PeakArgs {
+    uint8_t* work;         // ceil(lanes / 64) slabs of kPeakOffSlabBytesPerSample * ns bytes
+};
+
 // The state of one detector per channel, structure of arrays so that lanes of a wave touch consecutive words: 24 doubles
 // [field][nch] -- band-pass x[5] y[5], integrator x[3] y[3], threshold x[3] y[3] (newest first), previous peak amplitude,
 // previous signal value -- then 4 int32 [field][nch]: searching, samples after the peak, sample index, (unused).  All zero is
@@ -207,10 +217,21 @@ struct PkFilt {
     }
 };
 
-template <int V>
-struct PeakDet {
+// BL: with the baseline filter bl of the offline object (k_peak_offline).  It lives in band-pass slots 3-4 of the state (x) and
+// 8-9 (y), which OFFLINE_FW's three-coefficient band-pass never reads or writes: one state can take detect_fw and detect calls
+// in turn.  (A base of its own, so that the detectors without it keep their layout.)
+template <bool BL>
+struct PeakBaseline {};
+template <>
+struct PeakBaseline<true> {
+    PkFilt<2> bl;
+};
+
+template <int V, bool BL = false>
+struct PeakDet : PeakBaseline<BL> {
     static constexpr int NB = V == kPeakOnline ? 5 : 3;  // iir_filter_4th_order / iir_filter_2nd_order
     static constexpr int NG = V == kPeakOnline ? 3 : 2;  // iir_filter_2nd_order / iir_filter_1st_order
+    static_assert(!BL || V == kPeakOfflineFw, "the baseline belongs to the offline object");
     PkFilt<NB> bp;
     PkFilt<NG> ig;
     PkFilt<3> th;
@@ -228,6 +249,7 @@ struct PeakDet {
         prev_amp = prev_sig = 0.0;
         searching = after = 0;
         idx = 0;
+        if constexpr (BL) this->bl.x[0] = this->bl.x[1] = this->bl.y[0] = this->bl.y[1] = 0.0;
     }
     __device__ void load(const uint8_t* st, uint32_t nch, uint32_t c) {
         const double* d = reinterpret_cast<const double*>(st);
@@ -252,6 +274,13 @@ struct PeakDet {
         searching = w[c];
         after = w[(size_t)nch + c];
         idx = (uint32_t)w[(size_t)2 * nch + c];
+        if constexpr (BL) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                this->bl.x[i] = d[(size_t)(3 + i) * nch + c];
+                this->bl.y[i] = d[(size_t)(8 + i) * nch + c];
+            }
+        }
     }
     __device__ void save(uint8_t* st, uint32_t nch, uint32_t c) const {
         double* d = reinterpret_cast<double*>(st);
@@ -276,6 +305,13 @@ struct PeakDet {
         w[c] = searching;
         w[(size_t)nch + c] = after;
         w[(size_t)2 * nch + c] = (int32_t)idx;
+        if constexpr (BL) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                d[(size_t)(3 + i) * nch + c] = this->bl.x[i];
+                d[(size_t)(8 + i) * nch + c] = this->bl.y[i];
+            }
+        }
     }
 
     // Everything of detect() behind the band-pass output s: squaring and the integrator, the threshold, the state machine
@@ -393,13 +429,35 @@ __device__ void peak_block(PeakDet<V>& D, const PeakCoef& c, const uint8_t* p, u
     count[0] = cnt;
 }
 
+// Whether both kernels' sample loads may be whole words: wave-uniform, as every block base and row start is aligned when the
+// first one is and the sizes are multiples.
+template <int BPS>
+__device__ __forceinline__ bool peak_aligned(const PeakArgs& a) {
+    return (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(a.src) % BPS) == 0 && (a.block_bytes % BPS) == 0;
+}
+
+// What the detector of channel ch writes for block b: its count, its first max_peaks events and (TR) its traces, whose samples
+// are nch doubles apart.
+struct PeakOut {
+    uint32_t* count;
+    int32_t* index;
+    double* value;
+    double* sig;
+    double* thr;
+};
+template <bool TR>
+__device__ __forceinline__ PeakOut peak_out(const PeakArgs& a, uint32_t b, uint32_t ch) {
+    const uint64_t pair = (uint64_t)b * a.nch + ch;
+    const uint64_t tr = (uint64_t)b * a.ns * a.nch + ch;
+    return PeakOut{a.count + pair, a.index + pair * a.max_peaks, a.value + pair * a.max_peaks, TR ? a.sig + tr : nullptr, TR ? a.thr + tr : nullptr};
+}
+
 // One lane per detector: lane q = (block q / nch, channel q % nch) fresh, or channel q through every block (stateful).
 template <int BPS, int V, bool TR>
 __global__ __launch_bounds__(64) void k_peak(PeakArgs a, PeakCoef c) {
     const uint32_t q = blockIdx.x * 64u + threadIdx.x;
     if (q >= a.lanes) return;
-    // (wave-uniform: every block base and row start is aligned when the first one is and the sizes are multiples)
-    const bool aligned = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(a.src) % BPS) == 0 && (a.block_bytes % BPS) == 0;
+    const bool aligned = peak_aligned<BPS>(a);
     PeakDet<V> D;
     uint32_t b0, b1, ch;
     if (a.state) {
@@ -414,11 +472,9 @@ __global__ __launch_bounds__(64) void k_peak(PeakArgs a, PeakCoef c) {
         D.clear();
     }
     for (uint32_t b = b0; b < b1; ++b) {
-        const uint64_t pair = (uint64_t)b * a.nch + ch;
-        const uint64_t tr = (uint64_t)b * a.ns * a.nch + ch;
-        peak_block<BPS, V, TR>(D, c, a.src + (size_t)b * a.block_bytes + (size_t)ch * BPS, a.stride, a.ns, aligned, a.count + pair,
-                               a.index + pair * a.max_peaks, a.value + pair * a.max_peaks, a.max_peaks, TR ? a.sig + tr : nullptr,
-                               TR ? a.thr + tr : nullptr, a.nch);
+        const PeakOut o = peak_out<TR>(a, b, ch);
+        peak_block<BPS, V, TR>(D, c, a.src + (size_t)b * a.block_bytes + (size_t)ch * BPS, a.stride, a.ns, aligned, o.count, o.index, o.value,
+                               a.max_peaks, o.sig, o.thr, a.nch);
     }
     if (a.state) D.save(a.state, a.nch, ch);
 }
@@ -442,21 +498,6 @@ struct PeakOffCoef {
     PeakCoef c;              // band-pass (3 coefficients), integrator (2), threshold (3), atten, marker, nslope, hist
     double lf[2], lb[2];     // baseline low-pass (0.5 Hz, order 1)
     int32_t radius;          // (int)(10 fs / 1000)
-};
-
-struct PeakOffArgs {
-    const uint8_t* src;
-    uint64_t block_bytes;
-    uint32_t stride, nch, ns, nblocks;
-    uint32_t lanes;          // nblocks * nch (fresh) or nch (stateful)
-    uint8_t* state;          // stateful: the caller's state (PeakStateView), else null
-    uint8_t* work;           // ceil(lanes / 64) slabs of kPeakOffSlabBytesPerSample * ns bytes
-    uint32_t* count;
-    int32_t* index;
-    double* value;
-    uint64_t max_peaks;
-    double* sig;
-    double* thr;
 };
 
 // bytes of a wave's slab per sample: three double arrays and one int32 array of 64 lanes
@@ -491,25 +532,25 @@ struct OffPair {
     double a, b;
 };
 
-// Runs detect() once: one block of one detector (D: band-pass, integrator, threshold, state machine; bl: the baseline).
+// Runs detect() once: one block of one detector (band-pass, integrator, threshold, state machine and the baseline D.bl).
 // V, F, T, E: this lane's column of its wave's slab (element t at [t * 64]).
 template <int BPS, bool TR>
-__device__ void peak_offline_block(PeakDet<kPeakOfflineFw>& D, PkFilt<2>& bl, const PeakOffCoef& k, const uint8_t* p, uint32_t stride,
+__device__ void peak_offline_block(PeakDet<kPeakOfflineFw, true>& D, const PeakOffCoef& k, const uint8_t* p, uint32_t stride,
                                    uint32_t ns, bool aligned, double* V, double* F, double* T, int32_t* E, uint32_t* count, int32_t* index,
                                    double* value, uint64_t max_peaks, double* sig, double* thr, uint32_t nch) {
     const PeakCoef& c = k.c;
     auto xs = [&](uint32_t t) { return (double)sample_load<BPS>(p + (size_t)t * stride, aligned); };
     const double x0 = xs(0);
     D.bp.history(c.bf, c.bb, x0, c.hist);  // bandpass_ then baseline_ init_history_values(ecg_signal[0], fs)
-    bl.history(k.lf, k.lb, x0, c.hist);
+    D.bl.history(k.lf, k.lb, x0, c.hist);
     // baseline forward (stored), band-pass forward (state only)
     off_walk<16, false>(ns, xs, [&](uint32_t t, double x) {
-        V[(size_t)t * 64] = bl.step(k.lf, k.lb, x);
+        V[(size_t)t * 64] = D.bl.step(k.lf, k.lb, x);
         D.bp.step(c.bf, c.bb, x);
     });
     // baseline backward in place (kept as x - baseline, all the relocation reads), band-pass backward on x again
     off_walk<8, true>(ns, [&](uint32_t t) { return OffPair{xs(t), V[(size_t)t * 64]}; }, [&](uint32_t t, OffPair v) {
-        V[(size_t)t * 64] = v.a - bl.step(k.lf, k.lb, v.b);
+        V[(size_t)t * 64] = v.a - D.bl.step(k.lf, k.lb, v.b);
         F[(size_t)t * 64] = D.bp.step(c.bf, c.bb, v.a);
     });
     auto fs = [&](uint32_t t) { return F[(size_t)t * 64]; };
@@ -609,62 +650,35 @@ __device__ void peak_offline_block(PeakDet<kPeakOfflineFw>& D, PkFilt<2>& bl, co
     count[0] = cnt;
 }
 
-// The baseline filter of the offline object lives in band-pass slots 3-4 of the state (x) and 8-9 (y), which OFFLINE_FW's
-// three-coefficient band-pass never reads or writes: one state can take detect_fw and detect calls in turn.
-__device__ __forceinline__ void off_baseline_load(PkFilt<2>& bl, const uint8_t* st, uint32_t nch, uint32_t c) {
-    const double* d = reinterpret_cast<const double*>(st);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        bl.x[i] = d[(size_t)(3 + i) * nch + c];
-        bl.y[i] = d[(size_t)(8 + i) * nch + c];
-    }
-}
-__device__ __forceinline__ void off_baseline_save(const PkFilt<2>& bl, uint8_t* st, uint32_t nch, uint32_t c) {
-    double* d = reinterpret_cast<double*>(st);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        d[(size_t)(3 + i) * nch + c] = bl.x[i];
-        d[(size_t)(8 + i) * nch + c] = bl.y[i];
-    }
-}
-
 // One lane per detector: lane q = (block q / nch, channel q % nch) fresh, or channel q through every block (stateful).
 template <int BPS, bool TR>
 __global__ __launch_bounds__(64) void k_peak_offline(PeakOffArgs a, PeakOffCoef k) {
     const uint32_t q = blockIdx.x * 64u + threadIdx.x;
     if (q >= a.lanes) return;
-    const bool aligned = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(a.src) % BPS) == 0 && (a.block_bytes % BPS) == 0;
+    const bool aligned = peak_aligned<BPS>(a);
     double* V = reinterpret_cast<double*>(a.work + (size_t)blockIdx.x * kPeakOffSlabBytesPerSample * a.ns) + threadIdx.x;
     double* F = V + (size_t)64 * a.ns;
     double* T = F + (size_t)64 * a.ns;
     int32_t* E = reinterpret_cast<int32_t*>(T - threadIdx.x + (size_t)64 * a.ns) + threadIdx.x;
-    PeakDet<kPeakOfflineFw> D;
-    PkFilt<2> bl;
+    PeakDet<kPeakOfflineFw, true> D;
     uint32_t b0, b1, ch;
     if (a.state) {
         ch = q;
         b0 = 0;
         b1 = a.nblocks;
         D.load(a.state, a.nch, ch);
-        off_baseline_load(bl, a.state, a.nch, ch);
     } else {
         b0 = q / a.nch;
         ch = q - b0 * a.nch;
         b1 = b0 + 1;
         D.clear();
-        bl.x[0] = bl.x[1] = bl.y[0] = bl.y[1] = 0.0;
     }
     for (uint32_t b = b0; b < b1; ++b) {
-        const uint64_t pair = (uint64_t)b * a.nch + ch;
-        const uint64_t tr = (uint64_t)b * a.ns * a.nch + ch;
-        peak_offline_block<BPS, TR>(D, bl, k, a.src + (size_t)b * a.block_bytes + (size_t)ch * BPS, a.stride, a.ns, aligned, V, F, T, E,
-                                    a.count + pair, a.index + pair * a.max_peaks, a.value + pair * a.max_peaks, a.max_peaks,
-                                    TR ? a.sig + tr : nullptr, TR ? a.thr + tr : nullptr, a.nch);
+        const PeakOut o = peak_out<TR>(a, b, ch);
+        peak_offline_block<BPS, TR>(D, k, a.src + (size_t)b * a.block_bytes + (size_t)ch * BPS, a.stride, a.ns, aligned, V, F, T, E, o.count,
+                                    o.index, o.value, a.max_peaks, o.sig, o.thr, a.nch);
     }
-    if (a.state) {
-        D.save(a.state, a.nch, ch);
-        off_baseline_save(bl, a.state, a.nch, ch);
-    }
+    if (a.state) D.save(a.state, a.nch, ch);
 }
 
 }  // namespace rspt

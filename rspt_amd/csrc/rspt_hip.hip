@@ -664,6 +664,59 @@ static void launch_inv_native(rspt_hip_packer* p, uint32_t B, uint32_t nrow, voi
     hipLaunchKernelGGL((k_inv_native<XDELTA, CG>), ng, dim3(1024), lds, st, p->ws.planes, g, p->ws.dec_nb, nrow, p->ws.txor, p->ws.tsum, (uint8_t*)d_dst);
 }
 
+// The checks both peak entries make, and the kernel arguments from them (all of PeakOffArgs but its workspace): false where
+// either entry refuses the call.
+static bool peak_args(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, void* d_state, uint32_t* d_count,
+                      int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, PeakArgs& a) {
+    if (!p || !d_src || !d_count || nblocks == 0) return false;
+    if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return false;
+    if (max_peaks > 0 && (!d_index || !d_value)) return false;
+    if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return false;
+    const Geom& g = p->g;
+    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return false;
+    a.src = (const uint8_t*)d_src;
+    a.block_bytes = g.block_bytes;
+    a.stride = g.nch * g.bps;
+    a.nch = g.nch;
+    a.ns = g.ns;
+    a.nblocks = (uint32_t)nblocks;
+    a.lanes = d_state ? g.nch : (uint32_t)(nblocks * g.nch);
+    a.state = (uint8_t*)d_state;
+    a.count = d_count;
+    a.index = d_index;
+    a.value = d_value;
+    a.max_peaks = max_peaks;
+    a.sig = d_sig;
+    a.thr = d_threshold;
+    return true;
+}
+
+// A variant's three filters as the detector's constructor designs them (create_filter_iir(f.d, f.n, ...): numerator -> d), and
+// its constants.  (Every design is valid for fs > 0.)
+static bool peak_coef(int variant, double sampling_rate, double marker_val, PeakCoef& c) {
+    static const struct { int bp_order; double bp_lo, bp_hi; int ig_order; double A; } kVar[3] = {
+        {2, 10.0, 20.0, 2, 25.0}, {1, 10.0, 20.0, 1, 25.0}, {1, 15.0, 25.0, 1, 70.0}};
+    const auto& v = kVar[variant];
+    if (!design_iir(kFiltBandPass, v.bp_order, sampling_rate, v.bp_lo, v.bp_hi, c.bf, c.bb) ||
+        !design_iir(kFiltLowPass, v.ig_order, sampling_rate, 3.0, 0.0, c.gf, c.gb) ||
+        !design_iir(kFiltLowPass, 2, sampling_rate, 0.15, 0.0, c.tf, c.tb))
+        return false;
+    c.atten = 1.0 / (1.0 + v.A / sampling_rate);
+    c.marker = marker_val;
+    c.nslope = (int32_t)((100.0 * sampling_rate) / 1000.0);
+    c.hist = 4 * (int32_t)sampling_rate;
+    return true;
+}
+
+// One lane per detector, 64 to a workgroup, on the caller's stream.
+template <class Args, class Coef>
+static int peak_launch(rspt_hip_packer* p, void (*kern)(Args, Coef), const Args& a, const Coef& c, void* stream) {
+    HIPCHK(p, hipSetDevice(p->device));
+    hipLaunchKernelGGL(kern, dim3((a.lanes + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, c);
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
 extern "C" {
 
 const char* rspt_hip_status_string(int s) {
@@ -2032,61 +2085,22 @@ int rspt_hip_peak_state_bytes(rspt_hip_packer* p, size_t* bytes) {
 int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
                                    void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
                                    double* d_threshold, void* stream) {
-    if (!p || !d_src || !d_count || nblocks == 0) return RSPT_HIP_ERR_ARG;
-    if (variant < kPeakOnline || variant > kPeakOfflineFw) return RSPT_HIP_ERR_ARG;
-    if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return RSPT_HIP_ERR_ARG;
-    if (max_peaks > 0 && (!d_index || !d_value)) return RSPT_HIP_ERR_ARG;
-    if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return RSPT_HIP_ERR_ARG;
-    const Geom& g = p->g;
-    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
-    // the three filters as the detector's constructor designs them (create_filter_iir(f.d, f.n, ...): numerator -> d)
-    static const struct { int bp_order; double bp_lo, bp_hi; int ig_order; double A; } kVar[3] = {
-        {2, 10.0, 20.0, 2, 25.0}, {1, 10.0, 20.0, 1, 25.0}, {1, 15.0, 25.0, 1, 70.0}};
-    const auto& v = kVar[variant];
-    PeakCoef c{};
-    if (!design_iir(kFiltBandPass, v.bp_order, sampling_rate, v.bp_lo, v.bp_hi, c.bf, c.bb) ||
-        !design_iir(kFiltLowPass, v.ig_order, sampling_rate, 3.0, 0.0, c.gf, c.gb) ||
-        !design_iir(kFiltLowPass, 2, sampling_rate, 0.15, 0.0, c.tf, c.tb))
-        return RSPT_HIP_ERR_ARG;  // (not reached: every design is valid for fs > 0)
-    c.atten = 1.0 / (1.0 + v.A / sampling_rate);
-    c.marker = marker_val;
-    c.nslope = (int32_t)((100.0 * sampling_rate) / 1000.0);
-    c.hist = 4 * (int32_t)sampling_rate;
     PeakArgs a{};
-    a.src = (const uint8_t*)d_src;
-    a.block_bytes = g.block_bytes;
-    a.stride = g.nch * g.bps;
-    a.nch = g.nch;
-    a.ns = g.ns;
-    a.nblocks = (uint32_t)nblocks;
-    a.lanes = d_state ? g.nch : (uint32_t)(nblocks * g.nch);
-    a.state = (uint8_t*)d_state;
-    a.count = d_count;
-    a.index = d_index;
-    a.value = d_value;
-    a.max_peaks = max_peaks;
-    a.sig = d_sig;
-    a.thr = d_threshold;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t grid = (a.lanes + 63) / 64;
-    by_bps(g.bps, [&](auto bb) {
+    PeakCoef c{};
+    if (variant < kPeakOnline || variant > kPeakOfflineFw ||
+        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
+        !peak_coef(variant, sampling_rate, marker_val, c))
+        return RSPT_HIP_ERR_ARG;
+    return by_bps(p->g.bps, [&](auto bb) {
         constexpr int B = decltype(bb)::value;
-        auto go = [&](auto vv, auto tr) {
-            hipLaunchKernelGGL((k_peak<B, decltype(vv)::value, decltype(tr)::value>), dim3(grid), dim3(64), 0, st, a, c);
+        auto go = [&](auto vv) {
+            constexpr int V = decltype(vv)::value;
+            return peak_launch(p, d_sig ? &k_peak<B, V, true> : &k_peak<B, V, false>, a, c, stream);
         };
-        using O = std::integral_constant<int, kPeakOnline>;
-        using O1 = std::integral_constant<int, kPeakOnline1st>;
-        using F = std::integral_constant<int, kPeakOfflineFw>;
-        using T = std::true_type;
-        using N = std::false_type;
-        const bool tr = d_sig != nullptr;
-        if (variant == kPeakOnline) tr ? go(O(), T()) : go(O(), N());
-        else if (variant == kPeakOnline1st) tr ? go(O1(), T()) : go(O1(), N());
-        else tr ? go(F(), T()) : go(F(), N());
+        if (variant == kPeakOnline) return go(std::integral_constant<int, kPeakOnline>());
+        if (variant == kPeakOnline1st) return go(std::integral_constant<int, kPeakOnline1st>());
+        return go(std::integral_constant<int, kPeakOfflineFw>());
     });
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
 }
 
 int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int stateful, size_t* bytes) {
@@ -2101,55 +2115,23 @@ int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int sta
 int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
                                            void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
                                            size_t max_peaks, double* d_sig, double* d_threshold, void* stream) {
-    if (!p || !d_src || !d_count || !d_work || nblocks == 0) return RSPT_HIP_ERR_ARG;
-    if (((uintptr_t)d_work % 8) != 0) return RSPT_HIP_ERR_ARG;
-    if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return RSPT_HIP_ERR_ARG;
-    if (max_peaks > 0 && (!d_index || !d_value)) return RSPT_HIP_ERR_ARG;
-    if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return RSPT_HIP_ERR_ARG;
-    const Geom& g = p->g;
-    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
+    PeakOffArgs a{};
+    PeakOffCoef k{};
+    if (!d_work || ((uintptr_t)d_work % 8) != 0 ||
+        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
+        !peak_coef(kPeakOfflineFw, sampling_rate, marker_val, k.c))
+        return RSPT_HIP_ERR_ARG;
     // the reference's undefined cases: nr_slope_samples 0 (the shift runs every event off the end of the array) and a block
     // shorter than the relocation radius (the unsigned bound len - radius wraps)
-    const int32_t nslope = (int32_t)((100.0 * sampling_rate) / 1000.0);
-    const int32_t radius = (int32_t)((10.0 * sampling_rate) / 1000.0);
-    if (nslope == 0 || (uint64_t)g.ns < (uint64_t)radius) return RSPT_HIP_ERR_ARG;
-    // peak_detector_offline's constructor: create_filter_iir(f.d, f.n, ...), the numerator as d
-    PeakOffCoef k{};
-    PeakCoef& c = k.c;
-    if (!design_iir(kFiltBandPass, 1, sampling_rate, 15.0, 25.0, c.bf, c.bb) || !design_iir(kFiltLowPass, 1, sampling_rate, 3.0, 0.0, c.gf, c.gb) ||
-        !design_iir(kFiltLowPass, 1, sampling_rate, 0.5, 0.0, k.lf, k.lb) || !design_iir(kFiltLowPass, 2, sampling_rate, 0.15, 0.0, c.tf, c.tb))
-        return RSPT_HIP_ERR_ARG;  // (not reached: every design is valid for fs > 0)
-    c.atten = 1.0 / (1.0 + 70.0 / sampling_rate);
-    c.marker = marker_val;
-    c.nslope = nslope;
-    c.hist = 4 * (int32_t)sampling_rate;
-    k.radius = radius;
-    PeakOffArgs a{};
-    a.src = (const uint8_t*)d_src;
-    a.block_bytes = g.block_bytes;
-    a.stride = g.nch * g.bps;
-    a.nch = g.nch;
-    a.ns = g.ns;
-    a.nblocks = (uint32_t)nblocks;
-    a.lanes = d_state ? g.nch : (uint32_t)(nblocks * g.nch);
-    a.state = (uint8_t*)d_state;
+    k.radius = (int32_t)((10.0 * sampling_rate) / 1000.0);
+    if (k.c.nslope == 0 || (uint64_t)a.ns < (uint64_t)k.radius) return RSPT_HIP_ERR_ARG;
+    // peak_detector_offline's constructor adds the baseline: a 0.5 Hz first-order low-pass
+    if (!design_iir(kFiltLowPass, 1, sampling_rate, 0.5, 0.0, k.lf, k.lb)) return RSPT_HIP_ERR_ARG;
     a.work = (uint8_t*)d_work;
-    a.count = d_count;
-    a.index = d_index;
-    a.value = d_value;
-    a.max_peaks = max_peaks;
-    a.sig = d_sig;
-    a.thr = d_threshold;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t grid = (a.lanes + 63) / 64;
-    by_bps(g.bps, [&](auto bb) {
+    return by_bps(p->g.bps, [&](auto bb) {
         constexpr int B = decltype(bb)::value;
-        if (d_sig) hipLaunchKernelGGL((k_peak_offline<B, true>), dim3(grid), dim3(64), 0, st, a, k);
-        else hipLaunchKernelGGL((k_peak_offline<B, false>), dim3(grid), dim3(64), 0, st, a, k);
+        return peak_launch(p, d_sig ? &k_peak_offline<B, true> : &k_peak_offline<B, false>, a, k, stream);
     });
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
 }
 
 // ---- multi-GPU gather over RCCL.  RCCL is bound at run time: a process that never gathers (the C++ drop-in on one

@@ -260,6 +260,38 @@ def crc(a):
     return zlib.crc32(np.ascontiguousarray(a).tobytes())
 
 
+# ---- the GPU entries' results (torch is imported only here) ----
+
+def dev(data):
+    """native bytes -> a uint8 device tensor"""
+    import torch
+
+    return torch.from_numpy(np.array(data, dtype=np.uint8)).cuda()
+
+
+def to_result(out, max_peaks, traces=True):
+    """(count, index, value[, sig, thr]) tensors of a peak entry -> what detect returns (index / value lists cut at max_peaks)"""
+    count = out[0].cpu().numpy().astype(np.int64)
+    nblocks, nch = count.shape
+    idx, val = out[1].cpu().numpy(), out[2].cpu().numpy()
+    r = dict(count=count.tolist(),
+             index=[[idx[b, c, : min(count[b, c], max_peaks)].tolist() for c in range(nch)] for b in range(nblocks)],
+             value=[[val[b, c, : min(count[b, c], max_peaks)].tolist() for c in range(nch)] for b in range(nblocks)])
+    if traces:
+        r["sig"], r["thr"] = out[3].cpu().numpy(), out[4].cpu().numpy()
+    return r
+
+
+def events_equal(got, want, max_peaks=None):
+    """counts, indices (the first max_peaks) and value bits (NaNs made one)"""
+    assert got["count"] == want["count"]
+    cut = (lambda l: l[:max_peaks]) if max_peaks is not None else (lambda l: l)  # noqa: E731
+    for b in range(len(want["index"])):
+        for c in range(len(want["index"][b])):
+            assert got["index"][b][c] == cut(want["index"][b][c]), (b, c)
+            assert vhex(got["value"][b][c]) == vhex(cut(want["value"][b][c])), (b, c)
+
+
 # ---- the cases ----
 
 def _i32(a):

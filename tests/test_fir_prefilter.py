@@ -12,11 +12,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import devasm
 import fir_cases as fc
 from cases import digest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ERR_ARG = -1
 
 
@@ -99,27 +99,10 @@ def test_header_declares_the_entry_and_the_library_exports_it():
 
 
 @pytest.fixture(scope="module")
-def fir_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
+def fir_asm():
+    if not os.path.exists(devasm.HIPCC):
         pytest.skip("hipcc not found")
-    asm = str(tmp_path_factory.mktemp("asm") / "rspt.s")
-    subprocess.check_call(
-        [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", "-w",
-         "-I" + os.path.join(ROOT, "include"), "-o", asm, os.path.join(ROOT, "rspt_amd", "csrc", "rspt_hip.hip")]
-    )
-    funcs, cur = {}, None
-    for line in open(asm):
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            cur = m.group(1) if re.search(r"k_fir", m.group(1)) else None
-            if cur:
-                funcs[cur] = []
-        elif cur:
-            if line.startswith(".Lfunc_end"):
-                cur = None
-            else:
-                funcs[cur].append(line)
-    return funcs
+    return {n: body for n, body in devasm.functions().items() if re.search(r"k_fir", n)}
 
 
 def test_fir_kernels_round_every_product_and_sum_on_their_own(fir_asm):

@@ -14,10 +14,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import devasm
 import peak_cases as pc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ERR_ARG = -1
 
 
@@ -158,27 +158,10 @@ def test_header_declares_the_entries_and_the_library_exports_them():
 
 
 @pytest.fixture(scope="module")
-def peak_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
+def peak_asm():
+    if not os.path.exists(devasm.HIPCC):
         pytest.skip("hipcc not found")
-    asm = str(tmp_path_factory.mktemp("asm") / "rspt.s")
-    subprocess.check_call(
-        [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", "-w",
-         "-I" + os.path.join(ROOT, "include"), "-o", asm, os.path.join(ROOT, "rspt_amd", "csrc", "rspt_hip.hip")]
-    )
-    funcs, cur = {}, None
-    for line in open(asm):
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            cur = m.group(1) if re.search(r"k_peak|PkFilt|PeakDet|peak_block", m.group(1)) else None
-            if cur:
-                funcs[cur] = []
-        elif cur:
-            if line.startswith(".Lfunc_end"):
-                cur = None
-            else:
-                funcs[cur].append(line)
-    return funcs
+    return {n: body for n, body in devasm.functions().items() if re.search(r"k_peak|PkFilt|PeakDet|peak_block", n)}
 
 
 def test_peak_kernels_round_every_product_and_sum_on_their_own(peak_asm):
@@ -208,35 +191,11 @@ def gpu_result(pk, src, variant, fs, marker=1.0, max_peaks=None, state=None, tra
     """run the stage and bring back what pc.detect returns (index / value lists cut at max_peaks)"""
     import torch
 
-    nblocks = src.numel() // pk.block_bytes
     if max_peaks is None:
         max_peaks = pk.ns  # (room for every event)
     out = pk.peak_detect_batch(src, variant=variant, sampling_rate=fs, marker_val=marker, max_peaks=max_peaks, state=state, traces=traces)
     torch.cuda.synchronize()
-    count = out[0].cpu().numpy().astype(np.int64)
-    idx, val = out[1].cpu().numpy(), out[2].cpu().numpy()
-    r = dict(count=count.tolist(),
-             index=[[idx[b, c, : min(count[b, c], max_peaks)].tolist() for c in range(pk.nch)] for b in range(nblocks)],
-             value=[[val[b, c, : min(count[b, c], max_peaks)].tolist() for c in range(pk.nch)] for b in range(nblocks)])
-    if traces:
-        r["sig"], r["thr"] = out[3].cpu().numpy(), out[4].cpu().numpy()
-    return r
-
-
-def events_equal(got, want, max_peaks=None):
-    """counts, indices (the first max_peaks) and value bits (NaNs made one)"""
-    assert got["count"] == want["count"]
-    cut = (lambda l: l[:max_peaks]) if max_peaks is not None else (lambda l: l)  # noqa: E731
-    for b in range(len(want["index"])):
-        for c in range(len(want["index"][b])):
-            assert got["index"][b][c] == cut(want["index"][b][c]), (b, c)
-            assert pc.vhex(got["value"][b][c]) == pc.vhex(cut(want["value"][b][c])), (b, c)
-
-
-def _dev(data):
-    import torch
-
-    return torch.from_numpy(np.array(data, dtype=np.uint8)).cuda()
+    return pc.to_result(out, max_peaks, traces)
 
 
 VNAME = {v: k for k, v in pc.VARIANTS.items()}
@@ -249,7 +208,7 @@ def test_gpu_peak_bit_exact(api, pcases, name):
     events with the values s"""
     c = pcases[name]
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    src = _dev(c["data"])
+    src = pc.dev(c["data"])
     st = pk.peak_state() if c["stateful"] else None
     r = gpu_result(pk, src, VNAME[c["variant"]], c["fs"], 1.0, state=st)
     got, want = summary(r), c["rec"]
@@ -270,9 +229,9 @@ def test_gpu_peak_max_peaks_keeps_exact_counts(api, pcases, variant):
     c = pcases["walk3x400_i16_fs5_%s_fs5" % variant]
     want = pc.detect(pc.case_i32(c), c["variant"], c["fs"], 0.0)
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    src = _dev(c["data"])
+    src = pc.dev(c["data"])
     assert min(pc.flat([want["count"]])) > 3
-    events_equal(gpu_result(pk, src, variant, c["fs"], 0.0, max_peaks=3, traces=False), want, 3)
+    pc.events_equal(gpu_result(pk, src, variant, c["fs"], 0.0, max_peaks=3, traces=False), want, 3)
     count, index, value = pk.peak_detect_batch(src, variant=variant, sampling_rate=c["fs"], max_peaks=0)
     assert count.cpu().numpy().tolist() == want["count"] and index.numel() == 0 and value.numel() == 0
     pk.close()
@@ -287,7 +246,7 @@ def test_gpu_peak_stateful_calls_chain(api, variant):
     bps, nch, ns, B, fs = 4, 12, 3000, 4, 1000.0
     data = np.frombuffer(pc.synth.ecg_12ch_i32(), dtype=np.uint8)[: B * bps * nch * ns]
     pk = api.new_hzr(bps, nch, ns)
-    src = _dev(data)
+    src = pc.dev(data)
     whole = gpu_result(pk, src, variant, fs, -1.0, state=pk.peak_state())
     st = pk.peak_state()
     parts = [pk.peak_detect_batch(src[b * pk.block_bytes : (b + 1) * pk.block_bytes], variant=variant, sampling_rate=fs, marker_val=-1.0,
@@ -304,7 +263,7 @@ def test_gpu_peak_stateful_calls_chain(api, variant):
     assert fresh["count"][0] == whole["count"][0] and fresh["index"][0] == whole["index"][0]
     assert np.array_equal(fresh["sig"][0], whole["sig"][0])
     want = pc.detect(pc.native_to_i32(data, bps, nch, B * ns).reshape(B, ns, nch), pc.VARIANTS[variant], fs, -1.0, stateful=True)
-    events_equal(whole, want)
+    pc.events_equal(whole, want)
     assert pc.tdigest(whole["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(whole["thr"]) == pc.tdigest(want["thr"])
     pk.close()
 
@@ -329,7 +288,7 @@ def test_gpu_peak_odd_block_bytes_and_narrow_shapes(api, misalign):
         assert torch.equal(raw, before)  # (d_src is only read)
         want = pc.detect(np.stack([pc.native_to_i32(data[b * pk.block_bytes : (b + 1) * pk.block_bytes], bps, nch, ns) for b in range(nb)]),
                          pc.VARIANTS[variant], fs, -1.0)
-        events_equal(r, want)
+        pc.events_equal(r, want)
         assert pc.tdigest(r["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(r["thr"]) == pc.tdigest(want["thr"]), (bps, nch, ns)
         pk.close()
 
@@ -342,10 +301,10 @@ def test_gpu_peak_full_size_block(api):
     want = pc.detect(pc.native_to_i32(data, bps, nch, ns)[None], pc.ONLINE, fs, 1.0)
     assert sum(map(sum, want["count"])) > 64
     pk = api.new_xdelta_hzr(bps, nch, ns, 3)
-    src = _dev(data)
+    src = pc.dev(data)
     for st in (None, pk.peak_state()):
         r = gpu_result(pk, src, "online", fs, 1.0, max_peaks=256, state=st)
-        events_equal(r, want)
+        pc.events_equal(r, want)
         assert pc.tdigest(r["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(r["thr"]) == pc.tdigest(want["thr"])
     pk.close()
 
@@ -357,7 +316,7 @@ def test_gpu_peak_back_to_back_without_host_sync(api, pcases):
 
     names = ["ecg12x34199_i32_%s_fs%g" % (v, fs) for v in ("online", "online_1st", "offline_fw") for fs in (500, 2000)]
     pk = api.new_hzr(4, 12, 34199)
-    src = _dev(pcases[names[0]]["data"])
+    src = pc.dev(pcases[names[0]]["data"])
     outs = [pk.peak_detect_batch(src, variant=VNAME[pcases[n]["variant"]], sampling_rate=pcases[n]["fs"], max_peaks=64) for n in names]
     torch.cuda.synchronize()
     for n, (count, index, _) in zip(names, outs):
@@ -427,13 +386,13 @@ def test_gpu_peak_random_sweep(api):
     for k, bps, nch, ns, fs, variant, marker, max_peaks, nb, stateful, traces, amp in _sweep_cases():
         data = np.concatenate([pc.cases._rand_native(nch, ns, bps, 8000 + 7 * k + b, amp, walk=bool(k % 2)) for b in range(nb)])
         pk = api.new_hzr(bps, nch, ns)
-        r = gpu_result(pk, _dev(data), variant, fs, marker, max_peaks=max_peaks, state=pk.peak_state() if stateful else None, traces=traces)
+        r = gpu_result(pk, pc.dev(data), variant, fs, marker, max_peaks=max_peaks, state=pk.peak_state() if stateful else None, traces=traces)
         bb = pk.block_bytes
         want = pc.detect(np.stack([pc.native_to_i32(data[b * bb : (b + 1) * bb], bps, nch, ns) for b in range(nb)]), pc.VARIANTS[variant], fs,
                          marker, stateful)
         case = (k, bps, nch, ns, fs, variant, marker, max_peaks, nb, stateful, traces)
         assert r["count"] == want["count"], case
-        events_equal(r, want, max_peaks)
+        pc.events_equal(r, want, max_peaks)
         if traces:
             assert pc.tdigest(r["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(r["thr"]) == pc.tdigest(want["thr"]), case
         pk.close()
@@ -451,9 +410,9 @@ def test_gpu_designed_coefficients_feed_the_iir_prefilter(api):
     assert typed_num == want_num and typed_den == want_den
     data = np.frombuffer(pc.synth.ecg_12ch_i32(), dtype=np.uint8)[: 4 * 12 * 5000]
     pk = api.new_hzr(4, 12, 5000)
-    a, b = _dev(data), _dev(data)
+    a, b = pc.dev(data), pc.dev(data)
     pk.iir_prefilter_batch(a, n=den, d=num, init_nr_samples=2000, per_channel=True)
     pk.iir_prefilter_batch(b, n=typed_den, d=typed_num, init_nr_samples=2000, per_channel=True)
     torch.cuda.synchronize()
-    assert torch.equal(a, b) and not torch.equal(a, _dev(data))
+    assert torch.equal(a, b) and not torch.equal(a, pc.dev(data))
     pk.close()

@@ -12,11 +12,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import devasm
 import peak_cases as pc
 import peak_offline_cases as oc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ERR_ARG = -1
 
 
@@ -120,27 +120,10 @@ def test_work_bytes_refuses_a_null_handle():
 
 
 @pytest.fixture(scope="module")
-def offline_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
+def offline_asm():
+    if not os.path.exists(devasm.HIPCC):
         pytest.skip("hipcc not found")
-    asm = str(tmp_path_factory.mktemp("asm") / "rspt.s")
-    subprocess.check_call(
-        [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", "-w",
-         "-I" + os.path.join(ROOT, "include"), "-o", asm, os.path.join(ROOT, "rspt_amd", "csrc", "rspt_hip.hip")]
-    )
-    funcs, cur = {}, None
-    for line in open(asm):
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            cur = m.group(1) if re.search(r"k_peak_offline|peak_offline_block", m.group(1)) else None
-            if cur:
-                funcs[cur] = []
-        elif cur:
-            if line.startswith(".Lfunc_end"):
-                cur = None
-            else:
-                funcs[cur].append(line)
-    return funcs
+    return {n: body for n, body in devasm.functions().items() if re.search(r"k_peak_offline|peak_offline_block", n)}
 
 
 def test_offline_kernels_round_every_product_and_sum_on_their_own(offline_asm):
@@ -167,41 +150,14 @@ def api():
     return a
 
 
-def to_result(pk, out, nblocks, max_peaks, traces=True):
-    count = out[0].cpu().numpy().astype(np.int64)
-    idx, val = out[1].cpu().numpy(), out[2].cpu().numpy()
-    r = dict(count=count.tolist(),
-             index=[[idx[b, c, : min(count[b, c], max_peaks)].tolist() for c in range(pk.nch)] for b in range(nblocks)],
-             value=[[val[b, c, : min(count[b, c], max_peaks)].tolist() for c in range(pk.nch)] for b in range(nblocks)])
-    if traces:
-        r["sig"], r["thr"] = out[3].cpu().numpy(), out[4].cpu().numpy()
-    return r
-
-
 def gpu_result(pk, src, fs, marker=1.0, max_peaks=None, state=None, traces=True):
     import torch
 
-    nblocks = src.numel() // pk.block_bytes
     if max_peaks is None:
         max_peaks = pk.ns
     out = pk.peak_detect_offline_batch(src, fs, marker_val=marker, max_peaks=max_peaks, state=state, traces=traces)
     torch.cuda.synchronize()
-    return to_result(pk, out, nblocks, max_peaks, traces)
-
-
-def events_equal(got, want, max_peaks=None):
-    assert got["count"] == want["count"]
-    cut = (lambda l: l[:max_peaks]) if max_peaks is not None else (lambda l: l)  # noqa: E731
-    for b in range(len(want["index"])):
-        for c in range(len(want["index"][b])):
-            assert got["index"][b][c] == cut(want["index"][b][c]), (b, c)
-            assert pc.vhex(got["value"][b][c]) == pc.vhex(cut(want["value"][b][c])), (b, c)
-
-
-def _dev(data):
-    import torch
-
-    return torch.from_numpy(np.array(data, dtype=np.uint8)).cuda()
+    return pc.to_result(out, max_peaks, traces)
 
 
 def run_alternating(pk, src, c, marker, traces=True):
@@ -218,7 +174,7 @@ def run_alternating(pk, src, c, marker, traces=True):
             parts.append(pk.peak_detect_offline_batch(blk, c["fs"], marker_val=marker, max_peaks=pk.ns, state=st, traces=traces))
     torch.cuda.synchronize()
     out = [torch.cat([p[i] for p in parts]) for i in range(5 if traces else 3)]
-    return to_result(pk, out, len(c["calls"]), pk.ns, traces)
+    return pc.to_result(out, pk.ns, traces)
 
 
 @pytest.mark.gpu
@@ -227,7 +183,7 @@ def test_gpu_offline_bit_exact(api, ocases, name):
     """against the record: events and trace digests with marker 1.0 and traces; marker -1.0 without traces"""
     c = ocases[name]
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    src = _dev(c["data"])
+    src = pc.dev(c["data"])
     if c["calls"] is not None:
         r = run_alternating(pk, src, c, 1.0)
         m = run_alternating(pk, src, c, -1.0, traces=False)
@@ -246,9 +202,9 @@ def test_gpu_offline_max_peaks_keeps_exact_counts(api, ocases):
     c = ocases["ecg12x34199_i32_fs250"]
     want = oc.detect(oc.case_i32(c), c["fs"], -1.0)
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    src = _dev(c["data"])
+    src = pc.dev(c["data"])
     assert max(pc.flat([want["count"]])) > 3
-    events_equal(gpu_result(pk, src, c["fs"], -1.0, max_peaks=3, traces=False), want, 3)
+    pc.events_equal(gpu_result(pk, src, c["fs"], -1.0, max_peaks=3, traces=False), want, 3)
     count, index, value = pk.peak_detect_offline_batch(src, c["fs"], max_peaks=0)
     assert count.cpu().numpy().tolist() == want["count"] and index.numel() == 0 and value.numel() == 0
     pk.close()
@@ -262,7 +218,7 @@ def test_gpu_offline_stateful_calls_chain(api):
     bps, nch, ns, B, fs = 4, 12, 3000, 4, 1000.0
     data = np.frombuffer(pc.synth.ecg_12ch_i32(), dtype=np.uint8)[: B * bps * nch * ns]
     pk = api.new_hzr(bps, nch, ns)
-    src = _dev(data)
+    src = pc.dev(data)
     whole = gpu_result(pk, src, fs, -1.0, state=pk.peak_state())
     st = pk.peak_state()
     parts = [pk.peak_detect_offline_batch(src[b * pk.block_bytes : (b + 1) * pk.block_bytes], fs, marker_val=-1.0, max_peaks=ns, state=st,
@@ -279,7 +235,7 @@ def test_gpu_offline_stateful_calls_chain(api):
     assert fresh["count"][0] == whole["count"][0] and fresh["index"][0] == whole["index"][0]
     assert np.array_equal(fresh["sig"][0], whole["sig"][0])
     want = oc.detect(pc.native_to_i32(data, bps, nch, B * ns).reshape(B, ns, nch), fs, -1.0, stateful=True)
-    events_equal(whole, want)
+    pc.events_equal(whole, want)
     assert pc.tdigest(whole["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(whole["thr"]) == pc.tdigest(want["thr"])
     pk.close()
 
@@ -292,10 +248,10 @@ def test_gpu_offline_full_size_block(api):
     want = oc.detect(pc.native_to_i32(data, bps, nch, ns)[None], fs, 1.0)
     assert sum(map(sum, want["count"])) > 64
     pk = api.new_xdelta_hzr(bps, nch, ns, 3)
-    src = _dev(data)
+    src = pc.dev(data)
     for st in (None, pk.peak_state()):
         r = gpu_result(pk, src, fs, 1.0, max_peaks=256, state=st)
-        events_equal(r, want)
+        pc.events_equal(r, want)
         assert pc.tdigest(r["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(r["thr"]) == pc.tdigest(want["thr"])
     pk.close()
 
@@ -318,7 +274,7 @@ def test_gpu_offline_odd_block_bytes_and_narrow_shapes(api, misalign):
         r = gpu_result(pk, src, fs, -1.0)
         assert torch.equal(raw, before)
         want = oc.detect(np.stack([pc.native_to_i32(data[b * pk.block_bytes : (b + 1) * pk.block_bytes], bps, nch, ns) for b in range(nb)]), fs, -1.0)
-        events_equal(r, want)
+        pc.events_equal(r, want)
         assert pc.tdigest(r["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(r["thr"]) == pc.tdigest(want["thr"]), (bps, nch, ns)
         pk.close()
 
@@ -330,7 +286,7 @@ def test_gpu_offline_back_to_back_without_host_sync(api, ocases):
 
     names = ["ecg12x34199_i32_fs%d" % fs for fs in (250, 500, 1000, 2000)]
     pk = api.new_hzr(4, 12, 34199)
-    src = _dev(ocases[names[0]]["data"])
+    src = pc.dev(ocases[names[0]]["data"])
     outs = [pk.peak_detect_offline_batch(src, ocases[n]["fs"], max_peaks=256, state=pk.peak_state() if k % 2 else None) for k, n in enumerate(names)]
     torch.cuda.synchronize()
     for n, (count, index, _) in zip(names, outs):
@@ -409,12 +365,12 @@ def test_gpu_offline_random_sweep(api):
     for k, bps, nch, ns, fs, marker, max_peaks, nb, stateful, traces, amp in _sweep_cases():
         data = np.concatenate([pc.cases._rand_native(nch, ns, bps, 9000 + 7 * k + b, amp, walk=bool(k % 2)) for b in range(nb)])
         pk = api.new_hzr(bps, nch, ns)
-        r = gpu_result(pk, _dev(data), fs, marker, max_peaks=max_peaks, state=pk.peak_state() if stateful else None, traces=traces)
+        r = gpu_result(pk, pc.dev(data), fs, marker, max_peaks=max_peaks, state=pk.peak_state() if stateful else None, traces=traces)
         bb = pk.block_bytes
         want = oc.detect(np.stack([pc.native_to_i32(data[b * bb : (b + 1) * bb], bps, nch, ns) for b in range(nb)]), fs, marker, stateful)
         case = (k, bps, nch, ns, fs, marker, max_peaks, nb, stateful, traces)
         assert r["count"] == want["count"], case
-        events_equal(r, want, max_peaks)
+        pc.events_equal(r, want, max_peaks)
         if traces:
             assert pc.tdigest(r["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(r["thr"]) == pc.tdigest(want["thr"]), case
         pk.close()
@@ -426,7 +382,7 @@ def test_gpu_offline_and_detect_fw_differ(api, ocases):
     peaks, each the reference's"""
     c = ocases["ecg12x34199_i32_fs1000"]
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    src = _dev(c["data"])
+    src = pc.dev(c["data"])
     off = gpu_result(pk, src, c["fs"], traces=False)
     fw = pk.peak_detect_batch(src, variant="offline_fw", sampling_rate=c["fs"], max_peaks=pk.ns)
     import torch
@@ -453,7 +409,7 @@ def test_gpu_offline_relocation_collisions_sweep(api):
         cols.append(np.abs(((t + ph) % P) * 2 - P) * S + np.where((t % sp) < w, a, 0))
     data = pc._i32(np.stack(cols, axis=1))
     pk = api.new_hzr(4, nch, ns)
-    src = _dev(data)
+    src = pc.dev(data)
     ahead = 0
     for fs in (250.0, 200.0):
         st = {}
@@ -461,7 +417,7 @@ def test_gpu_offline_relocation_collisions_sweep(api):
         assert st["collisions"] > 0 and st["revisit_moves"] > 0, (fs, st)
         ahead += st["collisions_ahead"]
         r = gpu_result(pk, src, fs, -1.0)
-        events_equal(r, want)
+        pc.events_equal(r, want)
         assert pc.tdigest(r["sig"]) == pc.tdigest(want["sig"]) and pc.tdigest(r["thr"]) == pc.tdigest(want["thr"])
     assert ahead > 0
     pk.close()

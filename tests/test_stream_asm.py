@@ -11,20 +11,16 @@ import sys
 
 import pytest
 
+import devasm
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 @pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
+def device_asm():
+    if not os.path.exists(devasm.HIPCC):
         pytest.skip("hipcc not found")
-    asm = str(tmp_path_factory.mktemp("asm") / "rspt.s")
-    subprocess.check_call(
-        [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", "-w",
-         "-I" + os.path.join(ROOT, "include"), "-o", asm, os.path.join(ROOT, "rspt_amd", "csrc", "rspt_hip.hip")]
-    )
-    return asm
+    return devasm.asm_path()
 
 
 def test_no_register_is_touched_between_a_hand_issued_load_and_its_wait(device_asm):
@@ -84,25 +80,6 @@ def test_the_barrier_check_sees_the_hazard(tmp_path):
         assert ("1 barriers, %d unpublished" % want) in r.stdout, r.stdout
 
 
-def _kernel_bodies(asm_path):
-    """mangled kernel name -> its instruction lines (from the symbol's label to its .Lfunc_end)"""
-    import re
-
-    bodies, name, cur = {}, None, []
-    for ln in open(asm_path):
-        m = re.match(r"^(_Z\w+):\s", ln)
-        if m and name is None:
-            name, cur = m.group(1), []
-            continue
-        if name is not None:
-            if ln.startswith(".Lfunc_end"):
-                bodies[name] = cur
-                name = None
-            else:
-                cur.append(ln.strip())
-    return bodies
-
-
 def test_no_fused_multiply_add_where_the_reference_rounds_twice(device_asm):
     """The IIR pre-filter and the dct's table path restate the reference's arithmetic operation for operation: every product
     and every sum is rounded on its own (iir_filter.cpp:46-116, signal_packer_dct.cpp:76-87).  hipcc contracts a * b + c into
@@ -110,7 +87,7 @@ def test_no_fused_multiply_add_where_the_reference_rounds_twice(device_asm):
     count per ~2 M samples -- on no fixture, only on the full-size batch.  The ISA of these kernels must hold no fp FMA."""
     import re
 
-    bodies = _kernel_bodies(device_asm)
+    bodies = {k: [ln.strip() for ln in body] for k, body in devasm.functions().items()}
     fma = re.compile(r"^v_(fma|fmac|mad|mac|pk_fma)_(f64|f32|legacy_f32)\b")
     iir = [k for k in bodies if "k_iir" in k]
     dct = [k for k in bodies if re.search(r"5k_dctILb[01]E", k)]  # rspt::k_dct<true|false>: the dense-table transform

@@ -14,9 +14,7 @@ import argparse
 import json
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import torch
@@ -25,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import devasm  # noqa: E402
 import peak_offline_cases as oc  # noqa: E402
 import peak_cases as pc  # noqa: E402
 from rspt_amd import api, synth  # noqa: E402
@@ -48,30 +47,9 @@ def timed(fn, iters, warmup=1):
     return e0.elapsed_time(e1) / iters
 
 
-def innermost_loops(asm_path, pattern=r"^(_Z\w*14k_peak_offlineILi4ELb0E\w*):"):
-    """instruction counts of the innermost loops of one kernel, in program order (a loop: a label up to a branch back to it)"""
-    body, on = [], False
-    for line in open(asm_path):
-        if re.match(pattern, line):
-            on = True
-            continue
-        if on and line.startswith(".Lfunc_end"):
-            break
-        if on:
-            body.append(line)
-    labels, edges = {}, []
-    for i, ln in enumerate(body):
-        lm = re.match(r"^(\.LBB\w+):", ln)
-        if lm:
-            labels[lm.group(1)] = i
-        bm = re.match(r"^\s+s_(?:cbranch_\w+|branch)\s+(\.LBB\w+)", ln)
-        if bm and bm.group(1) in labels:
-            edges.append((labels[bm.group(1)], i))
-    loops = []
-    for lo, hi in sorted(edges):
-        if not any(lo <= l2 and h2 <= hi and (l2, h2) != (lo, hi) for l2, h2 in edges):
-            loops.append(sum(1 for s in body[lo : hi + 1] if re.match(r"^\s+[sv]_|^\s+(global|buffer|flat|ds|scratch)_", s)))
-    return loops
+def innermost_loops():
+    """instruction counts of the innermost loops of k_peak_offline<4, false>, in program order (tests/devasm.py)"""
+    return next((devasm.innermost_loops(body) for name, body in devasm.functions().items() if re.match(r"^_Z\w*14k_peak_offlineILi4ELb0E", name)), [])
 
 
 def main():
@@ -81,14 +59,7 @@ def main():
     ap.add_argument("--no-asm", action="store_true")
     a = ap.parse_args()
     assert api.lib().rspt_hip_device_count() > 0, "no gfx950 device: nothing to time"
-    loops = None
-    if not a.no_asm:
-        with tempfile.TemporaryDirectory() as tmp:
-            asm = os.path.join(tmp, "rspt.s")
-            subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                                   "-Wno-unused-value", "-w", "-I" + os.path.join(ROOT, "include"), "-o", asm,
-                                   os.path.join(ROOT, "rspt_amd", "csrc", "rspt_hip.hip")])
-            loops = innermost_loops(asm)
+    loops = None if a.no_asm else innermost_loops()
     res = []
     fs = 2000.0
     for name, nch, ns, nblocks, modes in (("64x(64ch x 65536 i32)", 64, 65536, 64, ("fresh", "stateful")), ("1024x(12ch x 8192 i32)", 12, 8192, 1024, ("fresh",))):

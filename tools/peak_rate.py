@@ -14,9 +14,7 @@ import argparse
 import json
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import torch
@@ -25,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import devasm  # noqa: E402
 import peak_cases as pc  # noqa: E402
 from rspt_amd import api, synth  # noqa: E402
 
@@ -45,35 +44,15 @@ def timed(fn, iters, warmup=1):
     return e0.elapsed_time(e1) / iters
 
 
-def loop_sizes(asm_path):
+def loop_sizes():
     """{(bps, variant, traces): (instructions of the largest innermost loop / CH, instructions of the smallest)} per k_peak
-    instance: a loop is a label up to a branch back to it, innermost when no other such branch lies inside"""
-    out, cur, body = {}, None, []
-    for line in open(asm_path):
-        m = re.match(r"^(_Z\w*6k_peakILi(\d)ELi(\d)ELb(\d)E\w*):", line)
-        if m:
-            cur, body = (int(m.group(2)), int(m.group(3)), bool(int(m.group(4)))), []
-            continue
-        if cur is None:
-            continue
-        if line.startswith(".Lfunc_end"):
-            labels, edges = {}, []  # back edges: (label line, branch line)
-            for i, ln in enumerate(body):
-                lm = re.match(r"^(\.LBB\w+):", ln)
-                if lm:
-                    labels[lm.group(1)] = i
-                bm = re.match(r"^\s+s_(?:cbranch_\w+|branch)\s+(\.LBB\w+)", ln)
-                if bm and bm.group(1) in labels:
-                    edges.append((labels[bm.group(1)], i))
-            loops = []  # innermost loops: no other back edge inside
-            for lo, hi in edges:
-                if not any(lo <= l2 and h2 <= hi and (l2, h2) != (lo, hi) for l2, h2 in edges):
-                    loops.append(sum(1 for s in body[lo : hi + 1] if re.match(r"^\s+[sv]_|^\s+(global|buffer|flat|ds)_", s)))
-            if loops:
-                out[cur] = (max(loops) / CH, min(loops))
-            cur = None
-        else:
-            body.append(line)
+    instance (tests/devasm.py: innermost_loops)"""
+    out = {}
+    for name, body in devasm.functions().items():
+        m = re.match(r"^_Z\w*6k_peakILi(\d)ELi(\d)ELb(\d)E", name)
+        loops = devasm.innermost_loops(body) if m else None
+        if loops:
+            out[(int(m.group(1)), int(m.group(2)), bool(int(m.group(3))))] = (max(loops) / CH, min(loops))
     return out
 
 
@@ -84,14 +63,7 @@ def main():
     ap.add_argument("--no-asm", action="store_true")
     a = ap.parse_args()
     assert api.lib().rspt_hip_device_count() > 0, "no gfx950 device: nothing to time"
-    sizes = {}
-    if not a.no_asm:
-        with tempfile.TemporaryDirectory() as tmp:
-            asm = os.path.join(tmp, "rspt.s")
-            subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                                   "-Wno-unused-value", "-w", "-I" + os.path.join(ROOT, "include"), "-o", asm,
-                                   os.path.join(ROOT, "rspt_amd", "csrc", "rspt_hip.hip")])
-            sizes = loop_sizes(asm)
+    sizes = {} if a.no_asm else loop_sizes()
     res = []
     fs = 2000.0
     for name, nch, ns, nblocks, modes in (("64x(64ch x 65536 i32)", 64, 65536, 64, ("fresh", "stateful")), ("1024x(12ch x 8192 i32)", 12, 8192, 1024, ("fresh",))):
