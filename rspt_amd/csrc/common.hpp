@@ -33,7 +33,11 @@ constexpr int kEncThreads = 1024;      // one hzr block per 1024-thread workgrou
 constexpr int kEncWaves = kEncThreads / kWave;
 constexpr int kMaxPlanes = 4;
 
-enum : uint32_t { kModeCopy = 0, kModeHuff = 1, kModeFill = 2, kModeSkip = 3 };
+// (kModeStaged exists in BlockMeta only: a Huffman block whose finished header + payload k_tree left in the staging area)
+enum : uint32_t { kModeCopy = 0, kModeHuff = 1, kModeFill = 2, kModeSkip = 3, kModeStaged = 4 };
+
+// Staging area of the small hzr blocks (k_tree -> k_encode): one slot per hzr block, [7-byte block header][payload <= 3 KiB]
+constexpr uint32_t kStageSlotWords = 772;  // u32: 7 + 3072 bytes, and the word the placing copy reads beyond them
 
 // Shape of one packer, passed to kernels by value.
 struct Geom {

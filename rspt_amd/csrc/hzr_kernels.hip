@@ -9,13 +9,15 @@
 //   k_tree    one wave per hzr block: Fill test (:285-305), Huffman tree with
 //             the reference's tie-break (:222-283), codes + pre-order tree
 //             description (:177-219), exact payload size -> block mode (:377-469),
-//             stream bit at which each 4 KiB segment's tokens start
+//             stream bit at which each 4 KiB segment's tokens start.  A small hzr block (few non-zero
+//             segments, tokens, payload bytes) is also encoded here, by the wave that built its code
+//             table: header + payload go to the block's staging slot (stage_small_block)
 //   k_layout  one workgroup per block: sizes -> stream offsets, stream framing
-//             (signal_packer_base.cpp:69-95, hzr_encode.c:521-522), work queues
-//   k_encode  persistent 1024-thread workgroups, one big hzr block at a time: one pass from
+//             (signal_packer_base.cpp:69-95, hzr_encode.c:521-522), work queue
+//   k_encode  persistent 1024-thread workgroups: first the staged small blocks are copied to their
+//             place in the streams, then one big hzr block at a time: one pass from
 //             lookup to an LDS image of the payload (:410-457), parallel CRC-32C
 //             (hzr_crc32c.c:77-84), block header (:475-481), coalesced copy-out
-//   k_encode_small   one wave per small hzr block (few non-zero segments, tokens, payload bytes)
 //   k_pack_*  the streams of a batch as one container (rspt_hip_pack_batch_dev)
 #include "common.hpp"
 
@@ -45,19 +47,22 @@ __device__ __forceinline__ uint32_t granule_byte_dyn(uint32_t w0, uint32_t w1, u
 
 // "Small" hzr blocks -- few non-zero 4 KiB segments -- are walked by ONE wave, row by row, instead of
 // by a 1024-thread workgroup: their histogram is taken inside k_tree (k_hist skips them) and, if they
-// also have few tokens and a small payload, they are encoded by k_encode_small.
+// also have few tokens and a small payload, the same wave encodes them right there (kModeStaged).
 // Clean-block invariant (rspt_hip_packer::plane_dirty): a Huffman block with at most this many tokens has its non-zero
 // granules wiped by the encoder that read it; k_layout flags every other block that holds a non-zero byte as dirty.
 // (Every small block qualifies: kSmallTokens <= kWipeTokens.)
 constexpr uint32_t kWipeTokens = 2048;
-__device__ __forceinline__ bool block_is_wiped(const BlockMeta& m) { return m.mode == kModeHuff && m.fill <= kWipeTokens; }
+__device__ __forceinline__ bool block_is_wiped(const BlockMeta& m) {
+    return m.mode == kModeStaged || (m.mode == kModeHuff && m.fill <= kWipeTokens);
+}
 constexpr uint32_t kSmallSegments = 2;    // non-zero 4 KiB segments (each costs one dependent HBM round trip)
 constexpr uint32_t kSmallTokens = 512;    // tokens
-constexpr uint32_t kSmallPayload = 3072;  // bytes; a wave's LDS slot holds X + payload + read slack
+constexpr uint32_t kSmallPayload = 3072;  // bytes; the wave's LDS holds the code table, X + payload + read slack
+static_assert(kStageSlotWords * 4 >= 7 + kSmallPayload + 4 + 4, "staging slot too small");
 
 struct WorkQueues {
-    uint32_t n_big, n_small;        // filled by k_layout
-    uint32_t next_big, next_small;  // consumed by k_encode / k_encode_small
+    uint32_t n_big;     // filled by k_layout
+    uint32_t next_big;  // consumed by k_encode
 };
 
 // Work distribution for k_hist / k_encode.  The hardware places workgroup i on XCD i % 8 and,
@@ -88,8 +93,11 @@ constexpr uint32_t kSegHistStride = kEncWaves * kSymStride;  // u16 elements per
 constexpr int kTreeWaves = 4;
 constexpr uint32_t kKeyMax = 0xFFFFFFFFu;
 
-// (5084 bytes per tree: eight 4-wave workgroups = 32 trees in flight per CU.  The kernel is a latency chain per wave -- one dense
-//  tree alone takes 0.045 ms -- so trees in flight are what it lives on: at 6.4 KB per tree a CU held 24.)
+// (5084 bytes per tree: eight 4-wave workgroups = 32 trees per CU by LDS; the one-wave encoder of the small blocks takes the
+//  kernel to 65 VGPRs, i.e. seven workgroups = 28 trees in flight per CU.  The kernel is a latency chain per wave -- one dense
+//  tree alone takes 0.045 ms -- so trees in flight are what it lives on; 32 against 24 measured no different: profiles/r03_notes.md 1f.
+//  The small blocks' CRC reads its slice-by-4 tables from global memory: 4 KiB of LDS per workgroup for them meant 24 trees per CU
+//  and measured 0.081 ms against 0.079, profiles/small_blocks_notes.md.)
 struct TreeLds {
     uint32_t key[kSymStride];     // leaf keys: count<<10 | (1023 - index); index order = creation order
     uint32_t lcnt[kNumSym];       // leaves in the subtree of each node, two u16 counts per word (LDS per wave decides how many
@@ -100,7 +108,6 @@ struct TreeLds {
     uint32_t tdesc[kTdescWords];
     __device__ __forceinline__ uint32_t* lhist() { return up; }
 };
-static_assert(sizeof(TreeLds) * 4 * 8 <= 160 * 1024, "eight k_tree workgroups per CU");
 
 // add the tokens of a zero run of length R to a histogram (same split as run_bits / run_emit)
 __device__ __forceinline__ void run_count(uint32_t* h, uint32_t R) {
@@ -110,7 +117,7 @@ __device__ __forceinline__ void run_count(uint32_t* h, uint32_t R) {
     if (rem) atomicAdd(&h[run_symbol(rem)], 1u);
 }
 
-// token histogram of a small block by one wave (zero runs are counted where they END; see encode_small_block)
+// token histogram of a small block by one wave (zero runs are counted where they END; see stage_small_block)
 __device__ __forceinline__ void small_block_hist(const uint8_t* __restrict__ in, uint32_t in_size, uint32_t segmask, uint32_t* h) {
     const uint32_t l = lane_id();
     const unsigned long long lt = (1ull << l) - 1ull;
@@ -369,17 +376,235 @@ __device__ __forceinline__ TreeOut build_tree(TreeLds& t, const uint32_t* h, uin
     return TreeOut{kModeCopy, in_size, 0u, 0u, 0u};
 }
 
+// ---------------------------------------------------------------------------------------------
+// Small blocks: the wave of k_tree that has just built the block's code table also encodes it, no workgroup barrier.
+// The wave streams over the block's rows in order, so it needs only forward information: every
+// zero run is emitted when it ENDS, right before the literal that ends it (or at the block end),
+// as floor(R/16662) capped tokens plus a remainder token -- the same token sequence as the
+// reference's greedy walk (hzr_encode.c:410-457).  Zero 4 KiB segments are skipped without a read.
+// The tree's LDS is dead by then except for the description: the code table goes where the keys were, the image
+// (X || payload + read slack) over the node arrays behind them.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kSlotImage = 826;  // words of X || payload (+ slack)
+static_assert(kSlotImage * 4 >= kSmallPayload + 4 + 72, "small-block image too small");
+static_assert(offsetof(TreeLds, key) == 0 && offsetof(TreeLds, lcnt) == kSymStride * 4, "the code table takes the key slots, the image starts behind them");
+static_assert((kSymStride + kSlotImage) * 4 <= offsetof(TreeLds, tdesc), "the image must leave the tree description alone");
+
+struct LinSink {  // bit sink of the one-wave encoder: a 32-bit partial word, whole words stored to the wave's image
+    uint32_t* img;
+    uint32_t lo, n, word;
+    __device__ __forceinline__ void start(uint32_t* s, uint32_t bitpos) {
+        img = s;
+        lo = 0;
+        n = bitpos & 31u;
+        word = bitpos >> 5;
+    }
+    __device__ __forceinline__ void put(uint32_t v, uint32_t len) {
+        lo |= v << n;
+        const uint32_t tot = n + len;
+        if (tot >= 32) {
+            atomicOr(&img[word], lo);
+            ++word;
+            lo = (v >> 1) >> (31u - n);
+            n = tot - 32;
+        } else {
+            n = tot;
+        }
+    }
+    __device__ __forceinline__ void flush() {
+        if (n) atomicOr(&img[word], lo);
+    }
+};
+
+// stream bits of the tokens of a zero run of length R (0 < R): capped tokens, then the remainder
+__device__ __forceinline__ uint32_t run_bits(const uint32_t* cwt, uint32_t R) {
+    const uint32_t q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
+    const uint32_t rem = R - q * kRunCap;
+    uint32_t bits = q * ((cwt[260] >> 24) + 14u);
+    if (rem) {
+        const uint32_t sym = run_symbol(rem);
+        bits += (cwt[sym] >> 24) + run_extra_bits(sym);
+    }
+    return bits;
+}
+
+template <typename Sink>
+__device__ __forceinline__ void run_emit(Sink& sink, const uint32_t* cwt, uint32_t R) {
+    const uint32_t q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
+    const uint32_t rem = R - q * kRunCap;
+    for (uint32_t i = 0; i < q; ++i) {
+        const uint32_t c = cwt[260];
+        sink.put(c & 0x00FFFFFFu, c >> 24);
+        sink.put(kRunCap - 279u, 14);
+    }
+    if (rem) {
+        const uint32_t sym = run_symbol(rem);
+        const uint32_t c = cwt[sym];
+        sink.put(c & 0x00FFFFFFu, c >> 24);
+        const uint32_t eb = run_extra_bits(sym);
+        if (eb) sink.put(run_extra_value(sym, rem), eb);
+    }
+}
+
+__device__ __forceinline__ uint32_t crc_chunk64_lin(const uint32_t* img, const uint32_t (*tab)[256], int32_t lo) {
+    const int32_t a = lo >> 2;
+    const uint32_t sh = (uint32_t)lo & 3u;
+    uint32_t c = 0;
+    uint32_t prev = a >= 0 ? img[a] : 0u;
+#pragma unroll
+    for (int32_t q = 0; q < 16; ++q) {
+        const int32_t ix = a + q + 1;
+        const uint32_t next = ix >= 0 ? img[ix] : 0u;
+        c ^= __builtin_amdgcn_alignbyte(next, prev, sh);
+        prev = next;
+        c = tab[3][c & 0xFFu] ^ tab[2][(c >> 8) & 0xFFu] ^ tab[1][(c >> 16) & 0xFFu] ^ tab[0][c >> 24];
+    }
+    return c;
+}
+
+// One wave: emit the block (code words in cwt, tree description in tdesc_lds, both LDS) into img, checksum it, and store
+// [7-byte block header][payload] to the block's staging slot; k_encode copies it to its stream offset, which only k_layout
+// knows.  The literals' granules are wiped on the way (clean-block invariant: block_is_wiped).
+__device__ __forceinline__ void stage_small_block(const uint32_t* cwt, uint32_t* img, const uint32_t* tdesc_lds, const uint32_t (*crc_tab)[256],
+                                                  uint8_t* __restrict__ in, uint32_t in_size, uint32_t segmask, uint32_t L, uint32_t tree_bits,
+                                                  const CrcConsts* __restrict__ cc, uint32_t* __restrict__ slot) {
+    const uint32_t l = lane_id();
+    for (uint32_t i = l; i < kSlotImage; i += 64) img[i] = 0;
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    if (l == 0) img[0] = cc->prefix;
+    const uint32_t twords = (tree_bits + 31) >> 5;
+    for (uint32_t i = l; i < twords; i += 64) atomicOr(&img[1 + i], tdesc_lds[i]);
+
+    uint32_t pend = 0;                    // zeros pending in front of the current position (wave-uniform)
+    uint32_t bitpos = 32u + tree_bits;    // next stream bit (wave-uniform)
+    const unsigned long long lt = (1ull << l) - 1ull;
+    const uint32_t nseg = (in_size + 4095u) >> 12;
+    for (uint32_t seg = 0; seg < nseg; ++seg) {
+        const uint32_t seg_base = seg << 12;
+        if (!((segmask >> seg) & 1u)) {
+            pend += min(4096u, in_size - seg_base);
+            continue;
+        }
+        uint4 rows[4];
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {  // the segment's four rows in one round trip (L2-hot: this wave has just counted them)
+            const uint32_t pos = seg_base + (r << 10) + 16u * l;
+            rows[r] = make_uint4(0, 0, 0, 0);
+            if (pos < in_size) rows[r] = *reinterpret_cast<const uint4*>(in + pos);
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {
+            const uint32_t base = seg_base + (r << 10);
+            if (base < in_size) {
+                const uint32_t row_valid = min(1024u, in_size - base);
+                Granule gr;
+                const uint32_t pos = base + 16u * l;
+                gr.nv = pos < in_size ? min(16u, in_size - pos) : 0u;
+                gr.w[0] = rows[r].x;
+                gr.w[1] = rows[r].y;
+                gr.w[2] = rows[r].z;
+                gr.w[3] = rows[r].w;
+                granule_finish(gr);
+                const uint32_t lits = ~gr.zm & ((1u << gr.nv) - 1u);
+                // clean-block invariant: every small block is wiped (block_is_wiped); this lane alone read the granule
+                if (lits) *reinterpret_cast<uint4*>(in + pos) = make_uint4(0, 0, 0, 0);
+                const unsigned long long nzb = __ballot(lits != 0);
+                if (!nzb) {
+                    pend += row_valid;
+                } else {
+                    // zeros in front of this granule: the nearest lower lane with a literal closes the run
+                    const uint32_t last_nz = lits ? 31u - (uint32_t)__builtin_clz(lits) : 0u;  // index of the granule's last literal
+                    const uint32_t trail = lits ? (15u - last_nz) : 16u;                         // zeros behind it inside the (full) granule
+                    const unsigned long long below = nzb & lt;
+                    const uint32_t p = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u;
+                    const uint32_t tp = (uint32_t)__shfl((int)trail, (int)p, 64);
+                    const uint32_t zb = below ? (16u * (l - 1u - p) + tp) : (16u * l + pend);
+                    // pass A: bits of this lane's tokens
+                    uint32_t nbits = 0;
+                    {
+                        uint32_t t = lits, prev_end = 0;  // prev_end = index after the previous literal
+                        bool first = true;
+                        while (t) {
+                            const uint32_t i = (uint32_t)__builtin_ctz(t);
+                            t &= t - 1;
+                            const uint32_t R = first ? (zb + i) : (i - prev_end);
+                            if (R) nbits += run_bits(cwt, R);
+                            nbits += cwt[granule_byte_dyn(gr.w[0], gr.w[1], gr.w[2], gr.w[3], i)] >> 24;
+                            prev_end = i + 1;
+                            first = false;
+                        }
+                    }
+                    const uint32_t inc = wave_scan_add(nbits);
+                    const uint32_t mypos = bitpos + inc - nbits;
+                    bitpos += read_lane(inc, 63);
+                    // pass B: emit
+                    if (nbits) {
+                        LinSink sink;
+                        sink.start(img, mypos);
+                        uint32_t t = lits, prev_end = 0;
+                        bool first = true;
+                        while (t) {
+                            const uint32_t i = (uint32_t)__builtin_ctz(t);
+                            t &= t - 1;
+                            const uint32_t R = first ? (zb + i) : (i - prev_end);
+                            if (R) run_emit(sink, cwt, R);
+                            const uint32_t c = cwt[granule_byte_dyn(gr.w[0], gr.w[1], gr.w[2], gr.w[3], i)];
+                            sink.put(c & 0x00FFFFFFu, c >> 24);
+                            prev_end = i + 1;
+                            first = false;
+                        }
+                        sink.flush();
+                    }
+                    // zeros behind the row's last literal stay pending
+                    const uint32_t pl = 63u - (uint32_t)__builtin_clzll(nzb);
+                    const uint32_t lastlit = read_lane(last_nz, pl);  // pl from a ballot: wave-uniform
+                    pend = row_valid - (16u * pl + lastlit + 1u);
+                }
+            }
+        }
+    }
+    if (pend && l == 0) {  // the run that reaches the block end
+        LinSink sink;
+        sink.start(img, bitpos);
+        run_emit(sink, cwt, pend);
+        sink.flush();
+    }
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+
+    // CRC-32C of X || payload: lane l owns the 64-byte chunk (63 - l) counted from the end
+    const int32_t Lv = (int32_t)L + 4;
+    const int32_t hi = Lv - 64 * (int32_t)(63u - l);
+    uint32_t c = 0;
+    if (hi > 0) c = crc_chunk64_lin(img, crc_tab, hi - 64);
+    const uint32_t crc = ~wave_xor_u32(gf_shift(cc, l, c));
+
+    // slot byte s = stream byte s of the encoded block: [L-1 u16][crc u32][mode], then payload byte s - 7 = image byte s - 3
+    const uint32_t nw = (7u + L + 3u) >> 2;
+    for (uint32_t w = l; w < nw; w += 64) {
+        uint32_t v;
+        if (w == 0) v = ((L - 1u) & 0xFFFFu) | (crc << 16);
+        else if (w == 1) v = (crc >> 16) | (kModeHuff << 16) | (img[1] << 24);
+        else v = __builtin_amdgcn_alignbyte(img[w], img[w - 1u], 1u);
+        slot[w] = v;
+    }
+}
+
 // k_tree: one wave per hzr block, 4 waves per workgroup.  Small blocks (<= kSmallSegments non-zero 4 KiB segments) take their
-// own histogram here; for the others k_hist left the block histogram and the per-segment histograms, which -- times the
-// code lengths -- give the stream bit at which each 4 KiB segment's tokens start (k_encode then needs no bit-count pass).
-__global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __restrict__ hist, const uint8_t* __restrict__ planes, Geom g,
+// own histogram here -- and, if they also have few tokens and a small payload, are encoded here too, into their staging slot
+// (BlockMeta::mode = kModeStaged: the one mark k_layout and k_encode go by); for the others k_hist left the block histogram and
+// the per-segment histograms, which -- times the code lengths -- give the stream bit at which each 4 KiB segment's tokens start
+// (k_encode then needs no bit-count pass).
+__global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __restrict__ hist, uint8_t* __restrict__ planes, Geom g,
                                                          const uint32_t* __restrict__ nbuse, const uint32_t* __restrict__ nzflag,
                                                          uint32_t nhb_total, uint32_t* __restrict__ cw, uint32_t* __restrict__ tdesc,
                                                          BlockMeta* __restrict__ meta, const uint32_t* __restrict__ seghist,
                                                          uint32_t* __restrict__ segbase, uint32_t* __restrict__ zero_next, uint32_t zero_words,
-                                                         uint32_t psel_arg) {
+                                                         const CrcConsts* __restrict__ cc, uint32_t* __restrict__ staging, uint32_t psel_arg) {
     const uint32_t psel = RSPT_DIAG_ONLY(psel_arg);  // timing probes (diagnostic builds only): no tree for plane 0 (bit 4) / planes >= 1 (bit 5)
     __shared__ TreeLds s_t[kTreeWaves];
+    static_assert(sizeof(TreeLds) * kTreeWaves * 8 <= 160 * 1024, "eight k_tree workgroups (32 trees) per CU");
     const uint32_t l = lane_id();
     const uint32_t wv = threadIdx.x >> 6;
     // the other copy of the per-call zero region, for the next call (rspt_hip.hip: zbuf)
@@ -405,13 +630,14 @@ __global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __rest
     }
     const uint32_t in_size = min(kHzrBlock, g.N - j * kHzrBlock);
     uint32_t* h = t.lhist();
+    uint8_t* in = planes + ((size_t)b * kMaxPlanes + k) * g.plane_stride + (size_t)j * kHzrBlock;
     const bool own_hist = (uint32_t)__popc(segmask) <= kSmallSegments;
     if (l == 0) segbase[(size_t)hb * kEncWaves] = 0xFFFFFFFFu;  // "no segment offsets" unless set below
     if (own_hist) {  // small block: this wave takes the histogram itself
         for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) h[i] = 0;
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
-        small_block_hist(planes + ((size_t)b * kMaxPlanes + k) * g.plane_stride + (size_t)j * kHzrBlock, in_size, segmask, h);
+        small_block_hist(in, in_size, segmask, h);
     } else {
         for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) h[i] = hist[(size_t)hb * kSymStride + i];
     }
@@ -419,8 +645,19 @@ __global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __rest
     __builtin_amdgcn_wave_barrier();
     uint32_t* cwo = cw + (size_t)hb * kSymStride;
     const TreeOut r = build_tree(t, h, in_size, [&](uint32_t sym, uint32_t code, uint32_t len) { cwo[sym] = code | (len << 24); });
-    if (l == 0) meta[hb] = BlockMeta{r.mode, r.payload_len, r.tree_bits, r.mode == kModeHuff ? r.ntok : r.fill};
+    // small enough for this wave to encode it right here?  (wave-uniform; the same mark decides in k_layout and k_encode)
+    const bool staged = own_hist && r.mode == kModeHuff && r.payload_len <= kSmallPayload && r.ntok <= kSmallTokens;
+    if (l == 0) meta[hb] = BlockMeta{staged ? kModeStaged : r.mode, r.payload_len, r.tree_bits, r.mode == kModeHuff ? r.ntok : r.fill};
     if (r.mode != kModeHuff) return;
+    if (staged) {
+        // the code words come back from the row this wave has just written (same wave, same CU: workgroup scope is enough)
+        uint32_t* lds = reinterpret_cast<uint32_t*>(&t);
+        __threadfence_block();
+        __builtin_amdgcn_wave_barrier();
+        for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) lds[i] = __hip_atomic_load(&cwo[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (past the L1)
+        stage_small_block(lds, lds + kSymStride, t.tdesc, cc->table, in, in_size, segmask, r.payload_len, r.tree_bits, cc, staging + (size_t)hb * kStageSlotWords);
+        return;
+    }
     uint32_t* tdo = tdesc + (size_t)hb * kTdescWords;
     for (uint32_t i = l; i < (uint32_t)kTdescWords; i += 64) tdo[i] = t.tdesc[i];
     if (own_hist) return;
@@ -466,16 +703,16 @@ __device__ __forceinline__ void store_le32(uint8_t* p, uint32_t v) {
     p[3] = (uint8_t)(v >> 24);
 }
 
-// It also sorts the hzr blocks into the work queues of k_encode: Fill blocks (8 bytes) are written
-// right here; Huffman blocks with few tokens and a small payload go to the `small` queue (one WAVE encodes one such
-// block), everything else to the `big` queue (one 1024-thread workgroup per block).
+// It also fills the work queue of k_encode: Fill blocks (8 bytes) are written right here; the small blocks k_tree has
+// encoded already (kModeStaged) only need their offset, which k_encode's placing copy reads from out_off; everything
+// else goes to the `big` queue (one 1024-thread workgroup per block).
 
 
 __global__ __launch_bounds__(256) void k_layout(Geom g, const uint32_t* __restrict__ nbuse, const BlockMeta* __restrict__ meta,
                                                const uint8_t* __restrict__ means_hdr, uint8_t* __restrict__ dst, uint64_t dst_stride,
                                                uint64_t* __restrict__ out_off, uint64_t* __restrict__ sizes, const CrcConsts* __restrict__ cc,
                                                const uint32_t* __restrict__ nzflag, WorkQueues* __restrict__ wq,
-                                               uint32_t* __restrict__ big_list, uint32_t* __restrict__ small_list,
+                                               uint32_t* __restrict__ big_list,
                                                uint32_t* __restrict__ plane_dirty, uint32_t dirty_shift, uint32_t psel_arg) {
     const uint32_t psel = RSPT_DIAG_ONLY(psel_arg);  // timing probes (diagnostic builds only): k_encode gets no plane 0 (bit 2) / planes >= 1 (bit 3)
     __shared__ uint64_t s_part[256];
@@ -552,9 +789,6 @@ __global__ __launch_bounds__(256) void k_layout(Geom g, const uint32_t* __restri
             f[5] = (uint8_t)(c >> 24);
             f[6] = (uint8_t)kModeFill;
             f[7] = (uint8_t)m.fill;
-        } else if (m.mode == kModeHuff && m.payload_len <= kSmallPayload && m.fill <= kSmallTokens &&
-                   __popc(nzflag[hb0 + q]) <= (int)kSmallSegments) {
-            small_list[atomicAdd(&wq->n_small, 1u)] = hb0 + q;
         } else if (m.mode == kModeHuff || m.mode == kModeCopy) {
             if (psel && ((q / g.nblk == 0 && (psel & 4u)) || (q / g.nblk >= 1 && (psel & 8u)))) continue;
             big_list[atomicAdd(&wq->n_big, 1u)] = hb0 + q;
@@ -613,270 +847,6 @@ constexpr uint32_t kTokQueueBase = 4200;     // stage word (> (16384 + 4) / 4 + 
 
 // byte q of the image (q = 0..3: X, q >= 4: payload byte q-4)
 __device__ __forceinline__ uint32_t stage_byte(const uint32_t* stage, uint32_t q) { return (stage[(q >> 2)] >> ((q & 3u) * 8)) & 0xFFu; }
-
-// ---------------------------------------------------------------------------------------------
-// Small blocks: one WAVE encodes one hzr block, 16 blocks per workgroup pass, no workgroup barrier.
-// The wave streams over the block's rows in order, so it needs only forward information: every
-// zero run is emitted when it ENDS, right before the literal that ends it (or at the block end),
-// as floor(R/16662) capped tokens plus a remainder token -- the same token sequence as the
-// reference's greedy walk (hzr_encode.c:410-457).  Zero 4 KiB segments are skipped without a read.
-// ---------------------------------------------------------------------------------------------
-constexpr uint32_t kSlotWords = 1090;  // per-wave LDS slot of the small-block encoder: [cw 264][image]
-constexpr uint32_t kSlotImage = kSlotWords - kSymStride;  // words of X || payload (+ slack)
-static_assert(kSlotImage * 4 >= kSmallPayload + 4 + 72, "small-block slot too small");
-
-struct LinSink {  // bit sink of the one-wave encoder: a 32-bit partial word, whole words stored to the wave's image
-    uint32_t* img;
-    uint32_t lo, n, word;
-    __device__ __forceinline__ void start(uint32_t* s, uint32_t bitpos) {
-        img = s;
-        lo = 0;
-        n = bitpos & 31u;
-        word = bitpos >> 5;
-    }
-    __device__ __forceinline__ void put(uint32_t v, uint32_t len) {
-        lo |= v << n;
-        const uint32_t tot = n + len;
-        if (tot >= 32) {
-            atomicOr(&img[word], lo);
-            ++word;
-            lo = (v >> 1) >> (31u - n);
-            n = tot - 32;
-        } else {
-            n = tot;
-        }
-    }
-    __device__ __forceinline__ void flush() {
-        if (n) atomicOr(&img[word], lo);
-    }
-};
-
-// stream bits of the tokens of a zero run of length R (0 < R): capped tokens, then the remainder
-__device__ __forceinline__ uint32_t run_bits(const uint32_t* cwt, uint32_t R) {
-    const uint32_t q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
-    const uint32_t rem = R - q * kRunCap;
-    uint32_t bits = q * ((cwt[260] >> 24) + 14u);
-    if (rem) {
-        const uint32_t sym = run_symbol(rem);
-        bits += (cwt[sym] >> 24) + run_extra_bits(sym);
-    }
-    return bits;
-}
-
-template <typename Sink>
-__device__ __forceinline__ void run_emit(Sink& sink, const uint32_t* cwt, uint32_t R) {
-    const uint32_t q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
-    const uint32_t rem = R - q * kRunCap;
-    for (uint32_t i = 0; i < q; ++i) {
-        const uint32_t c = cwt[260];
-        sink.put(c & 0x00FFFFFFu, c >> 24);
-        sink.put(kRunCap - 279u, 14);
-    }
-    if (rem) {
-        const uint32_t sym = run_symbol(rem);
-        const uint32_t c = cwt[sym];
-        sink.put(c & 0x00FFFFFFu, c >> 24);
-        const uint32_t eb = run_extra_bits(sym);
-        if (eb) sink.put(run_extra_value(sym, rem), eb);
-    }
-}
-
-__device__ __forceinline__ uint32_t crc_chunk64_lin(const uint32_t* img, const uint32_t (*tab)[256], int32_t lo) {
-    const int32_t a = lo >> 2;
-    const uint32_t sh = (uint32_t)lo & 3u;
-    uint32_t c = 0;
-    uint32_t prev = a >= 0 ? img[a] : 0u;
-#pragma unroll
-    for (int32_t q = 0; q < 16; ++q) {
-        const int32_t ix = a + q + 1;
-        const uint32_t next = ix >= 0 ? img[ix] : 0u;
-        c ^= __builtin_amdgcn_alignbyte(next, prev, sh);
-        prev = next;
-        c = tab[3][c & 0xFFu] ^ tab[2][(c >> 8) & 0xFFu] ^ tab[1][(c >> 16) & 0xFFu] ^ tab[0][c >> 24];
-    }
-    return c;
-}
-
-__device__ __forceinline__ void encode_small_block(uint32_t* cwt, uint32_t* img, const uint32_t (*crc_tab)[256], uint32_t hb,
-                                                   uint8_t* __restrict__ planes, const Geom& g,
-                                                   const uint32_t* __restrict__ nzflag, const BlockMeta* __restrict__ meta,
-                                                   const uint32_t* __restrict__ cw, const uint32_t* __restrict__ tdesc,
-                                                   const uint64_t* __restrict__ out_off, const CrcConsts* __restrict__ cc,
-                                                   uint8_t* __restrict__ dst, uint64_t dst_stride, uint32_t ablate_arg) {
-    const uint32_t ablate = RSPT_DIAG_ONLY(ablate_arg);  // timing probes: diagnostic builds only
-    const uint32_t l = lane_id();
-    if (ablate & 512u) return;
-    const uint32_t j = hb % g.nblk, k = (hb / g.nblk) % kMaxPlanes, b = hb / (g.nblk * kMaxPlanes);
-    const BlockMeta m = meta[hb];
-    const uint64_t off = out_off[hb];
-    const uint32_t segmask = nzflag[hb];
-    if (off == ~0ull) return;
-    const uint32_t in_size = min(kHzrBlock, g.N - j * kHzrBlock);
-    uint8_t* in = planes + ((size_t)b * kMaxPlanes + k) * g.plane_stride + (size_t)j * kHzrBlock;
-    const uint32_t L = m.payload_len;
-    for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) cwt[i] = cw[(size_t)hb * kSymStride + i];
-    for (uint32_t i = l; i < kSlotImage; i += 64) img[i] = 0;
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    if (l == 0) img[0] = cc->prefix;
-    const uint32_t twords = (m.tree_bits + 31) >> 5;
-    for (uint32_t i = l; i < twords; i += 64) atomicOr(&img[1 + i], tdesc[(size_t)hb * kTdescWords + i]);
-
-    uint32_t pend = 0;                       // zeros pending in front of the current position (wave-uniform)
-    uint32_t bitpos = 32u + m.tree_bits;     // next stream bit (wave-uniform)
-    const unsigned long long lt = (1ull << l) - 1ull;
-    const uint32_t nseg = (in_size + 4095u) >> 12;
-    // One wave walks 64 rows in order, so HBM latency is hidden by reading a whole 4 KiB segment
-    // (4 rows) at once, one segment ahead of the one being processed.
-    uint4 cur[4], nxt[4];
-    auto issue = [&](uint32_t seg, uint4* buf) {
-#pragma unroll
-        for (uint32_t r = 0; r < 4; ++r) {
-            const uint32_t pos = (seg << 12) + (r << 10) + 16u * l;
-            buf[r] = make_uint4(0, 0, 0, 0);
-            if (seg < nseg && ((segmask >> seg) & 1u) && pos < in_size) buf[r] = *reinterpret_cast<const uint4*>(in + pos);
-        }
-    };
-    issue(0, cur);
-    for (uint32_t seg = 0; seg < nseg && !(ablate & 1024u); ++seg) {
-        issue(seg + 1, nxt);
-        const uint32_t seg_base = seg << 12;
-        if (!((segmask >> seg) & 1u)) {
-            pend += min(4096u, in_size - seg_base);
-        } else {
-#pragma unroll
-            for (uint32_t r = 0; r < 4; ++r) {
-                const uint32_t base = seg_base + (r << 10);
-                if (base < in_size) {
-                    const uint32_t row_valid = min(1024u, in_size - base);
-                    Granule gr;
-                    const uint32_t pos = base + 16u * l;
-                    gr.nv = pos < in_size ? min(16u, in_size - pos) : 0u;
-                    gr.w[0] = cur[r].x;
-                    gr.w[1] = cur[r].y;
-                    gr.w[2] = cur[r].z;
-                    gr.w[3] = cur[r].w;
-                    granule_finish(gr);
-                    const uint32_t lits = ~gr.zm & ((1u << gr.nv) - 1u);
-                    // clean-block invariant: every small block is wiped (block_is_wiped); this lane alone read the granule
-                    if (lits) *reinterpret_cast<uint4*>(in + pos) = make_uint4(0, 0, 0, 0);
-                    const unsigned long long nzb = __ballot(lits != 0);
-                    if (!nzb) {
-                        pend += row_valid;
-                    } else {
-                        // zeros in front of this granule: the nearest lower lane with a literal closes the run
-                        const uint32_t last_nz = lits ? 31u - (uint32_t)__builtin_clz(lits) : 0u;  // index of the granule's last literal
-                        const uint32_t trail = lits ? (15u - last_nz) : 16u;                         // zeros behind it inside the (full) granule
-                        const unsigned long long below = nzb & lt;
-                        const uint32_t p = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u;
-                        const uint32_t tp = (uint32_t)__shfl((int)trail, (int)p, 64);
-                        const uint32_t zb = below ? (16u * (l - 1u - p) + tp) : (16u * l + pend);
-                        // pass A: bits of this lane's tokens
-                        uint32_t nbits = 0;
-                        {
-                            uint32_t t = lits, prev_end = 0;  // prev_end = index after the previous literal
-                            bool first = true;
-                            while (t) {
-                                const uint32_t i = (uint32_t)__builtin_ctz(t);
-                                t &= t - 1;
-                                const uint32_t R = first ? (zb + i) : (i - prev_end);
-                                if (R) nbits += run_bits(cwt, R);
-                                nbits += cwt[granule_byte_dyn(gr.w[0], gr.w[1], gr.w[2], gr.w[3], i)] >> 24;
-                                prev_end = i + 1;
-                                first = false;
-                            }
-                        }
-                        const uint32_t inc = wave_scan_add(nbits);
-                        const uint32_t mypos = bitpos + inc - nbits;
-                        bitpos += read_lane(inc, 63);
-                        // pass B: emit
-                        if (nbits) {
-                            LinSink sink;
-                            sink.start(img, mypos);
-                            uint32_t t = lits, prev_end = 0;
-                            bool first = true;
-                            while (t) {
-                                const uint32_t i = (uint32_t)__builtin_ctz(t);
-                                t &= t - 1;
-                                const uint32_t R = first ? (zb + i) : (i - prev_end);
-                                if (R) run_emit(sink, cwt, R);
-                                const uint32_t c = cwt[granule_byte_dyn(gr.w[0], gr.w[1], gr.w[2], gr.w[3], i)];
-                                sink.put(c & 0x00FFFFFFu, c >> 24);
-                                prev_end = i + 1;
-                                first = false;
-                            }
-                            sink.flush();
-                        }
-                        // zeros behind the row's last literal stay pending
-                        const uint32_t pl = 63u - (uint32_t)__builtin_clzll(nzb);
-                        const uint32_t lastlit = read_lane(last_nz, pl);  // pl from a ballot: wave-uniform
-                        pend = row_valid - (16u * pl + lastlit + 1u);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (uint32_t r = 0; r < 4; ++r) cur[r] = nxt[r];
-    }
-    if (pend && l == 0) {  // the run that reaches the block end
-        LinSink sink;
-        sink.start(img, bitpos);
-        run_emit(sink, cwt, pend);
-        sink.flush();
-    }
-    __threadfence_block();
-    __builtin_amdgcn_wave_barrier();
-
-    // CRC-32C of X || payload: lane l owns the 64-byte chunk (63 - l) counted from the end
-    const int32_t Lv = (int32_t)L + 4;
-    const int32_t hi = Lv - 64 * (int32_t)(63u - l);
-    uint32_t c = 0;
-    if (hi > 0 && !(ablate & 2048u)) c = crc_chunk64_lin(img, crc_tab, hi - 64);
-    const uint32_t crc = (ablate & 2048u) ? 0u : ~wave_xor_u32(gf_shift(cc, l, c));
-
-    uint8_t* o = dst + (size_t)b * dst_stride + off;
-    if (l == 0) {
-        o[0] = (uint8_t)(L - 1);
-        o[1] = (uint8_t)((L - 1) >> 8);
-        o[2] = (uint8_t)crc;
-        o[3] = (uint8_t)(crc >> 8);
-        o[4] = (uint8_t)(crc >> 16);
-        o[5] = (uint8_t)(crc >> 24);
-        o[6] = (uint8_t)kModeHuff;
-    }
-    const uint8_t* img8 = reinterpret_cast<const uint8_t*>(img) + 4;
-    for (uint32_t i = l; i < L; i += 64) o[7 + i] = img8[i];
-    __builtin_amdgcn_wave_barrier();  // the slot is reused by this wave's next block
-}
-
-// small blocks: 4 waves per workgroup, each wave pulls blocks on its own (no workgroup barrier after the table load)
-constexpr int kSmallWaves = 4;
-__global__ __launch_bounds__(kSmallWaves * 64) void k_encode_small(uint8_t* __restrict__ planes, Geom g, const uint32_t* __restrict__ nzflag,
-                                                                  const BlockMeta* __restrict__ meta, const uint32_t* __restrict__ cw,
-                                                                  const uint32_t* __restrict__ tdesc, const uint64_t* __restrict__ out_off,
-                                                                  const CrcConsts* __restrict__ cc, uint8_t* __restrict__ dst, uint64_t dst_stride,
-                                                                  WorkQueues* __restrict__ wq, const uint32_t* __restrict__ small_list, uint32_t ablate,
-                                                                  uint32_t* __restrict__ report) {
-    __shared__ uint32_t s_crc[4][256];
-    __shared__ uint32_t s_slot[kSmallWaves][kSlotWords];
-    // the host reads this (a word of its own memory) before the NEXT batches: a batch without small blocks needs no side stream
-    if (blockIdx.x == 0 && threadIdx.x == 0) *report = wq->n_small;
-    for (uint32_t i = threadIdx.x; i < 1024; i += kSmallWaves * 64) (&s_crc[0][0])[i] = (&cc->table[0][0])[i];
-    __syncthreads();
-    const uint32_t n_small = wq->n_small;
-    const uint32_t wv = threadIdx.x >> 6;
-    const uint32_t nwaves = gridDim.x * kSmallWaves;
-    for (uint32_t pass = 0;; ++pass) {
-        uint32_t i = blockIdx.x * kSmallWaves + wv;  // first block: static
-        if (pass) {
-            if (lane_id() == 0) i = nwaves + atomicAdd(&wq->next_small, 1u);
-            i = (uint32_t)__builtin_amdgcn_readfirstlane((int)i);
-        }
-        if (i >= n_small) break;
-        const uint32_t hb = small_list[i];
-        encode_small_block(s_slot[wv], s_slot[wv] + kSymStride, s_crc, hb, planes, g, nzflag, meta, cw, tdesc, out_off, cc, dst, dst_stride, ablate);
-    }
-}
 
 // ===========================================================================
 // container packing (rspt_hip_pack_batch_dev)

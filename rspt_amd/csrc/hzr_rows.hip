@@ -1,5 +1,5 @@
 // hzr_rows.hip -- the workgroup-per-block half of the hzr encoder: tokenizer + histogram (k_hist) and code emission
-// (k_encode) for the blocks that are not "small" (hzr_kernels.hip: k_tree / k_encode_small take those).
+// (k_encode) for the blocks that are not "small" (hzr_kernels.hip: k_tree takes those; k_encode only copies them to their place).
 //
 //   k_hist     persistent 1024-thread workgroups, one hzr block at a time (four 16-byte granules per lane): zero-run
 //              tokenizer (hzr_encode.c:133-173), per-wave 261-bin histograms in LDS -> the block's histogram and the
@@ -788,7 +788,6 @@ __global__ __launch_bounds__(kEncThreads, 8) void k_hist(const uint8_t* __restri
     } while (0)
 #endif
 
-constexpr uint32_t kYieldSmallBlocks = 2048;  // k_encode leaves an eighth of its slots to k_encode_small from this many small blocks on
 struct EncRowsLds {
     uint2 tab[kSymStride];  // {code, length} per lookup index; 261..263 = {0, 0} (a byte that ends no token)
     uint32_t crc[4][256];   // multiplication by x^(8*4096) as four byte-indexed lookups (CrcConsts::shift[78])
@@ -866,7 +865,7 @@ __device__ __forceinline__ void encode_block_rows(uint32_t hb, uint8_t* __restri
         ENC_STAMP(1);
         if (own_bits) {
             // the block's histogram was taken by k_tree in one piece (few non-zero segments, but too big for
-            // k_encode_small): count this wave's tokens here -- histogram in the (still unused) image, times the code lengths
+            // k_tree's own encoder): count this wave's tokens here -- histogram in the (still unused) image, times the code lengths
             uint32_t* myhist = d.stage + w * kSymStride;
             for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) myhist[i] = 0;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1009,30 +1008,49 @@ __device__ __forceinline__ void encode_block_rows(uint32_t hb, uint8_t* __restri
 #endif
 }
 
+// One wave: copy a staged small block (k_tree: stage_small_block; [header][payload], 7 + payload_len bytes from a word-aligned
+// slot) to its place in the stream -- bytes up to the destination's word boundary, whole words, the bytes behind them.
+__device__ __forceinline__ void place_staged_block(uint32_t hb, const Geom& g, const BlockMeta* __restrict__ meta, const uint64_t* __restrict__ out_off,
+                                                   const uint32_t* __restrict__ staging, uint8_t* __restrict__ dst, uint64_t dst_stride) {
+    const BlockMeta m = meta[hb];  // (one address per wave)
+    const uint64_t off = out_off[hb];
+    if (m.mode != kModeStaged || off == ~0ull) return;  // (~0: the stream does not fit dst_stride, nothing of it is written)
+    const uint32_t l = lane_id();
+    const uint32_t b = hb / (g.nblk * kMaxPlanes);
+    const uint32_t* sw = staging + (size_t)hb * kStageSlotWords;
+    uint8_t* o = dst + (size_t)b * dst_stride + off;
+    const uint32_t len = 7u + m.payload_len;
+    const uint32_t a = (uint32_t)(0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 3u;  // (len >= 8 > a)
+    const uint32_t nd = (len - a) >> 2, tail = (len - a) & 3u;
+    if (l < a) o[l] = (uint8_t)(sw[0] >> (8u * l));
+    uint32_t* ow = reinterpret_cast<uint32_t*>(o + a);
+    for (uint32_t i = l; i < nd; i += 64) ow[i] = __builtin_amdgcn_alignbyte(sw[i + 1u], sw[i], a);  // (sw[nd] lies inside the slot)
+    if (l < tail) {
+        const uint32_t q = a + 4u * nd + l;
+        o[q] = (uint8_t)(sw[q >> 2] >> (8u * (q & 3u)));
+    }
+}
+
 __global__ __launch_bounds__(kEncThreads, 8) void k_encode(uint8_t* __restrict__ planes, Geom g, const uint32_t* __restrict__ nzflag,
                                                           const BlockMeta* __restrict__ meta, const uint32_t* __restrict__ cw,
                                                           const uint32_t* __restrict__ tdesc, const uint64_t* __restrict__ out_off,
                                                           const CrcConsts* __restrict__ cc, uint8_t* __restrict__ dst, uint64_t dst_stride,
                                                           WorkQueues* __restrict__ wq, const uint32_t* __restrict__ big_list,
                                                           const uint32_t* __restrict__ segbase, const uint32_t* __restrict__ lists,
-                                                          const uint2* __restrict__ listinfo, unsigned long long* __restrict__ stamps, uint32_t yield) {
+                                                          const uint2* __restrict__ listinfo, unsigned long long* __restrict__ stamps,
+                                                          const uint32_t* __restrict__ staging, uint32_t nhb) {
+    // the small blocks k_tree encoded into the staging area: every wave of the grid places its share, one block at a time
+    for (uint32_t hb = blockIdx.x * kEncWaves + (threadIdx.x >> 6); hb < nhb; hb += gridDim.x * kEncWaves)
+        place_staged_block(hb, g, meta, out_off, staging, dst, dst_stride);
     (&g_e.crc[0][0])[threadIdx.x] = (&cc->shift[78][0][0])[threadIdx.x];  // multiplication by x^(8*4096): 4 x 256 entries, once per workgroup
     if (threadIdx.x < kRunClsEntries) g_e.runcls[threadIdx.x] = run_class_entry(threadIdx.x);
     if (threadIdx.x == 0) g_e.zero_word = 0;
     const uint32_t n_big = wq->n_big;
-    // The small blocks are encoded beside this kernel (k_encode_small, side stream) -- but two of these workgroups hold every
-    // wave slot of a CU, so the small ones only get in as these retire, and ran on for ~20 us behind the last big block.  When
-    // there are enough small blocks for that to matter an eighth of the grid steps aside from the start: the small-block kernel
-    // then ends well before this one (64-block batch: encode 0.333 + 0.021 behind it -> 0.328 + 0.010; with few small blocks
-    // the full grid is the faster one).  Every workgroup takes the same decision from the same counter.  `yield` = 0: the small-block
-    // kernel of this batch ran earlier, beside the next batch's front end (two batches in flight).
-    const uint32_t act = yield && wq->n_small >= kYieldSmallBlocks && gridDim.x >= 16u ? gridDim.x - gridDim.x / 8u : gridDim.x;
-    if (blockIdx.x >= act) return;
     // persistent: one big block per workgroup pass; the first one is static (index = workgroup id), the
     // rest come from a counter (one shared word sustains only ~88 fetch-adds per microsecond)
     for (uint32_t pass = 0;; ++pass) {
         __syncthreads();  // everyone is done with the previous block (and with the slot)
-        if (threadIdx.x == 0) g_e.slot = pass == 0 ? blockIdx.x : act + atomicAdd(&wq->next_big, 1u);
+        if (threadIdx.x == 0) g_e.slot = pass == 0 ? blockIdx.x : gridDim.x + atomicAdd(&wq->next_big, 1u);
         __syncthreads();
         const uint32_t i = g_e.slot;
         if (i >= n_big) break;

@@ -106,8 +106,8 @@ void make_crc_consts(CrcConsts& cc) {
     cc.pad[0] = cc.pad[1] = cc.pad[2] = 0;
 }
 
-enum Stage { ST_PRE = 0, ST_NB, ST_HIST, ST_TREE, ST_LAYOUT, ST_ENCODE, ST_ENCODE_SMALL, ST_COUNT };
-const char* kStageNames[ST_COUNT] = {"preprocess", "nb_scan", "hzr_hist", "hzr_tree", "layout", "hzr_encode", "hzr_encode_small"};
+enum Stage { ST_PRE = 0, ST_NB, ST_HIST, ST_TREE, ST_LAYOUT, ST_ENCODE, ST_COUNT };
+const char* kStageNames[ST_COUNT] = {"preprocess", "nb_scan", "hzr_hist", "hzr_tree", "layout", "hzr_encode"};
 
 }  // namespace
 
@@ -152,7 +152,7 @@ struct Workspace {
     Dev<uint32_t> nbuse;      // [cap]
     Dev<uint32_t> dec_nb;     // [cap] decode: planes of each stream (container index entry, else nb_state)
     Dev<uint32_t> big_list;   // [cap*4*nblk] hzr blocks for the workgroup-per-block encoder (filled by k_layout)
-    Dev<uint32_t> small_list; // [cap*4*nblk] hzr blocks for the wave-per-block encoder
+    Dev<uint32_t> staging;    // [cap*4*nblk][kStageSlotWords] header + payload of the small hzr blocks (k_tree -> k_encode), 3088 bytes each
     // The per-call zero region [nzflag | needmask | work counters | row sums] exists twice: while a call works in one copy its
     // k_tree zeroes the other for the next call (one store per thread) -- the memset in front of every call was a 9 us launch.
     Dev<uint32_t> zbuf[2];
@@ -318,11 +318,8 @@ struct rspt_hip_packer {
     bool profiling = false;
     bool ev_valid = false;
 
-    // ---- per-handle constants (rspt_hip_packer_create; h_nsmall at the first compress) ----
+    // ---- per-handle constants (rspt_hip_packer_create) ----
     Stream stream;
-    // the small-block encoder runs beside the big one (it fills the CUs the persistent grid frees in its tail)
-    Stream side;
-    Event ev_fork, ev_join;
     Event ev[ST_COUNT + 1];  // profiling
     Dev<unsigned long long> stamps;  // diagnostic s_memtime stamps: [512 hzr blocks][16 waves][8]
     Dev<CrcConsts> crc;
@@ -331,7 +328,6 @@ struct rspt_hip_packer {
     Dev<float> cos_tab, cos_tab_t;
     Dev<double2> fft_tw;    // [n] (cos, sin)(2 pi t / n)
     Dev<double2> fft_post;  // [n] (cos, sin)(pi k / 2n)
-    Pinned<uint32_t> h_nsmall;  // device-visible: the small-block count of a recent batch (written by k_encode_small)
     // the copy streams of the many-block pipeline and the feed, made by whichever of them comes first
     Stream m_up, m_down;
 
@@ -876,14 +872,6 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
             return RSPT_HIP_ERR_LAUNCH;
     }
     for (int i = 0; i <= ST_COUNT; ++i) hipEventCreate(p->ev[i].out());
-    // (highest priority: the latency-bound small blocks go first and are done long before the big encoder, so that the
-    // join at the end of the call finds its event complete)
-    int prio_lo = 0, prio_hi = 0;
-    hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (hipStreamCreateWithPriority(p->side.out(), hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(p->ev_fork.out(), hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(p->ev_join.out(), hipEventDisableTiming) != hipSuccess)
-        return RSPT_HIP_ERR_LAUNCH;
     if (kind == RSPT_HIP_KIND_DCT) {
         const double ratio1 = sqrt(2.0 / (double)(int)ns);
         const float cs0 = (float)(1 / sqrt(2));
@@ -951,7 +939,7 @@ void rspt_hip_packer_destroy(rspt_hip_packer* p) {
     hipSetDevice(p->device);
     // An open feed ends first: its partly filled group is still submitted, and that launch needs the workspace and constants.
     if (p->feed) rspt_hip_feed_end(p);
-    const hipStream_t streams[] = {p->stream, p->side, p->lag.stream};
+    const hipStream_t streams[] = {p->stream, p->lag.stream};
     for (hipStream_t s : streams)
         if (s) hipStreamSynchronize(s);
     p->fir.wait_all();  // (the FIR and median stages run on the caller's streams)
@@ -988,7 +976,7 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     w.zcap_words = nhb + max_blocks + 32 + 2 * max_blocks * (size_t)g.nch + 2;
     for (int i = 0; i < 2; ++i) ok &= hipMalloc(w.zbuf[i].out(), w.zcap_words * sizeof(uint32_t)) == hipSuccess;
     ok &= hipMalloc(w.big_list.out(), nhb * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(w.small_list.out(), nhb * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.staging.out(), nhb * (size_t)kStageSlotWords * sizeof(uint32_t)) == hipSuccess;
     ok &= hipMalloc(w.hist.out(), nhb * kSymStride * sizeof(uint32_t)) == hipSuccess;
     ok &= hipMalloc(w.cw.out(), nhb * kSymStride * sizeof(uint32_t)) == hipSuccess;
     ok &= hipMalloc(w.seghist.out(), nhb * (size_t)kSegHistStride * sizeof(uint16_t)) == hipSuccess;
@@ -1033,8 +1021,8 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
 // batch at a time on one stream; profiles/r04_notes.md, profiles/r04_pipeline_experiment.patch.)
 // front:  zero region, front-end kernel(s), escalation scan / fix-up, list of k_hist's blocks     (HBM-bound)
 // hist:   k_hist                                                                                  (vector-issue bound)
-// tree:   k_tree + k_layout                                                                       (latency chains, chip mostly idle)
-// small:  k_encode_small                                                                          (latency-bound, one wave per block)
+// tree:   k_tree + k_layout                                                                       (latency chains, chip mostly idle; the
+//                                                                                                  small blocks are encoded under the dense trees)
 // encode: k_encode                                                                                (vector-issue bound)
 static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, hipStream_t st) {
     const Geom& g = p->g;
@@ -1123,7 +1111,7 @@ static int phase_tree(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
     const Geom& g = p->g;
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
     hipLaunchKernelGGL(k_tree, dim3((nhb + 3) / 4), dim3(256), 0, st, p->ws.hist, p->ws.planes, g, p->ws.nbuse, p->nzflag, nhb, p->ws.cw, p->ws.tdesc, p->ws.meta, p->ws.seghist, p->ws.segbase,
-                       p->ws.zbuf[p->ws.zset ^ 1], (uint32_t)p->ws.zcap_words, p->psel);
+                       p->ws.zbuf[p->ws.zset ^ 1], (uint32_t)p->ws.zcap_words, p->crc, p->ws.staging, p->psel);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -1132,43 +1120,22 @@ static int phase_layout(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_
     const Geom& g = p->g;
     WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
     hipLaunchKernelGGL(k_layout, dim3(B), dim3(256), 0, st, g, p->ws.nbuse, p->ws.meta, p->ws.means, (uint8_t*)d_dst, (uint64_t)dst_stride, p->ws.out_off,
-                       d_sizes, p->crc, p->nzflag, wq, p->ws.big_list, p->ws.small_list, p->ws.plane_dirty, p->dirty_shift, p->psel);
+                       d_sizes, p->crc, p->nzflag, wq, p->ws.big_list, p->ws.plane_dirty, p->dirty_shift, p->psel);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
 
-static int phase_small(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_stride, hipStream_t ss) {
-    const Geom& g = p->g;
-    const uint32_t nhb = B * kMaxPlanes * g.nblk;
-    WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
-    const uint32_t want = (nhb + kSmallWaves - 1) / kSmallWaves;
-    const uint32_t sgrid = (uint32_t)(6 * p->num_cu) < want ? (uint32_t)(6 * p->num_cu) : want;  // ~22 KiB of LDS per workgroup
-    hipLaunchKernelGGL(k_encode_small, dim3(sgrid), dim3(kSmallWaves * 64), 0, ss, p->ws.planes, g, p->nzflag, p->ws.meta, p->ws.cw, p->ws.tdesc, p->ws.out_off,
-                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->ws.small_list, p->ablate, p->h_nsmall);
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
-}
-
-// `yield`: an eighth of the grid steps aside for k_encode_small running beside it on the side stream
-static int phase_encode(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_stride, hipStream_t st, uint32_t yield) {
+static int phase_encode(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_stride, hipStream_t st) {
     const Geom& g = p->g;
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
     WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
     hipLaunchKernelGGL(k_encode, dim3(persistent_grid(p, nhb, p->enc_grid)), dim3(kEncThreads), 0, st, p->ws.planes, g, p->nzflag, p->ws.meta, p->ws.cw, p->ws.tdesc, p->ws.out_off,
-                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->ws.big_list, p->ws.segbase, p->ws.lists, p->ws.listinfo, p->stamps, yield);
+                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->ws.big_list, p->ws.segbase, p->ws.lists, p->ws.listinfo, p->stamps, p->ws.staging, nhb);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
 
-static int ensure_nsmall(rspt_hip_packer* p) {
-    if (!p->h_nsmall) {
-        if (hipHostMalloc((void**)p->h_nsmall.out(), sizeof(uint32_t), hipHostMallocMapped) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        *p->h_nsmall = 0xFFFFFFFFu;  // (unknown yet)
-    }
-    return RSPT_HIP_OK;
-}
-
-// one batch, start to end on one stream (the small-block encoder beside the big one on the handle's side stream)
+// one batch, start to end on one stream
 static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t nblocks, void* d_dst, size_t dst_stride, uint64_t* d_sizes, hipStream_t st) {
     int rc = rspt_hip_reserve(p, nblocks);
     if (rc) return rc;
@@ -1197,21 +1164,7 @@ static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t n
     if ((rc = phase_layout(p, B, d_dst, dst_stride, d_sizes, st)) != 0) return rc;
 
     stamp(p, ST_ENCODE, st);
-    if ((rc = ensure_nsmall(p)) != 0) return rc;
-    // Both encoders depend on k_layout only.  The small-block one goes to the side stream (the big one yields it room) -- unless the
-    // recent batches of this handle held no small blocks at all: the fork and join of a second stream cost ~10 us, an empty
-    // kernel in line 2.  The guess only decides where the kernel runs.
-    const bool side = *(volatile uint32_t*)p->h_nsmall != 0u;
-    hipStream_t ss = side ? p->side : st;
-    if (side) {
-        HIPCHK(p, hipEventRecord(p->ev_fork, st));
-        HIPCHK(p, hipStreamWaitEvent(p->side, p->ev_fork, 0));
-    }
-    if ((rc = phase_small(p, B, d_dst, dst_stride, ss)) != 0) return rc;
-    if (side) HIPCHK(p, hipEventRecord(p->ev_join, p->side));
-    if ((rc = phase_encode(p, B, d_dst, dst_stride, st, 1u)) != 0) return rc;
-    stamp(p, ST_ENCODE_SMALL, st);
-    if (side) HIPCHK(p, hipStreamWaitEvent(st, p->ev_join, 0));
+    if ((rc = phase_encode(p, B, d_dst, dst_stride, st)) != 0) return rc;
     stamp(p, ST_COUNT, st);
     if (p->profiling) p->ev_valid = true;
     HIPCHK(p, hipGetLastError());

@@ -1,4 +1,4 @@
-"""how many hzr blocks of a batch go to which encoder (k_encode heavy / light, k_encode_small, Fill / skipped)"""
+"""how many hzr blocks of a batch go to which encoder (k_encode heavy / light, staged by k_tree, Fill / skipped)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -18,7 +18,6 @@ STAGES = {
     "hzr_tree": ["k_tree"],
     "layout": ["k_layout"],
     "hzr_encode": ["k_encode("],
-    "hzr_encode_small": ["k_encode_small"],
 }
 
 

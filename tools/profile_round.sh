@@ -7,7 +7,7 @@ timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- 
 timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-verify > $O/write.log 2>&1 || exit 1
 timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d $O/valu -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-verify > $O/valu.log 2>&1 || exit 1
 python3 tools/hbm_traffic.py $O/fetch $O/write $O/hbm_traffic.json > /dev/null || exit 1
-python3 tools/pmc_summary.py $O/valu k_encode_small k_encode k_hist k_tile_stream k_tree k_layout > $O/pmc_issue.txt || exit 1
+python3 tools/pmc_summary.py $O/valu k_encode k_hist k_tile_stream k_tree k_layout > $O/pmc_issue.txt || exit 1
 cp $O/hbm_traffic.json profiles/hbm_traffic.json
 timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
 cat $O/bench.json
