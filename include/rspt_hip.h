@@ -295,6 +295,32 @@ int rspt_hip_gather_wait(rspt_hip_packer* p, int slot, void* stream);
 int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
                                      int init_nr_samples, int per_channel, void* stream);
 
+/* ---- the IIR pre-filter with a carried state: one i_filter per channel over a recording that arrives in blocks ------
+ * The nblocks blocks of a call are consecutive pieces of ONE recording (block b holds its rows b * ns .. (b + 1) * ns - 1) and
+ * the next call on the same state continues where this one ended.  Per channel there is one reference object,
+ * i_filter::new_iir(n, d, nr_coefficients): on the channel's first sample ever it runs init_history_values(that sample,
+ * init_nr_samples), then filter_opt((double)x) on every sample of every block of every call, the rings running on
+ * (iir_filter.cpp:81-107); each result is truncated and stored in place as rspt_hip_iir_prefilter_batch_dev does, the rings
+ * keep the untruncated doubles -- so a NaN that enters a ring stays there across blocks and calls, as in the reference.
+ * Bit-identical with the reference's object driven the same way.  This is the per-channel driving only: one object shared by
+ * the channels AND carried over blocks has no counterpart in a use of the reference.
+ *   d_state         a caller-owned device buffer of rspt_hip_iir_state_bytes bytes, 8-byte aligned: per channel c, at byte
+ *                   88 * c, double x[5] (x_ring_: the last inputs, newest first), double y[5] (y_ring_: the last outputs,
+ *                   newest first, untruncated), uint64 started; places past nr_coefficients are not used.  All-zero bytes
+ *                   are a fresh object for every channel.  A state belongs to the handle's (bps, nch) and to the
+ *                   nr_coefficients that it was first used with; the coefficient VALUES may change from call to call, the
+ *                   rings simply run on.  Two states may be used in turn on one handle (two recordings of one shape).
+ *   init_nr_samples read only by a channel whose state is fresh (any value 0 .. 2^28 otherwise)
+ * RSPT_HIP_ERR_ARG for everything rspt_hip_iir_prefilter_batch_dev refuses, a NULL or misaligned d_state and a NULL bytes;
+ * RSPT_HIP_ERR_UNSUPPORTED for a call of 2^31 - 2^17 rows (nblocks * ns) or more: split the call, with a state that is exact.
+ * A channel is one serial chain over the whole call and only nch lanes run, so a call takes about the stateless per-channel
+ * time of ONE lane over nblocks * ns samples whatever nch <= 64 is (DESIGN.md 4b has the measured figures); calls of fewer
+ * than 64 rows take the slower one-thread-per-channel form.  Asynchronous on `stream`; calls on one handle or one state are
+ * stream-ordered.  The stage allocates nothing. */
+int rspt_hip_iir_state_bytes(rspt_hip_packer* p, size_t* bytes); /* nch * 88 */
+int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                                      int init_nr_samples, void* d_state, void* stream);
+
 /* ---- optional stage in front of compress: the reference's FIR pre-filter ---------------------------------------
  * i_filter::new_fir(kernel, kernel_size), init_history_values(first sample of the channel, n), filter_opt on every sample
  * (lib_rspt/lib_filter/fir_filter.cpp), result truncated to int32 and stored in the native sample width, on nblocks
@@ -311,6 +337,30 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
  * are stream-ordered.  Device and page-locked memory the stage needs belong to the handle. */
 int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
                                      void* stream);
+
+/* ---- the FIR pre-filter with a carried state: one i_filter per channel over a recording that arrives in blocks ------
+ * The nblocks blocks of a call are consecutive pieces of ONE recording and the next call on the same state continues where this
+ * one ended.  Per channel there is one reference object, i_filter::new_fir(kernel, K): init_history_values(the channel's first
+ * sample ever) once, then filter_opt on every sample of every block of every call (fir_filter.cpp:52-60).  With X = the
+ * channel's whole recording so far,
+ *     y[t] = ((((0.0 + X[t-K+1]*k[0]) + X[t-K+2]*k[1]) + ...) + X[t]*k[K-1]),    X[s < 0] = X[0]
+ * rounded, truncated and stored as rspt_hip_fir_prefilter_batch_dev does; in place and out of place as there (out of place
+ * d_src is only read).  Bit-identical with the reference's object driven the same way.
+ *   d_state         a caller-owned device buffer of rspt_hip_fir_state_bytes(p, kernel_size) bytes, 8-byte aligned: uint64
+ *                   started, then the last K - 1 input rows of the recording, oldest first, each row nch samples of bps bytes
+ *                   as in a block (the object's ring without its newest place), padded to a multiple of 8 bytes.  All-zero
+ *                   bytes are a fresh object for every channel.  K - 1 may exceed ns and may exceed a whole call: the new
+ *                   state is the tail of (old state ++ the call's rows).  A state belongs to the handle's (bps, nch) and to
+ *                   the kernel_size that sized it; the kernel's VALUES may change from call to call.  Two states may be used
+ *                   in turn on one handle.
+ * RSPT_HIP_ERR_ARG for everything rspt_hip_fir_prefilter_batch_dev refuses, a NULL or misaligned d_state and a NULL bytes;
+ * RSPT_HIP_ERR_UNSUPPORTED for a call of 2^31 - 2^17 rows (nblocks * ns) or more: split the call, with a state that is exact.
+ * Every output depends on inputs only, so the stage is as parallel as the stateless one and does the same multiply-add work,
+ * plus two copies of K - 1 rows.  Asynchronous on `stream`; calls on one handle or one state are
+ * stream-ordered.  The stage allocates nothing per state: the staged copy of the old state belongs to the handle. */
+int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes); /* 8 + ((K - 1) * nch * bps rounded up to 8) */
+int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                      void* d_state, void* stream);
 
 /* ---- optional stage in front of compress: the reference's rolling-window median -------------------------------
  * rolling_window_median<double>(window) (lib_rspt/lib_stat/rolling_window_median.h), one fresh object per channel of every

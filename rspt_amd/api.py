@@ -25,6 +25,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_block_bytes", "rspt_hip_current_nb", "rspt_hip_set_nb", "rspt_hip_set_verify", "rspt_hip_reserve", "rspt_hip_compress_batch_dev",
     "rspt_hip_decompress_batch_dev", "rspt_hip_decompress_packed_dev", "rspt_hip_pack_bound", "rspt_hip_pack_batch_dev", "rspt_hip_stream", "rspt_hip_synchronize", "rspt_hip_set_profiling", "rspt_hip_stage_count",
     "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_design_iir",
+    "rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev",
     "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
     "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
@@ -112,6 +113,13 @@ def lib():
     L.rspt_hip_iir_prefilter_batch_dev.restype = C.c_int
     L.rspt_hip_iir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
                                                    C.c_int, C.c_void_p]
+    L.rspt_hip_iir_state_bytes.restype, L.rspt_hip_iir_state_bytes.argtypes = C.c_int, [C.c_void_p, _szp]
+    L.rspt_hip_iir_prefilter_stream_dev.restype = C.c_int
+    L.rspt_hip_iir_prefilter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
+                                                    C.c_void_p, C.c_void_p]
+    L.rspt_hip_fir_state_bytes.restype, L.rspt_hip_fir_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
+    L.rspt_hip_fir_prefilter_stream_dev.restype = C.c_int
+    L.rspt_hip_fir_prefilter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p, C.c_void_p]
     L.rspt_hip_fir_prefilter_batch_dev.restype = C.c_int
     L.rspt_hip_fir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p]
     L.rspt_hip_median_filter_batch_dev.restype = C.c_int
@@ -354,8 +362,32 @@ class SignalPacker:
         self._check("rspt_hip_pack_batch_dev", rc)
         return d_packed, d_total
 
-    def iir_prefilter_batch(self, d_buf, n, d, init_nr_samples=2000, per_channel=False, stream=None):
-        """The reference's pre-filter step (rspt_test.cpp:116-136) on device-resident blocks, in place; asynchronous."""
+    def iir_state_bytes(self):
+        n = C.c_size_t()
+        self._check("rspt_hip_iir_state_bytes", self._L.rspt_hip_iir_state_bytes(self._h, C.byref(n)))
+        return n.value
+
+    def iir_state(self, device=None):
+        """A zeroed state for iir_prefilter_batch(state=...): a fresh filter for every channel (uint8 device tensor)."""
+        import torch
+
+        return torch.zeros(self.iir_state_bytes(), dtype=torch.uint8, device=device if device is not None else "cuda")
+
+    def fir_state_bytes(self, kernel_size):
+        n = C.c_size_t()
+        self._check("rspt_hip_fir_state_bytes", self._L.rspt_hip_fir_state_bytes(self._h, int(kernel_size), C.byref(n)))
+        return n.value
+
+    def fir_state(self, kernel_size, device=None):
+        """A zeroed state for fir_prefilter_batch(state=...) with a kernel of kernel_size taps: a fresh filter for every channel."""
+        import torch
+
+        return torch.zeros(self.fir_state_bytes(kernel_size), dtype=torch.uint8, device=device if device is not None else "cuda")
+
+    def iir_prefilter_batch(self, d_buf, n, d, init_nr_samples=2000, per_channel=False, stream=None, state=None):
+        """The reference's pre-filter step (rspt_test.cpp:116-136) on device-resident blocks, in place; asynchronous.
+        state: None, or an iir_state() tensor: the blocks are then consecutive pieces of one recording, one filter per channel
+        running through them and on into the next call (rspt_hip_iir_prefilter_stream_dev); needs per_channel=True."""
         import torch
 
         assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous()
@@ -364,6 +396,14 @@ class SignalPacker:
         nn, dd = np.ascontiguousarray(n, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
         assert nn.size == dd.size
         st = stream if stream is not None else torch.cuda.current_stream(d_buf.device).cuda_stream
+        if state is not None:
+            if not per_channel:
+                raise ValueError("iir_prefilter_batch: a carried state is one filter per channel (per_channel=True)")
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.iir_state_bytes()
+            rc = self._L.rspt_hip_iir_prefilter_stream_dev(self._h, d_buf.data_ptr(), nblocks, nn.ctypes.data_as(C.POINTER(C.c_double)),
+                                                           dd.ctypes.data_as(C.POINTER(C.c_double)), nn.size, init_nr_samples, state.data_ptr(), st)
+            self._check("rspt_hip_iir_prefilter_stream_dev", rc)
+            return d_buf
         rc = self._L.rspt_hip_iir_prefilter_batch_dev(self._h, d_buf.data_ptr(), nblocks, nn.ctypes.data_as(C.POINTER(C.c_double)),
                                                       dd.ctypes.data_as(C.POINTER(C.c_double)), nn.size, init_nr_samples, int(bool(per_channel)), st)
         self._check("rspt_hip_iir_prefilter_batch_dev", rc)
@@ -382,11 +422,19 @@ class SignalPacker:
         st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
         return nblocks, out, st
 
-    def fir_prefilter_batch(self, d_src, kernel, d_dst=None, stream=None):
+    def fir_prefilter_batch(self, d_src, kernel, d_dst=None, stream=None, state=None):
         """The reference's FIR pre-filter (i_filter::new_fir, init_history_values, filter_opt; rspt_hip.h) on device-resident
-        blocks: in place when d_dst is None, else into d_dst (same size, not overlapping d_src); asynchronous.  Returns the output."""
+        blocks: in place when d_dst is None, else into d_dst (same size, not overlapping d_src); asynchronous.  Returns the output.
+        state: None, or a fir_state(len(kernel)) tensor: the blocks are then consecutive pieces of one recording, one filter per
+        channel running through them and on into the next call (rspt_hip_fir_prefilter_stream_dev)."""
         nblocks, out, st = self._window_call_buffers(d_src, d_dst, stream)
         k = np.ascontiguousarray(kernel, dtype=np.float64).reshape(-1)
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.fir_state_bytes(k.size)
+            rc = self._L.rspt_hip_fir_prefilter_stream_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, k.ctypes.data_as(C.POINTER(C.c_double)),
+                                                           k.size, state.data_ptr(), st)
+            self._check("rspt_hip_fir_prefilter_stream_dev", rc)
+            return out
         rc = self._L.rspt_hip_fir_prefilter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, k.ctypes.data_as(C.POINTER(C.c_double)),
                                                       k.size, st)
         self._check("rspt_hip_fir_prefilter_batch_dev", rc)

@@ -31,6 +31,15 @@ struct IirCoef {
     int32_t init_steps;  // 4 * nr_samples of init_history_values (iir_filter.cpp:106-110)
 };
 
+// The carried state of one channel (rspt_hip_iir_prefilter_stream_dev; layout: rspt_hip.h): the rings as the reference's object
+// holds them between two filter_opt calls, newest first, the y ring as untruncated doubles.  All-zero bytes: a channel that
+// has not started (its first call runs init_history_values).
+struct IirCarry {
+    double x[5], y[5];
+    uint64_t started;
+};
+static_assert(sizeof(IirCarry) == 88, "rspt_hip.h documents 88 bytes per channel");
+
 // The filter state: x[i] = input i samples ago, y[i] = output i samples ago (x_ring_ / y_ring_ of iir_filter.cpp:46-62).
 template <int NC>
 struct IirState {
@@ -81,10 +90,11 @@ struct IirState {
 // Every product and sum is rounded on its own, in the reference's order.  Samples are handled in chunks of CH: the next
 // chunk's loads are in flight while this one is filtered, the feed-forward sums of the chunk are independent work the
 // scheduler places into the latency of the dependent chain, and the results leave as one store per sample.
-template <int BPS, int NC>
+// INIT = false: the history is the caller's (a carried state), the samples follow whatever f holds.
+template <int BPS, int NC, bool INIT = true>
 __device__ __forceinline__ void iir_channel(uint8_t* p, size_t stride, uint32_t ns, const IirCoef& c, IirState<NC>& f, bool aligned) {
-    const double x0 = (double)sample_load<BPS>(p, aligned);
-    {
+    if (INIT) {
+        const double x0 = (double)sample_load<BPS>(p, aligned);
         int32_t i = 0;
         for (; i < c.init_steps && i < NC - 1; ++i) f.step(c, x0);  // (the x ring still holds older inputs)
         if (i < c.init_steps) {
@@ -172,6 +182,37 @@ __global__ __launch_bounds__(64) void k_iir(uint8_t* __restrict__ buf, uint32_t 
     }
 }
 
+// The carried form of k_iir (calls of fewer than 64 rows): one thread per channel of ONE run of ns rows (the blocks of a call lie
+// back to back, so they are one interleaved block of nblocks * ns rows).  A channel that has started continues from its rings;
+// one that has not runs init_history_values on the call's first sample.  The rings are saved when the call ends.
+template <int BPS, int NC>
+__global__ __launch_bounds__(64) void k_iir_carry(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, IirCoef c, IirCarry* __restrict__ state) {
+    const uint32_t ch = blockIdx.x * 64u + threadIdx.x;
+    if (ch >= nch) return;
+    const size_t stride = (size_t)nch * BPS;
+    const bool aligned = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;
+    uint8_t* p = buf + (size_t)ch * BPS;
+    IirCarry& s = state[ch];
+    IirState<NC> f;
+    if (s.started) {
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            f.x[i] = s.x[i];
+            f.y[i] = s.y[i];
+        }
+        iir_channel<BPS, NC, false>(p, stride, ns, c, f, aligned);
+    } else {
+        f.clear();
+        iir_channel<BPS, NC, true>(p, stride, ns, c, f, aligned);
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        s.x[i] = f.x[i];
+        s.y[i] = f.y[i];
+    }
+    s.started = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The pipelined form.  A lone wave issues one instruction every ~2 ns whatever it is (tools/issue_rate.hip), so the time of a
 // channel is its sample count times the instructions the wave that HOLDS THE FILTER STATE has to issue per sample.  k_iir above
@@ -185,6 +226,15 @@ __global__ __launch_bounds__(64) void k_iir(uint8_t* __restrict__ buf, uint32_t 
 //   wave 5      stores the filtered samples of the chunk before
 // One workgroup barrier per chunk of 64 samples; the chunk being produced, the one in the recurrence and the one being stored
 // live in double-buffered LDS tiles [sample][lane] (conflict-free).  Needs ns >= 64 and init_steps >= NC - 1 (else k_iir).
+//
+// CARRY (rspt_hip_iir_prefilter_stream_dev): per-channel driving of ONE run of ns rows (nblocks = 1: the blocks of the call back to
+// back), the filter of channel ch living in state[ch].  A channel that has started loads its y ring instead of the history
+// initialisation, and the first producer's first set takes the NC - 1 inputs in front of the call from the state's x ring (in
+// place those rows are long overwritten); a channel that has not started runs init_history_values, and what its x ring then
+// holds -- x0 in the first min(init_steps, NC) places, 0.0 behind them -- stands in front of the call, so any init_steps will
+// do.  Whoever holds the run's last sample hands the last NC inputs on through L.xlast, as shared mode does for the next
+// channel, and the recurrence wave writes both rings back behind the last chunk.  The state is read before the first barrier
+// and written behind the last chunk's, by the workgroup that owns the channel.
 constexpr uint32_t kIirChunk = 64, kIirProd = 4, kIirPart = kIirChunk / kIirProd;  // four producer waves, 16 samples of a chunk each
 constexpr uint32_t kIirThreads = 64 * (2 + kIirProd);
 struct IirPipeLds {
@@ -195,10 +245,11 @@ struct IirPipeLds {
 // ~98.5 KiB of static LDS: one workgroup per CU, and only on a part with more than 64 KiB per workgroup (gfx950: 160 KiB)
 static_assert(sizeof(IirPipeLds) <= 160 * 1024, "k_iir_pipe: the tiles must fit one CU's LDS");
 
-template <int BPS, int NC, bool SHARED, bool ALIGNED>
+template <int BPS, int NC, bool SHARED, bool ALIGNED, bool CARRY = false>
 __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, IirCoef c, uint32_t nblocks,
-                                                 uint32_t lanes_per_wg) {
+                                                 uint32_t lanes_per_wg, IirCarry* __restrict__ state) {
     static_assert(NC >= 2 && NC <= 5, "IirPipeLds::xlast holds five inputs per channel");
+    static_assert(!(SHARED && CARRY), "a carried state is one filter per channel");
     __shared__ IirPipeLds L;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -227,6 +278,9 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
     constexpr int H = NC - 1;            // inputs in front of a sample that its feed-forward sum needs
     constexpr uint32_t SET = kIirPart + H;  // a producer's samples per chunk: its part and the H in front of it
     constexpr uint32_t kWriter = 1 + kIirProd;
+    // (lanes past the shape look at channel 0's state along with it and write nothing)
+    IirCarry* const cs = CARRY ? state + (valid ? ch0 : 0u) : nullptr;
+    const bool started = CARRY && cs->started != 0;
     for (uint32_t sc = 0; sc < nser; ++sc) {
         uint8_t* p = base + (size_t)sc * BPS;
         const double x0 = (double)sample_load<BPS>(p, aligned);
@@ -254,7 +308,10 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
         }
         for (uint32_t t = 0; t < nchunks + 2; ++t) {
             if (role == 0u) {
-                if (t == 0) {
+                if (CARRY && t == 0 && started) {
+#pragma unroll
+                    for (int i = 0; i < NC; ++i) f.y[i] = cs->y[i];
+                } else if (t == 0) {
                     // init_history_values (iir_filter.cpp:106-110): 4 * nr_samples calls of filter() on the channel's first sample
                     int32_t i = 0;
                     for (; i < c.init_steps && i < NC; ++i) f.step(c, x0);  // (until the x ring holds nothing but x0)
@@ -320,6 +377,14 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
 #pragma unroll
                         for (int i = 0; i < NC; ++i) f.x[i] = L.xlast[i][lane];
                     }
+                    if (CARRY && t == nchunks && valid) {  // the object as it stands behind the call's last sample
+#pragma unroll
+                        for (int i = 0; i < NC; ++i) {
+                            cs->x[i] = L.xlast[i][lane];
+                            cs->y[i] = f.y[i];
+                        }
+                        cs->started = 1;
+                    }
                 }
             } else if (role == kWriter) {
                 if (t >= 2) {
@@ -358,6 +423,10 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
                 if (s0 < 0) {  // (wave-uniform: the first producer's first set only)
 #pragma unroll
                     for (uint32_t j = 0; j < SET; ++j) xs[j] = (s0 + (int32_t)j < 0) ? x0 : xs[j];
+                    if (CARRY) {  // (s0 = -H: element j < H is the input H - j samples in front of the call, place H - 1 - j of the x ring)
+#pragma unroll
+                        for (int j = 0; j < H; ++j) xs[j] = started ? cs->x[H - 1 - j] : (H - 1 - j < c.init_steps ? x0 : 0.0);
+                    }
                 }
 #pragma unroll
                 for (uint32_t e = 0; e < kIirPart; ++e) {
@@ -368,7 +437,7 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
 #endif
                     L.ff[t & 1u][(role - 1u) * kIirPart + e][lane] = a;
                 }
-                if (SHARED && t + 1 == nchunks) {  // whoever holds the channel's last sample hands its last inputs on
+                if ((SHARED || CARRY) && t + 1 == nchunks) {  // whoever holds the channel's last sample hands its last inputs on
                     const int32_t last = (int32_t)ns - 1 - (s0 + H);  // index of sample ns-1 in this wave's part
                     if (last >= 0 && last < (int32_t)kIirPart) {
 #pragma unroll

@@ -24,6 +24,13 @@
 // earlier-processed chunk has written, and writes its own rows behind a barrier that follows all of its reads.  The only
 // rows a workgroup reads but does not own are the K - 1 in front of its span; k_fir_halo copies them into a side buffer
 // owned by the handle BEFORE the filter kernel starts (stream order), and the filter reads them there.
+//
+// Carried state (rspt_hip_fir_prefilter_stream_dev): the blocks of a call lie back to back, so the call is ONE block of
+// nblocks * ns rows, and the reference's object between two calls is its ring: the last K - 1 inputs of every channel.  The
+// K - 1 rows in front of the call's row 0 are one more piece (`head`), staged from the state -- or, on a fresh state, the
+// call's first row K - 1 times, which is what init_history_values leaves -- by k_fir_carry BEFORE anything is overwritten; a
+// second k_fir_carry launch then writes the new state, the last K - 1 rows of (head ++ call), from the staged head and d_src.
+// Stream order puts both in front of k_fir, so neither an in-place call nor K - 1 > nblocks * ns needs anything else.
 #include "common.hpp"
 
 // NO contraction in this file: every product and sum rounded on its own, as in the reference's x86-64 build (filter.hip says
@@ -77,10 +84,11 @@ __device__ __forceinline__ void fir_taps(double (&acc)[R], const double* __restr
 
 // One span of one channel group of one block per unit.  `halo` is null out of place; in place it holds, for span w >= 1 of
 // block b, the K - 1 rows in front of the span at halo + ((b * (nsplit - 1) + w - 1) * (K - 1)) * stride, each a copy of the
-// block's row with the same layout.
+// block's row with the same layout.  `head` is null without a carried state; else it holds the K - 1 rows in front of row 0
+// of block b at head + b * (K - 1) * stride (rows -(K - 1) .. -1 of the recording), and span 0 reads them in place of x[0].
 template <int BPS, bool ALIGNED>
 __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* __restrict__ coef,
-                                                    WinGeom g) {
+                                                    WinGeom g, const uint8_t* head) {
     constexpr uint32_t R = kFirR;
     const uint32_t tid = threadIdx.x;
     const uint32_t cl = tid % g.cw, sub = tid / g.cw;
@@ -101,15 +109,17 @@ __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t
         const uint32_t lane_off = subc * R * stride + chc * BPS;  // (below 2^31: the host checks)
         const uint64_t blk = b * g.block_bytes;
         const int32_t lo = (int32_t)(w * g.span);
-        const int32_t hi = min((int32_t)g.ns, lo + (int32_t)g.span);
-        // rows below `lim` come from the halo copy (in place, every span but the first)
-        const int32_t lim = (halo && w) ? lo : 0;
-        // address of row 0 of the lane's channel in the block, and where row 0 would be in the halo copy (only rows >= lo - K + 1
+        const int32_t hi = (int32_t)min((uint64_t)g.ns, (uint64_t)lo + g.span);
+        // rows below `lim` come from a staged copy: the halo (in place, every span but the first) or the head (carried state,
+        // span 0: rows below 0, down to `smin`)
+        const uint8_t* piece = w ? (halo ? halo + ((b * (g.nsplit - 1) + w - 1) * (uint64_t)(K - 1)) * stride : nullptr)
+                                 : (head ? head + (b * (uint64_t)(K - 1)) * stride : nullptr);
+        const int32_t lim = piece ? lo : 0;
+        const int32_t smin = (head && !w) ? -(int32_t)(K - 1) : 0;
+        // address of row 0 of the lane's channel in the block, and where row 0 would be in the staged copy (only rows >= lo - K + 1
         // are ever read there)
         const uintptr_t srow0 = reinterpret_cast<uintptr_t>(src + blk) + chc * BPS;
-        const uintptr_t hrow0 = lim ? reinterpret_cast<uintptr_t>(halo) + ((b * (g.nsplit - 1) + w - 1) * (uint64_t)(K - 1)) * stride + chc * BPS -
-                                          (uint64_t)(lo - (int32_t)(K - 1)) * stride
-                                    : srow0;
+        const uintptr_t hrow0 = piece ? reinterpret_cast<uintptr_t>(piece) + chc * BPS - (uint64_t)(int64_t)(lo - (int32_t)(K - 1)) * stride : srow0;
         const uint32_t nq = ((uint32_t)(hi - lo) + C - 1) / C;
         for (uint32_t q = nq; q-- > 0;) {
             const int32_t a = lo + (int32_t)(q * C);
@@ -117,16 +127,16 @@ __global__ __launch_bounds__(kFirThreads) void k_fir(const uint8_t* src, uint8_t
             const int32_t first = a - (int32_t)(G * R - 1);  // row of element 0 of the chunk's first lane
             const int32_t sb = first + (int32_t)(subc * R);
             // wave-uniform: every row the chunk touches (up to a + C + R) lies in [lim, ns) -- one address add per load, no clamps
-            const bool fast = first >= lim && a + (int32_t)(C + R) <= ns1;
+            const bool fast = first >= lim && a <= ns1 - (int32_t)(C + R);
             double acc[R];
             if (fast) {
                 const uint8_t* rowbase = src + blk + (uint64_t)(uint32_t)first * stride;
                 fir_taps<R>(acc, coef, K, [&](uint32_t m) { return sample_load<BPS>(rowbase + (uint64_t)m * stride + lane_off, ALIGNED); });
             } else {
                 fir_taps<R>(acc, coef, K, [&](uint32_t m) {
-                    const int32_t s = min(max(sb + (int32_t)m, 0), ns1);  // x[s < 0] = x[0]; rows past the block are never used
+                    const int32_t s = min(max(sb + (int32_t)m, smin), ns1);  // x[s < 0] = x[0] without a head; rows past the block are never used
                     const uintptr_t base = s < lim ? hrow0 : srow0;
-                    return sample_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(uint32_t)s * stride), ALIGNED);
+                    return sample_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(int64_t)s * stride), ALIGNED);
                 });
             }
             __syncthreads();  // every lane of the workgroup has read the chunk's rows before any of them is overwritten
@@ -157,6 +167,26 @@ __global__ __launch_bounds__(256) void k_fir_halo(const uint8_t* __restrict__ sr
         } else {
             for (uint64_t i = threadIdx.x; i < n; i += 256) d[i] = s[i];
         }
+    }
+}
+
+// The two byte movers of a carried-state call, n = (K - 1) * stride bytes each (rows of the block's layout), N = the call's rows:
+//   SAVE = false   head <- the state's rows if it has started, else the call's row 0 in every row (init_history_values)
+//   SAVE = true    state <- the last K - 1 rows of (head ++ call): the call's last K - 1 rows, or, where the call is shorter
+//                  than that, the head's rows from N on and then the whole call; and the state has started
+// `started` is the state's first word, `rows` follow it.  SAVE = true runs behind SAVE = false and in front of k_fir (stream
+// order), so the state is never read while it is written and d_src is still the input.
+template <bool SAVE>
+__global__ __launch_bounds__(256) void k_fir_carry(const uint8_t* __restrict__ src, uint8_t* head, uint64_t* started, uint8_t* rows, uint64_t n,
+                                                   uint32_t stride, uint32_t K, uint32_t N) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * 256u + threadIdx.x, step = (uint64_t)gridDim.x * 256u;
+    if (!SAVE) {
+        const bool st = *started != 0;
+        for (uint64_t i = i0; i < n; i += step) head[i] = st ? rows[i] : src[i % stride];
+    } else {
+        const uint64_t call = (uint64_t)N * stride;
+        for (uint64_t i = i0; i < n; i += step) rows[i] = call >= n ? src[call - n + i] : i + call < n ? head[i + call] : src[i + call - n];
+        if (i0 == 0) *started = 1;
     }
 }
 

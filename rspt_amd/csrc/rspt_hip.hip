@@ -255,7 +255,8 @@ struct LastCall {
 // rspt_hip_fir_prefilter_batch_dev: the coefficients of the last kSlots calls (the caller's array may go as soon as a call
 // returns, so each call copies it into page-locked memory and from there, on the call's stream, to the device), and the halo
 // rows of an in-place call.  A slot is refilled only once its last call is past it; the halo is replaced, and the handle
-// destroyed, only once the calls of all slots are.
+// destroyed, only once the calls of all slots are.  rspt_hip_fir_prefilter_stream_dev adds `head`, the staged K - 1 rows in front
+// of a carried-state call, under the same rule.
 struct FirStage {
     static constexpr int kSlots = 4;
     struct CoefSlot {
@@ -266,8 +267,8 @@ struct FirStage {
     };
     CoefSlot slot[kSlots];
     int next = 0;
-    Dev<uint8_t> halo;
-    size_t halo_cap = 0;
+    Dev<uint8_t> halo, head;
+    size_t halo_cap = 0, head_cap = 0;
     void wait_all() {
         for (CoefSlot& s : slot) s.last.wait();
     }
@@ -544,14 +545,14 @@ static void launch_iir(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCo
         const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;  // (block_bytes is a multiple of BPS)
         if (per_channel) {
             const uint32_t units = B * g.nch;
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((units + 63) / 64), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, 64u); };
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((units + 63) / 64), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, 64u, (IirCarry*)nullptr); };
             if (al) go(&k_iir_pipe<BPS, NC, false, (BPS == 4 || BPS == 2)>);
             else go(&k_iir_pipe<BPS, NC, false, false>);
         } else {
             // shared mode: lane <-> block; few lanes per workgroup so that the blocks' scattered accesses spread over the CUs
             uint32_t lpw = (B + (uint32_t)p->num_cu - 1) / (uint32_t)p->num_cu;
             lpw = lpw < 1 ? 1 : lpw > 64 ? 64 : lpw;
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((B + lpw - 1) / lpw), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, lpw); };
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((B + lpw - 1) / lpw), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, lpw, (IirCarry*)nullptr); };
             if (al) go(&k_iir_pipe<BPS, NC, true, (BPS == 4 || BPS == 2)>);
             else go(&k_iir_pipe<BPS, NC, true, false>);
         }
@@ -574,12 +575,43 @@ static void launch_iir_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const Ii
     }
 }
 
+// The carried form (rspt_hip_iir_prefilter_stream_dev): the call's blocks as one run of `rows` rows, lane <-> channel, the
+// filters in `state`.  Whether a channel is fresh is known on the device only, so the route depends on the run's length alone.
+template <int BPS, int NC>
+static void launch_iir_stream(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, const IirCoef& c, IirCarry* state, hipStream_t st) {
+    const Geom& g = p->g;
+    const dim3 grid((g.nch + 63) / 64);
+    if (rows >= kIirChunk) {
+        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;
+        const uint64_t run_bytes = (uint64_t)rows * g.nch * BPS;
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kIirThreads), 0, st, buf, g.nch, rows, run_bytes, c, 1u, 64u, state); };
+        if (al) go(&k_iir_pipe<BPS, NC, false, (BPS == 4 || BPS == 2), true>);
+        else go(&k_iir_pipe<BPS, NC, false, false, true>);
+        return;
+    }
+    hipLaunchKernelGGL((k_iir_carry<BPS, NC>), grid, dim3(64), 0, st, buf, g.nch, rows, c, state);
+}
+template <int BPS>
+static void launch_iir_stream_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, const IirCoef& c, IirCarry* state, hipStream_t st) {
+    switch (c.nc) {
+        case 2: launch_iir_stream<BPS, 2>(p, buf, rows, c, state, st); break;
+        case 3: launch_iir_stream<BPS, 3>(p, buf, rows, c, state, st); break;
+        case 4: launch_iir_stream<BPS, 4>(p, buf, rows, c, state, st); break;
+        default: launch_iir_stream<BPS, 5>(p, buf, rows, c, state, st); break;
+    }
+}
+
 // The decomposition of a sliding-window stage (WinGeom): channel groups of up to `threads` lanes' channels, runs of `run`
 // outputs per lane (kFirThreads / kFirR, kMedThreads / kMedRun), and spans along the time axis until there are about four
 // workgroups per CU -- each span at least 4 (K - 1) rows, so that the halo an in-place call stages is at most a quarter of the
-// batch.
-static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run) {
-    const Geom& g = p->g;
+// batch.  run_rows != 0 (a carried-state call): the nblocks blocks, back to back, taken as ONE block of run_rows = nblocks * ns rows.
+static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, uint32_t run_rows = 0) {
+    Geom g = p->g;
+    if (run_rows) {
+        g.ns = run_rows;
+        g.block_bytes = (uint64_t)run_rows * g.nch * g.bps;
+        nblocks = 1;
+    }
     WinGeom f{};
     f.block_bytes = g.block_bytes;
     f.stride = g.nch * g.bps;  // (window_call_checks checks the chunk's row offsets before a launch)
@@ -605,10 +637,11 @@ static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, ui
 }
 
 template <int BPS>
-static void launch_fir(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st) {
+static void launch_fir(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st,
+                       const uint8_t* head = nullptr) {
     const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
-    if (aligned) hipLaunchKernelGGL((k_fir<BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f);
-    else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f);
+    if (aligned) hipLaunchKernelGGL((k_fir<BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f, head);
+    else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f, head);
 }
 
 template <uint32_t N, int BPS>
@@ -1862,17 +1895,49 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
     return RSPT_HIP_OK;
 }
 
+// A carried-state call takes its blocks as one run of nblocks * ns rows, indexed in 32 bits with a chunk's reach beyond the last
+// row: runs of 2^31 - 2^17 rows and more are refused, and the caller splits the call (with a state that split is exact).
+static constexpr uint64_t kStreamMaxRows = (1ull << 31) - (1ull << 17);
+
+int rspt_hip_iir_state_bytes(rspt_hip_packer* p, size_t* bytes) {
+    if (!p || !bytes) return RSPT_HIP_ERR_ARG;
+    *bytes = (size_t)p->g.nch * sizeof(IirCarry);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                                      int init_nr_samples, void* d_state, void* stream) {
+    if (!p || !d_buf || !n || !d || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
+    if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    const uint64_t rows = (uint64_t)nblocks * p->g.ns;
+    if (rows >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    HIPCHK(p, hipSetDevice(p->device));
+    IirCoef c{};
+    for (size_t i = 0; i < nr_coefficients; ++i) {
+        c.n[i] = n[i];
+        c.d[i] = d[i];
+    }
+    c.nc = (uint32_t)nr_coefficients;
+    c.init_steps = 4 * init_nr_samples;
+    hipStream_t st = (hipStream_t)stream;
+    by_bps(p->g.bps, [&](auto bps) { launch_iir_stream_nc<decltype(bps)::value>(p, (uint8_t*)d_buf, (uint32_t)rows, c, (IirCarry*)d_state, st); });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
 // The checks of both windowed entry points, in the order they return: a null handle or buffer, nblocks == 0 or nblocks * nch
 // >= 2^31, and buffers that overlap without being the same (ERR_ARG); then a chunk's row offsets, which k_fir and k_med_short
 // compute in 32 bits (ERR_UNSUPPORTED: 2^24 channels and more).  Sets the geometry for the window K and whether the call is in place.
 static int window_call_checks(const rspt_hip_packer* p, const void* d_src, const void* d_dst, size_t nblocks, uint32_t K, uint32_t threads,
-                              uint32_t run, WinGeom* f, bool* in_place) {
+                              uint32_t run, WinGeom* f, bool* in_place, bool one_run = false) {
     if (!p || !d_src || !d_dst || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
     const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
     *in_place = s0 == d0;
     if (!*in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
-    *f = win_geom(p, nblocks, K, threads, run);
+    if (one_run && (uint64_t)nblocks * p->g.ns >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    *f = win_geom(p, nblocks, K, threads, run, one_run ? (uint32_t)(nblocks * p->g.ns) : 0u);
     if ((uint64_t)f->subs * run * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;
     return RSPT_HIP_OK;
 }
@@ -1880,7 +1945,7 @@ static int window_call_checks(const rspt_hip_packer* p, const void* d_src, const
 // The halo of an in-place call with more than one span per block: the K - 1 rows in front of every span but the first,
 // nblocks (nsplit - 1) pieces of (K - 1) rows.
 static uint64_t halo_pieces(const WinGeom& f, size_t nblocks, bool in_place) {
-    return in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;
+    return in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;  // (a carried-state call: one block)
 }
 
 static hipError_t launch_halo(const WinGeom& f, const void* d_src, uint8_t* halo, uint64_t pieces, hipStream_t st) {
@@ -1902,22 +1967,43 @@ static int finish_window_call(rspt_hip_packer* p, LastCall& last, hipError_t e, 
     return RSPT_HIP_OK;
 }
 
-int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
-                                     void* stream) {
+// Stage the head of a carried-state call and write the new state (k_fir_carry, fir.hip); the state: [u64 started][K - 1 rows].
+static hipError_t launch_fir_carry(const WinGeom& f, const void* d_src, uint8_t* head, void* d_state, hipStream_t st) {
+    uint64_t* started = (uint64_t*)d_state;
+    uint8_t* rows = (uint8_t*)d_state + 8;
+    const uint64_t n = (uint64_t)(f.K - 1) * f.stride;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
+    if (n) hipLaunchKernelGGL(k_fir_carry<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
+    hipLaunchKernelGGL(k_fir_carry<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
+    return hipGetLastError();
+}
+
+// Both FIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+static int fir_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size, void* d_state,
+                    void* stream) {
     if (!kernel || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
     WinGeom f;
     bool in_place;
-    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, (uint32_t)kernel_size, kFirThreads, kFirR, &f, &in_place)) return rc;
+    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, (uint32_t)kernel_size, kFirThreads, kFirR, &f, &in_place, d_state != nullptr)) return rc;
+    if (d_state) nblocks = 1;  // (the geometry's one block of nblocks * ns rows)
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     FirStage& fs = p->fir;
     const uint64_t pieces = halo_pieces(f, nblocks, in_place);
     const uint64_t halo_bytes = pieces * (uint64_t)(kernel_size - 1) * f.stride;
-    if (halo_bytes > fs.halo_cap) {
-        fs.wait_all();  // (no earlier call may still read the buffer being replaced)
-        fs.halo_cap = 0;
-        if (hipMalloc(fs.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        fs.halo_cap = halo_bytes;
+    const uint64_t head_bytes = d_state ? (uint64_t)(kernel_size - 1) * f.stride : 0;
+    if (halo_bytes > fs.halo_cap || head_bytes > fs.head_cap) {
+        fs.wait_all();  // (no earlier call may still read a buffer being replaced)
+        if (halo_bytes > fs.halo_cap) {
+            fs.halo_cap = 0;
+            if (hipMalloc(fs.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            fs.halo_cap = halo_bytes;
+        }
+        if (head_bytes > fs.head_cap) {
+            fs.head_cap = 0;
+            if (hipMalloc(fs.head.out(), head_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            fs.head_cap = head_bytes;
+        }
     }
     // the coefficients: the host waits only when kSlots calls are still ahead on the device
     FirStage::CoefSlot& cs = fs.slot[fs.next];
@@ -1933,17 +2019,36 @@ int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void
     fs.next = (fs.next + 1) % FirStage::kSlots;
     // (from here on every path ends in finish_window_call, which records `last`: the copy below reads the page-locked slot)
     hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_state) e = launch_fir_carry(f, d_src, fs.head, d_state, st);
     if (e == hipSuccess && pieces) e = launch_halo(f, d_src, fs.halo, pieces, st);
     if (e == hipSuccess) {
         const uint32_t bps = p->g.bps;
         const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
         const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;  // (block_bytes is a multiple of bps)
         by_bps(bps, [&](auto b) {
-            launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, cs.dev, aligned, st);
+            launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, cs.dev, aligned, st,
+                                           head_bytes ? (const uint8_t*)fs.head : nullptr);
         });
         e = hipGetLastError();
     }
     return finish_window_call(p, cs.last, e, st);
+}
+
+int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                     void* stream) {
+    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, nullptr, stream);
+}
+
+int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) {
+    if (!p || !bytes || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+    *bytes = 8 + (((size_t)(kernel_size - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                      void* d_state, void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
 }
 
 int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream) {

@@ -1,0 +1,127 @@
+"""The IIR and FIR pre-filters with a carried state: their test inputs and a numpy restatement.
+
+A case is ONE recording of nblocks * ns rows cut into nblocks blocks of the handle's shape (bps, nch, ns).  The reference
+user's loop is one i_filter per channel, init_history_values once on the channel's first sample, then filter_opt on every
+sample of every block in order -- so the answer does not depend on where the recording is cut, and the restatement is the
+stateless one over the concatenation: fir_cases.fir_i32 on all rows, iir_cases._chain without re-initialisation.
+
+The cases feed tests/golden/make_stream_filter_record.py, which records the compiled reference's answers in
+tests/golden/stream_filter_record.json.  The tests take the coefficients from that record (stored exactly).
+"""
+import numpy as np
+
+import cases
+import fir_cases as fc
+import iir_cases as ic
+from rspt_amd import synth
+
+
+def _take(data, bps, nch, rows):
+    d = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).reshape(-1)[: bps * nch * rows])
+    assert d.size == bps * nch * rows
+    return d
+
+
+def stream_cases():
+    """kind ('iir' | 'fir'), name, bps, nch, ns, nblocks, data (native bytes of nblocks * ns rows), and n, d, init (iir) or
+    kernel (fir)"""
+    ecg = np.frombuffer(synth.ecg_12ch_i32(), dtype=np.uint8)  # 34199 rows -> 16 blocks of 12 x 2048
+    ds = np.frombuffer(synth.data_stream_3ch_i24(), dtype=np.uint8)  # 20000 rows -> 20 blocks of 3 x 1000
+    C = []
+
+    def iir(name, bps, nch, ns, nblocks, coef, init, data):
+        C.append(dict(kind="iir", name=name, bps=bps, nch=nch, ns=ns, nblocks=nblocks, n=[float(v) for v in coef[0]],
+                      d=[float(v) for v in coef[1]], init=init, data=_take(data, bps, nch, ns * nblocks)))
+
+    def fir(name, bps, nch, ns, nblocks, kernel, data):
+        C.append(dict(kind="fir", name=name, bps=bps, nch=nch, ns=ns, nblocks=nblocks,
+                      kernel=[float(v) for v in np.asarray(kernel, dtype=np.float64)], data=_take(data, bps, nch, ns * nblocks)))
+
+    # ---- IIR ----
+    iir("iir_ecg12x2048x16_i32_harness_bandpass", 4, 12, 2048, 16, cases.IIR_BANDPASS, 2000, ecg)  # rspt_test.cpp:124-125
+    iir("iir_ds3x1000x20_i24_highpass", 3, 3, 1000, 20, cases.IIR_HIGHPASS, 2000, ds)
+    # every order with and without a history, every sample width, ns below 64 / not a multiple of 64 / one chunk, nch = 1
+    shapes = {2: (1, 1, 40, 8), 3: (2, 5, 100, 6), 4: (3, 3, 64, 5), 5: (4, 7, 232, 4)}
+    for nc in (2, 3, 4, 5):
+        for init in (0, 2000):
+            bps, nch, ns, nb = shapes[nc]
+            amp = 1 << (8 * bps - 2)
+            iir("iir_nc%d_init%d_i%d_%dx%dx%d" % (nc, init, 8 * bps, nch, ns, nb), bps, nch, ns, nb, ic.STABLE[nc], init,
+                cases._rand_native(nch, ns * nb, bps, 3000 + 10 * nc + (init > 0), amp, walk=(nc & 1) == 1))
+    iir("iir_nc5_init0_i32_1x50x9_below_a_chunk", 4, 1, 50, 9, ic.STABLE[5], 0, cases._rand_native(1, 450, 4, 3100, 1 << 28))
+    iir("iir_nc3_init1_i16_65x30x7", 2, 65, 30, 7, ic.STABLE[3], 1, cases._rand_native(65, 210, 2, 3101, 30000))
+    # an unstable filter: channel 1 is fed from row 700 on, passes 2^31 within its block, becomes +-inf and then NaN near row
+    # 2450 (block 4), and every later block is NaN from its first sample -- the NaN lives in the carried rings
+    iir("iir_unstable3x500x7_i32_nan_carried", 4, 3, 500, 7, ic.unstable(1.5), 3, ic.onset_block(3, 3500, 4, 3102, [None, 700, 0], 1000))
+    iir("iir_unstable2x40x6_i8_nan_carried_small_calls", 1, 2, 40, 6, ic.unstable(1e3), 0, ic.onset_block(2, 240, 1, 3103, [None, 30], 100))
+
+    # ---- FIR ----
+    fir("fir_ecg12x2048x16_i32_bandpass101", 4, 12, 2048, 16, fc.windowed_sinc_bandpass(101, 0.0005, 0.08), ecg)
+    fir("fir_ecg12x2048x16_i32_lowpass1001", 4, 12, 2048, 16, fc.windowed_sinc_lowpass(1001, 0.02), ecg)
+    fir("fir_ds3x1000x20_i24_k1_gain", 3, 3, 1000, 20, [0.75], ds)
+    fir("fir_rand7x143x7_i8_k2", 1, 7, 143, 7, [0.5, 0.5], cases._rand_native(7, 1001, 1, 3200, 100))
+    fir("fir_synth5x300x10_i16_lowpass31", 2, 5, 300, 10, fc.windowed_sinc_lowpass(31, 0.1), synth.synth_native(5, 3000, 3, bps=2, ecg=True).numpy())
+    fir("fir_rand1x500x10_i32_bandpass101", 4, 1, 500, 10, fc.windowed_sinc_bandpass(101, 0.01, 0.2),
+        cases._rand_native(1, 5000, 4, 3201, 1 << 24, walk=True))
+    fir("fir_rand3x700x4_i24_k4097", 3, 3, 700, 4, fc._rand_kernel(4097, 3202, 9), cases._rand_native(3, 2800, 3, 3203, 1 << 22))  # K - 1 > ns
+    fir("fir_rand2x40x5_i32_k65536", 4, 2, 40, 5, fc._rand_kernel(65536, 3204, 11), cases._rand_native(2, 200, 4, 3205, 1 << 22))  # K - 1 > any call
+    # a huge coefficient overflows a product to +-inf; inf + (-inf) is NaN: both truncate to INT32_MIN (fir_cases)
+    fir("fir_rand4x250x8_i32_inf_nan", 4, 4, 250, 8, [1e308, -1e308, 0.5, 1e308], cases._rand_native(4, 2000, 4, 3206, 1 << 30))
+    fir("fir_rand5x37x11_i16_k64_below_a_chunk", 2, 5, 37, 11, fc._rand_kernel(64, 3207, 5), cases._rand_native(5, 407, 2, 3208, 1 << 12))
+    return C
+
+
+# ---- the restatement ----
+
+def iir_stream_double(native, bps, nch, rows, n, d, init):
+    """[rows][nch] float64: one filter per channel over the whole recording, before the truncation"""
+    x = fc.native_to_i32(native, bps, nch, rows).astype(np.float64)
+    n = [float(v) for v in n]
+    d = [float(v) for v in d]
+    nc = len(n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        out, _, _ = ic._chain(list(x), [np.zeros(nch)] * nc, [np.zeros(nch)] * nc, n, d, init)
+    return np.array(out).reshape(rows, nch)
+
+
+def filtered(c, kernel=None, n=None, d=None):
+    """the filtered recording in the native sample width (bytes), as the stream entries leave it; coefficients from the case
+    unless given (the tests pass the record's exact ones)"""
+    rows = c["ns"] * c["nblocks"]
+    if c["kind"] == "fir":
+        y = fc.fir_i32(fc.native_to_i32(c["data"], c["bps"], c["nch"], rows), c["kernel"] if kernel is None else kernel)
+    else:
+        y = iir_stream_double(c["data"], c["bps"], c["nch"], rows, c["n"] if n is None else n, c["d"] if d is None else d, c["init"])
+    return fc.i32_to_native(fc.trunc_i32(y), c["bps"])
+
+
+def coef_to_record(c):
+    if c["kind"] == "fir":
+        return {"kernel": fc.kernel_to_record(c["kernel"])}
+    return {"n": ic.to_bits(c["n"]), "d": ic.to_bits(c["d"]), "init": c["init"]}
+
+
+def with_record_coefficients(c, r):
+    """the case with the record's coefficients (exact) in place of the ones computed here"""
+    if c["kind"] == "fir":
+        return dict(c, kernel=fc.kernel_from_record(r["kernel"]), rec=r)
+    return dict(c, n=ic.from_bits(r["n"]), d=ic.from_bits(r["d"]), rec=r)
+
+
+def splits(nblocks):
+    """the three drivings of a recording: all blocks in one call, one block per call, an uneven split (1, 5, 2, 8, 1, ...)"""
+    uneven, left, i = [], nblocks, 0
+    while left:
+        k = min((1, 5, 2, 8)[i % 4], left)
+        uneven.append(k)
+        left -= k
+        i += 1
+    return {"one_call": [nblocks], "per_block": [1] * nblocks, "uneven": uneven}
+
+
+# the equivalence with the stateless stages at full size: 64 ch x 65536 int32 as 16 blocks of 4096
+BIG = dict(bps=4, nch=64, ns=4096, nblocks=16, block=7)
+
+
+def big_data():
+    return synth.synth_native(BIG["nch"], BIG["ns"] * BIG["nblocks"], BIG["block"], bps=BIG["bps"], ecg=True).numpy()
