@@ -377,6 +377,35 @@ int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, voi
  * stream-ordered.  Device memory the stage needs belongs to the handle. */
 int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream);
 
+/* ---- the rolling-window median with a carried state: one object per channel over a recording that arrives in blocks ----
+ * The nblocks blocks of a call are consecutive pieces of ONE recording and the next call on the same state continues where this
+ * one ended.  Per channel there is one reference object, rolling_window_median<double>(window): insert((double)x) on every
+ * sample of every block of every call, (int32_t) of each return value stored as rspt_hip_median_filter_batch_dev stores it.
+ * With X = the channel's whole recording so far, T a sample's index in it and W = window,
+ *     lo = max(0, T - W + 1),  m = T - lo + 1,  s = sorted(X[lo .. T])
+ *     y[T] = m odd ? s[m / 2] : (int32_t)(((int64_t)s[m / 2 - 1] + s[m / 2]) / 2)      (C division: toward zero)
+ * W is NOT clamped to ns: it may exceed ns and it may exceed a whole call, and the expanding phase happens once per recording.
+ * Bit-identical with the reference's object driven block by block, however the recording is cut into blocks and calls.  In
+ * place and out of place as rspt_hip_median_filter_batch_dev (out of place d_src is only read).
+ *   d_state         a caller-owned device buffer of rspt_hip_median_state_bytes(p, window) bytes, 8-byte aligned: uint64 fill,
+ *                   then W - 1 rows, oldest first, each row nch samples of bps bytes as in a block, padded to a multiple of 8
+ *                   bytes.  fill = min(rows of the recording so far, W - 1) is the number of valid rows; they are the LAST fill
+ *                   rows of the buffer, and every row in front of them stays zero.  All-zero bytes are a fresh object for every
+ *                   channel.  The new state is the tail of (old state ++ the call's rows), so its bytes are a function of the
+ *                   recording and W alone, not of how the recording was cut.  A state belongs to the handle's (bps, nch) and to
+ *                   the window that sized it.  Two states may be used in turn on one handle.  window = 1 copies the blocks;
+ *                   its state is the 8-byte header and stays zero.
+ * RSPT_HIP_ERR_ARG for everything rspt_hip_median_filter_batch_dev refuses (window 0, bad buffers, nblocks * nch >= 2^31), a
+ * NULL or misaligned d_state and a NULL bytes; RSPT_HIP_ERR_UNSUPPORTED for a call of 2^31 - 2^17 rows (nblocks * ns) or more
+ * (split the call: with a state that is exact), and, from both entries, for a window above 32 with W - 1 > 2^17.  Windows up to
+ * 32 have no other limit; windows above 32 take any ns and any call length below the row limit (the stateless entry's
+ * ns <= 2^18 does not apply: a call is cut into segments of at most 2^18 rows that overlap by W - 1).
+ * Asynchronous on `stream`; calls on one handle or one state are stream-ordered.  The stage allocates nothing per state: the
+ * staged copy of the old state belongs to the handle. */
+int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes); /* 8 + ((W - 1) * nch * bps rounded up to 8) */
+int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state,
+                                      void* stream);
+
 /* ---- the reference's Butterworth designer (host only: no GPU, no handle) -------------------------------------------
  * create_filter_iir(num, den, butterworth, type, order, sampling_rate, cutoff_low, cutoff_high) of
  * lib_rspt/lib_filter/iir_filter_design.cpp, bit-identical with the reference's x86-64 build (same libm calls, same order of

@@ -26,6 +26,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_decompress_batch_dev", "rspt_hip_decompress_packed_dev", "rspt_hip_pack_bound", "rspt_hip_pack_batch_dev", "rspt_hip_stream", "rspt_hip_synchronize", "rspt_hip_set_profiling", "rspt_hip_stage_count",
     "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_design_iir",
     "rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev",
+    "rspt_hip_median_state_bytes", "rspt_hip_median_filter_stream_dev",
     "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
     "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
@@ -124,6 +125,9 @@ def lib():
     L.rspt_hip_fir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p]
     L.rspt_hip_median_filter_batch_dev.restype = C.c_int
     L.rspt_hip_median_filter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.rspt_hip_median_state_bytes.restype, L.rspt_hip_median_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
+    L.rspt_hip_median_filter_stream_dev.restype = C.c_int
+    L.rspt_hip_median_filter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
     L.rspt_hip_design_iir.restype = C.c_int
     L.rspt_hip_design_iir.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _szp]
     L.rspt_hip_peak_state_bytes.restype, L.rspt_hip_peak_state_bytes.argtypes = C.c_int, [C.c_void_p, _szp]
@@ -440,11 +444,30 @@ class SignalPacker:
         self._check("rspt_hip_fir_prefilter_batch_dev", rc)
         return out
 
-    def median_filter_batch(self, d_src, window, d_dst=None, stream=None):
+    def median_state_bytes(self, window):
+        n = C.c_size_t()
+        self._check("rspt_hip_median_state_bytes", self._L.rspt_hip_median_state_bytes(self._h, int(window), C.byref(n)))
+        return n.value
+
+    def median_state(self, window, device=None):
+        """A zeroed state for median_filter_batch(state=...) with this window: a fresh object for every channel."""
+        import torch
+
+        return torch.zeros(self.median_state_bytes(window), dtype=torch.uint8, device=device if device is not None else "cuda")
+
+    def median_filter_batch(self, d_src, window, d_dst=None, stream=None, state=None):
         """The reference's rolling-window median (rolling_window_median<double>(window), one per channel; rspt_hip.h) on
         device-resident blocks: in place when d_dst is None, else into d_dst (same size, not overlapping d_src); asynchronous.
-        Returns the output."""
+        Returns the output.
+        state: None (a fresh object per channel of every block), or a median_state(window) tensor: the blocks are then
+        consecutive pieces of one recording, one object per channel running through them and on into the next call
+        (rspt_hip_median_filter_stream_dev); the window is then not clamped to ns."""
         nblocks, out, st = self._window_call_buffers(d_src, d_dst, stream)
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.median_state_bytes(window)
+            rc = self._L.rspt_hip_median_filter_stream_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, int(window), state.data_ptr(), st)
+            self._check("rspt_hip_median_filter_stream_dev", rc)
+            return out
         rc = self._L.rspt_hip_median_filter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, int(window), st)
         self._check("rspt_hip_median_filter_batch_dev", rc)
         return out

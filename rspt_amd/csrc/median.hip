@@ -29,6 +29,19 @@
 // owns, are copied into the handle's halo buffer by k_fir_halo before k_med_short starts.  Generic: only k_med_tile_sort reads
 // the samples, and it runs before k_med_walk, which writes them, on the same stream; no kernel reads what another writes in
 // the same launch.
+//
+// Carried state (rspt_hip_median_filter_stream_dev): the blocks of a call lie back to back, so the call is ONE run of
+// N = nblocks * ns rows, and the reference's object between two calls is its window: the last min(rows so far, W - 1) inputs of
+// every channel.  The state is [u64 fill][W - 1 rows], the valid rows last and zeros in front of them.  k_med_carry copies it
+// into the handle's `head` buffer and then writes the new state, the tail of (old state ++ call) and min(fill + N, W - 1), from
+// the staged head and d_src -- both in front of every kernel that stores to d_dst (stream order).  The kernels lay the call out
+// as if all W - 1 head rows were there and skip the first W - 1 - fill of them: a run of k_med_short starts at row
+// max(-fill, t0 - (W - 1)); the generic path never sets their bits and never counts them.
+//   Generic: (head ++ call) is cut per channel into segments of S = W - 1 + L rows (S <= kMedMaxRanks): the W - 1 rows in front
+// of L new ones.  A segment is ranked on its own with segment-local indices (shorter last segments are padded with keys above
+// every sample's) and walked for its own new rows only.  The (segment, channel) items are worked through in pieces from the
+// LAST segment to the first: a walk writes only its segment's new rows, which no segment sorted later reads, so in place needs
+// no saved overlap rows.
 #include "common.hpp"
 
 namespace rspt {
@@ -39,6 +52,15 @@ constexpr uint32_t kMedRun = 32;         // consecutive outputs per lane (k_med_
 constexpr uint32_t kMedTile = 4096;      // keys of one LDS sort (k_med_tile_sort): 32 KiB
 constexpr uint32_t kMedSpan = 1024;      // outputs of one walk (k_med_walk)
 constexpr uint32_t kMedMaxRanks = 1u << 18;  // the longest channel of the generic path: its bitmaps take 4 (ns / 32 + ns / 1024) bytes of LDS
+constexpr uint32_t kMedMaxCarry = 1u << 17;  // the longest carried window (W - 1) of the generic path: half a segment stays new
+
+// The segments of a carried-state call of the generic path (head == null: the stateless call, one pair = one channel of a block).
+struct MedSeg {
+    const uint8_t* head;  // [u64 fill][W - 1 rows]: the staged old state
+    uint32_t L;           // new rows of a segment (the last one may hold fewer)
+    uint32_t nseg;        // segments per channel: ceil(N / L)
+    uint32_t N;           // rows of the call
+};
 
 // ---- short windows ----
 
@@ -75,8 +97,10 @@ __device__ __forceinline__ int32_t med_step(int32_t (&s)[N], uint32_t m, uint32_
 
 // One span of one channel group of one block per unit.  `halo` is null out of place; in place it holds, for span w >= 1 of
 // block b, the W - 1 rows in front of the span at halo + ((b * (nsplit - 1) + w - 1) * (W - 1)) * stride (k_fir_halo's layout).
-template <uint32_t N, int BPS, bool ALIGNED>
-__global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, uint8_t* dst, const uint8_t* halo, WinGeom g) {
+// HEAD: a carried-state call (one block); `head` is the staged state [u64 fill][W - 1 rows], and span 0's runs start up to `fill`
+// rows in front of row 0 and read those rows there.
+template <uint32_t N, int BPS, bool ALIGNED, bool HEAD = false>
+__global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, uint8_t* dst, const uint8_t* halo, WinGeom g, const uint8_t* head) {
     constexpr uint32_t R = kMedRun, G = 8;
     __shared__ int32_t stage[R * kMedThreads];  // [r][tid]: the chunk's outputs until every read of the chunk is done
     const uint32_t tid = threadIdx.x;
@@ -84,6 +108,7 @@ __global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, u
     const uint32_t W = g.K;
     const uint32_t C = g.subs * R;
     const uint32_t stride = g.stride;
+    const int32_t smin = HEAD ? -(int32_t)*reinterpret_cast<const uint64_t*>(head) : 0;  // the first row of the recording a window may hold
     for (uint64_t u = blockIdx.x; u < g.units; u += gridDim.x) {
         const uint32_t w = (uint32_t)(u % g.nsplit);
         const uint64_t rest = u / g.nsplit;
@@ -95,21 +120,22 @@ __global__ __launch_bounds__(kMedThreads) void k_med_short(const uint8_t* src, u
         const uint64_t blk = b * g.block_bytes;
         const int32_t lo = (int32_t)(w * g.span);
         const int32_t hi = min((int32_t)g.ns, lo + (int32_t)g.span);
-        const int32_t lim = (halo && w) ? lo : 0;  // rows below lim come from the halo copy
+        const int32_t lim = (halo && w) ? lo : 0;  // rows below lim come from a staged copy: the halo, or (rows below 0) the head
         const uintptr_t srow0 = reinterpret_cast<uintptr_t>(src + blk) + chc * BPS;
         const uintptr_t hrow0 = lim ? reinterpret_cast<uintptr_t>(halo) + ((b * (g.nsplit - 1) + w - 1) * (uint64_t)(W - 1)) * stride + chc * BPS -
                                           (uint64_t)(lo - (int32_t)(W - 1)) * stride
-                                    : srow0;
+                                : HEAD ? reinterpret_cast<uintptr_t>(head) + 8 + (uint64_t)(W - 1) * stride + chc * BPS
+                                       : srow0;
         auto ld = [&](int32_t s) {
             const uintptr_t base = s < lim ? hrow0 : srow0;
-            return sample_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(uint32_t)s * stride), ALIGNED);
+            return sample_load<BPS>(reinterpret_cast<const uint8_t*>(base + (uint64_t)(int64_t)s * stride), ALIGNED);
         };
         const uint32_t nq = ((uint32_t)(hi - lo) + C - 1) / C;
         for (uint32_t q = nq; q-- > 0;) {
             const int32_t a = lo + (int32_t)(q * C);
             const int32_t t0 = a + (int32_t)(sub * R);
             const int32_t e = live ? min(t0 + (int32_t)R, hi) : t0;          // outputs [t0, e): none for dead lanes and runs past the span
-            const int32_t s0 = e > t0 ? max(0, t0 - (int32_t)(W - 1)) : e;    // the run's window starts filling here (no rows read if e <= t0)
+            const int32_t s0 = e > t0 ? max(smin, t0 - (int32_t)(W - 1)) : e;  // the run's window starts filling here (no rows read if e <= t0)
             int32_t s[N];
 #pragma unroll
             for (uint32_t i = 0; i < N; ++i) s[i] = i < (N - 1) / 2 ? INT32_MIN : INT32_MAX;  // m = 0: Lo(0) = c
@@ -166,18 +192,40 @@ __device__ __forceinline__ int32_t med_key_value(uint64_t k) { return (int32_t)(
 
 // Pair p = (block, channel) of the piece [pair0, pair0 + npairs): keys[p][0 .. ns) sorted in runs of kMedTile.  With
 // `rank` (ns <= kMedTile: the sort is complete), also rank[p][t] = position of sample t.
-template <int BPS, bool ALIGNED>
-__global__ __launch_bounds__(kMedThreads) void k_med_tile_sort(const uint8_t* src, uint64_t* keys, uint32_t* rank, WinGeom g, uint64_t pair0) {
+// STREAM: pair = (segment counted from the last, channel), g.ns = the segment capacity S; index t of the segment is row
+// j L - (W - 1) + t of the call, a row of the staged head where that is negative, and a pad (above every sample, unique) from the
+// segment's own length on.
+template <int BPS, bool ALIGNED, bool STREAM = false>
+__global__ __launch_bounds__(kMedThreads) void k_med_tile_sort(const uint8_t* src, uint64_t* keys, uint32_t* rank, WinGeom g, uint64_t pair0, MedSeg sg) {
     __shared__ uint64_t sk[kMedTile];
     const uint32_t tiles = (g.ns + kMedTile - 1) / kMedTile;
     const uint64_t p = blockIdx.x / tiles;
     const uint32_t t0 = (blockIdx.x % tiles) * kMedTile;
     const uint64_t pair = pair0 + p;
     const uint32_t ch = (uint32_t)(pair % g.nch);
-    const uint8_t* base = src + (pair / g.nch) * g.block_bytes + ch * BPS;
-    for (uint32_t i = threadIdx.x; i < kMedTile; i += kMedThreads) {
-        const uint32_t t = t0 + i;
-        sk[i] = t < g.ns ? med_key(sample_load<BPS>(base + (uint64_t)t * g.stride, ALIGNED), t) : ~0ull;  // (padding sorts last)
+    if (STREAM) {
+        const uint32_t j = sg.nseg - 1u - (uint32_t)(pair / g.nch);
+        const uint32_t n = g.K - 1u + min(sg.L, sg.N - j * sg.L);
+        const int64_t first = (int64_t)j * sg.L - (int64_t)(g.K - 1u);  // the call's row of index 0
+        const uint8_t* hrow0 = sg.head + 8 + (uint64_t)(g.K - 1u) * g.stride + ch * BPS;  // where row 0 would be in the head
+        for (uint32_t i = threadIdx.x; i < kMedTile; i += kMedThreads) {
+            const uint32_t t = t0 + i;
+            uint64_t k = ~0ull;
+            if (t < n) {
+                const int64_t r = first + (int64_t)t;
+                const uint8_t* at = r < 0 ? hrow0 - (uint64_t)(-r) * g.stride : src + (uint64_t)r * g.stride + ch * BPS;
+                k = med_key(sample_load<BPS>(at, ALIGNED), t);
+            } else if (t < g.ns) {
+                k = 0xFFFFFFFF00000000ull | t;
+            }
+            sk[i] = k;
+        }
+    } else {
+        const uint8_t* base = src + (pair / g.nch) * g.block_bytes + ch * BPS;
+        for (uint32_t i = threadIdx.x; i < kMedTile; i += kMedThreads) {
+            const uint32_t t = t0 + i;
+            sk[i] = t < g.ns ? med_key(sample_load<BPS>(base + (uint64_t)t * g.stride, ALIGNED), t) : ~0ull;  // (padding sorts last)
+        }
     }
     __syncthreads();
     for (uint32_t k = 2; k <= kMedTile; k <<= 1) {
@@ -285,27 +333,39 @@ struct MedBits {
 
 // One wave per (pair of the piece, span of kMedSpan outputs).  keys: the piece's sorted keys, rank: their inverse.  The state
 // (p = rank of the lower median, below = window members with a smaller rank) is computed alike by every lane.
-template <int BPS, bool ALIGNED>
+// STREAM: pair and g.ns as in k_med_tile_sort; the spans cover the segment's new rows only (indices W - 1 .. n - 1), and `v0` is
+// the first index that holds a row of the recording: W - 1 - fill in the first segment, 0 in every other.
+template <int BPS, bool ALIGNED, bool STREAM = false>
 __global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ rank, uint8_t* dst, WinGeom g,
-                                                 uint64_t pair0) {
+                                                 uint64_t pair0, MedSeg sg) {
     extern __shared__ uint32_t med_lds[];
     const uint32_t lane = threadIdx.x;
     const bool writer = lane == 0;
     const uint32_t ns = g.ns, W = g.K;
-    const uint32_t spans = (ns + kMedSpan - 1) / kMedSpan;
+    const uint32_t spans = ((STREAM ? sg.L : ns) + kMedSpan - 1) / kMedSpan;
     const uint64_t p = blockIdx.x / spans;
-    const uint32_t lo = (blockIdx.x % spans) * kMedSpan;
-    const uint32_t hi = min(ns, lo + kMedSpan);
+    const uint64_t pair = pair0 + p;
+    uint32_t lo = (blockIdx.x % spans) * kMedSpan, n = ns, v0 = 0;
+    uintptr_t out0;  // address of index 0 of the pair's channel in dst (STREAM: only indices from W - 1 on are stored)
+    if (STREAM) {
+        const uint32_t j = sg.nseg - 1u - (uint32_t)(pair / g.nch);
+        n = W - 1u + min(sg.L, sg.N - j * sg.L);
+        lo += W - 1u;
+        if (lo >= n) return;  // (a span past a short last segment)
+        if (j == 0) v0 = W - 1u - (uint32_t)*reinterpret_cast<const uint64_t*>(sg.head);
+        out0 = reinterpret_cast<uintptr_t>(dst) + (uint32_t)(pair % g.nch) * BPS + (uint64_t)((int64_t)j * sg.L - (int64_t)(W - 1u)) * g.stride;
+    } else {
+        out0 = reinterpret_cast<uintptr_t>(dst) + (pair / g.nch) * g.block_bytes + (uint32_t)(pair % g.nch) * BPS;
+    }
+    const uint32_t hi = min(n, lo + kMedSpan);
     const uint32_t n0 = (ns + 31) / 32;
     MedBits bm{med_lds, med_lds + n0, (n0 + 31) / 32};
     for (uint32_t i = lane; i < n0 + bm.n1; i += 64) med_lds[i] = 0;
     __syncthreads();
     const uint32_t* rk = rank + p * ns;
     const uint64_t* kp = keys + p * ns;
-    const uint64_t pair = pair0 + p;
-    uint8_t* out = dst + (pair / g.nch) * g.block_bytes + (uint32_t)(pair % g.nch) * BPS;
     // the window of output lo - 1: samples [s0, lo)
-    const uint32_t s0 = lo >= W ? lo - W : 0;
+    const uint32_t s0 = lo >= W + v0 ? lo - W : v0;
     for (uint32_t t = s0 + lane; t < lo; t += 64) {
         const uint32_t r = rk[t];
         atomicOr(&bm.b0[r >> 5], 1u << (r & 31));
@@ -347,7 +407,7 @@ __global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ ke
         const uint32_t n = min(64u, hi - base);
         const uint32_t t = base + lane;
         const uint32_t rn = t < hi ? rk[t] : 0;
-        const uint32_t ro = (t < hi && t >= W) ? rk[t - W] : 0;
+        const uint32_t ro = (t < hi && t >= W + v0) ? rk[t - W] : 0;
         uint32_t myp = 0, myq = 0;
         for (uint32_t j = 0; j < n; ++j) {
             const uint32_t tj = base + j;
@@ -360,7 +420,7 @@ __global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ ke
                 ++below;
             }
             ++m;
-            if (tj >= W) {  // the window is full: sample tj - W leaves
+            if (tj >= W + v0) {  // the window is full: sample tj - W leaves
                 const uint32_t o = __shfl(ro, (int)j, 64);
                 --m;
                 bm.clear(o, writer);
@@ -393,8 +453,33 @@ __global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ ke
         }
         if (lane < n) {
             const int64_t sum = (int64_t)med_key_value(kp[myp]) + (int64_t)med_key_value(kp[myq]);
-            sample_store<BPS>(out + (uint64_t)t * g.stride, (int32_t)(sum / 2), ALIGNED);
+            sample_store<BPS>(reinterpret_cast<uint8_t*>(out0 + (uint64_t)t * g.stride), (int32_t)(sum / 2), ALIGNED);
         }
+    }
+}
+
+// ---- carried state ----
+
+// The two movers of a carried-state call, in units of T (bytes, or 32-bit words where everything is a multiple of 4): n = the
+// state's W - 1 rows, call = the call's N rows.  `state` and `head` are [u64 fill][rows].
+//   SAVE = false   head <- state
+//   SAVE = true    state rows <- the last W - 1 rows of (head rows ++ call): the call's last W - 1 rows, or, where the call is
+//                  shorter than that, the head's rows from N on and then the whole call (the valid rows stay last, the zeros in
+//                  front); fill <- min(fill + N, W - 1)
+// SAVE = true runs behind SAVE = false and in front of every kernel that writes d_dst (stream order): the state is never read
+// while it is written, and d_src is still the input.
+template <bool SAVE, class T>
+__global__ __launch_bounds__(256) void k_med_carry(const T* __restrict__ src, uint8_t* head, uint8_t* state, uint64_t n, uint64_t call, uint64_t wm1,
+                                                   uint64_t N) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * 256u + threadIdx.x, step = (uint64_t)gridDim.x * 256u;
+    T* hrows = reinterpret_cast<T*>(head + 8);
+    T* srows = reinterpret_cast<T*>(state + 8);
+    if (!SAVE) {
+        for (uint64_t i = i0; i < n; i += step) hrows[i] = srows[i];
+        if (i0 == 0) *reinterpret_cast<uint64_t*>(head) = *reinterpret_cast<const uint64_t*>(state);
+    } else {
+        for (uint64_t i = i0; i < n; i += step) srows[i] = call >= n ? src[call - n + i] : i + call < n ? hrows[i + call] : src[i + call - n];
+        if (i0 == 0) *reinterpret_cast<uint64_t*>(state) = min(*reinterpret_cast<const uint64_t*>(head) + N, wm1);
     }
 }
 

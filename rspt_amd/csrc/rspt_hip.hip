@@ -276,9 +276,10 @@ struct FirStage {
 
 // rspt_hip_median_filter_batch_dev: the halo rows of an in-place short-window call, and the sort buffers of the generic path
 // (two key buffers and the ranks of one piece of the batch), all behind the stage's last call.
+// rspt_hip_median_filter_stream_dev adds `head`, the staged copy of a carried-state call's old state, under the same rule.
 struct MedianStage {
-    Dev<uint8_t> halo;
-    size_t halo_cap = 0;
+    Dev<uint8_t> halo, head;
+    size_t halo_cap = 0, head_cap = 0;
     Dev<uint64_t> keys_a, keys_b;
     Dev<uint32_t> rank;
     size_t key_cap = 0;  // samples of each of the three
@@ -644,17 +645,33 @@ static void launch_fir(const WinGeom& f, const uint8_t* src, uint8_t* dst, const
     else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f, head);
 }
 
-template <uint32_t N, int BPS>
-static void launch_med_short(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st) {
+template <uint32_t N, int BPS, bool HEAD>
+static void launch_med_short(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st, const uint8_t* head) {
     const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
-    if (aligned) hipLaunchKernelGGL((k_med_short<N, BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f);
-    else hipLaunchKernelGGL((k_med_short<N, BPS, false>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f);
+    if (aligned) hipLaunchKernelGGL((k_med_short<N, BPS, (BPS == 4 || BPS == 2), HEAD>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f, head);
+    else hipLaunchKernelGGL((k_med_short<N, BPS, false, HEAD>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f, head);
 }
 
-// The generic path on the pairs [pair0, pair0 + npairs) of the batch: sort (tile sort, merge passes), then walk.
-template <int BPS>
+// k_med_short by its register bucket: the smallest of 4, 8, 16, 32 that holds W.
+template <bool HEAD>
+static hipError_t launch_med_short_w(uint32_t bps, const WinGeom& f, const void* d_src, void* d_dst, const uint8_t* halo, bool aligned, hipStream_t st,
+                                     const uint8_t* head) {
+    const uint32_t W = f.K;
+    by_bps(bps, [&](auto bb) {
+        constexpr int B = decltype(bb)::value;
+        if (W <= 4) launch_med_short<4, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+        else if (W <= 8) launch_med_short<8, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+        else if (W <= 16) launch_med_short<16, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+        else launch_med_short<32, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+    });
+    return hipGetLastError();
+}
+
+// The generic path on the pairs [pair0, pair0 + npairs) of the batch: sort (tile sort, merge passes), then walk.  STREAM: a pair
+// is a (segment, channel) of a carried-state call and f.ns the segment capacity (median.hip).
+template <int BPS, bool STREAM = false>
 static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const uint8_t* src, uint8_t* dst, uint64_t pair0, uint64_t npairs,
-                                     bool aligned, hipStream_t st) {
+                                     bool aligned, hipStream_t st, const MedSeg& sg = MedSeg{}) {
     MedianStage& ms = p->med;
     const uint32_t ns = f.ns;
     const uint32_t tiles = (ns + kMedTile - 1) / kMedTile;
@@ -662,10 +679,10 @@ static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const
     uint64_t* b = ms.keys_b;
     uint32_t* rank = ms.rank;
     const bool one_tile = tiles == 1;
-    if (aligned) hipLaunchKernelGGL((k_med_tile_sort<BPS, (BPS == 4 || BPS == 2)>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a,
-                                    one_tile ? rank : nullptr, f, pair0);
-    else hipLaunchKernelGGL((k_med_tile_sort<BPS, false>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a, one_tile ? rank : nullptr, f,
-                            pair0);
+    if (aligned) hipLaunchKernelGGL((k_med_tile_sort<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src,
+                                    a, one_tile ? rank : nullptr, f, pair0, sg);
+    else hipLaunchKernelGGL((k_med_tile_sort<BPS, false, STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a,
+                            one_tile ? rank : nullptr, f, pair0, sg);
     hipError_t e = hipGetLastError();
     const uint64_t total = npairs * ns;
     for (uint32_t width = kMedTile; e == hipSuccess && width < ns; width *= 2) {
@@ -676,11 +693,12 @@ static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const
         std::swap(a, b);
     }
     if (e != hipSuccess) return e;
-    const uint32_t spans = (ns + kMedSpan - 1) / kMedSpan;
+    const uint32_t spans = ((STREAM ? sg.L : ns) + kMedSpan - 1) / kMedSpan;
     const uint32_t n0 = (ns + 31) / 32;
     const size_t lds = (size_t)(n0 + (n0 + 31) / 32) * sizeof(uint32_t);
-    if (aligned) hipLaunchKernelGGL((k_med_walk<BPS, (BPS == 4 || BPS == 2)>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0);
-    else hipLaunchKernelGGL((k_med_walk<BPS, false>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0);
+    if (aligned) hipLaunchKernelGGL((k_med_walk<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f,
+                                    pair0, sg);
+    else hipLaunchKernelGGL((k_med_walk<BPS, false, STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0, sg);
     return hipGetLastError();
 }
 
@@ -2051,6 +2069,33 @@ int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, voi
     return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
 }
 
+// The median stage's buffers for a call: each grows behind the stage's last call, and `last` has its event from here on.
+static int median_reserve(MedianStage& ms, uint64_t halo_bytes, uint64_t head_bytes, uint64_t key_samples) {
+    if (halo_bytes > ms.halo_cap || head_bytes > ms.head_cap || key_samples > ms.key_cap) {
+        ms.last.wait();  // (no earlier call may still use a buffer being replaced)
+        if (halo_bytes > ms.halo_cap) {
+            ms.halo_cap = 0;
+            if (hipMalloc(ms.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            ms.halo_cap = halo_bytes;
+        }
+        if (head_bytes > ms.head_cap) {
+            ms.head_cap = 0;
+            if (hipMalloc(ms.head.out(), head_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            ms.head_cap = head_bytes;
+        }
+        if (key_samples > ms.key_cap) {
+            ms.key_cap = 0;
+            ms.rank.reset();
+            ms.keys_b.reset();
+            if (hipMalloc(ms.keys_a.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            if (hipMalloc(ms.keys_b.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            if (hipMalloc(ms.rank.out(), key_samples * sizeof(uint32_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            ms.key_cap = key_samples;
+        }
+    }
+    return ms.last.make_event() ? RSPT_HIP_OK : RSPT_HIP_ERR_ALLOC;
+}
+
 int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream) {
     if (!p || window == 0) return RSPT_HIP_ERR_ARG;
     const Geom& g = p->g;
@@ -2076,44 +2121,107 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
     const uint64_t pieces = is_short ? halo_pieces(f, nblocks, in_place) : 0;
     const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
     const uint64_t piece_pairs = is_short ? 0 : std::min<uint64_t>(pairs, std::max<uint64_t>(1, (1ull << 25) / g.ns));
-    const uint64_t key_samples = piece_pairs * g.ns;
-    if (halo_bytes > ms.halo_cap || key_samples > ms.key_cap) {
-        ms.last.wait();  // (no earlier call may still use a buffer being replaced)
-        if (halo_bytes > ms.halo_cap) {
-            ms.halo_cap = 0;
-            if (hipMalloc(ms.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            ms.halo_cap = halo_bytes;
-        }
-        if (key_samples > ms.key_cap) {
-            ms.key_cap = 0;
-            ms.rank.reset();
-            ms.keys_b.reset();
-            if (hipMalloc(ms.keys_a.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            if (hipMalloc(ms.keys_b.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            if (hipMalloc(ms.rank.out(), key_samples * sizeof(uint32_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            ms.key_cap = key_samples;
-        }
-    }
-    if (!ms.last.make_event()) return RSPT_HIP_ERR_ALLOC;
+    if (int rc = median_reserve(ms, halo_bytes, 0, piece_pairs * g.ns)) return rc;
     hipError_t e = hipSuccess;
     if (is_short) {
         if (pieces) e = launch_halo(f, d_src, ms.halo, pieces, st);
-        if (e == hipSuccess) {
-            const uint8_t* halo = pieces ? (const uint8_t*)ms.halo : nullptr;
-            by_bps(bps, [&](auto bb) {
-                constexpr int B = decltype(bb)::value;
-                if (W <= 4) launch_med_short<4, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
-                else if (W <= 8) launch_med_short<8, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
-                else if (W <= 16) launch_med_short<16, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
-                else launch_med_short<32, B>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st);
-            });
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch_med_short_w<false>(bps, f, d_src, d_dst, pieces ? (const uint8_t*)ms.halo : nullptr, aligned, st, nullptr);
     } else {
         for (uint64_t pair0 = 0; e == hipSuccess && pair0 < pairs; pair0 += piece_pairs) {
             const uint64_t np = std::min(piece_pairs, pairs - pair0);
             e = by_bps(bps, [&](auto bb) {
                 return launch_med_generic<decltype(bb)::value>(p, f, (const uint8_t*)d_src, (uint8_t*)d_dst, pair0, np, aligned, st);
+            });
+        }
+    }
+    return finish_window_call(p, ms.last, e, st);
+}
+
+int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) {
+    if (!p || !bytes || window == 0) return RSPT_HIP_ERR_ARG;
+    if (window > kMedShortMax && window - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;
+    *bytes = 8 + (((size_t)(window - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
+    return RSPT_HIP_OK;
+}
+
+// Stage the old state in the handle's head buffer and write the new one (k_med_carry, median.hip): in words where every
+// address and length is a multiple of 4.
+static hipError_t launch_med_carry(const WinGeom& f, const void* d_src, uint8_t* head, void* d_state, uint64_t rows, hipStream_t st) {
+    uint64_t n = (uint64_t)(f.K - 1) * f.stride, call = rows * f.stride;
+    const bool words = reinterpret_cast<uintptr_t>(d_src) % 4 == 0 && f.stride % 4 == 0;
+    if (words) n /= 4, call /= 4;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
+    uint8_t* state = (uint8_t*)d_state;
+    if (words) {
+        hipLaunchKernelGGL((k_med_carry<false, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<true, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
+    } else {
+        hipLaunchKernelGGL((k_med_carry<false, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<true, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
+    }
+    return hipGetLastError();
+}
+
+// The segment capacity S = W - 1 + L of a carried-state call of the generic path: 8 (W - 1) rounded up to 2^16, 2^17 or 2^18 --
+// at most one row in eight is sorted twice up to W - 1 = 2^15, one in two at the limit W - 1 = 2^17 -- and never more than the
+// call needs (one segment of W - 1 + N rows).  2^16 is the channel length the stateless path is measured at:
+// shorter segments save merge passes but pay a bitmap clear and W set bits per 1024 outputs more often than they save.
+static uint32_t median_segment_rows(uint32_t W, uint64_t rows) {
+    const uint64_t want = 8ull * (W - 1);
+    const uint64_t S = want <= (1u << 16) ? (1u << 16) : want <= (1u << 17) ? (1u << 17) : kMedMaxRanks;
+    return (uint32_t)std::min<uint64_t>(S, (uint64_t)(W - 1) + rows);
+}
+
+int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
+    if (!p || window == 0 || !d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    const uint32_t W = (uint32_t)std::min<size_t>(window, (size_t)kMedMaxCarry + 2);  // (not clamped to ns: the window is the recording's)
+    WinGeom f;
+    bool in_place;
+    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, W, kMedThreads, kMedRun, &f, &in_place, true)) return rc;
+    if (W > kMedShortMax && W - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;  // (at least half of every segment is new rows)
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t rows = (uint64_t)nblocks * g.ns;  // (below 2^31 - 2^17: window_call_checks)
+    if (W == 1) {  // a copy; the state is its header and stays zero
+        if (in_place) return RSPT_HIP_OK;
+        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, rows * f.stride, hipMemcpyDeviceToDevice, st));
+        return RSPT_HIP_OK;
+    }
+    MedianStage& ms = p->med;
+    const uint32_t bps = g.bps;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;
+    const bool is_short = W <= kMedShortMax;
+    const uint64_t pieces = is_short ? halo_pieces(f, 1, in_place) : 0;
+    const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
+    const uint64_t head_bytes = 8 + (uint64_t)(W - 1) * f.stride;
+    // generic: (segment, channel) items of S keys each, in pieces of up to 2^25 keys
+    MedSeg sg{};
+    WinGeom fg = f;
+    uint64_t items = 0, piece_items = 0;
+    if (!is_short) {
+        const uint32_t S = median_segment_rows(W, rows);
+        sg.L = S - (W - 1);
+        sg.nseg = (uint32_t)((rows + sg.L - 1) / sg.L);
+        sg.N = (uint32_t)rows;
+        fg.ns = S;
+        items = (uint64_t)sg.nseg * g.nch;
+        piece_items = std::min<uint64_t>(items, std::max<uint64_t>(1, (1ull << 25) / S));
+    }
+    if (int rc = median_reserve(ms, halo_bytes, head_bytes, piece_items * fg.ns)) return rc;
+    sg.head = ms.head;
+    // the new state is written from d_src before any kernel stores to d_dst
+    hipError_t e = launch_med_carry(f, d_src, ms.head, d_state, rows, st);
+    if (is_short) {
+        if (e == hipSuccess && pieces) e = launch_halo(f, d_src, ms.halo, pieces, st);
+        if (e == hipSuccess) e = launch_med_short_w<true>(bps, f, d_src, d_dst, pieces ? (const uint8_t*)ms.halo : nullptr, aligned, st, ms.head);
+    } else {
+        // from the last segment to the first: a walk writes its segment's new rows, which no segment sorted later reads
+        for (uint64_t item0 = 0; e == hipSuccess && item0 < items; item0 += piece_items) {
+            const uint64_t ni = std::min(piece_items, items - item0);
+            e = by_bps(bps, [&](auto bb) {
+                return launch_med_generic<decltype(bb)::value, true>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, aligned, st, sg);
             });
         }
     }
