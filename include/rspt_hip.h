@@ -500,6 +500,40 @@ int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src
                                            void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
                                            size_t max_peaks, double* d_sig, double* d_threshold, void* stream);
 
+/* ---- the reference's quality figure: PRDN[%] of a decoded block against its original ------------------------------
+ * What test_packer_ prints behind a round trip (lib_rspt_test/rspt_test.cpp:98-111), the only quality figure the reference
+ * publishes for its lossy packers, on nblocks device-resident blocks, bit-identical with the reference's x86-64 build.  Per
+ * block, with o the original and d the decoded block, each read into int32 per channel as convert_native_to_i32 does:
+ *     mse = 0.0; ref = 0.0                                   one pair of doubles for the WHOLE block
+ *     for c in 0 .. nch-1:                                   channel outer, sample inner
+ *         mean = (int32)(int64)((uint64)sum(o[c]) / (uint64)ns)      average_32: the division is UNSIGNED, so a negative channel
+ *                                                                    sum at an ns that is not a power of two gives a garbage mean
+ *         for s in 0 .. ns-1:
+ *             t = (double)(int32)(o[c][s] - d[c][s])         the int32 subtraction wraps
+ *             mse += t * t                                   double product, double sum, each rounded on its own
+ *             r = (int32)((o[c][s] - mean) * (o[c][s] - mean))       int * int: the subtraction and the square WRAP, r may be negative
+ *             ref += (double)r
+ *     PRDN = sqrt(mse / ref) * 100.0                         correctly rounded divide, square root and product, no contraction
+ * ref can be negative or zero: every NaN (the square root of a negative quotient, 0 / 0) is stored as the x86-64 default NaN
+ * 0xFFF8000000000000; ref == 0 with mse > 0 gives +inf; d == o gives 0.0 (-0.0 under a negative ref).
+ * Every term is an integer, so the sums are taken exactly in integers and in parallel where that provably equals the
+ * reference's chain of rounded adds: mse = (double)sum(t^2) where the exact sum(t^2) <= 2^53, and ref = (double)sum(r) where
+ * the exact sum(|r|) <= 2^53 (always so for nch * ns < 2^22) -- no partial sum then leaves +-2^53 and every add is exact.  A block
+ * that misses a condition takes the sequential path: one workgroup adds that sum's terms in the reference's order (tens of
+ * milliseconds per 2^22 samples; the blocks of a batch go side by side).
+ *   d_orig, d_dec   nblocks blocks each of the handle's shape, interleaved native layout; only read; may be the same buffer.
+ *                   The handle supplies the shape and the byte order (rspt_hip_set_byte_order); any packer kind will do.
+ *                   16-byte aligned buffers (and block sizes, for nblocks > 1) are read with the widest loads
+ *   d_prdn          [nblocks] doubles; required
+ *   d_mse, d_ref    [nblocks] doubles, optional (NULL): the two accumulators as the reference leaves them
+ *   d_path          [nblocks] uint32, optional (NULL): 0 where the block took the exact-integer path, 1 where the sequential one
+ * RSPT_HIP_ERR_ARG for nblocks == 0, a NULL d_orig, d_dec or d_prdn, and nblocks * nch >= 2^31; more than 65535 blocks are
+ * refused as by rspt_hip_reserve.  Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive
+ * calls on one handle are stream-ordered.  Nothing is allocated per call: the scratch (nblocks x nch channel sums, the per-block
+ * accumulators) is part of the workspace that rspt_hip_reserve sizes. */
+int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, double* d_prdn, double* d_mse,
+                            double* d_ref, uint32_t* d_path, void* stream);
+
 /* The handle's own (non-blocking) stream, as a hipStream_t. */
 void* rspt_hip_stream(rspt_hip_packer* p);
 

@@ -28,6 +28,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev",
     "rspt_hip_median_state_bytes", "rspt_hip_median_filter_stream_dev",
     "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
+    "rspt_hip_prdn_batch_dev",
     "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
     "rspt_hip_gather_post_sizes", "rspt_hip_gather_post_payload", "rspt_hip_gather_wait",
@@ -139,6 +140,8 @@ def lib():
     L.rspt_hip_peak_detect_offline_batch_dev.restype = C.c_int
     L.rspt_hip_peak_detect_offline_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rspt_hip_prdn_batch_dev.restype = C.c_int
+    L.rspt_hip_prdn_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rspt_hip_feed_begin.restype, L.rspt_hip_feed_begin.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]
     L.rspt_hip_feed_push.restype, L.rspt_hip_feed_push.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.rspt_hip_feed_submit.restype, L.rspt_hip_feed_submit.argtypes = C.c_int, [C.c_void_p]
@@ -547,6 +550,51 @@ class SignalPacker:
         if stream is not None:  # (the workspace goes back to torch's pool only once the caller's stream is past this call)
             work.record_stream(torch.cuda.ExternalStream(stream, device=dev))
         return out if traces else out[:3]
+
+    def prdn_batch(self, d_orig, d_dec, stream=None, parts=False):
+        """The reference's quality figure PRDN[%] (rspt_test.cpp:98-111; rspt_hip.h: rspt_hip_prdn_batch_dev) of the decoded
+        blocks d_dec against the originals d_orig, both device-resident in the native layout and only read; bit-identical with
+        the reference.  Asynchronous.  Returns a float64 device tensor [nblocks]; with parts, (prdn, mse, ref, path): the two
+        accumulators as the reference leaves them and, per block, 0 for the exact-integer path or 1 for the sequential one (int32)."""
+        import torch
+
+        for t in (d_orig, d_dec):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+        nblocks = d_orig.numel() // self.block_bytes
+        assert nblocks * self.block_bytes == d_orig.numel() == d_dec.numel()
+        dev = d_orig.device
+        prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
+        mse = ref = path = None
+        if parts:
+            mse, ref = torch.empty_like(prdn), torch.empty_like(prdn)
+            path = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        rc = self._L.rspt_hip_prdn_batch_dev(self._h, d_orig.data_ptr() if nblocks else None, d_dec.data_ptr() if nblocks else None, nblocks,
+                                             prdn.data_ptr() if nblocks else None, ptr(mse), ptr(ref), ptr(path), st)
+        self._check("rspt_hip_prdn_batch_dev", rc)
+        return (prdn, mse, ref, path) if parts else prdn
+
+    def roundtrip_quality(self, d_src, stream=None):
+        """The reference's test_packer_ (rspt_test.cpp:58-112) as one call: compress_batch -> decompress_batch -> prdn_batch on
+        one stream with no host synchronisation in between.  Meant for the lossy kinds (dct, hadamard); works for any.  Returns
+        (prdn, cr), float64 device tensors [nblocks]: PRDN[%] and the compression ratio block_bytes / compressed size as the
+        reference prints it.  Asynchronous; a stream that did not decode shows in its cr (the consumed size carries bit 63)."""
+        import torch
+
+        nblocks = d_src.numel() // self.block_bytes
+        d_dst, d_sizes = self.compress_batch(d_src, stream=stream)
+        d_out, d_consumed = self.decompress_batch(d_dst, nblocks, d_dst.shape[1], stream=stream)
+        prdn = self.prdn_batch(d_src.reshape(-1), d_out.reshape(-1), stream=stream)
+        ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream, device=d_src.device)) if stream is not None else None
+        if ctx is not None:
+            with ctx:
+                cr = float(self.block_bytes) / d_consumed.to(torch.float64)
+            for t in (d_dst, d_sizes, d_out, d_consumed):  # (back to torch's pool only once the caller's stream is past them)
+                t.record_stream(torch.cuda.ExternalStream(stream, device=d_src.device))
+        else:
+            cr = float(self.block_bytes) / d_consumed.to(torch.float64)
+        return prdn, cr
 
     def synchronize(self):
         self._check("rspt_hip_synchronize", self._L.rspt_hip_synchronize(self._h))

@@ -36,6 +36,7 @@
 #include "fir.hip"
 #include "median.hip"
 #include "peak.hip"
+#include "quality.hip"
 
 using namespace rspt;
 
@@ -184,6 +185,9 @@ struct Workspace {
     Dev<double2> fft_scratch;  // [fft_bpp][nch][n] (dct beyond the dense table)
     size_t fft_bpp = 0;        // blocks per pass (bounds the scratch to ~1 GiB)
     Dev<int32_t> mean_i32;     // [cap][nch]
+    // rspt_hip_prdn_batch_dev: [cap][nch] int64 channel sums | [cap][4] per-block accumulators | [cap] u32 flags, each part placed
+    // per call right behind the one before it (the first two are zeroed by one memset in front of the call's kernels)
+    Dev<unsigned long long> quality;
 };
 
 // rspt_hip_compress / rspt_hip_decompress: one block staged on the device
@@ -1053,6 +1057,7 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
         ok &= hipMalloc(w.fft_scratch.out(), w.fft_bpp * per_block) == hipSuccess;
         ok &= hipMalloc(w.mean_i32.out(), max_blocks * (size_t)g.nch * sizeof(int32_t)) == hipSuccess;
     }
+    ok &= hipMalloc(w.quality.out(), max_blocks * ((size_t)g.nch + 5) * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) return RSPT_HIP_ERR_ALLOC;
     // the clean-plane invariant starts from zeroed planes
     HIPCHK(p, hipMemset(w.planes, 0, max_blocks * kMaxPlanes * g.plane_stride + 4096));
@@ -2226,6 +2231,74 @@ int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, voi
         }
     }
     return finish_window_call(p, ms.last, e, st);
+}
+
+// ---- PRDN: the quality figure of the reference's harness (quality.hip) -----------------------------------------------------------
+// The decomposition of the two streaming passes for the widest load the buffers' alignment allows.
+static QGeom quality_geom(const rspt_hip_packer* p, size_t nblocks, int W) {
+    const Geom& g = p->g;
+    QGeom q{};
+    q.block_bytes = g.block_bytes;
+    q.nch = g.nch, q.ns = g.ns, q.be = g.be;
+    const uint32_t nw = W == 0 ? 1u : (g.bps == 3 ? 3u : 1u) * (uint32_t)W;
+    const uint32_t vs = W == 0 ? 1u : nw * 4u / g.bps;  // samples of a load group
+    uint32_t a = g.nch, b = vs;
+    while (b) {
+        const uint32_t t = a % b;
+        a = b, b = t;
+    }
+    q.rows = vs / a;  // the fewest rows that hold whole groups
+    const uint64_t qps = (uint64_t)q.rows * g.nch / vs;
+    q.qps = (uint32_t)qps;
+    q.nsub = qps < kQThreads ? kQThreads / q.qps : 1u;
+    q.ncg = (uint32_t)((qps + kQThreads - 1) / kQThreads);
+    q.nsr = g.ns / q.rows;
+    const uint64_t sweeps = ((uint64_t)q.nsr + q.nsub - 1) / q.nsub;
+    // workgroups: about 4096 in all where the blocks are long enough to give each at least 8 sweeps
+    uint64_t nsplit = std::min<uint64_t>(std::max<uint64_t>(1, sweeps / 8), (4096 + nblocks * q.ncg - 1) / (nblocks * q.ncg));
+    q.span = (uint32_t)std::max<uint64_t>(1, (sweeps + nsplit - 1) / nsplit) * q.nsub;
+    q.nsplit = (uint32_t)std::max<uint64_t>(1, ((uint64_t)q.nsr + q.span - 1) / q.span);
+    return q;
+}
+
+int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, double* d_prdn, double* d_mse, double* d_ref,
+                            uint32_t* d_path, void* stream) {
+    if (!p || !d_orig || !d_dec || !d_prdn || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
+    const Geom& g = p->g;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_orig), d0 = reinterpret_cast<uintptr_t>(d_dec);
+    auto aligned = [&](uintptr_t m) { return o0 % m == 0 && d0 % m == 0 && (nblocks == 1 || g.block_bytes % m == 0); };
+    const int W = aligned(16) ? 4 : aligned(4) ? 1 : 0;
+    QGeom q = quality_geom(p, nblocks, W);
+    q.aligned4 = aligned(4) ? 1u : 0u;
+    const uint64_t units = (uint64_t)nblocks * q.ncg * q.nsplit;
+    if (units >= (1ull << 31) || (uint64_t)q.rows * g.nch >= (1ull << 32)) return RSPT_HIP_ERR_UNSUPPORTED;
+    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t B = (uint32_t)nblocks;
+    unsigned long long* sums = p->ws.quality;
+    unsigned long long* acc = sums + (size_t)B * g.nch;
+    uint32_t* flag = reinterpret_cast<uint32_t*>(acc + (size_t)B * 4);
+    HIPCHK(p, hipMemsetAsync(sums, 0, ((size_t)B * g.nch + (size_t)B * 4) * sizeof(unsigned long long), st));
+    const uint8_t* o = (const uint8_t*)d_orig;
+    const uint8_t* d = (const uint8_t*)d_dec;
+    by_bps(g.bps, [&](auto bb) {
+        constexpr int BPS = decltype(bb)::value;
+        auto go = [&](auto ww) {
+            constexpr int WW = decltype(ww)::value;
+            hipLaunchKernelGGL((k_q_sums<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, q, sums);
+            hipLaunchKernelGGL((k_q_accum<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, acc);
+        };
+        if (W == 4) go(std::integral_constant<int, 4>());
+        else if (W == 1) go(std::integral_constant<int, 1>());
+        else go(std::integral_constant<int, 0>());
+        hipLaunchKernelGGL(k_q_finish, dim3((B + 255) / 256), dim3(256), 0, st, (const unsigned long long*)acc, B, flag, d_prdn, d_mse, d_ref, d_path);
+        hipLaunchKernelGGL(k_q_seq<BPS>, dim3(B), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, (const unsigned long long*)acc,
+                           (const uint32_t*)flag, d_prdn, d_mse, d_ref);
+    });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
 }
 
 int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff_low, double cutoff_high, double* num, double* den,
