@@ -65,7 +65,10 @@ int rspt_hip_device_count(void);
  * (signal_packer_xdelta_hzr.cpp:42-50, _hzr.cpp:42-49, _hadamard.cpp:47-55,
  * _dct.cpp:49-58): same meaning of (bytes_per_sample, nr_channels,
  * nr_samples_per_channel, nr_bytes_to_encode); `nb` is read by
- * RSPT_HIP_KIND_XDELTA_HZR only.  `device` is the HIP device ordinal. */
+ * RSPT_HIP_KIND_XDELTA_HZR only.  `device` is the HIP device ordinal.
+ * Shape limits: nch * ns < 2^31 (RSPT_HIP_ERR_ARG: the reference indexes with int); nch <= 65535, the reference's own limit --
+ * its converters convert_native_to_i32 / convert_i32_to_native count channels in a uint16_t (utils.cpp:57, 129), so 65536
+ * channels never terminate there -- and the ns limits of hadamard and dct: RSPT_HIP_ERR_UNSUPPORTED beyond. */
 int rspt_hip_packer_create(rspt_hip_packer** out, int kind, size_t bps, size_t nch, size_t ns, size_t nb, int device);
 
 /* Replaces i_signal_packer::delete_* (signal_packer.h:60-72). */
@@ -291,6 +294,9 @@ int rspt_hip_gather_wait(rspt_hip_packer* p, int slot, void* stream);
  *   per_channel     0: one filter object for all channels of a block, its state running on from channel to channel, as
  *                      in the reference's harness (the channels of a block are then a serial chain: one thread per block);
  *                   1: a fresh filter per channel (one i_filter per channel): one thread per channel
+ * Handles of more than 8191 channels: this stage, its carried-state form, the FIR and median stages (both forms), both peak
+ * stages and the PRDN stage are verified on handles of up to 8191 channels only and return RSPT_HIP_ERR_UNSUPPORTED beyond,
+ * before anything is launched (the packers and the two converters take up to 65535).
  * Asynchronous on `stream`. */
 int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
                                      int init_nr_samples, int per_channel, void* stream);
@@ -316,7 +322,8 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
  * A channel is one serial chain over the whole call and only nch lanes run, so a call takes about the stateless per-channel
  * time of ONE lane over nblocks * ns samples whatever nch <= 64 is (DESIGN.md 4b has the measured figures); calls of fewer
  * than 64 rows take the slower one-thread-per-channel form.  Asynchronous on `stream`; calls on one handle or one state are
- * stream-ordered.  The stage allocates nothing. */
+ * stream-ordered.  The stage allocates nothing.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_iir_state_bytes(rspt_hip_packer* p, size_t* bytes); /* nch * 88 */
 int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
                                       int init_nr_samples, void* d_state, void* stream);
@@ -334,7 +341,8 @@ int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nb
  *   kernel          host array of kernel_size doubles, 1 <= kernel_size <= 65536; read before the call returns
  * The handle only supplies the shape (bps, nch, ns); any packer kind will do.  nblocks * nch must stay below 2^31, as for the IIR
  * stage.  Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive calls on one handle
- * are stream-ordered.  Device and page-locked memory the stage needs belong to the handle. */
+ * are stream-ordered.  Device and page-locked memory the stage needs belong to the handle.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
                                      void* stream);
 
@@ -357,7 +365,8 @@ int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void
  * RSPT_HIP_ERR_UNSUPPORTED for a call of 2^31 - 2^17 rows (nblocks * ns) or more: split the call, with a state that is exact.
  * Every output depends on inputs only, so the stage is as parallel as the stateless one and does the same multiply-add work,
  * plus two copies of K - 1 rows.  Asynchronous on `stream`; calls on one handle or one state are
- * stream-ordered.  The stage allocates nothing per state: the staged copy of the old state belongs to the handle. */
+ * stream-ordered.  The stage allocates nothing per state: the staged copy of the old state belongs to the handle.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes); /* 8 + ((K - 1) * nch * bps rounded up to 8) */
 int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
                                       void* d_state, void* stream);
@@ -374,7 +383,8 @@ int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, voi
  *   window          1 or more (0 is RSPT_HIP_ERR_ARG); windows above 32 need ns <= 2^18 (else RSPT_HIP_ERR_UNSUPPORTED)
  * The handle only supplies the shape (bps, nch, ns); any packer kind will do.  nblocks * nch must stay below 2^31.
  * Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive calls on one handle are
- * stream-ordered.  Device memory the stage needs belongs to the handle. */
+ * stream-ordered.  Device memory the stage needs belongs to the handle.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream);
 
 /* ---- the rolling-window median with a carried state: one object per channel over a recording that arrives in blocks ----
@@ -401,7 +411,8 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
  * 32 have no other limit; windows above 32 take any ns and any call length below the row limit (the stateless entry's
  * ns <= 2^18 does not apply: a call is cut into segments of at most 2^18 rows that overlap by W - 1).
  * Asynchronous on `stream`; calls on one handle or one state are stream-ordered.  The stage allocates nothing per state: the
- * staged copy of the old state belongs to the handle. */
+ * staged copy of the old state belongs to the handle.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes); /* 8 + ((W - 1) * nch * bps rounded up to 8) */
 int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state,
                                       void* stream);
@@ -452,7 +463,8 @@ int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff
  * RSPT_HIP_ERR_ARG for an unknown variant, a sampling_rate that is not finite, <= 0 or > 2^20, a NULL d_src or d_count,
  * max_peaks > 0 with a NULL d_index or d_value, only one of d_sig / d_threshold, nblocks == 0, nblocks * nch >= 2^31, or
  * max_peaks above 2^32.  Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive calls
- * on one handle are stream-ordered.  The stage allocates nothing of its own. */
+ * on one handle are stream-ordered.  The stage allocates nothing of its own.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_peak_state_bytes(rspt_hip_packer* p, size_t* bytes); /* one detector per channel: nch * 208 bytes */
 int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
                                    void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
@@ -494,7 +506,8 @@ int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t
  * d_src or d_count, max_peaks > 0 with a NULL d_index or d_value, only one of d_sig / d_threshold, nblocks == 0,
  * nblocks * nch >= 2^31, max_peaks above 2^32), a NULL or misaligned d_work, and the reference's undefined cases: fs < 10
  * (nr_slope_samples 0: its shift runs past the end of the array) and ns < radius (its unsigned loop bound wraps).
- * Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev. */
+ * Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int stateful, size_t* bytes);
 int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
                                            void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
@@ -530,9 +543,30 @@ int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src
  * RSPT_HIP_ERR_ARG for nblocks == 0, a NULL d_orig, d_dec or d_prdn, and nblocks * nch >= 2^31; more than 65535 blocks are
  * refused as by rspt_hip_reserve.  Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev: successive
  * calls on one handle are stream-ordered.  Nothing is allocated per call: the scratch (nblocks x nch channel sums, the per-block
- * accumulators) is part of the workspace that rspt_hip_reserve sizes. */
+ * accumulators) is part of the workspace that rspt_hip_reserve sizes.
+ * Handles of more than 8191 channels: RSPT_HIP_ERR_UNSUPPORTED before anything is launched (see rspt_hip_iir_prefilter_batch_dev). */
 int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, double* d_prdn, double* d_mse,
                             double* d_ref, uint32_t* d_path, void* stream);
+
+/* ---- native <-> planar int32: the reference's convert_native_to_i32 / convert_i32_to_native as stages ---------------
+ * What every program of the reference runs first and last (lib_signalpacker/utils.cpp:51-191; rspt_test.cpp:62-64, 92-94,
+ * 119-135): the interleaved native block <-> a [channels][samples] int32 matrix, on nblocks device-resident blocks.
+ *   d_native   nblocks blocks of the handle's shape in the compress layout (sample-major, bps bytes per sample, in the byte
+ *              order of rspt_hip_set_byte_order); any alignment -- 16-byte aligned buffers take the widest accesses
+ *   d_planar   [nblocks][nch][ns] int32, 4-byte aligned (16-byte aligned buffers take the widest accesses)
+ * native -> i32 sign-extends every sample from bps bytes; i32 -> native keeps the low bps bytes of every value.  Both are
+ * bit-identical with the reference's functions for bps 1 - 4 and both values of reverse_byte_order, with one exception: the
+ * byte order has no effect on one-byte samples, as everywhere in this library.  The reference's bps == 1 reversed store writes
+ * at native + 1 (utils.cpp:115), one byte past the caller's buffer; that is not reproduced.
+ * Any packer kind will do: the handle supplies (bps, nch, ns) and the byte order, nothing else of it is used -- the stages
+ * allocate nothing and do not touch the workspace.  Handles of up to about a thousand channels with a 16-byte aligned d_native
+ * run the tile kernels of the packers' own front end and inverse (i32 -> native: only the common int32 shape and handles of
+ * fewer than 32 channels); everything else the 64 x 64 transposes k_wide_planar / k_wide_native.
+ * RSPT_HIP_ERR_ARG for a NULL handle or pointer, nblocks == 0, nblocks * nch >= 2^31, a d_planar that is not 4-byte aligned
+ * and any overlap of the two buffers; more than 65535 blocks are refused as by rspt_hip_reserve.  A refused call writes
+ * nothing.  Asynchronous on `stream`, with the ordering contract of rspt_hip_compress_batch_dev. */
+int rspt_hip_native_to_i32_batch_dev(rspt_hip_packer* p, const void* d_native, int32_t* d_planar, size_t nblocks, void* stream);
+int rspt_hip_i32_to_native_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, void* d_native, size_t nblocks, void* stream);
 
 /* The handle's own (non-blocking) stream, as a hipStream_t. */
 void* rspt_hip_stream(rspt_hip_packer* p);

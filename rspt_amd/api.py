@@ -28,7 +28,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev",
     "rspt_hip_median_state_bytes", "rspt_hip_median_filter_stream_dev",
     "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
-    "rspt_hip_prdn_batch_dev",
+    "rspt_hip_prdn_batch_dev", "rspt_hip_native_to_i32_batch_dev", "rspt_hip_i32_to_native_batch_dev",
     "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
     "rspt_hip_gather_post_sizes", "rspt_hip_gather_post_payload", "rspt_hip_gather_wait",
@@ -142,6 +142,10 @@ def lib():
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rspt_hip_prdn_batch_dev.restype = C.c_int
     L.rspt_hip_prdn_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rspt_hip_native_to_i32_batch_dev.restype = C.c_int
+    L.rspt_hip_native_to_i32_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.rspt_hip_i32_to_native_batch_dev.restype = C.c_int
+    L.rspt_hip_i32_to_native_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.rspt_hip_feed_begin.restype, L.rspt_hip_feed_begin.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]
     L.rspt_hip_feed_push.restype, L.rspt_hip_feed_push.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.rspt_hip_feed_submit.restype, L.rspt_hip_feed_submit.argtypes = C.c_int, [C.c_void_p]
@@ -574,6 +578,40 @@ class SignalPacker:
                                              prdn.data_ptr() if nblocks else None, ptr(mse), ptr(ref), ptr(path), st)
         self._check("rspt_hip_prdn_batch_dev", rc)
         return (prdn, mse, ref, path) if parts else prdn
+
+    def to_planar_i32(self, d_src, d_out=None, stream=None):
+        """The reference's convert_native_to_i32 (utils.cpp:123-191; rspt_hip.h: rspt_hip_native_to_i32_batch_dev) on
+        device-resident blocks in the native layout (uint8, any alignment; the byte order of set_byte_order): every sample
+        sign-extended from bps bytes.  Returns torch.int32 [nblocks, nch, ns].  Asynchronous."""
+        import torch
+
+        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
+        nblocks = d_src.numel() // self.block_bytes
+        assert nblocks * self.block_bytes == d_src.numel()
+        if d_out is None:
+            d_out = torch.empty((nblocks, self.nch, self.ns), dtype=torch.int32, device=d_src.device)
+        assert d_out.is_cuda and d_out.dtype == torch.int32 and d_out.is_contiguous() and d_out.numel() == nblocks * self.nch * self.ns
+        st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
+        rc = self._L.rspt_hip_native_to_i32_batch_dev(self._h, d_src.data_ptr() if nblocks else None, d_out.data_ptr() if nblocks else None, nblocks, st)
+        self._check("rspt_hip_native_to_i32_batch_dev", rc)
+        return d_out
+
+    def from_planar_i32(self, d_planar, d_out=None, stream=None):
+        """The reference's convert_i32_to_native (utils.cpp:51-121; rspt_hip.h: rspt_hip_i32_to_native_batch_dev): int32
+        [nblocks, nch, ns] on the device -> the blocks in the native layout, the low bps bytes of every value kept (the byte order
+        of set_byte_order).  Returns torch.uint8 [nblocks, block_bytes]; d_out may sit at any address.  Asynchronous."""
+        import torch
+
+        assert d_planar.is_cuda and d_planar.dtype == torch.int32 and d_planar.is_contiguous()
+        nblocks = d_planar.numel() // (self.nch * self.ns)
+        assert nblocks * self.nch * self.ns == d_planar.numel()
+        if d_out is None:
+            d_out = torch.empty((nblocks, self.block_bytes), dtype=torch.uint8, device=d_planar.device)
+        assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() == nblocks * self.block_bytes
+        st = stream if stream is not None else torch.cuda.current_stream(d_planar.device).cuda_stream
+        rc = self._L.rspt_hip_i32_to_native_batch_dev(self._h, d_planar.data_ptr() if nblocks else None, d_out.data_ptr() if nblocks else None, nblocks, st)
+        self._check("rspt_hip_i32_to_native_batch_dev", rc)
+        return d_out
 
     def roundtrip_quality(self, d_src, stream=None):
         """The reference's test_packer_ (rspt_test.cpp:58-112) as one call: compress_batch -> decompress_batch -> prdn_batch on

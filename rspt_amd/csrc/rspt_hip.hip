@@ -37,6 +37,7 @@
 #include "median.hip"
 #include "peak.hip"
 #include "quality.hip"
+#include "convert.hip"
 
 using namespace rspt;
 
@@ -308,7 +309,7 @@ struct rspt_hip_packer {
     bool dct_real = false;             // forward transform through the real-input FFT (n >= 256)
     uint32_t fftr_la = 0, fftr_lb = 0; // n/2 = 2^(la+lb)
     uint32_t ntile = 0;
-    uint32_t Tn_native = 0;  // tile of k_planar_native
+    uint32_t Tn_native = 0;  // tile of k_planar_native; 0: one row of all channels does not fit its LDS (more than 8192 channels) -> k_wide_native
     // tile geometry for the front end
     uint32_t T = 0, in_lds = 0;  // k_tile_planar: tile staged in LDS
     uint32_t Tp[5] = {0, 0, 0, 0, 0};  // k_tile_planes: tile length when kcount planes are staged: rows [kcount*nch][Tp+16] + nz flags
@@ -323,6 +324,7 @@ struct rspt_hip_packer {
     int big_endian = 0;   // samples arrive / leave with their bytes reversed (rspt_hip_set_byte_order)
     bool profiling = false;
     bool ev_valid = false;
+    bool conv_lds_raised = false;  // rspt_hip_native_to_i32_batch_dev has raised k_tile_planar's dynamic LDS limit
 
     // ---- per-handle constants (rspt_hip_packer_create) ----
     Stream stream;
@@ -706,6 +708,19 @@ static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const
     return hipGetLastError();
 }
 
+// The reference's channel limit: convert_native_to_i32 / convert_i32_to_native, which every one of its programs runs first and
+// last, count channels with a uint16_t (utils.cpp:57, 129) -- 65536 channels never terminate there.
+static constexpr size_t kMaxChannels = 65535;
+// The widest handle the filter, median, peak and PRDN stages are verified on (tests/test_gpu_wide_channels.py): beyond it they
+// return RSPT_HIP_ERR_UNSUPPORTED before anything is launched.
+static constexpr uint32_t kStageMaxChannels = 8191;
+static bool stage_too_wide(const rspt_hip_packer* p) { return p->g.nch > kStageMaxChannels; }
+
+template <int BPS>
+static void launch_wide_native(const Geom& g, const int32_t* planar, uint8_t* dst, uint32_t B, hipStream_t st) {
+    hipLaunchKernelGGL(k_wide_native<BPS>, dim3((g.ns + 63) / 64, (g.nch + 63) / 64, B), dim3(256), 0, st, planar, g, dst);
+}
+
 template <bool XDELTA, int CG>
 static void launch_inv_native(rspt_hip_packer* p, uint32_t B, uint32_t nrow, void* d_dst, hipStream_t st) {
     const Geom& g = p->g;
@@ -800,6 +815,7 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
     const int kind = kind_and_flags & ~RSPT_HIP_DCT_FORCE_FFT;
     if (kind < 0 || kind > 3 || bps < 1 || bps > 4 || nch == 0 || ns == 0) return RSPT_HIP_ERR_ARG;
     if ((unsigned long long)nch * ns >= (1ull << 31)) return RSPT_HIP_ERR_ARG;  // the reference indexes with int
+    if (nch > kMaxChannels) return RSPT_HIP_ERR_UNSUPPORTED;  // the reference's converters count channels in a uint16_t (utils.cpp:57, 129)
     if (kind == RSPT_HIP_KIND_XDELTA_HZR && (nb < 1 || nb > 4)) return RSPT_HIP_ERR_ARG;
     if (kind == RSPT_HIP_KIND_HADAMARD && (ns & (ns - 1))) return RSPT_HIP_ERR_ARG;  // fwht.c needs n = 2^k
     int ndev = 0;
@@ -879,8 +895,7 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
         uint32_t T = (uint32_t)(65536ull / (4ull * g.nch));
         T = T > 1 ? T - 1 : 0;
         if (T > 1024) T = 1024;
-        if (T < 1) return RSPT_HIP_ERR_UNSUPPORTED;
-        p->Tn_native = T;
+        p->Tn_native = T;  // (0 beyond 8192 channels: decompress ends in k_wide_native, convert.hip)
     }
     if (kind == RSPT_HIP_KIND_HADAMARD && ns > (1u << 22)) return RSPT_HIP_ERR_UNSUPPORTED;  // (up to 65536 one workgroup per channel; beyond, two passes: launch_fwht_big)
     if (kind == RSPT_HIP_KIND_DCT) {
@@ -1839,8 +1854,10 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
         }
         const uint32_t T = min(p->Tn_native, g.ns);
         const uint32_t lds = g.nch * (T + 1) * 4;
-        const dim3 ng((g.ns + T - 1) / T, B);
-        if (g.bps == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0) {
+        const dim3 ng(T ? (g.ns + T - 1) / T : 0u, B);
+        if (T == 0) {  // more channels than k_planar_native holds a row of: 64 x 64 tiles
+            by_bps(g.bps, [&](auto bps) { launch_wide_native<decltype(bps)::value>(g, final_planar, (uint8_t*)d_dst, B, st); });
+        } else if (g.bps == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0) {
             const uint32_t T4 = tile_i32x4(g);
             hipLaunchKernelGGL(k_planar_native_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, final_planar, g, T4,
                                (uint8_t*)d_dst);
@@ -1904,6 +1921,7 @@ int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nbl
                                      int init_nr_samples, int per_channel, void* stream) {
     if (!p || !d_buf || !n || !d || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
     if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;  // filter_opt covers 2..5 (iir_filter.cpp:87-103)
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     HIPCHK(p, hipSetDevice(p->device));
     IirCoef c{};
     for (size_t i = 0; i < nr_coefficients; ++i) {
@@ -1933,6 +1951,7 @@ int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nb
     if (!p || !d_buf || !n || !d || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
     if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     const uint64_t rows = (uint64_t)nblocks * p->g.ns;
     if (rows >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
     HIPCHK(p, hipSetDevice(p->device));
@@ -1959,6 +1978,7 @@ static int window_call_checks(const rspt_hip_packer* p, const void* d_src, const
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
     *in_place = s0 == d0;
     if (!*in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     if (one_run && (uint64_t)nblocks * p->g.ns >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
     *f = win_geom(p, nblocks, K, threads, run, one_run ? (uint32_t)(nblocks * p->g.ns) : 0u);
     if ((uint64_t)f->subs * run * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;
@@ -2265,6 +2285,7 @@ int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* 
                             uint32_t* d_path, void* stream) {
     if (!p || !d_orig || !d_dec || !d_prdn || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
     if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     const Geom& g = p->g;
     const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_orig), d0 = reinterpret_cast<uintptr_t>(d_dec);
     auto aligned = [&](uintptr_t m) { return o0 % m == 0 && d0 % m == 0 && (nblocks == 1 || g.block_bytes % m == 0); };
@@ -2301,6 +2322,84 @@ int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* 
     return RSPT_HIP_OK;
 }
 
+// ---- native <-> planar int32 (the reference's convert_native_to_i32 / convert_i32_to_native, utils.cpp:51-191) -------------------
+// The checks of both entries.  Nothing of the handle but its shape and byte order is used: no workspace, no allocation.
+static int convert_checks(const rspt_hip_packer* p, const void* d_native, const void* d_planar, size_t nblocks) {
+    if (!p || !d_native || !d_planar || nblocks == 0 || nblocks > 65535) return RSPT_HIP_ERR_ARG;  // (65535: grid.z, as rspt_hip_reserve)
+    const Geom& g = p->g;
+    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
+    const uintptr_t n0 = reinterpret_cast<uintptr_t>(d_native), p0 = reinterpret_cast<uintptr_t>(d_planar);
+    if (p0 & 3u) return RSPT_HIP_ERR_ARG;
+    const uint64_t nbytes = (uint64_t)nblocks * g.block_bytes, pbytes = (uint64_t)nblocks * g.N * sizeof(int32_t);
+    if (n0 < p0 + pbytes && p0 < n0 + nbytes) return RSPT_HIP_ERR_ARG;  // the two buffers overlap
+    return RSPT_HIP_OK;
+}
+
+// Narrow handles with a 16-byte aligned native buffer take the tile kernels of the packers' own front end and inverse; wide ones,
+// and native buffers at any other address, the 64 x 64 transposes k_wide_planar / k_wide_native.
+static bool convert_i32x4_ok(const Geom& g, const void* d_planar) {
+    return g.bps == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_planar) & 15) == 0;
+}
+
+int rspt_hip_native_to_i32_batch_dev(rspt_hip_packer* p, const void* d_native, int32_t* d_planar, size_t nblocks, void* stream) {
+    if (int rc = convert_checks(p, d_native, d_planar, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    const Geom& g = p->g;
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* src = (const uint8_t*)d_native;
+    const unsigned B = (unsigned)nblocks;
+    if (!p->wide && (reinterpret_cast<uintptr_t>(d_native) & 15) == 0) {
+        if (convert_i32x4_ok(g, d_planar)) {
+            const uint32_t T4 = tile_i32x4(g);
+            hipLaunchKernelGGL(k_tile_planar_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, src, g, T4, d_planar,
+                               (long long*)nullptr);
+        } else {
+            by_bps(g.bps, [&](auto bps) {
+                constexpr int BPS = decltype(bps)::value;
+                if (!p->conv_lds_raised) {  // (once per handle: a handle has one sample width)
+                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_planar<BPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->in_lds) != hipSuccess) return;
+                    p->conv_lds_raised = true;
+                }
+                hipLaunchKernelGGL((k_tile_planar<BPS>), dim3((g.ns + p->T - 1) / p->T, B), dim3(256), p->in_lds, st, src, g, p->T, d_planar);
+            });
+        }
+    } else {
+        by_bps(g.bps, [&](auto bps) {
+            hipLaunchKernelGGL(k_wide_planar<decltype(bps)::value>, dim3((g.ns + 63) / 64, (g.nch + 63) / 64, B), dim3(256), 0, st, src, g, d_planar);
+        });
+    }
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_i32_to_native_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, void* d_native, size_t nblocks, void* stream) {
+    if (int rc = convert_checks(p, d_native, d_planar, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    const Geom& g = p->g;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* dst = (uint8_t*)d_native;
+    const unsigned B = (unsigned)nblocks;
+    // k_planar_native divides per element and stores int8 / int16 / int24 byte by byte: it keeps only the handles of fewer than 32
+    // channels, where more than half of k_wide_native's 64-channel tile would be empty.
+    const bool narrow = !p->wide && p->Tn_native && (reinterpret_cast<uintptr_t>(d_native) & 15) == 0;
+    if (narrow && (convert_i32x4_ok(g, d_planar) || g.nch < 32)) {
+        if (convert_i32x4_ok(g, d_planar)) {
+            const uint32_t T4 = tile_i32x4(g);
+            hipLaunchKernelGGL(k_planar_native_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, d_planar, g, T4, dst);
+        } else {
+            const uint32_t T = min(p->Tn_native, g.ns);
+            by_bps(g.bps, [&](auto bps) {
+                hipLaunchKernelGGL((k_planar_native<decltype(bps)::value>), dim3((g.ns + T - 1) / T, B), dim3(256), g.nch * (T + 1) * 4, st, d_planar, g, T,
+                                   dst);
+            });
+        }
+    } else {
+        by_bps(g.bps, [&](auto bps) { launch_wide_native<decltype(bps)::value>(g, d_planar, dst, B, st); });
+    }
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
 int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff_low, double cutoff_high, double* num, double* den,
                         size_t* nr_coefficients) {
     if (!num || !den || !nr_coefficients) return RSPT_HIP_ERR_ARG;
@@ -2330,6 +2429,7 @@ int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t
         !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
         !peak_coef(variant, sampling_rate, marker_val, c))
         return RSPT_HIP_ERR_ARG;
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     return by_bps(p->g.bps, [&](auto bb) {
         constexpr int B = decltype(bb)::value;
         auto go = [&](auto vv) {
@@ -2360,6 +2460,7 @@ int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src
         !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
         !peak_coef(kPeakOfflineFw, sampling_rate, marker_val, k.c))
         return RSPT_HIP_ERR_ARG;
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     // the reference's undefined cases: nr_slope_samples 0 (the shift runs every event off the end of the array) and a block
     // shorter than the relocation radius (the unsigned bound len - radius wraps)
     k.radius = (int32_t)((10.0 * sampling_rate) / 1000.0);
