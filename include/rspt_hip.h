@@ -35,8 +35,29 @@ enum rspt_hip_kind {
     RSPT_HIP_KIND_HZR = 0,        /* lib_signalpacker/signal_packer_hzr.cpp:34-68        */
     RSPT_HIP_KIND_XDELTA_HZR = 1, /* lib_signalpacker/signal_packer_xdelta_hzr.cpp:34-88 */
     RSPT_HIP_KIND_DCT = 2,        /* lib_signalpacker/signal_packer_dct.cpp:36-156       */
-    RSPT_HIP_KIND_HADAMARD = 3    /* lib_signalpacker/signal_packer_hadamard.cpp:35-107  */
+    RSPT_HIP_KIND_HADAMARD = 3,   /* lib_signalpacker/signal_packer_hadamard.cpp:35-107  */
+    RSPT_HIP_KIND_BYTES = 4       /* lib_hzr/libhzr.h: hzr_encode / hzr_decode on a raw byte buffer (see below) */
 };
+
+/* RSPT_HIP_KIND_BYTES -- libhzr itself (lib_hzr/libhzr.h), without a sample packer around it.
+ * Create with rspt_hip_packer_create(&p, RSPT_HIP_KIND_BYTES, bps = 1, nch = 1, ns = in_size, nb (ignored), device),
+ * 1 <= in_size < 2^31; any other bps or nch is RSPT_HIP_ERR_ARG.  A handle is bound to ONE buffer size (the fixed-size
+ * contract of every handle here).  A block is a buffer of in_size bytes and its stream is exactly what
+ * hzr_encode(in, in_size, ...) writes: u32 LE in_size, then the hzr blocks -- no method byte, no plane length word.
+ *   rspt_hip_block_bytes = in_size;  rspt_hip_max_compressed_size = rspt_hip_hzr_max_compressed_size(in_size);
+ *   rspt_hip_current_nb = 1;  rspt_hip_set_nb = RSPT_HIP_ERR_ARG;  container index entries carry nb = 1.
+ * Every entry point that takes a handle keeps its contract: the host calls (RSPT_HIP_ERR_DST_TOO_SMALL stands in for
+ * hzr_encode's HZR_FAIL on a short buffer), the _many pipelines, the feed, the device batch calls, the container calls,
+ * rspt_hip_set_verify, profiling.  In the device batch form buffer b starts at d_src + b * in_size -- at any byte alignment
+ * when in_size is not a multiple of 16; only the batch base keeps the 16-byte rule -- and decodes to d_dst + b * in_size.
+ * Decode differs from hzr_decode in three points, the first two because a handle has one size:
+ *   - a stream whose master header names another decoded size than in_size is malformed (RSPT_HIP_ERR_CORRUPT, bit 63 of
+ *     d_consumed[b]); hzr_decode accepts any size up to out_size;
+ *   - d_consumed[b] / *src_len report the bytes the stream spans.  hzr_decode's "decoder reached the end of the input"
+ *     test (hzr_decode.c:668) is the caller's comparison of that value with the length it holds.
+ *   - a Fill block whose length field is not 1 is malformed.  No encoder writes one; hzr_decode would read the fill byte and
+ *     go on right behind it, hzr_verify would step over the whole length, so such a stream has no framing to follow.
+ * The filter, median, peak, PRDN and converter stages see such a handle as the shape (bps 1, nch 1, ns in_size). */
 
 /* Test hook, OR-ed into `kind` at create: a dct packer takes the fp64 FFT path also where the bit-exact dense-table path
  * would run (ns = 2^k <= 8192), so that the two can be compared with each other (tests/test_gpu_dct_fft.py). */
@@ -97,6 +118,9 @@ size_t rspt_hip_max_compressed_size(const rspt_hip_packer* p);
 
 /* Input bytes per block: bps*nch*ns. */
 size_t rspt_hip_block_bytes(const rspt_hip_packer* p);
+
+/* hzr_max_compressed_size (hzr_encode.c:489-497): 4 + n + 7 * ceil(n / 65536); 4 for n = 0.  Host only: no handle, no device. */
+size_t rspt_hip_hzr_max_compressed_size(size_t uncompressed_size);
 
 /* Current nr_bytes_to_compress_ (signal_packer_xdelta_hzr.cpp:39,66): the
  * state that mutates on escalation and must match between compressor and
@@ -208,6 +232,16 @@ int rspt_hip_compress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nb
  * d_consumed[b] = bytes of stream b used; bit 63 set = malformed stream. */
 int rspt_hip_decompress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, void* d_dst,
                                   uint64_t* d_consumed, void* stream);
+
+/* hzr_verify (hzr_decode.c:569-624) of nblocks libhzr streams resident in device memory, WITHOUT decoding them: the frame walk,
+ * the mode byte of every block (<= 2) and the CRC-32C of every block's payload against its header.  Stream b starts at
+ * d_src + b*src_stride and has d_src_len[b] bytes (a device array); nothing at or beyond d_src + b*src_stride + d_src_len[b] is read.
+ * d_decoded[b] = the decoded size its master header names; bit 63 set exactly where hzr_verify returns HZR_FAIL.  Like
+ * hzr_verify it accepts ANY decoded size, not only the handle's, and ignores bytes behind the last block.  No output bytes are
+ * produced and the handle's workspace is not touched.  RSPT_HIP_KIND_BYTES handles only (RSPT_HIP_ERR_ARG otherwise).
+ * Asynchronous on `stream`. */
+int rspt_hip_hzr_verify_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* d_src_len, size_t nblocks,
+                                  uint64_t* d_decoded, void* stream);
 
 /* ---- container: many streams, back to back (what a multi-GPU gather ships) ---
  * layout (little-endian):

@@ -14,8 +14,8 @@ import numpy as np
 
 from . import build as _build
 
-KIND_HZR, KIND_XDELTA_HZR, KIND_DCT, KIND_HADAMARD = 0, 1, 2, 3
-KINDS = {"hzr": 0, "xdelta_hzr": 1, "dct": 2, "hadamard": 3}
+KIND_HZR, KIND_XDELTA_HZR, KIND_DCT, KIND_HADAMARD, KIND_BYTES = 0, 1, 2, 3, 4
+KINDS = {"hzr": 0, "xdelta_hzr": 1, "dct": 2, "hadamard": 3, "bytes": 4}
 DCT_FORCE_FFT = 0x100  # RSPT_HIP_DCT_FORCE_FFT (test hook, include/rspt_hip.h)
 
 # every symbol include/rspt_hip.h declares (tests check the library exports them all)
@@ -32,6 +32,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
     "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
     "rspt_hip_gather_post_sizes", "rspt_hip_gather_post_payload", "rspt_hip_gather_wait",
+    "rspt_hip_hzr_max_compressed_size", "rspt_hip_hzr_verify_batch_dev",
     "rspt_hip_feed_begin", "rspt_hip_feed_push", "rspt_hip_feed_submit", "rspt_hip_feed_poll", "rspt_hip_feed_flush", "rspt_hip_feed_end",
 ]
 
@@ -146,6 +147,9 @@ def lib():
     L.rspt_hip_native_to_i32_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.rspt_hip_i32_to_native_batch_dev.restype = C.c_int
     L.rspt_hip_i32_to_native_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.rspt_hip_hzr_max_compressed_size.restype, L.rspt_hip_hzr_max_compressed_size.argtypes = C.c_size_t, [C.c_size_t]
+    L.rspt_hip_hzr_verify_batch_dev.restype = C.c_int
+    L.rspt_hip_hzr_verify_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.rspt_hip_feed_begin.restype, L.rspt_hip_feed_begin.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]
     L.rspt_hip_feed_push.restype, L.rspt_hip_feed_push.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.rspt_hip_feed_submit.restype, L.rspt_hip_feed_submit.argtypes = C.c_int, [C.c_void_p]
@@ -354,6 +358,24 @@ class SignalPacker:
         rc = self._L.rspt_hip_decompress_packed_dev(self._h, d_packed.data_ptr(), plen, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
         self._check("rspt_hip_decompress_packed_dev", rc)
         return d_out, d_consumed
+
+    def hzr_verify_batch(self, d_streams, d_lengths, src_stride=None, d_decoded=None, stream=None):
+        """hzr_verify of device-resident libhzr streams without decoding them (rspt_hip_hzr_verify_batch_dev; a `bytes` handle):
+        d_streams = uint8 cuda tensor, stream b at b * src_stride (default: the row length of a 2-d tensor), d_lengths = int64 cuda
+        tensor of their lengths -> d_decoded (int64: the size each master header names; negative = bit 63 = rejected)."""
+        import torch
+
+        nblocks = d_lengths.numel()
+        if src_stride is None:
+            src_stride = d_streams.numel() // nblocks
+        assert d_streams.is_cuda and d_streams.dtype == torch.uint8 and d_streams.is_contiguous()
+        assert d_lengths.is_cuda and d_lengths.dtype == torch.int64 and d_lengths.is_contiguous()
+        if d_decoded is None:
+            d_decoded = torch.empty(nblocks, dtype=torch.int64, device=d_streams.device)
+        st = stream if stream is not None else torch.cuda.current_stream(d_streams.device).cuda_stream
+        rc = self._L.rspt_hip_hzr_verify_batch_dev(self._h, d_streams.data_ptr(), src_stride, d_lengths.data_ptr(), nblocks, d_decoded.data_ptr(), st)
+        self._check("rspt_hip_hzr_verify_batch_dev", rc)
+        return d_decoded
 
     def pack_bound(self, nblocks):
         return self._L.rspt_hip_pack_bound(self._h, nblocks)
@@ -717,6 +739,16 @@ def new_hzr(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, de
 
 def new_dct(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, device=0):
     return SignalPacker(KIND_DCT, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, 2, device)
+
+
+def new_bytes(nbytes, device=0):
+    """libhzr on raw bytes (RSPT_HIP_KIND_BYTES): a handle for buffers of `nbytes` bytes; its streams are hzr_encode's"""
+    return SignalPacker(KIND_BYTES, 1, 1, nbytes, 1, device)
+
+
+def hzr_max_compressed_size(n):
+    """hzr_max_compressed_size (host only: no device needed)"""
+    return lib().rspt_hip_hzr_max_compressed_size(n)
 
 
 def new_hadamard(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, device=0):

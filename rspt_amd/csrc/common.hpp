@@ -32,6 +32,10 @@ constexpr int kWave = 64;
 constexpr int kEncThreads = 1024;      // one hzr block per 1024-thread workgroup
 constexpr int kEncWaves = kEncThreads / kWave;
 constexpr int kMaxPlanes = 4;
+// RSPT_HIP_KIND_BYTES (include/rspt_hip.h): one raw byte buffer per block, one bare libhzr stream out.  Buffer i of a call lives in
+// the FLAT plane i of the workspace -- plane (i & 3) of block slot (i >> 2) -- so a buffer costs one plane of every per-plane table,
+// and the hzr kernels, which index by (slot, plane, hzr block), run on it as they are.
+constexpr uint32_t kKindBytes = 4;
 
 // (kModeStaged exists in BlockMeta only: a Huffman block whose finished header + payload k_tree left in the staging area)
 enum : uint32_t { kModeCopy = 0, kModeHuff = 1, kModeFill = 2, kModeSkip = 3, kModeStaged = 4 };

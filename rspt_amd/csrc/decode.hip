@@ -51,6 +51,51 @@ __global__ void k_dec_frame(const uint8_t* __restrict__ src, uint64_t src_stride
                             uint32_t* __restrict__ dec_nb) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0) *dec_counter = 0;  // k_dec_block's work queue
+    if (g.kind == kKindBytes) {
+        // Bare framing (hzr_decode.c:626-674): thread t walks stream t, a libhzr stream on its own -- u32 LE size, then the hzr
+        // blocks -- whose blocks decode into flat plane t.  A handle is bound to one size: any other size in the master header
+        // is flagged.  consumed[t] = the bytes the stream's blocks span; trailing bytes are the caller's to compare.
+        if (t >= nblocks) return;
+        bool bad = false;
+        if (pidx) {  // (the container checks of the framed form below)
+            const uint64_t* head = pidx - 4;
+            const uint64_t payload = head[2];
+            const uint64_t off = pidx[2 * t], lw = pidx[2 * t + 1], len = lw & kIdxLenMask;
+            if (head[0] != 0x4B43415054505352ull || head[1] != nblocks || payload > packed_len - (32ull + 16ull * nblocks) || (lw >> 63) ||
+                off > payload || len > payload - off)
+                bad = true;
+        }
+        if ((t & 3u) == 0) dec_nb[t >> 2] = kMaxPlanes;  // (a flagged stream's blocks are skipped by their offsets)
+        const uint32_t hb0 = t * g.nblk;
+        uint64_t q = 4;
+        if (!bad) {
+            uint64_t limit;
+            const uint8_t* s = stream_base(src, src_stride_in, pidx, t, limit);
+            if (limit < 4 || ld_le32(s) != g.N) bad = true;
+            for (uint32_t j = 0; !bad && j < g.nblk; ++j) {
+                if (q + 7 > limit) {
+                    bad = true;
+                    break;
+                }
+                blk_off[hb0 + j] = q;
+                const uint32_t L = ld_le16(s + q) + 1u;
+                // (A Fill block's payload is its one byte: hzr_decode reads that byte and goes on right behind it whatever the
+                //  length field says (hzr_decode.c:362-370), while hzr_verify steps over the whole length.  No encoder writes
+                //  another length; a stream that holds one -- a Copy block's mode byte turned into 2 keeps every CRC -- has no
+                //  framing the two agree on, and is malformed here.)
+                const uint32_t mode = s[q + 6];
+                if (mode > 2 || (mode == kModeFill && L != 1u) || q + 7 + L > limit) {
+                    bad = true;
+                    break;
+                }
+                q += 7ull + L;
+            }
+        }
+        if (bad)
+            for (uint32_t j = 0; j < g.nblk; ++j) blk_off[hb0 + j] = ~0ull;
+        atomicOr((unsigned long long*)&consumed[t], (unsigned long long)(bad ? kBadBit : q));
+        return;
+    }
     const uint32_t b = t / kMaxPlanes, k = t % kMaxPlanes;
     if (b >= nblocks) return;
     uint32_t nb = *nb_state;
@@ -316,19 +361,20 @@ __device__ __forceinline__ bool wg_any(DecLds& d, uint32_t i, bool p) {
 __shared__ DecLds g_dec;
 
 // one hzr block (plane k, block j of stream b) by one 1024-thread workgroup
-__device__ __forceinline__ void dec_block(uint32_t k, uint32_t j, uint32_t b, const uint8_t* __restrict__ src, uint64_t src_stride, const Geom& g,
+// (plane k of block slot b0; b = the stream the block belongs to: b0 itself, or the buffer 4 b0 + k of a bare-stream handle)
+__device__ __forceinline__ void dec_block(uint32_t k, uint32_t j, uint32_t b0, uint32_t b, const uint8_t* __restrict__ src, uint64_t src_stride, const Geom& g,
                                           const uint32_t* __restrict__ dec_nb, const uint64_t* __restrict__ blk_off,
                                           uint8_t* __restrict__ planes, uint64_t* __restrict__ consumed,
                                           unsigned long long* __restrict__ stamps, const CrcConsts* __restrict__ vcc,
                                           const uint64_t* __restrict__ pidx) {
     DecLds& d = g_dec;
-    if (k >= dec_nb[b]) return;
+    if (k >= dec_nb[b0]) return;
     // (opaque per block: what derives from the thread index -- a few dozen LDS addresses -- is cheap to recompute; hoisted out of
     //  the kernel's persistent loop it sits in scratch memory and comes back by loads inside the barrier-bound tree rounds)
     uint32_t tid_ = threadIdx.x;
     asm volatile("" : "+v"(tid_));
     const uint32_t tid = tid_, l = tid & 63u, w = tid >> 6;
-    const uint32_t hb = hb_index(g, b, k, j);
+    const uint32_t hb = hb_index(g, b0, k, j);
 #define DEC_STAMP(i) do { if (stamps && tid == 0 && hb < 512u) stamps[hb * 8u + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
     DEC_STAMP(0);
     // diagnostic: wall-clock (100 MHz) start/end of every workgroup, for a concurrency census (tools/census_decode.py)
@@ -340,7 +386,7 @@ __device__ __forceinline__ void dec_block(uint32_t k, uint32_t j, uint32_t b, co
     const uint32_t L = ld_le16(s) + 1u;
     const uint32_t mode = s[6];
     const uint32_t out_size = min(kHzrBlock, g.N - j * kHzrBlock);
-    uint8_t* out = planes + ((size_t)b * kMaxPlanes + k) * g.plane_stride + (size_t)j * kHzrBlock;  // 16-byte aligned
+    uint8_t* out = planes + ((size_t)b0 * kMaxPlanes + k) * g.plane_stride + (size_t)j * kHzrBlock;  // 16-byte aligned
 
     if (mode == kModeFill) {  // hzr_decode.c:362-370
         if (vcc) {
@@ -827,7 +873,12 @@ __global__ __launch_bounds__(kDecThreads, 8) void k_dec_block(const uint8_t* __r
         const uint32_t i = s_next;
         if (i >= total) break;
         const uint32_t k = i % kMaxPlanes, x = i / kMaxPlanes;
-        dec_block(k, x % g.nblk, x / g.nblk, src, src_stride, g, dec_nb, blk_off, planes, consumed, stamps, vcc, pidx);
+        if (g.kind == kKindBytes) {  // total = buffers * nblk: block i % nblk of buffer i / nblk, which is flat plane i / nblk
+            const uint32_t sb = i / g.nblk;
+            dec_block(sb % kMaxPlanes, i % g.nblk, sb / kMaxPlanes, sb, src, src_stride, g, dec_nb, blk_off, planes, consumed, stamps, vcc, pidx);
+            continue;
+        }
+        dec_block(k, x % g.nblk, x / g.nblk, x / g.nblk, src, src_stride, g, dec_nb, blk_off, planes, consumed, stamps, vcc, pidx);
     }
 }
 

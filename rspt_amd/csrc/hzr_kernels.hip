@@ -765,6 +765,49 @@ __global__ __launch_bounds__(256) void k_layout(Geom g, const uint32_t* __restri
     }
     if (tid == 0) s_plane_end[0] = 0;
     __syncthreads();
+    if (g.kind == kKindBytes) {
+        // Bare framing (hzr_encode.c:499-545): every plane of the slot is a buffer of its own and leaves as one libhzr stream --
+        // u32 LE size, then the hzr blocks; no method byte, no plane length word -- at dst + (4 b + k) * dst_stride, its length
+        // in sizes[4 b + k].  k_encode is launched with four times the stride, so the offsets carry k * dst_stride.
+        for (uint32_t q = lo; q < hi; ++q) {
+            const uint32_t k = q / g.nblk;
+            const bool fits_k = 4ull + (s_plane_end[k + 1] - s_plane_end[k]) <= dst_stride;
+            // (out_off holds head + 8 (k + 1) + the encoded bytes in front of the block: back to the offset inside plane k's stream)
+            out_off[hb0 + q] = fits_k ? (uint64_t)k * dst_stride + 4ull + (out_off[hb0 + q] - head - 8ull * (k + 1) - s_plane_end[k]) : ~0ull;
+        }
+        if (tid < nb) {
+            const uint64_t total_k = 4ull + (s_plane_end[tid + 1] - s_plane_end[tid]);
+            sizes[(size_t)b * kMaxPlanes + tid] = total_k <= dst_stride ? total_k : (total_k | (1ull << 63));
+        }
+        if (tid < nb * 4) {
+            const uint32_t k = tid >> 2;
+            const bool fits_k = 4ull + (s_plane_end[k + 1] - s_plane_end[k]) <= dst_stride;
+            plane_dirty[(size_t)b * kMaxPlanes * 4 + tid] = fits_k ? s_dirty[tid] : 0xFFFFFFFFu;
+        }
+        uint8_t* o = dst + (size_t)b * kMaxPlanes * dst_stride;
+        for (uint32_t q = lo; q < hi; ++q) {
+            const BlockMeta m = meta[hb0 + q];
+            const uint64_t off = out_off[hb0 + q];
+            if (off == ~0ull) continue;  // the buffer's stream does not fit: nothing of it is written
+            if (m.mode == kModeFill) {  // EncodeFill, as below
+                uint8_t* f = o + off;
+                uint32_t c = 0xFFFFFFFFu ^ m.fill;
+                c = ~((c >> 8) ^ cc->table[0][c & 0xFFu]);
+                f[0] = 0;
+                f[1] = 0;
+                f[2] = (uint8_t)c;
+                f[3] = (uint8_t)(c >> 8);
+                f[4] = (uint8_t)(c >> 16);
+                f[5] = (uint8_t)(c >> 24);
+                f[6] = (uint8_t)kModeFill;
+                f[7] = (uint8_t)m.fill;
+            } else if (m.mode == kModeHuff || m.mode == kModeCopy) {
+                big_list[atomicAdd(&wq->n_big, 1u)] = hb0 + q;
+            }
+        }
+        if (tid < nb && 4ull + (s_plane_end[tid + 1] - s_plane_end[tid]) <= dst_stride) store_le32(o + (uint64_t)tid * dst_stride, g.N);  // hzr_encode.c:521-522
+        return;
+    }
     const uint64_t total = head + 8ull * nb + s_plane_end[nb];
     const bool fits = total <= dst_stride;
     if (tid == 0) sizes[b] = fits ? total : (total | (1ull << 63));
@@ -860,7 +903,7 @@ constexpr uint64_t kPackLenMask = (1ull << 56) - 1ull;  // index length word: le
 // A stream that did not fit dst_stride (bit 63 of sizes[i]: nothing was written) becomes an empty, flagged entry.
 __global__ __launch_bounds__(1024) void k_pack_index(const uint64_t* __restrict__ sizes, uint32_t nblocks, const uint32_t* __restrict__ nb_state,
                                                     const uint32_t* __restrict__ nbuse, uint8_t* __restrict__ packed,
-                                                    uint64_t* __restrict__ total) {
+                                                    uint64_t* __restrict__ total, uint32_t nb_fixed) {  // nb_fixed != 0: every entry's nb (bare streams: 1)
     __shared__ uint64_t s_w[16];
     __shared__ uint64_t s_carry;
     __shared__ uint32_t s_bad;
@@ -894,7 +937,7 @@ __global__ __launch_bounds__(1024) void k_pack_index(const uint64_t* __restrict_
         }
         if (i < nblocks) {
             index[2 * i] = pre + inc - v;
-            index[2 * i + 1] = len | ((uint64_t)(nbuse[i] & 0xFu) << 56) | (bad ? (1ull << 63) : 0ull);
+            index[2 * i + 1] = len | ((uint64_t)((nb_fixed ? nb_fixed : nbuse[i]) & 0xFu) << 56) | (bad ? (1ull << 63) : 0ull);
         }
         __syncthreads();
         if (tid == 0) s_carry = tot;

@@ -38,6 +38,7 @@
 #include "peak.hip"
 #include "quality.hip"
 #include "convert.hip"
+#include "bytes.hip"
 
 using namespace rspt;
 
@@ -108,6 +109,8 @@ void make_crc_consts(CrcConsts& cc) {
     cc.pad[0] = cc.pad[1] = cc.pad[2] = 0;
 }
 
+static_assert(kKindBytes == (uint32_t)RSPT_HIP_KIND_BYTES, "common.hpp and rspt_hip.h name the same kind");
+
 enum Stage { ST_PRE = 0, ST_NB, ST_HIST, ST_TREE, ST_LAYOUT, ST_ENCODE, ST_COUNT };
 const char* kStageNames[ST_COUNT] = {"preprocess", "nb_scan", "hzr_hist", "hzr_tree", "layout", "hzr_encode"};
 
@@ -149,7 +152,8 @@ using Stream = Owned<hipStream_t, hipStreamDestroy>;
 // Everything rspt_hip_reserve() sizes; replacing it releases the old workspace as a whole.
 struct Workspace {
     size_t cap_blocks = 0;
-    Dev<uint8_t> planes;      // [cap][4][plane_stride]
+    size_t cap_slots = 0;     // block slots of four planes each: cap_blocks, or a quarter of it for a bare-stream handle (one plane per buffer)
+    Dev<uint8_t> planes;      // [slots][4][plane_stride]
     Dev<int32_t> planar;      // [cap][N] (transform packers, decode)
     Dev<uint32_t> nbuse;      // [cap]
     Dev<uint32_t> dec_nb;     // [cap] decode: planes of each stream (container index entry, else nb_state)
@@ -813,7 +817,8 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
     *out = nullptr;
     const bool force_fft = (kind_and_flags & RSPT_HIP_DCT_FORCE_FFT) != 0;  // (test hook, see rspt_hip.h)
     const int kind = kind_and_flags & ~RSPT_HIP_DCT_FORCE_FFT;
-    if (kind < 0 || kind > 3 || bps < 1 || bps > 4 || nch == 0 || ns == 0) return RSPT_HIP_ERR_ARG;
+    if (kind < 0 || kind > RSPT_HIP_KIND_BYTES || bps < 1 || bps > 4 || nch == 0 || ns == 0) return RSPT_HIP_ERR_ARG;
+    if (kind == RSPT_HIP_KIND_BYTES && (bps != 1 || nch != 1)) return RSPT_HIP_ERR_ARG;  // a byte buffer of ns bytes (nb is ignored)
     if ((unsigned long long)nch * ns >= (1ull << 31)) return RSPT_HIP_ERR_ARG;  // the reference indexes with int
     if (nch > kMaxChannels) return RSPT_HIP_ERR_UNSUPPORTED;  // the reference's converters count channels in a uint16_t (utils.cpp:57, 129)
     if (kind == RSPT_HIP_KIND_XDELTA_HZR && (nb < 1 || nb > 4)) return RSPT_HIP_ERR_ARG;
@@ -839,7 +844,7 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
     g.method = kind == RSPT_HIP_KIND_DCT ? 1u : kind == RSPT_HIP_KIND_HADAMARD ? 2u : 0u;
     g.plane_stride = ((uint64_t)g.N + 255ull) & ~255ull;
     g.block_bytes = (uint64_t)bps * nch * ns;
-    p->nb_host = p->nb_ctor = kind == RSPT_HIP_KIND_HZR ? 4u : kind == RSPT_HIP_KIND_DCT ? 2u : kind == RSPT_HIP_KIND_HADAMARD ? 3u : (unsigned)nb;
+    p->nb_host = p->nb_ctor = kind == RSPT_HIP_KIND_HZR ? 4u : kind == RSPT_HIP_KIND_DCT ? 2u : kind == RSPT_HIP_KIND_HADAMARD ? 3u : kind == RSPT_HIP_KIND_BYTES ? 1u : (unsigned)nb;
 
     // tile geometry
     {
@@ -1023,8 +1028,16 @@ size_t rspt_hip_max_compressed_size(const rspt_hip_packer* p) {
     if (!p) return 0;
     const unsigned nbmax = p->g.kind == RSPT_HIP_KIND_XDELTA_HZR ? 4u : p->nb_ctor;
     const size_t hzr_max = 4 + (size_t)p->g.N + 7ull * p->g.nblk;  // hzr_encode.c:489-497
+    if (p->g.kind == RSPT_HIP_KIND_BYTES) return hzr_max;  // the bare stream
     return 1 + p->g.hdr_len + (size_t)nbmax * (4 + hzr_max);
 }
+
+size_t rspt_hip_hzr_max_compressed_size(size_t uncompressed_size) {  // hzr_encode.c:489-497
+    return 4 + (uncompressed_size ? uncompressed_size + 7 * ((uncompressed_size + kHzrBlock - 1) / kHzrBlock) : 0);
+}
+
+// block slots (four planes each) that `nblocks` blocks take: a bare-stream handle keeps buffer i in flat plane i
+static size_t slots_of(const rspt_hip_packer* p, size_t nblocks) { return p->g.kind == RSPT_HIP_KIND_BYTES ? (nblocks + 3) / 4 : nblocks; }
 
 int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     if (!p || max_blocks == 0) return RSPT_HIP_ERR_ARG;
@@ -1035,12 +1048,16 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     p->ws = Workspace();  // (released before the new one is made: the two are never held at once)
     const Geom& g = p->g;
     Workspace w;
-    const size_t nhb = max_blocks * kMaxPlanes * g.nblk;
+    // Everything per plane or per hzr block is sized by block slots: for a bare-stream handle a quarter of the blocks (one
+    // plane per buffer), and it needs none of the int32 / scan buffers of the sample packers.
+    const bool bare = g.kind == RSPT_HIP_KIND_BYTES;
+    const size_t slots = slots_of(p, max_blocks);
+    const size_t nhb = slots * kMaxPlanes * g.nblk;
     bool ok = true;
-    ok &= hipMalloc(w.planes.out(), max_blocks * kMaxPlanes * g.plane_stride + 4096) == hipSuccess;
+    ok &= hipMalloc(w.planes.out(), slots * kMaxPlanes * g.plane_stride + 4096) == hipSuccess;
     ok &= hipMalloc(w.nbuse.out(), max_blocks * sizeof(uint32_t)) == hipSuccess;
     ok &= hipMalloc(w.dec_nb.out(), max_blocks * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(w.plane_dirty.out(), max_blocks * kMaxPlanes * 4 * sizeof(uint32_t)) == hipSuccess;
+    ok &= hipMalloc(w.plane_dirty.out(), slots * kMaxPlanes * 4 * sizeof(uint32_t)) == hipSuccess;
     // one region zeroed per call by a single memset: [nzflag: B*4*nblk][needmask: B][work counters: 16]; the last two are
     // placed per call right behind the part of nzflag in use
     w.zcap_words = nhb + max_blocks + 32 + 2 * max_blocks * (size_t)g.nch + 2;
@@ -1058,10 +1075,10 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     ok &= hipMalloc(w.out_off.out(), nhb * sizeof(uint64_t)) == hipSuccess;
     ok &= hipMalloc(w.means.out(), max_blocks * (size_t)(g.hdr_len ? g.hdr_len : 4)) == hipSuccess;
     // planar int32 scratch: transform packers on compress, every packer on decompress
-    ok &= hipMalloc(w.planar.out(), max_blocks * (size_t)g.N * sizeof(int32_t) + 4096) == hipSuccess;
+    if (!bare) ok &= hipMalloc(w.planar.out(), max_blocks * (size_t)g.N * sizeof(int32_t) + 4096) == hipSuccess;
     const size_t nscan = std::max<size_t>(p->ntile, g.N / kRowTile + 1);  // tiles of 4096, or row tiles of 256 (k_inv_native)
-    ok &= hipMalloc(w.txor.out(), max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMalloc(w.tsum.out(), max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
+    if (!bare) ok &= hipMalloc(w.txor.out(), max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
+    if (!bare) ok &= hipMalloc(w.tsum.out(), max_blocks * nscan * sizeof(uint32_t)) == hipSuccess;
     if (g.ns % kRowTile == 0 && g.bps == 4) ok &= hipMalloc(w.rowrec.out(), max_blocks * (g.N / kRowTile) * (size_t)kRowRec * sizeof(uint32_t)) == hipSuccess;
     ok &= hipMalloc(w.blk_off.out(), nhb * sizeof(uint64_t)) == hipSuccess;
     if (g.kind == RSPT_HIP_KIND_DCT) ok &= hipMalloc(w.planar2.out(), max_blocks * (size_t)g.N * sizeof(int32_t) + 4096) == hipSuccess;
@@ -1075,12 +1092,13 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     ok &= hipMalloc(w.quality.out(), max_blocks * ((size_t)g.nch + 5) * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) return RSPT_HIP_ERR_ALLOC;
     // the clean-plane invariant starts from zeroed planes
-    HIPCHK(p, hipMemset(w.planes, 0, max_blocks * kMaxPlanes * g.plane_stride + 4096));
-    HIPCHK(p, hipMemset(w.plane_dirty, 0, max_blocks * kMaxPlanes * 4 * sizeof(uint32_t)));
+    HIPCHK(p, hipMemset(w.planes, 0, slots * kMaxPlanes * g.plane_stride + 4096));
+    HIPCHK(p, hipMemset(w.plane_dirty, 0, slots * kMaxPlanes * 4 * sizeof(uint32_t)));
     p->dirty_shift = 0;
     while (((g.nblk - 1) >> p->dirty_shift) >= 128u) ++p->dirty_shift;
     HIPCHK(p, hipDeviceSynchronize());  // (the calls that follow may come on any stream)
     w.cap_blocks = max_blocks;
+    w.cap_slots = slots;
     p->ws = std::move(w);
     p->nzflag = p->ws.zbuf[0];
     return RSPT_HIP_OK;
@@ -1101,7 +1119,7 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
     stamp(p, ST_PRE, st);
     const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR;
     {
-        const size_t nhb_call = nblocks * kMaxPlanes * g.nblk;
+        const size_t nhb_call = slots_of(p, nblocks) * kMaxPlanes * g.nblk;
         p->nzflag = p->ws.zbuf[p->ws.zset];
         p->needmask = p->nzflag + nhb_call;
         p->work_ctr = p->needmask + ((nblocks + 3) & ~(size_t)3);
@@ -1117,8 +1135,22 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
         p->ws.zero_ready[0] = p->ws.zero_ready[1] = false;  // this copy is in use now; the other one becomes ready once k_tree is launched
     }
     if (p->ws.planes_unknown || (p->ablate & ~(3u << 26)) || p->psel) {  // (diagnostic runs skip kernels and stores: never trust the planes they leave; probes 26 / 27 store everything)
-        HIPCHK(p, hipMemsetAsync(p->ws.plane_dirty, 0xFF, p->ws.cap_blocks * kMaxPlanes * 4 * sizeof(uint32_t), st));
+        HIPCHK(p, hipMemsetAsync(p->ws.plane_dirty, 0xFF, p->ws.cap_slots * kMaxPlanes * 4 * sizeof(uint32_t), st));
         p->ws.planes_unknown = false;
+    }
+    if (g.kind == RSPT_HIP_KIND_BYTES) {
+        // the ingest kernel is the whole front end: planes, segment bits and nbuse[] (no escalation: nb_state stays 1)
+        const uint64_t units = (uint64_t)nblocks * ((g.N + 4095u) >> 12);
+        const uint64_t want = 8ull * (uint64_t)p->num_cu;  // eight 256-thread workgroups per CU
+        hipLaunchKernelGGL(k_bytes_ingest, dim3((uint32_t)(units < want ? units : want)), dim3(kIngestThreads), 0, st, src, g, B, p->ws.planes, p->nzflag,
+                           p->ws.nbuse, p->ws.plane_dirty, p->dirty_shift);
+        HIPCHK(p, hipGetLastError());
+        stamp(p, ST_NB, st);
+        stamp(p, ST_HIST, st);
+        const uint32_t nhb = (uint32_t)slots_of(p, nblocks) * kMaxPlanes * g.nblk;
+        hipLaunchKernelGGL(k_histlist, dim3((nhb + 255) / 256), dim3(256), 0, st, p->nzflag, p->ws.nbuse, g, nhb, p->ws.big_list, p->work_ctr + 2, p->psel);
+        HIPCHK(p, hipGetLastError());
+        return RSPT_HIP_OK;
     }
     const uint32_t np = by_bps(g.bps, [&](auto bps) { return launch_front<decltype(bps)::value>(p, src, nblocks, st); });
     if (g.kind == RSPT_HIP_KIND_HADAMARD) {
@@ -1190,6 +1222,7 @@ static int phase_tree(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
 static int phase_layout(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_stride, uint64_t* d_sizes, hipStream_t st) {
     const Geom& g = p->g;
     WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
+    // (B = block slots; a bare-stream handle's k_layout writes one stream and one size per plane of a slot)
     hipLaunchKernelGGL(k_layout, dim3(B), dim3(256), 0, st, g, p->ws.nbuse, p->ws.meta, p->ws.means, (uint8_t*)d_dst, (uint64_t)dst_stride, p->ws.out_off,
                        d_sizes, p->crc, p->nzflag, wq, p->ws.big_list, p->ws.plane_dirty, p->dirty_shift, p->psel);
     HIPCHK(p, hipGetLastError());
@@ -1201,7 +1234,7 @@ static int phase_encode(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
     WorkQueues* wq = reinterpret_cast<WorkQueues*>(p->work_ctr + 4);
     hipLaunchKernelGGL(k_encode, dim3(persistent_grid(p, nhb, p->enc_grid)), dim3(kEncThreads), 0, st, p->ws.planes, g, p->nzflag, p->ws.meta, p->ws.cw, p->ws.tdesc, p->ws.out_off,
-                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride, wq, p->ws.big_list, p->ws.segbase, p->ws.lists, p->ws.listinfo, p->stamps, p->ws.staging, nhb);
+                       p->crc, (uint8_t*)d_dst, (uint64_t)dst_stride * (g.kind == RSPT_HIP_KIND_BYTES ? kMaxPlanes : 1), wq, p->ws.big_list, p->ws.segbase, p->ws.lists, p->ws.listinfo, p->stamps, p->ws.staging, nhb);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -1211,7 +1244,7 @@ static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t n
     int rc = rspt_hip_reserve(p, nblocks);
     if (rc) return rc;
     HIPCHK(p, hipSetDevice(p->device));
-    const uint32_t B = (uint32_t)nblocks;
+    const uint32_t B = (uint32_t)slots_of(p, nblocks);  // what the hzr kernels count in
     if ((rc = phase_front(p, (const uint8_t*)d_src, nblocks, st)) != 0) return rc;
     if ((rc = phase_hist(p, B, st)) != 0) return rc;
 
@@ -1264,7 +1297,8 @@ int rspt_hip_pack_batch_dev(rspt_hip_packer* p, const void* d_dst, size_t dst_st
     if ((reinterpret_cast<uintptr_t>(d_dst) & 15) || (dst_stride & 15) || (reinterpret_cast<uintptr_t>(d_packed) & 15)) return RSPT_HIP_ERR_ARG;
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_pack_index, dim3(1), dim3(1024), 0, st, d_sizes, (uint32_t)nblocks, p->nb_state, p->ws.nbuse, (uint8_t*)d_packed, d_total);
+    hipLaunchKernelGGL(k_pack_index, dim3(1), dim3(1024), 0, st, d_sizes, (uint32_t)nblocks, p->nb_state, p->ws.nbuse, (uint8_t*)d_packed, d_total,
+                       p->g.kind == RSPT_HIP_KIND_BYTES ? 1u : 0u);
     hipLaunchKernelGGL(k_pack_copy, dim3(32, (unsigned)nblocks), dim3(256), 0, st, (const uint8_t*)d_dst, (uint64_t)dst_stride, (uint32_t)nblocks,
                        (uint8_t*)d_packed);
     HIPCHK(p, hipGetLastError());
@@ -1784,16 +1818,24 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
         const uint32_t B = (uint32_t)nblocks;
         const uint8_t* src = (const uint8_t*)d_src;
         HIPCHK(p, hipMemsetAsync(d_consumed, 0, nblocks * sizeof(uint64_t), st));
-        hipLaunchKernelGGL(k_dec_frame, dim3((B * kMaxPlanes + 63) / 64), dim3(64), 0, st, src, (uint64_t)src_stride, B, g, p->nb_state, p->ws.blk_off,
+        const bool bare = g.kind == RSPT_HIP_KIND_BYTES;  // one thread and one flat plane per stream
+        hipLaunchKernelGGL(k_dec_frame, dim3(((bare ? B : B * kMaxPlanes) + 63) / 64), dim3(64), 0, st, src, (uint64_t)src_stride, B, g, p->nb_state, p->ws.blk_off,
                            d_consumed, p->ws.means, pidx, p->nb_state + 2, (uint64_t)packed_len, p->ws.dec_nb);
         {
             // persistent: block costs differ 10x (dense plane 0 against light planes) and the dispatcher places workgroup i
             // on XCD i % 8 in order, so a plain grid ran its second half at a quarter of the slots (tools/census_decode.py)
             // (k_dec_block takes the blocks plane-fastest: dense and light ones in turns)
-            const uint32_t total = g.nblk * B * kMaxPlanes;
+            const uint32_t total = bare ? g.nblk * B : g.nblk * B * kMaxPlanes;
             const uint32_t want = 2u * (uint32_t)p->num_cu;  // two 1024-thread workgroups (76 KiB of LDS each) per CU
             hipLaunchKernelGGL(k_dec_block, dim3(want < total ? want : total), dim3(kDecThreads), 0, st, src, (uint64_t)src_stride, g, p->ws.dec_nb, p->ws.blk_off,
                                p->ws.planes, d_consumed, p->ablate ? p->stamps : nullptr, p->verify ? p->crc : nullptr, pidx, p->nb_state + 2, total);
+        }
+        if (bare) {  // the planes are the output: out to the caller's buffers, whatever their alignment
+            const uint64_t units = (uint64_t)B * ((g.N + 15u) >> 4);
+            const uint64_t wgs = (units + 255) / 256, want = 16ull * (uint64_t)p->num_cu;
+            hipLaunchKernelGGL(k_bytes_emit, dim3((uint32_t)(wgs < want ? wgs : want)), dim3(256), 0, st, p->ws.planes, g, B, (uint8_t*)d_dst);
+            HIPCHK(p, hipGetLastError());
+            return RSPT_HIP_OK;
         }
         const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_DCT;
         const dim3 tg(p->ntile, B);
@@ -1881,8 +1923,17 @@ static int decompress_host(rspt_hip_packer* p, const void* src_host, size_t src_
     // The stream length is not an input (signal_packer.h:50-57): walk the chunk
     // lengths on the host to find it -- framing only, no decoding.
     const uint8_t* s = (const uint8_t*)src_host;
-    const unsigned nb = rspt_hip_current_nb(p);
+    const unsigned nb = p->g.kind == RSPT_HIP_KIND_BYTES ? 0u : rspt_hip_current_nb(p);
     size_t pos = 1 + p->g.hdr_len;
+    if (p->g.kind == RSPT_HIP_KIND_BYTES) {  // a bare stream has no length word: master header, then nblk block headers
+        if (src_cap < 4) return RSPT_HIP_ERR_CORRUPT;
+        pos = 4;
+        for (uint32_t j = 0; j < p->g.nblk; ++j) {
+            if (src_cap - pos < 7) return RSPT_HIP_ERR_CORRUPT;
+            pos += 7 + ((size_t)s[pos] | ((size_t)s[pos + 1] << 8)) + 1;
+            if (pos > p->stage.dst_cap || pos > src_cap) return RSPT_HIP_ERR_CORRUPT;
+        }
+    }
     for (unsigned k = 0; k < nb; ++k) {
         if (pos > src_cap || src_cap - pos < 4) return RSPT_HIP_ERR_CORRUPT;  // (never a read past what the caller vouched for)
         uint32_t len;
@@ -1906,6 +1957,18 @@ static int decompress_host(rspt_hip_packer* p, const void* src_host, size_t src_
         HIPCHK(p, hipStreamSynchronize(p->stream));
     }
     *src_len = (size_t)used;
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_hzr_verify_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* d_src_len, size_t nblocks,
+                                  uint64_t* d_decoded, void* stream) {
+    if (!p || !d_src || !d_src_len || !d_decoded || nblocks == 0 || nblocks > 0xFFFFFFFFu) return RSPT_HIP_ERR_ARG;
+    if (p->g.kind != RSPT_HIP_KIND_BYTES) return RSPT_HIP_ERR_ARG;
+    HIPCHK(p, hipSetDevice(p->device));
+    const uint64_t want = 2ull * (uint64_t)p->num_cu;  // a 1024-thread workgroup per stream, two to a CU
+    hipLaunchKernelGGL(k_hzr_verify, dim3((uint32_t)(nblocks < want ? nblocks : want)), dim3(kVerThreads), 0, (hipStream_t)stream, (const uint8_t*)d_src,
+                       (uint64_t)src_stride, d_src_len, (uint32_t)nblocks, p->crc, d_decoded);
+    HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
 
@@ -2644,11 +2707,11 @@ long long rspt_hip_debug_read(rspt_hip_packer* p, int which, void* host_buf, siz
     if (!p || !host_buf || p->ws.cap_blocks == 0) return RSPT_HIP_ERR_ARG;
     if (hipSetDevice(p->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return RSPT_HIP_ERR_LAUNCH;
     const Geom& g = p->g;
-    const size_t nhb = p->ws.cap_blocks * kMaxPlanes * g.nblk;
+    const size_t nhb = p->ws.cap_slots * kMaxPlanes * g.nblk;
     const void* src = nullptr;
     size_t n = 0;
     switch (which) {
-        case 0: src = p->ws.planes; n = p->ws.cap_blocks * kMaxPlanes * g.plane_stride; break;
+        case 0: src = p->ws.planes; n = p->ws.cap_slots * kMaxPlanes * g.plane_stride; break;
         case 1: src = p->ws.planar; n = p->ws.cap_blocks * (size_t)g.N * 4; break;
         case 2: src = p->ws.planar2; n = p->ws.planar2 ? p->ws.cap_blocks * (size_t)g.N * 4 : 0; break;
         case 3: src = p->ws.hist; n = nhb * kSymStride * 4; break;
