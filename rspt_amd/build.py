@@ -8,6 +8,7 @@ serialise on a file lock and the library is published with an atomic rename, so
 nobody ever maps a half-written file.
 """
 import fcntl
+import glob
 import hashlib
 import os
 import subprocess
@@ -17,95 +18,68 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librspt_hip.so")
 STAMP = LIB + ".src-sha"
-SOURCES = ["rspt_hip.hip", "signal_packer_hip.cpp"]
-DEPS = SOURCES + ["common.hpp", "preprocess.hip", "hzr_kernels.hip", "hzr_rows.hip", "transforms.hip", "decode.hip", "filter.hip", "fir.hip", "median.hip", "peak.hip", "quality.hip", "convert.hip", "bytes.hip"]
+DIAG_LIB = os.path.join(HERE, "librspt_hip_diag.so")
+SOURCES = ["rspt_hip.hip", "signal_packer_hip.cpp"]  # the translation units; everything else in csrc/ is included by them
 INCLUDES = [os.path.join(os.path.dirname(HERE), "include", f) for f in ("rspt_hip.h", "signal_packer.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value"]
 
 
-def fingerprint():
-    h = hashlib.sha256(" ".join(FLAGS + sorted(os.environ.get("RSPT_EXTRA_FLAGS", "").split())).encode())
-    for p in [os.path.join(CSRC, f) for f in DEPS] + INCLUDES:
-        if os.path.exists(p):
-            h.update(os.path.basename(p).encode())
-            h.update(open(p, "rb").read())
+def _extra_flags():
+    return os.environ.get("RSPT_EXTRA_FLAGS", "").split()
+
+
+def fingerprint(salt="", extra=None):
+    """Flags and every source file in csrc/ (whatever is added there is covered), plus the two public headers."""
+    h = hashlib.sha256((salt + " ".join(FLAGS + sorted(_extra_flags() if extra is None else extra))).encode())
+    deps = sorted(p for ext in ("hip", "hpp", "cpp") for p in glob.glob(os.path.join(CSRC, "*." + ext)))
+    for p in deps + [p for p in INCLUDES if os.path.exists(p)]:
+        h.update(os.path.basename(p).encode())
+        h.update(open(p, "rb").read())
     return h.hexdigest()
 
 
-def stale():
-    if not os.path.exists(LIB) or not os.path.exists(STAMP):
+def stale(lib=LIB, fp=None):
+    if not os.path.exists(lib) or not os.path.exists(lib + ".src-sha"):
         return True
-    return open(STAMP).read().strip() != fingerprint()
+    return open(lib + ".src-sha").read().strip() != (fp or fingerprint())
 
 
-def build(force=False, verbose=False):
-    if "-DRSPT_DIAG" in os.environ.get("RSPT_EXTRA_FLAGS", "").split():
-        # the diagnostic library (timing probes that skip work) must never become what api.lib() loads
-        raise RuntimeError("rspt_amd.build: -DRSPT_DIAG does not belong in RSPT_EXTRA_FLAGS; build the diagnostic library with "
-                           "`python -m rspt_amd.build --diag` and load it through RSPT_HIP_LIB")
-    if not force and not stale():
-        return LIB
-    with open(LIB + ".lock", "w") as lk:
+def _build(lib, flags, fp, force, verbose):
+    """Lock, re-check, compile to a temporary, publish library and stamp by atomic rename."""
+    if not force and not stale(lib, fp):
+        return lib
+    with open(lib + ".lock", "w") as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         try:
-            if not force and not stale():  # another process built it while we waited
-                return LIB
-            fp = fingerprint()
-            hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-            tmp = "%s.tmp.%d" % (LIB, os.getpid())
-            cmd = [hipcc] + FLAGS + os.environ.get("RSPT_EXTRA_FLAGS", "").split() + ["-o", tmp]
-            cmd += [os.path.join(CSRC, f) for f in SOURCES]
+            if not force and not stale(lib, fp):  # another process built it while we waited
+                return lib
+            tmp = "%s.tmp.%d" % (lib, os.getpid())
+            cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS + flags + ["-o", tmp] + [os.path.join(CSRC, f) for f in SOURCES]
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
-            os.replace(tmp, LIB)
-            with open(STAMP + ".tmp", "w") as f:
+            os.replace(tmp, lib)
+            with open(lib + ".src-sha.tmp", "w") as f:
                 f.write(fp + "\n")
-            os.replace(STAMP + ".tmp", STAMP)
+            os.replace(lib + ".src-sha.tmp", lib + ".src-sha")
         finally:
             fcntl.flock(lk, fcntl.LOCK_UN)
-    return LIB
+    return lib
 
 
-DIAG_LIB = os.path.join(HERE, "librspt_hip_diag.so")
+def build(force=False, verbose=False):
+    if "-DRSPT_DIAG" in _extra_flags():
+        # the diagnostic library (timing probes that skip work) must never become what api.lib() loads
+        raise RuntimeError("rspt_amd.build: -DRSPT_DIAG does not belong in RSPT_EXTRA_FLAGS; build the diagnostic library with "
+                           "`python -m rspt_amd.build --diag` and load it through RSPT_HIP_LIB")
+    return _build(LIB, _extra_flags(), fingerprint(), force, verbose)
 
 
 def build_diag(verbose=False):
     """The diagnostic build (-DRSPT_DIAG: timing probes that skip work, tuning knobs from the environment) never replaces the
-    product library: it goes to librspt_hip_diag.so, which is only ever loaded through RSPT_HIP_LIB.  Same care as build():
-    a content stamp, a file lock, publication by atomic rename."""
-    flags = [f for f in os.environ.get("RSPT_EXTRA_FLAGS", "").split() if f != "-DRSPT_DIAG"]
-    stamp = DIAG_LIB + ".src-sha"
-    h = hashlib.sha256(("diag " + " ".join(FLAGS + sorted(flags))).encode())
-    for p in [os.path.join(CSRC, f) for f in DEPS] + INCLUDES:
-        if os.path.exists(p):
-            h.update(os.path.basename(p).encode())
-            h.update(open(p, "rb").read())
-    fp = h.hexdigest()
-
-    def fresh():
-        return os.path.exists(DIAG_LIB) and os.path.exists(stamp) and open(stamp).read().strip() == fp
-
-    if fresh():
-        return DIAG_LIB
-    with open(DIAG_LIB + ".lock", "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        try:
-            if fresh():
-                return DIAG_LIB
-            hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-            tmp = "%s.tmp.%d" % (DIAG_LIB, os.getpid())
-            cmd = [hipcc] + FLAGS + ["-DRSPT_DIAG"] + flags + ["-o", tmp] + [os.path.join(CSRC, f) for f in SOURCES]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd)
-            os.replace(tmp, DIAG_LIB)
-            with open(stamp + ".tmp", "w") as f:
-                f.write(fp + "\n")
-            os.replace(stamp + ".tmp", stamp)
-        finally:
-            fcntl.flock(lk, fcntl.LOCK_UN)
-    return DIAG_LIB
+    product library: it goes to librspt_hip_diag.so, which is only ever loaded through RSPT_HIP_LIB."""
+    flags = [f for f in _extra_flags() if f != "-DRSPT_DIAG"]
+    return _build(DIAG_LIB, ["-DRSPT_DIAG"] + flags, fingerprint("diag ", flags), False, verbose)
 
 
 if __name__ == "__main__":

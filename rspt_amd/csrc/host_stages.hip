@@ -1,0 +1,748 @@
+// host_stages.hip -- the host side of the analysis stages: IIR, FIR, median, PRDN, converters, R-peak detectors; each stage's
+// launchers directly in front of its entries.  Included by rspt_hip.hip.
+
+// The widest handle the filter, median, peak and PRDN stages are verified on (tests/test_gpu_wide_channels.py): beyond it they
+// return RSPT_HIP_ERR_UNSUPPORTED before anything is launched.
+static constexpr uint32_t kStageMaxChannels = 8191;
+static bool stage_too_wide(const rspt_hip_packer* p) { return p->g.nch > kStageMaxChannels; }
+
+// A batch whose (block, channel) pairs the stages count in 32 bits: at least one block and nblocks * nch < 2^31 (nch >= 1:
+// rspt_hip_packer_create), as a division so that no nblocks wraps the product.
+static bool batch_count_ok(const rspt_hip_packer* p, size_t nblocks) { return nblocks != 0 && nblocks <= 0x7FFFFFFFu / p->g.nch; }
+
+// Whole-sample loads and stores: int16 / int32 samples in buffers on a sample boundary (block_bytes is a multiple of bps).
+static bool native_aligned(uint32_t bps, const void* src, const void* dst) {
+    return (bps == 4 || bps == 2) && reinterpret_cast<uintptr_t>(src) % bps == 0 && reinterpret_cast<uintptr_t>(dst) % bps == 0;
+}
+
+// A carried-state call takes its blocks as one run of nblocks * ns rows, indexed in 32 bits with a chunk's reach beyond the last
+// row: runs of 2^31 - 2^17 rows and more are refused, and the caller splits the call (with a state that split is exact).
+static constexpr uint64_t kStreamMaxRows = (1ull << 31) - (1ull << 17);
+
+// ---- IIR pre-filter (filter.hip) ----
+template <int BPS, int NC>
+static void launch_iir(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCoef& c, int per_channel, hipStream_t st) {
+    const Geom& g = p->g;
+    if (g.ns >= kIirChunk && c.init_steps >= NC - 1) {  // the pipelined form: recurrence, feed-forward sums and stores on waves of their own
+        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;  // (block_bytes is a multiple of BPS)
+        if (per_channel) {
+            const uint32_t units = B * g.nch;
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((units + 63) / 64), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, 64u, (IirCarry*)nullptr); };
+            if (al) go(&k_iir_pipe<BPS, NC, false, (BPS == 4 || BPS == 2)>);
+            else go(&k_iir_pipe<BPS, NC, false, false>);
+        } else {
+            // shared mode: lane <-> block; few lanes per workgroup so that the blocks' scattered accesses spread over the CUs
+            uint32_t lpw = (B + (uint32_t)p->num_cu - 1) / (uint32_t)p->num_cu;
+            lpw = lpw < 1 ? 1 : lpw > 64 ? 64 : lpw;
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((B + lpw - 1) / lpw), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, lpw, (IirCarry*)nullptr); };
+            if (al) go(&k_iir_pipe<BPS, NC, true, (BPS == 4 || BPS == 2)>);
+            else go(&k_iir_pipe<BPS, NC, true, false>);
+        }
+        return;
+    }
+    if (per_channel) {
+        const uint32_t threads = B * g.nch;
+        hipLaunchKernelGGL((k_iir<BPS, NC, false>), dim3((threads + 63) / 64), dim3(64), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B);
+    } else {
+        hipLaunchKernelGGL((k_iir<BPS, NC, true>), dim3((B + 63) / 64), dim3(64), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B);
+    }
+}
+template <int BPS>
+static void launch_iir_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCoef& c, int per_channel, hipStream_t st) {
+    switch (c.nc) {
+        case 2: launch_iir<BPS, 2>(p, buf, B, c, per_channel, st); break;
+        case 3: launch_iir<BPS, 3>(p, buf, B, c, per_channel, st); break;
+        case 4: launch_iir<BPS, 4>(p, buf, B, c, per_channel, st); break;
+        default: launch_iir<BPS, 5>(p, buf, B, c, per_channel, st); break;
+    }
+}
+
+// The carried form (rspt_hip_iir_prefilter_stream_dev): the call's blocks as one run of `rows` rows, lane <-> channel, the
+// filters in `state`.  Whether a channel is fresh is known on the device only, so the route depends on the run's length alone.
+template <int BPS, int NC>
+static void launch_iir_stream(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, const IirCoef& c, IirCarry* state, hipStream_t st) {
+    const Geom& g = p->g;
+    const dim3 grid((g.nch + 63) / 64);
+    if (rows >= kIirChunk) {
+        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;
+        const uint64_t run_bytes = (uint64_t)rows * g.nch * BPS;
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kIirThreads), 0, st, buf, g.nch, rows, run_bytes, c, 1u, 64u, state); };
+        if (al) go(&k_iir_pipe<BPS, NC, false, (BPS == 4 || BPS == 2), true>);
+        else go(&k_iir_pipe<BPS, NC, false, false, true>);
+        return;
+    }
+    hipLaunchKernelGGL((k_iir_carry<BPS, NC>), grid, dim3(64), 0, st, buf, g.nch, rows, c, state);
+}
+template <int BPS>
+static void launch_iir_stream_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, const IirCoef& c, IirCarry* state, hipStream_t st) {
+    switch (c.nc) {
+        case 2: launch_iir_stream<BPS, 2>(p, buf, rows, c, state, st); break;
+        case 3: launch_iir_stream<BPS, 3>(p, buf, rows, c, state, st); break;
+        case 4: launch_iir_stream<BPS, 4>(p, buf, rows, c, state, st); break;
+        default: launch_iir_stream<BPS, 5>(p, buf, rows, c, state, st); break;
+    }
+}
+
+// Both IIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+static int iir_call(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients, int init_nr_samples,
+                    int per_channel, void* d_state, void* stream) {
+    if (!p || !d_buf || !n || !d || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;  // filter_opt covers 2..5 (iir_filter.cpp:87-103)
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    const uint64_t rows = (uint64_t)nblocks * p->g.ns;
+    if (d_state && rows >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    HIPCHK(p, hipSetDevice(p->device));
+    IirCoef c{};
+    for (size_t i = 0; i < nr_coefficients; ++i) {
+        c.n[i] = n[i];
+        c.d[i] = d[i];
+    }
+    c.nc = (uint32_t)nr_coefficients;
+    c.init_steps = 4 * init_nr_samples;
+    hipStream_t st = (hipStream_t)stream;
+    by_bps(p->g.bps, [&](auto bps) {
+        constexpr int BPS = decltype(bps)::value;
+        if (d_state) launch_iir_stream_nc<BPS>(p, (uint8_t*)d_buf, (uint32_t)rows, c, (IirCarry*)d_state, st);
+        else launch_iir_nc<BPS>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st);
+    });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                                     int init_nr_samples, int per_channel, void* stream) {
+    return iir_call(p, d_buf, nblocks, n, d, nr_coefficients, init_nr_samples, per_channel, nullptr, stream);
+}
+
+int rspt_hip_iir_state_bytes(rspt_hip_packer* p, size_t* bytes) {
+    if (!p || !bytes) return RSPT_HIP_ERR_ARG;
+    *bytes = (size_t)p->g.nch * sizeof(IirCarry);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                                      int init_nr_samples, void* d_state, void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return iir_call(p, d_buf, nblocks, n, d, nr_coefficients, init_nr_samples, 0, d_state, stream);
+}
+
+// ---- the frame of the sliding-window stages (FIR, median) ----
+// The decomposition of a sliding-window stage (WinGeom): channel groups of up to `threads` lanes' channels, runs of `run`
+// outputs per lane (kFirThreads / kFirR, kMedThreads / kMedRun), and spans along the time axis until there are about four
+// workgroups per CU -- each span at least 4 (K - 1) rows, so that the halo an in-place call stages is at most a quarter of the
+// batch.  run_rows != 0 (a carried-state call): the nblocks blocks, back to back, taken as ONE block of run_rows = nblocks * ns rows.
+static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, uint32_t run_rows = 0) {
+    Geom g = p->g;
+    if (run_rows) {
+        g.ns = run_rows;
+        g.block_bytes = (uint64_t)run_rows * g.nch * g.bps;
+        nblocks = 1;
+    }
+    WinGeom f{};
+    f.block_bytes = g.block_bytes;
+    f.stride = g.nch * g.bps;  // (window_call_checks checks the chunk's row offsets before a launch)
+    f.nch = g.nch;
+    f.ns = g.ns;
+    f.K = K;
+    f.cw = g.nch < threads ? g.nch : threads;
+    f.subs = threads / f.cw;
+    f.ncg = (g.nch + f.cw - 1) / f.cw;
+    const uint32_t C = f.subs * run;
+    const uint64_t base_units = (uint64_t)nblocks * f.ncg;
+    const uint64_t want = 4ull * (uint64_t)p->num_cu;
+    uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
+    const uint64_t min_span = K > 1 ? 4ull * (K - 1) : 1;
+    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
+    nsplit = nsplit > max_split ? max_split : nsplit;
+    nsplit = nsplit < 1 ? 1 : nsplit;
+    const uint64_t span = ((g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
+    f.span = (uint32_t)span;
+    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
+    f.units = base_units * f.nsplit;
+    return f;
+}
+
+// The checks of both windowed entry points, in the order they return: a null handle or buffer, nblocks == 0 or nblocks * nch
+// >= 2^31, and buffers that overlap without being the same (ERR_ARG); then a chunk's row offsets, which k_fir and k_med_short
+// compute in 32 bits (ERR_UNSUPPORTED: 2^24 channels and more).  Sets the geometry for the window K and whether the call is in place.
+static int window_call_checks(const rspt_hip_packer* p, const void* d_src, const void* d_dst, size_t nblocks, uint32_t K, uint32_t threads,
+                              uint32_t run, WinGeom* f, bool* in_place, bool one_run = false) {
+    if (!p || !d_src || !d_dst || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    *in_place = s0 == d0;
+    if (!*in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    if (one_run && (uint64_t)nblocks * p->g.ns >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    *f = win_geom(p, nblocks, K, threads, run, one_run ? (uint32_t)(nblocks * p->g.ns) : 0u);
+    if ((uint64_t)f->subs * run * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;
+    return RSPT_HIP_OK;
+}
+
+// The halo of an in-place call with more than one span per block: the K - 1 rows in front of every span but the first,
+// nblocks (nsplit - 1) pieces of (K - 1) rows.
+static uint64_t halo_pieces(const WinGeom& f, size_t nblocks, bool in_place) {
+    return in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;  // (a carried-state call: one block)
+}
+
+static hipError_t launch_halo(const WinGeom& f, const void* d_src, uint8_t* halo, uint64_t pieces, hipStream_t st) {
+    const bool words = (reinterpret_cast<uintptr_t>(d_src) % 4) == 0 && (f.block_bytes % 4) == 0 && (f.stride % 4) == 0;
+    const uint32_t grid = (uint32_t)(pieces < 65536 ? pieces : 65536);
+    if (words) hipLaunchKernelGGL(k_fir_halo<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, halo, f, pieces);
+    else hipLaunchKernelGGL(k_fir_halo<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, halo, f, pieces);
+    return hipGetLastError();
+}
+
+// The end of a windowed call from the point where it has enqueued work: record `last` behind it, and report the first error.
+static int finish_window_call(rspt_hip_packer* p, LastCall& last, hipError_t e, hipStream_t st) {
+    const hipError_t er = last.record(st);
+    if (e == hipSuccess) e = er;
+    if (e != hipSuccess) {
+        p->last_hip_error = (int)e;
+        return RSPT_HIP_ERR_LAUNCH;
+    }
+    return RSPT_HIP_OK;
+}
+
+// ---- FIR pre-filter (fir.hip) ----
+template <int BPS>
+static void launch_fir(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st,
+                       const uint8_t* head = nullptr) {
+    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+    if (aligned) hipLaunchKernelGGL((k_fir<BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f, head);
+    else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f, head);
+}
+
+// Stage the head of a carried-state call and write the new state (k_fir_carry, fir.hip); the state: [u64 started][K - 1 rows].
+static hipError_t launch_fir_carry(const WinGeom& f, const void* d_src, uint8_t* head, void* d_state, hipStream_t st) {
+    uint64_t* started = (uint64_t*)d_state;
+    uint8_t* rows = (uint8_t*)d_state + 8;
+    const uint64_t n = (uint64_t)(f.K - 1) * f.stride;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
+    if (n) hipLaunchKernelGGL(k_fir_carry<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
+    hipLaunchKernelGGL(k_fir_carry<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
+    return hipGetLastError();
+}
+
+// Both FIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+static int fir_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size, void* d_state,
+                    void* stream) {
+    if (!kernel || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+    WinGeom f;
+    bool in_place;
+    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, (uint32_t)kernel_size, kFirThreads, kFirR, &f, &in_place, d_state != nullptr)) return rc;
+    if (d_state) nblocks = 1;  // (the geometry's one block of nblocks * ns rows)
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    FirStage& fs = p->fir;
+    const uint64_t pieces = halo_pieces(f, nblocks, in_place);
+    const uint64_t halo_bytes = pieces * (uint64_t)(kernel_size - 1) * f.stride;
+    const uint64_t head_bytes = d_state ? (uint64_t)(kernel_size - 1) * f.stride : 0;
+    if (halo_bytes > fs.halo.cap || head_bytes > fs.head.cap) {
+        fs.wait_all();  // (no earlier call may still read a buffer being replaced)
+        if (halo_bytes > fs.halo.cap && fs.halo.grow(halo_bytes)) return RSPT_HIP_ERR_ALLOC;
+        if (head_bytes > fs.head.cap && fs.head.grow(head_bytes)) return RSPT_HIP_ERR_ALLOC;
+    }
+    // the coefficients: the host waits only when kSlots calls are still ahead on the device
+    FirStage::CoefSlot& cs = fs.slot[fs.next];
+    HIPCHK(p, cs.last.wait());
+    if (cs.cap < kernel_size) {
+        cs.cap = 0;
+        if (hipHostMalloc((void**)cs.host.out(), kernel_size * sizeof(double), hipHostMallocDefault) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        if (hipMalloc(cs.dev.out(), kernel_size * sizeof(double)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        cs.cap = kernel_size;
+    }
+    if (!cs.last.make_event()) return RSPT_HIP_ERR_ALLOC;
+    memcpy(cs.host, kernel, kernel_size * sizeof(double));
+    fs.next = (fs.next + 1) % FirStage::kSlots;
+    // (from here on every path ends in finish_window_call, which records `last`: the copy below reads the page-locked slot)
+    hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_state) e = launch_fir_carry(f, d_src, fs.head, d_state, st);
+    if (e == hipSuccess && pieces) e = launch_halo(f, d_src, fs.halo, pieces, st);
+    if (e == hipSuccess) {
+        const bool aligned = native_aligned(p->g.bps, d_src, d_dst);
+        by_bps(p->g.bps, [&](auto b) {
+            launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, cs.dev, aligned, st,
+                                           head_bytes ? (const uint8_t*)fs.head : nullptr);
+        });
+        e = hipGetLastError();
+    }
+    return finish_window_call(p, cs.last, e, st);
+}
+
+int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                     void* stream) {
+    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, nullptr, stream);
+}
+
+int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) {
+    if (!p || !bytes || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+    *bytes = 8 + (((size_t)(kernel_size - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                                      void* d_state, void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
+}
+
+// ---- rolling median (median.hip) ----
+template <uint32_t N, int BPS, bool HEAD>
+static void launch_med_short(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st, const uint8_t* head) {
+    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+    if (aligned) hipLaunchKernelGGL((k_med_short<N, BPS, (BPS == 4 || BPS == 2), HEAD>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f, head);
+    else hipLaunchKernelGGL((k_med_short<N, BPS, false, HEAD>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f, head);
+}
+
+// k_med_short by its register bucket: the smallest of 4, 8, 16, 32 that holds W.
+template <bool HEAD>
+static hipError_t launch_med_short_w(uint32_t bps, const WinGeom& f, const void* d_src, void* d_dst, const uint8_t* halo, bool aligned, hipStream_t st,
+                                     const uint8_t* head) {
+    const uint32_t W = f.K;
+    by_bps(bps, [&](auto bb) {
+        constexpr int B = decltype(bb)::value;
+        if (W <= 4) launch_med_short<4, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+        else if (W <= 8) launch_med_short<8, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+        else if (W <= 16) launch_med_short<16, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+        else launch_med_short<32, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
+    });
+    return hipGetLastError();
+}
+
+// The generic path on the pairs [pair0, pair0 + npairs) of the batch: sort (tile sort, merge passes), then walk.  STREAM: a pair
+// is a (segment, channel) of a carried-state call and f.ns the segment capacity (median.hip).
+template <int BPS, bool STREAM = false>
+static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const uint8_t* src, uint8_t* dst, uint64_t pair0, uint64_t npairs,
+                                     bool aligned, hipStream_t st, const MedSeg& sg = MedSeg{}) {
+    MedianStage& ms = p->med;
+    const uint32_t ns = f.ns;
+    const uint32_t tiles = (ns + kMedTile - 1) / kMedTile;
+    uint64_t* a = ms.keys_a;
+    uint64_t* b = ms.keys_b;
+    uint32_t* rank = ms.rank;
+    const bool one_tile = tiles == 1;
+    if (aligned) hipLaunchKernelGGL((k_med_tile_sort<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src,
+                                    a, one_tile ? rank : nullptr, f, pair0, sg);
+    else hipLaunchKernelGGL((k_med_tile_sort<BPS, false, STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a,
+                            one_tile ? rank : nullptr, f, pair0, sg);
+    hipError_t e = hipGetLastError();
+    const uint64_t total = npairs * ns;
+    for (uint32_t width = kMedTile; e == hipSuccess && width < ns; width *= 2) {
+        const bool last = (uint64_t)width * 2 >= ns;
+        hipLaunchKernelGGL(k_med_merge, dim3((uint32_t)((total + kMedThreads - 1) / kMedThreads)), dim3(kMedThreads), 0, st, a, b, last ? rank : nullptr, ns,
+                           width, total);
+        e = hipGetLastError();
+        std::swap(a, b);
+    }
+    if (e != hipSuccess) return e;
+    const uint32_t spans = ((STREAM ? sg.L : ns) + kMedSpan - 1) / kMedSpan;
+    const uint32_t n0 = (ns + 31) / 32;
+    const size_t lds = (size_t)(n0 + (n0 + 31) / 32) * sizeof(uint32_t);
+    if (aligned) hipLaunchKernelGGL((k_med_walk<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f,
+                                    pair0, sg);
+    else hipLaunchKernelGGL((k_med_walk<BPS, false, STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0, sg);
+    return hipGetLastError();
+}
+
+// The median stage's buffers for a call: each grows behind the stage's last call, and `last` has its event from here on.
+static int median_reserve(MedianStage& ms, uint64_t halo_bytes, uint64_t head_bytes, uint64_t key_samples) {
+    if (halo_bytes > ms.halo.cap || head_bytes > ms.head.cap || key_samples > ms.key_cap) {
+        ms.last.wait();  // (no earlier call may still use a buffer being replaced)
+        if (halo_bytes > ms.halo.cap && ms.halo.grow(halo_bytes)) return RSPT_HIP_ERR_ALLOC;
+        if (head_bytes > ms.head.cap && ms.head.grow(head_bytes)) return RSPT_HIP_ERR_ALLOC;
+        if (key_samples > ms.key_cap) {
+            ms.key_cap = 0;
+            ms.rank.reset();
+            ms.keys_b.reset();
+            if (hipMalloc(ms.keys_a.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            if (hipMalloc(ms.keys_b.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            if (hipMalloc(ms.rank.out(), key_samples * sizeof(uint32_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+            ms.key_cap = key_samples;
+        }
+    }
+    return ms.last.make_event() ? RSPT_HIP_OK : RSPT_HIP_ERR_ALLOC;
+}
+
+int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) {
+    if (!p || !bytes || window == 0) return RSPT_HIP_ERR_ARG;
+    if (window > kMedShortMax && window - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;
+    *bytes = 8 + (((size_t)(window - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
+    return RSPT_HIP_OK;
+}
+
+// Stage the old state in the handle's head buffer and write the new one (k_med_carry, median.hip): in words where every
+// address and length is a multiple of 4.
+static hipError_t launch_med_carry(const WinGeom& f, const void* d_src, uint8_t* head, void* d_state, uint64_t rows, hipStream_t st) {
+    uint64_t n = (uint64_t)(f.K - 1) * f.stride, call = rows * f.stride;
+    const bool words = reinterpret_cast<uintptr_t>(d_src) % 4 == 0 && f.stride % 4 == 0;
+    if (words) n /= 4, call /= 4;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
+    uint8_t* state = (uint8_t*)d_state;
+    if (words) {
+        hipLaunchKernelGGL((k_med_carry<false, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<true, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
+    } else {
+        hipLaunchKernelGGL((k_med_carry<false, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<true, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
+    }
+    return hipGetLastError();
+}
+
+// The segment capacity S = W - 1 + L of a carried-state call of the generic path: 8 (W - 1) rounded up to 2^16, 2^17 or 2^18 --
+// at most one row in eight is sorted twice up to W - 1 = 2^15, one in two at the limit W - 1 = 2^17 -- and never more than the
+// call needs (one segment of W - 1 + N rows).  2^16 is the channel length the stateless path is measured at:
+// shorter segments save merge passes but pay a bitmap clear and W set bits per 1024 outputs more often than they save.
+static uint32_t median_segment_rows(uint32_t W, uint64_t rows) {
+    const uint64_t want = 8ull * (W - 1);
+    const uint64_t S = want <= (1u << 16) ? (1u << 16) : want <= (1u << 17) ? (1u << 17) : kMedMaxRanks;
+    return (uint32_t)std::min<uint64_t>(S, (uint64_t)(W - 1) + rows);
+}
+
+// Both median entries: d_state == NULL is the stateless call on nblocks blocks, where a window of ns or more is the expanding
+// median of the channel; else the blocks are one run behind the state, and the window is the recording's (not clamped to ns).
+static int median_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
+    if (!p || window == 0) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    const uint32_t W = (uint32_t)std::min<size_t>(window, d_state ? (size_t)kMedMaxCarry + 2 : g.ns);
+    WinGeom f;
+    bool in_place;
+    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, W, kMedThreads, kMedRun, &f, &in_place, d_state != nullptr)) return rc;
+    const bool is_short = W <= kMedShortMax;
+    // (the generic path's bitmaps live in LDS; with a state, at least half of every segment is new rows)
+    if (!is_short && (d_state ? W - 1 > kMedMaxCarry : g.ns > kMedMaxRanks)) return RSPT_HIP_ERR_UNSUPPORTED;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t rows = (uint64_t)nblocks * g.ns;  // (with a state below 2^31 - 2^17: window_call_checks)
+    if (W == 1) {  // a copy, sample width kept; a state is its header and stays zero
+        if (in_place) return RSPT_HIP_OK;
+        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, rows * f.stride, hipMemcpyDeviceToDevice, st));
+        return RSPT_HIP_OK;
+    }
+    MedianStage& ms = p->med;
+    const uint32_t bps = g.bps;
+    const bool aligned = native_aligned(bps, d_src, d_dst);
+    // buffers: the short path's halo, a state's staged copy, the generic path's keys and ranks
+    const uint64_t pieces = is_short ? halo_pieces(f, d_state ? 1 : nblocks, in_place) : 0;
+    const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
+    const uint64_t head_bytes = d_state ? 8 + (uint64_t)(W - 1) * f.stride : 0;
+    // generic: (block, channel) items of ns keys -- with a state (segment, channel) items of S keys -- in pieces of up to 2^25 keys
+    MedSeg sg{};
+    WinGeom fg = f;
+    uint64_t items = (uint64_t)nblocks * g.nch, piece_items = 0;
+    if (!is_short) {
+        if (d_state) {
+            fg.ns = median_segment_rows(W, rows);
+            sg.L = fg.ns - (W - 1);
+            sg.nseg = (uint32_t)((rows + sg.L - 1) / sg.L);
+            sg.N = (uint32_t)rows;
+            items = (uint64_t)sg.nseg * g.nch;
+        }
+        piece_items = std::min<uint64_t>(items, std::max<uint64_t>(1, (1ull << 25) / fg.ns));
+    }
+    if (int rc = median_reserve(ms, halo_bytes, head_bytes, piece_items * fg.ns)) return rc;
+    hipError_t e = hipSuccess;
+    if (d_state) {  // the new state is written from d_src before any kernel stores to d_dst
+        sg.head = ms.head;
+        e = launch_med_carry(f, d_src, ms.head, d_state, rows, st);
+    }
+    if (is_short) {
+        const uint8_t* halo = pieces ? (const uint8_t*)ms.halo : nullptr;
+        if (e == hipSuccess && pieces) e = launch_halo(f, d_src, ms.halo, pieces, st);
+        if (e == hipSuccess)
+            e = d_state ? launch_med_short_w<true>(bps, f, d_src, d_dst, halo, aligned, st, ms.head)
+                        : launch_med_short_w<false>(bps, f, d_src, d_dst, halo, aligned, st, nullptr);
+    } else {
+        // (with a state from the last segment to the first: a walk writes its segment's new rows, which no segment sorted later reads)
+        for (uint64_t item0 = 0; e == hipSuccess && item0 < items; item0 += piece_items) {
+            const uint64_t ni = std::min(piece_items, items - item0);
+            e = by_bps(bps, [&](auto bb) {
+                constexpr int B = decltype(bb)::value;
+                return d_state ? launch_med_generic<B, true>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, aligned, st, sg)
+                               : launch_med_generic<B>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, aligned, st);
+            });
+        }
+    }
+    return finish_window_call(p, ms.last, e, st);
+}
+
+int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream) {
+    return median_call(p, d_src, d_dst, nblocks, window, nullptr, stream);
+}
+
+int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return median_call(p, d_src, d_dst, nblocks, window, d_state, stream);
+}
+
+// ---- PRDN: the quality figure of the reference's harness (quality.hip) -----------------------------------------------------------
+// The decomposition of the two streaming passes for the widest load the buffers' alignment allows.
+static QGeom quality_geom(const rspt_hip_packer* p, size_t nblocks, int W) {
+    const Geom& g = p->g;
+    QGeom q{};
+    q.block_bytes = g.block_bytes;
+    q.nch = g.nch, q.ns = g.ns, q.be = g.be;
+    const uint32_t nw = W == 0 ? 1u : (g.bps == 3 ? 3u : 1u) * (uint32_t)W;
+    const uint32_t vs = W == 0 ? 1u : nw * 4u / g.bps;  // samples of a load group
+    uint32_t a = g.nch, b = vs;
+    while (b) {
+        const uint32_t t = a % b;
+        a = b, b = t;
+    }
+    q.rows = vs / a;  // the fewest rows that hold whole groups
+    const uint64_t qps = (uint64_t)q.rows * g.nch / vs;
+    q.qps = (uint32_t)qps;
+    q.nsub = qps < kQThreads ? kQThreads / q.qps : 1u;
+    q.ncg = (uint32_t)((qps + kQThreads - 1) / kQThreads);
+    q.nsr = g.ns / q.rows;
+    const uint64_t sweeps = ((uint64_t)q.nsr + q.nsub - 1) / q.nsub;
+    // workgroups: about 4096 in all where the blocks are long enough to give each at least 8 sweeps
+    uint64_t nsplit = std::min<uint64_t>(std::max<uint64_t>(1, sweeps / 8), (4096 + nblocks * q.ncg - 1) / (nblocks * q.ncg));
+    q.span = (uint32_t)std::max<uint64_t>(1, (sweeps + nsplit - 1) / nsplit) * q.nsub;
+    q.nsplit = (uint32_t)std::max<uint64_t>(1, ((uint64_t)q.nsr + q.span - 1) / q.span);
+    return q;
+}
+
+int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, double* d_prdn, double* d_mse, double* d_ref,
+                            uint32_t* d_path, void* stream) {
+    if (!p || !d_orig || !d_dec || !d_prdn || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    const Geom& g = p->g;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_orig), d0 = reinterpret_cast<uintptr_t>(d_dec);
+    auto aligned = [&](uintptr_t m) { return o0 % m == 0 && d0 % m == 0 && (nblocks == 1 || g.block_bytes % m == 0); };
+    const int W = aligned(16) ? 4 : aligned(4) ? 1 : 0;
+    QGeom q = quality_geom(p, nblocks, W);
+    q.aligned4 = aligned(4) ? 1u : 0u;
+    const uint64_t units = (uint64_t)nblocks * q.ncg * q.nsplit;
+    if (units >= (1ull << 31) || (uint64_t)q.rows * g.nch >= (1ull << 32)) return RSPT_HIP_ERR_UNSUPPORTED;
+    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t B = (uint32_t)nblocks;
+    unsigned long long* sums = p->ws.quality;
+    unsigned long long* acc = sums + (size_t)B * g.nch;
+    uint32_t* flag = reinterpret_cast<uint32_t*>(acc + (size_t)B * 4);
+    HIPCHK(p, hipMemsetAsync(sums, 0, ((size_t)B * g.nch + (size_t)B * 4) * sizeof(unsigned long long), st));
+    const uint8_t* o = (const uint8_t*)d_orig;
+    const uint8_t* d = (const uint8_t*)d_dec;
+    by_bps(g.bps, [&](auto bb) {
+        constexpr int BPS = decltype(bb)::value;
+        auto go = [&](auto ww) {
+            constexpr int WW = decltype(ww)::value;
+            hipLaunchKernelGGL((k_q_sums<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, q, sums);
+            hipLaunchKernelGGL((k_q_accum<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, acc);
+        };
+        if (W == 4) go(std::integral_constant<int, 4>());
+        else if (W == 1) go(std::integral_constant<int, 1>());
+        else go(std::integral_constant<int, 0>());
+        hipLaunchKernelGGL(k_q_finish, dim3((B + 255) / 256), dim3(256), 0, st, (const unsigned long long*)acc, B, flag, d_prdn, d_mse, d_ref, d_path);
+        hipLaunchKernelGGL(k_q_seq<BPS>, dim3(B), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, (const unsigned long long*)acc,
+                           (const uint32_t*)flag, d_prdn, d_mse, d_ref);
+    });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+// ---- native <-> planar int32 (the reference's convert_native_to_i32 / convert_i32_to_native, utils.cpp:51-191) -------------------
+// The checks of both entries.  Nothing of the handle but its shape and byte order is used: no workspace, no allocation.
+static int convert_checks(const rspt_hip_packer* p, const void* d_native, const void* d_planar, size_t nblocks) {
+    if (!p || !d_native || !d_planar || nblocks > 65535 || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;  // (65535: grid.z, as rspt_hip_reserve)
+    const Geom& g = p->g;
+    const uintptr_t n0 = reinterpret_cast<uintptr_t>(d_native), p0 = reinterpret_cast<uintptr_t>(d_planar);
+    if (p0 & 3u) return RSPT_HIP_ERR_ARG;
+    const uint64_t nbytes = (uint64_t)nblocks * g.block_bytes, pbytes = (uint64_t)nblocks * g.N * sizeof(int32_t);
+    if (n0 < p0 + pbytes && p0 < n0 + nbytes) return RSPT_HIP_ERR_ARG;  // the two buffers overlap
+    return RSPT_HIP_OK;
+}
+
+// Narrow handles with a 16-byte aligned native buffer take the tile kernels of the packers' own front end and inverse; wide ones,
+// and native buffers at any other address, the 64 x 64 transposes k_wide_planar / k_wide_native.
+static bool convert_i32x4_ok(const Geom& g, const void* d_planar) {
+    return g.bps == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_planar) & 15) == 0;
+}
+
+int rspt_hip_native_to_i32_batch_dev(rspt_hip_packer* p, const void* d_native, int32_t* d_planar, size_t nblocks, void* stream) {
+    if (int rc = convert_checks(p, d_native, d_planar, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    const Geom& g = p->g;
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* src = (const uint8_t*)d_native;
+    const unsigned B = (unsigned)nblocks;
+    if (!p->wide && (reinterpret_cast<uintptr_t>(d_native) & 15) == 0) {
+        if (convert_i32x4_ok(g, d_planar)) {
+            const uint32_t T4 = tile_i32x4(g);
+            hipLaunchKernelGGL(k_tile_planar_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, src, g, T4, d_planar,
+                               (long long*)nullptr);
+        } else {
+            by_bps(g.bps, [&](auto bps) {
+                constexpr int BPS = decltype(bps)::value;
+                if (!p->conv_lds_raised) {  // (once per handle: a handle has one sample width)
+                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_planar<BPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->in_lds) != hipSuccess) return;
+                    p->conv_lds_raised = true;
+                }
+                hipLaunchKernelGGL((k_tile_planar<BPS>), dim3((g.ns + p->T - 1) / p->T, B), dim3(256), p->in_lds, st, src, g, p->T, d_planar);
+            });
+        }
+    } else {
+        by_bps(g.bps, [&](auto bps) {
+            hipLaunchKernelGGL(k_wide_planar<decltype(bps)::value>, dim3((g.ns + 63) / 64, (g.nch + 63) / 64, B), dim3(256), 0, st, src, g, d_planar);
+        });
+    }
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_i32_to_native_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, void* d_native, size_t nblocks, void* stream) {
+    if (int rc = convert_checks(p, d_native, d_planar, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    const Geom& g = p->g;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* dst = (uint8_t*)d_native;
+    const unsigned B = (unsigned)nblocks;
+    // k_planar_native divides per element and stores int8 / int16 / int24 byte by byte: it keeps only the handles of fewer than 32
+    // channels, where more than half of k_wide_native's 64-channel tile would be empty.
+    const bool narrow = !p->wide && p->Tn_native && (reinterpret_cast<uintptr_t>(d_native) & 15) == 0;
+    if (narrow && (convert_i32x4_ok(g, d_planar) || g.nch < 32)) {
+        if (convert_i32x4_ok(g, d_planar)) {
+            const uint32_t T4 = tile_i32x4(g);
+            hipLaunchKernelGGL(k_planar_native_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, d_planar, g, T4, dst);
+        } else {
+            const uint32_t T = min(p->Tn_native, g.ns);
+            by_bps(g.bps, [&](auto bps) {
+                hipLaunchKernelGGL((k_planar_native<decltype(bps)::value>), dim3((g.ns + T - 1) / T, B), dim3(256), g.nch * (T + 1) * 4, st, d_planar, g, T,
+                                   dst);
+            });
+        }
+    } else {
+        by_bps(g.bps, [&](auto bps) { launch_wide_native<decltype(bps)::value>(g, d_planar, dst, B, st); });
+    }
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff_low, double cutoff_high, double* num, double* den,
+                        size_t* nr_coefficients) {
+    if (!num || !den || !nr_coefficients) return RSPT_HIP_ERR_ARG;
+    double n[5], d[5];
+    const int nc = design_iir(type, order, sampling_rate, cutoff_low, cutoff_high, n, d);
+    if (nc == 0) return RSPT_HIP_ERR_ARG;
+    for (int i = 0; i < nc; ++i) {
+        num[i] = n[i];
+        den[i] = d[i];
+    }
+    *nr_coefficients = (size_t)nc;
+    return RSPT_HIP_OK;
+}
+
+// ---- R-peak detectors (peak.hip) ----
+// The checks both peak entries make, and the kernel arguments from them (all of PeakOffArgs but its workspace): false where
+// either entry refuses the call.
+static bool peak_args(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, void* d_state, uint32_t* d_count,
+                      int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, PeakArgs& a) {
+    if (!p || !d_src || !d_count || !batch_count_ok(p, nblocks)) return false;
+    if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return false;
+    if (max_peaks > 0 && (!d_index || !d_value)) return false;
+    if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return false;
+    const Geom& g = p->g;
+    a.src = (const uint8_t*)d_src;
+    a.block_bytes = g.block_bytes;
+    a.stride = g.nch * g.bps;
+    a.nch = g.nch;
+    a.ns = g.ns;
+    a.nblocks = (uint32_t)nblocks;
+    a.lanes = d_state ? g.nch : (uint32_t)(nblocks * g.nch);
+    a.state = (uint8_t*)d_state;
+    a.count = d_count;
+    a.index = d_index;
+    a.value = d_value;
+    a.max_peaks = max_peaks;
+    a.sig = d_sig;
+    a.thr = d_threshold;
+    return true;
+}
+
+// A variant's three filters as the detector's constructor designs them (create_filter_iir(f.d, f.n, ...): numerator -> d), and
+// its constants.  (Every design is valid for fs > 0.)
+static bool peak_coef(int variant, double sampling_rate, double marker_val, PeakCoef& c) {
+    static const struct { int bp_order; double bp_lo, bp_hi; int ig_order; double A; } kVar[3] = {
+        {2, 10.0, 20.0, 2, 25.0}, {1, 10.0, 20.0, 1, 25.0}, {1, 15.0, 25.0, 1, 70.0}};
+    const auto& v = kVar[variant];
+    if (!design_iir(kFiltBandPass, v.bp_order, sampling_rate, v.bp_lo, v.bp_hi, c.bf, c.bb) ||
+        !design_iir(kFiltLowPass, v.ig_order, sampling_rate, 3.0, 0.0, c.gf, c.gb) ||
+        !design_iir(kFiltLowPass, 2, sampling_rate, 0.15, 0.0, c.tf, c.tb))
+        return false;
+    c.atten = 1.0 / (1.0 + v.A / sampling_rate);
+    c.marker = marker_val;
+    c.nslope = (int32_t)((100.0 * sampling_rate) / 1000.0);
+    c.hist = 4 * (int32_t)sampling_rate;
+    return true;
+}
+
+// One lane per detector, 64 to a workgroup, on the caller's stream.
+template <class Args, class Coef>
+static int peak_launch(rspt_hip_packer* p, void (*kern)(Args, Coef), const Args& a, const Coef& c, void* stream) {
+    HIPCHK(p, hipSetDevice(p->device));
+    hipLaunchKernelGGL(kern, dim3((a.lanes + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, c);
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_peak_state_bytes(rspt_hip_packer* p, size_t* bytes) {
+    if (!p || !bytes) return RSPT_HIP_ERR_ARG;
+    *bytes = (size_t)p->g.nch * kPeakStateBytesPerChannel;
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
+                                   void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
+                                   double* d_threshold, void* stream) {
+    PeakArgs a{};
+    PeakCoef c{};
+    if (variant < kPeakOnline || variant > kPeakOfflineFw ||
+        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
+        !peak_coef(variant, sampling_rate, marker_val, c))
+        return RSPT_HIP_ERR_ARG;
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    return by_bps(p->g.bps, [&](auto bb) {
+        constexpr int B = decltype(bb)::value;
+        auto go = [&](auto vv) {
+            constexpr int V = decltype(vv)::value;
+            return peak_launch(p, d_sig ? &k_peak<B, V, true> : &k_peak<B, V, false>, a, c, stream);
+        };
+        if (variant == kPeakOnline) return go(std::integral_constant<int, kPeakOnline>());
+        if (variant == kPeakOnline1st) return go(std::integral_constant<int, kPeakOnline1st>());
+        return go(std::integral_constant<int, kPeakOfflineFw>());
+    });
+}
+
+int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int stateful, size_t* bytes) {
+    if (!p || !bytes || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    const uint64_t lanes = stateful ? g.nch : (uint64_t)nblocks * g.nch;
+    *bytes = (size_t)(((lanes + 63) / 64) * kPeakOffSlabBytesPerSample * g.ns);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
+                                           void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
+                                           size_t max_peaks, double* d_sig, double* d_threshold, void* stream) {
+    PeakOffArgs a{};
+    PeakOffCoef k{};
+    if (!d_work || ((uintptr_t)d_work % 8) != 0 ||
+        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
+        !peak_coef(kPeakOfflineFw, sampling_rate, marker_val, k.c))
+        return RSPT_HIP_ERR_ARG;
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    // the reference's undefined cases: nr_slope_samples 0 (the shift runs every event off the end of the array) and a block
+    // shorter than the relocation radius (the unsigned bound len - radius wraps)
+    k.radius = (int32_t)((10.0 * sampling_rate) / 1000.0);
+    if (k.c.nslope == 0 || (uint64_t)a.ns < (uint64_t)k.radius) return RSPT_HIP_ERR_ARG;
+    // peak_detector_offline's constructor adds the baseline: a 0.5 Hz first-order low-pass
+    if (!design_iir(kFiltLowPass, 1, sampling_rate, 0.5, 0.0, k.lf, k.lb)) return RSPT_HIP_ERR_ARG;
+    a.work = (uint8_t*)d_work;
+    return by_bps(p->g.bps, [&](auto bb) {
+        constexpr int B = decltype(bb)::value;
+        return peak_launch(p, d_sig ? &k_peak_offline<B, true> : &k_peak_offline<B, false>, a, k, stream);
+    });
+}

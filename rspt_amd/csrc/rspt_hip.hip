@@ -1,10 +1,12 @@
-// rspt_hip.cpp -- C ABI (include/rspt_hip.h) over the gfx950 kernels.
+// rspt_hip.hip -- C ABI (include/rspt_hip.h) over the gfx950 kernels: the one translation unit of the unity build.
 //
 // One handle = one reference packer instance: it owns the device workspace
 // (what enc_/serialized_ are in signal_packer_base.h:20-21), one HIP stream and
 // the persistent nr_bytes_to_compress_ state (signal_packer_xdelta_hzr.cpp:39,66),
 // which lives in device memory so that batches chain without a host round trip.
 // There is no CPU path: every entry point fails loudly if the device is missing.
+// Here: create / reserve / destroy, the compress phases, the decoder, the single-block entries.  Included at the end: host_pipeline.hip
+// (compress_many / decompress_many / feed), host_gather.hip (RCCL), host_stages.hip (IIR, FIR, median, peak, PRDN, converters).
 #include "../../include/rspt_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -41,6 +43,8 @@
 #include "bytes.hip"
 
 using namespace rspt;
+
+#include "host_handle.hpp"
 
 namespace {
 
@@ -111,286 +115,7 @@ void make_crc_consts(CrcConsts& cc) {
 
 static_assert(kKindBytes == (uint32_t)RSPT_HIP_KIND_BYTES, "common.hpp and rspt_hip.h name the same kind");
 
-enum Stage { ST_PRE = 0, ST_NB, ST_HIST, ST_TREE, ST_LAYOUT, ST_ENCODE, ST_COUNT };
-const char* kStageNames[ST_COUNT] = {"preprocess", "nb_scan", "hzr_hist", "hzr_tree", "layout", "hzr_encode"};
-
 }  // namespace
-
-// ---- owners of HIP resources: move-only, each releases what it holds when destroyed or reset, and nothing when empty ----
-template <class T, auto Release>
-class Owned {
-  public:
-    Owned() = default;
-    Owned(Owned&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
-    Owned& operator=(Owned&& o) noexcept {
-        if (this != &o) {
-            reset();
-            h_ = o.h_;
-            o.h_ = nullptr;
-        }
-        return *this;
-    }
-    ~Owned() { reset(); }
-    void reset() {
-        if (h_) Release(h_);
-        h_ = nullptr;
-    }
-    T* out() {  // for the HIP call that creates the resource
-        reset();
-        return &h_;
-    }
-    operator T() const { return h_; }
-
-  private:
-    T h_ = nullptr;
-};
-template <class T> using Dev = Owned<T*, hipFree>;          // device memory
-template <class T> using Pinned = Owned<T*, hipHostFree>;   // page-locked host memory
-using Event = Owned<hipEvent_t, hipEventDestroy>;
-using Stream = Owned<hipStream_t, hipStreamDestroy>;
-
-// Everything rspt_hip_reserve() sizes; replacing it releases the old workspace as a whole.
-struct Workspace {
-    size_t cap_blocks = 0;
-    size_t cap_slots = 0;     // block slots of four planes each: cap_blocks, or a quarter of it for a bare-stream handle (one plane per buffer)
-    Dev<uint8_t> planes;      // [slots][4][plane_stride]
-    Dev<int32_t> planar;      // [cap][N] (transform packers, decode)
-    Dev<uint32_t> nbuse;      // [cap]
-    Dev<uint32_t> dec_nb;     // [cap] decode: planes of each stream (container index entry, else nb_state)
-    Dev<uint32_t> big_list;   // [cap*4*nblk] hzr blocks for the workgroup-per-block encoder (filled by k_layout)
-    Dev<uint32_t> staging;    // [cap*4*nblk][kStageSlotWords] header + payload of the small hzr blocks (k_tree -> k_encode), 3088 bytes each
-    // The per-call zero region [nzflag | needmask | work counters | row sums] exists twice: while a call works in one copy its
-    // k_tree zeroes the other for the next call (one store per thread) -- the memset in front of every call was a 9 us launch.
-    Dev<uint32_t> zbuf[2];
-    size_t zcap_words = 0;
-    bool zero_ready[2] = {false, false};  // the copy is known to be all zero
-    int zset = 0;                          // the copy the next call works in
-    // Clean-block invariant (k_tile_stream's skipped stores): between calls, hzr block j of plane k of block slot b holds
-    // zeros everywhere unless its bit in plane_dirty is set (128 bits per plane, bit = j >> dirty_shift).  The streaming
-    // front end writes only the 128-byte lines that hold a non-zero byte into a clean block; k_layout sets the bits of
-    // the blocks in which data stays behind, and the encoders wipe the non-zero granules of all others right after
-    // reading them (light blocks only: block_is_wiped).
-    Dev<uint32_t> plane_dirty;  // [cap*4][4]
-    bool planes_unknown = false;  // something else (decompress, a diagnostic run) wrote the planes: flag them all
-    Dev<uint32_t> hist;      // [cap*4*nblk][264]
-    Dev<uint32_t> seghist;   // [cap*4*nblk][16][264] u16: tokens ending in each 4 KiB segment (k_hist -> k_tree)
-    Dev<uint32_t> segbase;   // [cap*4*nblk][16] stream bit at which each segment's tokens start (k_tree -> k_encode)
-    Dev<uint32_t> lists;     // [cap*4*nblk][16][kListCap] (position << 9 | value) entries of the sparse segments (k_hist -> k_encode)
-    Dev<uint2> listinfo;     // [cap*4*nblk][16] {entries or kListNone, position behind the last literal before the segment}
-    Dev<uint32_t> cw;        // [cap*4*nblk][264] code | length << 24 per symbol
-    Dev<uint32_t> tdesc;     // [..][92]
-    Dev<BlockMeta> meta;     // [..]
-    Dev<uint64_t> out_off;   // [..]
-    Dev<uint8_t> means;      // [cap][hdr_len]
-    Dev<int32_t> planar2;    // [cap][N] second int32 buffer (dct output / idct output)
-    Dev<uint32_t> txor;      // [cap][ntile] decode scans
-    Dev<uint32_t> tsum;      // [cap][ntile]
-    Dev<uint32_t> rowrec;    // [cap][N / 256][kRowRec] row tile records of the int32 decode path (k_inv_rows)
-    Dev<uint64_t> blk_off;   // [cap*4*nblk] decode: hzr block offsets inside each stream
-    Dev<double2> fft_scratch;  // [fft_bpp][nch][n] (dct beyond the dense table)
-    size_t fft_bpp = 0;        // blocks per pass (bounds the scratch to ~1 GiB)
-    Dev<int32_t> mean_i32;     // [cap][nch]
-    // rspt_hip_prdn_batch_dev: [cap][nch] int64 channel sums | [cap][4] per-block accumulators | [cap] u32 flags, each part placed
-    // per call right behind the one before it (the first two are zeroed by one memset in front of the call's kernels)
-    Dev<unsigned long long> quality;
-};
-
-// rspt_hip_compress / rspt_hip_decompress: one block staged on the device
-struct HostStaging {
-    Dev<uint8_t> src;
-    Dev<uint8_t> dst;
-    Dev<uint64_t> size;
-    size_t dst_cap = 0;
-};
-
-// One group of blocks in flight between the host and the device: up, compress (or decompress), down.
-struct Slot {
-    Dev<uint8_t> d_src;
-    Dev<uint8_t> d_dst;
-    Dev<uint64_t> d_sizes;
-    Pinned<uint64_t> h_sizes;  // [n] stream lengths + [1] the nb_state behind the group (the feed)
-    Event ev_up, ev_comp, ev_down;
-};
-
-// rspt_hip_compress_many / rspt_hip_decompress_many: two slots of a chunk of blocks each
-struct ManyStaging {
-    size_t chunk = 0, stride = 0;
-    Slot slot[2];
-    Dev<uint64_t> idx[2];  // [4 + 2 x chunk] a container header + index over a slot's streams (decompress_many with src_len)
-    Pinned<uint64_t> hidx;  // 2 x (4 + 2 x chunk)
-};
-
-// rspt_hip_feed_*: a ring of block groups in flight
-struct FeedSlot : Slot {
-    enum State { FREE, FILLING, COMPRESSING, DOWNLOADING, DONE } state = FREE;
-    std::vector<void*> dst_host;
-    std::vector<size_t> dst_cap;
-    size_t count = 0, delivered = 0, first_seq = 0;
-    int error = 0;  // the group's launch failed: every block of it is reported with this status
-};
-struct Feed {
-    size_t G = 0, stride = 0;
-    std::vector<FeedSlot> slots;
-    size_t head = 0, tail = 0;  // ring positions: oldest slot not yet FREE; the slot being filled / filled next
-    size_t next_seq = 0;
-};
-
-// rspt_hip_gather_post_*: two slots of sizes (device + page-locked host) and events, on a gather stream of their own
-struct LagGather {
-    Stream stream;
-    Dev<uint64_t> dtotals[2];
-    Pinned<uint64_t> htotals[2];
-    Event ev_in[2], ev_sizes[2], ev_payload[2];
-    bool posted[2] = {false, false};
-    int world = 0;
-};
-
-// The last call of a windowed stage (FIR, median) that uses a set of the handle's buffers: `done` is recorded behind the call's
-// kernels on the caller's stream, and the buffers are refilled, replaced or released only once the device is past it.
-struct LastCall {
-    Event done;  // made by the first call
-    bool used = false;
-    bool make_event() { return done || hipEventCreateWithFlags(done.out(), hipEventDisableTiming) == hipSuccess; }
-    hipError_t wait() const { return used ? hipEventSynchronize(done) : hipSuccess; }
-    // (a failed record leaves nothing to wait on later: the device gets past the buffers now)
-    hipError_t record(hipStream_t st) {
-        const hipError_t e = hipEventRecord(done, st);
-        if (e != hipSuccess) hipStreamSynchronize(st);
-        used = e == hipSuccess;
-        return e;
-    }
-};
-
-// rspt_hip_fir_prefilter_batch_dev: the coefficients of the last kSlots calls (the caller's array may go as soon as a call
-// returns, so each call copies it into page-locked memory and from there, on the call's stream, to the device), and the halo
-// rows of an in-place call.  A slot is refilled only once its last call is past it; the halo is replaced, and the handle
-// destroyed, only once the calls of all slots are.  rspt_hip_fir_prefilter_stream_dev adds `head`, the staged K - 1 rows in front
-// of a carried-state call, under the same rule.
-struct FirStage {
-    static constexpr int kSlots = 4;
-    struct CoefSlot {
-        Pinned<double> host;
-        Dev<double> dev;
-        size_t cap = 0;
-        LastCall last;
-    };
-    CoefSlot slot[kSlots];
-    int next = 0;
-    Dev<uint8_t> halo, head;
-    size_t halo_cap = 0, head_cap = 0;
-    void wait_all() {
-        for (CoefSlot& s : slot) s.last.wait();
-    }
-};
-
-// rspt_hip_median_filter_batch_dev: the halo rows of an in-place short-window call, and the sort buffers of the generic path
-// (two key buffers and the ranks of one piece of the batch), all behind the stage's last call.
-// rspt_hip_median_filter_stream_dev adds `head`, the staged copy of a carried-state call's old state, under the same rule.
-struct MedianStage {
-    Dev<uint8_t> halo, head;
-    size_t halo_cap = 0, head_cap = 0;
-    Dev<uint64_t> keys_a, keys_b;
-    Dev<uint32_t> rank;
-    size_t key_cap = 0;  // samples of each of the three
-    LastCall last;
-};
-
-// The members are constructed in the order they are declared and released in the reverse order (rspt_hip_packer_destroy).
-struct rspt_hip_packer {
-    Geom g{};
-    int device = 0;
-    int last_hip_error = 0;
-    unsigned nb_ctor = 0;
-    unsigned nb_host = 0;  // last value of the device nb_state the host has seen (a lower bound: nb only grows)
-    int num_cu = 256;
-    uint32_t dirty_shift = 0;  // (Workspace::plane_dirty)
-    // dct (signal_packer_dct.cpp:60-74)
-    double dct_scale0 = 0, dct_scale1 = 0, idct_scale = 0;
-    float dct_cs0 = 0;
-    // dct beyond the dense table: fp64 FFT path (transforms.hip: k_dctfft_*)
-    bool dct_fft = false;
-    uint32_t fft_l1 = 0, fft_l2 = 0;   // n = 2^(l1+l2)
-    bool dct_real = false;             // forward transform through the real-input FFT (n >= 256)
-    uint32_t fftr_la = 0, fftr_lb = 0; // n/2 = 2^(la+lb)
-    uint32_t ntile = 0;
-    uint32_t Tn_native = 0;  // tile of k_planar_native; 0: one row of all channels does not fit its LDS (more than 8192 channels) -> k_wide_native
-    // tile geometry for the front end
-    uint32_t T = 0, in_lds = 0;  // k_tile_planar: tile staged in LDS
-    uint32_t Tp[5] = {0, 0, 0, 0, 0};  // k_tile_planes: tile length when kcount planes are staged: rows [kcount*nch][Tp+16] + nz flags
-    bool wide = false;          // more channels than a 16-sample tile of the front-end kernels holds in LDS: k_wide_planar + k_planar_planes
-    uint32_t k1_threads = 256;  // workgroup size of k_tile_planes (RSPT_K1_THREADS)
-    uint32_t k1_grid = 0;       // workgroups of k_tile_planes; 0 = by LDS footprint (RSPT_K1_GRID, tuning knob)
-    uint32_t hist_grid = 0;     // workgroups of the persistent k_hist / k_encode; 0 = two per CU (a CU's wave slots: one batch at a time)
-    uint32_t enc_grid = 0;
-    uint32_t ablate = 0;  // RSPT_ABLATE (diagnostic builds only; the product kernels ignore it): timing probes
-    uint32_t psel = 0;    // RSPT_PLANESEL (diagnostic builds only): which planes the hzr kernels take; bit 8 / 9: stop behind k_hist / k_tree
-    int verify = 0;       // decompress checks the block CRCs (rspt_hip_set_verify)
-    int big_endian = 0;   // samples arrive / leave with their bytes reversed (rspt_hip_set_byte_order)
-    bool profiling = false;
-    bool ev_valid = false;
-    bool conv_lds_raised = false;  // rspt_hip_native_to_i32_batch_dev has raised k_tile_planar's dynamic LDS limit
-
-    // ---- per-handle constants (rspt_hip_packer_create) ----
-    Stream stream;
-    Event ev[ST_COUNT + 1];  // profiling
-    Dev<unsigned long long> stamps;  // diagnostic s_memtime stamps: [512 hzr blocks][16 waves][8]
-    Dev<CrcConsts> crc;
-    Dev<uint32_t> nb_state;  // [4] persistent: [0] = nb; [2] = work counter of the decoder's persistent grid (zeroed by k_dec_frame)
-    // dct: COS[x][i] and its transpose, built on the host like the reference ctor; beyond the dense table the FFT twiddles
-    Dev<float> cos_tab, cos_tab_t;
-    Dev<double2> fft_tw;    // [n] (cos, sin)(2 pi t / n)
-    Dev<double2> fft_post;  // [n] (cos, sin)(pi k / 2n)
-    // the copy streams of the many-block pipeline and the feed, made by whichever of them comes first
-    Stream m_up, m_down;
-
-    // ---- the workspace, and the views into its per-call zero region (set by every compress call) ----
-    Workspace ws;
-    uint32_t* nzflag = nullptr;    // view: [cap*4*nblk] set by the front end when an hzr block holds a non-zero byte (= zbuf[set of the last call])
-    uint32_t* needmask = nullptr;  // view: [cap]
-    uint32_t* work_ctr = nullptr;  // view: [16] work counter of the persistent k_hist at 0, the WorkQueues of k_encode from 4 (zeroed per call)
-    long long* row_sum = nullptr;  // view: [blocks][nch] channel sums taken by the de-interleave pass (dct at large ns)
-    bool have_row_sum = false;     // this call's front end filled row_sum
-
-    // ---- host API staging ----
-    HostStaging stage;
-    ManyStaging many;
-    std::unique_ptr<Feed> feed;  // open between rspt_hip_feed_begin and rspt_hip_feed_end
-
-    // ---- FIR pre-filter stage ----
-    FirStage fir;
-
-    // ---- rolling median stage ----
-    MedianStage med;
-
-    // ---- gather state ----
-    Dev<uint64_t> gat_totals;  // [gat_world]: container lengths of all ranks (rspt_hip_gather_containers)
-    int gat_world = 0;
-    LagGather lag;
-};
-
-#define HIPCHK(p, call)                         \
-    do {                                        \
-        hipError_t e_ = (call);                 \
-        if (e_ != hipSuccess) {                 \
-            (p)->last_hip_error = (int)e_;      \
-            return RSPT_HIP_ERR_LAUNCH;         \
-        }                                       \
-    } while (0)
-
-static void stamp(rspt_hip_packer* p, int i, hipStream_t st) {
-    if (p->profiling) hipEventRecord(p->ev[i], st);
-}
-
-// f(std::integral_constant<int, BPS>()) for the handle's sample width
-template <class F>
-static auto by_bps(uint32_t bps, F&& f) {
-    switch (bps) {
-        case 1: return f(std::integral_constant<int, 1>());
-        case 2: return f(std::integral_constant<int, 2>());
-        case 3: return f(std::integral_constant<int, 3>());
-        default: return f(std::integral_constant<int, 4>());
-    }
-}
 
 // tile of k_tile_planar_i32x4 / k_planar_native_i32x4: T4 samples x nch channels in at most 32 KiB of LDS (four workgroups
 // per CU), T4 a multiple of 4
@@ -548,177 +273,9 @@ static void launch_fixup(rspt_hip_packer* p, const uint8_t* d_src, size_t nblock
     launch_planes<BPS, true>(p, d_src, nblocks, np, 4 - np, p->ws.nbuse, st);
 }
 
-
-template <int BPS, int NC>
-static void launch_iir(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCoef& c, int per_channel, hipStream_t st) {
-    const Geom& g = p->g;
-    if (g.ns >= kIirChunk && c.init_steps >= NC - 1) {  // the pipelined form: recurrence, feed-forward sums and stores on waves of their own
-        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;  // (block_bytes is a multiple of BPS)
-        if (per_channel) {
-            const uint32_t units = B * g.nch;
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((units + 63) / 64), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, 64u, (IirCarry*)nullptr); };
-            if (al) go(&k_iir_pipe<BPS, NC, false, (BPS == 4 || BPS == 2)>);
-            else go(&k_iir_pipe<BPS, NC, false, false>);
-        } else {
-            // shared mode: lane <-> block; few lanes per workgroup so that the blocks' scattered accesses spread over the CUs
-            uint32_t lpw = (B + (uint32_t)p->num_cu - 1) / (uint32_t)p->num_cu;
-            lpw = lpw < 1 ? 1 : lpw > 64 ? 64 : lpw;
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((B + lpw - 1) / lpw), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B, lpw, (IirCarry*)nullptr); };
-            if (al) go(&k_iir_pipe<BPS, NC, true, (BPS == 4 || BPS == 2)>);
-            else go(&k_iir_pipe<BPS, NC, true, false>);
-        }
-        return;
-    }
-    if (per_channel) {
-        const uint32_t threads = B * g.nch;
-        hipLaunchKernelGGL((k_iir<BPS, NC, false>), dim3((threads + 63) / 64), dim3(64), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B);
-    } else {
-        hipLaunchKernelGGL((k_iir<BPS, NC, true>), dim3((B + 63) / 64), dim3(64), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B);
-    }
-}
-template <int BPS>
-static void launch_iir_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCoef& c, int per_channel, hipStream_t st) {
-    switch (c.nc) {
-        case 2: launch_iir<BPS, 2>(p, buf, B, c, per_channel, st); break;
-        case 3: launch_iir<BPS, 3>(p, buf, B, c, per_channel, st); break;
-        case 4: launch_iir<BPS, 4>(p, buf, B, c, per_channel, st); break;
-        default: launch_iir<BPS, 5>(p, buf, B, c, per_channel, st); break;
-    }
-}
-
-// The carried form (rspt_hip_iir_prefilter_stream_dev): the call's blocks as one run of `rows` rows, lane <-> channel, the
-// filters in `state`.  Whether a channel is fresh is known on the device only, so the route depends on the run's length alone.
-template <int BPS, int NC>
-static void launch_iir_stream(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, const IirCoef& c, IirCarry* state, hipStream_t st) {
-    const Geom& g = p->g;
-    const dim3 grid((g.nch + 63) / 64);
-    if (rows >= kIirChunk) {
-        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;
-        const uint64_t run_bytes = (uint64_t)rows * g.nch * BPS;
-        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kIirThreads), 0, st, buf, g.nch, rows, run_bytes, c, 1u, 64u, state); };
-        if (al) go(&k_iir_pipe<BPS, NC, false, (BPS == 4 || BPS == 2), true>);
-        else go(&k_iir_pipe<BPS, NC, false, false, true>);
-        return;
-    }
-    hipLaunchKernelGGL((k_iir_carry<BPS, NC>), grid, dim3(64), 0, st, buf, g.nch, rows, c, state);
-}
-template <int BPS>
-static void launch_iir_stream_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, const IirCoef& c, IirCarry* state, hipStream_t st) {
-    switch (c.nc) {
-        case 2: launch_iir_stream<BPS, 2>(p, buf, rows, c, state, st); break;
-        case 3: launch_iir_stream<BPS, 3>(p, buf, rows, c, state, st); break;
-        case 4: launch_iir_stream<BPS, 4>(p, buf, rows, c, state, st); break;
-        default: launch_iir_stream<BPS, 5>(p, buf, rows, c, state, st); break;
-    }
-}
-
-// The decomposition of a sliding-window stage (WinGeom): channel groups of up to `threads` lanes' channels, runs of `run`
-// outputs per lane (kFirThreads / kFirR, kMedThreads / kMedRun), and spans along the time axis until there are about four
-// workgroups per CU -- each span at least 4 (K - 1) rows, so that the halo an in-place call stages is at most a quarter of the
-// batch.  run_rows != 0 (a carried-state call): the nblocks blocks, back to back, taken as ONE block of run_rows = nblocks * ns rows.
-static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, uint32_t run_rows = 0) {
-    Geom g = p->g;
-    if (run_rows) {
-        g.ns = run_rows;
-        g.block_bytes = (uint64_t)run_rows * g.nch * g.bps;
-        nblocks = 1;
-    }
-    WinGeom f{};
-    f.block_bytes = g.block_bytes;
-    f.stride = g.nch * g.bps;  // (window_call_checks checks the chunk's row offsets before a launch)
-    f.nch = g.nch;
-    f.ns = g.ns;
-    f.K = K;
-    f.cw = g.nch < threads ? g.nch : threads;
-    f.subs = threads / f.cw;
-    f.ncg = (g.nch + f.cw - 1) / f.cw;
-    const uint32_t C = f.subs * run;
-    const uint64_t base_units = (uint64_t)nblocks * f.ncg;
-    const uint64_t want = 4ull * (uint64_t)p->num_cu;
-    uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
-    const uint64_t min_span = K > 1 ? 4ull * (K - 1) : 1;
-    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
-    nsplit = nsplit > max_split ? max_split : nsplit;
-    nsplit = nsplit < 1 ? 1 : nsplit;
-    const uint64_t span = ((g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
-    f.span = (uint32_t)span;
-    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
-    f.units = base_units * f.nsplit;
-    return f;
-}
-
-template <int BPS>
-static void launch_fir(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st,
-                       const uint8_t* head = nullptr) {
-    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
-    if (aligned) hipLaunchKernelGGL((k_fir<BPS, (BPS == 4 || BPS == 2)>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f, head);
-    else hipLaunchKernelGGL((k_fir<BPS, false>), dim3(grid), dim3(kFirThreads), 0, st, src, dst, halo, coef, f, head);
-}
-
-template <uint32_t N, int BPS, bool HEAD>
-static void launch_med_short(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st, const uint8_t* head) {
-    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
-    if (aligned) hipLaunchKernelGGL((k_med_short<N, BPS, (BPS == 4 || BPS == 2), HEAD>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f, head);
-    else hipLaunchKernelGGL((k_med_short<N, BPS, false, HEAD>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, halo, f, head);
-}
-
-// k_med_short by its register bucket: the smallest of 4, 8, 16, 32 that holds W.
-template <bool HEAD>
-static hipError_t launch_med_short_w(uint32_t bps, const WinGeom& f, const void* d_src, void* d_dst, const uint8_t* halo, bool aligned, hipStream_t st,
-                                     const uint8_t* head) {
-    const uint32_t W = f.K;
-    by_bps(bps, [&](auto bb) {
-        constexpr int B = decltype(bb)::value;
-        if (W <= 4) launch_med_short<4, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
-        else if (W <= 8) launch_med_short<8, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
-        else if (W <= 16) launch_med_short<16, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
-        else launch_med_short<32, B, HEAD>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, halo, aligned, st, head);
-    });
-    return hipGetLastError();
-}
-
-// The generic path on the pairs [pair0, pair0 + npairs) of the batch: sort (tile sort, merge passes), then walk.  STREAM: a pair
-// is a (segment, channel) of a carried-state call and f.ns the segment capacity (median.hip).
-template <int BPS, bool STREAM = false>
-static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const uint8_t* src, uint8_t* dst, uint64_t pair0, uint64_t npairs,
-                                     bool aligned, hipStream_t st, const MedSeg& sg = MedSeg{}) {
-    MedianStage& ms = p->med;
-    const uint32_t ns = f.ns;
-    const uint32_t tiles = (ns + kMedTile - 1) / kMedTile;
-    uint64_t* a = ms.keys_a;
-    uint64_t* b = ms.keys_b;
-    uint32_t* rank = ms.rank;
-    const bool one_tile = tiles == 1;
-    if (aligned) hipLaunchKernelGGL((k_med_tile_sort<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src,
-                                    a, one_tile ? rank : nullptr, f, pair0, sg);
-    else hipLaunchKernelGGL((k_med_tile_sort<BPS, false, STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a,
-                            one_tile ? rank : nullptr, f, pair0, sg);
-    hipError_t e = hipGetLastError();
-    const uint64_t total = npairs * ns;
-    for (uint32_t width = kMedTile; e == hipSuccess && width < ns; width *= 2) {
-        const bool last = (uint64_t)width * 2 >= ns;
-        hipLaunchKernelGGL(k_med_merge, dim3((uint32_t)((total + kMedThreads - 1) / kMedThreads)), dim3(kMedThreads), 0, st, a, b, last ? rank : nullptr, ns,
-                           width, total);
-        e = hipGetLastError();
-        std::swap(a, b);
-    }
-    if (e != hipSuccess) return e;
-    const uint32_t spans = ((STREAM ? sg.L : ns) + kMedSpan - 1) / kMedSpan;
-    const uint32_t n0 = (ns + 31) / 32;
-    const size_t lds = (size_t)(n0 + (n0 + 31) / 32) * sizeof(uint32_t);
-    if (aligned) hipLaunchKernelGGL((k_med_walk<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f,
-                                    pair0, sg);
-    else hipLaunchKernelGGL((k_med_walk<BPS, false, STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0, sg);
-    return hipGetLastError();
-}
-
 // The reference's channel limit: convert_native_to_i32 / convert_i32_to_native, which every one of its programs runs first and
 // last, count channels with a uint16_t (utils.cpp:57, 129) -- 65536 channels never terminate there.
 static constexpr size_t kMaxChannels = 65535;
-// The widest handle the filter, median, peak and PRDN stages are verified on (tests/test_gpu_wide_channels.py): beyond it they
-// return RSPT_HIP_ERR_UNSUPPORTED before anything is launched.
-static constexpr uint32_t kStageMaxChannels = 8191;
-static bool stage_too_wide(const rspt_hip_packer* p) { return p->g.nch > kStageMaxChannels; }
 
 template <int BPS>
 static void launch_wide_native(const Geom& g, const int32_t* planar, uint8_t* dst, uint32_t B, hipStream_t st) {
@@ -732,59 +289,6 @@ static void launch_inv_native(rspt_hip_packer* p, uint32_t B, uint32_t nrow, voi
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_inv_native<XDELTA, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const dim3 ng((g.ns + S - 1) / S, (g.nch + CG - 1) / CG, B);
     hipLaunchKernelGGL((k_inv_native<XDELTA, CG>), ng, dim3(1024), lds, st, p->ws.planes, g, p->ws.dec_nb, nrow, p->ws.txor, p->ws.tsum, (uint8_t*)d_dst);
-}
-
-// The checks both peak entries make, and the kernel arguments from them (all of PeakOffArgs but its workspace): false where
-// either entry refuses the call.
-static bool peak_args(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, void* d_state, uint32_t* d_count,
-                      int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, PeakArgs& a) {
-    if (!p || !d_src || !d_count || nblocks == 0) return false;
-    if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return false;
-    if (max_peaks > 0 && (!d_index || !d_value)) return false;
-    if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return false;
-    const Geom& g = p->g;
-    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return false;
-    a.src = (const uint8_t*)d_src;
-    a.block_bytes = g.block_bytes;
-    a.stride = g.nch * g.bps;
-    a.nch = g.nch;
-    a.ns = g.ns;
-    a.nblocks = (uint32_t)nblocks;
-    a.lanes = d_state ? g.nch : (uint32_t)(nblocks * g.nch);
-    a.state = (uint8_t*)d_state;
-    a.count = d_count;
-    a.index = d_index;
-    a.value = d_value;
-    a.max_peaks = max_peaks;
-    a.sig = d_sig;
-    a.thr = d_threshold;
-    return true;
-}
-
-// A variant's three filters as the detector's constructor designs them (create_filter_iir(f.d, f.n, ...): numerator -> d), and
-// its constants.  (Every design is valid for fs > 0.)
-static bool peak_coef(int variant, double sampling_rate, double marker_val, PeakCoef& c) {
-    static const struct { int bp_order; double bp_lo, bp_hi; int ig_order; double A; } kVar[3] = {
-        {2, 10.0, 20.0, 2, 25.0}, {1, 10.0, 20.0, 1, 25.0}, {1, 15.0, 25.0, 1, 70.0}};
-    const auto& v = kVar[variant];
-    if (!design_iir(kFiltBandPass, v.bp_order, sampling_rate, v.bp_lo, v.bp_hi, c.bf, c.bb) ||
-        !design_iir(kFiltLowPass, v.ig_order, sampling_rate, 3.0, 0.0, c.gf, c.gb) ||
-        !design_iir(kFiltLowPass, 2, sampling_rate, 0.15, 0.0, c.tf, c.tb))
-        return false;
-    c.atten = 1.0 / (1.0 + v.A / sampling_rate);
-    c.marker = marker_val;
-    c.nslope = (int32_t)((100.0 * sampling_rate) / 1000.0);
-    c.hist = 4 * (int32_t)sampling_rate;
-    return true;
-}
-
-// One lane per detector, 64 to a workgroup, on the caller's stream.
-template <class Args, class Coef>
-static int peak_launch(rspt_hip_packer* p, void (*kern)(Args, Coef), const Args& a, const Coef& c, void* stream) {
-    HIPCHK(p, hipSetDevice(p->device));
-    hipLaunchKernelGGL(kern, dim3((a.lanes + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, c);
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
 }
 
 extern "C" {
@@ -1427,274 +931,6 @@ int rspt_hip_compress(rspt_hip_packer* p, const void* src_host, void* dst_host, 
     return RSPT_HIP_OK;
 }
 
-// the copy streams of the many-block pipeline and the feed: made once, by whichever of the two comes first
-static int ensure_copy_streams(rspt_hip_packer* p) {
-    if (!p->m_up && hipStreamCreateWithFlags(p->m_up.out(), hipStreamNonBlocking) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-    if (!p->m_down && hipStreamCreateWithFlags(p->m_down.out(), hipStreamNonBlocking) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-    return RSPT_HIP_OK;
-}
-
-// the staging stride of one compressed stream in a slot
-static size_t slot_stride(const rspt_hip_packer* p) { return (rspt_hip_max_compressed_size(p) + 255) & ~(size_t)255; }
-
-// a slot for n blocks (a caller that gets false drops the slot: nothing half-made is kept)
-static bool alloc_slot(const rspt_hip_packer* p, Slot& s, size_t n) {
-    return hipMalloc(s.d_src.out(), n * p->g.block_bytes + 64) == hipSuccess && hipMalloc(s.d_dst.out(), n * slot_stride(p)) == hipSuccess &&
-           hipMalloc(s.d_sizes.out(), n * sizeof(uint64_t)) == hipSuccess &&
-           hipHostMalloc((void**)s.h_sizes.out(), (n + 1) * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess &&
-           hipEventCreateWithFlags(s.ev_up.out(), hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(s.ev_comp.out(), hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(s.ev_down.out(), hipEventDisableTiming) == hipSuccess;
-}
-
-static int ensure_many(rspt_hip_packer* p) {
-    if (p->many.chunk) return RSPT_HIP_OK;
-    int rc = ensure_copy_streams(p);
-    if (rc) return rc;
-    // ~64 MiB of samples per chunk: long enough copies for the DMA engines, short enough that the pipeline fills quickly
-    size_t chunk = (64ull << 20) / p->g.block_bytes;
-    chunk = chunk < 1 ? 1 : chunk > 64 ? 64 : chunk;
-    ManyStaging m;
-    bool ok = alloc_slot(p, m.slot[0], chunk) && alloc_slot(p, m.slot[1], chunk);
-    for (int i = 0; i < 2; ++i) ok = ok && hipMalloc(m.idx[i].out(), (4 + 2 * chunk) * sizeof(uint64_t)) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)m.hidx.out(), 2 * (4 + 2 * chunk) * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-    if (!ok) return RSPT_HIP_ERR_ALLOC;
-    m.chunk = chunk;
-    m.stride = slot_stride(p);
-    p->many = std::move(m);
-    return rspt_hip_reserve(p, chunk);
-}
-
-static int compress_many_pipeline(rspt_hip_packer* p, const void* src_host, size_t nblocks, void* dst_host, size_t dst_stride, size_t* dst_len);
-
-int rspt_hip_compress_many(rspt_hip_packer* p, const void* src_host, size_t nblocks, void* dst_host, size_t dst_stride, size_t* dst_len) {
-    if (!p || !src_host || !dst_host || !dst_len || nblocks == 0) return RSPT_HIP_ERR_ARG;
-    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the workspace and the copy streams until rspt_hip_feed_end)
-    HIPCHK(p, hipSetDevice(p->device));
-    int rc = ensure_many(p);
-    if (rc) return rc;
-    rc = compress_many_pipeline(p, src_host, nblocks, dst_host, dst_stride, dst_len);
-    if (rc != RSPT_HIP_OK && rc != RSPT_HIP_ERR_DST_TOO_SMALL) {
-        // a failure in the middle: nothing may still be copying from or into the caller's buffers when we return
-        hipStreamSynchronize(p->m_up);
-        hipStreamSynchronize(p->stream);
-        hipStreamSynchronize(p->m_down);
-    }
-    return rc;
-}
-
-static int compress_many_pipeline(rspt_hip_packer* p, const void* src_host, size_t nblocks, void* dst_host, size_t dst_stride, size_t* dst_len) {
-    int rc = RSPT_HIP_OK;
-    const size_t C = p->many.chunk, bb = p->g.block_bytes;
-    const size_t nchunk = (nblocks + C - 1) / C;
-    const uint8_t* src = (const uint8_t*)src_host;
-    uint8_t* dst = (uint8_t*)dst_host;
-    bool too_small = false;
-    // the streams of chunk k leave for the host (exact lengths: its sizes have to be here first)
-    auto download = [&](size_t k) -> int {
-        Slot& s = p->many.slot[k & 1];
-        const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
-        HIPCHK(p, hipEventSynchronize(s.ev_comp));
-        const uint64_t* hs = s.h_sizes;
-        for (size_t i = 0; i < cnt; ++i) {
-            const uint64_t sz = hs[i];
-            if ((sz >> 63) || sz > dst_stride) {  // flagged by the device (did not fit the staging stride), or too long for the caller's
-                dst_len[first + i] = (sz >> 63) ? 0 : (size_t)sz;
-                too_small = true;
-                continue;
-            }
-            dst_len[first + i] = (size_t)sz;
-            HIPCHK(p, hipMemcpyAsync(dst + (first + i) * dst_stride, s.d_dst + i * p->many.stride, (size_t)sz, hipMemcpyDeviceToHost, p->m_down));
-        }
-        HIPCHK(p, hipEventRecord(s.ev_down, p->m_down));
-        return RSPT_HIP_OK;
-    };
-    for (size_t k = 0; k < nchunk; ++k) {
-        Slot& s = p->many.slot[k & 1];
-        const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
-        if (k >= 2) {
-            HIPCHK(p, hipStreamWaitEvent(p->m_up, s.ev_comp, 0));     // chunk k-2 has been read out of this slot
-            HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_down, 0));  // ... and its streams have left it
-        }
-        HIPCHK(p, hipMemcpyAsync(s.d_src, src + first * bb, cnt * bb, hipMemcpyHostToDevice, p->m_up));
-        HIPCHK(p, hipEventRecord(s.ev_up, p->m_up));
-        HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_up, 0));
-        rc = compress_batch_serial(p, s.d_src, cnt, s.d_dst, p->many.stride, s.d_sizes, p->stream);
-        if (rc) return rc;
-        HIPCHK(p, hipMemcpyAsync(s.h_sizes, s.d_sizes, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(p, hipEventRecord(s.ev_comp, p->stream));
-        if (k >= 1) {
-            rc = download(k - 1);
-            if (rc) return rc;
-        }
-    }
-    rc = download(nchunk - 1);
-    if (rc) return rc;
-    uint32_t nb_now = 0;
-    HIPCHK(p, hipMemcpyAsync(&nb_now, p->nb_state, sizeof(nb_now), hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(p, hipStreamSynchronize(p->stream));
-    HIPCHK(p, hipStreamSynchronize(p->m_down));
-    if (nb_now >= 1 && nb_now <= 4) p->nb_host = nb_now;
-    return too_small ? RSPT_HIP_ERR_DST_TOO_SMALL : RSPT_HIP_OK;
-}
-
-// ---- rspt_hip_feed_*: blocks that arrive over time ---------------------------------------------------------------------------
-int rspt_hip_feed_begin(rspt_hip_packer* p, size_t blocks_per_launch, size_t slots) {
-    if (!p || blocks_per_launch == 0 || blocks_per_launch > 4096 || slots < 2 || slots > 64 || p->feed) return RSPT_HIP_ERR_ARG;
-    HIPCHK(p, hipSetDevice(p->device));
-    int rc = ensure_copy_streams(p);
-    if (rc) return rc;
-    rc = rspt_hip_reserve(p, blocks_per_launch);
-    if (rc) return rc;
-    std::unique_ptr<Feed> f(new (std::nothrow) Feed());
-    if (!f) return RSPT_HIP_ERR_ALLOC;
-    f->G = blocks_per_launch;
-    f->stride = slot_stride(p);
-    f->slots.resize(slots);
-    for (auto& s : f->slots) {
-        if (!alloc_slot(p, s, f->G)) return RSPT_HIP_ERR_ALLOC;
-        s.dst_host.resize(f->G);
-        s.dst_cap.resize(f->G);
-    }
-    p->feed = std::move(f);
-    return RSPT_HIP_OK;
-}
-
-static int feed_launch(rspt_hip_packer* p, FeedSlot& s) {
-    Feed* f = p->feed.get();
-    HIPCHK(p, hipEventRecord(s.ev_up, p->m_up));
-    HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_up, 0));
-    const int rc = compress_batch_serial(p, s.d_src, s.count, s.d_dst, f->stride, s.d_sizes, p->stream);
-    if (rc) return rc;
-    HIPCHK(p, hipMemcpyAsync(s.h_sizes, s.d_sizes, s.count * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(p, hipMemcpyAsync(s.h_sizes + f->G, p->nb_state, sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(p, hipEventRecord(s.ev_comp, p->stream));
-    s.state = FeedSlot::COMPRESSING;
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_feed_submit(rspt_hip_packer* p) {
-    if (!p || !p->feed) return RSPT_HIP_ERR_ARG;
-    HIPCHK(p, hipSetDevice(p->device));
-    Feed* f = p->feed.get();
-    FeedSlot& s = f->slots[f->tail];
-    if (s.state != FeedSlot::FILLING || s.count == 0) return RSPT_HIP_OK;
-    const int rc = feed_launch(p, s);
-    if (rc) {  // nothing of this group will arrive: its blocks are reported by rspt_hip_feed_poll with the failure as their status
-        s.error = rc;
-        s.state = FeedSlot::DONE;
-    }
-    f->tail = (f->tail + 1) % f->slots.size();
-    return rc;
-}
-
-int rspt_hip_feed_push(rspt_hip_packer* p, const void* src_host, void* dst_host, size_t dst_cap) {
-    if (!p || !p->feed || !src_host || !dst_host) return RSPT_HIP_ERR_ARG;
-    HIPCHK(p, hipSetDevice(p->device));
-    Feed* f = p->feed.get();
-    FeedSlot& s = f->slots[f->tail];
-    if (s.state != FeedSlot::FREE && s.state != FeedSlot::FILLING) return RSPT_HIP_ERR_BUSY;  // the ring is full: poll first
-    if (s.state == FeedSlot::FREE) {
-        s.state = FeedSlot::FILLING;
-        s.count = s.delivered = 0;
-        s.error = 0;
-        s.first_seq = f->next_seq;
-    }
-    const size_t i = s.count;
-    HIPCHK(p, hipMemcpyAsync(s.d_src + i * p->g.block_bytes, src_host, p->g.block_bytes, hipMemcpyHostToDevice, p->m_up));
-    s.dst_host[i] = dst_host;
-    s.dst_cap[i] = dst_cap;
-    ++s.count;
-    ++f->next_seq;
-    if (s.count == f->G) return rspt_hip_feed_submit(p);
-    return RSPT_HIP_OK;
-}
-
-// move every slot as far as it can go without waiting (wait = true: wait for each step instead)
-static int feed_advance(rspt_hip_packer* p, bool wait) {
-    Feed* f = p->feed.get();
-    const size_t n = f->slots.size();
-    for (size_t k = 0; k < n; ++k) {
-        FeedSlot& s = f->slots[(f->head + k) % n];
-        if (s.state == FeedSlot::COMPRESSING) {
-            if (wait) HIPCHK(p, hipEventSynchronize(s.ev_comp));
-            const hipError_t q = hipEventQuery(s.ev_comp);
-            if (q == hipErrorNotReady) break;  // (the slots behind it are not further along: one compute stream)
-            if (q != hipSuccess) {
-                p->last_hip_error = (int)q;
-                return RSPT_HIP_ERR_LAUNCH;
-            }
-            const uint32_t nb_now = (uint32_t)s.h_sizes[f->G];
-            if (nb_now >= 1 && nb_now <= 4 && nb_now > p->nb_host) p->nb_host = nb_now;  // the next launch writes exactly the planes it needs
-            HIPCHK(p, hipStreamWaitEvent(p->m_down, s.ev_comp, 0));
-            for (size_t i = 0; i < s.count; ++i) {
-                const uint64_t sz = s.h_sizes[i];
-                if (!(sz >> 63) && sz <= s.dst_cap[i])
-                    HIPCHK(p, hipMemcpyAsync(s.dst_host[i], s.d_dst + i * f->stride, (size_t)sz, hipMemcpyDeviceToHost, p->m_down));
-            }
-            HIPCHK(p, hipEventRecord(s.ev_down, p->m_down));
-            s.state = FeedSlot::DOWNLOADING;
-        }
-        if (s.state == FeedSlot::DOWNLOADING) {
-            if (wait) HIPCHK(p, hipEventSynchronize(s.ev_down));
-            const hipError_t q = hipEventQuery(s.ev_down);
-            if (q == hipErrorNotReady) continue;  // (a later slot's compress may still be ready for its downloads)
-            if (q != hipSuccess) {
-                p->last_hip_error = (int)q;
-                return RSPT_HIP_ERR_LAUNCH;
-            }
-            s.state = FeedSlot::DONE;
-        }
-    }
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_feed_poll(rspt_hip_packer* p, size_t* seq, size_t* dst_len, int* status) {
-    if (!p || !p->feed || !seq || !dst_len || !status) return RSPT_HIP_ERR_ARG;
-    HIPCHK(p, hipSetDevice(p->device));
-    Feed* f = p->feed.get();
-    const int rc = feed_advance(p, false);
-    if (rc) return rc;
-    FeedSlot& s = f->slots[f->head];
-    if (s.state != FeedSlot::DONE) return 0;
-    const size_t i = s.delivered;
-    const uint64_t sz = s.error ? 0 : s.h_sizes[i];
-    *seq = s.first_seq + i;
-    if (s.error) {
-        *dst_len = 0;
-        *status = s.error;
-    } else if ((sz >> 63) || sz > s.dst_cap[i]) {
-        *dst_len = (sz >> 63) ? 0 : (size_t)sz;
-        *status = RSPT_HIP_ERR_DST_TOO_SMALL;
-    } else {
-        *dst_len = (size_t)sz;
-        *status = RSPT_HIP_OK;
-    }
-    if (++s.delivered == s.count) {
-        s.state = FeedSlot::FREE;
-        f->head = (f->head + 1) % f->slots.size();
-    }
-    return 1;
-}
-
-int rspt_hip_feed_flush(rspt_hip_packer* p) {
-    if (!p || !p->feed) return RSPT_HIP_ERR_ARG;
-    int rc = rspt_hip_feed_submit(p);
-    if (rc) return rc;
-    return feed_advance(p, true);
-}
-
-int rspt_hip_feed_end(rspt_hip_packer* p) {
-    if (!p || !p->feed) return RSPT_HIP_ERR_ARG;
-    hipSetDevice(p->device);
-    rspt_hip_feed_submit(p);
-    hipStreamSynchronize(p->m_up);
-    hipStreamSynchronize(p->stream);
-    hipStreamSynchronize(p->m_down);  // nothing is copying from or into the caller's buffers any more
-    p->feed.reset();
-    return RSPT_HIP_OK;
-}
-
 static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* pidx, size_t packed_len, size_t nblocks,
                           void* d_dst, uint64_t* d_consumed, void* stream);
 
@@ -1713,95 +949,6 @@ int rspt_hip_decompress_packed_dev(rspt_hip_packer* p, const void* d_packed, siz
     // header 32 bytes, index 16 bytes per stream, then the payload the offsets are relative to
     return decompress_dev(p, base + 32 + 16 * nblocks, 0, reinterpret_cast<const uint64_t*>(base + 32), packed_len, nblocks, d_dst, d_consumed,
                           stream);
-}
-
-static int decompress_many_pipeline(rspt_hip_packer* p, const void* src_host, size_t src_stride, const size_t* src_len, size_t nblocks, void* dst_host,
-                                    size_t* consumed) {
-    const size_t C = p->many.chunk, bb = p->g.block_bytes;
-    const size_t nchunk = (nblocks + C - 1) / C;
-    const uint8_t* src = (const uint8_t*)src_host;
-    uint8_t* dst = (uint8_t*)dst_host;
-    bool corrupt = false;
-    // the slots are used the other way round: streams go up into d_dst, blocks come back out of d_src
-    auto finish = [&](size_t k) -> int {
-        Slot& s = p->many.slot[k & 1];
-        const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
-        HIPCHK(p, hipEventSynchronize(s.ev_comp));
-        const uint64_t* hs = s.h_sizes;
-        for (size_t i = 0; i < cnt; ++i) {
-            const bool bad = (hs[i] >> 63) != 0;
-            consumed[first + i] = bad ? 0 : (size_t)hs[i];
-            corrupt |= bad;
-        }
-        return RSPT_HIP_OK;
-    };
-    for (size_t k = 0; k < nchunk; ++k) {
-        const int slot = (int)(k & 1);
-        Slot& s = p->many.slot[slot];
-        const size_t first = k * C, cnt = nblocks - first < C ? nblocks - first : C;
-        if (k >= 2) {
-            HIPCHK(p, hipStreamWaitEvent(p->m_up, s.ev_comp, 0));     // chunk k-2 has been decoded out of this slot
-            HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_down, 0));  // ... and its blocks have left it
-        }
-        uint64_t* hidx = nullptr;
-        if (src_len) {
-            // Only src_len[i] bytes of every stream go up, into a slot that still holds an earlier chunk's bytes behind them: the
-            // decoder is therefore bounded by each stream's OWN length -- an index over the slot in the container's form
-            // (offset, length; nb 0 = the handle's state), checked on the device like any container -- and not by the slot stride.
-            hidx = p->many.hidx + (size_t)slot * (4 + 2 * C);
-            if (k >= 2) HIPCHK(p, hipEventSynchronize(s.ev_up));  // (the upload of chunk k-2 has read this staging index)
-            hidx[0] = 0x4B43415054505352ull;
-            hidx[1] = cnt;
-            hidx[2] = (uint64_t)cnt * p->many.stride;
-            hidx[3] = 0;
-            for (size_t i = 0; i < cnt; ++i) {
-                const size_t nbytes = src_len[first + i] < src_stride ? src_len[first + i] : src_stride;
-                hidx[4 + 2 * i] = (uint64_t)i * p->many.stride;
-                hidx[4 + 2 * i + 1] = nbytes;
-                if (nbytes) HIPCHK(p, hipMemcpyAsync(s.d_dst + i * p->many.stride, src + (first + i) * src_stride, nbytes, hipMemcpyHostToDevice, p->m_up));
-            }
-            HIPCHK(p, hipMemcpyAsync(p->many.idx[slot], hidx, (4 + 2 * cnt) * sizeof(uint64_t), hipMemcpyHostToDevice, p->m_up));
-        } else {
-            HIPCHK(p, hipMemcpy2DAsync(s.d_dst, p->many.stride, src + first * src_stride, src_stride, src_stride, cnt, hipMemcpyHostToDevice, p->m_up));
-        }
-        HIPCHK(p, hipEventRecord(s.ev_up, p->m_up));
-        HIPCHK(p, hipStreamWaitEvent(p->stream, s.ev_up, 0));
-        const int rc = hidx ? decompress_dev(p, s.d_dst, 0, p->many.idx[slot] + 4, 32 + 16 * cnt + cnt * p->many.stride, cnt, s.d_src,
-                                             s.d_sizes, (void*)p->stream)
-                            : rspt_hip_decompress_batch_dev(p, s.d_dst, p->many.stride, cnt, s.d_src, s.d_sizes, (void*)p->stream);
-        if (rc) return rc;
-        HIPCHK(p, hipMemcpyAsync(s.h_sizes, s.d_sizes, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(p, hipEventRecord(s.ev_comp, p->stream));
-        // the blocks leave as soon as they are decoded: their size is known beforehand
-        HIPCHK(p, hipStreamWaitEvent(p->m_down, s.ev_comp, 0));
-        HIPCHK(p, hipMemcpyAsync(dst + first * bb, s.d_src, cnt * bb, hipMemcpyDeviceToHost, p->m_down));
-        HIPCHK(p, hipEventRecord(s.ev_down, p->m_down));
-        if (k >= 1) {
-            const int rf = finish(k - 1);
-            if (rf) return rf;
-        }
-    }
-    const int rf = finish(nchunk - 1);
-    if (rf) return rf;
-    HIPCHK(p, hipStreamSynchronize(p->m_down));
-    return corrupt ? RSPT_HIP_ERR_CORRUPT : RSPT_HIP_OK;
-}
-
-int rspt_hip_decompress_many(rspt_hip_packer* p, const void* src_host, size_t src_stride, const size_t* src_len, size_t nblocks, void* dst_host,
-                             size_t* consumed) {
-    if (!p || !src_host || !dst_host || !consumed || nblocks == 0 || src_stride == 0) return RSPT_HIP_ERR_ARG;
-    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the workspace and the copy streams until rspt_hip_feed_end)
-    HIPCHK(p, hipSetDevice(p->device));
-    int rc = ensure_many(p);
-    if (rc) return rc;
-    if (src_stride > p->many.stride) return RSPT_HIP_ERR_ARG;
-    rc = decompress_many_pipeline(p, src_host, src_stride, src_len, nblocks, dst_host, consumed);
-    if (rc != RSPT_HIP_OK && rc != RSPT_HIP_ERR_CORRUPT) {
-        hipStreamSynchronize(p->m_up);
-        hipStreamSynchronize(p->stream);
-        hipStreamSynchronize(p->m_down);
-    }
-    return rc;
 }
 
 static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* pidx, size_t packed_len, size_t nblocks,
@@ -1980,729 +1127,6 @@ int rspt_hip_decompress_bounded(rspt_hip_packer* p, const void* src_host, size_t
     return decompress_host(p, src_host, src_cap, src_len, dst_host);
 }
 
-int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
-                                     int init_nr_samples, int per_channel, void* stream) {
-    if (!p || !d_buf || !n || !d || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
-    if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;  // filter_opt covers 2..5 (iir_filter.cpp:87-103)
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    HIPCHK(p, hipSetDevice(p->device));
-    IirCoef c{};
-    for (size_t i = 0; i < nr_coefficients; ++i) {
-        c.n[i] = n[i];
-        c.d[i] = d[i];
-    }
-    c.nc = (uint32_t)nr_coefficients;
-    c.init_steps = 4 * init_nr_samples;
-    hipStream_t st = (hipStream_t)stream;
-    by_bps(p->g.bps, [&](auto bps) { launch_iir_nc<decltype(bps)::value>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st); });
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
-}
-
-// A carried-state call takes its blocks as one run of nblocks * ns rows, indexed in 32 bits with a chunk's reach beyond the last
-// row: runs of 2^31 - 2^17 rows and more are refused, and the caller splits the call (with a state that split is exact).
-static constexpr uint64_t kStreamMaxRows = (1ull << 31) - (1ull << 17);
-
-int rspt_hip_iir_state_bytes(rspt_hip_packer* p, size_t* bytes) {
-    if (!p || !bytes) return RSPT_HIP_ERR_ARG;
-    *bytes = (size_t)p->g.nch * sizeof(IirCarry);
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
-                                      int init_nr_samples, void* d_state, void* stream) {
-    if (!p || !d_buf || !n || !d || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
-    if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;
-    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    const uint64_t rows = (uint64_t)nblocks * p->g.ns;
-    if (rows >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
-    HIPCHK(p, hipSetDevice(p->device));
-    IirCoef c{};
-    for (size_t i = 0; i < nr_coefficients; ++i) {
-        c.n[i] = n[i];
-        c.d[i] = d[i];
-    }
-    c.nc = (uint32_t)nr_coefficients;
-    c.init_steps = 4 * init_nr_samples;
-    hipStream_t st = (hipStream_t)stream;
-    by_bps(p->g.bps, [&](auto bps) { launch_iir_stream_nc<decltype(bps)::value>(p, (uint8_t*)d_buf, (uint32_t)rows, c, (IirCarry*)d_state, st); });
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
-}
-
-// The checks of both windowed entry points, in the order they return: a null handle or buffer, nblocks == 0 or nblocks * nch
-// >= 2^31, and buffers that overlap without being the same (ERR_ARG); then a chunk's row offsets, which k_fir and k_med_short
-// compute in 32 bits (ERR_UNSUPPORTED: 2^24 channels and more).  Sets the geometry for the window K and whether the call is in place.
-static int window_call_checks(const rspt_hip_packer* p, const void* d_src, const void* d_dst, size_t nblocks, uint32_t K, uint32_t threads,
-                              uint32_t run, WinGeom* f, bool* in_place, bool one_run = false) {
-    if (!p || !d_src || !d_dst || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
-    const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    *in_place = s0 == d0;
-    if (!*in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    if (one_run && (uint64_t)nblocks * p->g.ns >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
-    *f = win_geom(p, nblocks, K, threads, run, one_run ? (uint32_t)(nblocks * p->g.ns) : 0u);
-    if ((uint64_t)f->subs * run * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;
-    return RSPT_HIP_OK;
-}
-
-// The halo of an in-place call with more than one span per block: the K - 1 rows in front of every span but the first,
-// nblocks (nsplit - 1) pieces of (K - 1) rows.
-static uint64_t halo_pieces(const WinGeom& f, size_t nblocks, bool in_place) {
-    return in_place && f.nsplit > 1 ? (uint64_t)nblocks * (f.nsplit - 1) : 0;  // (a carried-state call: one block)
-}
-
-static hipError_t launch_halo(const WinGeom& f, const void* d_src, uint8_t* halo, uint64_t pieces, hipStream_t st) {
-    const bool words = (reinterpret_cast<uintptr_t>(d_src) % 4) == 0 && (f.block_bytes % 4) == 0 && (f.stride % 4) == 0;
-    const uint32_t grid = (uint32_t)(pieces < 65536 ? pieces : 65536);
-    if (words) hipLaunchKernelGGL(k_fir_halo<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, halo, f, pieces);
-    else hipLaunchKernelGGL(k_fir_halo<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, halo, f, pieces);
-    return hipGetLastError();
-}
-
-// The end of a windowed call from the point where it has enqueued work: record `last` behind it, and report the first error.
-static int finish_window_call(rspt_hip_packer* p, LastCall& last, hipError_t e, hipStream_t st) {
-    const hipError_t er = last.record(st);
-    if (e == hipSuccess) e = er;
-    if (e != hipSuccess) {
-        p->last_hip_error = (int)e;
-        return RSPT_HIP_ERR_LAUNCH;
-    }
-    return RSPT_HIP_OK;
-}
-
-// Stage the head of a carried-state call and write the new state (k_fir_carry, fir.hip); the state: [u64 started][K - 1 rows].
-static hipError_t launch_fir_carry(const WinGeom& f, const void* d_src, uint8_t* head, void* d_state, hipStream_t st) {
-    uint64_t* started = (uint64_t*)d_state;
-    uint8_t* rows = (uint8_t*)d_state + 8;
-    const uint64_t n = (uint64_t)(f.K - 1) * f.stride;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
-    if (n) hipLaunchKernelGGL(k_fir_carry<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
-    hipLaunchKernelGGL(k_fir_carry<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
-    return hipGetLastError();
-}
-
-// Both FIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
-static int fir_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size, void* d_state,
-                    void* stream) {
-    if (!kernel || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
-    WinGeom f;
-    bool in_place;
-    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, (uint32_t)kernel_size, kFirThreads, kFirR, &f, &in_place, d_state != nullptr)) return rc;
-    if (d_state) nblocks = 1;  // (the geometry's one block of nblocks * ns rows)
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    FirStage& fs = p->fir;
-    const uint64_t pieces = halo_pieces(f, nblocks, in_place);
-    const uint64_t halo_bytes = pieces * (uint64_t)(kernel_size - 1) * f.stride;
-    const uint64_t head_bytes = d_state ? (uint64_t)(kernel_size - 1) * f.stride : 0;
-    if (halo_bytes > fs.halo_cap || head_bytes > fs.head_cap) {
-        fs.wait_all();  // (no earlier call may still read a buffer being replaced)
-        if (halo_bytes > fs.halo_cap) {
-            fs.halo_cap = 0;
-            if (hipMalloc(fs.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            fs.halo_cap = halo_bytes;
-        }
-        if (head_bytes > fs.head_cap) {
-            fs.head_cap = 0;
-            if (hipMalloc(fs.head.out(), head_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            fs.head_cap = head_bytes;
-        }
-    }
-    // the coefficients: the host waits only when kSlots calls are still ahead on the device
-    FirStage::CoefSlot& cs = fs.slot[fs.next];
-    HIPCHK(p, cs.last.wait());
-    if (cs.cap < kernel_size) {
-        cs.cap = 0;
-        if (hipHostMalloc((void**)cs.host.out(), kernel_size * sizeof(double), hipHostMallocDefault) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        if (hipMalloc(cs.dev.out(), kernel_size * sizeof(double)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        cs.cap = kernel_size;
-    }
-    if (!cs.last.make_event()) return RSPT_HIP_ERR_ALLOC;
-    memcpy(cs.host, kernel, kernel_size * sizeof(double));
-    fs.next = (fs.next + 1) % FirStage::kSlots;
-    // (from here on every path ends in finish_window_call, which records `last`: the copy below reads the page-locked slot)
-    hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_state) e = launch_fir_carry(f, d_src, fs.head, d_state, st);
-    if (e == hipSuccess && pieces) e = launch_halo(f, d_src, fs.halo, pieces, st);
-    if (e == hipSuccess) {
-        const uint32_t bps = p->g.bps;
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-        const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;  // (block_bytes is a multiple of bps)
-        by_bps(bps, [&](auto b) {
-            launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, cs.dev, aligned, st,
-                                           head_bytes ? (const uint8_t*)fs.head : nullptr);
-        });
-        e = hipGetLastError();
-    }
-    return finish_window_call(p, cs.last, e, st);
-}
-
-int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
-                                     void* stream) {
-    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, nullptr, stream);
-}
-
-int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) {
-    if (!p || !bytes || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
-    *bytes = 8 + (((size_t)(kernel_size - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
-                                      void* d_state, void* stream) {
-    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
-    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
-}
-
-// The median stage's buffers for a call: each grows behind the stage's last call, and `last` has its event from here on.
-static int median_reserve(MedianStage& ms, uint64_t halo_bytes, uint64_t head_bytes, uint64_t key_samples) {
-    if (halo_bytes > ms.halo_cap || head_bytes > ms.head_cap || key_samples > ms.key_cap) {
-        ms.last.wait();  // (no earlier call may still use a buffer being replaced)
-        if (halo_bytes > ms.halo_cap) {
-            ms.halo_cap = 0;
-            if (hipMalloc(ms.halo.out(), halo_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            ms.halo_cap = halo_bytes;
-        }
-        if (head_bytes > ms.head_cap) {
-            ms.head_cap = 0;
-            if (hipMalloc(ms.head.out(), head_bytes) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            ms.head_cap = head_bytes;
-        }
-        if (key_samples > ms.key_cap) {
-            ms.key_cap = 0;
-            ms.rank.reset();
-            ms.keys_b.reset();
-            if (hipMalloc(ms.keys_a.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            if (hipMalloc(ms.keys_b.out(), key_samples * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            if (hipMalloc(ms.rank.out(), key_samples * sizeof(uint32_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-            ms.key_cap = key_samples;
-        }
-    }
-    return ms.last.make_event() ? RSPT_HIP_OK : RSPT_HIP_ERR_ALLOC;
-}
-
-int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream) {
-    if (!p || window == 0) return RSPT_HIP_ERR_ARG;
-    const Geom& g = p->g;
-    const uint32_t W = (uint32_t)(window < g.ns ? window : g.ns);  // a window of ns or more is the expanding median of the channel
-    WinGeom f;
-    bool in_place;
-    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, W, kMedThreads, kMedRun, &f, &in_place)) return rc;
-    if (W > kMedShortMax && g.ns > kMedMaxRanks) return RSPT_HIP_ERR_UNSUPPORTED;  // (the generic path's bitmaps live in LDS)
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (W == 1) {  // a copy, sample width kept
-        if (in_place) return RSPT_HIP_OK;
-        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, (uint64_t)nblocks * g.block_bytes, hipMemcpyDeviceToDevice, st));
-        return RSPT_HIP_OK;
-    }
-    MedianStage& ms = p->med;
-    const uint32_t bps = g.bps;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;  // (block_bytes is a multiple of bps)
-    const uint64_t pairs = (uint64_t)nblocks * g.nch;
-    // buffers: the short path's halo, the generic path's keys and ranks for a piece of up to 2^25 samples (or one channel)
-    const bool is_short = W <= kMedShortMax;
-    const uint64_t pieces = is_short ? halo_pieces(f, nblocks, in_place) : 0;
-    const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
-    const uint64_t piece_pairs = is_short ? 0 : std::min<uint64_t>(pairs, std::max<uint64_t>(1, (1ull << 25) / g.ns));
-    if (int rc = median_reserve(ms, halo_bytes, 0, piece_pairs * g.ns)) return rc;
-    hipError_t e = hipSuccess;
-    if (is_short) {
-        if (pieces) e = launch_halo(f, d_src, ms.halo, pieces, st);
-        if (e == hipSuccess) e = launch_med_short_w<false>(bps, f, d_src, d_dst, pieces ? (const uint8_t*)ms.halo : nullptr, aligned, st, nullptr);
-    } else {
-        for (uint64_t pair0 = 0; e == hipSuccess && pair0 < pairs; pair0 += piece_pairs) {
-            const uint64_t np = std::min(piece_pairs, pairs - pair0);
-            e = by_bps(bps, [&](auto bb) {
-                return launch_med_generic<decltype(bb)::value>(p, f, (const uint8_t*)d_src, (uint8_t*)d_dst, pair0, np, aligned, st);
-            });
-        }
-    }
-    return finish_window_call(p, ms.last, e, st);
-}
-
-int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) {
-    if (!p || !bytes || window == 0) return RSPT_HIP_ERR_ARG;
-    if (window > kMedShortMax && window - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;
-    *bytes = 8 + (((size_t)(window - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
-    return RSPT_HIP_OK;
-}
-
-// Stage the old state in the handle's head buffer and write the new one (k_med_carry, median.hip): in words where every
-// address and length is a multiple of 4.
-static hipError_t launch_med_carry(const WinGeom& f, const void* d_src, uint8_t* head, void* d_state, uint64_t rows, hipStream_t st) {
-    uint64_t n = (uint64_t)(f.K - 1) * f.stride, call = rows * f.stride;
-    const bool words = reinterpret_cast<uintptr_t>(d_src) % 4 == 0 && f.stride % 4 == 0;
-    if (words) n /= 4, call /= 4;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
-    uint8_t* state = (uint8_t*)d_state;
-    if (words) {
-        hipLaunchKernelGGL((k_med_carry<false, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
-        hipLaunchKernelGGL((k_med_carry<true, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
-    } else {
-        hipLaunchKernelGGL((k_med_carry<false, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
-        hipLaunchKernelGGL((k_med_carry<true, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
-    }
-    return hipGetLastError();
-}
-
-// The segment capacity S = W - 1 + L of a carried-state call of the generic path: 8 (W - 1) rounded up to 2^16, 2^17 or 2^18 --
-// at most one row in eight is sorted twice up to W - 1 = 2^15, one in two at the limit W - 1 = 2^17 -- and never more than the
-// call needs (one segment of W - 1 + N rows).  2^16 is the channel length the stateless path is measured at:
-// shorter segments save merge passes but pay a bitmap clear and W set bits per 1024 outputs more often than they save.
-static uint32_t median_segment_rows(uint32_t W, uint64_t rows) {
-    const uint64_t want = 8ull * (W - 1);
-    const uint64_t S = want <= (1u << 16) ? (1u << 16) : want <= (1u << 17) ? (1u << 17) : kMedMaxRanks;
-    return (uint32_t)std::min<uint64_t>(S, (uint64_t)(W - 1) + rows);
-}
-
-int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
-    if (!p || window == 0 || !d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
-    const Geom& g = p->g;
-    const uint32_t W = (uint32_t)std::min<size_t>(window, (size_t)kMedMaxCarry + 2);  // (not clamped to ns: the window is the recording's)
-    WinGeom f;
-    bool in_place;
-    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, W, kMedThreads, kMedRun, &f, &in_place, true)) return rc;
-    if (W > kMedShortMax && W - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;  // (at least half of every segment is new rows)
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t rows = (uint64_t)nblocks * g.ns;  // (below 2^31 - 2^17: window_call_checks)
-    if (W == 1) {  // a copy; the state is its header and stays zero
-        if (in_place) return RSPT_HIP_OK;
-        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, rows * f.stride, hipMemcpyDeviceToDevice, st));
-        return RSPT_HIP_OK;
-    }
-    MedianStage& ms = p->med;
-    const uint32_t bps = g.bps;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    const bool aligned = (bps == 4 || bps == 2) && s0 % bps == 0 && d0 % bps == 0;
-    const bool is_short = W <= kMedShortMax;
-    const uint64_t pieces = is_short ? halo_pieces(f, 1, in_place) : 0;
-    const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
-    const uint64_t head_bytes = 8 + (uint64_t)(W - 1) * f.stride;
-    // generic: (segment, channel) items of S keys each, in pieces of up to 2^25 keys
-    MedSeg sg{};
-    WinGeom fg = f;
-    uint64_t items = 0, piece_items = 0;
-    if (!is_short) {
-        const uint32_t S = median_segment_rows(W, rows);
-        sg.L = S - (W - 1);
-        sg.nseg = (uint32_t)((rows + sg.L - 1) / sg.L);
-        sg.N = (uint32_t)rows;
-        fg.ns = S;
-        items = (uint64_t)sg.nseg * g.nch;
-        piece_items = std::min<uint64_t>(items, std::max<uint64_t>(1, (1ull << 25) / S));
-    }
-    if (int rc = median_reserve(ms, halo_bytes, head_bytes, piece_items * fg.ns)) return rc;
-    sg.head = ms.head;
-    // the new state is written from d_src before any kernel stores to d_dst
-    hipError_t e = launch_med_carry(f, d_src, ms.head, d_state, rows, st);
-    if (is_short) {
-        if (e == hipSuccess && pieces) e = launch_halo(f, d_src, ms.halo, pieces, st);
-        if (e == hipSuccess) e = launch_med_short_w<true>(bps, f, d_src, d_dst, pieces ? (const uint8_t*)ms.halo : nullptr, aligned, st, ms.head);
-    } else {
-        // from the last segment to the first: a walk writes its segment's new rows, which no segment sorted later reads
-        for (uint64_t item0 = 0; e == hipSuccess && item0 < items; item0 += piece_items) {
-            const uint64_t ni = std::min(piece_items, items - item0);
-            e = by_bps(bps, [&](auto bb) {
-                return launch_med_generic<decltype(bb)::value, true>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, aligned, st, sg);
-            });
-        }
-    }
-    return finish_window_call(p, ms.last, e, st);
-}
-
-// ---- PRDN: the quality figure of the reference's harness (quality.hip) -----------------------------------------------------------
-// The decomposition of the two streaming passes for the widest load the buffers' alignment allows.
-static QGeom quality_geom(const rspt_hip_packer* p, size_t nblocks, int W) {
-    const Geom& g = p->g;
-    QGeom q{};
-    q.block_bytes = g.block_bytes;
-    q.nch = g.nch, q.ns = g.ns, q.be = g.be;
-    const uint32_t nw = W == 0 ? 1u : (g.bps == 3 ? 3u : 1u) * (uint32_t)W;
-    const uint32_t vs = W == 0 ? 1u : nw * 4u / g.bps;  // samples of a load group
-    uint32_t a = g.nch, b = vs;
-    while (b) {
-        const uint32_t t = a % b;
-        a = b, b = t;
-    }
-    q.rows = vs / a;  // the fewest rows that hold whole groups
-    const uint64_t qps = (uint64_t)q.rows * g.nch / vs;
-    q.qps = (uint32_t)qps;
-    q.nsub = qps < kQThreads ? kQThreads / q.qps : 1u;
-    q.ncg = (uint32_t)((qps + kQThreads - 1) / kQThreads);
-    q.nsr = g.ns / q.rows;
-    const uint64_t sweeps = ((uint64_t)q.nsr + q.nsub - 1) / q.nsub;
-    // workgroups: about 4096 in all where the blocks are long enough to give each at least 8 sweeps
-    uint64_t nsplit = std::min<uint64_t>(std::max<uint64_t>(1, sweeps / 8), (4096 + nblocks * q.ncg - 1) / (nblocks * q.ncg));
-    q.span = (uint32_t)std::max<uint64_t>(1, (sweeps + nsplit - 1) / nsplit) * q.nsub;
-    q.nsplit = (uint32_t)std::max<uint64_t>(1, ((uint64_t)q.nsr + q.span - 1) / q.span);
-    return q;
-}
-
-int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, double* d_prdn, double* d_mse, double* d_ref,
-                            uint32_t* d_path, void* stream) {
-    if (!p || !d_orig || !d_dec || !d_prdn || nblocks == 0 || nblocks > 0x7FFFFFFFu / (p->g.nch ? p->g.nch : 1)) return RSPT_HIP_ERR_ARG;
-    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    const Geom& g = p->g;
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_orig), d0 = reinterpret_cast<uintptr_t>(d_dec);
-    auto aligned = [&](uintptr_t m) { return o0 % m == 0 && d0 % m == 0 && (nblocks == 1 || g.block_bytes % m == 0); };
-    const int W = aligned(16) ? 4 : aligned(4) ? 1 : 0;
-    QGeom q = quality_geom(p, nblocks, W);
-    q.aligned4 = aligned(4) ? 1u : 0u;
-    const uint64_t units = (uint64_t)nblocks * q.ncg * q.nsplit;
-    if (units >= (1ull << 31) || (uint64_t)q.rows * g.nch >= (1ull << 32)) return RSPT_HIP_ERR_UNSUPPORTED;
-    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t B = (uint32_t)nblocks;
-    unsigned long long* sums = p->ws.quality;
-    unsigned long long* acc = sums + (size_t)B * g.nch;
-    uint32_t* flag = reinterpret_cast<uint32_t*>(acc + (size_t)B * 4);
-    HIPCHK(p, hipMemsetAsync(sums, 0, ((size_t)B * g.nch + (size_t)B * 4) * sizeof(unsigned long long), st));
-    const uint8_t* o = (const uint8_t*)d_orig;
-    const uint8_t* d = (const uint8_t*)d_dec;
-    by_bps(g.bps, [&](auto bb) {
-        constexpr int BPS = decltype(bb)::value;
-        auto go = [&](auto ww) {
-            constexpr int WW = decltype(ww)::value;
-            hipLaunchKernelGGL((k_q_sums<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, q, sums);
-            hipLaunchKernelGGL((k_q_accum<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, acc);
-        };
-        if (W == 4) go(std::integral_constant<int, 4>());
-        else if (W == 1) go(std::integral_constant<int, 1>());
-        else go(std::integral_constant<int, 0>());
-        hipLaunchKernelGGL(k_q_finish, dim3((B + 255) / 256), dim3(256), 0, st, (const unsigned long long*)acc, B, flag, d_prdn, d_mse, d_ref, d_path);
-        hipLaunchKernelGGL(k_q_seq<BPS>, dim3(B), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, (const unsigned long long*)acc,
-                           (const uint32_t*)flag, d_prdn, d_mse, d_ref);
-    });
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
-}
-
-// ---- native <-> planar int32 (the reference's convert_native_to_i32 / convert_i32_to_native, utils.cpp:51-191) -------------------
-// The checks of both entries.  Nothing of the handle but its shape and byte order is used: no workspace, no allocation.
-static int convert_checks(const rspt_hip_packer* p, const void* d_native, const void* d_planar, size_t nblocks) {
-    if (!p || !d_native || !d_planar || nblocks == 0 || nblocks > 65535) return RSPT_HIP_ERR_ARG;  // (65535: grid.z, as rspt_hip_reserve)
-    const Geom& g = p->g;
-    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
-    const uintptr_t n0 = reinterpret_cast<uintptr_t>(d_native), p0 = reinterpret_cast<uintptr_t>(d_planar);
-    if (p0 & 3u) return RSPT_HIP_ERR_ARG;
-    const uint64_t nbytes = (uint64_t)nblocks * g.block_bytes, pbytes = (uint64_t)nblocks * g.N * sizeof(int32_t);
-    if (n0 < p0 + pbytes && p0 < n0 + nbytes) return RSPT_HIP_ERR_ARG;  // the two buffers overlap
-    return RSPT_HIP_OK;
-}
-
-// Narrow handles with a 16-byte aligned native buffer take the tile kernels of the packers' own front end and inverse; wide ones,
-// and native buffers at any other address, the 64 x 64 transposes k_wide_planar / k_wide_native.
-static bool convert_i32x4_ok(const Geom& g, const void* d_planar) {
-    return g.bps == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_planar) & 15) == 0;
-}
-
-int rspt_hip_native_to_i32_batch_dev(rspt_hip_packer* p, const void* d_native, int32_t* d_planar, size_t nblocks, void* stream) {
-    if (int rc = convert_checks(p, d_native, d_planar, nblocks)) return rc;
-    HIPCHK(p, hipSetDevice(p->device));
-    const Geom& g = p->g;
-    hipStream_t st = (hipStream_t)stream;
-    const uint8_t* src = (const uint8_t*)d_native;
-    const unsigned B = (unsigned)nblocks;
-    if (!p->wide && (reinterpret_cast<uintptr_t>(d_native) & 15) == 0) {
-        if (convert_i32x4_ok(g, d_planar)) {
-            const uint32_t T4 = tile_i32x4(g);
-            hipLaunchKernelGGL(k_tile_planar_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, src, g, T4, d_planar,
-                               (long long*)nullptr);
-        } else {
-            by_bps(g.bps, [&](auto bps) {
-                constexpr int BPS = decltype(bps)::value;
-                if (!p->conv_lds_raised) {  // (once per handle: a handle has one sample width)
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_planar<BPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->in_lds) != hipSuccess) return;
-                    p->conv_lds_raised = true;
-                }
-                hipLaunchKernelGGL((k_tile_planar<BPS>), dim3((g.ns + p->T - 1) / p->T, B), dim3(256), p->in_lds, st, src, g, p->T, d_planar);
-            });
-        }
-    } else {
-        by_bps(g.bps, [&](auto bps) {
-            hipLaunchKernelGGL(k_wide_planar<decltype(bps)::value>, dim3((g.ns + 63) / 64, (g.nch + 63) / 64, B), dim3(256), 0, st, src, g, d_planar);
-        });
-    }
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_i32_to_native_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, void* d_native, size_t nblocks, void* stream) {
-    if (int rc = convert_checks(p, d_native, d_planar, nblocks)) return rc;
-    HIPCHK(p, hipSetDevice(p->device));
-    const Geom& g = p->g;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* dst = (uint8_t*)d_native;
-    const unsigned B = (unsigned)nblocks;
-    // k_planar_native divides per element and stores int8 / int16 / int24 byte by byte: it keeps only the handles of fewer than 32
-    // channels, where more than half of k_wide_native's 64-channel tile would be empty.
-    const bool narrow = !p->wide && p->Tn_native && (reinterpret_cast<uintptr_t>(d_native) & 15) == 0;
-    if (narrow && (convert_i32x4_ok(g, d_planar) || g.nch < 32)) {
-        if (convert_i32x4_ok(g, d_planar)) {
-            const uint32_t T4 = tile_i32x4(g);
-            hipLaunchKernelGGL(k_planar_native_i32x4, dim3((g.ns + T4 - 1) / T4, B), dim3(256), g.nch * (T4 + 1) * 4, st, d_planar, g, T4, dst);
-        } else {
-            const uint32_t T = min(p->Tn_native, g.ns);
-            by_bps(g.bps, [&](auto bps) {
-                hipLaunchKernelGGL((k_planar_native<decltype(bps)::value>), dim3((g.ns + T - 1) / T, B), dim3(256), g.nch * (T + 1) * 4, st, d_planar, g, T,
-                                   dst);
-            });
-        }
-    } else {
-        by_bps(g.bps, [&](auto bps) { launch_wide_native<decltype(bps)::value>(g, d_planar, dst, B, st); });
-    }
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff_low, double cutoff_high, double* num, double* den,
-                        size_t* nr_coefficients) {
-    if (!num || !den || !nr_coefficients) return RSPT_HIP_ERR_ARG;
-    double n[5], d[5];
-    const int nc = design_iir(type, order, sampling_rate, cutoff_low, cutoff_high, n, d);
-    if (nc == 0) return RSPT_HIP_ERR_ARG;
-    for (int i = 0; i < nc; ++i) {
-        num[i] = n[i];
-        den[i] = d[i];
-    }
-    *nr_coefficients = (size_t)nc;
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_peak_state_bytes(rspt_hip_packer* p, size_t* bytes) {
-    if (!p || !bytes) return RSPT_HIP_ERR_ARG;
-    *bytes = (size_t)p->g.nch * kPeakStateBytesPerChannel;
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
-                                   void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
-                                   double* d_threshold, void* stream) {
-    PeakArgs a{};
-    PeakCoef c{};
-    if (variant < kPeakOnline || variant > kPeakOfflineFw ||
-        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
-        !peak_coef(variant, sampling_rate, marker_val, c))
-        return RSPT_HIP_ERR_ARG;
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    return by_bps(p->g.bps, [&](auto bb) {
-        constexpr int B = decltype(bb)::value;
-        auto go = [&](auto vv) {
-            constexpr int V = decltype(vv)::value;
-            return peak_launch(p, d_sig ? &k_peak<B, V, true> : &k_peak<B, V, false>, a, c, stream);
-        };
-        if (variant == kPeakOnline) return go(std::integral_constant<int, kPeakOnline>());
-        if (variant == kPeakOnline1st) return go(std::integral_constant<int, kPeakOnline1st>());
-        return go(std::integral_constant<int, kPeakOfflineFw>());
-    });
-}
-
-int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int stateful, size_t* bytes) {
-    if (!p || !bytes || nblocks == 0) return RSPT_HIP_ERR_ARG;
-    const Geom& g = p->g;
-    if ((uint64_t)nblocks * g.nch >= (1ull << 31)) return RSPT_HIP_ERR_ARG;
-    const uint64_t lanes = stateful ? g.nch : (uint64_t)nblocks * g.nch;
-    *bytes = (size_t)(((lanes + 63) / 64) * kPeakOffSlabBytesPerSample * g.ns);
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
-                                           void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
-                                           size_t max_peaks, double* d_sig, double* d_threshold, void* stream) {
-    PeakOffArgs a{};
-    PeakOffCoef k{};
-    if (!d_work || ((uintptr_t)d_work % 8) != 0 ||
-        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
-        !peak_coef(kPeakOfflineFw, sampling_rate, marker_val, k.c))
-        return RSPT_HIP_ERR_ARG;
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    // the reference's undefined cases: nr_slope_samples 0 (the shift runs every event off the end of the array) and a block
-    // shorter than the relocation radius (the unsigned bound len - radius wraps)
-    k.radius = (int32_t)((10.0 * sampling_rate) / 1000.0);
-    if (k.c.nslope == 0 || (uint64_t)a.ns < (uint64_t)k.radius) return RSPT_HIP_ERR_ARG;
-    // peak_detector_offline's constructor adds the baseline: a 0.5 Hz first-order low-pass
-    if (!design_iir(kFiltLowPass, 1, sampling_rate, 0.5, 0.0, k.lf, k.lb)) return RSPT_HIP_ERR_ARG;
-    a.work = (uint8_t*)d_work;
-    return by_bps(p->g.bps, [&](auto bb) {
-        constexpr int B = decltype(bb)::value;
-        return peak_launch(p, d_sig ? &k_peak_offline<B, true> : &k_peak_offline<B, false>, a, k, stream);
-    });
-}
-
-// ---- multi-GPU gather over RCCL.  RCCL is bound at run time: a process that never gathers (the C++ drop-in on one
-// GPU, the tests on the CPU box) does not load it.  A communicator must never cross library instances -- an ncclComm_t made by one
-// copy of RCCL is garbage to another (PyTorch wheels bundle their own librccl.so next to /opt/rocm's) -- so the binding goes to the
-// copy the process has ALREADY mapped (that is where the caller's ncclComm_t came from); only a process without any gets
-// librccl.so.1 from the loader's path; a process with two different copies mapped is refused unless RSPT_RCCL_LIB names the one.
-namespace {
-struct Rccl {
-    int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-    int (*Send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*Recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    bool ok = false;
-};
-constexpr int kNcclUint8 = 1, kNcclUint64 = 5;  // ncclDataType_t (rccl.h)
-int collect_rccl(struct dl_phdr_info* info, size_t, void* data) {
-    auto* v = static_cast<std::vector<std::string>*>(data);
-    if (info->dlpi_name && strstr(info->dlpi_name, "librccl.so")) {
-        char real[PATH_MAX];
-        const std::string path = realpath(info->dlpi_name, real) ? real : info->dlpi_name;
-        bool seen = false;
-        for (const auto& q : *v) seen = seen || q == path;
-        if (!seen) v->push_back(path);
-    }
-    return 0;
-}
-}  // namespace
-static const Rccl& rccl() {
-    static Rccl r = [] {
-        Rccl q;
-        void* h = nullptr;
-        if (const char* want = getenv("RSPT_RCCL_LIB")) {
-            h = dlopen(want, RTLD_NOW | RTLD_LOCAL);
-        } else {
-            std::vector<std::string> mapped;
-            dl_iterate_phdr(collect_rccl, &mapped);
-            if (mapped.size() > 1) return q;  // two copies in one process: which one made the caller's communicator is not ours to guess
-            if (mapped.size() == 1) {
-                h = dlopen(mapped[0].c_str(), RTLD_NOW | RTLD_NOLOAD | RTLD_LOCAL);  // the instance already in the process
-            } else {
-                h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-                if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-            }
-        }
-        if (!h) return q;
-        q.AllGather = reinterpret_cast<decltype(q.AllGather)>(dlsym(h, "ncclAllGather"));
-        q.Send = reinterpret_cast<decltype(q.Send)>(dlsym(h, "ncclSend"));
-        q.Recv = reinterpret_cast<decltype(q.Recv)>(dlsym(h, "ncclRecv"));
-        q.GroupStart = reinterpret_cast<decltype(q.GroupStart)>(dlsym(h, "ncclGroupStart"));
-        q.GroupEnd = reinterpret_cast<decltype(q.GroupEnd)>(dlsym(h, "ncclGroupEnd"));
-        q.ok = q.AllGather && q.Send && q.Recv && q.GroupStart && q.GroupEnd;
-        return q;
-    }();
-    return r;
-}
-
-int rspt_hip_gather_sizes(rspt_hip_packer* p, void* comm, int world, const uint64_t* d_total, uint64_t* d_totals, uint64_t* h_totals, void* stream) {
-    if (!p || !comm || world < 1 || !d_total || !d_totals) return RSPT_HIP_ERR_ARG;
-    const Rccl& R = rccl();
-    if (!R.ok) return RSPT_HIP_ERR_UNSUPPORTED;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (R.AllGather(d_total, d_totals, 1, kNcclUint64, comm, st) != 0) return RSPT_HIP_ERR_LAUNCH;
-    if (h_totals) HIPCHK(p, hipMemcpyAsync(h_totals, d_totals, (size_t)world * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_gather_payload(rspt_hip_packer* p, void* comm, int rank, int world, int root, const void* d_packed, const uint64_t* h_totals,
-                            void* d_recv, size_t recv_stride, void* stream) {
-    if (!p || !comm || world < 1 || rank < 0 || rank >= world || root < 0 || root >= world || !d_packed || !h_totals) return RSPT_HIP_ERR_ARG;
-    if (rank == root && !d_recv) return RSPT_HIP_ERR_ARG;
-    if (recv_stride & 15) return RSPT_HIP_ERR_ARG;  // (every rank's container must land 16-byte aligned: rspt_hip_decompress_packed_dev)
-    const Rccl& R = rccl();
-    if (!R.ok) return RSPT_HIP_ERR_UNSUPPORTED;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    for (int r = 0; r < world; ++r)
-        if (h_totals[r] > recv_stride) return RSPT_HIP_ERR_DST_TOO_SMALL;  // (every rank sees the same sizes and the same stride: nobody posts anything)
-    // one group: the root's receives and the peers' sends are matched pairwise, straight over each peer's own link to the root
-    if (R.GroupStart() != 0) return RSPT_HIP_ERR_LAUNCH;
-    int rc = 0;
-    if (rank == root) {
-        for (int r = 0; r < world && !rc; ++r)
-            if (r != root && h_totals[r]) rc = R.Recv((uint8_t*)d_recv + (size_t)r * recv_stride, (size_t)h_totals[r], kNcclUint8, r, comm, st);
-    } else if (h_totals[rank]) {
-        rc = R.Send(d_packed, (size_t)h_totals[rank], kNcclUint8, root, comm, st);
-    }
-    if (R.GroupEnd() != 0 || rc) return RSPT_HIP_ERR_LAUNCH;
-    if (rank == root && h_totals[root])
-        HIPCHK(p, hipMemcpyAsync((uint8_t*)d_recv + (size_t)root * recv_stride, d_packed, (size_t)h_totals[root], hipMemcpyDeviceToDevice, st));
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_gather_containers(rspt_hip_packer* p, void* comm, int rank, int world, int root, const void* d_packed, const uint64_t* d_total,
-                               void* d_recv, size_t recv_stride, uint64_t* h_totals, void* stream) {
-    if (!p || !h_totals || world < 1) return RSPT_HIP_ERR_ARG;
-    HIPCHK(p, hipSetDevice(p->device));
-    if (p->gat_world < world) {  // (a few words, kept with the handle)
-        p->gat_world = 0;
-        if (hipMalloc(p->gat_totals.out(), (size_t)world * sizeof(uint64_t)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        p->gat_world = world;
-    }
-    uint64_t* d_all = p->gat_totals;
-    int rc = rspt_hip_gather_sizes(p, comm, world, d_total, d_all, h_totals, stream);
-    if (rc == RSPT_HIP_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = RSPT_HIP_ERR_LAUNCH;  // the sizes are on the host now
-    if (rc == RSPT_HIP_OK) rc = rspt_hip_gather_payload(p, comm, rank, world, root, d_packed, h_totals, d_recv, recv_stride, stream);
-    return rc;
-}
-
-// The same gather without a host synchronisation in the step (what rspt_amd/shard.py LaggedGather does over torch.distributed):
-// the sizes of step i travel by a device all-gather and a copy into page-locked memory of the handle, on the handle's own gather
-// stream behind an event on `stream`; the host reads them when it posts the payload -- one step later, when they have long
-// arrived -- again on the gather stream, so that the payload of step i overlaps the kernels of step i + 1.
-static int gather_lag_ensure(rspt_hip_packer* p, int world) {
-    if (p->lag.world >= world) return RSPT_HIP_OK;
-    LagGather l;
-    bool ok = hipStreamCreateWithFlags(l.stream.out(), hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 2; ++i) {
-        ok = ok && hipMalloc(l.dtotals[i].out(), (size_t)world * sizeof(uint64_t)) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)l.htotals[i].out(), (size_t)world * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(l.ev_in[i].out(), hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(l.ev_sizes[i].out(), hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(l.ev_payload[i].out(), hipEventDisableTiming) == hipSuccess;
-    }
-    if (!ok) return RSPT_HIP_ERR_ALLOC;
-    if (p->lag.stream) HIPCHK(p, hipStreamSynchronize(p->lag.stream));  // (nothing may still use the smaller set it replaces)
-    l.world = world;
-    p->lag = std::move(l);
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_gather_post_sizes(rspt_hip_packer* p, void* comm, int world, const uint64_t* d_total, int slot, void* stream) {
-    if (!p || !comm || world < 1 || !d_total || slot < 0 || slot > 1) return RSPT_HIP_ERR_ARG;
-    HIPCHK(p, hipSetDevice(p->device));
-    int rc = gather_lag_ensure(p, world);
-    if (rc) return rc;
-    HIPCHK(p, hipEventRecord(p->lag.ev_in[slot], (hipStream_t)stream));  // d_total (and the container) are written on `stream`
-    HIPCHK(p, hipStreamWaitEvent(p->lag.stream, p->lag.ev_in[slot], 0));
-    rc = rspt_hip_gather_sizes(p, comm, world, d_total, p->lag.dtotals[slot], p->lag.htotals[slot], (void*)p->lag.stream);
-    if (rc) return rc;
-    HIPCHK(p, hipEventRecord(p->lag.ev_sizes[slot], p->lag.stream));
-    p->lag.posted[slot] = true;
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_gather_post_payload(rspt_hip_packer* p, void* comm, int rank, int world, int root, const void* d_packed, int slot, void* d_recv,
-                                 size_t recv_stride, uint64_t* h_totals) {
-    if (!p || slot < 0 || slot > 1 || !p->lag.posted[slot] || world > p->lag.world) return RSPT_HIP_ERR_ARG;
-    HIPCHK(p, hipSetDevice(p->device));
-    HIPCHK(p, hipEventSynchronize(p->lag.ev_sizes[slot]));  // (a step old in the steady state: does not wait)
-    p->lag.posted[slot] = false;
-    if (h_totals) memcpy(h_totals, p->lag.htotals[slot], (size_t)world * sizeof(uint64_t));
-    const int rc = rspt_hip_gather_payload(p, comm, rank, world, root, d_packed, p->lag.htotals[slot], d_recv, recv_stride, (void*)p->lag.stream);
-    if (rc) return rc;
-    HIPCHK(p, hipEventRecord(p->lag.ev_payload[slot], p->lag.stream));
-    return RSPT_HIP_OK;
-}
-
-int rspt_hip_gather_wait(rspt_hip_packer* p, int slot, void* stream) {
-    if (!p || slot < 0 || slot > 1) return RSPT_HIP_ERR_ARG;
-    if (!p->lag.ev_payload[slot]) return RSPT_HIP_OK;  // (nothing was ever posted)
-    HIPCHK(p, hipSetDevice(p->device));
-    HIPCHK(p, hipStreamWaitEvent((hipStream_t)stream, p->lag.ev_payload[slot], 0));
-    return RSPT_HIP_OK;
-}
-
 long long rspt_hip_debug_read(rspt_hip_packer* p, int which, void* host_buf, size_t cap) {
     if (!p || !host_buf || p->ws.cap_blocks == 0) return RSPT_HIP_ERR_ARG;
     if (hipSetDevice(p->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return RSPT_HIP_ERR_LAUNCH;
@@ -2750,4 +1174,9 @@ int rspt_hip_stage_times(rspt_hip_packer* p, float* ms, int n) {
     return RSPT_HIP_OK;
 }
 
+#include "host_pipeline.hip"
+#include "host_gather.hip"
+
 }  // extern "C"
+
+#include "host_stages.hip"  // (templates: outside the block; rspt_hip.h declares every entry extern "C")

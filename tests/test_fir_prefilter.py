@@ -242,6 +242,36 @@ def test_gpu_fir_back_to_back_kernels_without_host_sync(api, record):
 
 
 @pytest.mark.gpu
+def test_gpu_fir_halo_grows_between_back_to_back_calls_without_host_sync(api):
+    """two in-place calls on one handle and one stream, no host synchronisation between them, the second with the larger halo:
+    the handle replaces its halo buffer while the first call may still be in flight, and both results are exact.
+
+    3 ch x int16 x 20000, 2 blocks.  With 3 channels a workgroup's kFirThreads = 256 lanes hold 85 rows of channels, so a chunk
+    is 85 x kFirR = 85 x 16 = 1360 rows; 20000 rows allow at most 20000 // 1360 = 14 spans, each rounded up to whole chunks:
+    2 x 1360 = 2720 rows, ceil(20000 / 2720) = 8 spans per block for the 9-tap and the 257-tap kernel alike (4 (K - 1) <= 1360).
+    An in-place call stages the K - 1 rows in front of every span but the first: 2 x 7 pieces of 8 rows, then 2 x 7 of 256."""
+    import torch
+
+    bps, nch, ns = 2, 3, 20000
+    pk = api.new_hzr(bps, nch, ns)
+    data = np.concatenate([fc.cases._rand_native(nch, ns, bps, 910 + b, 1 << (8 * bps - 2)) for b in range(2)])
+    k_small, k_large = fc._rand_kernel(9, 911, 4), fc._rand_kernel(257, 912, 8)
+    a = torch.from_numpy(data).cuda()
+    b = a.clone()
+    torch.cuda.synchronize()
+    pk.fir_prefilter_batch(a, k_small)
+    pk.fir_prefilter_batch(b, k_large)
+    torch.cuda.synchronize()
+    bb = bps * nch * ns
+    for buf, k in ((a, k_small), (b, k_large)):
+        got = buf.cpu().numpy()
+        for i in range(2):
+            want = fc.fir_prefilter(data[i * bb : (i + 1) * bb], bps, nch, ns, k).tobytes()
+            assert got[i * bb : (i + 1) * bb].tobytes() == want, (len(k), i)
+    pk.close()
+
+
+@pytest.mark.gpu
 def test_gpu_fir_rejects_bad_arguments(api):
     import torch
 

@@ -57,7 +57,7 @@ class Parent:
 
 
 def segment_rows(W, rows):
-    """median_segment_rows of rspt_hip.hip: the segment capacity S = W - 1 + L"""
+    """median_segment_rows of host_stages.hip: the segment capacity S = W - 1 + L"""
     want = 8 * (W - 1)
     S = (1 << 16) if want <= (1 << 16) else (1 << 17) if want <= (1 << 17) else (1 << 18)
     return min(S, W - 1 + rows)
