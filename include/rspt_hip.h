@@ -362,6 +362,47 @@ int rspt_hip_iir_state_bytes(rspt_hip_packer* p, size_t* bytes); /* nch * 88 */
 int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
                                       int init_nr_samples, void* d_state, void* stream);
 
+/* ---- a cascade of IIR filters: the reference's objects chained per sample, truncated once ---------------------------
+ * The reference's filters return double and its users chain them per sample: lp->filter_opt(hp->filter_opt(x)) for a high-pass
+ * in front of a low-pass, three filters in peak_detector.h:89-91.  Two calls of rspt_hip_iir_prefilter_batch_dev do NOT give
+ * that answer (the intermediate result would be truncated and stored in the sample width); this stage does.
+ * Each channel has S objects f_k = i_filter::new_iir(n_k, d_k, nc_k), k = 0 .. S-1, 1 <= S <= 4; nc_k is 2..5 and may differ per
+ * section; n is the feedback side and d the feed-forward side, as in the IIR pre-filter stage.  On the channel's first sample x0
+ * every section runs f_k->init_history_values((double)x0, init_nr_samples[k]): every section is initialised with x0, the RAW
+ * first sample, not with the section's own input; init_nr_samples[k] = 0 (range 0 .. 2^28) runs nothing and leaves the rings
+ * zero, the right start for a section behind a high-pass.  Then, for every sample,
+ *     v = (double)x;  for k in 0..S-1:  v = use_filter[k] ? f_k->filter(v) : f_k->filter_opt(v);
+ *     y = (int32_t)v, as x86-64 truncates (every NaN, +-inf and |v| >= 2^31 -> INT32_MIN); the low bps bytes are stored in place
+ * Every product and sum is rounded on its own (no fused multiply-add); filter_opt sums in the order of rolling_iir_filter_N_
+ * (every feed-forward term, then the feedback terms), filter in the order of iir_filter.cpp:72-77 (feed-forward and feedback
+ * terms interleaved), so the two round differently.  Intermediate doubles are never truncated: a NaN or inf that leaves section
+ * k enters the rings of section k + 1.  Samples are little-endian.  Bit-identical with the reference's objects chained so.
+ *   nsections        S, 1..4
+ *   n, d             5 * nsections host doubles, section k at 5k; places past nc_k are not read
+ *   nr_coefficients  nsections values nc_k, each 2..5
+ *   init_nr_samples  nsections values, each 0 .. 2^28
+ *   use_filter       nsections bytes, or NULL: filter_opt for every section
+ * Stateless form (rspt_hip_iir_cascade_batch_dev): a fresh chain per (block, channel) -- the per-channel driving of the IIR
+ * pre-filter stage; there is no shared-object mode.
+ * Stream form (rspt_hip_iir_cascade_stream_dev): the blocks of a call are consecutive rows of one recording, one chain per
+ * channel lives in d_state and runs on into the next call.  d_state: rspt_hip_iir_cascade_state_bytes bytes, 8-byte aligned, the
+ * IIR pre-filter's record (88 bytes: double x[5], double y[5], uint64 started) for channel c, section k at byte
+ * 88 * (c * S + k).  All-zero bytes are a fresh chain; `started` of section 0 decides whether a channel initialises, and a call
+ * writes all S of them.  With S = 1 the layout is rspt_hip_iir_prefilter_stream_dev's own, and a state may move between the two
+ * entries.  init_nr_samples is read only by a channel whose state is fresh.
+ * RSPT_HIP_ERR_ARG for nsections outside 1..4, an nc_k outside 2..5, a bad init, NULL arrays (use_filter excepted), a misaligned
+ * or NULL state, nblocks = 0 or nblocks * nch >= 2^31; RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels, before anything is
+ * launched, and for a stream call of 2^31 - 2^17 rows (nblocks * ns) or more.  Runs of 32 rows and more (a block; in the
+ * stream form a call) take the pipelined kernel -- one recurrence wave per section, so the time per sample is the slowest
+ * section's, not the sum --, shorter ones one thread per channel.  Asynchronous on `stream`, stream-ordered per
+ * handle and per state; the stage allocates nothing. */
+int rspt_hip_iir_cascade_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                   const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* stream);
+int rspt_hip_iir_cascade_state_bytes(rspt_hip_packer* p, size_t nsections, size_t* bytes); /* nch * nsections * 88 */
+int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                    const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state,
+                                    void* stream);
+
 /* ---- optional stage in front of compress: the reference's FIR pre-filter ---------------------------------------
  * i_filter::new_fir(kernel, kernel_size), init_history_values(first sample of the channel, n), filter_opt on every sample
  * (lib_rspt/lib_filter/fir_filter.cpp), result truncated to int32 and stored in the native sample width, on nblocks

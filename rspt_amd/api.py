@@ -26,6 +26,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_decompress_batch_dev", "rspt_hip_decompress_packed_dev", "rspt_hip_pack_bound", "rspt_hip_pack_batch_dev", "rspt_hip_stream", "rspt_hip_synchronize", "rspt_hip_set_profiling", "rspt_hip_stage_count",
     "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_design_iir",
     "rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev",
+    "rspt_hip_iir_cascade_batch_dev", "rspt_hip_iir_cascade_state_bytes", "rspt_hip_iir_cascade_stream_dev",
     "rspt_hip_median_state_bytes", "rspt_hip_median_filter_stream_dev",
     "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
     "rspt_hip_prdn_batch_dev", "rspt_hip_native_to_i32_batch_dev", "rspt_hip_i32_to_native_batch_dev",
@@ -120,6 +121,10 @@ def lib():
     L.rspt_hip_iir_prefilter_stream_dev.restype = C.c_int
     L.rspt_hip_iir_prefilter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
                                                     C.c_void_p, C.c_void_p]
+    _casc = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), _u8p]
+    L.rspt_hip_iir_cascade_batch_dev.restype, L.rspt_hip_iir_cascade_batch_dev.argtypes = C.c_int, _casc + [C.c_void_p]
+    L.rspt_hip_iir_cascade_state_bytes.restype, L.rspt_hip_iir_cascade_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
+    L.rspt_hip_iir_cascade_stream_dev.restype, L.rspt_hip_iir_cascade_stream_dev.argtypes = C.c_int, _casc + [C.c_void_p, C.c_void_p]
     L.rspt_hip_fir_state_bytes.restype, L.rspt_hip_fir_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
     L.rspt_hip_fir_prefilter_stream_dev.restype = C.c_int
     L.rspt_hip_fir_prefilter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p, C.c_void_p]
@@ -440,6 +445,50 @@ class SignalPacker:
         rc = self._L.rspt_hip_iir_prefilter_batch_dev(self._h, d_buf.data_ptr(), nblocks, nn.ctypes.data_as(C.POINTER(C.c_double)),
                                                       dd.ctypes.data_as(C.POINTER(C.c_double)), nn.size, init_nr_samples, int(bool(per_channel)), st)
         self._check("rspt_hip_iir_prefilter_batch_dev", rc)
+        return d_buf
+
+    def iir_cascade_state_bytes(self, nsections):
+        n = C.c_size_t()
+        self._check("rspt_hip_iir_cascade_state_bytes", self._L.rspt_hip_iir_cascade_state_bytes(self._h, int(nsections), C.byref(n)))
+        return n.value
+
+    def iir_cascade_state(self, nsections, device=None):
+        """A zeroed state for iir_cascade_batch(state=...) with nsections sections: a fresh chain for every channel."""
+        import torch
+
+        return torch.zeros(self.iir_cascade_state_bytes(nsections), dtype=torch.uint8, device=device if device is not None else "cuda")
+
+    def iir_cascade_batch(self, d_buf, sections, stream=None, state=None):
+        """1 to 4 reference IIR filters per channel, chained in double and truncated once (rspt_hip.h: rspt_hip_iir_cascade_batch_dev),
+        on device-resident blocks, in place; asynchronous.  lp->filter_opt(hp->filter_opt(x)) is sections=[(hp_n, hp_d), (lp_n, lp_d, 0)].
+        sections: a list of (n, d), (n, d, init_nr_samples) or (n, d, init_nr_samples, use_filter); init_nr_samples defaults to
+        2000, use_filter (the section runs filter() instead of filter_opt()) to False.
+        state: None (a fresh chain per block and channel), or an iir_cascade_state(len(sections)) tensor: the blocks are then
+        consecutive pieces of one recording, one chain per channel running through them and on into the next call."""
+        import torch
+
+        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous()
+        nblocks = d_buf.numel() // self.block_bytes
+        assert nblocks * self.block_bytes == d_buf.numel()
+        S = len(sections)
+        if not 1 <= S <= 4:
+            raise ValueError("iir_cascade_batch: 1 to 4 sections")
+        nn, dd = np.zeros((S, 5)), np.zeros((S, 5))
+        nc, init, filt = np.zeros(S, dtype=np.uint32), np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.uint8)
+        for k, sec in enumerate(sections):
+            n, d = np.asarray(sec[0], dtype=np.float64).reshape(-1), np.asarray(sec[1], dtype=np.float64).reshape(-1)
+            if n.size != d.size or not 2 <= n.size <= 5:
+                raise ValueError("iir_cascade_batch: section %d needs 2 to 5 coefficients on each side" % k)
+            nn[k, : n.size], dd[k, : d.size] = n, d
+            nc[k], init[k], filt[k] = n.size, (sec[2] if len(sec) > 2 else 2000), bool(sec[3]) if len(sec) > 3 else False
+        st = stream if stream is not None else torch.cuda.current_stream(d_buf.device).cuda_stream
+        args = (self._h, d_buf.data_ptr(), nblocks, S, nn.ctypes.data_as(C.POINTER(C.c_double)), dd.ctypes.data_as(C.POINTER(C.c_double)),
+                nc.ctypes.data_as(C.POINTER(C.c_uint32)), init.ctypes.data_as(C.POINTER(C.c_int32)), filt.ctypes.data_as(_u8p))
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.iir_cascade_state_bytes(S)
+            self._check("rspt_hip_iir_cascade_stream_dev", self._L.rspt_hip_iir_cascade_stream_dev(*args, state.data_ptr(), st))
+        else:
+            self._check("rspt_hip_iir_cascade_batch_dev", self._L.rspt_hip_iir_cascade_batch_dev(*args, st))
         return d_buf
 
     def _window_call_buffers(self, d_src, d_dst, stream):

@@ -1,4 +1,4 @@
-// host_stages.hip -- the host side of the analysis stages: IIR, FIR, median, PRDN, converters, R-peak detectors; each stage's
+// host_stages.hip -- the host side of the analysis stages: IIR, IIR cascade, FIR, median, PRDN, converters, R-peak detectors; each stage's
 // launchers directly in front of its entries.  Included by rspt_hip.hip.
 
 // The widest handle the filter, median, peak and PRDN stages are verified on (tests/test_gpu_wide_channels.py): beyond it they
@@ -124,6 +124,74 @@ int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nb
                                       int init_nr_samples, void* d_state, void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
     return iir_call(p, d_buf, nblocks, n, d, nr_coefficients, init_nr_samples, 0, d_state, stream);
+}
+
+// ---- IIR cascade (iir_cascade.hip) ----
+// One run of `ns` rows per (block, channel): the stateless call's nblocks blocks of g.ns rows, or (CARRY) the call's blocks as one
+// block of nblocks * g.ns rows.  Whether a channel is fresh is known on the device only and the pipelined kernel starts from any
+// init_nr_samples, so the route depends on the run's length alone.
+template <int BPS, bool CARRY>
+static void launch_iir_cascade(rspt_hip_packer* p, uint8_t* buf, uint32_t B, uint32_t ns, uint64_t block_bytes, const CascadeArgs& a, IirCarry* state,
+                               hipStream_t st) {
+    const dim3 grid((B * p->g.nch + 63) / 64);
+    if (ns >= kCascChunk) {
+        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;  // (block_bytes is a multiple of BPS)
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64 * casc_waves(a.nsec)), 0, st, buf, p->g.nch, ns, block_bytes, a, B, state); };
+        if (al) go(&k_iir_cascade_pipe<BPS, (BPS == 4 || BPS == 2), CARRY>);
+        else go(&k_iir_cascade_pipe<BPS, false, CARRY>);
+        return;
+    }
+    hipLaunchKernelGGL((k_iir_cascade<BPS, CARRY>), grid, dim3(64), 0, st, buf, p->g.nch, ns, block_bytes, a, B, state);
+}
+
+// Both cascade entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+static int iir_cascade_call(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d,
+                            const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state, void* stream) {
+    if (!p || !d_buf || !n || !d || !nr_coefficients || !init_nr_samples || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (nsections < 1 || nsections > kCascMaxSections) return RSPT_HIP_ERR_ARG;
+    CascadeArgs a{};
+    a.nsec = (uint32_t)nsections;
+    for (size_t k = 0; k < nsections; ++k) {
+        const uint32_t nc = nr_coefficients[k];
+        if (nc < 2 || nc > 5 || init_nr_samples[k] < 0 || init_nr_samples[k] > (1 << 28)) return RSPT_HIP_ERR_ARG;
+        for (uint32_t i = 0; i < nc; ++i) {  // (places past nc_k are not read)
+            a.s[k].n[i] = n[5 * k + i];
+            a.s[k].d[i] = d[5 * k + i];
+        }
+        a.s[k].nc = nc;
+        a.s[k].init_steps = 4 * init_nr_samples[k];
+        if (use_filter && use_filter[k]) a.use_filter |= 1u << k;
+    }
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    const uint64_t rows = (uint64_t)nblocks * p->g.ns;
+    if (d_state && rows >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    by_bps(p->g.bps, [&](auto bps) {
+        constexpr int BPS = decltype(bps)::value;
+        if (d_state) launch_iir_cascade<BPS, true>(p, (uint8_t*)d_buf, 1u, (uint32_t)rows, rows * p->g.nch * BPS, a, (IirCarry*)d_state, st);
+        else launch_iir_cascade<BPS, false>(p, (uint8_t*)d_buf, (uint32_t)nblocks, p->g.ns, (uint64_t)p->g.block_bytes, a, nullptr, st);
+    });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_iir_cascade_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                   const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* stream) {
+    return iir_cascade_call(p, d_buf, nblocks, nsections, n, d, nr_coefficients, init_nr_samples, use_filter, nullptr, stream);
+}
+
+int rspt_hip_iir_cascade_state_bytes(rspt_hip_packer* p, size_t nsections, size_t* bytes) {
+    if (!p || !bytes || nsections < 1 || nsections > kCascMaxSections) return RSPT_HIP_ERR_ARG;
+    *bytes = (size_t)p->g.nch * nsections * sizeof(IirCarry);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                    const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state,
+                                    void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return iir_cascade_call(p, d_buf, nblocks, nsections, n, d, nr_coefficients, init_nr_samples, use_filter, d_state, stream);
 }
 
 // ---- the frame of the sliding-window stages (FIR, median) ----

@@ -1,0 +1,470 @@
+// iir_cascade.hip -- a cascade of 1 to 4 reference IIR filters per channel, chained in double and truncated once
+// (rspt_hip_iir_cascade_batch_dev / _stream_dev; semantics: rspt_hip.h).
+//
+// The reference's filter objects return double and its users chain them per sample -- lp->filter_opt(hp->filter_opt(x)), or the
+// three filters of peak_detector.h:89-91 -- so what enters section k + 1 is section k's untruncated output, NaN and inf
+// included, and only the last section's result is converted to int32.  Each section is one i_filter::new_iir object
+// (iir_filter.cpp:46-116) restated as in filter.hip (IirState), run through filter_opt() -- all feed-forward terms first, then the
+// feedback terms -- or through filter() -- the terms interleaved -- and initialised with the channel's RAW first sample.
+#include "common.hpp"
+
+// NO contraction in this file either, for the reason written in filter.hip: every product and sum is rounded on its own.
+#pragma clang fp contract(off)
+
+namespace rspt {
+
+constexpr uint32_t kCascMaxSections = 4;
+struct CascadeArgs {
+    IirCoef s[kCascMaxSections];
+    uint32_t nsec;        // 1..4
+    uint32_t use_filter;  // bit k: section k runs filter() instead of filter_opt()
+};
+
+template <class F>
+__device__ __forceinline__ void casc_by_nc(uint32_t nc, F&& f) {  // (nc is wave-uniform: a scalar branch)
+    switch (nc) {
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 5>{}); break;
+    }
+}
+
+// A section's rings outside the code that knows its order: five places each, newest first, the places past nc - 1 zero.
+template <int NC>
+__device__ __forceinline__ void casc_get(IirState<NC>& f, const double (&x)[5], const double (&y)[5]) {
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        f.x[i] = x[i];
+        f.y[i] = y[i];
+    }
+}
+template <int NC>
+__device__ __forceinline__ void casc_put(const IirState<NC>& f, double (&x)[5], double (&y)[5]) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        x[i] = i < NC ? f.x[i < NC ? i : 0] : 0.0;
+        y[i] = i < NC ? f.y[i < NC ? i : 0] : 0.0;
+    }
+}
+
+// init_history_values (iir_filter.cpp:109-113) on a fresh object: 4 * nr_samples calls of filter() on x0, as k_iir_pipe runs them
+__device__ __forceinline__ void casc_init(const IirCoef& c, double x0, double (&x)[5], double (&y)[5]) {
+    casc_by_nc(c.nc, [&](auto ncv) {
+        constexpr int NC = decltype(ncv)::value;
+        IirState<NC> f;
+        f.clear();
+        int32_t i = 0;
+        for (; i < c.init_steps && i < NC; ++i) f.step(c, x0);  // (until the x ring holds nothing but x0)
+        if (i < c.init_steps) {
+            double P[NC];
+#pragma unroll
+            for (int k = 0; k < NC; ++k) P[k] = c.d[k] * x0;
+#pragma unroll 4
+            for (; i < c.init_steps; ++i) f.step_const(c, P);
+        }
+        casc_put<NC>(f, x, y);
+    });
+}
+
+// One sample through one section: filter() is IirState::step; filter_opt() is one expression evaluated left to right
+// (iir_filter.cpp:26-44), every feed-forward term first.
+template <int NC, bool FILTER>
+__device__ __forceinline__ double casc_step(const IirCoef& c, IirState<NC>& f, double in) {
+    if (FILTER) return f.step(c, in);
+    f.shift(in);
+    double a = c.d[0] * f.x[0];
+#pragma unroll
+    for (int i = 1; i < NC; ++i) a = a + c.d[i] * f.x[i];
+#pragma unroll
+    for (int i = 1; i < NC; ++i) a = a - c.n[i] * f.y[i];
+    f.y[0] = a;
+    return a;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The plain kernel: one thread per (block, channel) runs the chain as written in rspt_hip.h, sample by sample.  It serves rows
+// shorter than a chunk of the pipelined kernel.  CARRY: one run of ns rows (nblocks = 1), the chain of channel ch in
+// state[ch * nsec ..]; `started` of section 0 decides whether the channel initialises.
+template <int BPS, bool CARRY>
+__global__ __launch_bounds__(64) void k_iir_cascade(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, CascadeArgs a, uint32_t nblocks,
+                                                    IirCarry* __restrict__ state) {
+    const uint32_t t = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t b = t / nch, ch = t - b * nch;
+    if (b >= nblocks) return;
+    const size_t stride = (size_t)nch * BPS;
+    const bool aligned = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0 && (block_bytes % BPS) == 0;
+    uint8_t* p = buf + (size_t)b * block_bytes + (size_t)ch * BPS;
+    IirCarry* const cs = CARRY ? state + (size_t)ch * a.nsec : nullptr;
+    const bool started = CARRY && cs[0].started != 0;
+    const double x0 = (double)sample_load<BPS>(p, aligned);
+    double x[kCascMaxSections][5], y[kCascMaxSections][5];
+#pragma unroll
+    for (uint32_t k = 0; k < kCascMaxSections; ++k) {
+        if (k >= a.nsec) continue;
+        if (started) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                x[k][i] = cs[k].x[i];
+                y[k][i] = cs[k].y[i];
+            }
+        } else {
+            casc_init(a.s[k], x0, x[k], y[k]);
+        }
+    }
+    for (uint32_t s = 0; s < ns; ++s) {
+        uint8_t* q = p + (size_t)s * stride;
+        double v = (double)sample_load<BPS>(q, aligned);
+#pragma unroll
+        for (uint32_t k = 0; k < kCascMaxSections; ++k) {
+            if (k >= a.nsec) continue;
+            const bool filt = (a.use_filter >> k) & 1u;
+            casc_by_nc(a.s[k].nc, [&](auto ncv) {
+                constexpr int NC = decltype(ncv)::value;
+                IirState<NC> f;
+                casc_get<NC>(f, x[k], y[k]);
+                v = filt ? casc_step<NC, true>(a.s[k], f, v) : casc_step<NC, false>(a.s[k], f, v);
+                casc_put<NC>(f, x[k], y[k]);
+            });
+        }
+        sample_store<BPS>(q, trunc_i32_c(v), aligned);  // C truncation, once, behind the last section
+    }
+    if (CARRY) {
+#pragma unroll
+        for (uint32_t k = 0; k < kCascMaxSections; ++k) {
+            if (k >= a.nsec) continue;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                cs[k].x[i] = x[k][i];
+                cs[k].y[i] = y[k][i];
+            }
+            cs[k].started = 1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The pipelined kernel, in the manner of k_iir_pipe: lane <-> channel in every wave, and the wave that holds a ring issues only
+// what depends on it.  A chunk of 32 samples per lane travels through 2 S + 1 stages, one stage per tick (one workgroup barrier),
+// in ONE LDS tile [sample][lane] of doubles that every stage rewrites in place (a lane reads and writes its own column only):
+//   tick j              two producer waves load the samples (two chunks ahead), convert them and write section 0's
+//                       feed-forward sums of half a chunk each (filter(): the samples themselves, as doubles)
+//   tick j + 2k + 1     section k's recurrence wave: sum -> output, its y ring in registers (filter(): both rings)
+//   tick j + 2k + 2     section k + 1's feed-forward wave: outputs of section k -> feed-forward sums of section k + 1, the inputs
+//                       in front of the chunk in registers (filter(): nothing to do, the tile passes as it is)
+//   tick j + 2S         the store wave truncates the last section's outputs (trunc_i32_c) and stores them
+// So S recurrences run at once, on chunks two ticks apart, and the time per sample is the slowest wave's, not the sum.  A chunk
+// owns tile j mod 9 from its producer to its store; 2 S + 1 <= 9 chunks are under way.  Waves 0..S-1 are the recurrence waves
+// (consecutive waves go to different SIMDs), then the S - 1 feed-forward waves, the two producers, the store wave.
+//
+// Every section starts from the channel's raw first sample x0 (init_history_values on a fresh object; all recurrence waves run it
+// at once in front of the first tick), and what its x ring then holds -- x0 in the first min(init_steps, nc) places, 0.0 behind --
+// stands in front of the run for the wave that forms its feed-forward sums, so any init_steps will do.  CARRY: ONE run of ns rows
+// (nblocks = 1); a channel whose section 0 has started takes every section's rings from state[ch * S + k] instead, and each
+// ring is written back by the wave that holds it, behind the run's last chunk.  A wave reads the state in front of the first
+// barrier and writes only places that no other wave reads, or (the producers' x ring) a tick later, behind a barrier.
+constexpr uint32_t kCascChunk = 32, kCascProd = 2, kCascPart = kCascChunk / kCascProd;
+constexpr uint32_t kCascSlots = 2 * kCascMaxSections + 1;
+constexpr uint32_t kCascGroup = 16;  // samples a wave reads from the tile together, works on, and writes together
+static_assert(kCascPart == kCascGroup && kCascChunk % kCascGroup == 0, "a producer takes one group of a chunk");
+__host__ __device__ constexpr uint32_t casc_waves(uint32_t nsec) { return 2 * nsec + 2; }
+constexpr uint32_t kCascMaxThreads = 64 * casc_waves(kCascMaxSections);
+struct CascLds {
+    double v[kCascSlots][kCascChunk][64];
+};
+// 144 KiB of static LDS: one workgroup per CU, on a part with 160 KiB per workgroup (gfx950)
+static_assert(sizeof(CascLds) <= 160 * 1024, "k_iir_cascade_pipe: the tiles must fit one CU's LDS");
+
+// section k's recurrence over one chunk, in place: feed-forward sums (filter(): inputs) -> outputs
+template <int NC, bool FILTER>
+__device__ __forceinline__ void casc_rec_chunk(double (*T)[64], uint32_t lane, uint32_t cnt, const IirCoef& c, IirState<NC>& f) {
+    auto rec = [&](double a) -> double {
+        if (FILTER) return f.step(c, a);
+#pragma unroll
+        for (int i = 1; i < NC; ++i) a = a - c.n[i] * f.y[i - 1];  // (y[i-1] now = y[i] of the step being taken)
+#pragma unroll
+        for (int i = NC - 1; i > 0; --i) f.y[i] = f.y[i - 1];
+        f.y[0] = a;
+        return a;
+    };
+    if (cnt == kCascChunk) {
+#pragma unroll 1
+        for (uint32_t e0 = 0; e0 < kCascChunk; e0 += kCascGroup) {
+            double v[kCascGroup];
+#pragma unroll
+            for (uint32_t e = 0; e < kCascGroup; ++e) v[e] = T[e0 + e][lane];
+#pragma unroll
+            for (uint32_t e = 0; e < kCascGroup; ++e) v[e] = rec(v[e]);
+#pragma unroll
+            for (uint32_t e = 0; e < kCascGroup; ++e) T[e0 + e][lane] = v[e];
+        }
+    } else {
+        for (uint32_t e = 0; e < cnt; ++e) T[e][lane] = rec(T[e][lane]);
+    }
+}
+
+// section k's feed-forward sums over one chunk, in place: inputs -> ((d0 x0 + d1 x1) + d2 x2) + ...; x = the inputs in front of
+// the chunk, newest first, and behind it the chunk's last five
+template <int NC>
+__device__ __forceinline__ void casc_ff_chunk(double (*T)[64], uint32_t lane, uint32_t cnt, const IirCoef& c, double (&x)[5]) {
+    constexpr int H = 4;
+    if (cnt == kCascChunk) {
+#pragma unroll 1
+        for (uint32_t e0 = 0; e0 < kCascChunk; e0 += kCascGroup) {
+            double xs[kCascGroup + H], o[kCascGroup];
+#pragma unroll
+            for (int i = 0; i < H; ++i) xs[i] = x[H - 1 - i];
+#pragma unroll
+            for (uint32_t e = 0; e < kCascGroup; ++e) xs[H + e] = T[e0 + e][lane];
+#pragma unroll
+            for (uint32_t e = 0; e < kCascGroup; ++e) {
+                double s = c.d[0] * xs[H + e];
+#pragma unroll
+                for (int i = 1; i < NC; ++i) s = s + c.d[i] * xs[H + e - i];
+                o[e] = s;
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < kCascGroup; ++e) T[e0 + e][lane] = o[e];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) x[i] = xs[kCascGroup + H - 1 - i];
+        }
+    } else {
+        for (uint32_t e = 0; e < cnt; ++e) {
+            const double in = T[e][lane];
+            double s = c.d[0] * in;
+#pragma unroll
+            for (int i = 1; i < NC; ++i) s = s + c.d[i] * x[i - 1];
+            T[e][lane] = s;
+#pragma unroll
+            for (int i = 4; i > 0; --i) x[i] = x[i - 1];
+            x[0] = in;
+        }
+    }
+}
+
+// What every wave of the pipelined kernel knows: its lane's run, its section, and the tick at which it meets chunk 0.
+struct CascWave {
+    uint8_t* p;       // the lane's first sample
+    size_t stride;    // bytes from one sample of the channel to the next
+    uint32_t ns, nchunks, nticks, lane, off;
+    bool valid;       // (lanes past the batch read block 0, channel 0 along with the others and store nothing)
+    bool started;     // CARRY: section 0 of the lane's channel has started
+    bool filt;        // the wave's section runs filter()
+    double x0;        // the run's first sample
+    IirCarry* cs;     // CARRY: the state of the wave's section of the lane's channel
+    double (*tiles)[kCascChunk][64];
+    __device__ __forceinline__ uint32_t count(uint32_t j) const { return min(kCascChunk, ns - j * kCascChunk); }
+};
+
+// Each role is a tick loop of its own with the same number of barriers, so that no role's registers live through another's.
+
+// section k's recurrence: sums -> outputs, its y ring in registers (filter(): both rings); the history initialisation in front
+template <bool CARRY>
+__device__ __forceinline__ void casc_wave_rec(const CascWave& w, const IirCoef& c) {
+    double x[5], y[5];
+    if (w.started) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            x[i] = w.cs->x[i];
+            y[i] = w.cs->y[i];
+        }
+    } else {
+        casc_init(c, w.x0, x, y);
+    }
+    for (uint32_t t = 0; t < w.nticks; ++t) {
+        const uint32_t j = t - w.off;  // (wraps in front of the wave's first chunk)
+        if (j < w.nchunks) {
+            casc_by_nc(c.nc, [&](auto ncv) {
+                constexpr int NC = decltype(ncv)::value;
+                IirState<NC> f;
+                casc_get<NC>(f, x, y);
+                if (w.filt) casc_rec_chunk<NC, true>(w.tiles[j % kCascSlots], w.lane, w.count(j), c, f);
+                else casc_rec_chunk<NC, false>(w.tiles[j % kCascSlots], w.lane, w.count(j), c, f);
+                casc_put<NC>(f, x, y);
+            });
+        }
+        __syncthreads();
+    }
+    if (CARRY && w.valid) {  // the object as it stands behind the run's last sample
+        for (uint32_t i = 0; i < c.nc; ++i) {
+            w.cs->y[i] = y[i];
+            if (w.filt) w.cs->x[i] = x[i];
+        }
+        w.cs->started = 1;
+    }
+}
+
+// section k >= 1's feed-forward sums: outputs of section k - 1 -> sums, the inputs in front of the chunk in registers
+// (filter(): the tile passes as it is, and the recurrence wave holds the x ring)
+template <bool CARRY>
+__device__ __forceinline__ void casc_wave_ff(const CascWave& w, const IirCoef& c) {
+    double x[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) x[i] = w.filt ? 0.0 : w.started ? w.cs->x[i] : (i < c.init_steps && i < (int)c.nc ? w.x0 : 0.0);
+    for (uint32_t t = 0; t < w.nticks; ++t) {
+        const uint32_t j = t - w.off;
+        if (j < w.nchunks && !w.filt) casc_by_nc(c.nc, [&](auto ncv) { casc_ff_chunk<decltype(ncv)::value>(w.tiles[j % kCascSlots], w.lane, w.count(j), c, x); });
+        __syncthreads();
+    }
+    if (CARRY && w.valid && !w.filt) {
+        for (uint32_t i = 0; i < c.nc; ++i) w.cs->x[i] = x[i];
+    }
+}
+
+// a producer: loads its half of every chunk two chunks ahead, converts, writes section 0's feed-forward sums (filter(): the samples)
+template <int BPS, bool ALIGNED, bool CARRY>
+__device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef& c, uint32_t part) {
+    constexpr int H = 4;
+    constexpr uint32_t SET = kCascPart + H;  // its 16 samples and the H in front: element e of chunk j is sample j * 32 + part * 16 - H + e
+    double x[5];  // the inputs in front of the run, newest first; behind the run's last chunk: the run's last inputs
+#pragma unroll
+    for (int i = 0; i < 5; ++i) x[i] = (w.filt || part != 0u) ? 0.0 : w.started ? w.cs->x[i] : (i < c.init_steps && i < (int)c.nc ? w.x0 : 0.0);
+    bool have_last = false;
+    int32_t cur[SET], nxt[SET], nx2[SET];
+    auto load_set = [&](int32_t (&v)[SET], uint32_t j) {
+        const int32_t s0 = (int32_t)(j * kCascChunk + part * kCascPart) - H;
+        if (s0 >= 0 && s0 + (int32_t)SET <= (int32_t)w.ns) {  // (wave-uniform; all but a run's first and last sets)
+            const uint8_t* q = w.p + (size_t)s0 * w.stride;
+#pragma unroll
+            for (uint32_t e = 0; e < SET; ++e) v[e] = sample_load<BPS>(q + (size_t)e * w.stride, ALIGNED);
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < SET; ++e) {
+                int32_t si = s0 + (int32_t)e;
+                si = si < 0 ? 0 : si >= (int32_t)w.ns ? (int32_t)w.ns - 1 : si;  // (clamped: what lies outside is never used as such)
+                v[e] = sample_load<BPS>(w.p + (size_t)si * w.stride, ALIGNED);
+            }
+        }
+    };
+    load_set(cur, 0);
+    if (w.nchunks > 1) load_set(nxt, 1);
+    for (uint32_t t = 0; t < w.nticks; ++t) {
+        const uint32_t j = t;
+        if (j < w.nchunks) {
+            if (j + 2 < w.nchunks) load_set(nx2, j + 2);  // (the loads have two ticks to arrive)
+            double(*T)[64] = w.tiles[j % kCascSlots];
+            const int32_t s0 = (int32_t)(j * kCascChunk + part * kCascPart) - H;
+            double xs[SET];
+#pragma unroll
+            for (uint32_t e = 0; e < SET; ++e) xs[e] = (double)cur[e];
+            if (w.filt) {
+#pragma unroll
+                for (uint32_t e = 0; e < kCascPart; ++e) T[part * kCascPart + e][w.lane] = xs[H + e];
+            } else {
+                if (s0 < 0) {  // (wave-uniform: the first producer's first set; element e < H is the input H - e in front of the run)
+#pragma unroll
+                    for (int e = 0; e < H; ++e) xs[e] = x[H - 1 - e];
+                }
+                casc_by_nc(c.nc, [&](auto ncv) {
+                    constexpr int NC = decltype(ncv)::value;
+#pragma unroll
+                    for (uint32_t e = 0; e < kCascPart; ++e) {
+                        double s = c.d[0] * xs[H + e];
+#pragma unroll
+                        for (int i = 1; i < NC; ++i) s = s + c.d[i] * xs[H + e - i];
+                        T[part * kCascPart + e][w.lane] = s;
+                    }
+                });
+                const int32_t last = (int32_t)w.ns - 1 - (s0 + H);  // index of sample ns - 1 in this wave's part
+                if (CARRY && j + 1 == w.nchunks && last >= 0 && last < (int32_t)kCascPart) {  // whoever holds the run's last sample
+                    have_last = true;
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) {
+                        double v = 0.0;
+#pragma unroll
+                        for (uint32_t e = 0; e < SET; ++e)
+                            if ((int32_t)e == last + H - i) v = xs[e];
+                        x[i] = v;
+                    }
+                }
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < SET; ++e) {
+                cur[e] = nxt[e];
+                nxt[e] = nx2[e];
+            }
+        }
+        __syncthreads();
+    }
+    // (behind the last barrier: the other producer has long read the ring, also in a run of one chunk)
+    if (CARRY && have_last && w.valid) {
+        for (uint32_t i = 0; i < c.nc; ++i) w.cs->x[i] = x[i];
+    }
+}
+
+// the store wave: the last section's outputs, truncated as C truncates them, once
+template <int BPS, bool ALIGNED>
+__device__ __forceinline__ void casc_wave_store(const CascWave& w) {
+    for (uint32_t t = 0; t < w.nticks; ++t) {
+        const uint32_t j = t - w.off;
+        if (j < w.nchunks) {
+            double(*T)[64] = w.tiles[j % kCascSlots];
+            const uint32_t cnt = w.count(j);
+            uint8_t* q = w.p + (size_t)j * kCascChunk * w.stride;
+            if (cnt == kCascChunk) {
+#pragma unroll 1
+                for (uint32_t e0 = 0; e0 < kCascChunk; e0 += kCascGroup) {
+                    double v[kCascGroup];
+#pragma unroll
+                    for (uint32_t e = 0; e < kCascGroup; ++e) v[e] = T[e0 + e][w.lane];
+                    if (w.valid) {
+#pragma unroll
+                        for (uint32_t e = 0; e < kCascGroup; ++e) sample_store<BPS>(q + (size_t)(e0 + e) * w.stride, trunc_i32_c(v[e]), ALIGNED);
+                    }
+                }
+            } else {
+                for (uint32_t e = 0; e < cnt; ++e) {
+                    const double v = T[e][w.lane];
+                    if (w.valid) sample_store<BPS>(q + (size_t)e * w.stride, trunc_i32_c(v), ALIGNED);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <int BPS, bool ALIGNED, bool CARRY>
+__global__ __launch_bounds__(kCascMaxThreads) void k_iir_cascade_pipe(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, CascadeArgs a,
+                                                                      uint32_t nblocks, IirCarry* __restrict__ state) {
+    __shared__ CascLds L;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t S = a.nsec;
+    CascWave w;
+    w.lane = threadIdx.x & 63u;
+    const uint32_t unit = blockIdx.x * 64u + w.lane;
+    const uint32_t b = unit / nch, ch0 = unit - b * nch;
+    w.valid = b < nblocks;
+    w.stride = (size_t)nch * BPS;
+    w.p = buf + (size_t)(w.valid ? b : 0u) * block_bytes + (size_t)(w.valid ? ch0 : 0u) * BPS;
+    w.ns = ns;
+    w.nchunks = (ns + kCascChunk - 1) / kCascChunk;
+    w.nticks = w.nchunks + 2 * S;
+    w.tiles = L.v;
+    w.x0 = (double)sample_load<BPS>(w.p, ALIGNED);
+    IirCarry* const cs0 = CARRY ? state + (size_t)(w.valid ? ch0 : 0u) * S : nullptr;
+    w.started = CARRY && cs0->started != 0;
+    auto section = [&](uint32_t k) {
+        w.cs = CARRY ? cs0 + k : nullptr;
+        w.filt = ((a.use_filter >> k) & 1u) != 0;
+        return a.s[k];
+    };
+    if (wave < S) {
+        __builtin_amdgcn_s_setprio(3);  // a recurrence wave goes first whenever it can issue
+        w.off = 2 * wave + 1;
+        casc_wave_rec<CARRY>(w, section(wave));
+    } else if (wave < 2 * S - 1) {
+        const uint32_t k = wave - S + 1;
+        w.off = 2 * k;
+        casc_wave_ff<CARRY>(w, section(k));
+    } else if (wave < 2 * S + 1) {
+        w.off = 0;
+        casc_wave_prod<BPS, ALIGNED, CARRY>(w, section(0), wave - (2 * S - 1));
+    } else {
+        w.off = 2 * S;
+        casc_wave_store<BPS, ALIGNED>(w);
+    }
+}
+
+}  // namespace rspt
+
+#pragma clang fp contract(fast)

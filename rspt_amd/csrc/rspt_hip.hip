@@ -35,6 +35,7 @@
 #include "transforms.hip"
 #include "decode.hip"
 #include "filter.hip"
+#include "iir_cascade.hip"
 #include "fir.hip"
 #include "median.hip"
 #include "peak.hip"
