@@ -4,8 +4,8 @@
 // reference's test harness drives them (lib_rspt_test/rspt_test.cpp:116-136): per channel, 4 * nr_samples copies of the
 // channel's first sample through filter(), then filter_opt() on every sample, the double result truncated to int32 and
 // written back in the native sample width.  Double arithmetic in the reference's order of operations, every product and sum
-// rounded on its own (plain operators under `#pragma clang fp contract(off)`, see below: no fused multiply-add, as in the reference's x86-64 build), so the filtered
-// block is bit-identical with the reference's.
+// rounded on its own, so the filtered block is bit-identical with the reference's.  The filter object itself (IirState: filter,
+// filter_opt, init_history_values) and the reason for `#pragma clang fp contract(off)` are stated in iir.hpp.
 //
 // Two modes, because the harness shares ONE filter object between the channels and its state runs on from channel to channel
 // (the history initialisation damps the old state by ~e^-10, it does not erase it: on the 24-bit test recording the carried
@@ -13,99 +13,21 @@
 //   shared       bit-exact with the harness; the channels of a block are a serial chain, so one thread takes one block
 //   per channel  a fresh filter per channel (what a caller with one i_filter per channel gets): one thread per channel,
 //                lane <-> channel so that every wave access is a contiguous row segment of the interleaved block
-#include "common.hpp"
+#include "iir.hpp"
 
-// NO contraction in this file.  hipcc's default is -ffp-contract=fast, and HIP's __dmul_rn / __dadd_rn are plain operators (not
-// the contraction barriers their CUDA namesakes are): left alone, the compiler fuses the recurrence's products and sums into
-// v_fma_f64 (83 of them in the round-2 kernel).  One fused rounding is ~1e-16 relative -- but this band-pass has poles at
-// 0.9994 and coefficients that cancel (3.14 y1 - 3.70 y2 + 1.97 y3 - 0.41 y4), which amplifies it to ~1e-7 absolute, enough to
-// move the truncated output by one count about once in 2 million samples (found on the 64 x 65536 bench batch; the small
-// fixtures never hit it).  With contraction off every product and sum is rounded on its own, as in the reference's x86-64 build.
+// NO contraction in this file: iir.hpp says why.
 #pragma clang fp contract(off)
 
 namespace rspt {
 
-struct IirCoef {
-    double n[5], d[5];  // feedback (n[0] unused) and feed-forward coefficients
-    uint32_t nc;        // 2..5
-    int32_t init_steps;  // 4 * nr_samples of init_history_values (iir_filter.cpp:106-110)
-};
-
-// The carried state of one channel (rspt_hip_iir_prefilter_stream_dev; layout: rspt_hip.h): the rings as the reference's object
-// holds them between two filter_opt calls, newest first, the y ring as untruncated doubles.  All-zero bytes: a channel that
-// has not started (its first call runs init_history_values).
-struct IirCarry {
-    double x[5], y[5];
-    uint64_t started;
-};
-static_assert(sizeof(IirCarry) == 88, "rspt_hip.h documents 88 bytes per channel");
-
-// The filter state: x[i] = input i samples ago, y[i] = output i samples ago (x_ring_ / y_ring_ of iir_filter.cpp:46-62).
-template <int NC>
-struct IirState {
-    double x[NC], y[NC];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int i = 0; i < NC; ++i) x[i] = y[i] = 0.0;
-    }
-    __device__ __forceinline__ void shift(double in) {  // iir_filter.cpp:66-71
-#pragma unroll
-        for (int i = NC - 1; i > 0; --i) {
-            x[i] = x[i - 1];
-            y[i] = y[i - 1];
-        }
-        x[0] = in;
-    }
-    // i_filter::filter (iir_filter.cpp:64-77): the terms join the sum one by one, feed-forward and feedback interleaved
-    __device__ __forceinline__ double step(const IirCoef& c, double in) {
-        shift(in);
-        double acc = (c.d[0] * x[0]);
-#pragma unroll
-        for (int i = 1; i < NC; ++i) {
-            acc = (acc + (c.d[i] * x[i]));
-            acc = (acc - (c.n[i] * y[i]));
-        }
-        y[0] = acc;
-        return acc;
-    }
-    // the same step once the whole x ring holds one value (init_history_values feeds a constant): the feed-forward products
-    // d[i] * x[i] are the same numbers every time -- P[i], computed once -- and only the feedback products are new
-    __device__ __forceinline__ void step_const(const IirCoef& c, const double (&P)[NC]) {
-#pragma unroll
-        for (int i = NC - 1; i > 0; --i) y[i] = y[i - 1];
-        double acc = P[0];
-#pragma unroll
-        for (int i = 1; i < NC; ++i) {
-            acc = (acc + P[i]);
-            acc = (acc - (c.n[i] * y[i]));
-        }
-        y[0] = acc;
-    }
-};
-
-// One channel: history initialisation with its first sample, then every sample in place.
-// filter_opt (iir_filter.cpp:79-104 with :23-41) is ONE expression evaluated left to right: all feed-forward terms first,
-//     ff = (((d0 x0 + d1 x1) + d2 x2) + d3 x3) + d4 x4            -- no output in it: computed for a whole chunk ahead of time
-//     y  = (((ff - n1 y1) - n2 y2) - n3 y3) - n4 y4                -- the serial part: one product and NC-1 subtractions per sample
-// Every product and sum is rounded on its own, in the reference's order.  Samples are handled in chunks of CH: the next
+// One channel: history initialisation with its first sample, then every sample in place through filter_opt, whose
+// feed-forward sum has no output in it (IirState::step_opt).  Samples are handled in chunks of CH: the next
 // chunk's loads are in flight while this one is filtered, the feed-forward sums of the chunk are independent work the
 // scheduler places into the latency of the dependent chain, and the results leave as one store per sample.
 // INIT = false: the history is the caller's (a carried state), the samples follow whatever f holds.
 template <int BPS, int NC, bool INIT = true>
 __device__ __forceinline__ void iir_channel(uint8_t* p, size_t stride, uint32_t ns, const IirCoef& c, IirState<NC>& f, bool aligned) {
-    if (INIT) {
-        const double x0 = (double)sample_load<BPS>(p, aligned);
-        int32_t i = 0;
-        for (; i < c.init_steps && i < NC - 1; ++i) f.step(c, x0);  // (the x ring still holds older inputs)
-        if (i < c.init_steps) {
-            f.step(c, x0);  // this one fills the ring's last place
-            ++i;
-            double P[NC];
-#pragma unroll
-            for (int k = 0; k < NC; ++k) P[k] = (c.d[k] * x0);
-            for (; i < c.init_steps; ++i) f.step_const(c, P);
-        }
-    }
+    if (INIT) f.init_history(c, (double)sample_load<BPS>(p, aligned));
     constexpr uint32_t CH = 16;
     int32_t cur[CH], nxt[CH];
     const uint32_t nfull = ns / CH;
@@ -126,24 +48,11 @@ __device__ __forceinline__ void iir_channel(uint8_t* p, size_t stride, uint32_t 
 #pragma unroll
         for (uint32_t e = 0; e < CH; ++e) xs[NC - 1 + e] = (double)cur[e];
 #pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) {
-            double a = (c.d[0] * xs[NC - 1 + e]);
-#pragma unroll
-            for (int i = 1; i < NC; ++i) a = (a + (c.d[i] * xs[NC - 1 + e - i]));
-            ff[e] = a;
-        }
+        for (uint32_t e = 0; e < CH; ++e) ff[e] = iir_ff<NC>(c.d, &xs[NC - 1 + e]);
         // the recurrence, then one store per sample
         int32_t out[CH];
 #pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) {
-            double a = ff[e];
-#pragma unroll
-            for (int i = 1; i < NC; ++i) a = (a - (c.n[i] * f.y[i - 1]));  // (y[i-1] now = y[i] of the step being taken)
-#pragma unroll
-            for (int i = NC - 1; i > 0; --i) f.y[i] = f.y[i - 1];
-            f.y[0] = a;
-            out[e] = trunc_i32_c(a);  // C truncation (rspt_test.cpp:130)
-        }
+        for (uint32_t e = 0; e < CH; ++e) out[e] = trunc_i32_c(f.feedback(c.n, ff[e]));  // C truncation (rspt_test.cpp:130)
 #pragma unroll
         for (int i = 0; i < NC; ++i) f.x[i] = xs[CH + NC - 2 - i];  // the last NC inputs, newest first
 #pragma unroll
@@ -153,14 +62,7 @@ __device__ __forceinline__ void iir_channel(uint8_t* p, size_t stride, uint32_t 
     }
     for (uint32_t s = nfull * CH; s < ns; ++s) {  // the tail, sample by sample
         uint8_t* q = p + (size_t)s * stride;
-        f.shift((double)sample_load<BPS>(q, aligned));
-        double a = (c.d[0] * f.x[0]);
-#pragma unroll
-        for (int i = 1; i < NC; ++i) a = (a + (c.d[i] * f.x[i]));
-#pragma unroll
-        for (int i = 1; i < NC; ++i) a = (a - (c.n[i] * f.y[i]));
-        f.y[0] = a;
-        sample_store<BPS>(q, trunc_i32_c(a), aligned);
+        sample_store<BPS>(q, trunc_i32_c(f.step_opt(c.n, c.d, (double)sample_load<BPS>(q, aligned))), aligned);
     }
 }
 
@@ -195,21 +97,13 @@ __global__ __launch_bounds__(64) void k_iir_carry(uint8_t* __restrict__ buf, uin
     IirCarry& s = state[ch];
     IirState<NC> f;
     if (s.started) {
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            f.x[i] = s.x[i];
-            f.y[i] = s.y[i];
-        }
+        f.load(s.x, s.y);
         iir_channel<BPS, NC, false>(p, stride, ns, c, f, aligned);
     } else {
         f.clear();
         iir_channel<BPS, NC, true>(p, stride, ns, c, f, aligned);
     }
-#pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        s.x[i] = f.x[i];
-        s.y[i] = f.y[i];
-    }
+    f.store(s.x, s.y);
     s.started = 1;
 }
 
@@ -235,6 +129,12 @@ __global__ __launch_bounds__(64) void k_iir_carry(uint8_t* __restrict__ buf, uin
 // do.  Whoever holds the run's last sample hands the last NC inputs on through L.xlast, as shared mode does for the next
 // channel, and the recurrence wave writes both rings back behind the last chunk.  The state is read before the first barrier
 // and written behind the last chunk's, by the workgroup that owns the channel.
+//
+// The recurrence (IirState::feedback) and the steps of the history initialisation come from iir.hpp.  The initialisation's
+// loop, the producers' clamped set load and feed-forward sums (iir_ff: it moved the four unaligned int24 per-channel
+// instantiations) and the selection of the run's last inputs are written out here, as in k_iir_cascade_pipe: moved into
+// functions of their own, each of them compiled to other instructions (up to +-34 per instantiation, other register counts),
+// and this kernel is kept instruction for instruction what was timed.
 constexpr uint32_t kIirChunk = 64, kIirProd = 4, kIirPart = kIirChunk / kIirProd;  // four producer waves, 16 samples of a chunk each
 constexpr uint32_t kIirThreads = 64 * (2 + kIirProd);
 struct IirPipeLds {
@@ -308,35 +208,25 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
         }
         for (uint32_t t = 0; t < nchunks + 2; ++t) {
             if (role == 0u) {
-                if (CARRY && t == 0 && started) {
+                if (CARRY && t == 0 && started) {  // (the y ring alone: this wave never reads x, the first producer takes it from the state)
 #pragma unroll
                     for (int i = 0; i < NC; ++i) f.y[i] = cs->y[i];
                 } else if (t == 0) {
-                    // init_history_values (iir_filter.cpp:106-110): 4 * nr_samples calls of filter() on the channel's first sample
+                    // IirState::init_history, written out: as a call it compiles to other code here (see above the kernel)
                     int32_t i = 0;
-                    for (; i < c.init_steps && i < NC; ++i) f.step(c, x0);  // (until the x ring holds nothing but x0)
+                    for (; i < c.init_steps && i < NC; ++i) f.step(c.n, c.d, x0);  // (until the x ring holds nothing but x0)
                     if (i < c.init_steps) {
                         double P[NC];
 #pragma unroll
                         for (int k = 0; k < NC; ++k) P[k] = c.d[k] * x0;
                         // (unrolled by the ring's length: the shifts of y become register names instead of moves)
 #pragma unroll 4
-                        for (; i < c.init_steps; ++i) f.step_const(c, P);
+                        for (; i < c.init_steps; ++i) f.step_const(c.n, P);
                     }
                 } else if (t <= nchunks) {
                     const uint32_t k = t - 1, bi = k & 1u;
                     const uint32_t cnt = min(kIirChunk, ns - k * kIirChunk);
-                    auto rec = [&](double a) -> double {
-#if defined(IIR_PROBE) && IIR_PROBE == 1  // timing probe (never in the product): no recurrence
-                        return a;
-#endif
-#pragma unroll
-                        for (int i = 1; i < NC; ++i) a = a - c.n[i] * f.y[i - 1];  // (y[i-1] now = y[i] of the step being taken)
-#pragma unroll
-                        for (int i = NC - 1; i > 0; --i) f.y[i] = f.y[i - 1];
-                        f.y[0] = a;
-                        return a;
-                    };
+                    auto rec = [&](double ff) { return f.feedback(c.n, ff); };
                     if (cnt == kIirChunk) {
                         // sixteen samples at a time: their feed-forward sums are read from LDS together (one wait), the results
                         // written together -- per sample the wave issues the recurrence and little else.  The truncation is the
@@ -397,14 +287,10 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
                             int32_t v[16];
 #pragma unroll
                             for (uint32_t e = 0; e < 16; ++e) v[e] = L.out[bi][e0 + e][lane];
-#if defined(IIR_PROBE) && IIR_PROBE == 3  // timing probe (never in the product): one store in sixteen
-                            if (valid) sample_store<BPS>(q + (size_t)e0 * stride, v[0] ^ v[5] ^ v[15], aligned);
-#else
                             if (valid) {
 #pragma unroll
                                 for (uint32_t e = 0; e < 16; ++e) sample_store<BPS>(q + (size_t)(e0 + e) * stride, v[e], aligned);
                             }
-#endif
                         }
                     } else {
                         for (uint32_t e = 0; e < cnt; ++e) {
@@ -425,16 +311,14 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ 
                     for (uint32_t j = 0; j < SET; ++j) xs[j] = (s0 + (int32_t)j < 0) ? x0 : xs[j];
                     if (CARRY) {  // (s0 = -H: element j < H is the input H - j samples in front of the call, place H - 1 - j of the x ring)
 #pragma unroll
-                        for (int j = 0; j < H; ++j) xs[j] = started ? cs->x[H - 1 - j] : (H - 1 - j < c.init_steps ? x0 : 0.0);
+                        for (int j = 0; j < H; ++j) xs[j] = started ? cs->x[H - 1 - j] : (H - 1 - j < c.init_steps ? x0 : 0.0)  /* iir_front: the place is below NC */;
                     }
                 }
 #pragma unroll
-                for (uint32_t e = 0; e < kIirPart; ++e) {
+                for (uint32_t e = 0; e < kIirPart; ++e) {  // (iir_ff, written out)
                     double a = c.d[0] * xs[H + e];
-#if !(defined(IIR_PROBE) && IIR_PROBE == 2)  // timing probe (never in the product): no feed-forward sums
 #pragma unroll
                     for (int i = 1; i < NC; ++i) a = a + c.d[i] * xs[H + e - i];
-#endif
                     L.ff[t & 1u][(role - 1u) * kIirPart + e][lane] = a;
                 }
                 if ((SHARED || CARRY) && t + 1 == nchunks) {  // whoever holds the channel's last sample hands its last inputs on

@@ -47,15 +47,6 @@ static void launch_iir(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCo
         hipLaunchKernelGGL((k_iir<BPS, NC, true>), dim3((B + 63) / 64), dim3(64), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, B);
     }
 }
-template <int BPS>
-static void launch_iir_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCoef& c, int per_channel, hipStream_t st) {
-    switch (c.nc) {
-        case 2: launch_iir<BPS, 2>(p, buf, B, c, per_channel, st); break;
-        case 3: launch_iir<BPS, 3>(p, buf, B, c, per_channel, st); break;
-        case 4: launch_iir<BPS, 4>(p, buf, B, c, per_channel, st); break;
-        default: launch_iir<BPS, 5>(p, buf, B, c, per_channel, st); break;
-    }
-}
 
 // The carried form (rspt_hip_iir_prefilter_stream_dev): the call's blocks as one run of `rows` rows, lane <-> channel, the
 // filters in `state`.  Whether a channel is fresh is known on the device only, so the route depends on the run's length alone.
@@ -72,15 +63,6 @@ static void launch_iir_stream(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, c
         return;
     }
     hipLaunchKernelGGL((k_iir_carry<BPS, NC>), grid, dim3(64), 0, st, buf, g.nch, rows, c, state);
-}
-template <int BPS>
-static void launch_iir_stream_nc(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, const IirCoef& c, IirCarry* state, hipStream_t st) {
-    switch (c.nc) {
-        case 2: launch_iir_stream<BPS, 2>(p, buf, rows, c, state, st); break;
-        case 3: launch_iir_stream<BPS, 3>(p, buf, rows, c, state, st); break;
-        case 4: launch_iir_stream<BPS, 4>(p, buf, rows, c, state, st); break;
-        default: launch_iir_stream<BPS, 5>(p, buf, rows, c, state, st); break;
-    }
 }
 
 // Both IIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
@@ -101,9 +83,11 @@ static int iir_call(rspt_hip_packer* p, void* d_buf, size_t nblocks, const doubl
     c.init_steps = 4 * init_nr_samples;
     hipStream_t st = (hipStream_t)stream;
     by_bps(p->g.bps, [&](auto bps) {
-        constexpr int BPS = decltype(bps)::value;
-        if (d_state) launch_iir_stream_nc<BPS>(p, (uint8_t*)d_buf, (uint32_t)rows, c, (IirCarry*)d_state, st);
-        else launch_iir_nc<BPS>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st);
+        by_nc(c.nc, [&](auto ncv) {
+            constexpr int BPS = decltype(bps)::value, NC = decltype(ncv)::value;
+            if (d_state) launch_iir_stream<BPS, NC>(p, (uint8_t*)d_buf, (uint32_t)rows, c, (IirCarry*)d_state, st);
+            else launch_iir<BPS, NC>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, per_channel, st);
+        });
     });
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;

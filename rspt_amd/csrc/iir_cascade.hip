@@ -4,11 +4,11 @@
 // The reference's filter objects return double and its users chain them per sample -- lp->filter_opt(hp->filter_opt(x)), or the
 // three filters of peak_detector.h:89-91 -- so what enters section k + 1 is section k's untruncated output, NaN and inf
 // included, and only the last section's result is converted to int32.  Each section is one i_filter::new_iir object
-// (iir_filter.cpp:46-116) restated as in filter.hip (IirState), run through filter_opt() -- all feed-forward terms first, then the
+// (iir_filter.cpp:46-116), stated in iir.hpp (IirState), run through filter_opt() -- all feed-forward terms first, then the
 // feedback terms -- or through filter() -- the terms interleaved -- and initialised with the channel's RAW first sample.
-#include "common.hpp"
+#include "iir.hpp"
 
-// NO contraction in this file either, for the reason written in filter.hip: every product and sum is rounded on its own.
+// NO contraction in this file: iir.hpp says why.
 #pragma clang fp contract(off)
 
 namespace rspt {
@@ -20,66 +20,34 @@ struct CascadeArgs {
     uint32_t use_filter;  // bit k: section k runs filter() instead of filter_opt()
 };
 
-template <class F>
-__device__ __forceinline__ void casc_by_nc(uint32_t nc, F&& f) {  // (nc is wave-uniform: a scalar branch)
-    switch (nc) {
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        default: f(std::integral_constant<int, 5>{}); break;
-    }
-}
-
-// A section's rings outside the code that knows its order: five places each, newest first, the places past nc - 1 zero.
-template <int NC>
-__device__ __forceinline__ void casc_get(IirState<NC>& f, const double (&x)[5], const double (&y)[5]) {
+// A section's rings where a kernel keeps them outside the code that knows their length (five places each, newest first, the
+// places past nc - 1 zero) at the start of a run: the carried ones, or a fresh object's behind init_history_values on x0.
+// (The loop is IirState::init_history written out, and the pipelined kernel's producers write their set load and their
+// selection of the last inputs out as k_iir_pipe does: see there.)
+__device__ __forceinline__ void casc_start(const IirCoef& c, double x0, bool started, const IirCarry* cs, double (&x)[5], double (&y)[5]) {
+    if (started) {
 #pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        f.x[i] = x[i];
-        f.y[i] = y[i];
-    }
-}
-template <int NC>
-__device__ __forceinline__ void casc_put(const IirState<NC>& f, double (&x)[5], double (&y)[5]) {
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        x[i] = i < NC ? f.x[i < NC ? i : 0] : 0.0;
-        y[i] = i < NC ? f.y[i < NC ? i : 0] : 0.0;
-    }
-}
-
-// init_history_values (iir_filter.cpp:109-113) on a fresh object: 4 * nr_samples calls of filter() on x0, as k_iir_pipe runs them
-__device__ __forceinline__ void casc_init(const IirCoef& c, double x0, double (&x)[5], double (&y)[5]) {
-    casc_by_nc(c.nc, [&](auto ncv) {
-        constexpr int NC = decltype(ncv)::value;
-        IirState<NC> f;
-        f.clear();
-        int32_t i = 0;
-        for (; i < c.init_steps && i < NC; ++i) f.step(c, x0);  // (until the x ring holds nothing but x0)
-        if (i < c.init_steps) {
-            double P[NC];
-#pragma unroll
-            for (int k = 0; k < NC; ++k) P[k] = c.d[k] * x0;
-#pragma unroll 4
-            for (; i < c.init_steps; ++i) f.step_const(c, P);
+        for (int i = 0; i < 5; ++i) {
+            x[i] = cs->x[i];
+            y[i] = cs->y[i];
         }
-        casc_put<NC>(f, x, y);
-    });
-}
-
-// One sample through one section: filter() is IirState::step; filter_opt() is one expression evaluated left to right
-// (iir_filter.cpp:26-44), every feed-forward term first.
-template <int NC, bool FILTER>
-__device__ __forceinline__ double casc_step(const IirCoef& c, IirState<NC>& f, double in) {
-    if (FILTER) return f.step(c, in);
-    f.shift(in);
-    double a = c.d[0] * f.x[0];
+    } else {
+        by_nc(c.nc, [&](auto ncv) {
+            IirState<decltype(ncv)::value> f;
+            f.clear();
+            constexpr int NC = decltype(ncv)::value;
+            int32_t i = 0;
+            for (; i < c.init_steps && i < NC; ++i) f.step(c.n, c.d, x0);  // (until the x ring holds nothing but x0)
+            if (i < c.init_steps) {
+                double P[NC];
 #pragma unroll
-    for (int i = 1; i < NC; ++i) a = a + c.d[i] * f.x[i];
-#pragma unroll
-    for (int i = 1; i < NC; ++i) a = a - c.n[i] * f.y[i];
-    f.y[0] = a;
-    return a;
+                for (int k = 0; k < NC; ++k) P[k] = c.d[k] * x0;
+#pragma unroll 4
+                for (; i < c.init_steps; ++i) f.step_const(c.n, P);
+            }
+            f.store(x, y);
+        });
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -101,16 +69,7 @@ __global__ __launch_bounds__(64) void k_iir_cascade(uint8_t* __restrict__ buf, u
     double x[kCascMaxSections][5], y[kCascMaxSections][5];
 #pragma unroll
     for (uint32_t k = 0; k < kCascMaxSections; ++k) {
-        if (k >= a.nsec) continue;
-        if (started) {
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                x[k][i] = cs[k].x[i];
-                y[k][i] = cs[k].y[i];
-            }
-        } else {
-            casc_init(a.s[k], x0, x[k], y[k]);
-        }
+        if (k < a.nsec) casc_start(a.s[k], x0, started, CARRY ? cs + k : nullptr, x[k], y[k]);
     }
     for (uint32_t s = 0; s < ns; ++s) {
         uint8_t* q = p + (size_t)s * stride;
@@ -119,12 +78,11 @@ __global__ __launch_bounds__(64) void k_iir_cascade(uint8_t* __restrict__ buf, u
         for (uint32_t k = 0; k < kCascMaxSections; ++k) {
             if (k >= a.nsec) continue;
             const bool filt = (a.use_filter >> k) & 1u;
-            casc_by_nc(a.s[k].nc, [&](auto ncv) {
-                constexpr int NC = decltype(ncv)::value;
-                IirState<NC> f;
-                casc_get<NC>(f, x[k], y[k]);
-                v = filt ? casc_step<NC, true>(a.s[k], f, v) : casc_step<NC, false>(a.s[k], f, v);
-                casc_put<NC>(f, x[k], y[k]);
+            by_nc(a.s[k].nc, [&](auto ncv) {
+                IirState<decltype(ncv)::value> f;
+                f.load(x[k], y[k]);
+                v = filt ? f.step(a.s[k].n, a.s[k].d, v) : f.step_opt(a.s[k].n, a.s[k].d, v);
+                f.store(x[k], y[k]);
             });
         }
         sample_store<BPS>(q, trunc_i32_c(v), aligned);  // C truncation, once, behind the last section
@@ -178,15 +136,7 @@ static_assert(sizeof(CascLds) <= 160 * 1024, "k_iir_cascade_pipe: the tiles must
 // section k's recurrence over one chunk, in place: feed-forward sums (filter(): inputs) -> outputs
 template <int NC, bool FILTER>
 __device__ __forceinline__ void casc_rec_chunk(double (*T)[64], uint32_t lane, uint32_t cnt, const IirCoef& c, IirState<NC>& f) {
-    auto rec = [&](double a) -> double {
-        if (FILTER) return f.step(c, a);
-#pragma unroll
-        for (int i = 1; i < NC; ++i) a = a - c.n[i] * f.y[i - 1];  // (y[i-1] now = y[i] of the step being taken)
-#pragma unroll
-        for (int i = NC - 1; i > 0; --i) f.y[i] = f.y[i - 1];
-        f.y[0] = a;
-        return a;
-    };
+    auto rec = [&](double a) { return FILTER ? f.step(c.n, c.d, a) : f.feedback(c.n, a); };
     if (cnt == kCascChunk) {
 #pragma unroll 1
         for (uint32_t e0 = 0; e0 < kCascChunk; e0 += kCascGroup) {
@@ -217,12 +167,7 @@ __device__ __forceinline__ void casc_ff_chunk(double (*T)[64], uint32_t lane, ui
 #pragma unroll
             for (uint32_t e = 0; e < kCascGroup; ++e) xs[H + e] = T[e0 + e][lane];
 #pragma unroll
-            for (uint32_t e = 0; e < kCascGroup; ++e) {
-                double s = c.d[0] * xs[H + e];
-#pragma unroll
-                for (int i = 1; i < NC; ++i) s = s + c.d[i] * xs[H + e - i];
-                o[e] = s;
-            }
+            for (uint32_t e = 0; e < kCascGroup; ++e) o[e] = iir_ff<NC>(c.d, &xs[H + e]);
 #pragma unroll
             for (uint32_t e = 0; e < kCascGroup; ++e) T[e0 + e][lane] = o[e];
 #pragma unroll
@@ -262,25 +207,17 @@ struct CascWave {
 template <bool CARRY>
 __device__ __forceinline__ void casc_wave_rec(const CascWave& w, const IirCoef& c) {
     double x[5], y[5];
-    if (w.started) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            x[i] = w.cs->x[i];
-            y[i] = w.cs->y[i];
-        }
-    } else {
-        casc_init(c, w.x0, x, y);
-    }
+    casc_start(c, w.x0, w.started, w.cs, x, y);
     for (uint32_t t = 0; t < w.nticks; ++t) {
         const uint32_t j = t - w.off;  // (wraps in front of the wave's first chunk)
         if (j < w.nchunks) {
-            casc_by_nc(c.nc, [&](auto ncv) {
+            by_nc(c.nc, [&](auto ncv) {
                 constexpr int NC = decltype(ncv)::value;
                 IirState<NC> f;
-                casc_get<NC>(f, x, y);
+                f.load(x, y);
                 if (w.filt) casc_rec_chunk<NC, true>(w.tiles[j % kCascSlots], w.lane, w.count(j), c, f);
                 else casc_rec_chunk<NC, false>(w.tiles[j % kCascSlots], w.lane, w.count(j), c, f);
-                casc_put<NC>(f, x, y);
+                f.store(x, y);
             });
         }
         __syncthreads();
@@ -300,10 +237,10 @@ template <bool CARRY>
 __device__ __forceinline__ void casc_wave_ff(const CascWave& w, const IirCoef& c) {
     double x[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) x[i] = w.filt ? 0.0 : w.started ? w.cs->x[i] : (i < c.init_steps && i < (int)c.nc ? w.x0 : 0.0);
+    for (int i = 0; i < 5; ++i) x[i] = w.filt ? 0.0 : w.started ? w.cs->x[i] : iir_front(c, w.x0, i);
     for (uint32_t t = 0; t < w.nticks; ++t) {
         const uint32_t j = t - w.off;
-        if (j < w.nchunks && !w.filt) casc_by_nc(c.nc, [&](auto ncv) { casc_ff_chunk<decltype(ncv)::value>(w.tiles[j % kCascSlots], w.lane, w.count(j), c, x); });
+        if (j < w.nchunks && !w.filt) by_nc(c.nc, [&](auto ncv) { casc_ff_chunk<decltype(ncv)::value>(w.tiles[j % kCascSlots], w.lane, w.count(j), c, x); });
         __syncthreads();
     }
     if (CARRY && w.valid && !w.filt) {
@@ -318,7 +255,7 @@ __device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef&
     constexpr uint32_t SET = kCascPart + H;  // its 16 samples and the H in front: element e of chunk j is sample j * 32 + part * 16 - H + e
     double x[5];  // the inputs in front of the run, newest first; behind the run's last chunk: the run's last inputs
 #pragma unroll
-    for (int i = 0; i < 5; ++i) x[i] = (w.filt || part != 0u) ? 0.0 : w.started ? w.cs->x[i] : (i < c.init_steps && i < (int)c.nc ? w.x0 : 0.0);
+    for (int i = 0; i < 5; ++i) x[i] = (w.filt || part != 0u) ? 0.0 : w.started ? w.cs->x[i] : iir_front(c, w.x0, i);
     bool have_last = false;
     int32_t cur[SET], nxt[SET], nx2[SET];
     auto load_set = [&](int32_t (&v)[SET], uint32_t j) {
@@ -355,15 +292,9 @@ __device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef&
 #pragma unroll
                     for (int e = 0; e < H; ++e) xs[e] = x[H - 1 - e];
                 }
-                casc_by_nc(c.nc, [&](auto ncv) {
-                    constexpr int NC = decltype(ncv)::value;
+                by_nc(c.nc, [&](auto ncv) {
 #pragma unroll
-                    for (uint32_t e = 0; e < kCascPart; ++e) {
-                        double s = c.d[0] * xs[H + e];
-#pragma unroll
-                        for (int i = 1; i < NC; ++i) s = s + c.d[i] * xs[H + e - i];
-                        T[part * kCascPart + e][w.lane] = s;
-                    }
+                    for (uint32_t e = 0; e < kCascPart; ++e) T[part * kCascPart + e][w.lane] = iir_ff<decltype(ncv)::value>(c.d, &xs[H + e]);
                 });
                 const int32_t last = (int32_t)w.ns - 1 - (s0 + H);  // index of sample ns - 1 in this wave's part
                 if (CARRY && j + 1 == w.nchunks && last >= 0 && last < (int32_t)kCascPart) {  // whoever holds the run's last sample

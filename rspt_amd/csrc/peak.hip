@@ -16,9 +16,9 @@
 // so every trace value and every event is bit-identical with the reference's x86-64 build.
 #include <cmath>
 
-#include "common.hpp"
+#include "iir.hpp"
 
-// NO contraction (as filter.hip): the filters' products and sums must each be rounded on their own.
+// NO contraction (iir.hpp says why): the filters' products and sums must each be rounded on their own.
 #pragma clang fp contract(off)
 
 namespace rspt {
@@ -176,46 +176,23 @@ struct PeakOffArgs : PeakArgs {
 constexpr uint32_t kPeakStateDoubles = 24, kPeakStateInts = 4;
 constexpr uint32_t kPeakStateBytesPerChannel = kPeakStateDoubles * 8 + kPeakStateInts * 4;
 
+// The detectors' filters are the iir_filter_*_order classes: the rings of IirState (iir.hpp), every sample through step_opt
+// (their filter() is one expression, all feed-forward terms first), the designer's numerator as d and its denominator as n.
+//
+// Their init_history_values(x0, .): `steps` calls of filter(x0), where once the x ring holds only x0 the feed-forward sum is
+// one number.  NOT IirState::init_history, and not to be merged with it: i_filter::filter interleaves feed-forward and feedback
+// terms, while these classes add all feed-forward terms into one number first and then apply the feedback terms -- other
+// roundings, other bits.
 template <int N>
-struct PkFilt {
-    double x[N], y[N];  // input / output i samples ago
-    // iir_filter_*_order::filter: all feed-forward terms left to right, then the feedback terms
-    __device__ __forceinline__ double step(const double* f, const double* b, double in) {
+__device__ void peak_history(IirState<N>& r, const double* n, const double* d, double x0, int32_t steps) {
+    int32_t i = 0;
+    for (; i < steps && i < N; ++i) r.step_opt(n, d, x0);
+    if (i >= steps) return;
+    double ff = d[0] * x0;
 #pragma unroll
-        for (int i = N - 1; i > 0; --i) {
-            x[i] = x[i - 1];
-            y[i] = y[i - 1];
-        }
-        x[0] = in;
-        double a = f[0] * x[0];
-#pragma unroll
-        for (int i = 1; i < N; ++i) a = a + f[i] * x[i];
-#pragma unroll
-        for (int i = 1; i < N; ++i) a = a - b[i] * y[i];
-        y[0] = a;
-        return a;
-    }
-    // the feedback half of a step whose feed-forward sum ff is known (the input is already in the x ring)
-    __device__ __forceinline__ double feedback(const double* b, double ff) {
-        double a = ff;
-#pragma unroll
-        for (int i = 1; i < N; ++i) a = a - b[i] * y[i - 1];  // (y[i - 1] is y[i] of the step being taken)
-#pragma unroll
-        for (int i = N - 1; i > 0; --i) y[i] = y[i - 1];
-        y[0] = a;
-        return a;
-    }
-    // init_history_values(x0, .): `steps` calls of filter(x0).  Once the x ring holds only x0 the feed-forward sum is one number.
-    __device__ void history(const double* f, const double* b, double x0, int32_t steps) {
-        int32_t i = 0;
-        for (; i < steps && i < N; ++i) step(f, b, x0);
-        if (i >= steps) return;
-        double ff = f[0] * x0;
-#pragma unroll
-        for (int k = 1; k < N; ++k) ff = ff + f[k] * x0;
-        for (; i < steps; ++i) feedback(b, ff);
-    }
-};
+    for (int k = 1; k < N; ++k) ff = ff + d[k] * x0;
+    for (; i < steps; ++i) r.feedback(n, ff);
+}
 
 // BL: with the baseline filter bl of the offline object (k_peak_offline).  It lives in band-pass slots 3-4 of the state (x) and
 // 8-9 (y), which OFFLINE_FW's three-coefficient band-pass never reads or writes: one state can take detect_fw and detect calls
@@ -224,7 +201,7 @@ template <bool BL>
 struct PeakBaseline {};
 template <>
 struct PeakBaseline<true> {
-    PkFilt<2> bl;
+    IirState<2> bl;
 };
 
 template <int V, bool BL = false>
@@ -232,24 +209,21 @@ struct PeakDet : PeakBaseline<BL> {
     static constexpr int NB = V == kPeakOnline ? 5 : 3;  // iir_filter_4th_order / iir_filter_2nd_order
     static constexpr int NG = V == kPeakOnline ? 3 : 2;  // iir_filter_2nd_order / iir_filter_1st_order
     static_assert(!BL || V == kPeakOfflineFw, "the baseline belongs to the offline object");
-    PkFilt<NB> bp;
-    PkFilt<NG> ig;
-    PkFilt<3> th;
+    IirState<NB> bp;
+    IirState<NG> ig;
+    IirState<3> th;
     double prev_amp, prev_sig;
     int32_t searching, after;
     uint32_t idx;  // sample_indx_ (an int: wraps)
 
     __device__ void clear() {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) bp.x[i] = bp.y[i] = 0.0;
-#pragma unroll
-        for (int i = 0; i < NG; ++i) ig.x[i] = ig.y[i] = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) th.x[i] = th.y[i] = 0.0;
+        bp.clear();
+        ig.clear();
+        th.clear();
         prev_amp = prev_sig = 0.0;
         searching = after = 0;
         idx = 0;
-        if constexpr (BL) this->bl.x[0] = this->bl.x[1] = this->bl.y[0] = this->bl.y[1] = 0.0;
+        if constexpr (BL) this->bl.clear();
     }
     __device__ void load(const uint8_t* st, uint32_t nch, uint32_t c) {
         const double* d = reinterpret_cast<const double*>(st);
@@ -317,8 +291,8 @@ struct PeakDet : PeakBaseline<BL> {
     // Everything of detect() behind the band-pass output s: squaring and the integrator, the threshold, the state machine
     // (branch-free, as written in the reference).  Returns whether the sample is an event; sig / h: the two trace values.
     __device__ __forceinline__ bool tail(const PeakCoef& c, double s_bp, double& sig, double& h) {
-        const double s = ig.step(c.gf, c.gb, s_bp * s_bp);
-        h = th.step(c.tf, c.tb, s);
+        const double s = ig.step_opt(c.gb, c.gf, s_bp * s_bp);
+        h = th.step_opt(c.tb, c.tf, s);
         sig = s;
         return machine(c, s, h);
     }
@@ -358,25 +332,25 @@ __device__ void peak_block(PeakDet<V>& D, const PeakCoef& c, const uint8_t* p, u
             ++cnt;
         }
     };
-    if (V == kPeakOfflineFw) D.bp.history(c.bf, c.bb, (double)sample_load<BPS>(p, aligned), c.hist);  // every detect_fw call
+    if (V == kPeakOfflineFw) peak_history(D.bp, c.bb, c.bf, (double)sample_load<BPS>(p, aligned), c.hist);  // every detect_fw call
     // ONLINE: the history runs where sample_indx_ is 0 -- the first sample of a fresh detector, or where the int wraps back
     // to 0 after 2^32 samples (then this block takes the sample-by-sample path below)
     bool simple = false;
     if (V != kPeakOfflineFw) {  // sample 0's `if (!sample_indx_++)`
         const bool first = D.idx == 0;
         simple = !first && (uint64_t)D.idx + ns > (1ull << 32);  // (0 comes back inside this block)
-        if (first) D.bp.history(c.bf, c.bb, (double)sample_load<BPS>(p, aligned), c.hist);
+        if (first) peak_history(D.bp, c.bb, c.bf, (double)sample_load<BPS>(p, aligned), c.hist);
         D.idx += 1;
     }
     if (simple) {
         for (uint32_t t = 0; t < ns; ++t) {
             const double x = (double)sample_load<BPS>(p + (size_t)t * stride, aligned);
             if (t > 0) {  // (sample 0's index was handled above)
-                if (D.idx == 0) D.bp.history(c.bf, c.bb, x, c.hist);
+                if (D.idx == 0) peak_history(D.bp, c.bb, c.bf, x, c.hist);
                 D.idx += 1;
             }
             double s, h;
-            const bool f = D.tail(c, D.bp.step(c.bf, c.bb, x), s, h);
+            const bool f = D.tail(c, D.bp.step_opt(c.bb, c.bf, x), s, h);
             emit(t, f, s, h);
         }
         count[0] = cnt;
@@ -404,12 +378,7 @@ __device__ void peak_block(PeakDet<V>& D, const PeakCoef& c, const uint8_t* p, u
 #pragma unroll
         for (uint32_t e = 0; e < CH; ++e) xs[NB - 1 + e] = (double)cur[e];
 #pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) {
-            double a = c.bf[0] * xs[NB - 1 + e];
-#pragma unroll
-            for (int i = 1; i < NB; ++i) a = a + c.bf[i] * xs[NB - 1 + e - i];
-            ff[e] = a;
-        }
+        for (uint32_t e = 0; e < CH; ++e) ff[e] = iir_ff<NB>(c.bf, &xs[NB - 1 + e]);
 #pragma unroll
         for (uint32_t e = 0; e < CH; ++e) {
             double s, h;
@@ -423,7 +392,7 @@ __device__ void peak_block(PeakDet<V>& D, const PeakCoef& c, const uint8_t* p, u
     }
     for (uint32_t t = nfull * CH; t < ns; ++t) {
         double s, h;
-        const bool f = D.tail(c, D.bp.step(c.bf, c.bb, (double)sample_load<BPS>(p + (size_t)t * stride, aligned)), s, h);
+        const bool f = D.tail(c, D.bp.step_opt(c.bb, c.bf, (double)sample_load<BPS>(p + (size_t)t * stride, aligned)), s, h);
         emit(t, f, s, h);
     }
     count[0] = cnt;
@@ -541,23 +510,23 @@ __device__ void peak_offline_block(PeakDet<kPeakOfflineFw, true>& D, const PeakO
     const PeakCoef& c = k.c;
     auto xs = [&](uint32_t t) { return (double)sample_load<BPS>(p + (size_t)t * stride, aligned); };
     const double x0 = xs(0);
-    D.bp.history(c.bf, c.bb, x0, c.hist);  // bandpass_ then baseline_ init_history_values(ecg_signal[0], fs)
-    D.bl.history(k.lf, k.lb, x0, c.hist);
+    peak_history(D.bp, c.bb, c.bf, x0, c.hist);  // bandpass_ then baseline_ init_history_values(ecg_signal[0], fs)
+    peak_history(D.bl, k.lb, k.lf, x0, c.hist);
     // baseline forward (stored), band-pass forward (state only)
     off_walk<16, false>(ns, xs, [&](uint32_t t, double x) {
-        V[(size_t)t * 64] = D.bl.step(k.lf, k.lb, x);
-        D.bp.step(c.bf, c.bb, x);
+        V[(size_t)t * 64] = D.bl.step_opt(k.lb, k.lf, x);
+        D.bp.step_opt(c.bb, c.bf, x);
     });
     // baseline backward in place (kept as x - baseline, all the relocation reads), band-pass backward on x again
     off_walk<8, true>(ns, [&](uint32_t t) { return OffPair{xs(t), V[(size_t)t * 64]}; }, [&](uint32_t t, OffPair v) {
-        V[(size_t)t * 64] = v.a - D.bl.step(k.lf, k.lb, v.b);
-        F[(size_t)t * 64] = D.bp.step(c.bf, c.bb, v.a);
+        V[(size_t)t * 64] = v.a - D.bl.step_opt(k.lb, k.lf, v.b);
+        F[(size_t)t * 64] = D.bp.step_opt(c.bb, c.bf, v.a);
     });
     auto fs = [&](uint32_t t) { return F[(size_t)t * 64]; };
-    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step(c.gf, c.gb, f * f); });
-    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step(c.gf, c.gb, f); });
-    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { D.th.step(c.tf, c.tb, f); });
-    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { T[(size_t)t * 64] = D.th.step(c.tf, c.tb, f); });
+    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step_opt(c.gb, c.gf, f * f); });
+    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step_opt(c.gb, c.gf, f); });
+    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { D.th.step_opt(c.tb, c.tf, f); });
+    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { T[(size_t)t * 64] = D.th.step_opt(c.tb, c.tf, f); });
     // the state machine; p over T, the shift folded in; E: the non-zero positions of p, those below nslope first (n0 of them)
     const uint32_t nslope = (uint32_t)c.nslope;  // (>= 1: the host refuses 0)
     uint32_t n = 0, n0 = 0;

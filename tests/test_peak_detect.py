@@ -161,7 +161,7 @@ def test_header_declares_the_entries_and_the_library_exports_them():
 def peak_asm():
     if not os.path.exists(devasm.HIPCC):
         pytest.skip("hipcc not found")
-    return {n: body for n, body in devasm.functions().items() if re.search(r"k_peak|PkFilt|PeakDet|peak_block", n)}
+    return {n: body for n, body in devasm.functions().items() if re.search(r"k_peak|IirState|PeakDet|peak_block", n)}
 
 
 def test_peak_kernels_round_every_product_and_sum_on_their_own(peak_asm):
