@@ -403,6 +403,42 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
                                     const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state,
                                     void* stream);
 
+/* ---- a zero-phase (forward-backward) IIR filter: one reference object run forward, then backward over its own output ----
+ * The reference's offline user runs a filter forward and then backward over the same object (peak_detector_offline::detect,
+ * peak_detector.h:309-328), which takes the delay and the phase distortion of a forward pass out again ("filtfilt").  Two calls of
+ * rspt_hip_iir_prefilter_batch_dev on a reversed buffer do NOT give that answer: the intermediate result would be truncated to
+ * the sample width and the second call would start a fresh object on the wrong sample.  This stage does, for one fresh object
+ * per (block, channel) -- there is no carried state: zero-phase filtering is offline by nature --
+ *     f = i_filter::new_iir(n, d, nr_coefficients)                         nr_coefficients 2..5
+ *     f->init_history_values((double)x[0], init_nr_samples)                0 .. 2^28
+ *     for t = 0 .. ns-1:      w[t] = f->filter_opt((double)x[t])
+ *     f->init_history_values(w[ns-1], backward_init_nr_samples)            0 .. 2^28
+ *     for t = ns-1 .. 0:      w[t] = f->filter_opt(w[t])
+ *     y[t] = (int32_t)w[t]
+ * The backward pass uses the same object as the forward pass, so the rings run on through the turn, as in detect()'s loops: the
+ * y ring holds the forward pass's last outputs and the x ring its last INPUTS (the raw samples x[ns-1], x[ns-2], ...).
+ * backward_init_nr_samples = 0 runs nothing before the backward pass (detect()'s way); a positive value runs filter()
+ * 4 * backward_init_nr_samples times on the last forward output -- init_history_values does not reset the rings
+ * (iir_filter.cpp:109-113), so the x ring then holds w[ns-1] in its first min(4 * backward_init_nr_samples, nr_coefficients)
+ * places and the forward pass's older inputs behind them.  w stays double between the passes and is truncated once: a NaN or
+ * +-inf that enters a ring stays there, through the turn as well.  The truncation is x86-64's, as in every other stage: every
+ * NaN, +-inf and |w| >= 2^31 becomes INT32_MIN, and the low bps bytes are stored IN PLACE, little-endian.  Every product and sum
+ * is rounded on its own (no fused multiply-add), in filter_opt's order.  Bit-identical with the reference driven this way.
+ *   n, d       host arrays of nr_coefficients doubles: feedback (n[0] unused) and feed-forward coefficients
+ *   d_work     a caller-owned device buffer, 8-byte aligned, of at least rspt_hip_iir_zero_phase_work_bytes(p, nblocks) bytes:
+ *              one slab double [ns][64] per wave of 64 (block, channel) lanes, ceil(nblocks * nch / 64) * 64 * ns * 8 bytes; it
+ *              holds w between the passes, needs no initialisation and nothing of it outlives the call
+ *   work_bytes the size of d_work
+ * RSPT_HIP_ERR_ARG for everything rspt_hip_iir_prefilter_batch_dev refuses, a backward_init_nr_samples outside 0 .. 2^28, a NULL
+ * or misaligned d_work, a work_bytes below the bound and a NULL bytes; RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels (and
+ * for a workspace whose byte count does not fit size_t), before anything is launched.  Blocks of 64 rows and more with
+ * init_nr_samples >= nr_coefficients - 1 take the pipelined kernel -- one wave holds the recurrence through both passes, four
+ * form the feed-forward sums, one writes --, the others one thread per (block, channel).  Asynchronous on
+ * `stream`; the stage allocates nothing. */
+int rspt_hip_iir_zero_phase_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t* bytes);
+int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                                      int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- optional stage in front of compress: the reference's FIR pre-filter ---------------------------------------
  * i_filter::new_fir(kernel, kernel_size), init_history_values(first sample of the channel, n), filter_opt on every sample
  * (lib_rspt/lib_filter/fir_filter.cpp), result truncated to int32 and stored in the native sample width, on nblocks

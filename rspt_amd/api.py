@@ -27,6 +27,7 @@ C_ABI_SYMBOLS = [
     "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_design_iir",
     "rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev",
     "rspt_hip_iir_cascade_batch_dev", "rspt_hip_iir_cascade_state_bytes", "rspt_hip_iir_cascade_stream_dev",
+    "rspt_hip_iir_zero_phase_work_bytes", "rspt_hip_iir_zero_phase_batch_dev",
     "rspt_hip_median_state_bytes", "rspt_hip_median_filter_stream_dev",
     "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
     "rspt_hip_prdn_batch_dev", "rspt_hip_native_to_i32_batch_dev", "rspt_hip_i32_to_native_batch_dev",
@@ -125,6 +126,10 @@ def lib():
     L.rspt_hip_iir_cascade_batch_dev.restype, L.rspt_hip_iir_cascade_batch_dev.argtypes = C.c_int, _casc + [C.c_void_p]
     L.rspt_hip_iir_cascade_state_bytes.restype, L.rspt_hip_iir_cascade_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
     L.rspt_hip_iir_cascade_stream_dev.restype, L.rspt_hip_iir_cascade_stream_dev.argtypes = C.c_int, _casc + [C.c_void_p, C.c_void_p]
+    L.rspt_hip_iir_zero_phase_work_bytes.restype, L.rspt_hip_iir_zero_phase_work_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
+    L.rspt_hip_iir_zero_phase_batch_dev.restype = C.c_int
+    L.rspt_hip_iir_zero_phase_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
+                                                    C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.rspt_hip_fir_state_bytes.restype, L.rspt_hip_fir_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
     L.rspt_hip_fir_prefilter_stream_dev.restype = C.c_int
     L.rspt_hip_fir_prefilter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p, C.c_void_p]
@@ -489,6 +494,33 @@ class SignalPacker:
             self._check("rspt_hip_iir_cascade_stream_dev", self._L.rspt_hip_iir_cascade_stream_dev(*args, state.data_ptr(), st))
         else:
             self._check("rspt_hip_iir_cascade_batch_dev", self._L.rspt_hip_iir_cascade_batch_dev(*args, st))
+        return d_buf
+
+    def iir_zero_phase_work_bytes(self, nblocks):
+        n = C.c_size_t()
+        self._check("rspt_hip_iir_zero_phase_work_bytes", self._L.rspt_hip_iir_zero_phase_work_bytes(self._h, int(nblocks), C.byref(n)))
+        return n.value
+
+    def iir_zero_phase_batch(self, d_buf, n, d, init_nr_samples=2000, backward_init_nr_samples=0, work=None, stream=None):
+        """Zero-phase (forward-backward) IIR filtering on device-resident blocks, in place; asynchronous.  One fresh reference
+        filter per (block, channel) runs forward over the block and then, the same object, backward over its own untruncated
+        output; the result is truncated once (rspt_hip.h: rspt_hip_iir_zero_phase_batch_dev).
+        work: a device tensor of at least iir_zero_phase_work_bytes(nblocks) bytes, 8-byte aligned; None: allocated here."""
+        import torch
+
+        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous()
+        nblocks = d_buf.numel() // self.block_bytes
+        assert nblocks * self.block_bytes == d_buf.numel()
+        nn, dd = np.ascontiguousarray(n, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
+        assert nn.size == dd.size
+        if work is None:
+            work = torch.empty(max(1, (self.iir_zero_phase_work_bytes(max(nblocks, 1)) + 7) // 8), dtype=torch.float64, device=d_buf.device)
+        assert work.is_cuda and work.is_contiguous()
+        st = stream if stream is not None else torch.cuda.current_stream(d_buf.device).cuda_stream
+        rc = self._L.rspt_hip_iir_zero_phase_batch_dev(self._h, d_buf.data_ptr(), nblocks, nn.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       dd.ctypes.data_as(C.POINTER(C.c_double)), nn.size, int(init_nr_samples),
+                                                       int(backward_init_nr_samples), work.data_ptr(), work.numel() * work.element_size(), st)
+        self._check("rspt_hip_iir_zero_phase_batch_dev", rc)
         return d_buf
 
     def _window_call_buffers(self, d_src, d_dst, stream):

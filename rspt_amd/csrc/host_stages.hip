@@ -1,4 +1,4 @@
-// host_stages.hip -- the host side of the analysis stages: IIR, IIR cascade, FIR, median, PRDN, converters, R-peak detectors; each stage's
+// host_stages.hip -- the host side of the analysis stages: IIR, IIR cascade, zero-phase IIR, FIR, median, PRDN, converters, R-peak detectors; each stage's
 // launchers directly in front of its entries.  Included by rspt_hip.hip.
 
 // The widest handle the filter, median, peak and PRDN stages are verified on (tests/test_gpu_wide_channels.py): beyond it they
@@ -176,6 +176,70 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
                                     void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
     return iir_cascade_call(p, d_buf, nblocks, nsections, n, d, nr_coefficients, init_nr_samples, use_filter, d_state, stream);
+}
+
+// ---- zero-phase IIR (iir_zero_phase.hip) ----
+// The workspace of a call: one slab double [ns][64] per wave of 64 (block, channel) lanes.  False where the byte count does not
+// fit size_t.
+static bool iir_zero_phase_bytes(const rspt_hip_packer* p, size_t nblocks, uint64_t* bytes) {
+    const uint64_t slabs = ((uint64_t)nblocks * p->g.nch + 63) / 64;  // (batch_count_ok: below 2^25 + 1)
+    const uint64_t per = (uint64_t)p->g.ns * 64 * sizeof(double);     // (ns < 2^31)
+    if (slabs > (uint64_t)SIZE_MAX / per) return false;
+    *bytes = slabs * per;
+    return true;
+}
+
+// Blocks of a chunk and more whose forward history fills the ring's tail take the pipelined kernel, the others one thread per
+// (block, channel).
+template <int BPS, int NC>
+static void launch_iir_zero_phase(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCoef& c, int init_nr_samples, int32_t back_steps, double* work,
+                                  hipStream_t st) {
+    const Geom& g = p->g;
+    const dim3 grid((B * g.nch + 63) / 64);
+    if (g.ns >= kZpChunk && init_nr_samples >= NC - 1) {
+        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;  // (block_bytes is a multiple of BPS)
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kZpThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, back_steps, B, work); };
+        if (al) go(&k_iir_zp_pipe<BPS, NC, (BPS == 4 || BPS == 2)>);
+        else go(&k_iir_zp_pipe<BPS, NC, false>);
+        return;
+    }
+    hipLaunchKernelGGL((k_iir_zp<BPS, NC>), grid, dim3(64), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, back_steps, B, work);
+}
+
+int rspt_hip_iir_zero_phase_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t* bytes) {
+    if (!p || !bytes || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    uint64_t n;
+    if (!iir_zero_phase_bytes(p, nblocks, &n)) return RSPT_HIP_ERR_UNSUPPORTED;
+    *bytes = (size_t)n;
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                                      int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes, void* stream) {
+    if (!p || !d_buf || !n || !d || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;
+    if (backward_init_nr_samples < 0 || backward_init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;
+    if (!d_work || reinterpret_cast<uintptr_t>(d_work) % 8) return RSPT_HIP_ERR_ARG;
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    uint64_t need;
+    if (!iir_zero_phase_bytes(p, nblocks, &need)) return RSPT_HIP_ERR_UNSUPPORTED;
+    if (work_bytes < need) return RSPT_HIP_ERR_ARG;
+    HIPCHK(p, hipSetDevice(p->device));
+    IirCoef c{};
+    for (size_t i = 0; i < nr_coefficients; ++i) {
+        c.n[i] = n[i];
+        c.d[i] = d[i];
+    }
+    c.nc = (uint32_t)nr_coefficients;
+    c.init_steps = 4 * init_nr_samples;
+    by_bps(p->g.bps, [&](auto bps) {
+        by_nc(c.nc, [&](auto ncv) {
+            launch_iir_zero_phase<decltype(bps)::value, decltype(ncv)::value>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, init_nr_samples,
+                                                                              4 * backward_init_nr_samples, (double*)d_work, (hipStream_t)stream);
+        });
+    });
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
 }
 
 // ---- the frame of the sliding-window stages (FIR, median) ----

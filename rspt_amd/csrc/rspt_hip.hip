@@ -36,6 +36,7 @@
 #include "decode.hip"
 #include "filter.hip"
 #include "iir_cascade.hip"
+#include "iir_zero_phase.hip"
 #include "fir.hip"
 #include "median.hip"
 #include "peak.hip"
