@@ -3,6 +3,7 @@
 // Restates i_filter::new_iir / init_history_values / filter / filter_opt of lib_rspt/lib_filter/iir_filter.cpp:46-116: two
 // rings of up to five doubles, x[i] = input i samples ago, y[i] = output i samples ago.  Double arithmetic in the reference's
 // order of operations, every product and sum rounded on its own, so a result is bit-identical with the reference's.
+// The tests judge these kernels against the same object stated once in numpy: tests/iir_model.py.
 #pragma once
 #include <type_traits>
 

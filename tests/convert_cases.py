@@ -12,6 +12,7 @@ function that makes its entries, so that a test can make them again from oracle/
 import numpy as np
 
 import cases
+from casetools import record_text
 
 FNV_OFFSET, FNV_PRIME = 0x811C9DC5, 0x01000193
 
@@ -141,10 +142,6 @@ def record_cases(backend, hash_of):
 
 def dump_record(entries):
     """the record file's text (one case per line)"""
-    import json
-
-    head = {"generator": "tests/golden/make_convert_record.py (the reference's convert_native_to_i32 / convert_i32_to_native and packers + "
-                         "tests/golden/convert_shim.cpp, g++ -O2 -std=gnu++11)",
-            "fnv1a": "32-bit FNV-1a of the output bytes (int32 matrices as little-endian bytes, [nch][ns])"}
-    return "{\n" + "".join(json.dumps(k) + ": " + json.dumps(v) + ",\n" for k, v in head.items()) + '"cases": [\n' + ",\n".join(
-        json.dumps(e) for e in entries) + "\n]\n}\n"
+    return record_text({"generator": "tests/golden/make_convert_record.py (the reference's convert_native_to_i32 / convert_i32_to_native and packers + "
+                                     "tests/golden/convert_shim.cpp, g++ -O2 -std=gnu++11)",
+                        "fnv1a": "32-bit FNV-1a of the output bytes (int32 matrices as little-endian bytes, [nch][ns])", "cases": entries})

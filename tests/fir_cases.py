@@ -5,11 +5,10 @@ tests/golden/fir_record.json.  The tests take the coefficients from that record 
 do not depend on numpy's window functions being bit-stable; the inputs are integer arithmetic or the shipped recordings, and the
 record holds their crc32.
 """
-import zlib
-
 import numpy as np
 
 import cases
+from casetools import crc  # noqa: F401  (fc.crc: the tests and generators use it beside the sample readers)
 from rspt_amd import synth
 
 INT32_MIN = -(1 << 31)
@@ -57,10 +56,6 @@ def fir_i32(x, kernel):
 def fir_prefilter(native, bps, nch, ns, kernel):
     """the filtered block in the native sample width (bytes), as rspt_hip_fir_prefilter_batch_dev writes it"""
     return i32_to_native(trunc_i32(fir_i32(native_to_i32(native, bps, nch, ns), kernel)), bps)
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes())
 
 
 # ---- coefficient sets (made here once; the record keeps them exactly) ----

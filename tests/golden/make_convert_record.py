@@ -9,21 +9,13 @@ deletes the build.  Large outputs appear as size and FNV-1a only.
 
     python tests/golden/make_convert_record.py [--ref DIR]     (DIR: the reference's root, default $REF or /root/reference)
 """
-import argparse
 import ctypes as C
-import glob
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
+import refrecord
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+refrecord.repo_paths()
 
 import convert_cases as cc  # noqa: E402
 
@@ -31,21 +23,8 @@ KINDS = {"hzr": 0, "xdelta_hzr": 1, "dct": 2, "hadamard": 3}
 
 
 class ShimBackend:
-    def __init__(self, ref, tmp):
-        R = os.path.join(ref, "lib_rspt")
-        objs = []
-        for f in sorted(glob.glob(os.path.join(R, "lib_hzr", "*.c"))) + [os.path.join(R, "lib_fwht", "fwht.c")]:
-            o = os.path.join(tmp, os.path.basename(f) + ".o")
-            subprocess.check_call(["gcc", "-O2", "-std=c11", "-DNDEBUG", "-fPIC", "-c", f, "-o", o])
-            objs.append(o)
-        cxx = [f for d in ("lib_signalpacker", "lib_zaxtensor", "lib_filter") for f in sorted(glob.glob(os.path.join(R, d, "*.cpp")))]
-        for f in cxx + [os.path.join(HERE, "convert_shim.cpp")]:
-            o = os.path.join(tmp, os.path.basename(f) + ".o")
-            subprocess.check_call(["g++", "-O2", "-std=gnu++11", "-w", "-fPIC", "-I" + ref, "-c", f, "-o", o])
-            objs.append(o)
-        lib = os.path.join(tmp, "libconvert_ref.so")
-        subprocess.check_call(["g++", "-shared", "-o", lib] + objs)
-        L = self.L = C.CDLL(lib)
+    def __init__(self, L):
+        self.L = L
         L.convert_shim_native_to_i32.restype = None
         L.convert_shim_native_to_i32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.convert_shim_i32_to_native.restype = None
@@ -77,19 +56,12 @@ class ShimBackend:
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
-    a = ap.parse_args()
     from oracle.oracle import Oracle
 
-    orc = Oracle()
-    tmp = tempfile.mkdtemp(prefix="convert_ref_")
-    try:
-        entries = cc.record_cases(ShimBackend(a.ref, tmp), orc.fnv1a)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    with open(os.path.join(HERE, "convert_record.json"), "w") as f:
-        f.write(cc.dump_record(entries))
+    with refrecord.ref_library("convert", **refrecord.PACKERS) as L:
+        entries = cc.record_cases(ShimBackend(L), Oracle().fnv1a)
+    with open(os.path.join(refrecord.HERE, "convert_record.json"), "w") as f:
+        f.write(cc.dump_record(entries))  # (tests/test_convert.py makes the same text again from oracle/_ref)
     print("%d cases" % len(entries))
 
 

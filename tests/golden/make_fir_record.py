@@ -12,35 +12,20 @@ and digest (tests/cases.py) of the filtered block in the native width; the 64 ch
     python tests/golden/make_fir_record.py [--ref DIR]     (DIR: the reference's root, default $REF or /root/reference,
                                                              as in oracle/Makefile)
 """
-import argparse
 import ctypes as C
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
+import refrecord
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+refrecord.repo_paths()
 
 import fir_cases as fc  # noqa: E402
 from cases import digest  # noqa: E402
 
 
-def build(ref, tmp):
-    lib = os.path.join(tmp, "libfir_ref.so")
-    src = os.path.join(ref, "lib_rspt", "lib_filter", "fir_filter.cpp")
-    subprocess.check_call(["g++", "-O2", "-std=gnu++11", "-w", "-fPIC", "-shared", "-I" + os.path.join(ref, "lib_rspt"), "-o", lib, src,
-                           os.path.join(HERE, "fir_shim.cpp")])
-    L = C.CDLL(lib)
+def bind(L):
     L.fir_shim_run.restype = None
     L.fir_shim_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
-    return L
 
 
 def run(L, native, bps, nch, ns, kernel, shared):
@@ -52,12 +37,8 @@ def run(L, native, bps, nch, ns, kernel, shared):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
-    a = ap.parse_args()
-    tmp = tempfile.mkdtemp(prefix="fir_ref_")
-    try:
-        L = build(a.ref, tmp)
+    with refrecord.ref_library("fir", ["lib_rspt/lib_filter/fir_filter.cpp"], ["lib_rspt"]) as L:
+        bind(L)
         out = {"generator": "tests/golden/make_fir_record.py (lib_filter/fir_filter.cpp + tests/golden/fir_shim.cpp, g++ -O2 -std=gnu++11)",
                "digest": "first 32 hex digits of the sha256 of the filtered native bytes (tests/cases.py: digest)",
                "cases": []}
@@ -76,16 +57,7 @@ def main():
             big[mode] = {"crc32": fc.crc(run(L, d, B["bps"], B["nch"], B["ns"], k, shared))}
         out["big"] = big
         print(B["name"], big["shared"], big["per_channel"])
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    with open(os.path.join(HERE, "fir_record.json"), "w") as f:  # (one case per line)
-        f.write("{\n")
-        for i, (key, v) in enumerate(out.items()):
-            if key == "cases":
-                f.write('"cases": [\n' + ",\n".join(json.dumps(c) for c in v) + "\n]")
-            else:
-                f.write(json.dumps(key) + ": " + json.dumps(v))
-            f.write(",\n" if i + 1 < len(out) else "\n}\n")
+    refrecord.write_record("fir_record.json", out)
 
 
 if __name__ == "__main__":

@@ -10,19 +10,20 @@ input and the digest (tests/cases.py) of the filtered block in both drivings:
 
     python tests/golden/make_iir_record.py          (needs oracle/_ref/librspt_ref.so: python -c "from oracle import oracle; oracle.build()")
 """
-import json
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))  # (tests/test_iir_edges.py loads this file by its path)
+
+import refrecord  # noqa: E402
+
+refrecord.repo_paths()
 
 import iir_cases as ic  # noqa: E402
 from cases import digest  # noqa: E402
+from casetools import record_text as _text  # noqa: E402
 
 
 def per_channel(filt, c):
@@ -46,16 +47,15 @@ def record_text(filt):
         rec["shared"] = digest(np.frombuffer(bytes(filt(c["data"], c["bps"], c["nch"], c["ns"], c["n"], c["d"], c["init"])), dtype=np.uint8))
         rec["per_channel"] = digest(per_channel(filt, c))
         recs.append(rec)
-    return ('{\n"generator": "tests/golden/make_iir_record.py (lib_filter/iir_filter.cpp + oracle/ref_shim.cpp, g++ -O2 -std=gnu++11)",\n'
-            '"digest": "first 32 hex digits of the sha256 of the filtered native bytes (tests/cases.py: digest)",\n'
-            '"cases": [\n' + ",\n".join(json.dumps(r) for r in recs) + "\n]\n}\n")  # (one case per line)
+    return _text({"generator": "tests/golden/make_iir_record.py (lib_filter/iir_filter.cpp + oracle/ref_shim.cpp, g++ -O2 -std=gnu++11)",
+                  "digest": "first 32 hex digits of the sha256 of the filtered native bytes (tests/cases.py: digest)", "cases": recs})
 
 
 def main():
     from oracle.oracle import Ref
 
     text = record_text(Ref().iir_prefilter)
-    with open(os.path.join(HERE, "iir_record.json"), "w") as f:
+    with open(os.path.join(refrecord.HERE, "iir_record.json"), "w") as f:
         f.write(text)
     print("%d cases" % text.count('"name"'))
 

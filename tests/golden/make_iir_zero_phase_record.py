@@ -12,35 +12,21 @@ the native width.
     python tests/golden/make_iir_zero_phase_record.py [--ref DIR]     (DIR: the reference's root, default $REF or /root/reference,
                                                                         as in oracle/Makefile)
 """
-import argparse
 import ctypes as C
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
+import refrecord
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+refrecord.repo_paths()
 
 import fir_cases as fc  # noqa: E402
 import iir_zero_phase_cases as zc  # noqa: E402
 from cases import digest  # noqa: E402
 
 
-def build(ref, tmp):
-    lib = os.path.join(tmp, "libiir_zero_phase_ref.so")
-    subprocess.check_call(["g++", "-O2", "-std=gnu++11", "-w", "-fPIC", "-shared", "-I" + os.path.join(ref, "lib_rspt"), "-o", lib,
-                           os.path.join(ref, "lib_rspt", "lib_filter", "iir_filter.cpp"), os.path.join(HERE, "iir_zero_phase_shim.cpp")])
-    L = C.CDLL(lib)
+def bind(L):
     L.iir_zero_phase_shim_run.restype = None
     L.iir_zero_phase_shim_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
-    return L
 
 
 def run(L, c):
@@ -53,12 +39,8 @@ def run(L, c):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
-    a = ap.parse_args()
-    tmp = tempfile.mkdtemp(prefix="iir_zero_phase_ref_")
-    try:
-        L = build(a.ref, tmp)
+    with refrecord.ref_library("iir_zero_phase", ["lib_rspt/lib_filter/iir_filter.cpp"], ["lib_rspt"]) as L:
+        bind(L)
         out = {"generator": "tests/golden/make_iir_zero_phase_record.py (lib_filter/iir_filter.cpp + tests/golden/iir_zero_phase_shim.cpp, "
                             "g++ -O2 -std=gnu++11)",
                "digest": "first 32 hex digits of the sha256 of the filtered native bytes (tests/cases.py: digest)",
@@ -70,16 +52,7 @@ def main():
             rec.update({"in_crc32": fc.crc(c["data"]), "crc32": fc.crc(y), "digest": digest(y)})
             out["cases"].append(rec)
             print(c["name"], rec["digest"], flush=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    with open(os.path.join(HERE, "iir_zero_phase_record.json"), "w") as f:  # (one case per line)
-        f.write("{\n")
-        for i, (key, v) in enumerate(out.items()):
-            if key == "cases":
-                f.write('"cases": [\n' + ",\n".join(json.dumps(c) for c in v) + "\n]")
-            else:
-                f.write(json.dumps(key) + ": " + json.dumps(v))
-            f.write(",\n" if i + 1 < len(out) else "\n}\n")
+    refrecord.write_record("iir_zero_phase_record.json", out)
 
 
 if __name__ == "__main__":

@@ -10,36 +10,22 @@ crc32s; and the doubles the reference returns on its own test's 20 inputs.
     python tests/golden/make_median_record.py [--ref DIR]     (DIR: the reference's root, default $REF or /root/reference,
                                                                 as in oracle/Makefile)
 """
-import argparse
 import ctypes as C
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
+import refrecord
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+refrecord.repo_paths()
 
 import median_cases as mc  # noqa: E402
 from cases import digest  # noqa: E402
 
 
-def build(ref, tmp):
-    lib = os.path.join(tmp, "libmedian_ref.so")
-    subprocess.check_call(["g++", "-O2", "-std=gnu++11", "-w", "-fPIC", "-shared", "-I" + os.path.join(ref, "lib_rspt", "lib_stat"), "-o", lib,
-                           os.path.join(HERE, "median_shim.cpp")])
-    L = C.CDLL(lib)
+def bind(L):
     L.median_shim_run.restype = None
     L.median_shim_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]
     L.median_shim_doubles.restype = None
     L.median_shim_doubles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
-    return L
 
 
 def run(L, native, bps, nch, ns, W):
@@ -50,12 +36,8 @@ def run(L, native, bps, nch, ns, W):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
-    a = ap.parse_args()
-    tmp = tempfile.mkdtemp(prefix="median_ref_")
-    try:
-        L = build(a.ref, tmp)
+    with refrecord.ref_library("median", [], ["lib_rspt/lib_stat"]) as L:
+        bind(L)
         out = {"generator": "tests/golden/make_median_record.py (lib_stat/rolling_window_median.h + tests/golden/median_shim.cpp, g++ -O2 -std=gnu++11)",
                "digest": "first 32 hex digits of the sha256 of the filtered native bytes (tests/cases.py: digest)",
                "ref20": {}, "cases": []}
@@ -77,16 +59,7 @@ def main():
             big["crc32"][str(W)] = mc.crc(run(L, d, B["bps"], B["nch"], B["ns"], W))
         out["big"] = big
         print(B["name"], big["crc32"])
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    with open(os.path.join(HERE, "median_record.json"), "w") as f:  # (one case per line)
-        f.write("{\n")
-        for i, (key, v) in enumerate(out.items()):
-            if key == "cases":
-                f.write('"cases": [\n' + ",\n".join(json.dumps(c) for c in v) + "\n]")
-            else:
-                f.write(json.dumps(key) + ": " + json.dumps(v))
-            f.write(",\n" if i + 1 < len(out) else "\n}\n")
+    refrecord.write_record("median_record.json", out)
 
 
 if __name__ == "__main__":

@@ -14,36 +14,21 @@ tdigest), and the revisits and collisions of the relocation as the restatement (
     python tests/golden/make_peak_offline_record.py [--ref DIR]     (DIR: the reference's root, default $REF or /root/reference,
                                                                       as in oracle/Makefile)
 """
-import argparse
 import ctypes as C
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
+import refrecord
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+refrecord.repo_paths()
 
 import peak_cases as pc  # noqa: E402
 import peak_offline_cases as oc  # noqa: E402
 
 
-def build(ref, tmp):
-    lib = os.path.join(tmp, "libpeak_offline_ref.so")
-    src = os.path.join(ref, "lib_rspt")
-    subprocess.check_call(["g++", "-O2", "-std=gnu++11", "-w", "-fPIC", "-shared", "-I" + src, "-o", lib, os.path.join(HERE, "peak_offline_shim.cpp"),
-                           os.path.join(src, "lib_filter", "iir_filter_design.cpp")])
-    L = C.CDLL(lib)
+def bind(L):
     P = C.c_void_p
     L.peak_offline_shim_run.restype = None
     L.peak_offline_shim_run.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, P, P, P, P]
-    return L
 
 
 def run(L, c, marker):
@@ -77,12 +62,8 @@ def events(c, ret, sig, marker):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
-    a = ap.parse_args()
-    tmp = tempfile.mkdtemp(prefix="peak_offline_ref_")
-    try:
-        L = build(a.ref, tmp)
+    with refrecord.ref_library("peak_offline", ["lib_rspt/lib_filter/iir_filter_design.cpp"], ["lib_rspt"]) as L:
+        bind(L)
         out = {"generator": "tests/golden/make_peak_offline_record.py (peak_detector.h, iir_filter_opt.h, filter.h, lib_filter/iir_filter_design.cpp + "
                             "tests/golden/peak_offline_shim.cpp, g++ -O2 -std=gnu++11)",
                "digest": "first 32 hex digits of the sha256 of a [nblocks][ns][nch] float64 trace, NaNs made one (tests/peak_cases.py: tdigest)",
@@ -102,16 +83,7 @@ def main():
                    "revisit_moves": st["revisit_moves"], "collisions": st["collisions"], "collisions_ahead": st["collisions_ahead"]}
             out["cases"].append(rec)
             print(c["name"], sum(count), "events", st, flush=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    with open(os.path.join(HERE, "peak_offline_record.json"), "w") as f:  # (one case per line)
-        f.write("{\n")
-        for i, (key, v) in enumerate(out.items()):
-            if key == "cases":
-                f.write(json.dumps(key) + ": [\n" + ",\n".join(json.dumps(c) for c in v) + "\n]")
-            else:
-                f.write(json.dumps(key) + ": " + json.dumps(v))
-            f.write(",\n" if i + 1 < len(out) else "\n}\n")
+    refrecord.write_record("peak_offline_record.json", out)
 
 
 if __name__ == "__main__":

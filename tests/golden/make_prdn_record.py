@@ -16,49 +16,25 @@ Full-size cases appear only as these figures, never as data.
     python tests/golden/make_prdn_record.py [--ref DIR]     (DIR: the reference's root, default $REF or /root/reference,
                                                               as in oracle/Makefile)
 """
-import argparse
 import ctypes as C
-import glob
-import json
 import os
-import shutil
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
+import refrecord
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+refrecord.repo_paths()
 
 import prdn_cases as pc  # noqa: E402
 
 KINDS = {"dct": 2, "hadamard": 3}
 
 
-def build(ref, tmp):
-    R = os.path.join(ref, "lib_rspt")
-    objs = []
-    for f in sorted(glob.glob(os.path.join(R, "lib_hzr", "*.c"))) + [os.path.join(R, "lib_fwht", "fwht.c")]:
-        o = os.path.join(tmp, os.path.basename(f) + ".o")
-        subprocess.check_call(["gcc", "-O2", "-std=c11", "-DNDEBUG", "-fPIC", "-c", f, "-o", o])
-        objs.append(o)
-    cxx = [f for d in ("lib_signalpacker", "lib_zaxtensor", "lib_filter") for f in sorted(glob.glob(os.path.join(R, d, "*.cpp")))]
-    for f in cxx + [os.path.join(HERE, "prdn_shim.cpp")]:
-        o = os.path.join(tmp, os.path.basename(f) + ".o")
-        subprocess.check_call(["g++", "-O2", "-std=gnu++11", "-w", "-fPIC", "-I" + ref, "-c", f, "-o", o])
-        objs.append(o)
-    lib = os.path.join(tmp, "libprdn_ref.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib] + objs)
-    L = C.CDLL(lib)
+def bind(L):
     L.prdn_shim_run.restype = C.c_int
     L.prdn_shim_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.prdn_shim_packer.restype = C.c_int
     L.prdn_shim_packer.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
-    return L
 
 
 def printed_bits(text):
@@ -76,44 +52,33 @@ def entry(c, prdn_bits):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
-    a = ap.parse_args()
-    tmp = tempfile.mkdtemp(prefix="prdn_ref_")
-    cwd = os.getcwd()
     out = {"generator": "tests/golden/make_prdn_record.py (lib_rspt_test/rspt_test.cpp test_packer_ + tests/golden/prdn_shim.cpp, g++ -O2 -std=gnu++11)",
            "prdn": "the reference's printed figure as the bit pattern of the double",
            "mse, ref, path": "from the numpy restatement tests/prdn_cases.py:prdn_parts (the reference prints PRDN only)", "cases": []}
-    try:
-        L = build(a.ref, tmp)
-        os.chdir(tmp)
-        buf = C.create_string_buffer(256)
-        for c in pc.synthetic_cases() + [pc.ref_seq_case()]:
-            rc = L.prdn_shim_run(c["orig"].ctypes.data, c["dec"].ctypes.data, c["ns"], c["nch"], c["bps"], buf, len(buf))
-            assert rc == 0, (c["name"], rc)
-            e = entry(c, printed_bits(buf.value))
-            out["cases"].append(e)
-            print(e["name"], buf.value.decode(), e["prdn"], "path", e["path"], flush=True)
-        for f in pc.lossy_fixtures():
-            data = np.ascontiguousarray(f["data"])
-            rc = L.prdn_shim_packer(KINDS[f["kind"]], data.ctypes.data, f["ns"], f["nch"], f["bps"], buf, len(buf))
-            assert rc == 0, (f["name"], rc)
-            with open("_decoded.bin", "rb") as fh:
-                e = entry(pc.lossy_case(f, fh.read()), printed_bits(buf.value))
-            e["kind"] = f["kind"]
-            out["cases"].append(e)
-            print(e["name"], buf.value.decode(), e["prdn"], "path", e["path"], flush=True)
-    finally:
-        os.chdir(cwd)
-        shutil.rmtree(tmp, ignore_errors=True)
-    with open(os.path.join(HERE, "prdn_record.json"), "w") as f:  # (one case per line)
-        f.write("{\n")
-        for i, (key, v) in enumerate(out.items()):
-            if key == "cases":
-                f.write('"cases": [\n' + ",\n".join(json.dumps(c) for c in v) + "\n]")
-            else:
-                f.write(json.dumps(key) + ": " + json.dumps(v))
-            f.write(",\n" if i + 1 < len(out) else "\n}\n")
+    cwd = os.getcwd()
+    with refrecord.ref_library("prdn", **refrecord.PACKERS) as L:
+        bind(L)
+        os.chdir(L.tmp)  # (test_packer_ writes _original.bin and _decoded.bin where it runs)
+        try:
+            buf = C.create_string_buffer(256)
+            for c in pc.synthetic_cases() + [pc.ref_seq_case()]:
+                rc = L.prdn_shim_run(c["orig"].ctypes.data, c["dec"].ctypes.data, c["ns"], c["nch"], c["bps"], buf, len(buf))
+                assert rc == 0, (c["name"], rc)
+                e = entry(c, printed_bits(buf.value))
+                out["cases"].append(e)
+                print(e["name"], buf.value.decode(), e["prdn"], "path", e["path"], flush=True)
+            for f in pc.lossy_fixtures():
+                data = np.ascontiguousarray(f["data"])
+                rc = L.prdn_shim_packer(KINDS[f["kind"]], data.ctypes.data, f["ns"], f["nch"], f["bps"], buf, len(buf))
+                assert rc == 0, (f["name"], rc)
+                with open("_decoded.bin", "rb") as fh:
+                    e = entry(pc.lossy_case(f, fh.read()), printed_bits(buf.value))
+                e["kind"] = f["kind"]
+                out["cases"].append(e)
+                print(e["name"], buf.value.decode(), e["prdn"], "path", e["path"], flush=True)
+        finally:
+            os.chdir(cwd)
+    refrecord.write_record("prdn_record.json", out)
 
 
 if __name__ == "__main__":

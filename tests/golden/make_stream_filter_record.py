@@ -12,37 +12,21 @@ filtered recording in the native width.
     python tests/golden/make_stream_filter_record.py [--ref DIR]     (DIR: the reference's root, default $REF or /root/reference,
                                                                        as in oracle/Makefile)
 """
-import argparse
 import ctypes as C
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
+import refrecord
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+refrecord.repo_paths()
 
 import fir_cases as fc  # noqa: E402
 import stream_filter_cases as sc  # noqa: E402
 from cases import digest  # noqa: E402
 
 
-def build(ref, tmp):
-    lib = os.path.join(tmp, "libstream_filter_ref.so")
-    filt = os.path.join(ref, "lib_rspt", "lib_filter")
-    subprocess.check_call(["g++", "-O2", "-std=gnu++11", "-w", "-fPIC", "-shared", "-I" + os.path.join(ref, "lib_rspt"), "-o", lib,
-                           os.path.join(filt, "iir_filter.cpp"), os.path.join(filt, "fir_filter.cpp"),
-                           os.path.join(HERE, "stream_filter_shim.cpp")])
-    L = C.CDLL(lib)
+def bind(L):
     L.stream_filter_shim_run.restype = None
     L.stream_filter_shim_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return L
 
 
 def run(L, c):
@@ -59,12 +43,8 @@ def run(L, c):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
-    a = ap.parse_args()
-    tmp = tempfile.mkdtemp(prefix="stream_filter_ref_")
-    try:
-        L = build(a.ref, tmp)
+    with refrecord.ref_library("stream_filter", ["lib_rspt/lib_filter/iir_filter.cpp", "lib_rspt/lib_filter/fir_filter.cpp"], ["lib_rspt"]) as L:
+        bind(L)
         out = {"generator": "tests/golden/make_stream_filter_record.py (lib_filter/iir_filter.cpp, fir_filter.cpp + "
                             "tests/golden/stream_filter_shim.cpp, g++ -O2 -std=gnu++11)",
                "digest": "first 32 hex digits of the sha256 of the filtered native bytes (tests/cases.py: digest)",
@@ -76,16 +56,7 @@ def main():
             rec.update({"in_crc32": fc.crc(c["data"]), "crc32": fc.crc(y), "digest": digest(y)})
             out["cases"].append(rec)
             print(c["name"], rec["digest"], flush=True)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    with open(os.path.join(HERE, "stream_filter_record.json"), "w") as f:  # (one case per line)
-        f.write("{\n")
-        for i, (key, v) in enumerate(out.items()):
-            if key == "cases":
-                f.write('"cases": [\n' + ",\n".join(json.dumps(c) for c in v) + "\n]")
-            else:
-                f.write(json.dumps(key) + ": " + json.dumps(v))
-            f.write(",\n" if i + 1 < len(out) else "\n}\n")
+    refrecord.write_record("stream_filter_record.json", out)
 
 
 if __name__ == "__main__":

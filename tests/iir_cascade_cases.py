@@ -15,8 +15,11 @@ import functools
 import numpy as np
 
 import cases
+import casetools
 import iir_cases as ic
+from casetools import _take
 from fir_cases import crc, i32_to_native, native_to_i32, trunc_i32  # noqa: F401
+from iir_model import IirModel
 from rspt_amd import synth
 
 CHUNK = 32  # k_iir_cascade_pipe: samples per chunk; runs of fewer rows take the plain kernel k_iir_cascade
@@ -29,12 +32,6 @@ README_NAMES = ("readme_ecg12x2048x16_i32_hp04_lp100", "readme_ds3x1000x20_i24_h
 
 def _sections(ncs, inits, modes):
     return [(list(ic.STABLE[nc][0]), list(ic.STABLE[nc][1]), init, bool(m)) for nc, init, m in zip(ncs, inits, modes)]
-
-
-def _take(data, bps, nch, rows):
-    d = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).reshape(-1)[: bps * nch * rows])
-    assert d.size == bps * nch * rows
-    return d
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,45 +80,21 @@ def cascade_cases():
 
 # ---- the restatement ----
 
-def _section_step(sec, xr, yr, v, opt):
-    """one call of filter_opt() (opt) or filter() on one object; every product and sum rounded on its own"""
-    n, d = sec[0], sec[1]
-    nc = len(n)
-    xr = [v] + xr[:-1]
-    yr = [None] + yr[:-1]
-    acc = d[0] * xr[0]
-    if opt:  # rolling_iir_filter_N_: one expression, left to right, every feed-forward term first
-        for i in range(1, nc):
-            acc = acc + d[i] * xr[i]
-        for i in range(1, nc):
-            acc = acc - n[i] * yr[i]
-    else:  # iir_filter.cpp:72-77: feed-forward and feedback terms interleaved
-        for i in range(1, nc):
-            acc = acc + d[i] * xr[i]
-            acc = acc - n[i] * yr[i]
-    yr[0] = acc
-    return acc, xr, yr
-
-
 def chain_double(x, sections):
     """x: [rows][lanes] float64, an independent chain per lane.  -> the last section's outputs before the truncation, and every
     section's outputs ([S][rows][lanes])"""
     rows, lanes = x.shape
-    secs = [([float(v) for v in n], [float(v) for v in d], init, f) for n, d, init, f in sections]
-    rings = []
+    per = np.empty((len(sections), rows, lanes))
     with np.errstate(over="ignore", invalid="ignore"):
-        for sec in secs:  # init_history_values(x0, init): 4 * init calls of filter() on the RAW first sample
-            xr, yr = [np.zeros(lanes)] * len(sec[0]), [np.zeros(lanes)] * len(sec[0])
-            for _ in range(4 * sec[2]):
-                _, xr, yr = _section_step(sec, xr, yr, x[0], False)
-            rings.append((xr, yr))
-        per = np.empty((len(secs), rows, lanes))
+        chain = []
+        for n, d, init, use_filter in sections:  # every section's history is made of the RAW first sample
+            f = IirModel(n, d, np.zeros(lanes))
+            f.init_history(x[0], 4 * init)
+            chain.append(f.filter if use_filter else f.filter_opt)
         for t in range(rows):
             v = x[t]
-            for k, sec in enumerate(secs):
-                v, xr, yr = _section_step(sec, rings[k][0], rings[k][1], v, not sec[3])
-                rings[k] = (xr, yr)
-                per[k, t] = v
+            for k, step in enumerate(chain):
+                v = per[k, t] = step(v)
     return per[-1], per
 
 
@@ -163,10 +136,4 @@ def with_record_coefficients(c, r):
 
 def splits(c):
     """the drivings of a recording as a stream: all blocks in one call, one block per call, an uneven cut (1, 5, 1, 8, ... blocks)"""
-    uneven, left, i = [], c["nblocks"], 0
-    while left:
-        k = min((1, 5, 1, 8)[i % 4], left)
-        uneven.append(k)
-        left -= k
-        i += 1
-    return {"one_call": [c["nblocks"]], "per_block": [1] * c["nblocks"], "uneven": uneven}
+    return casetools.splits(c["nblocks"], (1, 5, 1, 8))

@@ -16,6 +16,7 @@ import numpy as np
 
 import cases
 from fir_cases import INT32_MIN, crc, i32_to_native, native_to_i32, trunc_i32  # noqa: F401
+from iir_model import IirModel
 
 CHUNK_PIPE = 64  # k_iir_pipe: samples per chunk; the 16-sample fast path runs on full chunks only
 CHUNK_IIR = 16  # k_iir: samples per chunk, then a tail sample by sample
@@ -36,57 +37,24 @@ def kernel_of(ns, init, nc):
 
 # ---- the restatement ----
 
-def _chain(cols, xr, yr, n, d, init):
-    """one filter object over the samples cols[0..ns-1] (floats, or arrays: one independent filter per lane); returns the
-    unrounded outputs and the state.  filter() and filter_opt() of iir_filter.cpp, every product and sum rounded on its own"""
-    nc = len(n)
-    x0 = cols[0]
-    for _ in range(4 * init):  # init_history_values: filter(), feed-forward and feedback terms interleaved
-        xr = [x0] + xr[:-1]
-        yr = [None] + yr[:-1]
-        acc = d[0] * xr[0]
-        for i in range(1, nc):
-            acc = acc + d[i] * xr[i]
-            acc = acc - n[i] * yr[i]
-        yr[0] = acc
-    out = []
-    for v in cols:  # filter_opt(): one expression, left to right, every feed-forward term first
-        xr = [v] + xr[:-1]
-        yr = [None] + yr[:-1]
-        acc = d[0] * xr[0]
-        for i in range(1, nc):
-            acc = acc + d[i] * xr[i]
-        for i in range(1, nc):
-            acc = acc - n[i] * yr[i]
-        yr[0] = acc
-        out.append(acc)
-    return out, xr, yr
-
-
 def iir_double(native, bps, nch, ns, n, d, init, shared=True, nblocks=1):
     """[nblocks][ns][nch] float64: the reference's outputs before the truncation.  shared: one filter per block, its state
     running on from channel to channel (the harness); else a fresh filter per channel"""
     x = native_to_i32(native, bps, nch, ns * nblocks).reshape(nblocks, ns, nch).astype(np.float64)
-    n = [float(v) for v in n]
-    d = [float(v) for v in d]
-    nc = len(n)
     y = np.empty((nblocks, ns, nch), dtype=np.float64)
     with np.errstate(over="ignore", invalid="ignore"):
         if shared:
-            if nblocks == 1:  # (Python floats: the same IEEE doubles, far less overhead per operation)
-                xr, yr = [0.0] * nc, [0.0] * nc
-                for c in range(nch):
-                    out, xr, yr = _chain(x[0, :, c].tolist(), xr, yr, n, d, init)
-                    y[0, :, c] = out
-            else:
-                xr, yr = [np.zeros(nblocks)] * nc, [np.zeros(nblocks)] * nc
-                for c in range(nch):
-                    out, xr, yr = _chain(list(x[:, :, c].T), xr, yr, n, d, init)
-                    y[:, :, c] = np.array(out).T
+            # (one block: Python floats, the same IEEE doubles at far less overhead per operation; else a lane per block)
+            f = IirModel(n, d, 0.0 if nblocks == 1 else np.zeros(nblocks))
+            for c in range(nch):
+                col = x[0, :, c].tolist() if nblocks == 1 else list(x[:, :, c].T)
+                f.init_history(col[0], 4 * init)
+                y[:, :, c] = np.array(f.run(col)).T
         else:
             lanes = x.transpose(1, 0, 2).reshape(ns, nblocks * nch)
-            out, _, _ = _chain(list(lanes), [np.zeros(nblocks * nch)] * nc, [np.zeros(nblocks * nch)] * nc, n, d, init)
-            y[:] = np.array(out).reshape(ns, nblocks, nch).transpose(1, 0, 2)
+            f = IirModel(n, d, np.zeros(nblocks * nch))
+            f.init_history(lanes[0], 4 * init)
+            y[:] = np.array(f.run(list(lanes))).reshape(ns, nblocks, nch).transpose(1, 0, 2)
     return y
 
 

@@ -16,8 +16,9 @@ import numpy as np
 
 import cases
 import iir_cases as ic
+from casetools import _take
 from fir_cases import crc, i32_to_native, native_to_i32, trunc_i32  # noqa: F401
-from iir_cascade_cases import _section_step
+from iir_model import IirModel
 from rspt_amd import synth
 
 CHUNK = 64  # k_iir_zp_pipe: samples per chunk; blocks of fewer rows take the plain kernel k_iir_zp
@@ -30,12 +31,6 @@ SAME_DATA_PAIR = ("ns200_i32_3ch_x2_nc3_init1_b1_plain", "ns200_i32_3ch_x2_nc3_i
 def kernel_of(ns, init, nc):
     """which kernel rspt_hip_iir_zero_phase_batch_dev runs (launch_iir_zero_phase)"""
     return "pipe" if ns >= CHUNK and init >= nc - 1 else "plain"
-
-
-def _take(data, bps, nch, rows):
-    d = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).reshape(-1)[: bps * nch * rows])
-    assert d.size == bps * nch * rows
-    return d
 
 
 @functools.lru_cache(maxsize=None)
@@ -84,21 +79,12 @@ def zero_phase_cases():
 def zero_phase_double(x, n, d, init, binit):
     """x: [rows][lanes] float64, an independent object per lane.  -> (w after the backward pass, w after the forward pass),
     both [rows][lanes] and untruncated; every product and sum rounded on its own"""
-    rows, lanes = x.shape
-    sec = ([float(v) for v in n], [float(v) for v in d])
-    nc = len(sec[0])
-    fwd, back = np.empty((rows, lanes)), np.empty((rows, lanes))
     with np.errstate(over="ignore", invalid="ignore"):
-        xr, yr = [np.zeros(lanes)] * nc, [np.zeros(lanes)] * nc
-        for _ in range(4 * init):  # init_history_values: filter() on the first sample
-            _, xr, yr = _section_step(sec, xr, yr, x[0], False)
-        for t in range(rows):
-            fwd[t], xr, yr = _section_step(sec, xr, yr, x[t], True)
-        last = fwd[rows - 1].copy()
-        for _ in range(4 * binit):  # the same object: the rings run on
-            _, xr, yr = _section_step(sec, xr, yr, last, False)
-        for t in range(rows - 1, -1, -1):
-            back[t], xr, yr = _section_step(sec, xr, yr, fwd[t], True)
+        f = IirModel(n, d, np.zeros(x.shape[1]))
+        f.init_history(x[0], 4 * init)
+        fwd = np.array(f.run(list(x)))
+        f.init_history(fwd[-1], 4 * binit)  # the same object: the rings run on
+        back = np.array(f.run(list(fwd[::-1]))[::-1])
     return back, fwd
 
 
@@ -127,18 +113,7 @@ def forward_reverse_forward(c):
     """what the single stage gives when it is called, the buffer reversed in time, and called again: a forward pass truncated to
     the sample width, then a fresh object, initialised on the LAST sample, over the reversed block, truncated again"""
     def forward(data):
-        cc = dict(c, data=data)
-        x = _lanes(cc)
-        sec = (c["n"], c["d"])
-        nc = len(c["n"])
-        out = np.empty(x.shape)
-        with np.errstate(over="ignore", invalid="ignore"):
-            xr, yr = [np.zeros(x.shape[1])] * nc, [np.zeros(x.shape[1])] * nc
-            for _ in range(4 * c["init"]):
-                _, xr, yr = _section_step(sec, xr, yr, x[0], False)
-            for t in range(x.shape[0]):
-                out[t], xr, yr = _section_step(sec, xr, yr, x[t], True)
-        return i32_to_native(trunc_i32(_blocks(cc, out)), c["bps"])
+        return ic.iir_prefilter(data, c["bps"], c["nch"], c["ns"], c["n"], c["d"], c["init"], shared=False, nblocks=c["nblocks"])
 
     def reverse(data):
         return np.ascontiguousarray(data.reshape(c["nblocks"], c["ns"], c["nch"] * c["bps"])[:, ::-1]).reshape(-1)

@@ -7,11 +7,11 @@ with s the sorted window.  The cases feed tests/golden/make_median_record.py, wh
 in tests/golden/median_record.json; the inputs are integer arithmetic or the shipped recordings, and the record holds their crc32.
 """
 import heapq
-import zlib
 
 import numpy as np
 
 import cases
+from casetools import _i32, crc  # noqa: F401
 from fir_cases import i32_to_native, native_to_i32  # noqa: F401  (the same sample reading as the FIR stage)
 from rspt_amd import synth
 
@@ -84,14 +84,6 @@ def median_i32(x, W):
 def median_filter(native, bps, nch, ns, W):
     """the filtered block in the native sample width (bytes), as rspt_hip_median_filter_batch_dev writes it"""
     return i32_to_native(median_i32(native_to_i32(native, bps, nch, ns), W), bps)
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes())
-
-
-def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.int32)).view(np.uint8)
 
 
 def median_cases():

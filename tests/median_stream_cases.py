@@ -13,22 +13,14 @@ import bisect
 import numpy as np
 
 import cases
+import casetools
 import median_cases as mc
+from casetools import _i32, _take
 from median_cases import crc, i32_to_native, native_to_i32  # noqa: F401
 from rspt_amd import synth
 
 MAX_CARRY = 1 << 17  # the longest carried window (W - 1) above the short regime
 SHORT_MAX = 32
-
-
-def _take(data, bps, nch, rows):
-    d = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).reshape(-1)[: bps * nch * rows])
-    assert d.size == bps * nch * rows
-    return d
-
-
-def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.int32)).view(np.uint8)
 
 
 def stream_cases():
@@ -133,13 +125,7 @@ def state_after(data, bps, nch, W):
 
 def splits(nblocks):
     """the drivings of a recording: all blocks in one call, one block per call, an uneven cut (1, 3, rest)"""
-    uneven, left = [], nblocks
-    for k in (1, 3, nblocks):
-        k = min(k, left)
-        if k:
-            uneven.append(k)
-            left -= k
-    return {"one_call": [nblocks], "per_block": [1] * nblocks, "uneven": uneven}
+    return casetools.splits(nblocks, (1, 3, nblocks))
 
 
 def random_case(seed):

@@ -8,12 +8,13 @@ The cases feed tests/golden/make_peak_record.py, which records the compiled refe
 """
 import hashlib
 import math
-import zlib
 
 import numpy as np
 
 import cases
+from casetools import _i32, crc  # noqa: F401
 from fir_cases import i32_to_native, native_to_i32  # (the same sample reading as the other stages)
+from iir_model import IirModel
 from rspt_amd import synth
 
 HIGH_PASS, LOW_PASS, BAND_PASS, BAND_STOP = 0, 1, 2, 3
@@ -130,32 +131,11 @@ def detector_constants(variant, fs):
 
 # ---- the detector ----
 
-class _Filt:
-    """an iir_filter_*_order over many lanes: x[i], y[i] = input / output i samples ago"""
+class _Filt(IirModel):
+    """an iir_filter_*_order over L lanes, from the designer's (ff, fb) = the object's (d, n); its history runs filter_opt"""
 
     def __init__(self, ff, fb, L):
-        self.ff, self.fb = [float(v) for v in ff], [float(v) for v in fb]
-        self.x = [np.zeros(L) for _ in ff]
-        self.y = [np.zeros(L) for _ in ff]
-
-    def step(self, v):
-        self.x = [v] + self.x[:-1]
-        self.y = [None] + self.y[:-1]
-        a = self.ff[0] * self.x[0]
-        for i in range(1, len(self.ff)):
-            a = a + self.ff[i] * self.x[i]
-        for i in range(1, len(self.ff)):
-            a = a - self.fb[i] * self.y[i]
-        self.y[0] = a
-        return a
-
-    def history(self, v, steps, mask):
-        """init_history_values(v, .) on the lanes of mask"""
-        keep_x, keep_y = list(self.x), list(self.y)
-        for _ in range(steps):
-            self.step(v)
-        self.x = [np.where(mask, a, b) for a, b in zip(self.x, keep_x)]
-        self.y = [np.where(mask, a, b) for a, b in zip(self.y, keep_y)]
+        super().__init__(fb, ff, np.zeros(L))
 
 
 class Detector:
@@ -179,17 +159,17 @@ class Detector:
         fire, ret = np.zeros((ns, L), dtype=bool), np.zeros((ns, L))
         sig, thr = np.zeros((ns, L)), np.zeros((ns, L))
         if self.variant == OFFLINE_FW and ns:
-            self.bp.history(x[0], k["hist"], np.ones(L, dtype=bool))  # (every detect_fw call)
+            self.bp.init_history(x[0], k["hist"], np.ones(L, dtype=bool), opt=True)  # (every detect_fw call)
         for t in range(ns):
             v = x[t]
             if self.variant != OFFLINE_FW:
                 first = self.idx == 0  # (if (!sample_indx_++))
                 if first.any():
-                    self.bp.history(v, k["hist"], first)
+                    self.bp.init_history(v, k["hist"], first, opt=True)
                 self.idx = (self.idx + 1 + (1 << 31)) % (1 << 32) - (1 << 31)  # an int: wraps
-            s = self.bp.step(v)
-            s = self.ig.step(s * s)
-            h = self.th.step(s)
+            s = self.bp.filter_opt(v)
+            s = self.ig.filter_opt(s * s)
+            h = self.th.filter_opt(s)
             sig[t], thr[t] = s, h
             c1 = self.searching & (s > h * 1.5) & (self.prev_sig > s)
             take = c1 & ((self.prev_amp == 0) | (self.prev_sig > self.prev_amp * 0.5))
@@ -256,10 +236,6 @@ def flat(lists):
     return [v for row in lists for col in row for v in col]
 
 
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes())
-
-
 # ---- the GPU entries' results (torch is imported only here) ----
 
 def dev(data):
@@ -293,10 +269,6 @@ def events_equal(got, want, max_peaks=None):
 
 
 # ---- the cases ----
-
-def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.int32)).view(np.uint8).reshape(-1)
-
 
 def peak_inputs():
     """name, bps, nch, ns, nblocks, data (native bytes of nblocks blocks), fs list, stateful"""

@@ -10,6 +10,7 @@ import numpy as np
 
 import cases
 import peak_cases as pc
+from casetools import _i32
 from rspt_amd import synth
 
 BASELINE = (pc.LOW_PASS, 1, 0.5, 0.0)
@@ -56,15 +57,15 @@ class Offline:
     def fw(self, x, marker):
         """detect_fw on x [ns][L]: (peak_signal, filt_signal, threshold_signal, fired) [ns][L]"""
         ns, L = x.shape
-        self.bp.history(x[0], self.k["hist"], np.ones(L, dtype=bool))
+        self.bp.init_history(x[0], self.k["hist"], np.ones(L, dtype=bool), opt=True)
         f, h, p = np.zeros((ns, L)), np.zeros((ns, L)), np.zeros((ns, L))
         fired = np.zeros((ns, L), dtype=bool)
         for t in range(ns):
-            f[t] = self.bp.step(x[t])
+            f[t] = self.bp.filter_opt(x[t])
         for t in range(ns):
-            f[t] = self.ig.step(f[t] * f[t])
+            f[t] = self.ig.filter_opt(f[t] * f[t])
         for t in range(ns):
-            h[t] = self.th.step(f[t])
+            h[t] = self.th.filter_opt(f[t])
         for t in range(ns):
             fired[t], p[t] = self._machine(f[t], h[t], marker)
         return p, f, h, fired
@@ -74,25 +75,25 @@ class Offline:
         ns, L = x.shape
         k = self.k
         all_ = np.ones(L, dtype=bool)
-        self.bp.history(x[0], k["hist"], all_)
-        self.bl.history(x[0], k["hist"], all_)
+        self.bp.init_history(x[0], k["hist"], all_, opt=True)
+        self.bl.init_history(x[0], k["hist"], all_, opt=True)
         b, f, h, p = (np.zeros((ns, L)) for _ in range(4))
         for t in range(ns):
-            b[t] = self.bl.step(x[t])
+            b[t] = self.bl.filter_opt(x[t])
         for t in range(ns - 1, -1, -1):
-            b[t] = self.bl.step(b[t].copy())  # (a copy: the filter keeps its input, and b[t] is overwritten)
+            b[t] = self.bl.filter_opt(b[t].copy())  # (a copy: the filter keeps its input, and b[t] is overwritten)
         for t in range(ns):
-            self.bp.step(x[t])
+            self.bp.filter_opt(x[t])
         for t in range(ns - 1, -1, -1):
-            f[t] = self.bp.step(x[t])  # (on the input again)
+            f[t] = self.bp.filter_opt(x[t])  # (on the input again)
         for t in range(ns):
-            f[t] = self.ig.step(f[t] * f[t])
+            f[t] = self.ig.filter_opt(f[t] * f[t])
         for t in range(ns - 1, -1, -1):
-            f[t] = self.ig.step(f[t].copy())
+            f[t] = self.ig.filter_opt(f[t].copy())
         for t in range(ns):
-            self.th.step(f[t])
+            self.th.filter_opt(f[t])
         for t in range(ns - 1, -1, -1):
-            h[t] = self.th.step(f[t])
+            h[t] = self.th.filter_opt(f[t])
         for t in range(ns):
             p[t] = self._machine(f[t], h[t], marker)[1]
         ns_ = k["nslope"]
@@ -167,10 +168,6 @@ def detect(x_i32, fs, marker=1.0, stateful=False, calls=None, stats=None):
 
 
 # ---- the cases ----
-
-def _i32(a):
-    return pc._i32(a)
-
 
 def offline_inputs():
     """name, bps, nch, ns, nblocks, data (native bytes of nblocks blocks), fs list, stateful, calls"""

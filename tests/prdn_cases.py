@@ -13,11 +13,11 @@ sequential path).  The cases feed tests/golden/make_prdn_record.py, which record
 tests/golden/prdn_record.json; the inputs are integer arithmetic or the shipped recordings, and the record holds their crc32.
 """
 import struct
-import zlib
 
 import numpy as np
 
 import cases
+from casetools import _i32, crc  # noqa: F401
 from fir_cases import i32_to_native, native_to_i32  # noqa: F401
 
 NAN_BITS = 0xFFF8000000000000  # what the reference's x86-64 build returns for sqrt of a negative and for 0 / 0
@@ -32,10 +32,6 @@ def bits(x):
 
 def hexbits(x):
     return "%016x" % bits(x)
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes())
 
 
 def average_32(o):
@@ -89,10 +85,6 @@ def prdn_parts(orig, dec, bps, nch, ns):
 
 def prdn(orig, dec, bps, nch, ns):
     return prdn_parts(orig, dec, bps, nch, ns)[0]
-
-
-def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.int32)).view(np.uint8).reshape(-1)
 
 
 def _noisy(native, bps, nch, ns, seed, amp):

@@ -3,7 +3,7 @@
 A case is ONE recording of nblocks * ns rows cut into nblocks blocks of the handle's shape (bps, nch, ns).  The reference
 user's loop is one i_filter per channel, init_history_values once on the channel's first sample, then filter_opt on every
 sample of every block in order -- so the answer does not depend on where the recording is cut, and the restatement is the
-stateless one over the concatenation: fir_cases.fir_i32 on all rows, iir_cases._chain without re-initialisation.
+stateless one over the concatenation: fir_cases.fir_i32 on all rows, iir_cases.iir_double per channel on all rows.
 
 The cases feed tests/golden/make_stream_filter_record.py, which records the compiled reference's answers in
 tests/golden/stream_filter_record.json.  The tests take the coefficients from that record (stored exactly).
@@ -13,13 +13,9 @@ import numpy as np
 import cases
 import fir_cases as fc
 import iir_cases as ic
+import casetools
+from casetools import _take
 from rspt_amd import synth
-
-
-def _take(data, bps, nch, rows):
-    d = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).reshape(-1)[: bps * nch * rows])
-    assert d.size == bps * nch * rows
-    return d
 
 
 def stream_cases():
@@ -75,13 +71,7 @@ def stream_cases():
 
 def iir_stream_double(native, bps, nch, rows, n, d, init):
     """[rows][nch] float64: one filter per channel over the whole recording, before the truncation"""
-    x = fc.native_to_i32(native, bps, nch, rows).astype(np.float64)
-    n = [float(v) for v in n]
-    d = [float(v) for v in d]
-    nc = len(n)
-    with np.errstate(over="ignore", invalid="ignore"):
-        out, _, _ = ic._chain(list(x), [np.zeros(nch)] * nc, [np.zeros(nch)] * nc, n, d, init)
-    return np.array(out).reshape(rows, nch)
+    return ic.iir_double(native, bps, nch, rows, n, d, init, shared=False)[0]
 
 
 def filtered(c, kernel=None, n=None, d=None):
@@ -110,13 +100,7 @@ def with_record_coefficients(c, r):
 
 def splits(nblocks):
     """the three drivings of a recording: all blocks in one call, one block per call, an uneven split (1, 5, 2, 8, 1, ...)"""
-    uneven, left, i = [], nblocks, 0
-    while left:
-        k = min((1, 5, 2, 8)[i % 4], left)
-        uneven.append(k)
-        left -= k
-        i += 1
-    return {"one_call": [nblocks], "per_block": [1] * nblocks, "uneven": uneven}
+    return casetools.splits(nblocks, (1, 5, 2, 8))
 
 
 # the equivalence with the stateless stages at full size: 64 ch x 65536 int32 as 16 blocks of 4096
