@@ -18,29 +18,104 @@ KIND_HZR, KIND_XDELTA_HZR, KIND_DCT, KIND_HADAMARD, KIND_BYTES = 0, 1, 2, 3, 4
 KINDS = {"hzr": 0, "xdelta_hzr": 1, "dct": 2, "hadamard": 3, "bytes": 4}
 DCT_FORCE_FFT = 0x100  # RSPT_HIP_DCT_FORCE_FFT (test hook, include/rspt_hip.h)
 
-# every symbol include/rspt_hip.h declares (tests check the library exports them all)
-C_ABI_SYMBOLS = [
-    "rspt_hip_status_string", "rspt_hip_last_hip_error", "rspt_hip_device_count", "rspt_hip_packer_create",
-    "rspt_hip_packer_destroy", "rspt_hip_compress", "rspt_hip_decompress", "rspt_hip_decompress_bounded", "rspt_hip_max_compressed_size",
-    "rspt_hip_block_bytes", "rspt_hip_current_nb", "rspt_hip_set_nb", "rspt_hip_set_verify", "rspt_hip_reserve", "rspt_hip_compress_batch_dev",
-    "rspt_hip_decompress_batch_dev", "rspt_hip_decompress_packed_dev", "rspt_hip_pack_bound", "rspt_hip_pack_batch_dev", "rspt_hip_stream", "rspt_hip_synchronize", "rspt_hip_set_profiling", "rspt_hip_stage_count",
-    "rspt_hip_stage_name", "rspt_hip_stage_times", "rspt_hip_debug_read", "rspt_hip_iir_prefilter_batch_dev", "rspt_hip_fir_prefilter_batch_dev", "rspt_hip_median_filter_batch_dev", "rspt_hip_design_iir",
-    "rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev",
-    "rspt_hip_iir_cascade_batch_dev", "rspt_hip_iir_cascade_state_bytes", "rspt_hip_iir_cascade_stream_dev",
-    "rspt_hip_iir_zero_phase_work_bytes", "rspt_hip_iir_zero_phase_batch_dev",
-    "rspt_hip_median_state_bytes", "rspt_hip_median_filter_stream_dev",
-    "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev", "rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev",
-    "rspt_hip_prdn_batch_dev", "rspt_hip_native_to_i32_batch_dev", "rspt_hip_i32_to_native_batch_dev",
-    "rspt_hip_set_byte_order", "rspt_hip_host_alloc", "rspt_hip_host_free",
-    "rspt_hip_compress_many", "rspt_hip_decompress_many", "rspt_hip_gather_sizes", "rspt_hip_gather_payload", "rspt_hip_gather_containers",
-    "rspt_hip_gather_post_sizes", "rspt_hip_gather_post_payload", "rspt_hip_gather_wait",
-    "rspt_hip_hzr_max_compressed_size", "rspt_hip_hzr_verify_batch_dev",
-    "rspt_hip_feed_begin", "rspt_hip_feed_push", "rspt_hip_feed_submit", "rspt_hip_feed_poll", "rspt_hip_feed_flush", "rspt_hip_feed_end",
-]
+_p, _i, _u, _z, _d = C.c_void_p, C.c_int, C.c_uint, C.c_size_t, C.c_double
+_dp, _u8p, _szp = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)
+_casc = [_p, _p, _z, _z, _dp, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), _u8p]  # what both cascade entries start with
 
-_u8p = C.POINTER(C.c_uint8)
-_szp = C.POINTER(C.c_size_t)
+# The C ABI, stated once: every function include/rspt_hip.h declares -> (restype, argtypes).  bind() applies it to a loaded
+# library and tests/test_cabi.py holds it against the header's text.  A handle, a device pointer, a stream and a host buffer
+# taken as an address are all c_void_p; the typed pointers are the ones callers hand ctypes arrays or byref() values to.
+C_ABI = {
+    "rspt_hip_status_string": (C.c_char_p, [_i]),
+    "rspt_hip_last_hip_error": (_i, [_p]),
+    "rspt_hip_device_count": (_i, []),
+    "rspt_hip_packer_create": (_i, [C.POINTER(_p), _i, _z, _z, _z, _z, _i]),
+    "rspt_hip_packer_destroy": (None, [_p]),
+    "rspt_hip_compress": (_i, [_p, _p, _p, _z, _szp]),
+    "rspt_hip_decompress": (_i, [_p, _p, _szp, _p]),
+    "rspt_hip_decompress_bounded": (_i, [_p, _p, _z, _szp, _p]),
+    "rspt_hip_max_compressed_size": (_z, [_p]),
+    "rspt_hip_block_bytes": (_z, [_p]),
+    "rspt_hip_hzr_max_compressed_size": (_z, [_z]),
+    "rspt_hip_current_nb": (_u, [_p]),
+    "rspt_hip_set_nb": (_i, [_p, _u]),
+    "rspt_hip_set_verify": (_i, [_p, _i]),
+    "rspt_hip_set_byte_order": (_i, [_p, _i]),
+    "rspt_hip_host_alloc": (_p, [_z]),
+    "rspt_hip_host_free": (None, [_p]),
+    "rspt_hip_compress_many": (_i, [_p, _p, _z, _p, _z, _szp]),
+    "rspt_hip_decompress_many": (_i, [_p, _p, _z, _szp, _z, _p, _szp]),
+    "rspt_hip_feed_begin": (_i, [_p, _z, _z]),
+    "rspt_hip_feed_push": (_i, [_p, _p, _p, _z]),
+    "rspt_hip_feed_submit": (_i, [_p]),
+    "rspt_hip_feed_poll": (_i, [_p, _szp, _szp, C.POINTER(_i)]),
+    "rspt_hip_feed_flush": (_i, [_p]),
+    "rspt_hip_feed_end": (_i, [_p]),
+    "rspt_hip_reserve": (_i, [_p, _z]),
+    "rspt_hip_compress_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
+    "rspt_hip_decompress_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
+    "rspt_hip_hzr_verify_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
+    "rspt_hip_pack_bound": (_z, [_p, _z]),
+    "rspt_hip_pack_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p, _p]),
+    "rspt_hip_decompress_packed_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
+    "rspt_hip_gather_sizes": (_i, [_p, _p, _i, _p, _p, _p, _p]),
+    "rspt_hip_gather_payload": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "rspt_hip_gather_containers": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _z, _p, _p]),
+    "rspt_hip_gather_post_sizes": (_i, [_p, _p, _i, _p, _i, _p]),
+    "rspt_hip_gather_post_payload": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _z, _p]),
+    "rspt_hip_gather_wait": (_i, [_p, _i, _p]),
+    "rspt_hip_iir_prefilter_batch_dev": (_i, [_p, _p, _z, _dp, _dp, _z, _i, _i, _p]),
+    "rspt_hip_iir_state_bytes": (_i, [_p, _szp]),
+    "rspt_hip_iir_prefilter_stream_dev": (_i, [_p, _p, _z, _dp, _dp, _z, _i, _p, _p]),
+    "rspt_hip_iir_cascade_batch_dev": (_i, _casc + [_p]),
+    "rspt_hip_iir_cascade_state_bytes": (_i, [_p, _z, _szp]),
+    "rspt_hip_iir_cascade_stream_dev": (_i, _casc + [_p, _p]),
+    "rspt_hip_iir_zero_phase_work_bytes": (_i, [_p, _z, _szp]),
+    "rspt_hip_iir_zero_phase_batch_dev": (_i, [_p, _p, _z, _dp, _dp, _z, _i, _i, _p, _z, _p]),
+    "rspt_hip_fir_prefilter_batch_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p]),
+    "rspt_hip_fir_state_bytes": (_i, [_p, _z, _szp]),
+    "rspt_hip_fir_prefilter_stream_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p, _p]),
+    "rspt_hip_median_filter_batch_dev": (_i, [_p, _p, _p, _z, _z, _p]),
+    "rspt_hip_median_state_bytes": (_i, [_p, _z, _szp]),
+    "rspt_hip_median_filter_stream_dev": (_i, [_p, _p, _p, _z, _z, _p, _p]),
+    "rspt_hip_design_iir": (_i, [_i, _i, _d, _d, _d, _dp, _dp, _szp]),
+    "rspt_hip_peak_state_bytes": (_i, [_p, _szp]),
+    "rspt_hip_peak_detect_batch_dev": (_i, [_p, _p, _z, _i, _d, _d, _p, _p, _p, _p, _z, _p, _p, _p]),
+    "rspt_hip_peak_offline_work_bytes": (_i, [_p, _z, _i, _szp]),
+    "rspt_hip_peak_detect_offline_batch_dev": (_i, [_p, _p, _z, _d, _d, _p, _p, _p, _p, _p, _z, _p, _p, _p]),
+    "rspt_hip_prdn_batch_dev": (_i, [_p, _p, _p, _z, _p, _p, _p, _p, _p]),
+    "rspt_hip_native_to_i32_batch_dev": (_i, [_p, _p, _p, _z, _p]),
+    "rspt_hip_i32_to_native_batch_dev": (_i, [_p, _p, _p, _z, _p]),
+    "rspt_hip_stream": (_p, [_p]),
+    "rspt_hip_synchronize": (_i, [_p]),
+    "rspt_hip_set_profiling": (_i, [_p, _i]),
+    "rspt_hip_stage_count": (_i, [_p]),
+    "rspt_hip_stage_name": (C.c_char_p, [_p, _i]),
+    "rspt_hip_stage_times": (_i, [_p, C.POINTER(C.c_float), _i]),
+    "rspt_hip_debug_read": (C.c_longlong, [_p, _i, _p, _z]),
+}
+# the C++ factories behind the same library (include/signal_packer.h), via their C shim in signal_packer_hip.cpp
+CXX_SHIM = {
+    "rspt_cxx_new": (_p, [_i, _z, _z, _z, _z]),
+    "rspt_cxx_delete": (None, [_i, _p]),
+    "rspt_cxx_compress": (None, [_p, _p, _p, _z, _szp]),
+    "rspt_cxx_decompress": (_i, [_p, _p, _szp, _p]),
+    "rspt_cxx_set_device": (_i, [_i]),
+}
+C_ABI_SYMBOLS = list(C_ABI)  # every symbol include/rspt_hip.h declares (tests check the library exports them all)
 _lib = None
+
+
+def bind(L, missing_ok=False):
+    """Give every function of the two tables its restype and argtypes on the loaded library L and return L.  missing_ok: skip
+    what L does not export -- an older build loaded beside this one for A/B timing lacks the newer entries."""
+    for table in (C_ABI, CXX_SHIM):
+        for name, (restype, argtypes) in table.items():
+            if missing_ok and not hasattr(L, name):
+                continue
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, list(argtypes)
+    return L
 
 
 class RsptHipError(RuntimeError):
@@ -76,104 +151,13 @@ def lib():
     # /opt/rocm's runtime before importing torch leaves torch without a visible device).
     import torch  # noqa: F401
 
-    L = C.CDLL(path)
-    L.rspt_hip_status_string.restype, L.rspt_hip_status_string.argtypes = C.c_char_p, [C.c_int]
-    L.rspt_hip_last_hip_error.restype, L.rspt_hip_last_hip_error.argtypes = C.c_int, [C.c_void_p]
-    L.rspt_hip_device_count.restype, L.rspt_hip_device_count.argtypes = C.c_int, []
-    L.rspt_hip_packer_create.restype = C.c_int
-    L.rspt_hip_packer_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
-    L.rspt_hip_packer_destroy.restype, L.rspt_hip_packer_destroy.argtypes = None, [C.c_void_p]
-    L.rspt_hip_compress.restype, L.rspt_hip_compress.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _szp]
-    L.rspt_hip_decompress.restype, L.rspt_hip_decompress.argtypes = C.c_int, [C.c_void_p, C.c_void_p, _szp, C.c_void_p]
-    L.rspt_hip_decompress_bounded.restype, L.rspt_hip_decompress_bounded.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _szp, C.c_void_p]
-    L.rspt_hip_compress_many.restype = C.c_int
-    L.rspt_hip_compress_many.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _szp]
-    L.rspt_hip_decompress_many.restype = C.c_int
-    L.rspt_hip_decompress_many.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, _szp, C.c_size_t, C.c_void_p, _szp]
-    L.rspt_hip_max_compressed_size.restype, L.rspt_hip_max_compressed_size.argtypes = C.c_size_t, [C.c_void_p]
-    L.rspt_hip_block_bytes.restype, L.rspt_hip_block_bytes.argtypes = C.c_size_t, [C.c_void_p]
-    L.rspt_hip_current_nb.restype, L.rspt_hip_current_nb.argtypes = C.c_uint, [C.c_void_p]
-    L.rspt_hip_set_nb.restype, L.rspt_hip_set_nb.argtypes = C.c_int, [C.c_void_p, C.c_uint]
-    L.rspt_hip_set_verify.restype, L.rspt_hip_set_verify.argtypes = C.c_int, [C.c_void_p, C.c_int]
-    L.rspt_hip_reserve.restype, L.rspt_hip_reserve.argtypes = C.c_int, [C.c_void_p, C.c_size_t]
-    L.rspt_hip_compress_batch_dev.restype = C.c_int
-    L.rspt_hip_compress_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.rspt_hip_decompress_batch_dev.restype = C.c_int
-    L.rspt_hip_decompress_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rspt_hip_decompress_packed_dev.restype = C.c_int
-    L.rspt_hip_decompress_packed_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rspt_hip_synchronize.restype, L.rspt_hip_synchronize.argtypes = C.c_int, [C.c_void_p]
-    L.rspt_hip_stream.restype, L.rspt_hip_stream.argtypes = C.c_void_p, [C.c_void_p]
-    L.rspt_hip_pack_bound.restype, L.rspt_hip_pack_bound.argtypes = C.c_size_t, [C.c_void_p, C.c_size_t]
-    L.rspt_hip_pack_batch_dev.restype = C.c_int
-    L.rspt_hip_pack_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rspt_hip_set_profiling.restype, L.rspt_hip_set_profiling.argtypes = C.c_int, [C.c_void_p, C.c_int]
-    L.rspt_hip_stage_count.restype, L.rspt_hip_stage_count.argtypes = C.c_int, [C.c_void_p]
-    L.rspt_hip_stage_name.restype, L.rspt_hip_stage_name.argtypes = C.c_char_p, [C.c_void_p, C.c_int]
-    L.rspt_hip_stage_times.restype, L.rspt_hip_stage_times.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]
-    L.rspt_hip_debug_read.restype, L.rspt_hip_debug_read.argtypes = C.c_longlong, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.rspt_hip_set_byte_order.restype, L.rspt_hip_set_byte_order.argtypes = C.c_int, [C.c_void_p, C.c_int]
-    L.rspt_hip_host_alloc.restype, L.rspt_hip_host_alloc.argtypes = C.c_void_p, [C.c_size_t]
-    L.rspt_hip_host_free.restype, L.rspt_hip_host_free.argtypes = None, [C.c_void_p]
-    L.rspt_hip_iir_prefilter_batch_dev.restype = C.c_int
-    L.rspt_hip_iir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
-                                                   C.c_int, C.c_void_p]
-    L.rspt_hip_iir_state_bytes.restype, L.rspt_hip_iir_state_bytes.argtypes = C.c_int, [C.c_void_p, _szp]
-    L.rspt_hip_iir_prefilter_stream_dev.restype = C.c_int
-    L.rspt_hip_iir_prefilter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
-                                                    C.c_void_p, C.c_void_p]
-    _casc = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), _u8p]
-    L.rspt_hip_iir_cascade_batch_dev.restype, L.rspt_hip_iir_cascade_batch_dev.argtypes = C.c_int, _casc + [C.c_void_p]
-    L.rspt_hip_iir_cascade_state_bytes.restype, L.rspt_hip_iir_cascade_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
-    L.rspt_hip_iir_cascade_stream_dev.restype, L.rspt_hip_iir_cascade_stream_dev.argtypes = C.c_int, _casc + [C.c_void_p, C.c_void_p]
-    L.rspt_hip_iir_zero_phase_work_bytes.restype, L.rspt_hip_iir_zero_phase_work_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
-    L.rspt_hip_iir_zero_phase_batch_dev.restype = C.c_int
-    L.rspt_hip_iir_zero_phase_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
-                                                    C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.rspt_hip_fir_state_bytes.restype, L.rspt_hip_fir_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
-    L.rspt_hip_fir_prefilter_stream_dev.restype = C.c_int
-    L.rspt_hip_fir_prefilter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p, C.c_void_p]
-    L.rspt_hip_fir_prefilter_batch_dev.restype = C.c_int
-    L.rspt_hip_fir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.c_void_p]
-    L.rspt_hip_median_filter_batch_dev.restype = C.c_int
-    L.rspt_hip_median_filter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-    L.rspt_hip_median_state_bytes.restype, L.rspt_hip_median_state_bytes.argtypes = C.c_int, [C.c_void_p, C.c_size_t, _szp]
-    L.rspt_hip_median_filter_stream_dev.restype = C.c_int
-    L.rspt_hip_median_filter_stream_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.rspt_hip_design_iir.restype = C.c_int
-    L.rspt_hip_design_iir.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _szp]
-    L.rspt_hip_peak_state_bytes.restype, L.rspt_hip_peak_state_bytes.argtypes = C.c_int, [C.c_void_p, _szp]
-    L.rspt_hip_peak_detect_batch_dev.restype = C.c_int
-    L.rspt_hip_peak_detect_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rspt_hip_peak_offline_work_bytes.restype = C.c_int
-    L.rspt_hip_peak_offline_work_bytes.argtypes = [C.c_void_p, C.c_size_t, C.c_int, _szp]
-    L.rspt_hip_peak_detect_offline_batch_dev.restype = C.c_int
-    L.rspt_hip_peak_detect_offline_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rspt_hip_prdn_batch_dev.restype = C.c_int
-    L.rspt_hip_prdn_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rspt_hip_native_to_i32_batch_dev.restype = C.c_int
-    L.rspt_hip_native_to_i32_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.rspt_hip_i32_to_native_batch_dev.restype = C.c_int
-    L.rspt_hip_i32_to_native_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.rspt_hip_hzr_max_compressed_size.restype, L.rspt_hip_hzr_max_compressed_size.argtypes = C.c_size_t, [C.c_size_t]
-    L.rspt_hip_hzr_verify_batch_dev.restype = C.c_int
-    L.rspt_hip_hzr_verify_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.rspt_hip_feed_begin.restype, L.rspt_hip_feed_begin.argtypes = C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]
-    L.rspt_hip_feed_push.restype, L.rspt_hip_feed_push.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.rspt_hip_feed_submit.restype, L.rspt_hip_feed_submit.argtypes = C.c_int, [C.c_void_p]
-    L.rspt_hip_feed_poll.restype, L.rspt_hip_feed_poll.argtypes = C.c_int, [C.c_void_p, _szp, _szp, C.POINTER(C.c_int)]
-    L.rspt_hip_feed_flush.restype, L.rspt_hip_feed_flush.argtypes = C.c_int, [C.c_void_p]
-    L.rspt_hip_feed_end.restype, L.rspt_hip_feed_end.argtypes = C.c_int, [C.c_void_p]
-    # the C++ factories behind the same library (include/signal_packer.h), via their C shim
-    L.rspt_cxx_new.restype, L.rspt_cxx_new.argtypes = C.c_void_p, [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.rspt_cxx_delete.restype, L.rspt_cxx_delete.argtypes = None, [C.c_int, C.c_void_p]
-    L.rspt_cxx_compress.restype, L.rspt_cxx_compress.argtypes = None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _szp]
-    L.rspt_cxx_decompress.restype, L.rspt_cxx_decompress.argtypes = C.c_int, [C.c_void_p, C.c_void_p, _szp, C.c_void_p]
-    L.rspt_cxx_set_device.restype, L.rspt_cxx_set_device.argtypes = C.c_int, [C.c_int]
-    _lib = L
-    return L
+    _lib = bind(C.CDLL(path))
+    return _lib
+
+
+def _dptr(a):
+    """the double* of a float64 numpy array"""
+    return a.ctypes.data_as(_dp)
 
 
 def _as_u8(buf):
@@ -200,6 +184,41 @@ class SignalPacker:
     def _check(self, where, rc):
         if rc != 0:
             raise RsptHipError(where, rc, self._L.rspt_hip_last_hip_error(self._h))
+
+    # -- the frame of a device-batch call ---------------------------------------
+    def _call(self, entry, *args):
+        """entry(handle, *args); a status other than RSPT_HIP_OK raises RsptHipError under the entry's name"""
+        self._check(entry, getattr(self._L, entry)(self._h, *args))
+
+    def _nblocks(self, t, dtype=None, per_block=None):
+        """the block count of t: a contiguous device tensor of whole blocks (uint8, block_bytes each, unless told otherwise)"""
+        import torch
+
+        per_block = self.block_bytes if per_block is None else per_block
+        assert t.is_cuda and t.dtype == (torch.uint8 if dtype is None else dtype) and t.is_contiguous()
+        nblocks = t.numel() // per_block
+        assert nblocks * per_block == t.numel()
+        return nblocks
+
+    @staticmethod
+    def _stream(stream, device):
+        """the hipStream_t of a call: `stream`, or torch's current stream on `device` when it is None"""
+        import torch
+
+        return stream if stream is not None else torch.cuda.current_stream(device).cuda_stream
+
+    def _bytes(self, entry, *args):
+        """a *_state_bytes / *_work_bytes entry -> the byte count it writes through its size_t*"""
+        n = C.c_size_t()
+        self._call(entry, *args, C.byref(n))
+        return n.value
+
+    @staticmethod
+    def _zero_state(nbytes, device):
+        """a zeroed uint8 device tensor of nbytes: the fresh state of every carried-state stage"""
+        import torch
+
+        return torch.zeros(nbytes, dtype=torch.uint8, device=device if device is not None else "cuda")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -321,18 +340,15 @@ class SignalPacker:
         asynchronous on `stream` (default: torch's current stream)."""
         import torch
 
-        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
-        nblocks = d_src.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_src.numel()
+        nblocks = self._nblocks(d_src)
         if dst_stride is None:
             dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
         if d_dst is None:
             d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=d_src.device)
         if d_sizes is None:
             d_sizes = torch.empty(nblocks, dtype=torch.int64, device=d_src.device)
-        st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
-        rc = self._L.rspt_hip_compress_batch_dev(self._h, d_src.data_ptr(), nblocks, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
-        self._check("rspt_hip_compress_batch_dev", rc)
+        st = self._stream(stream, d_src.device)
+        self._call("rspt_hip_compress_batch_dev", d_src.data_ptr(), nblocks, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
         return d_dst, d_sizes
 
     def decompress_batch(self, d_streams, nblocks, src_stride, d_out=None, d_consumed=None, stream=None):
@@ -342,9 +358,8 @@ class SignalPacker:
             d_out = torch.empty((nblocks, self.block_bytes), dtype=torch.uint8, device=d_streams.device)
         if d_consumed is None:
             d_consumed = torch.empty(nblocks, dtype=torch.int64, device=d_streams.device)
-        st = stream if stream is not None else torch.cuda.current_stream(d_streams.device).cuda_stream
-        rc = self._L.rspt_hip_decompress_batch_dev(self._h, d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
-        self._check("rspt_hip_decompress_batch_dev", rc)
+        st = self._stream(stream, d_streams.device)
+        self._call("rspt_hip_decompress_batch_dev", d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
         return d_out, d_consumed
 
     def decompress_packed(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None):
@@ -364,9 +379,8 @@ class SignalPacker:
             d_out = torch.empty((nblocks, self.block_bytes), dtype=torch.uint8, device=d_packed.device)
         if d_consumed is None:
             d_consumed = torch.empty(nblocks, dtype=torch.int64, device=d_packed.device)
-        st = stream if stream is not None else torch.cuda.current_stream(d_packed.device).cuda_stream
-        rc = self._L.rspt_hip_decompress_packed_dev(self._h, d_packed.data_ptr(), plen, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
-        self._check("rspt_hip_decompress_packed_dev", rc)
+        st = self._stream(stream, d_packed.device)
+        self._call("rspt_hip_decompress_packed_dev", d_packed.data_ptr(), plen, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
         return d_out, d_consumed
 
     def hzr_verify_batch(self, d_streams, d_lengths, src_stride=None, d_decoded=None, stream=None):
@@ -382,9 +396,8 @@ class SignalPacker:
         assert d_lengths.is_cuda and d_lengths.dtype == torch.int64 and d_lengths.is_contiguous()
         if d_decoded is None:
             d_decoded = torch.empty(nblocks, dtype=torch.int64, device=d_streams.device)
-        st = stream if stream is not None else torch.cuda.current_stream(d_streams.device).cuda_stream
-        rc = self._L.rspt_hip_hzr_verify_batch_dev(self._h, d_streams.data_ptr(), src_stride, d_lengths.data_ptr(), nblocks, d_decoded.data_ptr(), st)
-        self._check("rspt_hip_hzr_verify_batch_dev", rc)
+        st = self._stream(stream, d_streams.device)
+        self._call("rspt_hip_hzr_verify_batch_dev", d_streams.data_ptr(), src_stride, d_lengths.data_ptr(), nblocks, d_decoded.data_ptr(), st)
         return d_decoded
 
     def pack_bound(self, nblocks):
@@ -400,68 +413,48 @@ class SignalPacker:
             d_packed = torch.empty(self.pack_bound(nblocks), dtype=torch.uint8, device=d_dst.device)
         if d_total is None:
             d_total = torch.zeros(1, dtype=torch.int64, device=d_dst.device)
-        st = stream if stream is not None else torch.cuda.current_stream(d_dst.device).cuda_stream
-        rc = self._L.rspt_hip_pack_batch_dev(self._h, d_dst.data_ptr(), stride, d_sizes.data_ptr(), nblocks, d_packed.data_ptr(), d_total.data_ptr(), st)
-        self._check("rspt_hip_pack_batch_dev", rc)
+        st = self._stream(stream, d_dst.device)
+        self._call("rspt_hip_pack_batch_dev", d_dst.data_ptr(), stride, d_sizes.data_ptr(), nblocks, d_packed.data_ptr(), d_total.data_ptr(), st)
         return d_packed, d_total
 
     def iir_state_bytes(self):
-        n = C.c_size_t()
-        self._check("rspt_hip_iir_state_bytes", self._L.rspt_hip_iir_state_bytes(self._h, C.byref(n)))
-        return n.value
+        return self._bytes("rspt_hip_iir_state_bytes")
 
     def iir_state(self, device=None):
         """A zeroed state for iir_prefilter_batch(state=...): a fresh filter for every channel (uint8 device tensor)."""
-        import torch
-
-        return torch.zeros(self.iir_state_bytes(), dtype=torch.uint8, device=device if device is not None else "cuda")
+        return self._zero_state(self.iir_state_bytes(), device)
 
     def fir_state_bytes(self, kernel_size):
-        n = C.c_size_t()
-        self._check("rspt_hip_fir_state_bytes", self._L.rspt_hip_fir_state_bytes(self._h, int(kernel_size), C.byref(n)))
-        return n.value
+        return self._bytes("rspt_hip_fir_state_bytes", int(kernel_size))
 
     def fir_state(self, kernel_size, device=None):
         """A zeroed state for fir_prefilter_batch(state=...) with a kernel of kernel_size taps: a fresh filter for every channel."""
-        import torch
-
-        return torch.zeros(self.fir_state_bytes(kernel_size), dtype=torch.uint8, device=device if device is not None else "cuda")
+        return self._zero_state(self.fir_state_bytes(kernel_size), device)
 
     def iir_prefilter_batch(self, d_buf, n, d, init_nr_samples=2000, per_channel=False, stream=None, state=None):
         """The reference's pre-filter step (rspt_test.cpp:116-136) on device-resident blocks, in place; asynchronous.
         state: None, or an iir_state() tensor: the blocks are then consecutive pieces of one recording, one filter per channel
         running through them and on into the next call (rspt_hip_iir_prefilter_stream_dev); needs per_channel=True."""
-        import torch
-
-        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous()
-        nblocks = d_buf.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_buf.numel()
+        nblocks = self._nblocks(d_buf)
         nn, dd = np.ascontiguousarray(n, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
         assert nn.size == dd.size
-        st = stream if stream is not None else torch.cuda.current_stream(d_buf.device).cuda_stream
+        st = self._stream(stream, d_buf.device)
+        args = (d_buf.data_ptr(), nblocks, _dptr(nn), _dptr(dd), nn.size, init_nr_samples)
         if state is not None:
             if not per_channel:
                 raise ValueError("iir_prefilter_batch: a carried state is one filter per channel (per_channel=True)")
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.iir_state_bytes()
-            rc = self._L.rspt_hip_iir_prefilter_stream_dev(self._h, d_buf.data_ptr(), nblocks, nn.ctypes.data_as(C.POINTER(C.c_double)),
-                                                           dd.ctypes.data_as(C.POINTER(C.c_double)), nn.size, init_nr_samples, state.data_ptr(), st)
-            self._check("rspt_hip_iir_prefilter_stream_dev", rc)
-            return d_buf
-        rc = self._L.rspt_hip_iir_prefilter_batch_dev(self._h, d_buf.data_ptr(), nblocks, nn.ctypes.data_as(C.POINTER(C.c_double)),
-                                                      dd.ctypes.data_as(C.POINTER(C.c_double)), nn.size, init_nr_samples, int(bool(per_channel)), st)
-        self._check("rspt_hip_iir_prefilter_batch_dev", rc)
+            self._call("rspt_hip_iir_prefilter_stream_dev", *args, state.data_ptr(), st)
+        else:
+            self._call("rspt_hip_iir_prefilter_batch_dev", *args, int(bool(per_channel)), st)
         return d_buf
 
     def iir_cascade_state_bytes(self, nsections):
-        n = C.c_size_t()
-        self._check("rspt_hip_iir_cascade_state_bytes", self._L.rspt_hip_iir_cascade_state_bytes(self._h, int(nsections), C.byref(n)))
-        return n.value
+        return self._bytes("rspt_hip_iir_cascade_state_bytes", int(nsections))
 
     def iir_cascade_state(self, nsections, device=None):
         """A zeroed state for iir_cascade_batch(state=...) with nsections sections: a fresh chain for every channel."""
-        import torch
-
-        return torch.zeros(self.iir_cascade_state_bytes(nsections), dtype=torch.uint8, device=device if device is not None else "cuda")
+        return self._zero_state(self.iir_cascade_state_bytes(nsections), device)
 
     def iir_cascade_batch(self, d_buf, sections, stream=None, state=None):
         """1 to 4 reference IIR filters per channel, chained in double and truncated once (rspt_hip.h: rspt_hip_iir_cascade_batch_dev),
@@ -470,11 +463,7 @@ class SignalPacker:
         2000, use_filter (the section runs filter() instead of filter_opt()) to False.
         state: None (a fresh chain per block and channel), or an iir_cascade_state(len(sections)) tensor: the blocks are then
         consecutive pieces of one recording, one chain per channel running through them and on into the next call."""
-        import torch
-
-        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous()
-        nblocks = d_buf.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_buf.numel()
+        nblocks = self._nblocks(d_buf)
         S = len(sections)
         if not 1 <= S <= 4:
             raise ValueError("iir_cascade_batch: 1 to 4 sections")
@@ -486,20 +475,18 @@ class SignalPacker:
                 raise ValueError("iir_cascade_batch: section %d needs 2 to 5 coefficients on each side" % k)
             nn[k, : n.size], dd[k, : d.size] = n, d
             nc[k], init[k], filt[k] = n.size, (sec[2] if len(sec) > 2 else 2000), bool(sec[3]) if len(sec) > 3 else False
-        st = stream if stream is not None else torch.cuda.current_stream(d_buf.device).cuda_stream
-        args = (self._h, d_buf.data_ptr(), nblocks, S, nn.ctypes.data_as(C.POINTER(C.c_double)), dd.ctypes.data_as(C.POINTER(C.c_double)),
+        st = self._stream(stream, d_buf.device)
+        args = (d_buf.data_ptr(), nblocks, S, _dptr(nn), _dptr(dd),
                 nc.ctypes.data_as(C.POINTER(C.c_uint32)), init.ctypes.data_as(C.POINTER(C.c_int32)), filt.ctypes.data_as(_u8p))
         if state is not None:
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.iir_cascade_state_bytes(S)
-            self._check("rspt_hip_iir_cascade_stream_dev", self._L.rspt_hip_iir_cascade_stream_dev(*args, state.data_ptr(), st))
+            self._call("rspt_hip_iir_cascade_stream_dev", *args, state.data_ptr(), st)
         else:
-            self._check("rspt_hip_iir_cascade_batch_dev", self._L.rspt_hip_iir_cascade_batch_dev(*args, st))
+            self._call("rspt_hip_iir_cascade_batch_dev", *args, st)
         return d_buf
 
     def iir_zero_phase_work_bytes(self, nblocks):
-        n = C.c_size_t()
-        self._check("rspt_hip_iir_zero_phase_work_bytes", self._L.rspt_hip_iir_zero_phase_work_bytes(self._h, int(nblocks), C.byref(n)))
-        return n.value
+        return self._bytes("rspt_hip_iir_zero_phase_work_bytes", int(nblocks))
 
     def iir_zero_phase_batch(self, d_buf, n, d, init_nr_samples=2000, backward_init_nr_samples=0, work=None, stream=None):
         """Zero-phase (forward-backward) IIR filtering on device-resident blocks, in place; asynchronous.  One fresh reference
@@ -508,19 +495,15 @@ class SignalPacker:
         work: a device tensor of at least iir_zero_phase_work_bytes(nblocks) bytes, 8-byte aligned; None: allocated here."""
         import torch
 
-        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous()
-        nblocks = d_buf.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_buf.numel()
+        nblocks = self._nblocks(d_buf)
         nn, dd = np.ascontiguousarray(n, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
         assert nn.size == dd.size
         if work is None:
             work = torch.empty(max(1, (self.iir_zero_phase_work_bytes(max(nblocks, 1)) + 7) // 8), dtype=torch.float64, device=d_buf.device)
         assert work.is_cuda and work.is_contiguous()
-        st = stream if stream is not None else torch.cuda.current_stream(d_buf.device).cuda_stream
-        rc = self._L.rspt_hip_iir_zero_phase_batch_dev(self._h, d_buf.data_ptr(), nblocks, nn.ctypes.data_as(C.POINTER(C.c_double)),
-                                                       dd.ctypes.data_as(C.POINTER(C.c_double)), nn.size, int(init_nr_samples),
-                                                       int(backward_init_nr_samples), work.data_ptr(), work.numel() * work.element_size(), st)
-        self._check("rspt_hip_iir_zero_phase_batch_dev", rc)
+        st = self._stream(stream, d_buf.device)
+        self._call("rspt_hip_iir_zero_phase_batch_dev", d_buf.data_ptr(), nblocks, _dptr(nn), _dptr(dd), nn.size, int(init_nr_samples),
+                   int(backward_init_nr_samples), work.data_ptr(), work.numel() * work.element_size(), st)
         return d_buf
 
     def _window_call_buffers(self, d_src, d_dst, stream):
@@ -528,13 +511,10 @@ class SignalPacker:
         contiguous uint8 on the device, the output d_src itself when d_dst is None, the current stream when stream is None."""
         import torch
 
-        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
-        nblocks = d_src.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_src.numel()
+        nblocks = self._nblocks(d_src)
         out = d_src if d_dst is None else d_dst
         assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == d_src.numel()
-        st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
-        return nblocks, out, st
+        return nblocks, out, self._stream(stream, d_src.device)
 
     def fir_prefilter_batch(self, d_src, kernel, d_dst=None, stream=None, state=None):
         """The reference's FIR pre-filter (i_filter::new_fir, init_history_values, filter_opt; rspt_hip.h) on device-resident
@@ -545,25 +525,17 @@ class SignalPacker:
         k = np.ascontiguousarray(kernel, dtype=np.float64).reshape(-1)
         if state is not None:
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.fir_state_bytes(k.size)
-            rc = self._L.rspt_hip_fir_prefilter_stream_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, k.ctypes.data_as(C.POINTER(C.c_double)),
-                                                           k.size, state.data_ptr(), st)
-            self._check("rspt_hip_fir_prefilter_stream_dev", rc)
-            return out
-        rc = self._L.rspt_hip_fir_prefilter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, k.ctypes.data_as(C.POINTER(C.c_double)),
-                                                      k.size, st)
-        self._check("rspt_hip_fir_prefilter_batch_dev", rc)
+            self._call("rspt_hip_fir_prefilter_stream_dev", d_src.data_ptr(), out.data_ptr(), nblocks, _dptr(k), k.size, state.data_ptr(), st)
+        else:
+            self._call("rspt_hip_fir_prefilter_batch_dev", d_src.data_ptr(), out.data_ptr(), nblocks, _dptr(k), k.size, st)
         return out
 
     def median_state_bytes(self, window):
-        n = C.c_size_t()
-        self._check("rspt_hip_median_state_bytes", self._L.rspt_hip_median_state_bytes(self._h, int(window), C.byref(n)))
-        return n.value
+        return self._bytes("rspt_hip_median_state_bytes", int(window))
 
     def median_state(self, window, device=None):
         """A zeroed state for median_filter_batch(state=...) with this window: a fresh object for every channel."""
-        import torch
-
-        return torch.zeros(self.median_state_bytes(window), dtype=torch.uint8, device=device if device is not None else "cuda")
+        return self._zero_state(self.median_state_bytes(window), device)
 
     def median_filter_batch(self, d_src, window, d_dst=None, stream=None, state=None):
         """The reference's rolling-window median (rolling_window_median<double>(window), one per channel; rspt_hip.h) on
@@ -575,23 +547,17 @@ class SignalPacker:
         nblocks, out, st = self._window_call_buffers(d_src, d_dst, stream)
         if state is not None:
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.median_state_bytes(window)
-            rc = self._L.rspt_hip_median_filter_stream_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, int(window), state.data_ptr(), st)
-            self._check("rspt_hip_median_filter_stream_dev", rc)
-            return out
-        rc = self._L.rspt_hip_median_filter_batch_dev(self._h, d_src.data_ptr(), out.data_ptr(), nblocks, int(window), st)
-        self._check("rspt_hip_median_filter_batch_dev", rc)
+            self._call("rspt_hip_median_filter_stream_dev", d_src.data_ptr(), out.data_ptr(), nblocks, int(window), state.data_ptr(), st)
+        else:
+            self._call("rspt_hip_median_filter_batch_dev", d_src.data_ptr(), out.data_ptr(), nblocks, int(window), st)
         return out
 
     def peak_state_bytes(self):
-        n = C.c_size_t()
-        self._check("rspt_hip_peak_state_bytes", self._L.rspt_hip_peak_state_bytes(self._h, C.byref(n)))
-        return n.value
+        return self._bytes("rspt_hip_peak_state_bytes")
 
     def peak_state(self, device=None):
         """A zeroed state for peak_detect_batch(state=...): a fresh detector for every channel (uint8 device tensor)."""
-        import torch
-
-        return torch.zeros(self.peak_state_bytes(), dtype=torch.uint8, device=device if device is not None else "cuda")
+        return self._zero_state(self.peak_state_bytes(), device)
 
     def _peak_call_buffers(self, d_src, max_peaks, state, traces, stream):
         """What both peak entries share: checks d_src (whole blocks of contiguous uint8 on the device) and state, allocates
@@ -599,9 +565,7 @@ class SignalPacker:
         -> (nblocks, outputs, stream, ptr); ptr(t): t's device pointer, None for None or an empty tensor."""
         import torch
 
-        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
-        nblocks = d_src.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_src.numel()
+        nblocks = self._nblocks(d_src)
         dev = d_src.device
         count = torch.empty((nblocks, self.nch), dtype=torch.int32, device=dev)
         index = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.int32, device=dev)
@@ -612,9 +576,8 @@ class SignalPacker:
             thr = torch.empty_like(sig)
         if state is not None:
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.peak_state_bytes()
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
-        return nblocks, (count, index, value, sig, thr), st, ptr
+        return nblocks, (count, index, value, sig, thr), self._stream(stream, dev), ptr
 
     def peak_detect_batch(self, d_src, variant="online", sampling_rate=None, marker_val=1.0, max_peaks=64, state=None, traces=False, stream=None):
         """The reference's R-peak detectors (peak_detector.h; rspt_hip.h: rspt_hip_peak_detect_batch_dev) on device-resident
@@ -628,15 +591,12 @@ class SignalPacker:
         v = PEAK_VARIANTS[variant] if isinstance(variant, str) else int(variant)
         nblocks, out, st, ptr = self._peak_call_buffers(d_src, max_peaks, state, traces, stream)
         count, index, value, sig, thr = out
-        rc = self._L.rspt_hip_peak_detect_batch_dev(self._h, d_src.data_ptr(), nblocks, v, float(sampling_rate), float(marker_val), ptr(state),
-                                                    count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
-        self._check("rspt_hip_peak_detect_batch_dev", rc)
+        self._call("rspt_hip_peak_detect_batch_dev", d_src.data_ptr(), nblocks, v, float(sampling_rate), float(marker_val), ptr(state),
+                   count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
         return out if traces else out[:3]
 
     def peak_offline_work_bytes(self, nblocks, stateful=False):
-        n = C.c_size_t()
-        self._check("rspt_hip_peak_offline_work_bytes", self._L.rspt_hip_peak_offline_work_bytes(self._h, nblocks, int(bool(stateful)), C.byref(n)))
-        return n.value
+        return self._bytes("rspt_hip_peak_offline_work_bytes", nblocks, int(bool(stateful)))
 
     def peak_detect_offline_batch(self, d_src, sampling_rate, marker_val=1.0, max_peaks=64, state=None, traces=False, stream=None):
         """The reference's zero-phase offline R-peak detector (peak_detector_offline::detect; rspt_hip.h:
@@ -651,9 +611,8 @@ class SignalPacker:
         count, index, value, sig, thr = out
         dev = d_src.device
         work = torch.empty(max(1, (self.peak_offline_work_bytes(max(nblocks, 1), state is not None) + 7) // 8), dtype=torch.float64, device=dev)
-        rc = self._L.rspt_hip_peak_detect_offline_batch_dev(self._h, d_src.data_ptr(), nblocks, float(sampling_rate), float(marker_val), ptr(state),
-                                                            work.data_ptr(), count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
-        self._check("rspt_hip_peak_detect_offline_batch_dev", rc)
+        self._call("rspt_hip_peak_detect_offline_batch_dev", d_src.data_ptr(), nblocks, float(sampling_rate), float(marker_val), ptr(state),
+                   work.data_ptr(), count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
         if stream is not None:  # (the workspace goes back to torch's pool only once the caller's stream is past this call)
             work.record_stream(torch.cuda.ExternalStream(stream, device=dev))
         return out if traces else out[:3]
@@ -665,21 +624,17 @@ class SignalPacker:
         accumulators as the reference leaves them and, per block, 0 for the exact-integer path or 1 for the sequential one (int32)."""
         import torch
 
-        for t in (d_orig, d_dec):
-            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
-        nblocks = d_orig.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_orig.numel() == d_dec.numel()
+        nblocks = self._nblocks(d_orig)
+        assert self._nblocks(d_dec) == nblocks
         dev = d_orig.device
         prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
         mse = ref = path = None
         if parts:
             mse, ref = torch.empty_like(prdn), torch.empty_like(prdn)
             path = torch.empty(nblocks, dtype=torch.int32, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        rc = self._L.rspt_hip_prdn_batch_dev(self._h, d_orig.data_ptr() if nblocks else None, d_dec.data_ptr() if nblocks else None, nblocks,
-                                             prdn.data_ptr() if nblocks else None, ptr(mse), ptr(ref), ptr(path), st)
-        self._check("rspt_hip_prdn_batch_dev", rc)
+        self._call("rspt_hip_prdn_batch_dev", d_orig.data_ptr() if nblocks else None, d_dec.data_ptr() if nblocks else None, nblocks,
+                   prdn.data_ptr() if nblocks else None, ptr(mse), ptr(ref), ptr(path), self._stream(stream, dev))
         return (prdn, mse, ref, path) if parts else prdn
 
     def to_planar_i32(self, d_src, d_out=None, stream=None):
@@ -688,15 +643,12 @@ class SignalPacker:
         sign-extended from bps bytes.  Returns torch.int32 [nblocks, nch, ns].  Asynchronous."""
         import torch
 
-        assert d_src.is_cuda and d_src.dtype == torch.uint8 and d_src.is_contiguous()
-        nblocks = d_src.numel() // self.block_bytes
-        assert nblocks * self.block_bytes == d_src.numel()
+        nblocks = self._nblocks(d_src)
         if d_out is None:
             d_out = torch.empty((nblocks, self.nch, self.ns), dtype=torch.int32, device=d_src.device)
         assert d_out.is_cuda and d_out.dtype == torch.int32 and d_out.is_contiguous() and d_out.numel() == nblocks * self.nch * self.ns
-        st = stream if stream is not None else torch.cuda.current_stream(d_src.device).cuda_stream
-        rc = self._L.rspt_hip_native_to_i32_batch_dev(self._h, d_src.data_ptr() if nblocks else None, d_out.data_ptr() if nblocks else None, nblocks, st)
-        self._check("rspt_hip_native_to_i32_batch_dev", rc)
+        st = self._stream(stream, d_src.device)
+        self._call("rspt_hip_native_to_i32_batch_dev", d_src.data_ptr() if nblocks else None, d_out.data_ptr() if nblocks else None, nblocks, st)
         return d_out
 
     def from_planar_i32(self, d_planar, d_out=None, stream=None):
@@ -705,15 +657,12 @@ class SignalPacker:
         of set_byte_order).  Returns torch.uint8 [nblocks, block_bytes]; d_out may sit at any address.  Asynchronous."""
         import torch
 
-        assert d_planar.is_cuda and d_planar.dtype == torch.int32 and d_planar.is_contiguous()
-        nblocks = d_planar.numel() // (self.nch * self.ns)
-        assert nblocks * self.nch * self.ns == d_planar.numel()
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
         if d_out is None:
             d_out = torch.empty((nblocks, self.block_bytes), dtype=torch.uint8, device=d_planar.device)
         assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() == nblocks * self.block_bytes
-        st = stream if stream is not None else torch.cuda.current_stream(d_planar.device).cuda_stream
-        rc = self._L.rspt_hip_i32_to_native_batch_dev(self._h, d_planar.data_ptr() if nblocks else None, d_out.data_ptr() if nblocks else None, nblocks, st)
-        self._check("rspt_hip_i32_to_native_batch_dev", rc)
+        st = self._stream(stream, d_planar.device)
+        self._call("rspt_hip_i32_to_native_batch_dev", d_planar.data_ptr() if nblocks else None, d_out.data_ptr() if nblocks else None, nblocks, st)
         return d_out
 
     def roundtrip_quality(self, d_src, stream=None):
@@ -803,8 +752,8 @@ def design_iir(type, order, fs, lo, hi=0.0):
         packer.iir_prefilter_batch(buf, n=den, d=num)"""
     t = FILTER_TYPES[type] if isinstance(type, str) else int(type)
     num, den, n = np.zeros(5), np.zeros(5), C.c_size_t()
-    rc = lib().rspt_hip_design_iir(t, int(order), float(fs), float(lo), float(hi), num.ctypes.data_as(C.POINTER(C.c_double)),
-                                   den.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n))
+    rc = lib().rspt_hip_design_iir(t, int(order), float(fs), float(lo), float(hi), _dptr(num),
+                                   _dptr(den), C.byref(n))
     if rc != 0:
         raise RsptHipError("rspt_hip_design_iir", rc)
     return num[: n.value].copy(), den[: n.value].copy()

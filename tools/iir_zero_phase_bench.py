@@ -54,13 +54,7 @@ def summary(v):
 
 def parent_single_stage(path, bps, nch, ns):
     """the single stage through another build of the library: (call(buf), close())"""
-    L = C.CDLL(path)
-    L.rspt_hip_packer_create.restype = C.c_int
-    L.rspt_hip_packer_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
-    L.rspt_hip_packer_destroy.restype, L.rspt_hip_packer_destroy.argtypes = None, [C.c_void_p]
-    L.rspt_hip_iir_prefilter_batch_dev.restype = C.c_int
-    L.rspt_hip_iir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t, C.c_int,
-                                                   C.c_int, C.c_void_p]
+    L = api.bind(C.CDLL(path), missing_ok=True)  # (a parent build lacks this build's newer entries)
     h = C.c_void_p()
     assert L.rspt_hip_packer_create(C.byref(h), api.KIND_HZR, bps, nch, ns, 4, 0) == 0
     n, d = (C.c_double * 5)(*IIR_BANDPASS[0]), (C.c_double * 5)(*IIR_BANDPASS[1])

@@ -2,10 +2,10 @@
 """Time the carried-state rolling median (rspt_hip_median_filter_stream_dev) against the stateless stage of
 another build of the library -- the parent commit's -- and print one JSON line.
 
-The other build is loaded beside this one in the same process (--parent-lib: a librspt_hip.so built from the parent commit;
-only its packer_create / destroy and rspt_hip_median_filter_batch_dev are bound), so that both sides see the same buffers and
-their runs alternate: parent, branch, parent, branch, ...  Per side: the median ms per call over the runs and the spread (max -
-min).
+The other build is loaded beside this one in the same process (--parent-lib: a librspt_hip.so built from the parent commit,
+bound by api.bind; only its packer_create / destroy and rspt_hip_median_filter_batch_dev are called), so that both sides see the
+same buffers and their runs alternate: parent, branch, parent, branch, ...  Per side: the median ms per call over the runs and
+the spread (max - min).
 
   shape  64 ch x 4,194,304 rows of int32: 64 blocks of 64 ch x 65536 as ONE stream call on a state that has started, against
          the parent's stateless call on the same bytes as 64 blocks; out of place and in place; W = 3, 7, 31, 101, 1001, 8191,
@@ -39,12 +39,7 @@ class Parent:
     """the stateless median entry of another build"""
 
     def __init__(self, path):
-        L = self.L = C.CDLL(path)
-        L.rspt_hip_packer_create.restype = C.c_int
-        L.rspt_hip_packer_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
-        L.rspt_hip_packer_destroy.restype, L.rspt_hip_packer_destroy.argtypes = None, [C.c_void_p]
-        L.rspt_hip_median_filter_batch_dev.restype = C.c_int
-        L.rspt_hip_median_filter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        self.L = api.bind(C.CDLL(path), missing_ok=True)  # (a parent build lacks this build's newer entries)
 
     def packer(self, bps, nch, ns):
         h = C.c_void_p()

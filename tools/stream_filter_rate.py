@@ -2,10 +2,10 @@
 """Time the carried-state pre-filters (rspt_hip_fir_prefilter_stream_dev, rspt_hip_iir_prefilter_stream_dev)
 against the stateless stages of another build of the library -- the parent commit's -- and print one JSON line.
 
-The other build is loaded beside this one in the same process (--parent-lib: a librspt_hip.so built from the parent commit;
-only its packer_create / destroy and the two stateless entries are bound), so that both sides see the same buffers and their
-runs alternate: parent, branch, parent, branch, ...  Per side: the median ms per call over the runs and the spread (max -
-min).  `margin_ok`: the branch's median is not above the parent's by more than twice the parent's spread.
+The other build is loaded beside this one in the same process (--parent-lib: a librspt_hip.so built from the parent commit,
+bound by api.bind; only its packer_create / destroy and the two stateless entries are called), so that both sides see the same
+buffers and their runs alternate: parent, branch, parent, branch, ...  Per side: the median ms per call over the runs and the
+spread (max - min).  `margin_ok`: the branch's median is not above the parent's by more than twice the parent's spread.
 
   FIR   64 x (64 ch x 65536 int32), K in {1, 101, 1001}, in place and out of place: stream mode on a state that has started
         against the parent's stateless call on the same batch (the same multiply-add work, plus the K - 1 rows of the state)
@@ -42,14 +42,7 @@ class Parent:
     """the stateless entries of another build"""
 
     def __init__(self, path):
-        L = self.L = C.CDLL(path)
-        L.rspt_hip_packer_create.restype = C.c_int
-        L.rspt_hip_packer_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
-        L.rspt_hip_packer_destroy.restype, L.rspt_hip_packer_destroy.argtypes = None, [C.c_void_p]
-        L.rspt_hip_iir_prefilter_batch_dev.restype = C.c_int
-        L.rspt_hip_iir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, _dp, _dp, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
-        L.rspt_hip_fir_prefilter_batch_dev.restype = C.c_int
-        L.rspt_hip_fir_prefilter_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _dp, C.c_size_t, C.c_void_p]
+        self.L = api.bind(C.CDLL(path), missing_ok=True)  # (a parent build lacks this build's newer entries)
 
     def packer(self, bps, nch, ns):
         h = C.c_void_p()
