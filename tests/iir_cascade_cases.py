@@ -80,9 +80,9 @@ def cascade_cases():
 
 # ---- the restatement ----
 
-def chain_double(x, sections):
+def chain_double(x, sections, models=None):
     """x: [rows][lanes] float64, an independent chain per lane.  -> the last section's outputs before the truncation, and every
-    section's outputs ([S][rows][lanes])"""
+    section's outputs ([S][rows][lanes]).  models: a list that takes the S filter objects as they stand behind the last row"""
     rows, lanes = x.shape
     per = np.empty((len(sections), rows, lanes))
     with np.errstate(over="ignore", invalid="ignore"):
@@ -91,6 +91,8 @@ def chain_double(x, sections):
             f = IirModel(n, d, np.zeros(lanes))
             f.init_history(x[0], 4 * init)
             chain.append(f.filter if use_filter else f.filter_opt)
+            if models is not None:
+                models.append(f)
         for t in range(rows):
             v = x[t]
             for k, step in enumerate(chain):

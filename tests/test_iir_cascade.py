@@ -6,7 +6,12 @@ CPU: the record's inputs, the numpy restatement (tests/iir_cascade_cases.py) aga
 checks that need no device.
 GPU (-m gpu): every case bit-exact against the record and the restatement, stateless and as a stream however the recording is
 cut into calls, the equivalence of one section with the IIR pre-filter stage (states included), that the state is used, and
-the statuses."""
+the statuses.
+
+These are hand-picked cases, and their streams are cut at whole blocks in three patterns.  Every residue of a run's and of a
+call's length mod the pipelined kernel's chunk, every (order, producer part, place of the last sample), cuts at any row and the
+contents of the carried state are covered by the seeded sweep, tests/test_iir_sweep.py (legs cascade and cascade_stream of
+tests/iir_sweep_cases.py)."""
 import ctypes as C
 import functools
 import json

@@ -6,7 +6,11 @@ CPU: the record's inputs, the numpy restatement (tests/iir_zero_phase_cases.py) 
 stage, that the backward history counts, the C ABI, the device ISA of the new kernels, and the argument checks that need no
 device.
 GPU (-m gpu): every case bit-exact against the record and the restatement, base addresses off the sample width, a workspace full
-of 0xFF bytes, a repeated call, both kernels on the same data, and the statuses."""
+of 0xFF bytes, a repeated call, both kernels on the same data, and the statuses.
+
+These are hand-picked cases: their block lengths put the last sample into three of the pipelined kernel's four producer parts and
+take five of the 64 residues mod its chunk.  Every residue, every (order, part, place of the last sample) and every backward
+history with every order are covered by the seeded sweep, tests/test_iir_sweep.py (leg zero_phase of tests/iir_sweep_cases.py)."""
 import ctypes as C
 import functools
 import json
