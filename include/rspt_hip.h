@@ -233,6 +233,33 @@ int rspt_hip_compress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nb
 int rspt_hip_decompress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, void* d_dst,
                                   uint64_t* d_consumed, void* stream);
 
+/* ---- planar int32 in and out: samples that already live in a [nblocks][nch][ns] int32 matrix skip the native block ----
+ * d_planar is what rspt_hip_native_to_i32_batch_dev writes and rspt_hip_i32_to_native_batch_dev reads: block b's channel c at
+ * d_planar + (b*nch + c)*ns.  It must be 4-byte aligned; 16-byte aligned buffers take the widest accesses.  The contract is two
+ * identities with the entries above:
+ *
+ *   compress_planar(P)  ==  rspt_hip_compress_batch_dev(rspt_hip_i32_to_native_batch_dev(P))
+ *       the streams, d_sizes, the bit-63 "did not fit" flag, the per-block nb and the handle's nb state afterwards are the same,
+ *       for every sample packer and sample width.  Only the low bps bytes of each value count: they are cut and sign-extended
+ *       before anything else, whatever lies above the sample width changes nothing.  rspt_hip_set_byte_order has no effect
+ *       (there are no bytes to order).  d_planar is ONLY READ: the transform packers copy it into the workspace first.
+ *   decompress_planar(S)  ==  rspt_hip_native_to_i32_batch_dev(rspt_hip_decompress_batch_dev(S))  with a little-endian handle
+ *       every value sign-extended from bps bytes; d_consumed and its bit 63 are those of the native entry, a flagged stream is
+ *       never followed, rspt_hip_set_verify applies.  The packed form takes each stream's nb from its index entry, as
+ *       rspt_hip_decompress_packed_dev does, and checks the container the same way.
+ *
+ * Native and planar calls may alternate on one handle in any order: they share the nb state and the workspace, under the
+ * ordering contract of rspt_hip_compress_batch_dev.  Channel counts up to the create limit work on both sides (there is no
+ * native tile here).  RSPT_HIP_ERR_ARG for a NULL handle or pointer, nblocks == 0, a d_planar off its 4-byte alignment, a
+ * RSPT_HIP_KIND_BYTES handle or a handle with an open feed; everything rspt_hip_reserve refuses (more than 65535 blocks) is
+ * refused as there.  A refused call writes nothing.  The host-pointer forms (compress, _many, the feed) stay native-only. */
+int rspt_hip_compress_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, void* d_dst, size_t dst_stride,
+                                       uint64_t* d_sizes, void* stream);
+int rspt_hip_decompress_planar_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, int32_t* d_planar,
+                                         uint64_t* d_consumed, void* stream);
+int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, int32_t* d_planar,
+                                          uint64_t* d_consumed, void* stream);
+
 /* hzr_verify (hzr_decode.c:569-624) of nblocks libhzr streams resident in device memory, WITHOUT decoding them: the frame walk,
  * the mode byte of every block (<= 2) and the CRC-32C of every block's payload against its header.  Stream b starts at
  * d_src + b*src_stride and has d_src_len[b] bytes (a device array); nothing at or beyond d_src + b*src_stride + d_src_len[b] is read.

@@ -54,6 +54,9 @@ C_ABI = {
     "rspt_hip_reserve": (_i, [_p, _z]),
     "rspt_hip_compress_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_decompress_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
+    "rspt_hip_compress_planar_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
+    "rspt_hip_decompress_planar_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
+    "rspt_hip_decompress_packed_planar_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
     "rspt_hip_hzr_verify_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_pack_bound": (_z, [_p, _z]),
     "rspt_hip_pack_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p, _p]),
@@ -168,8 +171,9 @@ def _as_u8(buf):
 class SignalPacker:
     """One i_signal_packer instance on one GPU."""
 
-    def __init__(self, kind, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, nr_bytes_to_encode=3, device=0):
-        self._L = lib()
+    def __init__(self, kind, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, nr_bytes_to_encode=3, device=0, library=None):
+        """library: another loaded and bound build of librspt_hip.so to run this handle on (A/B timing beside lib(), tools/planar_bench.py)"""
+        self._L = library if library is not None else lib()
         kind_flags = KINDS[kind] if isinstance(kind, str) else int(kind)
         self.kind = kind_flags & 0xFF
         self.bps, self.nch, self.ns = bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel
@@ -352,35 +356,70 @@ class SignalPacker:
         return d_dst, d_sizes
 
     def decompress_batch(self, d_streams, nblocks, src_stride, d_out=None, d_consumed=None, stream=None):
-        import torch
-
-        if d_out is None:
-            d_out = torch.empty((nblocks, self.block_bytes), dtype=torch.uint8, device=d_streams.device)
-        if d_consumed is None:
-            d_consumed = torch.empty(nblocks, dtype=torch.int64, device=d_streams.device)
+        d_out, d_consumed = self._decode_buffers(nblocks, d_streams.device, d_out, d_consumed, False)
         st = self._stream(stream, d_streams.device)
         self._call("rspt_hip_decompress_batch_dev", d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
         return d_out, d_consumed
 
-    def decompress_packed(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None):
-        """Decompress every stream of a container (what pack_batch / the multi-GPU gather produce) on the device.
-        Each stream is decoded with the nb of its own index entry.  Reads the 32-byte header to the host for the block
-        count (a synchronisation).  `nbytes`: container length if shorter than the tensor."""
+    def _decode_buffers(self, nblocks, device, d_out, d_consumed, planar):
+        """(d_out, d_consumed) of a decompress call, allocated where None: the native batch (uint8 [nblocks, block_bytes]) or,
+        planar, the int32 matrix [nblocks, nch, ns]"""
         import torch
 
+        if d_out is None:
+            d_out = (torch.empty((nblocks, self.nch, self.ns), dtype=torch.int32, device=device) if planar
+                     else torch.empty((nblocks, self.block_bytes), dtype=torch.uint8, device=device))
+        if planar:
+            assert d_out.is_cuda and d_out.dtype == torch.int32 and d_out.is_contiguous() and d_out.numel() == nblocks * self.nch * self.ns
+        if d_consumed is None:
+            d_consumed = torch.empty(nblocks, dtype=torch.int64, device=device)
+        return d_out, d_consumed
+
+    def compress_planar_batch(self, d_planar, d_dst=None, d_sizes=None, dst_stride=None, stream=None):
+        """compress_batch for samples that already live in int32 (rspt_hip.h: rspt_hip_compress_planar_batch_dev): d_planar is a
+        torch.int32 cuda tensor [nblocks, nch, ns], only read; the streams are those of compress_batch(from_planar_i32(d_planar)).
+        Returns (d_dst, d_sizes); asynchronous."""
+        import torch
+
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        if dst_stride is None:
+            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
+        if d_dst is None:
+            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=d_planar.device)
+        if d_sizes is None:
+            d_sizes = torch.empty(nblocks, dtype=torch.int64, device=d_planar.device)
+        st = self._stream(stream, d_planar.device)
+        self._call("rspt_hip_compress_planar_batch_dev", d_planar.data_ptr(), nblocks, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
+        return d_dst, d_sizes
+
+    def decompress_planar_batch(self, d_streams, nblocks, src_stride, d_out=None, d_consumed=None, stream=None):
+        """decompress_batch into torch.int32 [nblocks, nch, ns] (rspt_hip.h: rspt_hip_decompress_planar_batch_dev): the values of
+        to_planar_i32(decompress_batch(...)) on a little-endian handle.  Returns (d_out, d_consumed); asynchronous."""
+        d_out, d_consumed = self._decode_buffers(nblocks, d_streams.device, d_out, d_consumed, True)
+        st = self._stream(stream, d_streams.device)
+        self._call("rspt_hip_decompress_planar_batch_dev", d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
+        return d_out, d_consumed
+
+    def decompress_packed_planar(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None):
+        """decompress_packed into torch.int32 [nblocks, nch, ns] (rspt_hip.h: rspt_hip_decompress_packed_planar_dev)."""
+        return self.decompress_packed(d_packed, d_out, d_consumed, stream, nbytes, planar=True)
+
+    def decompress_packed(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None, planar=False):
+        """Decompress every stream of a container (what pack_batch / the multi-GPU gather produce) on the device.
+        Each stream is decoded with the nb of its own index entry.  Reads the 32-byte header to the host for the block
+        count (a synchronisation).  `nbytes`: container length if shorter than the tensor.  planar: into an int32 matrix
+        (decompress_packed_planar)."""
+        entry = "rspt_hip_decompress_packed_planar_dev" if planar else "rspt_hip_decompress_packed_dev"
         head = d_packed[:32].cpu().numpy().view(np.uint64)
         if int(head[0]) != 0x4B43415054505352:
             raise ValueError("not an RSPTPACK container")
         nblocks = int(head[1])
         plen = int(nbytes) if nbytes is not None else d_packed.numel()
         if nblocks == 0 or nblocks > 65535 or plen < 32 or nblocks > (plen - 32) // 16:  # (nothing is sized from an untrusted count)
-            raise RsptHipError("rspt_hip_decompress_packed_dev", -6 if 0 < nblocks <= 65535 else -1)
-        if d_out is None:
-            d_out = torch.empty((nblocks, self.block_bytes), dtype=torch.uint8, device=d_packed.device)
-        if d_consumed is None:
-            d_consumed = torch.empty(nblocks, dtype=torch.int64, device=d_packed.device)
+            raise RsptHipError(entry, -6 if 0 < nblocks <= 65535 else -1)
+        d_out, d_consumed = self._decode_buffers(nblocks, d_packed.device, d_out, d_consumed, planar)
         st = self._stream(stream, d_packed.device)
-        self._call("rspt_hip_decompress_packed_dev", d_packed.data_ptr(), plen, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
+        self._call(entry, d_packed.data_ptr(), plen, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
         return d_out, d_consumed
 
     def hzr_verify_batch(self, d_streams, d_lengths, src_stride=None, d_decoded=None, stream=None):

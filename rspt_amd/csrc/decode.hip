@@ -947,10 +947,12 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, u
 
 // PASS 0: tile XOR totals.  PASS 1: tile sums of o+128 (needs XOR carries).
 // PASS 2: final values p -> planar.  XDELTA=false: p = v, single pass.
+// sx: the results leave sign-extended from 32 - sx bits (0: as they are; 32 - 8 * bps where `planar` is the caller's matrix of
+// rspt_hip_decompress_planar_batch_dev, which may sit at any 4-byte aligned address)
 template <int PASS, bool XDELTA>
 __global__ __launch_bounds__(256) void k_inv_tile(const uint8_t* __restrict__ planes, Geom g, const uint32_t* __restrict__ dec_nb,
                                                  uint32_t ntile, uint32_t* __restrict__ txor, uint32_t* __restrict__ tsum,
-                                                 int32_t* __restrict__ planar) {
+                                                 int32_t* __restrict__ planar, uint32_t sx) {
     __shared__ uint32_t s_w[4];
     const uint32_t tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const uint32_t nb = dec_nb[b];  // planes of THIS stream (k_dec_frame)
@@ -996,7 +998,9 @@ __global__ __launch_bounds__(256) void k_inv_tile(const uint8_t* __restrict__ pl
     // tiles go through LDS instead (rows of 17 words: conflict-free both ways) and leave as 1 KiB per wave-store.
     __shared__ uint32_t s_t[256 * 17];
     const uint32_t tile0 = tile * kInvTile;
-    const bool whole = tile0 + kInvTile <= g.N && (((size_t)b * g.N + tile0) & 3u) == 0;  // (block-uniform)
+    const bool whole = tile0 + kInvTile <= g.N && (reinterpret_cast<uintptr_t>(planar + (size_t)b * g.N + tile0) & 15u) == 0;  // (block-uniform)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) p[e] = (uint32_t)((int32_t)(p[e] << sx) >> sx);
     if (whole) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) s_t[tid * 17 + e] = p[e];

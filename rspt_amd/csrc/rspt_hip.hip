@@ -43,6 +43,7 @@
 #include "quality.hip"
 #include "convert.hip"
 #include "bytes.hip"
+#include "planar.hip"
 
 using namespace rspt;
 
@@ -197,6 +198,37 @@ static uint32_t launch_front(rspt_hip_packer* p, const uint8_t* d_src, size_t nb
     dim3 grid((g.ns + p->T - 1) / p->T, (unsigned)nblocks);
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_planar<BPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->in_lds);
     hipLaunchKernelGGL((k_tile_planar<BPS>), grid, dim3(256), p->in_lds, st, d_src, g, p->T, p->ws.planar);
+    return 4;
+}
+
+// the front end of the two hzr packers over a planar source (planar.hip): planes [kfirst, kfirst + kcount); nbuse: the fix-up pass
+template <bool XD>
+static void launch_planar_stream(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, uint32_t kfirst, uint32_t kcount, const uint32_t* nbuse,
+                                 hipStream_t st) {
+    const Geom& g = p->g;
+    const uint64_t units = (uint64_t)nblocks * ((g.N + 4095u) >> 12);
+    const uint64_t want = 8ull * (uint64_t)p->num_cu;  // eight 256-thread workgroups per CU
+    hipLaunchKernelGGL(k_planar_stream<XD>, dim3((uint32_t)(units < want ? units : want)), dim3(kPlanarThreads), 0, st, d_planar, g, kfirst, kcount, p->ws.planes,
+                       p->needmask, p->nzflag, nbuse, (uint32_t)nblocks, nbuse ? nullptr : p->work_ctr + 1, p->nb_state, p->ws.nbuse, p->ws.plane_dirty,
+                       p->dirty_shift);
+}
+
+// main front-end pass over a planar source (rspt_hip_compress_planar_batch_dev); returns the number of planes it wrote.  There is
+// no native tile here: a wide handle takes the same route as a narrow one.
+static uint32_t launch_front_planar(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, hipStream_t st) {
+    const Geom& g = p->g;
+    if (g.kind == RSPT_HIP_KIND_XDELTA_HZR) {
+        const uint32_t np = p->nb_host;
+        launch_planar_stream<true>(p, d_planar, nblocks, 0, np, nullptr, st);
+        return np;
+    }
+    if (g.kind == RSPT_HIP_KIND_HZR) {
+        launch_planar_stream<false>(p, d_planar, nblocks, 0, 4, nullptr, st);
+        return 4;
+    }
+    // the transform packers work in place on ws.planar: the caller's matrix is copied there, cut to the sample width
+    hipLaunchKernelGGL(k_planar_ingest, dim3((g.ns + 4095u) / 4096u, g.nch, (unsigned)nblocks), dim3(256), 0, st, d_planar, g, p->ws.planar, p->row_sum);
+    p->have_row_sum = p->row_sum != nullptr;
     return 4;
 }
 
@@ -619,7 +651,8 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
 // tree:   k_tree + k_layout                                                                       (latency chains, chip mostly idle; the
 //                                                                                                  small blocks are encoded under the dense trees)
 // encode: k_encode                                                                                (vector-issue bound)
-static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, hipStream_t st) {
+// d_planar: the source is a planar int32 matrix (rspt_hip_compress_planar_batch_dev) and src is not looked at
+static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, hipStream_t st, const int32_t* d_planar = nullptr) {
     const Geom& g = p->g;
     const uint32_t B = (uint32_t)nblocks;
     stamp(p, ST_PRE, st);
@@ -658,7 +691,8 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
         HIPCHK(p, hipGetLastError());
         return RSPT_HIP_OK;
     }
-    const uint32_t np = by_bps(g.bps, [&](auto bps) { return launch_front<decltype(bps)::value>(p, src, nblocks, st); });
+    const uint32_t np = d_planar ? launch_front_planar(p, d_planar, nblocks, st)
+                                 : by_bps(g.bps, [&](auto bps) { return launch_front<decltype(bps)::value>(p, src, nblocks, st); });
     if (g.kind == RSPT_HIP_KIND_HADAMARD) {
         // per channel: mean removal, WHT, truncating /n (signal_packer_hadamard.cpp:57-72)
         const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
@@ -692,8 +726,12 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
     stamp(p, ST_NB, st);
     if (g.kind != RSPT_HIP_KIND_XDELTA_HZR && g.kind != RSPT_HIP_KIND_HZR)  // (k_tile_planes runs the scan in its last workgroup)
         hipLaunchKernelGGL(k_nb_scan, dim3(1), dim3(1024), 0, st, p->needmask, B, p->nb_state, p->ws.nbuse, 0);
-    if (xd && np < 4)  // nb may have escalated in this call: add the planes the main pass did not write
-        by_bps(g.bps, [&](auto bps) { launch_fixup<decltype(bps)::value>(p, src, nblocks, np, st); });
+    if (xd && np < 4) {  // nb may have escalated in this call: add the planes the main pass did not write
+        if (d_planar)
+            launch_planar_stream<true>(p, d_planar, nblocks, np, 4 - np, p->ws.nbuse, st);
+        else
+            by_bps(g.bps, [&](auto bps) { launch_fixup<decltype(bps)::value>(p, src, nblocks, np, st); });
+    }
     stamp(p, ST_HIST, st);
     // (the list of k_hist's blocks sits in big_list until k_layout refills that array for k_encode; its count in work_ctr[2])
     const uint32_t nhb = B * kMaxPlanes * g.nblk;
@@ -746,12 +784,13 @@ static int phase_encode(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_
 }
 
 // one batch, start to end on one stream
-static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t nblocks, void* d_dst, size_t dst_stride, uint64_t* d_sizes, hipStream_t st) {
+static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t nblocks, void* d_dst, size_t dst_stride, uint64_t* d_sizes, hipStream_t st,
+                                 const int32_t* d_planar = nullptr) {
     int rc = rspt_hip_reserve(p, nblocks);
     if (rc) return rc;
     HIPCHK(p, hipSetDevice(p->device));
     const uint32_t B = (uint32_t)slots_of(p, nblocks);  // what the hzr kernels count in
-    if ((rc = phase_front(p, (const uint8_t*)d_src, nblocks, st)) != 0) return rc;
+    if ((rc = phase_front(p, (const uint8_t*)d_src, nblocks, st, d_planar)) != 0) return rc;
     if ((rc = phase_hist(p, B, st)) != 0) return rc;
 
     stamp(p, ST_TREE, st);
@@ -789,6 +828,15 @@ int rspt_hip_compress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nb
     if (reinterpret_cast<uintptr_t>(d_src) & 15) return RSPT_HIP_ERR_ARG;  // tile loads are 16-byte aligned chunks
     if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
     return compress_batch_serial(p, d_src, nblocks, d_dst, dst_stride, d_sizes, (hipStream_t)stream);
+}
+
+int rspt_hip_compress_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, void* d_dst, size_t dst_stride, uint64_t* d_sizes,
+                                       void* stream) {
+    if (!p || !d_planar || !d_dst || !d_sizes || nblocks == 0) return RSPT_HIP_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_planar) & 3) return RSPT_HIP_ERR_ARG;
+    if (p->g.kind == RSPT_HIP_KIND_BYTES) return RSPT_HIP_ERR_ARG;  // (a byte buffer has no samples)
+    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
+    return compress_batch_serial(p, nullptr, nblocks, d_dst, dst_stride, d_sizes, (hipStream_t)stream, d_planar);
 }
 
 size_t rspt_hip_pack_bound(const rspt_hip_packer* p, size_t nblocks) {
@@ -933,8 +981,9 @@ int rspt_hip_compress(rspt_hip_packer* p, const void* src_host, void* dst_host, 
     return RSPT_HIP_OK;
 }
 
+// to_planar: d_dst is the caller's planar int32 matrix (rspt_hip_decompress_planar_batch_dev), not the native batch
 static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* pidx, size_t packed_len, size_t nblocks,
-                          void* d_dst, uint64_t* d_consumed, void* stream);
+                          void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar = false);
 
 int rspt_hip_decompress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, void* d_dst, uint64_t* d_consumed,
                                   void* stream) {
@@ -953,8 +1002,30 @@ int rspt_hip_decompress_packed_dev(rspt_hip_packer* p, const void* d_packed, siz
                           stream);
 }
 
+// what both planar decompress entries refuse in front of decompress_dev's own checks
+static bool planar_out_refused(const rspt_hip_packer* p, const int32_t* d_planar) {
+    return !p || !d_planar || (reinterpret_cast<uintptr_t>(d_planar) & 3) || p->g.kind == RSPT_HIP_KIND_BYTES;
+}
+
+int rspt_hip_decompress_planar_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, int32_t* d_planar,
+                                         uint64_t* d_consumed, void* stream) {
+    if (planar_out_refused(p, d_planar)) return RSPT_HIP_ERR_ARG;
+    return decompress_dev(p, d_src, src_stride, nullptr, 0, nblocks, d_planar, d_consumed, stream, true);
+}
+
+int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, int32_t* d_planar,
+                                          uint64_t* d_consumed, void* stream) {
+    if (planar_out_refused(p, d_planar)) return RSPT_HIP_ERR_ARG;
+    if (!d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 15)) return RSPT_HIP_ERR_ARG;
+    if (nblocks == 0 || nblocks > 65535) return RSPT_HIP_ERR_ARG;
+    if (packed_len < 32 || nblocks > (packed_len - 32) / 16) return RSPT_HIP_ERR_CORRUPT;
+    const uint8_t* base = (const uint8_t*)d_packed;
+    return decompress_dev(p, base + 32 + 16 * nblocks, 0, reinterpret_cast<const uint64_t*>(base + 32), packed_len, nblocks, d_planar, d_consumed,
+                          stream, true);
+}
+
 static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* pidx, size_t packed_len, size_t nblocks,
-                          void* d_dst, uint64_t* d_consumed, void* stream) {
+                          void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar) {
     if (!p || !d_src || !d_dst || !d_consumed || nblocks == 0) return RSPT_HIP_ERR_ARG;
     if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the plane workspace until rspt_hip_feed_end)
     int rc = rspt_hip_reserve(p, nblocks);
@@ -989,8 +1060,11 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
         const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_DCT;
         const dim3 tg(p->ntile, B);
         // int32 samples of the two hzr packers: the last inverse pass writes the interleaved block itself (k_inv_native)
-        const bool direct = (g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_HZR) && g.bps == 4 && (g.nch & 3) == 0 &&
-                            g.ns % kRowTile == 0 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0;
+        const bool lossless = g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_HZR;
+        const bool direct = lossless && !to_planar && g.bps == 4 && (g.nch & 3) == 0 && g.ns % kRowTile == 0 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0;
+        // planar out, lossless packers: the last inverse pass writes the caller's matrix itself, sign-extended from the sample width
+        int32_t* inv_out = lossless && to_planar ? (int32_t*)d_dst : (int32_t*)p->ws.planar;
+        const uint32_t inv_sx = lossless && to_planar ? 32u - 8u * g.bps : 0u;
         if (direct) {
             const uint32_t nrow = g.N / kRowTile;
             const dim3 rg((g.N / 16 + 255) / 256, B);
@@ -1014,13 +1088,13 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
             return RSPT_HIP_OK;
         }
         if (xd) {
-            hipLaunchKernelGGL((k_inv_tile<0, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
+            hipLaunchKernelGGL((k_inv_tile<0, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar, 0u);
             hipLaunchKernelGGL((k_inv_scan_tiles<true>), dim3(B), dim3(1024), 0, st, p->ws.txor, p->ntile);
-            hipLaunchKernelGGL((k_inv_tile<1, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
+            hipLaunchKernelGGL((k_inv_tile<1, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar, 0u);
             hipLaunchKernelGGL((k_inv_scan_tiles<false>), dim3(B), dim3(1024), 0, st, p->ws.tsum, p->ntile);
-            hipLaunchKernelGGL((k_inv_tile<2, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
+            hipLaunchKernelGGL((k_inv_tile<2, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, inv_out, inv_sx);
         } else {
-            hipLaunchKernelGGL((k_inv_tile<2, false>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar);
+            hipLaunchKernelGGL((k_inv_tile<2, false>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, inv_out, inv_sx);
         }
         const int32_t* final_planar = p->ws.planar;
         if (g.kind == RSPT_HIP_KIND_HADAMARD) {
@@ -1042,6 +1116,14 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
                 hipLaunchKernelGGL((k_dct<false>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g,
                                    p->ws.means, p->cos_tab_t, 0.0, p->idct_scale, p->dct_cs0, p->ws.planar2);
             final_planar = p->ws.planar2;
+        }
+        if (to_planar) {
+            if (!lossless) {  // the transform packers: the inverse transform's output, cut to the sample width as the native back ends cut it
+                const uint64_t wgs = ((uint64_t)B * g.N + 255) / 256, want = 16ull * (uint64_t)p->num_cu;
+                hipLaunchKernelGGL(k_planar_emit, dim3((uint32_t)(wgs < want ? wgs : want)), dim3(256), 0, st, final_planar, g, B, (int32_t*)d_dst);
+            }
+            HIPCHK(p, hipGetLastError());
+            return RSPT_HIP_OK;
         }
         const uint32_t T = min(p->Tn_native, g.ns);
         const uint32_t lds = g.nch * (T + 1) * 4;
