@@ -586,36 +586,67 @@ __device__ __forceinline__ void rotate_rows(uint32_t (&W)[4][4], RowCtx (&rc)[4]
 }
 
 // A wave whose four rows are all sparse (the segments of the "medium" blocks: every 4 KiB non-zero, a few literals per row)
-// takes them as ONE queue: two packed scans instead of four, one pass over the entries instead of one per row, and the
-// queue is the segment's entry list as it stands.  Between sparse rows nothing special happens at a row boundary: the zeros
-// in front of a row's first literal are the gap to the entry before it, whichever row that one came from; only entry 0
-// looks outside the segment (rc[0].zb0).  False: too many entries for the queue -- the caller goes row by row.
+// takes them as ONE queue, and the queue is the segment's entry list as it stands.  Between sparse rows nothing special
+// happens at a row boundary: the zeros in front of a row's first literal are the gap to the entry before it, whichever row
+// that one came from; only entry 0 looks outside the segment (rc[0].zb0).
+//
+// Such a segment rarely holds more than 64 granules that are not all zero (planes 1-2 of the xdelta planes: 16 to 32 of 256 on
+// average, tools/sparse_census.py), so those granules are first compacted into ONE row, in position order: a lane that holds
+// one hands its four words and its block position to lane (granules of the rows before) + (granules of lower lanes of its
+// row), through the wave's own queue words -- five columns of 64 words, read back before the first entry is written there.
+// One lane_lits, one scan and one entry loop then do what took four of each, with most lanes idle in every one of them.
+// Zero granules between compacted neighbours are the position gap, as they are between rows.  False: more than 64 such
+// granules, or too many entries for the queue -- the caller goes row by row (the same entries in the same order; keeping the
+// four-row body beside the compacted one for the first case cost k_hist 16 bytes of scratch).  W is never written here.
+constexpr uint32_t kCompactWords = 5u * 64u;  // the compaction's columns: w0..w3 and the position
+static_assert(kCompactWords <= kQueueEntries, "the compaction's scratch stays inside the wave's own queue slot (k_hist's and k_encode's own-count queues alike)");
+
 __device__ __forceinline__ bool hist_segment_sparse(const uint32_t (&W)[4][4], const RowCtx (&rc)[4], uint32_t in_size, uint32_t* h,
                                                     const uint32_t* runcls, uint32_t* queue, ListSink& sink) {
     const uint32_t l = lane_id();
-    uint32_t lits[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) lits[r] = lane_lits(W[r]);  // (bytes behind the block end were masked to zero at the load)
-    const uint32_t n01 = (uint32_t)__popc(lits[0]) | ((uint32_t)__popc(lits[1]) << 16);
-    const uint32_t n23 = (uint32_t)__popc(lits[2]) | ((uint32_t)__popc(lits[3]) << 16);
-    const uint32_t inc01 = wave_scan_add(n01), inc23 = wave_scan_add(n23);
-    const uint32_t tot01 = read_lane(inc01, 63), tot23 = read_lane(inc23, 63);
     const uint32_t last = rc[0].last | rc[1].last | rc[2].last | rc[3].last;  // the block ends in this segment: the run that reaches its end
-    const uint32_t S1 = tot01 & 0xFFFFu, S2 = S1 + (tot01 >> 16), S3 = S2 + (tot23 & 0xFFFFu);
-    const uint32_t T = S3 + (tot23 >> 16) + (last ? 1u : 0u);
-    if (T > kQueueEntries) return false;
-    if (T == 0) return true;  // nothing but zeros, and the block goes on
-    const uint32_t ex01 = inc01 - n01, ex23 = inc23 - n23;
+    unsigned long long nzg[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) nzg[r] = __ballot((W[r][0] | W[r][1] | W[r][2] | W[r][3]) != 0u);  // (bytes behind the block end were masked to zero at the load)
+    const uint32_t g1 = (uint32_t)__popcll(nzg[0]), g2 = g1 + (uint32_t)__popcll(nzg[1]), g3 = g2 + (uint32_t)__popcll(nzg[2]);
+    const uint32_t ng = g3 + (uint32_t)__popcll(nzg[3]);
+    if (ng > 64u) return false;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        uint32_t k = (r == 0 ? 0u : r == 1 ? S1 : r == 2 ? S2 : S3) + (((r < 2 ? ex01 : ex23) >> ((r & 1) * 16)) & 0xFFFFu);
-        uint32_t t = lits[r];
-        const uint32_t pos0 = rc[r].rb + 16u * l;
-        while (t) {
-            const uint32_t i = (uint32_t)__builtin_ctz(t);
-            t &= t - 1;
-            queue[k++] = ((pos0 + i) << 9) | granule_byte_dyn(W[r][0], W[r][1], W[r][2], W[r][3], i);
+        if ((W[r][0] | W[r][1] | W[r][2] | W[r][3]) != 0u) {
+            const uint32_t s = (r == 0 ? 0u : r == 1 ? g1 : r == 2 ? g2 : g3) +
+                               __builtin_amdgcn_mbcnt_hi((uint32_t)(nzg[r] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nzg[r], 0u));
+            queue[s] = W[r][0];
+            queue[64u + s] = W[r][1];
+            queue[128u + s] = W[r][2];
+            queue[192u + s] = W[r][3];
+            queue[256u + s] = rc[r].rb + 16u * l;
         }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    uint32_t cg[4] = {0u, 0u, 0u, 0u};
+    uint32_t pos0 = 0;
+    if (l < ng) {
+        cg[0] = queue[l];
+        cg[1] = queue[64u + l];
+        cg[2] = queue[128u + l];
+        cg[3] = queue[192u + l];
+        pos0 = queue[256u + l];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();  // every lane holds its granule: the entries may take the same words
+    uint32_t t = lane_lits(cg);
+    const uint32_t n = (uint32_t)__popc(t);
+    const uint32_t inc = wave_scan_add(n);
+    const uint32_t T = read_lane(inc, 63) + (last ? 1u : 0u);
+    if (T > kQueueEntries) return false;
+    if (T == 0) return true;  // nothing but zeros, and the block goes on
+    uint32_t k = inc - n;
+    while (t) {
+        const uint32_t i = (uint32_t)__builtin_ctz(t);
+        t &= t - 1;
+        queue[k++] = ((pos0 + i) << 9) | granule_byte_dyn(cg[0], cg[1], cg[2], cg[3], i);
     }
     if (last && l == 0) queue[T - 1u] = (in_size << 9) | kNoLit;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
