@@ -430,6 +430,42 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
                                     const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state,
                                     void* stream);
 
+/* ---- the IIR pre-filter and the IIR cascade on the planar int32 matrix: the reference's own filter step ---------------
+ * The reference filters samples where they live as int32: convert_native_to_i32 into a [nch][ns] matrix,
+ * enc.d2d[j][i] = filter->filter_opt(enc.d2d[j][i]) on that matrix, convert_i32_to_native, the packer
+ * (lib_rspt_test/rspt_test.cpp:116-136).  These four entries are that middle step for a caller whose samples are in the
+ * converters' matrix, so that native_to_i32 -> IIR -> compress_planar runs without leaving it.  Arguments, arithmetic, driving
+ * modes, routes and state are those of the native siblings above (rspt_hip_iir_prefilter_batch_dev / _stream_dev,
+ * rspt_hip_iir_cascade_batch_dev / _stream_dev) with int32_t* d_planar in place of void* d_buf:
+ *   d_planar   the matrix of rspt_hip_native_to_i32_batch_dev, block b's channel c at d_planar + (b*nch + c)*ns, filtered IN
+ *              PLACE; it needs 4-byte alignment only.
+ *   samples    the WHOLE int32 value is the sample, as in the reference's matrix loop: the handle's bps and byte order have no
+ *              effect.  The result is (int32_t)y as x86-64 truncates (every NaN, +-inf and |y| >= 2^31 -> INT32_MIN), stored
+ *              whole and NOT cut to bps.  So  i32_to_native(iir_planar(native_to_i32(X))) == iir_native(X)  for every bps, and
+ *              compress_planar(iir_planar(native_to_i32(X))) gives the streams of compress(iir_native(X)), because
+ *              compress_planar cuts as rspt_hip_i32_to_native_batch_dev does.
+ *   modes      per_channel = 0: one object per block, running on from channel to channel (the harness); 1: a fresh object per
+ *              (block, channel).  The cascade is per channel only.
+ *   stream     the blocks of a call are consecutive pieces of one recording: channel c's run is P[0][c][:], P[1][c][:], ...
+ *              d_state has the native entries' layout and size (rspt_hip_iir_state_bytes, rspt_hip_iir_cascade_state_bytes);
+ *              all-zero bytes are a fresh object.  Native and planar calls may alternate on one state, exactly where the native
+ *              samples are int32 (a narrower native call cuts what it stores, the rings run on uncut either way); with one
+ *              section a state may move between the single and the cascade entries, as for the native ones.
+ * Refused as the native sibling refuses it: RSPT_HIP_ERR_ARG for NULL pointers, nblocks = 0, nblocks * nch >= 2^31, an order
+ * outside 2..5, init_nr_samples outside 0 .. 2^28, nsections outside 1..4, a NULL or misaligned d_state -- and for a d_planar
+ * off its 4-byte alignment; RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels, before anything is launched, and for a stream
+ * call of 2^31 - 2^17 rows or more.  A refused call writes nothing.  Asynchronous on `stream`; the entries allocate nothing.
+ * Only these two stages have a planar form: the zero-phase IIR, FIR, median, peak and PRDN stages stay native-only. */
+int rspt_hip_iir_prefilter_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
+                                            size_t nr_coefficients, int init_nr_samples, int per_channel, void* stream);
+int rspt_hip_iir_prefilter_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
+                                             size_t nr_coefficients, int init_nr_samples, void* d_state, void* stream);
+int rspt_hip_iir_cascade_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                          const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* stream);
+int rspt_hip_iir_cascade_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                           const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state,
+                                           void* stream);
+
 /* ---- a zero-phase (forward-backward) IIR filter: one reference object run forward, then backward over its own output ----
  * The reference's offline user runs a filter forward and then backward over the same object (peak_detector_offline::detect,
  * peak_detector.h:309-328), which takes the delay and the phase distortion of a forward pass out again ("filtfilt").  Two calls of

@@ -73,6 +73,10 @@ C_ABI = {
     "rspt_hip_iir_cascade_batch_dev": (_i, _casc + [_p]),
     "rspt_hip_iir_cascade_state_bytes": (_i, [_p, _z, _szp]),
     "rspt_hip_iir_cascade_stream_dev": (_i, _casc + [_p, _p]),
+    "rspt_hip_iir_prefilter_planar_batch_dev": (_i, [_p, _p, _z, _dp, _dp, _z, _i, _i, _p]),
+    "rspt_hip_iir_prefilter_planar_stream_dev": (_i, [_p, _p, _z, _dp, _dp, _z, _i, _p, _p]),
+    "rspt_hip_iir_cascade_planar_batch_dev": (_i, _casc + [_p]),
+    "rspt_hip_iir_cascade_planar_stream_dev": (_i, _casc + [_p, _p]),
     "rspt_hip_iir_zero_phase_work_bytes": (_i, [_p, _z, _szp]),
     "rspt_hip_iir_zero_phase_batch_dev": (_i, [_p, _p, _z, _dp, _dp, _z, _i, _i, _p, _z, _p]),
     "rspt_hip_fir_prefilter_batch_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p]),
@@ -474,18 +478,30 @@ class SignalPacker:
         """The reference's pre-filter step (rspt_test.cpp:116-136) on device-resident blocks, in place; asynchronous.
         state: None, or an iir_state() tensor: the blocks are then consecutive pieces of one recording, one filter per channel
         running through them and on into the next call (rspt_hip_iir_prefilter_stream_dev); needs per_channel=True."""
-        nblocks = self._nblocks(d_buf)
+        return self._iir_prefilter("", d_buf, self._nblocks(d_buf), n, d, init_nr_samples, per_channel, stream, state)
+
+    def iir_prefilter_planar_batch(self, d_planar, n, d, init_nr_samples=2000, per_channel=False, stream=None, state=None):
+        """iir_prefilter_batch on samples that live in int32 (rspt_hip.h: rspt_hip_iir_prefilter_planar_batch_dev / _stream_dev):
+        d_planar is a torch.int32 cuda tensor [nblocks, nch, ns], filtered in place; the whole int32 value is the sample and the
+        result is stored whole, whatever the handle's bps.  n, d, init_nr_samples, per_channel and state as in iir_prefilter_batch."""
+        import torch
+
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        return self._iir_prefilter("planar_", d_planar, nblocks, n, d, init_nr_samples, per_channel, stream, state)
+
+    def _iir_prefilter(self, form, d_buf, nblocks, n, d, init_nr_samples, per_channel, stream, state):
+        """both layouts of the IIR pre-filter: form "" (native blocks) or "planar_" (the int32 matrix)"""
         nn, dd = np.ascontiguousarray(n, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
         assert nn.size == dd.size
         st = self._stream(stream, d_buf.device)
         args = (d_buf.data_ptr(), nblocks, _dptr(nn), _dptr(dd), nn.size, init_nr_samples)
         if state is not None:
             if not per_channel:
-                raise ValueError("iir_prefilter_batch: a carried state is one filter per channel (per_channel=True)")
+                raise ValueError("iir_prefilter_%sbatch: a carried state is one filter per channel (per_channel=True)" % form)
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.iir_state_bytes()
-            self._call("rspt_hip_iir_prefilter_stream_dev", *args, state.data_ptr(), st)
+            self._call("rspt_hip_iir_prefilter_%sstream_dev" % form, *args, state.data_ptr(), st)
         else:
-            self._call("rspt_hip_iir_prefilter_batch_dev", *args, int(bool(per_channel)), st)
+            self._call("rspt_hip_iir_prefilter_%sbatch_dev" % form, *args, int(bool(per_channel)), st)
         return d_buf
 
     def iir_cascade_state_bytes(self, nsections):
@@ -502,16 +518,28 @@ class SignalPacker:
         2000, use_filter (the section runs filter() instead of filter_opt()) to False.
         state: None (a fresh chain per block and channel), or an iir_cascade_state(len(sections)) tensor: the blocks are then
         consecutive pieces of one recording, one chain per channel running through them and on into the next call."""
-        nblocks = self._nblocks(d_buf)
+        return self._iir_cascade("", d_buf, self._nblocks(d_buf), sections, stream, state)
+
+    def iir_cascade_planar_batch(self, d_planar, sections, stream=None, state=None):
+        """iir_cascade_batch on samples that live in int32 (rspt_hip.h: rspt_hip_iir_cascade_planar_batch_dev / _stream_dev):
+        d_planar is a torch.int32 cuda tensor [nblocks, nch, ns], filtered in place; the whole int32 value is the sample and the
+        result is stored whole, whatever the handle's bps.  sections and state as in iir_cascade_batch."""
+        import torch
+
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        return self._iir_cascade("planar_", d_planar, nblocks, sections, stream, state)
+
+    def _iir_cascade(self, form, d_buf, nblocks, sections, stream, state):
+        """both layouts of the cascade: form "" (native blocks) or "planar_" (the int32 matrix)"""
         S = len(sections)
         if not 1 <= S <= 4:
-            raise ValueError("iir_cascade_batch: 1 to 4 sections")
+            raise ValueError("iir_cascade_%sbatch: 1 to 4 sections" % form)
         nn, dd = np.zeros((S, 5)), np.zeros((S, 5))
         nc, init, filt = np.zeros(S, dtype=np.uint32), np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.uint8)
         for k, sec in enumerate(sections):
             n, d = np.asarray(sec[0], dtype=np.float64).reshape(-1), np.asarray(sec[1], dtype=np.float64).reshape(-1)
             if n.size != d.size or not 2 <= n.size <= 5:
-                raise ValueError("iir_cascade_batch: section %d needs 2 to 5 coefficients on each side" % k)
+                raise ValueError("iir_cascade_%sbatch: section %d needs 2 to 5 coefficients on each side" % (form, k))
             nn[k, : n.size], dd[k, : d.size] = n, d
             nc[k], init[k], filt[k] = n.size, (sec[2] if len(sec) > 2 else 2000), bool(sec[3]) if len(sec) > 3 else False
         st = self._stream(stream, d_buf.device)
@@ -519,9 +547,9 @@ class SignalPacker:
                 nc.ctypes.data_as(C.POINTER(C.c_uint32)), init.ctypes.data_as(C.POINTER(C.c_int32)), filt.ctypes.data_as(_u8p))
         if state is not None:
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.iir_cascade_state_bytes(S)
-            self._call("rspt_hip_iir_cascade_stream_dev", *args, state.data_ptr(), st)
+            self._call("rspt_hip_iir_cascade_%sstream_dev" % form, *args, state.data_ptr(), st)
         else:
-            self._call("rspt_hip_iir_cascade_batch_dev", *args, st)
+            self._call("rspt_hip_iir_cascade_%sbatch_dev" % form, *args, st)
         return d_buf
 
     def iir_zero_phase_work_bytes(self, nblocks):

@@ -20,6 +20,101 @@
 
 namespace rspt {
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The planar form (rspt_hip_iir_*_planar_*_dev): the samples are the whole int32 values of the converters' matrix
+// [nblocks][nch][ns], filtered in place and stored whole.  Only where a sample of a run lives is new: the kernels below and
+// those of iir_cascade.hip take it as a flag PLANAR (BPS = 4, aligned), and the filter, the ticks and the routes are the native
+// ones.  The bodies of the three larger kernels are files of their own (k_iir_pipe_body.hpp, k_iir_cascade_body.hpp,
+// k_iir_cascade_pipe_body.hpp), included once into the native kernel and once into its planar form, with every planar statement
+// under `if constexpr (PLANAR)`: the native instantiations keep their names and are compiled from the statements they had.
+// A run is channel ch's row of one block (stateless), or its rows in the call's consecutive blocks (carried).
+// A neighbouring channel's row is adjacent in memory and another lane or workgroup is filtering it, so nothing here stores
+// past the end of a row, and a clamped load clamps the sample's INDEX in the run, never an address.
+struct PlanarRun {
+    int32_t* row;   // the run's first sample: the channel's row in the run's first block
+    uint32_t hns;   // samples of a row
+    size_t bstep;   // elements from a row to the same channel's row in the next block: nch * hns
+    // sample s of the run sits at (s / hns) * nch * hns + ch * hns + s % hns of the matrix
+    __device__ __forceinline__ int32_t* at(uint32_t s) const {
+        const uint32_t b = s / hns;
+        return row + (size_t)b * bstep + (s - b * hns);
+    }
+    // samples s .. s + n - 1 where they lie in one row, else nullptr (wave-uniform: s, n and hns are)
+    __device__ __forceinline__ int32_t* span(uint32_t s, uint32_t n) const {
+        const uint32_t b = s / hns, r = s - b * hns;
+        return r + n <= hns ? row + (size_t)b * bstep + r : nullptr;
+    }
+};
+// The run whose first sample is p.  block_bytes is one [nch][hns] block of the matrix; stateless (ONE_ROW) the run is one row of
+// ns samples, carried it is ns rows through ns / hns consecutive blocks.  (nch * hns < 2^31, rspt_hip_packer_create: a 32-bit
+// division, whose expansion holds no fused multiply-add as a 64-bit one's does.)
+template <bool ONE_ROW>
+__device__ __forceinline__ PlanarRun planar_run(uint8_t* p, uint32_t nch, uint32_t ns, uint64_t block_bytes) {
+    const uint32_t hns = ONE_ROW ? ns : (uint32_t)(block_bytes >> 2) / nch;
+    return PlanarRun{reinterpret_cast<int32_t*>(p), hns, (size_t)nch * hns};
+}
+
+// A producer's set of a run of ns samples: the H samples in front of its part and its 16-sample part, from sample s0 on.  A
+// set inside the run and inside one row takes the H in front as dwords and the part -- 64 contiguous bytes -- as four 16-byte
+// loads, which need the 4-byte alignment of an int32 only (as k_planar_stream's do).  A set at an end of the run (its indices
+// clamped into the run: what lies outside is never used as such) or across a block boundary goes dword by dword.
+// ONE_ROW: the run is one row (the stateless forms), no set straddles.
+template <uint32_t H, bool ONE_ROW>
+__device__ __forceinline__ void planar_load_set(const PlanarRun& run, uint32_t ns, int32_t s0, int32_t (&v)[16 + H]) {
+    const int32_t* q = nullptr;
+    if (s0 >= 0 && s0 + (int32_t)(16 + H) <= (int32_t)ns) q = ONE_ROW ? run.row + s0 : run.span((uint32_t)s0, 16 + H);
+    if (q) {  // (wave-uniform)
+#pragma unroll
+        for (uint32_t j = 0; j < H; ++j) v[j] = q[j];
+        __builtin_memcpy(&v[H], q + H, 64);
+    } else if constexpr (ONE_ROW) {
+#pragma unroll
+        for (uint32_t j = 0; j < 16 + H; ++j) {
+            const int32_t si = s0 + (int32_t)j;
+            v[j] = run.row[si < 0 ? 0 : si >= (int32_t)ns ? (int32_t)ns - 1 : si];
+        }
+    } else {
+        // (one division for the set: the place of its first sample, and from there on step by step)
+        const int32_t first = s0 < 0 ? 0 : s0 >= (int32_t)ns ? (int32_t)ns - 1 : s0;
+        uint32_t b = (uint32_t)first / run.hns, r = (uint32_t)first - b * run.hns;
+#pragma unroll
+        for (uint32_t j = 0; j < 16 + H; ++j) {
+            v[j] = run.row[(size_t)b * run.bstep + r];
+            const int32_t si = s0 + (int32_t)j;
+            if (si >= 0 && si + 1 < (int32_t)ns && ++r == run.hns) {  // (the next element is the next sample; its row may be the next block's)
+                r = 0;
+                ++b;
+            }
+        }
+    }
+}
+
+// The first n <= 16 of a writer's 16 results, from sample s of the run on: a whole part inside one row as four 16-byte stores,
+// else dword by dword -- never a byte past sample s + n - 1, which may be the row's last.
+template <bool ONE_ROW>
+__device__ __forceinline__ void planar_store_part(const PlanarRun& run, uint32_t s, uint32_t n, const int32_t (&v)[16], bool valid) {
+    int32_t* q = nullptr;
+    if (n == 16u) q = ONE_ROW ? run.row + s : run.span(s, 16u);
+    if (!valid) return;
+    if (q) {  // (wave-uniform)
+        __builtin_memcpy(q, &v[0], 64);
+    } else if constexpr (ONE_ROW) {
+#pragma unroll
+        for (uint32_t e = 0; e < 16; ++e)
+            if (e < n) run.row[s + e] = v[e];
+    } else {
+        uint32_t b = s / run.hns, r = s - b * run.hns;
+#pragma unroll
+        for (uint32_t e = 0; e < 16; ++e) {
+            if (e < n) run.row[(size_t)b * run.bstep + r] = v[e];
+            if (++r == run.hns) {
+                r = 0;
+                ++b;
+            }
+        }
+    }
+}
+
 // One channel: history initialisation with its first sample, then every sample in place through filter_opt, whose
 // feed-forward sum has no output in it (IirState::step_opt).  Samples are handled in chunks of CH: the next
 // chunk's loads are in flight while this one is filtered, the feed-forward sums of the chunk are independent work the
@@ -107,6 +202,43 @@ __global__ __launch_bounds__(64) void k_iir_carry(uint8_t* __restrict__ buf, uin
     s.started = 1;
 }
 
+// k_iir on the planar matrix: the two steps change places -- a channel's samples lie side by side, the channels' rows ns samples
+// apart, the blocks nch * ns.
+template <int NC, bool SHARED>
+__global__ __launch_bounds__(64) void k_iir_planar(int32_t* __restrict__ buf, uint32_t nch, uint32_t ns, IirCoef c, uint32_t nblocks) {
+    const uint32_t t = blockIdx.x * 64u + threadIdx.x;
+    IirState<NC> f;
+    f.clear();
+    if (SHARED) {  // one filter object for all channels of the block, as in the harness
+        if (t >= nblocks) return;
+        for (uint32_t ch = 0; ch < nch; ++ch) iir_channel<4, NC>(reinterpret_cast<uint8_t*>(buf + ((size_t)t * nch + ch) * ns), 4, ns, c, f, true);
+    } else {
+        if (t / nch >= nblocks) return;
+        iir_channel<4, NC>(reinterpret_cast<uint8_t*>(buf + (size_t)t * ns), 4, ns, c, f, true);
+    }
+}
+
+// k_iir_carry on the planar matrix: the run is the channel's row in each of the call's nblocks blocks in turn, ns samples each.
+// (It takes the block count, which k_iir_carry's arguments have no place for.)
+template <int NC>
+__global__ __launch_bounds__(64) void k_iir_planar_carry(int32_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint32_t nblocks, IirCoef c,
+                                                         IirCarry* __restrict__ state) {
+    const uint32_t ch = blockIdx.x * 64u + threadIdx.x;
+    if (ch >= nch) return;
+    IirCarry& s = state[ch];
+    IirState<NC> f;
+    const bool started = s.started != 0;
+    if (started) f.load(s.x, s.y);
+    else f.clear();
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        uint8_t* p = reinterpret_cast<uint8_t*>(buf + ((size_t)b * nch + ch) * ns);
+        if (b == 0 && !started) iir_channel<4, NC, true>(p, 4, ns, c, f, true);
+        else iir_channel<4, NC, false>(p, 4, ns, c, f, true);
+    }
+    f.store(s.x, s.y);
+    s.started = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The pipelined form.  A lone wave issues one instruction every ~2 ns whatever it is (tools/issue_rate.hip), so the time of a
 // channel is its sample count times the instructions the wave that HOLDS THE FILTER STATE has to issue per sample.  k_iir above
@@ -135,6 +267,11 @@ __global__ __launch_bounds__(64) void k_iir_carry(uint8_t* __restrict__ buf, uin
 // instantiations) and the selection of the run's last inputs are written out here, as in k_iir_cascade_pipe: moved into
 // functions of their own, each of them compiled to other instructions (up to +-34 per instantiation, other register counts),
 // and this kernel is kept instruction for instruction what was timed.
+//
+// PLANAR (k_iir_pipe_planar, the same body): lane <-> channel (or block) as before, so a wave's access touches 64 rows; a
+// producer's part and a writer's part are 64 contiguous bytes of one row (planar_load_set, planar_store_part).  block_bytes is
+// one [nch][hns] block of the matrix; with CARRY the run of ns rows passes through ns / hns such blocks, and a set or part across
+// a block boundary goes dword by dword.
 constexpr uint32_t kIirChunk = 64, kIirProd = 4, kIirPart = kIirChunk / kIirProd;  // four producer waves, 16 samples of a chunk each
 constexpr uint32_t kIirThreads = 64 * (2 + kIirProd);
 struct IirPipeLds {
@@ -148,201 +285,16 @@ static_assert(sizeof(IirPipeLds) <= 160 * 1024, "k_iir_pipe: the tiles must fit 
 template <int BPS, int NC, bool SHARED, bool ALIGNED, bool CARRY = false>
 __global__ __launch_bounds__(kIirThreads) void k_iir_pipe(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, IirCoef c, uint32_t nblocks,
                                                  uint32_t lanes_per_wg, IirCarry* __restrict__ state) {
-    static_assert(NC >= 2 && NC <= 5, "IirPipeLds::xlast holds five inputs per channel");
-    static_assert(!(SHARED && CARRY), "a carried state is one filter per channel");
-    __shared__ IirPipeLds L;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // lanes_per_wg < 64 spreads the lanes over more workgroups: in shared mode a lane is a BLOCK, its accesses are 16 MiB apart
-    // from its neighbours', and 64 of them per CU would ask one CU's memory path for more than it can give
-    const uint32_t unit = blockIdx.x * lanes_per_wg + lane;
-    uint32_t b, ch0, nser;
-    if (SHARED) {
-        b = unit;
-        ch0 = 0;
-        nser = nch;
-    } else {
-        b = unit / nch;
-        ch0 = unit - b * nch;
-        nser = 1;
-    }
-    // six waves on four SIMDs: the wave with the recurrence shares its SIMD with a producer -- it goes first whenever it can issue
-    if (role == 0u) __builtin_amdgcn_s_setprio(3);
-    const bool valid = lane < lanes_per_wg && b < nblocks;  // (lanes past the batch read block 0 along with the others and store nothing)
-    const size_t stride = (size_t)nch * BPS;
-    constexpr bool aligned = ALIGNED;  // (the host has looked at the base address: one load / store instruction per sample)
-    uint8_t* base = buf + (size_t)(valid ? b : 0u) * block_bytes + (size_t)(valid ? ch0 : 0u) * BPS;
-    const uint32_t nchunks = (ns + kIirChunk - 1) / kIirChunk;
-    IirState<NC> f;
-    f.clear();
-    constexpr int H = NC - 1;            // inputs in front of a sample that its feed-forward sum needs
-    constexpr uint32_t SET = kIirPart + H;  // a producer's samples per chunk: its part and the H in front of it
-    constexpr uint32_t kWriter = 1 + kIirProd;
-    // (lanes past the shape look at channel 0's state along with it and write nothing)
-    IirCarry* const cs = CARRY ? state + (valid ? ch0 : 0u) : nullptr;
-    const bool started = CARRY && cs->started != 0;
-    for (uint32_t sc = 0; sc < nser; ++sc) {
-        uint8_t* p = base + (size_t)sc * BPS;
-        const double x0 = (double)sample_load<BPS>(p, aligned);
-        int32_t cur[SET], nxt[SET], nx2[SET];
-        // element j of a producer's set in chunk t is sample t * 64 + (role - 1) * 16 - H + j; in front of the channel: the history (x0, see below)
-        auto load_set = [&](int32_t (&v)[SET], uint32_t t) {
-            const int32_t s0 = (int32_t)(t * kIirChunk + (role - 1u) * kIirPart) - H;
-            if (s0 >= 0 && s0 + (int32_t)SET <= (int32_t)ns) {  // (wave-uniform; all but a channel's first and last sets)
-                const uint8_t* q = p + (size_t)s0 * stride;
-#pragma unroll
-                for (uint32_t j = 0; j < SET; ++j) v[j] = sample_load<BPS>(q + (size_t)j * stride, aligned);
-            } else {
-#pragma unroll
-                for (uint32_t j = 0; j < SET; ++j) {
-                    int32_t si = s0 + (int32_t)j;
-                    si = si < 0 ? 0 : si >= (int32_t)ns ? (int32_t)ns - 1 : si;  // (clamped: what lies outside is never used as such)
-                    v[j] = sample_load<BPS>(p + (size_t)si * stride, aligned);
-                }
-            }
-        };
-        const bool producer = role >= 1u && role <= kIirProd;
-        if (producer) {
-            load_set(cur, 0);
-            if (nchunks > 1) load_set(nxt, 1);
-        }
-        for (uint32_t t = 0; t < nchunks + 2; ++t) {
-            if (role == 0u) {
-                if (CARRY && t == 0 && started) {  // (the y ring alone: this wave never reads x, the first producer takes it from the state)
-#pragma unroll
-                    for (int i = 0; i < NC; ++i) f.y[i] = cs->y[i];
-                } else if (t == 0) {
-                    // IirState::init_history, written out: as a call it compiles to other code here (see above the kernel)
-                    int32_t i = 0;
-                    for (; i < c.init_steps && i < NC; ++i) f.step(c.n, c.d, x0);  // (until the x ring holds nothing but x0)
-                    if (i < c.init_steps) {
-                        double P[NC];
-#pragma unroll
-                        for (int k = 0; k < NC; ++k) P[k] = c.d[k] * x0;
-                        // (unrolled by the ring's length: the shifts of y become register names instead of moves)
-#pragma unroll 4
-                        for (; i < c.init_steps; ++i) f.step_const(c.n, P);
-                    }
-                } else if (t <= nchunks) {
-                    const uint32_t k = t - 1, bi = k & 1u;
-                    const uint32_t cnt = min(kIirChunk, ns - k * kIirChunk);
-                    auto rec = [&](double ff) { return f.feedback(c.n, ff); };
-                    if (cnt == kIirChunk) {
-                        // sixteen samples at a time: their feed-forward sums are read from LDS together (one wait), the results
-                        // written together -- per sample the wave issues the recurrence and little else.  The truncation is the
-                        // GPU's own (saturating) conversion here; C's as the reference's build does it (trunc_i32_c, common.hpp) differs
-                        // from it only where this conversion returns INT_MAX (the double is >= 2^31 or +inf) and where the double
-                        // is NaN (this conversion: 0).  The largest result of the chunk is tracked (half an instruction per sample
-                        // instead of two); a NaN needs no tracking, because it is absorbing: the step after it multiplies it by
-                        // n[1], so every later output is NaN and the chunk's last one says whether any was (its high word: an
-                        // all-ones exponent, NaN or +-inf).  A chunk that reaches INT_MAX -- full-scale input through a filter that
-                        // overshoots -- or ends non-finite -- an unstable filter, non-finite coefficients -- is done once more, exactly.
-                        double ysave[NC];
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) ysave[i] = f.y[i];
-                        int32_t mx = (int32_t)0x80000000u;
-#pragma unroll 1
-                        for (uint32_t e0 = 0; e0 < kIirChunk; e0 += 16) {
-                            double a[16];
-                            int32_t o[16];
-#pragma unroll
-                            for (uint32_t e = 0; e < 16; ++e) a[e] = L.ff[bi][e0 + e][lane];
-#pragma unroll
-                            for (uint32_t e = 0; e < 16; ++e) o[e] = (int32_t)rec(a[e]);
-#pragma unroll
-                            for (uint32_t e = 0; e < 16; e += 2) mx = max(mx, max(o[e], o[e + 1]));  // (v_max3_i32)
-#pragma unroll
-                            for (uint32_t e = 0; e < 16; ++e) L.out[bi][e0 + e][lane] = o[e];
-                        }
-                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx == 0x7FFFFFFF || (__double2hiint(f.y[0]) & 0x7FF00000) == 0x7FF00000) != 0ull, 0)) {
-#pragma unroll
-                            for (int i = 0; i < NC; ++i) f.y[i] = ysave[i];
-#pragma unroll 1
-                            for (uint32_t e = 0; e < kIirChunk; ++e) L.out[bi][e][lane] = trunc_i32_c(rec(L.ff[bi][e][lane]));
-                        }
-                    } else {
-                        for (uint32_t e = 0; e < cnt; ++e) L.out[bi][e][lane] = trunc_i32_c(rec(L.ff[bi][e][lane]));  // C truncation (rspt_test.cpp:130)
-                    }
-                    if (SHARED && t == nchunks) {  // the x ring the next channel's initialisation starts from (its first NC - 1 calls see it)
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) f.x[i] = L.xlast[i][lane];
-                    }
-                    if (CARRY && t == nchunks && valid) {  // the object as it stands behind the call's last sample
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) {
-                            cs->x[i] = L.xlast[i][lane];
-                            cs->y[i] = f.y[i];
-                        }
-                        cs->started = 1;
-                    }
-                }
-            } else if (role == kWriter) {
-                if (t >= 2) {
-                    const uint32_t k = t - 2, bi = k & 1u;
-                    const uint32_t cnt = min(kIirChunk, ns - k * kIirChunk);
-                    uint8_t* q = p + (size_t)k * kIirChunk * stride;
-                    if (cnt == kIirChunk) {
-#pragma unroll 1
-                        for (uint32_t e0 = 0; e0 < kIirChunk; e0 += 16) {
-                            int32_t v[16];
-#pragma unroll
-                            for (uint32_t e = 0; e < 16; ++e) v[e] = L.out[bi][e0 + e][lane];
-                            if (valid) {
-#pragma unroll
-                                for (uint32_t e = 0; e < 16; ++e) sample_store<BPS>(q + (size_t)(e0 + e) * stride, v[e], aligned);
-                            }
-                        }
-                    } else {
-                        for (uint32_t e = 0; e < cnt; ++e) {
-                            const int32_t v = L.out[bi][e][lane];
-                            if (valid) sample_store<BPS>(q + (size_t)e * stride, v, aligned);
-                        }
-                    }
-                }
-            } else if (t < nchunks) {
-                if (t + 2 < nchunks) load_set(nx2, t + 2);  // (two chunks ahead: the loads have two ticks to arrive)
-                // the inputs as doubles; in front of the channel's first sample the x ring holds x0 (init_steps >= NC - 1: the host checks)
-                const int32_t s0 = (int32_t)(t * kIirChunk + (role - 1u) * kIirPart) - H;
-                double xs[SET];
-#pragma unroll
-                for (uint32_t j = 0; j < SET; ++j) xs[j] = (double)cur[j];
-                if (s0 < 0) {  // (wave-uniform: the first producer's first set only)
-#pragma unroll
-                    for (uint32_t j = 0; j < SET; ++j) xs[j] = (s0 + (int32_t)j < 0) ? x0 : xs[j];
-                    if (CARRY) {  // (s0 = -H: element j < H is the input H - j samples in front of the call, place H - 1 - j of the x ring)
-#pragma unroll
-                        for (int j = 0; j < H; ++j) xs[j] = started ? cs->x[H - 1 - j] : (H - 1 - j < c.init_steps ? x0 : 0.0)  /* iir_front: the place is below NC */;
-                    }
-                }
-#pragma unroll
-                for (uint32_t e = 0; e < kIirPart; ++e) {  // (iir_ff, written out)
-                    double a = c.d[0] * xs[H + e];
-#pragma unroll
-                    for (int i = 1; i < NC; ++i) a = a + c.d[i] * xs[H + e - i];
-                    L.ff[t & 1u][(role - 1u) * kIirPart + e][lane] = a;
-                }
-                if ((SHARED || CARRY) && t + 1 == nchunks) {  // whoever holds the channel's last sample hands its last inputs on
-                    const int32_t last = (int32_t)ns - 1 - (s0 + H);  // index of sample ns-1 in this wave's part
-                    if (last >= 0 && last < (int32_t)kIirPart) {
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) {
-                            double v = 0.0;
-#pragma unroll
-                            for (uint32_t j = 0; j < SET; ++j)
-                                if ((int32_t)j == last + H - i) v = xs[j];
-                            L.xlast[i][lane] = v;
-                        }
-                    }
-                }
-#pragma unroll
-                for (uint32_t j = 0; j < SET; ++j) {
-                    cur[j] = nxt[j];
-                    nxt[j] = nx2[j];
-                }
-            }
-            __syncthreads();
-        }
-    }
+    constexpr bool PLANAR = false;
+#include "k_iir_pipe_body.hpp"
+}
+
+template <int NC, bool SHARED, bool CARRY>
+__global__ __launch_bounds__(kIirThreads) void k_iir_pipe_planar(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, IirCoef c,
+                                                                 uint32_t nblocks, uint32_t lanes_per_wg, IirCarry* __restrict__ state) {
+    constexpr int BPS = 4;
+    constexpr bool ALIGNED = true, PLANAR = true;
+#include "k_iir_pipe_body.hpp"
 }
 
 }  // namespace rspt

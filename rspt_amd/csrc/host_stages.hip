@@ -65,10 +65,45 @@ static void launch_iir_stream(rspt_hip_packer* p, uint8_t* buf, uint32_t rows, c
     hipLaunchKernelGGL((k_iir_carry<BPS, NC>), grid, dim3(64), 0, st, buf, g.nch, rows, c, state);
 }
 
-// Both IIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+// The planar entries (rspt_hip_iir_prefilter_planar_*_dev): the native routes on the int32 matrix [B][nch][ns], whatever the
+// handle's bps.  A kernel takes block_bytes as one block of the matrix; a carried call is one run of B * ns rows through B of them.
+template <int NC>
+static void launch_iir_planar(rspt_hip_packer* p, int32_t* d_planar, uint32_t B, const IirCoef& c, int per_channel, IirCarry* state, hipStream_t st) {
+    const Geom& g = p->g;
+    uint8_t* buf = reinterpret_cast<uint8_t*>(d_planar);
+    const uint64_t block_bytes = (uint64_t)g.nch * g.ns * 4u;
+    if (state) {
+        const dim3 grid((g.nch + 63) / 64);
+        const uint32_t rows = B * g.ns;  // (below kStreamMaxRows: iir_call)
+        if (rows >= kIirChunk)
+            hipLaunchKernelGGL((k_iir_pipe_planar<NC, false, true>), grid, dim3(kIirThreads), 0, st, buf, g.nch, rows, block_bytes, c, 1u, 64u, state);
+        else
+            hipLaunchKernelGGL((k_iir_planar_carry<NC>), grid, dim3(64), 0, st, d_planar, g.nch, g.ns, B, c, state);
+        return;
+    }
+    if (g.ns >= kIirChunk && c.init_steps >= NC - 1) {
+        if (per_channel) {
+            const uint32_t units = B * g.nch;
+            hipLaunchKernelGGL((k_iir_pipe_planar<NC, false, false>), dim3((units + 63) / 64), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, block_bytes, c, B,
+                               64u, (IirCarry*)nullptr);
+        } else {  // (lanes per workgroup as in launch_iir: a lane is a block)
+            uint32_t lpw = (B + (uint32_t)p->num_cu - 1) / (uint32_t)p->num_cu;
+            lpw = lpw < 1 ? 1 : lpw > 64 ? 64 : lpw;
+            hipLaunchKernelGGL((k_iir_pipe_planar<NC, true, false>), dim3((B + lpw - 1) / lpw), dim3(kIirThreads), 0, st, buf, g.nch, g.ns, block_bytes, c, B,
+                               lpw, (IirCarry*)nullptr);
+        }
+        return;
+    }
+    if (per_channel) hipLaunchKernelGGL((k_iir_planar<NC, false>), dim3((B * g.nch + 63) / 64), dim3(64), 0, st, d_planar, g.nch, g.ns, c, B);
+    else hipLaunchKernelGGL((k_iir_planar<NC, true>), dim3((B + 63) / 64), dim3(64), 0, st, d_planar, g.nch, g.ns, c, B);
+}
+
+// All four IIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state;
+// planar: d_buf is the int32 matrix.
 static int iir_call(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients, int init_nr_samples,
-                    int per_channel, void* d_state, void* stream) {
+                    int per_channel, void* d_state, void* stream, bool planar = false) {
     if (!p || !d_buf || !n || !d || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (planar && reinterpret_cast<uintptr_t>(d_buf) % 4) return RSPT_HIP_ERR_ARG;
     if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;  // filter_opt covers 2..5 (iir_filter.cpp:87-103)
     if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     const uint64_t rows = (uint64_t)nblocks * p->g.ns;
@@ -82,6 +117,11 @@ static int iir_call(rspt_hip_packer* p, void* d_buf, size_t nblocks, const doubl
     c.nc = (uint32_t)nr_coefficients;
     c.init_steps = 4 * init_nr_samples;
     hipStream_t st = (hipStream_t)stream;
+    if (planar) {
+        by_nc(c.nc, [&](auto ncv) { launch_iir_planar<decltype(ncv)::value>(p, (int32_t*)d_buf, (uint32_t)nblocks, c, per_channel, (IirCarry*)d_state, st); });
+        HIPCHK(p, hipGetLastError());
+        return RSPT_HIP_OK;
+    }
     by_bps(p->g.bps, [&](auto bps) {
         by_nc(c.nc, [&](auto ncv) {
             constexpr int BPS = decltype(bps)::value, NC = decltype(ncv)::value;
@@ -110,6 +150,17 @@ int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nb
     return iir_call(p, d_buf, nblocks, n, d, nr_coefficients, init_nr_samples, 0, d_state, stream);
 }
 
+int rspt_hip_iir_prefilter_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
+                                            size_t nr_coefficients, int init_nr_samples, int per_channel, void* stream) {
+    return iir_call(p, d_planar, nblocks, n, d, nr_coefficients, init_nr_samples, per_channel, nullptr, stream, true);
+}
+
+int rspt_hip_iir_prefilter_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
+                                             size_t nr_coefficients, int init_nr_samples, void* d_state, void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return iir_call(p, d_planar, nblocks, n, d, nr_coefficients, init_nr_samples, 0, d_state, stream, true);
+}
+
 // ---- IIR cascade (iir_cascade.hip) ----
 // One run of `ns` rows per (block, channel): the stateless call's nblocks blocks of g.ns rows, or (CARRY) the call's blocks as one
 // block of nblocks * g.ns rows.  Whether a channel is fresh is known on the device only and the pipelined kernel starts from any
@@ -128,10 +179,26 @@ static void launch_iir_cascade(rspt_hip_packer* p, uint8_t* buf, uint32_t B, uin
     hipLaunchKernelGGL((k_iir_cascade<BPS, CARRY>), grid, dim3(64), 0, st, buf, p->g.nch, ns, block_bytes, a, B, state);
 }
 
-// Both cascade entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+// The planar entries: the same routes on the int32 matrix [B][nch][hns]; block_bytes is one block of it, and a carried call
+// (B = 1 for the kernel) is one run of ns rows through ns / hns of them.
+template <bool CARRY>
+static void launch_iir_cascade_planar(rspt_hip_packer* p, int32_t* d_planar, uint32_t B, uint32_t ns, const CascadeArgs& a, IirCarry* state, hipStream_t st) {
+    uint8_t* buf = reinterpret_cast<uint8_t*>(d_planar);
+    const uint64_t block_bytes = (uint64_t)p->g.nch * p->g.ns * 4u;
+    const dim3 grid((B * p->g.nch + 63) / 64);
+    if (ns >= kCascChunk)
+        hipLaunchKernelGGL((k_iir_cascade_pipe_planar<CARRY>), grid, dim3(64 * casc_waves(a.nsec)), 0, st, buf, p->g.nch, ns, block_bytes, a, B, state);
+    else
+        hipLaunchKernelGGL((k_iir_cascade_planar<CARRY>), grid, dim3(64), 0, st, buf, p->g.nch, ns, block_bytes, a, B, state);
+}
+
+// All four cascade entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the
+// state; planar: d_buf is the int32 matrix.
 static int iir_cascade_call(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d,
-                            const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state, void* stream) {
+                            const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state, void* stream,
+                            bool planar = false) {
     if (!p || !d_buf || !n || !d || !nr_coefficients || !init_nr_samples || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (planar && reinterpret_cast<uintptr_t>(d_buf) % 4) return RSPT_HIP_ERR_ARG;
     if (nsections < 1 || nsections > kCascMaxSections) return RSPT_HIP_ERR_ARG;
     CascadeArgs a{};
     a.nsec = (uint32_t)nsections;
@@ -151,6 +218,12 @@ static int iir_cascade_call(rspt_hip_packer* p, void* d_buf, size_t nblocks, siz
     if (d_state && rows >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
+    if (planar) {
+        if (d_state) launch_iir_cascade_planar<true>(p, (int32_t*)d_buf, 1u, (uint32_t)rows, a, (IirCarry*)d_state, st);
+        else launch_iir_cascade_planar<false>(p, (int32_t*)d_buf, (uint32_t)nblocks, p->g.ns, a, nullptr, st);
+        HIPCHK(p, hipGetLastError());
+        return RSPT_HIP_OK;
+    }
     by_bps(p->g.bps, [&](auto bps) {
         constexpr int BPS = decltype(bps)::value;
         if (d_state) launch_iir_cascade<BPS, true>(p, (uint8_t*)d_buf, 1u, (uint32_t)rows, rows * p->g.nch * BPS, a, (IirCarry*)d_state, st);
@@ -176,6 +249,18 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
                                     void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
     return iir_cascade_call(p, d_buf, nblocks, nsections, n, d, nr_coefficients, init_nr_samples, use_filter, d_state, stream);
+}
+
+int rspt_hip_iir_cascade_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                          const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* stream) {
+    return iir_cascade_call(p, d_planar, nblocks, nsections, n, d, nr_coefficients, init_nr_samples, use_filter, nullptr, stream, true);
+}
+
+int rspt_hip_iir_cascade_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, size_t nsections, const double* n, const double* d,
+                                           const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state,
+                                           void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return iir_cascade_call(p, d_planar, nblocks, nsections, n, d, nr_coefficients, init_nr_samples, use_filter, d_state, stream, true);
 }
 
 // ---- zero-phase IIR (iir_zero_phase.hip) ----

@@ -54,51 +54,21 @@ __device__ __forceinline__ void casc_start(const IirCoef& c, double x0, bool sta
 // The plain kernel: one thread per (block, channel) runs the chain as written in rspt_hip.h, sample by sample.  It serves rows
 // shorter than a chunk of the pipelined kernel.  CARRY: one run of ns rows (nblocks = 1), the chain of channel ch in
 // state[ch * nsec ..]; `started` of section 0 decides whether the channel initialises.
+// PLANAR (k_iir_cascade_planar, the same body; the int32 matrix [nblocks][nch][hns], filter.hip: PlanarRun): block_bytes is one
+// block of the matrix; stateless the run is the channel's row (ns = hns), CARRY it is the channel's rows in ns / hns blocks.
 template <int BPS, bool CARRY>
 __global__ __launch_bounds__(64) void k_iir_cascade(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, CascadeArgs a, uint32_t nblocks,
                                                     IirCarry* __restrict__ state) {
-    const uint32_t t = blockIdx.x * 64u + threadIdx.x;
-    const uint32_t b = t / nch, ch = t - b * nch;
-    if (b >= nblocks) return;
-    const size_t stride = (size_t)nch * BPS;
-    const bool aligned = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0 && (block_bytes % BPS) == 0;
-    uint8_t* p = buf + (size_t)b * block_bytes + (size_t)ch * BPS;
-    IirCarry* const cs = CARRY ? state + (size_t)ch * a.nsec : nullptr;
-    const bool started = CARRY && cs[0].started != 0;
-    const double x0 = (double)sample_load<BPS>(p, aligned);
-    double x[kCascMaxSections][5], y[kCascMaxSections][5];
-#pragma unroll
-    for (uint32_t k = 0; k < kCascMaxSections; ++k) {
-        if (k < a.nsec) casc_start(a.s[k], x0, started, CARRY ? cs + k : nullptr, x[k], y[k]);
-    }
-    for (uint32_t s = 0; s < ns; ++s) {
-        uint8_t* q = p + (size_t)s * stride;
-        double v = (double)sample_load<BPS>(q, aligned);
-#pragma unroll
-        for (uint32_t k = 0; k < kCascMaxSections; ++k) {
-            if (k >= a.nsec) continue;
-            const bool filt = (a.use_filter >> k) & 1u;
-            by_nc(a.s[k].nc, [&](auto ncv) {
-                IirState<decltype(ncv)::value> f;
-                f.load(x[k], y[k]);
-                v = filt ? f.step(a.s[k].n, a.s[k].d, v) : f.step_opt(a.s[k].n, a.s[k].d, v);
-                f.store(x[k], y[k]);
-            });
-        }
-        sample_store<BPS>(q, trunc_i32_c(v), aligned);  // C truncation, once, behind the last section
-    }
-    if (CARRY) {
-#pragma unroll
-        for (uint32_t k = 0; k < kCascMaxSections; ++k) {
-            if (k >= a.nsec) continue;
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                cs[k].x[i] = x[k][i];
-                cs[k].y[i] = y[k][i];
-            }
-            cs[k].started = 1;
-        }
-    }
+    constexpr bool PLANAR = false;
+#include "k_iir_cascade_body.hpp"
+}
+
+template <bool CARRY>
+__global__ __launch_bounds__(64) void k_iir_cascade_planar(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, CascadeArgs a,
+                                                           uint32_t nblocks, IirCarry* __restrict__ state) {
+    constexpr int BPS = 4;
+    constexpr bool PLANAR = true;
+#include "k_iir_cascade_body.hpp"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -121,6 +91,9 @@ __global__ __launch_bounds__(64) void k_iir_cascade(uint8_t* __restrict__ buf, u
 // (nblocks = 1); a channel whose section 0 has started takes every section's rings from state[ch * S + k] instead, and each
 // ring is written back by the wave that holds it, behind the run's last chunk.  A wave reads the state in front of the first
 // barrier and writes only places that no other wave reads, or (the producers' x ring) a tick later, behind a barrier.
+//
+// PLANAR (k_iir_cascade_pipe_planar, the same body, a CascWavePlanar): as k_iir_pipe's -- the producers' sets through
+// planar_load_set, the store wave's groups through planar_store_part.
 constexpr uint32_t kCascChunk = 32, kCascProd = 2, kCascPart = kCascChunk / kCascProd;
 constexpr uint32_t kCascSlots = 2 * kCascMaxSections + 1;
 constexpr uint32_t kCascGroup = 16;  // samples a wave reads from the tile together, works on, and writes together
@@ -201,6 +174,19 @@ struct CascWave {
     __device__ __forceinline__ uint32_t count(uint32_t j) const { return min(kCascChunk, ns - j * kCascChunk); }
 };
 
+struct CascWavePlanar : CascWave {
+    PlanarRun run;  // where the run's samples live in the matrix
+};
+// the lane's first sample and its run in the matrix (the overload on CascWave is never called: a statement under
+// `if constexpr (PLANAR)` outside a template is not compiled to anything, but it has to name something)
+template <bool ONE_ROW>
+__device__ __forceinline__ void casc_planar_start(CascWavePlanar& w, uint8_t* buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, uint32_t b, uint32_t ch) {
+    w.p = buf + (size_t)b * block_bytes + (size_t)ch * planar_run<ONE_ROW>(buf, nch, ns, block_bytes).hns * 4u;
+    w.run = planar_run<ONE_ROW>(w.p, nch, ns, block_bytes);
+}
+template <bool ONE_ROW>
+__device__ __forceinline__ void casc_planar_start(CascWave&, uint8_t*, uint32_t, uint32_t, uint64_t, uint32_t, uint32_t) {}
+
 // Each role is a tick loop of its own with the same number of barriers, so that no role's registers live through another's.
 
 // section k's recurrence: sums -> outputs, its y ring in registers (filter(): both rings); the history initialisation in front
@@ -249,8 +235,9 @@ __device__ __forceinline__ void casc_wave_ff(const CascWave& w, const IirCoef& c
 }
 
 // a producer: loads its half of every chunk two chunks ahead, converts, writes section 0's feed-forward sums (filter(): the samples)
-template <int BPS, bool ALIGNED, bool CARRY>
-__device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef& c, uint32_t part) {
+template <int BPS, bool ALIGNED, bool CARRY, class W>
+__device__ __forceinline__ void casc_wave_prod(const W& w, const IirCoef& c, uint32_t part) {
+    constexpr bool PLANAR = std::is_same<W, CascWavePlanar>::value;
     constexpr int H = 4;
     constexpr uint32_t SET = kCascPart + H;  // its 16 samples and the H in front: element e of chunk j is sample j * 32 + part * 16 - H + e
     double x[5];  // the inputs in front of the run, newest first; behind the run's last chunk: the run's last inputs
@@ -260,7 +247,9 @@ __device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef&
     int32_t cur[SET], nxt[SET], nx2[SET];
     auto load_set = [&](int32_t (&v)[SET], uint32_t j) {
         const int32_t s0 = (int32_t)(j * kCascChunk + part * kCascPart) - H;
-        if (s0 >= 0 && s0 + (int32_t)SET <= (int32_t)w.ns) {  // (wave-uniform; all but a run's first and last sets)
+        if constexpr (PLANAR) {
+            planar_load_set<(uint32_t)H, !CARRY>(w.run, w.ns, s0, v);
+        } else if (s0 >= 0 && s0 + (int32_t)SET <= (int32_t)w.ns) {  // (wave-uniform; all but a run's first and last sets)
             const uint8_t* q = w.p + (size_t)s0 * w.stride;
 #pragma unroll
             for (uint32_t e = 0; e < SET; ++e) v[e] = sample_load<BPS>(q + (size_t)e * w.stride, ALIGNED);
@@ -297,7 +286,10 @@ __device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef&
                     for (uint32_t e = 0; e < kCascPart; ++e) T[part * kCascPart + e][w.lane] = iir_ff<decltype(ncv)::value>(c.d, &xs[H + e]);
                 });
                 const int32_t last = (int32_t)w.ns - 1 - (s0 + H);  // index of sample ns - 1 in this wave's part
-                if (CARRY && j + 1 == w.nchunks && last >= 0 && last < (int32_t)kCascPart) {  // whoever holds the run's last sample
+                if constexpr (PLANAR) {
+                    // (the run's last inputs go to the state below, straight from the matrix: picked out of the set by index, as
+                    // in the native form, they cost this kernel 16 spilled VGPRs)
+                } else if (CARRY && j + 1 == w.nchunks && last >= 0 && last < (int32_t)kCascPart) {  // whoever holds the run's last sample
                     have_last = true;
 #pragma unroll
                     for (int i = 0; i < 5; ++i) {
@@ -315,6 +307,16 @@ __device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef&
                 nxt[e] = nx2[e];
             }
         }
+        if constexpr (PLANAR) {
+            // The x ring behind the run: its last nc samples.  At tick 1 nothing of the matrix is filtered yet -- the store wave's
+            // first tick is 2 S >= 2 (k_iir_cascade_pipe_body.hpp: w.off) -- and a pipelined run has kCascChunk rows and more, so
+            // the nc <= 5 samples exist and are the inputs.  The second producer writes them behind the first barrier: the first
+            // one has read the carried ring in front of it, and nobody else reads these places.
+            static_assert(kCascChunk >= 5 && kCascProd >= 2, "a pipelined run holds a ring's five inputs; a second producer writes them");
+            if (CARRY && t == 1u && part == 1u && !w.filt && w.valid) {
+                for (uint32_t i = 0; i < c.nc; ++i) w.cs->x[i] = (double)*w.run.at(w.ns - 1u - i);
+            }
+        }
         __syncthreads();
     }
     // (behind the last barrier: the other producer has long read the ring, also in a run of one chunk)
@@ -324,15 +326,24 @@ __device__ __forceinline__ void casc_wave_prod(const CascWave& w, const IirCoef&
 }
 
 // the store wave: the last section's outputs, truncated as C truncates them, once
-template <int BPS, bool ALIGNED>
-__device__ __forceinline__ void casc_wave_store(const CascWave& w) {
+template <int BPS, bool ALIGNED, bool CARRY, class W>
+__device__ __forceinline__ void casc_wave_store(const W& w) {
+    constexpr bool PLANAR = std::is_same<W, CascWavePlanar>::value;
     for (uint32_t t = 0; t < w.nticks; ++t) {
         const uint32_t j = t - w.off;
         if (j < w.nchunks) {
             double(*T)[64] = w.tiles[j % kCascSlots];
             const uint32_t cnt = w.count(j);
             uint8_t* q = w.p + (size_t)j * kCascChunk * w.stride;
-            if (cnt == kCascChunk) {
+            if constexpr (PLANAR) {
+#pragma unroll 1
+                for (uint32_t e0 = 0; e0 < cnt; e0 += kCascGroup) {
+                    int32_t o[kCascGroup];
+#pragma unroll
+                    for (uint32_t e = 0; e < kCascGroup; ++e) o[e] = trunc_i32_c(T[e0 + e][w.lane]);
+                    planar_store_part<!CARRY>(w.run, j * kCascChunk + e0, min(kCascGroup, cnt - e0), o, w.valid);
+                }
+            } else if (cnt == kCascChunk) {
 #pragma unroll 1
                 for (uint32_t e0 = 0; e0 < kCascChunk; e0 += kCascGroup) {
                     double v[kCascGroup];
@@ -357,43 +368,16 @@ __device__ __forceinline__ void casc_wave_store(const CascWave& w) {
 template <int BPS, bool ALIGNED, bool CARRY>
 __global__ __launch_bounds__(kCascMaxThreads) void k_iir_cascade_pipe(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, CascadeArgs a,
                                                                       uint32_t nblocks, IirCarry* __restrict__ state) {
-    __shared__ CascLds L;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t S = a.nsec;
-    CascWave w;
-    w.lane = threadIdx.x & 63u;
-    const uint32_t unit = blockIdx.x * 64u + w.lane;
-    const uint32_t b = unit / nch, ch0 = unit - b * nch;
-    w.valid = b < nblocks;
-    w.stride = (size_t)nch * BPS;
-    w.p = buf + (size_t)(w.valid ? b : 0u) * block_bytes + (size_t)(w.valid ? ch0 : 0u) * BPS;
-    w.ns = ns;
-    w.nchunks = (ns + kCascChunk - 1) / kCascChunk;
-    w.nticks = w.nchunks + 2 * S;
-    w.tiles = L.v;
-    w.x0 = (double)sample_load<BPS>(w.p, ALIGNED);
-    IirCarry* const cs0 = CARRY ? state + (size_t)(w.valid ? ch0 : 0u) * S : nullptr;
-    w.started = CARRY && cs0->started != 0;
-    auto section = [&](uint32_t k) {
-        w.cs = CARRY ? cs0 + k : nullptr;
-        w.filt = ((a.use_filter >> k) & 1u) != 0;
-        return a.s[k];
-    };
-    if (wave < S) {
-        __builtin_amdgcn_s_setprio(3);  // a recurrence wave goes first whenever it can issue
-        w.off = 2 * wave + 1;
-        casc_wave_rec<CARRY>(w, section(wave));
-    } else if (wave < 2 * S - 1) {
-        const uint32_t k = wave - S + 1;
-        w.off = 2 * k;
-        casc_wave_ff<CARRY>(w, section(k));
-    } else if (wave < 2 * S + 1) {
-        w.off = 0;
-        casc_wave_prod<BPS, ALIGNED, CARRY>(w, section(0), wave - (2 * S - 1));
-    } else {
-        w.off = 2 * S;
-        casc_wave_store<BPS, ALIGNED>(w);
-    }
+    constexpr bool PLANAR = false;
+#include "k_iir_cascade_pipe_body.hpp"
+}
+
+template <bool CARRY>
+__global__ __launch_bounds__(kCascMaxThreads) void k_iir_cascade_pipe_planar(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes,
+                                                                             CascadeArgs a, uint32_t nblocks, IirCarry* __restrict__ state) {
+    constexpr int BPS = 4;
+    constexpr bool ALIGNED = true, PLANAR = true;
+#include "k_iir_cascade_pipe_body.hpp"
 }
 
 }  // namespace rspt
