@@ -50,13 +50,18 @@ enum rspt_hip_kind {
  * hzr_encode's HZR_FAIL on a short buffer), the _many pipelines, the feed, the device batch calls, the container calls,
  * rspt_hip_set_verify, profiling.  In the device batch form buffer b starts at d_src + b * in_size -- at any byte alignment
  * when in_size is not a multiple of 16; only the batch base keeps the 16-byte rule -- and decodes to d_dst + b * in_size.
- * Decode differs from hzr_decode in three points, the first two because a handle has one size:
+ * Decode differs from hzr_decode in five points, the first two because a handle has one size:
  *   - a stream whose master header names another decoded size than in_size is malformed (RSPT_HIP_ERR_CORRUPT, bit 63 of
  *     d_consumed[b]); hzr_decode accepts any size up to out_size;
  *   - d_consumed[b] / *src_len report the bytes the stream spans.  hzr_decode's "decoder reached the end of the input"
  *     test (hzr_decode.c:668) is the caller's comparison of that value with the length it holds.
  *   - a Fill block whose length field is not 1 is malformed.  No encoder writes one; hzr_decode would read the fill byte and
  *     go on right behind it, hzr_verify would step over the whole length, so such a stream has no framing to follow.
+ *   - stricter than hzr_decode: a Huffman tree with a code of 32 bits or more is malformed.  hzr_decode walks codes of any
+ *     length; no block of 65536 bytes gives an optimal code that long (lengths from 24 up need Fibonacci counts).
+ *   - stricter than hzr_decode: a Huffman tree that holds a leaf with a symbol above 260 is malformed, used or not.
+ *     hzr_decode fails only when such a symbol is decoded.
+ *   (Both hold for the hzr blocks inside every packer kind's streams as well: rspt_hip_decompress_batch_dev.)
  * The filter, median, peak, PRDN and converter stages see such a handle as the shape (bps 1, nch 1, ns in_size). */
 
 /* Test hook, OR-ed into `kind` at create: a dct packer takes the fp64 FFT path also where the bit-exact dense-table path
@@ -106,9 +111,11 @@ int rspt_hip_compress(rspt_hip_packer* p, const void* src_host, void* dst_host, 
 int rspt_hip_decompress(rspt_hip_packer* p, const void* src_host, size_t* src_len, void* dst_host);
 
 /* The same for a caller that knows how many bytes are readable at src_host (no counterpart in the reference, whose decompress
- * trusts the stream's own length fields -- as rspt_hip_decompress does, up to rspt_hip_max_compressed_size: a damaged length field
- * of a stream from an untrusted source can send it past the end of a shorter buffer).  Nothing beyond src_host + src_cap is
- * read; a stream whose framing says otherwise is RSPT_HIP_ERR_CORRUPT. */
+ * trusts the stream's own length fields -- as rspt_hip_decompress does, up to the longest stream the format allows, 65536 bytes
+ * of payload for every hzr block whatever the block decodes to (another writer's Huffman block may be longer than its output, so
+ * this is more than rspt_hip_max_compressed_size where the last block is short): a damaged length field of a stream from an
+ * untrusted source can send it past the end of a shorter buffer).  Nothing beyond src_host + src_cap is read; a stream whose
+ * framing says otherwise is RSPT_HIP_ERR_CORRUPT. */
 int rspt_hip_decompress_bounded(rspt_hip_packer* p, const void* src_host, size_t src_cap, size_t* src_len, void* dst_host);
 
 /* Worst-case stream size of ONE block for this packer, allowing for nb
@@ -229,7 +236,11 @@ int rspt_hip_compress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nb
 
 /* Decompress nblocks streams resident in device memory (stream b at
  * d_src + b*src_stride) into d_dst (nblocks * rspt_hip_block_bytes() bytes).
- * d_consumed[b] = bytes of stream b used; bit 63 set = malformed stream. */
+ * d_consumed[b] = bytes of stream b used; bit 63 set = malformed stream.
+ * Every valid stream decodes, whatever writer made it -- any tree shape, duplicate or unused leaves, any tokenisation, any pad
+ * bits -- with two limits that are stricter than hzr_decode (lib_hzr/hzr_decode.c), which takes such streams: a block whose
+ * Huffman tree has a code of 32 bits or more, and a block whose tree holds a leaf symbol above 260 even where no code uses
+ * it, are malformed here (bit 63).  Neither encoder writes either; tests/test_hzr_foreign.py holds the decoder to both. */
 int rspt_hip_decompress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, void* d_dst,
                                   uint64_t* d_consumed, void* stream);
 

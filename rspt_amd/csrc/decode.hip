@@ -516,7 +516,7 @@ __device__ __forceinline__ void dec_block(uint32_t k, uint32_t j, uint32_t b0, u
             }
             const uint32_t bits = (uint32_t)win;
             if (!(bits & 1u)) {  // branch
-                if (pp + 1u > P || n >= 2u * kNumSym - 1u || depth >= 31u) {  // (depth 32+: deeper than the reference's 32-bit codes)
+                if (pp + 1u > P || n >= 2u * kNumSym - 1u || depth >= 31u) {  // (codes of 32 bits and more are refused: stricter than hzr_decode -- rspt_hip.h)
                     bad = 1;
                     break;
                 }
@@ -747,7 +747,7 @@ __device__ __forceinline__ void dec_block(uint32_t k, uint32_t j, uint32_t b0, u
     uint32_t deep = 0;
     for (uint32_t i = tid; i < nn; i += kDecThreads) {  // C
         // one walk to the root: the decisions come deepest first, so shifting them in from the right leaves the root's at
-        // bit 0 -- the code as the stream has it (root first, LSB first).  (Depths beyond 32 are refused below.)
+        // bit 0 -- the code as the stream has it (root first, LSB first).  (Depths beyond 31 are refused below.)
         uint32_t depth = 0, cur = i, code = 0;
         while (cur != 0 && depth < 40) {
             const uint32_t pw = t_par[cur];
@@ -760,13 +760,15 @@ __device__ __forceinline__ void dec_block(uint32_t k, uint32_t j, uint32_t b0, u
             if (depth > 31) deep = 1;
             // a single-leaf tree has depth 0: the stream still spends 1 bit per symbol (hzr_decode.c:290,463-470)
             const uint32_t elen = depth ? depth : 1u;
-            if (elen <= kLutBits)  // every leaf of <= 10 bits owns the entries code + m * 2^len
-                for (uint32_t e = code; e < (1u << kLutBits); e += 1u << elen) d.lut[e] = tok_entry(w_node & 511u, elen);
+            // every leaf of <= 10 bits owns the entries code + m * 2^depth -- the single leaf (depth 0) all of them: the value of
+            // its one bit per symbol means nothing to the reference, and the one-wave recovery above fills every entry too
+            if (elen <= kLutBits)
+                for (uint32_t e = code; e < (1u << kLutBits); e += 1u << depth) d.lut[e] = tok_entry(w_node & 511u, elen);
         } else if (depth == kLutBits) {
             d.lut[code] = long_prefix_entry(d, i);  // codes longer than the table index continue from here
         }
     }
-    if (wg_any(d, 2, deep != 0)) {  // deeper than the reference's decoder supports (hzr_decode.c: 32-bit codes)
+    if (wg_any(d, 2, deep != 0)) {  // a code of 32 bits or more: refused here (the reference's decoder walks on) -- rspt_hip.h
         if (tid == 0) atomicOr((unsigned long long*)&consumed[b], (unsigned long long)kBadBit);
         return;
     }

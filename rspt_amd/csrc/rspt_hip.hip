@@ -915,7 +915,12 @@ int rspt_hip_set_verify(rspt_hip_packer* p, int on) {
 static int ensure_host_staging(rspt_hip_packer* p) {
     if (p->stage.src) return RSPT_HIP_OK;
     HostStaging s;
-    s.dst_cap = rspt_hip_max_compressed_size(p) + 64;
+    // The stream buffer serves both directions.  What compress writes fits rspt_hip_max_compressed_size; what decompress is
+    // given may be longer: a Huffman block of another writer can have up to 65536 bytes of payload whatever it decodes to
+    // (hzr_decode takes it: tests/test_hzr_foreign.py, the full tree over a 16-byte block), so every block counts in full.
+    const size_t hzr_longest = 4 + (size_t)p->g.nblk * (7 + (size_t)kHzrBlock);
+    const size_t longest = p->g.kind == RSPT_HIP_KIND_BYTES ? hzr_longest : 1 + p->g.hdr_len + (size_t)kMaxPlanes * (4 + hzr_longest);
+    s.dst_cap = std::max(rspt_hip_max_compressed_size(p), longest) + 64;
     if (hipMalloc(s.src.out(), p->g.block_bytes + 64) != hipSuccess || hipMalloc(s.dst.out(), s.dst_cap) != hipSuccess ||
         hipMalloc(s.size.out(), sizeof(uint64_t)) != hipSuccess)
         return RSPT_HIP_ERR_ALLOC;
