@@ -466,7 +466,8 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
  * outside 2..5, init_nr_samples outside 0 .. 2^28, nsections outside 1..4, a NULL or misaligned d_state -- and for a d_planar
  * off its 4-byte alignment; RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels, before anything is launched, and for a stream
  * call of 2^31 - 2^17 rows or more.  A refused call writes nothing.  Asynchronous on `stream`; the entries allocate nothing.
- * Only these two stages have a planar form: the zero-phase IIR, FIR, median, peak and PRDN stages stay native-only. */
+ * Of the other stages the FIR pre-filter has a planar form too (rspt_hip_fir_prefilter_planar_batch_dev below); the zero-phase
+ * IIR, median, peak and PRDN stages stay native-only. */
 int rspt_hip_iir_prefilter_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
                                             size_t nr_coefficients, int init_nr_samples, int per_channel, void* stream);
 int rspt_hip_iir_prefilter_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
@@ -555,6 +556,45 @@ int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void
 int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes); /* 8 + ((K - 1) * nch * bps rounded up to 8) */
 int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
                                       void* d_state, void* stream);
+
+/* ---- the FIR pre-filter on the planar int32 matrix: i_filter::new_fir where the reference runs it ----------------------
+ * The other factory of the reference's filter interface on the matrix of the converters (see the planar IIR entries above):
+ * rspt_hip_fir_prefilter_batch_dev / _stream_dev with the matrix in place of the native blocks, so that
+ * native_to_i32 -> FIR -> compress_planar runs without leaving it.  kernel, kernel_size, the arithmetic, the truncation and the
+ * ordering contract are the native entries'.
+ *   d_src, d_dst    the matrix [nblocks][nch][ns], block b's channel c at d + (b*nch + c)*ns; 4-byte alignment is all it needs
+ *                   (16-byte aligned buffers with ns a multiple of 4 take wider loads and stores).  d_dst == d_src filters in
+ *                   place; any other overlap of the two nblocks*nch*ns*4-byte ranges is RSPT_HIP_ERR_ARG; out of place d_src is
+ *                   only read.
+ *   samples         the WHOLE int32 value is the sample: the handle's bps and byte order have no effect, and the result
+ *                   (int32_t)y (every NaN, +-inf and |y| >= 2^31 -> INT32_MIN) is stored whole and NOT cut to bps.  So
+ *                   i32_to_native(fir_planar(native_to_i32(X))) == fir_native(X) for every bps, and
+ *                   compress_planar(fir_planar(native_to_i32(X))) gives the streams of compress(fir_native(X)).
+ *   stream          the blocks of a call are consecutive pieces of one recording: channel c's run is P[0][c][:], P[1][c][:], ...
+ *                   and continues into the next call on the same state.  A window near the start of a block reaches into the
+ *                   blocks before it and, behind the call's first block, into the state.
+ *   d_state         caller-owned, 8-byte aligned, rspt_hip_fir_planar_state_bytes(p, kernel_size) bytes: uint64 started, then the
+ *                   last K - 1 input rows of the recording, oldest first, each row nch int32 values, padded to a multiple of 8
+ *                   bytes -- the native state's layout at bps = 4.  On a handle with bps = 4 the two sizes are equal and native
+ *                   and planar stream calls may alternate on one state; on a narrower handle a planar state is its own object,
+ *                   not interchangeable with the native one.  All-zero bytes are a fresh object (X[s < 0] = the channel's first
+ *                   sample ever).  K - 1 may exceed ns and may exceed a whole call; the kernel's VALUES may change between
+ *                   calls, its size may not; two states may be used in turn on one handle.
+ * RSPT_HIP_ERR_ARG for a NULL handle, buffer or kernel, a NULL bytes, nblocks = 0, nblocks * nch >= 2^31, kernel_size outside
+ * 1..65536, a matrix off its 4-byte alignment, buffers that overlap without being the same, a NULL or misaligned d_state;
+ * RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels, a stream call of 2^31 - 2^17 rows (nblocks * ns) or more, and a
+ * stateless call on rows of that many samples.  Refusals come before anything is launched, and a refused call writes nothing.
+ * Asynchronous on `stream`.  What a call stages belongs to the handle and only grows: with span = the samples one workgroup
+ * takes of a row and nsplit = ceil(ns / span), the K - 1 samples in front of every span but the first of an
+ * in-place call and in front of every row of a stream call,
+ *     4 * (K - 1) * nblocks * nch * ((in place ? nsplit - 1 : 0) + (stream ? 1 : 0))  bytes,
+ * plus 4 * (K - 1) * nch bytes of a stream call's old state.  nsplit is 1 unless the batch has fewer row groups than four per
+ * CU, and a span is at least 4 (K - 1) samples then.  A stateless out-of-place call stages nothing. */
+int rspt_hip_fir_prefilter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel,
+                                            size_t kernel_size, void* stream);
+int rspt_hip_fir_planar_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes); /* 8 + ((K - 1) * nch * 4 rounded up to 8) */
+int rspt_hip_fir_prefilter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel,
+                                             size_t kernel_size, void* d_state, void* stream);
 
 /* ---- optional stage in front of compress: the reference's rolling-window median -------------------------------
  * rolling_window_median<double>(window) (lib_rspt/lib_stat/rolling_window_median.h), one fresh object per channel of every

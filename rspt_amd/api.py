@@ -82,6 +82,9 @@ C_ABI = {
     "rspt_hip_fir_prefilter_batch_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p]),
     "rspt_hip_fir_state_bytes": (_i, [_p, _z, _szp]),
     "rspt_hip_fir_prefilter_stream_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p, _p]),
+    "rspt_hip_fir_prefilter_planar_batch_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p]),
+    "rspt_hip_fir_planar_state_bytes": (_i, [_p, _z, _szp]),
+    "rspt_hip_fir_prefilter_planar_stream_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p, _p]),
     "rspt_hip_median_filter_batch_dev": (_i, [_p, _p, _p, _z, _z, _p]),
     "rspt_hip_median_state_bytes": (_i, [_p, _z, _szp]),
     "rspt_hip_median_filter_stream_dev": (_i, [_p, _p, _p, _z, _z, _p, _p]),
@@ -595,6 +598,33 @@ class SignalPacker:
             self._call("rspt_hip_fir_prefilter_stream_dev", d_src.data_ptr(), out.data_ptr(), nblocks, _dptr(k), k.size, state.data_ptr(), st)
         else:
             self._call("rspt_hip_fir_prefilter_batch_dev", d_src.data_ptr(), out.data_ptr(), nblocks, _dptr(k), k.size, st)
+        return out
+
+    def fir_planar_state_bytes(self, kernel_size):
+        return self._bytes("rspt_hip_fir_planar_state_bytes", int(kernel_size))
+
+    def fir_planar_state(self, kernel_size, device=None):
+        """A zeroed state for fir_prefilter_planar_batch(state=...) with a kernel of kernel_size taps: rows of nch int32, so the
+        native fir_state() only where the handle's bps is 4."""
+        return self._zero_state(self.fir_planar_state_bytes(kernel_size), device)
+
+    def fir_prefilter_planar_batch(self, d_planar, kernel, d_out=None, stream=None, state=None):
+        """fir_prefilter_batch on samples that live in int32 (rspt_hip.h: rspt_hip_fir_prefilter_planar_batch_dev / _stream_dev):
+        d_planar is a torch.int32 cuda tensor [nblocks, nch, ns]; in place when d_out is None, else into d_out (same shape, not
+        overlapping d_planar).  The whole int32 value is the sample and the result is stored whole, whatever the handle's bps.
+        Returns the output.  state: None, or a fir_planar_state(len(kernel)) tensor, as in fir_prefilter_batch."""
+        import torch
+
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        out = d_planar if d_out is None else d_out
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == d_planar.numel()
+        st = self._stream(stream, d_planar.device)
+        k = np.ascontiguousarray(kernel, dtype=np.float64).reshape(-1)
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.fir_planar_state_bytes(k.size)
+            self._call("rspt_hip_fir_prefilter_planar_stream_dev", d_planar.data_ptr(), out.data_ptr(), nblocks, _dptr(k), k.size, state.data_ptr(), st)
+        else:
+            self._call("rspt_hip_fir_prefilter_planar_batch_dev", d_planar.data_ptr(), out.data_ptr(), nblocks, _dptr(k), k.size, st)
         return out
 
     def median_state_bytes(self, window):

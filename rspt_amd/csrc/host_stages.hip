@@ -425,7 +425,34 @@ static hipError_t launch_fir_carry(const WinGeom& f, const void* d_src, uint8_t*
     return hipGetLastError();
 }
 
-// Both FIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+// What every FIR call does before it enqueues: grow the handle's staging buffers (`halo`, `head`) behind the stage's earlier
+// calls, and copy the coefficients into the next slot -- the host waits only when kSlots calls are still ahead on the device.
+// From RSPT_HIP_OK on every path of the caller ends in finish_window_call on (*slot)->last: the copy that the caller enqueues
+// reads the page-locked slot.
+static int fir_take_slot(rspt_hip_packer* p, const double* kernel, size_t kernel_size, uint64_t halo_bytes, uint64_t head_bytes,
+                         FirStage::CoefSlot** slot) {
+    FirStage& fs = p->fir;
+    if (halo_bytes > fs.halo.cap || head_bytes > fs.head.cap) {
+        fs.wait_all();  // (no earlier call may still read a buffer being replaced)
+        if (halo_bytes > fs.halo.cap && fs.halo.grow(halo_bytes)) return RSPT_HIP_ERR_ALLOC;
+        if (head_bytes > fs.head.cap && fs.head.grow(head_bytes)) return RSPT_HIP_ERR_ALLOC;
+    }
+    FirStage::CoefSlot& cs = fs.slot[fs.next];
+    HIPCHK(p, cs.last.wait());
+    if (cs.cap < kernel_size) {
+        cs.cap = 0;
+        if (hipHostMalloc((void**)cs.host.out(), kernel_size * sizeof(double), hipHostMallocDefault) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        if (hipMalloc(cs.dev.out(), kernel_size * sizeof(double)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
+        cs.cap = kernel_size;
+    }
+    if (!cs.last.make_event()) return RSPT_HIP_ERR_ALLOC;
+    memcpy(cs.host, kernel, kernel_size * sizeof(double));
+    fs.next = (fs.next + 1) % FirStage::kSlots;
+    *slot = &cs;
+    return RSPT_HIP_OK;
+}
+
+// Both native FIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
 static int fir_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size, void* d_state,
                     void* stream) {
     if (!kernel || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
@@ -439,24 +466,9 @@ static int fir_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t n
     const uint64_t pieces = halo_pieces(f, nblocks, in_place);
     const uint64_t halo_bytes = pieces * (uint64_t)(kernel_size - 1) * f.stride;
     const uint64_t head_bytes = d_state ? (uint64_t)(kernel_size - 1) * f.stride : 0;
-    if (halo_bytes > fs.halo.cap || head_bytes > fs.head.cap) {
-        fs.wait_all();  // (no earlier call may still read a buffer being replaced)
-        if (halo_bytes > fs.halo.cap && fs.halo.grow(halo_bytes)) return RSPT_HIP_ERR_ALLOC;
-        if (head_bytes > fs.head.cap && fs.head.grow(head_bytes)) return RSPT_HIP_ERR_ALLOC;
-    }
-    // the coefficients: the host waits only when kSlots calls are still ahead on the device
-    FirStage::CoefSlot& cs = fs.slot[fs.next];
-    HIPCHK(p, cs.last.wait());
-    if (cs.cap < kernel_size) {
-        cs.cap = 0;
-        if (hipHostMalloc((void**)cs.host.out(), kernel_size * sizeof(double), hipHostMallocDefault) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        if (hipMalloc(cs.dev.out(), kernel_size * sizeof(double)) != hipSuccess) return RSPT_HIP_ERR_ALLOC;
-        cs.cap = kernel_size;
-    }
-    if (!cs.last.make_event()) return RSPT_HIP_ERR_ALLOC;
-    memcpy(cs.host, kernel, kernel_size * sizeof(double));
-    fs.next = (fs.next + 1) % FirStage::kSlots;
-    // (from here on every path ends in finish_window_call, which records `last`: the copy below reads the page-locked slot)
+    FirStage::CoefSlot* slot;
+    if (int rc = fir_take_slot(p, kernel, kernel_size, halo_bytes, head_bytes, &slot)) return rc;
+    FirStage::CoefSlot& cs = *slot;
     hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_state) e = launch_fir_carry(f, d_src, fs.head, d_state, st);
     if (e == hipSuccess && pieces) e = launch_halo(f, d_src, fs.halo, pieces, st);
@@ -486,6 +498,108 @@ int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, voi
                                       void* d_state, void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
     return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
+}
+
+// ---- FIR pre-filter on the planar int32 matrix (fir_planar.hip) ----
+// The decomposition of a sliding-window stage on the matrix (PlanarWin): a row = (block, channel) of ns samples, `lanes` lanes of
+// `run` outputs along it -- the smallest power of two that covers the row, at most `threads` --, threads / lanes rows to a
+// workgroup, and, as in win_geom, spans along the row until there are about four workgroups per CU, each span at least
+// 4 (K - 1) samples and a multiple of the chunk.  Only rows of more than one chunk are ever split.
+static PlanarWin planar_win(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, bool in_place, bool carried) {
+    const Geom& g = p->g;
+    PlanarWin f{};
+    f.rows = (uint64_t)nblocks * g.nch;
+    f.total = f.rows * g.ns;
+    f.nch = g.nch;
+    f.ns = g.ns;
+    f.K = K;
+    const uint64_t runs = ((uint64_t)g.ns + run - 1) / run;
+    f.lanes = 1;
+    while (f.lanes < threads && f.lanes < runs) f.lanes *= 2;
+    f.rpw = threads / f.lanes;
+    const uint32_t C = f.lanes * run;
+    const uint64_t groups = (f.rows + f.rpw - 1) / f.rpw;
+    const uint64_t want = 4ull * (uint64_t)p->num_cu;
+    uint64_t nsplit = groups >= want ? 1 : (want + groups - 1) / groups;
+    const uint64_t min_span = K > 1 ? 4ull * (K - 1) : 1;
+    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
+    nsplit = nsplit > max_split ? max_split : nsplit;
+    nsplit = nsplit < 1 ? 1 : nsplit;
+    const uint64_t span = (((uint64_t)g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
+    f.span = (uint32_t)span;
+    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
+    f.units = groups * f.nsplit;
+    f.in_place = in_place;
+    f.carried = carried;
+    f.npiece = (in_place ? f.nsplit - 1 : 0u) + (carried ? 1u : 0u);
+    return f;
+}
+
+// Both planar FIR entries: d_state == NULL is the stateless call, else the blocks are consecutive pieces of one recording behind
+// the state.  The handle's `halo` holds the fronts (4 (K - 1) nblocks nch npiece bytes), `head` the staged state (4 (K - 1) nch).
+static int fir_planar_call(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
+                           void* d_state, void* stream) {
+    if (!p || !d_src || !d_dst || !kernel || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    if (s0 % 4 || d0 % 4) return RSPT_HIP_ERR_ARG;
+    const uint64_t bytes = (uint64_t)nblocks * p->g.nch * p->g.ns * 4u;
+    const bool in_place = s0 == d0;
+    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    // a row's samples, and a carried call's run, are indexed in 32 bits with a chunk's reach beyond the last one
+    if ((d_state ? (uint64_t)nblocks * p->g.ns : (uint64_t)p->g.ns) >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    const uint32_t K = (uint32_t)kernel_size;
+    const PlanarWin f = planar_win(p, nblocks, K, kFirThreads, kFirR, in_place, d_state != nullptr);
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    FirStage& fs = p->fir;
+    const uint64_t front_n = f.rows * f.npiece * (uint64_t)(K - 1);     // samples of all fronts
+    const uint64_t head_n = d_state ? (uint64_t)(K - 1) * f.nch : 0;  // samples of the head
+    FirStage::CoefSlot* slot;
+    if (int rc = fir_take_slot(p, kernel, kernel_size, front_n * 4u, head_n * 4u, &slot)) return rc;
+    FirStage::CoefSlot& cs = *slot;
+    int32_t* head = reinterpret_cast<int32_t*>((uint8_t*)fs.head);
+    int32_t* front = reinterpret_cast<int32_t*>((uint8_t*)fs.halo);
+    auto mover_grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096)); };
+    hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_state) {
+        uint64_t* started = (uint64_t*)d_state;
+        int32_t* rows = reinterpret_cast<int32_t*>((uint8_t*)d_state + 8);
+        if (head_n) hipLaunchKernelGGL(k_firp_head, mover_grid(head_n), dim3(256), 0, st, d_src, head, started, rows, head_n, f.nch, f.ns);
+        hipLaunchKernelGGL(k_firp_save, mover_grid(head_n), dim3(256), 0, st, d_src, head, started, rows, head_n, f.nch, f.ns, K,
+                           (uint64_t)nblocks * f.ns);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && front_n) {
+        hipLaunchKernelGGL(k_firp_front, mover_grid(front_n), dim3(256), 0, st, d_src, head, front, f);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+        const bool wide = s0 % 16 == 0 && d0 % 16 == 0 && f.ns % 4 == 0;
+        if (wide) hipLaunchKernelGGL(k_fir_planar<true>, dim3(grid), dim3(kFirThreads), 0, st, d_src, d_dst, front, cs.dev, f);
+        else hipLaunchKernelGGL(k_fir_planar<false>, dim3(grid), dim3(kFirThreads), 0, st, d_src, d_dst, front, cs.dev, f);
+        e = hipGetLastError();
+    }
+    return finish_window_call(p, cs.last, e, st);
+}
+
+int rspt_hip_fir_prefilter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel,
+                                            size_t kernel_size, void* stream) {
+    return fir_planar_call(p, d_src, d_dst, nblocks, kernel, kernel_size, nullptr, stream);
+}
+
+int rspt_hip_fir_planar_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) {
+    if (!p || !bytes || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
+    *bytes = 8 + (((size_t)(kernel_size - 1) * p->g.nch * 4u + 7) & ~(size_t)7);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_fir_prefilter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel,
+                                             size_t kernel_size, void* d_state, void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return fir_planar_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
 }
 
 // ---- rolling median (median.hip) ----

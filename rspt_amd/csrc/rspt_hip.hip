@@ -38,6 +38,7 @@
 #include "iir_cascade.hip"
 #include "iir_zero_phase.hip"
 #include "fir.hip"
+#include "fir_planar.hip"
 #include "median.hip"
 #include "peak.hip"
 #include "quality.hip"
