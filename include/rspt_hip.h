@@ -773,6 +773,40 @@ int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src
 int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, double* d_prdn, double* d_mse,
                             double* d_ref, uint32_t* d_path, void* stream);
 
+/* ---- PRDN on the planar int32 matrix ---------------------------------------------------------------------------------
+ * The same figure on two [nblocks][nch][ns] int32 matrices, the form the reference itself computes it on (orig.d2d[j][i] and
+ * enc.d2d[j][i] are rows of two tensor_i32, rspt_test.cpp:98-111).  One identity with the native entry is the contract:
+ *     prdn_planar(O, D) == rspt_hip_prdn_batch_dev on a little-endian bps = 4 handle of the same (nch, ns), given
+ *     i32_to_native(O) and i32_to_native(D)
+ * in d_prdn, d_mse, d_ref and d_path, bit for bit.  The arithmetic text of rspt_hip_prdn_batch_dev applies word for word: the
+ * UNSIGNED division of the mean, t and r that WRAP, the 2^53 conditions of the exact-integer path and the sequential path behind
+ * them, every NaN stored as 0xFFF8000000000000, -0.0 under a negative ref.
+ *   sample value    the whole int32 is the sample, as in the planar IIR and FIR entries: the handle supplies (nch, ns) and
+ *                   nothing else; its bps and byte order have no effect.  On a handle of bps < 4 whose values lie inside the
+ *                   sample width the result equals the native entry's on rspt_hip_i32_to_native_batch_dev of the two matrices
+ *   d_orig, d_dec   block b's channel c at base + (b * nch + c) * ns; only read; may be the same buffer.  Both must be 4-byte
+ *                   aligned (else RSPT_HIP_ERR_ARG); each may sit at any 4-byte offset of its own.  Rows are read with 16-byte
+ *                   loads between a head and a tail of up to three samples (a row starts on a 16-byte boundary only where the
+ *                   base does and ns % 4 == 0); d_dec is read at d_orig's sample positions, so its loads are 16-byte aligned
+ *                   too where the two bases are congruent modulo 16
+ *   d_prdn          [nblocks] doubles; required
+ *   d_mse, d_ref, d_path   optional (NULL), as in rspt_hip_prdn_batch_dev
+ * There is no 8191-channel cap: that is the native tile's, which this entry never touches; every channel count a handle can
+ * have (65535) works.  The scratch is the native entry's (part of the workspace that rspt_hip_reserve sizes; nothing is
+ * allocated per call), so native and planar calls may alternate on one handle.
+ * Two forms, picked by the host (the constants are quality_planar.hip's): rows of up to 1024 samples take a wave
+ * each, longer rows a workgroup; where a call has at least 1024 workgroups of whole rows of at most 8192 samples, a row's owner
+ * takes the sum, the mean and the terms in one go (the row stays in registers up to 4096 samples, is read twice above); else a
+ * pass of row sums and a pass of terms over spans of rows, three reads of the batch.  Measured on an MI355X
+ * (tools/prdn_planar_bench.py, profiles/prdn_planar_bench.json): 64 x (64 ch x 65536) 0.552 ms (the native entry on the same
+ * values 0.546, from_planar_i32 x 2 + the native entry 1.342); 1024 x (12 ch x 8192) 0.181 ms (0.211, 0.512).
+ * RSPT_HIP_ERR_ARG for a NULL handle, d_orig, d_dec or d_prdn, nblocks == 0, nblocks * nch >= 2^31, a handle with an open feed,
+ * a misaligned d_orig or d_dec, and a RSPT_HIP_KIND_BYTES handle (as the planar packer entries); more than 65535 blocks are
+ * refused as by rspt_hip_reserve.  A refused call writes nothing.  Asynchronous on `stream`, with the ordering contract of
+ * rspt_hip_compress_batch_dev: stream-ordered with every other call on the handle. */
+int rspt_hip_prdn_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_orig, const int32_t* d_dec, size_t nblocks, double* d_prdn,
+                                   double* d_mse, double* d_ref, uint32_t* d_path, void* stream);
+
 /* ---- native <-> planar int32: the reference's convert_native_to_i32 / convert_i32_to_native as stages ---------------
  * What every program of the reference runs first and last (lib_signalpacker/utils.cpp:51-191; rspt_test.cpp:62-64, 92-94,
  * 119-135): the interleaved native block <-> a [channels][samples] int32 matrix, on nblocks device-resident blocks.

@@ -94,6 +94,7 @@ C_ABI = {
     "rspt_hip_peak_offline_work_bytes": (_i, [_p, _z, _i, _szp]),
     "rspt_hip_peak_detect_offline_batch_dev": (_i, [_p, _p, _z, _d, _d, _p, _p, _p, _p, _p, _z, _p, _p, _p]),
     "rspt_hip_prdn_batch_dev": (_i, [_p, _p, _p, _z, _p, _p, _p, _p, _p]),
+    "rspt_hip_prdn_planar_batch_dev": (_i, [_p, _p, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_native_to_i32_batch_dev": (_i, [_p, _p, _p, _z, _p]),
     "rspt_hip_i32_to_native_batch_dev": (_i, [_p, _p, _p, _z, _p]),
     "rspt_hip_stream": (_p, [_p]),
@@ -723,6 +724,12 @@ class SignalPacker:
 
         nblocks = self._nblocks(d_orig)
         assert self._nblocks(d_dec) == nblocks
+        return self._prdn("rspt_hip_prdn_batch_dev", d_orig, d_dec, nblocks, stream, parts)
+
+    def _prdn(self, entry, d_orig, d_dec, nblocks, stream, parts):
+        """both layouts of the PRDN stage: the outputs and the call"""
+        import torch
+
         dev = d_orig.device
         prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
         mse = ref = path = None
@@ -730,9 +737,20 @@ class SignalPacker:
             mse, ref = torch.empty_like(prdn), torch.empty_like(prdn)
             path = torch.empty(nblocks, dtype=torch.int32, device=dev)
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._call("rspt_hip_prdn_batch_dev", d_orig.data_ptr() if nblocks else None, d_dec.data_ptr() if nblocks else None, nblocks,
+        self._call(entry, d_orig.data_ptr() if nblocks else None, d_dec.data_ptr() if nblocks else None, nblocks,
                    prdn.data_ptr() if nblocks else None, ptr(mse), ptr(ref), ptr(path), self._stream(stream, dev))
         return (prdn, mse, ref, path) if parts else prdn
+
+    def prdn_planar_batch(self, d_orig, d_dec, stream=None, parts=False):
+        """prdn_batch on samples that live in int32 (rspt_hip.h: rspt_hip_prdn_planar_batch_dev): d_orig and d_dec are torch.int32
+        cuda tensors [nblocks, nch, ns], only read (they may be one tensor).  The whole int32 value is the sample, whatever the
+        handle's bps and byte order: the figure is prdn_batch's on a little-endian bps = 4 handle of the same (nch, ns) given
+        from_planar_i32 of the two.  No channel cap.  Asynchronous.  Returns what prdn_batch returns."""
+        import torch
+
+        nblocks = self._nblocks(d_orig, torch.int32, self.nch * self.ns)
+        assert self._nblocks(d_dec, torch.int32, self.nch * self.ns) == nblocks
+        return self._prdn("rspt_hip_prdn_planar_batch_dev", d_orig, d_dec, nblocks, stream, parts)
 
     def to_planar_i32(self, d_src, d_out=None, stream=None):
         """The reference's convert_native_to_i32 (utils.cpp:123-191; rspt_hip.h: rspt_hip_native_to_i32_batch_dev) on
@@ -773,15 +791,36 @@ class SignalPacker:
         d_dst, d_sizes = self.compress_batch(d_src, stream=stream)
         d_out, d_consumed = self.decompress_batch(d_dst, nblocks, d_dst.shape[1], stream=stream)
         prdn = self.prdn_batch(d_src.reshape(-1), d_out.reshape(-1), stream=stream)
-        ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream, device=d_src.device)) if stream is not None else None
-        if ctx is not None:
-            with ctx:
-                cr = float(self.block_bytes) / d_consumed.to(torch.float64)
-            for t in (d_dst, d_sizes, d_out, d_consumed):  # (back to torch's pool only once the caller's stream is past them)
-                t.record_stream(torch.cuda.ExternalStream(stream, device=d_src.device))
-        else:
+        return prdn, self._cr_behind(d_src.device, stream, d_consumed, (d_dst, d_sizes, d_out, d_consumed))
+
+    def _cr_behind(self, device, stream, d_consumed, temporaries):
+        """block_bytes / consumed size on the call's stream; the round trip's temporaries go back to torch's pool only once the
+        caller's stream is past them"""
+        import torch
+
+        if stream is None:
+            return float(self.block_bytes) / d_consumed.to(torch.float64)
+        ext = torch.cuda.ExternalStream(stream, device=device)
+        with torch.cuda.stream(ext):
             cr = float(self.block_bytes) / d_consumed.to(torch.float64)
-        return prdn, cr
+        for t in temporaries:
+            t.record_stream(ext)
+        return cr
+
+    def roundtrip_quality_planar(self, d_planar, stream=None):
+        """roundtrip_quality for samples that live in int32: compress_planar_batch -> decompress_planar_batch ->
+        prdn_planar_batch on one stream with no host synchronisation in between; d_planar is a torch.int32 cuda tensor
+        [nblocks, nch, ns], only read.  Returns (prdn, cr) as roundtrip_quality does.  PRDN is taken against the matrix AS GIVEN:
+        on a handle of bps < 4, values outside the sample width are cut by the packer but not by PRDN, which reads the whole
+        int32.  That differs from the reference's test_packer_, which converts from native first; for values inside the sample
+        width it is test_packer_ exactly, and equals roundtrip_quality(from_planar_i32(d_planar))."""
+        import torch
+
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        d_dst, d_sizes = self.compress_planar_batch(d_planar, stream=stream)
+        d_out, d_consumed = self.decompress_planar_batch(d_dst, nblocks, d_dst.shape[1], stream=stream)
+        prdn = self.prdn_planar_batch(d_planar, d_out, stream=stream)
+        return prdn, self._cr_behind(d_planar.device, stream, d_consumed, (d_dst, d_sizes, d_out, d_consumed))
 
     def synchronize(self):
         self._check("rspt_hip_synchronize", self._L.rspt_hip_synchronize(self._h))

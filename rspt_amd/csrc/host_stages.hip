@@ -859,6 +859,62 @@ int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* 
     return RSPT_HIP_OK;
 }
 
+// ---- PRDN on the planar int32 matrix (quality_planar.hip) -------------------------------------------------------------------------
+// whole_rows: a unit is a whole row (k_qp_rows); else rows longer than a wave's are cut into spans of whole sweeps while the call
+// has fewer than kQpUnits units and a span keeps kQpMinSweeps sweeps.
+static QPGeom quality_planar_geom(const Geom& g, size_t nblocks, bool whole_rows) {
+    QPGeom q{};
+    q.rows = (uint64_t)nblocks * g.nch;
+    q.nch = g.nch, q.ns = g.ns;
+    q.lanes = g.ns <= kQpWaveRow ? (uint32_t)kWave : kQpThreads;
+    q.span = g.ns, q.nsplit = 1;
+    if (q.lanes == kQpThreads && !whole_rows) {
+        const uint64_t sweeps = ((uint64_t)g.ns + kQpSweep - 1) / kQpSweep;
+        const uint64_t nsplit = std::min<uint64_t>(std::max<uint64_t>(1, sweeps / kQpMinSweeps), (kQpUnits + q.rows - 1) / q.rows);
+        const uint64_t span = (sweeps + nsplit - 1) / nsplit * kQpSweep;  // (at most ns rounded up to a sweep: below 2^32)
+        if (span < g.ns) q.span = (uint32_t)span, q.nsplit = (uint32_t)(((uint64_t)g.ns + span - 1) / span);
+    }
+    return q;
+}
+static uint64_t quality_planar_units(const QPGeom& q) { return q.lanes == (uint32_t)kWave ? (q.rows + kQpWaves - 1) / kQpWaves : q.rows * q.nsplit; }
+
+int rspt_hip_prdn_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_orig, const int32_t* d_dec, size_t nblocks, double* d_prdn, double* d_mse,
+                                   double* d_ref, uint32_t* d_path, void* stream) {
+    if (!p || !d_orig || !d_dec || !d_prdn || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (p->g.kind == RSPT_HIP_KIND_BYTES) return RSPT_HIP_ERR_ARG;  // (a byte buffer has no samples)
+    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_orig), d0 = reinterpret_cast<uintptr_t>(d_dec);
+    if ((o0 | d0) & 3u) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    QPGeom q = quality_planar_geom(g, nblocks, true);
+    bool fused = quality_planar_units(q) >= kQpFusedMinUnits && g.ns <= kQpFusedMaxNs;
+    if (p->qp_form) fused = p->qp_form == 2;
+    if (!fused) q = quality_planar_geom(g, nblocks, false);
+    const uint64_t units = quality_planar_units(q);  // (below 2^31: at most the rows of the call, or about kQpUnits where rows are cut)
+    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t B = (uint32_t)nblocks;
+    unsigned long long* sums = p->ws.quality;  // (the native entry's scratch, laid out as there)
+    unsigned long long* acc = sums + (size_t)B * g.nch;
+    uint32_t* flag = reinterpret_cast<uint32_t*>(acc + (size_t)B * 4);
+    HIPCHK(p, hipMemsetAsync(sums, 0, ((size_t)B * g.nch + (size_t)B * 4) * sizeof(unsigned long long), st));
+    const dim3 grid((uint32_t)units), wg(kQpThreads);
+    if (fused) {
+        if (g.ns <= (q.lanes == (uint32_t)kWave ? kQpWaveRow : kQpRowRegs))
+            hipLaunchKernelGGL(k_qp_rows<true>, grid, wg, 0, st, d_orig, d_dec, q, (long long*)sums, acc);
+        else hipLaunchKernelGGL(k_qp_rows<false>, grid, wg, 0, st, d_orig, d_dec, q, (long long*)sums, acc);
+    } else {
+        hipLaunchKernelGGL(k_qp_sums, grid, wg, 0, st, d_orig, q, sums);
+        hipLaunchKernelGGL(k_qp_accum, grid, wg, 0, st, d_orig, d_dec, q, (const long long*)sums, acc);
+    }
+    hipLaunchKernelGGL(k_q_finish, dim3((B + 255) / 256), dim3(256), 0, st, (const unsigned long long*)acc, B, flag, d_prdn, d_mse, d_ref, d_path);
+    hipLaunchKernelGGL(k_qp_seq, dim3(B), dim3(kQThreads), 0, st, d_orig, d_dec, g.nch, g.ns, (const long long*)sums, (const unsigned long long*)acc,
+                       (const uint32_t*)flag, d_prdn, d_mse, d_ref);
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
 // ---- native <-> planar int32 (the reference's convert_native_to_i32 / convert_i32_to_native, utils.cpp:51-191) -------------------
 // The checks of both entries.  Nothing of the handle but its shape and byte order is used: no workspace, no allocation.
 static int convert_checks(const rspt_hip_packer* p, const void* d_native, const void* d_planar, size_t nblocks) {

@@ -42,6 +42,7 @@
 #include "median.hip"
 #include "peak.hip"
 #include "quality.hip"
+#include "quality_planar.hip"
 #include "convert.hip"
 #include "bytes.hip"
 #include "planar.hip"
@@ -431,6 +432,7 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
     if (const char* e = getenv("RSPT_K1_GRID")) p->k1_grid = (uint32_t)atoi(e);
     if (const char* e = getenv("RSPT_HIST_GRID")) p->hist_grid = (uint32_t)atoi(e);
     if (const char* e = getenv("RSPT_ENC_GRID")) p->enc_grid = (uint32_t)atoi(e);
+    if (const char* e = getenv("RSPT_QP_FORM")) p->qp_form = (uint32_t)atoi(e);
 #endif
     if (p->k1_threads < 64 || p->k1_threads > 256) p->k1_threads = 256;  // (k_tile_planes is compiled for <= 256)
     p->ntile = (g.N + kInvTile - 1) / kInvTile;
