@@ -45,7 +45,7 @@ __device__ __forceinline__ uint32_t granule_byte_dyn(uint32_t w0, uint32_t w1, u
     return __builtin_amdgcn_perm(hi, lo, 0x0C0C0C00u | (i & 7u));  // byte (i & 7) of {hi,lo}, zero-extended
 }
 
-// "Small" hzr blocks -- few non-zero 4 KiB segments -- are walked by ONE wave, row by row, instead of
+// "Small" hzr blocks -- few non-zero 4 KiB segments -- are tokenized by ONE wave, segment by segment, instead of
 // by a 1024-thread workgroup: their histogram is taken inside k_tree (k_hist skips them) and, if they
 // also have few tokens and a small payload, the same wave encodes them right there (kModeStaged).
 // Clean-block invariant (rspt_hip_packer::plane_dirty): a Huffman block with at most this many tokens has its non-zero
@@ -88,16 +88,345 @@ __device__ __forceinline__ bool next_work(uint32_t* counter, uint32_t total, con
 constexpr uint32_t kSegHistStride = kEncWaves * kSymStride;  // u16 elements per hzr block (hzr_rows.hip: k_hist)
 
 // ===========================================================================
+// shared: sparse data as entry lists -- the tokenizer of k_hist's sparse segments, of k_encode's sparse rows and of k_tree's
+// small blocks, and the emit from such entries (k_encode's list blocks, k_tree's staged blocks)
+// ===========================================================================
+constexpr uint32_t kRunClsEntries = 280;  // lengths 0..278 and ">= 279" (hzr_internal.h:117-121)
+__device__ __forceinline__ uint32_t run_class_entry(uint32_t z) {
+    const uint32_t sym = run_symbol(z);
+    const uint32_t base = sym == 257 ? 3u : sym == 258 ? 7u : sym == 259 ? 23u : sym == 260 ? 279u : z;  // (runs of 1 and 2: no extra bits, value 0)
+    return sym | (run_extra_bits(sym) << 12) | (base << 16);
+}
+
+// OR a string of `len` <= 64 bits (hi:lo) into the image at bit `pos`.  Two words always; the third only where some lane's
+// string reaches into it -- with the usual four codes of ~5.5 bits per string that is no lane of the wave, and the third
+// atomic with its shifts and address is one instruction in eight of the dense emit (one wave-wide test instead)
+__device__ __forceinline__ void or_bits64(uint32_t* stage, uint32_t pos, uint32_t lo, uint32_t hi, uint32_t len) {
+    const uint32_t word = pos >> 5, sh = pos & 31u;
+    const uint64_t sv = (((uint64_t)hi << 32) | lo) << sh;
+    atomicOr(&stage[word], (uint32_t)sv);
+    atomicOr(&stage[(word + 1)], (uint32_t)(sv >> 32));
+    if (__builtin_amdgcn_ballot_w64(sh + len > 64u)) atomicOr(&stage[(word + 2)], (hi >> 1) >> (31u - sh));
+}
+
+// OR one token (<= 38 bits) into the image at bit `pos`
+__device__ __forceinline__ void or_token(uint32_t* stage, uint32_t pos, uint32_t lo, uint32_t hi, uint32_t len) {
+    const uint32_t word = pos >> 5, sh = pos & 31u;
+    const uint64_t sv = (((uint64_t)hi << 32) | lo) << sh;
+    atomicOr(&stage[word], (uint32_t)sv);
+    atomicOr(&stage[(word + 1)], (uint32_t)(sv >> 32));
+    if (sh + len > 64) atomicOr(&stage[(word + 2)], (hi >> 1) >> (31u - sh));
+}
+
+constexpr uint32_t kQueueEntries = 512;  // entries per wave in the sparse-row queue (8 x 64)
+
+// trailing (highest-address) zero bytes of a granule that is not all zero
+__device__ __forceinline__ uint32_t trail_zero_bytes(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
+    return w3 ? ((uint32_t)__clz((int)w3) >> 3) : w2 ? 4u + ((uint32_t)__clz((int)w2) >> 3) : w1 ? 8u + ((uint32_t)__clz((int)w1) >> 3)
+                                                                                             : 12u + ((uint32_t)__clz((int)w0) >> 3);
+}
+__device__ __forceinline__ uint32_t zero_mask16(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
+    return zero_nibble(w0) | (zero_nibble(w1) << 4) | (zero_nibble(w2) << 8) | (zero_nibble(w3) << 12);
+}
+
+// full kRunCap tokens in a run of R <= 65536 zeros.  Almost never any: the three compares sit behind one wave-wide test.
+__device__ __forceinline__ uint32_t run_caps(uint32_t R) {
+    uint32_t q = 0;
+    if (__builtin_amdgcn_ballot_w64(R >= kRunCap)) q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
+    return q;
+}
+
+__device__ __forceinline__ void hist_run(uint32_t* h, const uint32_t* runcls, uint32_t R) {
+    const uint32_t q = run_caps(R);
+    const uint32_t rem = R - q * kRunCap;
+    if (q) atomicAdd(&h[260], q);
+    if (rem) atomicAdd(&h[runcls[min(rem, kRunClsEntries - 1u)] & 0xFFFu], 1u);
+}
+
+// The code table of the emit helpers is anything that answers tab[index] with {code, length}: k_encode's uint2 table in LDS,
+// or the packed words k_tree keeps (PackedCodes, below).
+
+// the remainder token of a run (0 < rem < 16662) as a bit string
+template <class Tab>
+__device__ __forceinline__ void run_token(Tab tab, const uint32_t* runcls, uint32_t rem, uint64_t& v, uint32_t& len) {
+    const uint32_t e = runcls[min(rem, kRunClsEntries - 1u)];
+    const uint2 cw = tab[e & 0xFFFu];
+    v = (uint64_t)cw.x | ((uint64_t)(rem - (e >> 16)) << cw.y);
+    len = cw.y + ((e >> 12) & 0xFu);
+}
+
+// OR the tokens of a zero run into the image at bit `pos`; returns the bits written
+template <class Tab>
+__device__ __forceinline__ uint32_t emit_run(uint32_t* stage, Tab tab, const uint32_t* runcls, uint32_t pos, uint32_t R) {
+    const uint32_t q = run_caps(R);
+    const uint32_t rem = R - q * kRunCap;
+    uint32_t done = 0;
+    if (q) {
+        const uint2 c = tab[260];
+        const uint64_t v = (uint64_t)c.x | ((uint64_t)(kRunCap - 279u) << c.y);
+        for (uint32_t i = 0; i < q; ++i) {
+            or_token(stage, pos + done, (uint32_t)v, (uint32_t)(v >> 32), c.y + 14u);
+            done += c.y + 14u;
+        }
+    }
+    if (rem) {
+        uint64_t v;
+        uint32_t len;
+        run_token(tab, runcls, rem, v, len);
+        or_token(stage, pos + done, (uint32_t)v, (uint32_t)(v >> 32), len);
+        done += len;
+    }
+    return done;
+}
+
+// what a row needs to know about its surroundings (wave-uniform)
+struct RowCtx {
+    uint32_t zb0;    // zeros immediately before the row's first byte (cut at the block start)
+    uint32_t last;   // 1: the block ends with this row's last valid byte
+    uint32_t valid;  // bytes of this row inside the block (0..1024)
+    uint32_t rb;     // position of the row's first byte in the block
+};
+
+// rotate the rows through W[0] / rc[0]: the row bodies exist once in the instruction stream; four turns put everything back
+__device__ __forceinline__ void rotate_rows(uint32_t (&W)[4][4], RowCtx (&rc)[4]) {
+    const uint32_t t0 = W[0][0], t1 = W[0][1], t2 = W[0][2], t3 = W[0][3];
+    const RowCtx tc = rc[0];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        W[q][0] = W[q + 1][0];
+        W[q][1] = W[q + 1][1];
+        W[q][2] = W[q + 1][2];
+        W[q][3] = W[q + 1][3];
+        rc[q] = rc[q + 1];
+    }
+    W[3][0] = t0;
+    W[3][1] = t1;
+    W[3][2] = t2;
+    W[3][3] = t3;
+    rc[3] = tc;
+}
+
+// Sparse rows: the row's literals, in order, as (position, value) entries in a per-wave queue; the wave then takes the
+// queue 64 entries at a time -- the run in front of a literal is the gap to the entry before it, so nothing has to be
+// chained from lane to lane.  A row that ends the block appends a virtual entry at in_size (the run that reaches the end).
+constexpr uint32_t kNoLit = 0x100u;
+
+// the lane's non-zero bytes (bit i = byte i) -- bytes behind the block end were masked to zero at the load
+__device__ __forceinline__ uint32_t lane_lits(const uint32_t (&w)[4]) { return ~zero_mask16(w[0], w[1], w[2], w[3]) & 0xFFFFu; }
+
+// fills the queue; returns the number of entries (0: nothing ends in this row)
+__device__ __forceinline__ uint32_t sparse_queue(const uint32_t (&w)[4], const RowCtx& rc, uint32_t in_size, uint32_t lits, uint32_t* queue,
+                                                 bool& queued) {
+    const uint32_t l = lane_id();
+    const uint32_t n = (uint32_t)__popc(lits);
+    const uint32_t incl = wave_scan_add(n);
+    const uint32_t T = read_lane(incl, 63) + (rc.last ? 1u : 0u);
+    queued = queue != nullptr && T <= kQueueEntries;
+    if (T == 0 || !queued) return T;
+    uint32_t k = incl - n, t = lits;
+    const uint32_t pos0 = rc.rb + 16u * l;
+    while (t) {
+        const uint32_t i = (uint32_t)__builtin_ctz(t);
+        t &= t - 1;
+        queue[k++] = ((pos0 + i) << 9) | granule_byte_dyn(w[0], w[1], w[2], w[3], i);
+    }
+    if (rc.last && l == 0) queue[T - 1u] = (in_size << 9) | kNoLit;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return T;
+}
+
+// entry k of the queue and the zeros in front of it
+__device__ __forceinline__ void queue_entry(const uint32_t* queue, const RowCtx& rc, uint32_t k, uint32_t T, uint32_t& R, uint32_t& lit) {
+    R = 0;
+    lit = kNoLit;
+    if (k < T) {
+        const uint32_t e = queue[k];
+        const uint32_t before = k ? (queue[k - 1u] >> 9) + 1u : rc.rb - rc.zb0;  // position behind the literal before this one
+        lit = e & 0x1FFu;
+        R = (e >> 9) - before;
+    }
+}
+
+// without a queue: f(R, lit) for the lane's own entries, in stream order (the gap to the literal of a lower lane comes from a scan)
+template <class F>
+__device__ __forceinline__ void lane_entries(const uint32_t (&w)[4], const RowCtx& rc, uint32_t in_size, uint32_t lits, F f) {
+    const uint32_t l = lane_id();
+    const uint32_t pos0 = rc.rb + 16u * l;
+    const uint32_t mine = lits ? pos0 + (32u - (uint32_t)__clz((int)lits)) : 0u;  // position behind this lane's last literal
+    const uint32_t incl = wave_scan_incl(mine, 0u, [](uint32_t a, uint32_t b) { return a > b ? a : b; });
+    uint32_t before = dpp<0x138>(0u, incl);  // wave_shr:1: behind the last literal of the lanes below
+    before = max(l ? before : 0u, rc.rb - rc.zb0);
+    uint32_t t = lits;
+    while (t) {
+        const uint32_t i = (uint32_t)__builtin_ctz(t);
+        t &= t - 1;
+        f(pos0 + i - before, granule_byte_dyn(w[0], w[1], w[2], w[3], i));
+        before = pos0 + i + 1u;
+    }
+    if (rc.last && l == 63u) f(in_size - max(read_lane(incl, 63), rc.rb - rc.zb0), kNoLit);  // the run that reaches the block end
+}
+
+// The entries of a wave's sparse rows, kept for the encoder: a block of k_hist's whose sixteen segments all fit their list is
+// encoded by k_encode from the lists alone -- no second pass over its 64 KiB of mostly zeros (entry lists) -- and a
+// small block of k_tree's from its one list.
+constexpr uint32_t kListCap = 512;             // entries per list (k_hist: per 4 KiB segment; k_tree: per small block)
+constexpr uint32_t kListNone = 0xFFFFFFFFu;    // list info: no list (a dense row, or too many entries)
+struct ListSink {
+    uint32_t* dst;  // this wave's list
+    uint32_t n;     // entries so far, or kListNone
+};
+
+__device__ __forceinline__ void hist_row_sparse(const uint32_t (&w)[4], const RowCtx& rc, uint32_t in_size, uint32_t* h, const uint32_t* runcls,
+                                                uint32_t* queue, ListSink& sink) {
+    if (rc.valid == 0u) return;
+    if (!rc.last && !__ballot((w[0] | w[1] | w[2] | w[3]) != 0u)) return;  // nothing but zeros, and the block goes on: no token ends here
+    const uint32_t lits = lane_lits(w);
+    bool queued;
+    const uint32_t T = sparse_queue(w, rc, in_size, lits, queue, queued);
+    if (T == 0) return;
+    if (queued && sink.n != kListNone && sink.n + T <= kListCap) {
+        for (uint32_t c = lane_id(); c < T; c += 64) sink.dst[sink.n + c] = queue[c];
+        sink.n += T;
+    } else {
+        sink.n = kListNone;
+    }
+    if (queued) {
+        const uint32_t l = lane_id();
+        for (uint32_t c = 0; c < T; c += 64) {
+            uint32_t R, lit;
+            queue_entry(queue, rc, c + l, T, R, lit);
+            if (R) hist_run(h, runcls, R);
+            if (lit < 256u) atomicAdd(&h[lit], 1u);
+        }
+        __builtin_amdgcn_wave_barrier();  // the queue is reused by the next row
+    } else {
+        lane_entries(w, rc, in_size, lits, [&](uint32_t R, uint32_t lit) {
+            if (R) hist_run(h, runcls, R);
+            if (lit < 256u) atomicAdd(&h[lit], 1u);
+        });
+    }
+}
+
+// one entry per lane (R zeros, then the literal unless lit == kNoLit; R = 0 and no literal: nothing), in lane order
+template <class Tab>
+__device__ __forceinline__ void emit_entries(uint32_t R, uint32_t lit, Tab tab, const uint32_t* runcls, uint32_t* stage, uint32_t& base) {
+    const uint32_t q = run_caps(R);
+    const uint32_t rem = R - q * kRunCap;
+    uint64_t rv = 0;
+    uint32_t rl = 0;
+    if (rem) run_token(tab, runcls, rem, rv, rl);
+    const uint2 lc = tab[lit < 256u ? lit : 261u];
+    const uint64_t V = rv | ((uint64_t)lc.x << rl);  // <= 38 + 24 bits
+    const uint32_t vlen = rl + lc.y;
+    const uint32_t caplen = q ? q * (tab[260].y + 14u) : 0u;
+    const uint32_t len = caplen + vlen;
+    const uint32_t inc = wave_scan_add(len);
+    uint32_t pos = base + inc - len;
+    base += read_lane(inc, 63);
+    if (q) pos += emit_run(stage, tab, runcls, pos, q * kRunCap);
+    if (vlen) or_bits64(stage, pos, (uint32_t)V, (uint32_t)(V >> 32), vlen);
+}
+
+// A wave whose four rows are all sparse (the segments of the "medium" blocks: every 4 KiB non-zero, a few literals per row)
+// takes them as ONE queue, and the queue is the segment's entry list as it stands.  Between sparse rows nothing special
+// happens at a row boundary: the zeros in front of a row's first literal are the gap to the entry before it, whichever row
+// that one came from; only entry 0 looks outside the segment (rc[0].zb0).
+//
+// Such a segment rarely holds more than 64 granules that are not all zero (planes 1-2 of the xdelta planes: 16 to 32 of 256 on
+// average, tools/sparse_census.py), so those granules are first compacted into ONE row, in position order: a lane that holds
+// one hands its four words and its block position to lane (granules of the rows before) + (granules of lower lanes of its
+// row), through the wave's own queue words -- five columns of 64 words, read back before the first entry is written there.
+// One lane_lits, one scan and one entry loop then do what took four of each, with most lanes idle in every one of them.
+// Zero granules between compacted neighbours are the position gap, as they are between rows.  False: more than 64 such
+// granules, or too many entries for the queue -- the caller goes row by row (the same entries in the same order; keeping the
+// four-row body beside the compacted one for the first case cost k_hist 16 bytes of scratch).  W is never written here.
+constexpr uint32_t kCompactWords = 5u * 64u;  // the compaction's columns: w0..w3 and the position
+static_assert(kCompactWords <= kQueueEntries, "the compaction's scratch stays inside the wave's own queue slot (k_hist's and k_encode's own-count queues alike)");
+
+__device__ __forceinline__ bool hist_segment_sparse(const uint32_t (&W)[4][4], const RowCtx (&rc)[4], uint32_t in_size, uint32_t* h,
+                                                    const uint32_t* runcls, uint32_t* queue, ListSink& sink) {
+    const uint32_t l = lane_id();
+    const uint32_t last = rc[0].last | rc[1].last | rc[2].last | rc[3].last;  // the block ends in this segment: the run that reaches its end
+    unsigned long long nzg[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) nzg[r] = __ballot((W[r][0] | W[r][1] | W[r][2] | W[r][3]) != 0u);  // (bytes behind the block end were masked to zero at the load)
+    const uint32_t g1 = (uint32_t)__popcll(nzg[0]), g2 = g1 + (uint32_t)__popcll(nzg[1]), g3 = g2 + (uint32_t)__popcll(nzg[2]);
+    const uint32_t ng = g3 + (uint32_t)__popcll(nzg[3]);
+    if (ng > 64u) return false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if ((W[r][0] | W[r][1] | W[r][2] | W[r][3]) != 0u) {
+            const uint32_t s = (r == 0 ? 0u : r == 1 ? g1 : r == 2 ? g2 : g3) +
+                               __builtin_amdgcn_mbcnt_hi((uint32_t)(nzg[r] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nzg[r], 0u));
+            queue[s] = W[r][0];
+            queue[64u + s] = W[r][1];
+            queue[128u + s] = W[r][2];
+            queue[192u + s] = W[r][3];
+            queue[256u + s] = rc[r].rb + 16u * l;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    uint32_t cg[4] = {0u, 0u, 0u, 0u};
+    uint32_t pos0 = 0;
+    if (l < ng) {
+        cg[0] = queue[l];
+        cg[1] = queue[64u + l];
+        cg[2] = queue[128u + l];
+        cg[3] = queue[192u + l];
+        pos0 = queue[256u + l];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();  // every lane holds its granule: the entries may take the same words
+    uint32_t t = lane_lits(cg);
+    const uint32_t n = (uint32_t)__popc(t);
+    const uint32_t inc = wave_scan_add(n);
+    const uint32_t T = read_lane(inc, 63) + (last ? 1u : 0u);
+    if (T > kQueueEntries) return false;
+    if (T == 0) return true;  // nothing but zeros, and the block goes on
+    uint32_t k = inc - n;
+    while (t) {
+        const uint32_t i = (uint32_t)__builtin_ctz(t);
+        t &= t - 1;
+        queue[k++] = ((pos0 + i) << 9) | granule_byte_dyn(cg[0], cg[1], cg[2], cg[3], i);
+    }
+    if (last && l == 0) queue[T - 1u] = (in_size << 9) | kNoLit;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (sink.n != kListNone && sink.n + T <= kListCap) {
+        for (uint32_t c = l; c < T; c += 64) sink.dst[sink.n + c] = queue[c];
+        sink.n += T;
+    } else {
+        sink.n = kListNone;
+    }
+    const uint32_t before0 = rc[0].rb - rc[0].zb0;
+    for (uint32_t c = 0; c < T; c += 64) {
+        const uint32_t k = c + l;
+        if (k < T) {
+            const uint32_t e = queue[k];
+            const uint32_t before = k ? (queue[k - 1u] >> 9) + 1u : before0;  // position behind the literal before this one
+            const uint32_t R = (e >> 9) - before, lit = e & 0x1FFu;
+            if (R) hist_run(h, runcls, R);
+            if (lit < 256u) atomicAdd(&h[lit], 1u);
+        }
+    }
+    __builtin_amdgcn_wave_barrier();  // the queue is reused by the next block
+    return true;
+}
+
+// ===========================================================================
 // k_tree: one wave per hzr block, 4 waves per workgroup
 // ===========================================================================
 constexpr int kTreeWaves = 4;
 constexpr uint32_t kKeyMax = 0xFFFFFFFFu;
 
-// (5084 bytes per tree: eight 4-wave workgroups = 32 trees per CU by LDS; the one-wave encoder of the small blocks takes the
-//  kernel to 65 VGPRs, i.e. seven workgroups = 28 trees in flight per CU.  The kernel is a latency chain per wave -- one dense
-//  tree alone takes 0.045 ms -- so trees in flight are what it lives on; 32 against 24 measured no different: profiles/r03_notes.md 1f.
-//  The small blocks' CRC reads its slice-by-4 tables from global memory: 4 KiB of LDS per workgroup for them meant 24 trees per CU
-//  and measured 0.081 ms against 0.079, profiles/small_blocks_notes.md.)
+// (5084 bytes per tree and 1120 for the workgroup's run-class table: seven 4-wave workgroups = 28 trees per CU by LDS, and the
+//  same seven by registers -- 67 VGPRs with the small blocks' tokenizer and encoder, held there by the launch bound (89 and five
+//  workgroups without it).  The kernel
+//  is a latency chain per wave -- one dense tree alone takes 0.045 ms -- so trees in flight are what it lives on; 32 against 24
+//  measured no different: profiles/r03_notes.md 1f.  The small blocks' CRC reads its shift tables from global memory: 4 KiB of
+//  LDS per workgroup for CRC tables meant 24 trees per CU and measured 0.081 ms against 0.079, profiles/small_blocks_notes.md.)
 struct TreeLds {
     uint32_t key[kSymStride];     // leaf keys: count<<10 | (1023 - index); index order = creation order
     uint32_t lcnt[kNumSym];       // leaves in the subtree of each node, two u16 counts per word (LDS per wave decides how many
@@ -108,78 +437,6 @@ struct TreeLds {
     uint32_t tdesc[kTdescWords];
     __device__ __forceinline__ uint32_t* lhist() { return up; }
 };
-
-// add the tokens of a zero run of length R to a histogram (same split as run_bits / run_emit)
-__device__ __forceinline__ void run_count(uint32_t* h, uint32_t R) {
-    const uint32_t q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
-    const uint32_t rem = R - q * kRunCap;
-    if (q) atomicAdd(&h[260], q);
-    if (rem) atomicAdd(&h[run_symbol(rem)], 1u);
-}
-
-// token histogram of a small block by one wave (zero runs are counted where they END; see stage_small_block)
-__device__ __forceinline__ void small_block_hist(const uint8_t* __restrict__ in, uint32_t in_size, uint32_t segmask, uint32_t* h) {
-    const uint32_t l = lane_id();
-    const unsigned long long lt = (1ull << l) - 1ull;
-    const uint32_t nseg = (in_size + 4095u) >> 12;
-    uint32_t pend = 0;
-    for (uint32_t seg = 0; seg < nseg; ++seg) {
-        const uint32_t seg_base = seg << 12;
-        if (!((segmask >> seg) & 1u)) {
-            pend += min(4096u, in_size - seg_base);
-            continue;
-        }
-        uint4 rows[4];
-#pragma unroll
-        for (uint32_t r = 0; r < 4; ++r) {  // the segment's four rows in one round trip
-            const uint32_t pos = seg_base + (r << 10) + 16u * l;
-            rows[r] = make_uint4(0, 0, 0, 0);
-            if (pos < in_size) rows[r] = *reinterpret_cast<const uint4*>(in + pos);
-        }
-#pragma unroll
-        for (uint32_t r = 0; r < 4; ++r) {
-            const uint32_t base = seg_base + (r << 10);
-            if (base < in_size) {
-                const uint32_t row_valid = min(1024u, in_size - base);
-                Granule gr;
-                const uint32_t pos = base + 16u * l;
-                gr.nv = pos < in_size ? min(16u, in_size - pos) : 0u;
-                gr.w[0] = rows[r].x;
-                gr.w[1] = rows[r].y;
-                gr.w[2] = rows[r].z;
-                gr.w[3] = rows[r].w;
-                granule_finish(gr);
-                const uint32_t lits = ~gr.zm & ((1u << gr.nv) - 1u);
-                const unsigned long long nzb = __ballot(lits != 0);
-                if (!nzb) {
-                    pend += row_valid;
-                } else {
-                    const uint32_t last_nz = lits ? 31u - (uint32_t)__builtin_clz(lits) : 0u;
-                    const uint32_t trail = lits ? (15u - last_nz) : 16u;
-                    const unsigned long long below = nzb & lt;
-                    const uint32_t p = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u;
-                    const uint32_t tp = (uint32_t)__shfl((int)trail, (int)p, 64);
-                    const uint32_t zb = below ? (16u * (l - 1u - p) + tp) : (16u * l + pend);
-                    uint32_t t = lits, prev_end = 0;
-                    bool first = true;
-                    while (t) {
-                        const uint32_t i = (uint32_t)__builtin_ctz(t);
-                        t &= t - 1;
-                        const uint32_t R = first ? (zb + i) : (i - prev_end);
-                        if (R) run_count(h, R);
-                        atomicAdd(&h[granule_byte_dyn(gr.w[0], gr.w[1], gr.w[2], gr.w[3], i)], 1u);
-                        prev_end = i + 1;
-                        first = false;
-                    }
-                    const uint32_t pl = 63u - (uint32_t)__builtin_clzll(nzb);
-                    const uint32_t lastlit = read_lane(last_nz, pl);  // pl from a ballot: wave-uniform
-                    pend = row_valid - (16u * pl + lastlit + 1u);
-                }
-            }
-        }
-    }
-    if (pend && l == 0) run_count(h, pend);
-}
 
 // The merge loop with the live keys kept SORTED (descending) across lanes and registers: element e lives in lane e % 64 of
 // register e / 64, the n live ones are elements 0 .. n-1, so the two smallest keys -- the reference's `<=` scan picks exactly
@@ -267,11 +524,11 @@ struct TreeOut {  // wave-uniform
 };
 
 // One wave: token histogram h[0..260] (LDS) of an hzr block of in_size bytes -> Fill test (hzr_encode.c:285-305),
-// Huffman tree with the reference's tie-break (:222-283), code words via put_cw(sym, code, len), the pre-order tree
-// description in t.tdesc (:177-219), stream bits per token of every used symbol in t.key[sym], and the block's mode
-// and exact payload size (:377-469).
-template <class PutCw>
-__device__ __forceinline__ TreeOut build_tree(TreeLds& t, const uint32_t* h, uint32_t in_size, PutCw put_cw) {
+// Huffman tree with the reference's tie-break (:222-283), the pre-order tree description in t.tdesc (:177-219), and the
+// block's mode and exact payload size (:377-469).  The code words, code | length << 24, go to cw_out[sym] (global memory) and
+// t.key[sym] keeps the symbol's stream bits per token -- or, with cw_out == nullptr (wave-uniform), the code words stay in
+// t.key[sym] themselves: the table of a small block's own emit.
+__device__ __forceinline__ TreeOut build_tree(TreeLds& t, const uint32_t* h, uint32_t in_size, uint32_t* __restrict__ cw_out) {
     const uint32_t l = lane_id();
     // ---- leaves in ascending symbol order (hzr_encode.c:226-234) ----------
     uint32_t cnt[5], idx[5];
@@ -347,8 +604,9 @@ __device__ __forceinline__ TreeOut build_tree(TreeLds& t, const uint32_t* h, uin
             cur = u & 1023u;
         }
         const uint32_t sym = t.leafsym[i];
-        put_cw(sym, code, len);
-        t.key[sym] = len + run_extra_bits(sym);  // stream bits per token of this symbol (the key slots are free now)
+        const uint32_t packed = code | (len << 24);
+        if (cw_out) cw_out[sym] = packed;
+        t.key[sym] = cw_out ? len + run_extra_bits(sym) : packed;  // (the key slots are free now)
         // description: '1' then the 9-bit symbol, LSB first (hzr_encode.c:184-191)
         const uint32_t v = 1u | (sym << 1);
         const uint32_t wi = off >> 5, sh = off & 31u;
@@ -362,7 +620,8 @@ __device__ __forceinline__ TreeOut build_tree(TreeLds& t, const uint32_t* h, uin
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
         const uint32_t s2 = r * 64 + l;
-        if (cnt[r]) bits_sum += cnt[r] * t.key[s2 < (uint32_t)kNumSym ? s2 : 0u];
+        const uint32_t kept = t.key[s2 < (uint32_t)kNumSym ? s2 : 0u];
+        if (cnt[r]) bits_sum += cnt[r] * (cw_out ? kept : (kept >> 24) + run_extra_bits(s2));
     }
     bits_sum = wave_add_u32(bits_sum);
     const uint32_t ntok = wave_add_u32(cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4]);
@@ -377,208 +636,163 @@ __device__ __forceinline__ TreeOut build_tree(TreeLds& t, const uint32_t* h, uin
 }
 
 // ---------------------------------------------------------------------------------------------
-// Small blocks: the wave of k_tree that has just built the block's code table also encodes it, no workgroup barrier.
-// The wave streams over the block's rows in order, so it needs only forward information: every
-// zero run is emitted when it ENDS, right before the literal that ends it (or at the block end),
-// as floor(R/16662) capped tokens plus a remainder token -- the same token sequence as the
-// reference's greedy walk (hzr_encode.c:410-457).  Zero 4 KiB segments are skipped without a read.
-// The tree's LDS is dead by then except for the description: the code table goes where the keys were, the image
-// (X || payload + read slack) over the node arrays behind them.
+// Small blocks: one wave of k_tree tokenizes the block ONCE, with the compacted-row tokenizer of k_hist's sparse segments
+// (hist_segment_sparse and its fall-backs), counts the tokens into its histogram and keeps the entries -- position << 9 |
+// literal, in stream order, the run that reaches the block end as a last entry at in_size -- as one list in the block's own
+// staging slot (free until the block's header + payload go there; nothing else reads the slot of a block that is not staged).
+// After the tree the same wave encodes the block from that list alone, 64 entries per pass (emit_entries, as k_encode does
+// for its list blocks): a zero run is the gap between two entries, so all-zero segments, rows and granules cost nothing.
+// A staged block has at most kSmallTokens tokens and every entry yields at least one, so its list always fits kListCap; a
+// block whose list overflows is by the same count not staged and goes to k_encode as before.
+// The tree's LDS is dead by the emit except for the description: the code table stays where build_tree left it (the key
+// slots), the image (X || payload + read slack) goes over the node arrays behind them.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kSlotImage = 826;  // words of X || payload (+ slack)
 static_assert(kSlotImage * 4 >= kSmallPayload + 4 + 72, "small-block image too small");
 static_assert(offsetof(TreeLds, key) == 0 && offsetof(TreeLds, lcnt) == kSymStride * 4, "the code table takes the key slots, the image starts behind them");
 static_assert((kSymStride + kSlotImage) * 4 <= offsetof(TreeLds, tdesc), "the image must leave the tree description alone");
+static_assert(kQueueEntries * 4 <= offsetof(TreeLds, up), "the tokenizer's queue takes the key and lcnt words (build_tree initialises them afterwards); the histogram sits in up");
+static_assert(kListCap <= kStageSlotWords, "a small block's entry list waits in its staging slot");
 
-struct LinSink {  // bit sink of the one-wave encoder: a 32-bit partial word, whole words stored to the wave's image
-    uint32_t* img;
-    uint32_t lo, n, word;
-    __device__ __forceinline__ void start(uint32_t* s, uint32_t bitpos) {
-        img = s;
-        lo = 0;
-        n = bitpos & 31u;
-        word = bitpos >> 5;
-    }
-    __device__ __forceinline__ void put(uint32_t v, uint32_t len) {
-        lo |= v << n;
-        const uint32_t tot = n + len;
-        if (tot >= 32) {
-            atomicOr(&img[word], lo);
-            ++word;
-            lo = (v >> 1) >> (31u - n);
-            n = tot - 32;
-        } else {
-            n = tot;
+// Token histogram h and entry list of a small block by one wave; returns the number of entries, or kListNone.  Zero 4 KiB
+// segments are skipped without a read.  The tokenizer never sees the block end (RowCtx::last = 0): the run that reaches it
+// is counted and listed here, whichever segment the block's last literal lies in.
+__device__ __forceinline__ uint32_t small_block_tokens(const uint8_t* __restrict__ in, uint32_t in_size, uint32_t segmask, uint32_t* h,
+                                                       const uint32_t* runcls, uint32_t* queue, uint32_t* list) {
+    const uint32_t l = lane_id();
+    ListSink sink{list, 0u};
+    uint32_t behind = 0;  // position behind the block's last literal so far (wave-uniform)
+    for (uint32_t m = segmask; m; m &= m - 1u) {
+        const uint32_t seg_base = (uint32_t)__builtin_ctz(m) << 12;
+        uint32_t W[4][4];
+        RowCtx rc[4];
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {  // the segment's four rows in one round trip
+            const uint32_t pos = seg_base + (r << 10) + 16u * l;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (pos < in_size) v = *reinterpret_cast<const uint4*>(in + pos);  // plane rows are padded: a partial granule may over-read
+            W[r][0] = v.x;
+            W[r][1] = v.y;
+            W[r][2] = v.z;
+            W[r][3] = v.w;
+            if (pos + 16u > in_size && pos < in_size) {  // the block's last, partial granule: bytes behind it read as zero
+                const uint32_t nv = in_size - pos;
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q) {
+                    const uint32_t lo = q * 4u;
+                    W[r][q] = nv >= lo + 4u ? W[r][q] : nv <= lo ? 0u : (W[r][q] & ((1u << ((nv - lo) * 8u)) - 1u));
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {
+            const uint32_t rb = seg_base + (r << 10);
+            rc[r].rb = rb;
+            rc[r].valid = rb >= in_size ? 0u : min(1024u, in_size - rb);
+            rc[r].last = 0u;
+            rc[r].zb0 = rb - behind;
+            const unsigned long long nzg = __ballot((W[r][0] | W[r][1] | W[r][2] | W[r][3]) != 0u);
+            if (nzg) {
+                const uint32_t ph = 63u - (uint32_t)__builtin_clzll(nzg);
+                behind = rb + 16u * ph + 16u - read_lane(trail_zero_bytes(W[r][0], W[r][1], W[r][2], W[r][3]), ph);
+            }
+        }
+        if (!hist_segment_sparse(W, rc, in_size, h, runcls, queue, sink)) {  // more than 64 non-zero granules or 512 entries: row by row
+#pragma unroll 1
+            for (int r = 0; r < 4; ++r) {
+                hist_row_sparse(W[0], rc[0], in_size, h, runcls, queue, sink);
+                rotate_rows(W, rc);
+            }
         }
     }
-    __device__ __forceinline__ void flush() {
-        if (n) atomicOr(&img[word], lo);
+    const uint32_t R = in_size - behind;  // the run that reaches the block end
+    if (R) {
+        if (l == 0) hist_run(h, runcls, R);
+        if (sink.n < kListCap) {  // (kListNone is not)
+            if (l == 0) list[sink.n] = (in_size << 9) | kNoLit;
+            ++sink.n;
+        } else {
+            sink.n = kListNone;
+        }
+    }
+    return sink.n;
+}
+
+struct PackedCodes {  // k_tree's code table as the emit helpers read it: code | length << 24 per symbol
+    const uint32_t* w;
+    __device__ __forceinline__ uint2 operator[](uint32_t i) const {
+        const uint32_t c = w[i];
+        return make_uint2(c & 0x00FFFFFFu, c >> 24);
     }
 };
 
-// stream bits of the tokens of a zero run of length R (0 < R): capped tokens, then the remainder
-__device__ __forceinline__ uint32_t run_bits(const uint32_t* cwt, uint32_t R) {
-    const uint32_t q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
-    const uint32_t rem = R - q * kRunCap;
-    uint32_t bits = q * ((cwt[260] >> 24) + 14u);
-    if (rem) {
-        const uint32_t sym = run_symbol(rem);
-        bits += (cwt[sym] >> 24) + run_extra_bits(sym);
-    }
-    return bits;
-}
-
-template <typename Sink>
-__device__ __forceinline__ void run_emit(Sink& sink, const uint32_t* cwt, uint32_t R) {
-    const uint32_t q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
-    const uint32_t rem = R - q * kRunCap;
-    for (uint32_t i = 0; i < q; ++i) {
-        const uint32_t c = cwt[260];
-        sink.put(c & 0x00FFFFFFu, c >> 24);
-        sink.put(kRunCap - 279u, 14);
-    }
-    if (rem) {
-        const uint32_t sym = run_symbol(rem);
-        const uint32_t c = cwt[sym];
-        sink.put(c & 0x00FFFFFFu, c >> 24);
-        const uint32_t eb = run_extra_bits(sym);
-        if (eb) sink.put(run_extra_value(sym, rem), eb);
-    }
-}
-
-__device__ __forceinline__ uint32_t crc_chunk64_lin(const uint32_t* img, const uint32_t (*tab)[256], int32_t lo) {
-    const int32_t a = lo >> 2;
-    const uint32_t sh = (uint32_t)lo & 3u;
-    uint32_t c = 0;
-    uint32_t prev = a >= 0 ? img[a] : 0u;
-#pragma unroll
-    for (int32_t q = 0; q < 16; ++q) {
-        const int32_t ix = a + q + 1;
-        const uint32_t next = ix >= 0 ? img[ix] : 0u;
-        c ^= __builtin_amdgcn_alignbyte(next, prev, sh);
-        prev = next;
-        c = tab[3][c & 0xFFu] ^ tab[2][(c >> 8) & 0xFFu] ^ tab[1][(c >> 16) & 0xFFu] ^ tab[0][c >> 24];
-    }
-    return c;
-}
-
-// One wave: emit the block (code words in cwt, tree description in tdesc_lds, both LDS) into img, checksum it, and store
-// [7-byte block header][payload] to the block's staging slot; k_encode copies it to its stream offset, which only k_layout
-// knows.  The literals' granules are wiped on the way (clean-block invariant: block_is_wiped).
-__device__ __forceinline__ void stage_small_block(const uint32_t* cwt, uint32_t* img, const uint32_t* tdesc_lds, const uint32_t (*crc_tab)[256],
-                                                  uint8_t* __restrict__ in, uint32_t in_size, uint32_t segmask, uint32_t L, uint32_t tree_bits,
-                                                  const CrcConsts* __restrict__ cc, uint32_t* __restrict__ slot) {
+// One wave: emit the block from its n entries (list: global memory, written by this wave) with the code words in cwt and the
+// tree description in tdesc_lds (both LDS) into img, checksum it, and store [7-byte block header][payload] to the block's staging
+// slot -- over the list, which is in registers by then; k_encode copies it to its stream offset, which only k_layout knows.
+// The literals' granules are wiped on the way (clean-block invariant: block_is_wiped).  Work follows the payload: the image is
+// zeroed as far as the payload and the CRC's read slack reach, and the CRC-32C goes by words across the lanes.
+__device__ __forceinline__ void stage_small_block(uint32_t* cwt, uint32_t* img, const uint32_t* tdesc_lds, const uint32_t* runcls,
+                                                  const uint32_t* list, uint32_t n, uint8_t* __restrict__ in, uint32_t in_size, uint32_t L, uint32_t tree_bits,
+                                                  const CrcConsts* __restrict__ cc, uint32_t* slot) {
     const uint32_t l = lane_id();
-    for (uint32_t i = l; i < kSlotImage; i += 64) img[i] = 0;
-    __builtin_amdgcn_wave_barrier();
+    const uint32_t zwords = min(((L + 4u) >> 2) + 4u, kSlotImage);  // X + payload, the word the CRC reads behind them, or_bits64's reach
+    for (uint32_t i = l; i < zwords; i += 64) img[i] = 0;
+    if (l < 3u) cwt[(uint32_t)kNumSym + l] = 0u;  // index 261: {0, 0}, what an entry without a literal looks up; 263: the zero word in front of the image
     __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the list's stores (issued before the tree was built) are done before it is read back
     if (l == 0) img[0] = cc->prefix;
     const uint32_t twords = (tree_bits + 31) >> 5;
     for (uint32_t i = l; i < twords; i += 64) atomicOr(&img[1 + i], tdesc_lds[i]);
 
-    uint32_t pend = 0;                    // zeros pending in front of the current position (wave-uniform)
-    uint32_t bitpos = 32u + tree_bits;    // next stream bit (wave-uniform)
-    const unsigned long long lt = (1ull << l) - 1ull;
-    const uint32_t nseg = (in_size + 4095u) >> 12;
-    for (uint32_t seg = 0; seg < nseg; ++seg) {
-        const uint32_t seg_base = seg << 12;
-        if (!((segmask >> seg) & 1u)) {
-            pend += min(4096u, in_size - seg_base);
-            continue;
+    // the entries come back past the L1 (another lane stored them), the next pass's load in flight during this one's emit
+    auto entry = [&](uint32_t k) -> uint32_t { return k < n ? __hip_atomic_load(&list[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u; };
+    uint32_t base = 32u + tree_bits;  // next stream bit (wave-uniform): the payload starts at image byte 4
+    uint32_t carry = 0;               // the entry in front of lane 0's (wave-uniform)
+    uint32_t e_next = entry(l);
+    for (uint32_t c = 0; c < n; c += 64) {
+        const uint32_t e = e_next, kq = c + l;
+        e_next = entry(kq + 64u);
+        const uint32_t prev = dpp<0x138>(carry, e);  // wave_shr:1 -- lane l sees lane l-1's entry, lane 0 the pass before
+        uint32_t R = 0, lit = kNoLit;
+        if (kq < n) {
+            const uint32_t before = kq ? (prev >> 9) + 1u : 0u;  // position behind the literal before this one
+            lit = e & 0x1FFu;
+            R = (e >> 9) - before;
+            // clean-block invariant: a staged block leaves zeros behind (the granule of every literal)
+            if (lit < 256u && (e >> 9) < in_size) *reinterpret_cast<uint4*>(in + ((e >> 9) & ~15u)) = make_uint4(0, 0, 0, 0);
         }
-        uint4 rows[4];
-#pragma unroll
-        for (uint32_t r = 0; r < 4; ++r) {  // the segment's four rows in one round trip (L2-hot: this wave has just counted them)
-            const uint32_t pos = seg_base + (r << 10) + 16u * l;
-            rows[r] = make_uint4(0, 0, 0, 0);
-            if (pos < in_size) rows[r] = *reinterpret_cast<const uint4*>(in + pos);
-        }
-#pragma unroll
-        for (uint32_t r = 0; r < 4; ++r) {
-            const uint32_t base = seg_base + (r << 10);
-            if (base < in_size) {
-                const uint32_t row_valid = min(1024u, in_size - base);
-                Granule gr;
-                const uint32_t pos = base + 16u * l;
-                gr.nv = pos < in_size ? min(16u, in_size - pos) : 0u;
-                gr.w[0] = rows[r].x;
-                gr.w[1] = rows[r].y;
-                gr.w[2] = rows[r].z;
-                gr.w[3] = rows[r].w;
-                granule_finish(gr);
-                const uint32_t lits = ~gr.zm & ((1u << gr.nv) - 1u);
-                // clean-block invariant: every small block is wiped (block_is_wiped); this lane alone read the granule
-                if (lits) *reinterpret_cast<uint4*>(in + pos) = make_uint4(0, 0, 0, 0);
-                const unsigned long long nzb = __ballot(lits != 0);
-                if (!nzb) {
-                    pend += row_valid;
-                } else {
-                    // zeros in front of this granule: the nearest lower lane with a literal closes the run
-                    const uint32_t last_nz = lits ? 31u - (uint32_t)__builtin_clz(lits) : 0u;  // index of the granule's last literal
-                    const uint32_t trail = lits ? (15u - last_nz) : 16u;                         // zeros behind it inside the (full) granule
-                    const unsigned long long below = nzb & lt;
-                    const uint32_t p = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u;
-                    const uint32_t tp = (uint32_t)__shfl((int)trail, (int)p, 64);
-                    const uint32_t zb = below ? (16u * (l - 1u - p) + tp) : (16u * l + pend);
-                    // pass A: bits of this lane's tokens
-                    uint32_t nbits = 0;
-                    {
-                        uint32_t t = lits, prev_end = 0;  // prev_end = index after the previous literal
-                        bool first = true;
-                        while (t) {
-                            const uint32_t i = (uint32_t)__builtin_ctz(t);
-                            t &= t - 1;
-                            const uint32_t R = first ? (zb + i) : (i - prev_end);
-                            if (R) nbits += run_bits(cwt, R);
-                            nbits += cwt[granule_byte_dyn(gr.w[0], gr.w[1], gr.w[2], gr.w[3], i)] >> 24;
-                            prev_end = i + 1;
-                            first = false;
-                        }
-                    }
-                    const uint32_t inc = wave_scan_add(nbits);
-                    const uint32_t mypos = bitpos + inc - nbits;
-                    bitpos += read_lane(inc, 63);
-                    // pass B: emit
-                    if (nbits) {
-                        LinSink sink;
-                        sink.start(img, mypos);
-                        uint32_t t = lits, prev_end = 0;
-                        bool first = true;
-                        while (t) {
-                            const uint32_t i = (uint32_t)__builtin_ctz(t);
-                            t &= t - 1;
-                            const uint32_t R = first ? (zb + i) : (i - prev_end);
-                            if (R) run_emit(sink, cwt, R);
-                            const uint32_t c = cwt[granule_byte_dyn(gr.w[0], gr.w[1], gr.w[2], gr.w[3], i)];
-                            sink.put(c & 0x00FFFFFFu, c >> 24);
-                            prev_end = i + 1;
-                            first = false;
-                        }
-                        sink.flush();
-                    }
-                    // zeros behind the row's last literal stay pending
-                    const uint32_t pl = 63u - (uint32_t)__builtin_clzll(nzb);
-                    const uint32_t lastlit = read_lane(last_nz, pl);  // pl from a ballot: wave-uniform
-                    pend = row_valid - (16u * pl + lastlit + 1u);
-                }
-            }
-        }
-    }
-    if (pend && l == 0) {  // the run that reaches the block end
-        LinSink sink;
-        sink.start(img, bitpos);
-        run_emit(sink, cwt, pend);
-        sink.flush();
+        emit_entries(R, lit, PackedCodes{cwt}, runcls, img, base);
+        carry = read_lane(e, 63);
     }
     __threadfence_block();
     __builtin_amdgcn_wave_barrier();
 
-    // CRC-32C of X || payload: lane l owns the 64-byte chunk (63 - l) counted from the end
+    // CRC-32C of V = X || payload (Lv = L + 4 bytes from image byte 0) as 4-byte virtual words counted from its END: lane l owns
+    // the words l, l + 64, ... -- Horner over them with x^(8*256) per step (CrcConsts::shift[59]), then x^(8*4*(l+1)) to the end
+    // of V and a wave XOR: ceil(words / 64) steps, as k_encode's per-wave group (tools/kernel_model.py: crc_wave_words).
+    // Virtual word r = image words a and a + 1 joined at byte (Lv & 3), a = (Lv >> 2) - 1 - r; a = -1 is the zero word cwt[263].
     const int32_t Lv = (int32_t)L + 4;
-    const int32_t hi = Lv - 64 * (int32_t)(63u - l);
+    const uint32_t nvw = (uint32_t)(Lv + 3) >> 2;
+    const uint32_t K = (nvw + 63u) >> 6;  // steps of the fullest lane
+    const uint32_t sh = (uint32_t)Lv & 3u;
+    auto vword = [&](int32_t a) -> uint32_t { return __builtin_amdgcn_alignbyte(img[a + 1], img[a], sh); };
     uint32_t c = 0;
-    if (hi > 0) c = crc_chunk64_lin(img, crc_tab, hi - 64);
-    const uint32_t crc = ~wave_xor_u32(gf_shift(cc, l, c));
+    if (l < nvw) {
+        int32_t a = (Lv >> 2) - 1 - (int32_t)(l + 64u * (K - 1u));
+        if (K > 1u) {
+            c = a >= -1 ? vword(max(a, -1)) : 0u;  // (the top word: there for the low lanes only)
+            c = gf_shift(cc, 59u, c);
+            for (uint32_t kk = K - 2u; kk >= 1u; --kk) {
+                a += 64;
+                c ^= vword(a);
+                c = gf_shift(cc, 59u, c);
+            }
+            a += 64;
+        }
+        c ^= vword(a);
+    }
+    const uint32_t crc = ~wave_xor_u32(gf_shift4(cc, l, c));
 
     // slot byte s = stream byte s of the encoded block: [L-1 u16][crc u32][mode], then payload byte s - 7 = image byte s - 3
     const uint32_t nw = (7u + L + 3u) >> 2;
@@ -596,7 +810,7 @@ __device__ __forceinline__ void stage_small_block(const uint32_t* cwt, uint32_t*
 // (BlockMeta::mode = kModeStaged: the one mark k_layout and k_encode go by); for the others k_hist left the block histogram and
 // the per-segment histograms, which -- times the code lengths -- give the stream bit at which each 4 KiB segment's tokens start
 // (k_encode then needs no bit-count pass).
-__global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __restrict__ hist, uint8_t* __restrict__ planes, Geom g,
+__global__ __launch_bounds__(kTreeWaves * 64, 7) void k_tree(const uint32_t* __restrict__ hist, uint8_t* __restrict__ planes, Geom g,
                                                          const uint32_t* __restrict__ nbuse, const uint32_t* __restrict__ nzflag,
                                                          uint32_t nhb_total, uint32_t* __restrict__ cw, uint32_t* __restrict__ tdesc,
                                                          BlockMeta* __restrict__ meta, const uint32_t* __restrict__ seghist,
@@ -604,11 +818,14 @@ __global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __rest
                                                          const CrcConsts* __restrict__ cc, uint32_t* __restrict__ staging, uint32_t psel_arg) {
     const uint32_t psel = RSPT_DIAG_ONLY(psel_arg);  // timing probes (diagnostic builds only): no tree for plane 0 (bit 4) / planes >= 1 (bit 5)
     __shared__ TreeLds s_t[kTreeWaves];
-    static_assert(sizeof(TreeLds) * kTreeWaves * 8 <= 160 * 1024, "eight k_tree workgroups (32 trees) per CU");
+    __shared__ uint32_t s_runcls[kRunClsEntries];  // run length -> symbol, extra bits, base: the small blocks' tokenizer and emit
+    static_assert((sizeof(TreeLds) * kTreeWaves + sizeof(uint32_t) * kRunClsEntries) * 7 <= 160 * 1024, "seven k_tree workgroups (28 trees) per CU");
     const uint32_t l = lane_id();
-    const uint32_t wv = threadIdx.x >> 6;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (wave-uniform: the block's index, size and addresses stay in scalar registers)
     // the other copy of the per-call zero region, for the next call (rspt_hip.hip: zbuf)
     for (uint32_t i = blockIdx.x * (kTreeWaves * 64u) + threadIdx.x; i < zero_words; i += gridDim.x * (kTreeWaves * 64u)) zero_next[i] = 0;
+    for (uint32_t i = threadIdx.x; i < kRunClsEntries; i += kTreeWaves * 64u) s_runcls[i] = run_class_entry(i);
+    __syncthreads();  // (the only one: from here on every wave is on its own)
     // wave -> hzr block, plane-major: all the blocks of plane 0 (the dense, expensive ones) are dispatched first and
     // next to each other, so they spread over every CU; in (b, k, j) order they recur with a period that the
     // dispatcher's round-robin maps onto a quarter of the CUs (profiles/r01_notes.md: placement resonance)
@@ -618,12 +835,13 @@ __global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __rest
     const uint32_t k = v / per_plane, rest = v - k * per_plane;
     const uint32_t b = rest / g.nblk, j = rest - b * g.nblk;
     const uint32_t hb = hb_index(g, b, k, j);
-    TreeLds& t = s_t[wv];
+    TreeLds& t = s_t[threadIdx.x >> 6];  // (the wave's LDS through a vector register, as the merge loop's lane-0 stores want it: a scalar base costs them four moves per merge)
     if (k >= nbuse[b]) {
         if (l == 0) meta[hb] = BlockMeta{kModeSkip, 0, 0, 0};
         return;
     }
-    const uint32_t segmask = (psel && ((k == 0 && (psel & 16u)) || (k >= 1 && (psel & 32u)))) ? 0u : nzflag[hb];
+    const uint32_t segmask =  // (one word per wave: in a scalar register, so that what hangs on it is a scalar branch)
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)((psel && ((k == 0 && (psel & 16u)) || (k >= 1 && (psel & 32u)))) ? 0u : nzflag[hb]));
     if (!segmask) {  // all-zero block (flagged by the front end): EncodeFill with value 0
         if (l == 0) meta[hb] = BlockMeta{kModeFill, 1u, 0u, 0u};
         return;
@@ -633,31 +851,35 @@ __global__ __launch_bounds__(kTreeWaves * 64) void k_tree(const uint32_t* __rest
     uint8_t* in = planes + ((size_t)b * kMaxPlanes + k) * g.plane_stride + (size_t)j * kHzrBlock;
     const bool own_hist = (uint32_t)__popc(segmask) <= kSmallSegments;
     if (l == 0) segbase[(size_t)hb * kEncWaves] = 0xFFFFFFFFu;  // "no segment offsets" unless set below
-    if (own_hist) {  // small block: this wave takes the histogram itself
+    uint32_t* lds = reinterpret_cast<uint32_t*>(&t);
+    uint32_t* slot = staging + (size_t)hb * kStageSlotWords;
+    uint32_t nlist = kListNone;  // entries of the small block's list
+    if (own_hist) {  // small block: this wave takes the histogram itself, and keeps the entries
         for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) h[i] = 0;
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
-        small_block_hist(in, in_size, segmask, h);
+        const uint32_t nseg = (in_size + 4095u) >> 12;
+        nlist = small_block_tokens(in, in_size, segmask & ((1u << nseg) - 1u), h, s_runcls, lds, slot);
     } else {
         for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) h[i] = hist[(size_t)hb * kSymStride + i];
     }
     __threadfence_block();
     __builtin_amdgcn_wave_barrier();
+    // The code words: k_encode reads them from cw[]; a small block's stay in this wave's LDS (t.key), for its own emit -- they
+    // leave for cw[] only if the block turns out too big to be staged.
     uint32_t* cwo = cw + (size_t)hb * kSymStride;
-    const TreeOut r = build_tree(t, h, in_size, [&](uint32_t sym, uint32_t code, uint32_t len) { cwo[sym] = code | (len << 24); });
-    // small enough for this wave to encode it right here?  (wave-uniform; the same mark decides in k_layout and k_encode)
-    const bool staged = own_hist && r.mode == kModeHuff && r.payload_len <= kSmallPayload && r.ntok <= kSmallTokens;
+    const TreeOut r = build_tree(t, h, in_size, own_hist ? nullptr : cwo);
+    // small enough for this wave to encode it right here?  (wave-uniform; the same mark decides in k_layout and k_encode.  The
+    // list is there whenever the tokens are few enough -- see above; the test only keeps a read of a list that is not in bounds.)
+    const bool staged = own_hist && r.mode == kModeHuff && r.payload_len <= kSmallPayload && r.ntok <= kSmallTokens && nlist != kListNone;
     if (l == 0) meta[hb] = BlockMeta{staged ? kModeStaged : r.mode, r.payload_len, r.tree_bits, r.mode == kModeHuff ? r.ntok : r.fill};
     if (r.mode != kModeHuff) return;
     if (staged) {
-        // the code words come back from the row this wave has just written (same wave, same CU: workgroup scope is enough)
-        uint32_t* lds = reinterpret_cast<uint32_t*>(&t);
-        __threadfence_block();
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t i = l; i < (uint32_t)kSymStride; i += 64) lds[i] = __hip_atomic_load(&cwo[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (past the L1)
-        stage_small_block(lds, lds + kSymStride, t.tdesc, cc->table, in, in_size, segmask, r.payload_len, r.tree_bits, cc, staging + (size_t)hb * kStageSlotWords);
+        stage_small_block(lds, lds + kSymStride, t.tdesc, s_runcls, slot, nlist, in, in_size, r.payload_len, r.tree_bits, cc, slot);
         return;
     }
+    if (own_hist)  // k_encode takes the block (own_bits), untouched: it needs the code words after all
+        for (uint32_t i = l; i < (uint32_t)kNumSym; i += 64) cwo[i] = t.key[i];
     uint32_t* tdo = tdesc + (size_t)hb * kTdescWords;
     for (uint32_t i = l; i < (uint32_t)kTdescWords; i += 64) tdo[i] = t.tdesc[i];
     if (own_hist) return;
@@ -857,33 +1079,6 @@ __global__ __launch_bounds__(256) void k_layout(Geom g, const uint32_t* __restri
 // the virtual words tid, tid + 1024, ... counted from the END of V (tools/kernel_model.py:crc_strided).
 constexpr uint32_t kStageWords = kHzrBlock / 4 + 32;  // X + payload + read slack
 constexpr uint32_t kStagePhys = kStageWords + 2;
-
-constexpr uint32_t kRunClsEntries = 280;  // lengths 0..278 and ">= 279" (hzr_internal.h:117-121)
-__device__ __forceinline__ uint32_t run_class_entry(uint32_t z) {
-    const uint32_t sym = run_symbol(z);
-    const uint32_t base = sym == 257 ? 3u : sym == 258 ? 7u : sym == 259 ? 23u : sym == 260 ? 279u : z;  // (runs of 1 and 2: no extra bits, value 0)
-    return sym | (run_extra_bits(sym) << 12) | (base << 16);
-}
-
-// OR a string of `len` <= 64 bits (hi:lo) into the image at bit `pos`.  Two words always; the third only where some lane's
-// string reaches into it -- with the usual four codes of ~5.5 bits per string that is no lane of the wave, and the third
-// atomic with its shifts and address is one instruction in eight of the dense emit (one wave-wide test instead)
-__device__ __forceinline__ void or_bits64(uint32_t* stage, uint32_t pos, uint32_t lo, uint32_t hi, uint32_t len) {
-    const uint32_t word = pos >> 5, sh = pos & 31u;
-    const uint64_t sv = (((uint64_t)hi << 32) | lo) << sh;
-    atomicOr(&stage[word], (uint32_t)sv);
-    atomicOr(&stage[(word + 1)], (uint32_t)(sv >> 32));
-    if (__builtin_amdgcn_ballot_w64(sh + len > 64u)) atomicOr(&stage[(word + 2)], (hi >> 1) >> (31u - sh));
-}
-
-// OR one token (<= 38 bits) into the image at bit `pos`
-__device__ __forceinline__ void or_token(uint32_t* stage, uint32_t pos, uint32_t lo, uint32_t hi, uint32_t len) {
-    const uint32_t word = pos >> 5, sh = pos & 31u;
-    const uint64_t sv = (((uint64_t)hi << 32) | lo) << sh;
-    atomicOr(&stage[word], (uint32_t)sv);
-    atomicOr(&stage[(word + 1)], (uint32_t)(sv >> 32));
-    if (sh + len > 64) atomicOr(&stage[(word + 2)], (hi >> 1) >> (31u - sh));
-}
 
 constexpr uint32_t kLightPayload = 16384;    // bytes: below it the image words from kTokQueueBase on are free (sparse-row queues)
 constexpr uint32_t kTokQueueBase = 4200;     // stage word (> (16384 + 4) / 4 + 24)

@@ -22,20 +22,13 @@
 
 namespace rspt {
 
-constexpr uint32_t kQueueEntries = 512;  // entries per wave in the sparse-row queue (8 x 64)
+// (The sparse-row tokenizer -- RowCtx, the per-wave queue, the entry lists, hist_segment_sparse, emit_entries -- is shared with
+//  k_tree's small blocks and lives in hzr_kernels.hip.)
 static_assert(kTokQueueBase + kEncWaves * kQueueEntries <= kStageWords, "emit-phase queues sit in the image tail");
 // k_encode's own token count of a block (own_bits): sixteen per-wave histograms at the start of the image, the queues behind them
 constexpr uint32_t kOwnHistQueueBase = kEncWaves * kSymStride;
 static_assert(kOwnHistQueueBase >= kTokQueueBase && kOwnHistQueueBase + kEncWaves * kQueueEntries <= kStageWords, "own-count queues: behind the histograms, inside the image");
 
-// trailing (highest-address) zero bytes of a granule that is not all zero
-__device__ __forceinline__ uint32_t trail_zero_bytes(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
-    return w3 ? ((uint32_t)__clz((int)w3) >> 3) : w2 ? 4u + ((uint32_t)__clz((int)w2) >> 3) : w1 ? 8u + ((uint32_t)__clz((int)w1) >> 3)
-                                                                                             : 12u + ((uint32_t)__clz((int)w0) >> 3);
-}
-__device__ __forceinline__ uint32_t zero_mask16(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
-    return zero_nibble(w0) | (zero_nibble(w1) << 4) | (zero_nibble(w2) << 8) | (zero_nibble(w3) << 12);
-}
 __device__ __forceinline__ bool lane_bit(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 
 // zeros immediately before every lane's granule: the nearest lower lane whose granule is not all zero closes the run
@@ -54,20 +47,6 @@ __device__ __forceinline__ uint32_t run_ending_at(uint32_t i, uint32_t lits, uin
     return m ? i - (31u - (uint32_t)__clz((int)m)) : i + 1u + zb;
 }
 
-// full kRunCap tokens in a run of R <= 65536 zeros.  Almost never any: the three compares sit behind one wave-wide test.
-__device__ __forceinline__ uint32_t run_caps(uint32_t R) {
-    uint32_t q = 0;
-    if (__builtin_amdgcn_ballot_w64(R >= kRunCap)) q = (R >= kRunCap) + (R >= 2 * kRunCap) + (R >= 3 * kRunCap);
-    return q;
-}
-
-__device__ __forceinline__ void hist_run(uint32_t* h, const uint32_t* runcls, uint32_t R) {
-    const uint32_t q = run_caps(R);
-    const uint32_t rem = R - q * kRunCap;
-    if (q) atomicAdd(&h[260], q);
-    if (rem) atomicAdd(&h[runcls[min(rem, kRunClsEntries - 1u)] & 0xFFFu], 1u);
-}
-
 // stream bits of the tokens of a zero run
 __device__ __forceinline__ uint32_t run_bits_tab(const uint2* tab, const uint32_t* runcls, uint32_t R) {
     const uint32_t q = run_caps(R);
@@ -79,45 +58,6 @@ __device__ __forceinline__ uint32_t run_bits_tab(const uint2* tab, const uint32_
     }
     return bits;
 }
-
-// the remainder token of a run (0 < rem < 16662) as a bit string
-__device__ __forceinline__ void run_token(const uint2* tab, const uint32_t* runcls, uint32_t rem, uint64_t& v, uint32_t& len) {
-    const uint32_t e = runcls[min(rem, kRunClsEntries - 1u)];
-    const uint2 cw = tab[e & 0xFFFu];
-    v = (uint64_t)cw.x | ((uint64_t)(rem - (e >> 16)) << cw.y);
-    len = cw.y + ((e >> 12) & 0xFu);
-}
-
-// OR the tokens of a zero run into the image at bit `pos`; returns the bits written
-__device__ __forceinline__ uint32_t emit_run(uint32_t* stage, const uint2* tab, const uint32_t* runcls, uint32_t pos, uint32_t R) {
-    const uint32_t q = run_caps(R);
-    const uint32_t rem = R - q * kRunCap;
-    uint32_t done = 0;
-    if (q) {
-        const uint2 c = tab[260];
-        const uint64_t v = (uint64_t)c.x | ((uint64_t)(kRunCap - 279u) << c.y);
-        for (uint32_t i = 0; i < q; ++i) {
-            or_token(stage, pos + done, (uint32_t)v, (uint32_t)(v >> 32), c.y + 14u);
-            done += c.y + 14u;
-        }
-    }
-    if (rem) {
-        uint64_t v;
-        uint32_t len;
-        run_token(tab, runcls, rem, v, len);
-        or_token(stage, pos + done, (uint32_t)v, (uint32_t)(v >> 32), len);
-        done += len;
-    }
-    return done;
-}
-
-// what a row needs to know about its surroundings (wave-uniform)
-struct RowCtx {
-    uint32_t zb0;    // zeros immediately before the row's first byte (cut at the block start)
-    uint32_t last;   // 1: the block ends with this row's last valid byte
-    uint32_t valid;  // bytes of this row inside the block (0..1024)
-    uint32_t rb;     // position of the row's first byte in the block
-};
 
 // Attribution inside a block, rule B: the tokens of a zero run belong to the byte BEHIND the run (the literal that ends
 // it); a run that reaches the block end belongs to the block's last byte.  Inside a dense row the run's own last byte
@@ -330,127 +270,8 @@ __device__ __forceinline__ void emit_row_dense(const uint32_t (&w)[4], const Row
 }
 
 // ===========================================================================
-// sparse rows: the row's literals, in order, as (position, value) entries in a per-wave queue; the wave then takes the
-// queue 64 entries at a time -- the run in front of a literal is the gap to the entry before it, so nothing has to be
-// chained from lane to lane.  A row that ends the block appends a virtual entry at in_size (the run that reaches the end).
+// sparse rows (the entry queue, its tokenizer and emit_entries: hzr_kernels.hip)
 // ===========================================================================
-constexpr uint32_t kNoLit = 0x100u;
-
-// the lane's non-zero bytes (bit i = byte i) -- bytes behind the block end were masked to zero at the load
-__device__ __forceinline__ uint32_t lane_lits(const uint32_t (&w)[4]) { return ~zero_mask16(w[0], w[1], w[2], w[3]) & 0xFFFFu; }
-
-// fills the queue; returns the number of entries (0: nothing ends in this row)
-__device__ __forceinline__ uint32_t sparse_queue(const uint32_t (&w)[4], const RowCtx& rc, uint32_t in_size, uint32_t lits, uint32_t* queue,
-                                                 bool& queued) {
-    const uint32_t l = lane_id();
-    const uint32_t n = (uint32_t)__popc(lits);
-    const uint32_t incl = wave_scan_add(n);
-    const uint32_t T = read_lane(incl, 63) + (rc.last ? 1u : 0u);
-    queued = queue != nullptr && T <= kQueueEntries;
-    if (T == 0 || !queued) return T;
-    uint32_t k = incl - n, t = lits;
-    const uint32_t pos0 = rc.rb + 16u * l;
-    while (t) {
-        const uint32_t i = (uint32_t)__builtin_ctz(t);
-        t &= t - 1;
-        queue[k++] = ((pos0 + i) << 9) | granule_byte_dyn(w[0], w[1], w[2], w[3], i);
-    }
-    if (rc.last && l == 0) queue[T - 1u] = (in_size << 9) | kNoLit;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return T;
-}
-
-// entry k of the queue and the zeros in front of it
-__device__ __forceinline__ void queue_entry(const uint32_t* queue, const RowCtx& rc, uint32_t k, uint32_t T, uint32_t& R, uint32_t& lit) {
-    R = 0;
-    lit = kNoLit;
-    if (k < T) {
-        const uint32_t e = queue[k];
-        const uint32_t before = k ? (queue[k - 1u] >> 9) + 1u : rc.rb - rc.zb0;  // position behind the literal before this one
-        lit = e & 0x1FFu;
-        R = (e >> 9) - before;
-    }
-}
-
-// without a queue: f(R, lit) for the lane's own entries, in stream order (the gap to the literal of a lower lane comes from a scan)
-template <class F>
-__device__ __forceinline__ void lane_entries(const uint32_t (&w)[4], const RowCtx& rc, uint32_t in_size, uint32_t lits, F f) {
-    const uint32_t l = lane_id();
-    const uint32_t pos0 = rc.rb + 16u * l;
-    const uint32_t mine = lits ? pos0 + (32u - (uint32_t)__clz((int)lits)) : 0u;  // position behind this lane's last literal
-    const uint32_t incl = wave_scan_incl(mine, 0u, [](uint32_t a, uint32_t b) { return a > b ? a : b; });
-    uint32_t before = dpp<0x138>(0u, incl);  // wave_shr:1: behind the last literal of the lanes below
-    before = max(l ? before : 0u, rc.rb - rc.zb0);
-    uint32_t t = lits;
-    while (t) {
-        const uint32_t i = (uint32_t)__builtin_ctz(t);
-        t &= t - 1;
-        f(pos0 + i - before, granule_byte_dyn(w[0], w[1], w[2], w[3], i));
-        before = pos0 + i + 1u;
-    }
-    if (rc.last && l == 63u) f(in_size - max(read_lane(incl, 63), rc.rb - rc.zb0), kNoLit);  // the run that reaches the block end
-}
-
-// The entries of a wave's sparse rows, kept for k_encode: a block whose sixteen segments all fit their list is encoded from
-// the lists alone -- no second pass over its 64 KiB of mostly zeros (entry lists).
-constexpr uint32_t kListCap = 512;             // entries per 4 KiB segment
-constexpr uint32_t kListNone = 0xFFFFFFFFu;    // segment info: no list (a dense row, or too many entries)
-struct ListSink {
-    uint32_t* dst;  // this wave's list
-    uint32_t n;     // entries so far, or kListNone
-};
-
-__device__ __forceinline__ void hist_row_sparse(const uint32_t (&w)[4], const RowCtx& rc, uint32_t in_size, uint32_t* h, const uint32_t* runcls,
-                                                uint32_t* queue, ListSink& sink) {
-    if (rc.valid == 0u) return;
-    if (!rc.last && !__ballot((w[0] | w[1] | w[2] | w[3]) != 0u)) return;  // nothing but zeros, and the block goes on: no token ends here
-    const uint32_t lits = lane_lits(w);
-    bool queued;
-    const uint32_t T = sparse_queue(w, rc, in_size, lits, queue, queued);
-    if (T == 0) return;
-    if (queued && sink.n != kListNone && sink.n + T <= kListCap) {
-        for (uint32_t c = lane_id(); c < T; c += 64) sink.dst[sink.n + c] = queue[c];
-        sink.n += T;
-    } else {
-        sink.n = kListNone;
-    }
-    if (queued) {
-        const uint32_t l = lane_id();
-        for (uint32_t c = 0; c < T; c += 64) {
-            uint32_t R, lit;
-            queue_entry(queue, rc, c + l, T, R, lit);
-            if (R) hist_run(h, runcls, R);
-            if (lit < 256u) atomicAdd(&h[lit], 1u);
-        }
-        __builtin_amdgcn_wave_barrier();  // the queue is reused by the next row
-    } else {
-        lane_entries(w, rc, in_size, lits, [&](uint32_t R, uint32_t lit) {
-            if (R) hist_run(h, runcls, R);
-            if (lit < 256u) atomicAdd(&h[lit], 1u);
-        });
-    }
-}
-
-// one entry per lane (R zeros, then the literal unless lit == kNoLit; R = 0 and no literal: nothing), in lane order
-__device__ __forceinline__ void emit_entries(uint32_t R, uint32_t lit, const uint2* tab, const uint32_t* runcls, uint32_t* stage, uint32_t& base) {
-    const uint32_t q = run_caps(R);
-    const uint32_t rem = R - q * kRunCap;
-    uint64_t rv = 0;
-    uint32_t rl = 0;
-    if (rem) run_token(tab, runcls, rem, rv, rl);
-    const uint2 lc = tab[lit < 256u ? lit : 261u];
-    const uint64_t V = rv | ((uint64_t)lc.x << rl);  // <= 38 + 24 bits
-    const uint32_t vlen = rl + lc.y;
-    const uint32_t caplen = q ? q * (tab[260].y + 14u) : 0u;
-    const uint32_t len = caplen + vlen;
-    const uint32_t inc = wave_scan_add(len);
-    uint32_t pos = base + inc - len;
-    base += read_lane(inc, 63);
-    if (q) pos += emit_run(stage, tab, runcls, pos, q * kRunCap);
-    if (vlen) or_bits64(stage, pos, (uint32_t)V, (uint32_t)(V >> 32), vlen);
-}
-
 __device__ __forceinline__ void emit_row_sparse(const uint32_t (&w)[4], const RowCtx& rc, uint32_t in_size, const uint2* tab, const uint32_t* runcls,
                                                 uint32_t* stage, uint32_t& base, uint32_t* queue) {
     if (rc.valid == 0u) return;
@@ -564,112 +385,6 @@ __device__ __forceinline__ void load_block_rows(const uint8_t* __restrict__ in, 
                                                 RowCtx (&rc)[4], uint32_t* scr) {
     issue_block_loads(in, in_size, segmask, W);
     chain_block_rows(in_size, W, rc, scr);
-}
-
-// rotate the rows through W[0] / rc[0]: the row bodies exist once in the instruction stream; four turns put everything back
-__device__ __forceinline__ void rotate_rows(uint32_t (&W)[4][4], RowCtx (&rc)[4]) {
-    const uint32_t t0 = W[0][0], t1 = W[0][1], t2 = W[0][2], t3 = W[0][3];
-    const RowCtx tc = rc[0];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        W[q][0] = W[q + 1][0];
-        W[q][1] = W[q + 1][1];
-        W[q][2] = W[q + 1][2];
-        W[q][3] = W[q + 1][3];
-        rc[q] = rc[q + 1];
-    }
-    W[3][0] = t0;
-    W[3][1] = t1;
-    W[3][2] = t2;
-    W[3][3] = t3;
-    rc[3] = tc;
-}
-
-// A wave whose four rows are all sparse (the segments of the "medium" blocks: every 4 KiB non-zero, a few literals per row)
-// takes them as ONE queue, and the queue is the segment's entry list as it stands.  Between sparse rows nothing special
-// happens at a row boundary: the zeros in front of a row's first literal are the gap to the entry before it, whichever row
-// that one came from; only entry 0 looks outside the segment (rc[0].zb0).
-//
-// Such a segment rarely holds more than 64 granules that are not all zero (planes 1-2 of the xdelta planes: 16 to 32 of 256 on
-// average, tools/sparse_census.py), so those granules are first compacted into ONE row, in position order: a lane that holds
-// one hands its four words and its block position to lane (granules of the rows before) + (granules of lower lanes of its
-// row), through the wave's own queue words -- five columns of 64 words, read back before the first entry is written there.
-// One lane_lits, one scan and one entry loop then do what took four of each, with most lanes idle in every one of them.
-// Zero granules between compacted neighbours are the position gap, as they are between rows.  False: more than 64 such
-// granules, or too many entries for the queue -- the caller goes row by row (the same entries in the same order; keeping the
-// four-row body beside the compacted one for the first case cost k_hist 16 bytes of scratch).  W is never written here.
-constexpr uint32_t kCompactWords = 5u * 64u;  // the compaction's columns: w0..w3 and the position
-static_assert(kCompactWords <= kQueueEntries, "the compaction's scratch stays inside the wave's own queue slot (k_hist's and k_encode's own-count queues alike)");
-
-__device__ __forceinline__ bool hist_segment_sparse(const uint32_t (&W)[4][4], const RowCtx (&rc)[4], uint32_t in_size, uint32_t* h,
-                                                    const uint32_t* runcls, uint32_t* queue, ListSink& sink) {
-    const uint32_t l = lane_id();
-    const uint32_t last = rc[0].last | rc[1].last | rc[2].last | rc[3].last;  // the block ends in this segment: the run that reaches its end
-    unsigned long long nzg[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) nzg[r] = __ballot((W[r][0] | W[r][1] | W[r][2] | W[r][3]) != 0u);  // (bytes behind the block end were masked to zero at the load)
-    const uint32_t g1 = (uint32_t)__popcll(nzg[0]), g2 = g1 + (uint32_t)__popcll(nzg[1]), g3 = g2 + (uint32_t)__popcll(nzg[2]);
-    const uint32_t ng = g3 + (uint32_t)__popcll(nzg[3]);
-    if (ng > 64u) return false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if ((W[r][0] | W[r][1] | W[r][2] | W[r][3]) != 0u) {
-            const uint32_t s = (r == 0 ? 0u : r == 1 ? g1 : r == 2 ? g2 : g3) +
-                               __builtin_amdgcn_mbcnt_hi((uint32_t)(nzg[r] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nzg[r], 0u));
-            queue[s] = W[r][0];
-            queue[64u + s] = W[r][1];
-            queue[128u + s] = W[r][2];
-            queue[192u + s] = W[r][3];
-            queue[256u + s] = rc[r].rb + 16u * l;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    uint32_t cg[4] = {0u, 0u, 0u, 0u};
-    uint32_t pos0 = 0;
-    if (l < ng) {
-        cg[0] = queue[l];
-        cg[1] = queue[64u + l];
-        cg[2] = queue[128u + l];
-        cg[3] = queue[192u + l];
-        pos0 = queue[256u + l];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();  // every lane holds its granule: the entries may take the same words
-    uint32_t t = lane_lits(cg);
-    const uint32_t n = (uint32_t)__popc(t);
-    const uint32_t inc = wave_scan_add(n);
-    const uint32_t T = read_lane(inc, 63) + (last ? 1u : 0u);
-    if (T > kQueueEntries) return false;
-    if (T == 0) return true;  // nothing but zeros, and the block goes on
-    uint32_t k = inc - n;
-    while (t) {
-        const uint32_t i = (uint32_t)__builtin_ctz(t);
-        t &= t - 1;
-        queue[k++] = ((pos0 + i) << 9) | granule_byte_dyn(cg[0], cg[1], cg[2], cg[3], i);
-    }
-    if (last && l == 0) queue[T - 1u] = (in_size << 9) | kNoLit;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (sink.n != kListNone && sink.n + T <= kListCap) {
-        for (uint32_t c = l; c < T; c += 64) sink.dst[sink.n + c] = queue[c];
-        sink.n += T;
-    } else {
-        sink.n = kListNone;
-    }
-    const uint32_t before0 = rc[0].rb - rc[0].zb0;
-    for (uint32_t c = 0; c < T; c += 64) {
-        const uint32_t k = c + l;
-        if (k < T) {
-            const uint32_t e = queue[k];
-            const uint32_t before = k ? (queue[k - 1u] >> 9) + 1u : before0;  // position behind the literal before this one
-            const uint32_t R = (e >> 9) - before, lit = e & 0x1FFu;
-            if (R) hist_run(h, runcls, R);
-            if (lit < 256u) atomicAdd(&h[lit], 1u);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();  // the queue is reused by the next block
-    return true;
 }
 
 __device__ __forceinline__ void hist_rows(uint32_t (&W)[4][4], RowCtx (&rc)[4], uint32_t in_size, uint32_t* myhist, const uint32_t* runcls,

@@ -11,6 +11,8 @@ independently of) a GPU run:
 
 tests/test_kernel_model.py drives this against oracle/.
 """
+import functools
+
 import numpy as np
 
 CAP = 16662
@@ -183,6 +185,7 @@ def gf_mul(a, b):
     return r
 
 
+@functools.lru_cache(maxsize=None)
 def x_pow_bytes(nbytes):
     """x^(8*nbytes) mod P in reflected form"""
     r = 0x80000000  # 1
@@ -291,6 +294,47 @@ def crc_strided(msg, nthr=1024):
             c = gf_mul(c, G)
         c ^= vword(tid)
         total ^= gf_mul(c, x_pow_bytes(4 * (tid + 1)))
+    return total ^ 0xFFFFFFFF
+
+
+def crc_wave_words(msg, lanes=64):
+    """CRC-32C of msg the way ONE wave of k_tree does it for a staged small block (stage_small_block): crc_strided's
+    decomposition with the kernel's own addressing.  The image is V = X || msg in 32-bit words, zero behind V and one zero
+    word in front (index -1); virtual word r counted from the end of V is image words a and a + 1 joined at byte Lv & 3
+    (v_alignbyte), a = (Lv >> 2) - 1 - r.  Lane l takes r = l, l + lanes, ...: its top word may be missing (a < -1) or may
+    reach in front of V (a = -1), every other one is there; Horner with x^(8*4*lanes) per step -- ceil(words / lanes)
+    steps for the fullest lane --, then x^(8*4*(l+1)) to the end of V and an XOR over the lanes."""
+    V = init_prefix() + bytes(msg)
+    Lv = len(V)
+    padded = V + bytes(8 + (-Lv) % 4)
+    words = [int.from_bytes(padded[4 * i: 4 * i + 4], "little") for i in range(len(padded) // 4)]
+
+    def img(i):
+        assert -1 <= i < len(words)
+        return 0 if i < 0 else words[i]
+
+    sh = Lv & 3
+
+    def vword(a):
+        return ((img(a + 1) << 32 | img(a)) >> (8 * sh)) & 0xFFFFFFFF
+
+    nvw = (Lv + 3) >> 2
+    K = (nvw + lanes - 1) // lanes
+    G = x_pow_bytes(4 * lanes)
+    total = 0
+    for l in range(lanes):
+        c = 0
+        if l < nvw:
+            a = (Lv >> 2) - 1 - (l + lanes * (K - 1))
+            if K > 1:
+                c = vword(max(a, -1)) if a >= -1 else 0
+                c = gf_mul(c, G)
+                for _ in range(K - 2):
+                    a += lanes
+                    c = gf_mul(c ^ vword(a), G)
+                a += lanes
+            c ^= vword(a)
+        total ^= gf_mul(c, x_pow_bytes(4 * (l + 1)))
     return total ^ 0xFFFFFFFF
 
 
