@@ -466,8 +466,9 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
  * outside 2..5, init_nr_samples outside 0 .. 2^28, nsections outside 1..4, a NULL or misaligned d_state -- and for a d_planar
  * off its 4-byte alignment; RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels, before anything is launched, and for a stream
  * call of 2^31 - 2^17 rows or more.  A refused call writes nothing.  Asynchronous on `stream`; the entries allocate nothing.
- * Of the other stages the FIR pre-filter has a planar form too (rspt_hip_fir_prefilter_planar_batch_dev below); the zero-phase
- * IIR, median, peak and PRDN stages stay native-only. */
+ * Of the other stages the FIR pre-filter, the median and PRDN have planar forms too (rspt_hip_fir_prefilter_planar_batch_dev,
+ * rspt_hip_median_filter_planar_batch_dev, rspt_hip_prdn_planar_batch_dev below); the zero-phase IIR and the peak stages stay
+ * native-only. */
 int rspt_hip_iir_prefilter_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
                                             size_t nr_coefficients, int init_nr_samples, int per_channel, void* stream);
 int rspt_hip_iir_prefilter_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
@@ -641,6 +642,44 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
 int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes); /* 8 + ((W - 1) * nch * bps rounded up to 8) */
 int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state,
                                       void* stream);
+
+/* ---- the rolling-window median on the planar int32 matrix ------------------------------------------------------------
+ * rspt_hip_median_filter_batch_dev / _stream_dev with the matrix of the converters in place of the native blocks (see the planar
+ * IIR and FIR entries above), so that native_to_i32 -> median -> compress_planar runs without leaving it.  The formula, the
+ * window rules and the ordering contract are the native entries'.
+ *   d_src, d_dst    the matrix [nblocks][nch][ns], block b's channel c at d + (b*nch + c)*ns; 4-byte alignment is all it needs
+ *                   (16-byte aligned buffers with ns a multiple of 4 take wider loads and stores).  d_dst == d_src filters in
+ *                   place; any other overlap of the two nblocks*nch*ns*4-byte ranges is RSPT_HIP_ERR_ARG; out of place d_src is
+ *                   only read.
+ *   samples         the WHOLE int32 value is the sample: the handle's bps and byte order have no effect, and the median is
+ *                   stored whole and NOT cut to bps.  So i32_to_native(median_planar(native_to_i32(X))) == median_native(X)
+ *                   for every bps, and compress_planar(median_planar(native_to_i32(X))) gives the streams of
+ *                   compress(median_native(X)).
+ *   batch           one fresh rolling_window_median<double>(window) per row: the window is clamped to ns, window = 1 is a device
+ *                   copy (nothing is done in place), windows above 32 need ns <= 2^18 (else RSPT_HIP_ERR_UNSUPPORTED).
+ *   stream          the blocks of a call are consecutive pieces of one recording: channel c's run is P[0][c][:], P[1][c][:], ...
+ *                   and continues into the next call on the same state.  W is not clamped: it may exceed ns and a whole call.
+ *   d_state         caller-owned, 8-byte aligned, rspt_hip_median_planar_state_bytes(p, window) bytes: uint64 fill, then W - 1
+ *                   rows, oldest first, each row nch int32 values, the valid rows last and zeros in front, padded to a multiple
+ *                   of 8 bytes -- the native state's layout at bps = 4.  On a handle with bps = 4 the two sizes are equal and
+ *                   native and planar stream calls may alternate on one state; on a narrower handle a planar state is its own
+ *                   object, not interchangeable with the native one.  All-zero bytes are a fresh object.  The state's bytes
+ *                   after a call are a function of the recording and W alone.  window = 1: the header, which stays zero.
+ * RSPT_HIP_ERR_ARG for a NULL handle or buffer, a NULL bytes, window = 0, nblocks = 0, nblocks * nch >= 2^31, a matrix off its
+ * 4-byte alignment, buffers that overlap without being the same, a NULL or misaligned d_state; RSPT_HIP_ERR_UNSUPPORTED for more
+ * than 8191 channels, a stream call of 2^31 - 2^17 rows (nblocks * ns) or more and a stateless call on rows of that many
+ * samples, a stateless window above 32 on rows of more than 2^18 samples, and a stream window above 32 with W - 1 > 2^17.
+ * Refusals come before anything is launched, and a refused call writes nothing.  Asynchronous on `stream`, stream-ordered with
+ * every other call on the handle.  What a call stages belongs to the handle's median stage and only grows: for windows up to
+ * 32, with span = the samples one workgroup takes of a row and nsplit = ceil(ns / span), the W - 1 samples in
+ * front of every span but the first of an in-place call and in front of every row of a stream call,
+ *     4 * (W - 1) * nblocks * nch * ((in place ? nsplit - 1 : 0) + (stream ? 1 : 0))  bytes,
+ * plus 8 + 4 * (W - 1) * nch bytes of a stream call's old state; above 32 the native entries' keys and ranks (20 bytes per key of
+ * a piece of up to 2^25 keys).  A stateless out-of-place call of a window up to 32 stages nothing. */
+int rspt_hip_median_filter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* stream);
+int rspt_hip_median_planar_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes); /* 8 + ((W - 1) * nch * 4 rounded up to 8) */
+int rspt_hip_median_filter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* d_state,
+                                             void* stream);
 
 /* ---- the reference's Butterworth designer (host only: no GPU, no handle) -------------------------------------------
  * create_filter_iir(num, den, butterworth, type, order, sampling_rate, cutoff_low, cutoff_high) of

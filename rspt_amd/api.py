@@ -88,6 +88,9 @@ C_ABI = {
     "rspt_hip_median_filter_batch_dev": (_i, [_p, _p, _p, _z, _z, _p]),
     "rspt_hip_median_state_bytes": (_i, [_p, _z, _szp]),
     "rspt_hip_median_filter_stream_dev": (_i, [_p, _p, _p, _z, _z, _p, _p]),
+    "rspt_hip_median_filter_planar_batch_dev": (_i, [_p, _p, _p, _z, _z, _p]),
+    "rspt_hip_median_planar_state_bytes": (_i, [_p, _z, _szp]),
+    "rspt_hip_median_filter_planar_stream_dev": (_i, [_p, _p, _p, _z, _z, _p, _p]),
     "rspt_hip_design_iir": (_i, [_i, _i, _d, _d, _d, _dp, _dp, _szp]),
     "rspt_hip_peak_state_bytes": (_i, [_p, _szp]),
     "rspt_hip_peak_detect_batch_dev": (_i, [_p, _p, _z, _i, _d, _d, _p, _p, _p, _p, _z, _p, _p, _p]),
@@ -648,6 +651,32 @@ class SignalPacker:
             self._call("rspt_hip_median_filter_stream_dev", d_src.data_ptr(), out.data_ptr(), nblocks, int(window), state.data_ptr(), st)
         else:
             self._call("rspt_hip_median_filter_batch_dev", d_src.data_ptr(), out.data_ptr(), nblocks, int(window), st)
+        return out
+
+    def median_planar_state_bytes(self, window):
+        return self._bytes("rspt_hip_median_planar_state_bytes", int(window))
+
+    def median_planar_state(self, window, device=None):
+        """A zeroed state for median_filter_planar_batch(state=...) with this window: rows of nch int32, so the native
+        median_state() only where the handle's bps is 4."""
+        return self._zero_state(self.median_planar_state_bytes(window), device)
+
+    def median_filter_planar_batch(self, d_planar, window, d_out=None, stream=None, state=None):
+        """median_filter_batch on samples that live in int32 (rspt_hip.h: rspt_hip_median_filter_planar_batch_dev / _stream_dev):
+        d_planar is a torch.int32 cuda tensor [nblocks, nch, ns]; in place when d_out is None, else into d_out (same shape, not
+        overlapping d_planar).  The whole int32 value is the sample and the result is stored whole, whatever the handle's bps.
+        Returns the output.  state: None, or a median_planar_state(window) tensor, as in median_filter_batch."""
+        import torch
+
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        out = d_planar if d_out is None else d_out
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == d_planar.numel()
+        st = self._stream(stream, d_planar.device)
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.median_planar_state_bytes(window)
+            self._call("rspt_hip_median_filter_planar_stream_dev", d_planar.data_ptr(), out.data_ptr(), nblocks, int(window), state.data_ptr(), st)
+        else:
+            self._call("rspt_hip_median_filter_planar_batch_dev", d_planar.data_ptr(), out.data_ptr(), nblocks, int(window), st)
         return out
 
     def peak_state_bytes(self):

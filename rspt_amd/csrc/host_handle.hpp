@@ -192,6 +192,8 @@ struct FirStage {
 // rspt_hip_median_filter_batch_dev: the halo rows of an in-place short-window call, and the sort buffers of the generic path
 // (two key buffers and the ranks of one piece of the batch), all behind the stage's last call.
 // rspt_hip_median_filter_stream_dev adds `head`, the staged copy of a carried-state call's old state, under the same rule.
+// The planar entries (rspt_hip_median_filter_planar_batch_dev / _stream_dev) use the same buffers: `halo` holds the fronts of the
+// short path (the W - 1 samples in front of a span, k_firp_front), `head` the staged state, the keys and ranks the generic path's.
 struct MedianStage {
     StageBuf halo, head;
     Dev<uint64_t> keys_a, keys_b;

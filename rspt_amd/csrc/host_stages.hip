@@ -504,8 +504,10 @@ int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, voi
 // The decomposition of a sliding-window stage on the matrix (PlanarWin): a row = (block, channel) of ns samples, `lanes` lanes of
 // `run` outputs along it -- the smallest power of two that covers the row, at most `threads` --, threads / lanes rows to a
 // workgroup, and, as in win_geom, spans along the row until there are about four workgroups per CU, each span at least
-// 4 (K - 1) samples and a multiple of the chunk.  Only rows of more than one chunk are ever split.
-static PlanarWin planar_win(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, bool in_place, bool carried) {
+// 4 (K - 1) samples and a multiple of the chunk.  Only rows of more than one chunk are ever split.  `min_lanes` (a power of two)
+// bounds the rows of a workgroup for a kernel that keeps something per row.
+static PlanarWin planar_win(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, bool in_place, bool carried,
+                            uint32_t min_lanes = 1) {
     const Geom& g = p->g;
     PlanarWin f{};
     f.rows = (uint64_t)nblocks * g.nch;
@@ -514,7 +516,7 @@ static PlanarWin planar_win(const rspt_hip_packer* p, size_t nblocks, uint32_t K
     f.ns = g.ns;
     f.K = K;
     const uint64_t runs = ((uint64_t)g.ns + run - 1) / run;
-    f.lanes = 1;
+    f.lanes = min_lanes;
     while (f.lanes < threads && f.lanes < runs) f.lanes *= 2;
     f.rpw = threads / f.lanes;
     const uint32_t C = f.lanes * run;
@@ -626,7 +628,8 @@ static hipError_t launch_med_short_w(uint32_t bps, const WinGeom& f, const void*
 }
 
 // The generic path on the pairs [pair0, pair0 + npairs) of the batch: sort (tile sort, merge passes), then walk.  STREAM: a pair
-// is a (segment, channel) of a carried-state call and f.ns the segment capacity (median.hip).
+// is a (segment, channel) of a carried-state call and f.ns the segment capacity (median.hip).  BPS = kMedPlanar: the carried call
+// on the planar matrix, through k_medp_tile_sort / k_medp_walk (median_planar.hip).
 template <int BPS, bool STREAM = false>
 static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const uint8_t* src, uint8_t* dst, uint64_t pair0, uint64_t npairs,
                                      bool aligned, hipStream_t st, const MedSeg& sg = MedSeg{}) {
@@ -637,7 +640,9 @@ static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const
     uint64_t* b = ms.keys_b;
     uint32_t* rank = ms.rank;
     const bool one_tile = tiles == 1;
-    if (aligned) hipLaunchKernelGGL((k_med_tile_sort<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src,
+    if constexpr (BPS == kMedPlanar)
+        hipLaunchKernelGGL(k_medp_tile_sort, dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a, one_tile ? rank : nullptr, f, pair0, sg);
+    else if (aligned) hipLaunchKernelGGL((k_med_tile_sort<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src,
                                     a, one_tile ? rank : nullptr, f, pair0, sg);
     else hipLaunchKernelGGL((k_med_tile_sort<BPS, false, STREAM>), dim3((uint32_t)(npairs * tiles)), dim3(kMedThreads), 0, st, src, a,
                             one_tile ? rank : nullptr, f, pair0, sg);
@@ -654,7 +659,8 @@ static hipError_t launch_med_generic(rspt_hip_packer* p, const WinGeom& f, const
     const uint32_t spans = ((STREAM ? sg.L : ns) + kMedSpan - 1) / kMedSpan;
     const uint32_t n0 = (ns + 31) / 32;
     const size_t lds = (size_t)(n0 + (n0 + 31) / 32) * sizeof(uint32_t);
-    if (aligned) hipLaunchKernelGGL((k_med_walk<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f,
+    if constexpr (BPS == kMedPlanar) hipLaunchKernelGGL(k_medp_walk, dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0, sg);
+    else if (aligned) hipLaunchKernelGGL((k_med_walk<BPS, (BPS == 4 || BPS == 2), STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f,
                                     pair0, sg);
     else hipLaunchKernelGGL((k_med_walk<BPS, false, STREAM>), dim3((uint32_t)(npairs * spans)), dim3(64), lds, st, a, rank, dst, f, pair0, sg);
     return hipGetLastError();
@@ -788,6 +794,122 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
 int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
     return median_call(p, d_src, d_dst, nblocks, window, d_state, stream);
+}
+
+// ---- rolling median on the planar int32 matrix (median_planar.hip) ----
+template <uint32_t N>
+static void launch_med_planar(const PlanarWin& f, const int32_t* src, int32_t* dst, const int32_t* front, bool wide, hipStream_t st, const uint8_t* head) {
+    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+    if (wide) hipLaunchKernelGGL((k_med_planar<N, true>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, front, f, head);
+    else hipLaunchKernelGGL((k_med_planar<N, false>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, front, f, head);
+}
+
+// Both planar median entries: d_state == NULL is the stateless call, one fresh window per row, the window clamped to ns; else the
+// blocks are consecutive pieces of one recording behind the state and the window is the recording's.  The handle's MedianStage
+// holds the fronts of the short path (`halo`: 4 (W - 1) nblocks nch npiece bytes), the staged state (`head`) and the generic
+// path's keys and ranks.
+static int median_planar_call(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
+    if (!p || !d_src || !d_dst || window == 0 || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    if (s0 % 4 || d0 % 4) return RSPT_HIP_ERR_ARG;
+    const uint64_t bytes = (uint64_t)nblocks * g.nch * g.ns * 4u;
+    const bool in_place = s0 == d0;
+    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
+    // a row's samples, and a carried call's run, are indexed in 32 bits with a chunk's reach beyond the last one
+    const uint64_t rows = (uint64_t)nblocks * g.ns;  // of a carried call's run
+    if ((d_state ? rows : (uint64_t)g.ns) >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    const uint32_t W = (uint32_t)std::min<size_t>(window, d_state ? (size_t)kMedMaxCarry + 2 : g.ns);
+    const bool is_short = W <= kMedShortMax;
+    if (!is_short && (d_state ? W - 1 > kMedMaxCarry : g.ns > kMedMaxRanks)) return RSPT_HIP_ERR_UNSUPPORTED;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (W == 1) {  // a copy; a state is its header and stays zero
+        if (in_place) return RSPT_HIP_OK;
+        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, st));
+        return RSPT_HIP_OK;
+    }
+    MedianStage& ms = p->med;
+    // (the short path's decomposition; the generic path takes only its row count)
+    const PlanarWin f = planar_win(p, nblocks, W, kMedThreads, kMedRun, in_place, d_state != nullptr, kMedpMinLanes);
+    const uint64_t front_n = is_short ? f.rows * f.npiece * (uint64_t)(W - 1) : 0;  // samples of all fronts
+    const uint64_t head_n = d_state ? (uint64_t)(W - 1) * g.nch : 0;             // samples of the staged state
+    // generic: (row) items of ns keys -- with a state (segment, channel) items of S keys -- in pieces of up to 2^25 keys
+    // The generic kernels (k_med_tile_sort, k_med_merge, k_med_walk and their planar bodies) read block_bytes, stride, nch, ns and K
+    // of a WinGeom and nothing else: cw, subs, ncg, span, nsplit and units belong to the short kernels' decomposition (win_geom)
+    // and stay zero here.  A generic kernel that comes to read one of them needs it set here as well.
+    MedSeg sg{};
+    WinGeom fg{};
+    fg.nch = d_state ? g.nch : 1u;  // (stateless: a row is a block of one channel of 4-byte samples)
+    fg.stride = fg.nch * 4u;
+    fg.block_bytes = (uint64_t)g.ns * fg.stride;
+    fg.ns = g.ns;
+    fg.K = W;
+    uint64_t items = f.rows, piece_items = 0;
+    if (!is_short) {
+        if (d_state) {
+            fg.ns = median_segment_rows(W, rows);
+            sg.L = fg.ns - (W - 1);
+            sg.nseg = (uint32_t)((rows + sg.L - 1) / sg.L);
+            sg.N = (uint32_t)rows;
+            sg.bns = g.ns;
+            items = (uint64_t)sg.nseg * g.nch;
+        }
+        piece_items = std::min<uint64_t>(items, std::max<uint64_t>(1, (1ull << 25) / fg.ns));
+    }
+    if (int rc = median_reserve(ms, front_n * 4u, d_state ? 8 + head_n * 4u : 0, piece_items * fg.ns)) return rc;
+    auto mover_grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096)); };
+    hipError_t e = hipSuccess;
+    if (d_state) {  // stage the state, then write the new one from d_src: both before any kernel stores to d_dst
+        sg.head = ms.head;
+        hipLaunchKernelGGL((k_med_carry<false, uint32_t>), mover_grid(head_n), dim3(256), 0, st, (const uint32_t*)d_src, (uint8_t*)ms.head,
+                           (uint8_t*)d_state, head_n, (uint64_t)0, (uint64_t)(W - 1), rows);
+        hipLaunchKernelGGL(k_medp_save, mover_grid(head_n), dim3(256), 0, st, d_src, (const uint8_t*)ms.head, (uint8_t*)d_state, head_n, g.nch, g.ns,
+                           (uint64_t)(W - 1), rows);
+        e = hipGetLastError();
+    }
+    if (is_short) {
+        int32_t* front = reinterpret_cast<int32_t*>((uint8_t*)ms.halo);
+        if (e == hipSuccess && front_n) {
+            hipLaunchKernelGGL(k_firp_front, mover_grid(front_n), dim3(256), 0, st, d_src, reinterpret_cast<const int32_t*>((uint8_t*)ms.head + 8), front, f);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            const bool wide = s0 % 16 == 0 && d0 % 16 == 0 && g.ns % 4 == 0;
+            const uint8_t* head = d_state ? (const uint8_t*)ms.head : nullptr;
+            if (W <= 4) launch_med_planar<4>(f, d_src, d_dst, front, wide, st, head);
+            else if (W <= 8) launch_med_planar<8>(f, d_src, d_dst, front, wide, st, head);
+            else if (W <= 16) launch_med_planar<16>(f, d_src, d_dst, front, wide, st, head);
+            else launch_med_planar<32>(f, d_src, d_dst, front, wide, st, head);
+            e = hipGetLastError();
+        }
+    } else {
+        // (with a state from the last segment to the first: a walk writes its segment's new rows, which no segment sorted later reads)
+        for (uint64_t item0 = 0; e == hipSuccess && item0 < items; item0 += piece_items) {
+            const uint64_t ni = std::min(piece_items, items - item0);
+            e = d_state ? launch_med_generic<kMedPlanar, true>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, true, st, sg)
+                        : launch_med_generic<4>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, true, st);
+        }
+    }
+    return finish_window_call(p, ms.last, e, st);
+}
+
+int rspt_hip_median_filter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* stream) {
+    return median_planar_call(p, d_src, d_dst, nblocks, window, nullptr, stream);
+}
+
+int rspt_hip_median_planar_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) {
+    if (!p || !bytes || window == 0) return RSPT_HIP_ERR_ARG;
+    if (window > kMedShortMax && window - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;
+    *bytes = 8 + (((size_t)(window - 1) * p->g.nch * 4u + 7) & ~(size_t)7);
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_median_filter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* d_state,
+                                             void* stream) {
+    if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
+    return median_planar_call(p, d_src, d_dst, nblocks, window, d_state, stream);
 }
 
 // ---- PRDN: the quality figure of the reference's harness (quality.hip) -----------------------------------------------------------

@@ -60,7 +60,16 @@ struct MedSeg {
     uint32_t L;           // new rows of a segment (the last one may hold fewer)
     uint32_t nseg;        // segments per channel: ceil(N / L)
     uint32_t N;           // rows of the call
+    uint32_t bns;         // the planar matrix only: samples of a block's row (row r of the call is sample r % bns of block r / bns)
 };
+
+// BPS inside the bodies of k_med_tile_sort / k_med_walk where they work on the planar int32 matrix [nblocks][nch][ns]
+// (k_medp_tile_sort / k_medp_walk, median_planar.hip): the sample is a whole aligned word, and row r of a carried call's run of
+// channel ch lies at med_planar_at.
+constexpr int kMedPlanar = 0;
+__device__ __forceinline__ uint64_t med_planar_at(const MedSeg& sg, uint32_t nch, uint32_t ch, uint32_t r) {
+    return (((uint64_t)(r / sg.bns) * nch + ch) * sg.bns + r % sg.bns) * 4u;
+}
 
 // ---- short windows ----
 
@@ -194,60 +203,11 @@ __device__ __forceinline__ int32_t med_key_value(uint64_t k) { return (int32_t)(
 // `rank` (ns <= kMedTile: the sort is complete), also rank[p][t] = position of sample t.
 // STREAM: pair = (segment counted from the last, channel), g.ns = the segment capacity S; index t of the segment is row
 // j L - (W - 1) + t of the call, a row of the staged head where that is negative, and a pad (above every sample, unique) from the
-// segment's own length on.
+// segment's own length on.  The body is a file of its own: k_medp_tile_sort (median_planar.hip) includes it with BPS = kMedPlanar,
+// where the rows of the call lie in the planar matrix (med_planar_at) and the head's where they always do.
 template <int BPS, bool ALIGNED, bool STREAM = false>
 __global__ __launch_bounds__(kMedThreads) void k_med_tile_sort(const uint8_t* src, uint64_t* keys, uint32_t* rank, WinGeom g, uint64_t pair0, MedSeg sg) {
-    __shared__ uint64_t sk[kMedTile];
-    const uint32_t tiles = (g.ns + kMedTile - 1) / kMedTile;
-    const uint64_t p = blockIdx.x / tiles;
-    const uint32_t t0 = (blockIdx.x % tiles) * kMedTile;
-    const uint64_t pair = pair0 + p;
-    const uint32_t ch = (uint32_t)(pair % g.nch);
-    if (STREAM) {
-        const uint32_t j = sg.nseg - 1u - (uint32_t)(pair / g.nch);
-        const uint32_t n = g.K - 1u + min(sg.L, sg.N - j * sg.L);
-        const int64_t first = (int64_t)j * sg.L - (int64_t)(g.K - 1u);  // the call's row of index 0
-        const uint8_t* hrow0 = sg.head + 8 + (uint64_t)(g.K - 1u) * g.stride + ch * BPS;  // where row 0 would be in the head
-        for (uint32_t i = threadIdx.x; i < kMedTile; i += kMedThreads) {
-            const uint32_t t = t0 + i;
-            uint64_t k = ~0ull;
-            if (t < n) {
-                const int64_t r = first + (int64_t)t;
-                const uint8_t* at = r < 0 ? hrow0 - (uint64_t)(-r) * g.stride : src + (uint64_t)r * g.stride + ch * BPS;
-                k = med_key(sample_load<BPS>(at, ALIGNED), t);
-            } else if (t < g.ns) {
-                k = 0xFFFFFFFF00000000ull | t;
-            }
-            sk[i] = k;
-        }
-    } else {
-        const uint8_t* base = src + (pair / g.nch) * g.block_bytes + ch * BPS;
-        for (uint32_t i = threadIdx.x; i < kMedTile; i += kMedThreads) {
-            const uint32_t t = t0 + i;
-            sk[i] = t < g.ns ? med_key(sample_load<BPS>(base + (uint64_t)t * g.stride, ALIGNED), t) : ~0ull;  // (padding sorts last)
-        }
-    }
-    __syncthreads();
-    for (uint32_t k = 2; k <= kMedTile; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < kMedTile; i += kMedThreads) {
-                const uint32_t ixj = i ^ j;
-                if (ixj > i) {
-                    const uint64_t x = sk[i], y = sk[ixj];
-                    if (((i & k) == 0) == (x > y)) {
-                        sk[i] = y;
-                        sk[ixj] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    uint64_t* kp = keys + p * g.ns;
-    for (uint32_t i = threadIdx.x; i < kMedTile && t0 + i < g.ns; i += kMedThreads) {
-        kp[t0 + i] = sk[i];
-        if (rank) rank[p * g.ns + (uint32_t)sk[i]] = t0 + i;
-    }
+#include "k_med_tile_sort_body.hpp"
 }
 
 // One merge pass: runs of `width` sorted keys become runs of 2 width.  Every key finds its place by a binary search of the
@@ -335,127 +295,12 @@ struct MedBits {
 // (p = rank of the lower median, below = window members with a smaller rank) is computed alike by every lane.
 // STREAM: pair and g.ns as in k_med_tile_sort; the spans cover the segment's new rows only (indices W - 1 .. n - 1), and `v0` is
 // the first index that holds a row of the recording: W - 1 - fill in the first segment, 0 in every other.
+// The body is a file of its own: k_medp_walk (median_planar.hip) includes it with BPS = kMedPlanar and stores the segment's new
+// rows into the planar matrix (med_planar_at).
 template <int BPS, bool ALIGNED, bool STREAM = false>
 __global__ __launch_bounds__(64) void k_med_walk(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ rank, uint8_t* dst, WinGeom g,
                                                  uint64_t pair0, MedSeg sg) {
-    extern __shared__ uint32_t med_lds[];
-    const uint32_t lane = threadIdx.x;
-    const bool writer = lane == 0;
-    const uint32_t ns = g.ns, W = g.K;
-    const uint32_t spans = ((STREAM ? sg.L : ns) + kMedSpan - 1) / kMedSpan;
-    const uint64_t p = blockIdx.x / spans;
-    const uint64_t pair = pair0 + p;
-    uint32_t lo = (blockIdx.x % spans) * kMedSpan, n = ns, v0 = 0;
-    uintptr_t out0;  // address of index 0 of the pair's channel in dst (STREAM: only indices from W - 1 on are stored)
-    if (STREAM) {
-        const uint32_t j = sg.nseg - 1u - (uint32_t)(pair / g.nch);
-        n = W - 1u + min(sg.L, sg.N - j * sg.L);
-        lo += W - 1u;
-        if (lo >= n) return;  // (a span past a short last segment)
-        if (j == 0) v0 = W - 1u - (uint32_t)*reinterpret_cast<const uint64_t*>(sg.head);
-        out0 = reinterpret_cast<uintptr_t>(dst) + (uint32_t)(pair % g.nch) * BPS + (uint64_t)((int64_t)j * sg.L - (int64_t)(W - 1u)) * g.stride;
-    } else {
-        out0 = reinterpret_cast<uintptr_t>(dst) + (pair / g.nch) * g.block_bytes + (uint32_t)(pair % g.nch) * BPS;
-    }
-    const uint32_t hi = min(n, lo + kMedSpan);
-    const uint32_t n0 = (ns + 31) / 32;
-    MedBits bm{med_lds, med_lds + n0, (n0 + 31) / 32};
-    for (uint32_t i = lane; i < n0 + bm.n1; i += 64) med_lds[i] = 0;
-    __syncthreads();
-    const uint32_t* rk = rank + p * ns;
-    const uint64_t* kp = keys + p * ns;
-    // the window of output lo - 1: samples [s0, lo)
-    const uint32_t s0 = lo >= W + v0 ? lo - W : v0;
-    for (uint32_t t = s0 + lane; t < lo; t += 64) {
-        const uint32_t r = rk[t];
-        atomicOr(&bm.b0[r >> 5], 1u << (r & 31));
-        atomicOr(&bm.b1[r >> 10], 1u << ((r >> 5) & 31));
-    }
-    __syncthreads();
-    uint32_t m = lo - s0;  // reals in the window
-    uint32_t pm = 0, below = 0;
-    if (m) {  // the lower median: set bit number (m - 1) / 2, by a wave-wide count over the words of b0
-        const uint32_t k = (m - 1) / 2;
-        const uint32_t per = (n0 + 63) / 64, w0 = lane * per, w1 = min(n0, w0 + per);
-        uint32_t cnt = 0;
-        for (uint32_t w = w0; w < w1; ++w) cnt += __builtin_popcount(bm.b0[w]);
-        uint32_t incl = cnt;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t v = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += v;
-        }
-        const uint32_t excl = incl - cnt;
-        uint32_t found = 0;
-        if (excl <= k && k < incl) {  // exactly one lane
-            uint32_t left = k - excl;
-            for (uint32_t w = w0; w < w1; ++w) {
-                uint32_t bits = bm.b0[w];
-                const uint32_t c = __builtin_popcount(bits);
-                if (left < c) {
-                    for (; left; --left) bits &= bits - 1;
-                    found = (w << 5) | (uint32_t)__builtin_ctz(bits);
-                    break;
-                }
-                left -= c;
-            }
-        }
-        const uint64_t who = __ballot(excl <= k && k < incl);
-        pm = __shfl(found, (int)__builtin_ctzll(who), 64);
-        below = k;
-    }
-    for (uint32_t base = lo; base < hi; base += 64) {
-        const uint32_t n = min(64u, hi - base);
-        const uint32_t t = base + lane;
-        const uint32_t rn = t < hi ? rk[t] : 0;
-        const uint32_t ro = (t < hi && t >= W + v0) ? rk[t - W] : 0;
-        uint32_t myp = 0, myq = 0;
-        for (uint32_t j = 0; j < n; ++j) {
-            const uint32_t tj = base + j;
-            const uint32_t r = __shfl(rn, (int)j, 64);
-            bm.set(r, writer);
-            if (m == 0) {
-                pm = r;
-                below = 0;
-            } else if (r < pm) {
-                ++below;
-            }
-            ++m;
-            if (tj >= W + v0) {  // the window is full: sample tj - W leaves
-                const uint32_t o = __shfl(ro, (int)j, 64);
-                --m;
-                bm.clear(o, writer);
-                if (o < pm) {
-                    --below;
-                } else if (o == pm) {
-                    const uint32_t nx = bm.next(pm);
-                    if (nx != ~0u) {
-                        pm = nx;
-                    } else {
-                        pm = bm.prev(pm);
-                        --below;
-                    }
-                }
-            }
-            const uint32_t k = (m - 1) / 2;
-            while (below < k) {
-                pm = bm.next(pm);
-                ++below;
-            }
-            while (below > k) {
-                pm = bm.prev(pm);
-                --below;
-            }
-            const uint32_t q = (m & 1) ? pm : bm.next(pm);
-            if (lane == j) {
-                myp = pm;
-                myq = q;
-            }
-        }
-        if (lane < n) {
-            const int64_t sum = (int64_t)med_key_value(kp[myp]) + (int64_t)med_key_value(kp[myq]);
-            sample_store<BPS>(reinterpret_cast<uint8_t*>(out0 + (uint64_t)t * g.stride), (int32_t)(sum / 2), ALIGNED);
-        }
-    }
+#include "k_med_walk_body.hpp"
 }
 
 // ---- carried state ----

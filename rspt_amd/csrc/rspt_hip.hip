@@ -40,6 +40,7 @@
 #include "fir.hip"
 #include "fir_planar.hip"
 #include "median.hip"
+#include "median_planar.hip"
 #include "peak.hip"
 #include "quality.hip"
 #include "quality_planar.hip"
