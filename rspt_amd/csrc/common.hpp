@@ -71,6 +71,13 @@ struct WinGeom {
     uint64_t units;    // nblocks * ncg * nsplit
 };
 
+// Where sample `pos` of channel c of a carried call's run lies in the planar int32 matrix [nblocks][nch][ns], in samples: the
+// run of a channel is row c of block 0, then row c of block 1, ...  (pos in 32 or in 64 bits: the division is the caller's.)
+template <class Pos>
+__device__ __forceinline__ uint64_t planar_run_at(Pos pos, uint32_t nch, uint64_t c, uint32_t ns) {
+    return ((uint64_t)(pos / ns) * nch + c) * ns + pos % ns;
+}
+
 // CRC-32C constants for the parallel checksum (tools/kernel_model.py:crc_parallel).
 struct CrcConsts {
     uint32_t table[4][256];  // slice-by-4 LUTs, reflected poly 0x82F63B78; table[0] = hzr_crc32c.c:32

@@ -31,7 +31,8 @@
 
 namespace rspt {
 
-// Decomposition of a sliding-window stage on the planar matrix (the host's planar_win makes it); nothing in it is FIR's alone.
+// Decomposition of a sliding-window stage on the planar matrix (the host's planar_win makes it, with win_geom's split rule);
+// nothing in it is FIR's alone: the median's short path runs on it too.
 struct PlanarWin {
     uint64_t rows;     // nblocks * nch rows of ns samples
     uint64_t total;    // rows * ns: samples of the matrix
@@ -188,16 +189,22 @@ __global__ __launch_bounds__(256) void k_firp_head(const int32_t* __restrict__ s
         head[i] = st ? rows[i] : src[(i % nch) * ns];
 }
 
-// state <- the last K - 1 rows of (head ++ the call's run of N = nblocks * ns samples per channel); and the state has started.
+// The gather of both stages' save movers (k_firp_save, k_medp_save): rows <- the last k1 rows of (head's k1 rows ++ the call's
+// run of N = nblocks * ns samples per channel), n = k1 * nch samples, time-major.
+__device__ __forceinline__ void planar_save_rows(const int32_t* __restrict__ src, const int32_t* __restrict__ head, int32_t* __restrict__ rows, uint64_t n,
+                                                 uint32_t nch, uint32_t ns, uint64_t k1, uint64_t N) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        const uint64_t j = i / nch, c = i % nch;
+        const int64_t pos = (int64_t)N - (int64_t)k1 + (int64_t)j;  // sample of the run
+        rows[i] = pos >= 0 ? src[planar_run_at((uint64_t)pos, nch, c, ns)] : head[(j + N) * nch + c];
+    }
+}
+
+// state <- the last K - 1 rows of (head ++ the call's run of N samples per channel); and the state has started.
 __global__ __launch_bounds__(256) void k_firp_save(const int32_t* __restrict__ src, const int32_t* __restrict__ head, uint64_t* started,
                                                    int32_t* __restrict__ rows, uint64_t n, uint32_t nch, uint32_t ns, uint32_t K, uint64_t N) {
-    const uint64_t i0 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    for (uint64_t i = i0; i < n; i += (uint64_t)gridDim.x * 256u) {
-        const uint64_t j = i / nch, c = i % nch;
-        const int64_t pos = (int64_t)N - (int64_t)(K - 1) + (int64_t)j;  // sample of the run
-        rows[i] = pos >= 0 ? src[((uint64_t)pos / ns * nch + c) * ns + (uint64_t)pos % ns] : head[(j + N) * nch + c];
-    }
-    if (i0 == 0) *started = 1;
+    planar_save_rows(src, head, rows, n, nch, ns, K - 1, N);
+    if ((uint64_t)blockIdx.x * 256u + threadIdx.x == 0) *started = 1;
 }
 
 // front <- the K - 1 samples in front of every span that has a staged front (planar_staged): samples of the row itself, or, in
@@ -216,7 +223,7 @@ __global__ __launch_bounds__(256) void k_firp_front(const int32_t* __restrict__ 
         } else {  // (span 0 of a carried call)
             const uint64_t b = row / g.nch, c = row % g.nch;
             const int64_t pos = (int64_t)(b * g.ns) + s;  // sample of the channel's run in this call
-            v = pos >= 0 ? src[((uint64_t)pos / g.ns * g.nch + c) * g.ns + (uint64_t)pos % g.ns] : head[(uint64_t)((int64_t)k1 + pos) * g.nch + c];
+            v = pos >= 0 ? src[planar_run_at((uint64_t)pos, g.nch, c, g.ns)] : head[(uint64_t)((int64_t)k1 + pos) * g.nch + c];
         }
         front[i] = v;
     }

@@ -327,11 +327,27 @@ int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nb
     return RSPT_HIP_OK;
 }
 
-// ---- the frame of the sliding-window stages (FIR, median) ----
-// The decomposition of a sliding-window stage (WinGeom): channel groups of up to `threads` lanes' channels, runs of `run`
-// outputs per lane (kFirThreads / kFirR, kMedThreads / kMedRun), and spans along the time axis until there are about four
-// workgroups per CU -- each span at least 4 (K - 1) rows, so that the halo an in-place call stages is at most a quarter of the
-// batch.  run_rows != 0 (a carried-state call): the nblocks blocks, back to back, taken as ONE block of run_rows = nblocks * ns rows.
+// ---- the frame of the sliding-window stages (FIR, median), on the native block and on the planar int32 matrix ----
+// How far a sliding-window stage splits the time axis: spans until there are about four workgroups per CU -- each span at least
+// 4 (K - 1) samples, so that what an in-place call stages in front of its spans is at most a quarter of the batch, and a multiple
+// of the chunk of C outputs.  base_units: the call's workgroups before any split; ns: the samples along the axis.
+struct WinSplit {
+    uint32_t span, nsplit;
+};
+static WinSplit win_split(int num_cu, uint64_t base_units, uint32_t ns, uint32_t K, uint32_t C) {
+    const uint64_t want = 4ull * (uint64_t)num_cu;
+    uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
+    const uint64_t min_span = K > 1 ? 4ull * (K - 1) : 1;
+    const uint64_t max_split = ns / (min_span > C ? min_span : C);
+    nsplit = nsplit > max_split ? max_split : nsplit;
+    nsplit = nsplit < 1 ? 1 : nsplit;
+    const uint64_t span = ((ns + nsplit - 1) / nsplit + C - 1) / C * C;
+    return {(uint32_t)span, (uint32_t)((ns + span - 1) / span)};
+}
+
+// The decomposition on the native block (WinGeom): channel groups of up to `threads` lanes' channels, runs of `run` outputs per
+// lane (kFirThreads / kFirR, kMedThreads / kMedRun), and spans of rows (win_split).  run_rows != 0 (a carried-state call): the
+// nblocks blocks, back to back, taken as ONE block of run_rows = nblocks * ns rows.
 static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, uint32_t run_rows = 0) {
     Geom g = p->g;
     if (run_rows) {
@@ -348,36 +364,83 @@ static WinGeom win_geom(const rspt_hip_packer* p, size_t nblocks, uint32_t K, ui
     f.cw = g.nch < threads ? g.nch : threads;
     f.subs = threads / f.cw;
     f.ncg = (g.nch + f.cw - 1) / f.cw;
-    const uint32_t C = f.subs * run;
     const uint64_t base_units = (uint64_t)nblocks * f.ncg;
-    const uint64_t want = 4ull * (uint64_t)p->num_cu;
-    uint64_t nsplit = base_units >= want ? 1 : (want + base_units - 1) / base_units;
-    const uint64_t min_span = K > 1 ? 4ull * (K - 1) : 1;
-    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
-    nsplit = nsplit > max_split ? max_split : nsplit;
-    nsplit = nsplit < 1 ? 1 : nsplit;
-    const uint64_t span = ((g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
-    f.span = (uint32_t)span;
-    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
+    const WinSplit s = win_split(p->num_cu, base_units, g.ns, K, f.subs * run);
+    f.span = s.span;
+    f.nsplit = s.nsplit;
     f.units = base_units * f.nsplit;
     return f;
 }
 
-// The checks of both windowed entry points, in the order they return: a null handle or buffer, nblocks == 0 or nblocks * nch
-// >= 2^31, and buffers that overlap without being the same (ERR_ARG); then a chunk's row offsets, which k_fir and k_med_short
-// compute in 32 bits (ERR_UNSUPPORTED: 2^24 channels and more).  Sets the geometry for the window K and whether the call is in place.
-static int window_call_checks(const rspt_hip_packer* p, const void* d_src, const void* d_dst, size_t nblocks, uint32_t K, uint32_t threads,
-                              uint32_t run, WinGeom* f, bool* in_place, bool one_run = false) {
+// The decomposition on the matrix (PlanarWin): a row = (block, channel) of ns samples, `lanes` lanes of `run` outputs along it --
+// the smallest power of two that covers the row, at most `threads` --, threads / lanes rows to a workgroup, and spans of samples
+// (win_split).  Only rows of more than one chunk are ever split.  `min_lanes` (a power of two) bounds the rows of a workgroup for
+// a kernel that keeps something per row.
+static PlanarWin planar_win(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, bool in_place, bool carried,
+                            uint32_t min_lanes) {
+    const Geom& g = p->g;
+    PlanarWin f{};
+    f.rows = (uint64_t)nblocks * g.nch;
+    f.total = f.rows * g.ns;
+    f.nch = g.nch;
+    f.ns = g.ns;
+    f.K = K;
+    const uint64_t runs = ((uint64_t)g.ns + run - 1) / run;
+    f.lanes = min_lanes;
+    while (f.lanes < threads && f.lanes < runs) f.lanes *= 2;
+    f.rpw = threads / f.lanes;
+    const uint64_t groups = (f.rows + f.rpw - 1) / f.rpw;
+    const WinSplit s = win_split(p->num_cu, groups, g.ns, K, f.lanes * run);
+    f.span = s.span;
+    f.nsplit = s.nsplit;
+    f.units = groups * f.nsplit;
+    f.in_place = in_place;
+    f.carried = carried;
+    f.npiece = (in_place ? f.nsplit - 1 : 0u) + (carried ? 1u : 0u);
+    return f;
+}
+
+// A windowed call that passed its checks: whether it is in place, and its decomposition in its layout's form (the other stays zero).
+struct WinCall {
+    bool in_place;
+    WinGeom f;     // native
+    PlanarWin pf;  // planar
+};
+
+// The checks of all eight windowed entry points (FIR and median, native and planar, stateless and carried), in the order they
+// return.  ERR_ARG: a null handle or buffer, nblocks == 0 or nblocks * nch >= 2^31, a planar buffer off its 4-byte alignment,
+// and buffers that overlap without being the same.  Then ERR_UNSUPPORTED: a handle too wide; rows that the kernels index in 32
+// bits with a chunk's reach beyond the last one -- a carried call's run of nblocks * ns rows in either layout, a row of ns samples
+// of a stateless call on the matrix --; and on the native block a chunk's row offsets, which k_fir and k_med_short compute in 32
+// bits (2^24 channels and more).  Sets the decomposition for the window K; min_lanes: planar_win's.
+static int window_call_checks(const rspt_hip_packer* p, bool planar, const void* d_src, const void* d_dst, size_t nblocks, bool carried, uint32_t K,
+                              uint32_t threads, uint32_t run, WinCall* w, uint32_t min_lanes = 1) {
     if (!p || !d_src || !d_dst || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
-    const uint64_t bytes = (uint64_t)nblocks * p->g.block_bytes;
+    const Geom& g = p->g;
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    *in_place = s0 == d0;
-    if (!*in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
+    if (planar && (s0 % 4 || d0 % 4)) return RSPT_HIP_ERR_ARG;
+    const uint64_t bytes = (uint64_t)nblocks * (planar ? (uint64_t)g.nch * g.ns * 4u : g.block_bytes);
+    *w = WinCall{};
+    w->in_place = s0 == d0;
+    if (!w->in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
     if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    if (one_run && (uint64_t)nblocks * p->g.ns >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
-    *f = win_geom(p, nblocks, K, threads, run, one_run ? (uint32_t)(nblocks * p->g.ns) : 0u);
-    if ((uint64_t)f->subs * run * p->g.nch * p->g.bps >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;
+    const uint64_t run_rows = (uint64_t)nblocks * g.ns;
+    if ((carried ? run_rows : planar ? (uint64_t)g.ns : 0) >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
+    if (planar) {
+        w->pf = planar_win(p, nblocks, K, threads, run, w->in_place, carried, min_lanes);
+        return RSPT_HIP_OK;
+    }
+    w->f = win_geom(p, nblocks, K, threads, run, carried ? (uint32_t)run_rows : 0u);
+    if ((uint64_t)w->f.subs * run * w->f.stride >= (1ull << 31)) return RSPT_HIP_ERR_UNSUPPORTED;
     return RSPT_HIP_OK;
+}
+
+// The grid of a mover of n elements: 256 to a workgroup, at most 4096 workgroups (the movers stride by their grid).
+static dim3 mover_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096)); }
+
+// A carried state of either stage in either layout: a u64 header, then K - 1 rows of nch samples, to a multiple of 8 bytes.
+static size_t window_state_bytes(const rspt_hip_packer* p, size_t K, bool planar) {
+    return 8 + (((K - 1) * p->g.nch * (planar ? 4u : p->g.bps) + 7) & ~(size_t)7);
 }
 
 // The halo of an in-place call with more than one span per block: the K - 1 rows in front of every span but the first,
@@ -405,7 +468,7 @@ static int finish_window_call(rspt_hip_packer* p, LastCall& last, hipError_t e, 
     return RSPT_HIP_OK;
 }
 
-// ---- FIR pre-filter (fir.hip) ----
+// ---- FIR pre-filter (fir.hip; on the matrix fir_planar.hip) ----
 template <int BPS>
 static void launch_fir(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, const double* coef, bool aligned, hipStream_t st,
                        const uint8_t* head = nullptr) {
@@ -419,9 +482,49 @@ static hipError_t launch_fir_carry(const WinGeom& f, const void* d_src, uint8_t*
     uint64_t* started = (uint64_t*)d_state;
     uint8_t* rows = (uint8_t*)d_state + 8;
     const uint64_t n = (uint64_t)(f.K - 1) * f.stride;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
-    if (n) hipLaunchKernelGGL(k_fir_carry<false>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
-    hipLaunchKernelGGL(k_fir_carry<true>, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
+    if (n) hipLaunchKernelGGL(k_fir_carry<false>, mover_grid(n), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
+    hipLaunchKernelGGL(k_fir_carry<true>, mover_grid(n), dim3(256), 0, st, (const uint8_t*)d_src, head, started, rows, n, f.stride, f.K, f.ns);
+    return hipGetLastError();
+}
+
+// What a native call enqueues behind its coefficients: the carry movers, the halo (`pieces` of it), k_fir.
+static hipError_t launch_fir_native(rspt_hip_packer* p, const WinGeom& f, const void* d_src, void* d_dst, uint64_t pieces, const double* coef,
+                                    void* d_state, hipStream_t st) {
+    FirStage& fs = p->fir;
+    hipError_t e = d_state ? launch_fir_carry(f, d_src, fs.head, d_state, st) : hipSuccess;
+    if (e == hipSuccess && pieces) e = launch_halo(f, d_src, fs.halo, pieces, st);
+    if (e != hipSuccess) return e;
+    const bool aligned = native_aligned(p->g.bps, d_src, d_dst);
+    by_bps(p->g.bps, [&](auto b) {
+        launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, coef, aligned, st,
+                                       d_state && f.K > 1 ? (const uint8_t*)fs.head : nullptr);
+    });
+    return hipGetLastError();
+}
+
+// What a planar call enqueues behind its coefficients: the state's movers (head_n samples of the head), the fronts (front_n
+// samples in the handle's `halo`), k_fir_planar.  N: the samples per channel of a carried call's run.
+static hipError_t launch_fir_planar(rspt_hip_packer* p, const PlanarWin& f, const int32_t* d_src, int32_t* d_dst, uint64_t front_n, const double* coef,
+                                    void* d_state, uint64_t N, hipStream_t st) {
+    FirStage& fs = p->fir;
+    int32_t* head = reinterpret_cast<int32_t*>((uint8_t*)fs.head);
+    int32_t* front = reinterpret_cast<int32_t*>((uint8_t*)fs.halo);
+    if (d_state) {
+        uint64_t* started = (uint64_t*)d_state;
+        int32_t* rows = reinterpret_cast<int32_t*>((uint8_t*)d_state + 8);
+        const uint64_t head_n = (uint64_t)(f.K - 1) * f.nch;
+        if (head_n) hipLaunchKernelGGL(k_firp_head, mover_grid(head_n), dim3(256), 0, st, d_src, head, started, rows, head_n, f.nch, f.ns);
+        hipLaunchKernelGGL(k_firp_save, mover_grid(head_n), dim3(256), 0, st, d_src, head, started, rows, head_n, f.nch, f.ns, f.K, N);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (front_n) {
+        hipLaunchKernelGGL(k_firp_front, mover_grid(front_n), dim3(256), 0, st, d_src, head, front, f);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+    const bool wide = reinterpret_cast<uintptr_t>(d_src) % 16 == 0 && reinterpret_cast<uintptr_t>(d_dst) % 16 == 0 && f.ns % 4 == 0;
+    if (wide) hipLaunchKernelGGL(k_fir_planar<true>, dim3(grid), dim3(kFirThreads), 0, st, d_src, d_dst, front, coef, f);
+    else hipLaunchKernelGGL(k_fir_planar<false>, dim3(grid), dim3(kFirThreads), 0, st, d_src, d_dst, front, coef, f);
     return hipGetLastError();
 }
 
@@ -452,34 +555,30 @@ static int fir_take_slot(rspt_hip_packer* p, const double* kernel, size_t kernel
     return RSPT_HIP_OK;
 }
 
-// Both native FIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state.
+// All four FIR entries: d_state == NULL is the stateless call on nblocks blocks, else the blocks are one run behind the state;
+// planar: the buffers are int32 matrices, and the blocks of a carried call consecutive pieces of one recording.  The handle's
+// `halo` holds what is staged in front of the spans -- native, the halo's pieces of K - 1 rows; planar, the fronts of K - 1 samples
+// per row and piece -- and `head` the staged state, K - 1 rows of nch samples.
 static int fir_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size, void* d_state,
-                    void* stream) {
+                    void* stream, bool planar = false) {
     if (!kernel || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
-    WinGeom f;
-    bool in_place;
-    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, (uint32_t)kernel_size, kFirThreads, kFirR, &f, &in_place, d_state != nullptr)) return rc;
-    if (d_state) nblocks = 1;  // (the geometry's one block of nblocks * ns rows)
+    const uint32_t K = (uint32_t)kernel_size;
+    WinCall w;
+    if (int rc = window_call_checks(p, planar, d_src, d_dst, nblocks, d_state != nullptr, K, kFirThreads, kFirR, &w)) return rc;
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    FirStage& fs = p->fir;
-    const uint64_t pieces = halo_pieces(f, nblocks, in_place);
-    const uint64_t halo_bytes = pieces * (uint64_t)(kernel_size - 1) * f.stride;
-    const uint64_t head_bytes = d_state ? (uint64_t)(kernel_size - 1) * f.stride : 0;
+    const uint64_t row_bytes = (uint64_t)p->g.nch * (planar ? 4u : p->g.bps);  // nch samples
+    const uint64_t pieces = planar ? w.pf.rows * w.pf.npiece : halo_pieces(w.f, d_state ? 1 : nblocks, w.in_place);
+    const uint64_t halo_bytes = pieces * (uint64_t)(K - 1) * (planar ? 4u : row_bytes);
+    const uint64_t head_bytes = d_state ? (uint64_t)(K - 1) * row_bytes : 0;
     FirStage::CoefSlot* slot;
     if (int rc = fir_take_slot(p, kernel, kernel_size, halo_bytes, head_bytes, &slot)) return rc;
     FirStage::CoefSlot& cs = *slot;
     hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_state) e = launch_fir_carry(f, d_src, fs.head, d_state, st);
-    if (e == hipSuccess && pieces) e = launch_halo(f, d_src, fs.halo, pieces, st);
-    if (e == hipSuccess) {
-        const bool aligned = native_aligned(p->g.bps, d_src, d_dst);
-        by_bps(p->g.bps, [&](auto b) {
-            launch_fir<decltype(b)::value>(f, (const uint8_t*)d_src, (uint8_t*)d_dst, pieces ? (const uint8_t*)fs.halo : nullptr, cs.dev, aligned, st,
-                                           head_bytes ? (const uint8_t*)fs.head : nullptr);
-        });
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = planar ? launch_fir_planar(p, w.pf, (const int32_t*)d_src, (int32_t*)d_dst, pieces * (uint64_t)(K - 1), cs.dev, d_state,
+                                       (uint64_t)nblocks * p->g.ns, st)
+                   : launch_fir_native(p, w.f, d_src, d_dst, pieces, cs.dev, d_state, st);
     return finish_window_call(p, cs.last, e, st);
 }
 
@@ -488,11 +587,13 @@ int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void
     return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, nullptr, stream);
 }
 
-int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) {
+static int fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes, bool planar) {
     if (!p || !bytes || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
-    *bytes = 8 + (((size_t)(kernel_size - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
+    *bytes = window_state_bytes(p, kernel_size, planar);
     return RSPT_HIP_OK;
 }
+
+int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) { return fir_state_bytes(p, kernel_size, bytes, false); }
 
 int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
                                       void* d_state, void* stream) {
@@ -500,111 +601,20 @@ int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, voi
     return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
 }
 
-// ---- FIR pre-filter on the planar int32 matrix (fir_planar.hip) ----
-// The decomposition of a sliding-window stage on the matrix (PlanarWin): a row = (block, channel) of ns samples, `lanes` lanes of
-// `run` outputs along it -- the smallest power of two that covers the row, at most `threads` --, threads / lanes rows to a
-// workgroup, and, as in win_geom, spans along the row until there are about four workgroups per CU, each span at least
-// 4 (K - 1) samples and a multiple of the chunk.  Only rows of more than one chunk are ever split.  `min_lanes` (a power of two)
-// bounds the rows of a workgroup for a kernel that keeps something per row.
-static PlanarWin planar_win(const rspt_hip_packer* p, size_t nblocks, uint32_t K, uint32_t threads, uint32_t run, bool in_place, bool carried,
-                            uint32_t min_lanes = 1) {
-    const Geom& g = p->g;
-    PlanarWin f{};
-    f.rows = (uint64_t)nblocks * g.nch;
-    f.total = f.rows * g.ns;
-    f.nch = g.nch;
-    f.ns = g.ns;
-    f.K = K;
-    const uint64_t runs = ((uint64_t)g.ns + run - 1) / run;
-    f.lanes = min_lanes;
-    while (f.lanes < threads && f.lanes < runs) f.lanes *= 2;
-    f.rpw = threads / f.lanes;
-    const uint32_t C = f.lanes * run;
-    const uint64_t groups = (f.rows + f.rpw - 1) / f.rpw;
-    const uint64_t want = 4ull * (uint64_t)p->num_cu;
-    uint64_t nsplit = groups >= want ? 1 : (want + groups - 1) / groups;
-    const uint64_t min_span = K > 1 ? 4ull * (K - 1) : 1;
-    const uint64_t max_split = g.ns / (min_span > C ? min_span : C);
-    nsplit = nsplit > max_split ? max_split : nsplit;
-    nsplit = nsplit < 1 ? 1 : nsplit;
-    const uint64_t span = (((uint64_t)g.ns + nsplit - 1) / nsplit + C - 1) / C * C;
-    f.span = (uint32_t)span;
-    f.nsplit = (uint32_t)((g.ns + span - 1) / span);
-    f.units = groups * f.nsplit;
-    f.in_place = in_place;
-    f.carried = carried;
-    f.npiece = (in_place ? f.nsplit - 1 : 0u) + (carried ? 1u : 0u);
-    return f;
-}
-
-// Both planar FIR entries: d_state == NULL is the stateless call, else the blocks are consecutive pieces of one recording behind
-// the state.  The handle's `halo` holds the fronts (4 (K - 1) nblocks nch npiece bytes), `head` the staged state (4 (K - 1) nch).
-static int fir_planar_call(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel, size_t kernel_size,
-                           void* d_state, void* stream) {
-    if (!p || !d_src || !d_dst || !kernel || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
-    if (kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    if (s0 % 4 || d0 % 4) return RSPT_HIP_ERR_ARG;
-    const uint64_t bytes = (uint64_t)nblocks * p->g.nch * p->g.ns * 4u;
-    const bool in_place = s0 == d0;
-    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    // a row's samples, and a carried call's run, are indexed in 32 bits with a chunk's reach beyond the last one
-    if ((d_state ? (uint64_t)nblocks * p->g.ns : (uint64_t)p->g.ns) >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
-    const uint32_t K = (uint32_t)kernel_size;
-    const PlanarWin f = planar_win(p, nblocks, K, kFirThreads, kFirR, in_place, d_state != nullptr);
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    FirStage& fs = p->fir;
-    const uint64_t front_n = f.rows * f.npiece * (uint64_t)(K - 1);     // samples of all fronts
-    const uint64_t head_n = d_state ? (uint64_t)(K - 1) * f.nch : 0;  // samples of the head
-    FirStage::CoefSlot* slot;
-    if (int rc = fir_take_slot(p, kernel, kernel_size, front_n * 4u, head_n * 4u, &slot)) return rc;
-    FirStage::CoefSlot& cs = *slot;
-    int32_t* head = reinterpret_cast<int32_t*>((uint8_t*)fs.head);
-    int32_t* front = reinterpret_cast<int32_t*>((uint8_t*)fs.halo);
-    auto mover_grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096)); };
-    hipError_t e = hipMemcpyAsync(cs.dev, cs.host, kernel_size * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_state) {
-        uint64_t* started = (uint64_t*)d_state;
-        int32_t* rows = reinterpret_cast<int32_t*>((uint8_t*)d_state + 8);
-        if (head_n) hipLaunchKernelGGL(k_firp_head, mover_grid(head_n), dim3(256), 0, st, d_src, head, started, rows, head_n, f.nch, f.ns);
-        hipLaunchKernelGGL(k_firp_save, mover_grid(head_n), dim3(256), 0, st, d_src, head, started, rows, head_n, f.nch, f.ns, K,
-                           (uint64_t)nblocks * f.ns);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && front_n) {
-        hipLaunchKernelGGL(k_firp_front, mover_grid(front_n), dim3(256), 0, st, d_src, head, front, f);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
-        const bool wide = s0 % 16 == 0 && d0 % 16 == 0 && f.ns % 4 == 0;
-        if (wide) hipLaunchKernelGGL(k_fir_planar<true>, dim3(grid), dim3(kFirThreads), 0, st, d_src, d_dst, front, cs.dev, f);
-        else hipLaunchKernelGGL(k_fir_planar<false>, dim3(grid), dim3(kFirThreads), 0, st, d_src, d_dst, front, cs.dev, f);
-        e = hipGetLastError();
-    }
-    return finish_window_call(p, cs.last, e, st);
-}
-
 int rspt_hip_fir_prefilter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel,
                                             size_t kernel_size, void* stream) {
-    return fir_planar_call(p, d_src, d_dst, nblocks, kernel, kernel_size, nullptr, stream);
+    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, nullptr, stream, true);
 }
 
-int rspt_hip_fir_planar_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) {
-    if (!p || !bytes || kernel_size == 0 || kernel_size > kFirMaxTaps) return RSPT_HIP_ERR_ARG;
-    *bytes = 8 + (((size_t)(kernel_size - 1) * p->g.nch * 4u + 7) & ~(size_t)7);
-    return RSPT_HIP_OK;
-}
+int rspt_hip_fir_planar_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes) { return fir_state_bytes(p, kernel_size, bytes, true); }
 
 int rspt_hip_fir_prefilter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, const double* kernel,
                                              size_t kernel_size, void* d_state, void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
-    return fir_planar_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream);
+    return fir_call(p, d_src, d_dst, nblocks, kernel, kernel_size, d_state, stream, true);
 }
 
-// ---- rolling median (median.hip) ----
+// ---- rolling median (median.hip; on the matrix median_planar.hip) ----
 template <uint32_t N, int BPS, bool HEAD>
 static void launch_med_short(const WinGeom& f, const uint8_t* src, uint8_t* dst, const uint8_t* halo, bool aligned, hipStream_t st, const uint8_t* head) {
     const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
@@ -685,10 +695,10 @@ static int median_reserve(MedianStage& ms, uint64_t halo_bytes, uint64_t head_by
     return ms.last.make_event() ? RSPT_HIP_OK : RSPT_HIP_ERR_ALLOC;
 }
 
-int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) {
+static int median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes, bool planar) {
     if (!p || !bytes || window == 0) return RSPT_HIP_ERR_ARG;
     if (window > kMedShortMax && window - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;
-    *bytes = 8 + (((size_t)(window - 1) * p->g.nch * p->g.bps + 7) & ~(size_t)7);
+    *bytes = window_state_bytes(p, window, planar);
     return RSPT_HIP_OK;
 }
 
@@ -698,14 +708,14 @@ static hipError_t launch_med_carry(const WinGeom& f, const void* d_src, uint8_t*
     uint64_t n = (uint64_t)(f.K - 1) * f.stride, call = rows * f.stride;
     const bool words = reinterpret_cast<uintptr_t>(d_src) % 4 == 0 && f.stride % 4 == 0;
     if (words) n /= 4, call /= 4;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096);
+    const dim3 grid = mover_grid(n);
     uint8_t* state = (uint8_t*)d_state;
     if (words) {
-        hipLaunchKernelGGL((k_med_carry<false, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
-        hipLaunchKernelGGL((k_med_carry<true, uint32_t>), dim3(grid), dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<false, uint32_t>), grid, dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<true, uint32_t>), grid, dim3(256), 0, st, (const uint32_t*)d_src, head, state, n, call, f.K - 1, rows);
     } else {
-        hipLaunchKernelGGL((k_med_carry<false, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
-        hipLaunchKernelGGL((k_med_carry<true, uint8_t>), dim3(grid), dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<false, uint8_t>), grid, dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
+        hipLaunchKernelGGL((k_med_carry<true, uint8_t>), grid, dim3(256), 0, st, (const uint8_t*)d_src, head, state, n, call, f.K - 1, rows);
     }
     return hipGetLastError();
 }
@@ -720,68 +730,125 @@ static uint32_t median_segment_rows(uint32_t W, uint64_t rows) {
     return (uint32_t)std::min<uint64_t>(S, (uint64_t)(W - 1) + rows);
 }
 
-// Both median entries: d_state == NULL is the stateless call on nblocks blocks, where a window of ns or more is the expanding
+// The movers of a carried call on the matrix: stage the state as it is (k_med_carry<false>, in words), then gather the new one
+// from the tails of the blocks' rows (k_medp_save).
+static hipError_t launch_medp_carry(const PlanarWin& f, const int32_t* d_src, uint8_t* head, void* d_state, uint64_t rows, hipStream_t st) {
+    const uint64_t wm1 = f.K - 1, head_n = wm1 * f.nch;  // samples of the staged state
+    hipLaunchKernelGGL((k_med_carry<false, uint32_t>), mover_grid(head_n), dim3(256), 0, st, (const uint32_t*)d_src, head, (uint8_t*)d_state, head_n,
+                       (uint64_t)0, wm1, rows);
+    hipLaunchKernelGGL(k_medp_save, mover_grid(head_n), dim3(256), 0, st, d_src, (const uint8_t*)head, (uint8_t*)d_state, head_n, f.nch, f.ns, wm1, rows);
+    return hipGetLastError();
+}
+
+template <uint32_t N>
+static void launch_med_planar(const PlanarWin& f, const int32_t* src, int32_t* dst, const int32_t* front, bool wide, hipStream_t st, const uint8_t* head) {
+    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
+    if (wide) hipLaunchKernelGGL((k_med_planar<N, true>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, front, f, head);
+    else hipLaunchKernelGGL((k_med_planar<N, false>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, front, f, head);
+}
+
+// The short path on the matrix: the fronts (front_n samples of them, k_firp_front), then k_med_planar by its register bucket.
+// head: the staged state of a carried call, else null.
+static hipError_t launch_med_short_planar(const PlanarWin& f, const int32_t* d_src, int32_t* d_dst, int32_t* front, uint64_t front_n, const uint8_t* head,
+                                          hipStream_t st) {
+    if (front_n) {
+        hipLaunchKernelGGL(k_firp_front, mover_grid(front_n), dim3(256), 0, st, d_src, reinterpret_cast<const int32_t*>(head ? head + 8 : nullptr), front, f);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    const bool wide = reinterpret_cast<uintptr_t>(d_src) % 16 == 0 && reinterpret_cast<uintptr_t>(d_dst) % 16 == 0 && f.ns % 4 == 0;
+    const uint32_t W = f.K;
+    if (W <= 4) launch_med_planar<4>(f, d_src, d_dst, front, wide, st, head);
+    else if (W <= 8) launch_med_planar<8>(f, d_src, d_dst, front, wide, st, head);
+    else if (W <= 16) launch_med_planar<16>(f, d_src, d_dst, front, wide, st, head);
+    else launch_med_planar<32>(f, d_src, d_dst, front, wide, st, head);
+    return hipGetLastError();
+}
+
+// All four median entries: d_state == NULL is the stateless call on nblocks blocks, where a window of ns or more is the expanding
 // median of the channel; else the blocks are one run behind the state, and the window is the recording's (not clamped to ns).
-static int median_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
+// planar: the buffers are int32 matrices, a stateless row = (block, channel) a fresh window, the blocks of a carried call
+// consecutive pieces of one recording.  The handle's `halo` holds what the short path stages in front of its spans -- native, the
+// halo's pieces of W - 1 rows; planar, the fronts of W - 1 samples per row and piece --, `head` the staged state.
+static int median_call(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream,
+                       bool planar = false) {
     if (!p || window == 0) return RSPT_HIP_ERR_ARG;
     const Geom& g = p->g;
-    const uint32_t W = (uint32_t)std::min<size_t>(window, d_state ? (size_t)kMedMaxCarry + 2 : g.ns);
-    WinGeom f;
-    bool in_place;
-    if (int rc = window_call_checks(p, d_src, d_dst, nblocks, W, kMedThreads, kMedRun, &f, &in_place, d_state != nullptr)) return rc;
+    const bool carried = d_state != nullptr;
+    const uint32_t W = (uint32_t)std::min<size_t>(window, carried ? (size_t)kMedMaxCarry + 2 : g.ns);
+    WinCall w;
+    if (int rc = window_call_checks(p, planar, d_src, d_dst, nblocks, carried, W, kMedThreads, kMedRun, &w, kMedpMinLanes)) return rc;
     const bool is_short = W <= kMedShortMax;
     // (the generic path's bitmaps live in LDS; with a state, at least half of every segment is new rows)
-    if (!is_short && (d_state ? W - 1 > kMedMaxCarry : g.ns > kMedMaxRanks)) return RSPT_HIP_ERR_UNSUPPORTED;
+    if (!is_short && (carried ? W - 1 > kMedMaxCarry : g.ns > kMedMaxRanks)) return RSPT_HIP_ERR_UNSUPPORTED;
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t rows = (uint64_t)nblocks * g.ns;  // (with a state below 2^31 - 2^17: window_call_checks)
+    const uint64_t rows = (uint64_t)nblocks * g.ns;         // of a carried call's run (below 2^31 - 2^17: window_call_checks)
+    const uint32_t stride = g.nch * (planar ? 4u : g.bps);  // bytes of nch samples: a row of the native block, of a state
     if (W == 1) {  // a copy, sample width kept; a state is its header and stays zero
-        if (in_place) return RSPT_HIP_OK;
-        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, rows * f.stride, hipMemcpyDeviceToDevice, st));
+        if (w.in_place) return RSPT_HIP_OK;
+        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, rows * stride, hipMemcpyDeviceToDevice, st));
         return RSPT_HIP_OK;
     }
     MedianStage& ms = p->med;
     const uint32_t bps = g.bps;
-    const bool aligned = native_aligned(bps, d_src, d_dst);
-    // buffers: the short path's halo, a state's staged copy, the generic path's keys and ranks
-    const uint64_t pieces = is_short ? halo_pieces(f, d_state ? 1 : nblocks, in_place) : 0;
-    const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * f.stride;
-    const uint64_t head_bytes = d_state ? 8 + (uint64_t)(W - 1) * f.stride : 0;
-    // generic: (block, channel) items of ns keys -- with a state (segment, channel) items of S keys -- in pieces of up to 2^25 keys
+    const bool aligned = planar || native_aligned(bps, d_src, d_dst);
+    // buffers: what the short path stages in front of its spans, a state's staged copy, the generic path's keys and ranks
+    const uint64_t pieces = !is_short ? 0 : planar ? w.pf.rows * w.pf.npiece : halo_pieces(w.f, carried ? 1 : nblocks, w.in_place);
+    const uint64_t halo_bytes = pieces * (uint64_t)(W - 1) * (planar ? 4u : stride);
+    const uint64_t head_bytes = carried ? 8 + (uint64_t)(W - 1) * stride : 0;
+    // generic: (block, channel) items of ns keys -- with a state (segment, channel) items of S keys -- in pieces of up to 2^25 keys.
+    // Its kernels read block_bytes, stride, nch, ns and K of a WinGeom and nothing else.  Native that is the block, or the run as
+    // one block; on the matrix a stateless row is a block of one channel of 4-byte samples, and a carried call keeps the block of
+    // the matrix (k_medp_tile_sort / k_medp_walk find a row of the run by med_planar_at).
     MedSeg sg{};
-    WinGeom fg = f;
+    WinGeom fg{};
+    fg.nch = planar && !carried ? 1u : g.nch;
+    fg.stride = planar ? fg.nch * 4u : stride;
+    fg.block_bytes = planar ? (uint64_t)g.ns * fg.stride : w.f.block_bytes;
+    fg.ns = g.ns;
+    fg.K = W;
     uint64_t items = (uint64_t)nblocks * g.nch, piece_items = 0;
     if (!is_short) {
-        if (d_state) {
+        if (carried) {
             fg.ns = median_segment_rows(W, rows);
             sg.L = fg.ns - (W - 1);
             sg.nseg = (uint32_t)((rows + sg.L - 1) / sg.L);
             sg.N = (uint32_t)rows;
+            sg.bns = planar ? g.ns : 0u;
             items = (uint64_t)sg.nseg * g.nch;
         }
         piece_items = std::min<uint64_t>(items, std::max<uint64_t>(1, (1ull << 25) / fg.ns));
     }
     if (int rc = median_reserve(ms, halo_bytes, head_bytes, piece_items * fg.ns)) return rc;
     hipError_t e = hipSuccess;
-    if (d_state) {  // the new state is written from d_src before any kernel stores to d_dst
+    if (carried) {  // the state is staged and the new one written from d_src before any kernel stores to d_dst
         sg.head = ms.head;
-        e = launch_med_carry(f, d_src, ms.head, d_state, rows, st);
+        e = planar ? launch_medp_carry(w.pf, (const int32_t*)d_src, ms.head, d_state, rows, st) : launch_med_carry(w.f, d_src, ms.head, d_state, rows, st);
     }
-    if (is_short) {
+    if (e != hipSuccess) return finish_window_call(p, ms.last, e, st);
+    const uint8_t* head = carried ? (const uint8_t*)ms.head : nullptr;
+    if (is_short && planar) {
+        e = launch_med_short_planar(w.pf, (const int32_t*)d_src, (int32_t*)d_dst, reinterpret_cast<int32_t*>((uint8_t*)ms.halo), pieces * (uint64_t)(W - 1),
+                                    head, st);
+    } else if (is_short) {
         const uint8_t* halo = pieces ? (const uint8_t*)ms.halo : nullptr;
-        if (e == hipSuccess && pieces) e = launch_halo(f, d_src, ms.halo, pieces, st);
+        if (pieces) e = launch_halo(w.f, d_src, ms.halo, pieces, st);
         if (e == hipSuccess)
-            e = d_state ? launch_med_short_w<true>(bps, f, d_src, d_dst, halo, aligned, st, ms.head)
-                        : launch_med_short_w<false>(bps, f, d_src, d_dst, halo, aligned, st, nullptr);
+            e = carried ? launch_med_short_w<true>(bps, w.f, d_src, d_dst, halo, aligned, st, head)
+                        : launch_med_short_w<false>(bps, w.f, d_src, d_dst, halo, aligned, st, nullptr);
     } else {
         // (with a state from the last segment to the first: a walk writes its segment's new rows, which no segment sorted later reads)
+        const uint8_t* src = (const uint8_t*)d_src;
+        uint8_t* dst = (uint8_t*)d_dst;
         for (uint64_t item0 = 0; e == hipSuccess && item0 < items; item0 += piece_items) {
             const uint64_t ni = std::min(piece_items, items - item0);
-            e = by_bps(bps, [&](auto bb) {
-                constexpr int B = decltype(bb)::value;
-                return d_state ? launch_med_generic<B, true>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, aligned, st, sg)
-                               : launch_med_generic<B>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, aligned, st);
-            });
+            if (planar && carried) e = launch_med_generic<kMedPlanar, true>(p, fg, src, dst, item0, ni, true, st, sg);
+            else
+                e = by_bps(planar ? 4u : bps, [&](auto bb) {
+                    constexpr int B = decltype(bb)::value;
+                    return carried ? launch_med_generic<B, true>(p, fg, src, dst, item0, ni, aligned, st, sg)
+                                   : launch_med_generic<B>(p, fg, src, dst, item0, ni, aligned, st);
+                });
         }
     }
     return finish_window_call(p, ms.last, e, st);
@@ -791,125 +858,23 @@ int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void
     return median_call(p, d_src, d_dst, nblocks, window, nullptr, stream);
 }
 
+int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) { return median_state_bytes(p, window, bytes, false); }
+
 int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
     return median_call(p, d_src, d_dst, nblocks, window, d_state, stream);
 }
 
-// ---- rolling median on the planar int32 matrix (median_planar.hip) ----
-template <uint32_t N>
-static void launch_med_planar(const PlanarWin& f, const int32_t* src, int32_t* dst, const int32_t* front, bool wide, hipStream_t st, const uint8_t* head) {
-    const uint32_t grid = (uint32_t)(f.units < (1u << 20) ? f.units : (1u << 20));
-    if (wide) hipLaunchKernelGGL((k_med_planar<N, true>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, front, f, head);
-    else hipLaunchKernelGGL((k_med_planar<N, false>), dim3(grid), dim3(kMedThreads), 0, st, src, dst, front, f, head);
-}
-
-// Both planar median entries: d_state == NULL is the stateless call, one fresh window per row, the window clamped to ns; else the
-// blocks are consecutive pieces of one recording behind the state and the window is the recording's.  The handle's MedianStage
-// holds the fronts of the short path (`halo`: 4 (W - 1) nblocks nch npiece bytes), the staged state (`head`) and the generic
-// path's keys and ranks.
-static int median_planar_call(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* d_state, void* stream) {
-    if (!p || !d_src || !d_dst || window == 0 || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
-    const Geom& g = p->g;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    if (s0 % 4 || d0 % 4) return RSPT_HIP_ERR_ARG;
-    const uint64_t bytes = (uint64_t)nblocks * g.nch * g.ns * 4u;
-    const bool in_place = s0 == d0;
-    if (!in_place && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // in place, or apart
-    if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    // a row's samples, and a carried call's run, are indexed in 32 bits with a chunk's reach beyond the last one
-    const uint64_t rows = (uint64_t)nblocks * g.ns;  // of a carried call's run
-    if ((d_state ? rows : (uint64_t)g.ns) >= kStreamMaxRows) return RSPT_HIP_ERR_UNSUPPORTED;
-    const uint32_t W = (uint32_t)std::min<size_t>(window, d_state ? (size_t)kMedMaxCarry + 2 : g.ns);
-    const bool is_short = W <= kMedShortMax;
-    if (!is_short && (d_state ? W - 1 > kMedMaxCarry : g.ns > kMedMaxRanks)) return RSPT_HIP_ERR_UNSUPPORTED;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (W == 1) {  // a copy; a state is its header and stays zero
-        if (in_place) return RSPT_HIP_OK;
-        HIPCHK(p, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, st));
-        return RSPT_HIP_OK;
-    }
-    MedianStage& ms = p->med;
-    // (the short path's decomposition; the generic path takes only its row count)
-    const PlanarWin f = planar_win(p, nblocks, W, kMedThreads, kMedRun, in_place, d_state != nullptr, kMedpMinLanes);
-    const uint64_t front_n = is_short ? f.rows * f.npiece * (uint64_t)(W - 1) : 0;  // samples of all fronts
-    const uint64_t head_n = d_state ? (uint64_t)(W - 1) * g.nch : 0;             // samples of the staged state
-    // generic: (row) items of ns keys -- with a state (segment, channel) items of S keys -- in pieces of up to 2^25 keys
-    // The generic kernels (k_med_tile_sort, k_med_merge, k_med_walk and their planar bodies) read block_bytes, stride, nch, ns and K
-    // of a WinGeom and nothing else: cw, subs, ncg, span, nsplit and units belong to the short kernels' decomposition (win_geom)
-    // and stay zero here.  A generic kernel that comes to read one of them needs it set here as well.
-    MedSeg sg{};
-    WinGeom fg{};
-    fg.nch = d_state ? g.nch : 1u;  // (stateless: a row is a block of one channel of 4-byte samples)
-    fg.stride = fg.nch * 4u;
-    fg.block_bytes = (uint64_t)g.ns * fg.stride;
-    fg.ns = g.ns;
-    fg.K = W;
-    uint64_t items = f.rows, piece_items = 0;
-    if (!is_short) {
-        if (d_state) {
-            fg.ns = median_segment_rows(W, rows);
-            sg.L = fg.ns - (W - 1);
-            sg.nseg = (uint32_t)((rows + sg.L - 1) / sg.L);
-            sg.N = (uint32_t)rows;
-            sg.bns = g.ns;
-            items = (uint64_t)sg.nseg * g.nch;
-        }
-        piece_items = std::min<uint64_t>(items, std::max<uint64_t>(1, (1ull << 25) / fg.ns));
-    }
-    if (int rc = median_reserve(ms, front_n * 4u, d_state ? 8 + head_n * 4u : 0, piece_items * fg.ns)) return rc;
-    auto mover_grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 4096)); };
-    hipError_t e = hipSuccess;
-    if (d_state) {  // stage the state, then write the new one from d_src: both before any kernel stores to d_dst
-        sg.head = ms.head;
-        hipLaunchKernelGGL((k_med_carry<false, uint32_t>), mover_grid(head_n), dim3(256), 0, st, (const uint32_t*)d_src, (uint8_t*)ms.head,
-                           (uint8_t*)d_state, head_n, (uint64_t)0, (uint64_t)(W - 1), rows);
-        hipLaunchKernelGGL(k_medp_save, mover_grid(head_n), dim3(256), 0, st, d_src, (const uint8_t*)ms.head, (uint8_t*)d_state, head_n, g.nch, g.ns,
-                           (uint64_t)(W - 1), rows);
-        e = hipGetLastError();
-    }
-    if (is_short) {
-        int32_t* front = reinterpret_cast<int32_t*>((uint8_t*)ms.halo);
-        if (e == hipSuccess && front_n) {
-            hipLaunchKernelGGL(k_firp_front, mover_grid(front_n), dim3(256), 0, st, d_src, reinterpret_cast<const int32_t*>((uint8_t*)ms.head + 8), front, f);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) {
-            const bool wide = s0 % 16 == 0 && d0 % 16 == 0 && g.ns % 4 == 0;
-            const uint8_t* head = d_state ? (const uint8_t*)ms.head : nullptr;
-            if (W <= 4) launch_med_planar<4>(f, d_src, d_dst, front, wide, st, head);
-            else if (W <= 8) launch_med_planar<8>(f, d_src, d_dst, front, wide, st, head);
-            else if (W <= 16) launch_med_planar<16>(f, d_src, d_dst, front, wide, st, head);
-            else launch_med_planar<32>(f, d_src, d_dst, front, wide, st, head);
-            e = hipGetLastError();
-        }
-    } else {
-        // (with a state from the last segment to the first: a walk writes its segment's new rows, which no segment sorted later reads)
-        for (uint64_t item0 = 0; e == hipSuccess && item0 < items; item0 += piece_items) {
-            const uint64_t ni = std::min(piece_items, items - item0);
-            e = d_state ? launch_med_generic<kMedPlanar, true>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, true, st, sg)
-                        : launch_med_generic<4>(p, fg, (const uint8_t*)d_src, (uint8_t*)d_dst, item0, ni, true, st);
-        }
-    }
-    return finish_window_call(p, ms.last, e, st);
-}
-
 int rspt_hip_median_filter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* stream) {
-    return median_planar_call(p, d_src, d_dst, nblocks, window, nullptr, stream);
+    return median_call(p, d_src, d_dst, nblocks, window, nullptr, stream, true);
 }
 
-int rspt_hip_median_planar_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) {
-    if (!p || !bytes || window == 0) return RSPT_HIP_ERR_ARG;
-    if (window > kMedShortMax && window - 1 > kMedMaxCarry) return RSPT_HIP_ERR_UNSUPPORTED;
-    *bytes = 8 + (((size_t)(window - 1) * p->g.nch * 4u + 7) & ~(size_t)7);
-    return RSPT_HIP_OK;
-}
+int rspt_hip_median_planar_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes) { return median_state_bytes(p, window, bytes, true); }
 
 int rspt_hip_median_filter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, size_t window, void* d_state,
                                              void* stream) {
     if (!d_state || reinterpret_cast<uintptr_t>(d_state) % 8) return RSPT_HIP_ERR_ARG;
-    return median_planar_call(p, d_src, d_dst, nblocks, window, d_state, stream);
+    return median_call(p, d_src, d_dst, nblocks, window, d_state, stream, true);
 }
 
 // ---- PRDN: the quality figure of the reference's harness (quality.hip) -----------------------------------------------------------

@@ -68,7 +68,7 @@ struct MedSeg {
 // channel ch lies at med_planar_at.
 constexpr int kMedPlanar = 0;
 __device__ __forceinline__ uint64_t med_planar_at(const MedSeg& sg, uint32_t nch, uint32_t ch, uint32_t r) {
-    return (((uint64_t)(r / sg.bns) * nch + ch) * sg.bns + r % sg.bns) * 4u;
+    return planar_run_at(r, nch, ch, sg.bns) * 4u;
 }
 
 // ---- short windows ----

@@ -32,7 +32,7 @@
 //
 // Carry.  The state is the native one at bps = 4: [u64 fill][W - 1 rows of nch int32], valid rows last.  k_med_carry<false>
 // stages it as it is; k_medp_save gathers the new rows from the tails of the blocks' row c (and the staged head where the call
-// is shorter than W - 1).  Both precede every store to d_dst.
+// is shorter than W - 1) with k_firp_save's loop.  Both precede every store to d_dst.
 #include "common.hpp"
 
 namespace rspt {
@@ -168,18 +168,12 @@ __global__ __launch_bounds__(64) void k_medp_walk(const uint64_t* __restrict__ k
 }
 
 // state <- the last W - 1 rows of (head rows ++ the call's run of N = nblocks * ns samples per channel), gathered from the
-// matrix; fill <- min(fill + N, W - 1).  The valid rows stay last and the zeros in front (k_med_carry<true> on the matrix).
+// matrix by the FIR's loop (planar_save_rows, fir_planar.hip); fill <- min(fill + N, W - 1).  The valid rows stay last and the
+// zeros in front: what k_med_carry<true> writes for a native call.
 __global__ __launch_bounds__(256) void k_medp_save(const int32_t* __restrict__ src, const uint8_t* __restrict__ head, uint8_t* __restrict__ state,
                                                    uint64_t n, uint32_t nch, uint32_t ns, uint64_t wm1, uint64_t N) {
-    const uint64_t i0 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const int32_t* hrows = reinterpret_cast<const int32_t*>(head + 8);
-    int32_t* srows = reinterpret_cast<int32_t*>(state + 8);
-    for (uint64_t i = i0; i < n; i += (uint64_t)gridDim.x * 256u) {
-        const uint64_t j = i / nch, c = i % nch;
-        const int64_t pos = (int64_t)N - (int64_t)wm1 + (int64_t)j;  // sample of the run
-        srows[i] = pos >= 0 ? src[((uint64_t)pos / ns * nch + c) * ns + (uint64_t)pos % ns] : hrows[(j + N) * nch + c];
-    }
-    if (i0 == 0) *reinterpret_cast<uint64_t*>(state) = min(*reinterpret_cast<const uint64_t*>(head) + N, wm1);
+    planar_save_rows(src, reinterpret_cast<const int32_t*>(head + 8), reinterpret_cast<int32_t*>(state + 8), n, nch, ns, wm1, N);
+    if ((uint64_t)blockIdx.x * 256u + threadIdx.x == 0) *reinterpret_cast<uint64_t*>(state) = min(*reinterpret_cast<const uint64_t*>(head) + N, wm1);
 }
 
 }  // namespace rspt

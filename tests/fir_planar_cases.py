@@ -4,7 +4,7 @@ A planar buffer is the converters' int32 matrix [nblocks][nch][ns]: the whole in
 double, stored whole.  The answers are fir_cases.fir_i32 + trunc_i32 per channel on the int32 run -- a block's row for a stateless
 call, the blocks of all calls concatenated for a stream case -- transposed into the matrix: no second statement of the filter.
 
-The kernel's geometry, restated from the host's rule (planar_win, host_stages.hip): a lane holds R = 16 consecutive outputs, a
+The kernel's geometry, as planar_win_model restates the host's rule (planar_win, host_stages.hip): a lane holds R = 16 consecutive outputs, a
 workgroup 256 lanes; a row of ns samples takes the smallest power of two of lanes that covers it (at most 256), so a chunk is
 lanes * 16 outputs, at most CHUNK = 4096, and 256 / lanes rows share a workgroup; rows of more than one chunk are split into
 spans of whole chunks, each at least 4 (K - 1) samples, until there are about four workgroups per CU.
@@ -17,8 +17,10 @@ import functools
 import numpy as np
 
 import fir_cases as fc
+import planar_win_model
 from fir_cases import i32_to_native, native_to_i32, trunc_i32  # noqa: F401
 from iir_planar_cases import block, cut, native_of, planar_of, rows_of  # noqa: F401  (the layout helpers)
+from planar_win_model import state_bytes  # noqa: F401  (state_bytes(K, nch))
 
 R, THREADS = 16, 256
 CHUNK = R * THREADS
@@ -37,19 +39,7 @@ FULL = (1 << 31) - 1
 
 def geom(num_cu, nblocks, nch, ns, K):
     """dict(lanes, rows_per_workgroup, chunk, span, nsplit) of a call, as the host decides it"""
-    runs = (ns + R - 1) // R
-    lanes = 1
-    while lanes < THREADS and lanes < runs:
-        lanes *= 2
-    rpw = THREADS // lanes
-    C = lanes * R
-    groups = (nblocks * nch + rpw - 1) // rpw
-    want = 4 * num_cu
-    nsplit = 1 if groups >= want else (want + groups - 1) // groups
-    min_span = 4 * (K - 1) if K > 1 else 1
-    nsplit = max(1, min(nsplit, ns // max(min_span, C)))
-    span = ((ns + nsplit - 1) // nsplit + C - 1) // C * C
-    return dict(lanes=lanes, rows_per_workgroup=rpw, chunk=C, span=span, nsplit=(ns + span - 1) // span)
+    return planar_win_model.geom(num_cu, nblocks, nch, ns, K, THREADS, R)
 
 
 # ---- the answers ----
@@ -74,9 +64,6 @@ def stream_expected(P, kernel):
     tail = np.concatenate([np.repeat(rows[:1], K - 1, axis=0), rows], axis=0)[rows.shape[0]:]
     return planar_of(fir_rows(rows, kernel), nb, nch, ns), np.ascontiguousarray(tail, dtype=np.int32)
 
-
-def state_bytes(K, nch):
-    return 8 + ((K - 1) * nch * 4 + 7) // 8 * 8
 
 
 def state_image(K, nch, tail):

@@ -5,7 +5,7 @@ The answers are median_cases.median_i32 per row for a stateless call and median_
 calls concatenated for a stream case, transposed into the matrix: no second statement of the median.  Both restatements are pinned
 to the compiled reference by median_record.json and median_stream_record.json.
 
-The short kernel's geometry, restated from the host's rule (planar_win with kMedpMinLanes, host_stages.hip): a lane holds R = 32
+The short kernel's geometry, as planar_win_model restates the host's rule (planar_win with kMedpMinLanes, host_stages.hip): a lane holds R = 32
 consecutive outputs, a workgroup 256 lanes; a row of ns samples takes the smallest power of two of lanes that covers it, at least
 8 and at most 256, so a chunk is lanes * 32 outputs, at most CHUNK = 8192, and 256 / lanes rows share a workgroup; rows of more
 than one chunk are split into spans of whole chunks, each at least 4 (W - 1) samples, until there are about four workgroups per CU.
@@ -20,8 +20,10 @@ import numpy as np
 import cases
 import median_cases as mc
 import median_stream_cases as msc
+import planar_win_model
 from iir_planar_cases import block, cut, native_of, planar_of, rows_of  # noqa: F401  (the layout helpers)
 from median_cases import INT32_MAX, INT32_MIN, i32_to_native, native_to_i32  # noqa: F401
+from planar_win_model import state_bytes  # noqa: F401  (state_bytes(W, nch))
 
 R, THREADS, MIN_LANES = 32, 256, 8
 CHUNK = R * THREADS
@@ -44,19 +46,7 @@ FULL = (1 << 31) - 1
 
 def geom(num_cu, nblocks, nch, ns, W):
     """dict(lanes, rows_per_workgroup, chunk, span, nsplit) of a short-window call, as the host decides it"""
-    runs = (ns + R - 1) // R
-    lanes = MIN_LANES
-    while lanes < THREADS and lanes < runs:
-        lanes *= 2
-    rpw = THREADS // lanes
-    C = lanes * R
-    groups = (nblocks * nch + rpw - 1) // rpw
-    want = 4 * num_cu
-    nsplit = 1 if groups >= want else (want + groups - 1) // groups
-    min_span = 4 * (W - 1) if W > 1 else 1
-    nsplit = max(1, min(nsplit, ns // max(min_span, C)))
-    span = ((ns + nsplit - 1) // nsplit + C - 1) // C * C
-    return dict(lanes=lanes, rows_per_workgroup=rpw, chunk=C, span=span, nsplit=(ns + span - 1) // span)
+    return planar_win_model.geom(num_cu, nblocks, nch, ns, W, THREADS, R, MIN_LANES)
 
 
 # ---- the answers ----
@@ -74,9 +64,6 @@ def stream_expected(P, W):
     rows = rows_of(P)
     return planar_of(msc.median_stream_i32(rows, W), nb, nch, ns), state_image(rows, W)
 
-
-def state_bytes(W, nch):
-    return 8 + ((W - 1) * nch * 4 + 7) // 8 * 8
 
 
 def state_image(rows, W):
