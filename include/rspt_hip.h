@@ -467,8 +467,8 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
  * off its 4-byte alignment; RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels, before anything is launched, and for a stream
  * call of 2^31 - 2^17 rows or more.  A refused call writes nothing.  Asynchronous on `stream`; the entries allocate nothing.
  * Of the other stages the FIR pre-filter, the median and PRDN have planar forms too (rspt_hip_fir_prefilter_planar_batch_dev,
- * rspt_hip_median_filter_planar_batch_dev, rspt_hip_prdn_planar_batch_dev below); the zero-phase IIR and the peak stages stay
- * native-only. */
+ * rspt_hip_median_filter_planar_batch_dev, rspt_hip_prdn_planar_batch_dev below), and so has the zero-phase IIR
+ * (rspt_hip_iir_zero_phase_planar_batch_dev); the peak stages, which only read samples, stay native-only. */
 int rspt_hip_iir_prefilter_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
                                             size_t nr_coefficients, int init_nr_samples, int per_channel, void* stream);
 int rspt_hip_iir_prefilter_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
@@ -514,6 +514,30 @@ int rspt_hip_iir_cascade_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar
 int rspt_hip_iir_zero_phase_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t* bytes);
 int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
                                       int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes, void* stream);
+
+/* ---- the zero-phase IIR filter on the planar int32 matrix --------------------------------------------------------------
+ * rspt_hip_iir_zero_phase_batch_dev with the matrix of the converters in place of the native blocks (see the planar IIR entries
+ * above), so that native_to_i32 -> zero-phase IIR -> compress_planar runs without leaving it.  The operation, n, d, both history
+ * lengths, the arithmetic, the single truncation and the routes are the native entry's, one fresh object per row of the matrix.
+ *   d_planar   the matrix [nblocks][nch][ns], block b's channel c at d_planar + (b*nch + c)*ns; 4-byte alignment is all it needs
+ *   d_out      NULL or d_planar itself: the matrix is filtered IN PLACE.  Any other pointer: the result goes there (the same
+ *              shape, 4-byte aligned) and d_planar is only read; the two nblocks*nch*ns*4-byte ranges must then not overlap at
+ *              all.  Out of place costs nothing: the forward pass only reads the source, the backward pass only writes the
+ *              destination.
+ *   samples    the WHOLE int32 value is the sample: the handle's bps and byte order have no effect, and the result
+ *              (int32_t)w[t] (every NaN, +-inf and |w| >= 2^31 -> INT32_MIN) is stored whole and NOT cut to bps.  So
+ *              i32_to_native(zp_planar(native_to_i32(X))) == zp_native(X) for every bps, and
+ *              compress_planar(zp_planar(native_to_i32(X))) gives the streams of compress(zp_native(X)).
+ *   d_work     the native entry's workspace, sized by rspt_hip_iir_zero_phase_work_bytes(p, nblocks): one slab double [ns][64]
+ *              per 64 rows of the matrix (row b*nch + c is the unit); needs no initialisation
+ * RSPT_HIP_ERR_ARG for everything rspt_hip_iir_zero_phase_batch_dev refuses, a d_planar or d_out off its 4-byte alignment and
+ * matrices that overlap without being the same; RSPT_HIP_ERR_UNSUPPORTED for more than 8191 channels (and a workspace whose
+ * byte count does not fit size_t).  Refusals come before anything is launched, and a refused call writes nothing.  Rows of 64
+ * samples and more with init_nr_samples >= nr_coefficients - 1 take the pipelined kernel, the others one thread per row.
+ * Asynchronous on `stream`; the stage allocates nothing. */
+int rspt_hip_iir_zero_phase_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, int32_t* d_out, size_t nblocks, const double* n, const double* d,
+                                             size_t nr_coefficients, int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes,
+                                             void* stream);
 
 /* ---- optional stage in front of compress: the reference's FIR pre-filter ---------------------------------------
  * i_filter::new_fir(kernel, kernel_size), init_history_values(first sample of the channel, n), filter_opt on every sample

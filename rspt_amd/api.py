@@ -79,6 +79,7 @@ C_ABI = {
     "rspt_hip_iir_cascade_planar_stream_dev": (_i, _casc + [_p, _p]),
     "rspt_hip_iir_zero_phase_work_bytes": (_i, [_p, _z, _szp]),
     "rspt_hip_iir_zero_phase_batch_dev": (_i, [_p, _p, _z, _dp, _dp, _z, _i, _i, _p, _z, _p]),
+    "rspt_hip_iir_zero_phase_planar_batch_dev": (_i, [_p, _p, _p, _z, _dp, _dp, _z, _i, _i, _p, _z, _p]),
     "rspt_hip_fir_prefilter_batch_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p]),
     "rspt_hip_fir_state_bytes": (_i, [_p, _z, _szp]),
     "rspt_hip_fir_prefilter_stream_dev": (_i, [_p, _p, _p, _z, _dp, _z, _p, _p]),
@@ -567,18 +568,35 @@ class SignalPacker:
         filter per (block, channel) runs forward over the block and then, the same object, backward over its own untruncated
         output; the result is truncated once (rspt_hip.h: rspt_hip_iir_zero_phase_batch_dev).
         work: a device tensor of at least iir_zero_phase_work_bytes(nblocks) bytes, 8-byte aligned; None: allocated here."""
+        return self._iir_zero_phase("", d_buf, d_buf, self._nblocks(d_buf), n, d, init_nr_samples, backward_init_nr_samples, work, stream)
+
+    def iir_zero_phase_planar_batch(self, d_planar, n, d, init_nr_samples=2000, backward_init_nr_samples=0, out=None, work=None, stream=None):
+        """iir_zero_phase_batch on samples that live in int32 (rspt_hip.h: rspt_hip_iir_zero_phase_planar_batch_dev): d_planar is a
+        torch.int32 cuda tensor [nblocks, nch, ns]; in place when out is None, else into out (same shape, not overlapping
+        d_planar, which is then only read).  The whole int32 value is the sample and the result is stored whole, whatever the
+        handle's bps.  n, d, the history lengths and work as in iir_zero_phase_batch.  Returns the tensor that holds the result."""
         import torch
 
-        nblocks = self._nblocks(d_buf)
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        if out is None:
+            out = d_planar
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == d_planar.numel()
+        return self._iir_zero_phase("planar_", d_planar, out, nblocks, n, d, init_nr_samples, backward_init_nr_samples, work, stream)
+
+    def _iir_zero_phase(self, form, d_src, out, nblocks, n, d, init_nr_samples, backward_init_nr_samples, work, stream):
+        """both layouts of the zero-phase stage: form "" (native blocks, out is d_src) or "planar_" (the int32 matrix)"""
+        import torch
+
         nn, dd = np.ascontiguousarray(n, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
         assert nn.size == dd.size
         if work is None:
-            work = torch.empty(max(1, (self.iir_zero_phase_work_bytes(max(nblocks, 1)) + 7) // 8), dtype=torch.float64, device=d_buf.device)
+            work = torch.empty(max(1, (self.iir_zero_phase_work_bytes(max(nblocks, 1)) + 7) // 8), dtype=torch.float64, device=d_src.device)
         assert work.is_cuda and work.is_contiguous()
-        st = self._stream(stream, d_buf.device)
-        self._call("rspt_hip_iir_zero_phase_batch_dev", d_buf.data_ptr(), nblocks, _dptr(nn), _dptr(dd), nn.size, int(init_nr_samples),
+        st = self._stream(stream, d_src.device)
+        bufs = (d_src.data_ptr(), out.data_ptr()) if form else (d_src.data_ptr(),)
+        self._call("rspt_hip_iir_zero_phase_%sbatch_dev" % form, *bufs, nblocks, _dptr(nn), _dptr(dd), nn.size, int(init_nr_samples),
                    int(backward_init_nr_samples), work.data_ptr(), work.numel() * work.element_size(), st)
-        return d_buf
+        return out
 
     def _window_call_buffers(self, d_src, d_dst, stream):
         """(nblocks, output, stream) of a windowed stage's call (fir_prefilter_batch, median_filter_batch): whole blocks of

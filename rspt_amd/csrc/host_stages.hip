@@ -275,20 +275,27 @@ static bool iir_zero_phase_bytes(const rspt_hip_packer* p, size_t nblocks, uint6
 }
 
 // Blocks of a chunk and more whose forward history fills the ring's tail take the pipelined kernel, the others one thread per
-// (block, channel).
-template <int BPS, int NC>
-static void launch_iir_zero_phase(rspt_hip_packer* p, uint8_t* buf, uint32_t B, const IirCoef& c, int init_nr_samples, int32_t back_steps, double* work,
-                                  hipStream_t st) {
+// (block, channel): the one choice of both layouts.  PLANAR: src / dst are the int32 matrix [B][nch][ns] whatever the handle's
+// bps (dst == src in place); native: one buffer, BPS the handle's.
+template <int BPS, int NC, bool PLANAR>
+static void launch_iir_zero_phase(rspt_hip_packer* p, uint8_t* src, uint8_t* dst, uint32_t B, const IirCoef& c, int init_nr_samples, int32_t back_steps,
+                                  double* work, hipStream_t st) {
     const Geom& g = p->g;
     const dim3 grid((B * g.nch + 63) / 64);
-    if (g.ns >= kZpChunk && init_nr_samples >= NC - 1) {
-        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(buf) % BPS) == 0;  // (block_bytes is a multiple of BPS)
-        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kZpThreads), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, back_steps, B, work); };
+    const bool pipe = g.ns >= kZpChunk && init_nr_samples >= NC - 1;
+    if constexpr (PLANAR) {
+        if (pipe)
+            hipLaunchKernelGGL((k_iir_zp_pipe_planar<NC>), grid, dim3(kZpThreads), 0, st, src, dst, g.nch, g.ns, (uint64_t)g.nch * g.ns * 4u, c, back_steps, B, work);
+        else
+            hipLaunchKernelGGL((k_iir_zp_planar<NC>), grid, dim3(64), 0, st, (const int32_t*)src, (int32_t*)dst, g.ns, c, back_steps, B * g.nch, work);
+    } else if (pipe) {
+        const bool al = (BPS == 4 || BPS == 2) && (reinterpret_cast<uintptr_t>(src) % BPS) == 0;  // (block_bytes is a multiple of BPS)
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kZpThreads), 0, st, src, g.nch, g.ns, (uint64_t)g.block_bytes, c, back_steps, B, work); };
         if (al) go(&k_iir_zp_pipe<BPS, NC, (BPS == 4 || BPS == 2)>);
         else go(&k_iir_zp_pipe<BPS, NC, false>);
-        return;
+    } else {
+        hipLaunchKernelGGL((k_iir_zp<BPS, NC>), grid, dim3(64), 0, st, src, g.nch, g.ns, (uint64_t)g.block_bytes, c, back_steps, B, work);
     }
-    hipLaunchKernelGGL((k_iir_zp<BPS, NC>), grid, dim3(64), 0, st, buf, g.nch, g.ns, (uint64_t)g.block_bytes, c, back_steps, B, work);
 }
 
 int rspt_hip_iir_zero_phase_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t* bytes) {
@@ -299,9 +306,17 @@ int rspt_hip_iir_zero_phase_work_bytes(rspt_hip_packer* p, size_t nblocks, size_
     return RSPT_HIP_OK;
 }
 
-int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
-                                      int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes, void* stream) {
-    if (!p || !d_buf || !n || !d || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+// Both zero-phase entries.  Native: d_src is the blocks' buffer and d_dst the same.  Planar: d_src is the int32 matrix and d_dst
+// where the result goes -- the matrix itself, or one of its own that does not overlap it.
+static int iir_zero_phase_call(rspt_hip_packer* p, void* d_src, void* d_dst, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                               int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes, void* stream, bool planar) {
+    if (!p || !d_src || !d_dst || !n || !d || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (planar) {
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+        if (s0 % 4 || d0 % 4) return RSPT_HIP_ERR_ARG;
+        const uint64_t bytes = (uint64_t)nblocks * p->g.nch * p->g.ns * sizeof(int32_t);  // (nblocks * nch < 2^31, ns < 2^31)
+        if (s0 != d0 && s0 < d0 + bytes && d0 < s0 + bytes) return RSPT_HIP_ERR_ARG;  // the two matrices overlap without being the same
+    }
     if (nr_coefficients < 2 || nr_coefficients > 5 || init_nr_samples < 0 || init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;
     if (backward_init_nr_samples < 0 || backward_init_nr_samples > (1 << 28)) return RSPT_HIP_ERR_ARG;
     if (!d_work || reinterpret_cast<uintptr_t>(d_work) % 8) return RSPT_HIP_ERR_ARG;
@@ -317,14 +332,27 @@ int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nb
     }
     c.nc = (uint32_t)nr_coefficients;
     c.init_steps = 4 * init_nr_samples;
-    by_bps(p->g.bps, [&](auto bps) {
-        by_nc(c.nc, [&](auto ncv) {
-            launch_iir_zero_phase<decltype(bps)::value, decltype(ncv)::value>(p, (uint8_t*)d_buf, (uint32_t)nblocks, c, init_nr_samples,
-                                                                              4 * backward_init_nr_samples, (double*)d_work, (hipStream_t)stream);
-        });
-    });
+    auto go = [&](auto bps, auto ncv, auto pl) {
+        launch_iir_zero_phase<decltype(bps)::value, decltype(ncv)::value, decltype(pl)::value>(p, (uint8_t*)d_src, (uint8_t*)d_dst, (uint32_t)nblocks, c, init_nr_samples,
+                                                                                               4 * backward_init_nr_samples, (double*)d_work, (hipStream_t)stream);
+    };
+    if (planar) by_nc(c.nc, [&](auto ncv) { go(std::integral_constant<int, 4>{}, ncv, std::true_type{}); });
+    else by_bps(p->g.bps, [&](auto bps) { by_nc(c.nc, [&](auto ncv) { go(bps, ncv, std::false_type{}); }); });
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
+}
+
+int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients,
+                                      int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes, void* stream) {
+    return iir_zero_phase_call(p, d_buf, d_buf, nblocks, n, d, nr_coefficients, init_nr_samples, backward_init_nr_samples, d_work, work_bytes, stream, false);
+}
+
+int rspt_hip_iir_zero_phase_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, int32_t* d_out, size_t nblocks, const double* n, const double* d,
+                                             size_t nr_coefficients, int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes,
+                                             void* stream) {
+    int32_t* src = const_cast<int32_t*>(d_planar);  // (only read unless d_out is the matrix itself)
+    return iir_zero_phase_call(p, src, d_out ? d_out : src, nblocks, n, d, nr_coefficients, init_nr_samples, backward_init_nr_samples, d_work, work_bytes, stream,
+                               true);
 }
 
 // ---- the frame of the sliding-window stages (FIR, median), on the native block and on the planar int32 matrix ----

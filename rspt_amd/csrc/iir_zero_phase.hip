@@ -1,6 +1,6 @@
 // iir_zero_phase.hip -- the zero-phase (forward-backward) IIR stage: one reference filter object per (block, channel) run forward
-// over the block and then backward over its own untruncated outputs, truncated once (rspt_hip_iir_zero_phase_batch_dev;
-// semantics: rspt_hip.h).
+// over the block and then backward over its own untruncated outputs, truncated once (rspt_hip_iir_zero_phase_batch_dev, and
+// rspt_hip_iir_zero_phase_planar_batch_dev on the converters' int32 matrix; semantics: rspt_hip.h).
 //
 // The reference's offline user runs a filter forward and then backward over the SAME object (peak_detector.h:309-328), so the
 // rings run on through the turn:
@@ -47,6 +47,26 @@ __global__ __launch_bounds__(64) void k_iir_zp(uint8_t* __restrict__ buf, uint32
         sample_store<BPS>(p + (size_t)s * stride, trunc_i32_c(f.step_opt(c.n, c.d, W[(size_t)s * 64u])), aligned);  // C truncation, once
 }
 
+// k_iir_zp on the planar matrix (rspt_hip_iir_zero_phase_planar_batch_dev): row r = b * nch + ch of the converters' matrix
+// [nblocks][nch][ns], sample s at r * ns + s, the whole int32 the sample and the result stored whole.  The forward pass only reads
+// src and the backward pass only writes dst, so dst may be src itself (in place) or a matrix of its own.
+template <int NC>
+__global__ __launch_bounds__(64) void k_iir_zp_planar(const int32_t* src, int32_t* dst, uint32_t ns, IirCoef c, int32_t back_steps, uint32_t rows, double* work) {
+    const uint32_t r = blockIdx.x * 64u + threadIdx.x;
+    if (r >= rows) return;
+    const int32_t* x = src + (size_t)r * ns;
+    int32_t* y = dst + (size_t)r * ns;
+    double* W = work + (size_t)blockIdx.x * ns * 64u + threadIdx.x;  // this lane's column of its wave's slab
+    IirState<NC> f;
+    f.clear();
+    f.init_history(c, (double)x[0]);
+    for (uint32_t s = 0; s < ns; ++s) W[(size_t)s * 64u] = f.step_opt(c.n, c.d, (double)x[s]);
+    IirCoef cb = c;  // the turn, as in k_iir_zp
+    cb.init_steps = back_steps;
+    f.init_history(cb, f.y[0]);
+    for (uint32_t s = ns; s-- > 0;) y[s] = trunc_i32_c(f.step_opt(c.n, c.d, W[(size_t)s * 64u]));  // C truncation, once
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The pipelined kernel, in the manner of k_iir_pipe (filter.hip): a workgroup of six waves, lane <-> (block, channel) in all of
 // them, and the wave that holds the filter state issues only what depends on it.
@@ -74,6 +94,21 @@ __global__ __launch_bounds__(64) void k_iir_zp(uint8_t* __restrict__ buf, uint32
 // Needs ns >= 64 and a forward history that fills the ring's tail (the host checks; else k_iir_zp): in front of the channel's
 // first sample the x ring then holds x0.  Lanes past the batch read block 0, channel 0 along with the others, keep a column of
 // their own in the last slab (the workspace bound counts whole slabs) and store no sample.
+//
+// PLANAR (k_iir_zp_pipe_planar: the same ticks, roles and workspace; BPS = 4, aligned).  Lane <-> row r = b * nch + ch of the
+// matrix [nblocks][nch][ns], sample s of the row 4 bytes behind sample s - 1, the next row -- another lane's, or another
+// workgroup's -- directly behind the last sample.  Only two places see where a sample lives:
+//   the forward producers   a set inside the row takes its H samples in front as dwords and its 16-sample part, 64 contiguous
+//                           bytes, as four 16-byte loads that need the int32's alignment only (planar_load_set, filter.hip); a
+//                           set at an end of the row goes dword by dword, its sample INDEX clamped into the row, never an address
+//   the backward writer     the 16 outputs of a part lie at descending t: 64 contiguous bytes at ascending addresses, stored as
+//                           four 16-byte stores in reversed register order.  Only whole chunks go that way (all 64 positions are
+//                           samples of the row then); the partial last chunk is stored dword by dword, so no store passes
+//                           either end of the row
+// The producers read `buf` (the source) and the writer stores to `dst`, which is buf itself in place: x0 and every forward load
+// are issued in front of the barrier that ends the forward pass and the first sample is stored behind it, as in the native
+// kernel, so in place needs no staging and out of place costs nothing.  The backward producers, the forward writer, the
+// recurrence wave, the turn and L.xlast never see a sample's address.
 constexpr uint32_t kZpChunk = 64, kZpProd = 4, kZpPart = kZpChunk / kZpProd, kZpGroup = 16;
 constexpr uint32_t kZpThreads = 64 * (2 + kZpProd);
 constexpr uint32_t kZpWriter = 1 + kZpProd;
@@ -149,7 +184,7 @@ __device__ __forceinline__ void zp_wave_rec(ZpLds& L, const ZpWave& w, const Iir
 
 // waves 1-4: element j of a producer's set in chunk k is position k * 64 + part * 16 - H + j of the pass (forward: sample t = the
 // position; backward: t = ns - 1 - the position); the set is its 16 positions and the H in front of them.
-template <int BPS, int NC, bool ALIGNED>
+template <int BPS, int NC, bool ALIGNED, bool PLANAR = false>
 __device__ __forceinline__ void zp_wave_prod(ZpLds& L, const ZpWave& w, const IirCoef& c, int32_t back_steps, uint32_t part) {
     constexpr int H = NC - 1;
     constexpr uint32_t SET = kZpPart + H;
@@ -168,6 +203,10 @@ __device__ __forceinline__ void zp_wave_prod(ZpLds& L, const ZpWave& w, const Ii
         int32_t cur[SET], nxt[SET], nx2[SET];
         auto load_set = [&](int32_t (&v)[SET], uint32_t k) {
             const int32_t s0 = first(k);
+            if constexpr (PLANAR) {  // (w.p: the lane's row of the source matrix)
+                planar_load_set<(uint32_t)H, true>(PlanarRun{reinterpret_cast<int32_t*>(w.p), w.ns, 0}, w.ns, s0, v);
+                return;
+            }
             if (whole(s0)) {
                 const uint8_t* q = w.p + (size_t)s0 * w.stride;
 #pragma unroll
@@ -258,7 +297,7 @@ __device__ __forceinline__ void zp_wave_prod(ZpLds& L, const ZpWave& w, const Ii
 }
 
 // wave 5: the writer
-template <int BPS, bool ALIGNED>
+template <int BPS, bool ALIGNED, bool PLANAR = false>
 __device__ __forceinline__ void zp_wave_write(ZpLds& L, const ZpWave& w) {
     // forward: the untruncated doubles to the workspace
     for (uint32_t t = 0; t < w.nchunks + 2; ++t) {
@@ -291,6 +330,15 @@ __device__ __forceinline__ void zp_wave_write(ZpLds& L, const ZpWave& w) {
                     double v[kZpGroup];
 #pragma unroll
                     for (uint32_t e = 0; e < kZpGroup; ++e) v[e] = L.out[bi][e0 + e][w.lane];
+                    if constexpr (PLANAR) {
+                        // (a whole chunk: its 64 positions are samples of the row, so the group's 16 are the 64 bytes that end
+                        // with sample ns - 1 - (k * 64 + e0), in reversed order)
+                        int32_t r[kZpGroup];
+#pragma unroll
+                        for (uint32_t e = 0; e < kZpGroup; ++e) r[kZpGroup - 1u - e] = trunc_i32_c(v[e]);
+                        if (w.valid) __builtin_memcpy(q - (size_t)(e0 + kZpGroup - 1u) * 4u, &r[0], 64);
+                        continue;
+                    }
                     if (w.valid) {
 #pragma unroll
                         for (uint32_t e = 0; e < kZpGroup; ++e) sample_store<BPS>(q - (size_t)(e0 + e) * w.stride, trunc_i32_c(v[e]), ALIGNED);
@@ -307,31 +355,25 @@ __device__ __forceinline__ void zp_wave_write(ZpLds& L, const ZpWave& w) {
     }
 }
 
+// The body is a file of its own (k_iir_zp_pipe_body.hpp), included once into the native kernel and once into its planar form
+// with every planar statement under `if constexpr (PLANAR)`, as filter.hip's are and for its reason: the native instantiations
+// keep their names and are compiled from the statements they had (tools/isa_diff.py).
 template <int BPS, int NC, bool ALIGNED>
 __global__ __launch_bounds__(kZpThreads) void k_iir_zp_pipe(uint8_t* __restrict__ buf, uint32_t nch, uint32_t ns, uint64_t block_bytes, IirCoef c,
                                                           int32_t back_steps, uint32_t nblocks, double* work) {
-    __shared__ ZpLds L;
-    const uint32_t role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    ZpWave w;
-    w.lane = threadIdx.x & 63u;
-    const uint32_t unit = blockIdx.x * 64u + w.lane;
-    const uint32_t b = unit / nch, ch = unit - b * nch;
-    w.valid = b < nblocks;
-    w.stride = (size_t)nch * BPS;
-    w.p = buf + (size_t)(w.valid ? b : 0u) * block_bytes + (size_t)(w.valid ? ch : 0u) * BPS;
-    w.W = work + (size_t)blockIdx.x * ns * 64u + w.lane;
-    w.ns = ns;
-    w.nchunks = (ns + kZpChunk - 1) / kZpChunk;
-    w.x0 = (double)sample_load<BPS>(w.p, ALIGNED);
-    if (role == 0u) {
-        // six waves on four SIMDs: the wave with the recurrence shares its SIMD with a producer -- it goes first whenever it can issue
-        __builtin_amdgcn_s_setprio(3);
-        zp_wave_rec<NC>(L, w, c, back_steps);
-    } else if (role == kZpWriter) {
-        zp_wave_write<BPS, ALIGNED>(L, w);
-    } else {
-        zp_wave_prod<BPS, NC, ALIGNED>(L, w, c, back_steps, role - 1u);
-    }
+    constexpr bool PLANAR = false;
+    uint8_t* const dst = buf;
+#include "k_iir_zp_pipe_body.hpp"
+}
+
+// buf: the source matrix, only read; dst: where the result goes, buf itself in place (so neither is __restrict__); block_bytes:
+// one [nch][ns] block of the matrix.
+template <int NC>
+__global__ __launch_bounds__(kZpThreads) void k_iir_zp_pipe_planar(uint8_t* buf, uint8_t* dst, uint32_t nch, uint32_t ns, uint64_t block_bytes, IirCoef c,
+                                                                 int32_t back_steps, uint32_t nblocks, double* work) {
+    constexpr int BPS = 4;
+    constexpr bool ALIGNED = true, PLANAR = true;
+#include "k_iir_zp_pipe_body.hpp"
 }
 
 }  // namespace rspt
