@@ -468,7 +468,8 @@ int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblo
  * call of 2^31 - 2^17 rows or more.  A refused call writes nothing.  Asynchronous on `stream`; the entries allocate nothing.
  * Of the other stages the FIR pre-filter, the median and PRDN have planar forms too (rspt_hip_fir_prefilter_planar_batch_dev,
  * rspt_hip_median_filter_planar_batch_dev, rspt_hip_prdn_planar_batch_dev below), and so has the zero-phase IIR
- * (rspt_hip_iir_zero_phase_planar_batch_dev); the peak stages, which only read samples, stay native-only. */
+ * (rspt_hip_iir_zero_phase_planar_batch_dev) and both R-peak detectors (rspt_hip_peak_detect_planar_batch_dev,
+ * rspt_hip_peak_detect_offline_planar_batch_dev): every stage has a planar form. */
 int rspt_hip_iir_prefilter_planar_batch_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
                                             size_t nr_coefficients, int init_nr_samples, int per_channel, void* stream);
 int rspt_hip_iir_prefilter_planar_stream_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d,
@@ -800,6 +801,32 @@ int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int sta
 int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
                                            void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
                                            size_t max_peaks, double* d_sig, double* d_threshold, void* stream);
+
+/* ---- both R-peak detectors on the planar int32 matrix --------------------------------------------------------------
+ * rspt_hip_peak_detect_batch_dev and rspt_hip_peak_detect_offline_batch_dev on the converters' matrix: what the reference's user
+ * runs behind the filters (band-pass or zero-phase filter, then detect), without leaving the matrix the planar filters wrote.
+ * The reference's loop hands (double) of the int32 matrix element to detect(); so do these entries.  A planar filter stores its
+ * result whole and rspt_hip_i32_to_native_batch_dev cuts to the handle's width, so on a handle of bps < 4 the peaks of a filtered
+ * recording can be taken on the filter's own values only here.  Everything is the native sibling's, but:
+ *   d_planar      int32 [nblocks][nch][ns], block b's channel c at d_planar + (b * nch + c) * ns; 4-byte alignment is all it needs;
+ *                 only read.  The WHOLE int32 is the sample: the handle's bps and byte order have no effect.
+ *   d_count, d_index, d_value   unchanged (they are [nblocks][nch](...) already).
+ *   d_sig, d_threshold  optional [nblocks][nch][ns] doubles: planar as the samples are, row b * nch + c the traces of that row
+ *                 of the matrix.
+ *   d_state       the native layout and size (rspt_hip_peak_state_bytes); all-zero bytes are fresh detectors.  Channel c runs
+ *                 through rows c, nch + c, 2 nch + c, ... and on into the next call.  Native calls on a bps = 4 handle and
+ *                 planar calls may alternate on one state, and so may the online / OFFLINE_FW and the offline entries, as
+ *                 natively.
+ *   d_work        the native workspace and size (rspt_hip_peak_offline_work_bytes); needs no initialisation.
+ * Refused as the native sibling refuses it, and RSPT_HIP_ERR_ARG for a d_planar off its 4-byte alignment; more than 8191
+ * channels: RSPT_HIP_ERR_UNSUPPORTED.  All refusals come before any launch, and a refused call writes nothing.  Asynchronous on
+ * `stream`; the entries allocate nothing. */
+int rspt_hip_peak_detect_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, int variant, double sampling_rate,
+                                          double marker_val, void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks,
+                                          double* d_sig, double* d_threshold, void* stream);
+int rspt_hip_peak_detect_offline_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, double sampling_rate,
+                                                  double marker_val, void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index,
+                                                  double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, void* stream);
 
 /* ---- the reference's quality figure: PRDN[%] of a decoded block against its original ------------------------------
  * What test_packer_ prints behind a round trip (lib_rspt_test/rspt_test.cpp:98-111), the only quality figure the reference

@@ -97,6 +97,8 @@ C_ABI = {
     "rspt_hip_peak_detect_batch_dev": (_i, [_p, _p, _z, _i, _d, _d, _p, _p, _p, _p, _z, _p, _p, _p]),
     "rspt_hip_peak_offline_work_bytes": (_i, [_p, _z, _i, _szp]),
     "rspt_hip_peak_detect_offline_batch_dev": (_i, [_p, _p, _z, _d, _d, _p, _p, _p, _p, _p, _z, _p, _p, _p]),
+    "rspt_hip_peak_detect_planar_batch_dev": (_i, [_p, _p, _z, _i, _d, _d, _p, _p, _p, _p, _z, _p, _p, _p]),
+    "rspt_hip_peak_detect_offline_planar_batch_dev": (_i, [_p, _p, _z, _d, _d, _p, _p, _p, _p, _p, _z, _p, _p, _p]),
     "rspt_hip_prdn_batch_dev": (_i, [_p, _p, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_prdn_planar_batch_dev": (_i, [_p, _p, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_native_to_i32_batch_dev": (_i, [_p, _p, _p, _z, _p]),
@@ -704,20 +706,21 @@ class SignalPacker:
         """A zeroed state for peak_detect_batch(state=...): a fresh detector for every channel (uint8 device tensor)."""
         return self._zero_state(self.peak_state_bytes(), device)
 
-    def _peak_call_buffers(self, d_src, max_peaks, state, traces, stream):
-        """What both peak entries share: checks d_src (whole blocks of contiguous uint8 on the device) and state, allocates
-        (count, index, value, sig, thr) -- sig and thr None without traces -- and picks the stream (the current one when None).
+    def _peak_call_buffers(self, d_src, max_peaks, state, traces, stream, planar=False):
+        """What all peak entries share: checks d_src (whole blocks of contiguous uint8 on the device; planar: an int32 matrix
+        [nblocks, nch, ns]) and state, allocates (count, index, value, sig, thr) -- sig and thr None without traces, and laid out
+        as the samples are -- and picks the stream (the current one when None).
         -> (nblocks, outputs, stream, ptr); ptr(t): t's device pointer, None for None or an empty tensor."""
         import torch
 
-        nblocks = self._nblocks(d_src)
+        nblocks = self._nblocks(d_src, torch.int32, self.nch * self.ns) if planar else self._nblocks(d_src)
         dev = d_src.device
         count = torch.empty((nblocks, self.nch), dtype=torch.int32, device=dev)
         index = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.int32, device=dev)
         value = torch.empty((nblocks, self.nch, max_peaks), dtype=torch.float64, device=dev)
         sig = thr = None
         if traces:
-            sig = torch.empty((nblocks, self.ns, self.nch), dtype=torch.float64, device=dev)
+            sig = torch.empty((nblocks, self.nch, self.ns) if planar else (nblocks, self.ns, self.nch), dtype=torch.float64, device=dev)
             thr = torch.empty_like(sig)
         if state is not None:
             assert state.is_cuda and state.is_contiguous() and state.numel() * state.element_size() >= self.peak_state_bytes()
@@ -731,12 +734,24 @@ class SignalPacker:
         carries one detector per channel through the blocks and across calls (of one variant and sampling rate).  Asynchronous.
         Returns (count [nblocks, nch] int32, index [nblocks, nch, max_peaks] int32, value [nblocks, nch, max_peaks] float64) and,
         with traces, (sig, threshold) [nblocks, ns, nch] float64 as well."""
+        return self._peak_detect("rspt_hip_peak_detect_batch_dev", False, d_src, variant, sampling_rate, marker_val, max_peaks, state, traces, stream)
+
+    def peak_detect_planar_batch(self, d_planar, variant="online", sampling_rate=None, marker_val=1.0, max_peaks=64, state=None, traces=False,
+                                 stream=None):
+        """peak_detect_batch on samples that live in int32 (rspt_hip.h: rspt_hip_peak_detect_planar_batch_dev): d_planar is a
+        torch.int32 cuda tensor [nblocks, nch, ns], only read; the whole int32 value is the sample, whatever the handle's bps.
+        Returns what peak_detect_batch returns, the traces [nblocks, nch, ns].  state: a peak_state() tensor, which may
+        alternate with native calls where the handle's bps is 4."""
+        return self._peak_detect("rspt_hip_peak_detect_planar_batch_dev", True, d_planar, variant, sampling_rate, marker_val, max_peaks, state, traces,
+                                 stream)
+
+    def _peak_detect(self, entry, planar, d_src, variant, sampling_rate, marker_val, max_peaks, state, traces, stream):
         if sampling_rate is None:
             raise ValueError("peak_detect_batch: sampling_rate is required")
         v = PEAK_VARIANTS[variant] if isinstance(variant, str) else int(variant)
-        nblocks, out, st, ptr = self._peak_call_buffers(d_src, max_peaks, state, traces, stream)
+        nblocks, out, st, ptr = self._peak_call_buffers(d_src, max_peaks, state, traces, stream, planar)
         count, index, value, sig, thr = out
-        self._call("rspt_hip_peak_detect_batch_dev", d_src.data_ptr(), nblocks, v, float(sampling_rate), float(marker_val), ptr(state),
+        self._call(entry, d_src.data_ptr(), nblocks, v, float(sampling_rate), float(marker_val), ptr(state),
                    count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
         return out if traces else out[:3]
 
@@ -750,13 +765,24 @@ class SignalPacker:
         alternate with peak_detect_batch(variant="offline_fw") calls at the same rate).  The workspace is allocated here.
         Asynchronous.  Returns what peak_detect_batch returns: (count, index, value) of the final peak_signal's non-zero entries
         and, with traces, (filt_signal, threshold_signal) [nblocks, ns, nch] float64 as well."""
+        return self._peak_detect_offline("rspt_hip_peak_detect_offline_batch_dev", False, d_src, sampling_rate, marker_val, max_peaks, state, traces,
+                                         stream)
+
+    def peak_detect_offline_planar_batch(self, d_planar, sampling_rate, marker_val=1.0, max_peaks=64, state=None, traces=False, stream=None):
+        """peak_detect_offline_batch on samples that live in int32 (rspt_hip.h: rspt_hip_peak_detect_offline_planar_batch_dev):
+        d_planar is a torch.int32 cuda tensor [nblocks, nch, ns], only read; the whole int32 value is the sample.  Returns what
+        peak_detect_offline_batch returns, the traces [nblocks, nch, ns]."""
+        return self._peak_detect_offline("rspt_hip_peak_detect_offline_planar_batch_dev", True, d_planar, sampling_rate, marker_val, max_peaks, state,
+                                         traces, stream)
+
+    def _peak_detect_offline(self, entry, planar, d_src, sampling_rate, marker_val, max_peaks, state, traces, stream):
         import torch
 
-        nblocks, out, st, ptr = self._peak_call_buffers(d_src, max_peaks, state, traces, stream)
+        nblocks, out, st, ptr = self._peak_call_buffers(d_src, max_peaks, state, traces, stream, planar)
         count, index, value, sig, thr = out
         dev = d_src.device
         work = torch.empty(max(1, (self.peak_offline_work_bytes(max(nblocks, 1), state is not None) + 7) // 8), dtype=torch.float64, device=dev)
-        self._call("rspt_hip_peak_detect_offline_batch_dev", d_src.data_ptr(), nblocks, float(sampling_rate), float(marker_val), ptr(state),
+        self._call(entry, d_src.data_ptr(), nblocks, float(sampling_rate), float(marker_val), ptr(state),
                    work.data_ptr(), count.data_ptr(), ptr(index), ptr(value), max_peaks, ptr(sig), ptr(thr), st)
         if stream is not None:  # (the workspace goes back to torch's pool only once the caller's stream is past this call)
             work.record_stream(torch.cuda.ExternalStream(stream, device=dev))

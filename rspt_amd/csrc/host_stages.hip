@@ -1122,18 +1122,19 @@ int rspt_hip_design_iir(int type, int order, double sampling_rate, double cutoff
 }
 
 // ---- R-peak detectors (peak.hip) ----
-// The checks both peak entries make, and the kernel arguments from them (all of PeakOffArgs but its workspace): false where
-// either entry refuses the call.
+// The checks all four peak entries make, and the kernel arguments from them (all of PeakOffArgs but its workspace): false where
+// an entry refuses the call.  planar: d_src is the int32 matrix [nblocks][nch][ns] (and the traces are matrices of that shape).
 static bool peak_args(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, void* d_state, uint32_t* d_count,
-                      int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, PeakArgs& a) {
+                      int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, PeakArgs& a, bool planar) {
     if (!p || !d_src || !d_count || !batch_count_ok(p, nblocks)) return false;
+    if (planar && reinterpret_cast<uintptr_t>(d_src) % 4) return false;
     if (!std::isfinite(sampling_rate) || sampling_rate <= 0 || sampling_rate > (double)(1 << 20)) return false;
     if (max_peaks > 0 && (!d_index || !d_value)) return false;
     if ((uint64_t)max_peaks > (1ull << 32) || (!d_sig) != (!d_threshold)) return false;
     const Geom& g = p->g;
     a.src = (const uint8_t*)d_src;
-    a.block_bytes = g.block_bytes;
-    a.stride = g.nch * g.bps;
+    a.block_bytes = planar ? (uint64_t)g.N * sizeof(int32_t) : g.block_bytes;
+    a.stride = planar ? (uint32_t)sizeof(int32_t) : g.nch * g.bps;
     a.nch = g.nch;
     a.ns = g.ns;
     a.nblocks = (uint32_t)nblocks;
@@ -1180,26 +1181,48 @@ int rspt_hip_peak_state_bytes(rspt_hip_packer* p, size_t* bytes) {
     return RSPT_HIP_OK;
 }
 
-int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
-                                   void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
-                                   double* d_threshold, void* stream) {
+// Both online entries: d_src is the native batch, or (planar) the int32 matrix.
+static int peak_call(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val, void* d_state,
+                     uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, void* stream,
+                     bool planar) {
     PeakArgs a{};
     PeakCoef c{};
     if (variant < kPeakOnline || variant > kPeakOfflineFw ||
-        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
+        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a, planar) ||
         !peak_coef(variant, sampling_rate, marker_val, c))
         return RSPT_HIP_ERR_ARG;
     if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
-    return by_bps(p->g.bps, [&](auto bb) {
-        constexpr int B = decltype(bb)::value;
-        auto go = [&](auto vv) {
-            constexpr int V = decltype(vv)::value;
-            return peak_launch(p, d_sig ? &k_peak<B, V, true> : &k_peak<B, V, false>, a, c, stream);
-        };
+    auto by_variant = [&](auto go) {
         if (variant == kPeakOnline) return go(std::integral_constant<int, kPeakOnline>());
         if (variant == kPeakOnline1st) return go(std::integral_constant<int, kPeakOnline1st>());
         return go(std::integral_constant<int, kPeakOfflineFw>());
+    };
+    if (planar)
+        return by_variant([&](auto vv) {
+            constexpr int V = decltype(vv)::value;
+            return peak_launch(p, d_sig ? &k_peak_planar<V, true> : &k_peak_planar<V, false>, a, c, stream);
+        });
+    return by_bps(p->g.bps, [&](auto bb) {
+        constexpr int B = decltype(bb)::value;
+        return by_variant([&](auto vv) {
+            constexpr int V = decltype(vv)::value;
+            return peak_launch(p, d_sig ? &k_peak<B, V, true> : &k_peak<B, V, false>, a, c, stream);
+        });
     });
+}
+
+int rspt_hip_peak_detect_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, int variant, double sampling_rate, double marker_val,
+                                   void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
+                                   double* d_threshold, void* stream) {
+    return peak_call(p, d_src, nblocks, variant, sampling_rate, marker_val, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, stream,
+                     false);
+}
+
+int rspt_hip_peak_detect_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, int variant, double sampling_rate,
+                                          double marker_val, void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks,
+                                          double* d_sig, double* d_threshold, void* stream) {
+    return peak_call(p, d_planar, nblocks, variant, sampling_rate, marker_val, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold,
+                     stream, true);
 }
 
 int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int stateful, size_t* bytes) {
@@ -1210,13 +1233,14 @@ int rspt_hip_peak_offline_work_bytes(rspt_hip_packer* p, size_t nblocks, int sta
     return RSPT_HIP_OK;
 }
 
-int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
-                                           void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
-                                           size_t max_peaks, double* d_sig, double* d_threshold, void* stream) {
+// Both offline entries, as peak_call.
+static int peak_offline_call(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val, void* d_state,
+                             void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig,
+                             double* d_threshold, void* stream, bool planar) {
     PeakOffArgs a{};
     PeakOffCoef k{};
     if (!d_work || ((uintptr_t)d_work % 8) != 0 ||
-        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a) ||
+        !peak_args(p, d_src, nblocks, sampling_rate, d_state, d_count, d_index, d_value, max_peaks, d_sig, d_threshold, a, planar) ||
         !peak_coef(kPeakOfflineFw, sampling_rate, marker_val, k.c))
         return RSPT_HIP_ERR_ARG;
     if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
@@ -1227,8 +1251,23 @@ int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src
     // peak_detector_offline's constructor adds the baseline: a 0.5 Hz first-order low-pass
     if (!design_iir(kFiltLowPass, 1, sampling_rate, 0.5, 0.0, k.lf, k.lb)) return RSPT_HIP_ERR_ARG;
     a.work = (uint8_t*)d_work;
+    if (planar) return peak_launch(p, d_sig ? &k_peak_offline_planar<true> : &k_peak_offline_planar<false>, a, k, stream);
     return by_bps(p->g.bps, [&](auto bb) {
         constexpr int B = decltype(bb)::value;
         return peak_launch(p, d_sig ? &k_peak_offline<B, true> : &k_peak_offline<B, false>, a, k, stream);
     });
+}
+
+int rspt_hip_peak_detect_offline_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, double sampling_rate, double marker_val,
+                                           void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value,
+                                           size_t max_peaks, double* d_sig, double* d_threshold, void* stream) {
+    return peak_offline_call(p, d_src, nblocks, sampling_rate, marker_val, d_state, d_work, d_count, d_index, d_value, max_peaks, d_sig, d_threshold,
+                             stream, false);
+}
+
+int rspt_hip_peak_detect_offline_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, double sampling_rate,
+                                                  double marker_val, void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index,
+                                                  double* d_value, size_t max_peaks, double* d_sig, double* d_threshold, void* stream) {
+    return peak_offline_call(p, d_planar, nblocks, sampling_rate, marker_val, d_state, d_work, d_count, d_index, d_value, max_peaks, d_sig,
+                             d_threshold, stream, true);
 }

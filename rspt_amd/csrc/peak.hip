@@ -12,6 +12,10 @@
 // (peak_aligned) and each (block, channel)'s output pointers (peak_out).  The few lines of lane mapping stay in each kernel: moved
 // into a helper they changed k_peak's register allocation.
 //
+// Both kernels have a planar form (k_peak_planar, k_peak_offline_planar) on the converters' int32 matrix [nblocks][nch][ns]: the
+// same bodies (k_peak_block_body.hpp, k_peak_offline_block_body.hpp, each included into the native function and into the planar
+// one) with a row's address map, so that the native instantiations stay what they were.
+//
 // Double arithmetic in the reference's order of operations, every product and sum rounded on its own (no FMA: see the pragma),
 // so every trace value and every event is bit-identical with the reference's x86-64 build.
 #include <cmath>
@@ -313,89 +317,37 @@ struct PeakDet : PeakBaseline<BL> {
     }
 };
 
+// Two doubles side by side in a trace row: one 16-byte store.  A row of doubles starts on an 8-byte boundary and no better
+// (row * ns may be odd), which is all a global store of four dwords needs.
+typedef double peak_d2 __attribute__((ext_vector_type(2), aligned(8)));
+__device__ __forceinline__ void store_d2(double* q, double a, double b) {
+    peak_d2 v;
+    v.x = a;
+    v.y = b;
+    *reinterpret_cast<peak_d2*>(q) = v;
+}
+
 // Runs one detector through one block (ns samples at p, row stride `stride`); events and traces of this (block, channel).
 template <int BPS, int V, bool TR>
 __device__ void peak_block(PeakDet<V>& D, const PeakCoef& c, const uint8_t* p, uint32_t stride, uint32_t ns, bool aligned, uint32_t* count,
                            int32_t* index, double* value, uint64_t max_peaks, double* sig, double* thr, uint32_t nch) {
-    constexpr int NB = PeakDet<V>::NB;
-    uint32_t cnt = 0;
-    auto emit = [&](uint32_t t, bool fire, double s, double h) {
-        if (TR) {
-            sig[(size_t)t * nch] = s;
-            thr[(size_t)t * nch] = h;
-        }
-        if (fire) {
-            if (cnt < max_peaks) {
-                index[cnt] = (int32_t)t;
-                value[cnt] = c.marker == -1.0 ? s : c.marker;
-            }
-            ++cnt;
-        }
-    };
-    if (V == kPeakOfflineFw) peak_history(D.bp, c.bb, c.bf, (double)sample_load<BPS>(p, aligned), c.hist);  // every detect_fw call
-    // ONLINE: the history runs where sample_indx_ is 0 -- the first sample of a fresh detector, or where the int wraps back
-    // to 0 after 2^32 samples (then this block takes the sample-by-sample path below)
-    bool simple = false;
-    if (V != kPeakOfflineFw) {  // sample 0's `if (!sample_indx_++)`
-        const bool first = D.idx == 0;
-        simple = !first && (uint64_t)D.idx + ns > (1ull << 32);  // (0 comes back inside this block)
-        if (first) peak_history(D.bp, c.bb, c.bf, (double)sample_load<BPS>(p, aligned), c.hist);
-        D.idx += 1;
-    }
-    if (simple) {
-        for (uint32_t t = 0; t < ns; ++t) {
-            const double x = (double)sample_load<BPS>(p + (size_t)t * stride, aligned);
-            if (t > 0) {  // (sample 0's index was handled above)
-                if (D.idx == 0) peak_history(D.bp, c.bb, c.bf, x, c.hist);
-                D.idx += 1;
-            }
-            double s, h;
-            const bool f = D.tail(c, D.bp.step_opt(c.bb, c.bf, x), s, h);
-            emit(t, f, s, h);
-        }
-        count[0] = cnt;
-        return;
-    }
-    if (V != kPeakOfflineFw) D.idx += ns - 1;  // (no wrap back to 0 in this block)
-    // Chunks of CH samples: the next chunk's loads are in flight while this one runs, and the band-pass feed-forward sums of
-    // the chunk (independent of every output) are formed up front, for the scheduler to place into the dependent chain.
-    constexpr uint32_t CH = 16;
-    int32_t cur[CH], nxt[CH];
-    const uint32_t nfull = ns / CH;
-    if (nfull) {
-#pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) cur[e] = sample_load<BPS>(p + (size_t)e * stride, aligned);
-    }
-    for (uint32_t k = 0; k < nfull; ++k) {
-        const uint8_t* q = p + (size_t)k * CH * stride;
-        if (k + 1 < nfull) {
-#pragma unroll
-            for (uint32_t e = 0; e < CH; ++e) nxt[e] = sample_load<BPS>(q + (size_t)(CH + e) * stride, aligned);
-        }
-        double xs[CH + NB - 1], ff[CH];
-#pragma unroll
-        for (int i = 0; i < NB - 1; ++i) xs[i] = D.bp.x[NB - 2 - i];
-#pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) xs[NB - 1 + e] = (double)cur[e];
-#pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) ff[e] = iir_ff<NB>(c.bf, &xs[NB - 1 + e]);
-#pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) {
-            double s, h;
-            const bool f = D.tail(c, D.bp.feedback(c.bb, ff[e]), s, h);
-            emit(k * CH + e, f, s, h);
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) D.bp.x[i] = xs[CH + NB - 2 - i];
-#pragma unroll
-        for (uint32_t e = 0; e < CH; ++e) cur[e] = nxt[e];
-    }
-    for (uint32_t t = nfull * CH; t < ns; ++t) {
-        double s, h;
-        const bool f = D.tail(c, D.bp.step_opt(c.bb, c.bf, (double)sample_load<BPS>(p + (size_t)t * stride, aligned)), s, h);
-        emit(t, f, s, h);
-    }
-    count[0] = cnt;
+    constexpr bool PLANAR = false;
+    const int32_t* row = nullptr;  // (the planar form's arguments: named in the body's planar statements only)
+    const bool vec = false;
+#include "k_peak_block_body.hpp"
+}
+
+// peak_block on a row of the planar int32 matrix: the detector's ns samples side by side at `row` (the whole int32 is the
+// sample), its traces the rows sig / thr of ns doubles.  vec: every row of the matrix starts on a 16-byte boundary.
+template <int V, bool TR>
+__device__ void peak_block_planar(PeakDet<V>& D, const PeakCoef& c, const int32_t* row, uint32_t ns, bool vec, uint32_t* count, int32_t* index,
+                                  double* value, uint64_t max_peaks, double* sig, double* thr) {
+    constexpr int BPS = 4;
+    constexpr bool PLANAR = true;
+    const uint8_t* p = nullptr;  // (the native form's arguments: named in the body's native statements only)
+    constexpr uint32_t stride = 0, nch = 1;
+    constexpr bool aligned = true;
+#include "k_peak_block_body.hpp"
 }
 
 // Whether both kernels' sample loads may be whole words: wave-uniform, as every block base and row start is aligned when the
@@ -446,6 +398,41 @@ __global__ __launch_bounds__(64) void k_peak(PeakArgs a, PeakCoef c) {
                                a.max_peaks, o.sig, o.thr, a.nch);
     }
     if (a.state) D.save(a.state, a.nch, ch);
+}
+
+// ---- the planar forms ---------------------------------------------------------------------------------------------------
+// The samples are the converters' int32 matrix [nblocks][nch][ns] at a.src and the traces matrices of doubles of that shape:
+// detector (b, ch) reads row b * nch + ch and writes that row of each trace.  a.block_bytes and a.stride are not used.
+
+// Whether every row of the matrix starts on a 16-byte boundary (wave-uniform): then a lane's chunks may be 16-byte loads.
+__device__ __forceinline__ bool peak_rows_vec(const PeakArgs& a) { return (reinterpret_cast<uintptr_t>(a.src) % 16) == 0 && (a.ns % 4u) == 0; }
+
+template <bool TR>
+__device__ __forceinline__ PeakOut peak_out_planar(const PeakArgs& a, uint64_t rowi) {
+    const uint64_t tr = rowi * a.ns;
+    return PeakOut{a.count + rowi, a.index + rowi * a.max_peaks, a.value + rowi * a.max_peaks, TR ? a.sig + tr : nullptr, TR ? a.thr + tr : nullptr};
+}
+
+// One lane per detector, as k_peak: lane q is row q (fresh), or channel q through rows q, nch + q, ... (stateful).
+template <int V, bool TR>
+__global__ __launch_bounds__(64) void k_peak_planar(PeakArgs a, PeakCoef c) {
+    const uint32_t q = blockIdx.x * 64u + threadIdx.x;
+    if (q >= a.lanes) return;
+    const bool vec = peak_rows_vec(a);
+    const int32_t* m = reinterpret_cast<const int32_t*>(a.src);
+    PeakDet<V> D;
+    uint64_t r0 = q, r1 = (uint64_t)q + 1;  // the lane's rows: r0, r0 + step, ... below r1
+    if (a.state) {
+        r1 = (uint64_t)a.nblocks * a.nch;
+        D.load(a.state, a.nch, q);
+    } else {
+        D.clear();
+    }
+    for (uint64_t r = r0; r < r1; r += a.nch) {
+        const PeakOut o = peak_out_planar<TR>(a, r);
+        peak_block_planar<V, TR>(D, c, m + r * a.ns, a.ns, vec, o.count, o.index, o.value, a.max_peaks, o.sig, o.thr);
+    }
+    if (a.state) D.save(a.state, a.nch, q);
 }
 
 // ---- peak_detector_offline::detect (zero-phase) -------------------------------------------------------------------------
@@ -500,6 +487,14 @@ __device__ __forceinline__ void off_walk(uint32_t ns, Ld load, Body body) {
 struct OffPair {
     double a, b;
 };
+// the planar walks' steps of four samples: the 16 bytes of the row with their four V values; four (F, T) pairs
+struct OffXV4 {
+    int4 x;
+    double v[4];
+};
+struct OffFT4 {
+    OffPair v[4];
+};
 
 // Runs detect() once: one block of one detector (band-pass, integrator, threshold, state machine and the baseline D.bl).
 // V, F, T, E: this lane's column of its wave's slab (element t at [t * 64]).
@@ -507,116 +502,10 @@ template <int BPS, bool TR>
 __device__ void peak_offline_block(PeakDet<kPeakOfflineFw, true>& D, const PeakOffCoef& k, const uint8_t* p, uint32_t stride,
                                    uint32_t ns, bool aligned, double* V, double* F, double* T, int32_t* E, uint32_t* count, int32_t* index,
                                    double* value, uint64_t max_peaks, double* sig, double* thr, uint32_t nch) {
-    const PeakCoef& c = k.c;
-    auto xs = [&](uint32_t t) { return (double)sample_load<BPS>(p + (size_t)t * stride, aligned); };
-    const double x0 = xs(0);
-    peak_history(D.bp, c.bb, c.bf, x0, c.hist);  // bandpass_ then baseline_ init_history_values(ecg_signal[0], fs)
-    peak_history(D.bl, k.lb, k.lf, x0, c.hist);
-    // baseline forward (stored), band-pass forward (state only)
-    off_walk<16, false>(ns, xs, [&](uint32_t t, double x) {
-        V[(size_t)t * 64] = D.bl.step_opt(k.lb, k.lf, x);
-        D.bp.step_opt(c.bb, c.bf, x);
-    });
-    // baseline backward in place (kept as x - baseline, all the relocation reads), band-pass backward on x again
-    off_walk<8, true>(ns, [&](uint32_t t) { return OffPair{xs(t), V[(size_t)t * 64]}; }, [&](uint32_t t, OffPair v) {
-        V[(size_t)t * 64] = v.a - D.bl.step_opt(k.lb, k.lf, v.b);
-        F[(size_t)t * 64] = D.bp.step_opt(c.bb, c.bf, v.a);
-    });
-    auto fs = [&](uint32_t t) { return F[(size_t)t * 64]; };
-    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step_opt(c.gb, c.gf, f * f); });
-    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { F[(size_t)t * 64] = D.ig.step_opt(c.gb, c.gf, f); });
-    off_walk<16, false>(ns, fs, [&](uint32_t t, double f) { D.th.step_opt(c.tb, c.tf, f); });
-    off_walk<16, true>(ns, fs, [&](uint32_t t, double f) { T[(size_t)t * 64] = D.th.step_opt(c.tb, c.tf, f); });
-    // the state machine; p over T, the shift folded in; E: the non-zero positions of p, those below nslope first (n0 of them)
-    const uint32_t nslope = (uint32_t)c.nslope;  // (>= 1: the host refuses 0)
-    uint32_t n = 0, n0 = 0;
-    off_walk<8, false>(ns, [&](uint32_t t) { return OffPair{F[(size_t)t * 64], T[(size_t)t * 64]}; }, [&](uint32_t t, OffPair v) {
-        if (TR) {
-            sig[(size_t)t * nch] = v.a;
-            thr[(size_t)t * nch] = v.b;
-        }
-        const bool fire = D.machine(c, v.a, v.b);
-        const double val = c.marker == -1.0 ? v.a : c.marker;
-        const bool ev = fire && val != 0.0;  // (`if (peak_signal[i])`: NaN is an event, -0.0 is not)
-        const bool below = t < nslope;
-        T[(size_t)t * 64] = ev && below ? val : 0.0;
-        if (ev && (below || nslope > 1)) {
-            const uint32_t at = below ? t : t - nslope + 1u;
-            if (!below) T[(size_t)at * 64] = val;
-            E[(size_t)n * 64] = (int32_t)at;
-            n += 1;
-            n0 += below ? 1u : 0u;
-        }
-    });
-    // the relocation: visits the non-zero p[i], radius <= i <= ns - radius - 1, in ascending order, as the reference's loop
-    // does -- including a value moved ahead of i (visited again) and a value written over another (the later write wins).
-    // The candidates past the last visit `pos` are the E positions and, up to `fwd`, the targets of moves ahead.
-    const int32_t r = k.radius;
-    const int32_t lim = (int32_t)ns - r - 1;
-    int32_t pos = r - 1, fwd = -1;
-    uint32_t ia = 0, ib = n0;
-    constexpr int32_t kNone = 0x7fffffff;
-    for (;;) {
-        while (ia < n0 && E[(size_t)ia * 64] <= pos) ++ia;
-        while (ib < n && E[(size_t)ib * 64] <= pos) ++ib;
-        const int32_t ca = ia < n0 ? E[(size_t)ia * 64] : kNone, cb = ib < n ? E[(size_t)ib * 64] : kNone;
-        int32_t q = ca < cb ? ca : cb;
-        if (fwd > pos) {  // a dense look at (pos, min(fwd, q - 1)], 8 loads at a time
-            const int32_t hi = fwd < q - 1 ? fwd : q - 1;
-            for (int32_t a0 = pos + 1; a0 <= hi; a0 += 8) {
-                double w[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) w[u] = T[(size_t)(a0 + u <= hi ? a0 + u : hi) * 64];
-                int32_t f = kNone;
-#pragma unroll
-                for (int u = 7; u >= 0; --u) f = (a0 + u <= hi && w[u] != 0.0) ? a0 + u : f;
-                if (f != kNone) {
-                    q = f;
-                    break;
-                }
-            }
-        }
-        if (q > lim) break;
-        const double pv = T[(size_t)q * 64];
-        double mx = -2000000.0, mn = 2000000.0;
-        int32_t mxi = 0, mni = 0;
-        const int32_t j1 = q + r;  // (exclusive)
-        for (int32_t j0 = q - r; j0 < j1; j0 += 8) {
-            double w[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) w[u] = V[(size_t)(j0 + u < j1 ? j0 + u : j1 - 1) * 64];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (j0 + u < j1) {
-                    if (mx < w[u]) {
-                        mx = w[u];
-                        mxi = j0 + u;
-                    }
-                    if (mn > w[u]) {
-                        mn = w[u];
-                        mni = j0 + u;
-                    }
-                }
-            }
-        }
-        const int32_t to = mx > -mn ? mxi : mni;
-        T[(size_t)q * 64] = 0.0;
-        T[(size_t)to * 64] = pv;
-        if (to > q && to > fwd) fwd = to;
-        pos = q;
-    }
-    // the counts and the events: the non-zero final p in ascending order
-    uint32_t cnt = 0;
-    off_walk<16, false>(ns, [&](uint32_t t) { return T[(size_t)t * 64]; }, [&](uint32_t t, double v) {
-        if (v != 0.0) {
-            if (cnt < max_peaks) {
-                index[cnt] = (int32_t)t;
-                value[cnt] = v;
-            }
-            ++cnt;
-        }
-    });
-    count[0] = cnt;
+    constexpr bool PLANAR = false;
+    const int32_t* row = nullptr;  // (the planar form's arguments, as in peak_block)
+    const bool vec = false;
+#include "k_peak_offline_block_body.hpp"
 }
 
 // One lane per detector: lane q = (block q / nch, channel q % nch) fresh, or channel q through every block (stateful).
@@ -648,6 +537,45 @@ __global__ __launch_bounds__(64) void k_peak_offline(PeakOffArgs a, PeakOffCoef 
                                     o.index, o.value, a.max_peaks, o.sig, o.thr, a.nch);
     }
     if (a.state) D.save(a.state, a.nch, ch);
+}
+
+// peak_offline_block on a row of the planar int32 matrix (arguments as peak_block_planar's; the workspace is the native one).
+template <bool TR>
+__device__ void peak_offline_block_planar(PeakDet<kPeakOfflineFw, true>& D, const PeakOffCoef& k, const int32_t* row, uint32_t ns, bool vec, double* V,
+                                          double* F, double* T, int32_t* E, uint32_t* count, int32_t* index, double* value, uint64_t max_peaks,
+                                          double* sig, double* thr) {
+    constexpr int BPS = 4;
+    constexpr bool PLANAR = true;
+    const uint8_t* p = nullptr;  // (the native form's arguments, as in peak_block_planar)
+    constexpr uint32_t stride = 0, nch = 1;
+    constexpr bool aligned = true;
+#include "k_peak_offline_block_body.hpp"
+}
+
+// One lane per detector, as k_peak_planar; the slabs as k_peak_offline's.
+template <bool TR>
+__global__ __launch_bounds__(64) void k_peak_offline_planar(PeakOffArgs a, PeakOffCoef k) {
+    const uint32_t q = blockIdx.x * 64u + threadIdx.x;
+    if (q >= a.lanes) return;
+    const bool vec = peak_rows_vec(a);
+    const int32_t* m = reinterpret_cast<const int32_t*>(a.src);
+    double* V = reinterpret_cast<double*>(a.work + (size_t)blockIdx.x * kPeakOffSlabBytesPerSample * a.ns) + threadIdx.x;
+    double* F = V + (size_t)64 * a.ns;
+    double* T = F + (size_t)64 * a.ns;
+    int32_t* E = reinterpret_cast<int32_t*>(T - threadIdx.x + (size_t)64 * a.ns) + threadIdx.x;
+    PeakDet<kPeakOfflineFw, true> D;
+    uint64_t r0 = q, r1 = (uint64_t)q + 1;
+    if (a.state) {
+        r1 = (uint64_t)a.nblocks * a.nch;
+        D.load(a.state, a.nch, q);
+    } else {
+        D.clear();
+    }
+    for (uint64_t r = r0; r < r1; r += a.nch) {
+        const PeakOut o = peak_out_planar<TR>(a, r);
+        peak_offline_block_planar<TR>(D, k, m + r * a.ns, a.ns, vec, V, F, T, E, o.count, o.index, o.value, a.max_peaks, o.sig, o.thr);
+    }
+    if (a.state) D.save(a.state, a.nch, q);
 }
 
 }  // namespace rspt
