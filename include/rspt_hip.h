@@ -136,6 +136,25 @@ unsigned rspt_hip_current_nb(rspt_hip_packer* p);
 /* Set it (a decoder fed streams from another instance needs this). */
 int rspt_hip_set_nb(rspt_hip_packer* p, unsigned nb);
 
+/* The quantiser of the two lossy packers: the constants a user of the reference edits and rebuilds with -- `quality`
+ * (signal_packer_dct.cpp:39 = 128, signal_packer_hadamard.cpp:37 = 1) and nr_bytes_to_compress_ (2 and 3), the number of
+ * low bytes of every stored value that reach the stream.  RSPT_HIP_KIND_DCT and RSPT_HIP_KIND_HADAMARD only; a fresh handle
+ * has the reference's constants, and streams and decoded samples equal those of the reference rebuilt with the same two.
+ *   hadamard  stores (int)((double)WHT(x - mean)[i] / ((double)n / quality)) and decodes (int)((double)WHT(y)[i] / quality)
+ *             + mean (fwht.c:30-40): a LARGER quality is FINER, quality = n stores the raw transform.
+ *   dct       scales the forward sum by Cs[i] * sqrt(2/n) / quality and the inverse by sqrt(2/n) * quality
+ *             (signal_packer_dct.cpp:84, 97): a LARGER quality is COARSER.
+ * Neither number is in the stream: like nb of the xdelta packer they are state that compressor and decompressor must share
+ * (rspt_hip_set_nb stays RSPT_HIP_ERR_ARG for these kinds; container index entries carry nb).  The lossy packers never verify or
+ * escalate: a value that does not fit nb bytes loses its high bytes, as in the reference.
+ * RSPT_HIP_ERR_ARG, and the handle unchanged: another kind, nb outside 1..4, a quality that is not finite and > 0 or that leaves
+ * n / quality (hadamard) or one of the three dct scales not finite or zero, an open feed.  Ordered like rspt_hip_set_nb: it
+ * synchronises the device, and holds for every call on the handle from then on.  rspt_hip_max_compressed_size follows nb
+ * (take buffer sizes and strides from it after the call; a change of nb releases the staging of the _many pipelines, which
+ * the next of those calls makes again). */
+int rspt_hip_set_quantizer(rspt_hip_packer* p, double quality, unsigned nb);
+int rspt_hip_get_quantizer(const rspt_hip_packer* p, double* quality, unsigned* nb);
+
 /* Decompress normally trusts the stream like the reference does (hzr_decode.c:343 skips the block CRCs).  With
  * verify on, every Huffman / PlainCopy block's CRC-32C is recomputed on the device and compared with its header
  * (what hzr_verify does, hzr_decode.c:569-624); a mismatch makes the call return RSPT_HIP_ERR_CORRUPT (batch

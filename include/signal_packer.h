@@ -52,4 +52,10 @@ public:
  * host thread and one thread per GPU is how a C++ caller shards independent blocks over the devices of a node. */
 extern "C" int rspt_cxx_set_device(int device);
 
+/* The quantiser of an instance made by new_dct / new_hadamard (additive; in the reference these are the constants `quality`
+ * and nr_bytes_to_compress_ of the two classes, changed by editing the source): rspt_hip_set_quantizer of include/rspt_hip.h
+ * on the instance's handle, with its meaning, its refusals and its status codes (0 = done).  Compressor and decompressor
+ * must be given the same two numbers: neither is in the stream. */
+extern "C" int rspt_cxx_set_quantizer(i_signal_packer* instance, double quality, unsigned nb);
+
 #endif /* RSPT_AMD_SIGNAL_PACKER_H_ */

@@ -39,6 +39,8 @@ C_ABI = {
     "rspt_hip_hzr_max_compressed_size": (_z, [_z]),
     "rspt_hip_current_nb": (_u, [_p]),
     "rspt_hip_set_nb": (_i, [_p, _u]),
+    "rspt_hip_set_quantizer": (_i, [_p, _d, _u]),
+    "rspt_hip_get_quantizer": (_i, [_p, _dp, _p]),
     "rspt_hip_set_verify": (_i, [_p, _i]),
     "rspt_hip_set_byte_order": (_i, [_p, _i]),
     "rspt_hip_host_alloc": (_p, [_z]),
@@ -118,6 +120,7 @@ CXX_SHIM = {
     "rspt_cxx_compress": (None, [_p, _p, _p, _z, _szp]),
     "rspt_cxx_decompress": (_i, [_p, _p, _szp, _p]),
     "rspt_cxx_set_device": (_i, [_i]),
+    "rspt_cxx_set_quantizer": (_i, [_p, _d, _u]),
 }
 C_ABI_SYMBOLS = list(C_ABI)  # every symbol include/rspt_hip.h declares (tests check the library exports them all)
 _lib = None
@@ -340,6 +343,21 @@ class SignalPacker:
 
     def set_nb(self, nb):
         self._check("rspt_hip_set_nb", self._L.rspt_hip_set_nb(self._h, nb))
+
+    def quantizer(self):
+        """(quality, nb) of a dct / hadamard handle (rspt_hip_get_quantizer)"""
+        q, nb = C.c_double(), C.c_uint()
+        self._call("rspt_hip_get_quantizer", C.byref(q), C.cast(C.byref(nb), C.c_void_p))
+        return q.value, nb.value
+
+    def set_quantizer(self, quality=None, nb=None):
+        """The lossy packers' trade-off between size and distortion (rspt_hip.h: rspt_hip_set_quantizer): the reference's
+        `quality` constant -- dct: larger is COARSER (128 in the reference); hadamard: larger is FINER (1 in the reference) --
+        and nb, the low bytes of every stored value that reach the stream (dct 2, hadamard 3).  None keeps the current value.
+        Neither is in the stream: the decoding handle needs the same setting.  Synchronises the device."""
+        q0, nb0 = self.quantizer()
+        self._call("rspt_hip_set_quantizer", float(q0 if quality is None else quality), int(nb0 if nb is None else nb))
+        self.max_compressed_size = self._L.rspt_hip_max_compressed_size(self._h)  # (follows nb)
 
     def set_byte_order(self, big_endian=True):
         """samples arrive (compress) and leave (decompress) with their bytes reversed (utils.cpp reverse_byte_order branches)"""
@@ -976,8 +994,19 @@ def new_hzr(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, de
     return SignalPacker(KIND_HZR, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, 4, device)
 
 
-def new_dct(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, device=0):
-    return SignalPacker(KIND_DCT, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, 2, device)
+def _with_quantizer(pk, quality, nb):
+    if quality is not None or nb is not None:
+        try:
+            pk.set_quantizer(quality, nb)
+        except Exception:
+            pk.close()
+            raise
+    return pk
+
+
+def new_dct(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, device=0, quality=None, nb=None):
+    """quality, nb: SignalPacker.set_quantizer (None: the reference's 128 and 2)"""
+    return _with_quantizer(SignalPacker(KIND_DCT, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, 2, device), quality, nb)
 
 
 def new_bytes(nbytes, device=0):
@@ -990,8 +1019,9 @@ def hzr_max_compressed_size(n):
     return lib().rspt_hip_hzr_max_compressed_size(n)
 
 
-def new_hadamard(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, device=0):
-    return SignalPacker(KIND_HADAMARD, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, 3, device)
+def new_hadamard(bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, device=0, quality=None, nb=None):
+    """quality, nb: SignalPacker.set_quantizer (None: the reference's 1 and 3)"""
+    return _with_quantizer(SignalPacker(KIND_HADAMARD, bytes_per_channel, nr_of_channels, nr_of_samples_in_each_channel, 3, device), quality, nb)
 
 
 class CxxSignalPacker:
@@ -1010,6 +1040,12 @@ class CxxSignalPacker:
         if getattr(self, "_p", None):
             self._L.rspt_cxx_delete(self.kind, self._p)
             self._p = None
+
+    def set_quantizer(self, quality, nb):
+        """rspt_cxx_set_quantizer (include/signal_packer.h) on a dct / hadamard instance; raises RsptHipError where it is refused"""
+        rc = self._L.rspt_cxx_set_quantizer(self._p, float(quality), int(nb))
+        if rc != 0:
+            raise RsptHipError("rspt_cxx_set_quantizer", rc)
 
     def compress(self, src):
         a = _as_u8(src)

@@ -214,6 +214,12 @@ struct rspt_hip_packer {
     // dct (signal_packer_dct.cpp:60-74)
     double dct_scale0 = 0, dct_scale1 = 0, idct_scale = 0;
     float dct_cs0 = 0;
+    // the quantiser of the lossy packers (rspt_hip_set_quantizer): the reference's `quality` constant (signal_packer_dct.cpp:39,
+    // signal_packer_hadamard.cpp:37); their plane count, nr_bytes_to_compress_, is nb_host / nb_state.  hadamard other than
+    // quality 1 takes the kernels with the fp64 division (transforms.hip: QUANT) by n / quality forward, by quality inverse
+    double quality = 0;
+    bool had_quant = false;
+    double had_div_fwd = 0, had_div_inv = 0;
     // dct beyond the dense table: fp64 FFT path (transforms.hip: k_dctfft_*)
     bool dct_fft = false;
     uint32_t fft_l1 = 0, fft_l2 = 0;   // n = 2^(l1+l2)

@@ -298,11 +298,51 @@ static void launch_fwht_big(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_seg), hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4);
     hipLaunchKernelGGL(k_fwht_seg, dim3(segs, g.nch, B), dim3(1024), 32768 * 4, st, p->ws.planar, g);
     const uint32_t m1 = segs > 64u ? 64u : segs, m2 = segs / m1;
-    hipLaunchKernelGGL((k_fwht_cross<FORWARD>), dim3(g.ns / m1 / 256u, g.nch, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m1, 32768u,
-                       m2 == 1u ? 1u : 0u);
-    if (m2 > 1u)
-        hipLaunchKernelGGL((k_fwht_cross<FORWARD>), dim3(g.ns / m2 / 256u, g.nch, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m2,
-                           32768u * m1, 1u);
+    // the last cross pass ends the transform: the truncating /n or + mean, or the general quantiser (k_fwht_cross_q)
+    auto cross = [&](uint32_t m, uint32_t stride, uint32_t last) {
+        const dim3 grid(g.ns / m / 256u, g.nch, B);
+        if (last && p->had_quant)
+            hipLaunchKernelGGL((k_fwht_cross_q<FORWARD>), grid, dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m, stride, last,
+                               FORWARD ? p->had_div_fwd : p->had_div_inv);
+        else
+            hipLaunchKernelGGL((k_fwht_cross<FORWARD>), grid, dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m, stride, last);
+    };
+    cross(m1, 32768u, m2 == 1u ? 1u : 0u);
+    if (m2 > 1u) cross(m2, 32768u * m1, 1u);
+}
+
+// The quantiser of a lossy handle from the reference's `quality` constant, in the reference's evaluation order: the three dct
+// scales (signal_packer_dct.cpp:84, 97: `Cs[i] * ratio1 / quality` with Cs a float, `ratio1 * quality`) or the two hadamard
+// divisors (fwht.c:33, 39: `n / ratio` with n an int, `ratio`).  Shared by rspt_hip_packer_create and rspt_hip_set_quantizer.
+// false, and the handle as it was: a quality the arithmetic cannot take -- not finite, not > 0, or one that leaves a scale or
+// a divisor that is not finite and non-zero.  commit = false only asks whether q can be taken.
+static bool set_quality(rspt_hip_packer* p, double q, bool commit = true) {
+    auto usable = [](double v) { return std::isfinite(v) && v != 0.0; };
+    if (!std::isfinite(q) || !(q > 0.0)) return false;
+    if (p->g.kind == RSPT_HIP_KIND_DCT) {
+        const double ratio1 = sqrt(2.0 / (double)(int)p->g.ns);
+        const float cs0 = (float)(1 / sqrt(2));
+        const double s0 = cs0 * ratio1 / q;   // Cs[0]*ratio1/quality (dct.cpp:84)
+        const double s1 = 1.0f * ratio1 / q;  // Cs[i>0] = 1
+        const double si = ratio1 * q;         // dct.cpp:97
+        if (!usable(s0) || !usable(s1) || !usable(si)) return false;
+        if (!commit) return true;
+        p->dct_cs0 = cs0;
+        p->dct_scale0 = s0;
+        p->dct_scale1 = s1;
+        p->idct_scale = si;
+    } else if (p->g.kind == RSPT_HIP_KIND_HADAMARD) {
+        const double fdiv = (double)(int)p->g.ns / q;  // fwht_normalize: src[i] /= (n / ratio)
+        if (!usable(fdiv)) return false;
+        if (!commit) return true;
+        p->had_div_fwd = fdiv;
+        p->had_div_inv = q;     // fwht_normalize2: src[i] /= ratio
+        p->had_quant = q != 1.0;  // quality 1: the all-integer kernels (truncating /n, and no division on the way back)
+    } else {
+        return false;
+    }
+    p->quality = q;
+    return true;
 }
 
 template <int BPS>
@@ -489,14 +529,9 @@ int rspt_hip_packer_create(rspt_hip_packer** out, int kind_and_flags, size_t bps
             return RSPT_HIP_ERR_LAUNCH;
     }
     for (int i = 0; i <= ST_COUNT; ++i) hipEventCreate(p->ev[i].out());
-    if (kind == RSPT_HIP_KIND_DCT) {
-        const double ratio1 = sqrt(2.0 / (double)(int)ns);
-        const float cs0 = (float)(1 / sqrt(2));
-        p->dct_cs0 = cs0;
-        p->dct_scale0 = cs0 * ratio1 / 128.0;   // Cs[0]*ratio1/quality (dct.cpp:84)
-        p->dct_scale1 = 1.0f * ratio1 / 128.0;  // Cs[i>0] = 1
-        p->idct_scale = ratio1 * 128.0;          // dct.cpp:97
-    }
+    // the reference's constants (signal_packer_dct.cpp:39, signal_packer_hadamard.cpp:37)
+    if ((kind == RSPT_HIP_KIND_DCT && !set_quality(p.get(), 128.0)) || (kind == RSPT_HIP_KIND_HADAMARD && !set_quality(p.get(), 1.0)))
+        return RSPT_HIP_ERR_ARG;
     if (kind == RSPT_HIP_KIND_DCT && p->dct_fft) {
         const size_t n = ns;
         std::vector<double2> tw(n), post(n);
@@ -568,7 +603,9 @@ size_t rspt_hip_block_bytes(const rspt_hip_packer* p) { return p ? (size_t)p->g.
 
 size_t rspt_hip_max_compressed_size(const rspt_hip_packer* p) {
     if (!p) return 0;
-    const unsigned nbmax = p->g.kind == RSPT_HIP_KIND_XDELTA_HZR ? 4u : p->nb_ctor;
+    // (a lossy handle never escalates: the planes of its current setting, rspt_hip_set_quantizer)
+    const bool lossy = p->g.kind == RSPT_HIP_KIND_DCT || p->g.kind == RSPT_HIP_KIND_HADAMARD;
+    const unsigned nbmax = p->g.kind == RSPT_HIP_KIND_XDELTA_HZR ? 4u : lossy ? p->nb_host : p->nb_ctor;
     const size_t hzr_max = 4 + (size_t)p->g.N + 7ull * p->g.nblk;  // hzr_encode.c:489-497
     if (p->g.kind == RSPT_HIP_KIND_BYTES) return hzr_max;  // the bare stream
     return 1 + p->g.hdr_len + (size_t)nbmax * (4 + hzr_max);
@@ -697,20 +734,34 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
     }
     const uint32_t np = d_planar ? launch_front_planar(p, d_planar, nblocks, st)
                                  : by_bps(g.bps, [&](auto bps) { return launch_front<decltype(bps)::value>(p, src, nblocks, st); });
+    const uint32_t lossy_nb = p->nb_host;  // nr_bytes_to_compress_ of the lossy packers (rspt_hip_set_quantizer): they never escalate
     if (g.kind == RSPT_HIP_KIND_HADAMARD) {
-        // per channel: mean removal, WHT, truncating /n (signal_packer_hadamard.cpp:57-72)
+        // per channel: mean removal, WHT, truncating /n (signal_packer_hadamard.cpp:57-72); with a quality other than 1 the
+        // kernels that divide by n / quality instead (transforms.hip: QUANT)
         const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
         if (g.ns > 65536u) {  // two passes over the planar row (any 2^k the reference's own transform takes, fwht.c:4-28)
             hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32);
             launch_fwht_big<true>(p, B, st);
-            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, 3u, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
+            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, lossy_nb, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
         } else if (g.ns == 65536u) {  // the whole row in registers: read once, and the byte planes written straight from them
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-            hipLaunchKernelGGL((k_fwht64k<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, p->nzflag, 3u);
+            if (p->had_quant) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_q<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht64k_q<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, p->nzflag,
+                                   lossy_nb, p->had_div_fwd);
+            } else {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht64k<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, p->nzflag,
+                                   lossy_nb);
+            }
         } else {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-            hipLaunchKernelGGL((k_fwht<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
-            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, 3u, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
+            if (p->had_quant) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_q<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht_q<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->had_div_fwd);
+            } else {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
+            }
+            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, lossy_nb, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
         }
     } else if (g.kind == RSPT_HIP_KIND_DCT) {
         if (p->dct_fft) {
@@ -723,7 +774,7 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
             hipLaunchKernelGGL((k_dct<true>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means,
                                p->cos_tab, p->dct_scale0, p->dct_scale1, p->dct_cs0, p->ws.planar2);
         }
-        hipLaunchKernelGGL((k_planar_planes<true>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar2, g, 2u, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_planar_planes<true>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar2, g, lossy_nb, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
     }
     HIPCHK(p, hipGetLastError());
 
@@ -890,6 +941,32 @@ int rspt_hip_set_nb(rspt_hip_packer* p, unsigned nb) {
     uint32_t v = nb;
     HIPCHK(p, hipMemcpy(p->nb_state, &v, sizeof(v), hipMemcpyHostToDevice));
     p->nb_host = nb;
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_set_quantizer(rspt_hip_packer* p, double quality, unsigned nb) {
+    if (!p || nb < 1 || nb > 4) return RSPT_HIP_ERR_ARG;
+    if (p->g.kind != RSPT_HIP_KIND_DCT && p->g.kind != RSPT_HIP_KIND_HADAMARD) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;  // (groups in flight were launched with the setting they were pushed under)
+    HIPCHK(p, hipSetDevice(p->device));
+    HIPCHK(p, hipDeviceSynchronize());  // ordered like rspt_hip_set_nb: behind everything launched under the old setting
+    if (!set_quality(p, quality, false)) return RSPT_HIP_ERR_ARG;
+    uint32_t v = nb;
+    HIPCHK(p, hipMemcpy(p->nb_state, &v, sizeof(v), hipMemcpyHostToDevice));  // (a failure leaves the handle as it was)
+    set_quality(p, quality);
+    // the staging of rspt_hip_compress_many / rspt_hip_decompress_many holds one stream per rspt_hip_max_compressed_size, which
+    // follows nb: it is made again, for the new size, by the next of those calls (nothing of it is in flight behind the
+    // synchronisation above)
+    if (nb != p->nb_host) p->many = ManyStaging();
+    p->nb_host = nb;
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_get_quantizer(const rspt_hip_packer* p, double* quality, unsigned* nb) {
+    if (!p || !quality || !nb) return RSPT_HIP_ERR_ARG;
+    if (p->g.kind != RSPT_HIP_KIND_DCT && p->g.kind != RSPT_HIP_KIND_HADAMARD) return RSPT_HIP_ERR_ARG;
+    *quality = p->quality;
+    *nb = p->nb_host;
     return RSPT_HIP_OK;
 }
 
@@ -1110,10 +1187,17 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
             const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
             if (g.ns > 65536u) {
                 launch_fwht_big<false>(p, B, st);
+            } else if (g.ns == 65536u && p->had_quant) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_q<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht64k_q<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
+                                   (uint32_t*)nullptr, 0u, p->had_div_inv);
             } else if (g.ns == 65536u) {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
                 hipLaunchKernelGGL((k_fwht64k<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
                                    (uint32_t*)nullptr, 0u);
+            } else if (p->had_quant) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_q<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht_q<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->had_div_inv);
             } else {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
                 hipLaunchKernelGGL((k_fwht<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);

@@ -71,6 +71,13 @@ public:
 
     rspt_hip_packer* handle() const { return h_; }
 
+    // (a plane count that was set is not an escalation: nothing is printed for it)
+    int set_quantizer(double quality, unsigned nb) {
+        const int rc = rspt_hip_set_quantizer(h_, quality, nb);
+        if (rc == RSPT_HIP_OK) nb_seen_ = nb;
+        return rc;
+    }
+
 private:
     rspt_hip_packer* h_ = nullptr;
     unsigned nb_seen_ = 0;
@@ -106,6 +113,12 @@ int rspt_cxx_set_device(int device) {
     const int prev = t_device;
     t_device = device;
     return prev;
+}
+// the quantiser of a new_dct / new_hadamard instance (every instance here is a signal_packer_hip; any other kind, or an
+// instance whose handle could not be made, is RSPT_HIP_ERR_ARG)
+int rspt_cxx_set_quantizer(i_signal_packer* instance, double quality, unsigned nb) {
+    if (!instance) return RSPT_HIP_ERR_ARG;
+    return static_cast<signal_packer_hip*>(instance)->set_quantizer(quality, nb);
 }
 void* rspt_cxx_new(int kind, size_t bps, size_t nch, size_t ns, size_t nb) {
     switch (kind) {

@@ -37,6 +37,9 @@ __device__ __forceinline__ int32_t load_mean_hdr(const uint8_t* means, const Geo
     return (int32_t)(u << 8) >> 8;  // sign-extend 24 bits (hadamard.cpp:98-99)
 }
 
+// `int /= double` of fwht_normalize / fwht_normalize2 (fwht.c:30-40): the int converts to double, one IEEE division, C's truncation
+__device__ __forceinline__ int32_t fwht_quant(int32_t y, double div) { return trunc_i32_c(__ddiv_rn((double)y, div)); }
+
 // block-wide int64 sum of row[0..n) (1024 threads)
 __device__ __forceinline__ long long block_sum_row(const int32_t* row, uint32_t n, long long* s_red) {
     long long s = 0;
@@ -57,94 +60,22 @@ __device__ __forceinline__ long long block_sum_row(const int32_t* row, uint32_t 
 //   FORWARD  true : y = WHT(x - mean) / n, mean header written      (compress)
 //            false: x = WHT(y) + mean (header read), no normalisation
 //                   (decompress: fwht_normalize2 with ratio 1 is a no-op, fwht.c:36-40)
+//   QUANT    the general quantiser (rspt_hip_set_quantizer; `quality` of signal_packer_hadamard.cpp:37 other than 1):
+//            forward y = (int)((double)WHT(x - mean) / div), div = n / quality  (fwht_normalize, fwht.c:30-34)
+//            inverse x = (int)((double)WHT(y) / div) + mean, div = quality      (fwht_normalize2, fwht.c:36-40)
+//            a correctly rounded fp64 division and C's truncation as the reference's build computes it (trunc_i32_c).
+//            false: quality = 1, the all-integer form above, and `div` is not looked at.
 template <bool FORWARD>
 __global__ __launch_bounds__(1024) void k_fwht(int32_t* __restrict__ planar, Geom g, uint8_t* __restrict__ means) {
-    extern __shared__ __attribute__((aligned(16))) int32_t sh[];
-    __shared__ long long s_red[16];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t c = blockIdx.x, b = blockIdx.y;
-    const uint32_t n = g.ns;
-    int32_t* row = planar + (size_t)b * g.N + (size_t)c * n;
-    const uint32_t k = 31u - (uint32_t)__builtin_clz(n);
+    constexpr bool QUANT = false;
+    constexpr double div = 0.0;
+#include "k_fwht_body.hpp"
+}
 
-    int32_t mean;
-    if (FORWARD) {
-        mean = mean_from_sum(block_sum_row(row, n, s_red), n);
-        if (tid == 0) store_mean_hdr(means, g, b, c, mean);
-    } else {
-        mean = load_mean_hdr(means, g, b, c);
-    }
-
-    const uint32_t hn = n > 32768u ? 32768u : n;
-    const uint32_t halves = n / hn;  // 1 or 2
-    int32_t keep[32];                // results of half 0 while half 1's inputs are still being read
-    for (uint32_t h = 0; h < halves; ++h) {
-        for (uint32_t i = tid; i < hn; i += 1024) {
-            uint32_t a = (uint32_t)row[i];
-            if (halves == 2) {
-                const uint32_t bb = (uint32_t)row[i + hn];
-                a = h == 0 ? a + bb : a - bb;
-            }
-            sh[i] = (int32_t)a;
-        }
-        __syncthreads();
-        if (h == 1) {
-#pragma unroll
-            for (int jj = 0; jj < 32; ++jj) row[tid + 1024u * jj] = keep[jj];
-        }
-        // (lo,hi) -> (lo+hi, lo-hi) per stage (fwht.c:19-22); the stages commute exactly in wrap-around arithmetic, so
-        // three of them are taken at a time on eight values held in registers: a third of the LDS traffic and barriers
-        uint32_t w = hn >> 1;
-        while (w >= 4) {  // stages w, w/2, w/4 together: elements base + {0..7} * (w/4)
-            const uint32_t st = w >> 2;
-            for (uint32_t q = tid; q < (hn >> 3); q += 1024) {
-                const uint32_t base = ((q & ~(st - 1)) << 3) | (q & (st - 1));
-                uint32_t v[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = (uint32_t)sh[base + i * st];
-#pragma unroll
-                for (int d = 4; d >= 1; d >>= 1) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        if (!(i & d)) {
-                            const uint32_t x = v[i], y = v[i + d];
-                            v[i] = x + y;
-                            v[i + d] = x - y;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) sh[base + i * st] = (int32_t)v[i];
-            }
-            __syncthreads();
-            w >>= 3;
-        }
-        for (; w >= 1; w >>= 1) {  // the one or two stages left
-            for (uint32_t q = tid; q < (hn >> 1); q += 1024) {
-                const uint32_t lo = ((q & ~(w - 1)) << 1) | (q & (w - 1));
-                const uint32_t x = (uint32_t)sh[lo], y = (uint32_t)sh[lo + w];
-                sh[lo] = (int32_t)(x + y);
-                sh[lo + w] = (int32_t)(x - y);
-            }
-            __syncthreads();
-        }
-        auto finish = [&](uint32_t idx, int32_t y) -> int32_t {
-            if (FORWARD) {
-                // WHT(x - m) = WHT(x) - m*n*delta_0 (exact mod 2^32)
-                if (idx == 0) y = (int32_t)((uint32_t)y - (uint32_t)mean * n);
-                // fwht_normalize (fwht.c:30-34): int /= (n/1.0) = truncation toward zero
-                return (y + ((y >> 31) & (int32_t)(n - 1))) >> k;
-            }
-            return (int32_t)((uint32_t)y + (uint32_t)mean);
-        };
-        if (halves == 2 && h == 0) {
-#pragma unroll
-            for (int jj = 0; jj < 32; ++jj) keep[jj] = finish(tid + 1024u * jj, sh[tid + 1024u * jj]);
-        } else {
-            for (uint32_t i = tid; i < hn; i += 1024) row[h * hn + i] = finish(h * hn + i, sh[i]);
-        }
-        __syncthreads();
-    }
+template <bool FORWARD>
+__global__ __launch_bounds__(1024) void k_fwht_q(int32_t* __restrict__ planar, Geom g, uint8_t* __restrict__ means, double div) {
+    constexpr bool QUANT = true;
+#include "k_fwht_body.hpp"
 }
 
 // ---- rows longer than 65536 points (fwht.c:4-28 transforms any n = 2^k): two passes over the planar row ------------------------
@@ -190,9 +121,9 @@ __global__ __launch_bounds__(1024) void k_fwht_seg(int32_t* __restrict__ planar,
     for (uint32_t i = tid; i < hn / 4; i += 1024) reinterpret_cast<int4*>(seg)[i] = reinterpret_cast<const int4*>(sh)[i];
 }
 
-template <bool FORWARD, int M>
+template <bool FORWARD, bool QUANT, int M>
 __device__ __forceinline__ void fwht_cross_body(int32_t* __restrict__ row, uint32_t col, uint32_t stride, uint32_t group_span, bool last, uint32_t n,
-                                                int32_t mean) {
+                                                int32_t mean, double div) {
     // the M values of this column: row[base + i * stride], base = (col / stride) * group_span + col % stride
     const uint32_t base = (col / stride) * group_span + (col % stride);
     uint32_t v[M];
@@ -216,8 +147,12 @@ __device__ __forceinline__ void fwht_cross_body(int32_t* __restrict__ row, uint3
         if (last) {
             if (FORWARD) {
                 if (base + (size_t)i * stride == 0) y = (int32_t)((uint32_t)y - (uint32_t)mean * n);  // WHT(x - m) = WHT(x) - m*n*delta_0 (mod 2^32)
-                y = (y + ((y >> 31) & (int32_t)(n - 1))) >> k;                                          // truncation toward zero (fwht.c:30-34)
+                if (QUANT)
+                    y = fwht_quant(y, div);
+                else
+                    y = (y + ((y >> 31) & (int32_t)(n - 1))) >> k;                                      // truncation toward zero (fwht.c:30-34)
             } else {
+                if (QUANT) y = fwht_quant(y, div);
                 y = (int32_t)((uint32_t)y + (uint32_t)mean);
             }
         }
@@ -228,22 +163,20 @@ __device__ __forceinline__ void fwht_cross_body(int32_t* __restrict__ row, uint3
 // grid (n / m / 256, nch, blocks); m = values per column of this pass, `stride` = their distance in points
 // the mean: forward all 32 bits of it (mean_i32, k_row_means: the subtraction uses them all, hadamard.cpp:62-66), inverse the 24
 // bits the header kept (hadamard.cpp:98-99)
+// k_fwht_cross_q: the general quantiser in the last pass (k_fwht_q)
 template <bool FORWARD>
 __global__ __launch_bounds__(256) void k_fwht_cross(int32_t* __restrict__ planar, Geom g, const uint8_t* __restrict__ means,
                                                    const int32_t* __restrict__ mean_i32, uint32_t m, uint32_t stride, uint32_t last) {
-    const uint32_t c = blockIdx.y, b = blockIdx.z, n = g.ns;
-    int32_t* row = planar + (size_t)b * g.N + (size_t)c * n;
-    const uint32_t col = blockIdx.x * 256u + threadIdx.x;  // < n / m
-    const int32_t mean = !last ? 0 : FORWARD ? mean_i32[(size_t)b * g.nch + c] : load_mean_hdr(means, g, b, c);
-    const uint32_t span = stride * m;
-    switch (m) {
-        case 2: fwht_cross_body<FORWARD, 2>(row, col, stride, span, last != 0, n, mean); break;
-        case 4: fwht_cross_body<FORWARD, 4>(row, col, stride, span, last != 0, n, mean); break;
-        case 8: fwht_cross_body<FORWARD, 8>(row, col, stride, span, last != 0, n, mean); break;
-        case 16: fwht_cross_body<FORWARD, 16>(row, col, stride, span, last != 0, n, mean); break;
-        case 32: fwht_cross_body<FORWARD, 32>(row, col, stride, span, last != 0, n, mean); break;
-        default: fwht_cross_body<FORWARD, 64>(row, col, stride, span, last != 0, n, mean); break;
-    }
+    constexpr bool QUANT = false;
+    constexpr double div = 0.0;
+#include "k_fwht_cross_body.hpp"
+}
+
+template <bool FORWARD>
+__global__ __launch_bounds__(256) void k_fwht_cross_q(int32_t* __restrict__ planar, Geom g, const uint8_t* __restrict__ means,
+                                                     const int32_t* __restrict__ mean_i32, uint32_t m, uint32_t stride, uint32_t last, double div) {
+    constexpr bool QUANT = true;
+#include "k_fwht_cross_body.hpp"
 }
 
 // ---------------------------------------------------------------------------
@@ -285,148 +218,20 @@ __device__ __forceinline__ void fwht_regs(uint32_t (&v)[64]) {  // butterflies o
 
 // PLANES (compress): the normalised coefficients leave as byte planes + non-zero map straight away (what k_planar_planes
 // would do in another pass over HBM); a wave's 4096 outputs are exactly one 4 KiB segment of every plane.
+// k_fwht64k_q: the general quantiser (k_fwht_q)
 template <bool FORWARD, bool PLANES>
 __global__ __launch_bounds__(1024) void k_fwht64k(int32_t* __restrict__ planar, Geom g, uint8_t* __restrict__ means, uint8_t* __restrict__ planes,
                                                  uint32_t* __restrict__ nzflag, uint32_t nplanes) {
-    extern __shared__ __attribute__((aligned(16))) int32_t sh_i[];
-    uint32_t* sh = reinterpret_cast<uint32_t*>(sh_i);
-    __shared__ long long s_red[16];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t c = blockIdx.x, b = blockIdx.y;
-    constexpr uint32_t n = 65536u, k = 16u;
-    int32_t* row = planar + (size_t)b * g.N + (size_t)c * n;
+    constexpr bool QUANT = false;
+    constexpr double div = 0.0;
+#include "k_fwht64k_body.hpp"
+}
 
-    uint32_t v[64];  // layout 1: v[4 q + e] = row[4096 q + 4 tid + e]
-#pragma unroll
-    for (uint32_t q = 0; q < 16; ++q) {
-        const uint4 x = reinterpret_cast<const uint4*>(row)[q * 1024 + tid];
-        v[4 * q] = x.x;
-        v[4 * q + 1] = x.y;
-        v[4 * q + 2] = x.z;
-        v[4 * q + 3] = x.w;
-    }
-    int32_t mean;
-    if (FORWARD) {
-        long long sum = 0;
-#pragma unroll
-        for (int i = 0; i < 64; ++i) sum += (int32_t)v[i];
-        sum = wave_add_i64(sum);
-        if ((tid & 63u) == 0) s_red[tid >> 6] = sum;
-        __syncthreads();
-        long long t = 0;
-        for (uint32_t i = 0; i < 16; ++i) t += s_red[i];
-        mean = mean_from_sum(t, n);
-        if (tid == 0) store_mean_hdr(means, g, b, c, mean);
-    } else {
-        mean = load_mean_hdr(means, g, b, c);
-    }
-    fwht_regs<0, 6>(v);  // bits 0, 1, 12..15
-    // (pinned: left alone the scheduler sinks the last stage's differences -- needed in the second round only -- behind the first
-    //  round's LDS reads and keeps both of their inputs instead: 64 + 64 live registers and two dozen of them in scratch memory)
-#pragma unroll
-    for (int i = 32; i < 64; ++i) asm volatile("" : "+v"(v[i]));
-
-    // transpose 1: layout 1 -> layout 2
-    uint32_t w[64];
-    const uint32_t half = tid >> 9;  // bit 15 of the elements this thread holds in layouts 2 and 3
-    const uint32_t base2 = (((tid >> 6) & 7u) << 12) | (((tid >> 2) & 15u) << 8) | (tid & 3u);
-    const uint32_t swz2 = (base2 >> 8) & 7u;  // what fwht_swz flips in bits 2..4 of this thread's layout-2 addresses
-#pragma unroll
-    for (uint32_t h = 0; h < 2; ++h) {
-#pragma unroll
-        for (uint32_t qq = 0; qq < 8; ++qq) {
-            const uint32_t q = h * 8 + qq;
-            *reinterpret_cast<uint4*>(&sh[fwht_swz((qq << 12) | (tid << 2))]) = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-        }
-        __syncthreads();
-        if (half == h) {
-            // fwht_swz(base2 | r << 2) = base2 + ((r & 7 ^ c) << 2) + (r >> 3 << 5) with c = bits 8..10 of base2: eight addresses and
-            // immediate offsets (sixty-four computed addresses are sixty-four registers the three arrays do not leave)
-#pragma unroll
-            for (uint32_t n = 0; n < 8; ++n) {
-                const uint32_t* pn = sh + (base2 | ((n ^ swz2) << 2));
-#pragma unroll
-                for (uint32_t m = 0; m < 8; ++m) w[8 * m + n] = pn[m << 5];
-            }
-        }
-        __syncthreads();
-    }
-    fwht_regs<0, 6>(w);  // bits 2..7
-
-    // transpose 2: layout 2 -> layout 3 (each half: written and read by the same 512 threads).  Read back INTO w: with an
-    // array of its own the second round's stores still need w while the first round's loads are live -- 128 registers for the
-    // compiler, which cannot know that no thread takes part in both rounds, and 22 of them went to scratch memory (104
-    // scratch instructions per thread next to 64 loads and stores of data).
-    uint32_t(&u)[64] = w;
-    const uint32_t base3 = (((tid >> 6) & 7u) << 12) | ((tid & 63u) << 2);
-#pragma unroll
-    for (uint32_t h = 0; h < 2; ++h) {
-        if (half == h) {
-#pragma unroll
-            for (uint32_t n = 0; n < 8; ++n) {
-                uint32_t* pn = sh + (base2 | ((n ^ swz2) << 2));
-#pragma unroll
-                for (uint32_t m = 0; m < 8; ++m) pn[m << 5] = w[8 * m + n];
-            }
-        }
-        __syncthreads();
-        if (half == h) {
-#pragma unroll
-            for (uint32_t pp = 0; pp < 16; ++pp) {
-                const uint4 x = *reinterpret_cast<const uint4*>(&sh[fwht_swz(base3 | (pp << 8))]);
-                u[4 * pp] = x.x;
-                u[4 * pp + 1] = x.y;
-                u[4 * pp + 2] = x.z;
-                u[4 * pp + 3] = x.w;
-            }
-        }
-        __syncthreads();
-    }
-    fwht_regs<2, 6>(u);  // bits 8..11 (register-index bits 2..5; bits 0, 1 of the index are done)
-#pragma unroll
-    for (int i = 0; i < 64; ++i) asm volatile("" : "+v"(u[i]));  // (the output phase starts from 64 finished values, not in the middle of the butterflies)
-
-    const uint32_t i0 = ((tid >> 6) << 12) | ((tid & 63u) << 2);  // bits 15..12 and 7..2
-    uint32_t nzk[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (uint32_t pp = 0; pp < 16; ++pp) {
-        const uint32_t idx = i0 | (pp << 8);
-        uint32_t o[4];
-#pragma unroll
-        for (uint32_t e = 0; e < 4; ++e) {
-            int32_t y = (int32_t)u[4 * pp + e];
-            if (FORWARD) {
-                // WHT(x - m) = WHT(x) - m*n*delta_0 (exact mod 2^32); fwht_normalize (fwht.c:30-34): truncation toward zero
-                if (idx + e == 0) y = (int32_t)((uint32_t)y - (uint32_t)mean * n);
-                y = (y + ((y >> 31) & (int32_t)(n - 1))) >> k;
-            } else {
-                y = (int32_t)((uint32_t)y + (uint32_t)mean);
-            }
-            o[e] = (uint32_t)y;
-        }
-        if (!PLANES) {
-            *reinterpret_cast<uint4*>(row + idx) = make_uint4(o[0], o[1], o[2], o[3]);
-        } else {
-            // 4 x 4 byte transpose (preprocess.hip: transform_item): one dword per plane
-            const uint32_t lo01 = __builtin_amdgcn_perm(o[1], o[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(o[1], o[0], 0x07030602u);
-            const uint32_t lo23 = __builtin_amdgcn_perm(o[3], o[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(o[3], o[2], 0x07030602u);
-            const uint32_t pl[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),
-                                    __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};
-#pragma unroll
-            for (uint32_t kk = 0; kk < 4; ++kk) {
-                if (kk < nplanes) {
-                    *reinterpret_cast<uint32_t*>(planes + ((size_t)b * kMaxPlanes + kk) * g.plane_stride + (size_t)c * n + idx) = pl[kk];
-                    nzk[kk] |= pl[kk];
-                }
-            }
-            asm volatile("" ::: "memory");  // (one quad of outputs at a time: interleaved, their temporaries spill)
-        }
-    }
-    if (PLANES) {
-        const uint32_t flat = c * n + i0;  // this wave's outputs: [flat & ~4095, +4096)
-        for (uint32_t kk = 0; kk < nplanes; ++kk)
-            if (__ballot(nzk[kk] != 0) && (tid & 63u) == 0) atomicOr(&nzflag[hb_index(g, b, kk, flat >> 16)], 1u << ((flat >> 12) & 15u));
-    }
+template <bool FORWARD, bool PLANES>
+__global__ __launch_bounds__(1024) void k_fwht64k_q(int32_t* __restrict__ planar, Geom g, uint8_t* __restrict__ means, uint8_t* __restrict__ planes,
+                                                   uint32_t* __restrict__ nzflag, uint32_t nplanes, double div) {
+    constexpr bool QUANT = true;
+#include "k_fwht64k_body.hpp"
 }
 
 // n x n float matrix -> its transpose (the inverse DCT reads the cosine table the other way round), 32 x 32 tiles
@@ -911,6 +716,12 @@ template __global__ void k_fwht_cross<false>(int32_t*, Geom, const uint8_t*, con
 template __global__ void k_fwht<false>(int32_t*, Geom, uint8_t*);
 template __global__ void k_fwht64k<true, true>(int32_t*, Geom, uint8_t*, uint8_t*, uint32_t*, uint32_t);
 template __global__ void k_fwht64k<false, false>(int32_t*, Geom, uint8_t*, uint8_t*, uint32_t*, uint32_t);
+template __global__ void k_fwht_q<true>(int32_t*, Geom, uint8_t*, double);
+template __global__ void k_fwht_q<false>(int32_t*, Geom, uint8_t*, double);
+template __global__ void k_fwht_cross_q<true>(int32_t*, Geom, const uint8_t*, const int32_t*, uint32_t, uint32_t, uint32_t, double);
+template __global__ void k_fwht_cross_q<false>(int32_t*, Geom, const uint8_t*, const int32_t*, uint32_t, uint32_t, uint32_t, double);
+template __global__ void k_fwht64k_q<true, true>(int32_t*, Geom, uint8_t*, uint8_t*, uint32_t*, uint32_t, double);
+template __global__ void k_fwht64k_q<false, false>(int32_t*, Geom, uint8_t*, uint8_t*, uint32_t*, uint32_t, double);
 template __global__ void k_dct<true>(const int32_t*, Geom, uint8_t*, const float*, double, double, float, int32_t*);
 template __global__ void k_dct<false>(const int32_t*, Geom, uint8_t*, const float*, double, double, float, int32_t*);
 
