@@ -226,7 +226,11 @@ def hadamard_big_cases():
 
     return [dict(name="wave2x131072_hadamard", kind="hadamard", bps=4, nch=2, ns=131072, nb=3, data=wave(2, 131072, 3000.0, 71, 4)),
             dict(name="wave3x262144_i24_hadamard", kind="hadamard", bps=3, nch=3, ns=262144, nb=3, data=wave(3, 262144, 900.0, 72, 3)),
-            dict(name="wave1x4194304_i16_hadamard", kind="hadamard", bps=2, nch=1, ns=4194304, nb=3, data=wave(1, 4194304, 150.0, 73, 2))]
+            dict(name="wave1x4194304_i16_hadamard", kind="hadamard", bps=2, nch=1, ns=4194304, nb=3, data=wave(1, 4194304, 150.0, 73, 2)),
+            # the cross widths between those: 16 (2^19), 32 (2^20) and 64 as the only and last pass (2^21)
+            dict(name="wave2x524288_hadamard", kind="hadamard", bps=4, nch=2, ns=524288, nb=3, data=wave(2, 524288, 3000.0, 74, 4)),
+            dict(name="wave1x1048576_i24_hadamard", kind="hadamard", bps=3, nch=1, ns=1048576, nb=3, data=wave(1, 1048576, 1500.0, 75, 3)),
+            dict(name="wave1x2097152_hadamard", kind="hadamard", bps=4, nch=1, ns=2097152, nb=3, data=wave(1, 2097152, 750.0, 76, 4))]
 
 
 def dct_dense_big_cases():

@@ -76,7 +76,16 @@ def hadamard_cases():
 def cases_big_shapes():
     """name, bps, nch, ns of cases.hadamard_big_cases() without building their data"""
     return [dict(name="wave2x131072", bps=4, nch=2, ns=131072), dict(name="wave3x262144_i24", bps=3, nch=3, ns=262144),
-            dict(name="wave1x4194304_i16", bps=2, nch=1, ns=4194304)]
+            dict(name="wave1x4194304_i16", bps=2, nch=1, ns=4194304), dict(name="wave2x524288", bps=4, nch=2, ns=524288),
+            dict(name="wave1x1048576_i24", bps=3, nch=1, ns=1048576), dict(name="wave1x2097152", bps=4, nch=1, ns=2097152)]
+
+
+def hadamard_restated_cases():
+    """k_fwht_cross_q at the cross widths the cases above leave out: m = 16 (2^19), 32 (2^20) and 64 as the only and last pass
+    (2^21).  These are held to the restatement below, not to the record (all_cases() does not list them); the restatement's
+    transform is held to the reference at these row lengths through the oracle (tests/test_lossy_quantizer_record.py)."""
+    return [_case("%s_q3_nb3" % b["name"], "hadamard", b["bps"], b["nch"], b["ns"], 3.0, 3, src="big", nblocks=1, big=bi)
+            for bi, b in enumerate(cases_big_shapes()) if bi >= 3]
 
 
 def dct_cases():

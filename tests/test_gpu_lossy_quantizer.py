@@ -113,6 +113,31 @@ def test_planar_batch_is_the_rebuilt_reference(api, rec, name):
     pk.close()
 
 
+RESTATED = {c["name"]: c for c in lq.hadamard_restated_cases()}
+
+
+@pytest.mark.parametrize("name", list(RESTATED))
+def test_long_hadamard_cross_widths_are_the_restatement(api, orc, name):
+    """k_fwht_cross_q with m = 16, 32 and 64 as the last pass (2^19, 2^20, 2^21 points): the stored values, the header and the
+    decoded block against the numpy restatement of the quantiser, two blocks to a call"""
+    c = RESTATED[name]
+    data = lq.block_data(c, 0)
+    want, m32 = lq.restated_stored(c, data)
+    assert (want != 0).mean() > 0.001  # (the quantised transform is not all zero)
+    pk = _new(api, c)
+    got, d_dst, _ = _compress_batch(pk, [data, data])
+    assert got[0] == got[1]
+    vals, means, used = lq.stream_values(orc, got[0], "hadamard", c["nch"], c["ns"], c["nb"])
+    assert used == len(got[0])
+    assert (means == ((m32.astype(np.int64) << 8).astype(np.int32) >> 8)).all()
+    bad = np.nonzero(vals.reshape(-1) != want)[0]
+    assert bad.size == 0, (name, bad.size, bad[:8], vals.reshape(-1)[bad[:8]], want[bad[:8]])
+    dec, used = _decompress_batch(pk, d_dst, 2)
+    back = lq.restated_decode(c, vals, means).tobytes()
+    assert dec[0] == back and dec[1] == back and [int(u) for u in used] == [len(got[0])] * 2
+    pk.close()
+
+
 HOST = ["had_3x8_q7p3_nb1", "had_2x64_full_scale_q0p1_nb4", "had_2x32768_q3_nb3", "had_2x65536_q7p3_nb4", "wave3x262144_i24_q7p3_nb3",
         "dct_3x100_q1000_nb1", "dct_3x257_full_scale_q0p37_nb4"]
 

@@ -75,6 +75,28 @@ def test_the_restatement_is_the_reference_on_the_small_cases(record, orc):
     assert n >= 50  # (every case of at most 256 bytes, and the four of lossy_quantizer_cases.FULL_TOO)
 
 
+@pytest.mark.parametrize("name", [c["name"] for c in lq.hadamard_restated_cases()])
+def test_the_restatement_is_the_oracle_on_the_long_rows(orc, name):
+    """The cases that are held to the restatement alone (2^19, 2^20, 2^21 points): at the reference's own constants the
+    restatement stores what the oracle's packer stores, whose stream tests/test_oracle_golden.py holds to the real reference at
+    these very inputs -- so the numpy transform and the means are right at these row lengths."""
+    c = {c["name"]: c for c in lq.hadamard_restated_cases()}[name]
+    q0, nb0 = lq.DEFAULTS["hadamard"]
+    data = lq.block_data(c, 0)
+    pk = orc.packer("hadamard", c["bps"], c["nch"], c["ns"], nb0)
+    stream = pk.compress(data)
+    got, means, used = lq.stream_values(orc, stream, "hadamard", c["nch"], c["ns"], nb0)
+    assert used == len(stream)
+    want, m32 = lq.restated_stored(dict(c, q=q0, nb=nb0), data)
+    assert (got.reshape(-1) == want).all() and (means == ((m32.astype(np.int64) << 8).astype(np.int32) >> 8)).all()
+    dec, used, rc = pk.decompress(stream)
+    assert rc == 0 and lq.restated_decode(dict(c, q=q0, nb=nb0), got, means).tobytes() == dec
+    pk.close()
+    # and at the case's own setting the restatement keeps something: the quantised transform is not all zero
+    stored, _ = lq.restated_stored(c, data)
+    assert (stored != 0).mean() > 0.001
+
+
 def test_an_out_of_range_quotient_is_in_the_record(record, orc):
     """the case that exists for the x86 truncation value really produces it: at quality 2n the quotient is twice the wrapped
     transform, and what leaves int32 is stored as 0x80000000 (nb = 4 keeps it whole)"""
