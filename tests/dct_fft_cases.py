@@ -256,3 +256,26 @@ def stream_coeffs(orc, stream, c):
     assert rc == 0 and used.value == len(stream)
     assert header_bytes(me) == header
     return co, header
+
+
+def coeff_mismatch(orc, a, b, bps, nch, ns):
+    """two dct streams by their coefficients, decoded by the oracle: (the share that differs, the largest difference)"""
+    def coeffs(stream):
+        s = np.frombuffer(stream + b"\0" * 16, dtype=np.uint8).copy()
+        co = np.zeros((nch, ns), dtype=np.int32)
+        me = np.zeros(nch, dtype=np.int32)
+        used = C.c_size_t(0)
+        pk = orc.packer("dct", bps, nch, ns)
+        f = orc.lib.orc_packer_decompress_coeffs
+        f.restype = C.c_int
+        rc = f(C.c_void_p(pk._h), s.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(used), co.ctypes.data_as(C.POINTER(C.c_int32)),
+               me.ctypes.data_as(C.POINTER(C.c_int32)))
+        pk.close()
+        assert rc == 0
+        return co, me
+
+    ca, ma = coeffs(a)
+    cb, mb = coeffs(b)
+    assert (ma == mb).all()
+    d = np.abs(ca.astype(np.int64) - cb.astype(np.int64))
+    return float((d != 0).mean()), int(d.max())

@@ -1,4 +1,5 @@
-"""The device assembly of rspt_hip.hip for gfx950 (hipcc -S), for the tests and tools that read the kernels' ISA.
+"""The device assembly of rspt_hip.hip for gfx950 (hipcc -S), for the tests and tools that read the kernels' ISA.  The tests take
+it through tests/devframe.py: its `asm` fixture, and the checks that several modules make of it (rounds_separately, uses_no_scratch).
 
 Compiled once per process (the unity build takes over a minute on one core) and removed when the process ends."""
 import atexit

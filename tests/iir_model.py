@@ -58,3 +58,18 @@ class IirModel:
         """the outputs of one call per element of cols, in order"""
         step = self.filter_opt if opt else self.filter
         return [step(v) for v in cols]
+
+
+def state_rings(state, nch, S=1):
+    """a device state's bytes by the layout rspt_hip.h documents: per channel, and per channel x section for the cascade,
+    double x[5], y[5]; uint64 started -> x, y as [nch][S][5] float64 and started as [nch][S] uint64"""
+    raw = state.cpu().numpy()
+    assert raw.size == 88 * nch * S
+    words = raw.view(np.uint64).reshape(nch, S, 11)
+    return words[:, :, 0:5].view(np.float64), words[:, :, 5:10].view(np.float64), words[:, :, 10]
+
+
+def same_doubles(a, b):
+    """bit for bit, but any NaN matches any NaN (payload and sign differ between x86 and the GPU)"""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and bool(np.all((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))))

@@ -22,6 +22,8 @@ within the few hundred rows of a run only the first reaches +-inf and NaN (1.5 *
 past 2^31.
 """
 import functools
+import json
+import os
 
 import numpy as np
 
@@ -379,3 +381,21 @@ def stream_expected(c):
     y, models = stream_doubles(c)
     rings = [(np.array(f.x, dtype=np.float64), np.array(f.y, dtype=np.float64)) for f in models]
     return i32_to_native(trunc_i32(y), c["bps"]), rings
+
+
+# ---- the record and the answers, once per process ----
+
+@functools.lru_cache(maxsize=None)
+def record():
+    """name -> the compiled reference's answer (tests/golden/iir_sweep_record.json)"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "iir_sweep_record.json")) as f:
+        return {r["name"]: r for r in json.load(f)["cases"]}
+
+
+@functools.lru_cache(maxsize=None)
+def want(leg, name):
+    """the restatement's answer (and, for a stream, the model's rings behind the last row), computed once per process (read-only)"""
+    c = next(c for c in sweep_cases()[leg] if c["name"] == name)
+    out = stream_expected(c) if leg in STREAM_LEGS else (expected(c), None)
+    out[0].setflags(write=False)
+    return out

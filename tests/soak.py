@@ -20,7 +20,7 @@ import torch
 
 import cases
 from streamtools import describe_mismatch, parse_stream
-from test_gpu_fuzz import KINDS as BYTE_KINDS, _gen as gen_bytes
+from fuzz_cases import KINDS as BYTE_KINDS, gen as gen_bytes
 from oracle.oracle import Oracle
 from rspt_amd import api
 
@@ -337,7 +337,7 @@ THREADED = [False]
 def fft_case(seed, r):
     """the dct packer's fp64 FFT kernels (every ns = 2^k above 8192; forced here at smaller sizes too, where the reference's own
     arithmetic is the checker): coefficients equal except truncation-boundary flips of one count, sizes within 1 %"""
-    from test_gpu_dct_fft import _coeff_mismatch
+    from dct_fft_cases import coeff_mismatch
 
     lg = int(r.integers(4, 16))
     ns, nch, bps = 1 << lg, int(r.integers(1, 7)), int(r.choice([4, 4, 3, 2]))
@@ -352,7 +352,7 @@ def fft_case(seed, r):
     pk = api.SignalPacker(api.KIND_DCT | api.DCT_FORCE_FFT, bps, nch, ns, 2)
     got = pk.compress(data)
     bad = []
-    frac, dmax = _coeff_mismatch(orc._o, got, want, bps, nch, ns)
+    frac, dmax = coeff_mismatch(orc._o, got, want, bps, nch, ns)
     if dmax > 1 or frac > 4e-3 + 2.0 / (nch * ns):
         bad.append("coefficients: %.5f of them differ, by up to %d" % (frac, dmax))
     if abs(len(got) / len(want) - 1) > 0.01 + 40.0 / len(want):

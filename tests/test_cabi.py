@@ -6,13 +6,21 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from devframe import ERR_ARG, ERR_NO_DEVICE, ROOT
 
 
 def _declared():
     txt = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rspt_hip_[a-z_0-9]+)\s*\(", txt)))
+
+
+def test_the_tests_status_names_are_the_headers_enum():
+    """tests/devframe.py's OK, ERR_ARG, ... against the RSPT_HIP_* enumerators of rspt_hip_status, every one of them"""
+    import devframe
+
+    enum = dict(re.findall(r"\bRSPT_HIP_((?:OK|ERR_[A-Z_]+)) = (-?\d+)", open(os.path.join(ROOT, "include", "rspt_hip.h")).read()))
+    assert {k: int(v) for k, v in enum.items()} == {k: getattr(devframe, k) for k in devframe.STATUS_NAMES} and len(enum) == 9
 
 
 def test_library_exports_every_declared_symbol():
@@ -168,7 +176,7 @@ def test_create_fails_loudly_without_device():
         pytest.skip("a GPU is present")
     with pytest.raises(api.RsptHipError) as e:
         api.new_xdelta_hzr(4, 1, 8192, 3)
-    assert e.value.status == -2  # RSPT_HIP_ERR_NO_DEVICE: no CPU fallback exists
+    assert e.value.status == ERR_NO_DEVICE  # no CPU fallback exists
 
 
 def test_bad_arguments_are_rejected_before_touching_the_device():
@@ -205,5 +213,5 @@ def test_an_empty_batch_is_refused_under_the_name_of_its_entry():
     for entry, call in calls.items():
         with pytest.raises(api.RsptHipError) as e:
             call()
-        assert e.value.status == -1 and str(e.value).startswith(entry + ": "), (entry, str(e.value))
+        assert e.value.status == ERR_ARG and str(e.value).startswith(entry + ": "), (entry, str(e.value))
     pk.close()

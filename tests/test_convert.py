@@ -15,11 +15,9 @@ import pytest
 
 import cases
 import convert_cases as cc
+from devframe import ERR_ARG, ERR_UNSUPPORTED, ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORD = os.path.join(ROOT, "tests", "golden", "convert_record.json")
-
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 
 
 @pytest.fixture(scope="module")

@@ -1,22 +1,19 @@
 """The exact-value rule for the dct's FFT kernels without a GPU: the inputs keep out of the comparator's band (the record of
 tests/golden/make_dct_fft_exact_record.py), the fp64 restatement that every other dct test leans on (oracle.dct_big_*) passes
 the rule itself, and the comparator rejects a single coefficient moved by one count."""
-import json
-import os
 
 import numpy as np
 import pytest
 
 import dct_fft_cases as dc
+import devframe as df
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = [c["name"] for c in dc.all_cases() if c["k"] <= 16]
 
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "dct_fft_exact_record.json")) as f:
-        r = json.load(f)
+    r = df.golden("dct_fft_exact_record.json")
     assert r["cap"] == dc.CAP
     return {e["name"]: e for e in r["cases"]}
 

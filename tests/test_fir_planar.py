@@ -7,36 +7,25 @@ GPU (-m gpu): row ends, several spans per row, stream calls with their state, na
 the handle's sample width, overflow / inf / NaN, the cross identities with the native entry and with compress_planar_batch, a
 seeded sweep, back-to-back calls, refusals, a foreign stream.  Every buffer and state sits between guards."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import devasm
+import devframe as df
 import fir_cases as fc
 import fir_planar_cases as pc
 import stream_filter_cases as sc
 from cases import digest
-from test_iir_cascade import FUSED
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD, FILL = 64, 0xA5
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRIES = ("rspt_hip_fir_prefilter_planar_batch_dev", "rspt_hip_fir_planar_state_bytes", "rspt_hip_fir_prefilter_planar_stream_dev")
-
-
-def _golden(name):
-    with open(os.path.join(ROOT, "tests", "golden", name)) as f:
-        return json.load(f)
 
 
 # ---- CPU ----
 
 def test_planar_expectation_cut_to_the_sample_width_is_the_fir_record():
-    for c, r in zip(fc.fir_cases(), _golden("fir_record.json")["cases"]):
+    for c, r in zip(fc.fir_cases(), df.golden("fir_record.json")["cases"]):
         assert c["name"] == r["name"]
         k = fc.kernel_from_record(r["kernel"])
         P = pc.record_planar(c)
@@ -47,7 +36,7 @@ def test_planar_expectation_cut_to_the_sample_width_is_the_fir_record():
 
 
 def test_planar_stream_expectation_cut_to_the_sample_width_is_the_stream_record():
-    recs = {r["name"]: r for r in _golden("stream_filter_record.json")["cases"]}
+    recs = {r["name"]: r for r in df.golden("stream_filter_record.json")["cases"]}
     seen = 0
     for c in sc.stream_cases():
         if c["kind"] != "fir":
@@ -137,22 +126,12 @@ def test_overflow_cases_hold_int32_min_from_overflow_and_from_nan():
     assert list(nan["kernel"]) == [1e308, -1e308, 0.5, 1e308]
 
 
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
 def test_the_planar_filter_kernel_rounds_every_product_and_sum_on_its_own(asm):
     """k_fir_planar<wide>: two instantiations, no fp FMA and no f64 MFMA, separate v_mul_f64 / v_add_f64, wide loads and stores on
     the aligned one; the movers hold no fp arithmetic"""
-    names = [n for n in asm if re.search(r"12k_fir_planarIL", n)]
-    assert len(names) == 2, sorted(n for n in asm if "fir" in n)
+    names = df.rounds_separately(asm, r"12k_fir_planarIL", 2)
     for n in names:
-        assert not [ln for ln in asm[n] if FUSED.match(ln)], n
         text = "".join(asm[n])
-        assert re.search(r"^\s+v_mul_f64\b", text, re.M) and re.search(r"^\s+v_add_f64\b", text, re.M), n
         assert not re.search(r"^\s+scratch_", text, re.M), n
         assert re.search(r"global_load_dwordx4", text), n  # a lane's tap group is contiguous on either path
     assert len([n for n in names if re.search(r"global_store_dwordx4", "".join(asm[n]))]) == 1  # the aligned instantiation
@@ -163,21 +142,12 @@ def test_the_planar_filter_kernel_rounds_every_product_and_sum_on_its_own(asm):
 
 
 def test_header_table_and_library_agree_on_the_planar_entries():
-    from rspt_amd import api, build
-
-    hdr = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
-    flat = re.sub(r"\s+", " ", hdr)
-    for text in ("int rspt_hip_fir_prefilter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
-                 "const double* kernel, size_t kernel_size, void* stream);",
-                 "int rspt_hip_fir_planar_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes);",
-                 "int rspt_hip_fir_prefilter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
-                 "const double* kernel, size_t kernel_size, void* d_state, void* stream);"):
-        assert text in flat, text
-    out = subprocess.check_output(["nm", "-D", "--defined-only", build.build()]).decode()
-    L = api.lib()
-    for name in ENTRIES:
-        assert re.search(r"\bT %s$" % name, out, re.M) and hasattr(L, name), name
-        assert api.C_ABI[name] == api.C_ABI[name.replace("planar_", "")], name  # pointer types as the native siblings
+    df.check_entries(("int rspt_hip_fir_prefilter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
+                      "const double* kernel, size_t kernel_size, void* stream);",
+                      "int rspt_hip_fir_planar_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes);",
+                      "int rspt_hip_fir_prefilter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
+                      "const double* kernel, size_t kernel_size, void* d_state, void* stream);"),
+                     ENTRIES, native_of={n: n.replace("planar_", "") for n in ENTRIES})  # pointer types as the native siblings
 
 
 def test_argument_checks_that_need_no_device():
@@ -195,95 +165,17 @@ def test_argument_checks_that_need_no_device():
 
 # ---- GPU ----
 
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
-
-def _guarded_bytes(n, off, fill=None):
-    """(raw, view): n bytes on the device, `off` bytes past a 16-byte boundary, between two guards; view holds `fill` (bytes) or zeros"""
-    import torch
-
-    raw = torch.full((GUARD + off + n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    view = raw[GUARD + off : GUARD + off + n]
-    assert view.data_ptr() % 16 == off and raw.data_ptr() % 16 == 0
-    if fill is None:
-        view.zero_()
-    else:
-        view.copy_(torch.from_numpy(np.ascontiguousarray(fill).view(np.uint8).reshape(-1)))
-    return raw, view
-
-
-def _guarded(P, off):
-    """(raw, view): P on the device as int32 [nblocks][nch][ns], `off` bytes past a 16-byte boundary, between two guards"""
-    import torch
-
-    raw, view = _guarded_bytes(P.size * 4, off, np.array(P))
-    return raw, view.view(torch.int32).reshape(P.shape)
-
-
-def _guards_untouched(raw, off, n):
-    return int((raw[: GUARD + off] != FILL).count_nonzero()) == 0 and int((raw[GUARD + off + n :] != FILL).count_nonzero()) == 0
-
-
 def _what(c):
-    return "%s: %r" % (c["name"], {k: v for k, v in c.items() if k not in ("planar", "name", "kernel")})
-
-
-def _run(api, c, calls="own", pk=None):
-    """c through the planar entry (calls: None stateless, else blocks per call on a fresh guarded state) -> (output, state bytes or
-    None); checks the guards and that an out-of-place source is only read"""
-    import torch
-
-    P, K, nch = c["planar"], len(c["kernel"]), c["nch"]
-    calls = c["calls"] if calls == "own" else calls
-    own = pk is None
-    pk = pk or api.new_hzr(c["bps"], nch, c["ns"])
-    sraw, src = _guarded(P, c["src_off"])
-    if c["dst_off"] is None:
-        draw, dst = sraw, src
-    else:
-        draw, dst = _guarded(np.zeros_like(P), c["dst_off"])
-    state = None
-    if calls is None:
-        out = pk.fir_prefilter_planar_batch(src, c["kernel"], d_out=None if dst is src else dst)
-        assert out is dst
-    else:
-        nst = pk.fir_planar_state_bytes(K)
-        assert nst == pc.state_bytes(K, nch)
-        straw, state = _guarded_bytes(nst, 8)
-        b0 = 0
-        for k in calls:
-            pk.fir_prefilter_planar_batch(src[b0 : b0 + k], c["kernel"], d_out=None if dst is src else dst[b0 : b0 + k], state=state)
-            b0 += k
-        assert b0 == P.shape[0]
-    torch.cuda.synchronize()
-    got = dst.cpu().numpy()
-    assert _guards_untouched(sraw, c["src_off"], P.size * 4), ("source guards", _what(c))
-    if dst is not src:
-        assert _guards_untouched(draw, c["dst_off"], P.size * 4), ("destination guards", _what(c))
-        assert np.array_equal(src.cpu().numpy(), P), ("d_src is only read", _what(c))
-    sbytes = None
-    if state is not None:
-        assert _guards_untouched(straw, 8, nst), ("state guards", _what(c))
-        sbytes = state.cpu().numpy()
-    if own:
-        pk.close()
-    return got, sbytes
+    return df.what(c, hide=("planar", "kernel"))
 
 
 def _check(api, c, want=None, tail=None, calls="own"):
+    """c through the planar entry between guards (devframe.planar_window), against the restatement -> the output"""
     if want is None:
         want, tail = pc.expected(c)
-    got, sbytes = _run(api, c, calls)
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, ("output: %d differ, first at [block, channel, sample] %s" % (len(bad), bad[:1].tolist()), _what(c))
-    if sbytes is not None:
-        assert np.array_equal(sbytes, pc.state_image(len(c["kernel"]), c["nch"], tail)), ("state", _what(c))
-    return got
+    K, kernel = len(c["kernel"]), c["kernel"]
+    return df.planar_window(api, c, lambda pk, src, **kw: pk.fir_prefilter_planar_batch(src, kernel, **kw), lambda pk: pk.fir_planar_state_bytes(K),
+                            pc.state_bytes(K, c["nch"]), want, None if tail is None else pc.state_image(K, c["nch"], tail), calls, hide=("planar", "kernel"))[0]
 
 
 @pytest.mark.gpu
@@ -387,10 +279,10 @@ def test_gpu_native_and_planar_calls_alternate_on_one_state(api):
                 rec[b0 : b0 + n] = buf.cpu().numpy()
             else:
                 rows = rec[b0 : b0 + n].reshape(-1).view("<i4").reshape(n * ns, nch)
-                raw, view = _guarded(pc.planar_of(rows, n, nch, ns), 4)
+                raw, view = df.guarded_matrix(pc.planar_of(rows, n, nch, ns), 4)
                 pk.fir_prefilter_planar_batch(view, k, state=state)
                 torch.cuda.synchronize()
-                assert _guards_untouched(raw, 4, view.numel() * 4)
+                assert df.guards_untouched(raw, 4, view.numel() * 4)
                 rec[b0 : b0 + n] = pc.native_of(view.cpu().numpy()).reshape(n, bb)
             b0 += n
         return rec, state.cpu().numpy()
@@ -507,11 +399,11 @@ def test_gpu_planar_entries_refuse_bad_arguments_and_write_nothing(api):
     nch, ns = 3, 100
     pk = api.new_hzr(2, nch, ns)
     P = pc.block(4, nch, ns, 1701)
-    raw, view = _guarded(P, 0)
+    raw, view = df.guarded_matrix(P, 0)
     before = raw.clone()
     n = P.size * 4 // 2  # bytes of two blocks
     h, st = pk._h, torch.cuda.current_stream().cuda_stream
-    straw, state = _guarded_bytes(pk.fir_planar_state_bytes(65536) + 8, 8)
+    straw, state = df.guarded(pk.fir_planar_state_bytes(65536) + 8, 8, fill=0)
     sbefore = straw.clone()
     dp = C.POINTER(C.c_double)
     k3 = np.array([0.25, 0.5, 0.25])
@@ -557,7 +449,7 @@ def test_gpu_planar_entries_refuse_bad_arguments_and_write_nothing(api):
     got = view.cpu().numpy()
     want = pc.stream_expected(P[:2], np.ones(65536) / 65536)[0]
     assert np.array_equal(got[:2], want) and np.array_equal(got[2:], pc.stateless_expected(P[:2], np.ones(65536) / 65536))
-    assert _guards_untouched(raw, 0, P.size * 4) and _guards_untouched(straw, 8, state.numel())
+    assert df.guards_untouched(raw, 0, P.size * 4) and df.guards_untouched(straw, 8, state.numel())
     pk.close()
 
 
@@ -572,8 +464,8 @@ def test_gpu_planar_entries_run_on_a_foreign_stream(api):
     for c in picks:
         want = pc.expected(c)[0]
         pk = api.new_hzr(4, c["nch"], c["ns"])
-        raw, src = _guarded(c["planar"], c["src_off"])
-        draw, dst = (raw, src) if c["dst_off"] is None else _guarded(np.zeros_like(c["planar"]), c["dst_off"])
+        raw, src = df.guarded_matrix(c["planar"], c["src_off"])
+        draw, dst = (raw, src) if c["dst_off"] is None else df.guarded_matrix(c["planar"], c["dst_off"], fill=0)
         state = pk.fir_planar_state(len(c["kernel"])) if c["calls"] else None
         s.wait_stream(torch.cuda.current_stream())
         b0 = 0
@@ -582,5 +474,5 @@ def test_gpu_planar_entries_run_on_a_foreign_stream(api):
             b0 += k
         s.synchronize()
         off = c["src_off"] if dst is src else c["dst_off"]
-        assert np.array_equal(dst.cpu().numpy(), want) and _guards_untouched(draw, off, dst.numel() * 4), _what(c)
+        assert np.array_equal(dst.cpu().numpy(), want) and df.guards_untouched(draw, off, dst.numel() * 4), _what(c)
         pk.close()

@@ -4,26 +4,22 @@
 CPU: the record's inputs, the numpy restatement (tests/fir_cases.py) against the reference's answers
 (tests/golden/fir_record.json, both drivings), the C ABI, and the device ISA of the kernels (no fused or matrix f64 ops).
 GPU (-m gpu): bit-exact against the record and the restatement, in place and out of place."""
-import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import devasm
+import devframe as df
 import fir_cases as fc
 from cases import digest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG = -1
+from devframe import ERR_ARG, api  # noqa: F401
 
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "fir_record.json")) as f:
-        return json.load(f)
+    return df.golden("fir_record.json")
 
 
 @pytest.fixture(scope="module")
@@ -88,14 +84,8 @@ def test_the_record_holds_overflow_and_nan():
 
 
 def test_header_declares_the_entry_and_the_library_exports_it():
-    from rspt_amd import build
-
-    hdr = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
-    assert re.search(r"int\s+rspt_hip_fir_prefilter_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,\s*void\s*\*\s*d_dst\s*,"
-                     r"\s*size_t\s+nblocks\s*,\s*const\s+double\s*\*\s*kernel\s*,\s*size_t\s+kernel_size\s*,\s*void\s*\*\s*stream\s*\)", hdr)
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    assert re.search(r"\bT rspt_hip_fir_prefilter_batch_dev$", out, re.M)
+    df.check_entries([re.compile(r"int\s+rspt_hip_fir_prefilter_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,\s*void\s*\*\s*d_dst\s*,"
+                                 r"\s*size_t\s+nblocks\s*,\s*const\s+double\s*\*\s*kernel\s*,\s*size_t\s+kernel_size\s*,\s*void\s*\*\s*stream\s*\)")], ["rspt_hip_fir_prefilter_batch_dev"])
 
 
 @pytest.fixture(scope="module")
@@ -108,26 +98,13 @@ def fir_asm():
 def test_fir_kernels_round_every_product_and_sum_on_their_own(fir_asm):
     """no fused multiply-add and no f64 MFMA in any k_fir* kernel; every filter kernel (k_fir<bps, aligned>: k_fir_halo only
     copies bytes) multiplies and adds with v_mul_f64 and v_add_f64"""
-    filters = [n for n in fir_asm if re.search(r"5k_firIL", n)]
-    assert len(filters) == 6, sorted(fir_asm)  # int8, int16 (+aligned), int24, int32 (+aligned)
+    df.rounds_separately(fir_asm, r"5k_firIL", 6, fused=df.FUSED_F64)  # int8, int16 (+aligned), int24, int32 (+aligned)
     assert any("k_fir_halo" in n for n in fir_asm)
-    bad = re.compile(r"^\s+(v_fma\w*_f64|v_fmac\w*_f64|v_mad\w*_f64|v_mfma\w*f64)\b")
     for n, body in fir_asm.items():
-        assert not [ln for ln in body if bad.match(ln)], n
-    for n in filters:
-        text = "".join(fir_asm[n])
-        assert re.search(r"^\s+v_mul_f64\b", text, re.M) and re.search(r"^\s+v_add_f64\b", text, re.M), n
+        assert not [ln for ln in body if df.FUSED_F64.match(ln)], n
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def _batch(data, n):
     import torch

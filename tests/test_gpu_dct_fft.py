@@ -12,19 +12,12 @@ import numpy as np
 import pytest
 
 import dct_fft_cases as dc
+from devframe import api  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 PRDN_TOL = 0.05
 CR_TOL = 0.01
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
 
 
 def _block(nch, ns, idx, bps=4, ecg=True):
@@ -33,37 +26,13 @@ def _block(nch, ns, idx, bps=4, ecg=True):
     return synth.synth_native(nch, ns, block_index=idx, bps=bps, ecg=ecg).numpy().reshape(-1)
 
 
-def _coeff_mismatch(orc, a, b, bps, nch, ns):
-    import ctypes as C
-
-    def coeffs(stream):
-        s = np.frombuffer(stream + b"\0" * 16, dtype=np.uint8).copy()
-        co = np.zeros((nch, ns), dtype=np.int32)
-        me = np.zeros(nch, dtype=np.int32)
-        used = C.c_size_t(0)
-        pk = orc.packer("dct", bps, nch, ns)
-        f = orc.lib.orc_packer_decompress_coeffs
-        f.restype = C.c_int
-        rc = f(C.c_void_p(pk._h), s.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(used), co.ctypes.data_as(C.POINTER(C.c_int32)),
-               me.ctypes.data_as(C.POINTER(C.c_int32)))
-        pk.close()
-        assert rc == 0
-        return co, me
-
-    ca, ma = coeffs(a)
-    cb, mb = coeffs(b)
-    assert (ma == mb).all()
-    d = np.abs(ca.astype(np.int64) - cb.astype(np.int64))
-    return float((d != 0).mean()), int(d.max())
-
-
 @pytest.mark.parametrize("nch,ns", [(3, 16), (2, 64), (3, 256), (2, 512), (5, 1024), (2, 2048), (4, 4096), (2, 8192)])
 def test_forced_fft_path_vs_reference_arithmetic(api, orc, nch, ns, monkeypatch):
     data = _block(nch, ns, 3)
     want = orc.packer("dct", 4, nch, ns).compress(data)  # the reference's arithmetic (pinned in test_oracle_vs_ref)
     pk = api.SignalPacker(api.KIND_DCT | api.DCT_FORCE_FFT, 4, nch, ns, 2)  # the FFT kernels where the table path would run
     got = pk.compress(data)
-    frac, dmax = _coeff_mismatch(orc, got, want, 4, nch, ns)
+    frac, dmax = dc.coeff_mismatch(orc, got, want, 4, nch, ns)
     assert dmax <= 1 and frac <= 2e-3, (frac, dmax)  # only truncation-boundary flips
     assert abs(len(got) / len(want) - 1) <= CR_TOL
     po = orc.packer("dct", 4, nch, ns)
@@ -131,7 +100,7 @@ def test_dct_16384_against_the_reference_stream(api, orc, golden):
         pk = api.new_dct(bps, nch, ns)
         got = pk.compress(c["data"])
         assert abs(len(got) / len(want) - 1) <= CR_TOL
-        frac, dmax = _coeff_mismatch(orc, got, want, bps, nch, ns)
+        frac, dmax = dc.coeff_mismatch(orc, got, want, bps, nch, ns)
         assert dmax <= 1 and frac <= 2e-3, (frac, dmax)
         # the GPU inverse on the reference's stream, and on its own
         for s in (want, got):

@@ -14,18 +14,11 @@ import pytest
 
 import dct_fft_cases as dc
 import lossy_quantizer_cases as lq
+from devframe import api  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SWEEP = {c["name"]: c for c in dc.sweep_cases()}
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
 
 
 @pytest.fixture(scope="module")

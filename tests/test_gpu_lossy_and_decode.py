@@ -11,20 +11,13 @@ import numpy as np
 import pytest
 
 import cases
+from devframe import ERR_CORRUPT, api  # noqa: F401
 from streamtools import describe_mismatch, parse_stream
 
 pytestmark = pytest.mark.gpu
 
 PRDN_TOL = 0.05  # percentage points
 CR_TOL = 0.01
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
 
 
 ALL = cases.packer_cases()
@@ -100,7 +93,7 @@ def test_corrupt_stream_is_reported(api, orc, packer_cases):
     bad[15] = 7  # first hzr block header starts at 9: [len-1:2][crc:4][mode:1] -> invalid encoding mode
     with pytest.raises(api.RsptHipError) as e:
         pk.decompress(bytes(bad))
-    assert e.value.status == -6
+    assert e.value.status == ERR_CORRUPT
     bad = bytearray(s)
     bad[5:9] = (123).to_bytes(4, "little")  # master header disagrees with the packer's N
     with pytest.raises(api.RsptHipError):
@@ -127,7 +120,7 @@ def test_bit_flips_never_take_the_decoder_down(api, orc, packer_cases):
             dec, used = pk.decompress(bytes(bad) + bytes(64))
             assert dec == c["data"].tobytes(), "a damaged stream decoded to other bytes without being reported (bit %d)" % pos
         except api.RsptHipError as e:
-            assert e.status == -6, (pos, e.status)
+            assert e.status == ERR_CORRUPT, (pos, e.status)
             reported += 1
     assert reported >= 40  # (nearly every bit of a stream matters)
     dec, used = pk.decompress(s)
@@ -141,9 +134,9 @@ def test_tree_description_flips_with_long_codes(api, orc, n):
     (second-level slots, overflow walks; n = 65536: the parallel tree recovery, 3000: the one-wave parse).  Without block
     verification a damaged tree may decode to other bytes -- what is required is that every call returns (an error or n
     bytes) and that the handle still decodes the pristine stream."""
-    from test_gpu_fuzz import _gen
+    from fuzz_cases import gen
 
-    data = _gen(4242, n, "wide")
+    data = gen(4242, n, "wide")
     pk = api.new_hzr(1, 1, n)
     s = pk.compress(data, dst_max_len=pk.max_compressed_size)
     p = parse_stream(s)
@@ -159,7 +152,7 @@ def test_tree_description_flips_with_long_codes(api, orc, n):
             assert len(dec) == n
             outcomes[0] += 1
         except api.RsptHipError as e:
-            assert e.status == -6, (bit, e.status)
+            assert e.status == ERR_CORRUPT, (bit, e.status)
             outcomes[1] += 1
     assert outcomes[1] > 0  # (a flipped branch / leaf bit shifts the whole description: most of them cannot be a tree)
     dec, used = pk.decompress(s)
@@ -407,12 +400,12 @@ def test_bounded_decompress_and_fill_block_verification(api, orc):
     for cut in (1, 4, 5, 9, 100, len(s) // 2, len(s) - 1):
         with pytest.raises(api.RsptHipError) as e:
             pk.decompress(s[:cut], bounded=True)
-        assert e.value.status == -6, cut
+        assert e.value.status == ERR_CORRUPT, cut
     big = bytearray(s)
     big[1:5] = (0x7FFFFFF0).to_bytes(4, "little")  # plane 0 claims 2 GiB
     with pytest.raises(api.RsptHipError) as e:
         pk.decompress(bytes(big), bounded=True)
-    assert e.value.status == -6
+    assert e.value.status == ERR_CORRUPT
     dec, used = pk.decompress(s, bounded=True)
     assert used == len(s) and dec == data.tobytes()
     # a Fill block's value flipped: reported with verification on
@@ -425,7 +418,7 @@ def test_bounded_decompress_and_fill_block_verification(api, orc):
     pk.set_verify(True)
     with pytest.raises(api.RsptHipError) as e:
         pk.decompress(bytes(bad), bounded=True)
-    assert e.value.status == -6
+    assert e.value.status == ERR_CORRUPT
     pk.set_verify(False)
     dec, used = pk.decompress(bytes(bad), bounded=True)  # (without verification the damaged value is simply what comes out)
     assert used == len(s) and dec != data.tobytes()

@@ -4,35 +4,25 @@ inputs and settings in tests/lossy_quantizer_cases.py) -- bit for bit on the had
 dct, inside the gates of tests/test_gpu_dct_fft.py on the dct's FFT kernels -- through every kind of entry point, and the
 setter's own contract."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 
 import cases
+import devframe as df
 import lossy_quantizer_cases as lq
+from devframe import ERR_ARG, api  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = {c["name"]: c for c in lq.all_cases()}
 EXACT = [c["name"] for c in lq.all_cases() if c["fft"] is None]
 FFT = [c["name"] for c in lq.all_cases() if c["fft"] is not None]
 
 
 @pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
-
-@pytest.fixture(scope="module")
 def rec():
-    with open(os.path.join(ROOT, "tests", "golden", "lossy_quantizer_record.json")) as f:
-        return {e["name"]: e for e in json.load(f)["cases"]}
+    return {e["name"]: e for e in df.golden("lossy_quantizer_record.json")["cases"]}
 
 
 def _new(api, c, flags=0):
@@ -229,7 +219,7 @@ def test_the_many_pipeline_and_the_feed_follow_the_setting(api, rec, name):
     pk.feed_begin(1, 3)
     with pytest.raises(api.RsptHipError) as e:
         pk.set_quantizer(c["q"] * 2, c["nb"])
-    assert e.value.status == -1
+    assert e.value.status == ERR_ARG
     for d, o in zip(data, dst):
         assert pk.feed_push(np.ascontiguousarray(d), o)
     pk.feed_flush()

@@ -19,8 +19,9 @@ import numpy as np
 import pytest
 
 import cases
+from devframe import api  # noqa: F401
+from hzr_dev import Hzr, gpu_decode, gpu_encode
 from streamtools import describe_mismatch
-from test_hzr_bytes import Hzr, gpu_decode, gpu_encode
 
 pytestmark = pytest.mark.gpu
 
@@ -29,14 +30,6 @@ SEG = 4096
 RAGGED = 3 * SEG + 1007
 CAP = 16662
 MODE_COPY, MODE_HUFF, MODE_FILL, MODE_STAGED = 0, 1, 2, 4  # BlockMeta::mode (common.hpp); the stream's mode byte of a staged block is 1
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible: the HIP path cannot run (no CPU fallback)"
-    return a
 
 
 @pytest.fixture(scope="module")

@@ -11,22 +11,15 @@ import numpy as np
 import pytest
 
 import cases
+from devframe import api  # noqa: F401
+from hzr_dev import Hzr, gpu_decode, gpu_encode
 from streamtools import describe_mismatch
-from test_hzr_bytes import Hzr, gpu_decode, gpu_encode
 
 pytestmark = pytest.mark.gpu
 
 BLOCK = 65536
 SEG = 4096
 GRANULES = SEG // 16  # per segment
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible: the HIP path cannot run (no CPU fallback)"
-    return a
 
 
 @pytest.fixture(scope="module")

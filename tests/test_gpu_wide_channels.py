@@ -5,22 +5,20 @@ k_planar_native keeps one row of all channels in LDS, which ended create at 8192
 there.  Every stream is compared byte for byte with the CPU oracle (which tests/test_convert.py pins to the compiled reference's
 recorded hashes for these block generators), every decoded block with the oracle's.
 """
-import json
-import os
 
 import numpy as np
 import pytest
 
 import cases
 import convert_cases as cc
+import devframe as df
+from devframe import ERR_UNSUPPORTED
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("xdelta_hzr", "hzr", "dct", "hadamard")
 NB = {"xdelta_hzr": 3, "hzr": 4, "dct": 2, "hadamard": 3}
 NCH = (8192, 8193, 12000, 65535)
-ERR_UNSUPPORTED = -7
 
 
 def _ns(nch):
@@ -110,8 +108,7 @@ def test_wide_streams_have_the_references_hashes(orc):
 
     from rspt_amd import api
 
-    with open(os.path.join(ROOT, "tests", "golden", "convert_record.json")) as f:
-        by_name = {e["name"]: e for e in json.load(f)["cases"]}
+    by_name = {e["name"]: e for e in df.golden("convert_record.json")["cases"]}
     for c in cc.WIDE_PACKER_CASES:
         pk = api.SignalPacker(c["kind"], c["bps"], c["nch"], c["ns"], c["nb"])
         d = torch.from_numpy(cc.wide_packer_input(c)).cuda().reshape(1, -1)

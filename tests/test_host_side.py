@@ -9,8 +9,7 @@ import numpy as np
 import pytest
 
 import cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from devframe import ERR_ARG, ERR_CORRUPT, ERR_DST_TOO_SMALL, ROOT, api  # noqa: F401
 
 
 @pytest.mark.parametrize("bps", [1, 2, 3, 4])
@@ -39,14 +38,6 @@ def test_cxx_shard_example_compiles(tmp_path):
     subprocess.check_call(["g++", "-std=c++11", "-pthread", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "shard_devices.cpp"),
                            "-o", str(exe), "-L" + lib_dir, "-lrspt_hip", "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib"])
     assert exe.exists()
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
 
 
 @pytest.mark.gpu
@@ -131,7 +122,7 @@ def test_compress_many_equals_a_loop_of_compress_calls(api, orc, pinned):
     damaged[3, 15] = 7  # stream 3: the first hzr block header [len-1:2][crc:4][mode:1] starts at 9 -> invalid encoding mode
     with pytest.raises(api.RsptHipError) as e:
         pk.decompress_many(damaged, back[: (n - 70) * pk.block_bytes])
-    assert e.value.status == -6
+    assert e.value.status == ERR_CORRUPT
     # a destination stride too short for some streams: those report the size they need, the others arrive
     short = int(np.median(lens))
     out2 = np.zeros((n, short), dtype=np.uint8)
@@ -143,7 +134,7 @@ def test_compress_many_equals_a_loop_of_compress_calls(api, orc, pinned):
             assert out2[i, : lens[i]].tobytes() == want[i], i
     with pytest.raises(api.RsptHipError) as e:
         pk2.compress_many(src, out2)
-    assert e.value.status == -5
+    assert e.value.status == ERR_DST_TOO_SMALL
     pk.close()
     pk2.close()
     if pinned:
@@ -341,7 +332,7 @@ def test_feed_equals_a_loop_of_compress_calls(api, orc, group, slots, pinned):
     for i in range(n):
         ln, st = got[i]
         if i == small:
-            assert st == -5 and ln == len(want[i])
+            assert st == ERR_DST_TOO_SMALL and ln == len(want[i])
         else:
             assert st == 0 and dst_a[i][:ln].tobytes() == want[i], i
     assert pk.feed_poll() is None
@@ -351,7 +342,6 @@ def test_feed_equals_a_loop_of_compress_calls(api, orc, group, slots, pinned):
     pk.close()
     for b in bufs:
         b.close()
-
 
 
 @pytest.mark.gpu
@@ -409,7 +399,7 @@ def test_batch_entry_points_refuse_while_a_feed_is_open(api):
     pk.feed_begin(2, 2)
     with pytest.raises(api.RsptHipError) as e:
         pk.compress_batch(d_src)
-    assert e.value.status == -1
+    assert e.value.status == ERR_ARG
     with pytest.raises(api.RsptHipError):
         pk.decompress_batch(want_dst, B, want_dst.shape[1])
     host = d_src.cpu().numpy()
@@ -462,7 +452,7 @@ def test_page_locked_buffers_are_used_in_place(api, orc, kind, bps, nch, ns):
         tiny[:] = 0x55
         with pytest.raises(api.RsptHipError) as e:
             pk.compress_into(src.a[: x.size], tiny)
-        assert e.value.status == -5 and (tiny == 0x55).all(), room
+        assert e.value.status == ERR_DST_TOO_SMALL and (tiny == 0x55).all(), room
     for b in (src, dst, back):
         b.close()
     pk.close()

@@ -1,7 +1,6 @@
 """The raw hzr byte-buffer codec (RSPT_HIP_KIND_BYTES) against libhzr: every stream byte-for-byte hzr_encode's, every decode
 hzr_decode's, every verdict hzr_verify's.  The reference is the compiled one where oracle/_ref is there, else the oracle's
 restatement (the two are pinned to each other on the CPU: tests/test_oracle_golden.py)."""
-import ctypes as C
 import struct
 import zlib
 
@@ -9,51 +8,11 @@ import numpy as np
 import pytest
 
 import cases
+from devframe import ERR_ARG, ERR_CORRUPT, ERR_DST_TOO_SMALL, api  # noqa: F401
+from hzr_dev import BAD, Hzr, gpu_decode, gpu_encode
 from streamtools import describe_mismatch
 
 pytestmark = pytest.mark.gpu
-
-BAD = 1 << 63
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible: the HIP path cannot run (no CPU fallback)"
-    return a
-
-
-class Hzr:
-    """hzr_encode / hzr_decode / hzr_verify of the reference (or of its restatement)"""
-
-    def __init__(self, orc):
-        from oracle import oracle
-
-        self.orc = orc
-        self.ref = oracle.Ref() if oracle.have_ref() else None
-        self.enc = self.ref or orc
-
-    def encode(self, data):
-        return self.enc.hzr_encode(data)
-
-    def decode(self, stream, n):
-        """-> bytes, or None where hzr_decode fails (trailing bytes are not the decoder's business here: the restatement)"""
-        try:
-            return self.orc.hzr_decode(stream, n)[0]
-        except RuntimeError:
-            return None
-
-    def verify(self, stream):
-        """(ok, decoded size).  The reference checksums a block before it knows that the block ends inside the stream
-        (hzr_decode.c:606-618): a block's length of zeros behind the stream keeps that read inside our memory."""
-        s = np.frombuffer(bytes(stream), dtype=np.uint8)
-        padded = np.zeros(s.size + 65536 + 16, dtype=np.uint8)
-        padded[: s.size] = s
-        n = C.c_size_t(0)
-        f = self.ref.lib.ref_hzr_verify if self.ref else self.orc.lib.orc_hzr_verify
-        ok = f(padded.ctypes.data_as(C.POINTER(C.c_uint8)), s.size, C.byref(n))
-        return bool(ok), n.value
 
 
 @pytest.fixture(scope="module")
@@ -105,36 +64,6 @@ def content(orc, kind, n, seed=0):
     return np.resize(np.roll(_xdelta_plane(orc, 0 if kind == "xd0" else 2), -4099 * seed), n)
 
 
-# ---- device helpers -------------------------------------------------------------------------------------------------------
-def gpu_encode(pk, bufs, dst_stride=None, fill=None):
-    """-> (streams or None where flagged, raw d_dst as numpy [nb, stride], sizes)"""
-    import torch
-
-    d_src = torch.from_numpy(np.concatenate(bufs)).cuda()
-    n = len(bufs)
-    stride = dst_stride if dst_stride is not None else (pk.max_compressed_size + 255) // 256 * 256
-    d_dst = torch.full((n, stride), 0 if fill is None else fill, dtype=torch.uint8, device="cuda")
-    d_dst, d_sizes = pk.compress_batch(d_src, d_dst=d_dst, dst_stride=stride)
-    torch.cuda.synchronize()
-    sizes = d_sizes.cpu().numpy().view(np.uint64)
-    raw = d_dst.cpu().numpy()
-    out = [None if int(s) & BAD else raw[i, : int(s)].tobytes() for i, s in enumerate(sizes)]
-    return out, raw, sizes
-
-
-def gpu_decode(pk, streams, n):
-    """streams (bytes) through rspt_hip_decompress_batch_dev -> (outputs [len(streams), n], consumed as uint64)"""
-    import torch
-
-    stride = (max(len(s) for s in streams) + 15) // 16 * 16 + 16
-    host = np.zeros((len(streams), stride), dtype=np.uint8)
-    for i, s in enumerate(streams):
-        host[i, : len(s)] = np.frombuffer(s, dtype=np.uint8)
-    d_out, d_used = pk.decompress_batch(torch.from_numpy(host).cuda(), len(streams), stride)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().reshape(len(streams), n), d_used.cpu().numpy().view(np.uint64)
-
-
 def check_streams(hzr, got, bufs):
     for i, (g, b) in enumerate(zip(got, bufs)):
         want = hzr.encode(b)
@@ -162,10 +91,10 @@ def test_kat_stream_is_hzr_encode(api, hzr, golden, name):
     assert dec == data.tobytes() and used == len(got)
     with pytest.raises(api.RsptHipError) as e:  # HZR_FAIL of a short buffer
         pk.compress(data, dst_max_len=len(want) - 1)
-    assert e.value.status == -5
+    assert e.value.status == ERR_DST_TOO_SMALL
     with pytest.raises(api.RsptHipError) as e:
         pk.set_nb(2)
-    assert e.value.status == -1
+    assert e.value.status == ERR_ARG
     pk.close()
 
 
@@ -255,7 +184,7 @@ def test_host_bounded_and_container_forms(api, hzr, orc):
             assert dec == b.tobytes() and used == len(w)
         with pytest.raises(api.RsptHipError) as e:  # a bound inside the stream: nothing behind it is read
             pk.decompress(w[:-1], bounded=True)
-        assert e.value.status == -6
+        assert e.value.status == ERR_CORRUPT
     # rspt_hip_compress_many / rspt_hip_decompress_many
     src = np.concatenate(bufs)
     out = np.zeros((len(bufs), (pk.max_compressed_size + 15) // 16 * 16), dtype=np.uint8)
@@ -292,7 +221,7 @@ def test_other_decoded_size_is_flagged(api, hzr, orc):
     assert int(used[1]) & BAD and int(used[2]) & BAD
     with pytest.raises(api.RsptHipError) as e:
         pk.decompress(streams[1])
-    assert e.value.status == -6
+    assert e.value.status == ERR_CORRUPT
     pk.close()
 
 
@@ -369,7 +298,7 @@ def test_verify_matches_hzr_verify_on_200_streams(api, hzr, orc):
     other = api.new_hzr(1, 1, 16)
     with pytest.raises(api.RsptHipError) as e:  # bytes handles only
         other.hzr_verify_batch(torch.from_numpy(host).cuda(), d_len, src_stride=stride)
-    assert e.value.status == -1
+    assert e.value.status == ERR_ARG
     other.close()
     pk.close()
 

@@ -3,7 +3,7 @@ argument checks rspt_hip_packer_create makes before it touches a device.  No GPU
 import ctypes as C
 import random
 
-ERR_ARG = -1
+from devframe import ERR_ARG
 
 
 def test_hzr_max_compressed_size_is_the_oracles(orc):

@@ -14,21 +14,17 @@ contents of the carried state are covered by the seeded sweep, tests/test_iir_sw
 tests/iir_sweep_cases.py)."""
 import ctypes as C
 import functools
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import devasm
+import devframe as df
 import iir_cascade_cases as cc
 import iir_cases as ic
 from cases import digest
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRIES = ("rspt_hip_iir_cascade_batch_dev", "rspt_hip_iir_cascade_state_bytes", "rspt_hip_iir_cascade_stream_dev")
 CHUNK = cc.CHUNK
 
@@ -39,8 +35,7 @@ FORMS = ("stateless", "stream")
 
 @functools.lru_cache(maxsize=None)
 def _record():
-    with open(os.path.join(ROOT, "tests", "golden", "iir_cascade_record.json")) as f:
-        return json.load(f)
+    return df.golden("iir_cascade_record.json")
 
 
 @functools.lru_cache(maxsize=None)
@@ -140,32 +135,13 @@ def test_filter_and_filter_opt_round_differently():
 
 
 def test_header_declares_the_entries_and_the_library_exports_them():
-    from rspt_amd import api, build
-
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
-    for decl in (
+    df.check_entries((
         "int rspt_hip_iir_cascade_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d, "
         "const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* stream);",
         "int rspt_hip_iir_cascade_state_bytes(rspt_hip_packer* p, size_t nsections, size_t* bytes);",
         "int rspt_hip_iir_cascade_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, size_t nsections, const double* n, const double* d, "
         "const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, void* d_state, void* stream);",
-    ):
-        assert decl in hdr, decl
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    for name in ENTRIES:
-        assert re.search(r"\bT %s$" % name, out, re.M), name
-        assert name in api.C_ABI_SYMBOLS
-
-
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
-FUSED = re.compile(r"^\s+(v_fma\w*_f(64|32)|v_fmac\w*_f(64|32)|v_mad\w*_f(64|32)|v_mac\w*_f(64|32)|v_pk_fma\w*|v_mfma\w*f64)\b")
+    ), ENTRIES)
 
 
 def test_the_cascade_kernels_hold_no_fused_multiply_add(asm):
@@ -175,7 +151,7 @@ def test_the_cascade_kernels_hold_no_fused_multiply_add(asm):
     assert len(plain) == 8, sorted(plain)
     assert len(pipe) == 12, sorted(pipe)
     for n in plain + pipe:
-        assert not [ln for ln in asm[n] if FUSED.match(ln)], n
+        assert not [ln for ln in asm[n] if df.FUSED_F64_F32.match(ln)], n
 
 
 def test_argument_checks_that_need_no_device():
@@ -194,14 +170,6 @@ def test_argument_checks_that_need_no_device():
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def _drive(pk, sections, data, split, state):
     """the recording through successive calls of split[i] blocks each (state None: stateless calls); -> the filtered bytes"""

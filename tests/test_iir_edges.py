@@ -18,8 +18,8 @@ import pytest
 
 import iir_cases as ic
 from cases import digest
+from devframe import ROOT, api  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORD = os.path.join(ROOT, "tests", "golden", "iir_record.json")
 MODES = ("shared", "per_channel")
 
@@ -137,14 +137,6 @@ def test_record_text_is_reproduced_byte_for_byte():
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", NAMES)

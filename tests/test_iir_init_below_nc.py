@@ -14,6 +14,7 @@ import pytest
 
 import iir_cascade_cases as cc
 import iir_cases as ic
+from devframe import api  # noqa: F401
 
 NC, INIT, NCH, NBLOCKS = 5, 1, 3, 2
 N5, D5 = ic.STABLE[NC]
@@ -54,14 +55,6 @@ def test_the_case_stops_short_of_a_full_ring():
     assert 4 * INIT < NC == len(N5) == len(D5)
     assert ic.kernel_of(40, INIT, NC) == "iir" and ic.kernel_of(70, INIT, NC) == "pipe" and ic.CHUNK_PIPE < 70 < 2 * ic.CHUNK_PIPE
     assert 31 < cc.CHUNK < 33
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
 
 
 @pytest.mark.gpu

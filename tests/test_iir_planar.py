@@ -7,22 +7,18 @@ GPU (-m gpu): the sweep through the planar entries; row ends, stream boundaries 
 outside the handle's sample width; native and planar calls on one state; the reference pipeline to_planar_i32 -> IIR ->
 compress_planar_batch against the oracle and the native path; refusals; a foreign stream.  Every buffer sits between guards."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import cases
-import devasm
+import devframe as df
 import iir_planar_cases as pc
 import iir_sweep_cases as sw
-import test_iir_sweep as ts
 from cases import digest
-from test_iir_cascade import FUSED
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
+from iir_model import same_doubles, state_rings
 
-GUARD, FILL = 64, 0xA5
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 BANDPASS = cases.IIR_BANDPASS  # the harness's band-pass (rspt_test.cpp:116-136), init_nr_samples 2000
 
 
@@ -31,7 +27,7 @@ BANDPASS = cases.IIR_BANDPASS  # the harness's band-pass (rspt_test.cpp:116-136)
 @pytest.mark.parametrize("leg", pc.SWEEP_LEGS)
 def test_planar_expectation_cut_to_the_sample_width_is_the_reference_record(leg):
     for c in sw.sweep_cases()[leg]:
-        want, r = pc.sweep_expected(c), ts._record()[c["name"]]
+        want, r = pc.sweep_expected(c), sw.record()[c["name"]]
         assert want.shape == (c["nblocks"], c["nch"], c["ns"]) and want.dtype == np.int32
         y = pc.cut(want, c["bps"])
         assert digest(y) == r["digest"] and sw.crc(y) == r["crc32"], c["name"]
@@ -113,37 +109,21 @@ def test_route_and_width_cases_cover_what_they_are_for():
                                                                             ("single", True, False), ("cascade", True, None)}
 
 
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
 def test_the_planar_kernels_hold_no_fused_multiply_add(asm):
     """k_iir_planar (order x mode), k_iir_planar_carry (order), k_iir_pipe_planar (order x (per channel, shared, carried)),
     k_iir_cascade_planar and k_iir_cascade_pipe_planar (stateless, carried)"""
     want = {r"12k_iir_planarIL": 8, r"18k_iir_planar_carryIL": 4, r"17k_iir_pipe_planarIL": 12, r"20k_iir_cascade_planarIL": 2, r"25k_iir_cascade_pipe_planarIL": 2}
     for pat, count in want.items():
-        names = [n for n in asm if re.search(pat, n)]
-        assert len(names) == count, (pat, sorted(names))
-        for n in names:
-            assert not [ln for ln in asm[n] if FUSED.match(ln)], n
-            text = "".join(asm[n])
-            assert re.search(r"^\s+v_mul_f64\b", text, re.M) and re.search(r"^\s+v_add_f64\b", text, re.M), n
+        df.rounds_separately(asm, pat, count)
 
 
 def test_header_table_and_library_agree_on_the_planar_entries():
-    from rspt_amd import api
-
-    header = open(os.path.join(ts.ROOT, "include", "rspt_hip.h")).read()
-    L = api.lib()
-    for stage in ("prefilter", "cascade"):
-        for form in ("batch", "stream"):
-            name = "rspt_hip_iir_%s_planar_%s_dev" % (stage, form)
-            native = "rspt_hip_iir_%s_%s_dev" % (stage, form)
-            assert re.search(r"^int %s\(rspt_hip_packer\* p, int32_t\* d_planar, size_t nblocks," % name, header, re.M), name
-            assert api.C_ABI[name] == api.C_ABI[native] and hasattr(L, name), name
+    native_of = {"rspt_hip_iir_%s_planar_%s_dev" % (stage, form): "rspt_hip_iir_%s_%s_dev" % (stage, form) for stage in ("prefilter", "cascade") for form in ("batch", "stream")}
+    single = "int rspt_hip_iir_prefilter_planar_%s_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, const double* n, const double* d, size_t nr_coefficients, int init_nr_samples, %svoid* stream);"
+    cascade = ("int rspt_hip_iir_cascade_planar_%s_dev(rspt_hip_packer* p, int32_t* d_planar, size_t nblocks, size_t nsections, const double* n, const double* d, "
+               "const uint32_t* nr_coefficients, const int32_t* init_nr_samples, const uint8_t* use_filter, %svoid* stream);")
+    df.check_entries((single % ("batch", "int per_channel, "), single % ("stream", "void* d_state, "), cascade % ("batch", ""), cascade % ("stream", "void* d_state, ")),
+                     list(native_of), native_of)
 
 
 def test_argument_checks_that_need_no_device():
@@ -162,32 +142,8 @@ def test_argument_checks_that_need_no_device():
 
 # ---- GPU ----
 
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
-
-def _guarded(P, off):
-    """(raw, view): P on the device as int32 [nblocks][nch][ns], `off` bytes past a 16-byte boundary, between two guards"""
-    import torch
-
-    n = P.size * 4
-    raw = torch.full((GUARD + off + n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    view = raw[GUARD + off : GUARD + off + n].view(torch.int32).reshape(P.shape)
-    assert view.data_ptr() % 16 == off and raw.data_ptr() % 16 == 0
-    view.copy_(torch.from_numpy(np.array(P)))
-    return raw, view
-
-
-def _guards_untouched(raw, off, n):
-    return int((raw[: GUARD + off] != FILL).count_nonzero()) == 0 and int((raw[GUARD + off + n :] != FILL).count_nonzero()) == 0
-
-
 def _what(c):
-    return "%s: %r" % (c["name"], {k: v for k, v in c.items() if k not in ("data", "planar", "name")})
+    return df.what(c, hide=("data", "planar"))
 
 
 def _call(pk, c, view, state=None, stream=None):
@@ -203,7 +159,7 @@ def _run(api, c, P, want, rings, calls, off, what):
     import torch
 
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    raw, view = _guarded(P, off)
+    raw, view = df.guarded_matrix(P, off)
     state, S = None, len(pc.sections_of(c))
     if calls is None:
         _call(pk, c, view)
@@ -217,17 +173,17 @@ def _run(api, c, P, want, rings, calls, off, what):
         assert b0 == P.shape[0]
     torch.cuda.synchronize()
     got = view.cpu().numpy()
-    assert _guards_untouched(raw, off, P.size * 4), (what, "guards", _what(c))
+    assert df.guards_untouched(raw, off, P.size * 4), (what, "guards", _what(c))
     bad = np.argwhere(got != want)
     assert bad.size == 0, (what, "output: %d differ, first at [block, channel, sample] %s" % (len(bad), bad[:1].tolist()), _what(c))
     out = (got, None, None)
     if state is not None:
-        x, y, started = ts._rings(state, dict(c, sections=pc.sections_of(c)))
+        x, y, started = state_rings(state, c["nch"], S)
         assert (started == 1).all(), (what, "started", _what(c))
         for k, (mx, my) in enumerate(rings):
             nc = mx.shape[0]
-            assert ts._same_doubles(x[:, k, :nc].T, mx), (what, "x ring of section %d" % k, _what(c))
-            assert ts._same_doubles(y[:, k, :nc].T, my), (what, "y ring of section %d" % k, _what(c))
+            assert same_doubles(x[:, k, :nc].T, mx), (what, "x ring of section %d" % k, _what(c))
+            assert same_doubles(y[:, k, :nc].T, my), (what, "y ring of section %d" % k, _what(c))
         out = (got, x, y)
     pk.close()
     return out
@@ -235,16 +191,16 @@ def _run(api, c, P, want, rings, calls, off, what):
 
 def _sweep_leg(api, leg):
     for c in sw.sweep_cases()[leg]:
-        want, rec, P = pc.sweep_expected(c), ts._record()[c["name"]], pc.sweep_planar(c)
+        want, rec, P = pc.sweep_expected(c), sw.record()[c["name"]], pc.sweep_planar(c)
         off = 4 * c["off"]
         if leg in sw.STREAM_LEGS:
-            rings = ts._want(leg, c["name"])[1]
+            rings = sw.want(leg, c["name"])[1]
             assert all(L % c["ns"] == 0 for L in c["calls"])
             cutup = _run(api, c, P, want, rings, [L // c["ns"] for L in c["calls"]], off, "cut")
             whole = _run(api, c, P, want, rings, [c["nblocks"]], off, "one_call")
             for k, (mx, _) in enumerate(rings):  # however it is cut: the same first nc places
                 nc = mx.shape[0]
-                assert ts._same_doubles(cutup[1][:, k, :nc], whole[1][:, k, :nc]) and ts._same_doubles(cutup[2][:, k, :nc], whole[2][:, k, :nc]), ("cut invariance", _what(c))
+                assert same_doubles(cutup[1][:, k, :nc], whole[1][:, k, :nc]) and same_doubles(cutup[2][:, k, :nc], whole[2][:, k, :nc]), ("cut invariance", _what(c))
             got = cutup[0]
         else:
             got = _run(api, c, P, want, None, None, off, "stateless")[0]
@@ -279,7 +235,7 @@ def _cases(api, C):
             whole = _run(api, c, c["planar"], want, rings, [c["nblocks"]], c["off"], "one_call")
             for k, (mx, _) in enumerate(rings):
                 nc = mx.shape[0]
-                assert ts._same_doubles(cutup[1][:, k, :nc], whole[1][:, k, :nc]) and ts._same_doubles(cutup[2][:, k, :nc], whole[2][:, k, :nc]), ("cut invariance", _what(c))
+                assert same_doubles(cutup[1][:, k, :nc], whole[1][:, k, :nc]) and same_doubles(cutup[2][:, k, :nc], whole[2][:, k, :nc]), ("cut invariance", _what(c))
         else:
             _run(api, c, c["planar"], want, None, None, c["off"], "stateless")
 
@@ -334,13 +290,13 @@ def test_gpu_native_and_planar_calls_alternate_on_one_state(api):
                 rec[b0 : b0 + k] = buf.cpu().numpy()
             else:
                 rows = rec[b0 : b0 + k].reshape(-1).view("<i4").reshape(k * ns, nch)
-                raw, view = _guarded(pc.planar_of(rows, k, nch, ns), 4)
+                raw, view = df.guarded_matrix(pc.planar_of(rows, k, nch, ns), 4)
                 if entry == "single":
                     pk.iir_prefilter_planar_batch(view, n, d, init_nr_samples=7, per_channel=True, state=state)
                 else:
                     pk.iir_cascade_planar_batch(view, sections, state=state)
                 torch.cuda.synchronize()
-                assert _guards_untouched(raw, 4, view.numel() * 4)
+                assert df.guards_untouched(raw, 4, view.numel() * 4)
                 rec[b0 : b0 + k] = pc.native_of(view.cpu().numpy()).reshape(k, bb)
             b0 += k
         return rec, state.cpu().numpy()
@@ -413,7 +369,7 @@ def test_gpu_planar_entries_refuse_what_the_native_ones_refuse(api):
     nch, ns = 3, 100
     pk = api.new_hzr(2, nch, ns)
     P = pc.block(2, nch, ns, 77)
-    raw, view = _guarded(P, 0)
+    raw, view = df.guarded_matrix(P, 0)
     before = raw.clone()
     h, st = pk._h, torch.cuda.current_stream().cuda_stream
     state = torch.zeros(88 * nch * 4 + 8, dtype=torch.uint8, device="cuda")
@@ -472,7 +428,7 @@ def test_gpu_planar_entries_refuse_what_the_native_ones_refuse(api):
     # accepted: the extremes, on a handle whose bps is not 4
     assert single(nc=2) == 0 and single(nc=5, init=0) == 0 and cascade(S=4, nc=(5, 2, 5, 2), stream_form=True, state_ptr=state.data_ptr()) == 0
     torch.cuda.synchronize()
-    assert _guards_untouched(raw, 0, P.size * 4)
+    assert df.guards_untouched(raw, 0, P.size * 4)
     pk.close()
 
 
@@ -488,7 +444,7 @@ def test_gpu_planar_entries_run_on_a_foreign_stream(api):
     for c in picks:
         want = pc.expected(c)[0]
         pk = api.new_hzr(4, c["nch"], c["ns"])
-        raw, view = _guarded(c["planar"], c["off"])
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
         state = None
         if c["calls"]:
             state = pk.iir_state() if c["kind"] == "single" else pk.iir_cascade_state(len(c["sections"]))
@@ -498,5 +454,5 @@ def test_gpu_planar_entries_run_on_a_foreign_stream(api):
             _call(pk, c, view[b0 : b0 + k], state=state, stream=s.cuda_stream)
             b0 += k
         s.synchronize()
-        assert np.array_equal(view.cpu().numpy(), want) and _guards_untouched(raw, c["off"], view.numel() * 4), _what(c)
+        assert np.array_equal(view.cpu().numpy(), want) and df.guards_untouched(raw, c["off"], view.numel() * 4), _what(c)
         pk.close()

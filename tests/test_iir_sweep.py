@@ -9,34 +9,17 @@ GPU (-m gpu): one test per leg that loops over its cases.  The output equals the
 untouched guards; the zero-phase workspace is exactly its bound, starts as NaNs and sits between guards too; a stream's state is
 decoded by the layout rspt_hip.h documents and its rings equal the model's, and the same recording in one call gives the same
 output and the same rings."""
-import functools
-import json
-import os
 
 import numpy as np
 import pytest
 
+import devframe as df
 import iir_sweep_cases as sw
 from cases import digest
+from devframe import api  # noqa: F401
+from iir_model import same_doubles, state_rings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PART = sw.PART
-GUARD, FILL = 64, 0xA5
-
-
-@functools.lru_cache(maxsize=None)
-def _record():
-    with open(os.path.join(ROOT, "tests", "golden", "iir_sweep_record.json")) as f:
-        return {r["name"]: r for r in json.load(f)["cases"]}
-
-
-@functools.lru_cache(maxsize=None)
-def _want(leg, name):
-    """the restatement's answer (and, for a stream, the model's rings behind the last row), computed once per process (read-only)"""
-    c = next(c for c in sw.sweep_cases()[leg] if c["name"] == name)
-    out = sw.stream_expected(c) if leg in sw.STREAM_LEGS else (sw.expected(c), None)
-    out[0].setflags(write=False)
-    return out
 
 
 def _pipe_runs(leg, hands_on=False):
@@ -47,10 +30,9 @@ def _pipe_runs(leg, hands_on=False):
 # ---- CPU ----
 
 def test_record_inputs_have_not_drifted():
-    with open(os.path.join(ROOT, "tests", "golden", "iir_sweep_record.json")) as f:
-        rec = json.load(f)["cases"]
+    rec = df.golden("iir_sweep_record.json")["cases"]
     C = sw.all_cases()
-    assert len(C) == len(rec) == len(_record())
+    assert len(C) == len(rec) == len(sw.record())
     for c, r in zip(C, rec):
         assert (c["name"], c["leg"], c["bps"], c["nch"], c["ns"], c["nblocks"]) == (r["name"], r["leg"], r["bps"], r["nch"], r["ns"], r["nblocks"])
         assert sw.crc(c["data"]) == r["in_crc32"], c["name"]
@@ -59,7 +41,7 @@ def test_record_inputs_have_not_drifted():
 @pytest.mark.parametrize("leg", sw.LEGS)
 def test_restatement_matches_reference(leg):
     for c in sw.sweep_cases()[leg]:
-        y, r = _want(leg, c["name"])[0], _record()[c["name"]]
+        y, r = sw.want(leg, c["name"])[0], sw.record()[c["name"]]
         assert digest(y) == r["digest"] and sw.crc(y) == r["crc32"], c["name"]
 
 
@@ -68,7 +50,7 @@ def test_single_leg_oracle_matches_reference(orc):
         bb = c["bps"] * c["nch"] * c["ns"]
         y = b"".join(orc.iir_prefilter(c["data"][b * bb : (b + 1) * bb], c["bps"], c["nch"], c["ns"], c["n"], c["d"], c["init"], shared_state=c["shared"])
                      for b in range(c["nblocks"]))
-        assert digest(np.frombuffer(y, dtype=np.uint8)) == _record()[c["name"]]["digest"], c["name"]
+        assert digest(np.frombuffer(y, dtype=np.uint8)) == sw.record()[c["name"]]["digest"], c["name"]
 
 
 @pytest.mark.parametrize("leg", sw.LEGS)
@@ -176,32 +158,8 @@ def test_non_finite_values_travel_through_a_cut_or_the_turn(leg):
 
 # ---- GPU ----
 
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
-
-def _guarded(nbytes, off=0, fill=None):
-    """(raw, view): a device buffer of nbytes at `off` bytes behind a guard, another guard behind it; the view holds `fill`"""
-    import torch
-
-    raw = torch.full((GUARD + off + nbytes + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    view = raw[GUARD + off : GUARD + off + nbytes]
-    if fill is not None:
-        view.fill_(fill)
-    return raw, view
-
-
-def _guards_untouched(raw, off, nbytes):
-    return int((raw[: GUARD + off] != FILL).count_nonzero()) == 0 and int((raw[GUARD + off + nbytes :] != FILL).count_nonzero()) == 0
-
-
 def _what(c):
-    """the whole case but its samples, as text (a failure message shows a string in full)"""
-    return "%s: %r" % (c["name"], {k: v for k, v in c.items() if k not in ("data", "name")})
+    return df.what(c, hide=("data",))
 
 
 def _call(pk, c, buf, state=None, work=None):
@@ -220,26 +178,25 @@ def _stateless_leg(api, leg):
     import torch
 
     for c in sw.sweep_cases()[leg]:
-        want, rec = _want(leg, c["name"])[0], _record()[c["name"]]
+        want, rec = sw.want(leg, c["name"])[0], sw.record()[c["name"]]
         pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
         n = c["data"].size
-        raw, buf = _guarded(n, c["off"])
+        raw, buf = df.guarded(n, c["off"], c["data"])
         assert buf.data_ptr() % 4 == c["off"]
-        buf.copy_(torch.from_numpy(np.array(c["data"])))
         wraw = work = None
         if leg == "zero_phase":
             wn = pk.iir_zero_phase_work_bytes(c["nblocks"])
             assert wn == (c["nblocks"] * c["nch"] + 63) // 64 * 64 * c["ns"] * 8
-            wraw, work = _guarded(wn, 0, 0xFF)  # exactly the bound, NaNs throughout
+            wraw, work = df.guarded(wn, 0, 0xFF)  # exactly the bound, NaNs throughout
             assert work.data_ptr() % 8 == 0
         _call(pk, c, buf, work=work)
         torch.cuda.synchronize()
         got = buf.cpu().numpy()
         assert digest(got) == rec["digest"], ("record", _what(c))
         assert np.array_equal(got, want), ("restatement", _what(c))
-        assert _guards_untouched(raw, c["off"], n), ("guards", _what(c))
+        assert df.guards_untouched(raw, c["off"], n), ("guards", _what(c))
         if wraw is not None:
-            assert _guards_untouched(wraw, 0, work.numel()), ("workspace guards", _what(c))
+            assert df.guards_untouched(wraw, 0, work.numel()), ("workspace guards", _what(c))
         pk.close()
 
 
@@ -258,35 +215,18 @@ def test_gpu_zero_phase_sweep(api):
     _stateless_leg(api, "zero_phase")
 
 
-def _same_doubles(a, b):
-    """bit for bit, but any NaN matches any NaN (payload and sign differ between x86 and the GPU)"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))))
-
-
-def _rings(state, c):
-    """a state's bytes by the layout rspt_hip.h documents: per channel, and per channel x section for the cascade,
-    double x[5], y[5]; uint64 started -> x, y as [nch][S][5] float64 and started as [nch][S] uint64"""
-    S = len(c["sections"])
-    raw = state.cpu().numpy()
-    assert raw.size == 88 * c["nch"] * S
-    words = raw.view(np.uint64).reshape(c["nch"], S, 11)
-    return words[:, :, 0:5].view(np.float64), words[:, :, 5:10].view(np.float64), words[:, :, 10]
-
-
 def _stream_leg(api, leg):
     import torch
 
     for c in sw.sweep_cases()[leg]:
-        (want, rings), rec = _want(leg, c["name"]), _record()[c["name"]]
+        (want, rings), rec = sw.want(leg, c["name"]), sw.record()[c["name"]]
         S = len(c["sections"])
         pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
         n, row = c["data"].size, c["bps"] * c["nch"]
         new_state = pk.iir_state if leg == "single_stream" else lambda: pk.iir_cascade_state(S)
         seen = []
         for how, calls in (("cut", c["calls"]), ("one_call", [c["rows"]])):
-            raw, buf = _guarded(n, c["off"])
-            buf.copy_(torch.from_numpy(np.array(c["data"])))
+            raw, buf = df.guarded(n, c["off"], c["data"])
             state = new_state()
             assert state.numel() == 88 * c["nch"] * S and int(state.count_nonzero()) == 0
             r0 = 0
@@ -298,19 +238,19 @@ def _stream_leg(api, leg):
             got = buf.cpu().numpy()
             assert digest(got) == rec["digest"], (how, "record", _what(c))
             assert np.array_equal(got, want), (how, "restatement", _what(c))
-            assert _guards_untouched(raw, c["off"], n), (how, "guards", _what(c))
-            x, y, started = _rings(state, c)
+            assert df.guards_untouched(raw, c["off"], n), (how, "guards", _what(c))
+            x, y, started = state_rings(state, c["nch"], S)
             assert (started == 1).all(), (how, "started", _what(c))
             for k, (mx, my) in enumerate(rings):  # the model's [nc][nch] against the state's first nc places
                 nc = mx.shape[0]
-                assert _same_doubles(x[:, k, :nc].T, mx), (how, "x ring of section %d" % k, _what(c))
-                assert _same_doubles(y[:, k, :nc].T, my), (how, "y ring of section %d" % k, _what(c))
+                assert same_doubles(x[:, k, :nc].T, mx), (how, "x ring of section %d" % k, _what(c))
+                assert same_doubles(y[:, k, :nc].T, my), (how, "y ring of section %d" % k, _what(c))
             seen.append((got, x, y))
         (g0, x0, y0), (g1, x1, y1) = seen  # however it is cut: the same output, the same first nc places
         assert np.array_equal(g0, g1), ("cut invariance", _what(c))
         for k, (mx, _) in enumerate(rings):
             nc = mx.shape[0]
-            assert _same_doubles(x0[:, k, :nc], x1[:, k, :nc]) and _same_doubles(y0[:, k, :nc], y1[:, k, :nc]), ("cut invariance of the rings", k, _what(c))
+            assert same_doubles(x0[:, k, :nc], x1[:, k, :nc]) and same_doubles(y0[:, k, :nc], y1[:, k, :nc]), ("cut invariance of the rings", k, _what(c))
         pk.close()
 
 

@@ -13,21 +13,17 @@ take five of the 64 residues mod its chunk.  Every residue, every (order, part, 
 history with every order are covered by the seeded sweep, tests/test_iir_sweep.py (leg zero_phase of tests/iir_sweep_cases.py)."""
 import ctypes as C
 import functools
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import devasm
+import devframe as df
 import iir_cases as ic
 import iir_zero_phase_cases as zc
 from cases import IIR_BANDPASS, digest
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRIES = ("rspt_hip_iir_zero_phase_work_bytes", "rspt_hip_iir_zero_phase_batch_dev")
 CHUNK = zc.CHUNK
 
@@ -37,8 +33,7 @@ NAMES = [c["name"] for c in CASES]
 
 @functools.lru_cache(maxsize=None)
 def _record():
-    with open(os.path.join(ROOT, "tests", "golden", "iir_zero_phase_record.json")) as f:
-        return json.load(f)
+    return df.golden("iir_zero_phase_record.json")
 
 
 @functools.lru_cache(maxsize=None)
@@ -143,31 +138,11 @@ def test_the_backward_history_changes_the_answer():
 
 
 def test_header_declares_the_entries_and_the_library_exports_them():
-    from rspt_amd import api, build
-
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
-    for decl in (
+    df.check_entries((
         "int rspt_hip_iir_zero_phase_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t* bytes);",
         "int rspt_hip_iir_zero_phase_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, size_t nr_coefficients, "
         "int init_nr_samples, int backward_init_nr_samples, void* d_work, size_t work_bytes, void* stream);",
-    ):
-        assert decl in hdr, decl
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    for name in ENTRIES:
-        assert re.search(r"\bT %s$" % name, out, re.M), name
-        assert name in api.C_ABI_SYMBOLS
-    assert hasattr(api.SignalPacker, "iir_zero_phase_work_bytes") and hasattr(api.SignalPacker, "iir_zero_phase_batch")
-
-
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
-FUSED = re.compile(r"^\s+(v_fma\w*_f(64|32)|v_fmac\w*_f(64|32)|v_mad\w*_f(64|32)|v_mac\w*_f(64|32)|v_pk_fma\w*|v_mfma\w*f64)\b")
+    ), ENTRIES, methods=("iir_zero_phase_work_bytes", "iir_zero_phase_batch"))
 
 
 def test_the_zero_phase_kernels_hold_no_fused_multiply_add(asm):
@@ -177,7 +152,7 @@ def test_the_zero_phase_kernels_hold_no_fused_multiply_add(asm):
     assert len(plain) == 16, sorted(plain)
     assert len(pipe) == 24, sorted(pipe)
     for n in plain + pipe:
-        assert not [ln for ln in asm[n] if FUSED.match(ln)], n
+        assert not [ln for ln in asm[n] if df.FUSED_F64_F32.match(ln)], n
         assert [ln for ln in asm[n] if re.match(r"^\s+v_mul_f64\b", ln)], n  # (the recurrence is in there, unfused)
 
 
@@ -195,14 +170,6 @@ def test_argument_checks_that_need_no_device():
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def _run(pk, c, buf=None, work=None):
     """the case's blocks through one call; -> the filtered bytes"""

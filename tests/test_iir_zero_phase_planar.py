@@ -11,23 +11,17 @@ of 0xFF bytes, a repeated call, both routes on the same data, the identity with 
 width and byte order, the pipeline into compress_planar_batch, the refusals, a foreign stream."""
 import ctypes as C
 import functools
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import cases
-import devasm
+import devframe as df
 import iir_zero_phase_planar_cases as zp
 from cases import digest
-from test_iir_zero_phase import FUSED
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD, FILL = 64, 0xA5
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRY = "rspt_hip_iir_zero_phase_planar_batch_dev"
 INT32_MIN = -(1 << 31)
 
@@ -37,8 +31,7 @@ RECORDED_NAMES, NATIVE_NAMES = [c["name"] for c in RECORDED], [c["name"] for c i
 
 @functools.lru_cache(maxsize=None)
 def _record(which):
-    with open(os.path.join(ROOT, "tests", "golden", "iir_zero_phase_%srecord.json" % which)) as f:
-        return json.load(f)["cases"]
+    return df.golden("iir_zero_phase_%srecord.json" % which)["cases"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -145,28 +138,15 @@ def test_the_width_and_native_cases_cover_what_they_are_for():
 
 
 def test_header_table_and_library_agree_on_the_entry():
-    from rspt_amd import api, build
+    from rspt_amd import api
 
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
-    decl = ("int rspt_hip_iir_zero_phase_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, int32_t* d_out, size_t nblocks, "
-            "const double* n, const double* d, size_t nr_coefficients, int init_nr_samples, int backward_init_nr_samples, void* d_work, "
-            "size_t work_bytes, void* stream);")
-    assert decl in hdr
-    out = subprocess.check_output(["nm", "-D", "--defined-only", build.build()]).decode()
-    assert re.search(r"\bT %s$" % ENTRY, out, re.M)
-    assert ENTRY in api.C_ABI_SYMBOLS and hasattr(api.lib(), ENTRY)
+    df.check_entries(("int rspt_hip_iir_zero_phase_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, int32_t* d_out, size_t nblocks, "
+                      "const double* n, const double* d, size_t nr_coefficients, int init_nr_samples, int backward_init_nr_samples, void* d_work, "
+                      "size_t work_bytes, void* stream);",), (ENTRY,), methods=("iir_zero_phase_planar_batch",))
     # the native entry's arguments with (source, destination) in place of the buffer; no sizing entry of its own
     native = api.C_ABI["rspt_hip_iir_zero_phase_batch_dev"]
     assert api.C_ABI[ENTRY] == (native[0], native[1][:1] + [C.c_void_p, C.c_void_p] + native[1][2:])
     assert not [s for s in api.C_ABI_SYMBOLS if "zero_phase_planar" in s and s != ENTRY]
-    assert hasattr(api.SignalPacker, "iir_zero_phase_planar_batch")
-
-
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
 
 
 def test_the_planar_zero_phase_kernels_hold_no_fused_multiply_add(asm):
@@ -175,7 +155,7 @@ def test_the_planar_zero_phase_kernels_hold_no_fused_multiply_add(asm):
         names = [n for n in asm if re.search(pat, n)]
         assert len(names) == 4, (pat, sorted(names))
         for n in names:
-            assert not [ln for ln in asm[n] if FUSED.match(ln)], n
+            assert not [ln for ln in asm[n] if df.FUSED_F64_F32.match(ln)], n
             assert [ln for ln in asm[n] if re.match(r"^\s+v_mul_f64\b", ln)], n  # (the recurrence is in there, unfused)
 
 
@@ -193,34 +173,8 @@ def test_argument_checks_that_need_no_device():
 
 # ---- GPU ----
 
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
-
-def _guarded(P, off, fill=None):
-    """(raw, view): P on the device as int32 [nblocks][nch][ns], `off` bytes past a 16-byte boundary, between two guards;
-    fill: the matrix is not P but these bytes (a destination)"""
-    import torch
-
-    n = P.size * 4
-    raw = torch.full((GUARD + off + n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    view = raw[GUARD + off : GUARD + off + n].view(torch.int32).reshape(P.shape)
-    assert view.data_ptr() % 16 == off and raw.data_ptr() % 16 == 0
-    if fill is None:
-        view.copy_(torch.from_numpy(np.array(P)))
-    return raw, view
-
-
-def _guards_untouched(raw, off, n):
-    return int((raw[: GUARD + off] != FILL).count_nonzero()) == 0 and int((raw[GUARD + off + n :] != FILL).count_nonzero()) == 0
-
-
 def _what(c):
-    return "%s: %r" % (c["name"], {k: v for k, v in c.items() if k not in ("planar", "name", "rec")})
+    return df.what(c, hide=("planar", "rec"))
 
 
 def _differ(got, want):
@@ -240,19 +194,19 @@ def _check(api, c, off=None, out_off=None, pk=None):
     want, n = _want(c["name"]), c["planar"].size * 4
     own = pk is None
     pk = pk or api.new_hzr(c["bps"], c["nch"], c["ns"])
-    raw, view = _guarded(c["planar"], off)
+    raw, view = df.guarded_matrix(c["planar"], off)
     if out_off is None:
         res = _call(pk, c, view)
         assert res is view
     else:
-        oraw, out = _guarded(c["planar"], out_off, fill=True)
+        oraw, out = df.guarded_matrix(c["planar"], out_off, fill=df.FILL)
         res = _call(pk, c, view, out=out)
         assert res is out
     torch.cuda.synchronize()
     got = res.cpu().numpy()
-    assert _guards_untouched(raw, off, n), ("guards", _what(c))
+    assert df.guards_untouched(raw, off, n), ("guards", _what(c))
     if out_off is not None:
-        assert _guards_untouched(oraw, out_off, n), ("guards of the destination", _what(c))
+        assert df.guards_untouched(oraw, out_off, n), ("guards of the destination", _what(c))
         assert np.array_equal(view.cpu().numpy(), c["planar"]), ("the source changed", _what(c))
     assert not _differ(got, want), (_differ(got, want), _what(c))
     assert _same_as_record(c, got), ("record", _what(c))
@@ -329,7 +283,7 @@ def test_gpu_nothing_of_the_workspace_is_read_before_it_is_written(api, name):
     assert nb == (c["nblocks"] * c["nch"] + 63) // 64 * 64 * c["ns"] * 8
     raw = torch.full((nb + 64,), 0xFF, dtype=torch.uint8, device="cuda")
     assert raw.data_ptr() % 8 == 0
-    _, view = _guarded(c["planar"], c["off"])
+    _, view = df.guarded_matrix(c["planar"], c["off"])
     _call(pk, c, view, work=raw[:nb])
     torch.cuda.synchronize()
     assert not _differ(view.cpu().numpy(), _want(name)), _what(c)
@@ -348,7 +302,7 @@ def test_gpu_a_repeated_call_gives_the_same_output(api, name):
     work = torch.empty(pk.iir_zero_phase_work_bytes(c["nblocks"]) // 8, dtype=torch.float64, device="cuda")
     outs = []
     for _ in range(2):
-        _, view = _guarded(c["planar"], c["off"])
+        _, view = df.guarded_matrix(c["planar"], c["off"])
         _call(pk, c, view, work=work)
         torch.cuda.synchronize()
         outs.append(view.cpu().numpy())
@@ -442,8 +396,8 @@ def test_gpu_the_entry_refuses_before_anything_is_launched(api):
     nch, ns = 3, 100
     pk = api.new_hzr(2, nch, ns)
     P = zp.block(2, nch, ns, 77)
-    raw, view = _guarded(P, 0)
-    oraw, out = _guarded(P, 4, fill=True)
+    raw, view = df.guarded_matrix(P, 0)
+    oraw, out = df.guarded_matrix(P, 4, fill=df.FILL)
     h, st = pk._h, torch.cuda.current_stream().cuda_stream
     need = pk.iir_zero_phase_work_bytes(2)
     assert need == 64 * ns * 8
@@ -493,7 +447,7 @@ def test_gpu_the_entry_refuses_before_anything_is_launched(api):
     assert call(o=out.data_ptr(), nc=5, init=1 << 14, binit=1 << 14, w=work.data_ptr() + 8) == 0
     torch.cuda.synchronize()
     assert not torch.equal(raw, before) and not torch.equal(oraw, obefore)  # (and a call that runs does show)
-    assert _guards_untouched(raw, 0, nbytes) and _guards_untouched(oraw, 4, nbytes)
+    assert df.guards_untouched(raw, 0, nbytes) and df.guards_untouched(oraw, 4, nbytes)
     pk.close()
 
 
@@ -505,10 +459,10 @@ def test_gpu_the_entry_runs_on_a_foreign_stream(api):
     for name, out_off in ((zp.NEIGHBOURS, None), ("ns103_i32_3ch_x2_nc5_init3_b0_plain", 8)):
         c = _case(name)
         pk = api.new_hzr(4, c["nch"], c["ns"])
-        raw, view = _guarded(c["planar"], c["off"])
-        out = None if out_off is None else _guarded(c["planar"], out_off, fill=True)[1]
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
+        out = None if out_off is None else df.guarded_matrix(c["planar"], out_off, fill=df.FILL)[1]
         s.wait_stream(torch.cuda.current_stream())
         res = _call(pk, c, view, out=out, stream=s.cuda_stream)
         s.synchronize()
-        assert not _differ(res.cpu().numpy(), _want(name)) and _guards_untouched(raw, c["off"], view.numel() * 4), _what(c)
+        assert not _differ(res.cpu().numpy(), _want(name)) and df.guards_untouched(raw, c["off"], view.numel() * 4), _what(c)
         pk.close()

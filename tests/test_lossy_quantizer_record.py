@@ -3,23 +3,20 @@
 constants, and against the numpy restatement of both quantisers (tests/lossy_quantizer_cases.py); and the new entry points'
 signatures."""
 import ctypes as C
-import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import devframe as df
 import lossy_quantizer_cases as lq
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from devframe import ROOT
 
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "lossy_quantizer_record.json")) as f:
-        r = json.load(f)
+    r = df.golden("lossy_quantizer_record.json")
     return {e["name"]: e for e in r["cases"]}, {e["name"]: e for e in r["defaults"]}
 
 
@@ -121,7 +118,7 @@ def test_the_fft_cases_stay_inside_the_gates_on_the_cpu(record):
 
 
 def test_the_quantizer_entry_points_have_the_stated_signatures():
-    from rspt_amd import api, build
+    from rspt_amd import api
 
     L = api.lib()
     assert api.C_ABI["rspt_hip_set_quantizer"] == (C.c_int, [C.c_void_p, C.c_double, C.c_uint])
@@ -136,7 +133,7 @@ def test_the_quantizer_entry_points_have_the_stated_signatures():
     assert "int rspt_hip_get_quantizer(const rspt_hip_packer* p, double* quality, unsigned* nb);" in head
     cxx = " ".join(re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "signal_packer.h")).read(), flags=re.S).split())
     assert 'extern "C" int rspt_cxx_set_quantizer(i_signal_packer* instance, double quality, unsigned nb);' in cxx
-    exported = subprocess.check_output(["nm", "-D", "--defined-only", build.LIB]).decode()
+    exported = df.exported()
     for name in ("rspt_hip_set_quantizer", "rspt_hip_get_quantizer", "rspt_cxx_set_quantizer"):
         assert re.search(r"\bT %s\b" % name, exported), name  # C linkage: the plain name
 

@@ -4,26 +4,22 @@ rolling_window_median.h), one object per channel, on the GPU: rspt_hip_median_fi
 CPU: the record's inputs, the reference's own test expectations, the numpy restatement (tests/median_cases.py) against the
 reference's answers (tests/golden/median_record.json), the integer even-window rule, and the C ABI.
 GPU (-m gpu): bit-exact against the record and the restatement, in place and out of place, in both regimes."""
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import devframe as df
 import median_cases as mc
 from cases import digest
+from devframe import ERR_ARG, api  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG = -1
 SHORT_MAX = 32  # kMedShortMax in rspt_amd/csrc/median.hip: the regime switch
 
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "median_record.json")) as f:
-        return json.load(f)
+    return df.golden("median_record.json")
 
 
 @pytest.fixture(scope="module")
@@ -99,25 +95,11 @@ def test_a_window_of_ns_or_more_is_the_expanding_median():
 
 
 def test_header_declares_the_entry_and_the_library_exports_it():
-    from rspt_amd import build
-
-    hdr = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
-    assert re.search(r"int\s+rspt_hip_median_filter_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,\s*void\s*\*\s*d_dst\s*,"
-                     r"\s*size_t\s+nblocks\s*,\s*size_t\s+window\s*,\s*void\s*\*\s*stream\s*\)", hdr)
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    assert re.search(r"\bT rspt_hip_median_filter_batch_dev$", out, re.M)
+    df.check_entries([re.compile(r"int\s+rspt_hip_median_filter_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,\s*void\s*\*\s*d_dst\s*,"
+                                 r"\s*size_t\s+nblocks\s*,\s*size_t\s+window\s*,\s*void\s*\*\s*stream\s*\)")], ["rspt_hip_median_filter_batch_dev"])
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def _batch(data, n):
     import torch

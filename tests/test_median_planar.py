@@ -7,35 +7,25 @@ GPU (-m gpu): the record cases, row ends, several spans per row, values, both re
 one piece of keys, the cross identities with the native entries and with compress_planar_batch, ordering, refusals, a foreign
 stream, a seeded sweep.  Every buffer and state sits between guards."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import devasm
+import devframe as df
 import median_cases as mc
 import median_planar_cases as pc
 import median_stream_cases as msc
 from cases import digest
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD, FILL = 64, 0xA5
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRIES = ("rspt_hip_median_filter_planar_batch_dev", "rspt_hip_median_planar_state_bytes", "rspt_hip_median_filter_planar_stream_dev")
-
-
-def _golden(name):
-    with open(os.path.join(ROOT, "tests", "golden", name)) as f:
-        return json.load(f)
 
 
 # ---- CPU ----
 
 def test_planar_expectation_cut_to_the_sample_width_is_the_median_record():
-    rec = _golden("median_record.json")["cases"]
+    rec = df.golden("median_record.json")["cases"]
     Cs = mc.median_cases()
     assert len(Cs) == len(rec) == 27
     for c, r in zip(Cs, rec):
@@ -48,7 +38,7 @@ def test_planar_expectation_cut_to_the_sample_width_is_the_median_record():
 
 
 def test_planar_stream_expectation_cut_to_the_sample_width_is_the_stream_record():
-    recs = {r["name"]: r for r in _golden("median_stream_record.json")["cases"]}
+    recs = {r["name"]: r for r in df.golden("median_stream_record.json")["cases"]}
     Cs = msc.stream_cases()
     assert len(Cs) == len(recs) == 45
     for c in Cs:
@@ -155,23 +145,13 @@ def test_regime_and_stream_cases_cover_what_they_claim():
 
 
 def test_header_table_and_library_agree_on_the_planar_entries():
-    from rspt_amd import api, build
-
-    hdr = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
-    flat = re.sub(r"\s+", " ", hdr)
-    for text in ("int rspt_hip_median_filter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
-                 "size_t window, void* stream);",
-                 "int rspt_hip_median_planar_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes);",
-                 "int rspt_hip_median_filter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
-                 "size_t window, void* d_state, void* stream);"):
-        assert text in flat, text
-    out = subprocess.check_output(["nm", "-D", "--defined-only", build.build()]).decode()
-    L = api.lib()
-    for name in ENTRIES:
-        assert re.search(r"\bT %s$" % name, out, re.M) and hasattr(L, name) and name in api.C_ABI_SYMBOLS, name
-        assert api.C_ABI[name] == api.C_ABI[name.replace("planar_", "")], name  # pointer types as the native siblings
-    for m in ("median_filter_planar_batch", "median_planar_state_bytes", "median_planar_state"):
-        assert callable(getattr(api.SignalPacker, m)), m
+    df.check_entries(("int rspt_hip_median_filter_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
+                      "size_t window, void* stream);",
+                      "int rspt_hip_median_planar_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes);",
+                      "int rspt_hip_median_filter_planar_stream_dev(rspt_hip_packer* p, const int32_t* d_src, int32_t* d_dst, size_t nblocks, "
+                      "size_t window, void* d_state, void* stream);"),
+                     ENTRIES, native_of={n: n.replace("planar_", "") for n in ENTRIES},  # pointer types as the native siblings
+                     methods=("median_filter_planar_batch", "median_planar_state_bytes", "median_planar_state"))
 
 
 def test_argument_checks_that_need_no_device():
@@ -187,129 +167,34 @@ def test_argument_checks_that_need_no_device():
     assert bytes(buf.raw) == bytes(4096)
 
 
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
 def test_no_new_kernel_uses_scratch(asm):
     """k_med_planar: four buckets, wide and dword; the gathering mover; the planar kernels of the sort and the walk"""
-    text = open(devasm.asm_path()).read()
     short = [n for n in asm if re.search(r"\d+k_med_planarILj", n)]
     assert len(short) == 8, sorted(n for n in asm if "k_med" in n)
     names = short + [n for n in asm if re.search(r"\d+k_medp_save", n)] + [n for n in asm if re.search(r"\d+k_medp_(tile_sort|walk)E", n)]
     assert len(names) == 11, names
-    for n in names:
-        m = re.search(r"^\s*\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(n), text, re.M | re.S)
-        assert m, n
-        assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", m.group(1)), n
-        assert not re.search(r"^\s+scratch_", "".join(asm[n]), re.M), n
+    df.uses_no_scratch(asm, names)
     wide = [n for n in short if re.search(r"global_load_dwordx4", "".join(asm[n])) and re.search(r"global_store_dwordx4", "".join(asm[n]))]
     assert len(wide) == 4  # the aligned instantiations
 
 
 # ---- GPU ----
 
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
-
-def _guarded_bytes(n, off, fill=None):
-    """(raw, view): n bytes on the device, `off` bytes past a 16-byte boundary, between two guards; view holds `fill` (bytes) or zeros"""
-    import torch
-
-    raw = torch.full((GUARD + off + n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    view = raw[GUARD + off : GUARD + off + n]
-    assert view.data_ptr() % 16 == off and raw.data_ptr() % 16 == 0
-    if fill is None:
-        view.zero_()
-    else:
-        view.copy_(torch.from_numpy(np.ascontiguousarray(fill).view(np.uint8).reshape(-1)))
-    return raw, view
-
-
-def _guarded(P, off):
-    """(raw, view): P on the device as int32 [nblocks][nch][ns], `off` bytes past a 16-byte boundary, between two guards"""
-    import torch
-
-    raw, view = _guarded_bytes(P.size * 4, off, np.array(P))
-    return raw, view.view(torch.int32).reshape(P.shape)
-
-
-def _guards_untouched(raw, off, n):
-    return int((raw[: GUARD + off] != FILL).count_nonzero()) == 0 and int((raw[GUARD + off + n :] != FILL).count_nonzero()) == 0
+def _what(c):
+    return df.what(c, hide=("planar",))
 
 
 def _clean(api, pk):
     return api.lib().rspt_hip_last_hip_error(pk._h) == 0
 
 
-def _what(c):
-    return "%s: %r" % (c["name"], {k: v for k, v in c.items() if k not in ("planar", "name")})
-
-
-def _run(api, c, calls="own", pk=None, states=None):
-    """c through the planar entry (calls: None stateless, else blocks per call on a fresh guarded state) -> (output, state bytes or
-    None); checks the guards and that an out-of-place source is only read.  states: a list that receives the state's bytes and
-    the output so far after every call."""
-    import torch
-
-    P, W, nch = c["planar"], c["W"], c["nch"]
-    calls = c["calls"] if calls == "own" else calls
-    own = pk is None
-    pk = pk or api.new_hzr(c["bps"], nch, c["ns"])
-    sraw, src = _guarded(P, c["src_off"])
-    if c["dst_off"] is None:
-        draw, dst = sraw, src
-    else:
-        draw, dst = _guarded(np.zeros_like(P), c["dst_off"])
-    state = None
-    if calls is None:
-        out = pk.median_filter_planar_batch(src, W, d_out=None if dst is src else dst)
-        assert out is dst
-    else:
-        nst = pk.median_planar_state_bytes(W)
-        assert nst == pc.state_bytes(W, nch)
-        straw, state = _guarded_bytes(nst, 8)
-        b0 = 0
-        for k in calls:
-            pk.median_filter_planar_batch(src[b0 : b0 + k], W, d_out=None if dst is src else dst[b0 : b0 + k], state=state)
-            b0 += k
-            if states is not None:
-                torch.cuda.synchronize()
-                states.append((b0, state.cpu().numpy(), dst[:b0].cpu().numpy()))
-        assert b0 == P.shape[0]
-    torch.cuda.synchronize()
-    got = dst.cpu().numpy()
-    assert _guards_untouched(sraw, c["src_off"], P.size * 4), ("source guards", _what(c))
-    if dst is not src:
-        assert _guards_untouched(draw, c["dst_off"], P.size * 4), ("destination guards", _what(c))
-        assert np.array_equal(src.cpu().numpy(), P), ("d_src is only read", _what(c))
-    sbytes = None
-    if state is not None:
-        assert _guards_untouched(straw, 8, nst), ("state guards", _what(c))
-        sbytes = state.cpu().numpy()
-    if own:
-        assert _clean(api, pk)
-        pk.close()
-    return got, sbytes
-
-
 def _check(api, c, want=None, image=None, calls="own", states=None):
+    """c through the planar entry between guards (devframe.planar_window), against the restatement -> (output, state bytes)"""
     if want is None:
         want, image = pc.expected(c)
-    got, sbytes = _run(api, c, calls, states=states)
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, ("output: %d differ, first at [block, channel, sample] %s" % (len(bad), bad[:1].tolist()), _what(c))
-    if sbytes is not None:
-        assert np.array_equal(sbytes, image), ("state", _what(c))
-    return got, sbytes
+    W = c["W"]
+    return df.planar_window(api, c, lambda pk, src, **kw: pk.median_filter_planar_batch(src, W, **kw), lambda pk: pk.median_planar_state_bytes(W),
+                            pc.state_bytes(W, c["nch"]), want, image, calls, states)
 
 
 @pytest.mark.gpu
@@ -357,7 +242,7 @@ def test_gpu_pads_ties_and_truncation_toward_zero(api):
 def test_gpu_values_outside_the_sample_width_are_taken_whole_and_stored_uncut(api):
     for c in pc.width_cases():
         got, sbytes = _check(api, c)
-        got4, sbytes4 = _run(api, dict(c, bps=4))  # the handle's bps has no effect
+        got4, sbytes4 = _check(api, dict(c, bps=4))  # the handle's bps has no effect
         assert np.array_equal(got, got4) and (sbytes is None or np.array_equal(sbytes, sbytes4)), _what(c)
 
 
@@ -375,7 +260,7 @@ def test_gpu_generic_window_on_the_longest_row_and_refused_beyond_it(api):
     P = pc.block(1, 1, ns, 2950, 1 << 24)
     _check(api, dict(name="ranks_limit", nch=1, ns=ns, nblocks=1, planar=P, W=33, src_off=0, dst_off=None, calls=None, bps=4), pc.stateless_expected(P, 33))
     pk = api.new_hzr(4, 1, ns + 1)
-    raw, view = _guarded(np.zeros((1, 1, ns + 1), dtype=np.int32), 0)
+    raw, view = df.guarded_matrix(np.zeros((1, 1, ns + 1), dtype=np.int32))
     before = raw.clone()
     st = torch.cuda.current_stream().cuda_stream
     assert api.lib().rspt_hip_median_filter_planar_batch_dev(pk._h, view.data_ptr(), view.data_ptr(), 1, 33, st) == ERR_UNSUPPORTED
@@ -495,10 +380,10 @@ def test_gpu_native_and_planar_calls_alternate_on_one_state(api):
                     rec[b0 : b0 + n] = buf.cpu().numpy()
                 else:
                     rows = rec[b0 : b0 + n].reshape(-1).view("<i4").reshape(n * ns, nch)
-                    raw, view = _guarded(pc.planar_of(rows, n, nch, ns), 4)
+                    raw, view = df.guarded_matrix(pc.planar_of(rows, n, nch, ns), 4)
                     pk.median_filter_planar_batch(view, W, state=state)
                     torch.cuda.synchronize()
-                    assert _guards_untouched(raw, 4, view.numel() * 4)
+                    assert df.guards_untouched(raw, 4, view.numel() * 4)
                     rec[b0 : b0 + n] = pc.native_of(view.cpu().numpy()).reshape(n, bb)
                 b0 += n
             assert np.array_equal(rec.reshape(-1), pc.native_of(model)) and np.array_equal(state.cpu().numpy(), image), (W, plan)
@@ -566,11 +451,11 @@ def test_gpu_planar_entries_refuse_bad_arguments_and_write_nothing(api):
     nch, ns = 3, 100
     pk = api.new_hzr(2, nch, ns)
     P = pc.block(4, nch, ns, 2990)
-    raw, view = _guarded(P, 0)
+    raw, view = df.guarded_matrix(P, 0)
     before = raw.clone()
     n = P.size * 4 // 2  # bytes of two blocks
     h, st = pk._h, torch.cuda.current_stream().cuda_stream
-    straw, state = _guarded_bytes(pk.median_planar_state_bytes((1 << 17) + 1), 8)
+    straw, state = df.guarded(pk.median_planar_state_bytes((1 << 17) + 1), 8, fill=0)
     sbefore = straw.clone()
     base = view.data_ptr()
 
@@ -612,7 +497,7 @@ def test_gpu_planar_entries_refuse_bad_arguments_and_write_nothing(api):
     torch.cuda.synchronize()
     got = view.cpu().numpy()
     assert np.array_equal(got[2:], pc.stream_expected(P[:2], (1 << 17) + 1)[0]) and np.array_equal(got[:2], pc.stateless_expected(P[:2], 1 << 40))
-    assert _guards_untouched(raw, 0, P.size * 4) and _guards_untouched(straw, 8, state.numel())
+    assert df.guards_untouched(raw, 0, P.size * 4) and df.guards_untouched(straw, 8, state.numel())
     pk.close()
 
 
@@ -627,8 +512,8 @@ def test_gpu_planar_entries_run_on_a_foreign_stream(api):
     for c in picks:
         want = pc.expected(c)[0]
         pk = api.new_hzr(4, c["nch"], c["ns"])
-        raw, src = _guarded(c["planar"], c["src_off"])
-        draw, dst = (raw, src) if c["dst_off"] is None else _guarded(np.zeros_like(c["planar"]), c["dst_off"])
+        raw, src = df.guarded_matrix(c["planar"], c["src_off"])
+        draw, dst = (raw, src) if c["dst_off"] is None else df.guarded_matrix(c["planar"], c["dst_off"], fill=0)
         state = pk.median_planar_state(c["W"]) if c["calls"] else None
         s.wait_stream(torch.cuda.current_stream())
         b0 = 0
@@ -637,7 +522,7 @@ def test_gpu_planar_entries_run_on_a_foreign_stream(api):
             b0 += k
         s.synchronize()
         off = c["src_off"] if dst is src else c["dst_off"]
-        assert np.array_equal(dst.cpu().numpy(), want) and _guards_untouched(draw, off, dst.numel() * 4), _what(c)
+        assert np.array_equal(dst.cpu().numpy(), want) and df.guards_untouched(draw, off, dst.numel() * 4), _what(c)
         pk.close()
 
 

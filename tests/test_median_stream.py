@@ -8,21 +8,17 @@ GPU (-m gpu): every case bit-exact against the record and the restatement howeve
 out of place, the state's bytes, the equivalence with the stateless stage, that the state is used, and the statuses."""
 import ctypes as C
 import functools
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import devasm
+import devframe as df
 import median_cases as mc
 import median_stream_cases as msc
 from cases import digest
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRIES = ("rspt_hip_median_state_bytes", "rspt_hip_median_filter_stream_dev")
 
 CASES = msc.stream_cases()
@@ -32,8 +28,7 @@ BY_NAME = {c["name"]: c for c in CASES}
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "median_stream_record.json")) as f:
-        return {r["name"]: r for r in json.load(f)["cases"]}
+    return {r["name"]: r for r in df.golden("median_stream_record.json")["cases"]}
 
 
 @functools.lru_cache(maxsize=None)
@@ -111,24 +106,15 @@ def test_state_layout_restatement():
 
 
 def test_header_declares_the_entries_and_the_library_exports_them():
-    from rspt_amd import api, build
-
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
-    for decl in (
+    df.check_entries((
         "int rspt_hip_median_state_bytes(rspt_hip_packer* p, size_t window, size_t* bytes);",
         "int rspt_hip_median_filter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, "
         "void* d_state, void* stream);",
-    ):
-        assert decl in hdr, decl
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    for name in ENTRIES:
-        assert re.search(r"\bT %s$" % name, out, re.M), name
-        assert name in api.C_ABI_SYMBOLS
+    ), ENTRIES)
 
 
 def test_the_stateless_entry_keeps_its_signature():
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
+    hdr = df.header()
     assert "int rspt_hip_median_filter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, size_t window, void* stream);" in hdr
 
 
@@ -142,13 +128,6 @@ def test_argument_checks_that_need_no_device():
     state = C.create_string_buffer(4096)
     sp = (C.addressof(state) + 7) & ~7
     assert L.rspt_hip_median_filter_stream_dev(None, sp, sp, 1, 5, sp, None) == ERR_ARG
-
-
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
 
 
 FP = re.compile(r"^\s+(v_\w+_f(64|32|16)\w*|v_pk_\w+_f(32|16)\w*|v_mfma\w*|v_fma\w*|v_fmac\w*|v_mad\w*_f\w+|v_mac\w*_f\w+)\b")
@@ -187,25 +166,12 @@ def test_the_kernel_instantiations(asm):
 
 def test_the_widest_short_kernel_with_a_head_uses_no_scratch(asm):
     """k_med_short<32, ..., HEAD = true>: its 32-slot window stays in registers"""
-    text = open(devasm.asm_path()).read()
     names = [n for n in asm if re.search(r"11k_med_shortILj32E", n) and n.split("ELb")[-1].startswith("1")]
     assert len(names) == 6, names
-    for n in names:
-        m = re.search(r"^\s*\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(n), text, re.M | re.S)
-        assert m, n
-        assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", m.group(1)), n
-        assert not [ln for ln in asm[n] if re.match(r"^\s+scratch_", ln)], n
+    df.uses_no_scratch(asm, names)
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def _drive(pk, W, data, split, state, out_of_place=False, sync=False):
     """the recording through successive calls of split[i] blocks each; -> (filtered recording, source afterwards) as bytes"""

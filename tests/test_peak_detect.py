@@ -6,25 +6,21 @@ CPU: the record's inputs, the numpy restatement (tests/peak_cases.py) against th
 (tests/golden/peak_record.json), the designer through ctypes, the C ABI, and the kernels' ISA (no fused multiply-add).
 GPU (-m gpu): bit-exact against the record and the restatement, fresh and stateful, with and without traces."""
 import ctypes as C
-import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import devasm
+import devframe as df
 import peak_cases as pc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG = -1
+from devframe import ERR_ARG, api  # noqa: F401
 
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "peak_record.json")) as f:
-        return json.load(f)
+    return df.golden("peak_record.json")
 
 
 @pytest.fixture(scope="module")
@@ -141,20 +137,15 @@ def test_api_design_iir():
 
 
 def test_header_declares_the_entries_and_the_library_exports_them():
-    from rspt_amd import build
-
-    hdr = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
-    assert re.search(r"int\s+rspt_hip_design_iir\s*\(\s*int\s+type\s*,\s*int\s+order\s*,\s*double\s+sampling_rate\s*,\s*double\s+cutoff_low\s*,"
-                     r"\s*double\s+cutoff_high\s*,\s*double\s*\*\s*num\s*,\s*double\s*\*\s*den\s*,\s*size_t\s*\*\s*nr_coefficients\s*\)", hdr)
-    assert re.search(r"int\s+rspt_hip_peak_state_bytes\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*size_t\s*\*\s*bytes\s*\)", hdr)
-    assert re.search(r"int\s+rspt_hip_peak_detect_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,\s*size_t\s+nblocks\s*,"
-                     r"\s*int\s+variant\s*,\s*double\s+sampling_rate\s*,\s*double\s+marker_val\s*,\s*void\s*\*\s*d_state\s*,\s*uint32_t\s*\*\s*d_count\s*,"
-                     r"\s*int32_t\s*\*\s*d_index\s*,\s*double\s*\*\s*d_value\s*,\s*size_t\s+max_peaks\s*,\s*double\s*\*\s*d_sig\s*,"
-                     r"\s*double\s*\*\s*d_threshold\s*,\s*void\s*\*\s*stream\s*\)", hdr)
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    for n in ("rspt_hip_design_iir", "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev"):
-        assert re.search(r"\bT %s$" % n, out, re.M), n
+    df.check_entries([
+        re.compile(r"int\s+rspt_hip_design_iir\s*\(\s*int\s+type\s*,\s*int\s+order\s*,\s*double\s+sampling_rate\s*,\s*double\s+cutoff_low\s*,"
+                   r"\s*double\s+cutoff_high\s*,\s*double\s*\*\s*num\s*,\s*double\s*\*\s*den\s*,\s*size_t\s*\*\s*nr_coefficients\s*\)"),
+        re.compile(r"int\s+rspt_hip_peak_state_bytes\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*size_t\s*\*\s*bytes\s*\)"),
+        re.compile(r"int\s+rspt_hip_peak_detect_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,\s*size_t\s+nblocks\s*,"
+                   r"\s*int\s+variant\s*,\s*double\s+sampling_rate\s*,\s*double\s+marker_val\s*,\s*void\s*\*\s*d_state\s*,\s*uint32_t\s*\*\s*d_count\s*,"
+                   r"\s*int32_t\s*\*\s*d_index\s*,\s*double\s*\*\s*d_value\s*,\s*size_t\s+max_peaks\s*,\s*double\s*\*\s*d_sig\s*,"
+                   r"\s*double\s*\*\s*d_threshold\s*,\s*void\s*\*\s*stream\s*\)"),
+    ], ("rspt_hip_design_iir", "rspt_hip_peak_state_bytes", "rspt_hip_peak_detect_batch_dev"))
 
 
 @pytest.fixture(scope="module")
@@ -167,25 +158,12 @@ def peak_asm():
 def test_peak_kernels_round_every_product_and_sum_on_their_own(peak_asm):
     """no fused multiply-add and no f64 MFMA in any k_peak kernel (or device function of it); each multiplies and adds with
     v_mul_f64 and v_add_f64"""
-    kernels = [n for n in peak_asm if re.search(r"6k_peakIL", n)]
-    assert len(kernels) == 24, sorted(peak_asm)  # 4 widths x 3 variants x traces on / off
-    bad = re.compile(r"^\s+(v_fma\w*_f64|v_fmac\w*_f64|v_mad\w*_f64|v_mfma\w*f64)\b")
+    df.rounds_separately(peak_asm, r"6k_peakIL", 24, fused=df.FUSED_F64)  # 4 widths x 3 variants x traces on / off
     for n, body in peak_asm.items():
-        assert not [ln for ln in body if bad.match(ln)], n
-    for n in kernels:
-        text = "".join(peak_asm[n])
-        assert re.search(r"^\s+v_mul_f64\b", text, re.M) and re.search(r"^\s+v_add_f64\b", text, re.M), n
+        assert not [ln for ln in body if df.FUSED_F64.match(ln)], n
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def gpu_result(pk, src, variant, fs, marker=1.0, max_peaks=None, state=None, traces=True):
     """run the stage and bring back what pc.detect returns (index / value lists cut at max_peaks)"""

@@ -4,26 +4,22 @@
 CPU: the record's inputs, the numpy restatement (tests/peak_offline_cases.py) against the reference's answers
 (tests/golden/peak_offline_record.json), the C ABI, and the kernel's ISA (no fused multiply-add).
 GPU (-m gpu): bit-exact against the record and the restatement, fresh and stateful, with and without traces."""
-import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import devasm
+import devframe as df
 import peak_cases as pc
 import peak_offline_cases as oc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG = -1
+from devframe import ERR_ARG, api  # noqa: F401
 
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "peak_offline_record.json")) as f:
-        return json.load(f)
+    return df.golden("peak_offline_record.json")
 
 
 @pytest.fixture(scope="module")
@@ -93,19 +89,14 @@ def test_restatement_matches_reference(ocases, name):
 
 
 def test_header_declares_the_entries_and_the_library_exports_them():
-    from rspt_amd import build
-
-    hdr = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
-    assert re.search(r"int\s+rspt_hip_peak_offline_work_bytes\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*size_t\s+nblocks\s*,\s*int\s+stateful\s*,"
-                     r"\s*size_t\s*\*\s*bytes\s*\)", hdr)
-    assert re.search(r"int\s+rspt_hip_peak_detect_offline_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,"
-                     r"\s*size_t\s+nblocks\s*,\s*double\s+sampling_rate\s*,\s*double\s+marker_val\s*,\s*void\s*\*\s*d_state\s*,"
-                     r"\s*void\s*\*\s*d_work\s*,\s*uint32_t\s*\*\s*d_count\s*,\s*int32_t\s*\*\s*d_index\s*,\s*double\s*\*\s*d_value\s*,"
-                     r"\s*size_t\s+max_peaks\s*,\s*double\s*\*\s*d_sig\s*,\s*double\s*\*\s*d_threshold\s*,\s*void\s*\*\s*stream\s*\)", hdr)
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    for n in ("rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev"):
-        assert re.search(r"\bT %s$" % n, out, re.M), n
+    df.check_entries([
+        re.compile(r"int\s+rspt_hip_peak_offline_work_bytes\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*size_t\s+nblocks\s*,\s*int\s+stateful\s*,"
+                   r"\s*size_t\s*\*\s*bytes\s*\)"),
+        re.compile(r"int\s+rspt_hip_peak_detect_offline_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+void\s*\*\s*d_src\s*,"
+                   r"\s*size_t\s+nblocks\s*,\s*double\s+sampling_rate\s*,\s*double\s+marker_val\s*,\s*void\s*\*\s*d_state\s*,"
+                   r"\s*void\s*\*\s*d_work\s*,\s*uint32_t\s*\*\s*d_count\s*,\s*int32_t\s*\*\s*d_index\s*,\s*double\s*\*\s*d_value\s*,"
+                   r"\s*size_t\s+max_peaks\s*,\s*double\s*\*\s*d_sig\s*,\s*double\s*\*\s*d_threshold\s*,\s*void\s*\*\s*stream\s*\)"),
+    ], ("rspt_hip_peak_offline_work_bytes", "rspt_hip_peak_detect_offline_batch_dev"))
 
 
 def test_work_bytes_refuses_a_null_handle():
@@ -129,26 +120,14 @@ def offline_asm():
 def test_offline_kernels_round_every_product_and_sum_on_their_own(offline_asm):
     """no fused multiply-add and no f64 MFMA in any k_peak_offline kernel; each multiplies and adds with v_mul_f64 and
     v_add_f64, and nothing spills to scratch"""
-    kernels = [n for n in offline_asm if re.search(r"14k_peak_offlineIL", n)]
-    assert len(kernels) == 8, sorted(offline_asm)  # 4 widths x traces on / off
-    bad = re.compile(r"^\s+(v_fma\w*_f64|v_fmac\w*_f64|v_mad\w*_f64|v_mfma\w*f64)\b")
+    kernels = df.rounds_separately(offline_asm, r"14k_peak_offlineIL", 8, fused=df.FUSED_F64)  # 4 widths x traces on / off
     for n, body in offline_asm.items():
-        assert not [ln for ln in body if bad.match(ln)], n
+        assert not [ln for ln in body if df.FUSED_F64.match(ln)], n
     for n in kernels:
-        text = "".join(offline_asm[n])
-        assert re.search(r"^\s+v_mul_f64\b", text, re.M) and re.search(r"^\s+v_add_f64\b", text, re.M), n
-        assert not re.search(r"^\s+scratch_store", text, re.M), n
+        assert not re.search(r"^\s+scratch_store", "".join(offline_asm[n]), re.M), n
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def gpu_result(pk, src, fs, marker=1.0, max_peaks=None, state=None, traces=True):
     import torch

@@ -8,24 +8,18 @@ GPU (-m gpu): bit-exact against the record on every case, the identity with the 
 carried state, the workspace, streams, refusals and the pipeline behind the planar zero-phase filter."""
 import ctypes as C
 import functools
-import json
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import cases
-import devasm
+import devframe as df
 import peak_cases as pc
 import peak_offline_cases as oc
 import peak_planar_cases as pp
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ONLINE_ENTRY, OFFLINE_ENTRY = "rspt_hip_peak_detect_planar_batch_dev", "rspt_hip_peak_detect_offline_planar_batch_dev"
-FUSED = re.compile(r"^\s+(v_fma\w*_f64|v_fmac\w*_f64|v_mad\w*_f64|v_mfma\w*f64)\b")
 
 CASES = pp.recorded_cases()
 NAMES = [c["name"] for c in CASES]
@@ -34,8 +28,7 @@ BY_NAME = {c["name"]: c for c in CASES}
 
 @functools.lru_cache(maxsize=None)
 def _golden(which):
-    with open(os.path.join(ROOT, "tests", "golden", which)) as f:
-        return {r["name"]: r for r in json.load(f)["cases"]}
+    return {r["name"]: r for r in df.golden(which)["cases"]}
 
 
 def _rec(name):
@@ -131,22 +124,16 @@ def test_cut_to_the_handles_width_the_answer_is_another(name):
 
 
 def test_header_table_and_library_agree_on_both_entries():
-    from rspt_amd import api, build
-
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
-    assert ("int rspt_hip_peak_detect_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, int variant, double sampling_rate, "
-            "double marker_val, void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, "
-            "double* d_threshold, void* stream);") in hdr
-    assert ("int rspt_hip_peak_detect_offline_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, double sampling_rate, "
-            "double marker_val, void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, "
-            "double* d_sig, double* d_threshold, void* stream);") in hdr
-    assert "stay native-only" not in hdr.replace("(compress, _many, the feed) stay native-only", "")
-    out = subprocess.check_output(["nm", "-D", "--defined-only", build.build()]).decode()
-    for entry, native in ((ONLINE_ENTRY, "rspt_hip_peak_detect_batch_dev"), (OFFLINE_ENTRY, "rspt_hip_peak_detect_offline_batch_dev")):
-        assert re.search(r"\bT %s$" % entry, out, re.M), entry
-        assert entry in api.C_ABI_SYMBOLS and hasattr(api.lib(), entry)
-        assert api.C_ABI[entry] == api.C_ABI[native]  # (the native sibling's arguments, the matrix in place of the batch)
-    assert hasattr(api.SignalPacker, "peak_detect_planar_batch") and hasattr(api.SignalPacker, "peak_detect_offline_planar_batch")
+    df.check_entries(("int rspt_hip_peak_detect_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, int variant, double sampling_rate, "
+                      "double marker_val, void* d_state, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, double* d_sig, "
+                      "double* d_threshold, void* stream);",
+                      "int rspt_hip_peak_detect_offline_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, double sampling_rate, "
+                      "double marker_val, void* d_state, void* d_work, uint32_t* d_count, int32_t* d_index, double* d_value, size_t max_peaks, "
+                      "double* d_sig, double* d_threshold, void* stream);"),
+                     (ONLINE_ENTRY, OFFLINE_ENTRY),  # (the native sibling's arguments, the matrix in place of the batch)
+                     native_of={ONLINE_ENTRY: "rspt_hip_peak_detect_batch_dev", OFFLINE_ENTRY: "rspt_hip_peak_detect_offline_batch_dev"},
+                     methods=("peak_detect_planar_batch", "peak_detect_offline_planar_batch"))
+    assert "stay native-only" not in df.header().replace("(compress, _many, the feed) stay native-only", "")
 
 
 def test_argument_checks_that_need_no_device():
@@ -161,65 +148,14 @@ def test_argument_checks_that_need_no_device():
     assert buf.raw == bytes(4096)
 
 
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
 def test_the_planar_peak_kernels_hold_no_fused_multiply_add(asm):
     """k_peak_planar (3 variants x traces on / off) and k_peak_offline_planar (traces on / off): every product and sum with
     v_mul_f64 and v_add_f64, as in the native kernels"""
     for pat, n in ((r"13k_peak_planarIL", 6), (r"21k_peak_offline_planarIL", 2)):
-        names = [f for f in asm if re.search(pat, f)]
-        assert len(names) == n, (pat, sorted(names))
-        for f in names:
-            assert not [ln for ln in asm[f] if FUSED.match(ln)], f
-            text = "".join(asm[f])
-            assert re.search(r"^\s+v_mul_f64\b", text, re.M) and re.search(r"^\s+v_add_f64\b", text, re.M), f
+        df.rounds_separately(asm, pat, n, fused=df.FUSED_F64)
 
 
 # ---- GPU ----
-
-GUARD = 256  # bytes in front of and behind every buffer of a call
-FILL = 0xA5
-
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
-
-def _guarded(nbytes, off=0, fill=FILL):
-    """(raw, view): nbytes of uint8 on the device, `off` bytes past a 16-byte boundary, between two guards of FILL"""
-    import torch
-
-    raw = torch.full((GUARD + off + nbytes + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    view = raw[GUARD + off : GUARD + off + nbytes]
-    assert raw.data_ptr() % 16 == 0
-    if fill != FILL:
-        view.fill_(fill)
-    return raw, view
-
-
-def _guards_untouched(raw, off, n):
-    return int((raw[: GUARD + off] != FILL).count_nonzero()) == 0 and int((raw[GUARD + off + n :] != FILL).count_nonzero()) == 0
-
-
-def _matrix(P, off):
-    """(raw, view): P on the device as int32 [nblocks][nch][ns], `off` bytes past a 16-byte boundary, between guards"""
-    import torch
-
-    raw, v = _guarded(P.size * 4, off)
-    view = v.view(torch.int32).reshape(P.shape)
-    view.copy_(torch.from_numpy(np.array(P)))
-    assert view.data_ptr() % 16 == off
-    return raw, view
-
 
 def _run(api, pk, c, view, marker=1.0, max_peaks=None, traces=True, state=None, work_fill=0xFF, stream=None, kind=None, variant=None,
          trace_off=8):
@@ -235,11 +171,11 @@ def _run(api, pk, c, view, marker=1.0, max_peaks=None, traces=True, state=None, 
     mp = ns if max_peaks is None else max_peaks
     L = api.lib()
     st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    craw, count = _guarded(rows * 4)
-    iraw, index = _guarded(rows * mp * 4)
-    vraw, value = _guarded(rows * mp * 8)
-    sraw, sig = _guarded(rows * ns * 8 if traces else 0, trace_off)
-    hraw, thr = _guarded(rows * ns * 8 if traces else 0, trace_off)
+    craw, count = df.guarded(rows * 4)
+    iraw, index = df.guarded(rows * mp * 4)
+    vraw, value = df.guarded(rows * mp * 8)
+    sraw, sig = df.guarded(rows * ns * 8 if traces else 0, trace_off)
+    hraw, thr = df.guarded(rows * ns * 8 if traces else 0, trace_off)
     ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
     sp = state.data_ptr() if state is not None else None
     if kind == "online":
@@ -247,7 +183,7 @@ def _run(api, pk, c, view, marker=1.0, max_peaks=None, traces=True, state=None, 
                                                      ptr(value), mp, ptr(sig), ptr(thr), st)
     else:
         wb = pk.peak_offline_work_bytes(nblocks, state is not None)
-        wraw, work = _guarded(wb, 0, work_fill)
+        wraw, work = df.guarded(wb, 0, work_fill)
         rc = L.rspt_hip_peak_detect_offline_planar_batch_dev(pk._h, view.data_ptr(), nblocks, c["fs"], marker, sp, work.data_ptr(), count.data_ptr(),
                                                              ptr(index), ptr(value), mp, ptr(sig), ptr(thr), st)
     assert rc == 0, (rc, c["name"])
@@ -256,10 +192,10 @@ def _run(api, pk, c, view, marker=1.0, max_peaks=None, traces=True, state=None, 
     else:
         torch.cuda.ExternalStream(stream).synchronize()
     what = (c["name"], kind, marker, max_peaks, traces)
-    assert _guards_untouched(craw, 0, rows * 4) and _guards_untouched(iraw, 0, rows * mp * 4) and _guards_untouched(vraw, 0, rows * mp * 8), what
-    assert _guards_untouched(sraw, trace_off, sig.numel()) and _guards_untouched(hraw, trace_off, thr.numel()), what
+    assert df.guards_untouched(craw, 0, rows * 4) and df.guards_untouched(iraw, 0, rows * mp * 4) and df.guards_untouched(vraw, 0, rows * mp * 8), what
+    assert df.guards_untouched(sraw, trace_off, sig.numel()) and df.guards_untouched(hraw, trace_off, thr.numel()), what
     if kind == "offline":
-        assert _guards_untouched(wraw, 0, wb), what
+        assert df.guards_untouched(wraw, 0, wb), what
     out = [count.view(torch.int32).reshape(nblocks, nch), index.view(torch.int32).reshape(nblocks, nch, mp), value.view(torch.float64).reshape(nblocks, nch, mp)]
     if traces:
         out += [t.view(torch.float64).reshape(nblocks, nch, ns).transpose(1, 2).contiguous() for t in (sig, thr)]
@@ -270,7 +206,7 @@ def _check_case(api, c, want, off=None, keys=pp.RECORD_KEYS):
     """c on a matrix at `off`, marker 1.0 with traces and marker -1.0 without, against the record fields `want`"""
     off = c["off"] if off is None else off
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    raw, view = _matrix(c["planar"], off)
+    raw, view = df.guarded_matrix(c["planar"], off)
     before = raw.clone()
     new_state = (lambda: pk.peak_state()) if c["stateful"] else (lambda: None)
     if c["calls"] is None:
@@ -367,7 +303,7 @@ def test_gpu_markers_max_peaks_and_traces(api, name):
     c = BY_NAME[name]
     assert c["calls"] is None
     pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-    raw, view = _matrix(c["planar"], c["off"])
+    raw, view = df.guarded_matrix(c["planar"], c["off"])
     for marker in pp.MARKERS:
         want = _restated(name, marker)
         assert max(pc.flat([want["count"]])) > 1
@@ -401,12 +337,12 @@ def test_gpu_a_row_run_alone_leaves_its_neighbouring_trace_rows_untouched(api):
         ns, rows = c["ns"], c["nblocks"] * c["nch"]
         whole = _restated(name, 1.0)
         pk = api.new_hzr(4, 1, ns)
-        raw, view = _matrix(c["planar"], c["off"])
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
         for toff in (0, 8):
-            traws = [_guarded(rows * ns * 8, toff) for _ in range(2)]
+            traws = [df.guarded(rows * ns * 8, toff) for _ in range(2)]
             for r in range(rows):
                 b, ch = divmod(r, c["nch"])
-                craw, count = _guarded(4)
+                craw, count = df.guarded(4)
                 src = view.reshape(rows, ns)[r].data_ptr()
                 sp, hp = (t[1].data_ptr() + r * ns * 8 for t in traws)
                 st = torch.cuda.current_stream().cuda_stream
@@ -417,13 +353,13 @@ def test_gpu_a_row_run_alone_leaves_its_neighbouring_trace_rows_untouched(api):
                     rc = L.rspt_hip_peak_detect_offline_planar_batch_dev(pk._h, src, 1, c["fs"], 1.0, None, work.data_ptr(), count.data_ptr(), None, None, 0,
                                                                          sp, hp, st)
                 torch.cuda.synchronize()
-                assert rc == 0 and _guards_untouched(craw, 0, 4) and int(count.view(torch.int32)[0]) == whole["count"][b][ch], (name, r)
+                assert rc == 0 and df.guards_untouched(craw, 0, 4) and int(count.view(torch.int32)[0]) == whole["count"][b][ch], (name, r)
                 for (traw, t), key in zip(traws, ("sig", "thr")):
                     got = t.view(torch.float64).reshape(rows, ns)
-                    assert _guards_untouched(traw, toff, rows * ns * 8), (name, r, toff)
+                    assert df.guards_untouched(traw, toff, rows * ns * 8), (name, r, toff)
                     assert np.array_equal(pc.canon(got[r].cpu().numpy()), pc.canon(whole[key][b, :, ch])), (name, r, toff, key)
                     later = t.reshape(rows, ns * 8)[r + 1 :]
-                    assert int((later != FILL).count_nonzero()) == 0, (name, r, toff, key)  # (earlier rows hold their own traces)
+                    assert int((later != df.FILL).count_nonzero()) == 0, (name, r, toff, key)  # (earlier rows hold their own traces)
         pk.close()
 
 
@@ -452,7 +388,7 @@ def test_gpu_any_cut_of_a_recording_equals_the_uncut_run(api, variant):
                         value=[[[v for b in range(nb) for v in w["value"][b][ch]] for ch in range(nch)]], sig=w["sig"].reshape(1, total, nch),
                         thr=w["thr"].reshape(1, total, nch))
         pk = api.new_hzr(2, nch, ns)
-        raw, view = _matrix(P, 4 * (ns % 4))
+        raw, view = df.guarded_matrix(P, 4 * (ns % 4))
         st, parts, b0 = pk.peak_state(), [], 0
         for n in calls:
             parts.append(_run(api, pk, c, view[b0 : b0 + n], -1.0, state=st))
@@ -480,7 +416,7 @@ def test_gpu_one_state_alternates_between_native_and_planar_calls(api):
         c = BY_NAME[name]
         nb, nch, ns = c["planar"].shape
         pk = api.new_hzr(4, nch, ns)
-        raw, view = _matrix(c["planar"], c["off"])
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
         X = pp.rows_of(c["planar"])
         for marker in (1.0, -1.0):
             st, parts = pk.peak_state(), []
@@ -508,7 +444,7 @@ def test_gpu_the_offline_workspace_needs_no_initialisation(api):
     for name in ("rows2x65x37_offline_fs150", "trispikes1x4x4000_offline_fs250", "state2x65x50_offline_fs150"):
         c = BY_NAME[name]
         pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-        raw, view = _matrix(c["planar"], c["off"])
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
         for fill in (0xFF, 0x00, 0x7F):
             r = _run(api, pk, c, view, 1.0, state=pk.peak_state() if c["stateful"] else None, work_fill=fill)
             got = pp.summarize(r, r)
@@ -523,7 +459,7 @@ def test_gpu_a_repeated_call_gives_the_same_output(api):
     for name in ("rows2x65x48_online_1st_fs150", "burst1x3x3000_offline_fs1000"):
         c = BY_NAME[name]
         pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-        raw, view = _matrix(c["planar"], c["off"])
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
         call = pk.peak_detect_planar_batch if c["kind"] == "online" else pk.peak_detect_offline_planar_batch
         kw = dict(variant=c["variant"]) if c["kind"] == "online" else {}
         outs = [call(view, sampling_rate=c["fs"], marker_val=-1.0, max_peaks=c["ns"], traces=True, **kw) for _ in range(3)]
@@ -547,7 +483,7 @@ def test_gpu_the_entries_run_on_a_foreign_stream(api):
     for name in ("rows5x13x37_online_1st_fs150", "rows5x13x48_offline_fs150"):
         c = BY_NAME[name]
         pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-        raw, view = _matrix(c["planar"], c["off"])
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
         s.wait_stream(torch.cuda.current_stream())
         r = _run(api, pk, c, view, 1.0, stream=s.cuda_stream)
         got = pp.summarize(r, r)
@@ -568,7 +504,7 @@ def test_gpu_values_outside_the_width_go_in_whole_and_the_converter_route_differ
 
     for c in (c for c in CASES if c["group"] == "width"):
         pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
-        raw, view = _matrix(c["planar"], c["off"])
+        raw, view = df.guarded_matrix(c["planar"], c["off"])
         r = _run(api, pk, c, view, -1.0)
         got = pp.summarize(r, r)
         assert [k for k in ("count_m1", "index_m1", "values_m1", "sig", "thr") if got[k] != _rec(c["name"])[k]] == [], c["name"]
@@ -620,8 +556,8 @@ def test_gpu_every_refusal_returns_its_code_and_writes_nothing(api):
     nch, ns = 3, 100
     pk = api.new_hzr(2, nch, ns)
     P = pp._walk(2, nch, ns, 77)
-    raw, view = _matrix(P, 0)
-    bufs = {k: _guarded(n, 8 if k in ("sig", "thr") else 0) for k, n in (("count", 2 * nch * 4), ("index", 2 * nch * 4 * 4), ("value", 2 * nch * 4 * 8),
+    raw, view = df.guarded_matrix(P, 0)
+    bufs = {k: df.guarded(n, 8 if k in ("sig", "thr") else 0) for k, n in (("count", 2 * nch * 4), ("index", 2 * nch * 4 * 4), ("value", 2 * nch * 4 * 8),
                                                                          ("sig", 2 * nch * ns * 8), ("thr", 2 * nch * ns * 8), ("state", 208 * nch),
                                                                          ("work", pk.peak_offline_work_bytes(2) + 8))}
     befores = {k: r.clone() for k, (r, _) in bufs.items()}
@@ -670,7 +606,7 @@ def test_gpu_every_refusal_returns_its_code_and_writes_nothing(api):
     assert torch.equal(raw, mbefore) and not torch.equal(bufs["count"][0], befores["count"]) and not torch.equal(bufs["sig"][0], befores["sig"])
     assert torch.equal(bufs["state"][0], befores["state"])
     for k, n in (("count", 2 * nch * 4), ("index", 2 * nch * 4 * 4), ("value", 2 * nch * 4 * 8), ("sig", 2 * nch * ns * 8), ("thr", 2 * nch * ns * 8)):
-        assert _guards_untouched(bufs[k][0], 8 if k in ("sig", "thr") else 0, n), k
+        assert df.guards_untouched(bufs[k][0], 8 if k in ("sig", "thr") else 0, n), k
     short.close()
     wide.close()
     pk.close()

@@ -14,8 +14,8 @@ import pytest
 
 import convert_cases as cc
 import planar_cases as pc
+from devframe import ERR_ARG
 
-ERR_ARG = -1
 NB_CTOR = {"xdelta_hzr": 3, "hzr": 4, "dct": 2, "hadamard": 3}
 
 

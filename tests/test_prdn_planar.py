@@ -8,22 +8,19 @@ on both sides of every threshold of the host's choice of form, on handles of eve
 on real round trips, stream-ordered, and the refusals."""
 import ctypes as C
 import itertools
-import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import cases
-import devasm
+import devframe as df
 import planar_cases as pl
 import prdn_cases as pc
 import prdn_planar_cases as pp
+from devframe import ERR_ARG, ERR_UNSUPPORTED, ROOT, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRY = "rspt_hip_prdn_planar_batch_dev"
 SYNTH = [c["name"] for c in pc.synthetic_cases()]
 LOSSY = [c["name"] for c in pc.lossy_fixtures()]
@@ -33,8 +30,7 @@ NB_CTOR = {"hzr": 4, "xdelta_hzr": 3, "dct": 2, "hadamard": 3}
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "prdn_record.json")) as f:
-        return {r["name"]: r for r in json.load(f)["cases"]}
+    return {r["name"]: r for r in df.golden("prdn_record.json")["cases"]}
 
 
 @pytest.fixture(scope="module")
@@ -50,9 +46,7 @@ def pcases(orc):
 # ---- CPU ----
 
 def test_header_declares_the_entry_and_the_library_exports_it():
-    from rspt_amd import api, build
-
-    hdr = open(os.path.join(ROOT, "include", "rspt_hip.h")).read()
+    hdr = df.header(flat=False)
     m = re.search(r"int\s+rspt_hip_prdn_planar_batch_dev\s*\(\s*rspt_hip_packer\s*\*\s*p\s*,\s*const\s+int32_t\s*\*\s*d_orig\s*,\s*const\s+int32_t\s*\*\s*d_dec\s*,"
                   r"\s*size_t\s+nblocks\s*,\s*double\s*\*\s*d_prdn\s*,\s*double\s*\*\s*d_mse\s*,\s*double\s*\*\s*d_ref\s*,\s*uint32_t\s*\*\s*d_path\s*,"
                   r"\s*void\s*\*\s*stream\s*\)\s*;", hdr)
@@ -60,10 +54,7 @@ def test_header_declares_the_entry_and_the_library_exports_it():
     section = hdr[hdr.rindex("/* ----", 0, m.start()):m.start()]
     for word in ("whole int32", "bps = 4"):
         assert word in section, word
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    assert re.search(r"\bT %s$" % ENTRY, out, re.M)
-    assert ENTRY in api.C_ABI_SYMBOLS
+    df.check_entries((), (ENTRY,))
 
 
 def test_a_null_handle_is_refused_without_a_device():
@@ -116,33 +107,14 @@ def test_the_shapes_straddle_the_hosts_thresholds():
     assert not re.search(r"[<>=]=?\s*\d{3,}", body), "a threshold of the form choice is a literal"
 
 
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
 def test_no_new_kernel_uses_scratch(asm):
-    text = open(devasm.asm_path()).read()
     names = [n for n in asm if re.search(r"\d+k_qp_(sums|accum|rows|seq)", n)]
     kinds = {re.search(r"k_qp_[a-z]+", n).group(0) for n in names}
     assert {"k_qp_sums", "k_qp_accum", "k_qp_seq"} <= kinds, names
-    for n in names:
-        m = re.search(r"^\s*\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(n), text, re.M | re.S)
-        assert m, n
-        assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", m.group(1)), n
+    df.uses_no_scratch(asm, names)
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def _t(a):
     import torch

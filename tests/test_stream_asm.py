@@ -12,8 +12,7 @@ import sys
 import pytest
 
 import devasm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from devframe import ROOT
 
 
 @pytest.fixture(scope="module")

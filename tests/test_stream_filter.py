@@ -7,29 +7,24 @@ argument checks that need no device.
 GPU (-m gpu): every case bit-exact against the record and the restatement however the recording is cut into calls, the
 equivalence with the stateless stages, that the state is used, and the statuses."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import devasm
+import devframe as df
 import fir_cases as fc
 import iir_cases as ic
 import stream_filter_cases as sc
 from cases import IIR_BANDPASS, digest
+from devframe import ERR_ARG, ERR_UNSUPPORTED, api, asm  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
 ENTRIES = ("rspt_hip_iir_state_bytes", "rspt_hip_iir_prefilter_stream_dev", "rspt_hip_fir_state_bytes", "rspt_hip_fir_prefilter_stream_dev")
 
 
 @pytest.fixture(scope="module")
 def record():
-    with open(os.path.join(ROOT, "tests", "golden", "stream_filter_record.json")) as f:
-        return json.load(f)
+    return df.golden("stream_filter_record.json")
 
 
 @pytest.fixture(scope="module")
@@ -107,60 +102,35 @@ def test_fir_nan_case_holds_overflow_and_nan(scases):
 
 
 def test_header_declares_the_entries_and_the_library_exports_them():
-    from rspt_amd import api, build
-
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
-    for decl in (
+    df.check_entries((
         "int rspt_hip_iir_state_bytes(rspt_hip_packer* p, size_t* bytes);",
         "int rspt_hip_iir_prefilter_stream_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, "
         "size_t nr_coefficients, int init_nr_samples, void* d_state, void* stream);",
         "int rspt_hip_fir_state_bytes(rspt_hip_packer* p, size_t kernel_size, size_t* bytes);",
         "int rspt_hip_fir_prefilter_stream_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, "
         "size_t kernel_size, void* d_state, void* stream);",
-    ):
-        assert decl in hdr, decl
-    lib = build.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    for name in ENTRIES:
-        assert re.search(r"\bT %s$" % name, out, re.M), name
-        assert name in api.C_ABI_SYMBOLS
+    ), ENTRIES)
 
 
 def test_the_stateless_entries_keep_their_signatures():
-    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "rspt_hip.h")).read())
+    hdr = df.header()
     assert ("int rspt_hip_iir_prefilter_batch_dev(rspt_hip_packer* p, void* d_buf, size_t nblocks, const double* n, const double* d, "
             "size_t nr_coefficients, int init_nr_samples, int per_channel, void* stream);") in hdr
     assert ("int rspt_hip_fir_prefilter_batch_dev(rspt_hip_packer* p, const void* d_src, void* d_dst, size_t nblocks, const double* kernel, "
             "size_t kernel_size, void* stream);") in hdr
 
 
-@pytest.fixture(scope="module")
-def asm():
-    if not os.path.exists(devasm.HIPCC):
-        pytest.skip("hipcc not found")
-    return devasm.functions()
-
-
-FUSED = re.compile(r"^\s+(v_fma\w*_f(64|32)|v_fmac\w*_f(64|32)|v_mad\w*_f(64|32)|v_mac\w*_f(64|32)|v_pk_fma\w*|v_mfma\w*f64)\b")
-
-
 def test_the_new_filter_kernels_round_every_product_and_sum_on_their_own(asm):
     """k_iir_carry (calls of fewer than 64 rows) and the CARRY instantiations of k_iir_pipe (a fifth template argument `true`): no
     fp FMA, no f64 MFMA, and separate v_mul_f64 / v_add_f64; k_fir is the stateless stage's kernel with one more pointer, held
     to the same by tests/test_fir_prefilter.py -- here: still six instantiations, and the byte movers hold no fp arithmetic"""
-    carry = [n for n in asm if "k_iir_carry" in n]
-    pipe = [n for n in asm if re.search(r"10k_iir_pipeILi\dELi\dELb0ELb[01]ELb1EE", n)]
-    assert len(carry) == 16, sorted(carry)  # sample width x order
-    assert len(pipe) == 24, sorted(pipe)  # (int8, int16 (+aligned), int24, int32 (+aligned)) x order
-    for n in carry + pipe:
-        assert not [ln for ln in asm[n] if FUSED.match(ln)], n
-        text = "".join(asm[n])
-        assert re.search(r"^\s+v_mul_f64\b", text, re.M) and re.search(r"^\s+v_add_f64\b", text, re.M), n
+    df.rounds_separately(asm, r"k_iir_carry", 16)  # sample width x order
+    df.rounds_separately(asm, r"10k_iir_pipeILi\dELi\dELb0ELb[01]ELb1EE", 24)  # (int8, int16 (+aligned), int24, int32 (+aligned)) x order
     assert len([n for n in asm if re.search(r"5k_firIL", n)]) == 6
     movers = [n for n in asm if "k_fir_carry" in n]
     assert len(movers) == 2, movers
     for n in movers:
-        assert not [ln for ln in asm[n] if re.match(r"^\s+v_\w+_f64\b", ln) or FUSED.match(ln)], n
+        assert not [ln for ln in asm[n] if re.match(r"^\s+v_\w+_f64\b", ln) or df.FUSED_F64_F32.match(ln)], n
 
 
 def test_argument_checks_that_need_no_device():
@@ -179,14 +149,6 @@ def test_argument_checks_that_need_no_device():
 
 
 # ---- GPU ----
-
-@pytest.fixture(scope="module")
-def api():
-    from rspt_amd import api as a
-
-    assert a.lib().rspt_hip_device_count() > 0, "no gfx950 device visible"
-    return a
-
 
 def _state(pk, c):
     return pk.fir_state(len(c["kernel"])) if c["kind"] == "fir" else pk.iir_state()

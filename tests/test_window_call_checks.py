@@ -9,7 +9,8 @@ import ctypes as C
 
 import pytest
 
-ERR_ARG, ERR_UNSUPPORTED = -1, -7
+from devframe import ERR_ARG, ERR_UNSUPPORTED
+
 BPS = 2  # (a native sample is not a planar one: 2 and 4 bytes)
 ENTRIES = [(stage, planar, carried) for stage in ("fir_prefilter", "median_filter") for planar in (False, True) for carried in (False, True)]
 
