@@ -81,9 +81,18 @@ struct Workspace {
     Dev<double2> fft_scratch;  // [fft_bpp][nch][n] (dct beyond the dense table)
     size_t fft_bpp = 0;        // blocks per pass (bounds the scratch to ~1 GiB)
     Dev<int32_t> mean_i32;     // [cap][nch]
-    // rspt_hip_prdn_batch_dev: [cap][nch] int64 channel sums | [cap][4] per-block accumulators | [cap] u32 flags, each part placed
-    // per call right behind the one before it (the first two are zeroed by one memset in front of the call's kernels)
-    Dev<unsigned long long> quality;
+    Dev<unsigned long long> quality;  // [cap][quality_words(nch)]: the PRDN entries' scratch, carved up per call by QScratch
+};
+
+// The PRDN scratch of a call on B blocks: [B][nch] int64 channel sums | [B][4] per-block accumulators | [B] u32 flags, each part
+// right behind the one before it; the first two (clear_bytes) are zeroed by one memset in front of the call's kernels.
+constexpr size_t quality_words(size_t nch) { return nch + 4 + 1; }  // 64-bit words per block (a flag leaves half of its word unused)
+struct QScratch {
+    unsigned long long *sums, *acc;
+    uint32_t* flag;
+    size_t clear_bytes;
+    QScratch(unsigned long long* base, size_t B, size_t nch)
+        : sums(base), acc(base + B * nch), flag(reinterpret_cast<uint32_t*>(acc + B * 4)), clear_bytes(B * (nch + 4) * sizeof(unsigned long long)) {}
 };
 
 // rspt_hip_compress / rspt_hip_decompress: one block staged on the device

@@ -933,10 +933,32 @@ static QGeom quality_geom(const rspt_hip_packer* p, size_t nblocks, int W) {
     return q;
 }
 
+// The refusals both PRDN entries share, in front of each entry's own.
+static int prdn_checks(const rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, const double* d_prdn) {
+    if (!p || !d_orig || !d_dec || !d_prdn || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    return p->feed ? RSPT_HIP_ERR_ARG : RSPT_HIP_OK;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
+}
+
+// Both PRDN entries behind their refusals: the workspace, the zeroed scratch, then launch(s, st, false) -- the entry's streaming
+// passes --, k_q_finish, and launch(s, st, true) -- the entry's sequential kernel, which reads the flags k_q_finish wrote.
+template <class Launch>
+static int prdn_call(rspt_hip_packer* p, size_t nblocks, double* d_prdn, double* d_mse, double* d_ref, uint32_t* d_path, void* stream, Launch&& launch) {
+    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t B = (uint32_t)nblocks;
+    const QScratch s(p->ws.quality, B, p->g.nch);
+    HIPCHK(p, hipMemsetAsync(s.sums, 0, s.clear_bytes, st));
+    launch(s, st, false);
+    hipLaunchKernelGGL(k_q_finish, dim3((B + 255) / 256), dim3(256), 0, st, (const unsigned long long*)s.acc, B, s.flag, d_prdn, d_mse, d_ref, d_path);
+    launch(s, st, true);
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
 int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* d_dec, size_t nblocks, double* d_prdn, double* d_mse, double* d_ref,
                             uint32_t* d_path, void* stream) {
-    if (!p || !d_orig || !d_dec || !d_prdn || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
-    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
+    if (int rc = prdn_checks(p, d_orig, d_dec, nblocks, d_prdn)) return rc;
     if (stage_too_wide(p)) return RSPT_HIP_ERR_UNSUPPORTED;
     const Geom& g = p->g;
     const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_orig), d0 = reinterpret_cast<uintptr_t>(d_dec);
@@ -946,32 +968,24 @@ int rspt_hip_prdn_batch_dev(rspt_hip_packer* p, const void* d_orig, const void* 
     q.aligned4 = aligned(4) ? 1u : 0u;
     const uint64_t units = (uint64_t)nblocks * q.ncg * q.nsplit;
     if (units >= (1ull << 31) || (uint64_t)q.rows * g.nch >= (1ull << 32)) return RSPT_HIP_ERR_UNSUPPORTED;
-    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t B = (uint32_t)nblocks;
-    unsigned long long* sums = p->ws.quality;
-    unsigned long long* acc = sums + (size_t)B * g.nch;
-    uint32_t* flag = reinterpret_cast<uint32_t*>(acc + (size_t)B * 4);
-    HIPCHK(p, hipMemsetAsync(sums, 0, ((size_t)B * g.nch + (size_t)B * 4) * sizeof(unsigned long long), st));
     const uint8_t* o = (const uint8_t*)d_orig;
     const uint8_t* d = (const uint8_t*)d_dec;
-    by_bps(g.bps, [&](auto bb) {
-        constexpr int BPS = decltype(bb)::value;
-        auto go = [&](auto ww) {
-            constexpr int WW = decltype(ww)::value;
-            hipLaunchKernelGGL((k_q_sums<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, q, sums);
-            hipLaunchKernelGGL((k_q_accum<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, acc);
-        };
-        if (W == 4) go(std::integral_constant<int, 4>());
-        else if (W == 1) go(std::integral_constant<int, 1>());
-        else go(std::integral_constant<int, 0>());
-        hipLaunchKernelGGL(k_q_finish, dim3((B + 255) / 256), dim3(256), 0, st, (const unsigned long long*)acc, B, flag, d_prdn, d_mse, d_ref, d_path);
-        hipLaunchKernelGGL(k_q_seq<BPS>, dim3(B), dim3(kQThreads), 0, st, o, d, q, (const long long*)sums, (const unsigned long long*)acc,
-                           (const uint32_t*)flag, d_prdn, d_mse, d_ref);
+    return prdn_call(p, nblocks, d_prdn, d_mse, d_ref, d_path, stream, [&](const QScratch& s, hipStream_t st, bool seq) {
+        by_bps(g.bps, [&](auto bb) {
+            constexpr int BPS = decltype(bb)::value;
+            auto go = [&](auto ww) {
+                constexpr int WW = decltype(ww)::value;
+                hipLaunchKernelGGL((k_q_sums<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, q, s.sums);
+                hipLaunchKernelGGL((k_q_accum<BPS, WW>), dim3((uint32_t)units), dim3(kQThreads), 0, st, o, d, q, (const long long*)s.sums, s.acc);
+            };
+            if (seq)
+                hipLaunchKernelGGL(k_q_seq<BPS>, dim3((uint32_t)nblocks), dim3(kQThreads), 0, st, o, d, q, (const long long*)s.sums,
+                                   (const unsigned long long*)s.acc, (const uint32_t*)s.flag, d_prdn, d_mse, d_ref);
+            else if (W == 4) go(std::integral_constant<int, 4>());
+            else if (W == 1) go(std::integral_constant<int, 1>());
+            else go(std::integral_constant<int, 0>());
+        });
     });
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
 }
 
 // ---- PRDN on the planar int32 matrix (quality_planar.hip) -------------------------------------------------------------------------
@@ -995,9 +1009,8 @@ static uint64_t quality_planar_units(const QPGeom& q) { return q.lanes == (uint3
 
 int rspt_hip_prdn_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_orig, const int32_t* d_dec, size_t nblocks, double* d_prdn, double* d_mse,
                                    double* d_ref, uint32_t* d_path, void* stream) {
-    if (!p || !d_orig || !d_dec || !d_prdn || !batch_count_ok(p, nblocks)) return RSPT_HIP_ERR_ARG;
+    if (int rc = prdn_checks(p, d_orig, d_dec, nblocks, d_prdn)) return rc;
     if (p->g.kind == RSPT_HIP_KIND_BYTES) return RSPT_HIP_ERR_ARG;  // (a byte buffer has no samples)
-    if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
     const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_orig), d0 = reinterpret_cast<uintptr_t>(d_dec);
     if ((o0 | d0) & 3u) return RSPT_HIP_ERR_ARG;
     const Geom& g = p->g;
@@ -1006,28 +1019,20 @@ int rspt_hip_prdn_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_orig, co
     if (p->qp_form) fused = p->qp_form == 2;
     if (!fused) q = quality_planar_geom(g, nblocks, false);
     const uint64_t units = quality_planar_units(q);  // (below 2^31: at most the rows of the call, or about kQpUnits where rows are cut)
-    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
-    HIPCHK(p, hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t B = (uint32_t)nblocks;
-    unsigned long long* sums = p->ws.quality;  // (the native entry's scratch, laid out as there)
-    unsigned long long* acc = sums + (size_t)B * g.nch;
-    uint32_t* flag = reinterpret_cast<uint32_t*>(acc + (size_t)B * 4);
-    HIPCHK(p, hipMemsetAsync(sums, 0, ((size_t)B * g.nch + (size_t)B * 4) * sizeof(unsigned long long), st));
-    const dim3 grid((uint32_t)units), wg(kQpThreads);
-    if (fused) {
-        if (g.ns <= (q.lanes == (uint32_t)kWave ? kQpWaveRow : kQpRowRegs))
-            hipLaunchKernelGGL(k_qp_rows<true>, grid, wg, 0, st, d_orig, d_dec, q, (long long*)sums, acc);
-        else hipLaunchKernelGGL(k_qp_rows<false>, grid, wg, 0, st, d_orig, d_dec, q, (long long*)sums, acc);
-    } else {
-        hipLaunchKernelGGL(k_qp_sums, grid, wg, 0, st, d_orig, q, sums);
-        hipLaunchKernelGGL(k_qp_accum, grid, wg, 0, st, d_orig, d_dec, q, (const long long*)sums, acc);
-    }
-    hipLaunchKernelGGL(k_q_finish, dim3((B + 255) / 256), dim3(256), 0, st, (const unsigned long long*)acc, B, flag, d_prdn, d_mse, d_ref, d_path);
-    hipLaunchKernelGGL(k_qp_seq, dim3(B), dim3(kQThreads), 0, st, d_orig, d_dec, g.nch, g.ns, (const long long*)sums, (const unsigned long long*)acc,
-                       (const uint32_t*)flag, d_prdn, d_mse, d_ref);
-    HIPCHK(p, hipGetLastError());
-    return RSPT_HIP_OK;
+    return prdn_call(p, nblocks, d_prdn, d_mse, d_ref, d_path, stream, [&](const QScratch& s, hipStream_t st, bool seq) {
+        const dim3 grid((uint32_t)units), wg(kQpThreads);
+        if (seq) {
+            hipLaunchKernelGGL(k_qp_seq, dim3((uint32_t)nblocks), dim3(kQThreads), 0, st, d_orig, d_dec, g.nch, g.ns, (const long long*)s.sums,
+                               (const unsigned long long*)s.acc, (const uint32_t*)s.flag, d_prdn, d_mse, d_ref);
+        } else if (fused) {
+            if (g.ns <= (q.lanes == (uint32_t)kWave ? kQpWaveRow : kQpRowRegs))
+                hipLaunchKernelGGL(k_qp_rows<true>, grid, wg, 0, st, d_orig, d_dec, q, (long long*)s.sums, s.acc);
+            else hipLaunchKernelGGL(k_qp_rows<false>, grid, wg, 0, st, d_orig, d_dec, q, (long long*)s.sums, s.acc);
+        } else {
+            hipLaunchKernelGGL(k_qp_sums, grid, wg, 0, st, d_orig, q, s.sums);
+            hipLaunchKernelGGL(k_qp_accum, grid, wg, 0, st, d_orig, d_dec, q, (const long long*)s.sums, s.acc);
+        }
+    });
 }
 
 // ---- native <-> planar int32 (the reference's convert_native_to_i32 / convert_i32_to_native, utils.cpp:51-191) -------------------

@@ -14,6 +14,9 @@
 //               for ref = (double)SR; where both hold the block is done, else it is flagged
 //   k_q_seq     flagged blocks only (it exits at once for the others): one workgroup walks the block channel-outer, sample-inner,
 //               three waves put the double terms of a chunk into LDS while one lane adds the chunk before in the reference's order.
+// What the planar form (quality_planar.hip) shares is stated here once: the terms and a thread's accumulators (q_terms, QTerms),
+// the wave reduction (q_wave_sum), the finish, and the chain itself, q_seq_chain, which k_q_seq and k_qp_seq call with the
+// sample fetch of their layout -- the only place where the reference's ORDER of fp64 adds is reproduced.
 //
 // Layout of the two streaming passes.  A super-row is the fewest rows whose samples fill whole load groups (a group: 16 bytes,
 // 48 for int24; 4 or 12 where only 4-byte alignment is given; one sample where not even that).  A thread owns one group position
@@ -37,6 +40,7 @@ struct QGeom {
 };
 
 constexpr uint32_t kQThreads = 256;
+constexpr uint32_t kQWaves = kQThreads / kWave;
 constexpr uint32_t kQSlots = 4096;   // LDS accumulators of k_q_sums: groups of a super-row x samples of a group, where nsub > 1
 constexpr uint32_t kQChunk = 1024;   // samples of a chunk of k_q_seq
 
@@ -160,6 +164,28 @@ __device__ __forceinline__ void q_terms(int32_t o, int32_t d, int32_t mean, int3
     r = (int32_t)(dm * dm);
 }
 
+// A thread's four exact accumulators: the low and high 32 bits of every t^2 summed apart, sum r, sum |r|.
+struct QTerms {
+    unsigned long long lo = 0, hi = 0, sa = 0;
+    long long sr = 0;
+    __device__ __forceinline__ void add(int32_t ov, int32_t dv, int32_t mean) {
+        int32_t t, r;
+        q_terms(ov, dv, mean, t, r);
+        const unsigned long long t2 = (unsigned long long)((long long)t * (long long)t);  // up to 2^62
+        lo += (uint32_t)t2;
+        hi += t2 >> 32;
+        sr += r;
+        sa += (unsigned long long)(r < 0 ? -(long long)r : (long long)r);
+    }
+};
+
+__device__ __forceinline__ unsigned long long q_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += (unsigned long long)__shfl_xor((long long)v, m);
+    return v;
+}
+
+
 // sums[b][c] += the samples of channel c (sums starts from zero)
 template <int BPS, int W>
 __global__ __launch_bounds__(kQThreads) void k_q_sums(const uint8_t* __restrict__ o, QGeom g, unsigned long long* __restrict__ sums) {
@@ -213,23 +239,13 @@ template <int BPS, int W>
 __global__ __launch_bounds__(kQThreads) void k_q_accum(const uint8_t* __restrict__ o, const uint8_t* __restrict__ d, QGeom g,
                                                       const long long* __restrict__ sums, unsigned long long* __restrict__ acc) {
     using V = QVec<BPS, W>;
-    __shared__ unsigned long long s_red[kQThreads / kWave][4];
+    __shared__ unsigned long long s_red[kQWaves][4];
     const QUnit u = q_unit(g);
     const uint32_t tid = threadIdx.x;
     const uint8_t* bo = o + (uint64_t)u.b * g.block_bytes;
     const uint8_t* bd = d + (uint64_t)u.b * g.block_bytes;
     const long long* bs = sums + (uint64_t)u.b * g.nch;
-    unsigned long long lo = 0, hi = 0, sa = 0;
-    long long sr = 0;
-    auto term = [&](int32_t ov, int32_t dv, int32_t mean) {
-        int32_t t, r;
-        q_terms(ov, dv, mean, t, r);
-        const unsigned long long t2 = (unsigned long long)((long long)t * (long long)t);  // up to 2^62
-        lo += (uint32_t)t2;
-        hi += t2 >> 32;
-        sr += r;
-        sa += (unsigned long long)(r < 0 ? -(long long)r : (long long)r);
-    };
+    QTerms T;
     if (u.active && u.sr0 < u.sr1) {
         int32_t mean[V::VS];
         uint32_t c = (uint32_t)(((uint64_t)u.q * V::VS) % g.nch);
@@ -240,23 +256,21 @@ __global__ __launch_bounds__(kQThreads) void k_q_accum(const uint8_t* __restrict
         }
         q_walk<BPS, W, true>(bo, bd, g, u.q, u.sr0, u.sr1, [&](const int32_t(&ov)[V::VS], const int32_t(&dv)[V::VS]) {
 #pragma unroll
-            for (int k = 0; k < V::VS; ++k) term(ov[k], dv[k], mean[k]);
+            for (int k = 0; k < V::VS; ++k) T.add(ov[k], dv[k], mean[k]);
         });
     }
     if (u.split == 0 && u.cg == 0) {
         const uint64_t row0 = (uint64_t)g.nsr * g.rows, n = ((uint64_t)g.ns - row0) * g.nch;
         for (uint64_t i = tid; i < n; i += kQThreads) {
             const uint64_t at = (row0 * g.nch + i) * BPS;
-            term(sample_from_bytes<BPS>(bo + at, g.aligned4 != 0, g.be != 0), sample_from_bytes<BPS>(bd + at, g.aligned4 != 0, g.be != 0),
-                 mean_from_sum(bs[i % g.nch], g.ns));
+            T.add(sample_from_bytes<BPS>(bo + at, g.aligned4 != 0, g.be != 0), sample_from_bytes<BPS>(bd + at, g.aligned4 != 0, g.be != 0),
+                  mean_from_sum(bs[i % g.nch], g.ns));
         }
     }
-    unsigned long long v[4] = {lo, hi, (unsigned long long)sr, sa};
+    // (not q_flush: every wave here works on block u.b, and its walk over the waves' blocks measured slower -- DESIGN.md 4f)
+    unsigned long long v[4] = {T.lo, T.hi, (unsigned long long)T.sr, T.sa};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[j] += (unsigned long long)__shfl_xor((long long)v[j], m);
-    }
+    for (int j = 0; j < 4; ++j) v[j] = q_wave_sum(v[j]);
     if ((tid & (kWave - 1)) == 0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) s_red[tid / kWave][j] = v[j];
@@ -264,7 +278,7 @@ __global__ __launch_bounds__(kQThreads) void k_q_accum(const uint8_t* __restrict
     __syncthreads();
     if (tid < 4) {
         unsigned long long s = 0;
-        for (uint32_t w = 0; w < kQThreads / kWave; ++w) s += s_red[w][tid];
+        for (uint32_t w = 0; w < kQWaves; ++w) s += s_red[w][tid];
         if (s) atomicAdd(&acc[(uint64_t)u.b * 4 + tid], s);
     }
 }
@@ -305,33 +319,34 @@ __global__ __launch_bounds__(256) void k_q_finish(const unsigned long long* __re
     if (ref_out) ref_out[b] = ref;
 }
 
-// A flagged block in the reference's own order.  Chunk k = (channel, up to kQChunk consecutive samples of it); waves 1 .. 3 put the
-// terms of chunk k + 1 into one half of the LDS buffers while lane 0 adds chunk k from the other.
-template <int BPS>
-__global__ __launch_bounds__(kQThreads) void k_q_seq(const uint8_t* __restrict__ o, const uint8_t* __restrict__ d, QGeom g,
-                                                    const long long* __restrict__ sums, const unsigned long long* __restrict__ acc,
-                                                    const uint32_t* __restrict__ flag, double* __restrict__ prdn, double* __restrict__ mse_out,
-                                                    double* __restrict__ ref_out) {
-    const uint32_t b = blockIdx.x, fl = flag[b];
-    if (!fl) return;
+struct QPair {
+    int32_t o, d;
+};
+
+// A flagged block b (a workgroup of kQThreads; fl = flag[b], which the kernel has found non-zero before it set up its fetch) in the
+// reference's own order, for both layouts: fetch(c, s) reads the two samples of channel c at sample s, bs points at the sums of
+// the block's channels.
+// Chunk k = (channel, up to kQChunk consecutive samples of it); waves 1 .. 3 put the terms of chunk k + 1 into one half of the
+// LDS buffers while lane 0 adds chunk k from the other: a product is rounded on its way into LDS, so no product and add contract.
+template <class Fetch>
+__device__ __forceinline__ void q_seq_chain(uint32_t b, uint32_t nch, uint32_t ns, const long long* __restrict__ bs,
+                                            const unsigned long long* __restrict__ acc, uint32_t fl,
+                                            double* __restrict__ prdn, double* __restrict__ mse_out, double* __restrict__ ref_out, Fetch&& fetch) {
     __shared__ double s_t[2][kQChunk], s_r[2][kQChunk];
     const uint32_t tid = threadIdx.x;
-    const bool need_m = (fl & 1u) != 0, need_r = (fl & 2u) != 0, be = g.be != 0, al = g.aligned4 != 0;
-    const uint8_t* bo = o + (uint64_t)b * g.block_bytes;
-    const uint8_t* bd = d + (uint64_t)b * g.block_bytes;
-    const long long* bs = sums + (uint64_t)b * g.nch;
-    const uint32_t cpc = (g.ns + kQChunk - 1) / kQChunk;  // chunks per channel
-    const uint64_t nchunks = (uint64_t)g.nch * cpc;
+    const bool need_m = (fl & 1u) != 0, need_r = (fl & 2u) != 0;
+    const uint32_t cpc = (ns + kQChunk - 1) / kQChunk;  // chunks per channel
+    const uint64_t nchunks = (uint64_t)nch * cpc;
     auto produce = [&](uint64_t k, uint32_t t0, uint32_t nt) {
         const uint32_t c = (uint32_t)(k / cpc), s0 = (uint32_t)(k - (uint64_t)c * cpc) * kQChunk;
-        const uint32_t n = g.ns - s0 < kQChunk ? g.ns - s0 : kQChunk;
-        const int32_t mean = mean_from_sum(bs[c], g.ns);
+        const uint32_t n = ns - s0 < kQChunk ? ns - s0 : kQChunk;
+        const int32_t mean = mean_from_sum(bs[c], ns);
         double* pt = s_t[k & 1];
         double* pr = s_r[k & 1];
         for (uint32_t i = t0; i < n; i += nt) {
-            const uint64_t at = ((uint64_t)(s0 + i) * g.nch + c) * BPS;
+            const QPair x = fetch(c, s0 + i);
             int32_t t, r;
-            q_terms(sample_from_bytes<BPS>(bo + at, al, be), sample_from_bytes<BPS>(bd + at, al, be), mean, t, r);
+            q_terms(x.o, x.d, mean, t, r);
             if (need_m) pt[i] = __dmul_rn((double)t, (double)t);
             if (need_r) pr[i] = (double)r;
         }
@@ -344,7 +359,7 @@ __global__ __launch_bounds__(kQThreads) void k_q_seq(const uint8_t* __restrict__
             if (k + 1 < nchunks) produce(k + 1, tid - kWave, kQThreads - kWave);
         } else if (tid == 0) {
             const uint32_t s0 = (uint32_t)(k % cpc) * kQChunk;
-            const uint32_t n = g.ns - s0 < kQChunk ? g.ns - s0 : kQChunk;
+            const uint32_t n = ns - s0 < kQChunk ? ns - s0 : kQChunk;
             const double* pt = s_t[k & 1];
             const double* pr = s_r[k & 1];
             if (need_m && need_r) {
@@ -370,6 +385,23 @@ __global__ __launch_bounds__(kQThreads) void k_q_seq(const uint8_t* __restrict__
         if (mse_out) mse_out[b] = mse;
         if (ref_out) ref_out[b] = ref;
     }
+}
+
+// the chain on the interleaved block (BPS = 1 is instantiated but never flagged: t^2 <= 2^16 would need 2^37 samples)
+template <int BPS>
+__global__ __launch_bounds__(kQThreads) void k_q_seq(const uint8_t* __restrict__ o, const uint8_t* __restrict__ d, QGeom g,
+                                                    const long long* __restrict__ sums, const unsigned long long* __restrict__ acc,
+                                                    const uint32_t* __restrict__ flag, double* __restrict__ prdn, double* __restrict__ mse_out,
+                                                    double* __restrict__ ref_out) {
+    const uint32_t b = blockIdx.x, fl = flag[b];
+    if (!fl) return;
+    const bool be = g.be != 0, al = g.aligned4 != 0;
+    const uint8_t* bo = o + (uint64_t)b * g.block_bytes;
+    const uint8_t* bd = d + (uint64_t)b * g.block_bytes;
+    q_seq_chain(b, g.nch, g.ns, sums + (uint64_t)b * g.nch, acc, fl, prdn, mse_out, ref_out, [&](uint32_t c, uint32_t s) {
+        const uint64_t at = ((uint64_t)s * g.nch + c) * BPS;
+        return QPair{sample_from_bytes<BPS>(bo + at, al, be), sample_from_bytes<BPS>(bd + at, al, be)};
+    });
 }
 
 }  // namespace rspt

@@ -1,11 +1,12 @@
 // quality_planar.hip -- PRDN[%] (quality.hip) on the planar int32 matrix [nblocks][nch][ns] ("The planar form").
 //
-// The arithmetic, the accumulators (two limbs of sum t^2, sum r, sum |r| per block), the flag word and the finish are quality.hip's:
-// q_terms, q_prdn, q_s2_exact, q_sr_exact, k_q_finish and mean_from_sum are used as they are.  What differs is where a channel
-// lies: row (b, c) = b * nch + c of the matrix is ns consecutive words, so a unit of work is a piece of ONE row and has ONE mean:
+// The arithmetic, the accumulators (two limbs of sum t^2, sum r, sum |r| per block), the flag word, the wave reduction, the finish
+// and the sequential chain are quality.hip's: QTerms, q_wave_sum, q_seq_chain, k_q_finish and mean_from_sum are used as
+// they are.  What differs is where a channel lies: row (b, c) = b * nch + c of the matrix is ns consecutive words, so a unit of
+// work is a piece of ONE row and has ONE mean:
 //   k_qp_sums   the exact int64 row sums: one 64-bit atomic per unit into sums[row]
 //   k_qp_accum  the second pass over o and d: one mean per unit, four atomics per workgroup and block into acc[b]
-//   k_qp_seq    k_q_seq with the producer waves reading contiguous row chunks
+//   k_qp_seq    the chain of k_q_seq (q_seq_chain) with the row fetch
 // A unit is a span of a row taken by a whole workgroup (rows longer than kQpWaveRow samples), or a whole row taken by one wave,
 // four rows to a workgroup (shorter rows: a 16-sample row does not cost a workgroup).  Rows start on a 16-byte boundary only where
 // the base does and ns % 4 == 0, so every unit reads a head of up to three samples up to the first 16-byte boundary of the o row,
@@ -28,6 +29,7 @@ constexpr uint32_t kQpRowRegs = kQpThreads * 4 * kQpU;
 constexpr uint32_t kQpFusedMinUnits = 1024;
 constexpr uint32_t kQpFusedMaxNs = 8192;  // (the longest row at which the form was measured to win: DESIGN.md 4f)
 static_assert(kQpWaveRow == kWave * 4 * kQpU, "a wave holds its whole row in registers");
+static_assert(kQpThreads == kQThreads, "q_seq_chain is written for workgroups of kQThreads");
 
 struct QPGeom {
     uint64_t rows;    // nblocks * nch rows of ns samples
@@ -108,12 +110,6 @@ __device__ __forceinline__ void qp_walk(const int32_t* po, const int32_t* pd, ui
     if (l < n - tail0) f(po[tail0 + l], TWO ? pd[tail0 + l] : po[tail0 + l]);
 }
 
-__device__ __forceinline__ unsigned long long qp_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += (unsigned long long)__shfl_xor((long long)v, m);
-    return v;
-}
-
 // sums[row] += the samples of the unit (sums starts from zero)
 __global__ __launch_bounds__(kQpThreads) void k_qp_sums(const int32_t* __restrict__ o, QPGeom g, unsigned long long* __restrict__ sums) {
     __shared__ unsigned long long s_red[kQpWaves];
@@ -122,7 +118,7 @@ __global__ __launch_bounds__(kQpThreads) void k_qp_sums(const int32_t* __restric
     const int32_t* po = o + u.row * g.ns + u.s0;
     long long acc = 0;
     qp_walk<false>(po, po, u.n, u.l, g.lanes, [&](int32_t ov, int32_t) { acc += ov; });
-    const unsigned long long s = qp_wave_sum((unsigned long long)acc);
+    const unsigned long long s = q_wave_sum((unsigned long long)acc);
     if (g.lanes == (uint32_t)kWave) {
         if (u.l == 0 && u.active && s) atomicAdd(&sums[u.row], s);
         return;
@@ -136,13 +132,15 @@ __global__ __launch_bounds__(kQpThreads) void k_qp_sums(const int32_t* __restric
     }
 }
 
-// Four per-thread accumulators -> acc[b]: wave shuffle, LDS, then one atomic per accumulator for each block the workgroup's
-// waves worked on (the rows of a workgroup ascend, so equal blocks are neighbours; blk = ~0: the wave had no row).
-__device__ __forceinline__ void qp_flush(unsigned long long (&v)[4], uint32_t blk, unsigned long long* __restrict__ acc,
+// The accumulators of a workgroup's threads -> acc[b]: wave shuffle, LDS, then one atomic per accumulator for each block the
+// workgroup's waves worked on (the rows of a workgroup ascend, so equal blocks are neighbours; blk = ~0: the wave had no row).
+// (k_q_accum, whose waves all work on one block, keeps its plain sum over the waves: DESIGN.md 4f.)
+__device__ __forceinline__ void qp_flush(const QTerms& T, uint32_t blk, unsigned long long* __restrict__ acc,
                                          unsigned long long (&s_red)[kQpWaves][4], uint32_t (&s_blk)[kQpWaves]) {
     const uint32_t tid = threadIdx.x;
+    unsigned long long v[4] = {T.lo, T.hi, (unsigned long long)T.sr, T.sa};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = qp_wave_sum(v[j]);
+    for (int j = 0; j < 4; ++j) v[j] = q_wave_sum(v[j]);
     if ((tid & (kWave - 1)) == 0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) s_red[tid / kWave][j] = v[j];
@@ -163,20 +161,6 @@ __device__ __forceinline__ void qp_flush(unsigned long long (&v)[4], uint32_t bl
     }
 }
 
-struct QpTerms {
-    unsigned long long lo = 0, hi = 0, sa = 0;
-    long long sr = 0;
-    __device__ __forceinline__ void add(int32_t ov, int32_t dv, int32_t mean) {
-        int32_t t, r;
-        q_terms(ov, dv, mean, t, r);
-        const unsigned long long t2 = (unsigned long long)((long long)t * (long long)t);  // up to 2^62
-        lo += (uint32_t)t2;
-        hi += t2 >> 32;
-        sr += r;
-        sa += (unsigned long long)(r < 0 ? -(long long)r : (long long)r);
-    }
-};
-
 // acc[b] = {low and high 32 bits of every t^2 summed apart, sum r, sum |r|} (acc starts from zero)
 __global__ __launch_bounds__(kQpThreads) void k_qp_accum(const int32_t* __restrict__ o, const int32_t* __restrict__ d, QPGeom g,
                                                         const long long* __restrict__ sums, unsigned long long* __restrict__ acc) {
@@ -185,10 +169,9 @@ __global__ __launch_bounds__(kQpThreads) void k_qp_accum(const int32_t* __restri
     const QPUnit u = qp_unit(g);
     const uint64_t at = u.row * g.ns + u.s0;
     const int32_t mean = mean_from_sum(sums[u.row], g.ns);
-    QpTerms T;
+    QTerms T;
     qp_walk<true>(o + at, d + at, u.n, u.l, g.lanes, [&](int32_t ov, int32_t dv) { T.add(ov, dv, mean); });
-    unsigned long long v[4] = {T.lo, T.hi, (unsigned long long)T.sr, T.sa};
-    qp_flush(v, u.active ? (uint32_t)(u.row / g.nch) : ~0u, acc, s_red, s_blk);
+    qp_flush(T, u.active ? (uint32_t)(u.row / g.nch) : ~0u, acc, s_red, s_blk);
 }
 
 // Both passes in one: a unit owns a WHOLE row (nsplit == 1).  It reads the row of o, reduces the sum, derives the mean, then
@@ -206,7 +189,7 @@ __global__ __launch_bounds__(kQpThreads) void k_qp_rows(const int32_t* __restric
     const int32_t* po = o + u.row * g.ns;
     const int32_t* pd = d + u.row * g.ns;
     auto row_sum = [&](long long part) -> long long {  // the sum over the unit's lanes, in every lane
-        const unsigned long long s = qp_wave_sum((unsigned long long)part);
+        const unsigned long long s = q_wave_sum((unsigned long long)part);
         if (L == (uint32_t)kWave) return (long long)s;
         if ((tid & (kWave - 1)) == 0) s_sum[tid / kWave] = s;
         __syncthreads();
@@ -215,7 +198,7 @@ __global__ __launch_bounds__(kQpThreads) void k_qp_rows(const int32_t* __restric
         for (uint32_t w = 0; w < kQpWaves; ++w) t += s_sum[w];
         return (long long)t;
     };
-    QpTerms T;
+    QTerms T;
     long long total;
     if (REGS) {
         const uint32_t head = qp_head(po, n);
@@ -254,71 +237,21 @@ __global__ __launch_bounds__(kQpThreads) void k_qp_rows(const int32_t* __restric
         qp_walk<true>(po, pd, n, l, L, [&](int32_t ov, int32_t dv) { T.add(ov, dv, mean); });
     }
     if (l == 0 && u.active) sums[u.row] = total;
-    unsigned long long v[4] = {T.lo, T.hi, (unsigned long long)T.sr, T.sa};
-    qp_flush(v, u.active ? (uint32_t)(u.row / g.nch) : ~0u, acc, s_red, s_blk);
+    qp_flush(T, u.active ? (uint32_t)(u.row / g.nch) : ~0u, acc, s_red, s_blk);
 }
 
-// A flagged block in the reference's own order: k_q_seq (quality.hip) with chunk k = up to kQChunk consecutive words of a row.
+// A flagged block in the reference's own order: the chain of k_q_seq (quality.hip: q_seq_chain), a chunk up to kQChunk consecutive words of a row.
 __global__ __launch_bounds__(kQThreads) void k_qp_seq(const int32_t* __restrict__ o, const int32_t* __restrict__ d, uint32_t nch, uint32_t ns,
                                                      const long long* __restrict__ sums, const unsigned long long* __restrict__ acc,
                                                      const uint32_t* __restrict__ flag, double* __restrict__ prdn, double* __restrict__ mse_out,
                                                      double* __restrict__ ref_out) {
     const uint32_t b = blockIdx.x, fl = flag[b];
     if (!fl) return;
-    __shared__ double s_t[2][kQChunk], s_r[2][kQChunk];
-    const uint32_t tid = threadIdx.x;
-    const bool need_m = (fl & 1u) != 0, need_r = (fl & 2u) != 0;
     const uint64_t row0 = (uint64_t)b * nch;
-    const uint32_t cpc = (ns + kQChunk - 1) / kQChunk;  // chunks per channel
-    const uint64_t nchunks = (uint64_t)nch * cpc;
-    auto produce = [&](uint64_t k, uint32_t t0, uint32_t nt) {
-        const uint32_t c = (uint32_t)(k / cpc), s0 = (uint32_t)(k - (uint64_t)c * cpc) * kQChunk;
-        const uint32_t n = ns - s0 < kQChunk ? ns - s0 : kQChunk;
-        const int32_t mean = mean_from_sum(sums[row0 + c], ns);
-        const uint64_t at = (row0 + c) * ns + s0;
-        double* pt = s_t[k & 1];
-        double* pr = s_r[k & 1];
-        for (uint32_t i = t0; i < n; i += nt) {
-            int32_t t, r;
-            q_terms(o[at + i], d[at + i], mean, t, r);
-            if (need_m) pt[i] = __dmul_rn((double)t, (double)t);
-            if (need_r) pr[i] = (double)r;
-        }
-    };
-    produce(0, tid, kQThreads);
-    __syncthreads();
-    double mse = 0.0, ref = 0.0;
-    for (uint64_t k = 0; k < nchunks; ++k) {
-        if (tid >= kWave) {
-            if (k + 1 < nchunks) produce(k + 1, tid - kWave, kQThreads - kWave);
-        } else if (tid == 0) {
-            const uint32_t s0 = (uint32_t)(k % cpc) * kQChunk;
-            const uint32_t n = ns - s0 < kQChunk ? ns - s0 : kQChunk;
-            const double* pt = s_t[k & 1];
-            const double* pr = s_r[k & 1];
-            if (need_m && need_r) {
-#pragma unroll 8
-                for (uint32_t i = 0; i < n; ++i) {
-                    mse = __dadd_rn(mse, pt[i]);
-                    ref = __dadd_rn(ref, pr[i]);
-                }
-            } else if (need_m) {
-#pragma unroll 8
-                for (uint32_t i = 0; i < n; ++i) mse = __dadd_rn(mse, pt[i]);
-            } else {
-#pragma unroll 8
-                for (uint32_t i = 0; i < n; ++i) ref = __dadd_rn(ref, pr[i]);
-            }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (!need_m) q_s2_exact(acc + (uint64_t)b * 4, mse);
-        if (!need_r) q_sr_exact(acc + (uint64_t)b * 4, ref);
-        prdn[b] = q_prdn(mse, ref);
-        if (mse_out) mse_out[b] = mse;
-        if (ref_out) ref_out[b] = ref;
-    }
+    q_seq_chain(b, nch, ns, sums + row0, acc, fl, prdn, mse_out, ref_out, [&](uint32_t c, uint32_t s) {
+        const uint64_t at = (row0 + c) * ns + s;
+        return QPair{o[at], d[at]};
+    });
 }
 
 }  // namespace rspt

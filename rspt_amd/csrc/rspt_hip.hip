@@ -668,7 +668,7 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
         ok &= hipMalloc(w.fft_scratch.out(), w.fft_bpp * per_block) == hipSuccess;
         ok &= hipMalloc(w.mean_i32.out(), max_blocks * (size_t)g.nch * sizeof(int32_t)) == hipSuccess;
     }
-    ok &= hipMalloc(w.quality.out(), max_blocks * ((size_t)g.nch + 5) * sizeof(unsigned long long)) == hipSuccess;
+    ok &= hipMalloc(w.quality.out(), max_blocks * quality_words(g.nch) * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) return RSPT_HIP_ERR_ALLOC;
     // the clean-plane invariant starts from zeroed planes
     HIPCHK(p, hipMemset(w.planes, 0, slots * kMaxPlanes * g.plane_stride + 4096));

@@ -151,6 +151,32 @@ def ref_seq_case():
     return c
 
 
+# The sequential chain at the sample widths below int32: the smallest blocks whose sum t^2 leaves 2^53 (path 1, need_m, a finite
+# PRDN).  int24: one sample past a chunk of 1024 (a second chunk of one sample), and two channels of three chunks, where the channel
+# changes between chunks.  int16: t^2 < 2^32, so no block below 2^21 samples can be flagged; full-scale samples against their
+# complements reach 2^53 at 2300000.  int8 cannot be flagged at all (t^2 <= 2^16 would need 2^37 samples), so it has no case.
+SEQ_WIDTH_CASES = [dict(name="seq1x1025_i24", bps=3, nch=1, ns=1025), dict(name="seq2x2049_i24", bps=3, nch=2, ns=2049),
+                   dict(name="seq1x2300000_i16", bps=2, nch=1, ns=2300000)]
+_seq_width = {}
+
+
+def seq_width_case(name):
+    """the case of SEQ_WIDTH_CASES with its two blocks; int24 ones with `calm`, an unflagged pair (orig, dec) of the same shape"""
+    if name not in _seq_width:
+        c = dict(next(c for c in SEQ_WIDTH_CASES if c["name"] == name))
+        bps, nch, ns = c["bps"], c["nch"], c["ns"]
+        if bps == 3:
+            c["orig"] = cases._rand_native(nch, ns, 3, 2103, 1 << 22)
+            c["dec"] = _noisy(c["orig"], 3, nch, ns, 2153, 1 << 23)
+            calm = cases._rand_native(nch, ns, 3, 2104, 1 << 22)
+            c["calm"] = (calm, _noisy(calm, 3, nch, ns, 2154, 200))
+        else:
+            o = np.where(cases.hash_i32(ns, 2200, 2) >= 0, 32767, -32768).astype(np.int16)
+            c["orig"], c["dec"] = o.view(np.uint8), (-1 - o).view(np.uint8)
+        _seq_width[name] = c
+    return _seq_width[name]
+
+
 def lossy_fixtures():
     """every dct and hadamard fixture of tests/cases.py"""
     return [c for c in cases.packer_cases() if c["kind"] in ("dct", "hadamard")]

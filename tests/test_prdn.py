@@ -109,6 +109,21 @@ def test_stored_prdn_of_the_lossy_fixtures_is_reproduced(golden, record, pcases,
         assert abs(p - g["prdn"]) < 1e-9
 
 
+SEQ_WIDTH = [c["name"] for c in pc.SEQ_WIDTH_CASES]
+
+
+@pytest.mark.parametrize("name", SEQ_WIDTH)
+def test_the_narrow_sequential_cases_are_flagged(name):
+    """by the restatement alone: sum t^2 > 2^53 (so the chain computes mse), a finite figure; the int24 companion is not flagged"""
+    c = pc.seq_width_case(name)
+    p, mse, ref, path, info = pc.prdn_parts(c["orig"], c["dec"], c["bps"], c["nch"], c["ns"])
+    print(name, pc.hexbits(p), "s2 / 2^53 =", info["s2"] / pc.EXACT_LIMIT)
+    assert path == 1 and info["need_m"] and not info["need_r"] and np.isfinite(p) and p > 0
+    assert c["bps"] < 4 and {c["bps"] for c in pc.SEQ_WIDTH_CASES} == {2, 3}
+    if c["bps"] == 3:
+        assert c["ns"] % 1024 == 1 and pc.prdn_parts(*c["calm"], 3, c["nch"], c["ns"])[3] == 0
+
+
 def test_finish_follows_ieee():
     assert pc.bits(pc.finish(0.0, 0.0)) == pc.NAN_BITS and pc.bits(pc.finish(4.0, -1.0)) == pc.NAN_BITS
     assert pc.finish(4.0, 0.0) == float("inf") and pc.bits(pc.finish(0.0, 5.0)) == 0
@@ -207,6 +222,47 @@ def test_gpu_mixed_batch_takes_each_path_where_it_must(api, orc):
     for k, t in enumerate((p, mse, ref)):
         assert _u64(t).tolist() == [pc.bits(w[k]) for w in want], k
     assert _u64(p).tolist() == _orc_bits(orc, o, d, nb, 4, nch, ns).tolist()
+    pk.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SEQ_WIDTH)
+def test_gpu_sequential_chain_at_every_width(api, orc, name):
+    """k_q_seq at 2 and 3 bytes per sample (the record's sequential cases are all int32): as it is, big-endian, int24 also one byte
+    off a 16-byte boundary (the chain's byte-wise fetch) and as the outer blocks of a batch around an unflagged block"""
+    import torch
+
+    c = pc.seq_width_case(name)
+    bps, nch, ns, orig, dec = (c[k] for k in ("bps", "nch", "ns", "orig", "dec"))
+
+    def want_of(o, d):
+        w = pc.prdn_parts(o, d, bps, nch, ns)
+        assert pc.bits(w[0]) == pc.bits(orc.prdn(o, d, ns, nch, bps))
+        return pc.bits(w[0]), pc.bits(w[1]), pc.bits(w[2]), w[3]
+
+    def run(o, d):
+        p, mse, ref, path = pk.prdn_batch(o, d, parts=True)
+        torch.cuda.synchronize()
+        return list(zip(_u64(p).tolist(), _u64(mse).tolist(), _u64(ref).tolist(), path.cpu().tolist()))
+
+    def off_by_one(a):
+        buf = torch.zeros(a.size + 16, dtype=torch.uint8, device="cuda")
+        assert buf.data_ptr() % 16 == 0
+        buf[1 : 1 + a.size] = _dev(a)
+        return buf[1 : 1 + a.size]
+
+    want = want_of(orig, dec)
+    assert want[3] == 1
+    pk = api.new_hzr(bps, nch, ns)
+    assert run(_dev(orig), _dev(dec)) == [want]
+    if bps == 3:
+        assert run(off_by_one(orig), off_by_one(dec)) == [want], "one byte off"
+        calm = want_of(*c["calm"])
+        assert calm[3] == 0
+        got = run(_dev(np.concatenate([orig, c["calm"][0], orig])), _dev(np.concatenate([dec, c["calm"][1], dec])))
+        assert got == [want, calm, want], "the flag is per block"
+    pk.set_byte_order(True)
+    assert run(_dev(cases.reverse_samples(orig, bps)), _dev(cases.reverse_samples(dec, bps))) == [want], "big-endian"
     pk.close()
 
 

@@ -286,6 +286,26 @@ def test_gpu_identity_with_the_native_entry(api, nch, ns):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", [c["name"] for c in pc.SEQ_WIDTH_CASES])
+def test_gpu_identity_with_the_native_entry_on_flagged_blocks(api, name):
+    """the narrow sequential cases (tests/prdn_cases.py) as int32 matrices, on and off a 16-byte boundary: k_qp_seq gives the four
+    words k_q_seq gives at the case's own width, which are the restatement's"""
+    import torch
+
+    c = pc.seq_width_case(name)
+    O, D = pp.planar_of(c)
+    w = pc.prdn_parts(c["orig"], c["dec"], c["bps"], c["nch"], c["ns"])
+    want = ([pc.bits(w[0])], [pc.bits(w[1])], [pc.bits(w[2])], [w[3]])
+    assert w[3] == 1 and want == _want(O[None], D[None])
+    pk = api.new_hzr(c["bps"], c["nch"], c["ns"])
+    o, d = (torch.from_numpy(np.ascontiguousarray(c[k])).cuda() for k in ("orig", "dec"))
+    assert _got(pk.prdn_batch(o, d, parts=True)) == want
+    for off in (0, 4):
+        assert _got(pk.prdn_planar_batch(_at(O[None], off), _at(D[None], off), parts=True)) == want, off
+    pk.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kind,nch,ns", [("hadamard",) + s for s in pl.HADAMARD_SHAPES[:2]] + [("dct",) + s for s in pl.DCT_SHAPES[:3]])
 def test_gpu_round_trip(api, orc, kind, nch, ns):
     import torch
