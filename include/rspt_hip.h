@@ -263,6 +263,58 @@ int rspt_hip_compress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nb
 int rspt_hip_decompress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, void* d_dst,
                                   uint64_t* d_consumed, void* stream);
 
+/* ---- a quality ladder and a per-block choice: the lossy packers' quality chosen block by block, on the device ----
+ * ladder    host array of nladder = 1..8 qualities.  Every entry is validated as rspt_hip_set_quantizer validates its quality for
+ *           the handle's kind and ns (RSPT_HIP_ERR_ARG, nothing launched), and turned into the kernels' quantiser on the host
+ *           with the same arithmetic; the entries travel as kernel arguments -- nothing is copied to the device and nothing is
+ *           allocated per call.
+ * d_choice  device array of nblocks uint32 (4-byte aligned): block b takes ladder[d_choice[b]].
+ * Block b's stream, d_sizes[b] and decoded samples are byte for byte what rspt_hip_set_quantizer(p, ladder[d_choice[b]], nb)
+ * followed by rspt_hip_compress_batch_dev / rspt_hip_decompress_batch_dev gives for that block, nb being the handle's current
+ * one for every block.  An entry of quality 1 on a hadamard handle gives the all-integer kernels' stream: (int)((double)y / n)
+ * is the truncating division for n = 2^k.  The handle's own quality is neither read nor changed.  The choice is not in the
+ * stream: the decoder must be given the one the encoder had.
+ * d_choice[b] >= nladder: nothing is written for block b and d_sizes[b] is exactly bit 63 (compress) / bit 63 is added to
+ * d_consumed[b] (decompress); the other blocks are not affected.
+ * RSPT_HIP_KIND_HADAMARD at every row length, and RSPT_HIP_KIND_DCT where the dense table runs.  RSPT_HIP_ERR_UNSUPPORTED, before
+ * anything is launched: a dct handle on the FFT path (rows beyond the dense table, or RSPT_HIP_DCT_FORCE_FFT) -- the FFT kernels
+ * do not read a ladder yet -- and every other kind.  Everything else -- the ordering contract, the refusals, the 16-byte
+ * d_src, the workspace of rspt_hip_reserve -- is as in rspt_hip_compress_batch_dev / rspt_hip_decompress_batch_dev; a
+ * dst_stride of 2^32 bytes per 65536 samples of a block or more is RSPT_HIP_ERR_ARG (no stream is a thousandth of that). */
+int rspt_hip_compress_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, const double* ladder, size_t nladder,
+                                       const uint32_t* d_choice, void* d_dst, size_t dst_stride, uint64_t* d_sizes, void* stream);
+int rspt_hip_decompress_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, const double* ladder,
+                                         size_t nladder, const uint32_t* d_choice, void* d_dst, uint64_t* d_consumed, void* stream);
+
+/* ---- compress to a PRDN target: the smallest stream of a ladder whose PRDN is at most target_prdn, block by block ----
+ * The rule.  For block b and ladder entry k: o is the native block, d_k what decompress(compress(o)) gives at ladder[k] and the
+ * handle's nb, and (prdn_k, mse_k, path_k) what rspt_hip_prdn_batch_dev(o, d_k) gives.  Entry k MEETS THE TARGET iff
+ * path_k == 0 and (mse_k == 0 or prdn_k <= target_prdn): a NaN never meets it, and neither does a candidate whose figure needs
+ * the sequential path (an exact sum above 2^53).  d_choice[b] is the first k in ladder order that meets the target -- order
+ * the ladder coarse to fine; nothing assumes that PRDN is monotonic in it -- and nladder - 1 if no entry does.  d_prdn[b]
+ * (optional) is prdn of the chosen entry, bit for bit rspt_hip_prdn_batch_dev's where its path is 0, and +inf where it is 1.
+ * Streams and sizes are then those of rspt_hip_compress_batch_ladder_dev with that d_choice, which is the caller's to keep: the
+ * decoder needs it.
+ * The candidates run the kernels of a compress and a decompress call without the hzr stage (it changes no value): the front
+ * end once, then per entry the forward transform, the cut to nb bytes, the way back, the cut to the sample width and the PRDN
+ * kernels against the kept original.
+ * target_prdn must be finite and > 0 (RSPT_HIP_ERR_ARG); ladder, kinds and refusals as rspt_hip_compress_batch_ladder_dev;
+ * nblocks <= 65535.  Asynchronous on `stream`, no host synchronisation inside (beyond rspt_hip_reserve's when the workspace
+ * grows), stream-ordered with every other call on the handle; the handle's own quantiser is neither used nor changed.
+ * d_work: device memory, 16-byte aligned, at least the bytes rspt_hip_compress_target_work_bytes names for (nblocks, nladder)
+ * -- all scratch beyond the handle's workspace; contents unspecified afterwards. */
+int rspt_hip_compress_target_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t nladder, size_t* bytes);
+int rspt_hip_compress_target_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, const double* ladder, size_t nladder,
+                                       double target_prdn, void* d_dst, size_t dst_stride, uint64_t* d_sizes, uint32_t* d_choice,
+                                       double* d_prdn, void* d_work, void* stream);
+/* The candidates take one of two routes, picked from the handle's shape alone; both give the same d_choice, d_prdn and streams
+ * bit for bit.  general: every supported shape, the existing kernels per ladder entry as described above.  fused: hadamard rows
+ * of up to 8192 points with nch * ns < 2^22 (under which every reference sum of the PRDN is exact) -- one kernel reads each row
+ * once, keeps its mean and its transform in LDS and walks the ladder there, and the PRDN stage's own finishing kernel turns its
+ * exact sums into the figures.  For tests: route 0 = the host's choice (default), 1 = general, 2 = fused
+ * (RSPT_HIP_ERR_UNSUPPORTED where the fused probe does not run; RSPT_HIP_ERR_ARG for any other value). */
+int rspt_hip_debug_set_target_route(rspt_hip_packer* p, int route);
+
 /* ---- planar int32 in and out: samples that already live in a [nblocks][nch][ns] int32 matrix skip the native block ----
  * d_planar is what rspt_hip_native_to_i32_batch_dev writes and rspt_hip_i32_to_native_batch_dev reads: block b's channel c at
  * d_planar + (b*nch + c)*ns.  It must be 4-byte aligned; 16-byte aligned buffers take the widest accesses.  The contract is two

@@ -56,6 +56,11 @@ C_ABI = {
     "rspt_hip_reserve": (_i, [_p, _z]),
     "rspt_hip_compress_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_decompress_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
+    "rspt_hip_compress_batch_ladder_dev": (_i, [_p, _p, _z, _dp, _z, _p, _p, _z, _p, _p]),
+    "rspt_hip_decompress_batch_ladder_dev": (_i, [_p, _p, _z, _z, _dp, _z, _p, _p, _p, _p]),
+    "rspt_hip_compress_target_work_bytes": (_i, [_p, _z, _z, _szp]),
+    "rspt_hip_compress_target_batch_dev": (_i, [_p, _p, _z, _dp, _z, _d, _p, _z, _p, _p, _p, _p, _p]),
+    "rspt_hip_debug_set_target_route": (_i, [_p, _i]),
     "rspt_hip_compress_planar_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_decompress_planar_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
     "rspt_hip_decompress_packed_planar_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
@@ -371,11 +376,23 @@ class SignalPacker:
     def reserve(self, nblocks):
         self._check("rspt_hip_reserve", self._L.rspt_hip_reserve(self._h, nblocks))
 
-    def compress_batch(self, d_src, d_dst=None, d_sizes=None, dst_stride=None, stream=None):
-        """d_src: uint8 cuda tensor [nblocks, block_bytes].  Returns (d_dst, d_sizes);
-        asynchronous on `stream` (default: torch's current stream)."""
+    def _ladder_args(self, ladder, choice, nblocks):
+        """(double*, count, device pointer) of a ladder call: `ladder` a sequence of 1..8 qualities, `choice` a torch.int32 cuda
+        tensor [nblocks] of indices into it (rspt_hip.h: rspt_hip_compress_batch_ladder_dev)"""
         import torch
 
+        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+        assert choice.is_cuda and choice.dtype == torch.int32 and choice.is_contiguous() and choice.numel() == nblocks
+        return lad, (_dptr(lad), lad.size, choice.data_ptr())
+
+    def compress_batch(self, d_src, d_dst=None, d_sizes=None, dst_stride=None, stream=None, ladder=None, choice=None):
+        """d_src: uint8 cuda tensor [nblocks, block_bytes].  Returns (d_dst, d_sizes);
+        asynchronous on `stream` (default: torch's current stream).
+        ladder, choice (both or neither; dct / hadamard): block b is compressed at quality ladder[choice[b]], whatever the
+        handle's own -- choice a torch.int32 cuda tensor [nblocks]; an index outside the ladder sets bit 63 of d_sizes[b]."""
+        import torch
+
+        assert (ladder is None) == (choice is None)
         nblocks = self._nblocks(d_src)
         if dst_stride is None:
             dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
@@ -384,14 +401,58 @@ class SignalPacker:
         if d_sizes is None:
             d_sizes = torch.empty(nblocks, dtype=torch.int64, device=d_src.device)
         st = self._stream(stream, d_src.device)
-        self._call("rspt_hip_compress_batch_dev", d_src.data_ptr(), nblocks, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
+        if ladder is not None:
+            lad, largs = self._ladder_args(ladder, choice, nblocks)
+            self._call("rspt_hip_compress_batch_ladder_dev", d_src.data_ptr(), nblocks, *largs, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
+        else:
+            self._call("rspt_hip_compress_batch_dev", d_src.data_ptr(), nblocks, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
         return d_dst, d_sizes
 
-    def decompress_batch(self, d_streams, nblocks, src_stride, d_out=None, d_consumed=None, stream=None):
+    def decompress_batch(self, d_streams, nblocks, src_stride, d_out=None, d_consumed=None, stream=None, ladder=None, choice=None):
+        """ladder, choice: as compress_batch -- the decoder needs the choice the encoder had, it is not in the stream"""
+        assert (ladder is None) == (choice is None)
         d_out, d_consumed = self._decode_buffers(nblocks, d_streams.device, d_out, d_consumed, False)
         st = self._stream(stream, d_streams.device)
-        self._call("rspt_hip_decompress_batch_dev", d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
+        if ladder is not None:
+            lad, largs = self._ladder_args(ladder, choice, nblocks)
+            self._call("rspt_hip_decompress_batch_ladder_dev", d_streams.data_ptr(), src_stride, nblocks, *largs, d_out.data_ptr(),
+                       d_consumed.data_ptr(), st)
+        else:
+            self._call("rspt_hip_decompress_batch_dev", d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
         return d_out, d_consumed
+
+    def target_work_bytes(self, nblocks, nladder):
+        return self._bytes("rspt_hip_compress_target_work_bytes", int(nblocks), int(nladder))
+
+    def debug_set_target_route(self, route):
+        """compress_to_prdn's route, for tests: 0 the host's choice, 1 general, 2 the fused probe (rspt_hip_debug_set_target_route)"""
+        self._call("rspt_hip_debug_set_target_route", int(route))
+
+    def compress_to_prdn(self, d_src, target, ladder, work=None, stream=None, d_dst=None, dst_stride=None):
+        """The smallest stream of a quality ladder whose PRDN is at most `target` percent, block by block (rspt_hip.h:
+        rspt_hip_compress_target_batch_dev): block b takes the first entry of `ladder` (ordered coarse to fine) whose round trip
+        meets the target, and the last one if none does.  One asynchronous call; no hzr stage runs for a candidate.
+        work: a device tensor of at least target_work_bytes(nblocks, len(ladder)) bytes, 16-byte aligned; None: allocated here.
+        Returns (d_dst, d_sizes, d_choice, d_prdn): streams and sizes as compress_batch(ladder=, choice=d_choice) writes them,
+        the chosen indices (torch.int32; decompress_batch needs them) and the chosen entries' PRDN (float64)."""
+        import torch
+
+        nblocks = self._nblocks(d_src)
+        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+        dev = d_src.device
+        if dst_stride is None:
+            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
+        if d_dst is None:
+            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=dev)
+        d_sizes = torch.empty(nblocks, dtype=torch.int64, device=dev)
+        d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        d_prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
+        if work is None:
+            work = torch.empty((self.target_work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
+        assert work.is_cuda and work.is_contiguous()
+        self._call("rspt_hip_compress_target_batch_dev", d_src.data_ptr(), nblocks, _dptr(lad), lad.size, float(target), d_dst.data_ptr(),
+                   dst_stride, d_sizes.data_ptr(), d_choice.data_ptr(), d_prdn.data_ptr(), work.data_ptr(), self._stream(stream, dev))
+        return d_dst, d_sizes, d_choice, d_prdn
 
     def _decode_buffers(self, nblocks, device, d_out, d_consumed, planar):
         """(d_out, d_consumed) of a decompress call, allocated where None: the native batch (uint8 [nblocks, block_bytes]) or,

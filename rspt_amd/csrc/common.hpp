@@ -56,6 +56,15 @@ struct Geom {
     uint64_t block_bytes;   // bps*nch*ns
 };
 
+// A quality ladder of the lossy packers (rspt_hip_compress_batch_ladder_dev), passed to kernels by value: for each of its n <= 8
+// entries the quantiser the host made of the entry's quality -- hadamard: a = the divisor of the direction (n / q forward, q
+// inverse); dct: a = scale0, b = scale1 forward, b = the inverse scale on the way back.  Block b takes entry choice[b].
+constexpr uint32_t kMaxLadder = 8;
+struct QLadder {
+    double a[kMaxLadder], b[kMaxLadder];
+    uint32_t n;
+};
+
 // Decomposition of the sliding-window stages (k_fir, k_med_short; the host's win_geom makes it), passed to their kernels by
 // value: a workgroup takes one span of rows of one channel group of one block, lane <-> (channel, run of consecutive outputs),
 // channel fastest.  k_fir_halo reads the spans from it, the median's generic kernels only the block's shape and K.

@@ -1,4 +1,4 @@
-// The body of k_fwht64k and k_fwht64k_q (transforms.hip), included into both so that the quality-1 kernel stays the code that
+// The body of k_fwht64k, k_fwht64k_q and k_fwht64k_l (transforms.hip), included into each so that the quality-1 kernel stays the code that
 // was timed.  From the kernel: planar, g, means, planes, nzflag, nplanes; QUANT (constexpr bool) and, where it is set, div.
     extern __shared__ __attribute__((aligned(16))) int32_t sh_i[];
     uint32_t* sh = reinterpret_cast<uint32_t*>(sh_i);

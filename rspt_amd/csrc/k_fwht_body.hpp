@@ -1,4 +1,4 @@
-// The body of k_fwht and k_fwht_q (transforms.hip), included into both so that the quality-1 kernel stays the code that was
+// The body of k_fwht, k_fwht_q and k_fwht_l (transforms.hip), included into each so that the quality-1 kernel stays the code that was
 // timed.  From the kernel: planar, g, means; QUANT (constexpr bool) and, where it is set, div (the kernel's last argument).
     extern __shared__ __attribute__((aligned(16))) int32_t sh[];
     __shared__ long long s_red[16];

@@ -1,4 +1,4 @@
-// The body of k_fwht_cross and k_fwht_cross_q (transforms.hip), included into both so that the quality-1 kernel stays the code
+// The body of k_fwht_cross, k_fwht_cross_q and k_fwht_cross_l (transforms.hip), included into each so that the quality-1 kernel stays the code
 // that was timed.  From the kernel: planar, g, means, mean_i32, m, stride, last; QUANT (constexpr bool) and, where set, div.
     const uint32_t c = blockIdx.y, b = blockIdx.z, n = g.ns;
     int32_t* row = planar + (size_t)b * g.N + (size_t)c * n;

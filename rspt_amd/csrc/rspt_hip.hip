@@ -6,7 +6,8 @@
 // which lives in device memory so that batches chain without a host round trip.
 // There is no CPU path: every entry point fails loudly if the device is missing.
 // Here: create / reserve / destroy, the compress phases, the decoder, the single-block entries.  Included at the end: host_pipeline.hip
-// (compress_many / decompress_many / feed), host_gather.hip (RCCL), host_stages.hip (IIR, FIR, median, peak, PRDN, converters).
+// (compress_many / decompress_many / feed), host_gather.hip (RCCL), host_stages.hip (IIR, FIR, median, peak, PRDN, converters),
+// host_target.hip (compress to a PRDN target).
 #include "../../include/rspt_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -47,6 +48,7 @@
 #include "convert.hip"
 #include "bytes.hip"
 #include "planar.hip"
+#include "target.hip"
 
 using namespace rspt;
 
@@ -292,7 +294,7 @@ static void launch_dct_fft(rspt_hip_packer* p, uint32_t B, const int32_t* in, in
 
 // WHT of rows longer than 65536 points, in place in `planar` (transforms.hip: k_fwht_seg / k_fwht_cross)
 template <bool FORWARD>
-static void launch_fwht_big(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
+static void launch_fwht_big(rspt_hip_packer* p, uint32_t B, hipStream_t st, const QLadder* lad = nullptr, const uint32_t* choice = nullptr) {
     const Geom& g = p->g;
     const uint32_t segs = g.ns >> 15;  // 32768-point pieces per row: 4 .. 128
     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_seg), hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4);
@@ -301,7 +303,9 @@ static void launch_fwht_big(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
     // the last cross pass ends the transform: the truncating /n or + mean, or the general quantiser (k_fwht_cross_q)
     auto cross = [&](uint32_t m, uint32_t stride, uint32_t last) {
         const dim3 grid(g.ns / m / 256u, g.nch, B);
-        if (last && p->had_quant)
+        if (last && lad)  // a ladder call: the divisor of each block's own entry (k_fwht_cross_l)
+            hipLaunchKernelGGL((k_fwht_cross_l<FORWARD>), grid, dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m, stride, last, *lad, choice);
+        else if (last && p->had_quant)
             hipLaunchKernelGGL((k_fwht_cross_q<FORWARD>), grid, dim3(256), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32, m, stride, last,
                                FORWARD ? p->had_div_fwd : p->had_div_inv);
         else
@@ -315,34 +319,83 @@ static void launch_fwht_big(rspt_hip_packer* p, uint32_t B, hipStream_t st) {
 // scales (signal_packer_dct.cpp:84, 97: `Cs[i] * ratio1 / quality` with Cs a float, `ratio1 * quality`) or the two hadamard
 // divisors (fwht.c:33, 39: `n / ratio` with n an int, `ratio`).  Shared by rspt_hip_packer_create and rspt_hip_set_quantizer.
 // false, and the handle as it was: a quality the arithmetic cannot take -- not finite, not > 0, or one that leaves a scale or
-// a divisor that is not finite and non-zero.  commit = false only asks whether q can be taken.
-static bool set_quality(rspt_hip_packer* p, double q, bool commit = true) {
+// a divisor that is not finite and non-zero.  commit = false only asks whether q can be taken.  quantizer_of is the arithmetic
+// alone, for a handle's shape: the ladder entries take theirs from it too.
+struct Quantizer {
+    double dct_scale0, dct_scale1, idct_scale;
+    float dct_cs0;
+    double had_div_fwd, had_div_inv;
+};
+static bool quantizer_of(const Geom& g, double q, Quantizer* out) {
     auto usable = [](double v) { return std::isfinite(v) && v != 0.0; };
     if (!std::isfinite(q) || !(q > 0.0)) return false;
-    if (p->g.kind == RSPT_HIP_KIND_DCT) {
-        const double ratio1 = sqrt(2.0 / (double)(int)p->g.ns);
+    Quantizer z{};
+    if (g.kind == RSPT_HIP_KIND_DCT) {
+        const double ratio1 = sqrt(2.0 / (double)(int)g.ns);
         const float cs0 = (float)(1 / sqrt(2));
-        const double s0 = cs0 * ratio1 / q;   // Cs[0]*ratio1/quality (dct.cpp:84)
-        const double s1 = 1.0f * ratio1 / q;  // Cs[i>0] = 1
-        const double si = ratio1 * q;         // dct.cpp:97
-        if (!usable(s0) || !usable(s1) || !usable(si)) return false;
-        if (!commit) return true;
-        p->dct_cs0 = cs0;
-        p->dct_scale0 = s0;
-        p->dct_scale1 = s1;
-        p->idct_scale = si;
-    } else if (p->g.kind == RSPT_HIP_KIND_HADAMARD) {
-        const double fdiv = (double)(int)p->g.ns / q;  // fwht_normalize: src[i] /= (n / ratio)
-        if (!usable(fdiv)) return false;
-        if (!commit) return true;
-        p->had_div_fwd = fdiv;
-        p->had_div_inv = q;     // fwht_normalize2: src[i] /= ratio
-        p->had_quant = q != 1.0;  // quality 1: the all-integer kernels (truncating /n, and no division on the way back)
+        z.dct_cs0 = cs0;
+        z.dct_scale0 = cs0 * ratio1 / q;   // Cs[0]*ratio1/quality (dct.cpp:84)
+        z.dct_scale1 = 1.0f * ratio1 / q;  // Cs[i>0] = 1
+        z.idct_scale = ratio1 * q;         // dct.cpp:97
+        if (!usable(z.dct_scale0) || !usable(z.dct_scale1) || !usable(z.idct_scale)) return false;
+    } else if (g.kind == RSPT_HIP_KIND_HADAMARD) {
+        z.had_div_fwd = (double)(int)g.ns / q;  // fwht_normalize: src[i] /= (n / ratio)
+        z.had_div_inv = q;                      // fwht_normalize2: src[i] /= ratio
+        if (!usable(z.had_div_fwd)) return false;
     } else {
         return false;
     }
+    *out = z;
+    return true;
+}
+
+static bool set_quality(rspt_hip_packer* p, double q, bool commit = true) {
+    Quantizer z;
+    if (!quantizer_of(p->g, q, &z)) return false;
+    if (!commit) return true;
+    if (p->g.kind == RSPT_HIP_KIND_DCT) {
+        p->dct_cs0 = z.dct_cs0;
+        p->dct_scale0 = z.dct_scale0;
+        p->dct_scale1 = z.dct_scale1;
+        p->idct_scale = z.idct_scale;
+    } else {
+        p->had_div_fwd = z.had_div_fwd;
+        p->had_div_inv = z.had_div_inv;
+        p->had_quant = q != 1.0;  // quality 1: the all-integer kernels (truncating /n, and no division on the way back)
+    }
     p->quality = q;
     return true;
+}
+
+// The quantisers of a ladder call (rspt_hip_compress_batch_ladder_dev and its kin): every entry through quantizer_of, as kernel
+// arguments -- nothing goes to the device ahead of the launch.  fwd / inv: what the forward and the inverse transform kernels take.
+struct LadderSel {
+    QLadder fwd, inv;
+    const uint32_t* choice;
+};
+
+// RSPT_HIP_ERR_UNSUPPORTED: a kind or a path the ladder kernels do not cover; RSPT_HIP_ERR_ARG: no ladder, more than kMaxLadder
+// entries, or an entry that rspt_hip_set_quantizer would not take
+static int make_ladder(const rspt_hip_packer* p, const double* ladder, size_t nladder, const uint32_t* d_choice, LadderSel* out) {
+    const Geom& g = p->g;
+    if (g.kind != RSPT_HIP_KIND_HADAMARD && !(g.kind == RSPT_HIP_KIND_DCT && !p->dct_fft)) return RSPT_HIP_ERR_UNSUPPORTED;
+    if (!ladder || nladder < 1 || nladder > kMaxLadder) return RSPT_HIP_ERR_ARG;
+    LadderSel ls{};
+    for (size_t k = 0; k < nladder; ++k) {
+        Quantizer z;
+        if (!quantizer_of(g, ladder[k], &z)) return RSPT_HIP_ERR_ARG;
+        if (g.kind == RSPT_HIP_KIND_DCT) {
+            ls.fwd.a[k] = z.dct_scale0, ls.fwd.b[k] = z.dct_scale1;
+            ls.inv.b[k] = z.idct_scale;
+        } else {
+            ls.fwd.a[k] = z.had_div_fwd;
+            ls.inv.a[k] = z.had_div_inv;
+        }
+    }
+    ls.fwd.n = ls.inv.n = (uint32_t)nladder;
+    ls.choice = d_choice;
+    *out = ls;
+    return RSPT_HIP_OK;
 }
 
 template <int BPS>
@@ -683,6 +736,65 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     return RSPT_HIP_OK;
 }
 
+// The transform of the two lossy packers in a compress call, behind the front end's planar block in ws.planar: the coefficients'
+// low bytes leave as planes.  nzflag: where the plane kernels mark the non-zero segments (a compress call: the zero region).
+// ls: a ladder call -- the transform kernels take each block's quantiser from its ladder entry, not the handle's.
+static void launch_forward_transform(rspt_hip_packer* p, uint32_t B, hipStream_t st, uint32_t* nzflag, const LadderSel* ls) {
+    const Geom& g = p->g;
+    const uint32_t lossy_nb = p->nb_host;  // nr_bytes_to_compress_ of the lossy packers (rspt_hip_set_quantizer): they never escalate
+    if (g.kind == RSPT_HIP_KIND_HADAMARD) {
+        // per channel: mean removal, WHT, truncating /n (signal_packer_hadamard.cpp:57-72); with a quality other than 1 the
+        // kernels that divide by n / quality instead (transforms.hip: QUANT)
+        const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
+        if (g.ns > 65536u) {  // two passes over the planar row (any 2^k the reference's own transform takes, fwht.c:4-28)
+            hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32);
+            launch_fwht_big<true>(p, B, st, ls ? &ls->fwd : nullptr, ls ? ls->choice : nullptr);
+            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, lossy_nb, p->ws.planes, nzflag, (uint32_t*)nullptr);
+        } else if (g.ns == 65536u) {  // the whole row in registers: read once, and the byte planes written straight from them
+            if (ls) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_l<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht64k_l<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, nzflag,
+                                   lossy_nb, ls->fwd, ls->choice);
+            } else if (p->had_quant) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_q<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht64k_q<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, nzflag,
+                                   lossy_nb, p->had_div_fwd);
+            } else {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht64k<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, nzflag,
+                                   lossy_nb);
+            }
+        } else {
+            if (ls) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_l<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht_l<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, ls->fwd, ls->choice);
+            } else if (p->had_quant) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_q<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht_q<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->had_div_fwd);
+            } else {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+                hipLaunchKernelGGL((k_fwht<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
+            }
+            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, lossy_nb, p->ws.planes, nzflag, (uint32_t*)nullptr);
+        }
+    } else if (g.kind == RSPT_HIP_KIND_DCT) {
+        if (p->dct_fft) {
+            if (p->have_row_sum)  // the de-interleave pass summed the channels on its way: no second pass over the planar block
+                hipLaunchKernelGGL(k_means_from_sums, dim3((B * g.nch + 255) / 256), dim3(256), 0, st, p->row_sum, g, B, p->ws.means, p->ws.mean_i32);
+            else
+                hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32);
+            launch_dct_fft<true>(p, B, p->ws.planar, p->ws.planar2, st);
+        } else if (ls) {
+            hipLaunchKernelGGL((k_dct_l<true>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means,
+                               p->cos_tab, ls->fwd, ls->choice, p->dct_cs0, p->ws.planar2);
+        } else {
+            hipLaunchKernelGGL((k_dct<true>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means,
+                               p->cos_tab, p->dct_scale0, p->dct_scale1, p->dct_cs0, p->ws.planar2);
+        }
+        hipLaunchKernelGGL((k_planar_planes<true>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar2, g, lossy_nb, p->ws.planes, nzflag, (uint32_t*)nullptr);
+    }
+}
+
 // ---- the compress sequence, phase by phase ----------------------------------------------------------------------------------------
 // (Round 4 measured whether the phases of TWO batches can overlap -- two whole batches racing on two streams, and an ordered
 // schedule with the latency-bound middle of batch i on a second stream beside the front end of batch i+1: neither beats one
@@ -693,7 +805,8 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
 //                                                                                                  small blocks are encoded under the dense trees)
 // encode: k_encode                                                                                (vector-issue bound)
 // d_planar: the source is a planar int32 matrix (rspt_hip_compress_planar_batch_dev) and src is not looked at
-static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, hipStream_t st, const int32_t* d_planar = nullptr) {
+// ls: a ladder call -- the transform kernels take each block's quantiser from its ladder entry, not the handle's
+static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, hipStream_t st, const int32_t* d_planar = nullptr, const LadderSel* ls = nullptr) {
     const Geom& g = p->g;
     const uint32_t B = (uint32_t)nblocks;
     stamp(p, ST_PRE, st);
@@ -734,48 +847,7 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
     }
     const uint32_t np = d_planar ? launch_front_planar(p, d_planar, nblocks, st)
                                  : by_bps(g.bps, [&](auto bps) { return launch_front<decltype(bps)::value>(p, src, nblocks, st); });
-    const uint32_t lossy_nb = p->nb_host;  // nr_bytes_to_compress_ of the lossy packers (rspt_hip_set_quantizer): they never escalate
-    if (g.kind == RSPT_HIP_KIND_HADAMARD) {
-        // per channel: mean removal, WHT, truncating /n (signal_packer_hadamard.cpp:57-72); with a quality other than 1 the
-        // kernels that divide by n / quality instead (transforms.hip: QUANT)
-        const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
-        if (g.ns > 65536u) {  // two passes over the planar row (any 2^k the reference's own transform takes, fwht.c:4-28)
-            hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32);
-            launch_fwht_big<true>(p, B, st);
-            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, lossy_nb, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
-        } else if (g.ns == 65536u) {  // the whole row in registers: read once, and the byte planes written straight from them
-            if (p->had_quant) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_q<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht64k_q<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, p->nzflag,
-                                   lossy_nb, p->had_div_fwd);
-            } else {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht64k<true, true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->ws.planes, p->nzflag,
-                                   lossy_nb);
-            }
-        } else {
-            if (p->had_quant) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_q<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht_q<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->had_div_fwd);
-            } else {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht<true>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
-            }
-            hipLaunchKernelGGL((k_planar_planes<false>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar, g, lossy_nb, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
-        }
-    } else if (g.kind == RSPT_HIP_KIND_DCT) {
-        if (p->dct_fft) {
-            if (p->have_row_sum)  // the de-interleave pass summed the channels on its way: no second pass over the planar block
-                hipLaunchKernelGGL(k_means_from_sums, dim3((B * g.nch + 255) / 256), dim3(256), 0, st, p->row_sum, g, B, p->ws.means, p->ws.mean_i32);
-            else
-                hipLaunchKernelGGL(k_row_means, dim3(g.nch, B), dim3(1024), 0, st, p->ws.planar, g, p->ws.means, p->ws.mean_i32);
-            launch_dct_fft<true>(p, B, p->ws.planar, p->ws.planar2, st);
-        } else {
-            hipLaunchKernelGGL((k_dct<true>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g, p->ws.means,
-                               p->cos_tab, p->dct_scale0, p->dct_scale1, p->dct_cs0, p->ws.planar2);
-        }
-        hipLaunchKernelGGL((k_planar_planes<true>), dim3((g.N + 4095) / 4096, B), dim3(256), 0, st, p->ws.planar2, g, lossy_nb, p->ws.planes, p->nzflag, (uint32_t*)nullptr);
-    }
+    launch_forward_transform(p, B, st, p->nzflag, ls);
     HIPCHK(p, hipGetLastError());
 
     stamp(p, ST_NB, st);
@@ -840,12 +912,12 @@ static int phase_encode(rspt_hip_packer* p, uint32_t B, void* d_dst, size_t dst_
 
 // one batch, start to end on one stream
 static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t nblocks, void* d_dst, size_t dst_stride, uint64_t* d_sizes, hipStream_t st,
-                                 const int32_t* d_planar = nullptr) {
+                                 const int32_t* d_planar = nullptr, const LadderSel* ls = nullptr) {
     int rc = rspt_hip_reserve(p, nblocks);
     if (rc) return rc;
     HIPCHK(p, hipSetDevice(p->device));
     const uint32_t B = (uint32_t)slots_of(p, nblocks);  // what the hzr kernels count in
-    if ((rc = phase_front(p, (const uint8_t*)d_src, nblocks, st, d_planar)) != 0) return rc;
+    if ((rc = phase_front(p, (const uint8_t*)d_src, nblocks, st, d_planar, ls)) != 0) return rc;
     if ((rc = phase_hist(p, B, st)) != 0) return rc;
 
     stamp(p, ST_TREE, st);
@@ -865,10 +937,13 @@ static int compress_batch_serial(rspt_hip_packer* p, const void* d_src, size_t n
         p->ws.zset = zset_next;
         return RSPT_HIP_OK;
     }
+    // a choice outside the ladder: the block's transform has not run; k_layout is made to treat it as a stream that does not fit
+    if (ls) hipLaunchKernelGGL(k_ladder_refuse, dim3(B), dim3(256), 0, st, ls->choice, ls->fwd.n, p->g, (const uint32_t*)p->ws.nbuse, p->ws.meta);
     if ((rc = phase_layout(p, B, d_dst, dst_stride, d_sizes, st)) != 0) return rc;
 
     stamp(p, ST_ENCODE, st);
     if ((rc = phase_encode(p, B, d_dst, dst_stride, st)) != 0) return rc;
+    if (ls) hipLaunchKernelGGL(k_ladder_flag, dim3((B + 255) / 256), dim3(256), 0, st, ls->choice, ls->fwd.n, B, d_sizes, 0u);
     stamp(p, ST_COUNT, st);
     if (p->profiling) p->ev_valid = true;
     HIPCHK(p, hipGetLastError());
@@ -883,6 +958,18 @@ int rspt_hip_compress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nb
     if (reinterpret_cast<uintptr_t>(d_src) & 15) return RSPT_HIP_ERR_ARG;  // tile loads are 16-byte aligned chunks
     if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the handle's workspace until rspt_hip_feed_end)
     return compress_batch_serial(p, d_src, nblocks, d_dst, dst_stride, d_sizes, (hipStream_t)stream);
+}
+
+int rspt_hip_compress_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, const double* ladder, size_t nladder,
+                                       const uint32_t* d_choice, void* d_dst, size_t dst_stride, uint64_t* d_sizes, void* stream) {
+    if (!p || !d_src || !d_dst || !d_sizes || !d_choice || nblocks == 0) return RSPT_HIP_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_src) & 15) || (reinterpret_cast<uintptr_t>(d_choice) & 3)) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;
+    LadderSel ls;
+    if (int rc = make_ladder(p, ladder, nladder, d_choice, &ls)) return rc;
+    // (k_ladder_refuse's payload lengths must exceed the stride: 2^32 per hzr block, where a stream has at most 65543 bytes of one)
+    if ((unsigned long long)dst_stride >> 32 >= p->g.nblk) return RSPT_HIP_ERR_ARG;
+    return compress_batch_serial(p, d_src, nblocks, d_dst, dst_stride, d_sizes, (hipStream_t)stream, nullptr, &ls);
 }
 
 int rspt_hip_compress_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, void* d_dst, size_t dst_stride, uint64_t* d_sizes,
@@ -1067,13 +1154,79 @@ int rspt_hip_compress(rspt_hip_packer* p, const void* src_host, void* dst_host, 
     return RSPT_HIP_OK;
 }
 
+// The decoder behind k_dec_block: the planes of B blocks (ws.planes, dec_nb[b] of them each) -> planar values -> the inverse
+// transform of the lossy packers.  inv_out, inv_sx: where the lossless packers' last inverse pass writes, and its sign extension
+// (the lossy packers' goes to ws.planar, for their transform).  Returns where a lossy packer's planar result lies.
+static const int32_t* launch_inverse(rspt_hip_packer* p, uint32_t B, hipStream_t st, int32_t* inv_out, uint32_t inv_sx, const LadderSel* ls) {
+    const Geom& g = p->g;
+    const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_DCT;
+    const dim3 tg(p->ntile, B);
+    if (xd) {
+        hipLaunchKernelGGL((k_inv_tile<0, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar, 0u);
+        hipLaunchKernelGGL((k_inv_scan_tiles<true>), dim3(B), dim3(1024), 0, st, p->ws.txor, p->ntile);
+        hipLaunchKernelGGL((k_inv_tile<1, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar, 0u);
+        hipLaunchKernelGGL((k_inv_scan_tiles<false>), dim3(B), dim3(1024), 0, st, p->ws.tsum, p->ntile);
+        hipLaunchKernelGGL((k_inv_tile<2, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, inv_out, inv_sx);
+    } else {
+        hipLaunchKernelGGL((k_inv_tile<2, false>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, inv_out, inv_sx);
+    }
+    const int32_t* final_planar = p->ws.planar;
+    if (g.kind == RSPT_HIP_KIND_HADAMARD) {
+        const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
+        if (g.ns > 65536u) {
+            launch_fwht_big<false>(p, B, st, ls ? &ls->inv : nullptr, ls ? ls->choice : nullptr);
+        } else if (g.ns == 65536u && ls) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_l<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+            hipLaunchKernelGGL((k_fwht64k_l<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
+                               (uint32_t*)nullptr, 0u, ls->inv, ls->choice);
+        } else if (ls) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_l<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+            hipLaunchKernelGGL((k_fwht_l<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, ls->inv, ls->choice);
+        } else if (g.ns == 65536u && p->had_quant) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_q<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+            hipLaunchKernelGGL((k_fwht64k_q<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
+                               (uint32_t*)nullptr, 0u, p->had_div_inv);
+        } else if (g.ns == 65536u) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+            hipLaunchKernelGGL((k_fwht64k<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
+                               (uint32_t*)nullptr, 0u);
+        } else if (p->had_quant) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_q<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+            hipLaunchKernelGGL((k_fwht_q<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->had_div_inv);
+        } else {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
+            hipLaunchKernelGGL((k_fwht<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
+        }
+    } else if (g.kind == RSPT_HIP_KIND_DCT) {
+        if (p->dct_fft)
+            launch_dct_fft<false>(p, B, p->ws.planar, p->ws.planar2, st);
+        else if (ls)
+            hipLaunchKernelGGL((k_dct_l<false>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g,
+                               p->ws.means, p->cos_tab_t, ls->inv, ls->choice, p->dct_cs0, p->ws.planar2);
+        else
+            hipLaunchKernelGGL((k_dct<false>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g,
+                               p->ws.means, p->cos_tab_t, 0.0, p->idct_scale, p->dct_cs0, p->ws.planar2);
+        final_planar = p->ws.planar2;
+    }
+    return final_planar;
+}
+
 // to_planar: d_dst is the caller's planar int32 matrix (rspt_hip_decompress_planar_batch_dev), not the native batch
 static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* pidx, size_t packed_len, size_t nblocks,
-                          void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar = false);
+                          void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar = false, const LadderSel* ls = nullptr);
 
 int rspt_hip_decompress_batch_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, void* d_dst, uint64_t* d_consumed,
                                   void* stream) {
     return decompress_dev(p, d_src, src_stride, nullptr, 0, nblocks, d_dst, d_consumed, stream);
+}
+
+int rspt_hip_decompress_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, const double* ladder, size_t nladder,
+                                         const uint32_t* d_choice, void* d_dst, uint64_t* d_consumed, void* stream) {
+    if (!p || !d_src || !d_dst || !d_consumed || !d_choice || nblocks == 0 || (reinterpret_cast<uintptr_t>(d_choice) & 3)) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;
+    LadderSel ls;
+    if (int rc = make_ladder(p, ladder, nladder, d_choice, &ls)) return rc;
+    return decompress_dev(p, d_src, src_stride, nullptr, 0, nblocks, d_dst, d_consumed, stream, false, &ls);
 }
 
 int rspt_hip_decompress_packed_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, void* d_dst, uint64_t* d_consumed,
@@ -1111,7 +1264,7 @@ int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_pack
 }
 
 static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* pidx, size_t packed_len, size_t nblocks,
-                          void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar) {
+                          void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar, const LadderSel* ls) {
     if (!p || !d_src || !d_dst || !d_consumed || nblocks == 0) return RSPT_HIP_ERR_ARG;
     if (p->feed) return RSPT_HIP_ERR_ARG;  // (the feed owns the plane workspace until rspt_hip_feed_end)
     int rc = rspt_hip_reserve(p, nblocks);
@@ -1144,7 +1297,6 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
             return RSPT_HIP_OK;
         }
         const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_DCT;
-        const dim3 tg(p->ntile, B);
         // int32 samples of the two hzr packers: the last inverse pass writes the interleaved block itself (k_inv_native)
         const bool lossless = g.kind == RSPT_HIP_KIND_XDELTA_HZR || g.kind == RSPT_HIP_KIND_HZR;
         const bool direct = lossless && !to_planar && g.bps == 4 && (g.nch & 3) == 0 && g.ns % kRowTile == 0 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0;
@@ -1173,43 +1325,7 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
             HIPCHK(p, hipGetLastError());
             return RSPT_HIP_OK;
         }
-        if (xd) {
-            hipLaunchKernelGGL((k_inv_tile<0, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar, 0u);
-            hipLaunchKernelGGL((k_inv_scan_tiles<true>), dim3(B), dim3(1024), 0, st, p->ws.txor, p->ntile);
-            hipLaunchKernelGGL((k_inv_tile<1, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, p->ws.planar, 0u);
-            hipLaunchKernelGGL((k_inv_scan_tiles<false>), dim3(B), dim3(1024), 0, st, p->ws.tsum, p->ntile);
-            hipLaunchKernelGGL((k_inv_tile<2, true>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, inv_out, inv_sx);
-        } else {
-            hipLaunchKernelGGL((k_inv_tile<2, false>), tg, dim3(256), 0, st, p->ws.planes, g, p->ws.dec_nb, p->ntile, p->ws.txor, p->ws.tsum, inv_out, inv_sx);
-        }
-        const int32_t* final_planar = p->ws.planar;
-        if (g.kind == RSPT_HIP_KIND_HADAMARD) {
-            const uint32_t fw_lds = (g.ns > 32768u ? 32768u : g.ns) * 4u;
-            if (g.ns > 65536u) {
-                launch_fwht_big<false>(p, B, st);
-            } else if (g.ns == 65536u && p->had_quant) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k_q<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht64k_q<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
-                                   (uint32_t*)nullptr, 0u, p->had_div_inv);
-            } else if (g.ns == 65536u) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht64k<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht64k<false, false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, (uint8_t*)nullptr,
-                                   (uint32_t*)nullptr, 0u);
-            } else if (p->had_quant) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht_q<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht_q<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means, p->had_div_inv);
-            } else {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwht<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_lds);
-                hipLaunchKernelGGL((k_fwht<false>), dim3(g.nch, B), dim3(1024), fw_lds, st, p->ws.planar, g, p->ws.means);
-            }
-        } else if (g.kind == RSPT_HIP_KIND_DCT) {
-            if (p->dct_fft)
-                launch_dct_fft<false>(p, B, p->ws.planar, p->ws.planar2, st);
-            else
-                hipLaunchKernelGGL((k_dct<false>), dim3((g.ns + 255) / 256, (g.nch + kDctCh - 1) / kDctCh, B), dim3(256), 0, st, p->ws.planar, g,
-                                   p->ws.means, p->cos_tab_t, 0.0, p->idct_scale, p->dct_cs0, p->ws.planar2);
-            final_planar = p->ws.planar2;
-        }
+        const int32_t* final_planar = launch_inverse(p, B, st, inv_out, inv_sx, ls);
         if (to_planar) {
             if (!lossless) {  // the transform packers: the inverse transform's output, cut to the sample width as the native back ends cut it
                 const uint64_t wgs = ((uint64_t)B * g.N + 255) / 256, want = 16ull * (uint64_t)p->num_cu;
@@ -1221,7 +1337,13 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
         const uint32_t T = min(p->Tn_native, g.ns);
         const uint32_t lds = g.nch * (T + 1) * 4;
         const dim3 ng(T ? (g.ns + T - 1) / T : 0u, B);
-        if (T == 0) {  // more channels than k_planar_native holds a row of: 64 x 64 tiles
+        if (ls) {  // a ladder call: the 64 x 64 tiles that pass over a block whose choice lies outside the ladder, and its flag
+            by_bps(g.bps, [&](auto bps) {
+                hipLaunchKernelGGL(k_wide_native_l<decltype(bps)::value>, dim3((g.ns + 63) / 64, (g.nch + 63) / 64, B), dim3(256), 0, st, final_planar, g,
+                                   (uint8_t*)d_dst, ls->choice, ls->inv.n);
+            });
+            hipLaunchKernelGGL(k_ladder_flag, dim3((B + 255) / 256), dim3(256), 0, st, ls->choice, ls->inv.n, B, d_consumed, 1u);
+        } else if (T == 0) {  // more channels than k_planar_native holds a row of: 64 x 64 tiles
             by_bps(g.bps, [&](auto bps) { launch_wide_native<decltype(bps)::value>(g, final_planar, (uint8_t*)d_dst, B, st); });
         } else if (g.bps == 4 && (g.nch & 3) == 0 && (g.ns & 3) == 0 && g.nch <= 1024 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0) {
             const uint32_t T4 = tile_i32x4(g);
@@ -1357,3 +1479,4 @@ int rspt_hip_stage_times(rspt_hip_packer* p, float* ms, int n) {
 }  // extern "C"
 
 #include "host_stages.hip"  // (templates: outside the block; rspt_hip.h declares every entry extern "C")
+#include "host_target.hip"

@@ -78,6 +78,19 @@ __global__ __launch_bounds__(1024) void k_fwht_q(int32_t* __restrict__ planar, G
 #include "k_fwht_body.hpp"
 }
 
+// k_fwht_l: the general quantiser with the divisor of the block's own ladder entry, lad.a[choice[block]] (QLadder, common.hpp;
+// rspt_hip_compress_batch_ladder_dev).  A choice outside the ladder leaves the block alone: the host flags it.  An entry of
+// quality 1 divides by n (forward) and by 1 (inverse) in fp64: (int)((double)y / n) is the truncating division for n = 2^k.
+template <bool FORWARD>
+__global__ __launch_bounds__(1024) void k_fwht_l(int32_t* __restrict__ planar, Geom g, uint8_t* __restrict__ means, QLadder lad,
+                                                const uint32_t* __restrict__ choice) {
+    constexpr bool QUANT = true;
+    const uint32_t ch = choice[blockIdx.y];
+    if (ch >= lad.n) return;
+    const double div = lad.a[ch];
+#include "k_fwht_body.hpp"
+}
+
 // ---- rows longer than 65536 points (fwht.c:4-28 transforms any n = 2^k): two passes over the planar row ------------------------
 // WHT_n = WHT_{n / 32768} (x) WHT_32768 -- the stages act on one index bit each and commute exactly in wrap-around arithmetic.
 //   k_fwht_seg    the low 15 index bits: every contiguous 32768-point piece of the row through LDS, in place, nothing else
@@ -179,6 +192,18 @@ __global__ __launch_bounds__(256) void k_fwht_cross_q(int32_t* __restrict__ plan
 #include "k_fwht_cross_body.hpp"
 }
 
+// k_fwht_cross_l: the last pass with the divisor of the block's ladder entry (k_fwht_l)
+template <bool FORWARD>
+__global__ __launch_bounds__(256) void k_fwht_cross_l(int32_t* __restrict__ planar, Geom g, const uint8_t* __restrict__ means,
+                                                     const int32_t* __restrict__ mean_i32, uint32_t m, uint32_t stride, uint32_t last, QLadder lad,
+                                                     const uint32_t* __restrict__ choice) {
+    constexpr bool QUANT = true;
+    const uint32_t ch = choice[blockIdx.z];
+    if (ch >= lad.n) return;
+    const double div = lad.a[ch];
+#include "k_fwht_cross_body.hpp"
+}
+
 // ---------------------------------------------------------------------------
 // dense DCT-II / inverse, reference arithmetic.  thread <-> output index,
 // CH channels per workgroup share every table load.
@@ -234,6 +259,17 @@ __global__ __launch_bounds__(1024) void k_fwht64k_q(int32_t* __restrict__ planar
 #include "k_fwht64k_body.hpp"
 }
 
+// k_fwht64k_l: the divisor of the block's ladder entry (k_fwht_l)
+template <bool FORWARD, bool PLANES>
+__global__ __launch_bounds__(1024) void k_fwht64k_l(int32_t* __restrict__ planar, Geom g, uint8_t* __restrict__ means, uint8_t* __restrict__ planes,
+                                                   uint32_t* __restrict__ nzflag, uint32_t nplanes, QLadder lad, const uint32_t* __restrict__ choice) {
+    constexpr bool QUANT = true;
+    const uint32_t ch = choice[blockIdx.y];
+    if (ch >= lad.n) return;
+    const double div = lad.a[ch];
+#include "k_fwht64k_body.hpp"
+}
+
 // n x n float matrix -> its transpose (the inverse DCT reads the cosine table the other way round), 32 x 32 tiles
 __global__ __launch_bounds__(256) void k_transpose_f32(const float* __restrict__ a, float* __restrict__ t, uint32_t n) {
     __shared__ float s[32][33];
@@ -250,71 +286,18 @@ template <bool FORWARD>
 __global__ __launch_bounds__(256) void k_dct(const int32_t* __restrict__ in, Geom g, uint8_t* __restrict__ means,
                                             const float* __restrict__ tab, double scale0, double scale1, float cs0,
                                             int32_t* __restrict__ out) {
-    __shared__ float s_src[kDctCh][kDctChunk];
-    __shared__ long long s_red[4];
-    __shared__ int32_t s_mean[kDctCh];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t n = g.ns;
-    const uint32_t i = blockIdx.x * 256 + tid;
-    const uint32_t c0 = blockIdx.y * kDctCh;
-    const uint32_t b = blockIdx.z;
-    const uint32_t nc = min((uint32_t)kDctCh, g.nch - c0);
+#include "k_dct_body.hpp"
+}
 
-    if (FORWARD) {
-        for (uint32_t cc = 0; cc < nc; ++cc) {
-            long long t = block_sum_row(in + (size_t)b * g.N + (size_t)(c0 + cc) * n, n, s_red);
-            if (tid == 0) {
-                const int32_t m = mean_from_sum(t, n);
-                s_mean[cc] = m;
-                if (blockIdx.x == 0) store_mean_hdr(means, g, b, c0 + cc, m);
-            }
-        }
-    } else if (tid < nc) {
-        s_mean[tid] = load_mean_hdr(means, g, b, c0 + tid);
-    }
-    __syncthreads();
-
-    double sum[kDctCh] = {0, 0, 0, 0};
-    for (uint32_t x0 = 0; x0 < n; x0 += kDctChunk) {
-        const uint32_t cn = min(kDctChunk, n - x0);
-        for (uint32_t cc = 0; cc < nc; ++cc)
-            for (uint32_t x = tid; x < cn; x += 256) {
-                int32_t v = in[(size_t)b * g.N + (size_t)(c0 + cc) * n + x0 + x];
-                float f;
-                if (FORWARD) {
-                    v = (int32_t)((uint32_t)v - (uint32_t)s_mean[cc]);  // offset_32(-mean), dct.cpp:108-109
-                    f = (float)v;                                        // `int * float`: the int converts to float
-                } else {
-                    f = (float)v;
-                    if (x0 + x == 0) f = __fmul_rn(cs0, f);  // Cs[x]*dct[x] in float, Cs[0]=(float)(1/sqrt 2) (dct.cpp:95)
-                }
-                s_src[cc][x] = f;
-            }
-        __syncthreads();
-        if (i < n) {
-            for (uint32_t x = 0; x < cn; ++x) {
-                const float cv = tab[(size_t)(x0 + x) * n + i];
-#pragma unroll
-                for (int cc = 0; cc < kDctCh; ++cc) {
-                    // float product, then sequential accumulation in double, no contraction
-                    sum[cc] = __dadd_rn(sum[cc], (double)__fmul_rn(s_src[cc][x], cv));
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (i < n) {
-        for (uint32_t cc = 0; cc < nc; ++cc) {
-            double s;
-            if (FORWARD)
-                s = __dmul_rn(sum[cc], i == 0 ? scale0 : scale1);  // sum *= Cs[i]*sqrt(2/n)/128 (dct.cpp:84)
-            else
-                s = __dmul_rn(sum[cc], scale1);                    // sum *= sqrt(2/n)*128 (dct.cpp:97)
-            int32_t r = trunc_i32_c(s);                              // C truncation (dct.cpp:85,98)
-            if (!FORWARD) r = (int32_t)((uint32_t)r + (uint32_t)s_mean[cc]);
-            out[(size_t)b * g.N + (size_t)(c0 + cc) * n + i] = r;
-        }
-    }
+// k_dct_l: the scales of block b are those of its ladder entry (k_fwht_l); a choice outside the ladder leaves the block alone
+template <bool FORWARD>
+__global__ __launch_bounds__(256) void k_dct_l(const int32_t* __restrict__ in, Geom g, uint8_t* __restrict__ means,
+                                              const float* __restrict__ tab, QLadder lad, const uint32_t* __restrict__ choice, float cs0,
+                                              int32_t* __restrict__ out) {
+    const uint32_t ch = choice[blockIdx.z];
+    if (ch >= lad.n) return;
+    const double scale0 = lad.a[ch], scale1 = lad.b[ch];
+#include "k_dct_body.hpp"
 }
 
 // ---------------------------------------------------------------------------
@@ -724,5 +707,13 @@ template __global__ void k_fwht64k_q<true, true>(int32_t*, Geom, uint8_t*, uint8
 template __global__ void k_fwht64k_q<false, false>(int32_t*, Geom, uint8_t*, uint8_t*, uint32_t*, uint32_t, double);
 template __global__ void k_dct<true>(const int32_t*, Geom, uint8_t*, const float*, double, double, float, int32_t*);
 template __global__ void k_dct<false>(const int32_t*, Geom, uint8_t*, const float*, double, double, float, int32_t*);
+template __global__ void k_fwht_l<true>(int32_t*, Geom, uint8_t*, QLadder, const uint32_t*);
+template __global__ void k_fwht_l<false>(int32_t*, Geom, uint8_t*, QLadder, const uint32_t*);
+template __global__ void k_fwht_cross_l<true>(int32_t*, Geom, const uint8_t*, const int32_t*, uint32_t, uint32_t, uint32_t, QLadder, const uint32_t*);
+template __global__ void k_fwht_cross_l<false>(int32_t*, Geom, const uint8_t*, const int32_t*, uint32_t, uint32_t, uint32_t, QLadder, const uint32_t*);
+template __global__ void k_fwht64k_l<true, true>(int32_t*, Geom, uint8_t*, uint8_t*, uint32_t*, uint32_t, QLadder, const uint32_t*);
+template __global__ void k_fwht64k_l<false, false>(int32_t*, Geom, uint8_t*, uint8_t*, uint32_t*, uint32_t, QLadder, const uint32_t*);
+template __global__ void k_dct_l<true>(const int32_t*, Geom, uint8_t*, const float*, QLadder, const uint32_t*, float, int32_t*);
+template __global__ void k_dct_l<false>(const int32_t*, Geom, uint8_t*, const float*, QLadder, const uint32_t*, float, int32_t*);
 
 }  // namespace rspt
