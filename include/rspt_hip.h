@@ -342,6 +342,45 @@ int rspt_hip_decompress_planar_batch_dev(rspt_hip_packer* p, const void* d_src, 
 int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, int32_t* d_planar,
                                           uint64_t* d_consumed, void* stream);
 
+/* ---- the quality ladder and the PRDN target on the planar matrix ----
+ * The planar forms of rspt_hip_compress_batch_ladder_dev, rspt_hip_decompress_batch_ladder_dev and
+ * rspt_hip_compress_target_batch_dev, under three identities:
+ *
+ *   compress_planar_ladder(P, ladder, choice)  ==  rspt_hip_compress_batch_ladder_dev(rspt_hip_i32_to_native_batch_dev(P), ladder, choice)
+ *       the streams, d_sizes, and "exactly bit 63, nothing written" for d_choice[b] >= nladder.
+ *   decompress_planar_ladder(S, ladder, choice)  ==  rspt_hip_native_to_i32_batch_dev(rspt_hip_decompress_batch_ladder_dev(S, ladder, choice))
+ *       for a block whose choice lies outside the ladder no element of its rows in d_planar is written and bit 63 is added to
+ *       d_consumed[b]; the other blocks are not affected.
+ *   target_planar(P, ...)  ==  rspt_hip_compress_target_batch_dev(rspt_hip_i32_to_native_batch_dev(P), ...)
+ *       d_choice and d_prdn bit for bit, the streams byte for byte, d_sizes.  On a handle of bps < 4 the original of the rule is
+ *       therefore the matrix CUT TO THE SAMPLE WIDTH -- what the stream can carry, the convention of
+ *       rspt_hip_compress_planar_batch_dev: whatever lies above the low bps bytes of a value changes nothing.
+ *       (rspt_hip_prdn_planar_batch_dev's "the whole int32 is the sample" does not apply here.)
+ *
+ * The refusals are the union of the planar entries' and the ladder entries': d_planar and d_choice 4-byte aligned (any 4-byte
+ * alignment of the matrix works), RSPT_HIP_ERR_UNSUPPORTED for every kind but hadamard and the dense dct, the dst_stride bound,
+ * the ladder's validation, an open feed; the target entry adds the native one's (target_prdn, nblocks <= 65535, d_prdn 8-byte
+ * and d_work 16-byte aligned).  A refused call writes nothing.  d_planar is only read by the compress entries.  Asynchronous on
+ * `stream`, no host synchronisation inside beyond rspt_hip_reserve's; the handle's own quantiser is neither read nor changed.
+ *
+ * The target entry takes the native one's two routes under the same condition, and rspt_hip_debug_set_target_route governs
+ * it too; both give the same bits.  fused: the probe reads each row from the caller's matrix, cutting it as it loads -- no
+ * converter pass, no copy of the original, no decoded copy.  general: per ladder entry the matrix goes through the planar
+ * front end into the workspace; a cut copy of the original for the PRDN step is made only at bps < 4.  The tables of figures
+ * lie in the handle's workspace (rspt_hip_reserve), so d_work holds block-sized scratch alone:
+ * rspt_hip_compress_target_planar_work_bytes names it for the route a call would take NOW (after a change through
+ * rspt_hip_debug_set_target_route, ask again) -- general: one decoded copy, the segment marks, and the cut original at bps < 4,
+ * which at bps 4 is rspt_hip_compress_target_work_bytes less one planar copy or more; fused: 16 bytes, so that d_work is a
+ * pointer.  Nothing is written behind the bytes it names. */
+int rspt_hip_compress_planar_batch_ladder_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
+                                              const uint32_t* d_choice, void* d_dst, size_t dst_stride, uint64_t* d_sizes, void* stream);
+int rspt_hip_decompress_planar_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, const double* ladder,
+                                                size_t nladder, const uint32_t* d_choice, int32_t* d_planar, uint64_t* d_consumed, void* stream);
+int rspt_hip_compress_target_planar_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t nladder, size_t* bytes);
+int rspt_hip_compress_target_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
+                                              double target_prdn, void* d_dst, size_t dst_stride, uint64_t* d_sizes, uint32_t* d_choice,
+                                              double* d_prdn, void* d_work, void* stream);
+
 /* hzr_verify (hzr_decode.c:569-624) of nblocks libhzr streams resident in device memory, WITHOUT decoding them: the frame walk,
  * the mode byte of every block (<= 2) and the CRC-32C of every block's payload against its header.  Stream b starts at
  * d_src + b*src_stride and has d_src_len[b] bytes (a device array); nothing at or beyond d_src + b*src_stride + d_src_len[b] is read.
@@ -375,6 +414,33 @@ int rspt_hip_pack_batch_dev(rspt_hip_packer* p, const void* d_dst, size_t dst_st
  * truncated or corrupt container flags its streams (bit 63 of d_consumed[b]) instead of reading out of bounds. */
 int rspt_hip_decompress_packed_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, void* d_dst, uint64_t* d_consumed,
                                    void* stream);
+
+/* ---- the choice of a ladder or target compress in the container: no side channel beside the gathered containers ----
+ * The index length word is  length | nb << 56 | choice << 60 | invalid << 63.  Bits 60..62 are zero in what
+ * rspt_hip_pack_batch_dev writes, and rspt_hip_decompress_packed_dev / rspt_hip_decompress_packed_planar_dev ignore them: they
+ * decode a choice-carrying container as they decode the plain one.  A ladder has at most 8 entries, so three bits are a choice.
+ *
+ * rspt_hip_pack_batch_choice_dev is rspt_hip_pack_batch_dev with d_choice[b] (device, nblocks uint32, 4-byte aligned: what the
+ * ladder or target compress call had or wrote) in bits 60..62 of stream b's word.  Header, offsets, padding and nb bits are
+ * unchanged: with every choice 0 the container is byte for byte rspt_hip_pack_batch_dev's.  A block flagged in d_sizes (bit 63)
+ * becomes the empty flagged entry it is there, with choice bits 0.  A choice >= nladder (1..8) on a block that is NOT flagged
+ * in d_sizes is the caller's error: its entry is written flagged (bit 63, length 0, counted in the header, nothing copied)
+ * rather than with a choice that aliases another.  RSPT_HIP_ERR_UNSUPPORTED for every kind but hadamard and the dense dct.
+ *
+ * The two decoders take each stream's choice from its index entry, on the device:
+ *   rspt_hip_decompress_packed_ladder_dev         ==  rspt_hip_decompress_batch_ladder_dev on the same streams and choices
+ *   rspt_hip_decompress_packed_planar_ladder_dev  ==  rspt_hip_decompress_planar_batch_ladder_dev on them
+ * A stored choice >= nladder flags the block (bit 63 of d_consumed[b]) and writes nothing for it, and so does a flagged entry.
+ * The ladder itself stays a decoder argument, as the quality is: the header has no room for it and its format is not touched.
+ * The container checks are rspt_hip_decompress_packed_dev's: packed_len < 32 + 16 * nblocks is RSPT_HIP_ERR_CORRUPT before the
+ * device reads the index, and nothing at or behind d_packed + packed_len is read.  The choices pass through an array of the
+ * handle's workspace (rspt_hip_reserve). */
+int rspt_hip_pack_batch_choice_dev(rspt_hip_packer* p, const void* d_dst, size_t dst_stride, const uint64_t* d_sizes, size_t nblocks,
+                                   const uint32_t* d_choice, size_t nladder, void* d_packed, uint64_t* d_total, void* stream);
+int rspt_hip_decompress_packed_ladder_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, const double* ladder,
+                                          size_t nladder, void* d_dst, uint64_t* d_consumed, void* stream);
+int rspt_hip_decompress_packed_planar_ladder_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, const double* ladder,
+                                                 size_t nladder, int32_t* d_planar, uint64_t* d_consumed, void* stream);
 
 /* ---- multi-GPU: gather the containers of all ranks to one rank over RCCL -----------------------------
  * One process (or thread) per GPU, each with its own handle and its own ncclComm_t of one communicator.  The ranks hold

@@ -64,10 +64,17 @@ C_ABI = {
     "rspt_hip_compress_planar_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_decompress_planar_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
     "rspt_hip_decompress_packed_planar_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
+    "rspt_hip_compress_planar_batch_ladder_dev": (_i, [_p, _p, _z, _dp, _z, _p, _p, _z, _p, _p]),
+    "rspt_hip_decompress_planar_batch_ladder_dev": (_i, [_p, _p, _z, _z, _dp, _z, _p, _p, _p, _p]),
+    "rspt_hip_compress_target_planar_work_bytes": (_i, [_p, _z, _z, _szp]),
+    "rspt_hip_compress_target_planar_batch_dev": (_i, [_p, _p, _z, _dp, _z, _d, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_hzr_verify_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_pack_bound": (_z, [_p, _z]),
     "rspt_hip_pack_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p, _p]),
     "rspt_hip_decompress_packed_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
+    "rspt_hip_pack_batch_choice_dev": (_i, [_p, _p, _z, _p, _z, _p, _z, _p, _p, _p]),
+    "rspt_hip_decompress_packed_ladder_dev": (_i, [_p, _p, _z, _z, _dp, _z, _p, _p, _p]),
+    "rspt_hip_decompress_packed_planar_ladder_dev": (_i, [_p, _p, _z, _z, _dp, _z, _p, _p, _p]),
     "rspt_hip_gather_sizes": (_i, [_p, _p, _i, _p, _p, _p, _p]),
     "rspt_hip_gather_payload": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _z, _p]),
     "rspt_hip_gather_containers": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _z, _p, _p]),
@@ -435,9 +442,27 @@ class SignalPacker:
         work: a device tensor of at least target_work_bytes(nblocks, len(ladder)) bytes, 16-byte aligned; None: allocated here.
         Returns (d_dst, d_sizes, d_choice, d_prdn): streams and sizes as compress_batch(ladder=, choice=d_choice) writes them,
         the chosen indices (torch.int32; decompress_batch needs them) and the chosen entries' PRDN (float64)."""
+        return self._compress_to_prdn("rspt_hip_compress_target_batch_dev", self.target_work_bytes, d_src, self._nblocks(d_src), target, ladder,
+                                      work, stream, d_dst, dst_stride)
+
+    def target_planar_work_bytes(self, nblocks, nladder):
+        """bytes of compress_to_prdn_planar's work area, for the route a call would take now (debug_set_target_route)"""
+        return self._bytes("rspt_hip_compress_target_planar_work_bytes", int(nblocks), int(nladder))
+
+    def compress_to_prdn_planar(self, d_planar, target, ladder, work=None, stream=None, d_dst=None, dst_stride=None):
+        """compress_to_prdn for samples that already live in int32 (rspt_hip.h: rspt_hip_compress_target_planar_batch_dev): d_planar
+        is a torch.int32 cuda tensor [nblocks, nch, ns], only read; everything returned is what
+        compress_to_prdn(from_planar_i32(d_planar), ...) returns -- on a handle of bps < 4 the original is the matrix cut to the
+        sample width.  work: at least target_planar_work_bytes(nblocks, len(ladder)) bytes, 16-byte aligned; None: allocated here."""
         import torch
 
-        nblocks = self._nblocks(d_src)
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        return self._compress_to_prdn("rspt_hip_compress_target_planar_batch_dev", self.target_planar_work_bytes, d_planar, nblocks, target,
+                                      ladder, work, stream, d_dst, dst_stride)
+
+    def _compress_to_prdn(self, entry, work_bytes, d_src, nblocks, target, ladder, work, stream, d_dst, dst_stride):
+        import torch
+
         lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
         dev = d_src.device
         if dst_stride is None:
@@ -448,9 +473,9 @@ class SignalPacker:
         d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
         d_prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
         if work is None:
-            work = torch.empty((self.target_work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
+            work = torch.empty((work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
         assert work.is_cuda and work.is_contiguous()
-        self._call("rspt_hip_compress_target_batch_dev", d_src.data_ptr(), nblocks, _dptr(lad), lad.size, float(target), d_dst.data_ptr(),
+        self._call(entry, d_src.data_ptr(), nblocks, _dptr(lad), lad.size, float(target), d_dst.data_ptr(),
                    dst_stride, d_sizes.data_ptr(), d_choice.data_ptr(), d_prdn.data_ptr(), work.data_ptr(), self._stream(stream, dev))
         return d_dst, d_sizes, d_choice, d_prdn
 
@@ -468,12 +493,13 @@ class SignalPacker:
             d_consumed = torch.empty(nblocks, dtype=torch.int64, device=device)
         return d_out, d_consumed
 
-    def compress_planar_batch(self, d_planar, d_dst=None, d_sizes=None, dst_stride=None, stream=None):
+    def compress_planar_batch(self, d_planar, d_dst=None, d_sizes=None, dst_stride=None, stream=None, ladder=None, choice=None):
         """compress_batch for samples that already live in int32 (rspt_hip.h: rspt_hip_compress_planar_batch_dev): d_planar is a
         torch.int32 cuda tensor [nblocks, nch, ns], only read; the streams are those of compress_batch(from_planar_i32(d_planar)).
-        Returns (d_dst, d_sizes); asynchronous."""
+        ladder, choice: as compress_batch (rspt_hip_compress_planar_batch_ladder_dev).  Returns (d_dst, d_sizes); asynchronous."""
         import torch
 
+        assert (ladder is None) == (choice is None)
         nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
         if dst_stride is None:
             dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
@@ -482,27 +508,43 @@ class SignalPacker:
         if d_sizes is None:
             d_sizes = torch.empty(nblocks, dtype=torch.int64, device=d_planar.device)
         st = self._stream(stream, d_planar.device)
-        self._call("rspt_hip_compress_planar_batch_dev", d_planar.data_ptr(), nblocks, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
+        if ladder is not None:
+            lad, largs = self._ladder_args(ladder, choice, nblocks)
+            self._call("rspt_hip_compress_planar_batch_ladder_dev", d_planar.data_ptr(), nblocks, *largs, d_dst.data_ptr(), dst_stride,
+                       d_sizes.data_ptr(), st)
+        else:
+            self._call("rspt_hip_compress_planar_batch_dev", d_planar.data_ptr(), nblocks, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(), st)
         return d_dst, d_sizes
 
-    def decompress_planar_batch(self, d_streams, nblocks, src_stride, d_out=None, d_consumed=None, stream=None):
+    def decompress_planar_batch(self, d_streams, nblocks, src_stride, d_out=None, d_consumed=None, stream=None, ladder=None, choice=None):
         """decompress_batch into torch.int32 [nblocks, nch, ns] (rspt_hip.h: rspt_hip_decompress_planar_batch_dev): the values of
-        to_planar_i32(decompress_batch(...)) on a little-endian handle.  Returns (d_out, d_consumed); asynchronous."""
+        to_planar_i32(decompress_batch(...)) on a little-endian handle.  ladder, choice: as decompress_batch
+        (rspt_hip_decompress_planar_batch_ladder_dev).  Returns (d_out, d_consumed); asynchronous."""
+        assert (ladder is None) == (choice is None)
         d_out, d_consumed = self._decode_buffers(nblocks, d_streams.device, d_out, d_consumed, True)
         st = self._stream(stream, d_streams.device)
-        self._call("rspt_hip_decompress_planar_batch_dev", d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
+        if ladder is not None:
+            lad, largs = self._ladder_args(ladder, choice, nblocks)
+            self._call("rspt_hip_decompress_planar_batch_ladder_dev", d_streams.data_ptr(), src_stride, nblocks, *largs, d_out.data_ptr(),
+                       d_consumed.data_ptr(), st)
+        else:
+            self._call("rspt_hip_decompress_planar_batch_dev", d_streams.data_ptr(), src_stride, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
         return d_out, d_consumed
 
-    def decompress_packed_planar(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None):
-        """decompress_packed into torch.int32 [nblocks, nch, ns] (rspt_hip.h: rspt_hip_decompress_packed_planar_dev)."""
-        return self.decompress_packed(d_packed, d_out, d_consumed, stream, nbytes, planar=True)
+    def decompress_packed_planar(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None, ladder=None):
+        """decompress_packed into torch.int32 [nblocks, nch, ns] (rspt_hip.h: rspt_hip_decompress_packed_planar_dev, with a ladder
+        rspt_hip_decompress_packed_planar_ladder_dev)."""
+        return self.decompress_packed(d_packed, d_out, d_consumed, stream, nbytes, planar=True, ladder=ladder)
 
-    def decompress_packed(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None, planar=False):
+    def decompress_packed(self, d_packed, d_out=None, d_consumed=None, stream=None, nbytes=None, planar=False, ladder=None):
         """Decompress every stream of a container (what pack_batch / the multi-GPU gather produce) on the device.
         Each stream is decoded with the nb of its own index entry.  Reads the 32-byte header to the host for the block
         count (a synchronisation).  `nbytes`: container length if shorter than the tensor.  planar: into an int32 matrix
-        (decompress_packed_planar)."""
-        entry = "rspt_hip_decompress_packed_planar_dev" if planar else "rspt_hip_decompress_packed_dev"
+        (decompress_packed_planar).  ladder: the container carries a choice per stream (pack_batch(choice=)) and every stream is
+        decoded at ladder[its choice]; a stored choice outside the ladder flags its block and writes nothing for it."""
+        entry = "rspt_hip_decompress_packed%s%s_dev" % ("_planar" if planar else "", "" if ladder is None else "_ladder")
+        lad = None if ladder is None else np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+        largs = () if lad is None else (_dptr(lad), lad.size)
         head = d_packed[:32].cpu().numpy().view(np.uint64)
         if int(head[0]) != 0x4B43415054505352:
             raise ValueError("not an RSPTPACK container")
@@ -512,7 +554,7 @@ class SignalPacker:
             raise RsptHipError(entry, -6 if 0 < nblocks <= 65535 else -1)
         d_out, d_consumed = self._decode_buffers(nblocks, d_packed.device, d_out, d_consumed, planar)
         st = self._stream(stream, d_packed.device)
-        self._call(entry, d_packed.data_ptr(), plen, nblocks, d_out.data_ptr(), d_consumed.data_ptr(), st)
+        self._call(entry, d_packed.data_ptr(), plen, nblocks, *largs, d_out.data_ptr(), d_consumed.data_ptr(), st)
         return d_out, d_consumed
 
     def hzr_verify_batch(self, d_streams, d_lengths, src_stride=None, d_decoded=None, stream=None):
@@ -535,10 +577,14 @@ class SignalPacker:
     def pack_bound(self, nblocks):
         return self._L.rspt_hip_pack_bound(self._h, nblocks)
 
-    def pack_batch(self, d_dst, d_sizes, d_packed=None, d_total=None, stream=None):
-        """streams of a batch -> one container (layout: include/rspt_hip.h); asynchronous."""
+    def pack_batch(self, d_dst, d_sizes, d_packed=None, d_total=None, stream=None, choice=None, nladder=None):
+        """streams of a batch -> one container (layout: include/rspt_hip.h); asynchronous.
+        choice, nladder (both or neither; dct / hadamard): the torch.int32 cuda tensor [nblocks] a ladder or target compress call
+        had or returned, and the length of its ladder -- each stream's choice travels in its index entry
+        (rspt_hip_pack_batch_choice_dev) and decompress_packed(ladder=) needs nothing beside the container."""
         import torch
 
+        assert (choice is None) == (nladder is None)
         nblocks = d_sizes.numel()
         stride = d_dst.numel() // nblocks
         if d_packed is None:
@@ -546,7 +592,12 @@ class SignalPacker:
         if d_total is None:
             d_total = torch.zeros(1, dtype=torch.int64, device=d_dst.device)
         st = self._stream(stream, d_dst.device)
-        self._call("rspt_hip_pack_batch_dev", d_dst.data_ptr(), stride, d_sizes.data_ptr(), nblocks, d_packed.data_ptr(), d_total.data_ptr(), st)
+        if choice is not None:
+            assert choice.is_cuda and choice.dtype == torch.int32 and choice.is_contiguous() and choice.numel() == nblocks
+            self._call("rspt_hip_pack_batch_choice_dev", d_dst.data_ptr(), stride, d_sizes.data_ptr(), nblocks, choice.data_ptr(), int(nladder),
+                       d_packed.data_ptr(), d_total.data_ptr(), st)
+        else:
+            self._call("rspt_hip_pack_batch_dev", d_dst.data_ptr(), stride, d_sizes.data_ptr(), nblocks, d_packed.data_ptr(), d_total.data_ptr(), st)
         return d_packed, d_total
 
     def iir_state_bytes(self):

@@ -82,7 +82,19 @@ struct Workspace {
     size_t fft_bpp = 0;        // blocks per pass (bounds the scratch to ~1 GiB)
     Dev<int32_t> mean_i32;     // [cap][nch]
     Dev<unsigned long long> quality;  // [cap][quality_words(nch)]: the PRDN entries' scratch, carved up per call by QScratch
+    // the lossy packers only (a ladder needs one):
+    Dev<uint32_t> idx_choice;   // [cap] the choices of a container's index (k_index_choices -> the ladder kernels of the packed decoders)
+    Dev<uint64_t> pack_sizes;   // [cap] rspt_hip_pack_batch_choice_dev: the sizes k_pack_index reads (k_pack_choice_sizes)
+    Dev<uint8_t> target_tab;    // [kMaxLadder][cap] figures, sums and flags of rspt_hip_compress_target_planar_batch_dev (TargetWork)
 };
+
+// Workspace::target_tab for `blocks` blocks and a full ladder: the five tables of TargetWork (host_target.hip), each on a 256-byte
+// boundary -- two of doubles, two of uint32 and the sums of four 64-bit words, per (ladder entry, block)
+constexpr size_t target_tab_bytes(size_t blocks) {
+    const size_t cells = blocks * kMaxLadder;
+    auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    return 2 * pad(cells * sizeof(double)) + 2 * pad(cells * sizeof(uint32_t)) + pad(cells * 4 * sizeof(unsigned long long));
+}
 
 // The PRDN scratch of a call on B blocks: [B][nch] int64 channel sums | [B][4] per-block accumulators | [B] u32 flags, each part
 // right behind the one before it; the first two (clear_bytes) are zeroed by one memset in front of the call's kernels.

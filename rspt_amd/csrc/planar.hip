@@ -9,6 +9,7 @@
 //   k_planar_ingest  compress front end of the transform packers: caller's matrix -> ws.planar, cut to the sample width (the
 //                    transforms work in place there; the caller's buffer is only read), with the dct's channel sums
 //   k_planar_emit    decompress back end of the transform packers: inverse transform's output -> caller's matrix, cut
+//   k_planar_emit_l  the same behind a ladder call: the blocks whose choice lies outside the ladder are passed over
 // The lossless packers decode straight into the caller's matrix: k_inv_tile<2, *> (decode.hip) with its sign-extension shift.
 #include "common.hpp"
 
@@ -167,10 +168,18 @@ __global__ __launch_bounds__(256) void k_planar_ingest(const int32_t* __restrict
 
 // inverse transform's output -> caller's matrix, every value cut to the sample width (what the native back ends keep of it)
 __global__ __launch_bounds__(256) void k_planar_emit(const int32_t* __restrict__ planar, Geom g, uint32_t nblocks, int32_t* __restrict__ dst) {
-    const uint32_t sx = 32u - 8u * g.bps;
-    const uint64_t total = (uint64_t)nblocks * g.N;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256u)
-        dst[i] = (int32_t)cut_to_width((uint32_t)planar[i], sx);
+    constexpr bool kLadder = false;
+    constexpr const uint32_t* choice = nullptr;
+    constexpr uint32_t n = 0;
+#include "k_planar_emit_body.hpp"
+}
+
+// k_planar_emit_l: the back end of rspt_hip_decompress_planar_batch_ladder_dev -- no element of a block whose choice lies outside
+// the ladder of n entries is written
+__global__ __launch_bounds__(256) void k_planar_emit_l(const int32_t* __restrict__ planar, Geom g, uint32_t nblocks, int32_t* __restrict__ dst,
+                                                      const uint32_t* __restrict__ choice, uint32_t n) {
+    constexpr bool kLadder = true;
+#include "k_planar_emit_body.hpp"
 }
 
 }  // namespace rspt

@@ -49,6 +49,7 @@
 #include "bytes.hip"
 #include "planar.hip"
 #include "target.hip"
+#include "pack_choice.hip"
 
 using namespace rspt;
 
@@ -722,6 +723,11 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
         ok &= hipMalloc(w.mean_i32.out(), max_blocks * (size_t)g.nch * sizeof(int32_t)) == hipSuccess;
     }
     ok &= hipMalloc(w.quality.out(), max_blocks * quality_words(g.nch) * sizeof(unsigned long long)) == hipSuccess;
+    if (g.kind == RSPT_HIP_KIND_DCT || g.kind == RSPT_HIP_KIND_HADAMARD) {
+        ok &= hipMalloc(w.idx_choice.out(), max_blocks * sizeof(uint32_t)) == hipSuccess;
+        ok &= hipMalloc(w.pack_sizes.out(), max_blocks * sizeof(uint64_t)) == hipSuccess;
+        ok &= hipMalloc(w.target_tab.out(), target_tab_bytes(max_blocks)) == hipSuccess;
+    }
     if (!ok) return RSPT_HIP_ERR_ALLOC;
     // the clean-plane invariant starts from zeroed planes
     HIPCHK(p, hipMemset(w.planes, 0, slots * kMaxPlanes * g.plane_stride + 4096));
@@ -981,6 +987,17 @@ int rspt_hip_compress_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_plan
     return compress_batch_serial(p, nullptr, nblocks, d_dst, dst_stride, d_sizes, (hipStream_t)stream, d_planar);
 }
 
+int rspt_hip_compress_planar_batch_ladder_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
+                                              const uint32_t* d_choice, void* d_dst, size_t dst_stride, uint64_t* d_sizes, void* stream) {
+    if (!p || !d_planar || !d_dst || !d_sizes || !d_choice || nblocks == 0) return RSPT_HIP_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_planar) & 3) || (reinterpret_cast<uintptr_t>(d_choice) & 3)) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;
+    LadderSel ls;
+    if (int rc = make_ladder(p, ladder, nladder, d_choice, &ls)) return rc;  // (every kind without samples or without a ladder: unsupported)
+    if ((unsigned long long)dst_stride >> 32 >= p->g.nblk) return RSPT_HIP_ERR_ARG;  // (as rspt_hip_compress_batch_ladder_dev)
+    return compress_batch_serial(p, nullptr, nblocks, d_dst, dst_stride, d_sizes, (hipStream_t)stream, d_planar, &ls);
+}
+
 size_t rspt_hip_pack_bound(const rspt_hip_packer* p, size_t nblocks) {
     if (!p) return 0;
     return 32 + 16 * nblocks + nblocks * ((rspt_hip_max_compressed_size(p) + 15) & ~(size_t)15);
@@ -997,6 +1014,26 @@ int rspt_hip_pack_batch_dev(rspt_hip_packer* p, const void* d_dst, size_t dst_st
                        p->g.kind == RSPT_HIP_KIND_BYTES ? 1u : 0u);
     hipLaunchKernelGGL(k_pack_copy, dim3(32, (unsigned)nblocks), dim3(256), 0, st, (const uint8_t*)d_dst, (uint64_t)dst_stride, (uint32_t)nblocks,
                        (uint8_t*)d_packed);
+    HIPCHK(p, hipGetLastError());
+    return RSPT_HIP_OK;
+}
+
+int rspt_hip_pack_batch_choice_dev(rspt_hip_packer* p, const void* d_dst, size_t dst_stride, const uint64_t* d_sizes, size_t nblocks,
+                                   const uint32_t* d_choice, size_t nladder, void* d_packed, uint64_t* d_total, void* stream) {
+    if (!p || !d_dst || !d_sizes || !d_choice || !d_packed || !d_total || nblocks == 0 || nblocks > 65535) return RSPT_HIP_ERR_ARG;
+    const Geom& g = p->g;
+    if (g.kind != RSPT_HIP_KIND_HADAMARD && !(g.kind == RSPT_HIP_KIND_DCT && !p->dct_fft)) return RSPT_HIP_ERR_UNSUPPORTED;  // (make_ladder's kinds)
+    if (nladder < 1 || nladder > kMaxLadder || (reinterpret_cast<uintptr_t>(d_choice) & 3)) return RSPT_HIP_ERR_ARG;
+    if (nblocks > p->ws.cap_blocks) return RSPT_HIP_ERR_ARG;  // (as rspt_hip_pack_batch_dev)
+    if ((reinterpret_cast<uintptr_t>(d_dst) & 15) || (dst_stride & 15) || (reinterpret_cast<uintptr_t>(d_packed) & 15)) return RSPT_HIP_ERR_ARG;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t B = (uint32_t)nblocks;
+    // k_pack_index and k_pack_copy as rspt_hip_pack_batch_dev launches them, between the two kernels of pack_choice.hip
+    hipLaunchKernelGGL(k_pack_choice_sizes, dim3((B + 255) / 256), dim3(256), 0, st, d_sizes, d_choice, (uint32_t)nladder, B, (uint64_t*)p->ws.pack_sizes);
+    hipLaunchKernelGGL(k_pack_index, dim3(1), dim3(1024), 0, st, (const uint64_t*)p->ws.pack_sizes, B, p->nb_state, p->ws.nbuse, (uint8_t*)d_packed, d_total, 0u);
+    hipLaunchKernelGGL(k_pack_choice_bits, dim3((B + 255) / 256), dim3(256), 0, st, d_choice, B, (uint8_t*)d_packed);
+    hipLaunchKernelGGL(k_pack_copy, dim3(32, (unsigned)nblocks), dim3(256), 0, st, (const uint8_t*)d_dst, (uint64_t)dst_stride, B, (uint8_t*)d_packed);
     HIPCHK(p, hipGetLastError());
     return RSPT_HIP_OK;
 }
@@ -1263,6 +1300,50 @@ int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_pack
                           stream, true);
 }
 
+int rspt_hip_decompress_planar_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, const double* ladder,
+                                                size_t nladder, const uint32_t* d_choice, int32_t* d_planar, uint64_t* d_consumed, void* stream) {
+    if (!p || !d_src || !d_planar || !d_consumed || !d_choice || nblocks == 0) return RSPT_HIP_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_planar) & 3) || (reinterpret_cast<uintptr_t>(d_choice) & 3)) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;
+    LadderSel ls;
+    if (int rc = make_ladder(p, ladder, nladder, d_choice, &ls)) return rc;
+    return decompress_dev(p, d_src, src_stride, nullptr, 0, nblocks, d_planar, d_consumed, stream, true, &ls);
+}
+
+// Both packed ladder decoders: the container checks of rspt_hip_decompress_packed_dev, the choices of the index into the handle's
+// array (k_index_choices; the workspace is made first, so that decompress_dev's own rspt_hip_reserve leaves the array where it
+// is), and the decoder with that array as the ladder call's choice.
+static int decompress_packed_ladder(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, const double* ladder, size_t nladder,
+                                    void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar) {
+    if (!p || !d_dst || !d_consumed || !d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 15)) return RSPT_HIP_ERR_ARG;
+    if (to_planar && (reinterpret_cast<uintptr_t>(d_dst) & 3)) return RSPT_HIP_ERR_ARG;
+    if (nblocks == 0 || nblocks > 65535) return RSPT_HIP_ERR_ARG;
+    if (p->feed) return RSPT_HIP_ERR_ARG;
+    LadderSel ls;
+    if (int rc = make_ladder(p, ladder, nladder, nullptr, &ls)) return rc;
+    // header + index must be there before the device reads them (rspt_hip_decompress_packed_dev)
+    if (packed_len < 32 || nblocks > (packed_len - 32) / 16) return RSPT_HIP_ERR_CORRUPT;
+    if (int rc = rspt_hip_reserve(p, nblocks)) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    const uint8_t* base = (const uint8_t*)d_packed;
+    const uint64_t* index = reinterpret_cast<const uint64_t*>(base + 32);
+    hipLaunchKernelGGL(k_index_choices, dim3(((uint32_t)nblocks + 255) / 256), dim3(256), 0, (hipStream_t)stream, index, (uint32_t)nblocks,
+                       (uint32_t*)p->ws.idx_choice);
+    HIPCHK(p, hipGetLastError());
+    ls.choice = p->ws.idx_choice;
+    return decompress_dev(p, base + 32 + 16 * nblocks, 0, index, packed_len, nblocks, d_dst, d_consumed, stream, to_planar, &ls);
+}
+
+int rspt_hip_decompress_packed_ladder_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, const double* ladder,
+                                          size_t nladder, void* d_dst, uint64_t* d_consumed, void* stream) {
+    return decompress_packed_ladder(p, d_packed, packed_len, nblocks, ladder, nladder, d_dst, d_consumed, stream, false);
+}
+
+int rspt_hip_decompress_packed_planar_ladder_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, const double* ladder,
+                                                 size_t nladder, int32_t* d_planar, uint64_t* d_consumed, void* stream) {
+    return decompress_packed_ladder(p, d_packed, packed_len, nblocks, ladder, nladder, d_planar, d_consumed, stream, true);
+}
+
 static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, const uint64_t* pidx, size_t packed_len, size_t nblocks,
                           void* d_dst, uint64_t* d_consumed, void* stream, bool to_planar, const LadderSel* ls) {
     if (!p || !d_src || !d_dst || !d_consumed || nblocks == 0) return RSPT_HIP_ERR_ARG;
@@ -1329,7 +1410,13 @@ static int decompress_dev(rspt_hip_packer* p, const void* d_src, size_t src_stri
         if (to_planar) {
             if (!lossless) {  // the transform packers: the inverse transform's output, cut to the sample width as the native back ends cut it
                 const uint64_t wgs = ((uint64_t)B * g.N + 255) / 256, want = 16ull * (uint64_t)p->num_cu;
-                hipLaunchKernelGGL(k_planar_emit, dim3((uint32_t)(wgs < want ? wgs : want)), dim3(256), 0, st, final_planar, g, B, (int32_t*)d_dst);
+                if (ls) {  // a ladder call: the elements of a block whose choice lies outside the ladder are passed over, and its flag
+                    hipLaunchKernelGGL(k_planar_emit_l, dim3((uint32_t)(wgs < want ? wgs : want)), dim3(256), 0, st, final_planar, g, B, (int32_t*)d_dst,
+                                       ls->choice, ls->inv.n);
+                    hipLaunchKernelGGL(k_ladder_flag, dim3((B + 255) / 256), dim3(256), 0, st, ls->choice, ls->inv.n, B, d_consumed, 1u);
+                } else {
+                    hipLaunchKernelGGL(k_planar_emit, dim3((uint32_t)(wgs < want ? wgs : want)), dim3(256), 0, st, final_planar, g, B, (int32_t*)d_dst);
+                }
             }
             HIPCHK(p, hipGetLastError());
             return RSPT_HIP_OK;

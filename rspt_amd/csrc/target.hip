@@ -84,87 +84,16 @@ __device__ __forceinline__ void tp_fwht(uint32_t* sh, uint32_t n, uint32_t tid, 
 // acc: [nladder][nblocks][4] unsigned 64-bit, zero at the launch.  blockDim.x: a multiple of 64 with blockDim.x * kTpPer >= ns.
 __global__ __launch_bounds__(1024) void k_target_probe(const int32_t* __restrict__ orig, Geom g, QLadder fwd, QLadder inv, uint32_t nb,
                                                       uint32_t nblocks, unsigned long long* __restrict__ acc) {
-    extern __shared__ __attribute__((aligned(16))) int32_t sh_i[];
-    __shared__ unsigned long long s_part[16][4];
-    uint32_t* W = reinterpret_cast<uint32_t*>(sh_i);
-    const uint32_t tid = threadIdx.x, nt = blockDim.x, nw = nt >> 6;
-    const uint32_t c = blockIdx.x, b = blockIdx.y, n = g.ns;
-    uint32_t* T = W + tp_pad(n);
-    const int32_t* row = orig + (size_t)b * g.N + (size_t)c * n;
+    constexpr bool kPlanarCut = false;
+#include "k_target_probe_body.hpp"
+}
 
-    // a block-wide sum of four 64-bit values per thread, for thread 0 .. 3 the total of value tid
-    auto block_sum4 = [&](unsigned long long (&v)[4]) -> unsigned long long {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = q_wave_sum(v[j]);
-        if ((tid & 63u) == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s_part[tid >> 6][j] = v[j];
-        }
-        __syncthreads();
-        unsigned long long s = 0;
-        if (tid < 4)
-            for (uint32_t w = 0; w < nw; ++w) s += s_part[w][tid];
-        __syncthreads();
-        return s;
-    };
-
-    int32_t o[kTpPer];
-    unsigned long long first[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (uint32_t j = 0; j < kTpPer; ++j) {
-        const uint32_t i = tid + j * nt;
-        o[j] = i < n ? row[i] : 0;
-        if (i < n) W[tp_pad(i)] = (uint32_t)o[j];
-        first[0] += (unsigned long long)(long long)o[j];
-    }
-    __shared__ int32_t s_mean;
-    {
-        const unsigned long long s = block_sum4(first);  // (its first barrier also covers the stores to W)
-        if (tid == 0) s_mean = mean_from_sum((long long)s, n);
-    }
-    __syncthreads();
-    const int32_t mean = s_mean;
-    tp_fwht(W, n, tid, nt);
-    if (tid == 0) W[0] -= (uint32_t)mean * n;  // WHT(x - m) = WHT(x) - m*n*delta_0 (exact mod 2^32)
-    __syncthreads();
-
-    // the reference terms once: r = (int32)((o - mean) * (o - mean)), their sum and the sum of their magnitudes
-    long long sr = 0;
-    unsigned long long sa = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kTpPer; ++j) {
-        if (tid + j * nt < n) {
-            int32_t t, r;
-            q_terms(o[j], o[j], mean, t, r);
-            sr += r;
-            sa += (unsigned long long)(r < 0 ? -(long long)r : (long long)r);
-        }
-    }
-    const int32_t mean24 = (int32_t)((uint32_t)mean << 8) >> 8;  // what the header keeps (load_mean_hdr)
-    const uint32_t sx_nb = 32u - 8u * nb, sx = 32u - 8u * g.bps;
-    for (uint32_t k = 0; k < fwd.n; ++k) {
-        const double dfwd = fwd.a[k], dinv = inv.a[k];
-        for (uint32_t i = tid; i < n; i += nt) {
-            const int32_t y = fwht_quant((int32_t)W[tp_pad(i)], dfwd);
-            T[tp_pad(i)] = (uint32_t)((int32_t)((uint32_t)y << sx_nb) >> sx_nb);  // the low nb bytes, sign-extended: what the planes keep
-        }
-        __syncthreads();
-        tp_fwht(T, n, tid, nt);
-        QTerms q;
-#pragma unroll
-        for (uint32_t j = 0; j < kTpPer; ++j) {
-            const uint32_t i = tid + j * nt;
-            if (i < n) {
-                int32_t x = fwht_quant((int32_t)T[tp_pad(i)], dinv);
-                x = (int32_t)((uint32_t)x + (uint32_t)mean24);
-                x = (int32_t)((uint32_t)x << sx) >> sx;  // the cut to the sample width (k_planar_emit, the native back ends)
-                q.add(o[j], x, mean);
-            }
-        }
-        unsigned long long v[4] = {q.lo, q.hi, (unsigned long long)sr, sa};
-        const unsigned long long s = block_sum4(v);  // (its last barrier: every read of T is done before the next entry's stores)
-        if (tid < 4 && s) atomicAdd(&acc[((size_t)k * nblocks + b) * 4 + tid], s);
-    }
+// k_planar_target_probe: the probe of rspt_hip_compress_target_planar_batch_dev -- the rows are the caller's matrix (single dwords
+// at tid + j * nt: its 4-byte alignment is all they need), cut to the sample width on load
+__global__ __launch_bounds__(1024) void k_planar_target_probe(const int32_t* __restrict__ orig, Geom g, QLadder fwd, QLadder inv, uint32_t nb,
+                                                             uint32_t nblocks, unsigned long long* __restrict__ acc) {
+    constexpr bool kPlanarCut = true;
+#include "k_target_probe_body.hpp"
 }
 
 }  // namespace rspt
