@@ -315,6 +315,42 @@ int rspt_hip_compress_target_batch_dev(rspt_hip_packer* p, const void* d_src, si
  * (RSPT_HIP_ERR_UNSUPPORTED where the fused probe does not run; RSPT_HIP_ERR_ARG for any other value). */
 int rspt_hip_debug_set_target_route(rspt_hip_packer* p, int route);
 
+/* ---- compress to a byte budget: the finest entry of a ladder whose stream is at most budget bytes, block by block ----
+ * The rule.  For block b and ladder entry k: size_k(b) is the number rspt_hip_compress_batch_ladder_dev writes to d_sizes[b] when
+ * d_choice[b] = k and every stream fits the stride -- the length of the stream at ladder[k] and the handle's nb; bit 63 is never
+ * set in it.  budget(b) = d_budget ? d_budget[b] : budget_bytes; any value is allowed, 0 included.  d_choice[b] is the HIGHEST
+ * index k with size_k(b) <= budget(b) -- order the ladder coarse to fine, as for the PRDN target; nothing assumes that the sizes
+ * are sorted in it, and <= is inclusive -- and, if no entry fits, the entry of the smallest size, the lowest index among equals:
+ * the caller sees the miss as d_sizes[b] > budget(b).  Streams, d_sizes and (with d_choice) the decoded samples are then byte
+ * for byte those of rspt_hip_compress_batch_ladder_dev / rspt_hip_decompress_batch_ladder_dev with that d_choice, which is the
+ * caller's to keep: the decoder needs it.  A chosen stream that does not fit dst_stride is flagged as the ladder call flags it
+ * (bit 63 of d_sizes[b], nothing written); dst_stride plays no part in the choice.
+ * d_cand_sizes (optional): the whole table, size_k(b) at d_cand_sizes[k * nblocks + b].
+ * A candidate runs a compress call as far as the Huffman trees, behind which its size is known, and not a step further: no
+ * stream of a candidate is laid out or encoded, and the only output buffer is the caller's.
+ * budget_bytes is a size_t, which has 64 bits wherever this library is built.  ladder, kinds and refusals as
+ * rspt_hip_compress_target_batch_dev: RSPT_HIP_ERR_UNSUPPORTED for every kind and path without a ladder, nothing launched;
+ * RSPT_HIP_ERR_ARG for a bad ladder, an open feed, a null pointer, nblocks > 65535, a dst_stride of 2^32 bytes per 65536 samples
+ * or more, a d_src or d_work off a 16-byte boundary, a d_choice off a 4-byte one, a d_budget or d_cand_sizes off an 8-byte one.
+ * Asynchronous on `stream`, no host synchronisation inside (beyond rspt_hip_reserve's when the workspace grows) and nothing
+ * copied to the host; stream-ordered with every other call on the handle; the handle's own quantiser is neither read nor
+ * changed.
+ * d_work: device memory, 16-byte aligned, at least the bytes rspt_hip_compress_budget_work_bytes names for (nblocks, nladder) --
+ * the table of sizes, 8 bytes per (entry, block); contents unspecified afterwards. */
+int rspt_hip_compress_budget_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t nladder, size_t* bytes);
+int rspt_hip_compress_budget_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, const double* ladder, size_t nladder,
+                                       size_t budget_bytes, const uint64_t* d_budget, void* d_dst, size_t dst_stride, uint64_t* d_sizes,
+                                       uint32_t* d_choice, uint64_t* d_cand_sizes, void* d_work, void* stream);
+/* The candidates take one of two routes; both give the same table, d_choice and streams bit for bit.  general: every supported
+ * shape, one pass per ladder entry of the kernels of a ladder call whose every choice is that entry, stopped behind the trees.
+ * batched: hadamard rows of up to 8192 points with nladder * nblocks <= 65535 -- the handle's workspace grows to
+ * nladder * nblocks blocks (rspt_hip_reserve), one kernel reads each row once, keeps its transform in LDS and writes every
+ * entry's coefficients, and ONE pass of the plane, histogram and tree kernels runs over all of them.  For tests: route 0 = the
+ * host's choice (default), 1 = general, 2 = batched (RSPT_HIP_ERR_UNSUPPORTED where the handle's shape does not take it, and
+ * from the two entries above for a call of more than 65535 entry-blocks while it is forced; RSPT_HIP_ERR_ARG for any other
+ * value). */
+int rspt_hip_debug_set_budget_route(rspt_hip_packer* p, int route);
+
 /* ---- planar int32 in and out: samples that already live in a [nblocks][nch][ns] int32 matrix skip the native block ----
  * d_planar is what rspt_hip_native_to_i32_batch_dev writes and rspt_hip_i32_to_native_batch_dev reads: block b's channel c at
  * d_planar + (b*nch + c)*ns.  It must be 4-byte aligned; 16-byte aligned buffers take the widest accesses.  The contract is two

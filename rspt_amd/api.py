@@ -61,6 +61,9 @@ C_ABI = {
     "rspt_hip_compress_target_work_bytes": (_i, [_p, _z, _z, _szp]),
     "rspt_hip_compress_target_batch_dev": (_i, [_p, _p, _z, _dp, _z, _d, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_debug_set_target_route": (_i, [_p, _i]),
+    "rspt_hip_compress_budget_work_bytes": (_i, [_p, _z, _z, _szp]),
+    "rspt_hip_compress_budget_batch_dev": (_i, [_p, _p, _z, _dp, _z, _z, _p, _p, _z, _p, _p, _p, _p, _p]),
+    "rspt_hip_debug_set_budget_route": (_i, [_p, _i]),
     "rspt_hip_compress_planar_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_decompress_planar_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
     "rspt_hip_decompress_packed_planar_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
@@ -444,6 +447,49 @@ class SignalPacker:
         the chosen indices (torch.int32; decompress_batch needs them) and the chosen entries' PRDN (float64)."""
         return self._compress_to_prdn("rspt_hip_compress_target_batch_dev", self.target_work_bytes, d_src, self._nblocks(d_src), target, ladder,
                                       work, stream, d_dst, dst_stride)
+
+    def budget_work_bytes(self, nblocks, nladder):
+        """bytes of compress_to_budget's work area, for the route a call would take now (debug_set_budget_route)"""
+        return self._bytes("rspt_hip_compress_budget_work_bytes", int(nblocks), int(nladder))
+
+    def debug_set_budget_route(self, route):
+        """compress_to_budget's route, for tests: 0 the host's choice, 1 general, 2 batched (rspt_hip_debug_set_budget_route)"""
+        self._call("rspt_hip_debug_set_budget_route", int(route))
+
+    def compress_to_budget(self, d_src, budget, ladder, work=None, stream=None, d_dst=None, dst_stride=None, cand_sizes=False):
+        """The finest entry of a quality ladder whose stream is at most `budget` bytes, block by block (rspt_hip.h:
+        rspt_hip_compress_budget_batch_dev): block b takes the highest index of `ladder` (ordered coarse to fine) whose stream
+        fits, and the smallest stream if none does (then d_sizes[b] > its budget).  One asynchronous call; no candidate's stream
+        is written.  budget: an int for every block, or a torch.int64 cuda tensor [nblocks] (read as unsigned).
+        work: a device tensor of at least budget_work_bytes(nblocks, len(ladder)) bytes, 16-byte aligned; None: allocated here.
+        Returns (d_dst, d_sizes, d_choice): streams and sizes as compress_batch(ladder=, choice=d_choice) writes them and the
+        chosen indices (torch.int32; decompress_batch needs them); with cand_sizes also d_cand, torch.int64 [nladder, nblocks],
+        every candidate's stream size."""
+        import torch
+
+        nblocks = self._nblocks(d_src)
+        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+        dev = d_src.device
+        if dst_stride is None:
+            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
+        if d_dst is None:
+            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=dev)
+        d_sizes = torch.empty(nblocks, dtype=torch.int64, device=dev)
+        d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        d_cand = torch.empty((lad.size, nblocks), dtype=torch.int64, device=dev) if cand_sizes else None
+        if isinstance(budget, torch.Tensor):
+            assert budget.is_cuda and budget.dtype == torch.int64 and budget.is_contiguous() and budget.numel() == nblocks
+            scalar, d_budget = 0, budget.data_ptr()
+        else:
+            scalar, d_budget = int(budget), None
+            assert 0 <= scalar < 1 << 64
+        if work is None:
+            work = torch.empty((self.budget_work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
+        assert work.is_cuda and work.is_contiguous()
+        self._call("rspt_hip_compress_budget_batch_dev", d_src.data_ptr(), nblocks, _dptr(lad), lad.size, scalar, d_budget, d_dst.data_ptr(),
+                   dst_stride, d_sizes.data_ptr(), d_choice.data_ptr(), None if d_cand is None else d_cand.data_ptr(), work.data_ptr(),
+                   self._stream(stream, dev))
+        return (d_dst, d_sizes, d_choice) + ((d_cand,) if cand_sizes else ())
 
     def target_planar_work_bytes(self, nblocks, nladder):
         """bytes of compress_to_prdn_planar's work area, for the route a call would take now (debug_set_target_route)"""

@@ -7,7 +7,7 @@
 // There is no CPU path: every entry point fails loudly if the device is missing.
 // Here: create / reserve / destroy, the compress phases, the decoder, the single-block entries.  Included at the end: host_pipeline.hip
 // (compress_many / decompress_many / feed), host_gather.hip (RCCL), host_stages.hip (IIR, FIR, median, peak, PRDN, converters),
-// host_target.hip (compress to a PRDN target).
+// host_target.hip (compress to a PRDN target), host_budget.hip (compress to a byte budget).
 #include "../../include/rspt_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -50,6 +50,7 @@
 #include "planar.hip"
 #include "target.hip"
 #include "pack_choice.hip"
+#include "budget.hip"
 
 using namespace rspt;
 
@@ -801,6 +802,31 @@ static void launch_forward_transform(rspt_hip_packer* p, uint32_t B, hipStream_t
     }
 }
 
+// What every compress pass starts with, for `nblocks` blocks: the views into the per-call zero region -- the copy the pass works in,
+// zeroed here only where the call before has not done it -- and, where something else wrote the planes, every plane flagged dirty.
+static int front_begin(rspt_hip_packer* p, size_t nblocks, hipStream_t st) {
+    const Geom& g = p->g;
+    const size_t nhb_call = slots_of(p, nblocks) * kMaxPlanes * g.nblk;
+    p->nzflag = p->ws.zbuf[p->ws.zset];
+    p->needmask = p->nzflag + nhb_call;
+    p->work_ctr = p->needmask + ((nblocks + 3) & ~(size_t)3);
+    size_t zwords = (size_t)((p->work_ctr + 16) - p->nzflag);
+    p->row_sum = nullptr;
+    p->have_row_sum = false;
+    if (g.kind == RSPT_HIP_KIND_DCT && p->dct_fft) {  // channel sums of the de-interleave pass, 8-byte aligned behind the counters
+        zwords = (zwords + 1) & ~(size_t)1;
+        p->row_sum = reinterpret_cast<long long*>(p->nzflag + zwords);
+        zwords += 2 * nblocks * (size_t)g.nch;
+    }
+    if (!p->ws.zero_ready[p->ws.zset]) HIPCHK(p, hipMemsetAsync(p->nzflag, 0, zwords * sizeof(uint32_t), st));  // (first call, or after a failed one)
+    p->ws.zero_ready[0] = p->ws.zero_ready[1] = false;  // this copy is in use now; the other one becomes ready once k_tree is launched
+    if (p->ws.planes_unknown || (p->ablate & ~(3u << 26)) || p->psel) {  // (diagnostic runs skip kernels and stores: never trust the planes they leave; probes 26 / 27 store everything)
+        HIPCHK(p, hipMemsetAsync(p->ws.plane_dirty, 0xFF, p->ws.cap_slots * kMaxPlanes * 4 * sizeof(uint32_t), st));
+        p->ws.planes_unknown = false;
+    }
+    return RSPT_HIP_OK;
+}
+
 // ---- the compress sequence, phase by phase ----------------------------------------------------------------------------------------
 // (Round 4 measured whether the phases of TWO batches can overlap -- two whole batches racing on two streams, and an ordered
 // schedule with the latency-bound middle of batch i on a second stream beside the front end of batch i+1: neither beats one
@@ -817,26 +843,7 @@ static int phase_front(rspt_hip_packer* p, const uint8_t* src, size_t nblocks, h
     const uint32_t B = (uint32_t)nblocks;
     stamp(p, ST_PRE, st);
     const bool xd = g.kind == RSPT_HIP_KIND_XDELTA_HZR;
-    {
-        const size_t nhb_call = slots_of(p, nblocks) * kMaxPlanes * g.nblk;
-        p->nzflag = p->ws.zbuf[p->ws.zset];
-        p->needmask = p->nzflag + nhb_call;
-        p->work_ctr = p->needmask + ((nblocks + 3) & ~(size_t)3);
-        size_t zwords = (size_t)((p->work_ctr + 16) - p->nzflag);
-        p->row_sum = nullptr;
-        p->have_row_sum = false;
-        if (g.kind == RSPT_HIP_KIND_DCT && p->dct_fft) {  // channel sums of the de-interleave pass, 8-byte aligned behind the counters
-            zwords = (zwords + 1) & ~(size_t)1;
-            p->row_sum = reinterpret_cast<long long*>(p->nzflag + zwords);
-            zwords += 2 * nblocks * (size_t)g.nch;
-        }
-        if (!p->ws.zero_ready[p->ws.zset]) HIPCHK(p, hipMemsetAsync(p->nzflag, 0, zwords * sizeof(uint32_t), st));  // (first call, or after a failed one)
-        p->ws.zero_ready[0] = p->ws.zero_ready[1] = false;  // this copy is in use now; the other one becomes ready once k_tree is launched
-    }
-    if (p->ws.planes_unknown || (p->ablate & ~(3u << 26)) || p->psel) {  // (diagnostic runs skip kernels and stores: never trust the planes they leave; probes 26 / 27 store everything)
-        HIPCHK(p, hipMemsetAsync(p->ws.plane_dirty, 0xFF, p->ws.cap_slots * kMaxPlanes * 4 * sizeof(uint32_t), st));
-        p->ws.planes_unknown = false;
-    }
+    if (int rc = front_begin(p, nblocks, st)) return rc;
     if (g.kind == RSPT_HIP_KIND_BYTES) {
         // the ingest kernel is the whole front end: planes, segment bits and nbuse[] (no escalation: nb_state stays 1)
         const uint64_t units = (uint64_t)nblocks * ((g.N + 4095u) >> 12);
@@ -1567,3 +1574,4 @@ int rspt_hip_stage_times(rspt_hip_packer* p, float* ms, int n) {
 
 #include "host_stages.hip"  // (templates: outside the block; rspt_hip.h declares every entry extern "C")
 #include "host_target.hip"
+#include "host_budget.hip"
