@@ -142,9 +142,14 @@ def main():
     refrecord.write_record("lossy_quantizer_record.json", out, per_line=("cases", "defaults"))
 
 
-if __name__ == "__main__":
-    if os.environ.get("RSPT_LQ_STACK_LIFTED") != "1":  # a fresh child process with the stack limit lifted runs the cases
+def with_the_stack_limit_lifted(main):
+    """main() in a fresh child process whose stack limit is the hard one (fwht.c keeps two n-point arrays on the stack)"""
+    if os.environ.get("RSPT_LQ_STACK_LIFTED") != "1":
         hard = resource.getrlimit(resource.RLIMIT_STACK)[1]
         resource.setrlimit(resource.RLIMIT_STACK, (hard, hard))
         sys.exit(subprocess.call([sys.executable] + sys.argv, env=dict(os.environ, RSPT_LQ_STACK_LIFTED="1")))
     main()
+
+
+if __name__ == "__main__":
+    with_the_stack_limit_lifted(main)

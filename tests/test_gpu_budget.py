@@ -14,6 +14,7 @@ import pytest
 import budget_cases as bc
 import cases
 import devframe as df
+import lossy_dev as ld
 import lossy_quantizer_cases as lq
 from devframe import ERR_ARG, ERR_UNSUPPORTED, api  # noqa: F401
 
@@ -34,18 +35,7 @@ def _new(api, shape):
 
 def _composed(pk, d_src, ladder):
     """what a user does today, per ladder entry: (streams, sizes, decoded) on the host; the handle is left as it was"""
-    import torch
-
-    own = pk.quantizer()
-    out = []
-    for q in ladder:
-        pk.set_quantizer(q)
-        d_dst, d_sizes = pk.compress_batch(d_src)
-        d_out, _ = pk.decompress_batch(d_dst, d_src.shape[0], d_dst.shape[1])
-        torch.cuda.synchronize()
-        out.append((d_dst.cpu().numpy(), d_sizes.cpu().numpy(), d_out.cpu().numpy()))
-    pk.set_quantizer(own[0])
-    return out
+    return [(o["dst"], o["sizes"], o["out"]) for o in ld.composed(pk, d_src, ladder)]
 
 
 def _table(oracle):
@@ -56,22 +46,11 @@ def _table(oracle):
 
 def _held_to_the_oracle(pk, d_src, ladder, oracle, budget, tag):
     """one budget call -- budget: an int, or one int per block -- checked in full; -> the choices"""
-    import torch
-
-    B, K = d_src.shape[0], len(ladder)
+    B = d_src.shape[0]
     table = _table(oracle)
-    limits = [int(budget)] * B if isinstance(budget, int) else [int(v) for v in budget]
-    arg = budget if isinstance(budget, int) else torch.from_numpy(np.array([v - (1 << 64) if v >= BIT63 else v for v in limits], dtype=np.int64)).cuda()
-    own = pk.quantizer()
-    nwork = pk.budget_work_bytes(B, K)
-    work = torch.full(((nwork + 7) // 8 + 2,), float("nan"), dtype=torch.float64, device="cuda")
-    d_dst, d_sizes, d_choice, d_cand = pk.compress_to_budget(d_src, arg, ladder, work=work[:-2], cand_sizes=True)
-    d_out, d_used = pk.decompress_batch(d_dst, B, d_dst.shape[1], ladder=ladder, choice=d_choice)
-    torch.cuda.synchronize()
-    assert all(x != x for x in work[-2:].cpu().numpy()), (tag, "written behind the bytes the sizing call names")
-    assert pk.quantizer() == own, tag
-    choice, sizes, dst, out = d_choice.cpu().numpy(), d_sizes.cpu().numpy(), d_dst.cpu().numpy(), d_out.cpu().numpy()
-    assert np.array_equal(d_cand.cpu().numpy(), table), (tag, "the table of candidate sizes")
+    # (the work area's guard, the handle's quantiser, the decoder's consumed bytes and the handle's HIP error: lossy_dev.budget_call)
+    limits, choice, sizes, dst, out, cand = ld.budget_call(pk, d_src, ladder, budget, tag)
+    assert np.array_equal(cand, table), (tag, "the table of candidate sizes")
     for b in range(B):
         k = bc.choose(table[:, b], limits[b])
         assert int(choice[b]) == k, (tag, b, table[:, b].tolist(), limits[b], int(choice[b]))
@@ -79,15 +58,7 @@ def _held_to_the_oracle(pk, d_src, ladder, oracle, budget, tag):
         assert int(sizes[b]) == n, (tag, b, k)
         assert np.array_equal(dst[b, :n], oracle[k][0][b, :n]), (tag, b, k, "stream")
         assert np.array_equal(out[b], oracle[k][2][b]), (tag, b, k, "decoded")
-    assert np.array_equal(d_used.cpu().numpy(), sizes), tag
-    assert api_error(pk) == 0, tag
     return choice
-
-
-def api_error(pk):
-    from rspt_amd import api as a
-
-    return a.lib().rspt_hip_last_hip_error(pk._h)
 
 
 @pytest.fixture(scope="module")

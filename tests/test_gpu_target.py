@@ -14,6 +14,7 @@ import math
 import numpy as np
 import pytest
 
+import lossy_dev as ld
 import lossy_quantizer_cases as lq
 import prdn_cases
 import target_cases as tc
@@ -37,19 +38,7 @@ def _bits(a):
 
 def _composed(pk, d_src, c):
     """what a user does today, per ladder entry: (streams, sizes, prdn, mse, path) on the host; the handle is left as it was"""
-    import torch
-
-    own = pk.quantizer()
-    out = []
-    for q in c["ladder"]:
-        pk.set_quantizer(q)
-        d_dst, d_sizes = pk.compress_batch(d_src)
-        d_out, _ = pk.decompress_batch(d_dst, d_src.shape[0], d_dst.shape[1])
-        prdn, mse, ref, path = pk.prdn_batch(d_src.reshape(-1), d_out.reshape(-1), parts=True)
-        torch.cuda.synchronize()
-        out.append((d_dst.cpu().numpy(), d_sizes.cpu().numpy(), prdn.cpu().numpy(), mse.cpu().numpy(), path.cpu().numpy()))
-    pk.set_quantizer(own[0])
-    return out
+    return [(o["dst"], o["sizes"], o["prdn"], o["mse"], o["path"]) for o in ld.composed(pk, d_src, c["ladder"], prdn=True)]
 
 
 ROUTE_NAMES = {0: "auto", 1: "general", 2: "fused"}
@@ -81,11 +70,10 @@ def test_target_against_the_composed_oracle_and_the_restatement(api, name, route
     plain_before, plain_sizes = [t.cpu().numpy() for t in pk.compress_batch(d_src)]
     oracle = _composed(pk, d_src, c)
 
-    nwork = pk.target_work_bytes(nblocks, K)
-    work = torch.full(((nwork + 7) // 8 + 2,), float("nan"), dtype=torch.float64, device="cuda")
+    work = ld.guarded_work(pk.target_work_bytes(nblocks, K))
     d_dst, d_sizes, d_choice, d_prdn = pk.compress_to_prdn(d_src, c["target"], c["ladder"], work=work[:-2])
     torch.cuda.synchronize()
-    assert all(x != x for x in work[-2:].cpu().numpy())  # (nothing behind the bytes the sizing call names)
+    assert ld.work_guard_untouched(work)  # (nothing behind the bytes the sizing call names)
     assert pk.quantizer() == own
     choice, prdn, sizes, dst = d_choice.cpu().numpy(), d_prdn.cpu().numpy(), d_sizes.cpu().numpy(), d_dst.cpu().numpy()
 
