@@ -378,9 +378,9 @@ int rspt_hip_decompress_planar_batch_dev(rspt_hip_packer* p, const void* d_src, 
 int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, int32_t* d_planar,
                                           uint64_t* d_consumed, void* stream);
 
-/* ---- the quality ladder and the PRDN target on the planar matrix ----
- * The planar forms of rspt_hip_compress_batch_ladder_dev, rspt_hip_decompress_batch_ladder_dev and
- * rspt_hip_compress_target_batch_dev, under three identities:
+/* ---- the quality ladder, the PRDN target and the byte budget on the planar matrix ----
+ * The planar forms of rspt_hip_compress_batch_ladder_dev, rspt_hip_decompress_batch_ladder_dev,
+ * rspt_hip_compress_target_batch_dev and rspt_hip_compress_budget_batch_dev, under four identities:
  *
  *   compress_planar_ladder(P, ladder, choice)  ==  rspt_hip_compress_batch_ladder_dev(rspt_hip_i32_to_native_batch_dev(P), ladder, choice)
  *       the streams, d_sizes, and "exactly bit 63, nothing written" for d_choice[b] >= nladder.
@@ -392,11 +392,16 @@ int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_pack
  *       therefore the matrix CUT TO THE SAMPLE WIDTH -- what the stream can carry, the convention of
  *       rspt_hip_compress_planar_batch_dev: whatever lies above the low bps bytes of a value changes nothing.
  *       (rspt_hip_prdn_planar_batch_dev's "the whole int32 is the sample" does not apply here.)
+ *   budget_planar(P, ...)  ==  rspt_hip_compress_budget_batch_dev(rspt_hip_i32_to_native_batch_dev(P), ...)
+ *       d_choice, d_sizes (bit 63 included), the whole d_cand_sizes table and the streams byte for byte, and through
+ *       rspt_hip_decompress_planar_batch_ladder_dev the decoded matrix.  On a handle of bps < 4 only the low bps bytes of each
+ *       value count, as above; rspt_hip_set_byte_order has no effect.
  *
  * The refusals are the union of the planar entries' and the ladder entries': d_planar and d_choice 4-byte aligned (any 4-byte
  * alignment of the matrix works), RSPT_HIP_ERR_UNSUPPORTED for every kind but hadamard and the dense dct, the dst_stride bound,
  * the ladder's validation, an open feed; the target entry adds the native one's (target_prdn, nblocks <= 65535, d_prdn 8-byte
- * and d_work 16-byte aligned).  A refused call writes nothing.  d_planar is only read by the compress entries.  Asynchronous on
+ * and d_work 16-byte aligned), the budget entry the native one's (nblocks <= 65535, d_budget and d_cand_sizes 8-byte and d_work
+ * 16-byte aligned).  A refused call launches nothing and writes nothing.  d_planar is only read by the compress entries.  Asynchronous on
  * `stream`, no host synchronisation inside beyond rspt_hip_reserve's; the handle's own quantiser is neither read nor changed.
  *
  * The target entry takes the native one's two routes under the same condition, and rspt_hip_debug_set_target_route governs
@@ -407,7 +412,15 @@ int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_pack
  * rspt_hip_compress_target_planar_work_bytes names it for the route a call would take NOW (after a change through
  * rspt_hip_debug_set_target_route, ask again) -- general: one decoded copy, the segment marks, and the cut original at bps < 4,
  * which at bps 4 is rspt_hip_compress_target_work_bytes less one planar copy or more; fused: 16 bytes, so that d_work is a
- * pointer.  Nothing is written behind the bytes it names. */
+ * pointer.  Nothing is written behind the bytes it names.
+ *
+ * The budget entry takes the native one's two routes under the same conditions, and rspt_hip_debug_set_budget_route governs it
+ * too; both give the same bits.  batched: the probe reads each row from the caller's matrix, cutting it as it loads -- no
+ * converter pass, and no copy of the original in the workspace.  general: per ladder entry, and once more for the chosen streams,
+ * the matrix goes through the planar front end.  d_work is the native entry's on either route -- the table of sizes and nothing
+ * else: rspt_hip_compress_budget_planar_work_bytes names the bytes rspt_hip_compress_budget_work_bytes names, with its refusals
+ * (RSPT_HIP_ERR_UNSUPPORTED for more than 65535 entry-blocks while the batched route is forced).  Native and planar budget calls
+ * may alternate on one handle. */
 int rspt_hip_compress_planar_batch_ladder_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
                                               const uint32_t* d_choice, void* d_dst, size_t dst_stride, uint64_t* d_sizes, void* stream);
 int rspt_hip_decompress_planar_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, const double* ladder,
@@ -416,6 +429,10 @@ int rspt_hip_compress_target_planar_work_bytes(rspt_hip_packer* p, size_t nblock
 int rspt_hip_compress_target_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
                                               double target_prdn, void* d_dst, size_t dst_stride, uint64_t* d_sizes, uint32_t* d_choice,
                                               double* d_prdn, void* d_work, void* stream);
+int rspt_hip_compress_budget_planar_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t nladder, size_t* bytes);
+int rspt_hip_compress_budget_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
+                                              size_t budget_bytes, const uint64_t* d_budget, void* d_dst, size_t dst_stride, uint64_t* d_sizes,
+                                              uint32_t* d_choice, uint64_t* d_cand_sizes, void* d_work, void* stream);
 
 /* hzr_verify (hzr_decode.c:569-624) of nblocks libhzr streams resident in device memory, WITHOUT decoding them: the frame walk,
  * the mode byte of every block (<= 2) and the CRC-32C of every block's payload against its header.  Stream b starts at

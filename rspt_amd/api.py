@@ -71,6 +71,8 @@ C_ABI = {
     "rspt_hip_decompress_planar_batch_ladder_dev": (_i, [_p, _p, _z, _z, _dp, _z, _p, _p, _p, _p]),
     "rspt_hip_compress_target_planar_work_bytes": (_i, [_p, _z, _z, _szp]),
     "rspt_hip_compress_target_planar_batch_dev": (_i, [_p, _p, _z, _dp, _z, _d, _p, _z, _p, _p, _p, _p, _p]),
+    "rspt_hip_compress_budget_planar_work_bytes": (_i, [_p, _z, _z, _szp]),
+    "rspt_hip_compress_budget_planar_batch_dev": (_i, [_p, _p, _z, _dp, _z, _z, _p, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_hzr_verify_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_pack_bound": (_z, [_p, _z]),
     "rspt_hip_pack_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p, _p]),
@@ -465,9 +467,27 @@ class SignalPacker:
         Returns (d_dst, d_sizes, d_choice): streams and sizes as compress_batch(ladder=, choice=d_choice) writes them and the
         chosen indices (torch.int32; decompress_batch needs them); with cand_sizes also d_cand, torch.int64 [nladder, nblocks],
         every candidate's stream size."""
+        return self._compress_to_budget("rspt_hip_compress_budget_batch_dev", self.budget_work_bytes, d_src, self._nblocks(d_src), budget, ladder,
+                                        work, stream, d_dst, dst_stride, cand_sizes)
+
+    def budget_planar_work_bytes(self, nblocks, nladder):
+        """bytes of compress_to_budget_planar's work area: those of budget_work_bytes, on either route"""
+        return self._bytes("rspt_hip_compress_budget_planar_work_bytes", int(nblocks), int(nladder))
+
+    def compress_to_budget_planar(self, d_planar, budget, ladder, work=None, stream=None, d_dst=None, dst_stride=None, cand_sizes=False):
+        """compress_to_budget for samples that already live in int32 (rspt_hip.h: rspt_hip_compress_budget_planar_batch_dev): d_planar
+        is a contiguous torch.int32 cuda tensor [nblocks, nch, ns], only read; everything returned is what
+        compress_to_budget(from_planar_i32(d_planar), ...) returns -- on a handle of bps < 4 only the low bps bytes of a value count.
+        work: at least budget_planar_work_bytes(nblocks, len(ladder)) bytes, 16-byte aligned; None: allocated here."""
         import torch
 
-        nblocks = self._nblocks(d_src)
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        return self._compress_to_budget("rspt_hip_compress_budget_planar_batch_dev", self.budget_planar_work_bytes, d_planar, nblocks, budget,
+                                        ladder, work, stream, d_dst, dst_stride, cand_sizes)
+
+    def _compress_to_budget(self, entry, work_bytes, d_src, nblocks, budget, ladder, work, stream, d_dst, dst_stride, cand_sizes):
+        import torch
+
         lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
         dev = d_src.device
         if dst_stride is None:
@@ -484,11 +504,10 @@ class SignalPacker:
             scalar, d_budget = int(budget), None
             assert 0 <= scalar < 1 << 64
         if work is None:
-            work = torch.empty((self.budget_work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
+            work = torch.empty((work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
         assert work.is_cuda and work.is_contiguous()
-        self._call("rspt_hip_compress_budget_batch_dev", d_src.data_ptr(), nblocks, _dptr(lad), lad.size, scalar, d_budget, d_dst.data_ptr(),
-                   dst_stride, d_sizes.data_ptr(), d_choice.data_ptr(), None if d_cand is None else d_cand.data_ptr(), work.data_ptr(),
-                   self._stream(stream, dev))
+        self._call(entry, d_src.data_ptr(), nblocks, _dptr(lad), lad.size, scalar, d_budget, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(),
+                   d_choice.data_ptr(), None if d_cand is None else d_cand.data_ptr(), work.data_ptr(), self._stream(stream, dev))
         return (d_dst, d_sizes, d_choice) + ((d_cand,) if cand_sizes else ())
 
     def target_planar_work_bytes(self, nblocks, nladder):

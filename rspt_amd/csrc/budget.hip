@@ -1,4 +1,5 @@
-// budget.hip -- compress to a byte budget (rspt_hip_compress_budget_batch_dev): the finest ladder entry whose stream fits, per block.
+// budget.hip -- compress to a byte budget (rspt_hip_compress_budget_batch_dev and its planar form,
+// rspt_hip_compress_budget_planar_batch_dev): the finest ladder entry whose stream fits, per block.
 //
 //   k_budget_sizes    one wave per block slot: the stream size k_layout would name for the slot, from what k_tree left --
 //                     1 + hdr_len + 8 nb + the sum over the slot's nb * nblk hzr blocks of (7 + payload_len).  No byte of a stream
@@ -9,6 +10,8 @@
 //                     reads the row once, takes its mean and W = WHT(x - mean) once (k_tp_transform_body.hpp, the transform of
 //                     k_target_probe) and writes, per ladder entry k, fwht_quant(W, n / q_k) -- the coefficients k_fwht_l leaves
 //                     for a block of choice k -- as row c of block slot k * nblocks + b of the planar workspace.
+//   k_planar_budget_probe  the same body (k_budget_probe_body.hpp) for rspt_hip_compress_budget_planar_batch_dev: the rows come
+//                     from the caller's [nblocks][nch][ns] int32 matrix, cut to the sample width as they are loaded.
 #include "common.hpp"
 
 namespace rspt {
@@ -50,12 +53,16 @@ __global__ __launch_bounds__(256) void k_budget_select(const unsigned long long*
 // blockDim.x: a multiple of 64 with blockDim.x * kTpPer >= ns; dynamic LDS: tp_pad(ns) words.
 __global__ __launch_bounds__(1024) void k_budget_probe(const int32_t* orig, Geom g, QLadder fwd, uint32_t nblocks, int32_t* slots) {
     constexpr bool kPlanarCut = false;
-#include "k_tp_transform_body.hpp"
-    for (uint32_t k = 0; k < fwd.n; ++k) {
-        const double dfwd = fwd.a[k];
-        int32_t* out = slots + ((size_t)k * nblocks + b) * g.N + (size_t)c * n;
-        for (uint32_t i = tid; i < n; i += nt) out[i] = fwht_quant((int32_t)W[tp_pad(i)], dfwd);
-    }
+#include "k_budget_probe_body.hpp"
+}
+
+// k_planar_budget_probe: the probe of rspt_hip_compress_budget_planar_batch_dev -- the rows are the caller's matrix (single dwords
+// at tid + j * nt: its 4-byte alignment is all they need), cut to the sample width on load.  orig is only read and lies outside
+// slots: nothing but this kernel reads the matrix, and every slot of every entry is written from LDS.
+__global__ __launch_bounds__(1024) void k_planar_budget_probe(const int32_t* __restrict__ orig, Geom g, QLadder fwd, uint32_t nblocks,
+                                                             int32_t* __restrict__ slots) {
+    constexpr bool kPlanarCut = true;
+#include "k_budget_probe_body.hpp"
 }
 
 }  // namespace rspt
