@@ -351,6 +351,59 @@ int rspt_hip_compress_budget_batch_dev(rspt_hip_packer* p, const void* d_src, si
  * value). */
 int rspt_hip_debug_set_budget_route(rspt_hip_packer* p, int route);
 
+/* ---- compress a batch to one byte total: the lowest common PRDN level at which the whole batch fits ----
+ * A budget arrives for a batch -- a link, a file, a gather buffer has room for total_bytes of it -- and not per block.  The rule
+ * is minimax: every block is taken to the same PRDN level T, each at its smallest stream that meets T, and T is the lowest level
+ * at which the streams add up to at most total_bytes.  It is exact: no floating-point sum over blocks decides anything, levels
+ * compare as doubles that are bit-identical with rspt_hip_prdn_batch_dev's.
+ * The rule.  For block b and ladder entry k: size_k(b) is rspt_hip_compress_budget_batch_dev's size_k(b), and (prdn_k(b),
+ * mse_k(b), path_k(b)) is rspt_hip_compress_target_batch_dev's triple, what rspt_hip_prdn_batch_dev(o, d_k) gives.
+ *   Entry k of block b is RATED iff path_k(b) == 0 and (mse_k(b) == 0 or prdn_k(b) is not a NaN).  A rated entry's FIGURE is
+ *   f_k(b) = +0.0 if mse_k(b) == 0, else prdn_k(b); it may be +inf (a constant block with a lossy error) and is never negative.
+ *   The figure of an unrated entry is reported as a NaN (0x7FF8000000000000).  A block is rated iff it has a rated entry.
+ *   At a level T in [0, +inf], pick_T(b) is the rated entry of smallest size among those with f_k(b) <= T (inclusive), the
+ *   lowest index among equal sizes.  An unrated block takes its smallest stream at every level, the lowest index among equals,
+ *   and its figures never count.  T is ADMISSIBLE iff every rated block has a pick at T.  cost(T) is the sum over all blocks of
+ *   the size of the pick (of the smallest stream, for an unrated block), in 64 bits.  cost is non-increasing in T over
+ *   admissible levels and admissibility is monotone in T.
+ *   T* is the smallest admissible T with cost(T) <= total_bytes, and +inf -- which is always admissible -- if there is none.
+ *   T* is always one of the figures, or +inf; with no rated block at all T* is +0.0, whatever total_bytes.
+ * d_choice[b] = pick_T*(b); d_level[0] = T*; d_total[0] = cost(T*).  The caller sees a miss as d_total[0] > total_bytes; a T* of
+ * +inf alone is not one.  Any total_bytes is allowed, 0 and 2^64 - 1 included, and nothing assumes that sizes or figures are
+ * sorted along the ladder.  Every (block, entry) figure is a level of its own, and passing from one level to the next moves the
+ * picks of the blocks that have an entry at exactly that figure: the slack left under total_bytes is at most those blocks' steps.
+ * Streams, d_sizes and (with d_choice) the decoded samples are byte for byte those of rspt_hip_compress_batch_ladder_dev /
+ * rspt_hip_decompress_batch_ladder_dev with that d_choice, which is the caller's to keep.  A chosen stream that does not fit
+ * dst_stride is flagged as the ladder call flags it (bit 63 of d_sizes[b], nothing written); dst_stride plays no part in the rule.
+ * d_prdn[b] (optional): the figure of the chosen entry -- so +0.0 where its mse is 0, where the PRDN target entry reports the
+ * PRDN stage's own value -- and, as there, +inf where its path is 1.
+ * d_cand_sizes, d_cand_figs (optional): the two tables, size_k(b) and the figure of entry k of block b at [k * nblocks + b].
+ * d_level, d_total, d_prdn, d_cand_sizes and d_cand_figs are optional (NULL) and, if given, 8-byte aligned.
+ * Identity: on a ladder along which every block's sizes ascend strictly and every block's figures descend strictly, d_choice[b]
+ * is rspt_hip_compress_target_batch_dev's at target_prdn = T*, for every block that has an entry meeting T*.
+ * Kinds, ladder validation, the open feed, nblocks <= 65535, the dst_stride bound and the alignments of d_src, d_work (16 bytes)
+ * and d_choice (4 bytes) are refused exactly as rspt_hip_compress_budget_batch_dev refuses them: RSPT_HIP_ERR_UNSUPPORTED where
+ * there is no ladder (the FFT dct and every other kind), RSPT_HIP_ERR_ARG for the rest, nothing launched.
+ * Asynchronous on `stream`, no host synchronisation inside (beyond rspt_hip_reserve's when the workspace grows) and nothing
+ * copied to the host; stream-ordered with every other call on the handle; the handle's own quantiser is neither read nor changed.
+ * d_work: device memory, 16-byte aligned, at least the bytes rspt_hip_compress_total_work_bytes names for (nblocks, nladder) and
+ * the route a call would take now -- all scratch beyond the handle's workspace; contents unspecified afterwards. */
+int rspt_hip_compress_total_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t nladder, size_t* bytes);
+int rspt_hip_compress_total_batch_dev(rspt_hip_packer* p, const void* d_src, size_t nblocks, const double* ladder, size_t nladder,
+                                      size_t total_bytes, void* d_dst, size_t dst_stride, uint64_t* d_sizes, uint32_t* d_choice,
+                                      double* d_level, uint64_t* d_total, double* d_prdn, uint64_t* d_cand_sizes, double* d_cand_figs,
+                                      void* d_work, void* stream);
+/* The tables are filled on one of two routes; both give the same tables, level, choice and streams bit for bit.  general: every
+ * supported shape -- per ladder entry the PRDN target entry's general sequence and the byte budget entry's general sequence, into
+ * the two tables; its d_work holds the target entry's whole work area (two planar copies of the batch) beside the tables.  fused:
+ * hadamard rows of up to 8192 points with nch * ns < 2^22 and nladder * nblocks <= 65535 -- the handle's workspace grows to
+ * nladder * nblocks blocks (rspt_hip_reserve), one kernel reads each row once and leaves, per entry, the coefficients for the size
+ * table and the exact sums for the figure table, and ONE pass of the plane, histogram and tree kernels runs over all of them; its
+ * d_work holds tables alone, 72 bytes per (entry, block).  For tests: route 0 = the host's choice (default), 1 = general, 2 = fused
+ * (RSPT_HIP_ERR_UNSUPPORTED where the handle's shape does not take it, and from the two entries above for a call of more than
+ * 65535 entry-blocks while it is forced; RSPT_HIP_ERR_ARG for any other value). */
+int rspt_hip_debug_set_total_route(rspt_hip_packer* p, int route);   /* 0 host's pick, 1 general, 2 fused */
+
 /* ---- planar int32 in and out: samples that already live in a [nblocks][nch][ns] int32 matrix skip the native block ----
  * d_planar is what rspt_hip_native_to_i32_batch_dev writes and rspt_hip_i32_to_native_batch_dev reads: block b's channel c at
  * d_planar + (b*nch + c)*ns.  It must be 4-byte aligned; 16-byte aligned buffers take the widest accesses.  The contract is two

@@ -64,6 +64,9 @@ C_ABI = {
     "rspt_hip_compress_budget_work_bytes": (_i, [_p, _z, _z, _szp]),
     "rspt_hip_compress_budget_batch_dev": (_i, [_p, _p, _z, _dp, _z, _z, _p, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_debug_set_budget_route": (_i, [_p, _i]),
+    "rspt_hip_compress_total_work_bytes": (_i, [_p, _z, _z, _szp]),
+    "rspt_hip_compress_total_batch_dev": (_i, [_p, _p, _z, _dp, _z, _z, _p, _z, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "rspt_hip_debug_set_total_route": (_i, [_p, _i]),
     "rspt_hip_compress_planar_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_decompress_planar_batch_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
     "rspt_hip_decompress_packed_planar_dev": (_i, [_p, _p, _z, _z, _p, _p, _p]),
@@ -509,6 +512,50 @@ class SignalPacker:
         self._call(entry, d_src.data_ptr(), nblocks, _dptr(lad), lad.size, scalar, d_budget, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(),
                    d_choice.data_ptr(), None if d_cand is None else d_cand.data_ptr(), work.data_ptr(), self._stream(stream, dev))
         return (d_dst, d_sizes, d_choice) + ((d_cand,) if cand_sizes else ())
+
+    def total_work_bytes(self, nblocks, nladder):
+        """bytes of compress_to_total's work area, for the route a call would take now (debug_set_total_route)"""
+        return self._bytes("rspt_hip_compress_total_work_bytes", int(nblocks), int(nladder))
+
+    def debug_set_total_route(self, route):
+        """compress_to_total's route, for tests: 0 the host's choice, 1 general, 2 fused (rspt_hip_debug_set_total_route)"""
+        self._call("rspt_hip_debug_set_total_route", int(route))
+
+    def compress_to_total(self, d_src, total_bytes, ladder, work=None, stream=None, d_dst=None, dst_stride=None, tables=False):
+        """The whole batch in at most `total_bytes` bytes at the lowest common PRDN level (rspt_hip.h:
+        rspt_hip_compress_total_batch_dev): every block takes its smallest stream whose figure is at most the level T*, and T* is
+        the lowest level at which those streams add up to at most total_bytes -- +inf if none does (then d_total > total_bytes is
+        the miss).  One asynchronous call; no candidate's stream is written.  total_bytes: any int of 64 bits, unsigned.
+        work: a device tensor of at least total_work_bytes(nblocks, len(ladder)) bytes, 16-byte aligned; None: allocated here.
+        Returns (d_dst, d_sizes, d_choice, d_level, d_total, d_prdn): streams and sizes as compress_batch(ladder=,
+        choice=d_choice) writes them, the chosen indices (torch.int32; decompress_batch needs them), T* (float64 [1]), the sum
+        of the chosen sizes (torch.int64 [1]) and the chosen entries' figures (float64); with tables also d_cand_sizes
+        (torch.int64) and d_cand_figs (float64), both [nladder, nblocks]."""
+        import torch
+
+        nblocks = self._nblocks(d_src)
+        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+        dev = d_src.device
+        if dst_stride is None:
+            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
+        if d_dst is None:
+            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=dev)
+        d_sizes = torch.empty(nblocks, dtype=torch.int64, device=dev)
+        d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        d_level = torch.empty(1, dtype=torch.float64, device=dev)
+        d_total = torch.empty(1, dtype=torch.int64, device=dev)
+        d_prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
+        d_cand = torch.empty((lad.size, nblocks), dtype=torch.int64, device=dev) if tables else None
+        d_figs = torch.empty((lad.size, nblocks), dtype=torch.float64, device=dev) if tables else None
+        total_bytes = int(total_bytes)
+        assert 0 <= total_bytes < 1 << 64
+        if work is None:
+            work = torch.empty((self.total_work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
+        assert work.is_cuda and work.is_contiguous()
+        self._call("rspt_hip_compress_total_batch_dev", d_src.data_ptr(), nblocks, _dptr(lad), lad.size, total_bytes, d_dst.data_ptr(), dst_stride,
+                   d_sizes.data_ptr(), d_choice.data_ptr(), d_level.data_ptr(), d_total.data_ptr(), d_prdn.data_ptr(),
+                   None if d_cand is None else d_cand.data_ptr(), None if d_figs is None else d_figs.data_ptr(), work.data_ptr(), self._stream(stream, dev))
+        return (d_dst, d_sizes, d_choice, d_level, d_total, d_prdn) + ((d_cand, d_figs) if tables else ())
 
     def target_planar_work_bytes(self, nblocks, nladder):
         """bytes of compress_to_prdn_planar's work area, for the route a call would take now (debug_set_target_route)"""

@@ -260,6 +260,7 @@ struct rspt_hip_packer {
     uint32_t psel = 0;    // RSPT_PLANESEL (diagnostic builds only): which planes the hzr kernels take; bit 8 / 9: stop behind k_hist / k_tree
     uint32_t target_route = 0;  // rspt_hip_debug_set_target_route: 0 = the host's choice, 1 = the general route, 2 = the fused probe
     uint32_t budget_route = 0;  // rspt_hip_debug_set_budget_route: 0 = the host's choice, 1 = the general route, 2 = the batched one
+    uint32_t total_route = 0;   // rspt_hip_debug_set_total_route: 0 = the host's choice, 1 = the general route, 2 = the fused one
     uint32_t qp_form = 0; // RSPT_QP_FORM (diagnostic builds only): planar PRDN form; 0 = the host's choice, 1 = split, 2 = whole rows
     int verify = 0;       // decompress checks the block CRCs (rspt_hip_set_verify)
     int big_endian = 0;   // samples arrive / leave with their bytes reversed (rspt_hip_set_byte_order)

@@ -7,7 +7,8 @@
 // There is no CPU path: every entry point fails loudly if the device is missing.
 // Here: create / reserve / destroy, the compress phases, the decoder, the single-block entries.  Included at the end: host_pipeline.hip
 // (compress_many / decompress_many / feed), host_gather.hip (RCCL), host_stages.hip (IIR, FIR, median, peak, PRDN, converters),
-// host_target.hip (compress to a PRDN target), host_budget.hip (compress to a byte budget).
+// host_target.hip (compress to a PRDN target), host_budget.hip (compress to a byte budget), host_total.hip (compress a batch to one
+// byte total).
 #include "../../include/rspt_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -51,6 +52,7 @@
 #include "target.hip"
 #include "pack_choice.hip"
 #include "budget.hip"
+#include "total.hip"
 
 using namespace rspt;
 
@@ -1575,3 +1577,4 @@ int rspt_hip_stage_times(rspt_hip_packer* p, float* ms, int n) {
 #include "host_stages.hip"  // (templates: outside the block; rspt_hip.h declares every entry extern "C")
 #include "host_target.hip"
 #include "host_budget.hip"
+#include "host_total.hip"
