@@ -431,9 +431,10 @@ int rspt_hip_decompress_planar_batch_dev(rspt_hip_packer* p, const void* d_src, 
 int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_packed, size_t packed_len, size_t nblocks, int32_t* d_planar,
                                           uint64_t* d_consumed, void* stream);
 
-/* ---- the quality ladder, the PRDN target and the byte budget on the planar matrix ----
+/* ---- the quality ladder, the PRDN target, the byte budget and the byte total on the planar matrix ----
  * The planar forms of rspt_hip_compress_batch_ladder_dev, rspt_hip_decompress_batch_ladder_dev,
- * rspt_hip_compress_target_batch_dev and rspt_hip_compress_budget_batch_dev, under four identities:
+ * rspt_hip_compress_target_batch_dev, rspt_hip_compress_budget_batch_dev and rspt_hip_compress_total_batch_dev, under five
+ * identities:
  *
  *   compress_planar_ladder(P, ladder, choice)  ==  rspt_hip_compress_batch_ladder_dev(rspt_hip_i32_to_native_batch_dev(P), ladder, choice)
  *       the streams, d_sizes, and "exactly bit 63, nothing written" for d_choice[b] >= nladder.
@@ -449,12 +450,17 @@ int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_pack
  *       d_choice, d_sizes (bit 63 included), the whole d_cand_sizes table and the streams byte for byte, and through
  *       rspt_hip_decompress_planar_batch_ladder_dev the decoded matrix.  On a handle of bps < 4 only the low bps bytes of each
  *       value count, as above; rspt_hip_set_byte_order has no effect.
+ *   total_planar(P, ...)  ==  rspt_hip_compress_total_batch_dev(rspt_hip_i32_to_native_batch_dev(P), ...)
+ *       d_choice, d_level, d_total and d_prdn bit for bit, both tables (d_cand_sizes, d_cand_figs), d_sizes (bit 63 included) and
+ *       the streams byte for byte, on either route.  On a handle of bps < 4 only the low bps bytes of each value count, for the
+ *       sizes and for the original the figures are taken against, as above; rspt_hip_set_byte_order has no effect.
  *
  * The refusals are the union of the planar entries' and the ladder entries': d_planar and d_choice 4-byte aligned (any 4-byte
  * alignment of the matrix works), RSPT_HIP_ERR_UNSUPPORTED for every kind but hadamard and the dense dct, the dst_stride bound,
  * the ladder's validation, an open feed; the target entry adds the native one's (target_prdn, nblocks <= 65535, d_prdn 8-byte
  * and d_work 16-byte aligned), the budget entry the native one's (nblocks <= 65535, d_budget and d_cand_sizes 8-byte and d_work
- * 16-byte aligned).  A refused call launches nothing and writes nothing.  d_planar is only read by the compress entries.  Asynchronous on
+ * 16-byte aligned), the total entry the native one's (nblocks <= 65535, d_level, d_total, d_prdn, d_cand_sizes and d_cand_figs
+ * 8-byte and d_work 16-byte aligned).  A refused call launches nothing and writes nothing.  d_planar is only read by the compress entries.  Asynchronous on
  * `stream`, no host synchronisation inside beyond rspt_hip_reserve's; the handle's own quantiser is neither read nor changed.
  *
  * The target entry takes the native one's two routes under the same condition, and rspt_hip_debug_set_target_route governs
@@ -473,7 +479,19 @@ int rspt_hip_decompress_packed_planar_dev(rspt_hip_packer* p, const void* d_pack
  * the matrix goes through the planar front end.  d_work is the native entry's on either route -- the table of sizes and nothing
  * else: rspt_hip_compress_budget_planar_work_bytes names the bytes rspt_hip_compress_budget_work_bytes names, with its refusals
  * (RSPT_HIP_ERR_UNSUPPORTED for more than 65535 entry-blocks while the batched route is forced).  Native and planar budget calls
- * may alternate on one handle. */
+ * may alternate on one handle.
+ *
+ * The total entry takes the native one's two routes under the same conditions, and rspt_hip_debug_set_total_route governs it too
+ * (one setting for both forms); both give the same bits.  fused: the probe reads each row from the caller's matrix once, cutting
+ * it as it loads -- no converter pass, no copy of the original in the workspace, every slot only written; d_work is the native
+ * fused one's, tables alone: rspt_hip_compress_total_planar_work_bytes names exactly rspt_hip_compress_total_work_bytes' bytes.
+ * general: per ladder entry the matrix goes through the planar front end in the target entry's sequence and in the budget
+ * entry's, and once more for the chosen streams; the original of the figures is the matrix itself at bps 4 -- d_work is the
+ * native general one less one nblocks * nch * ns * 4 block rounded up to 256 bytes -- and a cut copy of it inside d_work at
+ * bps < 4, where d_work is the native general one's size.  The sizing call answers for the route a call would take NOW and
+ * refuses as the native one does (RSPT_HIP_ERR_UNSUPPORTED for more than 65535 entry-blocks while the fused route is forced).
+ * Nothing is written behind the bytes it names.  Native and planar total calls may alternate on one handle, and behind either
+ * the handle is in the same state. */
 int rspt_hip_compress_planar_batch_ladder_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
                                               const uint32_t* d_choice, void* d_dst, size_t dst_stride, uint64_t* d_sizes, void* stream);
 int rspt_hip_decompress_planar_batch_ladder_dev(rspt_hip_packer* p, const void* d_src, size_t src_stride, size_t nblocks, const double* ladder,
@@ -486,6 +504,11 @@ int rspt_hip_compress_budget_planar_work_bytes(rspt_hip_packer* p, size_t nblock
 int rspt_hip_compress_budget_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder, size_t nladder,
                                               size_t budget_bytes, const uint64_t* d_budget, void* d_dst, size_t dst_stride, uint64_t* d_sizes,
                                               uint32_t* d_choice, uint64_t* d_cand_sizes, void* d_work, void* stream);
+int rspt_hip_compress_total_planar_work_bytes(rspt_hip_packer* p, size_t nblocks, size_t nladder, size_t* bytes);
+int rspt_hip_compress_total_planar_batch_dev(rspt_hip_packer* p, const int32_t* d_planar, size_t nblocks, const double* ladder,
+                                             size_t nladder, size_t total_bytes, void* d_dst, size_t dst_stride, uint64_t* d_sizes,
+                                             uint32_t* d_choice, double* d_level, uint64_t* d_total, double* d_prdn,
+                                             uint64_t* d_cand_sizes, double* d_cand_figs, void* d_work, void* stream);
 
 /* hzr_verify (hzr_decode.c:569-624) of nblocks libhzr streams resident in device memory, WITHOUT decoding them: the frame walk,
  * the mode byte of every block (<= 2) and the CRC-32C of every block's payload against its header.  Stream b starts at

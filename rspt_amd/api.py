@@ -76,6 +76,8 @@ C_ABI = {
     "rspt_hip_compress_target_planar_batch_dev": (_i, [_p, _p, _z, _dp, _z, _d, _p, _z, _p, _p, _p, _p, _p]),
     "rspt_hip_compress_budget_planar_work_bytes": (_i, [_p, _z, _z, _szp]),
     "rspt_hip_compress_budget_planar_batch_dev": (_i, [_p, _p, _z, _dp, _z, _z, _p, _p, _z, _p, _p, _p, _p, _p]),
+    "rspt_hip_compress_total_planar_work_bytes": (_i, [_p, _z, _z, _szp]),
+    "rspt_hip_compress_total_planar_batch_dev": (_i, [_p, _p, _z, _dp, _z, _z, _p, _z, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "rspt_hip_hzr_verify_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p]),
     "rspt_hip_pack_bound": (_z, [_p, _z]),
     "rspt_hip_pack_batch_dev": (_i, [_p, _p, _z, _p, _z, _p, _p, _p]),
@@ -531,9 +533,28 @@ class SignalPacker:
         choice=d_choice) writes them, the chosen indices (torch.int32; decompress_batch needs them), T* (float64 [1]), the sum
         of the chosen sizes (torch.int64 [1]) and the chosen entries' figures (float64); with tables also d_cand_sizes
         (torch.int64) and d_cand_figs (float64), both [nladder, nblocks]."""
+        return self._compress_to_total("rspt_hip_compress_total_batch_dev", self.total_work_bytes, d_src, self._nblocks(d_src), total_bytes, ladder,
+                                       work, stream, d_dst, dst_stride, tables)
+
+    def total_planar_work_bytes(self, nblocks, nladder):
+        """bytes of compress_to_total_planar's work area, for the route a call would take now (debug_set_total_route): fused those
+        of total_work_bytes; general those less one planar copy of the batch at bps 4, and the same at bps < 4"""
+        return self._bytes("rspt_hip_compress_total_planar_work_bytes", int(nblocks), int(nladder))
+
+    def compress_to_total_planar(self, d_planar, total_bytes, ladder, work=None, stream=None, d_dst=None, dst_stride=None, tables=False):
+        """compress_to_total for samples that already live in int32 (rspt_hip.h: rspt_hip_compress_total_planar_batch_dev): d_planar
+        is a contiguous torch.int32 cuda tensor [nblocks, nch, ns], only read; everything returned is what
+        compress_to_total(from_planar_i32(d_planar), ...) returns -- on a handle of bps < 4 only the low bps bytes of a value count.
+        work: at least total_planar_work_bytes(nblocks, len(ladder)) bytes, 16-byte aligned; None: allocated here."""
         import torch
 
-        nblocks = self._nblocks(d_src)
+        nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
+        return self._compress_to_total("rspt_hip_compress_total_planar_batch_dev", self.total_planar_work_bytes, d_planar, nblocks, total_bytes,
+                                       ladder, work, stream, d_dst, dst_stride, tables)
+
+    def _compress_to_total(self, entry, work_bytes, d_src, nblocks, total_bytes, ladder, work, stream, d_dst, dst_stride, tables):
+        import torch
+
         lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
         dev = d_src.device
         if dst_stride is None:
@@ -550,9 +571,9 @@ class SignalPacker:
         total_bytes = int(total_bytes)
         assert 0 <= total_bytes < 1 << 64
         if work is None:
-            work = torch.empty((self.total_work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
+            work = torch.empty((work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
         assert work.is_cuda and work.is_contiguous()
-        self._call("rspt_hip_compress_total_batch_dev", d_src.data_ptr(), nblocks, _dptr(lad), lad.size, total_bytes, d_dst.data_ptr(), dst_stride,
+        self._call(entry, d_src.data_ptr(), nblocks, _dptr(lad), lad.size, total_bytes, d_dst.data_ptr(), dst_stride,
                    d_sizes.data_ptr(), d_choice.data_ptr(), d_level.data_ptr(), d_total.data_ptr(), d_prdn.data_ptr(),
                    None if d_cand is None else d_cand.data_ptr(), None if d_figs is None else d_figs.data_ptr(), work.data_ptr(), self._stream(stream, dev))
         return (d_dst, d_sizes, d_choice, d_level, d_total, d_prdn) + ((d_cand, d_figs) if tables else ())

@@ -1,8 +1,8 @@
-// The body of k_total_probe (total.hip), stated once so that a planar twin can include it.  From the kernel: orig, g, fwd, inv, nb,
-// nblocks, slots, acc and the constant kPlanarCut (k_target_probe_body.hpp).  Per ladder entry it is k_budget_probe_body.hpp's store
+// The body of k_total_probe and k_planar_total_probe (total.hip), included into both so that the native kernel stays the code that
+// was timed.  From the kernel: orig, g, fwd, inv, nb, nblocks, slots, acc and the constant kPlanarCut (k_target_probe_body.hpp).  Per ladder entry it is k_budget_probe_body.hpp's store
 // and k_target_probe_body.hpp's round trip on ONE fwht_quant(W, n / q_k): the coefficient goes to its slot as it is and, cut to nb
-// bytes, into the second LDS buffer.  orig may lie inside slots (k_budget_probe): the row is in o[] and in W, behind a barrier,
-// before the first store to a slot.
+// bytes, into the second LDS buffer.  The native kernel's orig may lie inside slots (k_budget_probe): the row is in o[] and in W,
+// behind a barrier, before the first store to a slot.
 #include "k_tp_transform_body.hpp"
 
     // the reference terms once: r = (int32)((o - mean) * (o - mean)), their sum and the sum of their magnitudes

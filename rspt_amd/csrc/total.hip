@@ -1,9 +1,12 @@
-// total.hip -- compress a batch to one byte total (rspt_hip_compress_total_batch_dev): the lowest common PRDN level whose picks fit.
+// total.hip -- compress a batch to one byte total (rspt_hip_compress_total_batch_dev and its planar form,
+// rspt_hip_compress_total_planar_batch_dev): the lowest common PRDN level whose picks fit.
 //
 //   k_total_probe   the fused route's front end (hadamard rows of up to kTpMaxNs points, nch * ns < 2^22): one workgroup per
 //                   (channel, block) reads the row once and does, per ladder entry, what k_budget_probe does -- the entry's
 //                   coefficients into row c of block slot k * nblocks + b -- and what k_target_probe does -- the round trip in the
 //                   second LDS buffer and the exact PRDN sums into acc (k_total_probe_body.hpp).
+//   k_planar_total_probe  the same body for rspt_hip_compress_total_planar_batch_dev: the rows come from the caller's
+//                   [nblocks][nch][ns] int32 matrix, cut to the sample width as they are loaded.
 //   k_total_figs    the figure of every (entry, block) as the bit pattern of a double: +0.0 where mse == 0, the PRDN where the entry
 //                   is rated, kTotalNaN where it is not.  A rated figure is never negative (100 * sqrt of a quotient whose numerator
 //                   is > 0: positive, +inf or a NaN), so figures and levels order as their patterns do, and kTotalNaN lies above
@@ -31,6 +34,15 @@ constexpr unsigned long long kTotalNone = ~0ull;                 // no size: an 
 __global__ __launch_bounds__(1024) void k_total_probe(const int32_t* orig, Geom g, QLadder fwd, QLadder inv, uint32_t nb, uint32_t nblocks,
                                                      int32_t* slots, unsigned long long* __restrict__ acc) {
     constexpr bool kPlanarCut = false;
+#include "k_total_probe_body.hpp"
+}
+
+// k_planar_total_probe: the probe of rspt_hip_compress_total_planar_batch_dev -- the rows are the caller's matrix (single dwords at
+// tid + j * nt: its 4-byte alignment is all they need), cut to the sample width on load.  orig is only read and lies outside
+// slots: nothing but this kernel reads the matrix, and every slot of every entry is only written.
+__global__ __launch_bounds__(1024) void k_planar_total_probe(const int32_t* __restrict__ orig, Geom g, QLadder fwd, QLadder inv, uint32_t nb,
+                                                            uint32_t nblocks, int32_t* __restrict__ slots, unsigned long long* __restrict__ acc) {
+    constexpr bool kPlanarCut = true;
 #include "k_total_probe_body.hpp"
 }
 
