@@ -393,6 +393,33 @@ class SignalPacker:
     def reserve(self, nblocks):
         self._check("rspt_hip_reserve", self._L.rspt_hip_reserve(self._h, nblocks))
 
+    def _dst(self, nblocks, d_dst, dst_stride, device):
+        """(d_dst, dst_stride) of a compress call: the caller's, or a stride that holds any stream -- max_compressed_size rounded up
+        to 256 -- and a destination of nblocks of them, allocated here"""
+        import torch
+
+        if dst_stride is None:
+            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
+        if d_dst is None:
+            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=device)
+        return d_dst, dst_stride
+
+    def _rate_buffers(self, work_bytes, d_src, nblocks, ladder, work, d_dst, dst_stride):
+        """what every rate-control call shares (compress_to_prdn, compress_to_budget, compress_to_total and their planar forms)
+        -> (the ladder as a float64 array, the device, d_dst, dst_stride, d_sizes, d_choice, work); work: the caller's, or
+        work_bytes(nblocks, nladder) bytes allocated here"""
+        import torch
+
+        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+        dev = d_src.device
+        d_dst, dst_stride = self._dst(nblocks, d_dst, dst_stride, dev)
+        d_sizes = torch.empty(nblocks, dtype=torch.int64, device=dev)
+        d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        if work is None:
+            work = torch.empty((work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
+        assert work.is_cuda and work.is_contiguous()
+        return lad, dev, d_dst, dst_stride, d_sizes, d_choice, work
+
     def _ladder_args(self, ladder, choice, nblocks):
         """(double*, count, device pointer) of a ladder call: `ladder` a sequence of 1..8 qualities, `choice` a torch.int32 cuda
         tensor [nblocks] of indices into it (rspt_hip.h: rspt_hip_compress_batch_ladder_dev)"""
@@ -411,10 +438,7 @@ class SignalPacker:
 
         assert (ladder is None) == (choice is None)
         nblocks = self._nblocks(d_src)
-        if dst_stride is None:
-            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
-        if d_dst is None:
-            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=d_src.device)
+        d_dst, dst_stride = self._dst(nblocks, d_dst, dst_stride, d_src.device)
         if d_sizes is None:
             d_sizes = torch.empty(nblocks, dtype=torch.int64, device=d_src.device)
         st = self._stream(stream, d_src.device)
@@ -493,14 +517,7 @@ class SignalPacker:
     def _compress_to_budget(self, entry, work_bytes, d_src, nblocks, budget, ladder, work, stream, d_dst, dst_stride, cand_sizes):
         import torch
 
-        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
-        dev = d_src.device
-        if dst_stride is None:
-            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
-        if d_dst is None:
-            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=dev)
-        d_sizes = torch.empty(nblocks, dtype=torch.int64, device=dev)
-        d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        lad, dev, d_dst, dst_stride, d_sizes, d_choice, work = self._rate_buffers(work_bytes, d_src, nblocks, ladder, work, d_dst, dst_stride)
         d_cand = torch.empty((lad.size, nblocks), dtype=torch.int64, device=dev) if cand_sizes else None
         if isinstance(budget, torch.Tensor):
             assert budget.is_cuda and budget.dtype == torch.int64 and budget.is_contiguous() and budget.numel() == nblocks
@@ -508,9 +525,6 @@ class SignalPacker:
         else:
             scalar, d_budget = int(budget), None
             assert 0 <= scalar < 1 << 64
-        if work is None:
-            work = torch.empty((work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
-        assert work.is_cuda and work.is_contiguous()
         self._call(entry, d_src.data_ptr(), nblocks, _dptr(lad), lad.size, scalar, d_budget, d_dst.data_ptr(), dst_stride, d_sizes.data_ptr(),
                    d_choice.data_ptr(), None if d_cand is None else d_cand.data_ptr(), work.data_ptr(), self._stream(stream, dev))
         return (d_dst, d_sizes, d_choice) + ((d_cand,) if cand_sizes else ())
@@ -555,14 +569,7 @@ class SignalPacker:
     def _compress_to_total(self, entry, work_bytes, d_src, nblocks, total_bytes, ladder, work, stream, d_dst, dst_stride, tables):
         import torch
 
-        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
-        dev = d_src.device
-        if dst_stride is None:
-            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
-        if d_dst is None:
-            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=dev)
-        d_sizes = torch.empty(nblocks, dtype=torch.int64, device=dev)
-        d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        lad, dev, d_dst, dst_stride, d_sizes, d_choice, work = self._rate_buffers(work_bytes, d_src, nblocks, ladder, work, d_dst, dst_stride)
         d_level = torch.empty(1, dtype=torch.float64, device=dev)
         d_total = torch.empty(1, dtype=torch.int64, device=dev)
         d_prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
@@ -570,9 +577,6 @@ class SignalPacker:
         d_figs = torch.empty((lad.size, nblocks), dtype=torch.float64, device=dev) if tables else None
         total_bytes = int(total_bytes)
         assert 0 <= total_bytes < 1 << 64
-        if work is None:
-            work = torch.empty((work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
-        assert work.is_cuda and work.is_contiguous()
         self._call(entry, d_src.data_ptr(), nblocks, _dptr(lad), lad.size, total_bytes, d_dst.data_ptr(), dst_stride,
                    d_sizes.data_ptr(), d_choice.data_ptr(), d_level.data_ptr(), d_total.data_ptr(), d_prdn.data_ptr(),
                    None if d_cand is None else d_cand.data_ptr(), None if d_figs is None else d_figs.data_ptr(), work.data_ptr(), self._stream(stream, dev))
@@ -596,18 +600,8 @@ class SignalPacker:
     def _compress_to_prdn(self, entry, work_bytes, d_src, nblocks, target, ladder, work, stream, d_dst, dst_stride):
         import torch
 
-        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
-        dev = d_src.device
-        if dst_stride is None:
-            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
-        if d_dst is None:
-            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=dev)
-        d_sizes = torch.empty(nblocks, dtype=torch.int64, device=dev)
-        d_choice = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        lad, dev, d_dst, dst_stride, d_sizes, d_choice, work = self._rate_buffers(work_bytes, d_src, nblocks, ladder, work, d_dst, dst_stride)
         d_prdn = torch.empty(nblocks, dtype=torch.float64, device=dev)
-        if work is None:
-            work = torch.empty((work_bytes(nblocks, lad.size) + 7) // 8, dtype=torch.float64, device=dev)
-        assert work.is_cuda and work.is_contiguous()
         self._call(entry, d_src.data_ptr(), nblocks, _dptr(lad), lad.size, float(target), d_dst.data_ptr(),
                    dst_stride, d_sizes.data_ptr(), d_choice.data_ptr(), d_prdn.data_ptr(), work.data_ptr(), self._stream(stream, dev))
         return d_dst, d_sizes, d_choice, d_prdn
@@ -634,10 +628,7 @@ class SignalPacker:
 
         assert (ladder is None) == (choice is None)
         nblocks = self._nblocks(d_planar, torch.int32, self.nch * self.ns)
-        if dst_stride is None:
-            dst_stride = (self.max_compressed_size + 255) // 256 * 256 if d_dst is None else d_dst.numel() // nblocks
-        if d_dst is None:
-            d_dst = torch.empty((nblocks, dst_stride), dtype=torch.uint8, device=d_planar.device)
+        d_dst, dst_stride = self._dst(nblocks, d_dst, dst_stride, d_planar.device)
         if d_sizes is None:
             d_sizes = torch.empty(nblocks, dtype=torch.int64, device=d_planar.device)
         st = self._stream(stream, d_planar.device)

@@ -85,16 +85,8 @@ struct Workspace {
     // the lossy packers only (a ladder needs one):
     Dev<uint32_t> idx_choice;   // [cap] the choices of a container's index (k_index_choices -> the ladder kernels of the packed decoders)
     Dev<uint64_t> pack_sizes;   // [cap] rspt_hip_pack_batch_choice_dev: the sizes k_pack_index reads (k_pack_choice_sizes)
-    Dev<uint8_t> target_tab;    // [kMaxLadder][cap] figures, sums and flags of rspt_hip_compress_target_planar_batch_dev (TargetWork)
+    Dev<uint8_t> target_tab;    // rate_work::Tables of [kMaxLadder][cap] cells: the figures of rspt_hip_compress_target_planar_batch_dev
 };
-
-// Workspace::target_tab for `blocks` blocks and a full ladder: the five tables of TargetWork (host_target.hip), each on a 256-byte
-// boundary -- two of doubles, two of uint32 and the sums of four 64-bit words, per (ladder entry, block)
-constexpr size_t target_tab_bytes(size_t blocks) {
-    const size_t cells = blocks * kMaxLadder;
-    auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    return 2 * pad(cells * sizeof(double)) + 2 * pad(cells * sizeof(uint32_t)) + pad(cells * 4 * sizeof(unsigned long long));
-}
 
 // The PRDN scratch of a call on B blocks: [B][nch] int64 channel sums | [B][4] per-block accumulators | [B] u32 flags, each part
 // right behind the one before it; the first two (clear_bytes) are zeroed by one memset in front of the call's kernels.
@@ -258,9 +250,7 @@ struct rspt_hip_packer {
     uint32_t enc_grid = 0;
     uint32_t ablate = 0;  // RSPT_ABLATE (diagnostic builds only; the product kernels ignore it): timing probes
     uint32_t psel = 0;    // RSPT_PLANESEL (diagnostic builds only): which planes the hzr kernels take; bit 8 / 9: stop behind k_hist / k_tree
-    uint32_t target_route = 0;  // rspt_hip_debug_set_target_route: 0 = the host's choice, 1 = the general route, 2 = the fused probe
-    uint32_t budget_route = 0;  // rspt_hip_debug_set_budget_route: 0 = the host's choice, 1 = the general route, 2 = the batched one
-    uint32_t total_route = 0;   // rspt_hip_debug_set_total_route: 0 = the host's choice, 1 = the general route, 2 = the fused one
+    uint32_t rate_route[3] = {0, 0, 0};  // rspt_hip_debug_set_{target,budget,total}_route (RateRule): 0 = the host's choice, 1 = the general route, 2 = the faster one
     uint32_t qp_form = 0; // RSPT_QP_FORM (diagnostic builds only): planar PRDN form; 0 = the host's choice, 1 = split, 2 = whole rows
     int verify = 0;       // decompress checks the block CRCs (rspt_hip_set_verify)
     int big_endian = 0;   // samples arrive / leave with their bytes reversed (rspt_hip_set_byte_order)

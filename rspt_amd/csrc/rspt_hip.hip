@@ -57,6 +57,7 @@
 using namespace rspt;
 
 #include "host_handle.hpp"
+#include "rate_work.hpp"
 
 namespace {
 
@@ -729,7 +730,7 @@ int rspt_hip_reserve(rspt_hip_packer* p, size_t max_blocks) {
     if (g.kind == RSPT_HIP_KIND_DCT || g.kind == RSPT_HIP_KIND_HADAMARD) {
         ok &= hipMalloc(w.idx_choice.out(), max_blocks * sizeof(uint32_t)) == hipSuccess;
         ok &= hipMalloc(w.pack_sizes.out(), max_blocks * sizeof(uint64_t)) == hipSuccess;
-        ok &= hipMalloc(w.target_tab.out(), target_tab_bytes(max_blocks)) == hipSuccess;
+        ok &= hipMalloc(w.target_tab.out(), rate_work::Tables(max_blocks * kMaxLadder).bytes) == hipSuccess;
     }
     if (!ok) return RSPT_HIP_ERR_ALLOC;
     // the clean-plane invariant starts from zeroed planes
@@ -1575,6 +1576,7 @@ int rspt_hip_stage_times(rspt_hip_packer* p, float* ms, int n) {
 }  // extern "C"
 
 #include "host_stages.hip"  // (templates: outside the block; rspt_hip.h declares every entry extern "C")
+#include "host_rate.hip"
 #include "host_target.hip"
 #include "host_budget.hip"
 #include "host_total.hip"

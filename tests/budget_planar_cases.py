@@ -25,7 +25,7 @@ OFFSETS = (0, 4)  # bytes past a 16-byte boundary
 
 
 def probe_threads(shape):
-    """the workgroup size of the batched route's probe for this shape (host_budget.hip)"""
+    """the workgroup size of the batched route's probe for this shape (host_rate.hip: probe_launch)"""
     return max(64, min(1024, shape[3] // 8))
 
 

@@ -43,7 +43,7 @@ PROBE_THREADS = {1: 64, 2: 64, 3: 64, 4: 64, 5: 64, 6: 64, 7: 64, 8: 64, 9: 64, 
 
 
 def probe_threads(ns):
-    """nt of host_target.hip / host_budget.hip: std::max(64u, std::min(1024u, g.ns / kTpPer))"""
+    """nt of host_rate.hip (probe_launch): std::max(64u, std::min(1024u, g.ns / kTpPer))"""
     return max(64, min(1024, ns // TP_PER))
 
 

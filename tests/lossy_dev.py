@@ -1,7 +1,7 @@
 """Device runs that the ladder, target, budget and row-length tests of the lossy packers share (tests/test_gpu_target.py,
-tests/test_gpu_budget.py, tests/test_gpu_hadamard_rows.py): the composed oracle -- what a user does today, one plain call per
-ladder entry -- and a target or a budget call inside a work area of exactly the bytes its sizing call names.  Nothing here knows
-what a result is compared with.
+tests/test_gpu_budget.py, tests/test_gpu_total.py, their planar siblings, tests/test_gpu_hadamard_rows.py): the composed oracle --
+what a user does today, one plain call per ladder entry -- and one call of any rate-control entry inside a work area of exactly
+the bytes its sizing call names (rate_call).  Nothing here knows what a result is compared with.
 
 torch is imported inside the functions, as in tests/devframe.py."""
 import numpy as np
@@ -47,40 +47,56 @@ def last_hip_error(pk):
     return a.lib().rspt_hip_last_hip_error(pk._h)
 
 
-def budget_call(pk, d_src, ladder, budget, tag):
-    """one rspt_hip_compress_budget_batch_dev with the table of candidate sizes -- budget: an int, or one int per block (any
-    uint64) -- and the decode of its streams with its choices.  Checked here: nothing is written behind the bytes the sizing call
-    names, the handle's quantiser is what it was, the decoder consumed the sizes, no HIP error.
-    -> (limits per block, choice, sizes, dst, out, cand) on the host"""
+RATE = {"target": "compress_to_prdn", "budget": "compress_to_budget", "total": "compress_to_total"}  # rule -> the binding's method
+RATE_TABLES = {"target": {}, "budget": dict(cand_sizes=True), "total": dict(tables=True)}
+BUDGET_FIELDS = ("limits", "choice", "sizes", "dst", "out", "cand")  # of rate_call's dict, for callers that unpack
+TARGET_FIELDS = ("choice", "prdn", "sizes", "dst")
+
+
+def budget_arg(budget):
+    """the binding's argument: an int stays one, one int per block (any uint64) becomes the int64 tensor that is read as unsigned"""
     import torch
 
-    B, K = d_src.shape[0], len(ladder)
-    limits = [int(budget)] * B if isinstance(budget, int) else [int(v) for v in budget]
-    arg = budget if isinstance(budget, int) else torch.from_numpy(np.array([v - (1 << 64) if v >= BIT63 else v for v in limits], dtype=np.int64)).cuda()
+    if isinstance(budget, int):
+        return budget
+    return torch.from_numpy(np.array([int(v) - (1 << 64) if int(v) >= BIT63 else int(v) for v in budget], dtype=np.int64)).cuda()
+
+
+def rate_call(pk, rule, src, arg, ladder, tag, planar=False, **kw):
+    """One call of a rate-control entry -- rule "target" (arg: the PRDN target), "budget" (arg: an int, or one int per block, any
+    uint64) or "total" (arg: the total) -- with every table it can return, on native blocks or, planar, on the int32 matrix, inside
+    a work area of exactly the bytes its sizing call names; then, where no stream is flagged, the decode of its streams with its
+    choices.  Checked here: nothing is written behind the named bytes, the budget entry's are the table alone from either source,
+    the handle's quantiser is what it was, the decoder consumed the sizes, no HIP error.
+    -> dict on the host: choice, sizes, dst, out (the decoded native batch, None where a stream is flagged) and, by rule,
+    prdn | limits, cand | level (its bit pattern), total, prdn, cand, figs; "dev": the device tensors as the binding returns them"""
+    import torch
+
+    B, K = src.shape[0], len(ladder)
+    form = "_planar" if planar else ""
     own = pk.quantizer()
-    work = guarded_work(pk.budget_work_bytes(B, K))
-    d_dst, d_sizes, d_choice, d_cand = pk.compress_to_budget(d_src, arg, ladder, work=work[:-2], cand_sizes=True)
-    d_out, d_used = pk.decompress_batch(d_dst, B, d_dst.shape[1], ladder=ladder, choice=d_choice)
+    nwork = getattr(pk, "%s%s_work_bytes" % (rule, form))(B, K)
+    if rule == "budget":
+        assert nwork == pk.budget_work_bytes(B, K) and K * B * 8 <= nwork < K * B * 8 + 256, tag
+    work = guarded_work(nwork)
+    res = getattr(pk, RATE[rule] + form)(src, budget_arg(arg) if rule == "budget" else arg, ladder, work=work[:-2], **RATE_TABLES[rule], **kw)
+    d_dst, d_sizes, d_choice = res[:3]
     torch.cuda.synchronize()
-    assert work_guard_untouched(work), (tag, "written behind the bytes the sizing call names")
-    assert pk.quantizer() == own, tag
     sizes = d_sizes.cpu().numpy()
-    assert np.array_equal(d_used.cpu().numpy(), sizes), tag
-    assert last_hip_error(pk) == 0, tag
-    return limits, d_choice.cpu().numpy(), sizes, d_dst.cpu().numpy(), d_out.cpu().numpy(), d_cand.cpu().numpy()
-
-
-def target_call(pk, d_src, target, ladder, tag, planar=False):
-    """one rspt_hip_compress_target_batch_dev -- planar: rspt_hip_compress_target_planar_batch_dev, d_src the int32 matrix -- with
-    the same checks -> (choice, prdn, sizes, dst) on the host"""
-    import torch
-
-    B, K = d_src.shape[0], len(ladder)
-    own = pk.quantizer()
-    work = guarded_work((pk.target_planar_work_bytes if planar else pk.target_work_bytes)(B, K))
-    d_dst, d_sizes, d_choice, d_prdn = (pk.compress_to_prdn_planar if planar else pk.compress_to_prdn)(d_src, target, ladder, work=work[:-2])
-    torch.cuda.synchronize()
+    d_out = None
+    if not (sizes.view(np.uint64) >> np.uint64(63)).any():
+        d_out, d_used = pk.decompress_batch(d_dst, B, d_dst.shape[1], ladder=ladder, choice=d_choice)
+        torch.cuda.synchronize()
+        assert np.array_equal(d_used.cpu().numpy(), sizes), tag
     assert work_guard_untouched(work), (tag, "written behind the bytes the sizing call names")
     assert pk.quantizer() == own, tag
     assert last_hip_error(pk) == 0, tag
-    return d_choice.cpu().numpy(), d_prdn.cpu().numpy(), d_sizes.cpu().numpy(), d_dst.cpu().numpy()
+    r = dict(dev=res, choice=d_choice.cpu().numpy(), sizes=sizes, dst=d_dst.cpu().numpy(), out=None if d_out is None else d_out.cpu().numpy())
+    if rule == "target":
+        r.update(prdn=res[3].cpu().numpy())
+    elif rule == "budget":
+        r.update(limits=[int(arg)] * B if isinstance(arg, int) else [int(v) for v in arg], cand=res[3].cpu().numpy())
+    else:
+        r.update(level=int(res[3].cpu().numpy().view(np.uint64)[0]), total=int(res[4].cpu().numpy().view(np.uint64)[0]), prdn=res[5].cpu().numpy(),
+                 cand=res[6].cpu().numpy(), figs=res[7].cpu().numpy())
+    return r

@@ -48,8 +48,8 @@ def _held_to_the_oracle(pk, d_src, ladder, oracle, budget, tag):
     """one budget call -- budget: an int, or one int per block -- checked in full; -> the choices"""
     B = d_src.shape[0]
     table = _table(oracle)
-    # (the work area's guard, the handle's quantiser, the decoder's consumed bytes and the handle's HIP error: lossy_dev.budget_call)
-    limits, choice, sizes, dst, out, cand = ld.budget_call(pk, d_src, ladder, budget, tag)
+    # (the work area's guard, the handle's quantiser, the decoder's consumed bytes and the handle's HIP error: lossy_dev.rate_call)
+    limits, choice, sizes, dst, out, cand = map(ld.rate_call(pk, "budget", d_src, budget, ladder, tag).get, ld.BUDGET_FIELDS)
     assert np.array_equal(cand, table), (tag, "the table of candidate sizes")
     for b in range(B):
         k = bc.choose(table[:, b], limits[b])

@@ -36,40 +36,12 @@ def _new(api, shape):
     return pk
 
 
-def _budget_arg(budget):
-    """the binding's argument: an int stays one, one int per block (any uint64) becomes the int64 tensor that is read as unsigned"""
-    import torch
-
-    if isinstance(budget, int):
-        return budget
-    return torch.from_numpy(np.array([v - (1 << 64) if v >= BIT63 else v for v in budget], dtype=np.int64)).cuda()
-
-
 def _native(pk, d_native, ladder, budget, shape, tag):
     """oracle (a): the native entry on the native blocks -> dict(choice, sizes, dst, cand, decoded) on the host, decoded as the
     planar matrix of the native decode.  A U64_MAX budget gives the table alone."""
-    limits, choice, sizes, dst, out, cand = ld.budget_call(pk, d_native, ladder, budget, (tag, "native oracle"))
+    limits, choice, sizes, dst, out, cand = map(ld.rate_call(pk, "budget", d_native, budget, ladder, (tag, "native oracle")).get, ld.BUDGET_FIELDS)
     assert not (sizes.view(np.uint64) & np.uint64(BIT63)).any(), tag
     return dict(choice=choice, sizes=sizes, dst=dst, cand=cand, decoded=bp.to_matrix(out, shape), limits=limits)
-
-
-def _planar_call(pk, src, ladder, budget, tag, **kw):
-    """one rspt_hip_compress_budget_planar_batch_dev inside a work area of exactly the bytes its sizing call names.  Checked here:
-    nothing is written behind those bytes, they are the native entry's, the quantiser is what it was, no HIP error.
-    -> (d_dst, d_sizes, d_choice, d_cand) on the device"""
-    import torch
-
-    B, K = src.shape[0], len(ladder)
-    own = pk.quantizer()
-    nwork = pk.budget_planar_work_bytes(B, K)
-    assert nwork == pk.budget_work_bytes(B, K) and K * B * 8 <= nwork < K * B * 8 + 256, tag
-    work = ld.guarded_work(nwork)
-    res = pk.compress_to_budget_planar(src, _budget_arg(budget), ladder, work=work[:-2], cand_sizes=True, **kw)
-    torch.cuda.synchronize()
-    assert ld.work_guard_untouched(work), (tag, "written behind the bytes the sizing call names")
-    assert pk.quantizer() == own, tag
-    assert ld.last_hip_error(pk) == 0, tag
-    return res
 
 
 def _equals(res, o, tag):
@@ -88,7 +60,7 @@ def _held(pk, P, off, ladder, budget, o, tag):
     """P from a base `off` bytes past a 16-byte boundary through one planar call, held to oracle (a); the matrix and its guards
     are untouched afterwards -> the call's device tensors"""
     sraw, src = df.guarded_matrix(P, off)
-    res = _planar_call(pk, src, ladder, budget, tag)
+    res = ld.rate_call(pk, "budget", src, budget, ladder, tag, planar=True)["dev"]
     _equals(res, o, tag)
     assert np.array_equal(src.cpu().numpy(), P) and df.guards_untouched(sraw, off, P.size * 4), (tag, "d_planar is only read")
     return res
@@ -299,7 +271,7 @@ def test_the_handle_behind_budget_calls(api, route):
                 assert np.array_equal(sizes, sizes0)
                 for b in range(9):
                     assert np.array_equal(dst[b, : int(sizes[b])], dst0[b, : int(sizes[b])]), (tag, b)
-        limits, choice, sizes, dst, out, cand = ld.budget_call(pk, d_native[lo:hi], ladder, o["limits"], tag + ("native",))
+        limits, choice, sizes, dst, out, cand = map(ld.rate_call(pk, "budget", d_native[lo:hi], o["limits"], ladder, tag + ("native",)).get, ld.BUDGET_FIELDS)
         assert np.array_equal(choice, o["choice"]) and np.array_equal(sizes, o["sizes"]) and np.array_equal(cand, o["cand"]), tag
         for b in range(hi - lo):
             assert np.array_equal(dst[b, : int(sizes[b])], o["dst"][b, : int(sizes[b])]), (tag, b)
@@ -327,7 +299,7 @@ def test_a_chosen_stream_that_does_not_fit_the_stride_is_flagged_as_the_planar_l
     pk.debug_set_budget_route(route)
     sraw, src = df.guarded_matrix(dirty, 4)
     d_dst = torch.full((5, stride), 0xC3, dtype=torch.uint8, device="cuda")
-    d_dst, d_sizes, d_choice, d_cand = _planar_call(pk, src, ladder, budgets, ROUTE_NAMES[route], d_dst=d_dst)
+    d_dst, d_sizes, d_choice, d_cand = ld.rate_call(pk, "budget", src, budgets, ladder, ROUTE_NAMES[route], planar=True, d_dst=d_dst)["dev"]
     l_dst = torch.full((5, stride), 0xC3, dtype=torch.uint8, device="cuda")
     l_dst, l_sizes = pk.compress_planar_batch(src, d_dst=l_dst, ladder=ladder, choice=d_choice)
     torch.cuda.synchronize()

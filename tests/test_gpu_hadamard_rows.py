@@ -156,7 +156,7 @@ def test_a_prdn_target_on_the_figures_themselves(rec, orc, runs, k, route):
         for planar, src in ((False, d_src), (True, d_planar)):
             for t in targets:
                 tag = (k, route, "planar" if planar else "native", float(t).hex())
-                choice, prdn, sizes, dst = ld.target_call(pk, src, t, hr.LADDER, tag, planar=planar)
+                choice, prdn, sizes, dst = map(ld.rate_call(pk, "target", src, t, hr.LADDER, tag, planar=planar).get, ld.TARGET_FIELDS)
                 for b in range(hr.NBLOCKS):
                     col = [row[b] for row in figs]
                     e, want = tc.choose(col, t)
@@ -184,7 +184,7 @@ def test_a_byte_budget_on_the_reference_s_sizes(rec, orc, runs, k, route):
     try:
         for budget, name in ((bc.derive_budgets(table), "per block"), (bc.scalar_budget(table), "one limit")):
             tag = (k, route, name)
-            limits, choice, sizes, dst, out, cand = ld.budget_call(pk, d8, hr.LADDER, budget, tag)
+            limits, choice, sizes, dst, out, cand = map(ld.rate_call(pk, "budget", d8, budget, hr.LADDER, tag).get, ld.BUDGET_FIELDS)
             assert np.array_equal(cand, table), (tag, "the table of candidate sizes", cand.tolist(), table.tolist())
             for i in range(2 * hr.NBLOCKS):
                 b = i % hr.NBLOCKS

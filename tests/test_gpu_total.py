@@ -210,7 +210,7 @@ def test_ladders_that_are_unsorted_or_repeat_and_duplicated_blocks(api, route):
             if ladder is bc.HADAMARD_LADDER and 0 < level < tt.INF:
                 # the identity of the header: sizes ascend and figures descend strictly, so the choice is the target entry's at T*
                 assert np.all(np.diff(sizes, axis=0) > 0) and np.all(np.diff(prdn, axis=0) < 0)
-                t_choice, t_prdn, _, _ = ld.target_call(pk, d_src, level, ladder, (ladder, total, "target"))
+                t_choice = ld.rate_call(pk, "target", d_src, level, ladder, (ladder, total, "target"))["choice"]
                 for b in range(6):
                     if any(tc.meets(prdn[k, b], mse[k, b], path[k, b], level) for k in range(4)):
                         assert int(t_choice[b]) == int(choice[b]), (total, b)
@@ -305,7 +305,7 @@ def test_a_chosen_stream_that_does_not_fit_the_stride_is_flagged_as_the_ladder_c
     stride = (chosen[2] + 15) // 16 * 16  # holds some of the chosen streams and not others: the stride plays no part in the rule
     assert chosen[0] <= stride < chosen[-1]
     d_dst = torch.full((NBLOCKS, stride), 0xC3, dtype=torch.uint8, device="cuda")
-    got = td.total_call(pk, d_src, ladder, total, "stride", d_dst=d_dst)
+    got = ld.rate_call(pk, "total", d_src, total, ladder, "stride", d_dst=d_dst)
     l_dst = torch.full((NBLOCKS, stride), 0xC3, dtype=torch.uint8, device="cuda")
     l_dst, l_sizes = pk.compress_batch(d_src, d_dst=l_dst, ladder=ladder, choice=torch.from_numpy(got["choice"]).cuda())
     torch.cuda.synchronize()

@@ -60,7 +60,7 @@ class Ref:
 
     def native(self, total):
         if total not in self._a:
-            o = td.total_call(self.pk, self.d_native, self.ladder, total, (self.shape, total, "native oracle"))
+            o = ld.rate_call(self.pk, "total", self.d_native, total, self.ladder, (self.shape, total, "native oracle"))
             o["decoded"] = None
             self._a[total] = o
         return self._a[total]
@@ -79,29 +79,6 @@ class Ref:
 
     def close(self):
         self.pk.close()
-
-
-def _planar_call(pk, src, ladder, total, tag, **kw):
-    """one rspt_hip_compress_total_planar_batch_dev with both tables inside a work area of exactly the bytes its sizing call names.
-    Checked here: nothing is written behind those bytes, the quantiser is what it was, no HIP error.
-    -> (d_dst, d_sizes, d_choice, d_level, d_total, d_prdn, d_cand, d_figs) on the device"""
-    import torch
-
-    B, K = src.shape[0], len(ladder)
-    own = pk.quantizer()
-    work = ld.guarded_work(pk.total_planar_work_bytes(B, K))
-    res = pk.compress_to_total_planar(src, total, ladder, work=work[:-2], tables=True, **kw)
-    torch.cuda.synchronize()
-    assert ld.work_guard_untouched(work), (tag, "written behind the bytes the sizing call names")
-    assert pk.quantizer() == own, tag
-    assert ld.last_hip_error(pk) == 0, tag
-    return res
-
-
-def _host(res):
-    d_dst, d_sizes, d_choice, d_level, d_total, d_prdn, d_cand, d_figs = res
-    return dict(choice=d_choice.cpu().numpy(), level=int(d_level.cpu().numpy().view(np.uint64)[0]), total=int(d_total.cpu().numpy().view(np.uint64)[0]),
-                prdn=d_prdn.cpu().numpy(), sizes=d_sizes.cpu().numpy(), dst=d_dst.cpu().numpy(), cand=d_cand.cpu().numpy(), figs=d_figs.cpu().numpy())
 
 
 def _equals(got, ref, total, tag):
@@ -131,10 +108,10 @@ def _held(pk, P, off, ref, total, tag, ladder=None):
     """P from a base `off` bytes past a 16-byte boundary through one planar call, held to both oracles; the matrix and its guards
     are untouched afterwards -> (the call's device tensors, the rule's level)"""
     sraw, src = df.guarded_matrix(P, off)
-    res = _planar_call(pk, src, ladder or ref.ladder, total, tag)
-    level = _equals(_host(res), ref, total, tag)
+    got = ld.rate_call(pk, "total", src, total, ladder or ref.ladder, tag, planar=True)
+    level = _equals(got, ref, total, tag)
     assert np.array_equal(src.cpu().numpy(), P) and df.guards_untouched(sraw, off, P.size * 4), (tag, "d_planar is only read")
-    return res, level
+    return got["dev"], level
 
 
 @pytest.fixture(scope="module")
@@ -359,8 +336,8 @@ def test_the_handle_behind_total_planar_calls(api, route):
 
 
 def _host_native(pk, d_native, ladder, total, tag):
-    """the native entry on this handle, as _host gives a planar call"""
-    o = td.total_call(pk, d_native, ladder, total, tag)
+    """the native entry on this handle: what _equals compares of a planar call"""
+    o = ld.rate_call(pk, "total", d_native, total, ladder, tag)
     return {k: o[k] for k in ("choice", "level", "total", "prdn", "sizes", "dst", "cand", "figs")}
 
 
@@ -382,8 +359,8 @@ def test_a_chosen_stream_that_does_not_fit_the_stride_is_flagged_as_the_planar_l
     pk.debug_set_total_route(route)
     sraw, src = df.guarded_matrix(dirty, 4)
     d_dst = torch.full((5, stride), 0xC3, dtype=torch.uint8, device="cuda")
-    res = _planar_call(pk, src, ladder, total, ROUTE_NAMES[route], d_dst=d_dst)
-    got = _host(res)
+    got = ld.rate_call(pk, "total", src, total, ladder, ROUTE_NAMES[route], planar=True, d_dst=d_dst)
+    res = got["dev"]
     l_dst = torch.full((5, stride), 0xC3, dtype=torch.uint8, device="cuda")
     l_dst, l_sizes = pk.compress_planar_batch(src, d_dst=l_dst, ladder=ladder, choice=res[2])
     torch.cuda.synchronize()

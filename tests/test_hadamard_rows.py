@@ -85,17 +85,18 @@ def test_the_case_list_is_what_it_exists_for(rec):
 
 
 def test_the_probe_launch_shapes_are_stated_once():
-    """nt of host_target.hip / host_budget.hip as tests/hadamard_rows_cases.py restates it, at the k the list expects: the five
-    workgroup sizes -- 1, 2, 4, 8 and 16 waves of partial sums -- all occur, idle lanes below 512 points included"""
+    """nt of host_rate.hip (probe_launch, the one launch of every fused probe) as tests/hadamard_rows_cases.py restates it, at the k
+    the list expects: the five workgroup sizes -- 1, 2, 4, 8 and 16 waves of partial sums -- all occur, idle lanes below 512
+    points included"""
     got = {k: hr.probe_threads(1 << k) for k in hr.FUSED}
     assert got == hr.PROBE_THREADS
     assert set(got.values()) == {64, 128, 256, 512, 1024}
     assert [k for k in hr.FUSED if got[k] == 256] == [11] and [k for k in hr.FUSED if got[k] == 512] == [12]
     assert all(got[k] * hr.TP_PER >= 1 << k for k in hr.FUSED)  # a thread holds TP_PER samples at the most
     assert [k for k in hr.FUSED if got[k] * hr.TP_PER > 1 << k] == list(range(1, 9))  # lanes that hold no octet
-    for name in ("host_target.hip", "host_budget.hip"):
+    for name, count in (("host_rate.hip", 1), ("host_target.hip", 0), ("host_budget.hip", 0), ("host_total.hip", 0)):  # probe_launch alone
         text = open("%s/rspt_amd/csrc/%s" % (df.ROOT, name)).read()
-        assert "nt = std::max(64u, std::min(1024u, g.ns / kTpPer));" in text, name
+        assert text.count("nt = std::max(64u, std::min(1024u, g.ns / kTpPer));") == count and text.count("kTpPer") == count, name
     assert "constexpr uint32_t kTpPer = %d;" % hr.TP_PER in open("%s/rspt_amd/csrc/target.hip" % df.ROOT).read()
 
 

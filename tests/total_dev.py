@@ -1,36 +1,12 @@
-"""Device runs of compress-a-batch-to-one-byte-total that its tests share (tests/test_gpu_total.py): one
-rspt_hip_compress_total_batch_dev inside a work area of exactly the bytes its sizing call names, under lossy_dev's guards, and the
-comparison of everything it returns with the composed oracle's tables put through the rule of tests/total_cases.py.
+"""What the device tests of compress-a-batch-to-one-byte-total share (tests/test_gpu_total.py): the comparison of everything one
+rspt_hip_compress_total_batch_dev returns (lossy_dev.rate_call) with the composed oracle's tables put through the rule of
+tests/total_cases.py.
 
 torch is imported inside the functions, as in tests/devframe.py."""
 import numpy as np
 
 import lossy_dev as ld
 import total_cases as tt
-
-
-def total_call(pk, d_src, ladder, total, tag, d_dst=None):
-    """one rspt_hip_compress_total_batch_dev with both tables, and the decode of its streams with its choices.  Checked here, as
-    lossy_dev.budget_call checks them: nothing is written behind the bytes the sizing call names, the handle's quantiser is what
-    it was, no HIP error; and, where every stream fits its stride, that the decoder consumed the sizes.
-    -> dict(choice, level (its bit pattern), total, prdn, sizes, dst, out, cand, figs) on the host"""
-    import torch
-
-    B, K = d_src.shape[0], len(ladder)
-    own = pk.quantizer()
-    work = ld.guarded_work(pk.total_work_bytes(B, K))
-    d_dst, d_sizes, d_choice, d_level, d_total, d_prdn, d_cand, d_figs = pk.compress_to_total(d_src, total, ladder, work=work[:-2], d_dst=d_dst, tables=True)
-    d_out, d_used = pk.decompress_batch(d_dst, B, d_dst.shape[1], ladder=ladder, choice=d_choice)
-    torch.cuda.synchronize()
-    assert ld.work_guard_untouched(work), (tag, "written behind the bytes the sizing call names")
-    assert pk.quantizer() == own, tag
-    sizes = d_sizes.cpu().numpy()
-    if not (sizes.view(np.uint64) >> np.uint64(63)).any():
-        assert np.array_equal(d_used.cpu().numpy(), sizes), tag
-    assert ld.last_hip_error(pk) == 0, tag
-    return dict(choice=d_choice.cpu().numpy(), level=int(d_level.cpu().numpy().view(np.uint64)[0]), total=int(d_total.cpu().numpy().view(np.uint64)[0]),
-                prdn=d_prdn.cpu().numpy(), sizes=sizes, dst=d_dst.cpu().numpy(), out=d_out.cpu().numpy(), cand=d_cand.cpu().numpy(),
-                figs=d_figs.cpu().numpy())
 
 
 def tables_of(oracle):
@@ -69,7 +45,7 @@ def held_to_the_oracle(pk, d_src, ladder, oracle, total, tag, second="brute"):
     if second:
         want = (tt.choose_total if second == "brute" else tt.choose_total_bisect)(*as_lists(sizes, prdn, mse, path), total)
         assert tt.same_level(want[0], level) and want[1] == choice.tolist() and want[2] == cost, (tag, "the two statements of the rule")
-    got = total_call(pk, d_src, ladder, total, tag)
+    got = ld.rate_call(pk, "total", d_src, total, ladder, tag)
     fbits, is_rated = figure_bits(prdn, mse, path)
     assert np.array_equal(got["cand"], sizes), (tag, "the table of candidate sizes")
     assert np.array_equal(got["figs"].view(np.uint64), fbits), (tag, "the table of figures")
